@@ -6,6 +6,10 @@
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 2 --rehearse-shared-device      (N ranks on GPU 0 over gloo at a toy shape: exercises the self-launch and
                                                            the whole N > 1 code path on a 1-GPU box; not a measurement)
+  python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed, rank 0, as DIR/<name>.npy;
+                                                           that step starts from the seeded initial state, so the same arguments
+                                                           give the same outputs and two builds can be compared output for output:
+                                                           see dump_outputs)
 
 A "step" = forward + backward + (gradient all-reduce) + global-norm clip + Adam on one synthetic Nancy-shaped batch
 per GPU (configs[1] of BASELINE.json: B=32, r=2, Tt=200, Td=180 => 360 mel frames per utterance, scheduled-sampling
@@ -111,7 +115,7 @@ def source_hash():
     return h.hexdigest()[:12]
 
 
-def time_steps(model, steps, warmup, barrier, world):
+def time_steps(model, steps, warmup, barrier, world, before_last=None):
     from tacotron_amd import lib
     for _ in range(warmup):
         model.step()
@@ -121,7 +125,9 @@ def time_steps(model, steps, warmup, barrier, world):
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            before_last()
         model.step()
     torch.cuda.synchronize()
     barrier()
@@ -132,6 +138,37 @@ def time_steps(model, steps, warmup, barrier, world):
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
     fwd_ms, bwd_ms = lib.profile_read(0), lib.profile_read(1)
     return float(elapsed.item()) / steps, fwd_ms, bwd_ms
+
+
+def dump_outputs(model, outdir, budget_bytes=60 << 20, seed=0):
+    """What the last timed step handed its caller, as float32 DIR/<name>.npy (at most `budget_bytes` of data in all): the loss and
+    its two terms, the global gradient norm, seq2seq_output / output / alignments, the gradients and the
+    parameters after the Adam update.  Arrays are taken smallest first; one larger than its even share of what is left of the
+    budget is written as a fixed sample instead -- a 1-D array of the flattened tensor at np.sort(default_rng(seed).choice(numel,
+    share, replace=False)), which depends on the shape only -- else whole, in its own shape.
+    With --dump-outputs the last timed step starts from the seeded initial state (main), so two runs with the same arguments
+    compute it from the same inputs: the forward outputs and the loss come out bit-identical, the gradients and updated
+    parameters differ only by the rounding of the fp32-atomic weight-gradient sums (~1e-7 rel-L2; none under TACO_DETERMINISTIC=1).
+    Without that restart, clip + Adam would carry those last-bit differences through the warm-up and timed steps (S1, 25 steps:
+    ~3e-2 rel-L2 on the gradients)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {'loss': model._loss, 'global_gradient_norm': model._gnorm, 'seq2seq_output': model.seq2seq_output,
+              'output': model.output, 'alignments': model.alignments, 'grads': model.grads, 'params': model.params.flat}
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = budget_bytes // 4
+    written = {}
+    for i, (name, t) in enumerate(items):
+        a = t.detach().float().cpu().numpy()
+        share = left // (len(items) - i)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, share, replace=False))]
+        left -= a.size
+        np.save(os.path.join(outdir, name + '.npy'), a)
+        written[name] = (tuple(t.shape), a.size)
+    sys.stderr.write('bench.py: wrote %s\n' % ', '.join('%s %s%s' % (k, list(s), '' if n == int(np.prod(s)) else ' (sample of %d)' % n)
+                                                        for k, (s, n) in written.items()))
 
 
 def family_profile(model, steps=3):
@@ -304,7 +341,12 @@ def main():
     ap.add_argument('--no-inference', action='store_true', help='skip the inference timing (clean per-kernel profiles of the train step)')
     ap.add_argument('--no-extras', action='store_true', help='skip the S2 (Td=500) and VCTK (109 speakers) legs and the family profile')
     ap.add_argument('--speakers', type=int, default=1, help='>1: VCTK-shaped multi-speaker model (BASELINE configs[4])')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32, <= 64 MB; '
+                         'that step then starts from the seeded initial state, so the same arguments give the same outputs')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     toy = args.rehearse_shared_device
     args.batch = args.batch or (4 if toy else 32)
     args.text_len = args.text_len or (24 if toy else 200)
@@ -354,9 +396,24 @@ def main():
         return Tacotron(cc, batch, train=True, seed=0, reducer=reducer)
 
     model = make_model(Td, args.speakers)
-    sec_per_step, fwd_ms, bwd_ms = time_steps(model, args.steps, args.warmup, barrier, world)
+    restart = None
+    if args.dump_outputs:
+        # The default weight gradients are summed with fp32 atomics, and clip + Adam turn their last-bit differences into visibly
+        # different parameters within a few steps.  So the last timed step starts again from the seeded initial state
+        # (parameters as initialised, Adam slots zero, step counter 0): what it computes then depends on the arguments only.
+        # One 28 MB device copy and two fills, enqueued on the step's stream.
+        p0, step0 = model.params.flat.clone(), model.global_step
+
+        def restart():
+            model.params.flat.copy_(p0)
+            model.adam_m.zero_()
+            model.adam_v.zero_()
+            model.global_step = step0
+    sec_per_step, fwd_ms, bwd_ms = time_steps(model, args.steps, args.warmup, barrier, world, before_last=restart)
     loss = float(model.loss)
     model.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
     train_cluster, train_mode = lib.last_cluster(0), lib.decoder_mode()
     allreduce = None
     if reducer is not None and rank == 0:

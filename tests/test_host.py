@@ -296,6 +296,63 @@ def test_bench_self_launch_command(monkeypatch):
         assert bench.self_launch(argparse.Namespace(gpus=8, rehearse_shared_device=False)) == 2
 
 
+def test_bench_dump_outputs_fits_budget_and_is_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed step's outputs as float32 .npy, at most 64 MB in all at the S1 shape (B=32, Tt=200,
+    Td=180, r=2: 111 MB whole); arrays over their share of the budget are a fixed sample that depends on the shape only."""
+    import importlib.util
+    import types
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda: None)
+    B, Tt, Td, n = 32, 200, 180, 6926609
+    g = torch.Generator().manual_seed(0)
+    model = types.SimpleNamespace(_loss=torch.rand(3, generator=g), _gnorm=torch.rand(1, generator=g),
+                                  seq2seq_output=torch.rand(B, Td, 160, generator=g), output=torch.rand(B, Td, 2050, generator=g),
+                                  alignments=torch.rand(B, Td, Tt, generator=g), grads=torch.rand(n, generator=g),
+                                  params=types.SimpleNamespace(flat=torch.rand(n, generator=g)))
+    names = ['loss', 'global_gradient_norm', 'seq2seq_output', 'output', 'alignments', 'grads', 'params']
+    for d in ('a', 'b'):
+        bench.dump_outputs(model, str(tmp_path / d))
+    assert sorted(os.listdir(tmp_path / 'a')) == sorted(k + '.npy' for k in names)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in os.listdir(tmp_path / 'a')) <= 64e6
+    for k in names:
+        a, b = np.load(tmp_path / 'a' / (k + '.npy')), np.load(tmp_path / 'b' / (k + '.npy'))
+        assert a.dtype == np.float32 and np.array_equal(a, b), k
+    for k, t in (('loss', model._loss), ('global_gradient_norm', model._gnorm), ('seq2seq_output', model.seq2seq_output),
+                 ('alignments', model.alignments)):
+        assert np.array_equal(np.load(tmp_path / 'a' / (k + '.npy')), t.numpy()), k   # whole, in its own shape
+    out = np.load(tmp_path / 'a' / 'output.npy')
+    full = model.output.numpy().reshape(-1)
+    assert out.ndim == 1 and out.size < full.size
+    assert np.array_equal(out, full[np.sort(np.random.default_rng(0).choice(full.size, out.size, replace=False))])
+
+
+def test_bench_time_steps_runs_the_restart_hook_before_the_last_timed_step(built_lib, monkeypatch):
+    """--dump-outputs: time_steps calls its `before_last` hook once, after the warm-up and the first steps-1 timed steps, right
+    before the last one; --steps sets the number of timed steps."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda: None)
+    monkeypatch.setattr(built_lib, 'profile_enable', lambda bits: None)
+    monkeypatch.setattr(built_lib, 'profile_read', lambda which, with_flops=False: [])
+    monkeypatch.setattr(torch, 'tensor', lambda x, dtype=None, device=None: torch.as_tensor(x, dtype=dtype))   # (no device here)
+    log = []
+
+    class Model:
+        def step(self):
+            log.append('step')
+    bench.time_steps(Model(), 4, 2, lambda: None, 1, before_last=lambda: log.append('restart'))
+    assert log == ['step'] * 5 + ['restart', 'step']
+    log.clear()
+    bench.time_steps(Model(), 3, 0, lambda: None, 1)
+    assert log == ['step'] * 3
+
+
 def test_device_feeder_keeps_raising_after_its_worker_died():
     """once the DeviceFeeder worker has died with an exception, EVERY later next() re-raises it (the first form raised once
     and then blocked forever on the empty queue); close() still returns."""
