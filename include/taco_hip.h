@@ -23,7 +23,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default)
 
-#define TACO_VERSION 118
+#define TACO_VERSION 119
 
 #define TACO_OK 0
 #define TACO_EINVAL (-1)   /* bad argument / unsupported shape   */
@@ -231,6 +231,26 @@ int taco_denorm_unframe(const float* output, const float* stft_mean, const float
  *   workspace: taco_griffinlim_workspace_bytes(B, F) bytes.  Hand-written 2048-point FFT, no vendor library. */
 int64_t taco_griffinlim_workspace_bytes(int B, int F);   /* F >= 5 frames (as taco_griffinlim), else TACO_EINVAL */
 int taco_griffinlim(const float* mag_t, const float* phase0, float* wave, void* workspace, int B, int F, int n_iter, void* stream);
+
+/* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
+/* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length
+ * 1200, hop_length 300, pre-emphasis 0.97, log(|.| + 1e-8), 80 mels): librosa.effects.trim (0.6 form: frame mean squares at
+ * 2048 / 512, top_db 60) -> dropped when longer than max_len, else zero-padded to max_len -> pre-emphasis -> librosa.stft
+ * (center=True) -> log magnitudes and log |mel_basis @ stft| (the complex STFT, as melspectrogram(S=stft) computes) -> the
+ * r-frame layout of audio.reshape_frames.
+ *   wave      (B, L) fp32 samples; row b holds wave_len[b] of them
+ *   wave_len  (B) int32 in HOST memory, 1 <= wave_len[b] <= L (checked; copied into the workspace on `stream`)
+ *   mel_basis (80, 1025) fp32 filterbank (tacotron_amd.audio.mel_basis: librosa.filters.mel(22050, 2048, 80))
+ *   mel       (B, Td, 80 r), stft (B, Td, 1025 r): fp32, or fp16 (round to nearest even of the same fp32 values) when
+ *             out_fp16 = 1; Td = (F / 4r) * 4 with F = 1 + max_len / 300.  Rows of dropped utterances are zero
+ *   bounds    (B, 2) int32: the trim [start, end) in samples of the input row
+ *   kept      (B) int32: 1 = end - start <= max_len, 0 = dropped (the reference's `return None, None`)
+ *   workspace taco_audio_features_workspace_bytes(B, L) bytes
+ * max_len: a multiple of 300 above 1024 giving at least 4r frames (the reference: 108000); r in 1..5.  Bit-reproducible (no
+ * atomics).  Bad arguments return TACO_EINVAL before anything is enqueued. */
+int64_t taco_audio_features_workspace_bytes(int B, int L);   /* B, L > 0, else TACO_EINVAL */
+int taco_audio_features(const float* wave, const int* wave_len, const float* mel_basis, void* mel, void* stft, int* bounds,
+                        int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16, void* stream);
 
 /* Bernoulli(p_keep) bytes from a counter-based hash RNG (replaces TF's dropout / Bernoulli sampler state). */
 int taco_fill_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, void* stream);

@@ -409,3 +409,9 @@ int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s);   // decoder3.hip; TACO_EN
 // Griffin-Lim (audio.py:77-97).  mag_t / phase0 (B, 1025, F); wave (B, 300 (F - 1)); work: griffinlim_workspace_floats floats
 int64_t griffinlim_workspace_floats(int B, int F);
 int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, float* work, int B, int F, int n_iter, hipStream_t s);
+
+// ---------------------------------------------------------------- features.hip
+// audio.process_audio (audio.py:38-65) for a batch: trim, drop / pad, pre-emphasis, STFT, mel, r-frame layout (taco_hip.h)
+int64_t audio_features_workspace_bytes(int B, int L);
+int launch_audio_features(const float* wave, const int* wave_len_host, const float* mel_basis, void* mel, void* stft, int* bounds,
+                          int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16, hipStream_t s);

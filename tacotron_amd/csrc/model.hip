@@ -1696,6 +1696,15 @@ extern "C" int taco_griffinlim(const float* mag_t, const float* phase0, float* w
   return launch_griffinlim(mag_t, phase0, wave, static_cast<float*>(workspace), B, F, n_iter, as_stream(stream));
 }
 
+extern "C" int64_t taco_audio_features_workspace_bytes(int B, int L) { return audio_features_workspace_bytes(B, L); }
+
+extern "C" int taco_audio_features(const float* wave, const int* wave_len, const float* mel_basis, void* mel, void* stft,
+                                   int* bounds, int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16,
+                                   void* stream) {
+  return launch_audio_features(wave, wave_len, mel_basis, mel, stft, bounds, kept, workspace, B, L, max_len, r, out_fp16,
+                               as_stream(stream));
+}
+
 extern "C" int taco_fill_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, void* stream) {
   TACO_REQUIRE(out && n > 0, "fill_bernoulli: bad arguments");
   return launch_bernoulli(out, n, p_one, seed, as_stream(stream));

@@ -1,5 +1,6 @@
-"""Host-side data helpers: synthetic Nancy-shaped batches and the reference's prompt front end
-(data_input.py:87-108).  I/O of real corpora (data_input.load_from_npy, preprocess.py) is out of scope."""
+"""Host-side data helpers: synthetic Nancy-shaped batches, the HBM-resident corpus / pinned feeder and the
+reference's prompt front end (data_input.py:87-108).  Real corpora are produced by tacotron_amd.preprocess (preprocess.py) and
+loaded by train.load_corpus (data_input.load_from_npy)."""
 from __future__ import annotations
 
 import queue

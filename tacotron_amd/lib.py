@@ -98,6 +98,8 @@ EXPORTS = {
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
+    'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_fill_bernoulli': (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     'taco_profile_enable': (C.c_int, [_I]),
     'taco_debug_last_cluster': (C.c_int, [_I]),
@@ -355,6 +357,36 @@ def griffinlim(mag_t, phase0, n_iter=50):
     _check(_lib.taco_griffinlim(ptr(mag_t), ptr(phase0), ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()),
            'taco_griffinlim')
     return wave
+
+
+def audio_features_workspace_bytes(B, L) -> int:
+    n = _lib.taco_audio_features_workspace_bytes(int(B), int(L))
+    if n < 0:
+        raise TacoError('taco_audio_features_workspace_bytes: bad shape (B=%d, L=%d)' % (B, L))
+    return n
+
+
+def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch.float16):
+    """audio.process_audio for a batch (include/taco_hip.h taco_audio_features).  wave (B, L) fp32 on the device, wave_len (B) host
+    ints, mel_basis (80, 1025) fp32 on the device -> (mel (B, Td, 80 r), stft (B, Td, 1025 r), kept (B) int32, bounds (B, 2) int32),
+    device tensors; out_dtype float16 or float32."""
+    B, L = wave.shape
+    if len(wave_len) != B:
+        raise ValueError('audio_features: %d lengths for %d waves' % (len(wave_len), B))
+    lens = (C.c_int32 * B)(*[int(x) for x in wave_len])
+    assert out_dtype in (torch.float16, torch.float32)
+    nbytes = audio_features_workspace_bytes(B, L)
+    F = 1 + int(max_len) // 300
+    Td = (F // (4 * r)) * 4 if r > 0 else 0
+    dev = wave.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    mel = torch.empty(B, max(Td, 0), 80 * max(r, 0), dtype=out_dtype, device=dev)
+    stft = torch.empty(B, max(Td, 0), 1025 * max(r, 0), dtype=out_dtype, device=dev)
+    bounds = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    _check(_lib.taco_audio_features(ptr(wave), lens, ptr(mel_basis), ptr(mel), ptr(stft), ptr(bounds), ptr(kept), ptr(work), B, L,
+                                    int(max_len), int(r), int(out_dtype == torch.float16), stream_ptr()), 'taco_audio_features')
+    return mel, stft, kept, bounds
 
 
 def fill_bernoulli(out, p_one, seed):
