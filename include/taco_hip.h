@@ -88,7 +88,9 @@ int taco_conv_gemm(const float* A, int lda, const float* W, int ldw, const float
 int taco_debug_gemm2_window(int lo, int hi);
 /* Pre-split weight images (round 6; csrc/kernels.h "weight images"): the bf16 plane image of a weight tensor W (taps, K, N; row pitch
  * ldw) that gemm2.hip's NN kernel reads instead of splitting W in registers.  The model-level entry points build the images of
- * their own weights themselves (into the workspace); this is the op-level door for parity tests and tools.
+ * their own weights themselves (into the workspace) and drop them from the table when they return; this is the op-level door
+ * for parity tests and tools.  Op-level calls see only images registered here, and those stay until the next W == NULL call or
+ * the next model-level call (which empties this thread's table on entry).
  *   W == NULL: clears this host thread's table, returns the number of launches that ran the image form since the previous such
  *   call (all threads).   img == NULL: returns the bytes image(W) needs.
  *   otherwise: registers image(W) at img (16-byte aligned, img_bytes >= that size) and enqueues its build on `stream`; the

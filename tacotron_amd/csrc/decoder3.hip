@@ -2258,68 +2258,62 @@ __global__ __launch_bounds__(NT) void decoder3_bwd_kernel(DecBwdArgs a) {
   else decoder3_bwd_body<R, RR, false>(a);
 }
 
-template <int R, int RR>
-int launch3(DecFwdArgs& a, int ncl, hipStream_t s) {
-  typedef Dims<R, RR> D;
-  void (*kern)(DecFwdArgs) = a.mel ? decoder3_fwd_kernel<R, RR, true> : decoder3_fwd_kernel<R, RR, false>;
-  const size_t smem = (size_t)D::kFloats * sizeof(float);
-  static_assert(D::kFloats * sizeof(float) <= 160 * 1024, "decoder3: LDS budget");
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+// One decoder3 instantiation (kernel, LDS bytes, name) in two steps.  prepare(): the LDS attribute and the co-residency check,
+// nothing enqueued -- TACO_ENOTFOUND when the grid cannot be resident at once (every workgroup must be: the all-gathers need all
+// 32 peers of a cluster running; the grid is always 8 clusters x 32 peers so that a cluster maps onto one XCD).  enqueue(): the
+// exchange-area memset (unless the caller zeroed it) and the launch.
+template <class Args>
+struct Launch3 {
+  void (*kern)(Args);
+  size_t smem;
+  const char* name;
+  int prepare() const {
+    if (smem > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      if (e != hipSuccess) {
+        taco_set_error("%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
+        return TACO_ELAUNCH;
+      }
+    }
+    int dev = 0, cus = 0, per_cu = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NT, smem);
+    return e != hipSuccess || (int64_t)cus * per_cu < (int64_t)8 * P3 ? TACO_ENOTFOUND : TACO_OK;
+  }
+  int enqueue(Args& a, hipStream_t s) const {
+    const hipError_t e = a.xchg_zeroed ? hipSuccess : hipMemsetAsync(a.xchg, 0, (size_t)decoder_xchg_bytes(a.B, a.Tt), s);
+    taco_tail_touch(s);
     if (e != hipSuccess) {
-      taco_set_error("decoder3_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+      taco_set_error("%s: memset: %s", name, hipGetErrorString(e));
       return TACO_ELAUNCH;
     }
+    TACO_KLAUNCH(kern, dim3(8 * P3), dim3(NT), smem, s, a);
+    TACO_LAUNCH_CHECK(name);
+    return TACO_OK;
   }
-  // every workgroup of the grid must be resident (the all-gathers need all 32 peers of a cluster running); the grid is always
-  // 8 clusters x 32 peers so that a cluster maps onto one XCD
-  int dev = 0, cus = 0, per_cu = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NT, smem);
-  if (e != hipSuccess || (int64_t)cus * per_cu < (int64_t)8 * P3) return TACO_ENOTFOUND;
-  if (!a.xchg_zeroed) e = hipMemsetAsync(a.xchg, 0, (size_t)decoder_xchg_bytes(a.B, a.Tt), s);
-  taco_tail_touch(s);
-  if (e != hipSuccess) {
-    taco_set_error("decoder3_fwd: memset: %s", hipGetErrorString(e));
-    return TACO_ELAUNCH;
-  }
-  (void)ncl;
-  TACO_KLAUNCH(kern, dim3(8 * P3), dim3(NT), smem, s, a);
-  TACO_LAUNCH_CHECK("decoder3_fwd");
-  return TACO_OK;
+};
+
+template <int R, int RR>
+Launch3<DecFwdArgs> inst3(const DecFwdArgs& a) {
+  static_assert(Dims<R, RR>::kFloats * sizeof(float) <= 160 * 1024, "decoder3: LDS budget");
+  void (*kern)(DecFwdArgs) = a.mel ? decoder3_fwd_kernel<R, RR, true> : decoder3_fwd_kernel<R, RR, false>;
+  return {kern, Dims<R, RR>::kFloats * sizeof(float), "decoder3_fwd"};
+}
+template <int R, int RR>
+Launch3<DecBwdArgs> inst3(const DecBwdArgs&) {
+  static_assert(BDims<R, RR>::kFloats * sizeof(float) <= 160 * 1024, "decoder3 backward: LDS budget");
+  return {decoder3_bwd_kernel<R, RR>, BDims<R, RR>::kFloats * sizeof(float), "decoder3_bwd"};
+}
+// the instantiation of a launch over nb <= 32 rows: R rows per cluster, whole clusters
+template <class Args>
+Launch3<Args> pick3(const Args& a, int nb) {
+  const int R = nb > 16 ? 4 : (nb > 8 ? 2 : 1);
+  if (a.r == 2) return R == 4 ? inst3<4, 2>(a) : (R == 2 ? inst3<2, 2>(a) : inst3<1, 2>(a));
+  return R == 4 ? inst3<4, 5>(a) : (R == 2 ? inst3<2, 5>(a) : inst3<1, 5>(a));
 }
 
 }  // namespace
-
-template <int R, int RR>
-int launch3b(DecBwdArgs& a, hipStream_t s) {
-  typedef BDims<R, RR> D;
-  void (*kern)(DecBwdArgs) = decoder3_bwd_kernel<R, RR>;
-  const size_t smem = (size_t)D::kFloats * sizeof(float);
-  static_assert(D::kFloats * sizeof(float) <= 160 * 1024, "decoder3 backward: LDS budget");
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) {
-      taco_set_error("decoder3_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return TACO_ELAUNCH;
-    }
-  }
-  int dev = 0, cus = 0, per_cu = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NT, smem);
-  if (e != hipSuccess || (int64_t)cus * per_cu < (int64_t)8 * P3) return TACO_ENOTFOUND;
-  if (!a.xchg_zeroed) e = hipMemsetAsync(a.xchg, 0, (size_t)decoder_xchg_bytes(a.B, a.Tt), s);
-  taco_tail_touch(s);
-  if (e != hipSuccess) {
-    taco_set_error("decoder3_bwd: memset: %s", hipGetErrorString(e));
-    return TACO_ELAUNCH;
-  }
-  TACO_KLAUNCH(kern, dim3(8 * P3), dim3(NT), smem, s, a);
-  TACO_LAUNCH_CHECK("decoder3_bwd");
-  return TACO_OK;
-}
 
 // Process-wide decoder mode (include/taco_hip.h taco_decoder_mode): 0 = decoder3 with the XCD-local exchange where a cluster's
 // placement allows it, 1 = decoder3 with the placement-independent agent-scope exchange only, 2 = decoder.hip.  The host
@@ -2362,43 +2356,15 @@ extern "C" int taco_decoder_mode(int mode) {
   return prev;
 }
 
-int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s) {
-  const char* env = getenv("TACO_DEC_V3");
-  if (dec_mode() >= 2 || (env && atoi(env) == 1)) return TACO_ENOTFOUND;   // TACO_DEC_V3=1: forward only (A/B runs)
-  if (a.Tt > TTP || a.B < 1 || (a.r != 2 && a.r != 5)) return TACO_ENOTFOUND;
-  if (!a.hoisted || (a.trace && !kProbes3)) return TACO_ENOTFOUND;
-  {
-    const int R0 = a.B > 16 ? 4 : (a.B > 8 ? 2 : 1);   // rows the widest launch's clusters span (whole clusters)
-    const int rows = a.B > 32 ? 32 : (a.B + R0 - 1) / R0 * R0;
-    if ((int64_t)rows * kX3Row * 8 + 1024 > decoder_xchg_bytes(a.B, a.Tt)) return TACO_ENOTFOUND;
-  }
-  a.xcc_table_ofs = (int)(decoder_xchg_bytes(a.B, a.Tt) / 4 - 256);
-  a.fast_ok = (dec_mode() == 0 && xcd_local_exchange_allowed()) ? 1 : 0;
-  a.fakew = kProbes3 ? ((getenv("TACO_DEC_FAKEX") ? 2 : 0)) : 0;
-  a.P = P3;
-  decoder_note_cluster(1, P3);
-  // B > 32 (round 6): consecutive launches over rows [row0, row0 + 32) -- every launch is the full 8 x 32 grid, the exchange area
-  // (granule epochs, placement table) is zeroed again in front of each launch after the first
-  for (int row0 = 0; row0 < a.B; row0 += 32) {
-    const int nb = a.B - row0 < 32 ? a.B - row0 : 32;
-    const int R = nb > 16 ? 4 : (nb > 8 ? 2 : 1);
-    a.row0 = row0;
-    if (row0 > 0) a.xchg_zeroed = 0;
-    int rc;
-    if (a.r == 2) rc = R == 4 ? launch3b<4, 2>(a, s) : (R == 2 ? launch3b<2, 2>(a, s) : launch3b<1, 2>(a, s));
-    else rc = R == 4 ? launch3b<4, 5>(a, s) : (R == 2 ? launch3b<2, 5>(a, s) : launch3b<1, 5>(a, s));
-    if (rc != TACO_OK) return rc;
-  }
-  return TACO_OK;
-}
-
-// Returns TACO_ENOTFOUND (nothing enqueued) when the shape is outside this kernel's scope; the caller then takes decoder.hip.
-int launch_decoder3_fwd(DecFwdArgs a, hipStream_t s) {
+// Both directions: the shared scope checks, then plan, then enqueue.  B > 32 (round 6): consecutive launches over rows
+// [row0, row0 + 32) -- every launch is the full 8 x 32 grid, the exchange area (granule epochs, placement table) is zeroed again in
+// front of each launch after the first.  Every instantiation the chunks use (at most two) is prepared before the first launch, so
+// TACO_ENOTFOUND means that nothing was enqueued; a failure after the first launch is TACO_ELAUNCH.
+template <class Args>
+static int launch3_chunks(Args& a, int which, hipStream_t s) {
   if (dec_mode() >= 2) return TACO_ENOTFOUND;
   if (a.Tt > TTP || a.B < 1 || (a.r != 2 && a.r != 5)) return TACO_ENOTFOUND;
-  if (a.mel && !a.pre2) return TACO_ENOTFOUND;   // training needs the hoisted pre-net
   if (a.trace && !kProbes3) return TACO_ENOTFOUND;   // (the production build carries no stamps; decoder.hip's trace then)
-  if ((int64_t)a.B * a.Td * kStRec * 4 >= (int64_t)1 << 31) return TACO_ENOTFOUND;   // (stash stores carry 31-bit byte offsets)
   {
     const int R0 = a.B > 16 ? 4 : (a.B > 8 ? 2 : 1);   // rows the widest launch's clusters span (whole clusters)
     const int rows = a.B > 32 ? 32 : (a.B + R0 - 1) / R0 * R0;
@@ -2406,19 +2372,30 @@ int launch_decoder3_fwd(DecFwdArgs a, hipStream_t s) {
   }
   a.xcc_table_ofs = (int)(decoder_xchg_bytes(a.B, a.Tt) / 4 - 256);   // last 1 KB of the exchange area
   a.fast_ok = (dec_mode() == 0 && xcd_local_exchange_allowed()) ? 1 : 0;
-  a.P = P3;
   a.fakew = kProbes3 ? ((getenv("TACO_DEC_FAKEX") ? 2 : 0)) : 0;
-  decoder_note_cluster(0, P3);
-  for (int row0 = 0; row0 < a.B; row0 += 32) {   // (B > 32: see launch_decoder3_bwd)
-    const int nb = a.B - row0 < 32 ? a.B - row0 : 32;
-    const int R = nb > 16 ? 4 : (nb > 8 ? 2 : 1);
-    const int ncl = (nb + R - 1) / R;
-    a.row0 = row0;
-    if (row0 > 0) a.xchg_zeroed = 0;
-    int rc;
-    if (a.r == 2) rc = R == 4 ? launch3<4, 2>(a, ncl, s) : (R == 2 ? launch3<2, 2>(a, ncl, s) : launch3<1, 2>(a, ncl, s));
-    else rc = R == 4 ? launch3<4, 5>(a, ncl, s) : (R == 2 ? launch3<2, 5>(a, ncl, s) : launch3<1, 5>(a, ncl, s));
-    if (rc != TACO_OK) return rc;
+  a.P = P3;
+  const int n = cdiv(a.B, 32);
+  const Launch3<Args> full = pick3(a, 32), last = pick3(a, a.B - 32 * (n - 1));
+  if (n > 1 && full.kern != last.kern) TACO_TRY(full.prepare());
+  TACO_TRY(last.prepare());
+  decoder_note_cluster(which, P3);
+  for (int i = 0; i < n; ++i) {
+    a.row0 = 32 * i;
+    if (i > 0) a.xchg_zeroed = 0;
+    TACO_TRY((i + 1 < n ? full : last).enqueue(a, s));
   }
   return TACO_OK;
+}
+
+int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s) {
+  const char* env = getenv("TACO_DEC_V3");
+  if ((env && atoi(env) == 1) || !a.hoisted) return TACO_ENOTFOUND;   // TACO_DEC_V3=1: forward only (A/B runs)
+  return launch3_chunks(a, 1, s);
+}
+
+// Returns TACO_ENOTFOUND (nothing enqueued) when the shape is outside this kernel's scope; the caller then takes decoder.hip.
+int launch_decoder3_fwd(DecFwdArgs a, hipStream_t s) {
+  if (a.mel && !a.pre2) return TACO_ENOTFOUND;   // training needs the hoisted pre-net
+  if ((int64_t)a.B * a.Td * kStRec * 4 >= (int64_t)1 << 31) return TACO_ENOTFOUND;   // (stash stores carry 31-bit byte offsets)
+  return launch3_chunks(a, 0, s);
 }

@@ -740,6 +740,7 @@ int launch_conv_gemm_tapsplit(const ConvGemmProblem& p, float* slabs, int64_t sl
           TACO_LAUNCH_CHECK("conv_gemm2 k-split");
           return TACO_OK;
         }
+        taco_prof_cancel(2, pslot, stream);
         if (rc != TACO_ENOTFOUND) return rc;
       }
     }

@@ -1089,7 +1089,9 @@ extern "C" __attribute__((visibility("default"))) int taco_debug_gemm2_window(in
 
 // Op-level access to the weight images (tests, tools): W == null clears this thread's table; img == null returns the bytes
 // image(W) needs; otherwise registers image(W) at img and builds it on `stream` -- the next taco_conv_gemm calls of this thread
-// whose weights are W then run the B-image form of the kernel.
+// whose weights are W then run the B-image form of the kernel.  Op-level calls see only images registered here (a model-level
+// call's own images leave the table when it returns); they stay until taco_debug_weight_image(NULL, ...) or the next
+// model-level call, which empties the table on entry.
 extern "C" __attribute__((visibility("default"))) int64_t taco_debug_weight_image(const float* W, int ldw, int taps, int K, int N, void* img,
                                                                                   int64_t img_bytes, void* stream_) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);

@@ -7,6 +7,7 @@
 // category is not being recorded); end stamps the stop event and the launch's algorithmic FLOPs.
 int taco_prof_begin(int which, hipStream_t s);
 void taco_prof_end(int which, int slot, hipStream_t s, double flops);
+void taco_prof_cancel(int which, int slot, hipStream_t s);   // the bracketed launch was not made: drops the slot, records nothing
 void taco_prof_label(int which, int slot, const char* fmt, ...) __attribute__((format(printf, 3, 4)));   // no-op when slot < 0
 
 // ---------------------------------------------------------------- gemm.hip

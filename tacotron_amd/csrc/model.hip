@@ -95,6 +95,10 @@ void taco_prof_end(int which, int slot, hipStream_t s, double flops) {
   r.flops[slot] = flops;
   r.n = slot + 1;
 }
+void taco_prof_cancel(int which, int slot, hipStream_t s) {
+  // (the ring does not advance: the next bracket reuses the slot; an unarmed bracket's recorded start is simply overwritten)
+  if (slot >= 0 && g_prof[which].armed[slot]) (void)taco_tail_disarm_timing(s);
+}
 
 namespace {
 inline int prof_begin(int which, hipStream_t s) { return taco_prof_begin(which, s); }
@@ -152,15 +156,24 @@ BiGruWeights bigru_weights(const float* P, const CbhgP& c) {
   return w;
 }
 
-// ops.CBHG forward (ops.py:48-132).  x (B*T, cin).
-// forward_impl's hook: work to enqueue (on the side stream) at the moment the NEXT cbhg_fwd launches its bi-GRU recurrence -- a
-// 64-workgroup kernel of 150-270 us that leaves 192 CUs idle.  Round 6: everything the backward pass derives from the parameters
-// alone (transposed weights, their plane images, transposed decoder composites) runs there, beside the post-net recurrence,
-// instead of beside the encoder's conv bank and proj1, whose launches it used to slow down by ~30 us.
-thread_local std::function<int(hipStream_t)>* g_pre_bigru_hook = nullptr;
+// Installs `value` in a thread-local routing variable for one stretch of code and puts the previous value back when the stretch
+// ends, on every return path.
+template <class T>
+struct ScopedSet {
+  T& var;
+  const T prev;
+  ScopedSet(T& v, T value) : var(v), prev(v) { v = value; }
+  ScopedSet(const ScopedSet&) = delete;
+  ~ScopedSet() { var = prev; }
+};
 
+// ops.CBHG forward (ops.py:48-132).  x (B*T, cin).
+// pre_bigru: work to enqueue (on the side stream) at the moment this pass launches its bi-GRU recurrence -- a 64-workgroup kernel
+// of 150-270 us that leaves 192 CUs idle.  Round 6: everything the backward pass derives from the parameters alone (transposed
+// weights, their plane images, transposed decoder composites) runs there, beside the post-net recurrence, instead of beside the
+// encoder's conv bank and proj1, whose launches it used to slow down by ~30 us.
 int cbhg_fwd(const float* P, const CbhgP& c, const float* x, int B, int T, const CbhgBufs& w, bool keep_ruc,
-             hipStream_t s) {
+             hipStream_t s, const std::function<int(hipStream_t)>* pre_bigru = nullptr) {
   const int M = B * T, KC = c.K * kCb;
   // conv bank: K 'same' convs + ReLU, concatenated on channels (ops.py:54-62), BN-affine + max-pool(2,1,same) (ops.py:64-71):
   // one batched launch whose epilogue pools along the sequence (gemm2.hip); the un-pooled activations are kept only when a
@@ -295,11 +308,7 @@ int cbhg_fwd(const float* P, const CbhgP& c, const float* x, int B, int T, const
     }
     TACO_TRY(launch_conv_gemm_batch(batch, s));
   }
-  if (g_pre_bigru_hook) {
-    std::function<int(hipStream_t)>* h = g_pre_bigru_hook;
-    g_pre_bigru_hook = nullptr;
-    TACO_TRY((*h)(s));
-  }
+  if (pre_bigru) TACO_TRY((*pre_bigru)(s));
   TACO_TRY(launch_bigru_fwd(w.xg, bigru_weights(P, c), c.spk ? w.h0 : nullptr, w.out, keep_ruc ? w.ruc : nullptr, B, T, s));
   return TACO_OK;
 }
@@ -505,26 +514,6 @@ static int register_weight_images(const Layouts& L, const WsLayout& W, const flo
   return rc;
 }
 
-// Tail events (common.h) are tracked while one of these is alive: the C-ABI calls that fork / join streams.  Not while the
-// caller's stream is being captured into a graph (a stop event on a captured launch is not a graph dependency).
-struct TailScope {
-  bool open = false;
-  TailScope(hipStream_t s, int kind, const TacoShape& sh) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-      (void)hipGetLastError();   // (not this call's failure to report: launches are checked with hipGetLastError)
-      return;
-    }
-    if (st != hipStreamCaptureStatusNone) return;
-    uint64_t key = 1469598103934665603ull;   // (FNV-1a over the call's kind and shape)
-    const int64_t f[8] = {kind, sh.B, sh.Tt, sh.Td, sh.r, sh.V, sh.S, (int64_t)(uintptr_t)s};
-    for (int64_t v : f) key = (key ^ (uint64_t)v) * 1099511628211ull;
-    taco_tail_open(key);
-    open = true;
-  }
-  ~TailScope() { if (open) taco_tail_close(); }
-};
-
 // encoder + attention memory + decoder + post-net; shared by train and inference forward.
 int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const float* P, const int32_t* text,
                  const int32_t* text_length, const int32_t* speaker, const float* mel, const uint8_t* ek1, const uint8_t* ek2, const uint8_t* dk1,
@@ -541,7 +530,6 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
   hipStream_t sd = side_fork(s);
   // pre-split bf16 plane images of the forward weights (gemm2.hip's B-image form): first thing on the side stream, beside the
   // embedding gather and the encoder pre_net; the main stream waits for them in front of the encoder CBHG (its first gemm2 launch)
-  weight_images_clear();
   TACO_TRY(register_weight_images(L, W, P, ws, train, 0, true));
   TACO_TRY(weight_images_build(sd));
   bool img_event = false;
@@ -714,12 +702,7 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
     return TACO_OK;
   };
   const bool late_prep = train && !getenv("TACO_BWD_PREP_EARLY");
-  if (late_prep) g_pre_bigru_hook = &bwd_prep;
-  const int rc_post = cbhg_fwd(P, PL.post, s2s, B, Td * r, pb, train, s);
-  if (g_pre_bigru_hook) {   // (not reached: cbhg_fwd failed before its recurrence)
-    g_pre_bigru_hook = nullptr;
-  }
-  TACO_TRY(rc_post);
+  TACO_TRY(cbhg_fwd(P, PL.post, s2s, B, Td * r, pb, train, s, late_prep ? &bwd_prep : nullptr));
   {
     // output rows are 1025 floats apart: gemm2.hip writes them with its shifted float4 epilogue (92 vs 105 us with scalar stores)
     ConvGemmProblem p = dense_problem(pb.out, 2 * kCb, ws + W.wd_pad, 1028, P + PL.post_dense.b, output, kFft, M2, kFft,
@@ -768,9 +751,11 @@ int tn_launch_batch(GemmTnBatch& b, hipStream_t s) {
 struct TnGroup {
   GemmTnBatch batch;
   hipStream_t s;
+  GemmTnBatch* const outer = g_tnq;
   explicit TnGroup(hipStream_t stream) : s(stream) { g_tnq = &batch; }
   int flush() { return batch.n ? tn_launch_batch(batch, s) : TACO_OK; }
-  ~TnGroup() { g_tnq = nullptr; }
+  void close() { g_tnq = outer; }   // ends the group before its scope does: later weight gradients launch on their own again
+  ~TnGroup() { close(); }
 };
 
 int tn(const float* A, int lda, int K, const float* Y, int ldy, int N, float* W, int ldw, int M, int T, int pad_l,
@@ -918,7 +903,7 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
     }
   }
   TACO_TRY(gru_group.flush());
-  g_tnq = nullptr;
+  gru_group.close();
   // small-tensor helper for the speaker sites: dz (B,128) -> dW (16,128), db, dspk_e (B,16) += dz . W^T
   auto spk_dense_bwd = [&](const float* dz, const DenseP& dp, int64_t wT) -> int {
     TACO_TRY(tn(w.spk_e, 16, 16, dz, kCb, kCb, G + dp.w, kCb, B, B, 0, s, 1, G + dp.b));
@@ -1200,6 +1185,8 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
             fin.atomic_out = 1;                    // dx_out += ...: zeroed above or pre-loaded by the caller with another term
             rc = launch_conv_gemm_slab_sum(fin, w.tapsplit, g.n, s);
             taco_prof_end(2, pslot, s, 2.0 * M * c.cin * kCb * taps);
+          } else {
+            taco_prof_cancel(2, pslot, s);
           }
         }
       }
@@ -1209,6 +1196,35 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
   }
   return TACO_OK;
 }
+
+// The scope of one model-level C-ABI call (taco_forward / taco_infer / taco_backward), constructed first, after argument
+// validation.  Host state the call installs on this thread dies with it, on every return path: the weight-image table (keyed by
+// this call's parameter pointers, pointing into its workspace) is emptied on entry and on exit, and the weight-gradient routing
+// and the TN queue are left empty.  Tail events (common.h) are tracked while the scope is alive -- not while the caller's stream
+// is being captured into a graph (a stop event on a captured launch is not a graph dependency).
+struct CallScope {
+  bool tails = false;
+  CallScope(hipStream_t s, int kind, const TacoShape& sh) {
+    weight_images_clear();
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+      (void)hipGetLastError();   // (not this call's failure to report: launches are checked with hipGetLastError)
+      return;
+    }
+    if (st != hipStreamCaptureStatusNone) return;
+    uint64_t key = 1469598103934665603ull;   // (FNV-1a over the call's kind and shape)
+    const int64_t f[8] = {kind, sh.B, sh.Tt, sh.Td, sh.r, sh.V, sh.S, (int64_t)(uintptr_t)s};
+    for (int64_t v : f) key = (key ^ (uint64_t)v) * 1099511628211ull;
+    taco_tail_open(key);
+    tails = true;
+  }
+  ~CallScope() {
+    if (tails) taco_tail_close();
+    weight_images_clear();
+    g_tn_side = nullptr;
+    g_tnq = nullptr;
+  }
+};
 
 }  // namespace
 
@@ -1252,11 +1268,11 @@ extern "C" int taco_forward(const TacoShape* shape, const float* params, const i
   TACO_TRY(validate_shape(shape));
   TACO_REQUIRE(params && text && text_length && mel && stft && seq2seq_output && output && alignments && loss && workspace,
                "taco_forward: null pointer argument");
+  hipStream_t s = as_stream(stream);
+  CallScope scope(s, 0, *shape);
   const Layouts& L = layouts_for(*shape);
   const WsLayout& W = L.Wtrain;
   float* ws = static_cast<float*>(workspace);
-  hipStream_t s = as_stream(stream);
-  TailScope tails(s, 0, *shape);
   TACO_TRY(forward_impl(*shape, L, W, params, text, text_length, speaker, mel, enc_keep1, enc_keep2, dec_keep1, dec_keep2, sample,
                         seq2seq_output, output, alignments, ws, true, s));
   // add_loss_op (tacotron.py:156-165) + sign gradients for the backward pass
@@ -1273,8 +1289,8 @@ extern "C" int taco_infer(const TacoShape* shape, const float* params, const int
   TACO_TRY(validate_shape(shape));
   TACO_REQUIRE(params && text && text_length && seq2seq_output && output && alignments && workspace,
                "taco_infer: null pointer argument");
+  CallScope scope(as_stream(stream), 1, *shape);
   const Layouts& L = layouts_for(*shape);
-  TailScope tails(as_stream(stream), 1, *shape);
   return forward_impl(*shape, L, L.Winfer, params, text, text_length, speaker, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                       seq2seq_output, output, alignments, static_cast<float*>(workspace), false, as_stream(stream));
 }
@@ -1287,6 +1303,8 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   TACO_TRY(validate_shape(shape));
   TACO_REQUIRE(params && text && text_length && seq2seq_output && alignments && grads && workspace,
                "taco_backward: null pointer argument");
+  hipStream_t s = as_stream(stream);
+  CallScope scope(s, 2, *shape);
   const Layouts& L = layouts_for(*shape);
   const ParamLayout& PL = L.P;
   const TransLayout& TL = L.T;
@@ -1294,15 +1312,11 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   float* ws = static_cast<float*>(workspace);
   float* G = grads;
   const float* P = params;
-  hipStream_t s = as_stream(stream);
   const int B = shape->B, Tt = shape->Tt, Td = shape->Td, r = shape->r, R80 = kMel * r;
   const int M1 = B * Tt, MD = B * Td, M2 = MD * r, F = Td * r;
   float* PT = ws + W.paramsT;
 
-  g_tn_side = nullptr;
-  TailScope tails(s, 2, *shape);
   // the weight-image table of this call (the images themselves were built by the taco_forward that ran on this workspace)
-  weight_images_clear();
   TACO_TRY(register_weight_images(L, W, P, ws, true, 0, false));
   TACO_TRY(register_weight_images(L, W, P, ws, true, 1, false));
   // ONE batched init launch for every accumulator of the pass: the gradient buffer, [d keys | E] (one (M1, 512) buffer), the small
@@ -1351,13 +1365,13 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
     scp.alt_dpj1 = ws + W.post_dpj1; scp.alt_dz1 = ws + W.post_dz1; scp.alt_dpool = ws + W.post_dpool;
     dPostIn = ws + W.post_dx;
     scp.dx_zeroed = own_dx;
-    g_tn_side = side;
   }
   pb.tapsplit = ws + W.tapsplit;   // (free in the backward pass: the conv-bank input gradient's partial tiles)
   pb.tapsplit_floats = W.tapsplit_floats;
-  const int rc_post = cbhg_bwd(P, PT, G, PL.post, TL.post, seq2seq_output, dPostOut, B, F, pb, scp, dPostIn, -1, -1, s);
-  g_tn_side = nullptr;
-  TACO_TRY(rc_post);
+  {
+    ScopedSet route(g_tn_side, side_tn ? side : nullptr);
+    TACO_TRY(cbhg_bwd(P, PT, G, PL.post, TL.post, seq2seq_output, dPostOut, B, F, pb, scp, dPostIn, -1, -1, s));
+  }
   // d seq2seq_output = sign(s2s - mel) + post-net path
   float* dS2S = ws + W.ds2s_tot;
   if (side_tn && own_dx && !taco_deterministic()) dS2S = dPostIn;   // (accumulated on top of the L1 term, see the init launch)
@@ -1508,6 +1522,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   }
   BwdScratch sce = sc;
   float *pre_dz2 = sc.gD, *pre_dz1 = sc.gE, *pre_demb = sc.gF;
+  hipStream_t enc_tn = nullptr;
   // (the per-layer speaker form, TACO_SPK_UNFUSED=1, keeps its weight gradients on the main stream: their operands live in ping-pong buffers)
   if (side_tn && side_stream().side && (!PL.enc.spk || spk_fused_form(PL.enc))) {
     // (the side stream is still busy with the decoder weight gradients forked above; the encoder's queue up behind them)
@@ -1515,15 +1530,12 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
     dP2 = ws + W.enc_dx;
     sce.dx_zeroed = own_dx;
     pre_dz2 = ws + W.pre_dz2; pre_dz1 = ws + W.pre_dz1; pre_demb = ws + W.pre_demb;
-    g_tn_side = side_stream().side;
+    enc_tn = side_stream().side;
   }
+  ScopedSet route(g_tn_side, enc_tn);   // (to the end of the pass: the speaker scatter and the pre_net's weight gradients too)
   eb.tapsplit = ws + W.tapsplit;
   eb.tapsplit_floats = W.tapsplit_floats;
-  int rc_enc = cbhg_bwd(P, PT, G, PL.enc, TL.enc, ws + W.p2, dEnc, B, Tt, eb, sce, dP2, 2, 1, s);
-  if (rc_enc != TACO_OK) {
-    g_tn_side = nullptr;
-    return rc_enc;
-  }
+  TACO_TRY(cbhg_bwd(P, PT, G, PL.enc, TL.enc, ws + W.p2, dEnc, B, Tt, eb, sce, dP2, 2, 1, s));
   if (PL.enc.spk) {   // (fused form: d spk_e was summed on the weight-gradient stream -- the speaker table's scatter follows it there)
     hipStream_t q = s;
     if (spk_fused_form(PL.enc)) TACO_TRY(tn_route(s, &q));
@@ -1554,7 +1566,6 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
                                             TACO_ACT_NONE), s));
   }
   TACO_TRY(launch_embedding_bwd(dEmb, text, G + PL.emb, M1, shape->V, s));
-  g_tn_side = nullptr;
   TACO_TRY(side_join(s, side));
   return record_segment(0, s);
 }

@@ -164,6 +164,36 @@ def test_conv_gemm_weight_image(built_lib, case, ns, monkeypatch):
     assert torch.equal(C0, C1), 'image form differs from the in-register split: max |d| = %g' % float((C0 - C1).abs().max())
 
 
+def test_model_weight_images_do_not_outlive_the_call(built_lib, monkeypatch):
+    """The weight images a model-level call builds are keyed by its parameter pointers and live in its workspace: they must leave
+    this thread's table when the call returns.  After one train step (forward, backward, clip + Adam) an op-level conv_gemm on a
+    parameter slice that the forward pass registered an image for (the encoder bi-GRU's x-side gate kernel: taps 1, K 128) must
+    compute with the UPDATED parameters, not read the pre-Adam image."""
+    from tacotron_amd.config import Config
+    from tacotron_amd.data import synthetic_batch
+    from tacotron_amd.model import Tacotron
+    monkeypatch.setenv('TACO_GEMM2_MIN_TILES', '1')
+    monkeypatch.setenv('TACO_GEMM2_BF16X', '1')
+    c = Config()
+    c.r, c.vocab_size = 2, 20
+    batch = synthetic_batch(2, 12, 6, c.r, c.vocab_size, seed=3, min_len=6)
+    m = Tacotron(c, batch, train=True, seed=0)
+    Wfull = m.params.view('encoder/cbhg/bigru/fw/gates/kernel')   # (256, 256): rows [0, 128) are the x-side part
+    W0 = Wfull[:128].double().cpu().numpy()
+    built_lib.weight_image(None)
+    m.step(lr=1e-3)
+    torch.cuda.synchronize()
+    W1 = Wfull[:128].double().cpu().numpy()
+    assert np.abs(W1 - W0).max() > 1e-4, 'the Adam step did not move the parameters: the test would not see a stale image'
+    M, K, N = 256, 128, 256
+    A = np.random.default_rng(5).standard_normal((M, K))
+    C = torch.full((M, N), float('nan'), device='cuda')
+    built_lib.conv_gemm(dev(A), Wfull[:128], C, M, N, K)
+    torch.cuda.synchronize()
+    ref, _ = conv_ref(A, W1[None], None, M, 0, 0)
+    assert report('conv_gemm after a train step', C.cpu().numpy(), ref)[0] < 5e-6
+
+
 @pytest.mark.parametrize('scale', [1.0, 1e-12, 3e7], ids=['unit', 'tiny', 'huge'])
 def test_bf16x3_products_are_fp32_grade(built_lib, scale, monkeypatch):
     """The bf16x3 form of gemm2.hip against the fp32 MFMA form of the same kernel and an fp64 product: a deep reduction (K = 2048
