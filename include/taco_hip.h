@@ -23,7 +23,7 @@ extern "C" {
 #endif
 #pragma GCC visibility push(default)
 
-#define TACO_VERSION 119
+#define TACO_VERSION 120
 
 #define TACO_OK 0
 #define TACO_EINVAL (-1)   /* bad argument / unsupported shape   */
@@ -148,6 +148,36 @@ int taco_backward(const TacoShape* shape, const float* params, const int32_t* te
 int taco_infer(const TacoShape* shape, const float* params, const int32_t* text, const int32_t* text_length,
                const int32_t* speaker,
                float* seq2seq_output, float* output, float* alignments, void* workspace, void* stream);
+
+/* Inference end detection (no reference counterpart: the reference always decodes Td steps and Tacotron 1 has no stop token; the
+ * signal is the attention reaching the last characters and staying there).  All three parameters are integers, so that the device
+ * and a host restatement agree exactly.  For row b with text length L (clamped to 1..Tt) and alignments a[t, :] of step t:
+ *   target = max(0, L - 1 - end_offset);  a_t = first index of the maximum of a[t, 0:Tt] (lowest index on ties, as np.argmax);
+ *   run_t = (a_t >= target) ? run_{t-1} + 1 : 0, run_{-1} = 0;  t* = the first t with run_t >= hold and t + 1 >= min_steps;
+ *   len_b = min(Td, 4 ceil((t* + 1) / 4)), or Td if there is no such t.
+ * len_b is a multiple of 4 steps (or Td) because the r-frame layout (audio.reshape_frames, audio.py:22-35) interleaves blocks of
+ * 4 decoder steps: cut inside a block, the chronological frames of taco_denorm_unframe would have holes.
+ * Valid rules: end_offset >= 0, hold >= 1, min_steps >= 1 (min_steps = Td + 1 is valid and never fires).  `reserved`: 0. */
+typedef struct TacoStopRule {
+  int32_t end_offset;
+  int32_t hold;
+  int32_t min_steps;
+  int32_t reserved;
+} TacoStopRule;
+
+/* Tacotron inference as taco_infer, with the end detection above.  Same workspace (train = 0) and output shapes; rule is a HOST
+ * pointer, lengths (B) int32 a device pointer that receives len_b.
+ *   - rows t < len_b of seq2seq_output and alignments are bit-identical to what taco_infer computes from the same inputs;
+ *   - rows t >= len_b of seq2seq_output, alignments and output are exactly 0;
+ *   - output is the post-net and final dense of the zero-filled seq2seq_output over all Td steps (the post-net's convolutions and
+ *     backward GRU reach past len_b), cleared from len_b on.
+ * The default decoder (decoder3.hip) evaluates the rule inside its step loop: each cluster of rows stops after the step of its
+ * longest row.  decoder.hip (taco_decoder_mode 2, and shapes decoder3.hip does not cover) decodes all Td steps and the rule then
+ * runs over its alignments: the same results, no time saved.  A NULL rule or lengths, or a rule outside the valid range, returns
+ * TACO_EINVAL before anything is enqueued.  Graph-capturable, as taco_infer. */
+int taco_infer_stop(const TacoShape* shape, const float* params, const int32_t* text, const int32_t* text_length,
+                    const int32_t* speaker, const TacoStopRule* rule, float* seq2seq_output, float* output, float* alignments,
+                    int32_t* lengths, void* workspace, void* stream);
 
 /* add_train_op (tacotron.py:167-185): global-norm clip (cap_grads) then TF-form Adam, in place.
  *   step = global_step after this update (1-based).  scratch: >= 256 floats.  gnorm_out[0] receives ||g||. */

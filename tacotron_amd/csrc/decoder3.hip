@@ -811,8 +811,10 @@ struct Lane {
   }
 };
 
-// TR: training (teacher frames, hoisted pre-net, stash for the backward pass) vs inference
-template <int R, int RR, bool TR>
+// TR: training (teacher frames, hoisted pre-net, stash for the backward pass) vs inference.
+// STOP (inference only; taco_infer_stop): the end-detection rule of include/taco_hip.h runs on every row's alignment in the softmax
+// block, and the cluster leaves the step loop after the step max over its valid rows of len_b - 1.
+template <int R, int RR, bool TR, bool STOP>
 __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
   typedef Dims<R, RR> D;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1086,6 +1088,11 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
   g0x.zero();
   g0g.zero();
   ghp.zero();
+  // (STOP) per-row end detection.  Wave q keeps row q's run of steps whose alignment argmax reached the target (srun) and, once the
+  // rule has fired, the row's length (slen; 0 = not yet).  It publishes the row's current length bound -- slen, Td while undecided,
+  // 0 for a row past the batch -- in SST[q] (LDS behind the kernel's own layout) for the step's exit test.
+  int srun = 0, slen = 0;
+  int* const SST = reinterpret_cast<int*>(smem + D::kFloats);
   for (int t = 0; t < Td; ++t) {
     X.epoch = (unsigned)(t + 1);
     if (kProbes3) {
@@ -1545,12 +1552,37 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
         const float inv = 1.0f / z;
         const bool wr = lead && rsel<R>(valid, q);
         float* al = a.align + (unsigned)(rsel<R>(brow, q) * Td + t) * (unsigned)Tt;
+        float bv = -INFINITY;   // (STOP) this lane's first maximum over its positions s < len, ascending s
+        int bi = 0x7fffffff;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int sx = L.lane + 64 * j;
           const float v = ev[j] * inv;
           ALS[sx * R + q] = v;
           if (wr && sx < Tt) al[sx] = v;
+          if constexpr (STOP) {
+            if (sx < ln && v > bv) bv = v, bi = sx;
+          }
+        }
+        if constexpr (STOP) {
+          // The decision must be the same in all 32 workgroups of the cluster, or the ones that stay spin on the ones that left
+          // until the bounded time-out.  It is: every input is bit-identical across them.  len comes from text_length; each
+          // energy ES[q][s] is computed once by its owner slot and every workgroup reads that one published float; and the
+          // softmax above is the same instruction sequence (fixed DPP reduction order, no atomics) in every workgroup.  The
+          // probabilities v are also exactly what the lead stores to `alignments`, so the host's restatement of the rule sees them.
+          // argmax over s < len (positions past the text hold 0 and the maximum is > 0: the same as over s < Tt); lowest index on
+          // ties, as np.argmax: a butterfly over (value, index) pairs under one total order leaves the same pair in every lane
+#pragma unroll
+          for (int o = 32; o; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+          }
+          const int off = a.stop_end_offset;
+          const int target = ln - 1 - off > 0 ? ln - 1 - off : 0;
+          srun = bi >= target ? srun + 1 : 0;
+          if (slen == 0 && srun >= a.stop_hold && t + 1 >= a.stop_min_steps) slen = min(Td, (t + 4) / 4 * 4);   // 4 ceil((t* + 1) / 4)
+          if (L.lane == 0) SST[q] = rsel<R>(valid, q) ? (slen ? slen : Td) : 0;
         }
       }
     }
@@ -1561,8 +1593,23 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
       for (int o = 32; o; o >>= 1) pm = max(pm, __shfl_xor(pm, o, 64));
       if (tid == 0) { X.trace[63] = X.tslot; X.trace[62] = pm; }
     }
+    if constexpr (STOP) {
+      // every workgroup of the cluster leaves after the same step (SST is identical in all of them, see above).  Nothing is left in
+      // flight: at inference the loop defers no store (the stash / prein stores behind round E are training only), step t's output
+      // and alignment rows were stored in rounds OUT and softmax above, and every granule a slower peer may still poll for in this
+      // step was published before this point.  The next launch's exchange area is zeroed in front of it (Launch3::enqueue or the
+      // caller's batched init), so the epochs this launch left behind are never read.
+      int mx = 0;
+#pragma unroll
+      for (int q = 0; q < R; ++q) mx = max(mx, SST[q]);
+      if (t + 1 >= __builtin_amdgcn_readfirstlane(mx)) break;
+    }
+  }
+  if constexpr (STOP) {
+    if (lead && tid < R && rsel<R>(valid, tid)) a.lengths[rsel<R>(brow, tid)] = SST[tid];
   }
 }
+
 
 // ------------------------------------------------------------------------------------------------------------
 // backward
@@ -2297,7 +2344,9 @@ struct Launch3 {
 template <int R, int RR>
 Launch3<DecFwdArgs> inst3(const DecFwdArgs& a) {
   static_assert(Dims<R, RR>::kFloats * sizeof(float) <= 160 * 1024, "decoder3: LDS budget");
-  void (*kern)(DecFwdArgs) = a.mel ? decoder3_fwd_kernel<R, RR, true> : decoder3_fwd_kernel<R, RR, false>;
+  static_assert(Dims<R, RR>::kFloats * sizeof(float) + 4 * sizeof(int) <= 160 * 1024, "decoder3 (stop): LDS budget");
+  if (a.lengths) return {decoder3_fwd_kernel<R, RR, false, true>, Dims<R, RR>::kFloats * sizeof(float) + 4 * sizeof(int), "decoder3_fwd_stop"};
+  void (*kern)(DecFwdArgs) = a.mel ? decoder3_fwd_kernel<R, RR, true, false> : decoder3_fwd_kernel<R, RR, false, false>;
   return {kern, Dims<R, RR>::kFloats * sizeof(float), "decoder3_fwd"};
 }
 template <int R, int RR>
@@ -2396,6 +2445,7 @@ int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s) {
 // Returns TACO_ENOTFOUND (nothing enqueued) when the shape is outside this kernel's scope; the caller then takes decoder.hip.
 int launch_decoder3_fwd(DecFwdArgs a, hipStream_t s) {
   if (a.mel && !a.pre2) return TACO_ENOTFOUND;   // training needs the hoisted pre-net
+  if (a.mel && a.lengths) return TACO_ENOTFOUND;   // (end detection is an inference form only)
   if ((int64_t)a.B * a.Td * kStRec * 4 >= (int64_t)1 << 31) return TACO_ENOTFOUND;   // (stash stores carry 31-bit byte offsets)
   return launch3_chunks(a, 0, s);
 }

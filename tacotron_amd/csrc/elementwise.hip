@@ -587,6 +587,60 @@ __global__ void bernoulli_kernel(uint8_t* __restrict__ out, int64_t n, uint32_t 
   }
 }
 
+// taco_infer_stop: rows t >= len[b] of one or two (B, Td, C) tensors become 0.  Grid-stride over (b, t) rows, one row per workgroup
+// at a time; the rows that are kept are neither read nor written.
+__global__ __launch_bounds__(256) void zero_tail_rows_kernel(float* __restrict__ x0, int C0, float* __restrict__ x1, int C1,
+                                                             const int32_t* __restrict__ len, int B, int Td) {
+  for (int row = blockIdx.x; row < B * Td; row += gridDim.x) {
+    const int b = row / Td, t = row - b * Td;
+    if (t < len[b]) continue;
+    for (int c = threadIdx.x; c < C0; c += blockDim.x) x0[(int64_t)row * C0 + c] = 0.f;
+    if (x1)
+      for (int c = threadIdx.x; c < C1; c += blockDim.x) x1[(int64_t)row * C1 + c] = 0.f;
+  }
+}
+
+// The end-detection rule of include/taco_hip.h (TacoStopRule) over stored alignments: one workgroup per batch row walks t in
+// order.  a_t = first index of max_s alignments[b, t, s] over s < Tt (lowest index on ties: lane-local ascending scan, then a
+// wave butterfly and a fixed-order pass over the four waves, all under the one total order (value desc, index asc)).
+__global__ __launch_bounds__(256) void stop_rule_kernel(const float* __restrict__ align, const int32_t* __restrict__ text_length,
+                                                        int32_t* __restrict__ len_out, int Tt, int Td, int end_offset, int hold,
+                                                        int min_steps) {
+  __shared__ float wv[4];
+  __shared__ int wi[4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int L = text_length[b];
+  L = L < 1 ? 1 : (L > Tt ? Tt : L);
+  const int target = L - 1 - end_offset > 0 ? L - 1 - end_offset : 0;
+  int run = 0, len = Td;
+  for (int t = 0; t < Td; ++t) {
+    const float* al = align + ((int64_t)b * Td + t) * Tt;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int s = threadIdx.x; s < Tt; s += 256) {
+      const float v = al[s];
+      if (v > bv) bv = v, bi = s;
+    }
+    for (int o = 32; o; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+    }
+    if (lane == 0) wv[wave] = bv, wi[wave] = bi;
+    __syncthreads();
+    bv = wv[0], bi = wi[0];
+    for (int w = 1; w < 4; ++w)
+      if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) bv = wv[w], bi = wi[w];
+    __syncthreads();   // (wv / wi are rewritten in the next step)
+    run = bi >= target ? run + 1 : 0;
+    if (run >= hold && t + 1 >= min_steps) {   // (uniform: every thread holds the same run)
+      len = min(Td, (t + 4) / 4 * 4);
+      break;
+    }
+  }
+  if (threadIdx.x == 0) len_out[b] = len;
+}
+
 }  // namespace
 
 #define EW_LAUNCH(kernel, n_items, stream, ...)                                                        \
@@ -673,6 +727,18 @@ int launch_affine_act_bwd(const float* pre, const float* gamma, const float* dy,
 int launch_mask_rows(const float* x, const int32_t* len, float* y, int B, int T, int C, hipStream_t s) {
   TACO_REQUIRE(C % 4 == 0, "mask_rows: C %% 4 != 0");
   EW_LAUNCH(mask_rows_kernel, (int64_t)B * T * (C / 4), s, x, len, y, B, T, C);
+  return TACO_OK;
+}
+int launch_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* len, int B, int Td, hipStream_t s) {
+  const int rows = B * Td;
+  TACO_KLAUNCH(zero_tail_rows_kernel, dim3(rows < 4096 ? rows : 4096), dim3(256), 0, s, x0, C0, x1, C1, len, B, Td);
+  TACO_LAUNCH_CHECK("zero_tail_rows");
+  return TACO_OK;
+}
+int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* len, int B, int Tt, int Td, int end_offset, int hold,
+                     int min_steps, hipStream_t s) {
+  TACO_KLAUNCH(stop_rule_kernel, dim3(B), dim3(256), 0, s, align, text_length, len, Tt, Td, end_offset, hold, min_steps);
+  TACO_LAUNCH_CHECK("stop_rule");
   return TACO_OK;
 }
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s) {

@@ -192,6 +192,11 @@ int launch_affine_act_bwd(const float* pre, const float* gamma, const float* dy,
 int launch_colsum_batched(const float* x, int ld, float* out, int B, int T, int N, hipStream_t s);
 // values = enc * (t < len[b])
 int launch_mask_rows(const float* x, const int32_t* len, float* y, int B, int T, int C, hipStream_t s);
+// taco_infer_stop: rows t >= len[b] of x0 (B, Td, C0) and, when non-null, x1 (B, Td, C1) are set to 0 in place (nothing is read)
+int launch_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* len, int B, int Td, hipStream_t s);
+// taco_infer_stop's end-detection rule (include/taco_hip.h) over the alignments (B, Td, Tt) of a full decode: len (B) int32
+int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* len, int B, int Tt, int Td, int end_offset, int hold,
+                     int min_steps, hipStream_t s);
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);  // y = a + b
 // L1 losses + sign gradients.  loss_parts[0..kLossParts) = per-block partial sums of |a-b| (overwritten; summed in block
 // order by launch_finish_loss: no atomics, reproducible).  grad (ldg >= N) = sign(a-b), pad columns zeroed.
@@ -362,6 +367,11 @@ struct DecFwdArgs {
   int xcc_table_ofs = 0;     // decoder3.hip: int offset, inside the exchange area, of the 256-entry placement table
   int fast_ok = 1;           // decoder3.hip: 0 forces the placement-independent (agent-scope) publish form (TACO_DEC_V3_AGENT=1)
   int row0 = 0;              // decoder3.hip: first batch row of this launch (B > 32 runs as consecutive launches of <= 32 rows, round 6)
+  // inference end detection (taco_infer_stop; appended last so that the other members keep their kernel-argument offsets):
+  // non-null = decoder3.hip runs its stop instantiation, which writes len_b of its rows here and leaves the step loop after its
+  // longest row.  decoder.hip ignores these members (model.hip applies the rule to its alignments afterwards).
+  int32_t* lengths = nullptr;
+  int stop_end_offset = 0, stop_hold = 1, stop_min_steps = 1;
 };
 int64_t decoder_xchg_bytes(int B, int Tt);
 int decoder_last_cluster(int which);   // cluster width (workgroups per row) of the last forward (0) / backward (1) launch

@@ -4,6 +4,7 @@
 //   taco_forward  = Tacotron.inference(train=True) + add_loss_op       (tacotron.py:107-165)
 //   taco_backward = opt.compute_gradients(loss)                        (tacotron.py:172)
 //   taco_infer    = Tacotron.inference(train=False)                    (tacotron.py:107-154, ops.py:5-25)
+//   taco_infer_stop = the same with end detection on the alignments   (no reference counterpart; include/taco_hip.h)
 #include <cstdarg>
 #include <functional>
 #include <map>
@@ -515,10 +516,11 @@ static int register_weight_images(const Layouts& L, const WsLayout& W, const flo
 }
 
 // encoder + attention memory + decoder + post-net; shared by train and inference forward.
+// rule / lengths (inference only, taco_infer_stop): end detection; rows t >= lengths[b] of s2s, align and output end up 0.
 int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const float* P, const int32_t* text,
                  const int32_t* text_length, const int32_t* speaker, const float* mel, const uint8_t* ek1, const uint8_t* ek2, const uint8_t* dk1,
                  const uint8_t* dk2, const uint8_t* sample, float* s2s, float* output, float* align, float* ws, bool train,
-                 hipStream_t s) {
+                 hipStream_t s, const TacoStopRule* rule = nullptr, int32_t* lengths = nullptr) {
   const ParamLayout& PL = L.P;
   const int B = sh.B, Tt = sh.Tt, Td = sh.Td, r = sh.r, R80 = kMel * r;
   const int M1 = B * Tt, M2 = B * Td * r;
@@ -667,18 +669,31 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
   da.xchg = ws + W.xchg; da.err = reinterpret_cast<int*>(ws + W.err);
   da.trace = getenv("TACO_DEC_TRACE") ? reinterpret_cast<long long*>(ws + W.err + 16) : nullptr;
   da.B = B; da.Tt = Tt; da.Td = Td; da.r = r; da.P = 1;
+  if (lengths) {
+    da.lengths = lengths;
+    da.stop_end_offset = rule->end_offset; da.stop_hold = rule->hold; da.stop_min_steps = rule->min_steps;
+  }
   // (the error words are STICKY: only taco_clear_error() resets them, so a time-out in any step stays visible to the
   //  guarded Adam update and to the host's next check, however rarely the host looks)
   {
     const int slot = prof_begin(0, s);
     da.xchg_zeroed = 1;
+    bool full_decode = false;   // decoder.hip: all Td steps, no end detection of its own
     int rc = launch_decoder3_fwd(da, s);
     if (rc == TACO_ENOTFOUND) {
       note_decoder_fallback(B, Tt, r);
       rc = launch_decoder_fwd(da, s);
+      full_decode = true;
     }
     TACO_TRY(rc);
     prof_end(0, slot, s);
+    if (lengths) {
+      if (full_decode)
+        TACO_TRY(launch_stop_rule(align, text_length, lengths, B, Tt, Td, rule->end_offset, rule->hold, rule->min_steps, s));
+      // rows past len_b: what the decoder computed there (decoder.hip, or the other rows of a decoder3 cluster up to its longest) or
+      // never wrote -- the post-net then reads zeros
+      TACO_TRY(launch_zero_tail_rows(s2s, R80, align, Tt, lengths, B, Td, s));
+    }
   }
   hipStream_t sl = s;
   if (train) {
@@ -710,6 +725,8 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
     p.Nld = 1028;
     TACO_TRY(launch_conv_gemm(p, s));
   }
+  // (the post-net's convolutions and backward GRU reach past len_b: `output` is formed over all Td steps, then cut)
+  if (lengths) TACO_TRY(launch_zero_tail_rows(output, kFft * r, nullptr, 0, lengths, B, Td, s));
   TACO_TRY(side_join(s, sl));
   return TACO_OK;
 }
@@ -1295,6 +1312,21 @@ extern "C" int taco_infer(const TacoShape* shape, const float* params, const int
                       seq2seq_output, output, alignments, static_cast<float*>(workspace), false, as_stream(stream));
 }
 
+
+extern "C" int taco_infer_stop(const TacoShape* shape, const float* params, const int32_t* text, const int32_t* text_length,
+                               const int32_t* speaker, const TacoStopRule* rule, float* seq2seq_output, float* output, float* alignments,
+                               int32_t* lengths, void* workspace, void* stream) {
+  TACO_TRY(validate_shape(shape));
+  TACO_REQUIRE(params && text && text_length && seq2seq_output && output && alignments && workspace && rule && lengths,
+               "taco_infer_stop: null pointer argument");
+  TACO_REQUIRE(rule->end_offset >= 0 && rule->hold >= 1 && rule->min_steps >= 1,
+               "taco_infer_stop: bad stop rule (end_offset %d must be >= 0, hold %d >= 1, min_steps %d >= 1)", rule->end_offset,
+               rule->hold, rule->min_steps);
+  CallScope scope(as_stream(stream), 1, *shape);
+  const Layouts& L = layouts_for(*shape);
+  return forward_impl(*shape, L, L.Winfer, params, text, text_length, speaker, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      seq2seq_output, output, alignments, static_cast<float*>(workspace), false, as_stream(stream), rule, lengths);
+}
 
 extern "C" int taco_backward(const TacoShape* shape, const float* params, const int32_t* text, const int32_t* text_length,
                              const int32_t* speaker, const float* seq2seq_output, const float* alignments, const uint8_t* enc_keep1,

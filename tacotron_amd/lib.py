@@ -57,6 +57,18 @@ class TacoTensorInfo(C.Structure):
                 ('dims', C.c_int32 * 4)]
 
 
+class TacoStopRule(C.Structure):
+    """Inference end detection (include/taco_hip.h): the row's length is fixed once the alignment argmax has stayed at or past
+    character L - 1 - end_offset for `hold` consecutive steps and at least `min_steps` steps have run; rounded up to 4 steps."""
+    _fields_ = [('end_offset', C.c_int32), ('hold', C.c_int32), ('min_steps', C.c_int32), ('reserved', C.c_int32)]
+
+    def __init__(self, end_offset=1, hold=4, min_steps=8):
+        super().__init__(int(end_offset), int(hold), int(min_steps), 0)
+
+    def __repr__(self):
+        return 'TacoStopRule(end_offset=%d, hold=%d, min_steps=%d)' % (self.end_offset, self.hold, self.min_steps)
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         'tacotron_amd: %s not found -- build it with `python -c "import __graft_entry__ as g; g.build()"` '
@@ -86,6 +98,7 @@ EXPORTS = {
     'taco_forward': (C.c_int, [_SH] + [_P] * 17),
     'taco_backward': (C.c_int, [_SH] + [_P] * 14),
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
+    'taco_infer_stop': (C.c_int, [_SH, _P, _P, _P, _P, C.POINTER(TacoStopRule), _P, _P, _P, _P, _P, _P]),
     'taco_clip_adam_step': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P]),
     'taco_clip_adam_step_guarded': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P, _P]),
     'taco_clear_error': (C.c_int, [_SH, _I, _P, _P]),
@@ -253,6 +266,13 @@ def backward(shape, params, text, text_length, s2s, align, masks, grads, workspa
 def infer(shape, params, text, text_length, s2s, out, align, workspace, speaker=None):
     _check(_lib.taco_infer(C.byref(shape), ptr(params), ptr(text), ptr(text_length), ptr(speaker), ptr(s2s), ptr(out), ptr(align),
                            ptr(workspace), stream_ptr()), 'taco_infer')
+
+
+def infer_stop(shape, params, text, text_length, rule, s2s, out, align, lengths, workspace, speaker=None):
+    """taco_infer with end detection: `rule` a TacoStopRule, `lengths` (B) int32 on the device receives len_b; rows t >= len_b of
+    s2s / out / align are 0."""
+    _check(_lib.taco_infer_stop(C.byref(shape), ptr(params), ptr(text), ptr(text_length), ptr(speaker), C.byref(rule) if rule is not None else None,
+                                ptr(s2s), ptr(out), ptr(align), ptr(lengths), ptr(workspace), stream_ptr()), 'taco_infer_stop')
 
 
 def clip_adam_step(params, grads, m, v, lr, cap, step, scratch, gnorm_out, err_words=None):

@@ -39,6 +39,8 @@ class Tacotron(object):
         self.seq2seq_output = torch.empty(B, Td, R80, device=dev)
         self.output = torch.empty(B, Td, F2, device=dev)
         self.alignments = torch.empty(B, Td, Tt, device=dev)
+        self.lengths = None               # (B) int32 decoder steps kept per row after run(stop=...); None after run()
+        self._lengths = None
         self._loss = torch.zeros(3, device=dev)
         self.workspace = torch.empty(lib.workspace_bytes(self.shape, train) // 4, dtype=torch.float32, device=dev)
         self.masks = None
@@ -221,11 +223,21 @@ class Tacotron(object):
         return self._gnorm[0]
 
     # -- inference --------------------------------------------------------------------------------------
-    def run(self):
-        """`sess.run([model.output, model.alignments])` for train=False (test.py:52-56)."""
+    def run(self, stop=None):
+        """`sess.run([model.output, model.alignments])` for train=False (test.py:52-56).
+        stop: a lib.TacoStopRule -- end detection (taco_infer_stop): `lengths` (B, int32, device) receives each row's decoder steps
+        len_b, and rows t >= len_b of the outputs and alignments are 0.  None: the reference's fixed Td steps."""
         i = self.inputs
-        lib.infer(self.shape, self.params.flat, i['text'], i['text_length'], self.seq2seq_output, self.output,
-                  self.alignments, self.workspace, self.speaker)
+        if stop is None:
+            self.lengths = None
+            lib.infer(self.shape, self.params.flat, i['text'], i['text_length'], self.seq2seq_output, self.output,
+                      self.alignments, self.workspace, self.speaker)
+        else:
+            if self._lengths is None:
+                self._lengths = torch.empty(self.shape.B, dtype=torch.int32, device=self.device)
+            self.lengths = self._lengths
+            lib.infer_stop(self.shape, self.params.flat, i['text'], i['text_length'], stop, self.seq2seq_output, self.output,
+                           self.alignments, self.lengths, self.workspace, self.speaker)
         return self.output, self.alignments
 
     # -- checkpoint (train.py:47,85-90: weights + Adam slots + global_step) --------------------------------

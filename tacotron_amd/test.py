@@ -2,7 +2,9 @@
 to 140 chars -> always max_decode_iter steps -> normalised log-magnitude spectrogram (B, Td, 1025 r) + alignments ->
 `audio.invert_spectrogram(out * stft_std + stft_mean)` per prompt (test.py:64).  The TensorBoard summary the reference
 wraps each sample in (test.py:65-69) is out of scope; the sample itself is written as <out_dir>/prompt_NNN.wav (16 kHz, the
-reference's sr) next to the de-normalised spectrogram and the alignment as .npy."""
+reference's sr) next to the de-normalised spectrogram and the alignment as .npy.
+--stop (opt-in, not in the reference): end detection on the attention (lib.TacoStopRule, include/taco_hip.h); each prompt's
+files are cut to its len_b decoder steps and prompt_NNN_len.npy holds len_b.  The rule's defaults are not tuned on a trained model."""
 from __future__ import annotations
 
 import argparse
@@ -37,12 +39,15 @@ def write_wav(path, samples, sr=SR):
         f.writeframes((x * 32767.0).astype('<i2').tobytes())
 
 
-def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True):
+def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
     size; only a smaller final batch builds a second one.  `speaker`: id fed to a multi-speaker model for every prompt
-    (data_input.py:101-106 feeds none: the reference's test.py cannot drive its own VCTK model)."""
+    (data_input.py:101-106 feeds none: the reference's test.py cannot drive its own VCTK model).
+    `stop`: a lib.TacoStopRule, or None for the reference's fixed max_decode_iter steps.  With a rule, prompt i keeps len_b decoder
+    steps: len_b r spectrogram frames, len_b alignment rows and the 300 (len_b r - 1) samples Griffin-Lim gives for that many frames
+    (the vocoder still runs over the full, zero-filled length); len_b goes to prompt_NNN_len.npy."""
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
         with open(meta_path, 'rb') as f:
@@ -74,7 +79,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                 model.load_state_dict(ckpt)
         else:
             model.set_inputs(batch)
-        out, al = model.run()
+        out, al = model.run(stop=stop)
         model.check()
         mean = model.stft_mean if model.stft_mean is not None else torch.zeros(config.fft_size * config.r)
         std = model.stft_std if model.stft_std is not None else torch.ones(config.fft_size * config.r)
@@ -83,11 +88,20 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
         wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n).cpu().numpy() if vocode else None
         spec, al = spec.cpu().numpy(), al.cpu().numpy()
+        lengths = model.lengths.cpu().numpy() if stop is not None else None
         for i in range(Bn):
-            np.save(os.path.join(out_dir, 'prompt_%03d_spec.npy' % n), spec[i])
-            np.save(os.path.join(out_dir, 'prompt_%03d_align.npy' % n), al[i])
-            if wav is not None:
-                write_wav(os.path.join(out_dir, 'prompt_%03d.wav' % n), wav[i])
+            si, ai, wi = spec[i], al[i], (wav[i] if wav is not None else None)
+            if lengths is not None:
+                L = int(lengths[i])
+                frames = min(L * config.r, si.shape[0])
+                si, ai = si[:frames], ai[:L]
+                if wi is not None:
+                    wi = wi[:300 * (frames - 1)]   # (Griffin-Lim of F frames: 300 (F - 1) samples, hop 300)
+                np.save(os.path.join(out_dir, 'prompt_%03d_len.npy' % n), np.int32(L))
+            np.save(os.path.join(out_dir, 'prompt_%03d_spec.npy' % n), si)
+            np.save(os.path.join(out_dir, 'prompt_%03d_align.npy' % n), ai)
+            if wi is not None:
+                write_wav(os.path.join(out_dir, 'prompt_%03d.wav' % n), wi)
             n += 1
     print('wrote %d samples to %s' % (n, out_dir))
     return n
@@ -99,10 +113,15 @@ if __name__ == '__main__':
     ap.add_argument('--checkpoint', default=None)
     ap.add_argument('--speaker', type=int, default=0, help='speaker id for a multi-speaker checkpoint')
     ap.add_argument('--out-dir', default='log/test')
+    ap.add_argument('--stop', action='store_true', help='end each prompt where its attention ends (not in the reference)')
+    ap.add_argument('--end-offset', type=int, default=1, help='--stop: argmax target is character L - 1 - end_offset')
+    ap.add_argument('--hold', type=int, default=4, help='--stop: consecutive steps at or past the target')
+    ap.add_argument('--min-steps', type=int, default=8, help='--stop: steps before the rule may fire')
     a = ap.parse_args()
     prompts = [p for p in sys.stdin.readlines() if len(p) > 0]
     c = Config()
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
     print('Building Tacotron')
-    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker)
+    rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
+    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, stop=rule)
