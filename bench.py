@@ -10,22 +10,29 @@
                                                            that step starts from the seeded initial state, so the same arguments
                                                            give the same outputs and two builds can be compared output for output:
                                                            see dump_outputs)
+  python bench.py ... --full                             (also every measurement that takes runs of its own: see below)
 
 A "step" = forward + backward + (gradient all-reduce) + global-norm clip + Adam on one synthetic Nancy-shaped batch
 per GPU (configs[1] of BASELINE.json: B=32, r=2, Tt=200, Td=180 => 360 mel frames per utterance, scheduled-sampling
 0.5, dropout 0.5), including the per-step generation of the dropout / sampling masks.  Inputs are resident in HBM
 before the timed region.  value = N * 32 * 360 / (max-over-ranks time per step).  Weak scaling (32 utterances per GPU).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps, writes its outputs (--dump-outputs) and prints the line; everything on it
+comes from the timed steps themselves:
   roofline     -- for the dominant kernel (persistent decoder fwd/bwd): algorithmic fp32 FLOPs per launch / average
                   launch duration measured with HIP events on the launch stream inside the timed region, against the
                   157.3 TFLOP/s fp32 (vector == f32-MFMA) peak.  See DESIGN.md for why that kernel is latency bound.
-  rooflines    -- the same per family: dominant kernel, MFMA GEMM family (events around every launch, separate untimed
-                  pass), whole step (SURVEY 8d FLOPs / ms_per_step), bi-GRU recurrences, inference B=1.
-  s2 / vctk    -- the S2 envelope (Td=500 = 1000 mel frames) and the 109-speaker configuration, same step, 1 GPU.
+  rooflines    -- the same per family: dominant kernel, whole step (SURVEY 8d FLOPs / ms_per_step); with --full also the
+                  MFMA GEMM family (events around every launch, separate untimed pass), bi-GRU recurrences, inference B=1.
+  kernels_ms / per_rank / box.decoder_* -- decoder launch times of the timed steps, the decoder mode and cluster width they ran.
+With --full, after those steps (`--no-extras`, `--no-inference`, `--no-cpu-baseline` leave parts out):
+  s2 / vctk / b64 -- the S2 envelope (Td=500 = 1000 mel frames), the 109-speaker configuration and (off-metric) 64 utterances
+                  per GPU, same step, 1 GPU.
   box / ab     -- `box`: what this box's fabric measures (granule hop latency same-XCD / cross-XCD, L2-hit and all-miss load latency,
                   one CU's stream bandwidth, latency-bound shader clock); `ab`: same-box, same-run A/B of the big-GEMM arithmetic
                   (bf16x3 vs fp32 MFMA) and of the decoder build (product vs previous form, libtaco_prevdec.so).
+  inference    -- prompt -> mel -> linear at B=1 and B=32, 1 GPU.
+  allreduce    -- N > 1 (or TACO_FORCE_DIST=1): per-segment collective times in a separate untimed pass.
   cpu_baseline -- the CPU restatement (oracle/taco_torch.py, fp32, torch-CPU GEMMs; NOT TensorFlow -- TF 1.2 cannot
                   be installed) timed on this box's host cores on the same workload, rank 0, N=1 only.
 """
@@ -337,9 +344,13 @@ def main():
     ap.add_argument('--rehearse-shared-device', action='store_true',
                     help='run the N ranks on GPU 0 over gloo at a toy shape (RCCL refuses two ranks on one device): a rehearsal of the '
                          'self-launch and of every N > 1 branch on a 1-GPU box, NOT a measurement')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-inference', action='store_true', help='skip the inference timing (clean per-kernel profiles of the train step)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the S2 (Td=500) and VCTK (109 speakers) legs and the family profile')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also take every measurement that needs runs of its own: family profile, in-run A/Bs, '
+                         'box probes, inference, the S2 / VCTK / B=64 legs, the all-reduce pass and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-inference', action='store_true', help='with --full: skip the inference timing')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the S2 (Td=500), VCTK (109 speakers) and B=64 legs, the '
+                                                              'family profile and the in-run A/Bs')
     ap.add_argument('--speakers', type=int, default=1, help='>1: VCTK-shaped multi-speaker model (BASELINE configs[4])')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32, <= 64 MB; '
@@ -416,7 +427,7 @@ def main():
         dump_outputs(model, args.dump_outputs)
     train_cluster, train_mode = lib.last_cluster(0), lib.decoder_mode()
     allreduce = None
-    if reducer is not None and rank == 0:
+    if args.full and reducer is not None and rank == 0:
         # separate untimed pass: events around every segment's collectives on the communication stream
         reducer.timing = True
         for _ in range(3):
@@ -428,11 +439,11 @@ def main():
                      'segments': [dict(d, us=seg_us[d['segment']]) for d in reducer.describe(model)],
                      'note': 'completion order inside taco_backward; us = segment final (its event reached on the communication '
                              'stream) -> its last collective done, median of 3 untimed steps'}
-    elif reducer is not None:
+    elif args.full and reducer is not None:
         for _ in range(3):
             model.step()   # (collectives need every rank)
     fam = ab = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         fam = family_profile(model)
         ab = {'gemm': ab_gemm(model),
               'weight_images': ab_env(model, 'TACO_GEMM2_BSPLIT', '1', '0', ('image_form', 'split_in_registers'),
@@ -447,7 +458,7 @@ def main():
 
     # ---- inference (BASELINE configs[3]: prompt -> mel -> linear, Tt=140 as data_input.MAX_TEXT_LEN, always Td steps) ----
     infer = None
-    if rank == 0 and world == 1 and not args.no_inference:
+    if args.full and rank == 0 and world == 1 and not args.no_inference:
         ci = Config()
         ci.r, ci.vocab_size, ci.num_speakers = 2, 60, args.speakers
         ci.max_decode_iter = Td
@@ -478,7 +489,7 @@ def main():
 
     # ---- the other measured configurations (rank 0 of a 1-GPU run only; the driver's scaling runs skip them) ----
     s2 = vctk = b64 = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         def leg(Td_, speakers, steps=8, warmup=3, B_=None):
             m = make_model(Td_, speakers, B_)
             # best of two timed passes: about one host call in a hundred stalls for 80-90 ms (profiles/r03_inference_outlier_probe.txt),
@@ -583,6 +594,16 @@ def main():
             rooflines.append({'what': 'inference B=1 (whole forward)', 'bound': 'mfma', 'limiter': 'latency', 'achieved': infer['B1']['tflops'],
                               'peak': PEAK, 'unit': 'TFLOP/s', 'frac': infer['B1']['tflops'] / PEAK,
                               'ms': infer['B1']['ms_per_batch'], 'gflop': infer['B1']['gflop']})
+        # which box this was: the latency-bound kernels (decoder, bi-GRU: 58 % of the step) scale with the shader clock the chip
+        # sustains, and boxes of one pool differ by ~10 % (round 4: the same build ran 8.86 and 9.30 ms per step); the clock and
+        # fabric probes are runs of their own (--full)
+        box = {'shader_clock_ghz_latency_bound': lib.clock_probe()} if args.full else {}
+        box.update({'decoder_mode': train_mode,
+                    'decoder_mode_note': '0 = decoder3.hip with the XCD-local exchange (product default), 1 = decoder3.hip with the '
+                                         'agent-scope exchange, 2 = decoder.hip (include/taco_hip.h taco_decoder_mode)',
+                    'decoder_cluster_width_train': train_cluster})
+        if args.full and world == 1:
+            box.update(lib.fabric_probe())
         res = {
             'metric': 'mel-frames/sec (train step, batch=32 r=2)', 'value': frames / sec_per_step, 'unit': 'mel-frames/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': sec_per_step * 1e3,
@@ -595,7 +616,7 @@ def main():
                           'all mantissa bits set -- its worst case -- 1.4e-7 / 1.8e-7 / 3.2e-7 rel-L2 at chains of 256 / 1024 / 2048 against '
                           '2e-8 of the fp32 instruction: inside a 4e-7 bar, asserted by tests/test_gpu_ops.py::test_bf16x3_adversarial_operands '
                           '(profiles/r06_bf16x3_acc2.txt; one accumulator, as in round 5: 1.9e-6 at 2048).  The strict fp32-instruction step '
-                          'time is ab.gemm.median_ms.fp32_mfma',
+                          'time is ab.gemm.median_ms.fp32_mfma (--full)',
             'config': {'workload': 'Nancy-shaped train step (BASELINE configs[1]): B=%d/GPU, r=%d, Tt=%d chars, Td=%d steps '
                                    '(%d mel frames/utt), sched-sampling 0.5, dropout 0.5, V=60, speakers=%d, fwd+bwd+clip+Adam'
                                    % (B, c.r, Tt, Td, Td * c.r, args.speakers),
@@ -606,14 +627,7 @@ def main():
             'kernels_ms': {'decoder_fwd_kernel': fa, 'decoder_bwd_kernel': ba,
                            'us_per_decoder_step_fwd': fa * 1e3 / Td, 'us_per_decoder_step_bwd': ba * 1e3 / Td,
                            'non_decoder_critical_path_ms': sec_per_step * 1e3 - fa - ba},
-            'final_loss': loss, 'build': source_hash(),
-            # which box this was: the latency-bound kernels (decoder, bi-GRU: 58 % of the step) scale with the shader clock the chip
-            # sustains, and boxes of one pool differ by ~10 % (round 4: the same build ran 8.86 and 9.30 ms per step)
-            'box': dict({'shader_clock_ghz_latency_bound': lib.clock_probe(), 'decoder_mode': train_mode,
-                         'decoder_mode_note': '0 = decoder3.hip with the XCD-local exchange (product default), 1 = decoder3.hip with the '
-                                              'agent-scope exchange, 2 = decoder.hip (include/taco_hip.h taco_decoder_mode)',
-                         'decoder_cluster_width_train': train_cluster},
-                        **(lib.fabric_probe() if world == 1 else {})),
+            'final_loss': loss, 'build': source_hash(), 'box': box,
         }
         if per_rank:
             res['per_rank'] = per_rank
@@ -636,7 +650,7 @@ def main():
             res['b64'] = b64
         if infer:
             res['inference'] = infer
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(B, Tt, Td, c.r, c.vocab_size)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)

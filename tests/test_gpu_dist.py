@@ -136,14 +136,15 @@ def test_bench_self_launches_n_ranks_from_the_plain_command(built_lib):
     """`python bench.py --gpus 2` must start by itself: no WORLD_SIZE in the environment -> bench.py re-executes
     itself under torch.distributed.run, one process per rank.  On a 1-GPU box `--rehearse-shared-device` puts both ranks on GPU 0
     over gloo at a toy shape, so the self-launch and every N > 1 branch of the bench (process group, GradReducer on a communication
-    stream, barriers, max-over-ranks timing, per-rank decoder times, ONE JSON line from rank 0) execute here."""
+    stream, barriers, max-over-ranks timing, per-rank decoder times, ONE JSON line from rank 0) execute here; --full adds the
+    untimed all-reduce pass (`allreduce`)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--rehearse-shared-device', '--steps', '3',
-                        '--warmup', '1'], env=env, capture_output=True, text=True, timeout=800)
+                        '--warmup', '1', '--full'], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [x for x in r.stdout.splitlines() if x.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -155,3 +156,34 @@ def test_bench_self_launches_n_ranks_from_the_plain_command(built_lib):
     assert j['allreduce']['world'] == 2 and j['allreduce']['backend'] == 'gloo' and len(j['allreduce']['segments']) == 5
     assert [p['rank'] for p in j['per_rank']] == [0, 1] and all(p['us_per_decoder_step_fwd'] > 0 for p in j['per_rank'])
     assert j['value'] > 0 and np.isfinite(j['final_loss'])
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_times_the_steps_and_nothing_else(built_lib):
+    """Without --full, bench.py sets up, warms up, times the steps and prints its ONE line: the headline fields and what the timed
+    steps recorded themselves (decoder launch times, per-rank times at N > 1), none of the measurements that take runs of their own
+    (in-run A/Bs, family profile, box probes, inference, the other legs, the all-reduce pass, the CPU baseline).  Once on one GPU
+    and once as the 2-rank rehearsal, both at a toy shape."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    full_only = {'ab', 'allreduce', 's2', 'vctk', 'b64', 'inference', 'cpu_baseline'}
+    for extra, world in ((['--gpus', '1', '--batch', '4', '--text-len', '24', '--dec-steps', '10'], 1),
+                         (['--gpus', '2', '--rehearse-shared-device'], 2)):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1'] + extra,
+                           env=env, capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [x for x in r.stdout.splitlines() if x.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        print('  plain line, %d GPU(s): %.3f ms/step, keys %s' % (world, j['ms_per_step'], sorted(j)))
+        assert j['metric'] == 'mel-frames/sec (train step, batch=32 r=2)' and j['unit'] == 'mel-frames/s'
+        assert j['higher_is_better'] is True and j['dtype'] == 'f32' and j['n_gpus'] == world and j['steps'] == 3
+        assert j['ms_per_step'] > 0 and j['value'] > 0 and np.isfinite(j['final_loss'])
+        assert not full_only & set(j), sorted(full_only & set(j))
+        assert 'shader_clock_ghz_latency_bound' not in j['box'] and 'decoder_mode' in j['box']
+        assert [x['what'] for x in j['rooflines']][1:] == ['whole train step']
+        assert j['kernels_ms']['us_per_decoder_step_fwd'] > 0 and j['kernels_ms']['us_per_decoder_step_bwd'] > 0
+        assert ('per_rank' in j) == (world > 1)

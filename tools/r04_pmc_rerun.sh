@@ -15,5 +15,5 @@ a = json.load(open('$O/r04_pmc.json')); a['step'] = json.load(open('$O/r04_pmc_s
 json.dump(a, open('$O/r04_pmc.json', 'w'), indent=1)
 PY
 cp $O/r04_pmc.json $R/profiles/pmc_latest.json
-python bench.py > $O/r04_bench.json 2> $O/r04_bench.err
+python bench.py --full > $O/r04_bench.json 2> $O/r04_bench.err
 cat $O/r04_clock.txt $O/r04_pmc_step.txt; tail -c 400 $O/r04_bench.json
