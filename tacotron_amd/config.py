@@ -22,7 +22,6 @@ RESTORE_FROM = None
 class Config(object):
     """Same attribute names as the reference; mutated at runtime by train()/test() exactly as the reference
     drivers do (`config.r`, `config.vocab_size`, `config.data_path`, `config.save_path`, `config.restore`)."""
-    max_decode_iter = maximum_audio_length // (r * hop_length)
     attention_units = 256
     decoder_units = 256
     mel_features = 80
@@ -50,6 +49,20 @@ class Config(object):
     data_path = 'data/nancy/'
     save_path = 'nancy/tacotron'
     restore = False
+
+    # models/tacotron.py:13 evaluates maximum_audio_length // (r hop_length) once, with audio.r; here `r` is changed at run time
+    # (test.py from the checkpoint, train.py from meta.pkl), so the decode length follows the r in use unless a caller sets it
+    _max_decode_iter = None
+
+    @property
+    def max_decode_iter(self):
+        if self._max_decode_iter is not None:
+            return self._max_decode_iter
+        return maximum_audio_length // (self.r * hop_length)
+
+    @max_decode_iter.setter
+    def max_decode_iter(self, value):
+        self._max_decode_iter = value
 
     def validate(self):
         """The HIP kernels compile the reference's layer widths in (include/taco_hip.h); refuse anything else loudly."""

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from oracle import griffinlim_numpy as gl
+from oracle import taco_numpy as on
 from tacotron_amd import audio
 from tacotron_amd.audio import reshape_frames
 from tests import audio_ref
@@ -75,7 +76,7 @@ def _check_features(gpu_log, ref_log, what):
     assert dl.max() <= 2e-3, '%s: log error %.2e on bins >= 1e-3 of the frame maximum' % (what, dl.max())
 
 
-@pytest.mark.parametrize('r', [2, 3, 5])
+@pytest.mark.parametrize('r', [1, 2, 3, 4, 5])
 @pytest.mark.parametrize('idx', [[3], list(range(7))], ids=['B1', 'B7'])
 def test_features_match_reference(built_lib, r, idx):
     mel, stft, kept, bounds = _run(idx, r)
@@ -151,12 +152,8 @@ def _write_wav16(path, y, sr=16000):
         f.writeframes(np.clip(np.round(y * 32767), -32768, 32767).astype('<i2').tobytes())
 
 
-def test_preprocess_nancy_end_to_end(built_lib, tmp_path):
-    from tacotron_amd import preprocess, train
-    from tacotron_amd.config import Config
-    from tacotron_amd.data import Vocab
-    from tacotron_amd.model import Tacotron
-
+def _write_nancy(tmp_path):
+    """Six utterances in the Blizzard Nancy layout (prompts.data + wavn/); the third is longer than max_len and is dropped."""
     lines = ['Hello world.', 'The quick brown fox!', 'Too long to keep.', 'Jumps over.', 'A lazy dog?', 'Zebra quartz.']
     lens = [30000, 45000, 130000, 20000, 60000, 36000]
     wav_dir = tmp_path / 'nancy' / 'wavn'
@@ -165,6 +162,16 @@ def test_preprocess_nancy_end_to_end(built_lib, tmp_path):
         for i, (text, n) in enumerate(zip(lines, lens)):
             f.write('( nancy%03d "%s" )\n' % (i + 1, text))
             _write_wav16(wav_dir / ('nancy%03d.wav' % (i + 1)), 0.8 * _voice(n, 20 + i, f0=120.0 + 15 * i))
+    return lines, wav_dir
+
+
+def test_preprocess_nancy_end_to_end(built_lib, tmp_path):
+    from tacotron_amd import preprocess, train
+    from tacotron_amd.config import Config
+    from tacotron_amd.data import Vocab
+    from tacotron_amd.model import Tacotron
+
+    lines, wav_dir = _write_nancy(tmp_path)
     count = preprocess.main(['nancy', '--data-dir', str(tmp_path)])
     assert count == 5
     out = str(tmp_path / 'nancy')
@@ -198,3 +205,36 @@ def test_preprocess_nancy_end_to_end(built_lib, tmp_path):
     loss = float(m.loss)
     print('  loss on the preprocessed corpus: %.4f' % loss)
     assert np.isfinite(loss) and loss > 0
+
+
+def test_preprocess_r3_corpus_trains_like_the_oracle(built_lib, tmp_path):
+    """`preprocess --r 3` -> a corpus of Td = ((1 + 108000 // 300) // 12) * 4 = 120 steps of 3 frames -> one Tacotron step on it
+    (decoder.hip: decoder3 has no r = 3 instantiation) gives the fp64 oracle's loss on the same batch and masks."""
+    from tacotron_amd import preprocess, train
+    from tacotron_amd.config import Config
+    from tacotron_amd.model import Tacotron
+
+    _write_nancy(tmp_path)
+    assert preprocess.main(['nancy', '--data-dir', str(tmp_path), '--r', '3']) == 5
+    meta, data, _, _ = train.load_corpus(str(tmp_path / 'nancy'))
+    assert meta['r'] == 3
+    assert data['mel'].shape == (5, 120, 240) and data['stft'].shape == (5, 120, 3075)
+    c = Config()
+    c.r, c.vocab_size = meta['r'], len(meta['vocab'])
+    assert c.max_decode_iter == 120
+    inp = {'text': data['text'], 'text_length': data['text_length'],
+           'mel': np.ascontiguousarray(data['mel'], dtype=np.float32), 'stft': np.ascontiguousarray(data['stft'], dtype=np.float32)}
+    m = Tacotron(c, {k: torch.from_numpy(v) for k, v in inp.items()}, train=True, seed=0)
+    p64 = {k: v.astype(np.float64) for k, v in m.params.to_dict().items()}
+    masks = m.draw_masks()
+    m.forward(masks)
+    m.backward()
+    torch.cuda.synchronize()
+    m.check()
+    assert built_lib.last_cluster(0) == 8 and built_lib.last_cluster(1) == 8   # decoder.hip
+    fm = {k: v.cpu().numpy().astype(np.float64) for k, v in masks.items()}
+    s2s, out, _, _ = on.forward(p64, {k: (v.astype(np.float64) if v.dtype == np.float32 else v) for k, v in inp.items()},
+                                3, 120, True, fm)
+    loss = on.loss_fn(s2s, out, inp['mel'].astype(np.float64), inp['stft'].astype(np.float64))
+    print('  r = 3 corpus: loss hip %.6f oracle %.6f' % (float(m.loss), loss))
+    assert abs(float(m.loss) - loss) <= 1e-5 * loss

@@ -146,6 +146,8 @@ CASES = {
     'full': _full,                                              # B=32, Tt=200, Td=180, r=2
     'b1': lambda: _random(1, 30, 40, 2, 33, 12),
     'b48': lambda: _random(48, 41, 24, 2, 33, 13),              # two decoder3 launches (32 + 16 rows)
+    'r3': lambda: _random(6, 50, 24, 3, 33, 14),                # r = 3 / 4: decoder.hip and the separate stop-rule kernel
+    'r4': lambda: _random(6, 50, 24, 4, 33, 15),                #   in every mode (decoder3 has no r = 3 / 4 instantiation)
 }
 
 
@@ -160,7 +162,7 @@ def test_prefix_identity_and_lengths(built_lib, case, mode, monkeypatch):
     p64 = {k: np.asarray(v, dtype=np.float64) for k, v in p.items()}
     I = Infer(built_lib, p, text, tl, Td, r, V)
     full = I.infer()
-    assert (built_lib.last_cluster(0) == 32) == (mode != 'v3_off')
+    assert (built_lib.last_cluster(0) == 32) == (mode != 'v3_off' and r in (2, 5))
     B = I.B
     # a rule chosen from this decode so that the lengths spread ...
     rule = spread_rule(built_lib, full[2], tl)

@@ -29,6 +29,18 @@ def test_config_defaults_equal_reference():
         c.validate()
 
 
+@pytest.mark.parametrize('r,steps', [(1, 360), (2, 180), (3, 120), (4, 90), (5, 72)])
+def test_max_decode_iter_follows_r(r, steps):
+    """maximum_audio_length // (r hop_length) for the r in use: the drivers set config.r at run time (checkpoint, meta.pkl)."""
+    c = cfg.Config()
+    c.r = r
+    assert c.max_decode_iter == steps == 108000 // (300 * r)
+    c.max_decode_iter = 8                  # an explicit setting holds whatever r is
+    c.r = 1 if r != 1 else 2
+    assert c.max_decode_iter == 8
+    assert cfg.Config().max_decode_iter == 180
+
+
 def test_reshape_frames_matches_reference_vectors():
     g = np.load(os.path.join(GOLD, 'reshape_frames.npz'))
     n = 0
@@ -40,7 +52,7 @@ def test_reshape_frames_matches_reference_vectors():
         assert np.array_equal(f, g['fwd' + k[1:]]), k
         assert np.array_equal(reshape_frames(f, r, forward=False), g['inv' + k[1:]]), k
         n += 1
-    assert n == 4
+    assert n == 10
     # audio.py:106-115 self-test: ramp round trip
     test = np.repeat(np.arange(40)[:, None] + 1, 7, axis=1)
     assert np.array_equal(reshape_frames(reshape_frames(test.T, 2), 2, forward=False), test)

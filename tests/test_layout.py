@@ -24,7 +24,7 @@ def test_exports_match_header(built_lib):
     assert built_lib.version() == declared_v
 
 
-@pytest.mark.parametrize('V,r,S', [(60, 2, 1), (20, 5, 1), (33, 3, 1), (60, 2, 109), (20, 2, 7)])
+@pytest.mark.parametrize('V,r,S', [(60, 2, 1), (20, 5, 1), (33, 3, 1), (41, 1, 1), (27, 4, 1), (60, 2, 109), (20, 2, 7)])
 def test_param_table_matches_oracle_spec(built_lib, V, r, S):
     shape = built_lib.make_shape(4, 10, 6, r, V, S)
     table = built_lib.param_table(shape)

@@ -22,7 +22,7 @@ def test_param_count_matches_survey():
     assert sum(int(np.prod(s)) for _, s, _ in on.param_spec(60, 2)) == 6926609
 
 
-@pytest.mark.parametrize('r', [2, 5])
+@pytest.mark.parametrize('r', [1, 2, 3, 4, 5])
 def test_numpy_and_torch_restatements_agree(r):
     V = 20
     p = on.init_params(V, r, seed=1, perturb=0.3)
