@@ -55,6 +55,48 @@ class Decisions:
         return torch.where(take, nxt, z)
 
 
+class Recorder:
+    """Named intermediates of one forward pass and, after the backward pass, their gradients: the stage-by-stage reference
+    for the HIP backward pass (tests/test_gpu_backward_stages.py).  Bit-neutral: it only calls retain_grad() on tensors the
+    graph forms anyway and registers hooks that read, never change, the gradient flowing through them.  (At S2 -- B=32,
+    Td=500 -- it raises the oracle's peak RSS from 19.5 to 19.9 GB.)  Two quantities are accumulated over the steps:
+        'decoder/attention_v@row'  (B, 256)      each batch row's contribution to d attention_v (they sum to its gradient)
+        'decoder/values@ctx'       (B, Tt, 256)  the part of d values that flows through the context vectors
+    Names: 'encoder/emb', 'encoder/pre_net/{l1,l2}pre', '<cbhg prefix>{in,pool,proj1pre,proj1}' (proj1 = after its ReLU and
+    BN: the proj2 input), 'decoder/keys', 'decoder/values', 'seq2seq_output', and per step t '@t' names:
+    'decoder/pre_net/{l1,l2}pre', 'decoder/x', 'decoder/gru_<l>/{gates,candidate}' (pre-activations), 'decoder/o'
+    (cell_output), 'decoder/q', 'decoder/ctx'."""
+
+    def __init__(self):
+        self.t, self.acc, self.grad = {}, {}, {}
+
+    def keep(self, name, x):
+        if x.requires_grad:
+            x.retain_grad()
+            self.t[name] = x
+        return x
+
+    def accumulate(self, name, x, fn):
+        """acc[name] += fn(d x) when the gradient of x arrives"""
+        if x.requires_grad:
+            def hook(g):
+                v = fn(g.detach())
+                self.acc[name] = v if name not in self.acc else self.acc[name] + v
+            x.register_hook(hook)
+        return x
+
+    def collect(self):
+        """After the backward pass: name -> gradient (numpy).  Drops the references to the graph."""
+        self.grad = {k: (v.grad.numpy() if v.grad is not None else None) for k, v in self.t.items()}
+        self.grad.update({k: v.numpy() for k, v in self.acc.items()})
+        self.t, self.acc = {}, {}
+        return self.grad
+
+
+def _keep(rec, name, x):
+    return x if rec is None else rec.keep(name, x)
+
+
 def _relu(dec, name, x):
     return torch.relu(x) if dec is None else dec.relu(name, x)
 
@@ -80,11 +122,11 @@ def _maxpool(x):
     return F.max_pool1d(xt, 2, 1).transpose(1, 2)
 
 
-def _gru(x, h, wg, bg, wc, bc):
+def _gru(x, h, wg, bg, wc, bc, rec=None, name='{}'):
     H = h.shape[-1]
-    g = torch.sigmoid(torch.addmm(bg, torch.cat([x, h], 1), wg))
+    g = torch.sigmoid(_keep(rec, name.format('gates'), torch.addmm(bg, torch.cat([x, h], 1), wg)))
     r, u = g.split(H, 1)
-    c = torch.tanh(torch.addmm(bc, torch.cat([x, r * h], 1), wc))
+    c = torch.tanh(_keep(rec, name.format('candidate'), torch.addmm(bc, torch.cat([x, r * h], 1), wc)))
     return u * h + (1 - u) * c
 
 
@@ -112,14 +154,16 @@ def _highway(x, p, prefix, dec=None):
     return h * t + x * (1 - t)
 
 
-def cbhg(x, p, prefix, K, spk=None, dec=None):
+def cbhg(x, p, prefix, K, spk=None, dec=None, rec=None):
+    x = _keep(rec, prefix + 'in', x)
     bank = torch.cat([_conv_same(x, p[prefix + 'bank_%d/kernel' % k], p[prefix + 'bank_%d/bias' % k])
                       for k in range(1, K + 1)], 2)
     bank = _relu(dec, prefix + 'bank', bank)
     z = _bn(bank, p[prefix + 'bank_bn/gamma'], p[prefix + 'bank_bn/beta'])
-    y = _maxpool(z) if dec is None else dec.pool2(prefix + 'pool', z)
-    y = _relu(dec, prefix + 'proj1', _conv_same(y, p[prefix + 'proj1/kernel'], p[prefix + 'proj1/bias']))
-    y = _bn(y, p[prefix + 'proj1_bn/gamma'], p[prefix + 'proj1_bn/beta'])
+    y = _keep(rec, prefix + 'pool', _maxpool(z) if dec is None else dec.pool2(prefix + 'pool', z))
+    y = _keep(rec, prefix + 'proj1pre', _conv_same(y, p[prefix + 'proj1/kernel'], p[prefix + 'proj1/bias']))
+    y = _bn(_relu(dec, prefix + 'proj1', y), p[prefix + 'proj1_bn/gamma'], p[prefix + 'proj1_bn/beta'])
+    y = _keep(rec, prefix + 'proj1', y)
     y = _conv_same(y, p[prefix + 'proj2/kernel'], p[prefix + 'proj2/bias'])
     y = _bn(y, p[prefix + 'proj2_bn/gamma'], p[prefix + 'proj2_bn/beta'])
     h = y + x
@@ -135,32 +179,36 @@ def cbhg(x, p, prefix, K, spk=None, dec=None):
     return _bigru(h, p, prefix + 'bigru/', h0)
 
 
-def _prenet(x, p, prefix, k1, k2, dec=None, tag=''):
-    l1 = _relu(dec, prefix + 'l1' + tag, F.linear(x, p[prefix + 'dense/kernel'].t(), p[prefix + 'dense/bias']))
+def _prenet(x, p, prefix, k1, k2, dec=None, tag='', rec=None):
+    l1 = _keep(rec, prefix + 'l1pre' + tag, F.linear(x, p[prefix + 'dense/kernel'].t(), p[prefix + 'dense/bias']))
+    l1 = _relu(dec, prefix + 'l1' + tag, l1)
     if k1 is not None:
         l1 = l1 * (2.0 * k1)
-    l2 = _relu(dec, prefix + 'l2' + tag, F.linear(l1, p[prefix + 'dense_1/kernel'].t(), p[prefix + 'dense_1/bias']))
+    l2 = _keep(rec, prefix + 'l2pre' + tag, F.linear(l1, p[prefix + 'dense_1/kernel'].t(), p[prefix + 'dense_1/bias']))
+    l2 = _relu(dec, prefix + 'l2' + tag, l2)
     if k2 is not None:
         l2 = l2 * (2.0 * k2)
     return l2
 
 
-def forward(p, inputs, r, n_steps, train, masks=None, dec=None):
+def forward(p, inputs, r, n_steps, train, masks=None, dec=None, rec=None):
     """p: dict name->tensor; inputs: dict of tensors (text int64, text_length int64, mel, stft);
     masks: dict of float tensors (0/1); dec: optional Decisions (record / force the ReLU and max-pool decisions; the decoder
-    pre_net sites are named per step: 'decoder/pre_net/l1@<t>').  Returns (seq2seq_output, output, alignments, encoded)."""
+    pre_net sites are named per step: 'decoder/pre_net/l1@<t>'); rec: optional Recorder (named intermediates whose gradients
+    the backward pass leaves in it).  Returns (seq2seq_output, output, alignments, encoded)."""
     masks = masks or {}
     g = (lambda k: masks.get(k)) if train else (lambda k: None)
     text = inputs['text']
     B, Tt = text.shape
-    emb = F.embedding(text, p['embedding'])
+    emb = _keep(rec, 'encoder/emb', F.embedding(text, p['embedding']))
     spk = F.embedding(inputs['speaker'], p['speaker_embed']) if ('speaker' in inputs and 'speaker_embed' in p) else None
-    enc = cbhg(_prenet(emb, p, 'encoder/pre_net/', g('enc_keep1'), g('enc_keep2'), dec), p, 'encoder/cbhg/', 16, spk, dec)
+    enc = cbhg(_prenet(emb, p, 'encoder/pre_net/', g('enc_keep1'), g('enc_keep2'), dec, rec=rec), p, 'encoder/cbhg/', 16, spk, dec,
+               rec)
 
     # attention memory (tacotron.py:48-52)
     valid = torch.arange(Tt)[None, :] < inputs['text_length'][:, None]
-    values = enc * valid[:, :, None].to(enc.dtype)
-    keys = torch.matmul(values, p['decoder/memory_layer/kernel'])
+    values = _keep(rec, 'decoder/values', enc * valid[:, :, None].to(enc.dtype))
+    keys = _keep(rec, 'decoder/keys', torch.matmul(values, p['decoder/memory_layer/kernel']))
     v = p['decoder/attention_v']
 
     nmel = 80
@@ -172,19 +220,26 @@ def forward(p, inputs, r, n_steps, train, masks=None, dec=None):
     dk1, dk2, smp = g('dec_keep1'), g('dec_keep2'), g('sample')
     for t in range(n_steps):
         pn = _prenet(prev[:, nmel * (r - 1):], p, 'decoder/pre_net/',
-                     dk1[:, t] if dk1 is not None else None, dk2[:, t] if dk2 is not None else None, dec, '@%d' % t)
-        x = F.linear(torch.cat([pn, att], 1), p['decoder/in_proj/kernel'].t(), p['decoder/in_proj/bias'])
+                     dk1[:, t] if dk1 is not None else None, dk2[:, t] if dk2 is not None else None, dec, '@%d' % t, rec)
+        x = _keep(rec, 'decoder/x@%d' % t,
+                  F.linear(torch.cat([pn, att], 1), p['decoder/in_proj/kernel'].t(), p['decoder/in_proj/bias']))
         inp = x
         for l in range(3):
             h[l] = _gru(inp, h[l], p['decoder/gru_%d/gates/kernel' % l], p['decoder/gru_%d/gates/bias' % l],
-                        p['decoder/gru_%d/candidate/kernel' % l], p['decoder/gru_%d/candidate/bias' % l])
+                        p['decoder/gru_%d/candidate/kernel' % l], p['decoder/gru_%d/candidate/bias' % l], rec,
+                        'decoder/gru_%d/{}@%d' % (l, t))
             inp = h[l]
-        o = F.linear(x + h[2], p['decoder/out_proj/kernel'].t(), p['decoder/out_proj/bias'])
-        q = torch.mm(o, p['decoder/query_layer/kernel'])
-        score = torch.tanh(keys + q[:, None, :]).matmul(v)
+        o = _keep(rec, 'decoder/o@%d' % t, F.linear(x + h[2], p['decoder/out_proj/kernel'].t(), p['decoder/out_proj/bias']))
+        q = _keep(rec, 'decoder/q@%d' % t, torch.mm(o, p['decoder/query_layer/kernel']))
+        e = torch.tanh(keys + q[:, None, :])
+        score = e.matmul(v)
+        if rec is not None:   # d v = sum over (b, t, s) of d score * e: keep the sum over (t, s) per row b
+            rec.accumulate('decoder/attention_v@row', score, lambda gs, e=e: torch.einsum('bs,bsk->bk', gs, e.detach()))
         score = score.masked_fill(~valid, float('-inf'))
         a = torch.softmax(score, 1)
-        ctx = torch.bmm(a[:, None, :], values)[:, 0]
+        ctx = _keep(rec, 'decoder/ctx@%d' % t, torch.bmm(a[:, None, :], values)[:, 0])
+        if rec is not None:   # ctx = a . values: d values += a^T d ctx
+            rec.accumulate('decoder/values@ctx', ctx, lambda gc, a=a: torch.einsum('bs,bk->bsk', a.detach(), gc))
         att = torch.mm(torch.cat([o, ctx], 1), p['decoder/attention_layer/kernel'])
         outs.append(o)
         aligns.append(a)
@@ -194,9 +249,9 @@ def forward(p, inputs, r, n_steps, train, masks=None, dec=None):
             prev = mel[:, t + 1]
             if smp is not None:
                 prev = torch.where(smp[t][:, None] > 0.5, o, prev)
-    s2s = torch.stack(outs, 1)
+    s2s = _keep(rec, 'seq2seq_output', torch.stack(outs, 1))
     al = torch.stack(aligns, 1)
-    post = cbhg(s2s.reshape(B, n_steps * r, nmel), p, 'post/cbhg/', 8, None, dec)
+    post = cbhg(s2s.reshape(B, n_steps * r, nmel), p, 'post/cbhg/', 8, None, dec, rec)
     out = F.linear(post, p['post/dense/kernel'].t(), p['post/dense/bias']).reshape(B, n_steps, -1)
     return s2s, out, al, enc
 
@@ -209,8 +264,9 @@ def to_torch(pnp, dtype=torch.float64, requires_grad=False):
     return {k: torch.tensor(v, dtype=dtype, requires_grad=requires_grad) for k, v in pnp.items()}
 
 
-def loss_and_grads(pnp, inputs_np, r, n_steps, masks_np=None, dtype=torch.float64, dec=None):
-    """Convenience: numpy in, numpy out.  Returns (loss, s2s, out, align, grads dict).  dec: optional Decisions."""
+def loss_and_grads(pnp, inputs_np, r, n_steps, masks_np=None, dtype=torch.float64, dec=None, rec=None):
+    """Convenience: numpy in, numpy out.  Returns (loss, s2s, out, align, grads dict).  dec: optional Decisions; rec: optional
+    Recorder, whose `grad` holds the intermediates' gradients (numpy) on return."""
     p = to_torch(pnp, dtype, True)
     inputs = {
         'text': torch.tensor(inputs_np['text'], dtype=torch.int64),
@@ -221,10 +277,12 @@ def loss_and_grads(pnp, inputs_np, r, n_steps, masks_np=None, dtype=torch.float6
     if 'speaker' in inputs_np:
         inputs['speaker'] = torch.tensor(inputs_np['speaker'], dtype=torch.int64)
     masks = {k: torch.tensor(v, dtype=dtype) for k, v in (masks_np or {}).items()}
-    s2s, out, al, _ = forward(p, inputs, r, n_steps, True, masks, dec)
+    s2s, out, al, _ = forward(p, inputs, r, n_steps, True, masks, dec, rec)
     loss = loss_fn(s2s, out, inputs['mel'], inputs['stft'])
     loss.backward()
     grads = {k: (t.grad.numpy() if t.grad is not None else None) for k, t in p.items()}
+    if rec is not None:
+        rec.collect()
     return float(loss.detach()), s2s.detach().numpy(), out.detach().numpy(), al.detach().numpy(), grads
 
 

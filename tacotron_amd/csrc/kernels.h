@@ -332,10 +332,11 @@ constexpr int kGsC = 1536;                // 3*256 candidate pre-act grads
 constexpr int kGsX = 2304;                // 256 dx (in-proj output grad)
 constexpr int kGsQ = 2560;                // 256 dq
 constexpr int kGsP1S = 2816;              // 256 d prenet-1 pre-act of step t+1 if that step was fed cell_output[t], else 0
-constexpr int kGsCtx = 3072;              // 256 d context
+constexpr int kGsCtx = 3072;              // 256 unused: neither BPTT kernel writes it (d context travels as E, bwd.dkeys_e)
 constexpr int kGsP2 = 3328;               // 128 d prenet-2 pre-act
 constexpr int kGsP1 = 3456;               // 256 d prenet-1 pre-act
-constexpr int kGsO = 3712;                // 80r (<= 400) d cell_output (total)
+constexpr int kGsO = 3712;                // 80r (<= 400) d cell_output: direct + dx_{t+1} Wx_o^T (its q and pre-net-feed parts
+                                          //   enter the out-proj weight gradient as factors, model.hip)
 constexpr int kGsRec = 4112;
 
 struct DecFwdArgs {

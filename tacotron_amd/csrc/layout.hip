@@ -478,6 +478,8 @@ void build_ws_layout(const TacoShape& s, bool train, const TransLayout& T, WsLay
     // encoder-output gradient is then ONE product [d keys | E] . [Wm^T ; Wx_c^T]
     W.dkeys = a.add("bwd.dkeys_e", {M1, 2 * kAtt});
     W.dvalues = W.dkeys + kAtt;
+    // d seq2seq_output in total; when the post-net's input gradient has a buffer of its own (bwd.post.dx, default) that buffer
+    // accumulates on top of bwd.ds2s and holds it instead
     W.ds2s_tot = a.add("bwd.ds2s_tot", {MD, R80});
     W.bc_fa = a.add("bwd.comp.fa", {kDec, dec_fan_cols(s.r)});      // [Wx_o^T | 0]
     W.bc_wmx = a.add("bwd.comp.wmx", {2 * kAtt, 2 * kCb});          // [Wm^T ; Wx_c^T]

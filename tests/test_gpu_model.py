@@ -726,7 +726,8 @@ def test_peaked_attention_fixture(built_lib):
 def test_s2_envelope(built_lib):
     """BASELINE envelope S2 (B=32, Tt=200, Td=500 = 1000 mel frames, r=2).  Size-independent properties (finite, alignment
     rows sum to 1 and vanish past text_length, loss == fp64 recomputation, bit-reproducible forward, causality: the first
-    180 steps equal the S1 run on the truncated inputs) AND a forward comparison with the fp64 CPU restatement."""
+    180 steps equal the S1 run on the truncated inputs) AND a forward comparison with the fp64 CPU restatement.  (Loss and
+    gradient parity at this size, stage by stage and per parameter: tests/test_gpu_backward_stages.py.)"""
     B, Tt, Td, r, V = 32, 200, 500, 2, 60
     torch.set_num_threads(min(os.cpu_count() or 1, 16))
     inp, masks = _full_case(B, Tt, Td, r, V)

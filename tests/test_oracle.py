@@ -213,3 +213,103 @@ def test_decisions_record_and_force_are_consistent():
     flipped['encoder/cbhg/bank'] = m
     _, _, _, _, g3 = ot.loss_and_grads(p, f(inp), r, Td, f(masks), dec=ot.Decisions(flipped))
     assert np.abs(g3['encoder/pre_net/dense_1/kernel'] - g0['encoder/pre_net/dense_1/kernel']).max() > 0
+
+
+def _recorded_case():
+    r, V, B, Tt, Td = 2, 40, 4, 37, 12
+    p = on.init_params(V, r, seed=4, perturb=0.2)
+    inp, masks = small_case(r=r, V=V, B=B, Tt=Tt, Td=Td, seed=8)
+    inp = {k: (v.astype(np.float64) if v.dtype == np.float32 else v) for k, v in inp.items()}
+    return p, inp, _f64(masks), r, Td
+
+
+def test_recorder_changes_nothing():
+    """The recorder only keeps gradients: every output and every parameter gradient is bit-identical with and without it,
+    and it holds the per-step decoder tensors of every step."""
+    p, inp, masks, r, Td = _recorded_case()
+    plain = ot.loss_and_grads(p, inp, r, Td, masks)
+    rec = ot.Recorder()
+    got = ot.loss_and_grads(p, inp, r, Td, masks, rec=rec)
+    assert got[0] == plain[0]
+    for a, b in zip(got[1:4], plain[1:4]):
+        assert np.array_equal(a, b)
+    for k, g in plain[4].items():
+        assert np.array_equal(got[4][k], g), k
+    G = rec.grad
+    for t in range(Td):
+        for name in ('decoder/x', 'decoder/o', 'decoder/pre_net/l1pre', 'decoder/pre_net/l2pre', 'decoder/gru_2/gates',
+                     'decoder/gru_0/candidate'):
+            assert G['%s@%d' % (name, t)] is not None, (name, t)
+    # (the last step's query and context feed nothing the loss sees)
+    assert G['decoder/q@%d' % (Td - 1)] is None and np.linalg.norm(G['decoder/q@0']) > 0
+    assert G['decoder/keys'].shape == (4, 37, 256) and G['post/cbhg/pool'].shape == (4, 2 * Td, 1024)
+
+
+def test_recorder_per_row_attention_v_and_context_part():
+    """The per-row attention_v contributions sum to the parameter's gradient; the context part of d values plus the keys
+    part (d keys Wm^T) is the whole gradient of the values."""
+    p, inp, masks, r, Td = _recorded_case()
+    rec = ot.Recorder()
+    grads = ot.loss_and_grads(p, inp, r, Td, masks, rec=rec)[4]
+    rows = rec.grad['decoder/attention_v@row']
+    g = grads['decoder/attention_v']
+    assert rows.shape == (4, 256) and np.all(np.linalg.norm(rows, axis=1) > 0)
+    assert np.abs(rows.sum(0) - g).max() <= 1e-12 * np.abs(g).max()
+    dv = rec.grad['decoder/values@ctx'] + rec.grad['decoder/keys'] @ p['decoder/memory_layer/kernel'].T
+    assert np.abs(dv - rec.grad['decoder/values']).max() <= 1e-12 * np.abs(dv).max()
+
+
+def test_recorder_composes_with_forced_decisions():
+    """Recording under a forced Decisions: results equal the forced run without a recorder, bit for bit, and the recorded
+    gradients follow the forced decision (a flipped pre-net unit's pre-activation gradient moves from zero or to zero)."""
+    p, inp, masks, r, Td = _recorded_case()
+    dec = ot.Decisions()
+    ot.loss_and_grads(p, inp, r, Td, masks, dec=dec)
+    force = {k: v.to(torch.float64) for k, v in dec.rec.items()}
+    site = 'encoder/pre_net/l1'
+    f = force[site].clone()
+    f[0, 0, :] = 1.0 - f[0, 0, :]
+    force[site] = f
+    plain = ot.loss_and_grads(p, inp, r, Td, masks, dec=ot.Decisions(dict(force)))
+    rec = ot.Recorder()
+    got = ot.loss_and_grads(p, inp, r, Td, masks, dec=ot.Decisions(dict(force)), rec=rec)
+    assert got[0] == plain[0]
+    for k, g in plain[4].items():
+        assert np.array_equal(got[4][k], g), k
+    dz1 = rec.grad['encoder/pre_net/l1pre'][0, 0]
+    keep = masks['enc_keep1'][0, 0] > 0
+    on_now = f[0, 0].numpy() > 0.5
+    assert np.all(dz1[~(on_now & keep)] == 0) and np.any(dz1[on_now & keep] != 0)
+
+
+def test_stage_bars_have_teeth():
+    """The stage comparison (tests/stage_bars.py) on host arrays: one row perturbed so that the whole tensor stays inside the
+    tensor bar fails the row bar; one exact-zero site perturbed fails the exact-zero check."""
+    from tests.stage_bars import ROW_BAR, TENSOR_BAR, compare, exact_zero_failures, failures
+    p, inp, masks, r, Td = _recorded_case()
+    rec = ot.Recorder()
+    ot.loss_and_grads(p, inp, r, Td, masks, rec=rec)
+    ref = np.stack([rec.grad['decoder/gru_1/gates@%d' % t] for t in range(Td)], 1)    # (B, Td, 512)
+    B = ref.shape[0]
+    assert not failures(compare('gates', ref.copy(), ref, (B, Td)))
+    nr = np.linalg.norm(ref, axis=2)
+    den = np.maximum(nr, 1e-2 * np.sqrt(np.mean(nr ** 2)))
+    b, t = np.unravel_index(int(np.argmin(den)), den.shape)
+    hip = ref.copy()
+    rng = np.random.default_rng(0)
+    e = rng.standard_normal(512)
+    hip[b, t] += 3 * ROW_BAR * den[b, t] * e / np.linalg.norm(e)
+    st = compare('gates', hip, ref, (B, Td))
+    print('  one row off: tensor rel-L2 %.2e, worst row %.2e at %s' % (st['rel'], st['row'], st['at']))
+    assert st['rel'] <= TENSOR_BAR and st['at'] == (b, t)
+    bad = failures(st)
+    assert len(bad) == 1 and 'worst row' in bad[0]
+    # exact zeros: d keys past text_length
+    dk = rec.grad['decoder/keys']
+    past = (np.arange(dk.shape[1])[None, :] >= inp['text_length'][:, None])[:, :, None]
+    assert past.any() and not exact_zero_failures('dkeys', dk, past)
+    hip = dk.copy()
+    i = np.argwhere(np.broadcast_to(past, dk.shape))[0]
+    hip[tuple(i)] = 1e-30
+    assert exact_zero_failures('dkeys', hip, past)
+    assert not failures(compare('dkeys', hip, dk, dk.shape[:2]))   # (which the other bars do not see)
