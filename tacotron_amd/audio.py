@@ -104,12 +104,13 @@ def load_wav(path, sr):
 _MEL_DEVICE = {}
 
 
-def process_audio(waves, lengths, r, max_len=MAXIMUM_AUDIO_LENGTH, dtype=None):
+def process_audio(waves, lengths, r, max_len=MAXIMUM_AUDIO_LENGTH, dtype=None, out=None, work=None):
     """audio.process_audio (audio.py:38-65) for a batch, on the GPU (csrc/features.hip): trim, drop the utterances longer than
     max_len after trimming, zero-pad the others to max_len, pre-emphasis, STFT, complex mel, log, r-frame layout.
     waves: (B, L) fp32 device tensor (row b valid up to lengths[b]) or a list of 1-D arrays; lengths: host ints (None with a list:
     the arrays' lengths).  Returns device tensors (mel (B, Td, 80 r), stft (B, Td, 1025 r), kept (B) int32, bounds (B, 2) int32
-    trim [start, end)), mel / stft in `dtype` (default float16, what preprocess.py stores; or float32).  Dropped rows are zero."""
+    trim [start, end)), mel / stft in `dtype` (default float16, what preprocess.py stores; or float32).  Dropped rows are zero.
+    out / work: the caller's own (mel, stft, kept, bounds) buffers and workspace, as lib.audio_features takes them."""
     import torch
 
     from . import lib
@@ -127,4 +128,4 @@ def process_audio(waves, lengths, r, max_len=MAXIMUM_AUDIO_LENGTH, dtype=None):
     dev = waves.device
     if dev.index not in _MEL_DEVICE:   # (a blocking upload from pageable memory: complete before any stream uses it)
         _MEL_DEVICE[dev.index] = torch.from_numpy(mel_basis()).to(dev)
-    return lib.audio_features(waves.contiguous(), lengths, _MEL_DEVICE[dev.index], r, max_len, dtype)
+    return lib.audio_features(waves.contiguous(), lengths, _MEL_DEVICE[dev.index], r, max_len, dtype, out=out, work=work)

@@ -14,12 +14,13 @@ import torch
 from . import lib
 
 
-def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None):
+def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None):
+    """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh)."""
     dev = out.device
     mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
-    mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True)   # (B, 1025, F)
+    mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
     if phase0 is None:
         g = torch.Generator(device='cpu').manual_seed(seed)
         phase0 = (2.0 * math.pi * torch.rand(mag_t.shape, generator=g)).to(dev)
-    return lib.griffinlim(mag_t, phase0.contiguous(), n_iter)
+    return lib.griffinlim(mag_t, phase0.contiguous(), n_iter, out=wave, work=work)

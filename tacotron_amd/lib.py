@@ -217,16 +217,26 @@ def gemm_tn(A, dY, dW, M, N, K, taps=1, T=None, pad_l=0, accumulate=False, lda=N
                              int(accumulate), stream_ptr()), 'taco_gemm_tn')
 
 
-def weight_image(W=None, taps=1, K=0, N=0, ldw=None):
+def weight_image_bytes(W, taps, K, N, ldw=None):
+    need = _lib.taco_debug_weight_image(ptr(W), ldw or N, taps, K, N, None, 0, None)
+    if need < 0:
+        raise TacoError('taco_debug_weight_image: %d' % need)
+    return int(need)
+
+
+def weight_image(W=None, taps=1, K=0, N=0, ldw=None, img=None):
     """Op-level door to the pre-split weight images (include/taco_hip.h taco_debug_weight_image).  W None: clear this thread's
-    table.  Otherwise builds and registers the bf16 plane image of W (taps, K, N) and returns the image tensor (keep it alive)."""
+    table.  Otherwise builds and registers the bf16 plane image of W (taps, K, N) and returns the image tensor (keep it alive).
+    img: the caller's own buffer of at least weight_image_bytes(...) bytes (16-byte aligned) instead of a fresh one."""
     if W is None:   # -> launches that ran the image form since the previous clear
         return int(_lib.taco_debug_weight_image(None, 0, 0, 0, 0, None, 0, None))
     ldw = ldw or N
     need = _lib.taco_debug_weight_image(ptr(W), ldw, taps, K, N, None, 0, None)
     if need < 0:
         raise TacoError('taco_debug_weight_image: %d' % need)
-    img = torch.empty(need // 2, dtype=torch.int16, device=W.device)
+    if img is None:
+        img = torch.empty(need // 2, dtype=torch.int16, device=W.device)
+    assert img.numel() * img.element_size() >= need and img.data_ptr() % 16 == 0, 'taco: weight image buffer too small or misaligned'
     rc = _lib.taco_debug_weight_image(ptr(W), ldw, taps, K, N, ptr(img), need, stream_ptr())
     _check(int(rc), 'taco_debug_weight_image')
     return img
@@ -351,13 +361,23 @@ def debug_spin(blocks, threads, lds_bytes, usec, stream=None):
     _check(_lib.taco_debug_spin(int(blocks), int(threads), int(lds_bytes), int(usec), sp), 'taco_debug_spin')
 
 
-def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=False):
-    """(B, Td, r*C) normalised r-frame layout -> chronological de-normalised (B, F, C) [and / or exp() transposed (B, C, F)]."""
+def _own_or_given(given, shape, dtype, device, what):
+    """a fresh torch.empty tensor, or the caller's buffer after a shape / dtype / device check"""
+    if given is None:
+        return torch.empty(*shape, dtype=dtype, device=device)
+    if tuple(given.shape) != tuple(shape) or given.dtype != dtype or given.device != device or not given.is_contiguous():
+        raise ValueError('%s: expected a contiguous %s tensor of shape %s on %s' % (what, dtype, tuple(shape), device))
+    return given
+
+
+def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=False, spec=None, mag_t=None):
+    """(B, Td, r*C) normalised r-frame layout -> chronological de-normalised (B, F, C) [and / or exp() transposed (B, C, F)].
+    spec / mag_t: the caller's own output buffers (default: fresh ones)."""
     B, Td, RC = output.shape
     Cw = RC // r
     F = (Td // 4) * 4 * r
-    spec = torch.empty(B, F, Cw, device=output.device) if want_spec else None
-    mag_t = torch.empty(B, Cw, F, device=output.device) if want_mag_t else None
+    spec = _own_or_given(spec, (B, F, Cw), torch.float32, output.device, 'denorm_unframe: spec') if want_spec else None
+    mag_t = _own_or_given(mag_t, (B, Cw, F), torch.float32, output.device, 'denorm_unframe: mag_t') if want_mag_t else None
     _check(_lib.taco_denorm_unframe(ptr(output), ptr(stft_mean), ptr(stft_std), ptr(spec), ptr(mag_t), B, Td, r, Cw,
                                     stream_ptr()), 'taco_denorm_unframe')
     if want_spec and want_mag_t:
@@ -365,15 +385,23 @@ def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=Fa
     return spec if want_spec else mag_t
 
 
-def griffinlim(mag_t, phase0, n_iter=50):
-    """mag_t, phase0 (B, 1025, F) -> waveform (B, 300 (F - 1)); audio.griffinlim on the GPU."""
+def griffinlim_workspace_floats(B, F) -> int:
+    nbytes = _lib.taco_griffinlim_workspace_bytes(int(B), int(F))
+    if nbytes < 0:
+        raise TacoError('taco_griffinlim_workspace_bytes: bad shape')
+    return nbytes // 4
+
+
+def griffinlim(mag_t, phase0, n_iter=50, out=None, work=None):
+    """mag_t, phase0 (B, 1025, F) -> waveform (B, 300 (F - 1)); audio.griffinlim on the GPU.  out / work: the caller's own
+    waveform buffer and workspace (griffinlim_workspace_floats(B, F) floats); default: fresh ones."""
     B, Cb, F = mag_t.shape
     assert Cb == 1025 and phase0.shape == mag_t.shape
     nbytes = _lib.taco_griffinlim_workspace_bytes(B, F)
     if nbytes < 0:
         raise TacoError('taco_griffinlim_workspace_bytes: bad shape')
-    work = torch.empty(nbytes // 4, device=mag_t.device)
-    wave = torch.empty(B, 300 * (F - 1), device=mag_t.device)
+    work = _own_or_given(work, (nbytes // 4,), torch.float32, mag_t.device, 'griffinlim: work')
+    wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, mag_t.device, 'griffinlim: out')
     _check(_lib.taco_griffinlim(ptr(mag_t), ptr(phase0), ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()),
            'taco_griffinlim')
     return wave
@@ -386,10 +414,11 @@ def audio_features_workspace_bytes(B, L) -> int:
     return n
 
 
-def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch.float16):
+def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch.float16, out=None, work=None):
     """audio.process_audio for a batch (include/taco_hip.h taco_audio_features).  wave (B, L) fp32 on the device, wave_len (B) host
     ints, mel_basis (80, 1025) fp32 on the device -> (mel (B, Td, 80 r), stft (B, Td, 1025 r), kept (B) int32, bounds (B, 2) int32),
-    device tensors; out_dtype float16 or float32."""
+    device tensors; out_dtype float16 or float32.  out: the caller's own (mel, stft, kept, bounds) buffers, work: the caller's
+    own workspace (uint8, audio_features_workspace_bytes(B, L) bytes); default: fresh ones."""
     B, L = wave.shape
     if len(wave_len) != B:
         raise ValueError('audio_features: %d lengths for %d waves' % (len(wave_len), B))
@@ -399,11 +428,12 @@ def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch
     F = 1 + int(max_len) // 300
     Td = (F // (4 * r)) * 4 if r > 0 else 0
     dev = wave.device
-    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    mel = torch.empty(B, max(Td, 0), 80 * max(r, 0), dtype=out_dtype, device=dev)
-    stft = torch.empty(B, max(Td, 0), 1025 * max(r, 0), dtype=out_dtype, device=dev)
-    bounds = torch.empty(B, 2, dtype=torch.int32, device=dev)
-    kept = torch.empty(B, dtype=torch.int32, device=dev)
+    o = out if out is not None else (None, None, None, None)
+    work = _own_or_given(work, (nbytes,), torch.uint8, dev, 'audio_features: work')
+    mel = _own_or_given(o[0], (B, max(Td, 0), 80 * max(r, 0)), out_dtype, dev, 'audio_features: mel')
+    stft = _own_or_given(o[1], (B, max(Td, 0), 1025 * max(r, 0)), out_dtype, dev, 'audio_features: stft')
+    kept = _own_or_given(o[2], (B,), torch.int32, dev, 'audio_features: kept')
+    bounds = _own_or_given(o[3], (B, 2), torch.int32, dev, 'audio_features: bounds')
     _check(_lib.taco_audio_features(ptr(wave), lens, ptr(mel_basis), ptr(mel), ptr(stft), ptr(bounds), ptr(kept), ptr(work), B, L,
                                     int(max_len), int(r), int(out_dtype == torch.float16), stream_ptr()), 'taco_audio_features')
     return mel, stft, kept, bounds

@@ -3,7 +3,12 @@ restatement of audio.process_audio (tests/audio_ref.py; PARITY WITH LIBROSA UNPI
 
 Features are compared in the linear domain, frame by frame: |exp(gpu) - exp(ref)| <= 1e-5 * max(exp(ref)) over the frame, and
 on the bins at least 1e-3 of the frame maximum the log difference is <= 2e-3.  Trim bounds and keep flags are exact (the
-signals keep every trim frame far from the -60 dB threshold, checked below)."""
+signals keep every trim frame far from the -60 dB threshold, checked below).
+
+Outputs and workspace of the feature kernel (and of taco_denorm_unframe / Griffin-Lim in the round trip) are the tests' own
+buffers from a guarded arena (tests/poison.py), poisoned before the call -- `ones` for mel / stft (every byte differs from a
+written zero, in fp16 too) and for the int32 bounds / kept, NaN for the workspace: afterwards every output element is written
+(rows of dropped utterances as zeros) and the guard bands are intact."""
 import os
 import pickle as pkl
 import wave
@@ -17,6 +22,7 @@ from oracle import taco_numpy as on
 from tacotron_amd import audio
 from tacotron_amd.audio import reshape_frames
 from tests import audio_ref
+from tests.poison import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -60,9 +66,19 @@ def _ref(i):
 
 
 def _run(idx, r, dtype=torch.float32):
+    from tacotron_amd import lib
     sig = _signals()
     waves = [sig[i] for i in idx]
-    return audio.process_audio(waves, None, r, MAX_LEN, dtype)
+    B, L = len(waves), max(len(w) for w in waves)
+    Td = ((1 + MAX_LEN // 300) // (4 * r)) * 4
+    G = Guarded({'mel': ((B, Td, 80 * r), dtype, 'ones'), 'stft': ((B, Td, 1025 * r), dtype, 'ones'),
+                 'kept': ((B,), torch.int32, 'ones'), 'bounds': ((B, 2), torch.int32, 'ones'),
+                 'work': ((lib.audio_features_workspace_bytes(B, L),), torch.uint8, 'qnan')})
+    res = audio.process_audio(waves, None, r, MAX_LEN, dtype, out=(G['mel'], G['stft'], G['kept'], G['bounds']), work=G['work'])
+    torch.cuda.synchronize()
+    G.check('mel', 'stft', 'kept', 'bounds')
+    assert all(a.data_ptr() == G[k].data_ptr() for a, k in zip(res, ('mel', 'stft', 'kept', 'bounds')))
+    return res
 
 
 def _check_features(gpu_log, ref_log, what):
@@ -132,13 +148,21 @@ def test_round_trip_through_griffinlim(built_lib):
     r = 2
     _, stft, _, _ = _run([0], r)
     RC = stft.shape[2]
+    F = (stft.shape[1] // 4) * 4 * r
+    G = Guarded({'mag_t': ((1, 1025, F), torch.float32, 'qnan'), 'wave': ((1, 300 * (F - 1)), torch.float32, 'qnan'),
+                 'work': ((lib.griffinlim_workspace_floats(1, F),), torch.float32, 'qnan')})
     mag_t = lib.denorm_unframe(stft.contiguous(), torch.zeros(RC, device='cuda'), torch.ones(RC, device='cuda'), r,
-                               want_spec=False, want_mag_t=True)   # (1, 1025, F) = exp(log |X| + ...)
-    F = mag_t.shape[2]
+                               want_spec=False, want_mag_t=True, mag_t=G['mag_t'])   # (1, 1025, F) = exp(log |X| + ...)
+    torch.cuda.synchronize()
+    G.check('mag_t')
+    assert mag_t.shape[2] == F
     ph = torch.as_tensor(2 * np.pi * np.random.default_rng(7).random((1, 1025, F)), dtype=torch.float32, device='cuda')
     mag = mag_t[0].double().cpu().numpy()
-    w0 = lib.griffinlim(mag_t, ph, 0)[0].double().cpu().numpy()
-    w50 = lib.griffinlim(mag_t, ph, 50)[0].double().cpu().numpy()
+    w0 = lib.griffinlim(mag_t, ph, 0, out=G['wave'], work=G['work'])[0].double().cpu().numpy()
+    G.check('wave')
+    G.refill('wave', 'work')
+    w50 = lib.griffinlim(mag_t, ph, 50, out=G['wave'], work=G['work'])[0].double().cpu().numpy()
+    G.check('wave')
     sc0, sc50 = gl.spectral_convergence(w0, mag), gl.spectral_convergence(w50, mag)
     print('  spectral convergence %.4f -> %.4f after 50 rounds' % (sc0, sc50))
     assert sc50 < 0.5 * sc0

@@ -1,10 +1,16 @@
 """GPU: op-level parity of the HIP kernels (through the C ABI) against NumPy fp64 restatements.
-Tolerances (fp32 kernel vs fp64 oracle): rel-L2 <= 2e-6 * sqrt(K)-ish, stated per test."""
+Tolerances (fp32 kernel vs fp64 oracle): rel-L2 <= 2e-6 * sqrt(K)-ish, stated per test.
+
+Every output and scratch buffer is carved from a guarded arena (tests/poison.py `Guarded`) and starts poisoned -- NaN (`qnan`) for
+what a kernel overwrites, 7.0 / 7.5 where a test needs a finite fill, `noise` for scratch, `ones` for byte outputs; buffers the
+header wants zeroed (Adam's m, v) are zeroed.  After the call the guard bands are bytewise intact, written buffers hold no
+poison, and the margins of strided outputs kept their fill bytewise."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import taco_numpy as on
+from tests.poison import Guarded
 from tests.util import report
 
 pytestmark = pytest.mark.gpu
@@ -52,8 +58,10 @@ def test_naive_gemm_plumbing(built_lib):
     rng = np.random.default_rng(0)
     M, N, K = 37, 24, 19
     A, W, b = rng.standard_normal((M, K)), rng.standard_normal((1, K, N)), rng.standard_normal(N)
-    C = torch.zeros(M, N, device='cuda')
+    G = Guarded({'C': ((M, N), torch.float32, 'qnan')})
+    C = G['C']
     built_lib.debug_gemm_naive(dev(A), dev(W), C, M, N, K, bias=dev(b), act=1)
+    G.check('C')
     ref, _ = conv_ref(A, W, b, M, 0, 1)
     r, m = report('naive gemm', C.cpu().numpy(), ref)
     assert r < 1e-6
@@ -86,12 +94,15 @@ def test_conv_gemm(built_lib, case):
     scale = rng.standard_normal(N) if 'scale' in extras else None
     shift = rng.standard_normal(N) if 'scale' in extras else None
     res = rng.standard_normal((M, N)) if 'residual' in extras else None
-    C = torch.full((M, N), float('nan'), device='cuda')
-    Cpre = torch.full((M, N), float('nan'), device='cuda') if 'pre' in extras else None
+    G = Guarded({'C': ((M, N), torch.float32, 'qnan'), 'Cpre': ((M, N), torch.float32, 'qnan')})
+    C = G['C']
+    Cpre = G['Cpre'] if 'pre' in extras else None
     built_lib.conv_gemm(dev(A), dev(W), C, M, N, K, taps=taps, T=T, pad_l=pad_l, act=act,
                         bias=None if bias is None else dev(bias), scale=None if scale is None else dev(scale),
                         shift=None if shift is None else dev(shift), residual=None if res is None else dev(res),
                         keep=None if keep is None else dev(keep, torch.uint8), Cpre=Cpre)
+    G.check(*(('C', 'Cpre') if Cpre is not None else ('C',)))      # (an unused Cpre keeps its poison: nothing wrote there)
+    assert Cpre is not None or G.margin_intact('Cpre', torch.ones(M, N, dtype=torch.bool))
     ref, pre = conv_ref(A, W, bias, T, pad_l, act, keep, scale, shift, res)
     r, m = report('conv_gemm %s' % (case[:7],), C.cpu().numpy(), ref)
     assert r < 5e-6
@@ -151,15 +162,18 @@ def test_conv_gemm_weight_image(built_lib, case, ns, monkeypatch):
     dA, dW, db = dev(A), dev(W), (None if bias is None else dev(bias))
     ref, _ = conv_ref(A, W, bias, T, pad_l, act)
     built_lib.weight_image(None)
-    C0 = torch.full((M, N), float('nan'), device='cuda')
+    G = Guarded({'C0': ((M, N), torch.float32, 'qnan'), 'C1': ((M, N), torch.float32, 'qnan'),
+                 'img': ((built_lib.weight_image_bytes(dW, taps, K, N) // 2,), torch.int16, 'qnan')})
+    C0 = G['C0']
     built_lib.conv_gemm(dA, dW, C0, M, N, K, taps=taps, T=T, pad_l=pad_l, act=act, bias=db)      # no image registered: in-register split
     assert built_lib.weight_image(None) == 0
-    img = built_lib.weight_image(dW, taps=taps, K=K, N=N)
-    C1 = torch.full((M, N), float('nan'), device='cuda')
+    img = built_lib.weight_image(dW, taps=taps, K=K, N=N, img=G['img'])
+    C1 = G['C1']
     built_lib.conv_gemm(dA, dW, C1, M, N, K, taps=taps, T=T, pad_l=pad_l, act=act, bias=db)
     torch.cuda.synchronize()
     assert built_lib.weight_image(None) == 1, 'the launch did not take the image form'
     del img
+    G.check('C0', 'C1')
     assert report('conv_gemm image form %s' % (case[:7],), C1.cpu().numpy(), ref)[0] < 5e-6
     assert torch.equal(C0, C1), 'image form differs from the in-register split: max |d| = %g' % float((C0 - C1).abs().max())
 
@@ -187,9 +201,11 @@ def test_model_weight_images_do_not_outlive_the_call(built_lib, monkeypatch):
     assert np.abs(W1 - W0).max() > 1e-4, 'the Adam step did not move the parameters: the test would not see a stale image'
     M, K, N = 256, 128, 256
     A = np.random.default_rng(5).standard_normal((M, K))
-    C = torch.full((M, N), float('nan'), device='cuda')
+    G = Guarded({'C': ((M, N), torch.float32, 'qnan')})
+    C = G['C']
     built_lib.conv_gemm(dev(A), Wfull[:128], C, M, N, K)
     torch.cuda.synchronize()
+    G.check('C')
     ref, _ = conv_ref(A, W1[None], None, M, 0, 0)
     assert report('conv_gemm after a train step', C.cpu().numpy(), ref)[0] < 5e-6
 
@@ -212,10 +228,12 @@ def test_bf16x3_products_are_fp32_grade(built_lib, scale, monkeypatch):
     err = {}
     for bx in ('0', '1'):
         monkeypatch.setenv('TACO_GEMM2_BF16X', bx)
-        C = torch.full((M, N), float('nan'), device='cuda')
+        G = Guarded({'C': ((M, N), torch.float32, 'qnan')})
+        C = G['C']
         before = built_lib.debug_gemm2_window(0, 1 << 30)
         built_lib.conv_gemm(dev(A), dev(W), C, M, N, K, taps=taps, T=T, pad_l=1, act=0)
         assert built_lib.debug_gemm2_window(0, 1 << 30) == 1, 'the launch did not go to gemm2.hip'
+        G.check('C')
         err[bx] = report('gemm2 %s scale=%g' % ('bf16x3' if bx == '1' else 'fp32  ', scale), C.cpu().numpy(), ref)
     assert err['0'][0] < 5e-6 and err['1'][0] < 5e-6
     assert err['1'][0] <= 2.0 * err['0'][0] and err['1'][1] <= 2.5 * err['0'][1]
@@ -242,10 +260,12 @@ def _adversarial_case(rng, kernel, kind, depth):
         ref = A.astype(np.float64) @ W[0].astype(np.float64)
 
         def run(built_lib):
-            C = torch.full((M, N), float('nan'), device='cuda')
+            G = Guarded({'C': ((M, N), torch.float32, 'qnan')})
+            C = G['C']
             built_lib.debug_gemm2_window(0, 1 << 30)
             built_lib.conv_gemm(dev(A), dev(W), C, M, N, K, taps=1, T=M, pad_l=0, act=0)
             assert built_lib.debug_gemm2_window(0, 1 << 30) == 1, 'the launch did not go to gemm2.hip'
+            G.check('C')
             return C.cpu().numpy()
     else:
         M, N, K = depth, 256, 512          # dW (K, N) = A^T (K, M) dY (M, N): the reduction runs over the M = depth rows
@@ -253,8 +273,10 @@ def _adversarial_case(rng, kernel, kind, depth):
         ref = A.astype(np.float64).T @ dY.astype(np.float64)
 
         def run(built_lib):
-            dW = torch.full((1, K, N), float('nan'), device='cuda')
+            G = Guarded({'dW': ((1, K, N), torch.float32, 'qnan')})
+            dW = G['dW']
             built_lib.gemm_tn(dev(A), dev(dY), dW, M, N, K, taps=1, T=M, pad_l=0, accumulate=False)
+            G.check('dW')
             return dW[0].cpu().numpy()
     return run, ref
 
@@ -319,11 +341,12 @@ def test_conv_gemm_ksplit(built_lib, case):
     A = rng.standard_normal((M, K))
     W = rng.standard_normal((taps, K, N)) / np.sqrt(K * taps)
     bias = rng.standard_normal(N)
-    slabs = torch.empty(4 * M * N, device='cuda')
     outs = []
-    for _ in range(2):
-        C = torch.full((M, N), float('nan'), device='cuda')
+    for fill in ('noise', 'qnan'):         # what the partial slabs hold before the call must not matter
+        G = Guarded({'slabs': ((4 * M * N,), torch.float32, fill), 'C': ((M, N), torch.float32, 'qnan')})
+        slabs, C = G['slabs'], G['C']
         built_lib.conv_gemm_ksplit(dev(A), dev(W), C, M, N, K, slabs, taps=taps, T=T, pad_l=pad_l, act=act, bias=dev(bias))
+        G.check('C')
         outs.append(C.clone())
     ref, _ = conv_ref(A, W, bias, T, pad_l, act)
     assert report('conv_gemm_ksplit %s' % (case,), outs[0].cpu().numpy(), ref)[0] < 5e-6
@@ -350,7 +373,8 @@ def test_conv_gemm_v2_shifted_rows(built_lib, N, ldc, act, variant, monkeypatch)
     W = rng.standard_normal((1, K, N)) / np.sqrt(K)
     Wp = np.zeros((K, nld)); Wp[:, :N] = W[0]
     bias = rng.standard_normal(N)
-    flat = torch.full((M * ldc + 64,), 7.5, device='cuda')
+    G = Guarded({'flat': ((M * ldc + 64,), torch.float32, 7.5)})
+    flat = G['flat']
     before = built_lib.debug_gemm2_window(0, 1 << 30)
     built_lib.conv_gemm_nld(dev(A), dev(Wp), flat, M, N, K, nld, nld, ldc, act=act, bias=dev(bias))
     assert built_lib.debug_gemm2_window(0, 1 << 30) == 1, 'the launch did not go to gemm2.hip'
@@ -358,6 +382,7 @@ def test_conv_gemm_v2_shifted_rows(built_lib, N, ldc, act, variant, monkeypatch)
     C = flat[:M * ldc].view(M, ldc)
     assert report('shifted rows N=%d ldc=%d %s' % (N, ldc, variant), C[:, :N].cpu().numpy(), ref)[0] < 5e-6
     assert bool((C[:, N:] == 7.5).all()) and bool((flat[M * ldc:] == 7.5).all())
+    G.check()
 
 
 def test_conv_gemm_strided_unaligned(built_lib):
@@ -366,12 +391,17 @@ def test_conv_gemm_strided_unaligned(built_lib):
     M, K, N = 96, 1025, 256
     A = rng.standard_normal((M, K))
     W = rng.standard_normal((1, K, N)) / 32
-    flat = torch.zeros(M * 300 + 20, device='cuda')          # C = flat[20:] viewed with ldc = 300
+    G = Guarded({'flat': ((M * 300 + 20,), torch.float32, 'qnan')})
+    flat = G['flat']                                         # C = flat[20:] viewed with ldc = 300
     built_lib.conv_gemm(dev(A), dev(W), flat[20:], M, N, K, lda=1025, ldc=300)
     C = flat[:M * 300].view(M, 300)
     ref, _ = conv_ref(A, W, None, M, 0, 0)
     assert report('unaligned lda', C[:, 20:276].cpu().numpy(), ref)[0] < 5e-6
-    assert float(C[:, :20].abs().max()) == 0 and float(C[:, 276:].abs().max()) == 0
+    # the margins keep their fill BYTEWISE (the stricter form of `== 0` on a zeroed buffer), the 20 floats behind the last row too
+    margin = torch.ones(M * 300 + 20, dtype=torch.bool)
+    margin[:M * 300].view(M, 300)[:, 20:276] = False
+    assert G.margin_intact('flat', margin) and not bool(torch.isnan(C[:, 20:276]).any())
+    G.check()
 
 
 TN_CASES = [(128, 128, 128, 128, 1, 0), (360, 36, 80, 128, 3, 1), (5760, 180, 256, 512, 1, 1), (400, 40, 128, 128, 1, -1),
@@ -402,11 +432,14 @@ def test_gemm_tn(built_lib, case, tn2, monkeypatch):
             st = t + sh
             if 0 <= st < T:
                 ref[j] += x[:, st].T @ y[:, t]
-    dW = torch.full((taps, K, N), 7.0, device='cuda')
+    G = Guarded({'dW': ((taps, K, N), torch.float32, 7.0)})
+    dW = G['dW']
     built_lib.gemm_tn(dev(A), dev(dY), dW, M, N, K, taps=taps, T=T, pad_l=pad_l, accumulate=False)
     assert report('gemm_tn %s' % (case,), dW.cpu().numpy(), ref)[0] < 5e-6
+    G.check()
     built_lib.gemm_tn(dev(A), dev(dY), dW, M, N, K, taps=taps, T=T, pad_l=pad_l, accumulate=True)
     assert report('  accumulate', dW.cpu().numpy(), 2 * ref)[0] < 5e-6
+    G.check()
 
 
 @pytest.mark.parametrize('B,T', [(2, 9), (3, 50), (32, 200)])
@@ -421,17 +454,22 @@ def test_bigru_fwd(built_lib, B, T):
     x = rng.standard_normal((B, T, 128))
     ref = on.bigru(x, p, 'g/')
     w = {k[2:]: dev(v) for k, v in p.items()}
-    xg = torch.zeros(B, T, 768, device='cuda')
-    out = torch.zeros(B, T, 256, device='cuda')
-    ruc = torch.zeros(B, T, 768, device='cuda')
-    built_lib.bigru_fwd(dev(x), w, xg, out, ruc, B, T)
-    r, m = report('bigru_fwd B=%d T=%d' % (B, T), out.cpu().numpy(), ref)
-    assert r < 2e-5 and m < 1e-4
+    for fill in ('qnan', 'noise') if (B, T) == (3, 50) else ('qnan',):
+        G = Guarded({'xg': ((B, T, 768), torch.float32, fill), 'out': ((B, T, 256), torch.float32, fill),
+                     'ruc': ((B, T, 768), torch.float32, fill)})
+        xg, out, ruc = G['xg'], G['out'], G['ruc']
+        built_lib.bigru_fwd(dev(x), w, xg, out, ruc, B, T)
+        r, m = report('bigru_fwd B=%d T=%d (%s)' % (B, T, fill), out.cpu().numpy(), ref)
+        assert r < 2e-5 and m < 1e-4
+        G.check('out', 'ruc')            # (xg is scratch: bounds only)
+        assert bool(torch.isfinite(ruc).all())
 
 
 def test_bernoulli(built_lib):
-    out = torch.zeros(1 << 20, dtype=torch.uint8, device='cuda')
+    G = Guarded({'out': ((1 << 20,), torch.uint8, 'ones'), 'odd': ((1001,), torch.uint8, 'ones')})
+    out = G['out']
     built_lib.fill_bernoulli(out, 0.5, 123)
+    G.check('out')
     a = out.cpu().numpy().copy()
     assert set(np.unique(a)) == {0, 1} and abs(a.mean() - 0.5) < 3e-3
     built_lib.fill_bernoulli(out, 0.5, 123)
@@ -441,9 +479,10 @@ def test_bernoulli(built_lib):
     assert abs((a == b).mean() - 0.5) < 3e-3           # independent streams
     built_lib.fill_bernoulli(out, 0.25, 9)
     assert abs(out.float().mean().item() - 0.25) < 3e-3
-    odd = torch.zeros(1001, dtype=torch.uint8, device='cuda')
+    odd = G['odd']
     built_lib.fill_bernoulli(odd, 1.0, 1)
     assert int(odd.sum()) == 1001
+    G.check('out', 'odd')      # (the three bytes behind element 1000 kept their 255)
 
 
 @pytest.mark.parametrize('gscale', [0.01, 30.0], ids=['noclip', 'clip'])
@@ -454,13 +493,16 @@ def test_clip_adam_step(built_lib, gscale):
     p = {'w': p0.copy()}
     m = {'w': np.zeros(n)}
     v = {'w': np.zeros(n)}
-    P, Mm, Vv = dev(p0), torch.zeros(n, device='cuda'), torch.zeros(n, device='cuda')
-    scratch, gn_out = torch.zeros(256, device='cuda'), torch.zeros(1, device='cuda')
+    G = Guarded({'P': ((n,), torch.float32, 'qnan'), 'm': ((n,), torch.float32, 'zeros'), 'v': ((n,), torch.float32, 'zeros'),
+                 'scratch': ((256,), torch.float32, 'noise'), 'gnorm': ((1,), torch.float32, 'noise')})
+    P, Mm, Vv, scratch, gn_out = G['P'], G['m'], G['v'], G['scratch'], G['gnorm']   # (m, v: the caller zeroes them)
+    P.copy_(dev(p0))
     for step in (1, 2, 3):
         g = rng.standard_normal(n) * gscale
         gn = on.clip_adam_step(p, {'w': g}, m, v, step, 5e-4)
         built_lib.clip_adam_step(P, dev(g), Mm, Vv, 5e-4, 5.0, step, scratch, gn_out)
         assert abs(gn_out.item() - gn) < 1e-4 * gn
+        G.check('gnorm')
     assert report('adam params', P.cpu().numpy(), p['w'])[1] < 2e-6
     assert report('adam m', Mm.cpu().numpy(), m['w'])[0] < 1e-5
     # fp32 (1 - 0.999f) carries a 4.7e-5 relative rounding error, exactly as TF's fp32 ApplyAdam kernel does
