@@ -264,6 +264,31 @@ int taco_denorm_unframe(const float* output, const float* stft_mean, const float
 int64_t taco_griffinlim_workspace_bytes(int B, int F);   /* F >= 5 frames (as taco_griffinlim), else TACO_EINVAL */
 int taco_griffinlim(const float* mag_t, const float* phase0, float* wave, void* workspace, int B, int F, int n_iter, void* stream);
 
+/* Griffin-Lim per utterance (no reference counterpart: the reference vocodes one prompt at a time, test.py:64).  As
+ * taco_griffinlim, but row b is vocoded over its own first F_b = min(F, frames[b] * frames_per_unit) frames -- columns
+ * 0 .. F_b - 1 of its (1025, F) matrices -- so that a batch that ended per row (the lengths of taco_infer_stop) gives every
+ * prompt the Griffin-Lim of that prompt alone, and the frames past a row's end cost no FFT.
+ *   mag_t  (B, 1025, F), wave (B, 300 (F - 1)) as above; the row pitch stays F
+ *   frames (B) int32 on the DEVICE; frames_per_unit >= 1: pass r with the lengths of taco_infer_stop (decoder steps), 1 with
+ *          frame counts
+ *   phase0 (B, 1025, F) initial angles in radians, or NULL: the phases then come from the device.  Element (b, k, t) has index
+ *          i = (b * 1025 + k) * F + t, h = splitmix64(seed * 0xD1342543DE82EF95 + i) in 64-bit wrap-around arithmetic (the mixing
+ *          of taco_fill_bernoulli), u = h >> 40 (24 bits), and the unit phasor is (cos, sin) of 2 pi u / 2^24, formed with
+ *          sincospif of 2 u / 2^24 (exact in fp32).  All integers: a host restatement gives the same u.  seed is ignored when
+ *          phase0 is given
+ *   - samples [0, 300 (F_b - 1)) of row b are bit-identical to what taco_griffinlim writes for B = 1, F = F_b from that row's
+ *     first F_b columns (copied contiguous) and the same phases; the samples from 300 (F_b - 1) on are exactly 0;
+ *   - a row with F_b < 5 (frames[b] <= 0 included; the centre padding needs more than 1024 samples) is all zeros and does no FFT
+ *     work;
+ *   - columns t >= F_b of mag_t and phase0 have no influence on anything (they may hold NaN).
+ * The host reads nothing from frames and does not synchronise: graph-capturable, and a replay follows whatever frames holds at
+ * replay time.  workspace: taco_griffinlim_rows_workspace_bytes bytes (one window sum-of-squares table per row: it depends on
+ * F_b at the tail).  NULL mag_t / frames / wave / workspace, B <= 0, F < 5, n_iter < 0 or frames_per_unit < 1 return TACO_EINVAL
+ * before anything is enqueued.  TACO_VERSION did not change with these two entry points: detect them by the symbol. */
+int64_t taco_griffinlim_rows_workspace_bytes(int B, int F);     /* B > 0, F >= 5, else TACO_EINVAL */
+int taco_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
+                         int frames_per_unit, float* wave, void* workspace, int B, int F, int n_iter, void* stream);
+
 /* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
 /* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length
  * 1200, hop_length 300, pre-emphasis 0.97, log(|.| + 1e-8), 80 mels): librosa.effects.trim (0.6 form: frame mean squares at

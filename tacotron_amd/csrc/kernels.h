@@ -421,6 +421,11 @@ int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s);   // decoder3.hip; TACO_EN
 // Griffin-Lim (audio.py:77-97).  mag_t / phase0 (B, 1025, F); wave (B, 300 (F - 1)); work: griffinlim_workspace_floats floats
 int64_t griffinlim_workspace_floats(int B, int F);
 int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, float* work, int B, int F, int n_iter, hipStream_t s);
+// the same per row (taco_hip.h taco_griffinlim_rows): row b over min(F, frames[b] * frames_per_unit) frames, frames (B) int32 on the
+// device; phase0 nullable (counter-hash phases from `seed`); work: griffinlim_rows_workspace_floats floats
+int64_t griffinlim_rows_workspace_floats(int B, int F);
+int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
+                           float* wave, float* work, int B, int F, int n_iter, hipStream_t s);
 
 // ---------------------------------------------------------------- features.hip
 // audio.process_audio (audio.py:38-65) for a batch: trim, drop / pad, pre-emphasis, STFT, mel, r-frame layout (taco_hip.h)

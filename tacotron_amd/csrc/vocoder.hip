@@ -10,6 +10,14 @@
 //              forward FFT -> new unit-modulus angles (B, F, 1025)
 // The overlap-add is a GATHER (each output sample sums the segments that cover it, in frame order): no atomics, results are
 // reproducible.  gl_wave applies the same gather once more for the final waveform.
+//
+// Per-utterance frame counts (taco_griffinlim_rows): every kernel takes the row pitch F, a nullable device array `frames` and a
+// multiplier; row b is vocoded over its first F_b = min(F, frames[b] * multiplier) frames (frames == nullptr: F_b = F, which is
+// how taco_griffinlim launches the SAME kernels -- device code is compiled with floating-point contraction on, so only one body
+// for both entry points makes a row of the rows form bit-identical to taco_griffinlim of that row alone).  F_b replaces F in the
+// reflect padding, the overlap-add and the window normalisation; the addressing of mag_t, phases, segments and angles keeps the
+// pitch F.  A frame workgroup with t >= F_b returns at entry, before it builds its twiddle table: the grid stays (F, B) because
+// the host never learns the lengths, and the frames past a row's end cost one integer load and a compare.
 #include <algorithm>
 
 #include "common.h"
@@ -58,8 +66,28 @@ __device__ __forceinline__ void make_twiddles(float* twr, float* twi) {
   }
 }
 
-// window sum-of-squares (librosa.filters.window_sumsquare) over n = NFFT + HOP (F - 1) samples
-__global__ void gl_wss_kernel(float* __restrict__ wss, int F) {
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {   // as elementwise.hip (bernoulli_kernel)
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// frames of row b: F without a frames array, else min(F, frames[b] * per_unit); a row below 5 frames (the reflect padding of
+// n_fft/2 needs more than 1024 samples) has none
+__device__ __forceinline__ int row_frames(const int32_t* __restrict__ frames, int per_unit, int b, int F) {
+  if (!frames) return F;
+  const int64_t n = (int64_t)frames[b] * per_unit;
+  if (n < 5) return 0;
+  return n > F ? F : (int)n;
+}
+
+// window sum-of-squares (librosa.filters.window_sumsquare) of row blockIdx.y over n = NFFT + HOP (F_b - 1) samples; rows are
+// `pitch` floats apart (0: one table for a batch whose rows all have F frames)
+__global__ void gl_wss_kernel(float* __restrict__ wss_all, int64_t pitch, int Fp, const int32_t* __restrict__ frames, int per_unit) {
+  const int F = row_frames(frames, per_unit, blockIdx.y, Fp);
+  if (F == 0) return;
+  float* wss = wss_all + (int64_t)blockIdx.y * pitch;
   const int n = NFFT + HOP * (F - 1);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     float acc = 0.f;
@@ -77,24 +105,36 @@ __global__ void gl_wss_kernel(float* __restrict__ wss, int F) {
   }
 }
 
-// angles (B, F, NBIN, 2) <- unit phasors of the given phase angles (radians)
-__global__ void gl_init_kernel(const float* __restrict__ phase, float* __restrict__ ang, int F, int64_t total) {
+// angles (B, F, NBIN, 2) <- unit phasors of the given phase angles (radians), or, phase == nullptr, of the counter-hash phases
+// of taco_griffinlim_rows: element (b, k, t) of the (B, NBIN, F) matrix has index j, u = splitmix64(seed * C + j) >> 40 (24 bits)
+// and the angle 2 pi u / 2^24; 2 u / 2^24 is exact in fp32.  Frames t >= F_b are left alone.
+__global__ void gl_init_kernel(const float* __restrict__ phase, uint64_t seed, float* __restrict__ ang, int F, int64_t total,
+                               const int32_t* __restrict__ frames, int per_unit) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t bt = i / NBIN;
     const int k = (int)(i - bt * NBIN);
     const int64_t b = bt / F;
     const int t = (int)(bt - b * F);
+    if (t >= row_frames(frames, per_unit, (int)b, F)) continue;
+    const int64_t j = (b * NBIN + k) * F + t;   // phase is (B, NBIN, F) like the magnitude matrix
     float s, c;
-    sincosf(phase[(b * NBIN + k) * F + t], &s, &c);   // phase is (B, NBIN, F) like the magnitude matrix
+    if (phase) {
+      sincosf(phase[j], &s, &c);
+    } else {
+      const uint32_t u = (uint32_t)(splitmix64(seed * 0xD1342543DE82EF95ull + (uint64_t)j) >> 40);
+      sincospif((float)u * (2.0f / 16777216.0f), &s, &c);
+    }
     ang[i * 2] = c;
     ang[i * 2 + 1] = s;
   }
 }
 
 __global__ __launch_bounds__(FT) void gl_synth_kernel(const float* __restrict__ mag_t, const float* __restrict__ ang,
-                                                      float* __restrict__ seg, int F) {
+                                                      float* __restrict__ seg, int F,
+                                                      const int32_t* __restrict__ frames, int per_unit) {
   __shared__ float re[NFFT], im[NFFT], twr[NFFT / 2], twi[NFFT / 2];
   const int t = blockIdx.x, b = blockIdx.y;
+  if (t >= row_frames(frames, per_unit, b, F)) return;   // (the whole workgroup: nothing of this frame is ever read)
   make_twiddles(twr, twi);
   const float* a = ang + ((int64_t)b * F + t) * NBIN * 2;
   const float* m = mag_t + (int64_t)b * NBIN * F + t;
@@ -114,7 +154,7 @@ __global__ __launch_bounds__(FT) void gl_synth_kernel(const float* __restrict__ 
   for (int j = threadIdx.x; j < WIN; j += FT) o[j] = re[WOFF + j] * (1.0f / NFFT) * hann(j);
 }
 
-// sample i of the overlap-added, normalised signal of length NFFT + HOP (F - 1) (before the centre trim)
+// sample i of the overlap-added, normalised signal of length NFFT + HOP (F - 1) (before the centre trim); F = the row's frames
 __device__ __forceinline__ float ola_sample(const float* __restrict__ seg_b, const float* __restrict__ wss, int i, int F) {
   float acc = 0.f;
   int t_hi = (i - WOFF) / HOP;
@@ -132,12 +172,16 @@ __device__ __forceinline__ float ola_sample(const float* __restrict__ seg_b, con
 }
 
 __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ seg, const float* __restrict__ wss,
-                                                     float* __restrict__ ang, int F) {
+                                                     int64_t wss_pitch, float* __restrict__ ang, int Fp,
+                                                     const int32_t* __restrict__ frames, int per_unit) {
   __shared__ float re[NFFT], im[NFFT], twr[NFFT / 2], twi[NFFT / 2];
   const int t = blockIdx.x, b = blockIdx.y;
+  const int F = row_frames(frames, per_unit, b, Fp);   // frames of this row; Fp = the pitch
+  if (t >= F) return;
   make_twiddles(twr, twi);
+  wss += (int64_t)b * wss_pitch;
   const int L = HOP * (F - 1);   // length of the trimmed signal y
-  const float* sb = seg + (int64_t)b * F * WIN;
+  const float* sb = seg + (int64_t)b * Fp * WIN;
   for (int j = threadIdx.x; j < NFFT; j += FT) {
     float v = 0.f;
     if (j >= WOFF && j < WOFF + WIN) {
@@ -152,7 +196,7 @@ __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ s
     im[r0] = 0.f;
   }
   fft2048(re, im, twr, twi, -1.0f);
-  float* a = ang + ((int64_t)b * F + t) * NBIN * 2;
+  float* a = ang + ((int64_t)b * Fp + t) * NBIN * 2;
   for (int k = threadIdx.x; k < NBIN; k += FT) {
     const float xr = re[k], xi = im[k];
     const float n2 = xr * xr + xi * xi;
@@ -167,12 +211,17 @@ __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ s
   }
 }
 
-__global__ void gl_wave_kernel(const float* __restrict__ seg, const float* __restrict__ wss, float* __restrict__ wave, int F) {
-  const int L = HOP * (F - 1);
+// every sample of the row: the overlap-add below HOP (F_b - 1), 0 from there on
+__global__ void gl_wave_kernel(const float* __restrict__ seg, const float* __restrict__ wss, int64_t wss_pitch,
+                               float* __restrict__ wave, int Fp, const int32_t* __restrict__ frames, int per_unit) {
+  const int L = HOP * (Fp - 1);
   const int b = blockIdx.y;
-  const float* sb = seg + (int64_t)b * F * WIN;
+  const int F = row_frames(frames, per_unit, b, Fp);
+  const int Lb = F > 0 ? HOP * (F - 1) : 0;
+  wss += (int64_t)b * wss_pitch;
+  const float* sb = seg + (int64_t)b * Fp * WIN;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < L; i += gridDim.x * blockDim.x)
-    wave[(int64_t)b * L + i] = ola_sample(sb, wss, i + NFFT / 2, F);
+    wave[(int64_t)b * L + i] = i < Lb ? ola_sample(sb, wss, i + NFFT / 2, F) : 0.f;
 }
 
 }  // namespace
@@ -181,24 +230,45 @@ int64_t griffinlim_workspace_floats(int B, int F) {
   return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (NFFT + (int64_t)HOP * (F - 1)) + 64;
 }
 
-int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, float* work, int B, int F, int n_iter,
-                      hipStream_t s) {
-  TACO_REQUIRE(mag_t && phase0 && wave && work && B > 0 && n_iter >= 0, "griffinlim: bad arguments");
-  TACO_REQUIRE(F >= 5, "griffinlim: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
+int64_t griffinlim_rows_workspace_floats(int B, int F) {   // one window sum-of-squares table per row (it depends on F_b)
+  return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (int64_t)B * (NFFT + (int64_t)HOP * (F - 1)) + 64;
+}
+
+// the launches of both entry points.  frames == nullptr: every row has F frames and one window table serves the batch
+static int griffinlim_launches(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int per_unit,
+                               float* wave, float* work, int B, int F, int n_iter, hipStream_t s) {
   float* ang = work;
   float* seg = ang + (int64_t)B * F * NBIN * 2;
   float* wss = seg + (int64_t)B * F * WIN;
   const int n = NFFT + HOP * (F - 1);
-  TACO_KLAUNCH(gl_wss_kernel, dim3((n + 255) / 256), dim3(256), 0, s, wss, F);
+  const int64_t wss_pitch = frames ? n : 0;
+  TACO_KLAUNCH(gl_wss_kernel, dim3((n + 255) / 256, frames ? B : 1), dim3(256), 0, s, wss, wss_pitch, F, frames, per_unit);
   const int64_t total = (int64_t)B * F * NBIN;
-  TACO_KLAUNCH(gl_init_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, phase0, ang, F,
-                     total);
+  TACO_KLAUNCH(gl_init_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, phase0, seed, ang, F,
+                     total, frames, per_unit);
   for (int it = 0; it < n_iter; ++it) {
-    TACO_KLAUNCH(gl_synth_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, ang, seg, F);
-    TACO_KLAUNCH(gl_anal_kernel, dim3(F, B), dim3(FT), 0, s, seg, wss, ang, F);
+    TACO_KLAUNCH(gl_synth_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, ang, seg, F, frames, per_unit);
+    TACO_KLAUNCH(gl_anal_kernel, dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit);
   }
-  TACO_KLAUNCH(gl_synth_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, ang, seg, F);
-  TACO_KLAUNCH(gl_wave_kernel, dim3((HOP * (F - 1) + 255) / 256, B), dim3(256), 0, s, seg, wss, wave, F);
+  TACO_KLAUNCH(gl_synth_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, ang, seg, F, frames, per_unit);
+  TACO_KLAUNCH(gl_wave_kernel, dim3((HOP * (F - 1) + 255) / 256, B), dim3(256), 0, s, seg, wss, wss_pitch, wave, F, frames, per_unit);
+  return TACO_OK;
+}
+
+int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, float* work, int B, int F, int n_iter,
+                      hipStream_t s) {
+  TACO_REQUIRE(mag_t && phase0 && wave && work && B > 0 && n_iter >= 0, "griffinlim: bad arguments");
+  TACO_REQUIRE(F >= 5, "griffinlim: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
+  griffinlim_launches(mag_t, phase0, 0, nullptr, 1, wave, work, B, F, n_iter, s);
   TACO_LAUNCH_CHECK("griffinlim");
+  return TACO_OK;
+}
+
+int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
+                           float* wave, float* work, int B, int F, int n_iter, hipStream_t s) {
+  TACO_REQUIRE(mag_t && frames && wave && work && B > 0 && n_iter >= 0 && frames_per_unit >= 1, "griffinlim_rows: bad arguments");
+  TACO_REQUIRE(F >= 5, "griffinlim_rows: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
+  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, s);
+  TACO_LAUNCH_CHECK("griffinlim_rows");
   return TACO_OK;
 }

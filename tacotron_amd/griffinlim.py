@@ -4,7 +4,11 @@
 log-magnitude frames in the r-frame layout -- and returns waveforms (B, 300 (F - 1)), F = (Td // 4) * 4 * r:
 de-normalise + inverse r-frame layout + exp + transpose in ONE HIP gather (taco_denorm_unframe), then Griffin-Lim
 (taco_griffinlim: hand-written 2048-point FFT, 50 rounds like the reference).  The reference draws the initial phase with
-np.random.rand; here it comes from a seeded torch generator so that a run can be reproduced."""
+np.random.rand; here it comes from a seeded torch generator so that a run can be reproduced.
+
+With `lengths` (the per-row decoder steps `Tacotron.run(stop=rule)` leaves on the device) every row is vocoded over its own
+len_b r frames (taco_griffinlim_rows): the Griffin-Lim of that prompt alone, zeros behind it, and -- unless the caller gives
+phase0 -- initial phases from the library's counter-hash generator: no host random numbers, no upload, nothing read back."""
 from __future__ import annotations
 
 import math
@@ -14,12 +18,17 @@ import torch
 from . import lib
 
 
-def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None):
-    """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh)."""
+def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
+                       lengths=None):
+    """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
+    lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats."""
     dev = out.device
     mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
+    if lengths is not None:
+        return lib.griffinlim_rows(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
+                                   frames_per_unit=r, out=wave, work=work)
     if phase0 is None:
         g = torch.Generator(device='cpu').manual_seed(seed)
         phase0 = (2.0 * math.pi * torch.rand(mag_t.shape, generator=g)).to(dev)

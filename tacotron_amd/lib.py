@@ -111,6 +111,8 @@ EXPORTS = {
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    'taco_griffinlim_rows_workspace_bytes': (C.c_int64, [_I, _I]),
+    'taco_griffinlim_rows': (C.c_int, [_P, _P, C.c_uint64, _P, _I, _P, _P, _I, _I, _I, _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_fill_bernoulli': (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
@@ -404,6 +406,39 @@ def griffinlim(mag_t, phase0, n_iter=50, out=None, work=None):
     wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, mag_t.device, 'griffinlim: out')
     _check(_lib.taco_griffinlim(ptr(mag_t), ptr(phase0), ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()),
            'taco_griffinlim')
+    return wave
+
+
+def griffinlim_rows_workspace_floats(B, F) -> int:
+    nbytes = _lib.taco_griffinlim_rows_workspace_bytes(int(B), int(F))
+    if nbytes < 0:
+        raise TacoError('taco_griffinlim_rows_workspace_bytes: bad shape')
+    return nbytes // 4
+
+
+def griffinlim_rows(mag_t, frames, phase0=None, seed=0, n_iter=50, frames_per_unit=1, out=None, work=None):
+    """Griffin-Lim per utterance (include/taco_hip.h taco_griffinlim_rows): mag_t (B, 1025, F), frames (B) int32 on the device ->
+    waveform (B, 300 (F - 1)); row b is the Griffin-Lim of its first F_b = min(F, frames[b] * frames_per_unit) frames, 0 from
+    sample 300 (F_b - 1) on.  phase0 (B, 1025, F) initial angles, or None: seeded phases drawn on the device.  out / work: the
+    caller's own waveform buffer and workspace (griffinlim_rows_workspace_floats(B, F) floats); default: fresh ones."""
+    if mag_t.dim() != 3 or mag_t.shape[1] != 1025 or mag_t.dtype != torch.float32:
+        raise ValueError('griffinlim_rows: mag_t must be a float32 tensor of shape (B, 1025, F), got %s %s' % (mag_t.dtype, tuple(mag_t.shape)))
+    B, _, F = mag_t.shape
+    dev = mag_t.device
+    if tuple(frames.shape) != (B,) or frames.dtype != torch.int32 or frames.device != dev:
+        raise ValueError('griffinlim_rows: frames must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
+                         % (B, dev, frames.dtype, tuple(frames.shape), frames.device))
+    if phase0 is not None and (phase0.shape != mag_t.shape or phase0.dtype != torch.float32 or phase0.device != dev):
+        raise ValueError('griffinlim_rows: phase0 must be a float32 tensor of shape %s on %s' % (tuple(mag_t.shape), dev))
+    if int(frames_per_unit) < 1 or int(n_iter) < 0:
+        raise ValueError('griffinlim_rows: frames_per_unit >= 1 and n_iter >= 0, got %d and %d' % (frames_per_unit, n_iter))
+    nbytes = _lib.taco_griffinlim_rows_workspace_bytes(B, F)
+    if nbytes < 0:
+        raise TacoError('taco_griffinlim_rows_workspace_bytes: bad shape (B=%d, F=%d)' % (B, F))
+    work = _own_or_given(work, (nbytes // 4,), torch.float32, dev, 'griffinlim_rows: work')
+    wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, dev, 'griffinlim_rows: out')
+    _check(_lib.taco_griffinlim_rows(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), int(frames_per_unit),
+                                     ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()), 'taco_griffinlim_rows')
     return wave
 
 

@@ -4,7 +4,9 @@ to 140 chars -> always max_decode_iter steps -> normalised log-magnitude spectro
 wraps each sample in (test.py:65-69) is out of scope; the sample itself is written as <out_dir>/prompt_NNN.wav (16 kHz, the
 reference's sr) next to the de-normalised spectrogram and the alignment as .npy.
 --stop (opt-in, not in the reference): end detection on the attention (lib.TacoStopRule, include/taco_hip.h); each prompt's
-files are cut to its len_b decoder steps and prompt_NNN_len.npy holds len_b.  The rule's defaults are not tuned on a trained model."""
+files are cut to its len_b decoder steps and prompt_NNN_len.npy holds len_b.  The rule's defaults are not tuned on a trained model.
+--vocode-lengths (opt-in, with --stop): Griffin-Lim runs per prompt over its own len_b r frames (lib.griffinlim_rows) with phases
+drawn on the device, so prompt_NNN.wav is the Griffin-Lim of that prompt alone."""
 from __future__ import annotations
 
 import argparse
@@ -39,7 +41,7 @@ def write_wav(path, samples, sr=SR):
         f.writeframes((x * 32767.0).astype('<i2').tobytes())
 
 
-def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None):
+def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -47,7 +49,12 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     (data_input.py:101-106 feeds none: the reference's test.py cannot drive its own VCTK model).
     `stop`: a lib.TacoStopRule, or None for the reference's fixed max_decode_iter steps.  With a rule, prompt i keeps len_b decoder
     steps: len_b r spectrogram frames, len_b alignment rows and the 300 (len_b r - 1) samples Griffin-Lim gives for that many frames
-    (the vocoder still runs over the full, zero-filled length); len_b goes to prompt_NNN_len.npy."""
+    (the vocoder still runs over the full, zero-filled length); len_b goes to prompt_NNN_len.npy.
+    `vocode_lengths` (needs `stop`): the vocoder gets model.lengths and runs over each prompt's own frames only; the files keep
+    their sizes, the samples are the Griffin-Lim of that prompt alone, from phases drawn on the device (seed = index of the batch's
+    first prompt)."""
+    if vocode_lengths and stop is None:
+        raise ValueError('test: vocode_lengths needs a stop rule (the lengths come from taco_infer_stop)')
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
         with open(meta_path, 'rb') as f:
@@ -86,7 +93,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n).cpu().numpy() if vocode else None
+        wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n,
+                                 lengths=model.lengths if vocode_lengths else None).cpu().numpy() if vocode else None
         spec, al = spec.cpu().numpy(), al.cpu().numpy()
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         for i in range(Bn):
@@ -117,11 +125,15 @@ if __name__ == '__main__':
     ap.add_argument('--end-offset', type=int, default=1, help='--stop: argmax target is character L - 1 - end_offset')
     ap.add_argument('--hold', type=int, default=4, help='--stop: consecutive steps at or past the target')
     ap.add_argument('--min-steps', type=int, default=8, help='--stop: steps before the rule may fire')
+    ap.add_argument('--vocode-lengths', action='store_true',
+                    help='--stop: Griffin-Lim over the frames of each prompt alone, phases drawn on the device')
     a = ap.parse_args()
+    if a.vocode_lengths and not a.stop:
+        ap.error('--vocode-lengths needs --stop')
     prompts = [p for p in sys.stdin.readlines() if len(p) > 0]
     c = Config()
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
     print('Building Tacotron')
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
-    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, stop=rule)
+    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, stop=rule, vocode_lengths=a.vocode_lengths)
