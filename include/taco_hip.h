@@ -289,6 +289,38 @@ int64_t taco_griffinlim_rows_workspace_bytes(int B, int F);     /* B > 0, F >= 5
 int taco_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
                          int frames_per_unit, float* wave, void* workspace, int B, int F, int n_iter, void* stream);
 
+/* Fast Griffin-Lim with a convergence readout (no reference counterpart beyond the loss audio.py:90-92 prints when verbose).
+ * The momentum update of Perraudin, Balazs and Sondergaard, "A fast Griffin-Lim algorithm" (WASPAA 2013).  Round
+ * i = 0 .. n_iter - 1, with M = |mag_t| and angles_0 from phase0 / the seed:
+ *     t_i = STFT(ISTFT(M * angles_i))                        (one round of the plain algorithm)
+ *     c_i = t_i for i = 0, else t_i + momentum * (t_i - t_{i-1})     per bin, complex, fp32
+ *     angles_{i+1} = c_i / |c_i|, and (1, 0) where c_i = 0
+ * and the waveform is ISTFT(M * angles_{n_iter}).  librosa's griffinlim(momentum = a) forms t_i - a / (1 + a) t_{i-1}, which is
+ * c_i / (1 + a): a positive factor per bin, so the phases are the same.  momentum = 0 is the plain algorithm.
+ *   mag_t, phase0 (nullable: device counter-hash phases from seed), wave, frames_per_unit, B, F, n_iter: exactly as for the
+ *          per-utterance entry point above
+ *   frames (B) int32 on the DEVICE, or NULL: every row then has F frames (one window table for the batch, as the plain entry
+ *          point); frames_per_unit is ignored then but must still be >= 1
+ *   momentum 0 <= momentum < 1
+ *   conv   (B, n_iter + 1) device floats, or NULL.  conv[b, i] = || |t_i| - M ||_F / || M ||_F over row b's own F_b frames x 1025
+ *          bins for i < n_iter (conv[b, 0] is that of the initial phases), and conv[b, n_iter] is the same quantity for
+ *          angles_{n_iter}: the spectral convergence of the RETURNED waveform (the STFT of the overlap-added signal that is written
+ *          out; one more analysis pass, run only when conv is given).  A row with F_b = 0 or || M || = 0 gets zeros.  Every element
+ *          is written
+ *   - momentum = 0: wave is bit-identical to the per-utterance entry point with the same arguments (frames given) and to the plain
+ *     one (frames NULL, phase0 given); n_iter <= 1: wave does not depend on momentum; wave does not depend on whether conv is given;
+ *   - the per-row contract above holds for every momentum, for wave and for row b of conv: bit-identical to a B = 1, F = F_b call
+ *     on that row's first F_b columns; zeros behind 300 (F_b - 1) samples; no FFT work for F_b < 5; columns t >= F_b may hold NaN;
+ *   - no atomics: the same arguments give the same bits in wave and conv.
+ * No allocation, no host synchronisation, nothing read from frames on the host: graph-capturable.  workspace:
+ * taco_griffinlim_fast_workspace_bytes bytes, 8-byte aligned, arbitrary contents (the per-utterance layout, a second spectrum
+ * (B, F, 1025, 2) and the readout's partial sums; independent of n_iter).  NULL mag_t / wave / workspace, B <= 0, F < 5, n_iter < 0,
+ * frames_per_unit < 1, momentum < 0, >= 1 or NaN return TACO_EINVAL before anything is enqueued.  TACO_VERSION did not change with
+ * these two entry points: detect them by the symbol. */
+int64_t taco_griffinlim_fast_workspace_bytes(int B, int F);      /* B > 0, F >= 5, else TACO_EINVAL */
+int taco_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
+                         float momentum, float* wave, float* conv, void* workspace, int B, int F, int n_iter, void* stream);
+
 /* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
 /* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length
  * 1200, hop_length 300, pre-emphasis 0.97, log(|.| + 1e-8), 80 mels): librosa.effects.trim (0.6 form: frame mean squares at

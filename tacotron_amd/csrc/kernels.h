@@ -426,6 +426,11 @@ int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, floa
 int64_t griffinlim_rows_workspace_floats(int B, int F);
 int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
                            float* wave, float* work, int B, int F, int n_iter, hipStream_t s);
+// fast Griffin-Lim (taco_hip.h taco_griffinlim_fast): momentum rounds and the per-round convergence readout; frames and conv
+// nullable; work: griffinlim_fast_workspace_floats floats (the rows layout, the previous spectrum, the readout's partial sums)
+int64_t griffinlim_fast_workspace_floats(int B, int F);
+int launch_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
+                           float momentum, float* wave, float* conv, float* work, int B, int F, int n_iter, hipStream_t s);
 
 // ---------------------------------------------------------------- features.hip
 // audio.process_audio (audio.py:38-65) for a batch: trim, drop / pad, pre-emphasis, STFT, mel, r-frame layout (taco_hip.h)

@@ -1750,6 +1750,18 @@ extern "C" int taco_griffinlim_rows(const float* mag_t, const float* phase0, uin
                                 as_stream(stream));
 }
 
+extern "C" int64_t taco_griffinlim_fast_workspace_bytes(int B, int F) {
+  if (B <= 0 || F < 5) return TACO_EINVAL;
+  return griffinlim_fast_workspace_floats(B, F) * (int64_t)sizeof(float);
+}
+
+extern "C" int taco_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
+                                    int frames_per_unit, float momentum, float* wave, float* conv, void* workspace, int B, int F,
+                                    int n_iter, void* stream) {
+  return launch_griffinlim_fast(mag_t, phase0, seed, frames, frames_per_unit, momentum, wave, conv, static_cast<float*>(workspace), B,
+                                F, n_iter, as_stream(stream));
+}
+
 extern "C" int64_t taco_audio_features_workspace_bytes(int B, int L) { return audio_features_workspace_bytes(B, L); }
 
 extern "C" int taco_audio_features(const float* wave, const int* wave_len, const float* mel_basis, void* mel, void* stft,

@@ -18,6 +18,13 @@
 // reflect padding, the overlap-add and the window normalisation; the addressing of mag_t, phases, segments and angles keeps the
 // pitch F.  A frame workgroup with t >= F_b returns at entry, before it builds its twiddle table: the grid stays (F, B) because
 // the host never learns the lengths, and the frames past a row's end cost one integer load and a compare.
+//
+// Fast Griffin-Lim (taco_griffinlim_fast; Perraudin, Balazs, Sondergaard 2013) and the convergence readout live in the epilogue of
+// the SAME analysis body, as template parameters: MOM keeps the previous round's spectrum t_{i-1} in a second (B, F, 1025, 2)
+// buffer and takes the phases of c_i = t_i + alpha (t_i - t_{i-1}); CONV reduces (|t_i[k]| - M[k])^2 over the frame's bins in a
+// fixed order (wave butterfly, then the four wave sums in LDS) into a (B, F) scratch that gl_conv_kernel sums per row, again in
+// an order that depends on F_b alone; WRITE = false is the readout's own last pass, which stores no angles.  The instantiation
+// <false, false, true> is the body both older entry points launch; alpha = 0 launches it as well.
 #include <algorithm>
 
 #include "common.h"
@@ -71,6 +78,16 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {   // as elementwise
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
   x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
   return x ^ (x >> 31);
+}
+
+// sum of v over the 256 threads of the workgroup in a fixed order, returned to every thread: xor butterfly inside each wave, then
+// the four wave sums through sh (4 floats of LDS nobody else touches until the next barrier)
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 // frames of row b: F without a frames array, else min(F, frames[b] * per_unit); a row below 5 frames (the reflect padding of
@@ -171,9 +188,20 @@ __device__ __forceinline__ float ola_sample(const float* __restrict__ seg_b, con
   return w > 1.17549435e-38f ? acc / w : acc;
 }
 
+// momentum / readout arguments of gl_anal_kernel (unused ones are null / 0)
+struct GlExtra {
+  float* tprev;         // MOM: (B, F, NBIN, 2) spectrum of the previous round, interleaved like ang
+  float alpha;          // MOM: momentum
+  int read_prev;        // MOM: 0 in round 0 (the buffer holds nothing yet and is not read)
+  int write_prev;       // MOM: 0 in the last round (nobody reads it)
+  const float* mag_t;   // CONV: the magnitudes (B, NBIN, F)
+  float* part;          // CONV: (B, F) sum over the frame's bins of (|t[k]| - M[k])^2
+};
+
+template <bool MOM, bool CONV, bool WRITE>
 __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ seg, const float* __restrict__ wss,
                                                      int64_t wss_pitch, float* __restrict__ ang, int Fp,
-                                                     const int32_t* __restrict__ frames, int per_unit) {
+                                                     const int32_t* __restrict__ frames, int per_unit, GlExtra x) {
   __shared__ float re[NFFT], im[NFFT], twr[NFFT / 2], twi[NFFT / 2];
   const int t = blockIdx.x, b = blockIdx.y;
   const int F = row_frames(frames, per_unit, b, Fp);   // frames of this row; Fp = the pitch
@@ -197,18 +225,80 @@ __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ s
   }
   fft2048(re, im, twr, twi, -1.0f);
   float* a = ang + ((int64_t)b * Fp + t) * NBIN * 2;
+  float dev2 = 0.f;
   for (int k = threadIdx.x; k < NBIN; k += FT) {
-    const float xr = re[k], xi = im[k];
-    const float n2 = xr * xr + xi * xi;
-    float c = 1.f, s = 0.f;   // np.angle(0) = 0
-    if (n2 > 0.f) {
-      const float inv = rsqrtf(n2);
-      c = xr * inv;
-      s = xi * inv;
+    float xr = re[k], xi = im[k];
+    if constexpr (CONV) {
+      const float d = sqrtf(xr * xr + xi * xi) - fabsf(x.mag_t[((int64_t)b * NBIN + k) * Fp + t]);
+      dev2 += d * d;
     }
-    a[2 * k] = c;
-    a[2 * k + 1] = s;
+    if constexpr (MOM) {   // c = t + alpha (t - t_prev); t takes t_prev's place
+      float2* p = reinterpret_cast<float2*>(x.tprev + ((int64_t)b * Fp + t) * NBIN * 2) + k;
+      const float tr = xr, ti = xi;
+      if (x.read_prev) {
+        const float2 pv = *p;
+        xr = tr + x.alpha * (tr - pv.x);
+        xi = ti + x.alpha * (ti - pv.y);
+      }
+      if (x.write_prev) *p = make_float2(tr, ti);
+    }
+    if constexpr (WRITE) {
+      const float n2 = xr * xr + xi * xi;
+      float c = 1.f, s = 0.f;   // np.angle(0) = 0
+      if (n2 > 0.f) {
+        const float inv = rsqrtf(n2);
+        c = xr * inv;
+        s = xi * inv;
+      }
+      a[2 * k] = c;
+      a[2 * k + 1] = s;
+    }
   }
+  if constexpr (CONV) {   // (the twiddle table is dead after the FFT's last barrier: its first floats carry the wave sums)
+    const float tot = block_sum(dev2, twr);
+    if (threadIdx.x == 0) x.part[(int64_t)b * Fp + t] = tot;
+  }
+}
+
+// mpart (B, F) <- sum over the bins of M[k]^2 of frame t < F_b (once per call, for the readout's denominator)
+__global__ __launch_bounds__(FT) void gl_magsq_kernel(const float* __restrict__ mag_t, float* __restrict__ mpart, int F,
+                                                      const int32_t* __restrict__ frames, int per_unit) {
+  __shared__ float sh[4];
+  const int t = blockIdx.x, b = blockIdx.y;
+  if (t >= row_frames(frames, per_unit, b, F)) return;
+  const float* m = mag_t + (int64_t)b * NBIN * F + t;
+  float acc = 0.f;
+  for (int k = threadIdx.x; k < NBIN; k += FT) {
+    const float v = m[(int64_t)k * F];
+    acc += v * v;
+  }
+  const float tot = block_sum(acc, sh);
+  if (threadIdx.x == 0) mpart[(int64_t)b * F + t] = tot;
+}
+
+// conv[b, col] <- sqrt(sum_t part[b, t] / sum_t mpart[b, t]) over the row's F_b frames, 0 for a row without frames or magnitudes.
+// Thread j sums the frames j, j + 256, ... and block_sum the threads: the order depends on F_b alone.  first: sum mpart into
+// msq[b]; later rounds read it back.
+__global__ __launch_bounds__(FT) void gl_conv_kernel(const float* __restrict__ part, const float* __restrict__ mpart,
+                                                     float* __restrict__ msq, float* __restrict__ conv, int col, int ncol, int Fp,
+                                                     const int32_t* __restrict__ frames, int per_unit, int first) {
+  __shared__ float sh[8];
+  const int b = blockIdx.x;
+  const int F = row_frames(frames, per_unit, b, Fp);
+  float acc = 0.f, macc = 0.f;
+  for (int t = threadIdx.x; t < F; t += FT) {
+    acc += part[(int64_t)b * Fp + t];
+    if (first) macc += mpart[(int64_t)b * Fp + t];
+  }
+  const float num = block_sum(acc, sh);
+  float den;
+  if (first) {
+    den = block_sum(macc, sh + 4);
+    if (threadIdx.x == 0) msq[b] = den;
+  } else {
+    den = msq[b];
+  }
+  if (threadIdx.x == 0) conv[(int64_t)b * ncol + col] = (F > 0 && den > 0.f) ? sqrtf(num / den) : 0.f;
 }
 
 // every sample of the row: the overlap-add below HOP (F_b - 1), 0 from there on
@@ -234,23 +324,53 @@ int64_t griffinlim_rows_workspace_floats(int B, int F) {   // one window sum-of-
   return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (int64_t)B * (NFFT + (int64_t)HOP * (F - 1)) + 64;
 }
 
-// the launches of both entry points.  frames == nullptr: every row has F frames and one window table serves the batch
+// the rows layout (without its 64 floats of slack), then the previous spectrum, the two (B, F) partial-sum tables, ||M||^2 per row
+static int64_t griffinlim_fast_offset(int B, int F) { return griffinlim_rows_workspace_floats(B, F) - 64; }
+int64_t griffinlim_fast_workspace_floats(int B, int F) {
+  return griffinlim_fast_offset(B, F) + (int64_t)B * F * NBIN * 2 + 2 * (int64_t)B * F + B + 64;
+}
+
+// the launches of all three entry points.  frames == nullptr: every row has F frames and one window table serves the batch.
+// alpha > 0: momentum rounds with the previous spectrum in `tprev`; conv != nullptr: the readout, (B, n_iter + 1), with its
+// scratch in `red` (2 B F + B floats).  alpha == 0 and conv == nullptr are the launches of taco_griffinlim / taco_griffinlim_rows.
 static int griffinlim_launches(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int per_unit,
-                               float* wave, float* work, int B, int F, int n_iter, hipStream_t s) {
+                               float* wave, float* work, int B, int F, int n_iter, hipStream_t s, float alpha = 0.f,
+                               float* conv = nullptr, float* tprev = nullptr, float* red = nullptr) {
   float* ang = work;
   float* seg = ang + (int64_t)B * F * NBIN * 2;
   float* wss = seg + (int64_t)B * F * WIN;
   const int n = NFFT + HOP * (F - 1);
   const int64_t wss_pitch = frames ? n : 0;
+  const bool mom = alpha > 0.f;
+  GlExtra x{mom ? tprev : nullptr, alpha, 0, 0, mag_t, red};
+  float* mpart = red ? red + (int64_t)B * F : nullptr;
+  float* msq = red ? mpart + (int64_t)B * F : nullptr;
   TACO_KLAUNCH(gl_wss_kernel, dim3((n + 255) / 256, frames ? B : 1), dim3(256), 0, s, wss, wss_pitch, F, frames, per_unit);
   const int64_t total = (int64_t)B * F * NBIN;
   TACO_KLAUNCH(gl_init_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, phase0, seed, ang, F,
                      total, frames, per_unit);
+  if (conv) TACO_KLAUNCH(gl_magsq_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, mpart, F, frames, per_unit);
   for (int it = 0; it < n_iter; ++it) {
     TACO_KLAUNCH(gl_synth_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, ang, seg, F, frames, per_unit);
-    TACO_KLAUNCH(gl_anal_kernel, dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit);
+    x.read_prev = it > 0;
+    x.write_prev = it < n_iter - 1;
+    if (mom && conv)
+      TACO_KLAUNCH((gl_anal_kernel<true, true, true>), dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit, x);
+    else if (mom)
+      TACO_KLAUNCH((gl_anal_kernel<true, false, true>), dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit, x);
+    else if (conv)
+      TACO_KLAUNCH((gl_anal_kernel<false, true, true>), dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit, x);
+    else
+      TACO_KLAUNCH((gl_anal_kernel<false, false, true>), dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit, x);
+    if (conv)
+      TACO_KLAUNCH(gl_conv_kernel, dim3(B), dim3(FT), 0, s, red, mpart, msq, conv, it, n_iter + 1, F, frames, per_unit, (int)(it == 0));
   }
   TACO_KLAUNCH(gl_synth_kernel, dim3(F, B), dim3(FT), 0, s, mag_t, ang, seg, F, frames, per_unit);
+  if (conv) {   // the readout of the returned waveform: one more analysis pass that stores no angles
+    TACO_KLAUNCH((gl_anal_kernel<false, true, false>), dim3(F, B), dim3(FT), 0, s, seg, wss, wss_pitch, ang, F, frames, per_unit, x);
+    TACO_KLAUNCH(gl_conv_kernel, dim3(B), dim3(FT), 0, s, red, mpart, msq, conv, n_iter, n_iter + 1, F, frames, per_unit,
+                 (int)(n_iter == 0));
+  }
   TACO_KLAUNCH(gl_wave_kernel, dim3((HOP * (F - 1) + 255) / 256, B), dim3(256), 0, s, seg, wss, wss_pitch, wave, F, frames, per_unit);
   return TACO_OK;
 }
@@ -270,5 +390,18 @@ int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t see
   TACO_REQUIRE(F >= 5, "griffinlim_rows: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
   griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, s);
   TACO_LAUNCH_CHECK("griffinlim_rows");
+  return TACO_OK;
+}
+
+int launch_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
+                           float momentum, float* wave, float* conv, float* work, int B, int F, int n_iter, hipStream_t s) {
+  TACO_REQUIRE(mag_t && wave && work && B > 0 && n_iter >= 0 && frames_per_unit >= 1, "griffinlim_fast: bad arguments");
+  TACO_REQUIRE(momentum >= 0.f && momentum < 1.f, "griffinlim_fast: momentum %g is not in [0, 1)", (double)momentum);   // (NaN fails)
+  TACO_REQUIRE(F >= 5, "griffinlim_fast: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
+  TACO_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7) == 0, "griffinlim_fast: workspace is not 8-byte aligned");
+  float* tprev = work + griffinlim_fast_offset(B, F);
+  float* red = tprev + (int64_t)B * F * NBIN * 2;
+  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, s, momentum, conv, tprev, red);
+  TACO_LAUNCH_CHECK("griffinlim_fast");
   return TACO_OK;
 }

@@ -8,7 +8,10 @@ np.random.rand; here it comes from a seeded torch generator so that a run can be
 
 With `lengths` (the per-row decoder steps `Tacotron.run(stop=rule)` leaves on the device) every row is vocoded over its own
 len_b r frames (taco_griffinlim_rows): the Griffin-Lim of that prompt alone, zeros behind it, and -- unless the caller gives
-phase0 -- initial phases from the library's counter-hash generator: no host random numbers, no upload, nothing read back."""
+phase0 -- initial phases from the library's counter-hash generator: no host random numbers, no upload, nothing read back.
+
+With `momentum` (opt-in) the rounds are those of the fast Griffin-Lim algorithm (taco_griffinlim_fast), and `want_conv` returns the
+per-round spectral convergence next to the waveform."""
 from __future__ import annotations
 
 import math
@@ -19,13 +22,25 @@ from . import lib
 
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
-                       lengths=None):
+                       lengths=None, momentum=None, want_conv=False):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
-    lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats."""
+    lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
+    momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
+    Balazs and Sondergaard (lib.griffinlim_fast; 0.99 is librosa's default), with `lengths` or without; work then holds
+    lib.griffinlim_fast_workspace_floats.  Without phase0 the phases of that path ALWAYS come from the device's counter-hash
+    generator (seeded by `seed`; no host draw, no upload) -- not the torch-generator phases of the momentum=None path without
+    lengths, so the same seed gives another waveform there.
+    want_conv (needs momentum): returns (waveform, conv (B, n_iter + 1)), the spectral convergence in front of every round and of
+    the waveform returned (include/taco_hip.h)."""
+    if want_conv and momentum is None:
+        raise ValueError('invert_spectrogram: want_conv needs momentum (0 for the plain rounds)')
     dev = out.device
     mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
+    if momentum is not None:
+        return lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
+                                   momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work)
     if lengths is not None:
         return lib.griffinlim_rows(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
                                    frames_per_unit=r, out=wave, work=work)

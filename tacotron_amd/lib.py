@@ -113,6 +113,8 @@ EXPORTS = {
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'taco_griffinlim_rows_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim_rows': (C.c_int, [_P, _P, C.c_uint64, _P, _I, _P, _P, _I, _I, _I, _P]),
+    'taco_griffinlim_fast_workspace_bytes': (C.c_int64, [_I, _I]),
+    'taco_griffinlim_fast': (C.c_int, [_P, _P, C.c_uint64, _P, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_fill_bernoulli': (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
@@ -440,6 +442,50 @@ def griffinlim_rows(mag_t, frames, phase0=None, seed=0, n_iter=50, frames_per_un
     _check(_lib.taco_griffinlim_rows(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), int(frames_per_unit),
                                      ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()), 'taco_griffinlim_rows')
     return wave
+
+
+def griffinlim_fast_workspace_floats(B, F) -> int:
+    nbytes = _lib.taco_griffinlim_fast_workspace_bytes(int(B), int(F))
+    if nbytes < 0:
+        raise TacoError('taco_griffinlim_fast_workspace_bytes: bad shape')
+    return nbytes // 4
+
+
+def griffinlim_fast(mag_t, frames=None, phase0=None, seed=0, n_iter=50, momentum=0.99, frames_per_unit=1, want_conv=False,
+                    out=None, conv=None, work=None):
+    """Fast Griffin-Lim (include/taco_hip.h taco_griffinlim_fast): mag_t (B, 1025, F) -> waveform (B, 300 (F - 1)), or with
+    want_conv (waveform, conv (B, n_iter + 1)): the spectral convergence in front of every round and, last, of the waveform
+    returned.  momentum in [0, 1): 0 is the plain algorithm.  frames (B) int32 on the device, or None: every row has F frames.
+    phase0 (B, 1025, F) initial angles, or None: seeded phases drawn on the device.  out / conv / work: the caller's own buffers
+    (work: griffinlim_fast_workspace_floats(B, F) floats); default: fresh ones.  A conv buffer implies want_conv."""
+    if mag_t.dim() != 3 or mag_t.shape[1] != 1025 or mag_t.dtype != torch.float32:
+        raise ValueError('griffinlim_fast: mag_t must be a float32 tensor of shape (B, 1025, F), got %s %s' % (mag_t.dtype, tuple(mag_t.shape)))
+    B, _, F = mag_t.shape
+    dev = mag_t.device
+    if frames is not None and (tuple(frames.shape) != (B,) or frames.dtype != torch.int32 or frames.device != dev):
+        raise ValueError('griffinlim_fast: frames must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
+                         % (B, dev, frames.dtype, tuple(frames.shape), frames.device))
+    if phase0 is not None and (phase0.shape != mag_t.shape or phase0.dtype != torch.float32 or phase0.device != dev):
+        raise ValueError('griffinlim_fast: phase0 must be a float32 tensor of shape %s on %s' % (tuple(mag_t.shape), dev))
+    if int(frames_per_unit) < 1 or int(n_iter) < 0:
+        raise ValueError('griffinlim_fast: frames_per_unit >= 1 and n_iter >= 0, got %d and %d' % (frames_per_unit, n_iter))
+    momentum = float(momentum)
+    if not 0.0 <= momentum < 1.0:   # (NaN fails both comparisons)
+        raise ValueError('griffinlim_fast: momentum must be in [0, 1), got %r' % momentum)
+    if C.c_float(momentum).value >= 1.0:
+        raise ValueError('griffinlim_fast: momentum %r rounds to 1 in float32' % momentum)
+    want_conv = bool(want_conv) or conv is not None
+    n_iter = int(n_iter)
+    nbytes = _lib.taco_griffinlim_fast_workspace_bytes(B, F)
+    if nbytes < 0:
+        raise TacoError('taco_griffinlim_fast_workspace_bytes: bad shape (B=%d, F=%d)' % (B, F))
+    nwork = nbytes // 4
+    work = _own_or_given(work, (nwork,), torch.float32, dev, 'griffinlim_fast: work')
+    wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, dev, 'griffinlim_fast: out')
+    conv = _own_or_given(conv, (B, n_iter + 1), torch.float32, dev, 'griffinlim_fast: conv') if want_conv else None
+    _check(_lib.taco_griffinlim_fast(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), int(frames_per_unit),
+                                     momentum, ptr(wave), ptr(conv), ptr(work), B, F, n_iter, stream_ptr()), 'taco_griffinlim_fast')
+    return (wave, conv) if want_conv else wave
 
 
 def audio_features_workspace_bytes(B, L) -> int:

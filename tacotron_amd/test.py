@@ -6,7 +6,10 @@ reference's sr) next to the de-normalised spectrogram and the alignment as .npy.
 --stop (opt-in, not in the reference): end detection on the attention (lib.TacoStopRule, include/taco_hip.h); each prompt's
 files are cut to its len_b decoder steps and prompt_NNN_len.npy holds len_b.  The rule's defaults are not tuned on a trained model.
 --vocode-lengths (opt-in, with --stop): Griffin-Lim runs per prompt over its own len_b r frames (lib.griffinlim_rows) with phases
-drawn on the device, so prompt_NNN.wav is the Griffin-Lim of that prompt alone."""
+drawn on the device, so prompt_NNN.wav is the Griffin-Lim of that prompt alone.
+--gl-momentum A (opt-in, not in the reference): fast Griffin-Lim rounds with momentum A in [0, 1) (lib.griffinlim_fast), phases drawn
+on the device; prompt_NNN_conv.npy holds the prompt's n_iter + 1 spectral-convergence values and the batch's worst final value is
+printed.  --gl-iters N: the number of rounds (default 50, the reference's).  Both combine with --stop / --vocode-lengths."""
 from __future__ import annotations
 
 import argparse
@@ -41,7 +44,8 @@ def write_wav(path, samples, sr=SR):
         f.writeframes((x * 32767.0).astype('<i2').tobytes())
 
 
-def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False):
+def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
+         gl_momentum=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -52,9 +56,15 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     (the vocoder still runs over the full, zero-filled length); len_b goes to prompt_NNN_len.npy.
     `vocode_lengths` (needs `stop`): the vocoder gets model.lengths and runs over each prompt's own frames only; the files keep
     their sizes, the samples are the Griffin-Lim of that prompt alone, from phases drawn on the device (seed = index of the batch's
-    first prompt)."""
+    first prompt).
+    `gl_momentum`: None, or the momentum of the fast Griffin-Lim rounds; prompt_NNN_conv.npy then holds the n_iter + 1 convergence
+    values of the prompt (over the frames the vocoder ran on: the prompt's own with `vocode_lengths`, else the full length)."""
     if vocode_lengths and stop is None:
         raise ValueError('test: vocode_lengths needs a stop rule (the lengths come from taco_infer_stop)')
+    if gl_momentum is not None and not 0.0 <= float(gl_momentum) < 1.0:
+        raise ValueError('test: gl_momentum must be in [0, 1), got %r' % (gl_momentum,))
+    if int(n_iter) < 0:
+        raise ValueError('test: n_iter must be >= 0, got %r' % (n_iter,))
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
         with open(meta_path, 'rb') as f:
@@ -93,8 +103,16 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n,
-                                 lengths=model.lengths if vocode_lengths else None).cpu().numpy() if vocode else None
+        conv = None
+        if vocode and gl_momentum is not None:
+            wav, conv = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum, want_conv=True,
+                                           lengths=model.lengths if vocode_lengths else None)
+            wav, conv = wav.cpu().numpy(), conv.cpu().numpy()
+            print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
+                  % (gl_momentum, n_iter, float(conv[:, -1].max())))
+        else:
+            wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n,
+                                     lengths=model.lengths if vocode_lengths else None).cpu().numpy() if vocode else None
         spec, al = spec.cpu().numpy(), al.cpu().numpy()
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         for i in range(Bn):
@@ -110,12 +128,14 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             np.save(os.path.join(out_dir, 'prompt_%03d_align.npy' % n), ai)
             if wi is not None:
                 write_wav(os.path.join(out_dir, 'prompt_%03d.wav' % n), wi)
+            if conv is not None:
+                np.save(os.path.join(out_dir, 'prompt_%03d_conv.npy' % n), conv[i])
             n += 1
     print('wrote %d samples to %s' % (n, out_dir))
     return n
 
 
-if __name__ == '__main__':
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('-t', '--train-set', default='nancy')
     ap.add_argument('--checkpoint', default=None)
@@ -127,13 +147,26 @@ if __name__ == '__main__':
     ap.add_argument('--min-steps', type=int, default=8, help='--stop: steps before the rule may fire')
     ap.add_argument('--vocode-lengths', action='store_true',
                     help='--stop: Griffin-Lim over the frames of each prompt alone, phases drawn on the device')
-    a = ap.parse_args()
+    ap.add_argument('--gl-momentum', type=float, default=None,
+                    help='fast Griffin-Lim rounds with this momentum in [0, 1) (0.99: librosa\'s default); writes prompt_NNN_conv.npy')
+    ap.add_argument('--gl-iters', type=int, default=50, help='Griffin-Lim rounds (the reference: 50)')
+    a = ap.parse_args(argv)
     if a.vocode_lengths and not a.stop:
         ap.error('--vocode-lengths needs --stop')
+    if a.gl_iters < 0:
+        ap.error('--gl-iters must be >= 0')
+    if a.gl_momentum is not None and not 0.0 <= a.gl_momentum < 1.0:
+        ap.error('--gl-momentum must be in [0, 1)')
+    return a
+
+
+if __name__ == '__main__':
+    a = parse_args()
     prompts = [p for p in sys.stdin.readlines() if len(p) > 0]
     c = Config()
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
     print('Building Tacotron')
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
-    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, stop=rule, vocode_lengths=a.vocode_lengths)
+    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
+         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum)
