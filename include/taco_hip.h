@@ -321,6 +321,42 @@ int64_t taco_griffinlim_fast_workspace_bytes(int B, int F);      /* B > 0, F >= 
 int taco_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
                          float momentum, float* wave, float* conv, void* workspace, int B, int F, int n_iter, void* stream);
 
+/* Waveform finishing (no reference counterpart: the reference writes the pre-emphasised Griffin-Lim signal as it is,
+ * audio.py:67-74).  Undoes the front end's pre-emphasis, optionally cuts leading / trailing silence by the front end's energy
+ * rule, and emits fp32 samples and / or PCM16 by write_wav's rule, so that what leaves the device is finished audio.
+ *   wave    (B, L) fp32: what the three Griffin-Lim entry points write, L = 300 (F - 1)
+ *   samples (B) int32 on the DEVICE, or NULL: n_b = clamp(samples[b], 0, L); NULL: n_b = L.  The host reads nothing from it
+ *   deemphasis  a in [0, 1);  trim_top_db >= 0 (0: no trim)
+ *   out     (B, L) fp32, nullable;  pcm (B, L) int16, nullable; at least one of the two
+ *   bounds  (B, 2) int32 and peak (B) fp32, both required
+ * Per row b, in this order:
+ *   1. de-emphasis  y[0] = x[0], y[n] = x[n] + a y[n-1] for n < n_b: the inverse of e[n] = y[n] - a y[n-1].  a == 0 gives y = x
+ *      bit for bit.  Evaluated as a scan of the maps c -> a c + x[n] over chunks of 2048 samples at fixed positions of the row;
+ *      the lag-k term a^k x[n-k] passes through at most 2k + 16 roundings, so
+ *      |y - y_exact|[n] <= 2^-24 (16 S[n] + 2 T[n]) to first order, S[n] = |x[n]| + a S[n-1], T[n] = a (T[n-1] + S[n-1])
+ *   2. trim (trim_top_db > 0)  mean squares of frames of 2048 samples at hop 512 over y[0 : n_b] reflect-padded by 1024
+ *      (1 + n_b / 512 frames); a frame is kept when 10 log10(max(1e-10, ms)) - 10 log10(max(1e-10, max ms)) > -trim_top_db;
+ *      s_b = 512 first, e_b = min(n_b, 512 (last + 1)) -- librosa.effects.trim as taco_audio_features applies it with 60 dB.  An
+ *      all-zero row is all 0 dB and is not trimmed.  trim_top_db == 0: [s_b, e_b) = [0, n_b); n_b == 0: [0, 0).
+ *      bounds[b] = (s_b, e_b)
+ *   3. peak[b] = max |y[n]| over [s_b, e_b) (exact); 0 for an empty range
+ *   4. out[b, i] = y[s_b + i] for i < e_b - s_b, exactly 0 behind;  pcm[b, i] = (int16) trunc(v * 32767.0f) with
+ *      v = peak_b > 1 ? y / peak_b : y -- one IEEE fp32 division, one rounded fp32 multiply (no contraction) -- and 0 behind
+ *   - every element of out, pcm, bounds and peak is written and nothing outside them; the workspace may hold arbitrary bytes;
+ *   - no atomics: the same arguments give the same bits;
+ *   - row b of a B-row call is bit-identical to a B = 1, L = n_b call on a contiguous copy of x[b, 0 : n_b] (n_b >= 1): bounds,
+ *     peak and the first n_b elements of out and pcm;
+ *   - samples x[b, n >= n_b] have no influence on anything (they may hold NaN); non-finite samples inside n_b do not fault, the
+ *     row's values are then unspecified.
+ * No allocation, no host synchronisation, no workgroup waits for another one: one stream-ordered enqueue, graph-capturable.
+ * workspace: taco_wave_finish_workspace_bytes bytes (y, the chunk aggregates, block maxima and frame energies).  NULL wave /
+ * bounds / peak / workspace, out and pcm both NULL, out == wave, B <= 0, L <= 0, deemphasis < 0, >= 1 or NaN, trim_top_db < 0 or
+ * NaN return TACO_EINVAL before anything is enqueued.  TACO_VERSION did not change with these two entry points: detect them by the
+ * symbol. */
+int64_t taco_wave_finish_workspace_bytes(int B, int L);          /* B > 0, L > 0, else TACO_EINVAL */
+int taco_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out, int16_t* pcm,
+                     int32_t* bounds, float* peak, void* workspace, int B, int L, void* stream);
+
 /* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
 /* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length
  * 1200, hop_length 300, pre-emphasis 0.97, log(|.| + 1e-8), 80 mels): librosa.effects.trim (0.6 form: frame mean squares at

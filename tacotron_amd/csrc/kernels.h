@@ -431,6 +431,11 @@ int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t see
 int64_t griffinlim_fast_workspace_floats(int B, int F);
 int launch_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
                            float momentum, float* wave, float* conv, float* work, int B, int F, int n_iter, hipStream_t s);
+// waveform finishing (taco_hip.h taco_wave_finish): de-emphasis scan, energy trim, peak, fp32 / PCM16 emit; samples, out, pcm
+// nullable (not both of out and pcm); work: wave_finish_workspace_floats floats
+int64_t wave_finish_workspace_floats(int B, int L);
+int launch_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out, int16_t* pcm,
+                       int32_t* bounds, float* peak, void* workspace, int B, int L, hipStream_t s);
 
 // ---------------------------------------------------------------- features.hip
 // audio.process_audio (audio.py:38-65) for a batch: trim, drop / pad, pre-emphasis, STFT, mel, r-frame layout (taco_hip.h)

@@ -1762,6 +1762,16 @@ extern "C" int taco_griffinlim_fast(const float* mag_t, const float* phase0, uin
                                 F, n_iter, as_stream(stream));
 }
 
+extern "C" int64_t taco_wave_finish_workspace_bytes(int B, int L) {
+  if (B <= 0 || L <= 0) return TACO_EINVAL;
+  return wave_finish_workspace_floats(B, L) * (int64_t)sizeof(float);
+}
+
+extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out,
+                                int16_t* pcm, int32_t* bounds, float* peak, void* workspace, int B, int L, void* stream) {
+  return launch_wave_finish(wave, samples, deemphasis, trim_top_db, out, pcm, bounds, peak, workspace, B, L, as_stream(stream));
+}
+
 extern "C" int64_t taco_audio_features_workspace_bytes(int B, int L) { return audio_features_workspace_bytes(B, L); }
 
 extern "C" int taco_audio_features(const float* wave, const int* wave_len, const float* mel_basis, void* mel, void* stft,

@@ -25,6 +25,9 @@
 // fixed order (wave butterfly, then the four wave sums in LDS) into a (B, F) scratch that gl_conv_kernel sums per row, again in
 // an order that depends on F_b alone; WRITE = false is the readout's own last pass, which stores no angles.  The instantiation
 // <false, false, true> is the body both older entry points launch; alpha = 0 launches it as well.
+//
+// Waveform finishing (taco_wave_finish) follows the Griffin-Lim kernels below: the de-emphasis scan, the energy trim, the peak and
+// the fp32 / PCM16 emit of the waveform gl_wave_kernel wrote.
 #include <algorithm>
 
 #include "common.h"
@@ -314,6 +317,229 @@ __global__ void gl_wave_kernel(const float* __restrict__ seg, const float* __res
     wave[(int64_t)b * L + i] = i < Lb ? ola_sample(sb, wss, i + NFFT / 2, F) : 0.f;
 }
 
+// ---- waveform finishing (taco_hip.h taco_wave_finish): de-emphasis, energy trim, peak, fp32 / PCM16 emit ---------------------
+// y[n] = x[n] + a y[n-1] is a first-order linear scan: sample n is the map c -> a c + x[n], and maps compose as
+// (A, B) o (A', B') = (A A', B' + A' B).  A row is cut into chunks of WF_CHUNK samples at FIXED positions (chunk c = samples
+// [2048 c, 2048 c + 2048) of the row, whatever B and L are), one workgroup per chunk:
+//   wf_scan<true>   the chunk's end value from a zero carry, into the workspace (only chunks that have a successor)
+//   wf_scan<false>  the carry into chunk c rebuilt from the aggregates 0 .. c-1 in order (c fused multiply-adds with a^2048, formed
+//                   by eleven squarings -- nothing assumes that it underflows), the scan again, y and max |y| of every 512 samples
+//                   (one wave's share) into the workspace
+//   wf_ms           mean square of the trim frames of y (one wave per frame), only with a trim
+//   wf_bounds       one workgroup per row: the bounds from the frame energies, the peak from the 512-sample maxima
+//   wf_emit         out / pcm shifted by the row's start
+// No workgroup waits for another one inside a launch; the order of every sum depends on the position in the row and n_b alone.
+constexpr int WF_T = 256, WF_PER = 8, WF_CHUNK = WF_T * WF_PER;
+constexpr int WF_TRIM_FRAME = 2048, WF_TRIM_HOP = 512;
+constexpr int WF_BT = 512;   // wf_bounds block
+
+__device__ __forceinline__ int wf_len(const int32_t* __restrict__ samples, int b, int L) {
+  if (!samples) return L;
+  const int n = samples[b];
+  return n < 0 ? 0 : (n > L ? L : n);
+}
+
+// numpy.pad(mode='reflect') index for any pad width (period 2 (n - 1)); as features.hip
+__device__ __forceinline__ int wf_reflect(int64_t p, int64_t n) {
+  if (n <= 1) return 0;
+  const int64_t per = 2 * (n - 1);
+  int64_t q = p % per;
+  if (q < 0) q += per;
+  return (int)(q >= n ? per - q : q);
+}
+
+template <bool AGG>
+__global__ __launch_bounds__(WF_T) void wf_scan_kernel(const float* __restrict__ wave, const int32_t* __restrict__ samples, float a,
+                                                       float* __restrict__ y_all, int64_t y_pitch, float* __restrict__ agg_all,
+                                                       int nch, float* __restrict__ pm_all, int npm, int L) {
+  __shared__ float shA[WF_T / 64], shB[WF_T / 64];
+  const int c = blockIdx.x, b = blockIdx.y;
+  const int n = wf_len(samples, b, L);
+  const int64_t base = (int64_t)c * WF_CHUNK;
+  if (AGG ? base + WF_CHUNK >= n : base >= n) return;   // (the whole workgroup) AGG: nobody reads the last chunk's aggregate
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float* x = wave + (int64_t)b * L;
+  const int64_t i0 = base + (int64_t)threadIdx.x * WF_PER;
+  float v[WF_PER];
+  if (i0 + WF_PER <= n && (reinterpret_cast<uintptr_t>(x + i0) & 15) == 0) {
+    const float4 p = *reinterpret_cast<const float4*>(x + i0), q = *reinterpret_cast<const float4*>(x + i0 + 4);
+    v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = p.w;
+    v[4] = q.x; v[5] = q.y; v[6] = q.z; v[7] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < WF_PER; ++j) v[j] = i0 + j < n ? x[i0 + j] : 0.f;   // (samples from n_b on are never read)
+  }
+  float y[WF_PER];
+  if (a == 0.f) {   // y = x bit for bit (a fused multiply-add with 0 would turn -0 into +0)
+#pragma unroll
+    for (int j = 0; j < WF_PER; ++j) y[j] = v[j];
+  } else {
+    // the thread's own samples from a zero carry, and a^(j+1)
+    float pw[WF_PER];
+    y[0] = v[0];
+    pw[0] = a;
+#pragma unroll
+    for (int j = 1; j < WF_PER; ++j) {
+      y[j] = fmaf(a, y[j - 1], v[j]);
+      pw[j] = __fmul_rn(pw[j - 1], a);
+    }
+    // inclusive scan of the threads' maps (A, Bv) over the wave: the later map's A multiplies the earlier map's end value
+    float A = pw[WF_PER - 1], Bv = y[WF_PER - 1];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float Ap = __shfl_up(A, d), Bp = __shfl_up(Bv, d);
+      if (lane >= d) {
+        Bv = fmaf(A, Bp, Bv);
+        A = __fmul_rn(A, Ap);
+      }
+    }
+    float Aex = __shfl_up(A, 1), Bex = __shfl_up(Bv, 1);
+    if (lane == 0) {
+      Aex = 1.f;
+      Bex = 0.f;
+    }
+    if (lane == 63) {
+      shA[w] = A;
+      shB[w] = Bv;
+    }
+    __syncthreads();
+    float carry = 0.f;   // y[base - 1]
+    if (!AGG) {
+      float a2k = a;
+#pragma unroll
+      for (int k = 0; k < 11; ++k) a2k = __fmul_rn(a2k, a2k);   // a^2048
+      const float* agg = agg_all + (int64_t)b * nch;
+      for (int k = 0; k < c; ++k) carry = fmaf(a2k, carry, agg[k]);
+    }
+    for (int k = 0; k < w; ++k) carry = fmaf(shA[k], carry, shB[k]);   // ... the end value of the wave in front
+    const float E = fmaf(Aex, carry, Bex);                              // ... of the thread in front
+#pragma unroll
+    for (int j = 0; j < WF_PER; ++j) y[j] = fmaf(pw[j], E, y[j]);
+  }
+  if (AGG) {
+    if (threadIdx.x == WF_T - 1) agg_all[(int64_t)b * nch + c] = y[WF_PER - 1];
+    return;
+  }
+  float* yo = y_all + (int64_t)b * y_pitch + i0;   // (16-byte aligned: the pitch is a multiple of 4 floats, i0 of 8)
+  float m = 0.f;
+  if (i0 + WF_PER <= n) {
+    *reinterpret_cast<float4*>(yo) = make_float4(y[0], y[1], y[2], y[3]);
+    *reinterpret_cast<float4*>(yo + 4) = make_float4(y[4], y[5], y[6], y[7]);
+#pragma unroll
+    for (int j = 0; j < WF_PER; ++j) m = fmaxf(m, fabsf(y[j]));
+  } else {
+#pragma unroll
+    for (int j = 0; j < WF_PER; ++j)
+      if (i0 + j < n) {
+        yo[j] = y[j];
+        m = fmaxf(m, fabsf(y[j]));
+      }
+  }
+  m = wave_max(m);   // the wave's 512 samples
+  const int64_t blk = base / 512 + w;
+  if (lane == 0 && blk * 512 < n) pm_all[(int64_t)b * npm + blk] = m;
+}
+
+// ms[b, t] = mean square of trim frame t of y (2048 samples at hop 512 of the row reflect-padded by 1024); one wave per frame
+__global__ __launch_bounds__(WF_T) void wf_ms_kernel(const float* __restrict__ y_all, int64_t y_pitch, const int32_t* __restrict__ samples,
+                                                     float* __restrict__ ms_all, int nms, int L) {
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int n = wf_len(samples, b, L);
+  const int t = blockIdx.x * (WF_T / 64) + (threadIdx.x >> 6);
+  if (n == 0 || t >= 1 + n / WF_TRIM_HOP) return;
+  const float* y = y_all + (int64_t)b * y_pitch;
+  float acc = 0.f;
+  for (int i = lane; i < WF_TRIM_FRAME; i += 64) {
+    const int64_t p = (int64_t)t * WF_TRIM_HOP + i - WF_TRIM_FRAME / 2;
+    const float v = y[p >= 0 && p < n ? (int)p : wf_reflect(p, n)];
+    acc = fmaf(v, v, acc);
+  }
+  const float m = wave_sum(acc) * (1.0f / WF_TRIM_FRAME);
+  if (lane == 0) ms_all[(int64_t)b * nms + t] = m;
+}
+
+// one workgroup per row: bounds (fb_trim_kernel's rule with -top_db in place of -60; top_db == 0: no trim) and the peak
+__global__ __launch_bounds__(WF_BT) void wf_bounds_kernel(const float* __restrict__ ms_all, int nms, const float* __restrict__ pm_all,
+                                                          int npm, const int32_t* __restrict__ samples, float top_db,
+                                                          int32_t* __restrict__ bounds, float* __restrict__ peak, int L) {
+  constexpr int NW = WF_BT / 64;
+  __shared__ float red_max[NW];
+  __shared__ int red_lo[NW], red_hi[NW];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int n = wf_len(samples, b, L);
+  int start = 0, end = n;
+  if (top_db > 0.f && n > 0) {   // (uniform)
+    const float* ms = ms_all + (int64_t)b * nms;
+    const int nt = 1 + n / WF_TRIM_HOP;
+    float mx = 0.f;
+    for (int t = threadIdx.x; t < nt; t += WF_BT) mx = fmaxf(mx, ms[t]);
+    mx = wave_max(mx);
+    if (lane == 0) red_max[w] = mx;
+    __syncthreads();
+    mx = red_max[0];
+    for (int i = 1; i < NW; ++i) mx = fmaxf(mx, red_max[i]);
+    const float ref_db = 10.f * log10f(fmaxf(1e-10f, mx));
+    int lo = 0x7fffffff, hi = -1;
+    for (int t = threadIdx.x; t < nt; t += WF_BT)
+      if (10.f * log10f(fmaxf(1e-10f, ms[t])) - ref_db > -top_db) {
+        lo = min(lo, t);
+        hi = max(hi, t);
+      }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo = min(lo, __shfl_xor(lo, o));
+      hi = max(hi, __shfl_xor(hi, o));
+    }
+    if (lane == 0) {
+      red_lo[w] = lo;
+      red_hi[w] = hi;
+    }
+    __syncthreads();
+    for (int i = 0; i < NW; ++i) {
+      lo = min(lo, red_lo[i]);
+      hi = max(hi, red_hi[i]);
+    }
+    start = end = 0;   // (no frame passes: only a row with non-finite samples gets here)
+    if (hi >= 0) {
+      start = lo * WF_TRIM_HOP;
+      end = min(n, (hi + 1) * WF_TRIM_HOP);
+    }
+    __syncthreads();   // red_max is used again below
+  }
+  // start is a multiple of 512 and end is one or n: the 512-sample maxima tile [start, end) exactly
+  const float* pm = pm_all + (int64_t)b * npm;
+  float pk = 0.f;
+  for (int k = start / 512 + threadIdx.x; (int64_t)k * 512 < end; k += WF_BT) pk = fmaxf(pk, pm[k]);
+  pk = wave_max(pk);
+  if (lane == 0) red_max[w] = pk;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < NW; ++i) pk = fmaxf(pk, red_max[i]);
+    bounds[2 * b] = start;
+    bounds[2 * b + 1] = end;
+    peak[b] = pk;
+  }
+}
+
+// out[b, i] = y[s_b + i], pcm[b, i] = trunc(32767 y / max(1, peak)) (write_wav's rule in fp32: one rounded division, one rounded
+// multiply) for i < e_b - s_b, zeros behind
+__global__ __launch_bounds__(256) void wf_emit_kernel(const float* __restrict__ y_all, int64_t y_pitch, const int32_t* __restrict__ bounds,
+                                                      const float* __restrict__ peak, float* __restrict__ out,
+                                                      int16_t* __restrict__ pcm, int L) {
+  const int b = blockIdx.y;
+  const int s = bounds[2 * b], m = bounds[2 * b + 1] - s;
+  const float pk = peak[b];
+  const float* y = y_all + (int64_t)b * y_pitch + s;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += (int64_t)gridDim.x * 256) {
+    const float v = i < m ? y[i] : 0.f;
+    if (out) out[(int64_t)b * L + i] = v;
+    if (pcm) {
+      const float u = pk > 1.f ? __fdiv_rn(v, pk) : v;
+      pcm[(int64_t)b * L + i] = (int16_t)(int)truncf(__fmul_rn(u, 32767.0f));
+    }
+  }
+}
+
 }  // namespace
 
 int64_t griffinlim_workspace_floats(int B, int F) {
@@ -403,5 +629,39 @@ int launch_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t see
   float* red = tprev + (int64_t)B * F * NBIN * 2;
   griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, s, momentum, conv, tprev, red);
   TACO_LAUNCH_CHECK("griffinlim_fast");
+  return TACO_OK;
+}
+
+// workspace of taco_wave_finish: y (B, L rounded up to 4), the chunk aggregates, the 512-sample maxima, the trim frames' mean
+// squares, and 64 floats of slack for the 16-byte alignment of y
+static int64_t wf_pitch(int L) { return ((int64_t)L + 3) & ~(int64_t)3; }
+static int wf_chunks(int L) { return cdiv(L, WF_CHUNK); }
+static int wf_blocks(int L) { return cdiv(L, 512); }
+static int wf_frames(int L) { return 1 + L / WF_TRIM_HOP; }
+int64_t wave_finish_workspace_floats(int B, int L) {
+  return (int64_t)B * (wf_pitch(L) + wf_chunks(L) + wf_blocks(L) + wf_frames(L)) + 64;
+}
+
+int launch_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out, int16_t* pcm,
+                       int32_t* bounds, float* peak, void* workspace, int B, int L, hipStream_t s) {
+  TACO_REQUIRE(wave && bounds && peak && workspace && B > 0 && L > 0, "wave_finish: bad arguments");
+  TACO_REQUIRE(out || pcm, "wave_finish: out and pcm are both NULL");
+  TACO_REQUIRE(out != wave, "wave_finish: out may not alias wave (the emit pass shifts by the trim start)");
+  TACO_REQUIRE(deemphasis >= 0.f && deemphasis < 1.f, "wave_finish: deemphasis %g is not in [0, 1)", (double)deemphasis);   // (NaN fails)
+  TACO_REQUIRE(trim_top_db >= 0.f, "wave_finish: trim_top_db %g is negative or NaN", (double)trim_top_db);
+  const int64_t pitch = wf_pitch(L);
+  const int nch = wf_chunks(L), npm = wf_blocks(L), nms = wf_frames(L);
+  float* y = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
+  float* agg = y + (int64_t)B * pitch;
+  float* pm = agg + (int64_t)B * nch;
+  float* ms = pm + (int64_t)B * npm;
+  if (deemphasis != 0.f && nch > 1)
+    TACO_KLAUNCH((wf_scan_kernel<true>), dim3(nch - 1, B), dim3(WF_T), 0, s, wave, samples, deemphasis, y, pitch, agg, nch, pm, npm, L);
+  TACO_KLAUNCH((wf_scan_kernel<false>), dim3(nch, B), dim3(WF_T), 0, s, wave, samples, deemphasis, y, pitch, agg, nch, pm, npm, L);
+  if (trim_top_db > 0.f)
+    TACO_KLAUNCH(wf_ms_kernel, dim3(cdiv(nms, WF_T / 64), B), dim3(WF_T), 0, s, y, pitch, samples, ms, nms, L);
+  TACO_KLAUNCH(wf_bounds_kernel, dim3(B), dim3(WF_BT), 0, s, ms, nms, pm, npm, samples, trim_top_db, bounds, peak, L);
+  TACO_KLAUNCH(wf_emit_kernel, dim3(std::min(cdiv(L, 1024), 2048), B), dim3(256), 0, s, y, pitch, bounds, peak, out, pcm, L);
+  TACO_LAUNCH_CHECK("wave_finish");
   return TACO_OK;
 }

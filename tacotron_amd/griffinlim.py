@@ -11,7 +11,10 @@ len_b r frames (taco_griffinlim_rows): the Griffin-Lim of that prompt alone, zer
 phase0 -- initial phases from the library's counter-hash generator: no host random numbers, no upload, nothing read back.
 
 With `momentum` (opt-in) the rounds are those of the fast Griffin-Lim algorithm (taco_griffinlim_fast), and `want_conv` returns the
-per-round spectral convergence next to the waveform."""
+per-round spectral convergence next to the waveform.
+
+`finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
+front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16."""
 from __future__ import annotations
 
 import math
@@ -48,3 +51,27 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         g = torch.Generator(device='cpu').manual_seed(seed)
         phase0 = (2.0 * math.pi * torch.rand(mag_t.shape, generator=g)).to(dev)
     return lib.griffinlim(mag_t, phase0.contiguous(), n_iter, out=wave, work=work)
+
+
+def finish_samples(lengths, r, L):
+    """(B) int32 decoder steps -> (B) int32 samples n_b of the rows of a (B, L) waveform, L = 300 (F - 1), by the rule of
+    taco_griffinlim_rows: F_b = min(F, lengths * r) frames, n_b = 300 (F_b - 1), and 0 below 5 frames.  Torch ops on the tensor's own
+    device; nothing is read back."""
+    F = int(L) // 300 + 1
+    Fb = torch.clamp(lengths.to(torch.int64) * int(r), max=F)
+    return torch.where(Fb < 5, torch.zeros_like(Fb), 300 * (Fb - 1)).to(torch.int32)
+
+
+def finish_waveform(wave, lengths=None, r=1, deemphasis=0.97, trim_top_db=0.0, want_out=True, want_pcm=True, out=None, pcm=None,
+                    bounds=None, peak=None, work=None):
+    """wave (B, L) as invert_spectrogram returns it -> (out, pcm, bounds, peak) of lib.wave_finish: de-emphasised (the inverse of the
+    front end's pre-emphasis 0.97), trimmed at trim_top_db (0: not trimmed), as fp32 and as PCM16.  lengths: (B) int32 decoder steps
+    on the device (model.lengths, with r the reduction factor): row b then ends where its Griffin-Lim ended."""
+    if lengths is not None:
+        if int(r) < 1:
+            raise ValueError('finish_waveform: r must be >= 1, got %r' % (r,))
+        if wave.dim() != 2 or tuple(lengths.shape) != (wave.shape[0],) or lengths.dtype != torch.int32:
+            raise ValueError('finish_waveform: lengths must be an int32 tensor of shape (B,) for a (B, L) waveform')
+    samples = None if lengths is None else finish_samples(lengths, r, wave.shape[1])
+    return lib.wave_finish(wave, samples, deemphasis=deemphasis, trim_top_db=trim_top_db, want_out=want_out, want_pcm=want_pcm, out=out,
+                           pcm=pcm, bounds=bounds, peak=peak, work=work)

@@ -115,6 +115,8 @@ EXPORTS = {
     'taco_griffinlim_rows': (C.c_int, [_P, _P, C.c_uint64, _P, _I, _P, _P, _I, _I, _I, _P]),
     'taco_griffinlim_fast_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim_fast': (C.c_int, [_P, _P, C.c_uint64, _P, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
+    'taco_wave_finish_workspace_bytes': (C.c_int64, [_I, _I]),
+    'taco_wave_finish': (C.c_int, [_P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_fill_bernoulli': (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
@@ -486,6 +488,53 @@ def griffinlim_fast(mag_t, frames=None, phase0=None, seed=0, n_iter=50, momentum
     _check(_lib.taco_griffinlim_fast(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), int(frames_per_unit),
                                      momentum, ptr(wave), ptr(conv), ptr(work), B, F, n_iter, stream_ptr()), 'taco_griffinlim_fast')
     return (wave, conv) if want_conv else wave
+
+
+def wave_finish_workspace_floats(B, L) -> int:
+    nbytes = _lib.taco_wave_finish_workspace_bytes(int(B), int(L))
+    if nbytes < 0:
+        raise TacoError('taco_wave_finish_workspace_bytes: bad shape (B=%d, L=%d)' % (B, L))
+    return nbytes // 4
+
+
+def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=True, want_pcm=True, out=None, pcm=None, bounds=None,
+                peak=None, work=None):
+    """Waveform finishing (include/taco_hip.h taco_wave_finish): wave (B, L) fp32 -> (out (B, L) fp32 or None, pcm (B, L) int16 or
+    None, bounds (B, 2) int32, peak (B) fp32).  Per row: de-emphasis y[n] = x[n] + deemphasis * y[n-1] over its first n_b samples,
+    the energy trim [s_b, e_b) at trim_top_db below the loudest frame (0: none), peak = max |y| inside it, then out = y[s_b : e_b]
+    and pcm = write_wav's PCM16 of it, zeros behind.  samples (B) int32 on the device, or None: every row has L samples.
+    deemphasis in [0, 1); trim_top_db >= 0.  out / pcm / bounds / peak / work: the caller's own buffers (work:
+    wave_finish_workspace_floats(B, L) floats); default: fresh ones.  An out / pcm buffer implies want_out / want_pcm."""
+    if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[0] < 1 or wave.shape[1] < 1:
+        raise ValueError('wave_finish: wave must be a float32 tensor of shape (B, L), got %s %s' % (wave.dtype, tuple(wave.shape)))
+    if not wave.is_contiguous():
+        raise ValueError('wave_finish: wave must be contiguous')
+    B, L = wave.shape
+    dev = wave.device
+    if samples is not None and (tuple(samples.shape) != (B,) or samples.dtype != torch.int32 or samples.device != dev):
+        raise ValueError('wave_finish: samples must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
+                         % (B, dev, samples.dtype, tuple(samples.shape), samples.device))
+    deemphasis, trim_top_db = float(deemphasis), float(trim_top_db)
+    if not 0.0 <= deemphasis < 1.0:   # (NaN fails both comparisons)
+        raise ValueError('wave_finish: deemphasis must be in [0, 1), got %r' % deemphasis)
+    if C.c_float(deemphasis).value >= 1.0:
+        raise ValueError('wave_finish: deemphasis %r rounds to 1 in float32' % deemphasis)
+    if not trim_top_db >= 0.0:
+        raise ValueError('wave_finish: trim_top_db must be >= 0, got %r' % trim_top_db)
+    want_out = bool(want_out) or out is not None
+    want_pcm = bool(want_pcm) or pcm is not None
+    if not (want_out or want_pcm):
+        raise ValueError('wave_finish: at least one of out and pcm is needed')
+    out = _own_or_given(out, (B, L), torch.float32, dev, 'wave_finish: out') if want_out else None
+    if out is not None and out.data_ptr() == wave.data_ptr():
+        raise ValueError('wave_finish: out may not alias wave')
+    pcm = _own_or_given(pcm, (B, L), torch.int16, dev, 'wave_finish: pcm') if want_pcm else None
+    bounds = _own_or_given(bounds, (B, 2), torch.int32, dev, 'wave_finish: bounds')
+    peak = _own_or_given(peak, (B,), torch.float32, dev, 'wave_finish: peak')
+    work = _own_or_given(work, (wave_finish_workspace_floats(B, L),), torch.float32, dev, 'wave_finish: work')
+    _check(_lib.taco_wave_finish(ptr(wave), ptr(samples), deemphasis, trim_top_db, ptr(out), ptr(pcm), ptr(bounds), ptr(peak),
+                                 ptr(work), B, L, stream_ptr()), 'taco_wave_finish')
+    return out, pcm, bounds, peak
 
 
 def audio_features_workspace_bytes(B, L) -> int:

@@ -9,7 +9,11 @@ files are cut to its len_b decoder steps and prompt_NNN_len.npy holds len_b.  Th
 drawn on the device, so prompt_NNN.wav is the Griffin-Lim of that prompt alone.
 --gl-momentum A (opt-in, not in the reference): fast Griffin-Lim rounds with momentum A in [0, 1) (lib.griffinlim_fast), phases drawn
 on the device; prompt_NNN_conv.npy holds the prompt's n_iter + 1 spectral-convergence values and the batch's worst final value is
-printed.  --gl-iters N: the number of rounds (default 50, the reference's).  Both combine with --stop / --vocode-lengths."""
+printed.  --gl-iters N: the number of rounds (default 50, the reference's).  Both combine with --stop / --vocode-lengths.
+--deemphasis [A] / --trim-db DB (opt-in, not in the reference): the waveform is finished on the device (griffinlim.finish_waveform,
+taco_wave_finish): de-emphasis with A in [0, 1) (0.97 when A is left out: the inverse of the training features' pre-emphasis) and / or
+the front end's energy trim at DB > 0 decibels below the loudest frame.  prompt_NNN.wav is then written from the device's int16
+samples and holds e - s of them; prompt_NNN_trim.npy holds [s, e].  They combine with every option above."""
 from __future__ import annotations
 
 import argparse
@@ -23,7 +27,7 @@ import torch
 
 from .config import Config
 from .data import load_prompts
-from .griffinlim import invert_spectrogram
+from .griffinlim import finish_waveform, invert_spectrogram
 from .model import Tacotron
 from .params import ParamBuffer
 from . import lib
@@ -44,8 +48,20 @@ def write_wav(path, samples, sr=SR):
         f.writeframes((x * 32767.0).astype('<i2').tobytes())
 
 
+def write_wav_pcm(path, int16_samples, sr=SR):
+    """mono PCM16 from samples that already are int16 (the device's, lib.wave_finish): no arithmetic on the host."""
+    x = np.ascontiguousarray(int16_samples)
+    if x.dtype != np.int16 or x.ndim != 1:
+        raise ValueError('write_wav_pcm: expected a 1-d int16 array, got %s %s' % (x.dtype, x.shape))
+    with wave.open(path, 'wb') as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(sr)
+        f.writeframes(x.astype('<i2', copy=False).tobytes())
+
+
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None):
+         gl_momentum=None, deemphasis=None, trim_db=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -58,13 +74,21 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     their sizes, the samples are the Griffin-Lim of that prompt alone, from phases drawn on the device (seed = index of the batch's
     first prompt).
     `gl_momentum`: None, or the momentum of the fast Griffin-Lim rounds; prompt_NNN_conv.npy then holds the n_iter + 1 convergence
-    values of the prompt (over the frames the vocoder ran on: the prompt's own with `vocode_lengths`, else the full length)."""
+    values of the prompt (over the frames the vocoder ran on: the prompt's own with `vocode_lengths`, else the full length).
+    `deemphasis` (None, or a in [0, 1)) / `trim_db` (None, or decibels > 0): with either, the batch's waveform is finished on the
+    device (finish_waveform; with `stop`, each row over the samples of its own len_b r frames) and prompt_NNN.wav is written from
+    the device's int16 samples: e - s of them, [s, e] in prompt_NNN_trim.npy.  The other files are unchanged."""
     if vocode_lengths and stop is None:
         raise ValueError('test: vocode_lengths needs a stop rule (the lengths come from taco_infer_stop)')
     if gl_momentum is not None and not 0.0 <= float(gl_momentum) < 1.0:
         raise ValueError('test: gl_momentum must be in [0, 1), got %r' % (gl_momentum,))
     if int(n_iter) < 0:
         raise ValueError('test: n_iter must be >= 0, got %r' % (n_iter,))
+    if deemphasis is not None and not 0.0 <= float(deemphasis) < 1.0:
+        raise ValueError('test: deemphasis must be in [0, 1), got %r' % (deemphasis,))
+    if trim_db is not None and not float(trim_db) > 0.0:
+        raise ValueError('test: trim_db must be > 0, got %r' % (trim_db,))
+    finish = deemphasis is not None or trim_db is not None
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
         with open(meta_path, 'rb') as f:
@@ -104,7 +128,22 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
         conv = None
-        if vocode and gl_momentum is not None:
+        pcm = trim = None
+        if vocode and finish:
+            if gl_momentum is not None:
+                wav, conv = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum, want_conv=True,
+                                               lengths=model.lengths if vocode_lengths else None)
+                conv = conv.cpu().numpy()
+                print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
+                      % (gl_momentum, n_iter, float(conv[:, -1].max())))
+            else:
+                wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n,
+                                         lengths=model.lengths if vocode_lengths else None)
+            _, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
+                                              deemphasis=0.0 if deemphasis is None else deemphasis,
+                                              trim_top_db=0.0 if trim_db is None else trim_db, want_out=False)
+            pcm, trim, wav = pcm.cpu().numpy(), trim.cpu().numpy(), None
+        elif vocode and gl_momentum is not None:
             wav, conv = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum, want_conv=True,
                                            lengths=model.lengths if vocode_lengths else None)
             wav, conv = wav.cpu().numpy(), conv.cpu().numpy()
@@ -128,6 +167,10 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             np.save(os.path.join(out_dir, 'prompt_%03d_align.npy' % n), ai)
             if wi is not None:
                 write_wav(os.path.join(out_dir, 'prompt_%03d.wav' % n), wi)
+            if pcm is not None:
+                s_b, e_b = int(trim[i, 0]), int(trim[i, 1])
+                write_wav_pcm(os.path.join(out_dir, 'prompt_%03d.wav' % n), pcm[i, :e_b - s_b])
+                np.save(os.path.join(out_dir, 'prompt_%03d_trim.npy' % n), trim[i])
             if conv is not None:
                 np.save(os.path.join(out_dir, 'prompt_%03d_conv.npy' % n), conv[i])
             n += 1
@@ -150,6 +193,10 @@ def parse_args(argv=None):
     ap.add_argument('--gl-momentum', type=float, default=None,
                     help='fast Griffin-Lim rounds with this momentum in [0, 1) (0.99: librosa\'s default); writes prompt_NNN_conv.npy')
     ap.add_argument('--gl-iters', type=int, default=50, help='Griffin-Lim rounds (the reference: 50)')
+    ap.add_argument('--deemphasis', type=float, nargs='?', const=0.97, default=None, metavar='A',
+                    help='undo the training features\' pre-emphasis on the device: y[n] = x[n] + A y[n-1], A in [0, 1) (default 0.97)')
+    ap.add_argument('--trim-db', type=float, default=None, metavar='DB',
+                    help='cut leading / trailing silence more than DB > 0 decibels below the loudest frame; writes prompt_NNN_trim.npy')
     a = ap.parse_args(argv)
     if a.vocode_lengths and not a.stop:
         ap.error('--vocode-lengths needs --stop')
@@ -157,6 +204,10 @@ def parse_args(argv=None):
         ap.error('--gl-iters must be >= 0')
     if a.gl_momentum is not None and not 0.0 <= a.gl_momentum < 1.0:
         ap.error('--gl-momentum must be in [0, 1)')
+    if a.deemphasis is not None and not 0.0 <= a.deemphasis < 1.0:
+        ap.error('--deemphasis must be in [0, 1)')
+    if a.trim_db is not None and not a.trim_db > 0.0:
+        ap.error('--trim-db must be > 0')
     return a
 
 
@@ -169,4 +220,4 @@ if __name__ == '__main__':
     print('Building Tacotron')
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
-         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum)
+         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db)
