@@ -11,7 +11,9 @@ pids=()
 # alternations (profiles/r05_dec_sched_ab.txt): BPTT 14.19 -> 13.66 us per decoder step, forward unchanged, S1 step -0.1 ms;
 # max-ilp / max-memory-clause / iterative-minreg are slower, the strategy does nothing for bigru.hip.
 D3FLAGS="-mllvm -amdgpu-sched-strategy=iterative-maxocc"
-for f in gemm gemm2 vocoder features elementwise bigru decoder highway prenet layout model; do
+# every object but the decoder pair, which the three libraries take in different builds
+COMMON="gemm gemm2 vocoder features elementwise bigru highway prenet layout stream model"
+for f in $COMMON decoder; do
   hipcc $FLAGS -c $f.hip -o ../../build/obj/$f.o &
   pids+=($!)
 done
@@ -28,7 +30,10 @@ pids+=($!)
 hipcc $FLAGS $D3FLAGS -DTACO_NO_RS -DTACO_NO_POLL128 -DTACO_NO_SHADOW -DTACO_NO_GROUPED_FANDQ -DTACO_NO_UNIPOLL -DTACO_NO_TANH_SPLIT -c decoder3.hip -o ../../build/obj/decoder3_prev.o &
 pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC -o $OUT ../../build/obj/{gemm,gemm2,vocoder,features,elementwise,bigru,decoder,decoder3,highway,prenet,layout,model}.o
-hipcc --offload-arch=gfx950 -shared -fPIC -o ../libtaco_probe.so ../../build/obj/{gemm,gemm2,vocoder,features,elementwise,bigru,decoder_probe,decoder3_probe,highway,prenet,layout,model}.o
-hipcc --offload-arch=gfx950 -shared -fPIC -o ../libtaco_prevdec.so ../../build/obj/{gemm,gemm2,vocoder,features,elementwise,bigru,decoder,decoder3_prev,highway,prenet,layout,model}.o
+link() {   # link <library> <decoder object> <decoder3 object>
+  hipcc --offload-arch=gfx950 -shared -fPIC -o $1 $(printf '../../build/obj/%s.o ' $COMMON $2 $3)
+}
+link $OUT decoder decoder3
+link ../libtaco_probe.so decoder_probe decoder3_probe
+link ../libtaco_prevdec.so decoder decoder3_prev
 echo "built $(realpath $OUT)"

@@ -2329,12 +2329,7 @@ struct Launch3 {
     return e != hipSuccess || (int64_t)cus * per_cu < (int64_t)8 * P3 ? TACO_ENOTFOUND : TACO_OK;
   }
   int enqueue(Args& a, hipStream_t s) const {
-    const hipError_t e = a.xchg_zeroed ? hipSuccess : hipMemsetAsync(a.xchg, 0, (size_t)decoder_xchg_bytes(a.B, a.Tt), s);
-    taco_tail_touch(s);
-    if (e != hipSuccess) {
-      taco_set_error("%s: memset: %s", name, hipGetErrorString(e));
-      return TACO_ELAUNCH;
-    }
+    if (!a.xchg_zeroed) TACO_TRY(taco_memset_async(a.xchg, 0, (size_t)decoder_xchg_bytes(a.B, a.Tt), s, name));
     TACO_KLAUNCH(kern, dim3(8 * P3), dim3(NT), smem, s, a);
     TACO_LAUNCH_CHECK(name);
     return TACO_OK;

@@ -300,12 +300,7 @@ int launch_audio_features(const float* wave, const int* wave_len_host, const flo
   int* len_d = reinterpret_cast<int*>(ws + W.len);
   int* rng = reinterpret_cast<int*>(ws + W.rng);
   float* ms = reinterpret_cast<float*>(ws + W.ms);
-  hipError_t e = hipMemcpyAsync(len_d, wave_len_host, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) {
-    taco_set_error("audio_features: length upload: %s", hipGetErrorString(e));
-    return TACO_ELAUNCH;
-  }
-  taco_tail_touch(s);
+  TACO_TRY(taco_upload_async(len_d, wave_len_host, (size_t)B * sizeof(int), s, "audio_features: length upload"));
   TACO_KLAUNCH(fb_ranges_kernel, dim3(1), dim3(256), 0, s, mel_basis, rng);
   TACO_KLAUNCH(fb_trim_kernel, dim3(B), dim3(TT), 0, s, wave, len_d, ms, W.ms_stride, bounds, kept, L, max_len);
   FrameArgs a;

@@ -1,14 +1,7 @@
 // kernels.h -- internal launch interface shared by the .hip translation units of libtaco_hip.so.
 #pragma once
 #include "common.h"
-
-// ---------------------------------------------------------------- profiling rings (model.hip)
-// category 0 / 1: decoder fwd / bwd kernel, 2: MFMA GEMM family, 3: bi-GRU recurrences.  begin returns a slot (or -1 when the
-// category is not being recorded); end stamps the stop event and the launch's algorithmic FLOPs.
-int taco_prof_begin(int which, hipStream_t s);
-void taco_prof_end(int which, int slot, hipStream_t s, double flops);
-void taco_prof_cancel(int which, int slot, hipStream_t s);   // the bracketed launch was not made: drops the slot, records nothing
-void taco_prof_label(int which, int slot, const char* fmt, ...) __attribute__((format(printf, 3, 4)));   // no-op when slot < 0
+#include "stream.h"
 
 // ---------------------------------------------------------------- gemm.hip
 constexpr int kMaxGemmBatch = 16;

@@ -14,226 +14,6 @@ void taco_set_error(const char* fmt, ...) {
 }
 extern "C" const char* taco_last_error_string(void) { return g_err; }
 
-// ---- tail events (common.h) ----
-namespace {
-constexpr int kTailRing = 64, kTailStreams = 8, kPlanWords = 8, kPlans = 32;   // (a plan covers 64 * kPlanWords launches per stream)
-hipStream_t const kDepMany = reinterpret_cast<hipStream_t>(~(uintptr_t)0);
-struct TailTrack {
-  bool used = false;
-  hipStream_t s = nullptr;
-  hipEvent_t ring[kTailRing] = {};
-  int next = 0;
-  int tail_slot = -1;          // ring slot that still owns `tail` (-1: stolen, not a ring event, or no tail)
-  hipEvent_t tail = nullptr;   // rides on the last launch on s; nullptr once anything it does not cover was enqueued behind it
-  bool has_dep = false;        // behind the last launch s was made to wait for events of stream `dep` (kDepMany: of several streams):
-  hipStream_t dep = nullptr;   //   `tail` then still covers everything a fork TO `dep` has to wait for (dep's own order covers the rest)
-  int launches = 0;            // launches on s in this scope
-  int tail_idx = -1;           // launch index of `tail`
-  bool declined = false;       // the last launch on s carried no event because the plan did not ask for one
-  int dev = 0;                 // device the ring's events belong to
-  uint64_t stamp = 0;          // last use (least-recently-used take-over when a caller keeps handing in new streams)
-  bool armed = false;          // profiling bracket: the next launch carries these two events
-  hipEvent_t arm_start = nullptr, arm_stop = nullptr;
-  int arm_launches = 0;
-};
-// Which launches of a call need an event is learned, not declared: the first call of a kind / shape puts an event on EVERY launch
-// and notes the (stream, launch index) pairs a fork, join or segment actually consumed; later calls put events on those only
-// (an event on all ~90 launches of a step costs what the ~17 markers it replaces cost: measured, profiles/r06_tail_events_ab.txt).
-// A fork that finds no event because the plan declined it falls back to a recorded marker -- always correct -- and the plan is
-// learned again by the next call.
-struct TailPlan {
-  bool used = false, learned = false;
-  uint64_t key = 0;
-  uint64_t bits[kTailStreams][kPlanWords] = {};
-};
-thread_local TailTrack g_tail[kTailStreams];
-thread_local TailPlan g_plans[kPlans];
-thread_local TailPlan* g_plan = nullptr;
-thread_local int g_plan_next = 0;
-thread_local bool g_tail_on = false, g_learning = false;
-thread_local uint64_t g_tail_clock = 0;
-void tail_drop(TailTrack* t);
-TailTrack* tail_find(hipStream_t s, bool create) {
-  for (TailTrack& t : g_tail)
-    if (t.used && t.s == s) {
-      t.stamp = ++g_tail_clock;
-      return &t;
-    }
-  if (!create) return nullptr;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  TailTrack* lru = nullptr;
-  for (TailTrack& t : g_tail) {
-    if (!t.used) {
-      t.used = true;
-      t.s = s;
-      t.dev = dev;
-      t.stamp = ++g_tail_clock;
-      return &t;
-    }
-    // a caller that hands in ever new streams: the least recently used entry of the SAME device is taken over (its ring events
-    // are not bound to a stream); entries of streams that launched in this scope are left alone
-    if (t.dev == dev && t.launches == 0 && !t.tail && !t.armed && (!lru || t.stamp < lru->stamp)) lru = &t;
-  }
-  if (lru) {
-    lru->s = s;
-    lru->stamp = ++g_tail_clock;
-    tail_drop(lru);
-    lru->tail_idx = -1;
-    lru->declined = false;
-  }
-  return lru;
-}
-void tail_consumed(TailTrack* t) {
-  if (g_learning && g_plan && t->tail_idx >= 0 && t->tail_idx < 64 * kPlanWords)
-    g_plan->bits[t - g_tail][t->tail_idx >> 6] |= 1ull << (t->tail_idx & 63);
-}
-void tail_drop(TailTrack* t) {
-  t->tail = nullptr;
-  t->tail_slot = -1;
-  t->has_dep = false;
-  t->dep = nullptr;
-}
-}  // namespace
-
-hipEvent_t taco_tail_take(hipStream_t s, hipEvent_t* start) {
-  *start = nullptr;
-  if (!g_tail_on) return nullptr;
-  TailTrack* t = tail_find(s, true);
-  if (!t) return nullptr;   // (more streams than the table holds: those launch plainly and fork through recorded events)
-  const int idx = t->launches++;
-  ++t->arm_launches;
-  t->has_dep = false;       // (this launch is ordered behind every wait enqueued so far: its event covers them)
-  t->dep = nullptr;
-  if (t->armed) {           // a profiling bracket's pair: timing events the ring does not own
-    t->armed = false;
-    *start = t->arm_start;
-    t->tail = t->arm_stop;
-    t->tail_slot = -1;
-    t->tail_idx = idx;
-    t->declined = false;
-    return t->tail;
-  }
-  const bool want = g_learning || (g_plan && idx < 64 * kPlanWords && ((g_plan->bits[t - g_tail][idx >> 6] >> (idx & 63)) & 1));
-  if (!want) {
-    tail_drop(t);
-    t->declined = true;
-    return nullptr;
-  }
-  const int slot = t->next;
-  t->next = (slot + 1) % kTailRing;
-  t->declined = false;
-  if (!t->ring[slot] && hipEventCreateWithFlags(&t->ring[slot], hipEventDisableTiming) != hipSuccess) {
-    t->ring[slot] = nullptr;
-    tail_drop(t);
-    return nullptr;
-  }
-  t->tail = t->ring[slot];
-  t->tail_slot = slot;
-  t->tail_idx = idx;
-  return t->tail;
-}
-hipEvent_t taco_tail_event(hipStream_t s, hipStream_t for_stream) {
-  if (!g_tail_on) return nullptr;
-  TailTrack* t = tail_find(s, false);
-  if (!t) return nullptr;
-  if (t->tail && t->has_dep && (t->dep == kDepMany || t->dep != for_stream)) return nullptr;   // (waits behind the launch that `for_stream` does not inherit by its own order)
-  if (t->tail) tail_consumed(t);
-  else if (t->declined && g_plan && !g_learning) g_plan->learned = false;   // (mispredicted: this call falls back, the next one learns)
-  return t->tail;
-}
-hipEvent_t taco_tail_steal(hipStream_t s, hipEvent_t give, bool* owned) {
-  *owned = false;
-  hipEvent_t e = taco_tail_event(s, nullptr);
-  if (!e) return nullptr;
-  TailTrack* t = tail_find(s, false);
-  if (t->tail_slot >= 0 && t->ring[t->tail_slot] == e) {
-    t->ring[t->tail_slot] = give;   // (an event lives in exactly one place: a ring slot or its new owner)
-    t->tail_slot = -1;
-    *owned = true;
-  }
-  return e;   // (not owned: a profiling bracket's stop event, or one that was stolen before -- whoever waits for it does so before it is bound again)
-}
-void taco_tail_touch(hipStream_t s) {
-  TailTrack* t = tail_find(s, false);
-  if (t) {
-    tail_drop(t);
-    t->declined = false;
-  }
-}
-void taco_tail_open(uint64_t key) {
-  const char* e = getenv("TACO_TAIL_EVENTS");
-  g_tail_on = !(e && atoi(e) == 0);
-  g_plan = nullptr;
-  g_learning = false;
-  for (TailTrack& t : g_tail) {
-    tail_drop(&t);
-    t.launches = 0;
-    t.tail_idx = -1;
-    t.declined = false;
-    t.armed = false;
-  }
-  if (!g_tail_on) return;
-  for (TailPlan& p : g_plans)
-    if (p.used && p.key == key) g_plan = &p;
-  if (!g_plan) {
-    g_plan = &g_plans[g_plan_next];
-    g_plan_next = (g_plan_next + 1) % kPlans;
-    *g_plan = TailPlan();
-    g_plan->used = true;
-    g_plan->key = key;
-  }
-  if (!g_plan->learned || (e && atoi(e) == 2)) {   // (TACO_TAIL_EVENTS=2: an event on every launch, always)
-    g_learning = true;
-    for (auto& row : g_plan->bits)
-      for (uint64_t& w : row) w = 0;
-  }
-}
-void taco_tail_close() {
-  if (g_tail_on && g_learning && g_plan) g_plan->learned = true;
-  g_tail_on = false;
-  g_learning = false;
-  g_plan = nullptr;
-  for (TailTrack& t : g_tail) {
-    tail_drop(&t);
-    t.armed = false;
-  }
-}
-bool taco_tail_wait(hipStream_t waiter, hipStream_t producer) {
-  hipEvent_t e = taco_tail_event(producer, waiter);
-  if (!e) return false;
-  if (hipStreamWaitEvent(waiter, e, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  // the wait itself is not covered by the waiter's last launch -- except for a fork back TO the producer, whose own order covers it
-  if (TailTrack* w = tail_find(waiter, false)) {
-    if (!w->has_dep) {
-      w->has_dep = true;
-      w->dep = producer;
-    } else if (w->dep != producer) {
-      w->dep = kDepMany;
-    }
-  }
-  return true;
-}
-bool taco_tail_arm_timing(hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-  if (!g_tail_on) return false;
-  TailTrack* t = tail_find(s, true);
-  if (!t) return false;
-  t->armed = true;
-  t->arm_start = start;
-  t->arm_stop = stop;
-  t->arm_launches = 0;
-  return true;
-}
-int taco_tail_disarm_timing(hipStream_t s) {
-  TailTrack* t = tail_find(s, false);
-  if (!t) return 0;
-  t->armed = false;
-  return t->arm_launches;
-}
-
 extern "C" int taco_version(void) { return TACO_VERSION; }
 
 int validate_shape(const TacoShape* s) {

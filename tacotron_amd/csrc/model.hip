@@ -40,68 +40,6 @@ const Layouts& layouts_for(const TacoShape& s) {
   return *L;
 }
 
-
-// ---- HIP-event profiling rings (taco_profile_enable / taco_profile_read[2]) ----
-// category: 0 decoder forward kernel, 1 decoder backward kernel, 2 MFMA GEMM family (conv_gemm, gemm_tn, highway stack),
-// 3 bi-GRU recurrences.  Every bracketed launch gets a hipEventRecord pair on ITS launch stream plus its algorithmic FLOPs.
-struct ProfRing {
-  static constexpr int kCap = 4096;
-  hipEvent_t start[kCap], stop[kCap];
-  double flops[kCap];
-  bool armed[kCap];       // the pair rides on the bracketed launch (tail events, common.h) instead of being recorded as two markers
-  char label[kCap][96];   // what the launch was (taco_prof_label; read by taco_debug_profile_labels before taco_profile_read2)
-  int created = 0;   // events created so far (lazily, in steps: creating 2 x 4096 events up front costs milliseconds)
-  int n = 0;
-};
-ProfRing g_prof[4];
-int g_prof_mask = 0;   // bit c: category c is recorded
-
-}  // namespace
-
-int taco_prof_begin(int which, hipStream_t s) {
-  if (!(g_prof_mask & (1 << which))) return -1;
-  ProfRing& r = g_prof[which];
-  if (r.n >= ProfRing::kCap) return -1;
-  while (r.created <= r.n) {
-    if (hipEventCreate(&r.start[r.created]) != hipSuccess || hipEventCreate(&r.stop[r.created]) != hipSuccess) return -1;
-    ++r.created;
-  }
-  // inside a tail-event scope (common.h) the pair rides on the bracketed launch itself -- two marker packets around the decoder
-  // kernels were ~20 us of the timed step; outside (op-level calls, capture) the bracket is two recorded markers as before
-  r.armed[r.n] = taco_tail_arm_timing(s, r.start[r.n], r.stop[r.n]);
-  if (!r.armed[r.n]) (void)hipEventRecord(r.start[r.n], s);
-  r.label[r.n][0] = 0;
-  return r.n;
-}
-void taco_prof_label(int which, int slot, const char* fmt, ...) {
-  if (slot < 0) return;
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_prof[which].label[slot], sizeof(g_prof[which].label[slot]), fmt, ap);
-  va_end(ap);
-}
-void taco_prof_end(int which, int slot, hipStream_t s, double flops) {
-  if (slot < 0) return;
-  ProfRing& r = g_prof[which];
-  if (!r.armed[slot]) {
-    (void)hipEventRecord(r.stop[slot], s);
-  } else {
-    // the pair was armed for the next launch on s.  One launch since: it carried both events.  Several (a k-split pair, the decoder
-    // in chunks of 32 rows): the first one carried both -- `stop` is recorded again behind the last, which is what counts.  None:
-    // both are recorded now.
-    const int rode = taco_tail_disarm_timing(s);
-    if (rode == 0) (void)hipEventRecord(r.start[slot], s);
-    if (rode != 1) (void)hipEventRecord(r.stop[slot], s);
-  }
-  r.flops[slot] = flops;
-  r.n = slot + 1;
-}
-void taco_prof_cancel(int which, int slot, hipStream_t s) {
-  // (the ring does not advance: the next bracket reuses the slot; an unarmed bracket's recorded start is simply overwritten)
-  if (slot >= 0 && g_prof[which].armed[slot]) (void)taco_tail_disarm_timing(s);
-}
-
-namespace {
 inline int prof_begin(int which, hipStream_t s) { return taco_prof_begin(which, s); }
 inline void prof_end(int which, int slot, hipStream_t s) { taco_prof_end(which, slot, s, 0.0); }
 
@@ -156,17 +94,6 @@ BiGruWeights bigru_weights(const float* P, const CbhgP& c) {
   w.wg[1] = P + c.bw.wg; w.bg[1] = P + c.bw.bg; w.wc[1] = P + c.bw.wc; w.bc[1] = P + c.bw.bc;
   return w;
 }
-
-// Installs `value` in a thread-local routing variable for one stretch of code and puts the previous value back when the stretch
-// ends, on every return path.
-template <class T>
-struct ScopedSet {
-  T& var;
-  const T prev;
-  ScopedSet(T& v, T value) : var(v), prev(v) { v = value; }
-  ScopedSet(const ScopedSet&) = delete;
-  ~ScopedSet() { var = prev; }
-};
 
 // ops.CBHG forward (ops.py:48-132).  x (B*T, cin).
 // pre_bigru: work to enqueue (on the side stream) at the moment this pass launches its bi-GRU recurrence -- a 64-workgroup kernel
@@ -326,86 +253,6 @@ DecWeights dec_weights(const float* P, const ParamLayout& L) {
   return w;
 }
 
-// Side stream: work that is independent of the main chain runs here while a 64-workgroup recurrent kernel (bi-GRU) or the
-// encoder leaves most of the chip idle.  side_fork(): the side stream waits for everything enqueued on `s` so far;
-// side_join(): `s` waits for the side work.  No host synchronisation; TACO_NO_OVERLAP=1 keeps everything on `s`.
-constexpr int kGradSegments = 5;
-struct SideStream {
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev_img = nullptr;   // the forward weight images are built (recorded on the side stream; the main stream waits in front of the encoder CBHG)
-  bool off = false;
-  // gradient-segment events of the most recent taco_backward issued by this thread on this device (taco_wait_grad_segment):
-  // segment [4] post-net, [3] decoder, [2] encoder projections / highways / bi-GRU, [1] encoder conv bank, [0] embedding + encoder
-  // pre_net of the flat gradient buffer is final
-  hipEvent_t ev_seg[kGradSegments] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_seg_use[kGradSegments] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // what taco_wait_grad_segment waits for: ev_seg or a tail event (common.h)
-  bool seg_recorded = false;
-};
-SideStream& side_stream() {
-  static thread_local SideStream ss[16];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  SideStream& x = ss[dev & 15];
-  if (!x.side && !x.off) {
-    const char* e = getenv("TACO_NO_OVERLAP");
-    if ((e && atoi(e) != 0) || hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&x.ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.ev_join, hipEventDisableTiming) != hipSuccess) {
-      x.side = nullptr;
-      x.off = true;
-    }
-  }
-  return x;
-}
-int record_segment(int seg, hipStream_t on) {
-  SideStream& x = side_stream();
-  if (!x.ev_seg[seg] && hipEventCreateWithFlags(&x.ev_seg[seg], hipEventDisableTiming) != hipSuccess) {
-    taco_set_error("taco_backward: cannot create the gradient-segment event");
-    return TACO_ELAUNCH;
-  }
-  // (tail events, common.h: the segment's event is the one riding on the last launch on `on` -- taken out of that stream's ring,
-  //  this segment's previous event refills the slot -- instead of a marker behind it)
-  bool owned = false;
-  if (hipEvent_t t = taco_tail_steal(on, x.ev_seg[seg], &owned)) {
-    if (owned) x.ev_seg[seg] = t;
-    x.ev_seg_use[seg] = t;   // (not owned: the stop event of a profiling bracket -- taco_wait_grad_segment waits for it before it is bound again)
-  } else {
-    // no tail event to take (`on` waits for side-stream work behind its last launch: the end of the pass): the marker goes to the
-    // SIDE stream, made to wait for `on`'s last launch first -- it covers both streams and sits between no two kernels of `on`
-    hipStream_t at = on;
-    if (x.side && x.side != on && !x.off && taco_tail_wait(x.side, on)) at = x.side;
-    if (hipEventRecord(x.ev_seg[seg], at) != hipSuccess) {
-      taco_set_error("taco_backward: hipEventRecord(segment %d) failed", seg);
-      return TACO_ELAUNCH;
-    }
-    x.ev_seg_use[seg] = x.ev_seg[seg];
-  }
-  if (seg == 0) x.seg_recorded = true;
-  return TACO_OK;
-}
-hipStream_t side_fork(hipStream_t s) {
-  SideStream& x = side_stream();
-  // (profile bit 4: everything on the caller's stream, so that the per-launch event timing of the GEMM family measures each
-  //  kernel by itself instead of two streams' kernels sharing the chip)
-  if (x.off || (g_prof_mask & 16)) return s;
-  if (taco_tail_wait(x.side, s)) return x.side;
-  if (hipEventRecord(x.ev_fork, s) != hipSuccess || hipStreamWaitEvent(x.side, x.ev_fork, 0) != hipSuccess) return s;
-  taco_tail_touch(x.side);
-  return x.side;
-}
-int side_join(hipStream_t s, hipStream_t side) {
-  if (side == s) return TACO_OK;
-  SideStream& x = side_stream();
-  if (taco_tail_wait(s, side)) return TACO_OK;
-  if (hipEventRecord(x.ev_join, side) != hipSuccess || hipStreamWaitEvent(s, x.ev_join, 0) != hipSuccess) {
-    taco_set_error("side_join: event record/wait failed");
-    return TACO_ELAUNCH;
-  }
-  taco_tail_touch(s);
-  return TACO_OK;
-}
-
 // Decoder composite weights.  The decoder step is a chain of linear maps with few nonlinearities in between; wherever two
 // linear maps follow each other (attention layer -> input projection -> GRU-1 gates; output projection -> query layer /
 // next step's pre_net) their product is formed here once per call, so that the persistent kernel needs one exchange
@@ -525,7 +372,7 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
   const int B = sh.B, Tt = sh.Tt, Td = sh.Td, r = sh.r, R80 = kMel * r;
   const int M1 = B * Tt, M2 = B * Td * r;
   // embedding (tacotron.py:111-114) first: the side stream's fork below then waits for THIS launch's stop event (tail events,
-  // common.h) instead of a marker recorded on the caller's stream in front of the call's first kernel
+  // stream.h) instead of a marker recorded on the caller's stream in front of the call's first kernel
   // (same box, alternated four times: 7.02-7.13 vs 7.07-7.16 ms per step, profiles/r06_fwd_fork_order_ab.txt)
   TACO_TRY(launch_embedding(P + PL.emb, text, ws + W.emb, M1, sh.V, s));
   // decoder composites depend on the parameters only: side stream, concurrent with the encoder
@@ -534,20 +381,10 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
   // embedding gather and the encoder pre_net; the main stream waits for them in front of the encoder CBHG (its first gemm2 launch)
   TACO_TRY(register_weight_images(L, W, P, ws, train, 0, true));
   TACO_TRY(weight_images_build(sd));
-  bool img_event = false;
-  hipEvent_t img_ev = nullptr;
+  StreamMark img;
   if (sd != s) {
-    SideStream& x = side_stream();
-    // (tail events: the image launch's own event.  Its ring slot comes round again after 64 more launches on the side stream --
-    //  far more than are enqueued before the wait below -- and would then name a LATER launch of the same stream: still correct)
-    img_ev = taco_tail_event(sd, s);
-    if (img_ev) {
-      img_event = true;
-    } else {
-      if (!x.ev_img && hipEventCreateWithFlags(&x.ev_img, hipEventDisableTiming) != hipSuccess) x.ev_img = nullptr;
-      if (x.ev_img && hipEventRecord(x.ev_img, sd) == hipSuccess) img_event = true, img_ev = x.ev_img;
-      else TACO_TRY(side_join(s, sd));   // (no event: fall back to a full join here)
-    }
+    img = side_mark_images(sd, s);
+    if (!img.ev) TACO_TRY(side_join(s, sd));   // (no event: fall back to a full join here)
   }
   // ONE batched init launch for everything that is a plain copy / zero pad of parameters (side stream, first thing on it):
   //   post/dense (256, 1025) kernel -> pitch 1028 so the W tile loads are 16-byte aligned float4 (pad columns are never stored);
@@ -620,13 +457,7 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
     TACO_TRY(launch_embedding(P + PL.spk_embed, speaker, ws + W.spk_e, B, sh.S, s, 16));
     eb.spk_e = ws + W.spk_e;
   }
-  if (img_event) {
-    if (hipStreamWaitEvent(s, img_ev, 0) != hipSuccess) {
-      taco_set_error("forward: cannot wait for the weight images");
-      return TACO_ELAUNCH;
-    }
-    taco_tail_touch(s);
-  }
+  if (img.ev && stream_wait_mark(s, img) != TACO_OK) TACO_TRY(side_join(s, sd));
   TACO_TRY(cbhg_fwd(P, PL.enc, ws + W.p2, B, Tt, eb, train, s));
   // attention memory (BahdanauAttention.__init__; tacotron.py:48-52)
   TACO_TRY(launch_mask_rows(eb.out, text_length, ws + W.values, B, Tt, kAtt, s));
@@ -734,32 +565,6 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
 // Weight-gradient GEMM.  Inside a TnGroup scope the call is queued and launched with its independent siblings in ONE grid
 // (launch_gemm_tn_batch); otherwise it is launched immediately.
 thread_local GemmTnBatch* g_tnq = nullptr;
-// Side routing: while set, every weight-gradient launch issued for stream `s` goes to this stream instead, ordered behind the
-// work enqueued on `s` so far by an event.  The CBHG backward passes use it: their ~27 weight-gradient GEMMs (0.5 / 0.7 ms per
-// step) feed nothing but the gradient buffer, so they run beside the activation-gradient chain -- much of which is small
-// launches that leave most CUs idle -- instead of inside it.  Their operands then must not be reused in place by the chain
-// (BwdScratch::alt_*).  TACO_NO_SIDE_TN=1 keeps them on the main stream (A/B runs).
-thread_local hipStream_t g_tn_side = nullptr;
-thread_local hipEvent_t g_tn_ev = nullptr;
-int tn_route(hipStream_t s, hipStream_t* out) {
-  *out = s;
-  if (!g_tn_side || g_tn_side == s || (g_prof_mask & 16)) return TACO_OK;
-  if (!g_tn_ev && hipEventCreateWithFlags(&g_tn_ev, hipEventDisableTiming) != hipSuccess) {
-    taco_set_error("weight-gradient side stream: cannot create an event");
-    return TACO_ELAUNCH;
-  }
-  if (taco_tail_wait(g_tn_side, s)) {
-    *out = g_tn_side;
-    return TACO_OK;
-  }
-  if (hipEventRecord(g_tn_ev, s) != hipSuccess || hipStreamWaitEvent(g_tn_side, g_tn_ev, 0) != hipSuccess) {
-    taco_set_error("weight-gradient side stream: event record/wait failed");
-    return TACO_ELAUNCH;
-  }
-  taco_tail_touch(g_tn_side);
-  *out = g_tn_side;
-  return TACO_OK;
-}
 int tn_launch_batch(GemmTnBatch& b, hipStream_t s) {
   hipStream_t q;
   TACO_TRY(tn_route(s, &q));
@@ -935,12 +740,7 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
     // and everything behind it is batched after the highway chain below
     TACO_TRY(launch_add(w.dh0, w.dh0 + (int64_t)B * kCb, w.dsm2[4], (int64_t)B * kCb, s));
   } else if (c.spk) {
-    hipError_t e = hipMemsetAsync(w.dspk_e, 0, (size_t)B * 16 * sizeof(float), s);
-    taco_tail_touch(s);
-    if (e != hipSuccess) {
-      taco_set_error("cbhg_bwd: memset: %s", hipGetErrorString(e));
-      return TACO_ELAUNCH;
-    }
+    TACO_TRY(taco_memset_async(w.dspk_e, 0, (size_t)B * 16 * sizeof(float), s, "cbhg_bwd"));
     // h0 = relu(dense(spk)) feeds both directions: d h0 = dh0[fw] + dh0[bw]
     TACO_TRY(launch_add(w.dh0, w.dh0 + (int64_t)B * kCb, w.dsmall, (int64_t)B * kCb, s));
     TACO_TRY(launch_act_bwd(w.h0, w.dsmall, nullptr, w.dsmall, (int64_t)B * kCb, TACO_ACT_RELU, s));
@@ -1125,12 +925,7 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
   //      atomics by ONE batched launch (all K transposed convolutions run concurrently instead of as a dependent chain) ----
   {
     if (!sc.dx_zeroed) {
-      hipError_t e = hipMemsetAsync(dx_out, 0, (size_t)M * c.cin * sizeof(float), s);
-      taco_tail_touch(s);
-      if (e != hipSuccess) {
-        taco_set_error("cbhg_bwd: memset: %s", hipGetErrorString(e));
-        return TACO_ELAUNCH;
-      }
+      TACO_TRY(taco_memset_async(dx_out, 0, (size_t)M * c.cin * sizeof(float), s, "cbhg_bwd"));
     }
     ConvGemmBatch batch;
     batch.n = c.K;
@@ -1214,36 +1009,9 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
   return TACO_OK;
 }
 
-// The scope of one model-level C-ABI call (taco_forward / taco_infer / taco_backward), constructed first, after argument
-// validation.  Host state the call installs on this thread dies with it, on every return path: the weight-image table (keyed by
-// this call's parameter pointers, pointing into its workspace) is emptied on entry and on exit, and the weight-gradient routing
-// and the TN queue are left empty.  Tail events (common.h) are tracked while the scope is alive -- not while the caller's stream
-// is being captured into a graph (a stop event on a captured launch is not a graph dependency).
-struct CallScope {
-  bool tails = false;
-  CallScope(hipStream_t s, int kind, const TacoShape& sh) {
-    weight_images_clear();
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
-      (void)hipGetLastError();   // (not this call's failure to report: launches are checked with hipGetLastError)
-      return;
-    }
-    if (st != hipStreamCaptureStatusNone) return;
-    uint64_t key = 1469598103934665603ull;   // (FNV-1a over the call's kind and shape)
-    const int64_t f[8] = {kind, sh.B, sh.Tt, sh.Td, sh.r, sh.V, sh.S, (int64_t)(uintptr_t)s};
-    for (int64_t v : f) key = (key ^ (uint64_t)v) * 1099511628211ull;
-    taco_tail_open(key);
-    tails = true;
-  }
-  ~CallScope() {
-    if (tails) taco_tail_close();
-    weight_images_clear();
-    g_tn_side = nullptr;
-    g_tnq = nullptr;
-  }
-};
-
 }  // namespace
+
+void tn_queue_reset() { g_tnq = nullptr; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // C ABI
@@ -1354,8 +1122,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   // ONE batched init launch for every accumulator of the pass: the gradient buffer, [d keys | E] (one (M1, 512) buffer), the small
   // decoder weight-gradient factors, the two CBHG input-gradient accumulators (when they have buffers of their own) and the
   // decoder exchange area (the forward kernel is long done with it)
-  const bool own_dx = getenv("TACO_NO_SIDE_TN") == nullptr && !side_stream().off &&
-                      side_stream().side != nullptr;
+  const bool own_dx = getenv("TACO_NO_SIDE_TN") == nullptr && side_stream_or_null() != nullptr;
   {
     InitBatch ib;
     TACO_TRY(ib.fill(G, PL.total));
@@ -1386,7 +1153,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   hipStream_t side = side_fork(s);
   TACO_TRY(tn(pb.out, 2 * kCb, 2 * kCb, dOutPad, 1028, kFft, G + PL.post_dense.w, kFft, M2, M2, 0, side, 1, G + PL.post_dense.b, 1028));
   // ---- post-net CBHG (input = seq2seq_output viewed as (B, Td*r, 80)) ----
-  // The CBHG's ~27 weight-gradient GEMMs feed nothing but the gradient buffer: they go to the side stream (g_tn_side) and run
+  // The CBHG's ~27 weight-gradient GEMMs feed nothing but the gradient buffer: they go to the side stream (ScopedRoute, stream.h) and run
   // beside the activation-gradient chain, much of which is small launches that leave most CUs idle.  (Running them UNDERNEATH
   // the BPTT kernel instead was measured in rounds 2 and 3 -- both sides run ~1.5x slower while they share CUs, net 0.6 % -- and
   // removed in round 4 together with the data-parallel mode that overlapped collectives with that launch.)
@@ -1401,7 +1168,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   pb.tapsplit = ws + W.tapsplit;   // (free in the backward pass: the conv-bank input gradient's partial tiles)
   pb.tapsplit_floats = W.tapsplit_floats;
   {
-    ScopedSet route(g_tn_side, side_tn ? side : nullptr);
+    ScopedRoute route(side_tn ? side : nullptr);
     TACO_TRY(cbhg_bwd(P, PT, G, PL.post, TL.post, seq2seq_output, dPostOut, B, F, pb, scp, dPostIn, -1, -1, s));
   }
   // d seq2seq_output = sign(s2s - mel) + post-net path
@@ -1556,15 +1323,15 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   float *pre_dz2 = sc.gD, *pre_dz1 = sc.gE, *pre_demb = sc.gF;
   hipStream_t enc_tn = nullptr;
   // (the per-layer speaker form, TACO_SPK_UNFUSED=1, keeps its weight gradients on the main stream: their operands live in ping-pong buffers)
-  if (side_tn && side_stream().side && (!PL.enc.spk || spk_fused_form(PL.enc))) {
+  if (side_tn && side_stream_or_null() && (!PL.enc.spk || spk_fused_form(PL.enc))) {
     // (the side stream is still busy with the decoder weight gradients forked above; the encoder's queue up behind them)
     sce.alt_dpj1 = ws + W.enc_dpj1; sce.alt_dz1 = ws + W.enc_dz1; sce.alt_dpool = ws + W.enc_dpool;
     dP2 = ws + W.enc_dx;
     sce.dx_zeroed = own_dx;
     pre_dz2 = ws + W.pre_dz2; pre_dz1 = ws + W.pre_dz1; pre_demb = ws + W.pre_demb;
-    enc_tn = side_stream().side;
+    enc_tn = side_stream_or_null();
   }
-  ScopedSet route(g_tn_side, enc_tn);   // (to the end of the pass: the speaker scatter and the pre_net's weight gradients too)
+  ScopedRoute route(enc_tn);   // (to the end of the pass: the speaker scatter and the pre_net's weight gradients too)
   eb.tapsplit = ws + W.tapsplit;
   eb.tapsplit_floats = W.tapsplit_floats;
   TACO_TRY(cbhg_bwd(P, PT, G, PL.enc, TL.enc, ws + W.p2, dEnc, B, Tt, eb, sce, dP2, 2, 1, s));
@@ -1617,13 +1384,7 @@ extern "C" int taco_grad_segments(const TacoShape* shape, int64_t* bounds) {
 
 extern "C" int taco_wait_grad_segment(int seg, void* stream) {
   TACO_REQUIRE(seg >= 0 && seg < kGradSegments, "taco_wait_grad_segment: segment %d out of range", seg);
-  SideStream& x = side_stream();
-  TACO_REQUIRE(x.seg_recorded && x.ev_seg_use[seg], "taco_wait_grad_segment: no taco_backward was issued by this thread on this device");
-  if (hipStreamWaitEvent(as_stream(stream), x.ev_seg_use[seg], 0) != hipSuccess) {
-    taco_set_error("taco_wait_grad_segment: hipStreamWaitEvent failed");
-    return TACO_ELAUNCH;
-  }
-  return TACO_OK;
+  return wait_grad_segment(seg, as_stream(stream));
 }
 
 extern "C" int taco_conv_gemm(const float* A, int lda, const float* W, int ldw, const float* bias, const float* scale,
@@ -1714,12 +1475,7 @@ extern "C" int taco_clear_error(const TacoShape* shape, int train, void* workspa
   TACO_REQUIRE(workspace != nullptr, "taco_clear_error: null workspace");
   const Layouts& L = layouts_for(*shape);
   const WsLayout& W = train ? L.Wtrain : L.Winfer;
-  hipError_t e = hipMemsetAsync(static_cast<float*>(workspace) + W.err, 0, 512 * sizeof(float), as_stream(stream));
-  if (e != hipSuccess) {
-    taco_set_error("taco_clear_error: memset: %s", hipGetErrorString(e));
-    return TACO_ELAUNCH;
-  }
-  return TACO_OK;
+  return taco_memset_async(static_cast<float*>(workspace) + W.err, 0, 512 * sizeof(float), as_stream(stream), "taco_clear_error");
 }
 
 extern "C" int taco_denorm_unframe(const float* output, const float* stft_mean, const float* stft_std, float* spec,
@@ -1800,38 +1556,10 @@ extern "C" int taco_debug_fabric_probe(long long* out32, void* gran4k, const voi
   return launch_fabric_probe(out32, gran4k, scratch, scratch_bytes, iters, as_stream(stream));
 }
 
-extern "C" int taco_profile_enable(int mask) {
-  g_prof_mask = mask & 31;
-  return TACO_OK;
-}
+extern "C" int taco_profile_enable(int mask) { return prof_enable(mask); }
 
-extern "C" int taco_profile_read2(int which, float* ms, double* flops, int cap) {
-  TACO_REQUIRE(which >= 0 && which < 4, "profile_read: category %d out of range", which);
-  ProfRing& r = g_prof[which];
-  int n = 0;
-  for (int i = 0; i < r.n; ++i) {
-    if (hipEventSynchronize(r.stop[i]) != hipSuccess) break;
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, r.start[i], r.stop[i]) != hipSuccess) break;
-    if (ms && n < cap) ms[n] = t;
-    if (flops && n < cap) flops[n] = r.flops[i];
-    ++n;
-  }
-  r.n = 0;
-  return n;
-}
+extern "C" int taco_profile_read2(int which, float* ms, double* flops, int cap) { return prof_read(which, ms, flops, cap); }
 
-extern "C" int taco_debug_profile_labels(int which, char* buf, int cap) {
-  TACO_REQUIRE(which >= 0 && which < 4 && buf && cap > 0, "profile_labels: bad arguments");
-  ProfRing& r = g_prof[which];
-  int pos = 0;
-  for (int i = 0; i < r.n; ++i) {
-    const int w = snprintf(buf + pos, cap - pos, "%s\n", r.label[i]);
-    if (w < 0 || pos + w >= cap) break;
-    pos += w;
-  }
-  buf[pos < cap ? pos : cap - 1] = 0;
-  return r.n;
-}
+extern "C" int taco_debug_profile_labels(int which, char* buf, int cap) { return prof_labels(which, buf, cap); }
 
 extern "C" int taco_profile_read(int which, float* ms, int cap) { return taco_profile_read2(which, ms, nullptr, cap); }

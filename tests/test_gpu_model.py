@@ -533,7 +533,7 @@ def test_medium_shape_with_optional_paths(built_lib, knob, monkeypatch):
 
 
 def test_tail_event_plan_replays_the_learning_call(built_lib, monkeypatch):
-    """Cross-stream forks / joins wait for a stop event that rides on the producing stream's last launch (common.h, layout.hip).
+    """Cross-stream forks / joins wait for a stop event that rides on the producing stream's last launch (stream.h, stream.hip).
     Which launches carry one is LEARNED: the first call of a kind / shape puts an event on every launch, later calls only on the
     launches a fork / join / gradient segment consumed.  Same inputs, TACO_DETERMINISTIC=1 (fixed summation orders, so a race
     would show as a changed bit): the learning call, three planned calls, a call on recorded markers (TACO_TAIL_EVENTS=0), a call
