@@ -89,10 +89,7 @@ __device__ __forceinline__ Pl3 zero_pl3() {
 // TACO_GEMM2_BF16X (read on every launch): 1 (default) = the fp32 products of the big GEMM kernels are formed on the bf16 matrix
 // pipe from exact three-way operand splits (fp32-grade results, 3/8 of the matrix-pipe time); 0 = v_mfma_f32_32x32x2_f32, the
 // form of rounds 2-4 (A/B runs, bisecting).
-inline bool env_bf16x() {
-  const char* e = getenv("TACO_GEMM2_BF16X");
-  return !(e && atoi(e) == 0);
-}
+inline bool env_bf16x() { return sw_on<SW_GEMM2_BF16X>(); }
 
 // Longest accumulation CHAIN (k-products added into one accumulator register) a launch may have on the bf16x3 form; longer chains
 // take the fp32 MFMA form.  Why (round 6; tools/micro/mfma_bf16_probe.hip, tools/bf16x3_chain_probe.py, profiles/r06_mfma_probe.txt,
@@ -107,9 +104,6 @@ inline bool env_bf16x() {
 // input gradient -- are k-split into chains of 768-1741, the weight gradients into row ranges of 320-720); what the bound catches is
 // a plain deep call (taco_conv_gemm with K x taps > 2048) and TACO_DETERMINISTIC=1's one-workgroup-per-tile weight gradients.
 // TACO_BF16X_MAX_CHAIN overrides (probing).
-inline int bf16x_max_chain() {
-  const char* e = getenv("TACO_BF16X_MAX_CHAIN");
-  return e ? atoi(e) : 2048;
-}
+inline int bf16x_max_chain() { return sw_int<SW_BF16X_MAX_CHAIN>(); }
 
 }  // namespace

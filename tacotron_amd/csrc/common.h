@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "../../include/taco_hip.h"
+#include "switches.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -123,7 +124,4 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 // TACO_DETERMINISTIC=1: every reduction that is otherwise combined with fp32 atomics (split-M weight gradients, the K-way conv
 // bank input gradient, BN / bias column sums, the embedding scatter) runs in a fixed order instead -- slower, but two runs of
 // the same step give bit-identical gradients (needed to bisect a training divergence).  Read on every call.
-static inline bool taco_deterministic() {
-  const char* e = getenv("TACO_DETERMINISTIC");
-  return e && atoi(e) != 0;
-}
+static inline bool taco_deterministic() { return sw_on<SW_DETERMINISTIC>(); }

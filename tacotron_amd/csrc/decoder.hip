@@ -1373,7 +1373,7 @@ int pick_cluster(K kernel, size_t smem, int B, int want) {
 // mat-vecs (TACO_DEC_NO_LRES=1 disables it, for A/B runs).
 void lres_plan(size_t& smem, int& r0, int& r1) {
   r0 = r1 = 0;
-  if (getenv("TACO_DEC_NO_LRES")) return;
+  if (sw_on<SW_DEC_NO_LRES>()) return;
   for (int l = 0; l < 2; ++l)
     for (int rows = 8; rows >= 4; rows -= 4)
       if (smem + (size_t)rows * NT * 16 <= (size_t)158 * 1024) {
@@ -1384,13 +1384,10 @@ void lres_plan(size_t& smem, int& r0, int& r1) {
 }
 int probe_bits() {
   if (!kProbes) return 0;
-  return (getenv("TACO_DEC_FAKEW") ? 1 : 0) | (getenv("TACO_DEC_FAKEX") ? 2 : 0) | (getenv("TACO_DEC_NOPF") ? 8 : 0) |
-         (getenv("TACO_DEC_NOLIVE") ? 16 : 0);
+  return (sw_on<SW_DEC_FAKEW>() ? 1 : 0) | (sw_on<SW_DEC_FAKEX>() ? 2 : 0) | (sw_on<SW_DEC_NOPF>() ? 8 : 0) | (sw_on<SW_DEC_NOLIVE>() ? 16 : 0);
 }
 int env_cluster(int dflt) {
-  const char* e = getenv("TACO_DEC_CLUSTER");
-  if (!e) return dflt;
-  const int v = atoi(e);
+  const int v = sw_int<SW_DEC_CLUSTER>();
   return (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32) ? v : dflt;
 }
 

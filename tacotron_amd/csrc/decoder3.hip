@@ -2381,7 +2381,7 @@ static bool xcd_local_exchange_allowed() {
     bool ok = false;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess)
       ok = strncmp(prop.gcnArchName, "gfx950", 6) == 0 && prop.multiProcessorCount == 256;
-    if (const char* e = getenv("TACO_DEC_ALLOW_XCD_LOCAL")) ok = atoi(e) != 0;   // (bring-up of a new part: force either way)
+    if (const char* e = sw_text<SW_DEC_ALLOW_XCD_LOCAL>()) ok = atoi(e) != 0;   // (bring-up of a new part: force either way)
     cache[dev] = ok ? 1 : -1;
   }
   return cache[dev] > 0;
@@ -2389,8 +2389,7 @@ static bool xcd_local_exchange_allowed() {
 
 static int g_dec_mode = 0;
 static int dec_mode() {
-  const char* v3 = getenv("TACO_DEC_V3");
-  const int floor = (v3 && atoi(v3) == 0) ? 2 : (getenv("TACO_DEC_V3_AGENT") ? 1 : 0);
+  const int floor = sw_int<SW_DEC_V3>() == 0 ? 2 : (sw_on<SW_DEC_V3_AGENT>() ? 1 : 0);
   return floor > g_dec_mode ? floor : g_dec_mode;
 }
 extern "C" int taco_decoder_mode(int mode) {
@@ -2416,7 +2415,7 @@ static int launch3_chunks(Args& a, int which, hipStream_t s) {
   }
   a.xcc_table_ofs = (int)(decoder_xchg_bytes(a.B, a.Tt) / 4 - 256);   // last 1 KB of the exchange area
   a.fast_ok = (dec_mode() == 0 && xcd_local_exchange_allowed()) ? 1 : 0;
-  a.fakew = kProbes3 ? ((getenv("TACO_DEC_FAKEX") ? 2 : 0)) : 0;
+  a.fakew = kProbes3 && sw_on<SW_DEC_FAKEX>() ? 2 : 0;
   a.P = P3;
   const int n = cdiv(a.B, 32);
   const Launch3<Args> full = pick3(a, 32), last = pick3(a, a.B - 32 * (n - 1));
@@ -2432,8 +2431,7 @@ static int launch3_chunks(Args& a, int which, hipStream_t s) {
 }
 
 int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s) {
-  const char* env = getenv("TACO_DEC_V3");
-  if ((env && atoi(env) == 1) || !a.hoisted) return TACO_ENOTFOUND;   // TACO_DEC_V3=1: forward only (A/B runs)
+  if (sw_int<SW_DEC_V3>() == 1 || !a.hoisted) return TACO_ENOTFOUND;   // TACO_DEC_V3=1: forward only (A/B runs)
   return launch3_chunks(a, 1, s);
 }
 

@@ -712,10 +712,8 @@ int launch_conv_gemm_tapsplit(const ConvGemmProblem& p, float* slabs, int64_t sl
           bestS = S;
         }
       }
-      if (const char* e = getenv("TACO_KSPLIT")) {   // tuning override
-        const int v = atoi(e);
-        if (v >= 1 && v <= maxS) bestS = v;
-      }
+      const int forced = sw_int<SW_KSPLIT>();   // tuning override
+      if (forced >= 1 && forced <= maxS) bestS = forced;
       if (bestS >= 2) {
         ConvGemmBatch b;
         b.n = bestS;
@@ -792,12 +790,8 @@ static void dispatch_tn(int flags, dim3 grid, hipStream_t s, const GemmTnArgs& a
 
 // Workgroups a weight-gradient launch aims for (TACO_TN_BLOCKS overrides; swept on S1: 384 / 768 / 1536 / 3072 -> family 5.17 / 4.67 / 4.49 / 4.45 ms per step).
 static int tn_block_target() {
-  static const int v = [] {
-    const char* e = getenv("TACO_TN_BLOCKS");
-    const int x = e ? atoi(e) : 0;
-    return x > 0 ? x : 3072;
-  }();
-  return v;
+  const int x = sw_int<SW_TN_BLOCKS>();
+  return x > 0 ? x : 3072;
 }
 
 // Validates one problem, derives its vector flags and split plan.  Returns the tile size used (64 or 128).
@@ -815,16 +809,14 @@ static int plan_gemm_tn(GemmTnArgs& a, bool force_small, dim3& grid, int64_t gro
       ((int64_t)a.M + 16) * a.ldy * 4 < lim31)
     a.flags |= 2;
   // taps merged into K where K is no multiple of the 64-row tile (kernels.h GemmTnArgs::ktap; vector A operand only; |shift| <= 16)
-  const char* em = getenv("TACO_TN_MERGE_TAPS");   // (0: one tile row per tap, rounds 1-6; read per launch so that a test can cover both)
-  const bool merge_taps = !(em && atoi(em) == 0);
+  const bool merge_taps = sw_on<SW_TN_MERGE_TAPS>();   // (0: one tile row per tap, rounds 1-6; a test covers both)
   if (merge_taps && a.ktap == 0 && (a.flags & 1) && a.taps > 1 && a.taps <= 17 && a.K % 64 != 0 && a.pad_l <= 16 && a.taps - 1 - a.pad_l <= 16) {
     a.ktap = a.K;
     a.K *= a.taps;
     a.taps = 1;
   }
   // TACO_TN_BM=64|128 forces the tile (tuning harness); TACO_TN_BIG_TILES = least number of 128 x 128 tiles for the big tile
-  static const int force_bm = [] { const char* e = getenv("TACO_TN_BM"); return e ? atoi(e) : 0; }();
-  static const int big_tiles = [] { const char* e = getenv("TACO_TN_BIG_TILES"); return e ? atoi(e) : 128; }();
+  const int force_bm = sw_int<SW_TN_BM>(), big_tiles = sw_int<SW_TN_BIG_TILES>();
   bool big = !force_small && (int64_t)cdiv(a.K, 128) * cdiv(a.N, 128) * a.taps * a.batch >= big_tiles && a.K >= 128 && a.N >= 128;
   if (!force_small && force_bm == 128 && a.K >= 128 && a.N >= 128) big = true;
   if (force_bm == 64) big = false;
@@ -844,8 +836,7 @@ static int plan_gemm_tn(GemmTnArgs& a, bool force_small, dim3& grid, int64_t gro
   a.splits = splits;
   a.chunk = chunk;
   grid = dim3(cdiv(a.K, bm), cdiv(a.N, bm), a.batch * a.taps * splits);
-  const char* ex = getenv("TACO_TN_XCD");   // XCD-aware block order (0: plain); read per launch so that a test can cover both orders
-  a.xcd = ex ? atoi(ex) : 1;
+  a.xcd = sw_int<SW_TN_XCD>();   // XCD-aware block order (0: plain); a test covers both orders
   return bm;
 }
 

@@ -956,13 +956,10 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 struct Variant {
   int bk, ns;
 };
-Variant env_variant() {   // read on every launch (tests and the tuning harness switch variants inside one process)
-  Variant r{16, 4};
-  if (const char* e = getenv("TACO_GEMM2_VARIANT")) {   // "<BK>x<stages>": 16x4 (default), 32x2 (forward conv banks), 32x3, 16x3, 16x5
-    int bk = 0, ns = 0;
-    if (sscanf(e, "%dx%d", &bk, &ns) == 2 && (bk == 16 || bk == 32) && ns >= 2 && ns <= 5) r = Variant{bk, ns};
-  }
-  return r;
+Variant parse_variant(const char* e) {   // "<BK>x<stages>": 16x4 (default), 32x2 (forward conv banks), 32x3, 16x3, 16x5
+  int bk = 0, ns = 0;
+  if (e && sscanf(e, "%dx%d", &bk, &ns) == 2 && (bk == 16 || bk == 32) && ns >= 2 && ns <= 5) return Variant{bk, ns};
+  return Variant{16, 4};
 }
 template <int BK, int NS, int BX = 0>
 int launch_variant(const Gemm2Args& g, int tiles, hipStream_t s) {
@@ -1071,8 +1068,7 @@ const void* weight_image_find(const float* W, int ldw, int taps, int K, int N, i
 }
 
 int gemm2_min_tiles() {
-  const char* e = getenv("TACO_GEMM2_MIN_TILES");   // 0 disables the second-generation kernel
-  return e ? atoi(e) : 160;
+  return sw_int<SW_GEMM2_MIN_TILES>();   // 0 disables the second-generation kernel
 }
 
 // Returns TACO_ENOTFOUND (nothing launched) when the batch does not meet the DMA contract or is too small to fill the chip
@@ -1159,7 +1155,7 @@ int launch_conv_gemm2(ConvGemmBatch& batch, hipStream_t stream, bool force) {
   if (tiles < min_tiles) return TACO_ENOTFOUND;
   if (!any_pool) {   // (pooled batches were promised to their caller by conv_gemm2_would_launch: no debug window for them)
     const int idx = g_win_idx++;
-    if (getenv("TACO_GEMM2_TRACE"))
+    if (sw_on<SW_GEMM2_TRACE>())
       for (int i = 0; i < batch.n; ++i)
         fprintf(stderr, "gemm2 #%d.%d M=%d N=%d K=%d taps=%d T=%d pad_l=%d act=%d keep=%d res=%d pre=%d aff=%d atomic=%d bias_stride=%d lda=%d ldw=%d ldc=%d\n",
                 idx, i, batch.p[i].M, batch.p[i].N, batch.p[i].K, batch.p[i].taps, batch.p[i].T, batch.p[i].pad_l, batch.p[i].act,
@@ -1195,11 +1191,9 @@ int launch_conv_gemm2(ConvGemmBatch& batch, hipStream_t stream, bool force) {
       return p.it1 > 0 ? (int64_t)(p.it1 - p.it0) : (int64_t)p.taps * ((p.K + 31) / 32);
     };
     for (int i = 1; i < batch.n; ++i) same = same && depth(g.batch.p[i]) == depth(g.batch.p[0]);
-    const char* e = getenv("TACO_GEMM2_XCD");
-    g.xcd_map = (same && !(e && atoi(e) == 0)) ? 1 : 0;
+    g.xcd_map = (same && sw_on<SW_GEMM2_XCD>()) ? 1 : 0;
     // conv-bank order: 16 or 8 problems of different depth with the same number of tiles each (g.batch.p is sorted deepest first)
-    const char* eb = getenv("TACO_GEMM2_BANK_XCD");
-    bool bank = !same && !(eb && atoi(eb) == 0) && (batch.n == 16 || batch.n == 8);
+    bool bank = !same && sw_on<SW_GEMM2_BANK_XCD>() && (batch.n == 16 || batch.n == 8);
     const int t = g.mt[0] * cdiv(g.batch.p[0].N, TN);
     for (int i = 1; i < batch.n && bank; ++i) bank = g.mt[i] * cdiv(g.batch.p[i].N, TN) == t;
     if (bank) {
@@ -1218,8 +1212,9 @@ int launch_conv_gemm2(ConvGemmBatch& batch, hipStream_t stream, bool force) {
       tiles = batch.n == 16 ? 16 * t : 8 * 2 * h;   // grid: 8 XCDs x the longest share
     }
   }
-  Variant v = env_variant();
-  if (!getenv("TACO_GEMM2_VARIANT")) {
+  const char* const forced = sw_text<SW_GEMM2_VARIANT>();   // (tests and the tuning harness switch variants inside one process)
+  Variant v = parse_variant(forced);
+  if (!forced) {
     // Both forms hold 64 KB of LDS (two workgroups per CU).  Four 16-deep stages keep 48 k-columns in flight instead of 32:
     // inside a train step the operands come from HBM / the Infinity Cache, not from a warm L2, and the deeper ring is what
     // the launches with long rows wait less with (same-box family traces, profiles/r04_gemm_variants.txt: post-net proj1
@@ -1239,8 +1234,7 @@ int launch_conv_gemm2(ConvGemmBatch& batch, hipStream_t stream, bool force) {
   }
   if (env_bf16x() && chain <= bf16x_max_chain()) {   // 16-deep tiles only (K = 80, K % 32 != 0 and the forward banks alike); the ring depth follows the variant
     // every problem's weights have a pre-split plane image (weight_image_add): the B-image form.  TACO_GEMM2_BSPLIT=0: never (A/B runs).
-    const char* eb2 = getenv("TACO_GEMM2_BSPLIT");
-    bool img = !(eb2 && atoi(eb2) == 0);
+    bool img = sw_on<SW_GEMM2_BSPLIT>();
     for (int i = 0; i < g.batch.n && img; ++i) {
       ConvGemmProblem& p = g.batch.p[i];
       p.Wimg = weight_image_find(p.W, p.ldw, p.taps, p.K, p.Nld > 0 ? p.Nld : p.N, &p.img_its);
@@ -1249,8 +1243,7 @@ int launch_conv_gemm2(ConvGemmBatch& batch, hipStream_t stream, bool force) {
     if (img) {
       __atomic_fetch_add(&g_img_launches, (int64_t)1, __ATOMIC_RELAXED);
       // 20 KB per stage: three stages = 60 KB (two workgroups per CU), four = 80 KB (2 x 80 = the CU's whole 160 KB)
-      static const int bi_ns = [] { const char* e = getenv("TACO_GEMM2_BI_NS"); return e ? atoi(e) : 3; }();
-      if (bi_ns == 4) return launch_variant<16, 4, 2>(g, tiles, stream);
+      if (sw_int<SW_GEMM2_BI_NS>() == 4) return launch_variant<16, 4, 2>(g, tiles, stream);
       return launch_variant<16, 3, 2>(g, tiles, stream);
     }
     if (v.bk == 16 && v.ns == 3) return launch_variant<16, 3, 1>(g, tiles, stream);
@@ -1288,9 +1281,7 @@ bool gemm_tn2_eligible(const GemmTnArgs& a) {
   // (e.g. post proj1 dW 207 vs 199 us, dense dW 140 vs 71 us, bank dW 70 vs 43 us): the weight gradients are split-M launches
   // whose workgroups run only 8-12 stages before a 128 x 128 atomic epilogue, and the interleaved column map of the b64
   // fragment reads turns that epilogue into two half-used-cache-line atomics per row.  Kept for the tuning harness.
-  const char* e2 = getenv("TACO_TN2");   // read on every call (the A/B harness toggles it inside one process)
-  const bool on = e2 && atoi(e2) != 0;
-  if (!on || gemm2_min_tiles() <= 0 || taco_deterministic()) return false;
+  if (!sw_on<SW_TN2>() || gemm2_min_tiles() <= 0 || taco_deterministic()) return false;
   if (a.batch != 1 || a.K < 96 || a.N < 96 || a.M < 512) return false;
   if (a.lda % 4 || a.ldy % 4 || a.K % 4 || !al16(a.A) || !al16(a.Y)) return false;
   const int nld = a.Nld > 0 ? a.Nld : (a.N % 4 == 0 ? a.N : 0);

@@ -45,7 +45,7 @@ inline void prof_end(int which, int slot, hipStream_t s) { taco_prof_end(which, 
 
 // multi-speaker encoder: the fused form (adapters inside the highway stack kernels, round 6) unless TACO_SPK_UNFUSED=1
 static bool spk_fused_form(const CbhgP& c) {
-  return c.spk && c.has_adapt[0] && c.has_adapt[1] && c.has_adapt[2] && c.has_adapt[3] && !getenv("TACO_SPK_UNFUSED");
+  return c.spk && c.has_adapt[0] && c.has_adapt[1] && c.has_adapt[2] && c.has_adapt[3] && !sw_on<SW_SPK_UNFUSED>();
 }
 
 struct CbhgBufs {
@@ -108,8 +108,7 @@ int cbhg_fwd(const float* P, const CbhgP& c, const float* x, int B, int T, const
   // backward pass will read them.  Shapes the DMA kernel does not take run conv and pool as two passes.
   const float bn_rs = 1.0f / sqrtf(1.0f + kBnEps);   // BN in inference mode: gamma / sqrt(moving_var(=1) + eps), folded in the epilogue
   {
-    const char* nf = getenv("TACO_NO_POOL_FUSE");   // A/B and test switch: always the two-pass form
-    const bool no_fuse = nf && atoi(nf) != 0;
+    const bool no_fuse = sw_on<SW_NO_POOL_FUSE>();   // A/B and test switch: always the two-pass form
     ConvGemmBatch batch;
     auto fill = [&](bool fused) {
       batch.n = c.K;
@@ -323,7 +322,7 @@ void note_decoder_fallback(int B, int Tt, int r) {
   static std::map<std::tuple<int, int, int>, bool> seen;
   std::lock_guard<std::mutex> g(mu);
   bool& s = seen[std::make_tuple(B, Tt, r)];
-  if (s || getenv("TACO_QUIET")) return;
+  if (s || sw_on<SW_QUIET>()) return;
   s = true;
   const int mode = taco_decoder_mode(-1);
   if (mode >= 2)
@@ -339,8 +338,7 @@ void note_decoder_fallback(int B, int Tt, int r) {
 // (transposed) weights; `build`: queue the images of that phase for weight_images_build (taco_forward / taco_infer), or only
 // register them (taco_backward: they were built by the taco_forward that ran on this workspace).  TACO_GEMM2_BSPLIT=0: no images.
 static int register_weight_images(const Layouts& L, const WsLayout& W, const float* P, float* ws, bool train, int phase, bool build) {
-  const char* e = getenv("TACO_GEMM2_BSPLIT");
-  if ((e && atoi(e) == 0) || W.wimg < 0) return TACO_OK;
+  if (!sw_on<SW_GEMM2_BSPLIT>() || W.wimg < 0) return TACO_OK;
   int rc = TACO_OK;
   int64_t off = 0;
   for_each_weight_image(L.P, L.T, train, [&](int ksrc, int64_t koff, int kld, int dsrc, int64_t doff, int dld, int taps, int K, int N, bool bwd) {
@@ -405,11 +403,12 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
   // by the previous output (scheduled sampling); decoder.hip, the fallback, still writes all of them itself.
   if (train) TACO_TRY(ib.copy2d(ws + W.prein, kMel, mel + kMel * (r - 1), R80, B * Td, kMel));
   TACO_TRY(build_dec_composites(P, PL, W, ws, r, ib, sd));
+  const bool prep_early = train && sw_on<SW_BWD_PREP_EARLY>();
   if (train) {
     // everything the backward pass derives from the parameters alone (transposed / tap-flipped weight copies, transposed
     // composites) is built here, beside the encoder, instead of at the head of taco_backward's critical path
     // (round 6: enqueued beside the POST-NET bi-GRU recurrence instead -- `bwd_prep` below; TACO_BWD_PREP_EARLY=1: here, as in rounds 2-5)
-    if (getenv("TACO_BWD_PREP_EARLY")) {
+    if (prep_early) {
       TACO_TRY(prepare_transposes(P, PL, L.T, ws + W.paramsT, r, sd));
       TACO_TRY(register_weight_images(L, W, P, ws, train, 1, true));
       TACO_TRY(weight_images_build(sd));
@@ -432,12 +431,12 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
     }
   }
   // encoder pre_net (tacotron.py:128) on the embedding gathered above
-  if (!getenv("TACO_NO_PRENET_FUSE")) {   // both layers in one launch (prenet.hip)
+  if (!sw_on<SW_NO_PRENET_FUSE>()) {   // both layers in one launch (prenet.hip)
     PrenetArgs pa;
     pa.x = ws + W.emb; pa.w1 = P + PL.enc_pre1.w; pa.b1 = P + PL.enc_pre1.b; pa.w2 = P + PL.enc_pre2.w; pa.b2 = P + PL.enc_pre2.b;
     pa.keep1 = train ? ek1 : nullptr; pa.keep2 = train ? ek2 : nullptr;
     pa.y1 = ws + W.p1; pa.y2 = ws + W.p2; pa.M = M1;
-    pa.trace = getenv("TACO_PN_TRACE") ? reinterpret_cast<long long*>(ws + W.err + 400) : nullptr;
+    pa.trace = sw_on<SW_PN_TRACE>() ? reinterpret_cast<long long*>(ws + W.err + 400) : nullptr;
     TACO_TRY(launch_prenet_fwd(pa, s));
   } else {
     ConvGemmProblem p = dense_problem(ws + W.emb, kEmbed, P + PL.enc_pre1.w, kPre1, P + PL.enc_pre1.b, ws + W.p1, kPre1, M1,
@@ -498,7 +497,7 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
   da.pre2 = train ? ws + W.stash + kStP2 : nullptr;
   da.ldpre2 = kStRec;
   da.xchg = ws + W.xchg; da.err = reinterpret_cast<int*>(ws + W.err);
-  da.trace = getenv("TACO_DEC_TRACE") ? reinterpret_cast<long long*>(ws + W.err + 16) : nullptr;
+  da.trace = sw_on<SW_DEC_TRACE>() ? reinterpret_cast<long long*>(ws + W.err + 16) : nullptr;
   da.B = B; da.Tt = Tt; da.Td = Td; da.r = r; da.P = 1;
   if (lengths) {
     da.lengths = lengths;
@@ -547,7 +546,7 @@ int forward_impl(const TacoShape& sh, const Layouts& L, const WsLayout& W, const
     if (q != at && sl == s) sl = q;   // (make sure the join below covers it)
     return TACO_OK;
   };
-  const bool late_prep = train && !getenv("TACO_BWD_PREP_EARLY");
+  const bool late_prep = train && !prep_early;
   TACO_TRY(cbhg_fwd(P, PL.post, s2s, B, Td * r, pb, train, s, late_prep ? &bwd_prep : nullptr));
   {
     // output rows are 1025 floats apart: gemm2.hip writes them with its shifted float4 epilogue (92 vs 105 us with scalar stores)
@@ -754,8 +753,7 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
     // gradients).  Cut along k instead (launch_conv_gemm_tapsplit: S grouped chunks + ordered slab sum; the slab area is free until
     // the bank gather at the end of this pass).  TACO_XPROJ_BWD_KSPLIT=0: one launch, as in rounds 1-6.
     const ConvGemmProblem q = dense_problem(dxg, 6 * kCb, PT + t.gru_x, kCb, nullptr, gh, kCb, M, kCb, 6 * kCb, TACO_ACT_NONE);
-    const char* e = getenv("TACO_XPROJ_BWD_KSPLIT");
-    if (w.tapsplit && !(e && atoi(e) == 0) && !taco_deterministic()) TACO_TRY(launch_conv_gemm_tapsplit(q, w.tapsplit, w.tapsplit_floats, s));
+    if (w.tapsplit && sw_on<SW_XPROJ_BWD_KSPLIT>() && !taco_deterministic()) TACO_TRY(launch_conv_gemm_tapsplit(q, w.tapsplit, w.tapsplit_floats, s));
     else TACO_TRY(launch_conv_gemm(q, s));
   }
   // ---- highway layers 3..0 (with their input adapters / speaker sites) ----
@@ -906,8 +904,7 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
     p.A = dz1; p.lda = c.c1; p.W = PT + t.p1; p.ldw = KC; p.C = dpool; p.ldc = KC; p.M = M; p.N = KC; p.K = c.c1;
     p.taps = 3; p.T = T; p.pad_l = 1; p.act = TACO_ACT_NONE;
     int rc = TACO_ENOTFOUND;
-    const char* nf = getenv("TACO_NO_POOL_FUSE");
-    if (!taco_deterministic() && !(nf && atoi(nf) != 0)) {
+    if (!taco_deterministic() && !sw_on<SW_NO_POOL_FUSE>()) {
       ConvGemmProblem q = p;
       q.C = dbank; q.pool = 2; q.pool_x = w.bank; q.scale = P + c.bank_g; q.shift = P + c.bank_be;
       q.scale_mul = 1.0f / sqrtf(1.0f + kBnEps); q.pool_dgamma = G + c.bank_g; q.pool_dbeta = G + c.bank_be;
@@ -968,7 +965,7 @@ int cbhg_bwd(const float* P, const float* PT, float* G, const CbhgP& c, const Cb
       for (int k = 2; k <= c.K; ++k) contiguous = contiguous && t.bank[k - 1] == t.bank[k - 2] + (int64_t)(k - 1) * kCb * c.cin;
       int rc = TACO_ENOTFOUND;
       const int64_t mn = (int64_t)M * c.cin;
-      if (contiguous && w.tapsplit && c.cin % 4 == 0 && getenv("TACO_NO_BANK_GATHER") == nullptr) {
+      if (contiguous && w.tapsplit && c.cin % 4 == 0 && !sw_on<SW_NO_BANK_GATHER>()) {
         const int taps = c.K * (c.K + 1) / 2, nit = taps * (kCb / 32);
         const int mtiles = cdiv(M, 128) * cdiv(c.cin, 128);
         int64_t S = 512 / mtiles;
@@ -1122,7 +1119,8 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   // ONE batched init launch for every accumulator of the pass: the gradient buffer, [d keys | E] (one (M1, 512) buffer), the small
   // decoder weight-gradient factors, the two CBHG input-gradient accumulators (when they have buffers of their own) and the
   // decoder exchange area (the forward kernel is long done with it)
-  const bool own_dx = getenv("TACO_NO_SIDE_TN") == nullptr && side_stream_or_null() != nullptr;
+  const bool side_tn_on = !sw_on<SW_NO_SIDE_TN>();
+  const bool own_dx = side_tn_on && side_stream_or_null() != nullptr;
   {
     InitBatch ib;
     TACO_TRY(ib.fill(G, PL.total));
@@ -1159,7 +1157,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   // removed in round 4 together with the data-parallel mode that overlapped collectives with that launch.)
   BwdScratch scp = sc;
   float* dPostIn = sc.gC;   // (M2, 80)
-  const bool side_tn = side != s && getenv("TACO_NO_SIDE_TN") == nullptr;
+  const bool side_tn = side != s && side_tn_on;
   if (side_tn) {
     scp.alt_dpj1 = ws + W.post_dpj1; scp.alt_dz1 = ws + W.post_dz1; scp.alt_dpool = ws + W.post_dpool;
     dPostIn = ws + W.post_dx;
@@ -1201,7 +1199,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
     a.dkeys = ws + W.dkeys; a.ldk = 2 * kAtt; a.datt_v = ws + W.dattv;
     a.hoisted = 1;
     a.xchg = ws + W.xchg; a.err = reinterpret_cast<int*>(ws + W.err) + 1;
-    a.trace = getenv("TACO_DEC_TRACE") ? reinterpret_cast<long long*>(ws + W.err + 16) + 128 : nullptr;
+    a.trace = sw_on<SW_DEC_TRACE>() ? reinterpret_cast<long long*>(ws + W.err + 16) + 128 : nullptr;
     a.B = B; a.Tt = Tt; a.Td = Td; a.r = r; a.P = 1;
     a.xchg_zeroed = 1;
     const int slot = prof_begin(1, s);
@@ -1344,7 +1342,7 @@ extern "C" int taco_backward(const TacoShape* shape, const float* params, const 
   float* dz2 = pre_dz2;
   float* dz1 = pre_dz1;
   float* dEmb = pre_demb;
-  if (!getenv("TACO_NO_PRENET_FUSE")) {
+  if (!sw_on<SW_NO_PRENET_FUSE>()) {
     // the activation-gradient chain d p2 -> dz2 -> dz1 -> d embedding in one launch (prenet.hip); the two weight gradients follow
     PrenetArgs pa;
     pa.x = dP2; pa.x_out = dz2; pa.y2_in = ws + W.p2; pa.y1_in = ws + W.p1; pa.keep2 = enc_keep2; pa.keep1 = enc_keep1;

@@ -120,8 +120,8 @@ void tail_touch(hipStream_t s) {
 }
 // opens the scope of one C-ABI call; key = kind + shape of the call (its launch plan)
 void tail_open(uint64_t key) {
-  const char* e = getenv("TACO_TAIL_EVENTS");
-  g_tail_on = !(e && atoi(e) == 0);
+  const int mode = sw_int<SW_TAIL_EVENTS>();
+  g_tail_on = mode != 0;
   g_plan = nullptr;
   g_learning = false;
   for (TailTrack& t : g_tail) {
@@ -141,7 +141,7 @@ void tail_open(uint64_t key) {
     g_plan->used = true;
     g_plan->key = key;
   }
-  if (!g_plan->learned || (e && atoi(e) == 2)) {   // (TACO_TAIL_EVENTS=2: an event on every launch, always)
+  if (!g_plan->learned || mode == 2) {   // (TACO_TAIL_EVENTS=2: an event on every launch, always)
     g_learning = true;
     for (auto& row : g_plan->bits)
       for (uint64_t& w : row) w = 0;
@@ -382,8 +382,7 @@ SideStream& side_stream() {
   (void)hipGetDevice(&dev);
   SideStream& x = ss[dev & 15];
   if (!x.side && !x.off) {
-    const char* e = getenv("TACO_NO_OVERLAP");
-    if ((e && atoi(e) != 0) || hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) != hipSuccess ||
+    if (sw_on<SW_NO_OVERLAP>() || hipStreamCreateWithFlags(&x.side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&x.ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&x.ev_join, hipEventDisableTiming) != hipSuccess) {
       x.side = nullptr;

@@ -516,7 +516,8 @@ def test_pooled_bank_epilogue_tile_edges(built_lib, B, Tt, Td, monkeypatch):
 
 @pytest.mark.parametrize('knob', ['TACO_NO_BANK_GATHER=1', 'TACO_GEMM2_XCD=0', 'TACO_GEMM2_BF16X=0', 'TACO_DEC_NO_LRES=1',
                                   'TACO_TN_XCD=0', 'TACO_GEMM2_BANK_XCD=0', 'TACO_GEMM2_BSPLIT=0', 'TACO_TN_MERGE_TAPS=0',
-                                  'TACO_TAIL_EVENTS=0', 'TACO_TAIL_EVENTS=2', 'TACO_XPROJ_BWD_KSPLIT=0'])
+                                  'TACO_TAIL_EVENTS=0', 'TACO_TAIL_EVENTS=2', 'TACO_XPROJ_BWD_KSPLIT=0',
+                                  'TACO_NO_SIDE_TN=1', 'TACO_BWD_PREP_EARLY=1'])
 def test_medium_shape_with_optional_paths(built_lib, knob, monkeypatch):
     """The fallback / A-B switches of the train step keep parity: the conv bank's input gradient as K atomic-accumulating problems
     (TACO_NO_BANK_GATHER=1: the path taken when the slabs do not fit or the kernels are not contiguous), gemm2's plain tile order
@@ -525,7 +526,9 @@ def test_medium_shape_with_optional_paths(built_lib, knob, monkeypatch):
     (TACO_TN_XCD=0, TACO_GEMM2_BANK_XCD=0: round 5's XCD-aware orders off) and the weight operand split in registers instead of
     read from the pre-split plane images (TACO_GEMM2_BSPLIT=0, round 6); cross-stream forks / joins through recorded marker packets
     (TACO_TAIL_EVENTS=0, rounds 1-6) or with a stop event on every launch (=2, the learning call's form) instead of the learned
-    launch plan; the bi-GRU x-projection's input gradient as one launch (TACO_XPROJ_BWD_KSPLIT=0)."""
+    launch plan; the bi-GRU x-projection's input gradient as one launch (TACO_XPROJ_BWD_KSPLIT=0); the CBHG
+    weight-gradient GEMMs on the caller's stream (TACO_NO_SIDE_TN=1) and the backward pass's parameter-only preparations beside
+    the encoder (TACO_BWD_PREP_EARLY=1, rounds 2-5)."""
     k, v = knob.split('=')
     monkeypatch.setenv(k, v)
     test_medium_shape_forward_backward(built_lib)
