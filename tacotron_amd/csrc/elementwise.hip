@@ -769,8 +769,11 @@ int launch_transpose_batch(TransposeBatch& b, hipStream_t s) {
   TACO_LAUNCH_CHECK("transpose_batch");
   return TACO_OK;
 }
-int launch_denorm_unframe(const float* out, const float* mean, const float* stdv, float* spec, float* mag_t, int B, int Td,
-                          int r, int C, hipStream_t s) {
+extern "C" int taco_denorm_unframe(const float* out, const float* mean, const float* stdv, float* spec, float* mag_t, int B,
+                                   int Td, int r, int C, void* stream) {
+  TACO_REQUIRE(out && mean && stdv && (spec || mag_t) && B > 0 && Td > 0 && r >= 1 && r <= 5 && C > 0,
+               "denorm_unframe: bad arguments");
+  hipStream_t s = as_stream(stream);
   const int F = (Td / 4) * 4 * r;
   TACO_REQUIRE(F > 0, "denorm_unframe: Td=%d holds no whole chunk of 4 steps", Td);
   TACO_KLAUNCH(denorm_unframe_kernel, dim3((C + 31) / 32, (F + 31) / 32, B), dim3(32, 8), 0, s, out, mean, stdv, spec,
@@ -794,7 +797,9 @@ int launch_clip_adam(float* p, const float* g, float* m, float* v, int64_t n, fl
   TACO_LAUNCH_CHECK("clip_adam");
   return TACO_OK;
 }
-int launch_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, hipStream_t s) {
+extern "C" int taco_fill_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, void* stream) {
+  TACO_REQUIRE(out && n > 0, "fill_bernoulli: bad arguments");
+  hipStream_t s = as_stream(stream);
   double t = (double)p_one * 4294967296.0;
   uint32_t thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : (t <= 0 ? 0u : (uint32_t)t);
   TACO_KLAUNCH(bernoulli_kernel, dim3(grid_for((n + 1) / 2)), dim3(kThreads), 0, s, out, n, thresh, seed);
@@ -813,9 +818,10 @@ __global__ void spin_kernel(long long ticks, int lds_words) {
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
   if (lds_words > 0 && spin_lds[(threadIdx.x * 7) % lds_words] == -12345) spin_lds[0] = 1;   // keeps the touch alive
 }
-int launch_spin(int blocks, int threads, int lds_bytes, int usec, hipStream_t s) {
+extern "C" int taco_debug_spin(int blocks, int threads, int lds_bytes, int usec, void* stream) {
   TACO_REQUIRE(blocks > 0 && threads > 0 && threads <= 1024 && lds_bytes >= 0 && lds_bytes <= 160 * 1024 && usec >= 0,
                "debug_spin: bad arguments");
+  hipStream_t s = as_stream(stream);
   if (lds_bytes > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(spin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) {
@@ -851,8 +857,9 @@ __global__ __launch_bounds__(512) void clock_probe_kernel(long long* out, int it
   }
   if (x == 12345.678f) out[2] = 1;   // keeps the chain alive
 }
-int launch_clock_probe(long long* out, int iters, hipStream_t s) {
+extern "C" int taco_debug_clock_probe(long long* out, int iters, void* stream) {   // out[0] = shader cycles, out[1] = 100 MHz ticks
   TACO_REQUIRE(out && iters > 0, "clock_probe: bad arguments");
+  hipStream_t s = as_stream(stream);
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   TACO_KLAUNCH(clock_probe_kernel, dim3(cus > 0 ? cus : 256), dim3(512), 0, s, out, iters, 0.999f, 0.001f);
@@ -956,8 +963,10 @@ __global__ __launch_bounds__(64) void fabric_probe_kernel(long long* out, fp_u64
   }
   if (b == 0) out[6] = iters;
 }
-int launch_fabric_probe(long long* out32, void* gran4k, const void* scratch, int64_t scratch_bytes, int iters, hipStream_t s) {
+extern "C" int taco_debug_fabric_probe(long long* out32, void* gran4k, const void* scratch, long long scratch_bytes, int iters,
+                                       void* stream) {
   TACO_REQUIRE(out32 && gran4k && scratch && scratch_bytes >= (32 << 20) && iters > 0, "fabric_probe: bad arguments");
+  hipStream_t s = as_stream(stream);
   TACO_KLAUNCH(fabric_probe_kernel, dim3(64), dim3(64), 0, s, out32, reinterpret_cast<fp_u64*>(gran4k),
                      reinterpret_cast<const unsigned*>(scratch), (long long)(scratch_bytes / 4), iters);
   TACO_LAUNCH_CHECK("fabric_probe");

@@ -275,13 +275,15 @@ FeatWs feat_ws(int B, int L) {
 
 }  // namespace
 
-int64_t audio_features_workspace_bytes(int B, int L) {
+// ---- C ABI (include/taco_hip.h)
+extern "C" int64_t taco_audio_features_workspace_bytes(int B, int L) {
   if (B <= 0 || L <= 0) return TACO_EINVAL;
   return feat_ws(B, L).bytes;
 }
 
-int launch_audio_features(const float* wave, const int* wave_len_host, const float* mel_basis, void* mel, void* stft, int* bounds,
-                          int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16, hipStream_t s) {
+extern "C" int taco_audio_features(const float* wave, const int* wave_len_host, const float* mel_basis, void* mel, void* stft,
+                                   int* bounds, int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16,
+                                   void* stream) {
   TACO_REQUIRE(wave && wave_len_host && mel_basis && mel && stft && bounds && kept && workspace,
                "audio_features: null pointer");
   TACO_REQUIRE(B > 0 && L > 0, "audio_features: B=%d L=%d", B, L);
@@ -295,6 +297,7 @@ int launch_audio_features(const float* wave, const int* wave_len_host, const flo
   for (int b = 0; b < B; ++b)
     TACO_REQUIRE(wave_len_host[b] >= 1 && wave_len_host[b] <= L, "audio_features: wave_len[%d]=%d outside 1..L=%d", b,
                  wave_len_host[b], L);
+  hipStream_t s = as_stream(stream);
   const FeatWs W = feat_ws(B, L);
   char* ws = static_cast<char*>(workspace);
   int* len_d = reinterpret_cast<int*>(ws + W.len);

@@ -1,4 +1,7 @@
-// kernels.h -- internal launch interface shared by the .hip translation units of libtaco_hip.so.
+// kernels.h -- internal launch interface shared by the .hip translation units of libtaco_hip.so: what one unit calls in another.
+// A C-ABI entry point (include/taco_hip.h) that needs nothing from another unit is defined beside its kernels and has no
+// declaration here: all of vocoder.hip and features.hip, and the op-level and probe entry points of elementwise.hip,
+// decoder.hip and stream.hip.
 #pragma once
 #include "common.h"
 #include "stream.h"
@@ -210,18 +213,11 @@ struct TransposeBatch {
   int n = 0;
 };
 int launch_transpose_batch(TransposeBatch& b, hipStream_t s);
-// inverse r-frame layout + de-normalisation (+ optional exp / transpose for the vocoder); see the kernel
-int launch_denorm_unframe(const float* out, const float* mean, const float* stdv, float* spec, float* mag_t, int B, int Td,
-                          int r, int C, hipStream_t s);
 constexpr int kSumsqParts = 256;
 int launch_sumsq(const float* x, int64_t n, float* out, hipStream_t s);  // out[0..kSumsqParts) = per-block sums of x^2 (overwritten)
 // err (nullable): two int32 decoder error words; if either is non-zero the update is skipped (gnorm_out = -1)
 int launch_clip_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float cap, int64_t step,
                      const float* sumsq, float* gnorm_out, const int32_t* err, hipStream_t s);
-int launch_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, hipStream_t s);
-int launch_spin(int blocks, int threads, int lds_bytes, int usec, hipStream_t s);
-int launch_clock_probe(long long* out, int iters, hipStream_t s);   // out[0] = shader cycles, out[1] = 100 MHz ticks of `iters` dependent FMAs
-int launch_fabric_probe(long long* out32, void* gran4k, const void* scratch, int64_t scratch_bytes, int iters, hipStream_t s);
 // Batched buffer initialisation: up to kMaxInitJobs zero-fills / (strided) copies of fp32 blocks in ONE launch instead of one
 // runtime memset / memcpy launch each (~5 us apiece, serialised on their stream).  Jobs of a batch must not overlap.
 constexpr int kMaxInitJobs = 16;
@@ -368,7 +364,6 @@ struct DecFwdArgs {
   int stop_end_offset = 0, stop_hold = 1, stop_min_steps = 1;
 };
 int64_t decoder_xchg_bytes(int B, int Tt);
-int decoder_last_cluster(int which);   // cluster width (workgroups per row) of the last forward (0) / backward (1) launch
 int launch_decoder_fwd(DecFwdArgs a, hipStream_t s);
 // decoder3.hip: clusters of 32 workgroups x up to 4 rows with register-resident weights.  TACO_ENOTFOUND (nothing enqueued) when
 // the shape is outside its scope (Tt > 256, r not in {2, 5}) or TACO_DEC_V3=0: the caller then takes launch_decoder_fwd.  B > 32 (round 6):
@@ -409,29 +404,3 @@ struct DecBwdArgs {
 };
 int launch_decoder_bwd(DecBwdArgs a, hipStream_t s);
 int launch_decoder3_bwd(DecBwdArgs a, hipStream_t s);   // decoder3.hip; TACO_ENOTFOUND outside its scope
-
-// ---------------------------------------------------------------- vocoder.hip
-// Griffin-Lim (audio.py:77-97).  mag_t / phase0 (B, 1025, F); wave (B, 300 (F - 1)); work: griffinlim_workspace_floats floats
-int64_t griffinlim_workspace_floats(int B, int F);
-int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, float* work, int B, int F, int n_iter, hipStream_t s);
-// the same per row (taco_hip.h taco_griffinlim_rows): row b over min(F, frames[b] * frames_per_unit) frames, frames (B) int32 on the
-// device; phase0 nullable (counter-hash phases from `seed`); work: griffinlim_rows_workspace_floats floats
-int64_t griffinlim_rows_workspace_floats(int B, int F);
-int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
-                           float* wave, float* work, int B, int F, int n_iter, hipStream_t s);
-// fast Griffin-Lim (taco_hip.h taco_griffinlim_fast): momentum rounds and the per-round convergence readout; frames and conv
-// nullable; work: griffinlim_fast_workspace_floats floats (the rows layout, the previous spectrum, the readout's partial sums)
-int64_t griffinlim_fast_workspace_floats(int B, int F);
-int launch_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
-                           float momentum, float* wave, float* conv, float* work, int B, int F, int n_iter, hipStream_t s);
-// waveform finishing (taco_hip.h taco_wave_finish): de-emphasis scan, energy trim, peak, fp32 / PCM16 emit; samples, out, pcm
-// nullable (not both of out and pcm); work: wave_finish_workspace_floats floats
-int64_t wave_finish_workspace_floats(int B, int L);
-int launch_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out, int16_t* pcm,
-                       int32_t* bounds, float* peak, void* workspace, int B, int L, hipStream_t s);
-
-// ---------------------------------------------------------------- features.hip
-// audio.process_audio (audio.py:38-65) for a batch: trim, drop / pad, pre-emphasis, STFT, mel, r-frame layout (taco_hip.h)
-int64_t audio_features_workspace_bytes(int B, int L);
-int launch_audio_features(const float* wave, const int* wave_len_host, const float* mel_basis, void* mel, void* stft, int* bounds,
-                          int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16, hipStream_t s);

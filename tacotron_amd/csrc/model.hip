@@ -1,5 +1,6 @@
-// model.hip -- host-side orchestration of the Tacotron hot path on one GPU + the C ABI (include/taco_hip.h).
-// Every function only ENQUEUES work on the caller's stream: no allocation, no synchronisation.
+// model.hip -- host-side orchestration of the Tacotron hot path on one GPU + the model-level part of the C ABI (include/taco_hip.h;
+// an entry point that launches one file's kernels is defined in that file).  Every function only ENQUEUES work on the caller's
+// stream: no allocation, no synchronisation.
 //
 //   taco_forward  = Tacotron.inference(train=True) + add_loss_op       (tacotron.py:107-165)
 //   taco_backward = opt.compute_gradients(loss)                        (tacotron.py:172)
@@ -1475,89 +1476,3 @@ extern "C" int taco_clear_error(const TacoShape* shape, int train, void* workspa
   const WsLayout& W = train ? L.Wtrain : L.Winfer;
   return taco_memset_async(static_cast<float*>(workspace) + W.err, 0, 512 * sizeof(float), as_stream(stream), "taco_clear_error");
 }
-
-extern "C" int taco_denorm_unframe(const float* output, const float* stft_mean, const float* stft_std, float* spec,
-                                   float* mag_t, int B, int Td, int r, int C, void* stream) {
-  TACO_REQUIRE(output && stft_mean && stft_std && (spec || mag_t) && B > 0 && Td > 0 && r >= 1 && r <= 5 && C > 0,
-               "denorm_unframe: bad arguments");
-  return launch_denorm_unframe(output, stft_mean, stft_std, spec, mag_t, B, Td, r, C, as_stream(stream));
-}
-
-extern "C" int64_t taco_griffinlim_workspace_bytes(int B, int F) {
-  if (B <= 0 || F < 5) return TACO_EINVAL;   // launch_griffinlim needs F >= 5 (centre padding of 1024 samples at hop 300)
-  return griffinlim_workspace_floats(B, F) * (int64_t)sizeof(float);
-}
-
-extern "C" int taco_griffinlim(const float* mag_t, const float* phase0, float* wave, void* workspace, int B, int F, int n_iter,
-                               void* stream) {
-  return launch_griffinlim(mag_t, phase0, wave, static_cast<float*>(workspace), B, F, n_iter, as_stream(stream));
-}
-
-extern "C" int64_t taco_griffinlim_rows_workspace_bytes(int B, int F) {
-  if (B <= 0 || F < 5) return TACO_EINVAL;
-  return griffinlim_rows_workspace_floats(B, F) * (int64_t)sizeof(float);
-}
-
-extern "C" int taco_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
-                                    int frames_per_unit, float* wave, void* workspace, int B, int F, int n_iter, void* stream) {
-  return launch_griffinlim_rows(mag_t, phase0, seed, frames, frames_per_unit, wave, static_cast<float*>(workspace), B, F, n_iter,
-                                as_stream(stream));
-}
-
-extern "C" int64_t taco_griffinlim_fast_workspace_bytes(int B, int F) {
-  if (B <= 0 || F < 5) return TACO_EINVAL;
-  return griffinlim_fast_workspace_floats(B, F) * (int64_t)sizeof(float);
-}
-
-extern "C" int taco_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
-                                    int frames_per_unit, float momentum, float* wave, float* conv, void* workspace, int B, int F,
-                                    int n_iter, void* stream) {
-  return launch_griffinlim_fast(mag_t, phase0, seed, frames, frames_per_unit, momentum, wave, conv, static_cast<float*>(workspace), B,
-                                F, n_iter, as_stream(stream));
-}
-
-extern "C" int64_t taco_wave_finish_workspace_bytes(int B, int L) {
-  if (B <= 0 || L <= 0) return TACO_EINVAL;
-  return wave_finish_workspace_floats(B, L) * (int64_t)sizeof(float);
-}
-
-extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out,
-                                int16_t* pcm, int32_t* bounds, float* peak, void* workspace, int B, int L, void* stream) {
-  return launch_wave_finish(wave, samples, deemphasis, trim_top_db, out, pcm, bounds, peak, workspace, B, L, as_stream(stream));
-}
-
-extern "C" int64_t taco_audio_features_workspace_bytes(int B, int L) { return audio_features_workspace_bytes(B, L); }
-
-extern "C" int taco_audio_features(const float* wave, const int* wave_len, const float* mel_basis, void* mel, void* stft,
-                                   int* bounds, int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16,
-                                   void* stream) {
-  return launch_audio_features(wave, wave_len, mel_basis, mel, stft, bounds, kept, workspace, B, L, max_len, r, out_fp16,
-                               as_stream(stream));
-}
-
-extern "C" int taco_fill_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, void* stream) {
-  TACO_REQUIRE(out && n > 0, "fill_bernoulli: bad arguments");
-  return launch_bernoulli(out, n, p_one, seed, as_stream(stream));
-}
-
-extern "C" int taco_debug_last_cluster(int which) { return decoder_last_cluster(which); }
-
-extern "C" int taco_debug_spin(int blocks, int threads, int lds_bytes, int usec, void* stream) {
-  return launch_spin(blocks, threads, lds_bytes, usec, as_stream(stream));
-}
-
-extern "C" int taco_debug_clock_probe(long long* out3, int iters, void* stream) {
-  return launch_clock_probe(out3, iters, as_stream(stream));
-}
-
-extern "C" int taco_debug_fabric_probe(long long* out32, void* gran4k, const void* scratch, long long scratch_bytes, int iters, void* stream) {
-  return launch_fabric_probe(out32, gran4k, scratch, scratch_bytes, iters, as_stream(stream));
-}
-
-extern "C" int taco_profile_enable(int mask) { return prof_enable(mask); }
-
-extern "C" int taco_profile_read2(int which, float* ms, double* flops, int cap) { return prof_read(which, ms, flops, cap); }
-
-extern "C" int taco_debug_profile_labels(int which, char* buf, int cap) { return prof_labels(which, buf, cap); }
-
-extern "C" int taco_profile_read(int which, float* ms, int cap) { return taco_profile_read2(which, ms, nullptr, cap); }

@@ -98,6 +98,3 @@ int taco_prof_begin(int which, hipStream_t s);
 void taco_prof_end(int which, int slot, hipStream_t s, double flops);
 void taco_prof_cancel(int which, int slot, hipStream_t s);   // the bracketed launch was not made: drops the slot, records nothing
 void taco_prof_label(int which, int slot, const char* fmt, ...) __attribute__((format(printf, 3, 4)));   // no-op when slot < 0
-int prof_enable(int mask);
-int prof_read(int which, float* ms, double* flops, int cap);
-int prof_labels(int which, char* buf, int cap);

@@ -333,11 +333,11 @@ void taco_prof_cancel(int which, int slot, hipStream_t s) {
   // (the ring does not advance: the next bracket reuses the slot; an unarmed bracket's recorded start is simply overwritten)
   if (slot >= 0 && g_prof[which].armed[slot]) (void)tail_disarm_timing(s);
 }
-int prof_enable(int mask) {
+extern "C" int taco_profile_enable(int mask) {
   g_prof_mask = mask & 31;
   return TACO_OK;
 }
-int prof_read(int which, float* ms, double* flops, int cap) {
+extern "C" int taco_profile_read2(int which, float* ms, double* flops, int cap) {
   TACO_REQUIRE(which >= 0 && which < 4, "profile_read: category %d out of range", which);
   ProfRing& r = g_prof[which];
   int n = 0;
@@ -352,7 +352,8 @@ int prof_read(int which, float* ms, double* flops, int cap) {
   r.n = 0;
   return n;
 }
-int prof_labels(int which, char* buf, int cap) {
+extern "C" int taco_profile_read(int which, float* ms, int cap) { return taco_profile_read2(which, ms, nullptr, cap); }
+extern "C" int taco_debug_profile_labels(int which, char* buf, int cap) {
   TACO_REQUIRE(which >= 0 && which < 4 && buf && cap > 0, "profile_labels: bad arguments");
   ProfRing& r = g_prof[which];
   int pos = 0;

@@ -542,18 +542,41 @@ __global__ __launch_bounds__(256) void wf_emit_kernel(const float* __restrict__ 
 
 }  // namespace
 
-int64_t griffinlim_workspace_floats(int B, int F) {
+// ---- C ABI (include/taco_hip.h): the Griffin-Lim entry points and taco_wave_finish, each workspace size beside its float count
+static int64_t griffinlim_workspace_floats(int B, int F) {
   return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (NFFT + (int64_t)HOP * (F - 1)) + 64;
 }
 
-int64_t griffinlim_rows_workspace_floats(int B, int F) {   // one window sum-of-squares table per row (it depends on F_b)
+static int64_t griffinlim_rows_workspace_floats(int B, int F) {   // one window sum-of-squares table per row (it depends on F_b)
   return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (int64_t)B * (NFFT + (int64_t)HOP * (F - 1)) + 64;
 }
 
 // the rows layout (without its 64 floats of slack), then the previous spectrum, the two (B, F) partial-sum tables, ||M||^2 per row
 static int64_t griffinlim_fast_offset(int B, int F) { return griffinlim_rows_workspace_floats(B, F) - 64; }
-int64_t griffinlim_fast_workspace_floats(int B, int F) {
+static int64_t griffinlim_fast_workspace_floats(int B, int F) {
   return griffinlim_fast_offset(B, F) + (int64_t)B * F * NBIN * 2 + 2 * (int64_t)B * F + B + 64;
+}
+
+// F >= 5: the centre (reflect) padding of n_fft / 2 = 1024 samples at hop 300 needs more than 1024 samples
+static bool griffinlim_shape_ok(int B, int F) { return B > 0 && F >= 5; }
+
+extern "C" int64_t taco_griffinlim_workspace_bytes(int B, int F) {
+  return griffinlim_shape_ok(B, F) ? griffinlim_workspace_floats(B, F) * (int64_t)sizeof(float) : TACO_EINVAL;
+}
+extern "C" int64_t taco_griffinlim_rows_workspace_bytes(int B, int F) {
+  return griffinlim_shape_ok(B, F) ? griffinlim_rows_workspace_floats(B, F) * (int64_t)sizeof(float) : TACO_EINVAL;
+}
+extern "C" int64_t taco_griffinlim_fast_workspace_bytes(int B, int F) {
+  return griffinlim_shape_ok(B, F) ? griffinlim_fast_workspace_floats(B, F) * (int64_t)sizeof(float) : TACO_EINVAL;
+}
+
+// What all three Griffin-Lim entry points require, in the order a caller sees the refusals.  `who`: the entry point's name in the
+// messages; pointers: whether every pointer that entry point requires is non-null; momentum: 0 where there is none.
+static int griffinlim_require(const char* who, bool pointers, int B, int F, int n_iter, int frames_per_unit, float momentum = 0.f) {
+  TACO_REQUIRE(pointers && B > 0 && n_iter >= 0 && frames_per_unit >= 1, "%s: bad arguments", who);
+  TACO_REQUIRE(momentum >= 0.f && momentum < 1.f, "%s: momentum %g is not in [0, 1)", who, (double)momentum);   // (NaN fails)
+  TACO_REQUIRE(F >= 5, "%s: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", who, F);
+  return TACO_OK;
 }
 
 // the launches of all three entry points.  frames == nullptr: every row has F frames and one window table serves the batch.
@@ -601,33 +624,33 @@ static int griffinlim_launches(const float* mag_t, const float* phase0, uint64_t
   return TACO_OK;
 }
 
-int launch_griffinlim(const float* mag_t, const float* phase0, float* wave, float* work, int B, int F, int n_iter,
-                      hipStream_t s) {
-  TACO_REQUIRE(mag_t && phase0 && wave && work && B > 0 && n_iter >= 0, "griffinlim: bad arguments");
-  TACO_REQUIRE(F >= 5, "griffinlim: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
-  griffinlim_launches(mag_t, phase0, 0, nullptr, 1, wave, work, B, F, n_iter, s);
+extern "C" int taco_griffinlim(const float* mag_t, const float* phase0, float* wave, void* workspace, int B, int F, int n_iter,
+                               void* stream) {
+  TACO_TRY(griffinlim_require("griffinlim", mag_t && phase0 && wave && workspace, B, F, n_iter, 1));
+  griffinlim_launches(mag_t, phase0, 0, nullptr, 1, wave, static_cast<float*>(workspace), B, F, n_iter, as_stream(stream));
   TACO_LAUNCH_CHECK("griffinlim");
   return TACO_OK;
 }
 
-int launch_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
-                           float* wave, float* work, int B, int F, int n_iter, hipStream_t s) {
-  TACO_REQUIRE(mag_t && frames && wave && work && B > 0 && n_iter >= 0 && frames_per_unit >= 1, "griffinlim_rows: bad arguments");
-  TACO_REQUIRE(F >= 5, "griffinlim_rows: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
-  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, s);
+extern "C" int taco_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
+                                    int frames_per_unit, float* wave, void* workspace, int B, int F, int n_iter, void* stream) {
+  TACO_TRY(griffinlim_require("griffinlim_rows", mag_t && frames && wave && workspace, B, F, n_iter, frames_per_unit));
+  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, static_cast<float*>(workspace), B, F, n_iter,
+                      as_stream(stream));
   TACO_LAUNCH_CHECK("griffinlim_rows");
   return TACO_OK;
 }
 
-int launch_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
-                           float momentum, float* wave, float* conv, float* work, int B, int F, int n_iter, hipStream_t s) {
-  TACO_REQUIRE(mag_t && wave && work && B > 0 && n_iter >= 0 && frames_per_unit >= 1, "griffinlim_fast: bad arguments");
-  TACO_REQUIRE(momentum >= 0.f && momentum < 1.f, "griffinlim_fast: momentum %g is not in [0, 1)", (double)momentum);   // (NaN fails)
-  TACO_REQUIRE(F >= 5, "griffinlim_fast: F=%d frames < 5 (the reflect padding of n_fft/2 needs more than 1024 samples)", F);
-  TACO_REQUIRE((reinterpret_cast<uintptr_t>(work) & 7) == 0, "griffinlim_fast: workspace is not 8-byte aligned");
+extern "C" int taco_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
+                                    int frames_per_unit, float momentum, float* wave, float* conv, void* workspace, int B, int F,
+                                    int n_iter, void* stream) {
+  TACO_TRY(griffinlim_require("griffinlim_fast", mag_t && wave && workspace, B, F, n_iter, frames_per_unit, momentum));
+  TACO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "griffinlim_fast: workspace is not 8-byte aligned");
+  float* work = static_cast<float*>(workspace);
   float* tprev = work + griffinlim_fast_offset(B, F);
   float* red = tprev + (int64_t)B * F * NBIN * 2;
-  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, s, momentum, conv, tprev, red);
+  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, as_stream(stream), momentum, conv, tprev,
+                      red);
   TACO_LAUNCH_CHECK("griffinlim_fast");
   return TACO_OK;
 }
@@ -638,17 +661,19 @@ static int64_t wf_pitch(int L) { return ((int64_t)L + 3) & ~(int64_t)3; }
 static int wf_chunks(int L) { return cdiv(L, WF_CHUNK); }
 static int wf_blocks(int L) { return cdiv(L, 512); }
 static int wf_frames(int L) { return 1 + L / WF_TRIM_HOP; }
-int64_t wave_finish_workspace_floats(int B, int L) {
-  return (int64_t)B * (wf_pitch(L) + wf_chunks(L) + wf_blocks(L) + wf_frames(L)) + 64;
+extern "C" int64_t taco_wave_finish_workspace_bytes(int B, int L) {
+  if (B <= 0 || L <= 0) return TACO_EINVAL;
+  return ((int64_t)B * (wf_pitch(L) + wf_chunks(L) + wf_blocks(L) + wf_frames(L)) + 64) * (int64_t)sizeof(float);
 }
 
-int launch_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out, int16_t* pcm,
-                       int32_t* bounds, float* peak, void* workspace, int B, int L, hipStream_t s) {
+extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out,
+                                int16_t* pcm, int32_t* bounds, float* peak, void* workspace, int B, int L, void* stream) {
   TACO_REQUIRE(wave && bounds && peak && workspace && B > 0 && L > 0, "wave_finish: bad arguments");
   TACO_REQUIRE(out || pcm, "wave_finish: out and pcm are both NULL");
   TACO_REQUIRE(out != wave, "wave_finish: out may not alias wave (the emit pass shifts by the trim start)");
   TACO_REQUIRE(deemphasis >= 0.f && deemphasis < 1.f, "wave_finish: deemphasis %g is not in [0, 1)", (double)deemphasis);   // (NaN fails)
   TACO_REQUIRE(trim_top_db >= 0.f, "wave_finish: trim_top_db %g is negative or NaN", (double)trim_top_db);
+  hipStream_t s = as_stream(stream);
   const int64_t pitch = wf_pitch(L);
   const int nch = wf_chunks(L), npm = wf_blocks(L), nms = wf_frames(L);
   float* y = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);

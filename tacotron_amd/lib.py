@@ -162,11 +162,26 @@ def version() -> int:
     return _lib.taco_version()
 
 
-def param_count(shape: TacoShape) -> int:
-    n = _lib.taco_param_count(C.byref(shape))
+def _size(fn_name, *args) -> int:
+    """What a size function of the library returns (a TacoShape goes by reference), or TacoError when it refuses its arguments."""
+    n = getattr(_lib, fn_name)(*[C.byref(a) if isinstance(a, TacoShape) else int(a) for a in args])
     if n < 0:
-        raise TacoError('taco_param_count: ' + last_error())
+        raise TacoError('%s(%s): bad arguments (rc=%d)' % (fn_name, ', '.join(repr(a) for a in args), n))
     return n
+
+
+def _unit_interval(x, what) -> float:
+    """x as a float in [0, 1) that is still below 1 as a float32, or ValueError"""
+    x = float(x)
+    if not 0.0 <= x < 1.0:   # (NaN fails both comparisons)
+        raise ValueError('%s must be in [0, 1), got %r' % (what, x))
+    if C.c_float(x).value >= 1.0:
+        raise ValueError('%s %r rounds to 1 in float32' % (what, x))
+    return x
+
+
+def param_count(shape: TacoShape) -> int:
+    return _size('taco_param_count', shape)
 
 
 def _table(fn, *args):
@@ -184,10 +199,7 @@ def param_table(shape: TacoShape):
 
 
 def workspace_bytes(shape: TacoShape, train: bool) -> int:
-    n = _lib.taco_workspace_bytes(C.byref(shape), int(train))
-    if n < 0:
-        raise TacoError('taco_workspace_bytes: ' + last_error())
-    return n
+    return _size('taco_workspace_bytes', shape, train)
 
 
 def workspace_table(shape: TacoShape, train: bool):
@@ -391,33 +403,40 @@ def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=Fa
     return spec if want_spec else mag_t
 
 
+def _griffinlim_args(who, mag_t, frames, phase0, frames_per_unit, n_iter, need_frames=False, need_phase0=False):
+    """The argument check of the three Griffin-Lim wrappers -> (B, F, device, frames_per_unit, n_iter); ValueError names `who`."""
+    if mag_t.dim() != 3 or mag_t.shape[1] != 1025 or mag_t.dtype != torch.float32:
+        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, 1025, F), got %s %s' % (who, mag_t.dtype, tuple(mag_t.shape)))
+    B, _, F = mag_t.shape
+    dev = mag_t.device
+    if (frames is None and need_frames) or (
+            frames is not None and (tuple(frames.shape) != (B,) or frames.dtype != torch.int32 or frames.device != dev)):
+        raise ValueError('%s: frames must be an int32 tensor of shape (%d,) on %s, got %s'
+                         % (who, B, dev, frames if frames is None else '%s %s on %s' % (frames.dtype, tuple(frames.shape), frames.device)))
+    if (phase0 is None and need_phase0) or (
+            phase0 is not None and (phase0.shape != mag_t.shape or phase0.dtype != torch.float32 or phase0.device != dev)):
+        raise ValueError('%s: phase0 must be a float32 tensor of shape %s on %s' % (who, tuple(mag_t.shape), dev))
+    if int(frames_per_unit) < 1 or int(n_iter) < 0:
+        raise ValueError('%s: frames_per_unit >= 1 and n_iter >= 0, got %d and %d' % (who, frames_per_unit, n_iter))
+    return B, F, dev, int(frames_per_unit), int(n_iter)
+
+
 def griffinlim_workspace_floats(B, F) -> int:
-    nbytes = _lib.taco_griffinlim_workspace_bytes(int(B), int(F))
-    if nbytes < 0:
-        raise TacoError('taco_griffinlim_workspace_bytes: bad shape')
-    return nbytes // 4
+    return _size('taco_griffinlim_workspace_bytes', B, F) // 4
 
 
 def griffinlim(mag_t, phase0, n_iter=50, out=None, work=None):
     """mag_t, phase0 (B, 1025, F) -> waveform (B, 300 (F - 1)); audio.griffinlim on the GPU.  out / work: the caller's own
     waveform buffer and workspace (griffinlim_workspace_floats(B, F) floats); default: fresh ones."""
-    B, Cb, F = mag_t.shape
-    assert Cb == 1025 and phase0.shape == mag_t.shape
-    nbytes = _lib.taco_griffinlim_workspace_bytes(B, F)
-    if nbytes < 0:
-        raise TacoError('taco_griffinlim_workspace_bytes: bad shape')
-    work = _own_or_given(work, (nbytes // 4,), torch.float32, mag_t.device, 'griffinlim: work')
-    wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, mag_t.device, 'griffinlim: out')
-    _check(_lib.taco_griffinlim(ptr(mag_t), ptr(phase0), ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()),
-           'taco_griffinlim')
+    B, F, dev, _, n_iter = _griffinlim_args('griffinlim', mag_t, None, phase0, 1, n_iter, need_phase0=True)
+    work = _own_or_given(work, (griffinlim_workspace_floats(B, F),), torch.float32, dev, 'griffinlim: work')
+    wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, dev, 'griffinlim: out')
+    _check(_lib.taco_griffinlim(ptr(mag_t), ptr(phase0), ptr(wave), ptr(work), B, F, n_iter, stream_ptr()), 'taco_griffinlim')
     return wave
 
 
 def griffinlim_rows_workspace_floats(B, F) -> int:
-    nbytes = _lib.taco_griffinlim_rows_workspace_bytes(int(B), int(F))
-    if nbytes < 0:
-        raise TacoError('taco_griffinlim_rows_workspace_bytes: bad shape')
-    return nbytes // 4
+    return _size('taco_griffinlim_rows_workspace_bytes', B, F) // 4
 
 
 def griffinlim_rows(mag_t, frames, phase0=None, seed=0, n_iter=50, frames_per_unit=1, out=None, work=None):
@@ -425,32 +444,17 @@ def griffinlim_rows(mag_t, frames, phase0=None, seed=0, n_iter=50, frames_per_un
     waveform (B, 300 (F - 1)); row b is the Griffin-Lim of its first F_b = min(F, frames[b] * frames_per_unit) frames, 0 from
     sample 300 (F_b - 1) on.  phase0 (B, 1025, F) initial angles, or None: seeded phases drawn on the device.  out / work: the
     caller's own waveform buffer and workspace (griffinlim_rows_workspace_floats(B, F) floats); default: fresh ones."""
-    if mag_t.dim() != 3 or mag_t.shape[1] != 1025 or mag_t.dtype != torch.float32:
-        raise ValueError('griffinlim_rows: mag_t must be a float32 tensor of shape (B, 1025, F), got %s %s' % (mag_t.dtype, tuple(mag_t.shape)))
-    B, _, F = mag_t.shape
-    dev = mag_t.device
-    if tuple(frames.shape) != (B,) or frames.dtype != torch.int32 or frames.device != dev:
-        raise ValueError('griffinlim_rows: frames must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
-                         % (B, dev, frames.dtype, tuple(frames.shape), frames.device))
-    if phase0 is not None and (phase0.shape != mag_t.shape or phase0.dtype != torch.float32 or phase0.device != dev):
-        raise ValueError('griffinlim_rows: phase0 must be a float32 tensor of shape %s on %s' % (tuple(mag_t.shape), dev))
-    if int(frames_per_unit) < 1 or int(n_iter) < 0:
-        raise ValueError('griffinlim_rows: frames_per_unit >= 1 and n_iter >= 0, got %d and %d' % (frames_per_unit, n_iter))
-    nbytes = _lib.taco_griffinlim_rows_workspace_bytes(B, F)
-    if nbytes < 0:
-        raise TacoError('taco_griffinlim_rows_workspace_bytes: bad shape (B=%d, F=%d)' % (B, F))
-    work = _own_or_given(work, (nbytes // 4,), torch.float32, dev, 'griffinlim_rows: work')
+    B, F, dev, frames_per_unit, n_iter = _griffinlim_args('griffinlim_rows', mag_t, frames, phase0, frames_per_unit, n_iter,
+                                                          need_frames=True)
+    work = _own_or_given(work, (griffinlim_rows_workspace_floats(B, F),), torch.float32, dev, 'griffinlim_rows: work')
     wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, dev, 'griffinlim_rows: out')
-    _check(_lib.taco_griffinlim_rows(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), int(frames_per_unit),
-                                     ptr(wave), ptr(work), B, F, int(n_iter), stream_ptr()), 'taco_griffinlim_rows')
+    _check(_lib.taco_griffinlim_rows(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), frames_per_unit,
+                                     ptr(wave), ptr(work), B, F, n_iter, stream_ptr()), 'taco_griffinlim_rows')
     return wave
 
 
 def griffinlim_fast_workspace_floats(B, F) -> int:
-    nbytes = _lib.taco_griffinlim_fast_workspace_bytes(int(B), int(F))
-    if nbytes < 0:
-        raise TacoError('taco_griffinlim_fast_workspace_bytes: bad shape')
-    return nbytes // 4
+    return _size('taco_griffinlim_fast_workspace_bytes', B, F) // 4
 
 
 def griffinlim_fast(mag_t, frames=None, phase0=None, seed=0, n_iter=50, momentum=0.99, frames_per_unit=1, want_conv=False,
@@ -460,41 +464,19 @@ def griffinlim_fast(mag_t, frames=None, phase0=None, seed=0, n_iter=50, momentum
     returned.  momentum in [0, 1): 0 is the plain algorithm.  frames (B) int32 on the device, or None: every row has F frames.
     phase0 (B, 1025, F) initial angles, or None: seeded phases drawn on the device.  out / conv / work: the caller's own buffers
     (work: griffinlim_fast_workspace_floats(B, F) floats); default: fresh ones.  A conv buffer implies want_conv."""
-    if mag_t.dim() != 3 or mag_t.shape[1] != 1025 or mag_t.dtype != torch.float32:
-        raise ValueError('griffinlim_fast: mag_t must be a float32 tensor of shape (B, 1025, F), got %s %s' % (mag_t.dtype, tuple(mag_t.shape)))
-    B, _, F = mag_t.shape
-    dev = mag_t.device
-    if frames is not None and (tuple(frames.shape) != (B,) or frames.dtype != torch.int32 or frames.device != dev):
-        raise ValueError('griffinlim_fast: frames must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
-                         % (B, dev, frames.dtype, tuple(frames.shape), frames.device))
-    if phase0 is not None and (phase0.shape != mag_t.shape or phase0.dtype != torch.float32 or phase0.device != dev):
-        raise ValueError('griffinlim_fast: phase0 must be a float32 tensor of shape %s on %s' % (tuple(mag_t.shape), dev))
-    if int(frames_per_unit) < 1 or int(n_iter) < 0:
-        raise ValueError('griffinlim_fast: frames_per_unit >= 1 and n_iter >= 0, got %d and %d' % (frames_per_unit, n_iter))
-    momentum = float(momentum)
-    if not 0.0 <= momentum < 1.0:   # (NaN fails both comparisons)
-        raise ValueError('griffinlim_fast: momentum must be in [0, 1), got %r' % momentum)
-    if C.c_float(momentum).value >= 1.0:
-        raise ValueError('griffinlim_fast: momentum %r rounds to 1 in float32' % momentum)
+    B, F, dev, frames_per_unit, n_iter = _griffinlim_args('griffinlim_fast', mag_t, frames, phase0, frames_per_unit, n_iter)
+    momentum = _unit_interval(momentum, 'griffinlim_fast: momentum')
     want_conv = bool(want_conv) or conv is not None
-    n_iter = int(n_iter)
-    nbytes = _lib.taco_griffinlim_fast_workspace_bytes(B, F)
-    if nbytes < 0:
-        raise TacoError('taco_griffinlim_fast_workspace_bytes: bad shape (B=%d, F=%d)' % (B, F))
-    nwork = nbytes // 4
-    work = _own_or_given(work, (nwork,), torch.float32, dev, 'griffinlim_fast: work')
+    work = _own_or_given(work, (griffinlim_fast_workspace_floats(B, F),), torch.float32, dev, 'griffinlim_fast: work')
     wave = _own_or_given(out, (B, 300 * (F - 1)), torch.float32, dev, 'griffinlim_fast: out')
     conv = _own_or_given(conv, (B, n_iter + 1), torch.float32, dev, 'griffinlim_fast: conv') if want_conv else None
-    _check(_lib.taco_griffinlim_fast(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), int(frames_per_unit),
+    _check(_lib.taco_griffinlim_fast(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), frames_per_unit,
                                      momentum, ptr(wave), ptr(conv), ptr(work), B, F, n_iter, stream_ptr()), 'taco_griffinlim_fast')
     return (wave, conv) if want_conv else wave
 
 
 def wave_finish_workspace_floats(B, L) -> int:
-    nbytes = _lib.taco_wave_finish_workspace_bytes(int(B), int(L))
-    if nbytes < 0:
-        raise TacoError('taco_wave_finish_workspace_bytes: bad shape (B=%d, L=%d)' % (B, L))
-    return nbytes // 4
+    return _size('taco_wave_finish_workspace_bytes', B, L) // 4
 
 
 def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=True, want_pcm=True, out=None, pcm=None, bounds=None,
@@ -514,11 +496,7 @@ def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=T
     if samples is not None and (tuple(samples.shape) != (B,) or samples.dtype != torch.int32 or samples.device != dev):
         raise ValueError('wave_finish: samples must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
                          % (B, dev, samples.dtype, tuple(samples.shape), samples.device))
-    deemphasis, trim_top_db = float(deemphasis), float(trim_top_db)
-    if not 0.0 <= deemphasis < 1.0:   # (NaN fails both comparisons)
-        raise ValueError('wave_finish: deemphasis must be in [0, 1), got %r' % deemphasis)
-    if C.c_float(deemphasis).value >= 1.0:
-        raise ValueError('wave_finish: deemphasis %r rounds to 1 in float32' % deemphasis)
+    deemphasis, trim_top_db = _unit_interval(deemphasis, 'wave_finish: deemphasis'), float(trim_top_db)
     if not trim_top_db >= 0.0:
         raise ValueError('wave_finish: trim_top_db must be >= 0, got %r' % trim_top_db)
     want_out = bool(want_out) or out is not None
@@ -538,10 +516,7 @@ def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=T
 
 
 def audio_features_workspace_bytes(B, L) -> int:
-    n = _lib.taco_audio_features_workspace_bytes(int(B), int(L))
-    if n < 0:
-        raise TacoError('taco_audio_features_workspace_bytes: bad shape (B=%d, L=%d)' % (B, L))
-    return n
+    return _size('taco_audio_features_workspace_bytes', B, L)
 
 
 def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch.float16, out=None, work=None):

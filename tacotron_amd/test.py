@@ -60,6 +60,41 @@ def write_wav_pcm(path, int16_samples, sr=SR):
         f.writeframes(x.astype('<i2', copy=False).tobytes())
 
 
+def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None):
+    """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given); ValueError."""
+    if vocode_lengths and not stop:
+        raise ValueError('vocode_lengths (--vocode-lengths) needs a stop rule (--stop): the lengths come from taco_infer_stop')
+    if gl_momentum is not None and not 0.0 <= float(gl_momentum) < 1.0:
+        raise ValueError('gl_momentum (--gl-momentum) must be in [0, 1), got %r' % (gl_momentum,))
+    if int(n_iter) < 0:
+        raise ValueError('n_iter (--gl-iters) must be >= 0, got %r' % (n_iter,))
+    if deemphasis is not None and not 0.0 <= float(deemphasis) < 1.0:
+        raise ValueError('deemphasis (--deemphasis) must be in [0, 1), got %r' % (deemphasis,))
+    if trim_db is not None and not float(trim_db) > 0.0:
+        raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (trim_db,))
+
+
+def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None):
+    """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
+    spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300)."""
+    path = os.path.join(out_dir, 'prompt_%03d' % n)
+    if len_b is not None:
+        frames = min(len_b * r, spec.shape[0])
+        spec, align = spec[:frames], align[:len_b]
+        if wav is not None:
+            wav = wav[:300 * (frames - 1)]
+        np.save(path + '_len.npy', np.int32(len_b))
+    np.save(path + '_spec.npy', spec)
+    np.save(path + '_align.npy', align)
+    if wav is not None:
+        write_wav(path + '.wav', wav)
+    if pcm is not None:   # (finished on the device: already cut to the row's own samples, then trimmed to [s, e))
+        write_wav_pcm(path + '.wav', pcm[:int(trim[1]) - int(trim[0])])
+        np.save(path + '_trim.npy', trim)
+    if conv is not None:
+        np.save(path + '_conv.npy', conv)
+
+
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
          gl_momentum=None, deemphasis=None, trim_db=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
@@ -78,16 +113,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     `deemphasis` (None, or a in [0, 1)) / `trim_db` (None, or decibels > 0): with either, the batch's waveform is finished on the
     device (finish_waveform; with `stop`, each row over the samples of its own len_b r frames) and prompt_NNN.wav is written from
     the device's int16 samples: e - s of them, [s, e] in prompt_NNN_trim.npy.  The other files are unchanged."""
-    if vocode_lengths and stop is None:
-        raise ValueError('test: vocode_lengths needs a stop rule (the lengths come from taco_infer_stop)')
-    if gl_momentum is not None and not 0.0 <= float(gl_momentum) < 1.0:
-        raise ValueError('test: gl_momentum must be in [0, 1), got %r' % (gl_momentum,))
-    if int(n_iter) < 0:
-        raise ValueError('test: n_iter must be >= 0, got %r' % (n_iter,))
-    if deemphasis is not None and not 0.0 <= float(deemphasis) < 1.0:
-        raise ValueError('test: deemphasis must be in [0, 1), got %r' % (deemphasis,))
-    if trim_db is not None and not float(trim_db) > 0.0:
-        raise ValueError('test: trim_db must be > 0, got %r' % (trim_db,))
+    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db)
     finish = deemphasis is not None or trim_db is not None
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
@@ -127,52 +153,26 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        conv = None
-        pcm = trim = None
-        if vocode and finish:
+        wav = conv = pcm = trim = None
+        if vocode:
+            wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
+                                     want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None)
             if gl_momentum is not None:
-                wav, conv = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum, want_conv=True,
-                                               lengths=model.lengths if vocode_lengths else None)
-                conv = conv.cpu().numpy()
+                wav, conv = wav[0], wav[1].cpu().numpy()
                 print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
                       % (gl_momentum, n_iter, float(conv[:, -1].max())))
+            if finish:   # (the fp32 waveform stays on the device)
+                _, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
+                                                  deemphasis=0.0 if deemphasis is None else deemphasis,
+                                                  trim_top_db=0.0 if trim_db is None else trim_db, want_out=False)
+                pcm, trim, wav = pcm.cpu().numpy(), trim.cpu().numpy(), None
             else:
-                wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n,
-                                         lengths=model.lengths if vocode_lengths else None)
-            _, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
-                                              deemphasis=0.0 if deemphasis is None else deemphasis,
-                                              trim_top_db=0.0 if trim_db is None else trim_db, want_out=False)
-            pcm, trim, wav = pcm.cpu().numpy(), trim.cpu().numpy(), None
-        elif vocode and gl_momentum is not None:
-            wav, conv = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum, want_conv=True,
-                                           lengths=model.lengths if vocode_lengths else None)
-            wav, conv = wav.cpu().numpy(), conv.cpu().numpy()
-            print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
-                  % (gl_momentum, n_iter, float(conv[:, -1].max())))
-        else:
-            wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n,
-                                     lengths=model.lengths if vocode_lengths else None).cpu().numpy() if vocode else None
+                wav = wav.cpu().numpy()
         spec, al = spec.cpu().numpy(), al.cpu().numpy()
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         for i in range(Bn):
-            si, ai, wi = spec[i], al[i], (wav[i] if wav is not None else None)
-            if lengths is not None:
-                L = int(lengths[i])
-                frames = min(L * config.r, si.shape[0])
-                si, ai = si[:frames], ai[:L]
-                if wi is not None:
-                    wi = wi[:300 * (frames - 1)]   # (Griffin-Lim of F frames: 300 (F - 1) samples, hop 300)
-                np.save(os.path.join(out_dir, 'prompt_%03d_len.npy' % n), np.int32(L))
-            np.save(os.path.join(out_dir, 'prompt_%03d_spec.npy' % n), si)
-            np.save(os.path.join(out_dir, 'prompt_%03d_align.npy' % n), ai)
-            if wi is not None:
-                write_wav(os.path.join(out_dir, 'prompt_%03d.wav' % n), wi)
-            if pcm is not None:
-                s_b, e_b = int(trim[i, 0]), int(trim[i, 1])
-                write_wav_pcm(os.path.join(out_dir, 'prompt_%03d.wav' % n), pcm[i, :e_b - s_b])
-                np.save(os.path.join(out_dir, 'prompt_%03d_trim.npy' % n), trim[i])
-            if conv is not None:
-                np.save(os.path.join(out_dir, 'prompt_%03d_conv.npy' % n), conv[i])
+            wi, len_b, pi, ti, ci = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv))
+            write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci)
             n += 1
     print('wrote %d samples to %s' % (n, out_dir))
     return n
@@ -198,16 +198,10 @@ def parse_args(argv=None):
     ap.add_argument('--trim-db', type=float, default=None, metavar='DB',
                     help='cut leading / trailing silence more than DB > 0 decibels below the loudest frame; writes prompt_NNN_trim.npy')
     a = ap.parse_args(argv)
-    if a.vocode_lengths and not a.stop:
-        ap.error('--vocode-lengths needs --stop')
-    if a.gl_iters < 0:
-        ap.error('--gl-iters must be >= 0')
-    if a.gl_momentum is not None and not 0.0 <= a.gl_momentum < 1.0:
-        ap.error('--gl-momentum must be in [0, 1)')
-    if a.deemphasis is not None and not 0.0 <= a.deemphasis < 1.0:
-        ap.error('--deemphasis must be in [0, 1)')
-    if a.trim_db is not None and not a.trim_db > 0.0:
-        ap.error('--trim-db must be > 0')
+    try:
+        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db)
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 

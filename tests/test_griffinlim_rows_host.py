@@ -76,6 +76,40 @@ def test_wrapper_refuses_wrong_shapes_and_dtypes(built_lib):
         built_lib.griffinlim_rows(torch.ones(B, 1025, 4), frames)
 
 
+def test_plain_wrapper_refuses_bad_arguments_before_any_device_call(built_lib):
+    """lib.griffinlim, the oldest wrapper, refuses through the same check as the two above: ValueError (it used to assert, and to
+    dereference phase0=None), before the entry point is called"""
+    import inspect
+    B, F = 2, 8
+    mag, ph = torch.ones(B, 1025, F), torch.zeros(B, 1025, F)
+    called = []
+    real = built_lib._lib.taco_griffinlim
+    bad = [
+        dict(mag_t=torch.ones(B, 1024, F), phase0=torch.zeros(B, 1024, F)),    # not 1025 bins
+        dict(mag_t=torch.ones(1025, F), phase0=torch.zeros(1025, F)),           # no batch dimension
+        dict(mag_t=mag.double(), phase0=ph),                                    # not float32
+        dict(mag_t=mag, phase0=None),
+        dict(mag_t=mag, phase0=torch.zeros(B, 1025, F + 1)),                    # phases of another shape
+        dict(mag_t=mag, phase0=ph.double()),
+        dict(mag_t=mag, phase0=ph, n_iter=-1),
+        dict(mag_t=mag, phase0=ph, out=torch.zeros(B, 300 * F)),                # waveform buffer of the wrong length
+        dict(mag_t=mag, phase0=ph, work=torch.zeros(built_lib.griffinlim_workspace_floats(B, F) - 1)),   # too small a workspace
+    ]
+    try:
+        built_lib._lib.taco_griffinlim = lambda *a: called.append(a) or 0
+        for kw in bad:
+            with pytest.raises(ValueError):
+                built_lib.griffinlim(**kw)
+        with pytest.raises(built_lib.TacoError):   # F < 5
+            built_lib.griffinlim(torch.ones(B, 1025, 4), torch.zeros(B, 1025, 4))
+    finally:
+        built_lib._lib.taco_griffinlim = real
+    assert not called
+    sig = inspect.signature(built_lib.griffinlim).parameters
+    assert [(k, sig[k].default) for k in list(sig)[2:]] == [('n_iter', 50), ('out', None), ('work', None)]
+    assert list(sig)[:2] == ['mag_t', 'phase0'] and all(sig[k].default is inspect.Parameter.empty for k in list(sig)[:2])
+
+
 def test_invert_spectrogram_and_driver_signatures(built_lib):
     import inspect
     from tacotron_amd import test as drv
