@@ -253,6 +253,27 @@ int taco_debug_fabric_probe(long long* out32, void* gran4k, const void* scratch,
 int taco_denorm_unframe(const float* output, const float* stft_mean, const float* stft_std, float* spec, float* mag_t,
                         int B, int Td, int r, int C, void* stream);
 
+/* ---- corpus boundary ----------------------------------------------------------------------------------------------------- */
+/* The batch gather of the training corpus with the reference's target standardisation (data_input.py:55-65
+ * `(x - mean) / std`, which the reference applies to the whole corpus on the host) fused in: the inverse of
+ * taco_denorm_unframe's affine map.  The corpus stays in memory as preprocess stores it.
+ *   src    (N, row): N utterances of row = Td * C values; fp16 when src_fp16 != 0, else fp32
+ *   index  (B) int64 on the DEVICE, or NULL: identity (row b of src; needs B <= N)
+ *   mean, std (C) fp32; the column of element e of an utterance is e % C.  Both NULL: a pure gather / widening, bit-equal to
+ *          the conversion.  Exactly one NULL is TACO_EINVAL
+ *   out    (B, row) fp32:  out[b, e] = (float(src[index[b], e]) - mean[e % C]) / std[e % C], one IEEE fp32 subtraction and one
+ *          correctly rounded fp32 division (no reciprocal multiply) -- NumPy's (x.astype(float32) - mean) / std bit for bit
+ *   n_bad  int32 on the device, or NULL.  A row whose index is outside [0, N) reads nothing, is written as zeros and adds one to
+ *          *n_bad, which the call zeroes on `stream` first
+ * Right for every base alignment the element types allow and every row and C: the host picks, per call, the widest access
+ * V in {8 (fp16 only), 4, 2, 1} elements with row % V == 0, src a multiple of V elements and out a multiple of min(V, 4) floats
+ * (V = 8: 16-byte loads, two 16-byte stores).  One launch of B x ceil(row / (1024 V)) workgroups; no allocation, no host
+ * synchronisation, no workgroup waits for another one: graph-capturable.  NULL src / out, N, B, row or C <= 0, row % C != 0,
+ * index == NULL with B > N, or out overlapping src return TACO_EINVAL before anything is enqueued.  TACO_VERSION did not change
+ * with this entry point: detect it by the symbol. */
+int taco_corpus_batch(const void* src, int src_fp16, const int64_t* index, const float* mean, const float* std, float* out,
+                      int32_t* n_bad, int64_t N, int B, int64_t row, int C, void* stream);
+
 /* ---- vocoder ---------------------------------------------------------------------------------------------- */
 /* audio.griffinlim (audio.py:77-97) with the reference's constants compiled in (n_fft 2048, win_length 1200, hop_length 300,
  * periodic Hann, librosa center=True framing): n_iter rounds of istft -> stft keeping the given magnitudes, then a final istft.

@@ -1,6 +1,7 @@
 """Host-side data helpers: synthetic Nancy-shaped batches, the HBM-resident corpus / pinned feeder and the
 reference's prompt front end (data_input.py:87-108).  Real corpora are produced by tacotron_amd.preprocess (preprocess.py) and
-loaded by train.load_corpus (data_input.load_from_npy)."""
+opened by train.open_corpus (data_input.load_from_npy): the feeders keep them as stored (fp16) and standardise in the batch
+gather (`norm=`, lib.corpus_batch)."""
 from __future__ import annotations
 
 import queue
@@ -43,26 +44,74 @@ def synthetic_corpus(n=256, Tt=200, Td=180, r=2, V=60, seed=1234, rank=0, num_sp
     return b
 
 
+def _torch_dtype(v):
+    return v.dtype if isinstance(v, torch.Tensor) else torch.from_numpy(np.empty(0, dtype=v.dtype)).dtype
+
+
+def _norm_tensors(norm, data, device):
+    """{name: (mean, std)} as fp32 tensors on `device`, after a length check against the last axis of data[name]."""
+    out = {}
+    for k, (mean, std) in (norm or {}).items():
+        pair = tuple(torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float32))).to(device) for a in (mean, std))
+        width = data[k].shape[-1]
+        if data[k].ndim != 3 or any(tuple(t.shape) != (width,) for t in pair):
+            raise ValueError('norm[%r]: mean and std must have length %d, the last axis of the (N, Td, C) tensor' % (k, width))
+        out[k] = pair
+    return out
+
+
 class DeviceCorpus:
     """The whole corpus resident in HBM (MI355X: 288 GB per GPU -- the Nancy corpus, 12 K utterances x 1.6 MB at the reference's
     padded shapes, is 19 GB), uploaded once; a minibatch is a device-side row gather on the caller's stream (51 MB: ~20 us of HBM
     time) and the train loop moves NO bytes over PCIe per step.  Same `next()` contract as DeviceFeeder, which remains the path
-    for corpora beyond the budget."""
+    for corpora beyond the budget.
 
-    def __init__(self, data, batch_size, device='cuda', seed=1000, draw=None, chunk_rows=64):
+    norm = {name: (mean, std)} (train.open_corpus): the named (N, Td, C) tensors are uploaded in their STORED dtype (fp16 from
+    preprocess: half the HBM) straight from the array they are given as (a memmap is never materialised on the host), and
+    `next()` standardises them inside the gather, lib.corpus_batch -- the bits of (x.astype(float32) - mean) / std."""
+
+    def __init__(self, data, batch_size, device='cuda', seed=1000, draw=None, chunk_rows=64, norm=None):
         self.device = torch.device(device)
         self.B = int(batch_size)
-        host = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))) for k, v in data.items()}
+        self.norm = _norm_tensors(norm, data, self.device)
+        host = {k: (v if isinstance(v, torch.Tensor) or k in self.norm else torch.from_numpy(np.ascontiguousarray(v)))
+                for k, v in data.items()}
         self.n = len(next(iter(host.values())))
         self._rng = np.random.default_rng(seed)
         self._draw = draw if draw is not None else (lambda step: self._rng.integers(self.n, size=self.B))
         self.data = {}
         for k, v in host.items():   # chunked upload: no second full-size pinned copy of a 19 GB array
-            d = torch.empty(v.shape, dtype=v.dtype, device=self.device)
-            for i in range(0, self.n, chunk_rows):
-                d[i:i + chunk_rows].copy_(v[i:i + chunk_rows])
+            d = torch.empty(tuple(v.shape), dtype=_torch_dtype(v), device=self.device)
+            if k in self.norm:
+                self._upload_staged(v, d, chunk_rows)
+            else:
+                for i in range(0, self.n, chunk_rows):
+                    d[i:i + chunk_rows].copy_(v[i:i + chunk_rows])
             self.data[k] = d
         self._step = 0
+
+    def _upload_staged(self, v, d, chunk_rows):
+        """v (array, memmap or tensor on the host) -> d through two pinned staging chunks: the host fills one (for a memmap this is
+        the read from the file) while the other's non-blocking copy is in flight; a chunk is refilled once the event behind its
+        copy has passed."""
+        pin = self.device.type == 'cuda'
+        stage = [torch.empty((chunk_rows,) + tuple(v.shape[1:]), dtype=d.dtype, pin_memory=pin) for _ in range(2)]
+        done = [None, None]
+        for j, i in enumerate(range(0, self.n, chunk_rows)):
+            k, m = j & 1, min(chunk_rows, self.n - i)
+            if done[k] is not None:
+                done[k].synchronize()
+            if isinstance(v, torch.Tensor):
+                stage[k][:m].copy_(v[i:i + m])
+            else:
+                np.copyto(stage[k][:m].numpy(), v[i:i + m])   # (straight from the array or memmap: no tensor over read-only memory)
+            d[i:i + m].copy_(stage[k][:m], non_blocking=True)
+            if pin:
+                done[k] = torch.cuda.Event()
+                done[k].record(torch.cuda.current_stream(self.device))
+        for ev in done:
+            if ev is not None:
+                ev.synchronize()
 
     @staticmethod
     def nbytes(data):
@@ -71,7 +120,12 @@ class DeviceCorpus:
     def next(self):
         idx = torch.as_tensor(np.asarray(self._draw(self._step), dtype=np.int64)).to(self.device, non_blocking=True)
         self._step += 1
-        return {k: torch.index_select(v, 0, idx) for k, v in self.data.items()}
+        if not self.norm:
+            return {k: torch.index_select(v, 0, idx) for k, v in self.data.items()}
+        from . import lib
+        with torch.cuda.device(self.device):
+            return {k: (lib.corpus_batch(v, *self.norm[k], index=idx) if k in self.norm else torch.index_select(v, 0, idx))
+                    for k, v in self.data.items()}
 
     def close(self):
         pass
@@ -84,20 +138,32 @@ class DeviceFeeder:
     A worker thread draws the indices of batch s + depth, copies the rows into PINNED staging buffers and enqueues the copy into one of depth + 1 device buffer sets on a copy stream; `next()`
     makes the caller's stream wait for that copy's event (no host block) and hands out the device tensors -- `Tacotron.set_inputs`
     on them is a pointer swap.  A buffer set is overwritten only after the consumer's stream has passed the event recorded by the
-    `next()` call that retired it.  With device='cpu' (tests) the same rotation runs synchronously without pinning."""
+    `next()` call that retired it.  With device='cpu' (tests) the same rotation runs synchronously without pinning.
 
-    def __init__(self, data, batch_size, device='cuda', depth=2, seed=1000, draw=None):
-        self.data = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))) for k, v in data.items()}
-        self.n = len(next(iter(self.data.values())))
-        self.B, self.depth = int(batch_size), int(depth)
+    norm = {name: (mean, std)} (train.open_corpus): the pinned and device slots of the named tensors hold the STORED dtype (fp16:
+    half the bytes over PCIe), read row by row from the array as given (a memmap stays a memmap).  `next()` standardises the slot
+    into an fp32 tensor of the same rotation with lib.corpus_batch on the caller's stream, behind the ready-event wait, and hands
+    that out.  The lifetime rule is unchanged: the slot's `_free` event is still recorded by the FOLLOWING `next()`, i.e. on the
+    caller's stream behind that launch, so a slot is refilled only after its standardisation has read it -- and the fp32 tensor
+    of a slot is rewritten only when the slot comes round again, by a launch on the caller's own stream.  device='cpu': the same
+    map with torch, `(x.float() - mean) / std`, the same bits."""
+
+    def __init__(self, data, batch_size, device='cuda', depth=2, seed=1000, draw=None, norm=None):
         self.device = torch.device(device)
         self.cuda = self.device.type == 'cuda'
+        self.norm = _norm_tensors(norm, data, self.device)
+        self.data = {k: (v if isinstance(v, torch.Tensor) or k in self.norm else torch.from_numpy(np.ascontiguousarray(v)))
+                     for k, v in data.items()}
+        self.n = len(next(iter(self.data.values())))
+        self.B, self.depth = int(batch_size), int(depth)
         self._rng = np.random.default_rng(seed)
         self._draw = draw if draw is not None else (lambda step: self._rng.integers(self.n, size=self.B))
         nslots = self.depth + 1
         shp = {k: (self.B,) + tuple(v.shape[1:]) for k, v in self.data.items()}
-        self._pinned = [{k: torch.empty(shp[k], dtype=v.dtype, pin_memory=self.cuda) for k, v in self.data.items()} for _ in range(nslots)]
-        self._dev = [{k: torch.empty(shp[k], dtype=v.dtype, device=self.device) for k, v in self.data.items()} for _ in range(nslots)]
+        self._pinned = [{k: torch.empty(shp[k], dtype=_torch_dtype(v), pin_memory=self.cuda) for k, v in self.data.items()} for _ in range(nslots)]
+        self._dev = [{k: torch.empty(shp[k], dtype=_torch_dtype(v), device=self.device) for k, v in self.data.items()} for _ in range(nslots)]
+        # fp32 images of the standardised tensors, one per slot (the GPU path writes them in place; the CPU path replaces them)
+        self._out = [{k: torch.empty(shp[k], dtype=torch.float32, device=self.device) for k in self.norm if self.cuda} for _ in range(nslots)]
         self._ready = [None] * nslots          # copy-stream event: the slot's H2D copy is complete
         self._free = [None] * nslots           # consumer-stream event: the consumer no longer reads the slot
         self._copy = torch.cuda.Stream(self.device) if self.cuda else None
@@ -118,6 +184,11 @@ class DeviceFeeder:
         idx = [int(i) for i in np.asarray(self._draw(step)).reshape(-1)]
         for k, v in self.data.items():
             dst = self._pinned[slot][k]
+            if not isinstance(v, torch.Tensor):   # (a stored array or memmap of a `norm` tensor: NumPy row copies, same form)
+                dst = dst.numpy()
+                for i, j in enumerate(idx):
+                    dst[i] = v[j]
+                continue
             for i, j in enumerate(idx):      # row copies (a 1.4 MB memcpy each at the Nancy shape): no intra-op thread pool -- on a
                 dst[i].copy_(v[j])           # 256-core host torch.index_select with its default 128 threads took 19 ms per batch, 0.5 ms with 8
         if self.cuda:
@@ -176,7 +247,18 @@ class DeviceFeeder:
             self._slots.release()
         self._last = item
         self._step += 1
-        return self._dev[item]
+        if not self.norm:
+            return self._dev[item]
+        batch = dict(self._dev[item])
+        if self.cuda:
+            from . import lib
+            with torch.cuda.device(self.device):
+                for k, (mean, std) in self.norm.items():
+                    batch[k] = lib.corpus_batch(self._dev[item][k], mean, std, out=self._out[item][k])
+        else:
+            for k, (mean, std) in self.norm.items():
+                batch[k] = (self._dev[item][k].float() - mean) / std
+        return batch
 
     def close(self):
         self._stop = True

@@ -109,6 +109,7 @@ EXPORTS = {
     'taco_debug_clock_probe': (C.c_int, [_P, _I, _P]),
     'taco_debug_fabric_probe': (C.c_int, [_P, _P, _P, C.c_int64, _I, _P]),
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'taco_corpus_batch': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'taco_griffinlim_rows_workspace_bytes': (C.c_int64, [_I, _I]),
@@ -401,6 +402,61 @@ def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=Fa
     if want_spec and want_mag_t:
         return spec, mag_t
     return spec if want_spec else mag_t
+
+
+def corpus_batch_width(src_addr, out_addr, row, fp16) -> int:
+    """Elements per thread and access taco_corpus_batch picks (include/taco_hip.h): the largest V in {8 (fp16 only), 4, 2, 1}
+    with row % V == 0, the source address a multiple of V elements and the output address a multiple of min(V, 4) floats.
+    Pure host arithmetic, the restatement of the library's rule; V = 8 is the 16-byte vector path, V = 1 the scalar one."""
+    esz = 2 if fp16 else 4
+    v = 8 if fp16 else 4
+    while v > 1:
+        if row % v == 0 and src_addr % (v * esz) == 0 and out_addr % (min(v, 4) * 4) == 0:
+            return v
+        v >>= 1
+    return 1
+
+
+def _corpus_batch_args(src, mean, std, index, n_bad):
+    """The argument check of corpus_batch -> (N, row, C, B, device); ValueError before any library call."""
+    who = 'corpus_batch'
+    if src.dtype not in (torch.float16, torch.float32):
+        raise ValueError('%s: src must be float16 or float32, got %s' % (who, src.dtype))
+    if src.dim() != 3 or min(src.shape) < 1:
+        raise ValueError('%s: src must have shape (N, Td, C), got %s' % (who, tuple(src.shape)))
+    if not src.is_contiguous():
+        raise ValueError('%s: src must be contiguous' % who)
+    N, Td, Cw = src.shape
+    dev = src.device
+    if (mean is None) != (std is None):
+        raise ValueError('%s: mean and std must both be given or both be None' % who)
+    for name, t in (('mean', mean), ('std', std)):
+        if t is not None and (tuple(t.shape) != (Cw,) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous float32 tensor of shape (%d,) on %s, got %s %s on %s'
+                             % (who, name, Cw, dev, t.dtype, tuple(t.shape), t.device))
+    if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != dev or not index.is_contiguous()):
+        raise ValueError('%s: index must be a contiguous int64 tensor of shape (B,) on %s, got %s %s on %s'
+                         % (who, dev, index.dtype, tuple(index.shape), index.device))
+    if index is not None and index.numel() < 1:
+        raise ValueError('%s: index is empty' % who)
+    if n_bad is not None and (n_bad.numel() != 1 or n_bad.dtype != torch.int32 or n_bad.device != dev):
+        raise ValueError('%s: n_bad must be one int32 on %s' % (who, dev))
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: src must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    return N, Td * Cw, Cw, (N if index is None else index.numel()), dev
+
+
+def corpus_batch(src, mean, std, index=None, out=None, n_bad=None):
+    """Batch gather with the corpus standardisation fused in (include/taco_hip.h taco_corpus_batch): src (N, Td, C) fp16 or fp32,
+    mean / std (C) fp32 or both None (pure gather / widening), index (B) int64 on the device or None (identity, B = N) ->
+    out (B, Td, C) fp32 = (float(src[index]) - mean) / std, NumPy's fp32 result bit for bit.  A row whose index is outside
+    [0, N) comes out as zeros and is counted in n_bad (one int32 on the device, zeroed by the call) when given.  out: the
+    caller's own buffer; default: a fresh one."""
+    N, row, Cw, B, dev = _corpus_batch_args(src, mean, std, index, n_bad)
+    out = _own_or_given(out, (B, row // Cw, Cw), torch.float32, dev, 'corpus_batch: out')
+    _check(_lib.taco_corpus_batch(ptr(src), int(src.dtype == torch.float16), ptr(index), ptr(mean), ptr(std), ptr(out), ptr(n_bad),
+                                  N, B, row, Cw, stream_ptr()), 'taco_corpus_batch')
+    return out
 
 
 def _griffinlim_args(who, mag_t, frames, phase0, frames_per_unit, n_iter, need_frames=False, need_phase0=False):

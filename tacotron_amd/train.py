@@ -61,6 +61,33 @@ def load_corpus(data_path, seed=0):
     return meta, data, stft_mean, stft_std
 
 
+def open_corpus(data_path, seed=0):
+    """load_corpus without the widening: (meta, data, norm), or None when there is no meta.pkl.  data['stft'] / data['mel'] are
+    the npy files memory-mapped AS STORED (fp16 from tacotron_amd.preprocess; fp32 files are accepted); norm = {'stft': (mean,
+    std), 'mel': (mean, std)} holds load_corpus's statistics -- the same seeded 100-utterance draw, widened to fp32 after the rows
+    are taken, which gives the same bits -- for the feeders to standardise in the batch gather (`norm=`, lib.corpus_batch).
+    The host never holds an fp32 copy of the corpus."""
+    meta_path = os.path.join(data_path, 'meta.pkl')
+    if not os.path.exists(meta_path):
+        return None
+    with open(meta_path, 'rb') as f:
+        meta = pkl.load(f)
+    stft, mel = (np.load(os.path.join(data_path, n + '.npy'), mmap_mode='r') for n in ('stfts', 'mels'))
+    idx = np.random.default_rng(seed).integers(len(stft), size=100)
+    norm = {}
+    for name, arr in (('stft', stft), ('mel', mel)):
+        if arr.dtype not in (np.float16, np.float32):
+            raise ValueError('%s: %ss.npy holds %s, expected float16 or float32' % (data_path, name, arr.dtype))
+        rows = arr[idx].astype(np.float32)
+        norm[name] = (rows.mean((0, 1)), rows.std((0, 1)))
+    data = {'text': np.load(os.path.join(data_path, 'texts.npy')).astype(np.int32),
+            'text_length': np.load(os.path.join(data_path, 'text_lens.npy')).astype(np.int32), 'stft': stft, 'mel': mel}
+    spk_path = os.path.join(data_path, 'speakers.npy')   # data_input.py:76-83: present for multi-speaker corpora (VCTK)
+    if os.path.exists(spk_path):
+        data['speaker'] = np.load(spk_path).astype(np.int32)
+    return meta, data, norm
+
+
 def latest_checkpoint(ckpt_prefix):
     """tf.train.latest_checkpoint (train.py:49-52) for files named '<prefix>-<step>': the highest STEP, not the
     lexicographically last name ('tacotron-5000' sorts after 'tacotron-10000')."""
@@ -75,13 +102,19 @@ def latest_checkpoint(ckpt_prefix):
     return best
 
 
-def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY):
+def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False):
+    """corpus_fp32: standardise the whole corpus on the host and feed fp32 (load_corpus; A/B runs) instead of keeping it as stored
+    and standardising in the batch gather (open_corpus + norm=, the default).  The batches are bit-identical either way."""
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
-    corpus = load_corpus(config.data_path)
-    stft_mean = stft_std = None
+    corpus = load_corpus(config.data_path) if corpus_fp32 else open_corpus(config.data_path)
+    stft_mean = stft_std = norm = None
     if corpus is not None:
-        meta, data, stft_mean, stft_std = corpus
+        if corpus_fp32:
+            meta, data, stft_mean, stft_std = corpus
+        else:
+            meta, data, norm = corpus
+            stft_mean, stft_std = norm['stft']
         config.r, config.vocab_size = meta['r'], len(meta['vocab'])
         if 'speaker' in data:                       # train.py:29
             config.num_speakers = int(data['speaker'].max()) + 1
@@ -100,9 +133,9 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY):
     dev = torch.device('cuda', local)
     budget = float(os.environ.get('TACO_CORPUS_HBM_GB', '64')) * (1 << 30)
     if DeviceCorpus.nbytes(data) <= budget:
-        feeder = DeviceCorpus(data, config.batch_size, device=dev, seed=1000 + rank)
+        feeder = DeviceCorpus(data, config.batch_size, device=dev, seed=1000 + rank, norm=norm)
     else:
-        feeder = DeviceFeeder(data, config.batch_size, device=dev, depth=2, seed=1000 + rank)
+        feeder = DeviceFeeder(data, config.batch_size, device=dev, depth=2, seed=1000 + rank, norm=norm)
 
     def next_batch(step):
         return feeder.next()
@@ -198,10 +231,12 @@ if __name__ == '__main__':
     ap.add_argument('-d', '--debug', type=bool, default=False)
     ap.add_argument('-r', '--restore', type=bool, default=False)
     ap.add_argument('--steps', type=int, default=1000000)
+    ap.add_argument('--corpus-fp32', action='store_true',
+                    help='standardise the corpus on the host and feed fp32 (the earlier path) instead of keeping it as stored')
     a = ap.parse_args()
     c = Config()
     c.data_path = 'data/%s/' % a.train_set
     c.restore = a.restore
     c.save_path = 'debug' if a.debug else '%s/tacotron' % a.train_set
     print('Building Tacotron')
-    train(c, a.steps)
+    train(c, a.steps, corpus_fp32=a.corpus_fp32)
