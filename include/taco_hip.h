@@ -398,6 +398,40 @@ int64_t taco_audio_features_workspace_bytes(int B, int L);   /* B, L > 0, else T
 int taco_audio_features(const float* wave, const int* wave_len, const float* mel_basis, void* mel, void* stft, int* bounds,
                         int* kept, void* workspace, int B, int L, int max_len, int r, int out_fp16, void* stream);
 
+/* PCM decode and resampling, the stage in front of taco_audio_features: the role of librosa.load(fname, mono=True, sr=sr)
+ * (audio.py:39) from the bytes of the WAV data chunk on.  librosa resamples with resampy's 'kaiser_best' windowed sinc; the host
+ * (tacotron_amd.audio.resample_filter) evaluates that filter once per rate pair as a polyphase table and this entry point applies it.
+ *   pcm     (B, row_bytes) bytes: row b holds little-endian PCM frames as they sit in the file, channels interleaved; one format
+ *           per call: width in 1..4 bytes per sample (8-bit unsigned, 16 / 24 / 32-bit signed), channels in 1..8
+ *   rows    (B, 2) int32 on the DEVICE: (n_orig_b, n_calc_b), the row's input frames and the outputs to compute.  The host reads
+ *           nothing from it and derives no length: librosa's are n_calc = int(n_orig ratio), row length int(ceil(n_orig ratio)).
+ *           Used as n_orig_b clamped to [0, row_bytes / (width channels)], n_calc_b clamped to [0, L]
+ *   taps    (Q, n_left + n_right) fp32: row p serves the outputs t with (t P) % Q == p; its first n_left entries multiply
+ *           x[nn], x[nn - 1], ..., the other n_right multiply x[nn + 1], x[nn + 2], ..., nn = (t P) / Q (64-bit product); rows with
+ *           fewer taps are zero-padded.  P / Q = input rate / output rate
+ *   wave    (B, L) fp32
+ * Per row b:
+ *   - decode: sample = (u - 128) / 128 (8-bit), float(v) 2^-(bits - 1) with the int -> float conversion rounded to nearest even
+ *     (16 / 32-bit), sign-extended v times 2^-23 (24-bit); mono = the fp32 sum over the channels divided by their count in one IEEE
+ *     division, the sum in channel order (8 channels: the balanced tree of NumPy's 8-accumulator block) -- the bits of
+ *     x.reshape(-1, channels).mean(axis=1, dtype=float32), i.e. of tacotron_amd.audio.load_wav.  The mono signal x exists in LDS only
+ *   - P == Q is decode-only: wave[b, t] = x[t] for t < min(n_orig_b, n_calc_b); taps is not read and may be NULL
+ *   - otherwise wave[b, t] for t < n_calc_b is the sum over the taps of row (t P) % Q, in signal order (x[nn - n_left + 1] first,
+ *     x[nn + n_right] last), with x = 0 outside [0, n_orig_b): fp32 taps, one fp32 fused multiply-add chain per output
+ *   - wave[b, t] = 0 exactly for n_calc_b <= t < L (min(n_orig_b, n_calc_b) when decode-only); every element of wave is written
+ *     and nothing outside it
+ *   - bytes of row b behind n_orig_b frames have no influence
+ *   - no atomics: the same arguments give the same bits; row b of a B-row call is bit-identical to a B = 1 call on that row
+ * A workgroup computes TACO_WAVE_RESAMPLE_TILE consecutive outputs of one row from an LDS copy of the frames they read.  No
+ * workspace, no allocation, no host synchronisation, no workgroup waits for another one: one stream-ordered enqueue,
+ * graph-capturable.  NULL pcm / rows / wave, NULL taps with P != Q, width outside 1..4, channels outside 1..8, P, Q, n_left or
+ * n_right < 1, B <= 0 or > 65535, L <= 0, row_bytes <= 0 or not a multiple of width channels, and a P / Q and tap count whose tile
+ * does not fit 64 KiB of LDS (((TILE - 1) P / Q + 1 + n_left + n_right) floats; Q == 1: rounded up to a multiple of P, plus the taps)
+ * return TACO_EINVAL before anything is enqueued.  TACO_VERSION did not change with this entry point: detect it by the symbol. */
+#define TACO_WAVE_RESAMPLE_TILE 1024
+int taco_wave_resample(const uint8_t* pcm, int64_t row_bytes, int width, int channels, const int32_t* rows, const float* taps,
+                       int P, int Q, int n_left, int n_right, float* wave, int B, int L, void* stream);
+
 /* Bernoulli(p_keep) bytes from a counter-based hash RNG (replaces TF's dropout / Bernoulli sampler state). */
 int taco_fill_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, void* stream);
 

@@ -326,3 +326,188 @@ extern "C" int taco_audio_features(const float* wave, const int* wave_len_host, 
   TACO_LAUNCH_CHECK("audio_features");
   return TACO_OK;
 }
+
+// ---- PCM decode and kaiser_best resampling (taco_hip.h taco_wave_resample): the stage in front of the feature kernels -----------
+// A workgroup owns RS_TILE consecutive outputs of one row.  With first = (t0 P) / Q - (n_left - 1) the tile reads the frames
+// [first, first + span): it decodes them (and mixes the channels down) straight into LDS, frames outside [0, n_orig) as 0 -- the
+// clipping of the two dot products by the row's ends IS this zero extension (0 w = 0, s + 0 = s, exactly).  In signal order the K =
+// n_left + n_right taps of phase p are g[m] = taps[p][n_left - 1 - m] (m < n_left: the left wing, x[nn - i]) and taps[p][m] (the right
+// wing, x[nn + 1 + k]), and output t is sum_m g[m] x[nn - (n_left - 1) + m], one fp32 chain in that order.
+//   UNI (Q == 1): every output has phase 0 and nn = t P, so a tap is wave-uniform (an LDS broadcast of the row staged in signal
+//     order) and serves the RS_TILE / RS_BLOCK outputs of a lane.  LDS holds the span de-interleaved into P planes (frame u ->
+//     plane u % P, slot u / P): lanes with consecutive outputs then read consecutive words for every tap, whatever P is.
+//   otherwise the lanes of a wave have different phases: plain LDS layout, each lane reads its own tap row through L2.
+constexpr int RS_TILE = TACO_WAVE_RESAMPLE_TILE, RS_BLOCK = 256, RS_PER = RS_TILE / RS_BLOCK;
+constexpr int64_t RS_LDS_MAX = 64 * 1024;
+
+namespace {
+
+struct ResampleArgs {
+  const uint8_t* pcm;
+  const int32_t* rows;
+  const float* taps;
+  float* wave;
+  int64_t row_bytes;
+  int width, channels, P, Q, n_left, n_right, L, plane;   // plane: floats per LDS plane (UNI)
+};
+
+// one channel of one frame, audio.load_wav's arithmetic: 8-bit (u - 128) / 128; 16 / 32-bit float(v) 2^-(bits - 1) (int -> float
+// rounds to nearest even); 24-bit sign-extended, times 2^-23
+__device__ __forceinline__ float rs_sample(const uint8_t* p, int width) {
+  switch (width) {
+    case 1: return ((float)p[0] - 128.0f) / 128.0f;
+    case 2: return (float)(int16_t)(uint16_t)(p[0] | (p[1] << 8)) * 0x1p-15f;
+    case 3: {
+      int32_t v = p[0] | (p[1] << 8) | (p[2] << 16);
+      v = v >= (1 << 23) ? v - (1 << 24) : v;
+      return (float)v * 0x1p-23f;
+    }
+    default: return (float)(int32_t)((uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24)) * 0x1p-31f;
+  }
+}
+
+// mono frame: numpy's mean(axis=1, dtype=float32) over the channels -- its fp32 sum (in channel order below 8 channels; 8 channels
+// go through its 8-accumulator block, a balanced tree) and one IEEE division by the count
+__device__ __forceinline__ float rs_frame(const uint8_t* p, int width, int channels) {
+  if (channels == 1) return rs_sample(p, width);
+  float s;
+  if (channels == 8) {
+    float r[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) r[c] = rs_sample(p + c * width, width);
+    s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  } else {
+    s = rs_sample(p, width);
+    for (int c = 1; c < channels; ++c) s += rs_sample(p + c * width, width);
+  }
+  return __fdiv_rn(s, (float)channels);
+}
+
+// P == Q: wave[b, t] = frame t of the row for t < min(n_orig, n_calc), 0 behind
+__global__ __launch_bounds__(RS_BLOCK) void wave_decode_kernel(ResampleArgs a) {
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * RS_TILE;
+  const int tile = min(RS_TILE, a.L - t0);
+  const int fb = a.width * a.channels;
+  const int n_orig = max(0, (int)min<int64_t>(a.rows[2 * b], a.row_bytes / fb));
+  const int n = min(n_orig, a.rows[2 * b + 1]);
+  const uint8_t* row = a.pcm + (int64_t)b * a.row_bytes;
+  float* out = a.wave + (int64_t)b * a.L + t0;
+  for (int o = threadIdx.x; o < tile; o += RS_BLOCK)
+    out[o] = t0 + o < n ? rs_frame(row + (int64_t)(t0 + o) * fb, a.width, a.channels) : 0.f;
+}
+
+template <bool UNI>
+__global__ __launch_bounds__(RS_BLOCK) void wave_resample_kernel(ResampleArgs a) {
+  extern __shared__ float rs_x[];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int t0 = blockIdx.x * RS_TILE;
+  const int tile = min(RS_TILE, a.L - t0);                       // outputs of this workgroup (the grid covers L exactly)
+  const int fb = a.width * a.channels;
+  const int n_orig = max(0, (int)min<int64_t>(a.rows[2 * b], a.row_bytes / fb));   // never a byte outside the row
+  const int n_calc = max(0, min(a.rows[2 * b + 1], a.L));
+  float* out = a.wave + (int64_t)b * a.L + t0;
+  const int live = min(tile, n_calc - t0);                       // outputs below n_calc; <= 0: the tile is all zeros
+  if (live <= 0) {
+    for (int o = tid; o < tile; o += RS_BLOCK) out[o] = 0.f;
+    return;
+  }
+  const int K = a.n_left + a.n_right;
+  const int64_t first = (int64_t)t0 * a.P / a.Q - (a.n_left - 1);
+  const int span = (int)((int64_t)(t0 + live - 1) * a.P / a.Q - (a.n_left - 1) + K - first);   // <= the host's bound
+  const uint8_t* row = a.pcm + (int64_t)b * a.row_bytes;
+  for (int u = tid; u < span; u += RS_BLOCK) {
+    const int64_t j = first + u;
+    const float v = (j >= 0 && j < n_orig) ? rs_frame(row + j * fb, a.width, a.channels) : 0.f;
+    if (UNI) rs_x[(u % a.P) * a.plane + u / a.P] = v;
+    else rs_x[u] = v;
+  }
+  float* gs = rs_x + a.plane * a.P;                              // UNI: the K taps in signal order, behind the planes
+  if (UNI)
+    for (int m = tid; m < K; m += RS_BLOCK) gs[m] = a.taps[m < a.n_left ? a.n_left - 1 - m : m];
+  __syncthreads();
+  if (UNI) {
+    float acc[RS_PER];
+#pragma unroll
+    for (int r = 0; r < RS_PER; ++r) acc[r] = 0.f;
+    int pl = 0, slot = 0;                                        // plane and slot of tap m: m % P, m / P
+#pragma unroll 4
+    for (int m = 0; m < K; ++m) {
+      const float g = gs[m];                                     // one address for the whole wave: an LDS broadcast
+      const float* x = rs_x + pl * a.plane + slot + tid;
+#pragma unroll
+      for (int r = 0; r < RS_PER; ++r) acc[r] = fmaf(g, x[r * RS_BLOCK], acc[r]);   // (slots past `span` are never stored)
+      if (++pl == a.P) {
+        pl = 0;
+        ++slot;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < RS_PER; ++r) {
+      const int o = tid + r * RS_BLOCK;
+      if (o < tile) out[o] = o < live ? acc[r] : 0.f;
+    }
+  } else {
+    for (int o = tid; o < tile; o += RS_BLOCK) {
+      float acc = 0.f;
+      if (o < live) {
+        const int64_t tp = (int64_t)(t0 + o) * a.P;
+        const int64_t nn = tp / a.Q;
+        const float* g = a.taps + (tp - nn * a.Q) * K;
+        const float* x = rs_x + (nn - (a.n_left - 1) - first);
+        for (int m = 0; m < a.n_left; ++m) acc = fmaf(g[a.n_left - 1 - m], x[m], acc);
+        for (int m = a.n_left; m < K; ++m) acc = fmaf(g[m], x[m], acc);
+      }
+      out[o] = acc;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int taco_wave_resample(const uint8_t* pcm, int64_t row_bytes, int width, int channels, const int32_t* rows,
+                                  const float* taps, int P, int Q, int n_left, int n_right, float* wave, int B, int L,
+                                  void* stream) {
+  TACO_REQUIRE(pcm && rows && wave, "wave_resample: null pointer");
+  TACO_REQUIRE(width >= 1 && width <= 4 && channels >= 1 && channels <= 8, "wave_resample: width=%d outside 1..4 or channels=%d outside 1..8",
+               width, channels);
+  TACO_REQUIRE(P >= 1 && Q >= 1 && n_left >= 1 && n_right >= 1, "wave_resample: P=%d Q=%d n_left=%d n_right=%d must all be >= 1", P, Q,
+               n_left, n_right);
+  TACO_REQUIRE(taps || P == Q, "wave_resample: taps is NULL and P=%d != Q=%d", P, Q);
+  TACO_REQUIRE(B > 0 && B <= 65535 && L > 0, "wave_resample: B=%d (1..65535) L=%d", B, L);
+  TACO_REQUIRE(row_bytes > 0 && row_bytes % (width * channels) == 0, "wave_resample: row_bytes=%lld is not a positive multiple of width * channels = %d",
+               (long long)row_bytes, width * channels);
+  ResampleArgs a;
+  a.pcm = pcm;
+  a.rows = rows;
+  a.taps = taps;
+  a.wave = wave;
+  a.row_bytes = row_bytes;
+  a.width = width;
+  a.channels = channels;
+  a.P = P;
+  a.Q = Q;
+  a.n_left = n_left;
+  a.n_right = n_right;
+  a.L = L;
+  a.plane = 0;
+  const dim3 grid((unsigned)cdiv(L, RS_TILE), (unsigned)B);
+  hipStream_t s = as_stream(stream);
+  if (P == Q) {
+    TACO_KLAUNCH(wave_decode_kernel, grid, dim3(RS_BLOCK), 0, s, a);   // decode-only: no filter, taps is not read
+  } else {
+    // frames a tile reads: the positions of its first and last output are at most (RS_TILE - 1) P / Q + 1 apart
+    const int64_t span = (int64_t)(RS_TILE - 1) * P / Q + 1 + n_left + n_right;
+    int64_t lds = span * 4;
+    if (Q == 1) {
+      a.plane = (int)((span + P - 1) / P);   // last slot stored (span - 1) / P; last slot read RS_TILE - 1 + (K - 1) / P, not behind it
+      lds = ((int64_t)a.plane * P + n_left + n_right) * 4;   // and the taps in signal order behind the planes
+    }
+    TACO_REQUIRE(lds <= RS_LDS_MAX, "wave_resample: P=%d Q=%d with %d taps needs %lld bytes of LDS per tile, more than %lld", P, Q,
+                 n_left + n_right, (long long)lds, (long long)RS_LDS_MAX);
+    if (Q == 1) TACO_KLAUNCH(wave_resample_kernel<true>, grid, dim3(RS_BLOCK), (size_t)lds, s, a);
+    else TACO_KLAUNCH(wave_resample_kernel<false>, grid, dim3(RS_BLOCK), (size_t)lds, s, a);
+  }
+  TACO_LAUNCH_CHECK("wave_resample");
+  return TACO_OK;
+}

@@ -120,6 +120,7 @@ EXPORTS = {
     'taco_wave_finish': (C.c_int, [_P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'taco_wave_resample': (C.c_int, [_P, C.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     'taco_fill_bernoulli': (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
     'taco_profile_enable': (C.c_int, [_I]),
     'taco_debug_last_cluster': (C.c_int, [_I]),
@@ -598,6 +599,64 @@ def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch
     _check(_lib.taco_audio_features(ptr(wave), lens, ptr(mel_basis), ptr(mel), ptr(stft), ptr(bounds), ptr(kept), ptr(work), B, L,
                                     int(max_len), int(r), int(out_dtype == torch.float16), stream_ptr()), 'taco_audio_features')
     return mel, stft, kept, bounds
+
+
+WAVE_RESAMPLE_TILE = 1024   # outputs per workgroup of taco_wave_resample (include/taco_hip.h TACO_WAVE_RESAMPLE_TILE)
+
+
+def wave_resample(pcm, rows, taps, width, channels, P, Q, n_left, n_right, L=None, out=None):
+    """PCM decode and kaiser_best resampling (include/taco_hip.h taco_wave_resample): pcm (B, row_bytes) uint8, the interleaved
+    little-endian frames of B files of one format (width 1..4 bytes per sample, channels 1..8); rows (B, 2) int32 on the device,
+    (n_orig_b, n_calc_b); taps (Q, n_left + n_right) float32, the polyphase table of audio.resample_filter (None allowed when
+    P == Q: decode-only) -> wave (B, L) float32: row b holds its n_calc_b resampled samples (P == Q: its decoded frames), zeros behind.
+    L: the width of a fresh result; out: the caller's own (B, L) buffer instead."""
+    who = 'wave_resample'
+    if pcm.dim() != 2 or pcm.dtype != torch.uint8 or pcm.shape[0] < 1 or pcm.shape[1] < 1 or not pcm.is_contiguous():
+        raise ValueError('%s: pcm must be a contiguous uint8 tensor of shape (B, row_bytes), got %s %s' % (who, pcm.dtype, tuple(pcm.shape)))
+    B, row_bytes = pcm.shape
+    dev = pcm.device
+    if B > 65535:
+        raise ValueError('%s: at most 65535 rows per call, got %d' % (who, B))
+    ints = dict(width=width, channels=channels, P=P, Q=Q, n_left=n_left, n_right=n_right)
+    for name, v in ints.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError('%s: %s must be an integer, got %r' % (who, name, v))
+    width, channels, P, Q, n_left, n_right = (int(ints[k]) for k in ('width', 'channels', 'P', 'Q', 'n_left', 'n_right'))
+    if not (1 <= width <= 4 and 1 <= channels <= 8):
+        raise ValueError('%s: width must be in 1..4 and channels in 1..8, got %d and %d' % (who, width, channels))
+    if min(P, Q, n_left, n_right) < 1:
+        raise ValueError('%s: P, Q, n_left and n_right must be >= 1, got %d, %d, %d, %d' % (who, P, Q, n_left, n_right))
+    if row_bytes % (width * channels):
+        raise ValueError('%s: row_bytes %d is not a multiple of width * channels = %d' % (who, row_bytes, width * channels))
+    if tuple(rows.shape) != (B, 2) or rows.dtype != torch.int32 or rows.device != dev or not rows.is_contiguous():
+        raise ValueError('%s: rows must be a contiguous int32 tensor of shape (%d, 2) on %s, got %s %s on %s'
+                         % (who, B, dev, rows.dtype, tuple(rows.shape), rows.device))
+    if taps is None and P != Q:
+        raise ValueError('%s: taps may be None only when P == Q (decode-only), got P = %d, Q = %d' % (who, P, Q))
+    if taps is not None and (tuple(taps.shape) != (Q, n_left + n_right) or taps.dtype != torch.float32 or taps.device != dev
+                             or not taps.is_contiguous()):
+        raise ValueError('%s: taps must be a contiguous float32 tensor of shape (%d, %d) on %s, got %s %s on %s'
+                         % (who, Q, n_left + n_right, dev, taps.dtype, tuple(taps.shape), taps.device))
+    if P != Q:   # the library's own rule: the frames one tile reads must fit 64 KiB of LDS
+        span = (WAVE_RESAMPLE_TILE - 1) * P // Q + 1 + n_left + n_right
+        if (-(-span // P) * P + n_left + n_right if Q == 1 else span) * 4 > 64 * 1024:
+            raise ValueError('%s: P / Q = %d / %d with %d taps reads %d frames per tile, more than 64 KiB of LDS hold'
+                             % (who, P, Q, n_left + n_right, span))
+    if (L is None) == (out is None):
+        raise ValueError('%s: give exactly one of L and out' % who)
+    if out is None and (isinstance(L, bool) or int(L) != L or int(L) < 1):
+        raise ValueError('%s: L must be a positive integer, got %r' % (who, L))
+    if out is not None and (out.dim() != 2 or out.shape[0] != B or out.shape[1] < 1):
+        raise ValueError('%s: out must have shape (%d, L), got %s' % (who, B, tuple(out.shape)))
+    L = int(L) if out is None else out.shape[1]
+    if out is not None:
+        _own_or_given(out, (B, L), torch.float32, dev, who + ': out')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: pcm must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    wave = _own_or_given(out, (B, L), torch.float32, dev, who + ': out')
+    _check(_lib.taco_wave_resample(ptr(pcm), row_bytes, width, channels, ptr(rows), ptr(taps), P, Q, n_left, n_right, ptr(wave), B, L,
+                                   stream_ptr()), 'taco_wave_resample')
+    return wave
 
 
 def fill_bernoulli(out, p_one, seed):

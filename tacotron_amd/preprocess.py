@@ -13,7 +13,12 @@ speakers.npy.  Differences from the reference, on purpose:
   - speakers.npy holds the speakers of the KEPT utterances; the reference saved one per listed utterance (preprocess.py:202-203),
     which misaligns it with the other arrays as soon as one utterance is dropped;
   - meta.pkl records the rate the corpus was read at; the reference's save_vocab(name) left it at its default of 16000 for VCTK;
-  - WAV files are read by audio.load_wav (stdlib `wave`; resampling by scipy's resample_poly instead of resampy).
+  - WAV files are read with the standard library's `wave`.  With resample='host' (the default) audio.load_wav decodes on the reader
+    threads and resamples a file of another rate with scipy's resample_poly -- a polyphase FIR with scipy's own Kaiser design,
+    NOT the reference's filter; with resample='device' (--resample device) the reader threads hand over the files' bytes and the
+    GPU decodes and resamples them (audio.load_batch_device, taco_wave_resample) with resampy's 'kaiser_best' windowed sinc, the
+    filter behind the reference's librosa.load, and scipy is not needed.  Only VCTK (48 kHz files read at 24 kHz) is resampled;
+    for a corpus stored at its own rate both paths decode to the same bits.
 """
 from __future__ import annotations
 
@@ -111,9 +116,17 @@ def _truncate_npy(path, rows):
         f.truncate(offset + rows * int(np.prod(new_shape[1:], dtype=np.int64)) * dtype.itemsize)
 
 
-def preprocess(data, out_dir, sr=16000, r=2, max_len=audio.MAXIMUM_AUDIO_LENGTH, batch=BATCH, verbose=True):
-    """preprocess.preprocess (preprocess.py:161-204) with the features from the GPU.  Returns the number of kept utterances."""
+RESAMPLE_PATHS = ('host', 'device')
+
+
+def preprocess(data, out_dir, sr=16000, r=2, max_len=audio.MAXIMUM_AUDIO_LENGTH, batch=BATCH, verbose=True, resample='host'):
+    """preprocess.preprocess (preprocess.py:161-204) with the features from the GPU.  resample: where the files are decoded and
+    brought to `sr` -- 'host' (audio.load_wav) or 'device' (audio.load_batch_device: resampy's kaiser_best filter).  Returns the
+    number of kept utterances."""
     import torch
+
+    if resample not in RESAMPLE_PATHS:
+        raise ValueError('preprocess: resample must be one of %s, got %r' % (', '.join(RESAMPLE_PATHS), resample))
 
     os.makedirs(out_dir, exist_ok=True)
     prompts, files = data['prompts'], data['audio_files']
@@ -130,13 +143,19 @@ def preprocess(data, out_dir, sr=16000, r=2, max_len=audio.MAXIMUM_AUDIO_LENGTH,
     count = 0
     t0 = time.perf_counter()
     with ThreadPoolExecutor(max_workers=_reader_threads()) as pool:
-        load = lambda lo: [pool.submit(audio.load_wav, f, sr) for f in files[lo:lo + batch]]   # noqa: E731
+        if resample == 'device':
+            load = lambda lo: [pool.submit(audio.read_wav_raw, f) for f in files[lo:lo + batch]]   # noqa: E731
+        else:
+            load = lambda lo: [pool.submit(audio.load_wav, f, sr) for f in files[lo:lo + batch]]   # noqa: E731
         pending = load(0)
         for lo in range(0, n, batch):
             waves = [fut.result() for fut in pending]
             pending = load(lo + batch) if lo + batch < n else []   # the next batch is read while this one runs on the GPU
             nb = len(waves)
-            mel, stft, kept, _ = audio.process_audio(waves, None, r, max_len, torch.float16)
+            lengths = None
+            if resample == 'device':
+                waves, lengths = audio.load_batch_device(waves, sr)
+            mel, stft, kept, _ = audio.process_audio(waves, lengths, r, max_len, torch.float16)
             h_mel[:nb].copy_(mel, non_blocking=True)
             h_stft[:nb].copy_(stft, non_blocking=True)
             k = kept.cpu().numpy()                          # (synchronises the stream: the pinned copies are complete)
@@ -170,17 +189,24 @@ def preprocess(data, out_dir, sr=16000, r=2, max_len=audio.MAXIMUM_AUDIO_LENGTH,
     return count
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Preprocess a corpus into data/<set>/ (features on the GPU)')
     ap.add_argument('dataset', help='name of the dataset to preprocess: ' + ', '.join(sorted(prepare_functions)))
     ap.add_argument('--data-dir', default='data/')
     ap.add_argument('--r', type=int, default=2, help='decoder frames per step (audio.r)')
-    a = ap.parse_args(argv)
+    ap.add_argument('--resample', choices=RESAMPLE_PATHS, default='host',
+                    help="where WAV files are decoded and resampled: 'host' (scipy's resample_poly) or 'device' (the GPU, with "
+                         "resampy's kaiser_best filter, the reference's)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if a.dataset not in prepare_functions:
         raise NotImplementedError('No prepare function exists for the %s dataset' % a.dataset)
     sr = 24000 if a.dataset == 'vctk' else 16000
     data = prepare_functions[a.dataset](a.data_dir)
-    return preprocess(data, os.path.join(a.data_dir, a.dataset), sr=sr, r=a.r)
+    return preprocess(data, os.path.join(a.data_dir, a.dataset), sr=sr, r=a.r, resample=a.resample)
 
 
 if __name__ == '__main__':
