@@ -378,6 +378,47 @@ int64_t taco_wave_finish_workspace_bytes(int B, int L);          /* B > 0, L > 0
 int taco_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out, int16_t* pcm,
                      int32_t* bounds, float* peak, void* workspace, int B, int L, void* stream);
 
+/* Joining the finished pieces of long prompts (no reference counterpart: the reference cannot speak a line of more than 140
+ * characters).  A long prompt is cut on the host where a speaker would pause (tacotron_amd.data.split_prompt), its pieces are
+ * synthesised as rows of ordinary batches and finished by taco_wave_finish; this entry point puts the finished pieces of every
+ * prompt together -- silence between them, a short linear ramp at every interior edge -- and emits one fp32 row and / or one PCM16
+ * row per prompt, scaled by the PROMPT'S peak.
+ *   pieces  (N, pitch) fp32, pitch >= L: row i holds piece i from index 0 -- the `out` of taco_wave_finish, already shifted by its
+ *           trim start
+ *   bounds  (N, 2) int32 on the DEVICE: the `bounds` of taco_wave_finish as written; len_i = clamp(bounds[i][1] - bounds[i][0], 0, L).
+ *           The host reads nothing from it
+ *   first   (P + 1) int32 in HOST memory: the pieces of prompt p are rows first[p] .. first[p+1] - 1 (checked: first[0] == 0,
+ *           non-decreasing, first[P] == N; a prompt may have no pieces; copied into the workspace on `stream`)
+ *   gap     (N) int32 in HOST memory: samples of silence behind piece i (checked >= 0, copied likewise; ignored for the last piece
+ *           of a prompt)
+ *   fade    >= 0: the length in samples of the linear ramp at every interior edge
+ *   out     (P, Lj) fp32, nullable;  pcm (P, Lj) int16, nullable; at least one of the two
+ *   offsets (N) int32, total (P) int32 and peak (P) fp32, all required
+ * Per prompt p, with o running from 0 and o += len_i + gap_i behind each piece (64-bit):
+ *   1. offsets[i] = min(o, Lj);  total[p] = min(Lj, o_last + len_last), 0 for a prompt without pieces
+ *   2. f_i = min(fade, len_i / 2) (integer division: the two ramps of a piece never meet; len_i <= 1 has none) and
+ *      w(k) = (k + 0.5) / f_i -- one rounded fp32 addition, one IEEE fp32 division.  Sample n of piece i is x w(n) for n < f_i when i
+ *      is not the first piece of its prompt, x w(len_i - 1 - n) for n >= len_i - f_i when i is not the last one -- one rounded fp32
+ *      multiply (no contraction) -- and x bit for bit otherwise; fade == 0 copies every sample
+ *   3. the sample goes to out[p, o_i + n] when that index is below Lj; gaps are exactly 0, and so is everything from total[p] to Lj
+ *   4. peak[p] = max |v| over [0, total[p]) (exact); 0 for an empty range
+ *   5. pcm[p, j] = (int16) trunc(v' * 32767.0f) with v' = peak_p > 1 ? v / peak_p : v: taco_wave_finish's rule with the prompt's peak.
+ *      The pieces are joined at their fp32 amplitudes; the per-piece peaks of taco_wave_finish play no part
+ *   - every element of out, pcm, offsets, total and peak is written and nothing outside them, for any Lj and any alignment of out
+ *     and pcm (16-byte / 8-byte stores where the row's address allows, scalar ones at a row's two edges);
+ *   - pieces[i, n >= len_i] has no influence on anything (it may hold NaN); the workspace may hold arbitrary bytes;
+ *   - no atomics: the same arguments give the same bits;
+ *   - prompt p of a P-prompt call is bit-identical to a P = 1 call on its own pieces.
+ * No allocation, no host synchronisation, no workgroup waits for another one; everything is ordered on `stream`.  workspace:
+ * taco_wave_join_workspace_bytes bytes (the joined fp32 rows when out is NULL, the tile maxima, the copies of first and gap).  NULL
+ * pieces / bounds / first / gap / offsets / total / peak / workspace, out and pcm both NULL, out overlapping pieces, N, P, L or
+ * Lj <= 0, pitch < L, fade < 0, a first that does not start at 0, decreases or does not end at N, and a negative gap return
+ * TACO_EINVAL before anything is enqueued.  TACO_VERSION did not change with these two entry points: detect them by the symbol. */
+int64_t taco_wave_join_workspace_bytes(int N, int P, int Lj);      /* N, P, Lj > 0, else TACO_EINVAL */
+int taco_wave_join(const float* pieces, int64_t pitch, const int32_t* bounds, const int32_t* first, const int32_t* gap, int fade,
+                   float* out, int16_t* pcm, int32_t* offsets, int32_t* total, float* peak, void* workspace,
+                   int N, int P, int L, int Lj, void* stream);
+
 /* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
 /* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length
  * 1200, hop_length 300, pre-emphasis 0.97, log(|.| + 1e-8), 80 mels): librosa.effects.trim (0.6 form: frame mean squares at

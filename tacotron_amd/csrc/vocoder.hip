@@ -27,7 +27,8 @@
 // <false, false, true> is the body both older entry points launch; alpha = 0 launches it as well.
 //
 // Waveform finishing (taco_wave_finish) follows the Griffin-Lim kernels below: the de-emphasis scan, the energy trim, the peak and
-// the fp32 / PCM16 emit of the waveform gl_wave_kernel wrote.
+// the fp32 / PCM16 emit of the waveform gl_wave_kernel wrote.  Joining the finished pieces of a long prompt (taco_wave_join) comes
+// last: the pieces' offsets, the joined fp32 row with its edge ramps, the prompt's peak and PCM16.
 #include <algorithm>
 
 #include "common.h"
@@ -540,9 +541,161 @@ __global__ __launch_bounds__(256) void wf_emit_kernel(const float* __restrict__ 
   }
 }
 
+// ---- joining finished pieces (taco_hip.h taco_wave_join): offsets, joined fp32 rows with edge ramps, peak, PCM16 ---------------
+//   wj_offsets  one workgroup per prompt: o_i = sum of len + gap of the pieces in front, an integer scan over chunks of 256 pieces
+//               with a 64-bit carry (any number of pieces per prompt); offsets (clamped to Lj) and total
+//   wj_emit     one workgroup per (prompt, tile of 1024 outputs): the piece under an output by binary search in the prompt's
+//               offsets -- the clamped ones are enough: a piece at or behind Lj is under no output -- then the sample, ramped at
+//               interior edges, or 0 in a gap; max |v| of the tile into the workspace
+//   wj_pcm      one workgroup per (prompt, tile): the prompt's peak from its tile maxima (every workgroup forms it; the first one
+//               of a prompt stores it), then PCM16 of the joined fp32 row
+// A thread owns 4 consecutive outputs that start on a 16-byte (fp32) / 8-byte (int16) boundary of the ROW'S ADDRESS, whatever Lj and
+// the pointer are: chunk c of a row that begins `a` elements behind such a boundary covers outputs [4c - a, 4c - a + 4); whole chunks
+// are one vector store, the two edge chunks scalar ones.  The source is read by scalars (it is misaligned against the destination by
+// offsets[i] % 4 in general; a wave still reads 1 KiB of consecutive floats).  Maxima are exact in any order and the scan is in
+// integers: nothing depends on P, on the tiling or on the alignment.  No workgroup waits for another one.
+constexpr int WJ_T = 256, WJ_PER = 4, WJ_TILE = WJ_T * WJ_PER;
+
+__device__ __forceinline__ int wj_len(const int32_t* __restrict__ bounds, int i, int L) {
+  const int64_t n = (int64_t)bounds[2 * i + 1] - (int64_t)bounds[2 * i];
+  return n < 0 ? 0 : (n > L ? L : (int)n);
+}
+
+__global__ __launch_bounds__(WJ_T) void wj_offsets_kernel(const int32_t* __restrict__ bounds, const int32_t* __restrict__ first,
+                                                          const int32_t* __restrict__ gap, int32_t* __restrict__ offsets,
+                                                          int32_t* __restrict__ total, int L, int Lj) {
+  __shared__ long long sh[WJ_T / 64];
+  const int p = blockIdx.x, lo = first[p], hi = first[p + 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lo == hi) {   // (uniform) a prompt without pieces
+    if (threadIdx.x == 0) total[p] = 0;
+    return;
+  }
+  long long carry = 0;   // o of the chunk's first piece
+  for (int64_t base = lo; base < hi; base += WJ_T) {   // (uniform)
+    const int i = base + threadIdx.x < hi ? (int)(base + threadIdx.x) : -1;
+    int len = 0;
+    long long step = 0;
+    if (i >= 0) {
+      len = wj_len(bounds, i, L);
+      step = (long long)len + (i + 1 < hi ? (long long)gap[i] : 0);   // (the gap behind a prompt's last piece is ignored)
+    }
+    long long inc = step;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const long long t = __shfl_up(inc, d);
+      if (lane >= d) inc += t;
+    }
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    long long o = carry + inc - step;
+    for (int k = 0; k < w; ++k) o += sh[k];
+    if (i >= 0) {
+      offsets[i] = (int32_t)(o < Lj ? o : Lj);
+      if (i == hi - 1) total[p] = (int32_t)(o + len < Lj ? o + len : Lj);
+    }
+    carry += (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();   // sh is written again in the next chunk
+  }
+}
+
+// sample n < len of piece i (row `src`), ramped when it lies within f = min(fade, len / 2) samples of an interior edge
+__device__ __forceinline__ float wj_sample(const float* __restrict__ src, int n, int len, int fade, bool is_first, bool is_last) {
+  const float x = src[n];
+  const int f = min(fade, len >> 1);
+  if (f > 0) {
+    if (!is_first && n < f) return __fmul_rn(x, __fdiv_rn(__fadd_rn((float)n, 0.5f), (float)f));
+    if (!is_last && n >= len - f) return __fmul_rn(x, __fdiv_rn(__fadd_rn((float)(len - 1 - n), 0.5f), (float)f));
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(WJ_T) void wj_emit_kernel(const float* __restrict__ pieces, int64_t pitch, const int32_t* __restrict__ bounds,
+                                                       const int32_t* __restrict__ first, const int32_t* __restrict__ offsets, int fade,
+                                                       float* __restrict__ dst, int64_t dst_pitch, float* __restrict__ tmax, int ntile,
+                                                       int L, int Lj) {
+  __shared__ float sh[WJ_T / 64];
+  const int p = blockIdx.x / ntile, t = blockIdx.x % ntile;
+  const int lo = first[p], hi = first[p + 1];
+  float* row = dst + (int64_t)p * dst_pitch;
+  const int a = (int)((reinterpret_cast<uintptr_t>(row) >> 2) & 3);   // floats of the row's start behind a 16-byte boundary
+  const int64_t j0 = ((int64_t)t * WJ_T + threadIdx.x) * WJ_PER - a;
+  float v[WJ_PER] = {0.f, 0.f, 0.f, 0.f};
+  if (j0 < Lj && hi > lo) {
+    const int jf = j0 < 0 ? 0 : (int)j0;
+    int i = lo, e = hi;   // the last piece with offsets[i] <= jf is in [i, e); offsets[lo] == 0
+    while (e - i > 1) {
+      const int mid = i + ((e - i) >> 1);
+      if (offsets[mid] <= jf) i = mid; else e = mid;
+    }
+    int off = offsets[i], len = wj_len(bounds, i, L);
+#pragma unroll
+    for (int k = 0; k < WJ_PER; ++k) {
+      const int64_t j = j0 + k;
+      if (j < 0 || j >= Lj) continue;
+      while (i + 1 < hi && offsets[i + 1] <= j) {   // (a piece that starts at Lj is under no output: offsets are clamped to Lj)
+        ++i;
+        off = offsets[i];
+        len = wj_len(bounds, i, L);
+      }
+      const int n = (int)j - off;
+      if (n < len) v[k] = wj_sample(pieces + (int64_t)i * pitch, n, len, fade, i == lo, i == hi - 1);
+    }
+  }
+  if (j0 >= 0 && j0 + WJ_PER <= Lj) {
+    *reinterpret_cast<float4*>(row + j0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < WJ_PER; ++k)
+      if (j0 + k >= 0 && j0 + k < Lj) row[j0 + k] = v[k];
+  }
+  float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));   // (outputs outside the row stayed 0)
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) tmax[(int64_t)p * ntile + t] = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+
+// peak[p] = the maximum of the prompt's tile maxima; pcm by wf_emit_kernel's rule with that peak.  tiles: workgroups per prompt
+// (ntile, or 1 when there is no pcm: the peak alone)
+__global__ __launch_bounds__(WJ_T) void wj_pcm_kernel(const float* __restrict__ src, int64_t src_pitch, const float* __restrict__ tmax,
+                                                      int ntile, int tiles, float* __restrict__ peak, int16_t* __restrict__ pcm, int Lj) {
+  __shared__ float sh[WJ_T / 64];
+  const int p = blockIdx.x / tiles, t = blockIdx.x % tiles;
+  float m = 0.f;
+  for (int k = threadIdx.x; k < ntile; k += WJ_T) m = fmaxf(m, tmax[(int64_t)p * ntile + k]);
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  __syncthreads();
+  const float pk = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  if (t == 0 && threadIdx.x == 0) peak[p] = pk;
+  if (!pcm) return;
+  int16_t* row = pcm + (int64_t)p * Lj;
+  const int a = (int)((reinterpret_cast<uintptr_t>(row) >> 1) & 3);   // samples of the row's start behind an 8-byte boundary
+  const int64_t j0 = ((int64_t)t * WJ_T + threadIdx.x) * WJ_PER - a;
+  if (j0 >= Lj) return;
+  const float* x = src + (int64_t)p * src_pitch;
+  int16_t q[WJ_PER] = {0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < WJ_PER; ++k) {
+    const int64_t j = j0 + k;
+    if (j < 0 || j >= Lj) continue;
+    const float u = x[j];
+    q[k] = (int16_t)(int)truncf(__fmul_rn(pk > 1.f ? __fdiv_rn(u, pk) : u, 32767.0f));
+  }
+  if (j0 >= 0 && j0 + WJ_PER <= Lj) {
+    *reinterpret_cast<short4*>(row + j0) = make_short4(q[0], q[1], q[2], q[3]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < WJ_PER; ++k)
+      if (j0 + k >= 0 && j0 + k < Lj) row[j0 + k] = q[k];
+  }
+}
+
 }  // namespace
 
-// ---- C ABI (include/taco_hip.h): the Griffin-Lim entry points and taco_wave_finish, each workspace size beside its float count
+// ---- C ABI (include/taco_hip.h): the Griffin-Lim entry points, taco_wave_finish and taco_wave_join, each workspace
+// size beside its float count
 static int64_t griffinlim_workspace_floats(int B, int F) {
   return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (NFFT + (int64_t)HOP * (F - 1)) + 64;
 }
@@ -688,5 +841,52 @@ extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float
   TACO_KLAUNCH(wf_bounds_kernel, dim3(B), dim3(WF_BT), 0, s, ms, nms, pm, npm, samples, trim_top_db, bounds, peak, L);
   TACO_KLAUNCH(wf_emit_kernel, dim3(std::min(cdiv(L, 1024), 2048), B), dim3(256), 0, s, y, pitch, bounds, peak, out, pcm, L);
   TACO_LAUNCH_CHECK("wave_finish");
+  return TACO_OK;
+}
+
+// workspace of taco_wave_join: the joined fp32 rows (P, Lj rounded up to 4; used when out is NULL), the tile maxima, the device copies
+// of first and gap, and 64 bytes of slack for the 16-byte alignment of the rows
+static int64_t wj_pitch(int Lj) { return ((int64_t)Lj + 3) & ~(int64_t)3; }
+static int wj_tiles(int Lj) { return cdiv(cdiv((int64_t)Lj + 3, WJ_PER), WJ_T); }   // chunks of a row at its worst alignment
+extern "C" int64_t taco_wave_join_workspace_bytes(int N, int P, int Lj) {
+  if (N <= 0 || P <= 0 || Lj <= 0) return TACO_EINVAL;
+  return ((int64_t)P * (wj_pitch(Lj) + wj_tiles(Lj)) + (int64_t)P + 1 + N) * 4 + 64;
+}
+
+extern "C" int taco_wave_join(const float* pieces, int64_t pitch, const int32_t* bounds, const int32_t* first, const int32_t* gap,
+                              int fade, float* out, int16_t* pcm, int32_t* offsets, int32_t* total, float* peak, void* workspace,
+                              int N, int P, int L, int Lj, void* stream) {
+  TACO_REQUIRE(pieces && bounds && first && gap && offsets && total && peak && workspace, "wave_join: null pointer");
+  TACO_REQUIRE(out || pcm, "wave_join: out and pcm are both NULL");
+  TACO_REQUIRE(N > 0 && P > 0 && L > 0 && Lj > 0, "wave_join: N=%d P=%d L=%d Lj=%d", N, P, L, Lj);
+  TACO_REQUIRE(pitch >= L, "wave_join: pitch %lld is below L=%d", (long long)pitch, L);
+  TACO_REQUIRE(fade >= 0, "wave_join: fade %d is negative", fade);
+  if (out) {
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(pieces), p1 = p0 + (((uint64_t)N - 1) * (uint64_t)pitch + (uint64_t)L) * 4;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uint64_t)P * (uint64_t)Lj * 4;
+    TACO_REQUIRE(o1 <= p0 || p1 <= o0, "wave_join: out overlaps pieces");
+  }
+  TACO_REQUIRE(first[0] == 0 && first[P] == N, "wave_join: first[0]=%d, first[P]=%d: they must be 0 and N=%d", first[0], first[P], N);
+  for (int p = 0; p < P; ++p)
+    TACO_REQUIRE(first[p] <= first[p + 1], "wave_join: first[%d]=%d is above first[%d]=%d", p, first[p], p + 1, first[p + 1]);
+  for (int i = 0; i < N; ++i) TACO_REQUIRE(gap[i] >= 0, "wave_join: gap[%d]=%d is negative", i, gap[i]);
+  const int ntile = wj_tiles(Lj);
+  TACO_REQUIRE((int64_t)P * ntile <= 0x7fffffff, "wave_join: P=%d prompts of %d tiles are more than one grid holds", P, ntile);
+  hipStream_t s = as_stream(stream);
+  const int64_t rpitch = wj_pitch(Lj);
+  float* rows = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
+  float* tmax = rows + (int64_t)P * rpitch;
+  int32_t* first_d = reinterpret_cast<int32_t*>(tmax + (int64_t)P * ntile);
+  int32_t* gap_d = first_d + P + 1;
+  TACO_TRY(taco_upload_async(first_d, first, ((size_t)P + 1) * sizeof(int32_t), s, "wave_join: first upload"));
+  TACO_TRY(taco_upload_async(gap_d, gap, (size_t)N * sizeof(int32_t), s, "wave_join: gap upload"));
+  float* dst = out ? out : rows;
+  const int64_t dst_pitch = out ? (int64_t)Lj : rpitch;
+  const int tiles = pcm ? ntile : 1;
+  TACO_KLAUNCH(wj_offsets_kernel, dim3(P), dim3(WJ_T), 0, s, bounds, first_d, gap_d, offsets, total, L, Lj);
+  TACO_KLAUNCH(wj_emit_kernel, dim3((unsigned)((int64_t)P * ntile)), dim3(WJ_T), 0, s, pieces, pitch, bounds, first_d, offsets, fade,
+               dst, dst_pitch, tmax, ntile, L, Lj);
+  TACO_KLAUNCH(wj_pcm_kernel, dim3((unsigned)((int64_t)P * tiles)), dim3(WJ_T), 0, s, dst, dst_pitch, tmax, ntile, tiles, peak, pcm, Lj);
+  TACO_LAUNCH_CHECK("wave_join");
   return TACO_OK;
 }

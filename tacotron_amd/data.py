@@ -312,3 +312,41 @@ def load_prompts(prompts, ivocab, batch_size=32):
     for i in range(0, len(prompts), batch_size):
         yield {'text': torch.from_numpy(text[i:i + batch_size].copy()),
                'text_length': torch.from_numpy(np.minimum(text_length[i:i + batch_size], MAX_TEXT_LEN))}
+
+
+# ---- long prompts: split on the host where a speaker would pause (test.py --long; joined on the device by taco_wave_join) ----------
+END, SENTENCE, CLAUSE, WORD, HARD = range(5)   # how a piece ends: the prompt's end, '.?!', ',;:', a word boundary, mid-word
+KIND_NAMES = ('END', 'SENTENCE', 'CLAUSE', 'WORD', 'HARD')
+
+
+def split_prompt(line, max_chars=MAX_TEXT_LEN):
+    """One raw line -> [(piece_line, kind)], every piece_line a line load_prompts takes: at most max_chars characters and a newline.
+    A line whose stripped text has <= max_chars characters comes back untouched as [(line, END)].  Otherwise, while more than
+    max_chars characters remain, the text is cut after k characters, 1 <= k <= max_chars, in front of a space that follows a
+    non-space: at the last such k behind one of '.?!' (SENTENCE), else the last behind one of ',;:' (CLAUSE), else the last one
+    (WORD), else at k = max_chars (HARD: a word longer than max_chars).  The piece is text[:k] + '\\n' -- the newline keeps
+    load_prompts' `text_length = len(raw line)` the same for a piece as for a short prompt that ends its line -- and the rest goes on
+    without its leading spaces; the last piece has kind END."""
+    max_chars = int(max_chars)
+    if max_chars < 1:
+        raise ValueError('split_prompt: max_chars must be >= 1, got %r' % (max_chars,))
+    text = line.strip()
+    if len(text) <= max_chars:
+        return [(line, END)]
+    pieces = []
+    while len(text) > max_chars:
+        cuts = [k for k in range(1, max_chars + 1) if text[k] == ' ' and text[k - 1] != ' ']
+        sentence = [k for k in cuts if text[k - 1] in '.?!']
+        clause = [k for k in cuts if text[k - 1] in ',;:']
+        if sentence:
+            k, kind = sentence[-1], SENTENCE
+        elif clause:
+            k, kind = clause[-1], CLAUSE
+        elif cuts:
+            k, kind = cuts[-1], WORD
+        else:
+            k, kind = max_chars, HARD
+        pieces.append((text[:k] + '\n', kind))
+        text = text[k:].lstrip()
+    pieces.append((text + '\n', END))
+    return pieces

@@ -14,7 +14,11 @@ With `momentum` (opt-in) the rounds are those of the fast Griffin-Lim algorithm 
 per-round spectral convergence next to the waveform.
 
 `finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
-front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16."""
+front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16.
+
+`join_waveform(pieces, bounds, first, kinds)` (opt-in) puts the finished pieces of long prompts together on the device (taco_wave_join):
+a pause after each piece by the kind of cut that ended it (data.split_prompt), a short linear ramp at every interior edge, one fp32 /
+PCM16 row per prompt."""
 from __future__ import annotations
 
 import math
@@ -22,6 +26,9 @@ import math
 import torch
 
 from . import lib
+from .data import CLAUSE, SENTENCE, WORD
+
+SR = 16000   # test.py:11
 
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
@@ -75,3 +82,28 @@ def finish_waveform(wave, lengths=None, r=1, deemphasis=0.97, trim_top_db=0.0, w
     samples = None if lengths is None else finish_samples(lengths, r, wave.shape[1])
     return lib.wave_finish(wave, samples, deemphasis=deemphasis, trim_top_db=trim_top_db, want_out=want_out, want_pcm=want_pcm, out=out,
                            pcm=pcm, bounds=bounds, peak=peak, work=work)
+
+
+def join_samples(ms, sr=SR):
+    """milliseconds -> samples at `sr`, rounded to the nearest sample; ValueError below 0 or NaN"""
+    ms = float(ms)
+    if not ms >= 0.0 or math.isinf(ms):
+        raise ValueError('join_waveform: a duration must be a finite number of milliseconds >= 0, got %r' % (ms,))
+    return int(round(ms * sr / 1000.0))
+
+
+def join_gaps(kinds, pause_ms=(300.0, 150.0, 0.0), sr=SR):
+    """the samples of silence behind each piece from the kind of cut that ended it: pause_ms = (SENTENCE, CLAUSE, WORD) milliseconds;
+    a HARD cut (inside a word) and the END of a prompt get none"""
+    if len(pause_ms) != 3:
+        raise ValueError('join_waveform: pause_ms must be (SENTENCE, CLAUSE, WORD) milliseconds, got %r' % (pause_ms,))
+    table = {SENTENCE: join_samples(pause_ms[0], sr), CLAUSE: join_samples(pause_ms[1], sr), WORD: join_samples(pause_ms[2], sr)}
+    return [table.get(int(k), 0) for k in kinds]
+
+
+def join_waveform(pieces, bounds, first, kinds, pause_ms=(300.0, 150.0, 0.0), fade_ms=5.0, **kw):
+    """pieces (N, L) and bounds (N, 2) as finish_waveform returns them (out, bounds), first (P + 1) host integers, kinds (N) the
+    kinds of data.split_prompt -> (out, pcm, offsets, total, peak) of lib.wave_join, with gap = join_gaps(kinds, pause_ms) and a ramp of
+    fade_ms milliseconds at every interior edge.  The defaults (300 / 150 / 0 ms pauses, 5 ms ramps) are choices, not tuned by ear.
+    Keywords go to lib.wave_join (Lj, want_out, want_pcm and the caller's own buffers)."""
+    return lib.wave_join(pieces, bounds, first, join_gaps(kinds, pause_ms), fade=join_samples(fade_ms), **kw)

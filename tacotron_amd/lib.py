@@ -118,6 +118,9 @@ EXPORTS = {
     'taco_griffinlim_fast': (C.c_int, [_P, _P, C.c_uint64, _P, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     'taco_wave_finish_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_wave_finish': (C.c_int, [_P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'taco_wave_join_workspace_bytes': (C.c_int64, [_I, _I, _I]),
+    'taco_wave_join': (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
+                                 _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_wave_resample': (C.c_int, [_P, C.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
@@ -570,6 +573,102 @@ def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=T
     _check(_lib.taco_wave_finish(ptr(wave), ptr(samples), deemphasis, trim_top_db, ptr(out), ptr(pcm), ptr(bounds), ptr(peak),
                                  ptr(work), B, L, stream_ptr()), 'taco_wave_finish')
     return out, pcm, bounds, peak
+
+
+def wave_join_workspace_bytes(N, P, Lj) -> int:
+    return _size('taco_wave_join_workspace_bytes', N, P, Lj)
+
+
+def _host_int32(x, n, what):
+    """a host sequence of n integers that fit int32 -> a list of ints, or ValueError"""
+    if torch.is_tensor(x):
+        if x.device.type != 'cpu' or x.dtype.is_floating_point or x.dtype == torch.bool:
+            raise ValueError('%s must be integers in host memory, got a %s tensor on %s' % (what, x.dtype, x.device))
+        x = x.tolist()
+    try:
+        x = list(x)
+    except TypeError:
+        raise ValueError('%s must be a sequence of %d integers, got %r' % (what, n, x)) from None
+    if len(x) != n:
+        raise ValueError('%s must hold %d integers, got %d' % (what, n, len(x)))
+    for v in x:
+        try:
+            ok = not isinstance(v, bool) and int(v) == v and -(1 << 31) <= int(v) < (1 << 31)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('%s must hold integers that fit int32, got %r' % (what, v))
+    return [int(v) for v in x]
+
+
+def wave_join(pieces, bounds, first, gap, fade=0, Lj=None, want_out=True, want_pcm=True, out=None, pcm=None, offsets=None, total=None,
+              peak=None, work=None):
+    """Joins the finished pieces of long prompts (include/taco_hip.h taco_wave_join): pieces (N, L) fp32 on the device -- the `out` of
+    wave_finish, or rows `pitch` >= L floats apart (a view with stride (pitch, 1)) -- and bounds (N, 2) int32 on the device, the
+    `bounds` of wave_finish -> (out (P, Lj) fp32 or None, pcm (P, Lj) int16 or None, offsets (N) int32, total (P) int32, peak (P)
+    fp32).  first: P + 1 host integers, the pieces of prompt p are rows first[p] .. first[p+1] - 1; gap: N host integers >= 0, the
+    samples of silence behind each piece (ignored behind a prompt's last one); fade >= 0: samples of the linear ramp at every interior
+    edge.  Prompt p's row holds its pieces at offsets[i], total[p] samples in all, zeros behind; pcm is scaled by the prompt's peak.
+    Lj: the row length; default: the worst case max_p (K_p L + the prompt's gaps) rounded up to a multiple of 8, with which nothing is
+    ever cut and the host needs no length from the device.  out / pcm / offsets / total / peak / work: the caller's own buffers (work:
+    uint8, wave_join_workspace_bytes(N, P, Lj) bytes); default: fresh ones.  An out / pcm buffer implies want_out / want_pcm."""
+    who = 'wave_join'
+    if not torch.is_tensor(pieces) or pieces.dim() != 2 or pieces.dtype != torch.float32 or pieces.shape[0] < 1 or pieces.shape[1] < 1:
+        raise ValueError('%s: pieces must be a float32 tensor of shape (N, L), got %s %s'
+                         % (who, getattr(pieces, 'dtype', type(pieces)), tuple(getattr(pieces, 'shape', ()))))
+    N, L = pieces.shape
+    dev = pieces.device
+    if L > 1 and pieces.stride(1) != 1:
+        raise ValueError('%s: the samples of a piece must be contiguous, got strides %s' % (who, tuple(pieces.stride())))
+    pitch = pieces.stride(0) if N > 1 else max(pieces.stride(0), L)
+    if pitch < L:
+        raise ValueError('%s: the rows of pieces are %d floats apart, fewer than L = %d' % (who, pitch, L))
+    if (not torch.is_tensor(bounds) or tuple(bounds.shape) != (N, 2) or bounds.dtype != torch.int32 or bounds.device != dev
+            or not bounds.is_contiguous()):
+        raise ValueError('%s: bounds must be a contiguous int32 tensor of shape (%d, 2) on %s' % (who, N, dev))
+    try:
+        P = len(first) - 1
+    except TypeError:
+        raise ValueError('%s: first must be a sequence of P + 1 integers' % who) from None
+    if P < 1:
+        raise ValueError('%s: first must hold P + 1 >= 2 integers, got %d' % (who, P + 1))
+    first = _host_int32(first, P + 1, who + ': first')
+    gap = _host_int32(gap, N, who + ': gap')
+    if first[0] != 0 or first[P] != N:
+        raise ValueError('%s: first must start at 0 and end at N = %d, got %d and %d' % (who, N, first[0], first[P]))
+    if any(first[p] > first[p + 1] for p in range(P)):
+        raise ValueError('%s: first must not decrease, got %r' % (who, first))
+    if min(gap) < 0:
+        raise ValueError('%s: gap must be >= 0, got %d' % (who, min(gap)))
+    if isinstance(fade, bool) or int(fade) != fade or int(fade) < 0:
+        raise ValueError('%s: fade must be an integer >= 0, got %r' % (who, fade))
+    fade = int(fade)
+    want_out = bool(want_out) or out is not None
+    want_pcm = bool(want_pcm) or pcm is not None
+    if not (want_out or want_pcm):
+        raise ValueError('%s: at least one of out and pcm is needed' % who)
+    if Lj is None:
+        worst = max((first[p + 1] - first[p]) * L + sum(gap[first[p]:first[p + 1] - 1]) for p in range(P))
+        Lj = max(8, -(-worst // 8) * 8)
+    if isinstance(Lj, bool) or int(Lj) != Lj or not 1 <= int(Lj) < (1 << 31):
+        raise ValueError('%s: Lj must be an integer in [1, 2^31), got %r' % (who, Lj))
+    Lj = int(Lj)
+    out = _own_or_given(out, (P, Lj), torch.float32, dev, who + ': out') if want_out else None
+    if out is not None:
+        p0, o0 = pieces.data_ptr(), out.data_ptr()
+        if o0 < p0 + ((N - 1) * pitch + L) * 4 and p0 < o0 + P * Lj * 4:
+            raise ValueError('%s: out may not overlap pieces' % who)
+    pcm = _own_or_given(pcm, (P, Lj), torch.int16, dev, who + ': pcm') if want_pcm else None
+    offsets = _own_or_given(offsets, (N,), torch.int32, dev, who + ': offsets')
+    total = _own_or_given(total, (P,), torch.int32, dev, who + ': total')
+    peak = _own_or_given(peak, (P,), torch.float32, dev, who + ': peak')
+    work = _own_or_given(work, (wave_join_workspace_bytes(N, P, Lj),), torch.uint8, dev, who + ': work')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: pieces must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_wave_join(C.c_void_p(pieces.data_ptr()), pitch, ptr(bounds), (C.c_int32 * (P + 1))(*first), (C.c_int32 * N)(*gap),
+                               fade, ptr(out), ptr(pcm), ptr(offsets), ptr(total), ptr(peak), ptr(work), N, P, L, Lj, stream_ptr()),
+           'taco_wave_join')
+    return out, pcm, offsets, total, peak
 
 
 def audio_features_workspace_bytes(B, L) -> int:

@@ -13,7 +13,14 @@ printed.  --gl-iters N: the number of rounds (default 50, the reference's).  Bot
 --deemphasis [A] / --trim-db DB (opt-in, not in the reference): the waveform is finished on the device (griffinlim.finish_waveform,
 taco_wave_finish): de-emphasis with A in [0, 1) (0.97 when A is left out: the inverse of the training features' pre-emphasis) and / or
 the front end's energy trim at DB > 0 decibels below the loudest frame.  prompt_NNN.wav is then written from the device's int16
-samples and holds e - s of them; prompt_NNN_trim.npy holds [s, e].  They combine with every option above."""
+samples and holds e - s of them; prompt_NNN_trim.npy holds [s, e].  They combine with every option above.
+--long (opt-in, with --stop; not in the reference): a line of more than 140 characters is cut where a speaker would pause
+(data.split_prompt), its pieces run as rows of ordinary batches, each ending where its attention ends, every piece is finished on the
+device (de-emphasis and trim stay off unless asked for) and the pieces of a prompt are joined there (griffinlim.join_waveform,
+taco_wave_join): --pause-ms SENTENCE,CLAUSE,WORD of silence behind a piece by the kind of its cut, a linear ramp of --fade-ms at every
+interior edge, PCM16 by the prompt's peak.  One prompt_NNN.wav per prompt; prompt_NNN_pieces.npy holds (offset, length, gap, kind) per
+piece and the per-piece arrays are prompt_NNN_kMM_{spec,align,len,trim}.npy.  A prompt of one piece writes the files it writes without
+--long.  Without --long a line of more than 140 characters is refused as before (ValueError from load_prompts)."""
 from __future__ import annotations
 
 import argparse
@@ -26,13 +33,16 @@ import numpy as np
 import torch
 
 from .config import Config
-from .data import load_prompts
-from .griffinlim import finish_waveform, invert_spectrogram
+from .data import KIND_NAMES, load_prompts, split_prompt
+from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform
 from .model import Tacotron
 from .params import ParamBuffer
 from . import lib
 
 SR = 16000   # test.py:11
+PAUSE_MS = (300.0, 150.0, 0.0)   # --long: silence behind a SENTENCE / CLAUSE / WORD cut; choices, not tuned by anyone's ear
+FADE_MS = 5.0                    # --long: the ramp at every interior edge; likewise
+JOIN_GROUP = 256                 # --long: pieces per lib.wave_join call (a group ends at the first prompt boundary at or past it)
 
 
 def write_wav(path, samples, sr=SR):
@@ -60,8 +70,26 @@ def write_wav_pcm(path, int16_samples, sr=SR):
         f.writeframes(x.astype('<i2', copy=False).tobytes())
 
 
-def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None):
+def long_options(long):
+    """`long` of test(): None / False (off), True (the defaults) or a dict with 'pause_ms' (SENTENCE, CLAUSE, WORD) and / or 'fade_ms'
+    -> None or (pause_ms, fade_ms); ValueError"""
+    if long is None or long is False:
+        return None
+    opt = {} if long is True else dict(long)
+    unknown = set(opt) - {'pause_ms', 'fade_ms'}
+    if unknown:
+        raise ValueError('long (--long): unknown settings %s' % sorted(unknown))
+    pause_ms = tuple(float(x) for x in opt.get('pause_ms', PAUSE_MS))
+    fade_ms = float(opt.get('fade_ms', FADE_MS))
+    join_gaps([], pause_ms)   # (their ranges)
+    join_samples(fade_ms)
+    return pause_ms, fade_ms
+
+
+def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given); ValueError."""
+    if long_options(long) is not None and not stop:
+        raise ValueError('long (--long) needs a stop rule (--stop): without one every piece carries max_decode_iter steps')
     if vocode_lengths and not stop:
         raise ValueError('vocode_lengths (--vocode-lengths) needs a stop rule (--stop): the lengths come from taco_infer_stop')
     if gl_momentum is not None and not 0.0 <= float(gl_momentum) < 1.0:
@@ -74,10 +102,11 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
         raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (trim_db,))
 
 
-def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None):
+def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
-    spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300)."""
-    path = os.path.join(out_dir, 'prompt_%03d' % n)
+    spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
+    piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav."""
+    path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
         spec, align = spec[:frames], align[:len_b]
@@ -90,13 +119,14 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         write_wav(path + '.wav', wav)
     if pcm is not None:   # (finished on the device: already cut to the row's own samples, then trimmed to [s, e))
         write_wav_pcm(path + '.wav', pcm[:int(trim[1]) - int(trim[0])])
+    if trim is not None:
         np.save(path + '_trim.npy', trim)
     if conv is not None:
         np.save(path + '_conv.npy', conv)
 
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None, deemphasis=None, trim_db=None):
+         gl_momentum=None, deemphasis=None, trim_db=None, long=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -112,9 +142,19 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     values of the prompt (over the frames the vocoder ran on: the prompt's own with `vocode_lengths`, else the full length).
     `deemphasis` (None, or a in [0, 1)) / `trim_db` (None, or decibels > 0): with either, the batch's waveform is finished on the
     device (finish_waveform; with `stop`, each row over the samples of its own len_b r frames) and prompt_NNN.wav is written from
-    the device's int16 samples: e - s of them, [s, e] in prompt_NNN_trim.npy.  The other files are unchanged."""
-    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db)
-    finish = deemphasis is not None or trim_db is not None
+    the device's int16 samples: e - s of them, [s, e] in prompt_NNN_trim.npy.  The other files are unchanged.
+    `long` (needs `stop` and `vocode`): None, True, or a dict with 'pause_ms' (SENTENCE, CLAUSE, WORD; default 300, 150, 0) and / or
+    'fade_ms' (default 5) -- choices, not tuned by ear.  Every prompt is cut into pieces of at most 140 characters (data.split_prompt),
+    the pieces run in order as rows of batches of <= 32, every batch is finished on the device into its rows of one buffer (without
+    `deemphasis` / `trim_db`: bounds [0, n_b)), and the pieces of each prompt are joined there (join_waveform), <= 256 pieces and the
+    rest of the prompt they end in per call.  prompt_NNN.wav holds the prompt's total samples, prompt_NNN_pieces.npy (K, 4) int32
+    offset, length, gap, kind per piece, prompt_NNN_kMM_*.npy the arrays of piece MM; a prompt of one piece writes the files and the
+    contents it writes without `long`."""
+    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long)
+    long = long_options(long)
+    if long is not None and not vocode:
+        raise ValueError('long (--long) joins waveforms: it needs vocode')
+    finish = deemphasis is not None or trim_db is not None or long is not None
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
         with open(meta_path, 'rb') as f:
@@ -127,21 +167,23 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     if ckpt is not None:
         config.r, config.vocab_size = ckpt.get('shape', (config.r, config.vocab_size))
         config.num_speakers = int(ckpt.get('num_speakers', 1))
-    params = None
+    state = {'params': None}
     models = {}   # batch size -> Tacotron
     os.makedirs(out_dir, exist_ok=True)
-    n = 0
-    for batch in load_prompts(prompts, ivocab):
+
+    def synthesise(batch, n, out_rows=None, bounds_rows=None):
+        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths), host arrays or None.  out_rows /
+        bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made"""
         Bn = batch['text'].shape[0]
         if config.num_speakers > 1:
             batch['speaker'] = torch.full((Bn,), int(speaker), dtype=torch.int32)
-        if params is None:
+        if state['params'] is None:
             shape = lib.make_shape(Bn, batch['text'].shape[1], config.max_decode_iter, config.r, config.vocab_size,
                                    config.num_speakers)
-            params = ParamBuffer(shape, 'cuda').init_(0)
+            state['params'] = ParamBuffer(shape, 'cuda').init_(0)
         model = models.get(Bn)
         if model is None:
-            model = models[Bn] = Tacotron(config, batch, train=False, params=params)
+            model = models[Bn] = Tacotron(config, batch, train=False, params=state['params'])
             if ckpt is not None:
                 model.load_state_dict(ckpt)
         else:
@@ -164,18 +206,82 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             if finish:   # (the fp32 waveform stays on the device)
                 _, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
                                                   deemphasis=0.0 if deemphasis is None else deemphasis,
-                                                  trim_top_db=0.0 if trim_db is None else trim_db, want_out=False)
-                pcm, trim, wav = pcm.cpu().numpy(), trim.cpu().numpy(), None
+                                                  trim_top_db=0.0 if trim_db is None else trim_db, want_out=out_rows is not None,
+                                                  want_pcm=out_rows is None, out=out_rows, bounds=bounds_rows)
+                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
             else:
                 wav = wav.cpu().numpy()
-        spec, al = spec.cpu().numpy(), al.cpu().numpy()
         lengths = model.lengths.cpu().numpy() if stop is not None else None
+        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths
+
+    n = 0
+    if long is not None:
+        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long)
+        print('wrote %d samples to %s' % (n, out_dir))
+        return n
+    for batch in load_prompts(prompts, ivocab):
+        Bn = batch['text'].shape[0]
+        spec, al, wav, conv, pcm, trim, lengths = synthesise(batch, n)
         for i in range(Bn):
             wi, len_b, pi, ti, ci = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv))
             write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci)
             n += 1
     print('wrote %d samples to %s' % (n, out_dir))
     return n
+
+
+def _test_long(config, prompts, ivocab, out_dir, synthesise, long):
+    """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write"""
+    pause_ms, fade_ms = long
+    split = [split_prompt(p) for p in prompts]
+    groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
+    held = 0
+    for p, pieces in enumerate(split):
+        held += len(pieces)
+        if held >= JOIN_GROUP or p == len(split) - 1:
+            groups.append((start, p + 1))
+            start, held = p + 1, 0
+    L = 300 * ((config.max_decode_iter // 4) * 4 * config.r - 1)   # samples per row of invert_spectrogram
+    row = 0   # index of the next piece over the whole run (the Griffin-Lim seed of its batch, as the prompt index is without `long`)
+    for lo, hi in groups:
+        lines = [line for pieces in split[lo:hi] for line, _ in pieces]
+        kinds = [kind for pieces in split[lo:hi] for _, kind in pieces]
+        first = np.concatenate([[0], np.cumsum([len(pieces) for pieces in split[lo:hi]])]).astype(np.int64).tolist()
+        N = len(lines)
+        rows = torch.empty(N, L, dtype=torch.float32, device='cuda')
+        bounds = torch.empty(N, 2, dtype=torch.int32, device='cuda')
+        arrays = []   # per piece: (spec, align, len_b, trim, conv)
+        at = 0
+        for batch in load_prompts(lines, ivocab):
+            Bn = batch['text'].shape[0]
+            spec, al, _, conv, _, trim, lengths = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i]) for i in range(Bn)]
+            at += Bn
+        gap = join_gaps(kinds, pause_ms)
+        _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
+        pcm, total, offsets = pcm.cpu().numpy(), total.cpu().numpy(), offsets.cpu().numpy()   # (the one copy back of the group)
+        for p in range(lo, hi):
+            a, b = first[p - lo], first[p - lo + 1]
+            path = os.path.join(out_dir, 'prompt_%03d' % p)
+            for k in range(a, b):
+                spec, al, len_b, trim, conv = arrays[k]
+                write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a)
+            write_wav_pcm(path + '.wav', pcm[p - lo, :int(total[p - lo])])
+            if b - a > 1:
+                table = [[int(offsets[k]), min(L, max(0, int(arrays[k][3][1]) - int(arrays[k][3][0]))), 0 if k == b - 1 else gap[k],
+                          kinds[k]] for k in range(a, b)]
+                np.save(path + '_pieces.npy', np.array(table, dtype=np.int32))
+                print('prompt %d: %d pieces (%s), %d samples' % (p, b - a, ' '.join(KIND_NAMES[kinds[k]] for k in range(a, b)),
+                                                                 int(total[p - lo])))
+        row += N
+    return len(split)
+
+
+def _pause_ms(text):
+    parts = text.split(',')
+    if len(parts) != 3:
+        raise argparse.ArgumentTypeError('expected SENTENCE,CLAUSE,WORD, got %r' % text)
+    return tuple(float(x) for x in parts)
 
 
 def parse_args(argv=None):
@@ -197,9 +303,18 @@ def parse_args(argv=None):
                     help='undo the training features\' pre-emphasis on the device: y[n] = x[n] + A y[n-1], A in [0, 1) (default 0.97)')
     ap.add_argument('--trim-db', type=float, default=None, metavar='DB',
                     help='cut leading / trailing silence more than DB > 0 decibels below the loudest frame; writes prompt_NNN_trim.npy')
+    ap.add_argument('--long', action='store_true',
+                    help='--stop: cut a line of more than 140 characters where a speaker would pause, synthesise the pieces and join '
+                         'them on the device into one prompt_NNN.wav (not in the reference)')
+    ap.add_argument('--pause-ms', type=_pause_ms, default=PAUSE_MS, metavar='SENTENCE,CLAUSE,WORD',
+                    help='--long: milliseconds of silence behind a piece cut after .?! / after ,;: / at a word boundary (default '
+                         '300,150,0: choices of the author, not tuned by ear; a cut inside a word gets none)')
+    ap.add_argument('--fade-ms', type=float, default=FADE_MS,
+                    help='--long: milliseconds of linear ramp at every interior edge of a piece (default 5: a choice, not tuned by ear)')
     a = ap.parse_args(argv)
+    a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
     try:
-        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db)
+        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -214,4 +329,4 @@ if __name__ == '__main__':
     print('Building Tacotron')
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
-         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db)
+         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long)
