@@ -89,6 +89,16 @@ __device__ __forceinline__ float wave_max(float v) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
+// Counter-based random bits (the Bernoulli masks, the device phases of taco_griffinlim_rows): draw i of a seed is the output
+// function of the splitmix64 generator on seed * 0xD1342543DE82EF95 + i, in 64-bit wrap-around arithmetic
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint64_t counter_hash(uint64_t seed, uint64_t i) { return splitmix64(seed * 0xD1342543DE82EF95ull + i); }
+
 // Workgroup barrier for LDS-only communication: waits for this wave's LDS traffic (lgkmcnt) but NOT for its outstanding
 // global loads/stores (vmcnt), unlike __syncthreads(), so prefetch loads and stash stores stay in flight across it.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -16,6 +16,7 @@ inline int grid_for(int64_t n_items, int per_block = kThreads, int cap = 4096) {
   return (int)g;
 }
 
+// any block size, the wave sums added in sequence behind a leading barrier.  NOT vocoder.hip's block_sum4 (four waves, pairwise).
 __device__ __forceinline__ float block_sum(float v, float* red /* >= 4 floats LDS */) {
   v = wave_sum(v);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -644,18 +645,11 @@ __global__ __launch_bounds__(256) void corpus_batch_kernel(const T* __restrict__
   }
 }
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 __global__ void bernoulli_kernel(uint8_t* __restrict__ out, int64_t n, uint32_t thresh, uint64_t seed) {
   // each thread produces 8 bytes from one 64-bit hash: 8-bit resolution per draw would be too coarse, so draw
   // one hash per byte pair (2 x 32-bit lanes).
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i * 2 < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint64_t h = splitmix64(seed * 0xD1342543DE82EF95ull + (uint64_t)i);
+    const uint64_t h = counter_hash(seed, (uint64_t)i);
     const uint32_t lo = (uint32_t)h, hi = (uint32_t)(h >> 32);
     out[i * 2] = lo < thresh ? 1 : 0;
     if (i * 2 + 1 < n) out[i * 2 + 1] = hi < thresh ? 1 : 0;

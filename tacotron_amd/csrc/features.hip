@@ -1,5 +1,5 @@
 // features.hip -- training features from waveforms on the GPU (audio.process_audio, audio.py:38-65; the producer half of
-// preprocess.py).  The reference's constants are compiled in, as in vocoder.hip: n_fft 2048, win_length 1200 (periodic Hann,
+// preprocess.py).  The reference's constants are compiled in (stft.h, with vocoder.hip): n_fft 2048, win_length 1200 (periodic Hann,
 // zero-padded to 2048 around its centre), hop 300, pre-emphasis 0.97, log(|.| + 1e-8).  Per utterance, in the reference's order:
 //
 //   1. trim     librosa.effects.trim(wave) with its defaults, in the librosa 0.6 form: the mean square of frames of 2048
@@ -28,34 +28,17 @@
 
 #include <algorithm>
 
-#include "common.h"
 #include "kernels.h"
+#include "stft.h"
 
 namespace {
 
-constexpr int NFFT = 2048, NBIN = 1025, WIN = 1200, HOP = 300, WOFF = (NFFT - WIN) / 2;   // window occupies [424, 1624)
 constexpr int NH = NFFT / 2;                  // 1024-point complex FFT of the even / odd samples
 constexpr int NMEL = 80;
-constexpr int FT = 256;                       // fb_frames block
-constexpr int TT = 512;                       // fb_trim block
-constexpr int TRIM_FRAME = 2048, TRIM_HOP = 512;
+constexpr int TT = 512;                       // fb_trim block (fb_frames runs stft.h's FT threads)
 constexpr float PREEMPH = 0.97f, LOG_EPS = 1e-8f;
 
-// LDS index with one pad word per 32: the radix-2 stages' stride-2 (first stage) and stride-2^s accesses spread over the 32
-// banks of ds_read_b32 / ds_write_b32 (cdna_hip_programming.md Guideline 4)
-__device__ __forceinline__ int pd(int i) { return i + (i >> 5); }
-constexpr int NH_PAD = NH + NH / 32;
-
-__device__ __forceinline__ int bitrev10(int x) { return (int)(__brev((unsigned)x) >> 22); }
-
-// numpy.pad(mode='reflect') index for any pad width: period 2 (n - 1)
-__device__ __forceinline__ int64_t reflect_any(int64_t p, int64_t n) {
-  if (n <= 1) return 0;
-  const int64_t per = 2 * (n - 1);
-  int64_t q = p % per;
-  if (q < 0) q += per;
-  return q >= n ? per - q : q;
-}
+constexpr int NH_PAD = NH + NH / 32;          // zr / zi carry one pad word per 32 (cdna_hip_programming.md Guideline 4)
 
 // nonzero run [lo, hi) of every filterbank row: one wave per row
 __global__ __launch_bounds__(256) void fb_ranges_kernel(const float* __restrict__ basis, int* __restrict__ rng) {
@@ -91,12 +74,7 @@ __global__ __launch_bounds__(TT) void fb_trim_kernel(const float* __restrict__ w
   float* ms = ms_all + (int64_t)b * ms_stride;
   float mx = 0.f;
   for (int t = w; t < nt; t += NW) {
-    float acc = 0.f;
-    for (int i = lane; i < TRIM_FRAME; i += 64) {
-      const float v = x[reflect_any((int64_t)t * TRIM_HOP + i - TRIM_FRAME / 2, n)];
-      acc = fmaf(v, v, acc);
-    }
-    const float m = wave_sum(acc) * (1.0f / TRIM_FRAME);
+    const float m = trim_frame_ms(x, n, t, lane);
     if (lane == 0) ms[t] = m;   // read back below by this same wave only
     mx = fmaxf(mx, m);
   }
@@ -104,11 +82,11 @@ __global__ __launch_bounds__(TT) void fb_trim_kernel(const float* __restrict__ w
   __syncthreads();
   mx = red_max[0];
   for (int i = 1; i < NW; ++i) mx = fmaxf(mx, red_max[i]);
-  const float ref_db = 10.f * log10f(fmaxf(1e-10f, mx));
+  const float ref_db = trim_db(mx);
   int lo = 0x7fffffff, hi = -1;
   if (lane == 0)
     for (int t = w; t < nt; t += NW)
-      if (10.f * log10f(fmaxf(1e-10f, ms[t])) - ref_db > -60.f) {
+      if (trim_pass(ms[t], ref_db, 60.f)) {
         lo = min(lo, t);
         hi = max(hi, t);
       }
@@ -122,11 +100,8 @@ __global__ __launch_bounds__(TT) void fb_trim_kernel(const float* __restrict__ w
       lo = min(lo, red_lo[i]);
       hi = max(hi, red_hi[i]);
     }
-    int start = 0, end = 0;   // (no non-silent frame: only a NaN wave gets here; librosa returns the empty slice)
-    if (hi >= 0) {
-      start = lo * TRIM_HOP;
-      end = min(n, (hi + 1) * TRIM_HOP);
-    }
+    int start, end;
+    trim_bounds(lo, hi, n, start, end);
     bounds[2 * b] = start;
     bounds[2 * b + 1] = end;
     kept[b] = (end - start <= max_len) ? 1 : 0;
@@ -154,12 +129,8 @@ __global__ __launch_bounds__(FT) void fb_frames_kernel(FrameArgs a) {
   __shared__ float xr[NBIN], xi[NBIN];       // the frame's 1025 complex bins
   __shared__ float twr[NH], twi[NH];         // e^{-2 pi i k / 2048}, k < 1024
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int k = tid; k < NH; k += FT) {
-    float s, c;
-    sincospif(-2.0f * (float)k / (float)NFFT, &s, &c);
-    twr[k] = c;
-    twi[k] = s;
-  }
+  constexpr LdsPad32 pd;
+  make_twiddles(twr, twi);
   // this thread's input samples: j = 2n (real part) and 2n + 1 (imaginary part) for n = tid + FT u; their window values
   float win[2 * (NH / FT)];
 #pragma unroll
@@ -167,9 +138,8 @@ __global__ __launch_bounds__(FT) void fb_frames_kernel(FrameArgs a) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int j = 2 * (tid + FT * u) + h;
-      float s, c;
-      sincospif(2.0f * (float)(j - WOFF) / (float)WIN, &s, &c);
-      win[2 * u + h] = (j >= WOFF && j < WOFF + WIN) ? 0.5f - 0.5f * c : 0.f;
+      const float hw = hann(j - WOFF);   // (evaluated for every j: a select, no divergent branch)
+      win[2 * u + h] = (j >= WOFF && j < WOFF + WIN) ? hw : 0.f;
     }
   const int64_t total = (int64_t)a.B * a.Fk;
   const int rc = 4 * a.r;
@@ -206,27 +176,11 @@ __global__ __launch_bounds__(FT) void fb_frames_kernel(FrameArgs a) {
         }
         v[h] = e * win[2 * u + h];
       }
-      const int p = pd(bitrev10(n));
+      const int p = pd(bitrev<10>(n));
       zr[p] = v[0];
       zi[p] = v[1];
     }
-#pragma unroll 1
-    for (int s = 0; s < 10; ++s) {
-      const int half = 1 << s;
-      __syncthreads();
-      for (int t = tid; t < NH / 2; t += FT) {
-        const int pos = t & (half - 1);
-        const int i0 = ((t >> s) << (s + 1)) + pos, i1 = i0 + half;
-        const int k = pos << (10 - s);   // W_1024^(pos 512 / half) = W_2048^(pos 1024 / half)
-        const float wr = twr[k], wi = twi[k];
-        const int p0 = pd(i0), p1 = pd(i1);
-        const float ar = zr[p1], ai = zi[p1];
-        const float tr = ar * wr - ai * wi, ti = ar * wi + ai * wr;
-        const float ur = zr[p0], ui = zi[p0];
-        zr[p0] = ur + tr; zi[p0] = ui + ti;
-        zr[p1] = ur - tr; zi[p1] = ui - ti;
-      }
-    }
+    fft_stages<10>(zr, zi, twr, twi, -1.0f, pd);
     __syncthreads();
     // Hermitian split: Z = E' + i O' (E', O' the FFTs of the even / odd samples); X[k] = E'[k] + W_2048^k O'[k]
     for (int k = tid; k < NBIN; k += FT) {

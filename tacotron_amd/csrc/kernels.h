@@ -1,7 +1,7 @@
 // kernels.h -- internal launch interface shared by the .hip translation units of libtaco_hip.so: what one unit calls in another.
 // A C-ABI entry point (include/taco_hip.h) that needs nothing from another unit is defined beside its kernels and has no
 // declaration here: all of vocoder.hip and features.hip, and the op-level and probe entry points of elementwise.hip,
-// decoder.hip and stream.hip.
+// decoder.hip and stream.hip.  Device code that features.hip and vocoder.hip share is not an interface between units either: stft.h.
 #pragma once
 #include "common.h"
 #include "stream.h"

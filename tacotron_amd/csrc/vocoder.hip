@@ -31,62 +31,21 @@
 // last: the pieces' offsets, the joined fp32 row with its edge ramps, the prompt's peak and PCM16.
 #include <algorithm>
 
-#include "common.h"
 #include "kernels.h"
+#include "stft.h"
 
 namespace {
 
-constexpr int NFFT = 2048, NBIN = 1025, WIN = 1200, HOP = 300, WOFF = (NFFT - WIN) / 2;   // window occupies [424, 1624)
-constexpr int FT = 256;
-
-__device__ __forceinline__ float hann(int i) {   // periodic Hann(1200), i in [0, 1200)
-  float s, c;
-  sincospif(2.0f * (float)i / (float)WIN, &s, &c);
-  return 0.5f - 0.5f * c;
-}
-
-// in-place 2048-point FFT of (re, im) in LDS; data must already be in bit-reversed order.  sign = -1 forward, +1 inverse
-// (unscaled).  tw[k] = e^{-2 pi i k / 2048}, k < 1024.
+// in-place 2048-point FFT of (re, im) in LDS, plain index (stft.h fft_stages); the results are visible to every thread on return
 __device__ __forceinline__ void fft2048(float* re, float* im, const float* twr, const float* twi, float sign) {
-#pragma unroll 1
-  for (int s = 0; s < 11; ++s) {
-    const int half = 1 << s;
-    __syncthreads();
-    for (int j = threadIdx.x; j < NFFT / 2; j += FT) {
-      const int pos = j & (half - 1);
-      const int i0 = ((j >> s) << (s + 1)) + pos, i1 = i0 + half;
-      const int k = pos << (10 - s);
-      const float wr = twr[k], wi = -sign * twi[k];   // twi holds sin(-2 pi k / N): forward uses it as is
-      const float xr = re[i1], xi = im[i1];
-      const float tr = xr * wr - xi * wi, ti = xr * wi + xi * wr;
-      const float ur = re[i0], ui = im[i0];
-      re[i0] = ur + tr; im[i0] = ui + ti;
-      re[i1] = ur - tr; im[i1] = ui - ti;
-    }
-  }
+  fft_stages<11>(re, im, twr, twi, sign, LdsPlain());
   __syncthreads();
-}
-__device__ __forceinline__ int bitrev11(int x) { return (int)(__brev((unsigned)x) >> 21); }
-
-__device__ __forceinline__ void make_twiddles(float* twr, float* twi) {
-  for (int k = threadIdx.x; k < NFFT / 2; k += FT) {
-    float s, c;
-    sincospif(-2.0f * (float)k / (float)NFFT, &s, &c);
-    twr[k] = c;
-    twi[k] = s;
-  }
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {   // as elementwise.hip (bernoulli_kernel)
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
 }
 
 // sum of v over the 256 threads of the workgroup in a fixed order, returned to every thread: xor butterfly inside each wave, then
-// the four wave sums through sh (4 floats of LDS nobody else touches until the next barrier)
-__device__ __forceinline__ float block_sum(float v, float* sh) {
+// the four wave sums through sh (4 floats of LDS nobody else touches until the next barrier) as (s0 + s1) + (s2 + s3).
+// NOT elementwise.hip's block_sum: that one takes any block size and adds the wave sums in sequence -- other bits.
+__device__ __forceinline__ float block_sum4(float v, float* sh) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
@@ -142,7 +101,7 @@ __global__ void gl_init_kernel(const float* __restrict__ phase, uint64_t seed, f
     if (phase) {
       sincosf(phase[j], &s, &c);
     } else {
-      const uint32_t u = (uint32_t)(splitmix64(seed * 0xD1342543DE82EF95ull + (uint64_t)j) >> 40);
+      const uint32_t u = (uint32_t)(counter_hash(seed, (uint64_t)j) >> 40);
       sincospif((float)u * (2.0f / 16777216.0f), &s, &c);
     }
     ang[i * 2] = c;
@@ -163,10 +122,10 @@ __global__ __launch_bounds__(FT) void gl_synth_kernel(const float* __restrict__ 
   for (int k = threadIdx.x; k < NBIN; k += FT) {
     const float mg = fabsf(m[(int64_t)k * F]);
     const float xr = mg * a[2 * k], xi = mg * a[2 * k + 1];
-    const int r0 = bitrev11(k);
+    const int r0 = bitrev<11>(k);
     re[r0] = xr; im[r0] = xi;
     if (k > 0 && k < NFFT / 2) {
-      const int r1 = bitrev11(NFFT - k);
+      const int r1 = bitrev<11>(NFFT - k);
       re[r1] = xr; im[r1] = -xi;
     }
   }
@@ -223,7 +182,7 @@ __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ s
       if (q >= L) q = 2 * (L - 1) - q;
       v = ola_sample(sb, wss, q + NFFT / 2, F) * hann(j - WOFF);
     }
-    const int r0 = bitrev11(j);
+    const int r0 = bitrev<11>(j);
     re[r0] = v;
     im[r0] = 0.f;
   }
@@ -259,7 +218,7 @@ __global__ __launch_bounds__(FT) void gl_anal_kernel(const float* __restrict__ s
     }
   }
   if constexpr (CONV) {   // (the twiddle table is dead after the FFT's last barrier: its first floats carry the wave sums)
-    const float tot = block_sum(dev2, twr);
+    const float tot = block_sum4(dev2, twr);
     if (threadIdx.x == 0) x.part[(int64_t)b * Fp + t] = tot;
   }
 }
@@ -276,12 +235,12 @@ __global__ __launch_bounds__(FT) void gl_magsq_kernel(const float* __restrict__ 
     const float v = m[(int64_t)k * F];
     acc += v * v;
   }
-  const float tot = block_sum(acc, sh);
+  const float tot = block_sum4(acc, sh);
   if (threadIdx.x == 0) mpart[(int64_t)b * F + t] = tot;
 }
 
 // conv[b, col] <- sqrt(sum_t part[b, t] / sum_t mpart[b, t]) over the row's F_b frames, 0 for a row without frames or magnitudes.
-// Thread j sums the frames j, j + 256, ... and block_sum the threads: the order depends on F_b alone.  first: sum mpart into
+// Thread j sums the frames j, j + 256, ... and block_sum4 the threads: the order depends on F_b alone.  first: sum mpart into
 // msq[b]; later rounds read it back.
 __global__ __launch_bounds__(FT) void gl_conv_kernel(const float* __restrict__ part, const float* __restrict__ mpart,
                                                      float* __restrict__ msq, float* __restrict__ conv, int col, int ncol, int Fp,
@@ -294,10 +253,10 @@ __global__ __launch_bounds__(FT) void gl_conv_kernel(const float* __restrict__ p
     acc += part[(int64_t)b * Fp + t];
     if (first) macc += mpart[(int64_t)b * Fp + t];
   }
-  const float num = block_sum(acc, sh);
+  const float num = block_sum4(acc, sh);
   float den;
   if (first) {
-    den = block_sum(macc, sh + 4);
+    den = block_sum4(macc, sh + 4);
     if (threadIdx.x == 0) msq[b] = den;
   } else {
     den = msq[b];
@@ -331,22 +290,12 @@ __global__ void gl_wave_kernel(const float* __restrict__ seg, const float* __res
 //   wf_emit         out / pcm shifted by the row's start
 // No workgroup waits for another one inside a launch; the order of every sum depends on the position in the row and n_b alone.
 constexpr int WF_T = 256, WF_PER = 8, WF_CHUNK = WF_T * WF_PER;
-constexpr int WF_TRIM_FRAME = 2048, WF_TRIM_HOP = 512;
 constexpr int WF_BT = 512;   // wf_bounds block
 
 __device__ __forceinline__ int wf_len(const int32_t* __restrict__ samples, int b, int L) {
   if (!samples) return L;
   const int n = samples[b];
   return n < 0 ? 0 : (n > L ? L : n);
-}
-
-// numpy.pad(mode='reflect') index for any pad width (period 2 (n - 1)); as features.hip
-__device__ __forceinline__ int wf_reflect(int64_t p, int64_t n) {
-  if (n <= 1) return 0;
-  const int64_t per = 2 * (n - 1);
-  int64_t q = p % per;
-  if (q < 0) q += per;
-  return (int)(q >= n ? per - q : q);
 }
 
 template <bool AGG>
@@ -447,19 +396,12 @@ __global__ __launch_bounds__(WF_T) void wf_ms_kernel(const float* __restrict__ y
   const int b = blockIdx.y, lane = threadIdx.x & 63;
   const int n = wf_len(samples, b, L);
   const int t = blockIdx.x * (WF_T / 64) + (threadIdx.x >> 6);
-  if (n == 0 || t >= 1 + n / WF_TRIM_HOP) return;
-  const float* y = y_all + (int64_t)b * y_pitch;
-  float acc = 0.f;
-  for (int i = lane; i < WF_TRIM_FRAME; i += 64) {
-    const int64_t p = (int64_t)t * WF_TRIM_HOP + i - WF_TRIM_FRAME / 2;
-    const float v = y[p >= 0 && p < n ? (int)p : wf_reflect(p, n)];
-    acc = fmaf(v, v, acc);
-  }
-  const float m = wave_sum(acc) * (1.0f / WF_TRIM_FRAME);
+  if (n == 0 || t >= 1 + n / TRIM_HOP) return;
+  const float m = trim_frame_ms(y_all + (int64_t)b * y_pitch, n, t, lane);
   if (lane == 0) ms_all[(int64_t)b * nms + t] = m;
 }
 
-// one workgroup per row: bounds (fb_trim_kernel's rule with -top_db in place of -60; top_db == 0: no trim) and the peak
+// one workgroup per row: bounds (stft.h's trim rule; top_db == 0: no trim) and the peak
 __global__ __launch_bounds__(WF_BT) void wf_bounds_kernel(const float* __restrict__ ms_all, int nms, const float* __restrict__ pm_all,
                                                           int npm, const int32_t* __restrict__ samples, float top_db,
                                                           int32_t* __restrict__ bounds, float* __restrict__ peak, int L) {
@@ -471,7 +413,7 @@ __global__ __launch_bounds__(WF_BT) void wf_bounds_kernel(const float* __restric
   int start = 0, end = n;
   if (top_db > 0.f && n > 0) {   // (uniform)
     const float* ms = ms_all + (int64_t)b * nms;
-    const int nt = 1 + n / WF_TRIM_HOP;
+    const int nt = 1 + n / TRIM_HOP;
     float mx = 0.f;
     for (int t = threadIdx.x; t < nt; t += WF_BT) mx = fmaxf(mx, ms[t]);
     mx = wave_max(mx);
@@ -479,10 +421,10 @@ __global__ __launch_bounds__(WF_BT) void wf_bounds_kernel(const float* __restric
     __syncthreads();
     mx = red_max[0];
     for (int i = 1; i < NW; ++i) mx = fmaxf(mx, red_max[i]);
-    const float ref_db = 10.f * log10f(fmaxf(1e-10f, mx));
+    const float ref_db = trim_db(mx);
     int lo = 0x7fffffff, hi = -1;
     for (int t = threadIdx.x; t < nt; t += WF_BT)
-      if (10.f * log10f(fmaxf(1e-10f, ms[t])) - ref_db > -top_db) {
+      if (trim_pass(ms[t], ref_db, top_db)) {
         lo = min(lo, t);
         hi = max(hi, t);
       }
@@ -500,11 +442,7 @@ __global__ __launch_bounds__(WF_BT) void wf_bounds_kernel(const float* __restric
       lo = min(lo, red_lo[i]);
       hi = max(hi, red_hi[i]);
     }
-    start = end = 0;   // (no frame passes: only a row with non-finite samples gets here)
-    if (hi >= 0) {
-      start = lo * WF_TRIM_HOP;
-      end = min(n, (hi + 1) * WF_TRIM_HOP);
-    }
+    trim_bounds(lo, hi, n, start, end);
     __syncthreads();   // red_max is used again below
   }
   // start is a multiple of 512 and end is one or n: the 512-sample maxima tile [start, end) exactly
@@ -522,8 +460,7 @@ __global__ __launch_bounds__(WF_BT) void wf_bounds_kernel(const float* __restric
   }
 }
 
-// out[b, i] = y[s_b + i], pcm[b, i] = trunc(32767 y / max(1, peak)) (write_wav's rule in fp32: one rounded division, one rounded
-// multiply) for i < e_b - s_b, zeros behind
+// out[b, i] = y[s_b + i], pcm[b, i] = pcm16(y, peak) for i < e_b - s_b, zeros behind
 __global__ __launch_bounds__(256) void wf_emit_kernel(const float* __restrict__ y_all, int64_t y_pitch, const int32_t* __restrict__ bounds,
                                                       const float* __restrict__ peak, float* __restrict__ out,
                                                       int16_t* __restrict__ pcm, int L) {
@@ -534,10 +471,7 @@ __global__ __launch_bounds__(256) void wf_emit_kernel(const float* __restrict__ 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < L; i += (int64_t)gridDim.x * 256) {
     const float v = i < m ? y[i] : 0.f;
     if (out) out[(int64_t)b * L + i] = v;
-    if (pcm) {
-      const float u = pk > 1.f ? __fdiv_rn(v, pk) : v;
-      pcm[(int64_t)b * L + i] = (int16_t)(int)truncf(__fmul_rn(u, 32767.0f));
-    }
+    if (pcm) pcm[(int64_t)b * L + i] = pcm16(v, pk);
   }
 }
 
@@ -680,8 +614,7 @@ __global__ __launch_bounds__(WJ_T) void wj_pcm_kernel(const float* __restrict__ 
   for (int k = 0; k < WJ_PER; ++k) {
     const int64_t j = j0 + k;
     if (j < 0 || j >= Lj) continue;
-    const float u = x[j];
-    q[k] = (int16_t)(int)truncf(__fmul_rn(pk > 1.f ? __fdiv_rn(u, pk) : u, 32767.0f));
+    q[k] = pcm16(x[j], pk);
   }
   if (j0 >= 0 && j0 + WJ_PER <= Lj) {
     *reinterpret_cast<short4*>(row + j0) = make_short4(q[0], q[1], q[2], q[3]);
@@ -813,7 +746,7 @@ extern "C" int taco_griffinlim_fast(const float* mag_t, const float* phase0, uin
 static int64_t wf_pitch(int L) { return ((int64_t)L + 3) & ~(int64_t)3; }
 static int wf_chunks(int L) { return cdiv(L, WF_CHUNK); }
 static int wf_blocks(int L) { return cdiv(L, 512); }
-static int wf_frames(int L) { return 1 + L / WF_TRIM_HOP; }
+static int wf_frames(int L) { return 1 + L / TRIM_HOP; }
 extern "C" int64_t taco_wave_finish_workspace_bytes(int B, int L) {
   if (B <= 0 || L <= 0) return TACO_EINVAL;
   return ((int64_t)B * (wf_pitch(L) + wf_chunks(L) + wf_blocks(L) + wf_frames(L)) + 64) * (int64_t)sizeof(float);

@@ -148,6 +148,28 @@ def test_trim_edge_rows(built_lib):
     assert tuple(bounds[0]) == (0, Lc)
 
 
+def test_front_end_and_finishing_cut_the_same_samples(built_lib):
+    """the -60 dB bounds of taco_audio_features equal the bounds of taco_wave_finish at trim_top_db 60 on the same rows, exactly:
+    both kernels state csrc/stft.h's trim rule.  Three rows of different lengths, 1e-5 noise around a 0.5-amplitude tone whose
+    edges lie at least 64 samples from every trim frame's edge (no frame is near the threshold: -16 dB or above against -91 dB)"""
+    from tacotron_amd import audio
+    L, lengths, body = 6000, [6000, 4097, 1537], [(2200, 4300), (1600, 2300), (1200, 1400)]
+    rng = np.random.default_rng(17)
+    x = np.zeros((3, L), np.float32)
+    for b, (n, (s, e)) in enumerate(zip(lengths, body)):
+        x[b, :n] = 1e-5 * rng.standard_normal(n)
+        x[b, s:e] += 0.5 * np.sin(2 * np.pi * 180 * np.arange(s, e) / 16000.0)
+    wave = dev(x)
+    front = built_lib.audio_features(wave, lengths, dev(audio.mel_basis()), 1, max_len=L)[3]
+    finish = built_lib.wave_finish(wave, samples=dev(lengths, torch.int32), deemphasis=0.0, trim_top_db=60.0)[2]
+    torch.cuda.synchronize()
+    front, finish = front.cpu().numpy(), finish.cpu().numpy()
+    print('  front end %s, finishing %s' % (front.tolist(), finish.tolist()))
+    assert np.array_equal(front, finish)
+    # the bounds by hand: frame t covers [512 t - 1024, 512 t + 1024) of the reflect-padded row and passes when it holds tone
+    assert finish.tolist() == [[1536, 5632], [1024, 3584], [512, 1537]]
+
+
 # ---- rows, determinism, poison ------------------------------------------------------------------------------------------------
 ROWS_N = [L_FULL, 0, 1, 59700, 12345]
 
