@@ -75,7 +75,11 @@ int taco_workspace_table(const TacoShape* shape, int train, TacoTensorInfo* rows
  *   row(m,tap): m = b*T + t  ->  t' = t + tap - pad_l ; zero row unless 0 <= t' < T   ('same' conv1d, ops.py:54-60;
  *   taps = 1, pad_l = 0 is tf.layers.dense, tacotron.py:40-43).
  *   post(y) = (keep ? y * keep[m,n] * 2 : y) * scale[n] + shift[n] + residual[m,n]   (each optional / nullable)
- *   Cpre (nullable) receives the value before scale/shift/residual.  W tap stride is K*ldw floats. */
+ *   scale and shift are independent: either alone applies (scale alone: y * scale[n]; shift alone: y + shift[n]).
+ *   Cpre (nullable) receives the value before scale/shift/residual.  W tap stride is K*ldw floats.
+ *   Pitches: A lda, W ldw, residual ldr, C ldc; Cpre has no pitch argument of its own and is written with the pitch of C
+ *   (element (m, n) at Cpre[m * ldc + n]); keep is dense, one byte per element, read at keep[m * N + n].  No pointer needs more
+ *   than its type's alignment: 16-byte aligned operands with pitches and K, N multiples of 4 only select the vector forms. */
 int taco_conv_gemm(const float* A, int lda, const float* W, int ldw, const float* bias, const float* scale,
                    const float* shift, const float* residual, int ldr, const uint8_t* keep, float* C, int ldc,
                    float* Cpre, int M, int N, int K, int taps, int T, int pad_l, int act, void* stream);

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import taco_numpy as on
+from tests.gemm_paths import conv_ref
 from tests.poison import Guarded
 from tests.util import report
 
@@ -18,40 +19,6 @@ pytestmark = pytest.mark.gpu
 
 def dev(a, dtype=torch.float32):
     return torch.as_tensor(np.ascontiguousarray(a)).to('cuda', dtype).contiguous()
-
-
-def conv_ref(A, W, bias, T, pad_l, act, keep=None, scale=None, shift=None, residual=None):
-    """A (M,K) with M = B*T; W (taps,K,N)."""
-    M, K = A.shape
-    taps, _, N = W.shape
-    B = M // T
-    x = A.reshape(B, T, K)
-    pad_r = taps - 1 - pad_l
-    xp = np.pad(x, ((0, 0), (max(pad_l, 0), max(pad_r, 0)), (0, 0)))
-    y = np.zeros((B, T, N))
-    for j in range(taps):
-        sh = j - pad_l
-        for t in range(T):
-            st = t + sh
-            if 0 <= st < T:
-                y[:, t] += x[:, st] @ W[j]
-    y = y.reshape(M, N)
-    if bias is not None:
-        y = y + bias
-    if act == 1:
-        y = np.maximum(y, 0)
-    elif act == 2:
-        y = on.sigmoid(y)
-    elif act == 3:
-        y = np.tanh(y)
-    if keep is not None:
-        y = y * keep * 2
-    pre = y.copy()
-    if scale is not None:
-        y = y * scale + (shift if shift is not None else 0)
-    if residual is not None:
-        y = y + residual
-    return y, pre
 
 
 def test_naive_gemm_plumbing(built_lib):
@@ -76,8 +43,8 @@ CASES = [
     (90, 9, 128, 80, 8, 3, 1, 'bias'),
     (64, 64, 1025, 256, 1, 0, 0, 'bias'),
     (200, 200, 256, 256, 1, 0, 1, 'bias,keep'),
-    (6400, 200, 256, 256, 1, 0, 2, 'bias'),        # big-tile path
-    (3000, 3000, 384, 136, 1, 0, 3, 'bias'),       # big-tile path with ragged edges
+    (6400, 200, 256, 256, 1, 0, 2, 'bias'),        # 100 tiles of 128 x 128: still the 64 x 64 kernel (tests/gemm_paths.py nn_tile)
+    (3000, 3000, 384, 136, 1, 0, 3, 'bias'),       # 72 tiles, ragged edges; the 128 x 128 kernel: tests/test_gpu_gemm_paths.py
     (36, 9, 128, 128, 5, 2, 0, 'residual'),
     (36, 9, 80, 128, 6, 3, 0, ''),                 # backward-style pad (k-1 - (k-1)//2)
 ]
