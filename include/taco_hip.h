@@ -183,6 +183,35 @@ int taco_infer_stop(const TacoShape* shape, const float* params, const int32_t* 
                     const int32_t* speaker, const TacoStopRule* rule, float* seq2seq_output, float* output, float* alignments,
                     int32_t* lengths, void* workspace, void* stream);
 
+/* Alignment scores: per utterance, how the attention read its text (the role of the attention picture the reference sends to
+ * TensorBoard, train.py:92-103 and test.py:60-69, as numbers that stay on the device).  Built on the stop rule's argmax walk.
+ *   alignments  (B, Td, Tt) as taco_forward, taco_infer or taco_infer_stop write them
+ *   text_length (B) int32;  steps (B) int32 on the DEVICE, or NULL: the `lengths` of taco_infer_stop;  max_jump >= 0
+ *   counts (B, 6) int32 and means (B, 2) fp32, both required
+ * For row b:  L = clamp(text_length[b], 1, Tt);  n = Td when steps is NULL, else clamp(steps[b], 0, Td).  For every scored step
+ * t < n, a_t is the lowest index s < Tt at which a[t, s] equals the maximum of the step's non-NaN elements, and 0 when every
+ * element is NaN -- for a step without NaN the stop rule's a_t, lowest index on ties -- and p_t = a[t, a_t].
+ *   counts[b] = { n,
+ *                 end       = max_t a_t, 0 when n == 0,
+ *                 pad_steps = #{t : a_t >= L},
+ *                 back      = #{1 <= t < n : a_t < a_{t-1}},
+ *                 skip      = #{1 <= t < n : a_t > a_{t-1} + max_jump},
+ *                 covered   = #{s < L : a_t == s for some t < n} }
+ *   means[b]  = { focus    = (1 / n) sum_t p_t,
+ *                 pad_mass = (1 / n) sum_t sum_{s >= L} a[t, s] },  both 0 when n == 0
+ * The means are fp32 sums in a fixed order (the same arguments give the same bits); a NaN among their terms makes them NaN,
+ * the counts are defined for any input.  Rows t >= n and every other row's data have no influence on row b.
+ * One launch of B workgroups, each keeping its row's a_t in LDS: no workspace, no allocation, no host synchronisation, no
+ * workgroup waits for another one; graph-capturable.  Nothing outside counts and means is written; alignments needs the
+ * alignment of a float only (16-byte loads are used when Tt % 4 == 0 and the base allows).  The LDS record holds
+ * TACO_ALIGNMENT_MAX_TD steps and the bitmap behind `covered` TACO_ALIGNMENT_MAX_TT characters.  NULL alignments / text_length /
+ * counts / means, B, Td or Tt <= 0, max_jump < 0, Td > TACO_ALIGNMENT_MAX_TD or Tt > TACO_ALIGNMENT_MAX_TT return TACO_EINVAL before
+ * anything is enqueued.  TACO_VERSION did not change with this entry point: detect it by the symbol. */
+#define TACO_ALIGNMENT_MAX_TD 16384
+#define TACO_ALIGNMENT_MAX_TT 16384
+int taco_alignment_scores(const float* alignments, const int32_t* text_length, const int32_t* steps, int max_jump,
+                          int32_t* counts, float* means, int B, int Td, int Tt, void* stream);
+
 /* add_train_op (tacotron.py:167-185): global-norm clip (cap_grads) then TF-form Adam, in place.
  *   step = global_step after this update (1-based).  scratch: >= 256 floats.  gnorm_out[0] receives ||g||. */
 int taco_clip_adam_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr, float cap,

@@ -193,6 +193,10 @@ int launch_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* l
 // taco_infer_stop's end-detection rule (include/taco_hip.h) over the alignments (B, Td, Tt) of a full decode: len (B) int32
 int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* len, int B, int Tt, int Td, int end_offset, int hold,
                      int min_steps, hipStream_t s);
+// taco_alignment_scores (include/taco_hip.h) over alignments (B, Td, Tt): counts (B, 6) int32, means (B, 2); steps nullable.  One
+// launch of B workgroups; the entry point has checked the arguments (Td, Tt within TACO_ALIGNMENT_MAX_TD / _TT)
+int launch_alignment_scores(const float* align, const int32_t* text_length, const int32_t* steps, int max_jump, int32_t* counts,
+                            float* means, int B, int Td, int Tt, hipStream_t s);
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);  // y = a + b
 // L1 losses + sign gradients.  loss_parts[0..kLossParts) = per-block partial sums of |a-b| (overwritten; summed in block
 // order by launch_finish_loss: no atomics, reproducible).  grad (ldg >= N) = sign(a-b), pad columns zeroed.

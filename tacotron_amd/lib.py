@@ -99,6 +99,7 @@ EXPORTS = {
     'taco_backward': (C.c_int, [_SH] + [_P] * 14),
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
     'taco_infer_stop': (C.c_int, [_SH, _P, _P, _P, _P, C.POINTER(TacoStopRule), _P, _P, _P, _P, _P, _P]),
+    'taco_alignment_scores': (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
     'taco_clip_adam_step': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P]),
     'taco_clip_adam_step_guarded': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P, _P]),
     'taco_clear_error': (C.c_int, [_SH, _I, _P, _P]),
@@ -306,6 +307,43 @@ def infer_stop(shape, params, text, text_length, rule, s2s, out, align, lengths,
     s2s / out / align are 0."""
     _check(_lib.taco_infer_stop(C.byref(shape), ptr(params), ptr(text), ptr(text_length), ptr(speaker), C.byref(rule) if rule is not None else None,
                                 ptr(s2s), ptr(out), ptr(align), ptr(lengths), ptr(workspace), stream_ptr()), 'taco_infer_stop')
+
+
+ALIGN_COUNTS = ('n', 'end', 'pad_steps', 'back', 'skip', 'covered')   # columns of counts (include/taco_hip.h taco_alignment_scores)
+ALIGN_MEANS = ('focus', 'pad_mass')                                   # columns of means
+MAX_JUMP = 3                       # `skip` counts argmax moves of more than this many characters in one decoder step; a choice
+ALIGN_MAX_TD = ALIGN_MAX_TT = 16384   # TACO_ALIGNMENT_MAX_TD / _TT
+
+
+def alignment_scores(alignments, text_length, steps=None, max_jump=MAX_JUMP, counts=None, means=None):
+    """Per-utterance attention scores (include/taco_hip.h taco_alignment_scores): alignments (B, Td, Tt) fp32, text_length (B) int32,
+    steps (B) int32 or None -- the lengths of infer_stop; None scores all Td steps -- all on the device -> (counts (B, 6) int32 in the
+    order ALIGN_COUNTS, means (B, 2) fp32 in the order ALIGN_MEANS), device tensors.  Enqueued on the current stream; nothing is
+    copied and nothing waits.  counts / means: the caller's own buffers; default: fresh ones."""
+    who = 'alignment_scores'
+    if not torch.is_tensor(alignments) or alignments.dim() != 3 or alignments.dtype != torch.float32 or min(alignments.shape) < 1:
+        raise ValueError('%s: alignments must be a float32 tensor of shape (B, Td, Tt), got %s %s'
+                         % (who, getattr(alignments, 'dtype', type(alignments)), tuple(getattr(alignments, 'shape', ()))))
+    if not alignments.is_contiguous():
+        raise ValueError('%s: alignments must be contiguous' % who)
+    B, Td, Tt = alignments.shape
+    dev = alignments.device
+    if Td > ALIGN_MAX_TD or Tt > ALIGN_MAX_TT:
+        raise ValueError('%s: at most %d steps and %d characters, got Td = %d, Tt = %d' % (who, ALIGN_MAX_TD, ALIGN_MAX_TT, Td, Tt))
+    for name, t, needed in (('text_length', text_length, True), ('steps', steps, False)):
+        if t is None and not needed:
+            continue
+        if (not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous int32 tensor of shape (%d,) on %s' % (who, name, B, dev))
+    if isinstance(max_jump, bool) or int(max_jump) != max_jump or not 0 <= int(max_jump) < (1 << 31):
+        raise ValueError('%s: max_jump must be an integer in [0, 2^31), got %r' % (who, max_jump))
+    counts = _own_or_given(counts, (B, len(ALIGN_COUNTS)), torch.int32, dev, who + ': counts')
+    means = _own_or_given(means, (B, len(ALIGN_MEANS)), torch.float32, dev, who + ': means')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: alignments must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_alignment_scores(ptr(alignments), ptr(text_length), ptr(steps), int(max_jump), ptr(counts), ptr(means), B, Td, Tt,
+                                      stream_ptr()), 'taco_alignment_scores')
+    return counts, means
 
 
 def clip_adam_step(params, grads, m, v, lr, cap, step, scratch, gnorm_out, err_words=None):

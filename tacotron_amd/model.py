@@ -41,6 +41,7 @@ class Tacotron(object):
         self.alignments = torch.empty(B, Td, Tt, device=dev)
         self.lengths = None               # (B) int32 decoder steps kept per row after run(stop=...); None after run()
         self._lengths = None
+        self._align_scores = None         # (counts, means) of alignment_scores(), allocated at its first call
         self._loss = torch.zeros(3, device=dev)
         self.workspace = torch.empty(lib.workspace_bytes(self.shape, train) // 4, dtype=torch.float32, device=dev)
         self.masks = None
@@ -239,6 +240,19 @@ class Tacotron(object):
             lib.infer_stop(self.shape, self.params.flat, i['text'], i['text_length'], stop, self.seq2seq_output, self.output,
                            self.alignments, self.lengths, self.workspace, self.speaker)
         return self.output, self.alignments
+
+    # -- alignment monitor --------------------------------------------------------------------------------
+    def alignment_scores(self, max_jump=lib.MAX_JUMP):
+        """Per-utterance attention scores of `alignments` (lib.alignment_scores): (counts (B, 6) int32, means (B, 2) fp32) in the
+        order lib.ALIGN_COUNTS / lib.ALIGN_MEANS.  After run(stop=...) each row is scored over its own `lengths` steps, otherwise
+        (run(), a training step) over all Td.  One launch on the current stream into two tensors the model allocates once and
+        returns every time; no copy and no synchronisation -- read them where the host synchronises anyway."""
+        if self._align_scores is None:
+            B = self.shape.B
+            self._align_scores = (torch.empty(B, len(lib.ALIGN_COUNTS), dtype=torch.int32, device=self.device),
+                                  torch.empty(B, len(lib.ALIGN_MEANS), dtype=torch.float32, device=self.device))
+        counts, means = self._align_scores
+        return lib.alignment_scores(self.alignments, self.inputs['text_length'], self.lengths, max_jump, counts, means)
 
     # -- checkpoint (train.py:47,85-90: weights + Adam slots + global_step) --------------------------------
     def state_dict(self):

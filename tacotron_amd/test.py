@@ -20,7 +20,12 @@ device (de-emphasis and trim stay off unless asked for) and the pieces of a prom
 taco_wave_join): --pause-ms SENTENCE,CLAUSE,WORD of silence behind a piece by the kind of its cut, a linear ramp of --fade-ms at every
 interior edge, PCM16 by the prompt's peak.  One prompt_NNN.wav per prompt; prompt_NNN_pieces.npy holds (offset, length, gap, kind) per
 piece and the per-piece arrays are prompt_NNN_kMM_{spec,align,len,trim}.npy.  A prompt of one piece writes the files it writes without
---long.  Without --long a line of more than 140 characters is refused as before (ValueError from load_prompts)."""
+--long.  Without --long a line of more than 140 characters is refused as before (ValueError from load_prompts).
+--align-scores (opt-in; the reference draws the attention picture for TensorBoard instead, test.py:60-69): the per-utterance attention
+scores are computed on the device (Tacotron.alignment_scores, taco_alignment_scores; over each prompt's own steps with --stop) and
+prompt_NNN_ascore.npy holds the prompt's 8 values as float64 (lib.ALIGN_COUNTS, then lib.ALIGN_MEANS); prompt_NNN_align.png is the
+attention picture over the kept steps (alignment.attention_png); a prompt that alignment.flags marks gets one `WARNING prompt N: ...`
+line.  With --long a prompt of several pieces writes one pair per piece (prompt_NNN_kMM_*).  It combines with every option above."""
 from __future__ import annotations
 
 import argparse
@@ -33,6 +38,7 @@ import numpy as np
 import torch
 
 from .config import Config
+from .alignment import attention_png, flags, scores_row
 from .data import KIND_NAMES, load_prompts, split_prompt
 from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform
 from .model import Tacotron
@@ -102,10 +108,12 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
         raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (trim_db,))
 
 
-def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None):
+def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
-    piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav."""
+    piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
+    ascore (--align-scores): the prompt's 8 alignment scores, written as _ascore.npy (float64) next to _align.png, the attention picture
+    over the kept alignment rows at `zoom` pixels per cell."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -123,10 +131,13 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_trim.npy', trim)
     if conv is not None:
         np.save(path + '_conv.npy', conv)
+    if ascore is not None:
+        np.save(path + '_ascore.npy', np.asarray(ascore, dtype=np.float64))
+        attention_png(path + '_align.png', align, zoom=zoom)
 
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None, deemphasis=None, trim_db=None, long=None):
+         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -149,7 +160,10 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     `deemphasis` / `trim_db`: bounds [0, n_b)), and the pieces of each prompt are joined there (join_waveform), <= 256 pieces and the
     rest of the prompt they end in per call.  prompt_NNN.wav holds the prompt's total samples, prompt_NNN_pieces.npy (K, 4) int32
     offset, length, gap, kind per piece, prompt_NNN_kMM_*.npy the arrays of piece MM; a prompt of one piece writes the files and the
-    contents it writes without `long`."""
+    contents it writes without `long`.
+    `align_scores`: every batch is scored on the device (Tacotron.alignment_scores: over model.lengths with `stop`, else all steps) and
+    each prompt -- with `long`, each piece -- additionally writes _ascore.npy and _align.png (write_prompt); a prompt whose scores
+    alignment.flags marks is named in one WARNING line.  Nothing else changes."""
     check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long)
     long = long_options(long)
     if long is not None and not vocode:
@@ -172,7 +186,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     os.makedirs(out_dir, exist_ok=True)
 
     def synthesise(batch, n, out_rows=None, bounds_rows=None):
-        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths), host arrays or None.  out_rows /
+        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores), host arrays or None.  out_rows /
         bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made"""
         Bn = batch['text'].shape[0]
         if config.num_speakers > 1:
@@ -189,6 +203,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         else:
             model.set_inputs(batch)
         out, al = model.run(stop=stop)
+        scores = model.alignment_scores() if align_scores else None   # (enqueued behind the decode; read with the other results below)
         model.check()
         mean = model.stft_mean if model.stft_mean is not None else torch.zeros(config.fft_size * config.r)
         std = model.stft_std if model.stft_std is not None else torch.ones(config.fft_size * config.r)
@@ -212,25 +227,34 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             else:
                 wav = wav.cpu().numpy()
         lengths = model.lengths.cpu().numpy() if stop is not None else None
-        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths
+        if scores is not None:
+            scores = np.stack([scores_row(c, m) for c, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
+        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores
+
+    def marks(score, L):
+        """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
+        return flags(score[:6], score[6:], L, end_offset=stop.end_offset if stop is not None else 1)
 
     n = 0
     if long is not None:
-        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long)
+        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks)
         print('wrote %d samples to %s' % (n, out_dir))
         return n
     for batch in load_prompts(prompts, ivocab):
         Bn = batch['text'].shape[0]
-        spec, al, wav, conv, pcm, trim, lengths = synthesise(batch, n)
+        spec, al, wav, conv, pcm, trim, lengths, scores = synthesise(batch, n)
         for i in range(Bn):
-            wi, len_b, pi, ti, ci = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv))
-            write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci)
+            wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
+            write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si)
+            found = marks(si, int(batch['text_length'][i])) if si is not None else []
+            if found:
+                print('WARNING prompt %d: %s' % (n, ', '.join(found)))
             n += 1
     print('wrote %d samples to %s' % (n, out_dir))
     return n
 
 
-def _test_long(config, prompts, ivocab, out_dir, synthesise, long):
+def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks):
     """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write"""
     pause_ms, fade_ms = long
     split = [split_prompt(p) for p in prompts]
@@ -250,12 +274,13 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long):
         N = len(lines)
         rows = torch.empty(N, L, dtype=torch.float32, device='cuda')
         bounds = torch.empty(N, 2, dtype=torch.int32, device='cuda')
-        arrays = []   # per piece: (spec, align, len_b, trim, conv)
+        arrays = []   # per piece: (spec, align, len_b, trim, conv, scores, text length)
         at = 0
         for batch in load_prompts(lines, ivocab):
             Bn = batch['text'].shape[0]
-            spec, al, _, conv, _, trim, lengths = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
-            arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i]) for i in range(Bn)]
+            spec, al, _, conv, _, trim, lengths, scores = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i],
+                        None if scores is None else scores[i], int(batch['text_length'][i])) for i in range(Bn)]
             at += Bn
         gap = join_gaps(kinds, pause_ms)
         _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
@@ -263,9 +288,15 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long):
         for p in range(lo, hi):
             a, b = first[p - lo], first[p - lo + 1]
             path = os.path.join(out_dir, 'prompt_%03d' % p)
+            found = []
             for k in range(a, b):
-                spec, al, len_b, trim, conv = arrays[k]
-                write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a)
+                spec, al, len_b, trim, conv, score, text_len = arrays[k]
+                write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score)
+                names = marks(score, text_len) if score is not None else []
+                if names:
+                    found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
+            if found:
+                print('WARNING prompt %d: %s' % (p, '; '.join(found)))
             write_wav_pcm(path + '.wav', pcm[p - lo, :int(total[p - lo])])
             if b - a > 1:
                 table = [[int(offsets[k]), min(L, max(0, int(arrays[k][3][1]) - int(arrays[k][3][0]))), 0 if k == b - 1 else gap[k],
@@ -311,6 +342,9 @@ def parse_args(argv=None):
                          '300,150,0: choices of the author, not tuned by ear; a cut inside a word gets none)')
     ap.add_argument('--fade-ms', type=float, default=FADE_MS,
                     help='--long: milliseconds of linear ramp at every interior edge of a piece (default 5: a choice, not tuned by ear)')
+    ap.add_argument('--align-scores', action='store_true',
+                    help='score every prompt\'s attention on the device: prompt_NNN_ascore.npy (8 values: n, end, pad_steps, back, skip, '
+                         'covered, focus, pad_mass), prompt_NNN_align.png, and a WARNING line for a prompt the (untuned) thresholds mark')
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
     try:
@@ -329,4 +363,5 @@ if __name__ == '__main__':
     print('Building Tacotron')
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
-         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long)
+         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
+         align_scores=a.align_scores)

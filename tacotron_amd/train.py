@@ -1,7 +1,10 @@
 """train.py -- host driver with the reference's CLI and loop contract (train.py:16-126): -t/--train-set, -d/--debug,
 -r/--restore; LR annealing every 1000 steps, loss-explosion guard, checkpoint + listening sample every SAVE_EVERY steps
 (train.py:85-103; the TensorBoard wrapping is out of scope, the sample is written as .wav / .npy under log/<save_path>/).
-Without a preprocessed corpus under data/<set>/ it trains on synthetic Nancy-shaped batches."""
+Without a preprocessed corpus under data/<set>/ it trains on synthetic Nancy-shaped batches.
+--align-log (opt-in): the alignment monitor.  At every log step the batch's attention is scored on the device
+(Tacotron.alignment_scores) and a second line gives the batch means of focus, covered / L, back, skip and pad_mass and the number of
+rows alignment.flags marks; the listening sample gets attention_<step>.png and attention_<step>_scores.npy next to its .npy."""
 from __future__ import annotations
 
 import argparse
@@ -19,9 +22,11 @@ from .dist import GradReducer, init_from_env
 from .model import Tacotron
 
 
-def save_sample(model, out_dir, step, n_iter=50):
+def save_sample(model, out_dir, step, n_iter=50, align=False):
     """train.py:92-103: `ideal` = the target spectrogram of utterance 0 through Griffin-Lim, `sample` = the model's output for
-    it, plus its alignment; both de-normalised with the corpus statistics (identity for synthetic data)."""
+    it, plus its alignment; both de-normalised with the corpus statistics (identity for synthetic data).
+    align (--align-log): additionally attention_<step>.png, the reference's attention picture of utterance 0 (alignment.attention_png),
+    and attention_<step>_scores.npy, its 8 alignment scores as float64 (lib.ALIGN_COUNTS, then lib.ALIGN_MEANS)."""
     from . import lib
     from .griffinlim import invert_spectrogram
     from .test import write_wav
@@ -36,7 +41,23 @@ def save_sample(model, out_dir, step, n_iter=50):
     write_wav(os.path.join(out_dir, 'ideal_%d.wav' % step), wav[0])
     write_wav(os.path.join(out_dir, 'sample_%d.wav' % step), wav[1])
     np.save(os.path.join(out_dir, 'sample_%d_spec.npy' % step), spec[1])
-    np.save(os.path.join(out_dir, 'attention_%d.npy' % step), model.alignments[0].cpu().numpy())
+    attention = model.alignments[0].cpu().numpy()
+    np.save(os.path.join(out_dir, 'attention_%d.npy' % step), attention)
+    if align:
+        from .alignment import attention_png, scores_row
+        counts, means = model.alignment_scores()
+        attention_png(os.path.join(out_dir, 'attention_%d.png' % step), attention)
+        np.save(os.path.join(out_dir, 'attention_%d_scores.npy' % step), scores_row(counts[0].cpu().numpy(), means[0].cpu().numpy()))
+
+
+def align_line(counts, means, text_length, Tt):
+    """The --align-log line of one batch from its host arrays: counts (B, 6), means (B, 2), text_length (B)."""
+    from .alignment import flags
+    counts, means = np.asarray(counts), np.asarray(means, dtype=np.float64)
+    L = np.clip(np.asarray(text_length, dtype=np.int64), 1, Tt)
+    flagged = sum(1 for c, m, l in zip(counts, means, L) if flags(c, m, l))
+    return ('align focus %.3f covered %.3f back %.2f skip %.2f pad_mass %.4f flagged %d/%d' %
+            (means[:, 0].mean(), (counts[:, 5] / L).mean(), counts[:, 3].mean(), counts[:, 4].mean(), means[:, 1].mean(), flagged, len(L)))
 
 
 def load_corpus(data_path, seed=0):
@@ -102,8 +123,10 @@ def latest_checkpoint(ckpt_prefix):
     return best
 
 
-def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False):
-    """corpus_fp32: standardise the whole corpus on the host and feed fp32 (load_corpus; A/B runs) instead of keeping it as stored
+def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False):
+    """align_log: score the batch's attention on the device at every log step and print a second line (module docstring); no launch,
+    copy or synchronisation is added to any other step.
+    corpus_fp32: standardise the whole corpus on the host and feed fp32 (load_corpus; A/B runs) instead of keeping it as stored
     and standardising in the batch gather (open_corpus + norm=, the default).  The batches are bit-identical either way."""
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
@@ -170,6 +193,7 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
                 torch.cuda.synchronize()
                 t_mark, s_mark = time.perf_counter(), step
             if gs % log_every == 0 or gs % save_every == 0:
+                scores = model.alignment_scores() if align_log else None   # one launch, enqueued in front of the sync below
                 loss = float(model.loss)                      # the only host sync, every log_every steps
                 try:
                     model.check()                             # decoder exchange time-outs surface here (sticky flag; the
@@ -182,6 +206,9 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
                     s2s_l, out_l = (float(x) for x in model.loss_terms)
                     print('step %d loss %.1f (seq2seq %.1f + output %.1f) gnorm %.2f decoder-mode %d' %
                           (gs, loss, s2s_l, out_l, float(model.global_gradient_norm), model.decoder_mode))
+                    if scores is not None:                    # (B, 6) + (B, 2) + (B) values, already computed: no alignment tensor travels
+                        print('step %d %s' % (gs, align_line(scores[0].cpu().numpy(), scores[1].cpu().numpy(),
+                                                             model.inputs['text_length'].cpu().numpy(), model.shape.Tt)))
                 # train.py:77-80; `not isfinite` added: the bf16x3 GEMMs turn an Inf operand into NaN (inf - inf in the plane split),
                 # and `NaN > 1e8` is False -- a diverged run must still stop here
                 if (not math.isfinite(loss) or loss > 1e8) and gs > 500:
@@ -195,7 +222,7 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
                     os.makedirs(os.path.dirname(ckpt_prefix) or '.', exist_ok=True)
                     torch.save(model.state_dict(), '%s-%d' % (ckpt_prefix, gs))
                     print('saving sample')
-                    save_sample(model, os.path.join('log', config.save_path), gs)
+                    save_sample(model, os.path.join('log', config.save_path), gs, align=align_log)
                 if distributed:
                     # rank 0 spent a while on the host; the others must not run ahead into the next step's collectives (and the
                     # persistent decoder kernels of a rank that waits inside a collective keep spinning on their peers)
@@ -225,7 +252,7 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
     return model
 
 
-if __name__ == '__main__':
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('-t', '--train-set', default='nancy')
     ap.add_argument('-d', '--debug', type=bool, default=False)
@@ -233,10 +260,17 @@ if __name__ == '__main__':
     ap.add_argument('--steps', type=int, default=1000000)
     ap.add_argument('--corpus-fp32', action='store_true',
                     help='standardise the corpus on the host and feed fp32 (the earlier path) instead of keeping it as stored')
-    a = ap.parse_args()
+    ap.add_argument('--align-log', action='store_true',
+                    help='alignment monitor: a second log line with the batch means of the per-utterance attention scores (computed on '
+                         'the device) and the rows the untuned thresholds of alignment.flags mark; attention_<step>.png with every sample')
+    return ap.parse_args(argv)
+
+
+if __name__ == '__main__':
+    a = parse_args()
     c = Config()
     c.data_path = 'data/%s/' % a.train_set
     c.restore = a.restore
     c.save_path = 'debug' if a.debug else '%s/tacotron' % a.train_set
     print('Building Tacotron')
-    train(c, a.steps, corpus_fp32=a.corpus_fp32)
+    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log)
