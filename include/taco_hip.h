@@ -212,6 +212,44 @@ int taco_infer_stop(const TacoShape* shape, const float* params, const int32_t* 
 int taco_alignment_scores(const float* alignments, const int32_t* text_length, const int32_t* steps, int max_jump,
                           int32_t* counts, float* means, int B, int Td, int Tt, void* stream);
 
+/* ---- held-out evaluation: frame distance over a dynamic-time-warping path ------------------------------------------------- */
+/* Frames in use: x (B, F, C) chronological frames (taco_denorm_unframe's spec).  n[b] = 1 + the last f with x[b, f, c] > floor for
+ * some c, and 0 when there is none; a NaN compares false.  The corpus pads every recording with frames of exactly log(1e-8) and
+ * stores no frame count, so the recorded length is read off the frames.  One launch of B workgroups, no workspace, no allocation,
+ * no host synchronisation; graph-capturable.  NULL x / n or B, F, C <= 0 return TACO_EINVAL before anything is enqueued. */
+int taco_frames_active(const float* x, float floor, int32_t* n, int B, int F, int C, void* stream);
+
+/* Dynamic time warping of two frame sequences per batch row (the warp behind mel-cepstral distortion, MCD-DTW).
+ *   a (B, Fa, C), b (B, Fb, C) fp32 chronological frames;  na, nb (B) int32 on the DEVICE, or NULL: Fa / Fb; used clamped to
+ *   [0, Fa] / [0, Fb];  basis (K, C) fp32, or NULL: K == C and the coefficients are the channels themselves;
+ *   cost (B) fp32 and steps (B) int32, both required;  workspace: taco_frame_dtw_workspace_bytes(B, Fa, Fb, K) bytes, arbitrary
+ *   contents (NULL allowed when that is 0).
+ * Exact semantics -- every operation below is ONE fp32 operation rounded to nearest even, nothing is fused, denormals are kept, so a
+ * NumPy float32 restatement gives the same bits:
+ *   1. coefficients  u[i, k] = sum_c basis[k, c] * a[b, i, c]: acc = +0, then for c = 0 .. C-1 acc = acc + (basis[k, c] * a[b, i, c]);
+ *      v[j, k] likewise from b.  With basis NULL u[i, k] = a[b, i, k].
+ *   2. local distance  d(i, j) = sqrt(s), s = +0, then for k = 0 .. K-1  t = u[i, k] - v[j, k];  s = s + (t * t);  sqrt correctly rounded.
+ *   3. recurrence  D[0][0] = d(0, 0), N[0][0] = 1.  Otherwise the predecessor is the candidate of smallest D among (i-1, j-1),
+ *      (i-1, j), (i, j-1), those inside the table only; on equal D the earliest in that order wins;
+ *      D[i][j] = D[pred] + d(i, j), N[i][j] = N[pred] + 1.
+ *   4. results  cost[b] = D[na-1][nb-1], steps[b] = N[na-1][nb-1] (the cells on the chosen path); both 0 when na == 0 or nb == 0.
+ * Frames i >= na and j >= nb and every other row's data have no influence on row b.  With non-finite inputs the results are
+ * unspecified, but the launch ends and writes nothing outside cost / steps / workspace.
+ * One launch, a workgroup per row walking the anti-diagonals i + j = const with the three live diagonals of (D, N) in LDS; the
+ * coefficients are computed once per row, into LDS where they fit beside the diagonals (160 KiB) and else into the row's slice of
+ * `workspace`.  The Fa x Fb table is never materialised.  No allocation, no host synchronisation, no workgroup waits for another
+ * one; graph-capturable; the same arguments give the same bits.
+ * NOT provided: the warping path itself (it needs an Fa x Fb direction table) and a Sakoe-Chiba band (every cell is visited).
+ * NULL a / b / cost / steps, B, Fa, Fb, C or K <= 0, basis == NULL with K != C, K > TACO_DTW_MAX_K, C > TACO_DTW_MAX_C, Fa or Fb >
+ * TACO_DTW_MAX_FRAMES, or a NULL workspace where one is needed return TACO_EINVAL before anything is enqueued; the size function
+ * returns TACO_EINVAL for the same shapes.  TACO_VERSION did not change with these entry points: detect them by the symbol. */
+#define TACO_DTW_MAX_FRAMES 1024
+#define TACO_DTW_MAX_K 32
+#define TACO_DTW_MAX_C 128
+int64_t taco_frame_dtw_workspace_bytes(int B, int Fa, int Fb, int K);
+int taco_frame_dtw(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
+                   int32_t* steps, void* workspace, int B, int Fa, int Fb, int C, int K, void* stream);
+
 /* add_train_op (tacotron.py:167-185): global-norm clip (cap_grads) then TF-form Adam, in place.
  *   step = global_step after this update (1-based).  scratch: >= 256 floats.  gnorm_out[0] receives ||g||. */
 int taco_clip_adam_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr, float cap,

@@ -197,6 +197,11 @@ int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* le
 // launch of B workgroups; the entry point has checked the arguments (Td, Tt within TACO_ALIGNMENT_MAX_TD / _TT)
 int launch_alignment_scores(const float* align, const int32_t* text_length, const int32_t* steps, int max_jump, int32_t* counts,
                             float* means, int B, int Td, int Tt, hipStream_t s);
+// taco_frames_active / taco_frame_dtw (include/taco_hip.h; dtw.hip): one launch of B workgroups each; the entry points have checked
+// the arguments (Fa, Fb, C, K within TACO_DTW_MAX_*; workspace given where the coefficients do not fit LDS)
+int launch_frames_active(const float* x, float floor, int32_t* n, int B, int F, int C, hipStream_t s);
+int launch_frame_dtw(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost, int32_t* steps,
+                     float* workspace, int B, int Fa, int Fb, int C, int K, hipStream_t s);
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);  // y = a + b
 // L1 losses + sign gradients.  loss_parts[0..kLossParts) = per-block partial sums of |a-b| (overwritten; summed in block
 // order by launch_finish_loss: no atomics, reproducible).  grad (ldg >= N) = sign(a-b), pad columns zeroed.

@@ -1,0 +1,194 @@
+"""evaluate.py -- held-out evaluation of a checkpoint (no counterpart in the reference, which never scores one): for the last N
+utterances of the corpus, the ones `train --holdout N` never draws,
+  (a) the teacher-forced loss: taco_forward through a train=True Tacotron on the checkpoint's parameters with masks=None, i.e. no
+      dropout and no sampling -- the three numbers the train log prints, on utterances the optimiser has not seen;
+  (b) a free-running score: the prompt's text is decoded with end detection (run(stop=TacoStopRule())), the predicted and the
+      recorded mel frames are put in chronological order on the device, and their mel-cepstral distortion is taken over a dynamic-
+      time-warping path (Tacotron.mel_distortion -> lib.frame_dtw; the warp because a free-running decoder does not keep the
+      recording's timing).  The recorded frame count is read off the frames (lib.frames_active): the corpus pads every recording
+      with frames of log(1e-8) and stores no length.
+Only cost, steps, na, nb and the three losses of each batch travel to the host.
+
+    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval]
+
+prints one line per batch and a final line with the mean teacher-forced loss and the mean and worst MCD, and writes
+eval_<step>.npy, one row per utterance: index, na, nb, steps, cost, mcd (float64; COLUMNS).
+
+WHAT THIS MCD IS: MCD_DB * cost / steps, where cost sums the Euclidean distance of DCT coefficients 1 .. cepstra (c0 left out) of
+the model's OWN 80-band natural-log mel frames along the path, and steps counts the path's cells.  It is comparable between
+checkpoints of this project on the same held-out set.  It is NOT comparable with figures published from other feature extractors
+(mel-generalised cepstra of a vocoder analysis, other band counts, log bases, frame rates or path-length conventions).
+
+The final batch is padded to the batch size by repeating its last utterance; the copies are left out of the per-utterance rows and
+of the MCD statistics.  The teacher-forced loss is one number per batch (and the CBHG's batch normalisation sees the whole batch),
+so the padded batch enters the mean loss weighted by its share of real rows.  Without a corpus on disk the synthetic pool of
+train.py stands in, as there."""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import lib
+from .config import Config
+from .data import DeviceCorpus, synthetic_corpus
+from .model import Tacotron
+from .params import ParamBuffer
+from .train import latest_checkpoint, open_corpus
+
+COLUMNS = ('index', 'na', 'nb', 'steps', 'cost', 'mcd')
+PAD_FLOOR = float(np.float16(np.log(1e-8)))   # the value preprocess stores in the padding frames (fp16 of log(1e-8))
+
+
+def holdout_batches(n, holdout, batch_size, keep=None):
+    """The last `holdout` of n utterances in batches of batch_size -> [(index (batch_size,) int64, valid)]: the first `valid` entries
+    of a batch are its utterances, in corpus order; the rest of the final batch repeats its last utterance.  keep: a boolean mask over
+    the n utterances (e.g. one speaker's); held-out utterances outside it are skipped."""
+    n, holdout, batch_size = int(n), int(holdout), int(batch_size)
+    if not 0 < holdout <= n:
+        raise ValueError('holdout must be in 1..%d (the corpus size), got %d' % (n, holdout))
+    if batch_size < 1:
+        raise ValueError('batch_size must be >= 1, got %d' % batch_size)
+    idx = np.arange(n - holdout, n, dtype=np.int64)
+    if keep is not None:
+        idx = idx[np.asarray(keep, dtype=bool)[idx]]
+    out = []
+    for lo in range(0, len(idx), batch_size):
+        part = idx[lo:lo + batch_size]
+        valid = len(part)
+        if valid < batch_size:
+            part = np.concatenate([part, np.full(batch_size - valid, part[-1], dtype=np.int64)])
+        out.append((part, valid))
+    return out
+
+
+def unpad(batches, per_batch):
+    """per_batch[i] (batch_size, ...) host arrays of batch i -> the rows of the real utterances, concatenated in corpus order"""
+    return np.concatenate([np.asarray(x)[:valid] for (_, valid), x in zip(batches, per_batch)])
+
+
+def mcd_rows(index, na, nb, steps, cost):
+    """host arrays of the utterances -> (n, 6) float64 in the order COLUMNS; mcd is NaN for an utterance without a path (steps 0)"""
+    steps = np.asarray(steps, dtype=np.float64)
+    cost = np.asarray(cost, dtype=np.float64)
+    mcd = np.full(len(steps), np.nan)
+    np.divide(lib.MCD_DB * cost, steps, out=mcd, where=steps > 0)
+    return np.stack([np.asarray(index, dtype=np.float64), np.asarray(na, dtype=np.float64), np.asarray(nb, dtype=np.float64), steps,
+                     cost, mcd], axis=1)
+
+
+def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None):
+    """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  stop: the lib.TacoStopRule of the
+    free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
+    ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection)."""
+    torch.cuda.set_device(device)
+    dev = torch.device('cuda', device)
+    corpus = open_corpus(config.data_path)
+    norm = None
+    if corpus is not None:
+        meta, data, norm = corpus
+        config.r, config.vocab_size = meta['r'], len(meta['vocab'])
+        if 'speaker' in data:
+            config.num_speakers = int(data['speaker'].max()) + 1
+    else:
+        print('no corpus under %s -- synthetic Nancy-shaped utterances' % config.data_path)
+        data = synthetic_corpus(max(256, 4 * config.batch_size), 200, config.max_decode_iter, config.r, config.vocab_size, seed=1234,
+                                num_speakers=config.num_speakers)
+    n = len(data['text'])
+    keep = None
+    if speaker is not None:
+        if 'speaker' not in data:
+            raise ValueError('--speaker %d: the corpus under %s has no speakers.npy' % (speaker, config.data_path))
+        keep = np.asarray(data['speaker']) == int(speaker)
+    B = config.batch_size
+    batches = holdout_batches(n, holdout, B, keep)
+    if not batches:
+        raise ValueError('none of the last %d utterances belongs to speaker %d' % (holdout, speaker))
+    first = n - int(holdout)
+    held = {k: v[first:] for k, v in data.items()}   # (a memmap stays one: only the held-out rows are read and uploaded)
+    feeder = DeviceCorpus(held, B, device=dev, norm=norm, draw=lambda step: batches[step][0] - first)
+    ckpt = torch.load(checkpoint) if checkpoint else None
+    batch = feeder.next()
+    shape = lib.make_shape(B, batch['text'].shape[1], batch['mel'].shape[1], config.r, config.vocab_size, config.num_speakers)
+    params = ParamBuffer(shape, dev).init_(0)
+    forced = Tacotron(config, batch, train=True, device=dev, params=params)   # (a): shares `params` with the decoder below
+    text = {k: batch[k] for k in ('text', 'text_length', 'speaker') if k in batch}
+    free = Tacotron(config, text, train=False, device=dev, params=params)    # (b): max_decode_iter free-running steps at the most
+    if ckpt is not None:
+        forced.load_state_dict(ckpt)
+        free.global_step = forced.global_step
+    else:
+        print('no checkpoint -- scoring the seed-0 initialisation')
+    if norm is not None:
+        free.mel_mean, free.mel_std = norm['mel']
+    stop = stop if stop is not None else lib.TacoStopRule()
+    r, Td = config.r, batch['mel'].shape[1]
+    recorded = torch.empty(B, (Td // 4) * 4 * r, 80, device=dev)
+    raw = torch.empty(B, Td, 80 * r, device=dev)
+    nb = torch.empty(B, dtype=torch.int32, device=dev)
+    zeros, ones = torch.zeros(80 * r, device=dev), torch.ones(80 * r, device=dev)
+    per = {k: [] for k in ('na', 'nb', 'steps', 'cost')}
+    losses = []
+    for i, (index, valid) in enumerate(batches):
+        if i:
+            batch = feeder.next()
+            forced.set_inputs(batch)
+            free.set_inputs({k: batch[k] for k in text})
+        forced.forward(None)
+        free.run(stop=stop)
+        # the recording as stored (a pure widening gather: no standardisation to undo), in chronological order
+        lib.corpus_batch(feeder.data['mel'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw)
+        lib.denorm_unframe(raw, zeros, ones, r, spec=recorded)
+        lib.frames_active(recorded, PAD_FLOOR, nb)
+        cost, steps, na = free.mel_distortion(recorded, nb, cepstra)
+        loss = forced._loss.cpu().numpy().astype(np.float64)       # the host synchronisation of the batch
+        forced.check()
+        free.check()
+        got = {'na': na.cpu().numpy(), 'nb': nb.cpu().numpy(), 'steps': steps.cpu().numpy(), 'cost': cost.cpu().numpy()}
+        if trace is not None:
+            trace.append({'predicted': free.predicted_mel()[0].cpu().numpy(), 'recorded': recorded.cpu().numpy(), 'na': got['na'].copy(),
+                          'nb': got['nb'].copy()})
+        for k, v in got.items():
+            per[k].append(v)
+        losses.append(loss)
+        mcd = mcd_rows(index[:valid], *(got[k][:valid] for k in ('na', 'nb', 'steps', 'cost')))[:, 5]
+        print('batch %d (%d utterances) loss %.1f (seq2seq %.1f + output %.1f) mcd mean %.3f dB worst %.3f dB frames %d / %d'
+              % (i, valid, loss[0], loss[1], loss[2], np.nanmean(mcd), np.nanmax(mcd), int(got['na'][:valid].sum()),
+                 int(got['nb'][:valid].sum())))
+    feeder.close()
+    rows = mcd_rows(unpad(batches, [b[0] for b in batches]), *(unpad(batches, per[k]) for k in ('na', 'nb', 'steps', 'cost')))
+    weight = np.array([valid for _, valid in batches], dtype=np.float64)
+    mean_loss = float((np.stack(losses)[:, 0] * weight).sum() / weight.sum())
+    print('held out: %d utterances, teacher-forced loss %.1f, MCD-DTW mean %.3f dB worst %.3f dB (utterance %d) over %d cepstra of '
+          'the model\'s own mel frames' % (len(rows), mean_loss, np.nanmean(rows[:, 5]), np.nanmax(rows[:, 5]),
+                                         int(rows[int(np.nanargmax(rows[:, 5])), 0]), cepstra))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'eval_%d.npy' % forced.global_step), rows)
+    return rows, mean_loss
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('-t', '--train-set', default='nancy')
+    ap.add_argument('--checkpoint', default=None, help='default: the latest weights/<set>/tacotron-<step>')
+    ap.add_argument('--holdout', type=int, default=64, help='the last N utterances of the corpus (train --holdout N never draws them)')
+    ap.add_argument('--speaker', type=int, default=None, help='multi-speaker corpus: only the held-out utterances of this speaker')
+    ap.add_argument('--cepstra', type=int, default=13, help='DCT coefficients 1 .. N of the 80 mel bands the distance is taken over')
+    ap.add_argument('--out-dir', default='log/eval')
+    return ap.parse_args(argv)
+
+
+def main(argv=None, config=None):
+    """config: a Config to start from instead of the defaults (its data_path is kept)"""
+    a = parse_args(argv)
+    c = config if config is not None else Config()
+    if config is None:
+        c.data_path = 'data/%s/' % a.train_set
+    checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
+    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir)
+
+
+if __name__ == '__main__':
+    main()

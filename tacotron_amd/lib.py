@@ -7,6 +7,7 @@ the import of this module raises, and every entry point raises `TacoError` on a 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 # HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  One train step uses the caller's
@@ -16,6 +17,7 @@ import os
 # The variable is read when the HIP runtime initialises, i.e. at the first device call -- set it before anything touches the GPU.
 from . import QUEUES_SET_BY_USER as _QUEUES_SET_BY_USER, TORCH_IMPORTED_FIRST as _TORCH_IMPORTED_FIRST   # (package __init__ applied the default)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 # If the process may have touched the GPU before importing this package (and did not set the variable itself) the runtime is up
@@ -100,6 +102,9 @@ EXPORTS = {
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
     'taco_infer_stop': (C.c_int, [_SH, _P, _P, _P, _P, C.POINTER(TacoStopRule), _P, _P, _P, _P, _P, _P]),
     'taco_alignment_scores': (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    'taco_frames_active': (C.c_int, [_P, C.c_float, _P, _I, _I, _I, _P]),
+    'taco_frame_dtw_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
+    'taco_frame_dtw': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_clip_adam_step': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P]),
     'taco_clip_adam_step_guarded': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P, _P]),
     'taco_clear_error': (C.c_int, [_SH, _I, _P, _P]),
@@ -444,6 +449,93 @@ def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=Fa
     if want_spec and want_mag_t:
         return spec, mag_t
     return spec if want_spec else mag_t
+
+
+DTW_MAX_FRAMES, DTW_MAX_K, DTW_MAX_C = 1024, 32, 128   # TACO_DTW_MAX_FRAMES / _K / _C
+MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)        # mel-cepstral distortion in dB per unit of Euclidean cepstral distance
+
+
+def dct_basis(C=80, first=1, count=13):
+    """Rows first .. first + count - 1 of the orthonormal DCT-II over C points, (count, C) float32 on the host, computed in float64
+    and rounded once: row k is sqrt(2 / C) cos(pi (c + 1/2) k / C), row 0 is sqrt(1 / C).  The default leaves out c0 (the frame's
+    mean log energy) and keeps the 13 cepstral coefficients MCD is usually taken over."""
+    C, first, count = int(C), int(first), int(count)
+    if C < 1 or first < 0 or count < 1 or first + count > C:
+        raise ValueError('dct_basis: need C >= 1, first >= 0, count >= 1 and first + count <= C, got C = %d, first = %d, count = %d'
+                         % (C, first, count))
+    k = np.arange(first, first + count, dtype=np.float64)[:, None]
+    c = np.arange(C, dtype=np.float64)[None, :]
+    rows = np.sqrt(2.0 / C) * np.cos(np.pi * (c + 0.5) * k / C)
+    rows[k[:, 0] == 0] = np.sqrt(1.0 / C)
+    return rows.astype(np.float32)
+
+
+def _frames_arg(who, name, x):
+    if not torch.is_tensor(x) or x.dim() != 3 or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise ValueError('%s: %s must be a float32 tensor of shape (B, F, C), got %s %s'
+                         % (who, name, getattr(x, 'dtype', type(x)), tuple(getattr(x, 'shape', ()))))
+    if not x.is_contiguous():
+        raise ValueError('%s: %s must be contiguous' % (who, name))
+
+
+def frames_active(x, floor, n=None):
+    """Frames in use per row (include/taco_hip.h taco_frames_active): x (B, F, C) fp32 chronological frames on the device ->
+    n (B) int32 on the device, 1 + the last frame with an element above `floor` (0: none; a NaN is not above anything).  Enqueued on
+    the current stream; nothing is copied and nothing waits.  n: the caller's own buffer; default: a fresh one."""
+    who = 'frames_active'
+    _frames_arg(who, 'x', x)
+    floor = float(floor)
+    if floor != floor:
+        raise ValueError('%s: floor is NaN' % who)
+    B, F, Cw = x.shape
+    n = _own_or_given(n, (B,), torch.int32, x.device, who + ': n')
+    if x.device.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: x must be on the GPU, got %s (there is no CPU fallback)' % (who, x.device))
+    _check(_lib.taco_frames_active(ptr(x), floor, ptr(n), B, F, Cw, stream_ptr()), 'taco_frames_active')
+    return n
+
+
+def frame_dtw_workspace_bytes(B, Fa, Fb, K) -> int:
+    return _size('taco_frame_dtw_workspace_bytes', B, Fa, Fb, K)
+
+
+def frame_dtw(a, b, na=None, nb=None, basis=None, cost=None, steps=None, work=None):
+    """Dynamic time warping per batch row (include/taco_hip.h taco_frame_dtw): a (B, Fa, C), b (B, Fb, C) fp32 chronological frames,
+    na / nb (B) int32 or None (all Fa / Fb frames), basis (K, C) fp32 or None (the channels themselves), all on the device ->
+    (cost (B) fp32, steps (B) int32), device tensors: the summed Euclidean distance of the coefficient vectors along the cheapest
+    warping path and the number of cells on it; cost / steps is the mean distance per step, MCD_DB times that the distortion in dB.
+    Enqueued on the current stream; nothing is copied and nothing waits.  cost / steps / work: the caller's own buffers (work: uint8,
+    frame_dtw_workspace_bytes(B, Fa, Fb, K) bytes); default: fresh ones."""
+    who = 'frame_dtw'
+    _frames_arg(who, 'a', a)
+    _frames_arg(who, 'b', b)
+    B, Fa, Cw = a.shape
+    dev = a.device
+    if b.shape[0] != B or b.shape[2] != Cw or b.device != dev:
+        raise ValueError('%s: b must have shape (%d, Fb, %d) on %s, got %s on %s' % (who, B, Cw, dev, tuple(b.shape), b.device))
+    Fb = b.shape[1]
+    if max(Fa, Fb) > DTW_MAX_FRAMES or Cw > DTW_MAX_C:
+        raise ValueError('%s: at most %d frames of %d channels, got Fa = %d, Fb = %d, C = %d' % (who, DTW_MAX_FRAMES, DTW_MAX_C, Fa, Fb, Cw))
+    for name, t in (('na', na), ('nb', nb)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != torch.int32 or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous int32 tensor of shape (%d,) on %s' % (who, name, B, dev))
+    if basis is not None and (not torch.is_tensor(basis) or basis.dim() != 2 or basis.shape[1] != Cw or basis.shape[0] < 1
+                              or basis.dtype != torch.float32 or basis.device != dev or not basis.is_contiguous()):
+        raise ValueError('%s: basis must be a contiguous float32 tensor of shape (K, %d) on %s' % (who, Cw, dev))
+    K = Cw if basis is None else basis.shape[0]
+    if K > DTW_MAX_K:
+        raise ValueError('%s: at most %d coefficients per frame, got %d%s'
+                         % (who, DTW_MAX_K, K, ' (no basis: the channels themselves)' if basis is None else ''))
+    cost = _own_or_given(cost, (B,), torch.float32, dev, who + ': cost')
+    steps = _own_or_given(steps, (B,), torch.int32, dev, who + ': steps')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    nbytes = frame_dtw_workspace_bytes(B, Fa, Fb, K)
+    work = _own_or_given(work, (nbytes,), torch.uint8, dev, who + ': work')
+    _check(_lib.taco_frame_dtw(ptr(a), ptr(na), ptr(b), ptr(nb), ptr(basis), ptr(cost), ptr(steps), ptr(work) if nbytes else None,
+                               B, Fa, Fb, Cw, K, stream_ptr()), 'taco_frame_dtw')
+    return cost, steps
 
 
 def corpus_batch_width(src_addr, out_addr, row, fp16) -> int:

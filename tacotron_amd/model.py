@@ -42,6 +42,8 @@ class Tacotron(object):
         self.lengths = None               # (B) int32 decoder steps kept per row after run(stop=...); None after run()
         self._lengths = None
         self._align_scores = None         # (counts, means) of alignment_scores(), allocated at its first call
+        self._mel_eval = None             # the tensors of predicted_mel() / mel_distortion(), allocated at their first call
+        self.mel_mean = self.mel_std = None   # (80 r) statistics the corpus's mel targets were standardised with; None: identity
         self._loss = torch.zeros(3, device=dev)
         self.workspace = torch.empty(lib.workspace_bytes(self.shape, train) // 4, dtype=torch.float32, device=dev)
         self.masks = None
@@ -253,6 +255,57 @@ class Tacotron(object):
                                   torch.empty(B, len(lib.ALIGN_MEANS), dtype=torch.float32, device=self.device))
         counts, means = self._align_scores
         return lib.alignment_scores(self.alignments, self.inputs['text_length'], self.lengths, max_jump, counts, means)
+
+    # -- held-out evaluation ------------------------------------------------------------------------------
+    def _mel_eval_tensors(self, cepstra):
+        B, Td, r, dev = self.shape.B, self.shape.Td, self.shape.r, self.device
+        e = self._mel_eval
+        if e is None:
+            F = (Td // 4) * 4 * r
+            e = self._mel_eval = {'frames': torch.empty(B, F, 80, device=dev), 'na': torch.empty(B, dtype=torch.int32, device=dev),
+                                  'cost': torch.empty(B, device=dev), 'steps': torch.empty(B, dtype=torch.int32, device=dev),
+                                  'zeros': torch.zeros(80 * r, device=dev), 'ones': torch.ones(80 * r, device=dev), 'stats': None,
+                                  'basis': {}, 'work': {}}
+        if cepstra is not None and cepstra not in e['basis']:
+            e['basis'][cepstra] = torch.from_numpy(lib.dct_basis(80, 1, cepstra)).to(dev)
+        return e
+
+    def predicted_mel(self):
+        """`seq2seq_output` as chronological de-normalised mel frames (B, F, 80), F = (Td / 4) 4 r (lib.denorm_unframe with
+        `mel_mean` / `mel_std`; identity when they are None), and na (B) int32, the frames each row holds: lengths * r after
+        run(stop=...), else F.  Enqueued on the current stream into tensors the model allocates once and returns every time."""
+        e = self._mel_eval_tensors(None)
+        if self.mel_mean is None:
+            mean, std = e['zeros'], e['ones']
+        else:
+            if e['stats'] is None or e['stats'][0] is not self.mel_mean or e['stats'][1] is not self.mel_std:
+                e['stats'] = (self.mel_mean, self.mel_std, torch.as_tensor(self.mel_mean, dtype=torch.float32).to(self.device).contiguous(),
+                              torch.as_tensor(self.mel_std, dtype=torch.float32).to(self.device).contiguous())
+            mean, std = e['stats'][2:]
+        lib.denorm_unframe(self.seq2seq_output, mean, std, self.shape.r, spec=e['frames'])
+        if self.lengths is None:
+            e['na'].fill_(e['frames'].shape[1])
+        else:
+            torch.mul(self.lengths, self.shape.r, out=e['na'])
+        return e['frames'], e['na']
+
+    def mel_distortion(self, recorded, nb=None, cepstra=13):
+        """Distance of the model's mel frames from `recorded` over a dynamic-time-warping path (lib.frame_dtw): recorded (B, Fb, 80)
+        fp32 chronological de-normalised log-mel frames on the device, nb (B) int32 their frame counts or None (all Fb), cepstra the
+        DCT coefficients 1 .. cepstra the distance is taken over (lib.dct_basis) -> (cost (B) fp32, steps (B) int32, na (B) int32),
+        device tensors; lib.MCD_DB * cost / steps is the row's mel-cepstral distortion in dB, taken over this model's own 80-band
+        natural-log mel frames.  The prediction is predicted_mel().  Everything is enqueued on the current stream into tensors the
+        model allocates once (per cepstra / Fb) and returns every time; no copy and no synchronisation."""
+        cepstra = int(cepstra)
+        lib._frames_arg('mel_distortion', 'recorded', recorded)
+        e = self._mel_eval_tensors(cepstra)
+        frames, na = self.predicted_mel()
+        key = (recorded.shape[1], cepstra)
+        if key not in e['work']:   # (empty unless the coefficients of both sequences do not fit LDS: include/taco_hip.h)
+            e['work'][key] = torch.empty(lib.frame_dtw_workspace_bytes(self.shape.B, frames.shape[1], *key), dtype=torch.uint8,
+                                         device=self.device)
+        cost, steps = lib.frame_dtw(frames, recorded, na, nb, e['basis'][cepstra], e['cost'], e['steps'], e['work'][key])
+        return cost, steps, na
 
     # -- checkpoint (train.py:47,85-90: weights + Adam slots + global_step) --------------------------------
     def state_dict(self):

@@ -4,7 +4,8 @@
 Without a preprocessed corpus under data/<set>/ it trains on synthetic Nancy-shaped batches.
 --align-log (opt-in): the alignment monitor.  At every log step the batch's attention is scored on the device
 (Tacotron.alignment_scores) and a second line gives the batch means of focus, covered / L, back, skip and pad_mass and the number of
-rows alignment.flags marks; the listening sample gets attention_<step>.png and attention_<step>_scores.npy next to its .npy."""
+rows alignment.flags marks; the listening sample gets attention_<step>.png and attention_<step>_scores.npy next to its .npy.
+--holdout N (default 0): the last N utterances are never drawn, so that tacotron_amd.evaluate can score checkpoints on them."""
 from __future__ import annotations
 
 import argparse
@@ -123,8 +124,20 @@ def latest_checkpoint(ckpt_prefix):
     return best
 
 
-def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False):
-    """align_log: score the batch's attention on the device at every log step and print a second line (module docstring); no launch,
+def holdout_draw(n, holdout, batch_size, seed):
+    """The minibatch draw that leaves the last `holdout` of n utterances alone: step -> batch_size indices ~ U{0 .. n - holdout - 1}
+    from np.random.default_rng(seed), the generator and the call the feeders use on their own -- with holdout = 0 the same values."""
+    n, holdout = int(n), int(holdout)
+    if not 0 <= holdout < n:
+        raise ValueError('--holdout %d: must be >= 0 and below the corpus size %d' % (holdout, n))
+    rng = np.random.default_rng(seed)
+    return lambda step: rng.integers(n - holdout, size=int(batch_size))
+
+
+def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False, holdout=0):
+    """holdout: the last N utterances of the corpus are never drawn (tacotron_amd.evaluate scores a checkpoint on them); 0: every
+    utterance is drawn, as before.
+    align_log: score the batch's attention on the device at every log step and print a second line (module docstring); no launch,
     copy or synchronisation is added to any other step.
     corpus_fp32: standardise the whole corpus on the host and feed fp32 (load_corpus; A/B runs) instead of keeping it as stored
     and standardising in the batch gather (open_corpus + norm=, the default).  The batches are bit-identical either way."""
@@ -155,10 +168,12 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
     # batch alone would be ~2 x the 8.4 ms train step.
     dev = torch.device('cuda', local)
     budget = float(os.environ.get('TACO_CORPUS_HBM_GB', '64')) * (1 << 30)
+    # --holdout: the same seeded generator over the first n - N utterances; 0 leaves the feeders' own draw in place
+    draw = holdout_draw(len(data['text']), holdout, config.batch_size, 1000 + rank) if holdout else None
     if DeviceCorpus.nbytes(data) <= budget:
-        feeder = DeviceCorpus(data, config.batch_size, device=dev, seed=1000 + rank, norm=norm)
+        feeder = DeviceCorpus(data, config.batch_size, device=dev, seed=1000 + rank, norm=norm, draw=draw)
     else:
-        feeder = DeviceFeeder(data, config.batch_size, device=dev, depth=2, seed=1000 + rank, norm=norm)
+        feeder = DeviceFeeder(data, config.batch_size, device=dev, depth=2, seed=1000 + rank, norm=norm, draw=draw)
 
     def next_batch(step):
         return feeder.next()
@@ -263,6 +278,8 @@ def parse_args(argv=None):
     ap.add_argument('--align-log', action='store_true',
                     help='alignment monitor: a second log line with the batch means of the per-utterance attention scores (computed on '
                          'the device) and the rows the untuned thresholds of alignment.flags mark; attention_<step>.png with every sample')
+    ap.add_argument('--holdout', type=int, default=0, metavar='N',
+                    help='never draw the last N utterances of the corpus: the set `python -m tacotron_amd.evaluate --holdout N` scores')
     return ap.parse_args(argv)
 
 
@@ -273,4 +290,4 @@ if __name__ == '__main__':
     c.restore = a.restore
     c.save_path = 'debug' if a.debug else '%s/tacotron' % a.train_set
     print('Building Tacotron')
-    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log)
+    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log, holdout=a.holdout)
