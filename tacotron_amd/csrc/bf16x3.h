@@ -29,13 +29,6 @@ __device__ __forceinline__ void split2(float x0, float x1, unsigned& h, unsigned
   l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
 }
 __device__ __forceinline__ Pl3 split8(float f0, float f1, float f2, float f3, float f4, float f5, float f6, float f7) {
-#ifdef GEMM2_LAB_NOSPLIT   // timing lab: no VALU work at all (results are garbage)
-  Pl3 g;
-  g.h = u32x4{__float_as_uint(f0), __float_as_uint(f1), __float_as_uint(f2), __float_as_uint(f3)};
-  g.m = u32x4{__float_as_uint(f4), __float_as_uint(f5), __float_as_uint(f6), __float_as_uint(f7)};
-  g.l = g.h;
-  return g;
-#endif
   unsigned h[4], m[4], l[4];
   split2(f0, f1, h[0], m[0], l[0]);
   split2(f2, f3, h[1], m[1], l[1]);
@@ -50,20 +43,7 @@ __device__ __forceinline__ Pl3 split8(float f0, float f1, float f2, float f3, fl
 __device__ __forceinline__ f32x16 mfma_bf(const u32x4& a, const u32x4& b, const f32x16& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-// acc += a * b over the lanes' 16 k-slots, smallest terms first
-__device__ __forceinline__ void mfma6(f32x16& acc, const Pl3& a, const Pl3& b) {
-#ifdef GEMM2_LAB_NOMFMA    // timing lab: the planes are formed and dropped (results are garbage)
-  asm volatile("" ::"v"(a.h), "v"(a.m), "v"(a.l), "v"(b.h), "v"(b.m), "v"(b.l));
-  return;
-#endif
-  acc = mfma_bf(a.l, b.h, acc);
-  acc = mfma_bf(a.h, b.l, acc);
-  acc = mfma_bf(a.m, b.m, acc);
-  acc = mfma_bf(a.m, b.h, acc);
-  acc = mfma_bf(a.h, b.m, acc);
-  acc = mfma_bf(a.h, b.h, acc);
-}
-// Two-accumulator form (round 6, the default of both kernels; -DTACO_BF16X_ACC1 = one accumulator, rounds 5 / early 6): the five
+// Two-accumulator form (round 6 in both kernels; rounds 5 / early 6 had one accumulator): the five
 // low-order plane products go to `lo`, h h to `hi`; the kernels add the two once behind their k-loop.  The matrix pipe rounds every
 // product onto the grid of the accumulator it is added to (bf16x_max_chain below): against `lo` -- ~2^-7 of `hi` -- the l h / h l
 // products (2^-16 of a product) keep ~20 more bits than against the full sum, and `hi` only ever receives 16-bit products.

@@ -117,12 +117,9 @@ __device__ __forceinline__ bool spin_fail_uniform(unsigned& spin, const Xc& X) {
       return true;
     }
   }
-#ifndef TACO_POLL_SLEEP
-#define TACO_POLL_SLEEP 1
-#endif
   // (measured on the wave-uniform loop, profiles/r05_unipoll_knobs.txt: sleeping only on long waits, or not at all, gains 0.05 us
   //  per step in the forward kernel and LOSES 0.13 in the BPTT kernel -- its re-polls compete with the stash prefetch for the L2)
-  if (TACO_POLL_SLEEP > 0) __builtin_amdgcn_s_sleep(TACO_POLL_SLEEP);
+  __builtin_amdgcn_s_sleep(1);
   return false;
 }
 __device__ __forceinline__ bool spin_fail(unsigned& spin, const Xc& X) {
@@ -189,26 +186,6 @@ __device__ __forceinline__ int opaque_tid() {
 // Epilogue operands (bias, gate, previous state: LDS) are read IN FRONT of a round's mat-vec and kept alive across it by an opaque
 // use behind it: inside the result lanes' branch -- where the compiler sinks them -- each read is a full LDS round trip on the
 // round's critical chain (mat-vec -> reduction -> [read bias] -> activation -> [read u, h] -> blend -> publish).
-#if !defined(TACO_NO_SHADOW_C) && !defined(TACO_NO_SHADOW)
-constexpr bool kShadowC = true;       // rounds G1 / G2 of the forward kernel: input half of the candidate mat-vec in the poll shadow (round 6, late)
-#else
-constexpr bool kShadowC = false;
-#endif
-#if !defined(TACO_NO_SHADOW_O) && !defined(TACO_NO_BWD_SHADOW) && !defined(TACO_NO_SHADOW)
-constexpr bool kBwdShadowO = true;    // BPTT round DQ's gather: the d out / dx rows of round OUT's mat-vec in its shadow (round 6, late)
-#else
-constexpr bool kBwdShadowO = false;
-#endif
-#if !defined(TACO_NO_PIN_SHADOW)
-constexpr bool kPinShadow = true;     // -DTACO_NO_PIN_SHADOW: A/B builds
-#else
-constexpr bool kPinShadow = false;
-#endif
-#if !defined(TACO_NO_EPI_PRELOAD)
-constexpr bool kEpiPreload = true;    // -DTACO_NO_EPI_PRELOAD: reads at their use sites (A/B builds)
-#else
-constexpr bool kEpiPreload = false;
-#endif
 __device__ __forceinline__ void keep_alive(float& a) { asm volatile("" : "+v"(a)); }
 __device__ __forceinline__ void keep_alive(float& a, float& b) { asm volatile("" : "+v"(a), "+v"(b)); }
 __device__ __forceinline__ void keep_alive(float& a, float& b, float& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
@@ -225,17 +202,12 @@ constexpr bool kShadow = true;    // -DTACO_NO_SHADOW: the whole mat-vec in its 
 #else
 constexpr bool kShadow = false;
 #endif
+constexpr bool kShadowC = kShadow;       // rounds G1 / G2 of the forward kernel: input half of the candidate mat-vec in the poll shadow (round 6, late)
+constexpr bool kBwdShadowO = kShadow;    // BPTT round DQ's gather: the d out / dx rows of round OUT's mat-vec in its shadow (round 6, late)
 // round E's shadow (the [cell_output ; h1] rows of the next G0): bit 0 = the x mat-vec's part, bits 1-2 = the gates' part:
 // 2 = all of it (rows >= 128; 13 weight registers -- measured: spills), 4 = its first five registers only (the cell_output rows)
-#ifndef TACO_ESHADOW
-#define TACO_ESHADOW 5
-#endif
-constexpr int kEShadow = kShadow ? TACO_ESHADOW : 0;
-#if !defined(TACO_NO_BWD_SHADOW)
-constexpr bool kBwdShadow = kShadow;   // the BPTT kernel's shadow (dup half of G_l in round C_l's gather); -DTACO_NO_BWD_SHADOW: A/B
-#else
-constexpr bool kBwdShadow = false;
-#endif
+constexpr int kEShadow = kShadow ? 5 : 0;
+constexpr bool kBwdShadow = kShadow;   // the BPTT kernel's shadow (dup half of G_l in round C_l's gather)
 #if !defined(TACO_NO_GROUPED_FANDQ)
 constexpr bool kGroupedFanDq = true;   // FAN / DQ rounds of the BPTT kernel: one reduce-scatter for all slots / rows; -DTACO_NO_GROUPED_FANDQ: round 3's wave sums
 #else
@@ -261,12 +233,8 @@ constexpr bool kTanhSplit = false;
 // The BPTT kernel's energy backward uses the same factors (1 - tanh^2 = 4 r (1 - r), which unlike 1 - th * th does not cancel near
 // saturation), as TWO unswitched passes chosen by one wave-uniform branch per step: with the exact-form fallback INSIDE the
 // (memory row, batch row) loop the kernel got slower (13.55 -> 13.95 us per step), as two passes faster (13.61 -> 13.50;
-// profiles/r05_tanh_ab.txt).  -DTACO_NO_TANH_SPLIT_BWD: the sum form (A/B builds).
-#if !defined(TACO_NO_TANH_SPLIT_BWD) && !defined(TACO_NO_TANH_SPLIT)
-constexpr bool kTanhSplitB = true;
-#else
-constexpr bool kTanhSplitB = false;
-#endif
+// profiles/r05_tanh_ab.txt).
+constexpr bool kTanhSplitB = kTanhSplit;
 constexpr float kTwoLog2e = 2.8853900817779268f;
 constexpr float kTanhBound = 8.f;
 __device__ __forceinline__ float exp2_2x(float x) { return __builtin_amdgcn_exp2f(kTwoLog2e * x); }   // exp(2 x)
@@ -521,23 +489,15 @@ __device__ __forceinline__ XV<R> lds_rows(const float* xp) {
   }
   return o;
 }
-// mat-vecs of at most this many rows per lane issue ALL their reads in one burst (0: never).  Measured in round 4 (same-box A/B,
+// No mat-vec issues ALL its reads in one burst, however few rows per lane it has.  Measured in round 4 (same-box A/B,
 // profiles/r04_dec_ab.txt): 4 changes nothing, 8 is SLOWER (fwd 12.12 -> 12.34 us per step) although no register is spilled -- the
 // reads of eight waves queue on the CU's one LDS pipe either way, and a burst only delays the first FMA.
-#ifndef TACO_MV_BURST
-#define TACO_MV_BURST 0
-#endif
-constexpr int kMvBurst = TACO_MV_BURST;
 // x: LDS vector laid out [k][R].  The k loop is software-pipelined in chunks of CH rows (the next chunk's ds_reads are issued in
 // front of the current chunk's FMAs) with scheduling barriers at the chunk boundaries: left alone, hipcc hoists ALL KPL reads
 // of a mat-vec to its head (KPL x R live registers; with the resident weights that spilled ~500 registers to scratch).
 template <int R, int KPL, int LPC, int CHX = 0>
 __device__ __forceinline__ void mv(const WReg<KPL>& r, const float* x, int lk, Acc<R>& a) {
-#ifdef TACO_MV_CH
-  constexpr int CH = CHX ? CHX : TACO_MV_CH;
-#else
-  constexpr int CH = CHX ? CHX : (KPL <= kMvBurst ? KPL : (R == 4 ? 2 : 4));
-#endif
+  constexpr int CH = CHX ? CHX : (R == 4 ? 2 : 4);
   constexpr int NCH = (KPL + CH - 1) / CH;
   const float* xb = x + lk * R;
   XV<R> cur[CH], nxt[CH];
@@ -799,11 +759,7 @@ struct Lane {
   __device__ __forceinline__ Lane() {
     tid = opaque_tid();
     lane = tid & 63;
-#if defined(TACO_SWAVE)
-    wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: what depends on it alone is scalar code (branches, not exec masks)
-#else
     wave = tid >> 6;
-#endif
     lk = lane & (LPC - 1);
     rho = rs_rho<R, LPC>(lk);
     res = rho >= 0;
@@ -959,13 +915,7 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
   __syncthreads();
 
   float* const H1 = U0 + KA * R;     // h of GRU-1 lives behind [p2 ; out]
-#ifdef TACO_P_NOSTASH
   float* const stash = a.stash;
-  const bool kNoStash = true;
-#else
-  float* const stash = a.stash;
-  const bool kNoStash = false;
-#endif
   // Batch row this lane STORES for when it is the result lane (rs_rho) of a valid row, else -1; one value per
   // column-group width.  Launch constants: three registers for the whole kernel instead of two select chains per store site.
   int sb64, sb32, sbO;
@@ -974,7 +924,6 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
     sb64 = (r64 >= 0 && rsel<R>(valid, r64)) ? rsel<R>(brow, r64) : -1;
     sb32 = (r32 >= 0 && rsel<R>(valid, r32)) ? rsel<R>(brow, r32) : -1;
     sbO = (rO >= 0 && rsel<R>(valid, rO)) ? rsel<R>(brow, rO) : -1;
-    if (kNoStash) sb64 = sb32 = sbO = -1;   // timing probe: no stash / output stores at all (results are garbage)
   }
   const unsigned ldp2 = (unsigned)a.ldpre2;
   // Stash stores through a buffer descriptor (round 6, late): the lane's launch-constant byte offset in a VGPR (a lane that stores
@@ -1049,19 +998,7 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
     k1n = k2n = 1;
 #pragma unroll
     for (int q = 0; q < R; ++q) fon[q] = 0;
-#ifdef TACO_P_PARKOPAQUE   // timing probe: the parked values come out of opaque moves instead of loads (nothing folds; garbage results)
-    asm volatile("" : "+v"(p2n), "+v"(k1n), "+v"(k2n));
-#pragma unroll
-    for (int q = 0; q < R; ++q) asm volatile("" : "+v"(fon[q]));
-    if (false) {
-#elif defined(TACO_P_NOPARK)
-    if (false) {   // timing probe: no next-step input loads at all (results are garbage)
-#else
     if (TR && tn < Td) {
-#endif
-#ifdef TACO_P_PARKHOT
-      tn = 1;   // timing probe: the same loads from lines that are L2-resident (issue cost without the miss latency; garbage results)
-#endif
       if (a.sample) {   // step tn - 1's flags: row q of step tn is fed by that step's output
         static_for<R>([&](auto Q) {
           constexpr int q = decltype(Q)::value;
@@ -1121,7 +1058,7 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
       //  pre-net rows [0, 128) and the alignment segment are left)
       Acc<R> ax = g0x, ag = g0g;
       float pbx = 0.f, pbg = 0.f, ph1 = 0.f;
-      constexpr bool kPre0 = kEpiPreload && RR == 2;   // (r = 5: with 25 + 9 weight registers of this round live the three values spill)
+      constexpr bool kPre0 = RR == 2;   // (r = 5: with 25 + 9 weight registers of this round live the three values spill)
       if constexpr (kPre0) {
         pbx = BIAS[D::b_in + n8];
         pbg = BIAS[D::b_g + n16];
@@ -1201,19 +1138,17 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
         float* const CL = l == 1 ? CAT1 : CAT2;
         Acc<R> ag = ghp;   // recurrent half: formed in the shadow of round C_{l-1}'s gather
         float pb = 0.f, ph = 0.f;
-        if constexpr (kEpiPreload) {
-          pb = BIAS[D::b_g + l * 768 + n8 + (M.lane >> 5) * kDec];
-          ph = HL[n8 * R + M.rho];
-        }
+        pb = BIAS[D::b_g + l * 768 + n8 + (M.lane >> 5) * kDec];
+        ph = HL[n8 * R + M.rho];
         if constexpr (kShadow) mv_part<R, 16, 32, 0, 8>(l == 1 ? wg1 : wg2, CL, M.lk, ag);
         else mv<R, 16, 32>(l == 1 ? wg1 : wg2, CL, M.lk, ag);
-        if constexpr (kEpiPreload) keep_alive(pb, ph);
+        keep_alive(pb, ph);
         col_sum_all<R, 32>(ag);
         float gg = 0.f, gv = 0.f;
         if (M.res) {
-          gg = sigmoid_fast(pick<R>(ag, M.rho) + (kEpiPreload ? pb : BIAS[D::b_g + l * 768 + n8 + (M.lane >> 5) * kDec]));
+          gg = sigmoid_fast(pick<R>(ag, M.rho) + pb);
           if (M.lane < 32) {
-            gv = gg * (kEpiPreload ? ph : HL[n8 * R + M.rho]);
+            gv = gg * ph;
             CIN[(kDec + n8) * R + M.rho] = gv;
             put_granule<R>(X, X3_G + (l - 1) * 512, n8, M.rho, gv);
           } else {
@@ -1248,18 +1183,14 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
         ac.zero();
         if (kShadowC && l > 0) ac = acp;
         float pb = 0.f, pu = 0.f, ph = 0.f, px = 0.f;
-        if constexpr (kEpiPreload) {
-          pb = BIAS[D::b_c + l * 768 + n8];
-          pu = US[n8 * R + L.rho];
-          ph = HL[n8 * R + L.rho];
-          if (l == 2) px = XS[n8 * R + L.rho];
-        }
+        pb = BIAS[D::b_c + l * 768 + n8];
+        pu = US[n8 * R + L.rho];
+        ph = HL[n8 * R + L.rho];
+        if (l == 2) px = XS[n8 * R + L.rho];
         if (kShadowC && l > 0) mv_part<R, 8, 64, 4, 8>(l == 1 ? wc1 : wc2, CIN, L.lane, ac);
         else mv<R, 8, 64>(l == 0 ? wc0 : (l == 1 ? wc1 : wc2), CIN, L.lane, ac);
-        if constexpr (kEpiPreload) {
-          if (l == 2) keep_alive(pb, pu, ph, px);
-          else keep_alive(pb, pu, ph);
-        }
+        if (l == 2) keep_alive(pb, pu, ph, px);
+        else keep_alive(pb, pu, ph);
         col_sum_all<R, 64>(ac);
         auto hput = [&](int n, int q, float hn) {
           const int o_hl = l == 0 ? D::o_u0 + KA * R : (l == 1 ? D::o_cat1 : D::o_cat2) + kDec * R;
@@ -1279,12 +1210,12 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
         };
         float cc = 0.f, hn = 0.f, yy = 0.f;
         if (L.res) {
-          cc = tanh_fast(pick<R>(ac, L.rho) + (kEpiPreload ? pb : BIAS[D::b_c + l * 768 + n8]));
-          const float u = kEpiPreload ? pu : US[n8 * R + L.rho];
-          hn = u * (kEpiPreload ? ph : HL[n8 * R + L.rho]) + (1.f - u) * cc;
-          if (l == 2) yy = (kEpiPreload ? px : XS[n8 * R + L.rho]) + hn;
+          cc = tanh_fast(pick<R>(ac, L.rho) + pb);
+          const float u = pu;
+          hn = u * ph + (1.f - u) * cc;
+          if (l == 2) yy = px + hn;
           put_granule<R>(X, X3_C + l * 256, n8, L.rho, hn);
-          if (l == 2 && kEpiPreload) {
+          if (l == 2) {
             smem[D::o_cat2 + kDec * R + n8 * R + L.rho] = hn;
             smem[D::o_ys + n8 * R + L.rho] = yy;
           } else {
@@ -1300,10 +1231,10 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
             const int lk = opaque_tid() & 31;
             if (l == 0) mv_part<R, 16, 32, 8, 16>(wg1, CAT1, lk, ghp);
             else mv_part<R, 16, 32, 8, 16>(wg2, CAT2, lk, ghp);
-            if constexpr (kPinShadow) pin<R>(ghp);
+            pin<R>(ghp);
           }
           if constexpr (R >= 2 && MU == 1) {
-            if (l == 2 && kEpiPreload) {
+            if (l == 2) {
               if (S.pend[0]) {
                 xsp[0] = XS[S.un[0] * R + S.uh[0] * 2];
                 xsp[1] = XS[S.un[0] * R + S.uh[0] * 2 + 1];
@@ -1334,9 +1265,9 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
       Acc<R> ao;
       ao.zero();
       float pbo = 0.f;
-      if constexpr (kEpiPreload) pbo = BIAS[D::b_o + nO];
+      pbo = BIAS[D::b_o + nO];
       mv<R, D::KPL_O, D::LPC_O>(wo, YS, O.lk, ao);
-      if constexpr (kEpiPreload) keep_alive(pbo);
+      keep_alive(pbo);
       col_sum_all<R, D::LPC_O>(ao);
       auto oput = [&](int n, int q, float v) {
         const int i = n < kAtt ? D::o_qs + q * kAtt + n : D::o_u0 + (kPre2 + n - kAtt) * R + q;
@@ -1344,7 +1275,7 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
       };
       float yo = 0.f;
       if (O.res) {
-        yo = pick<R>(ao, O.rho) + (kEpiPreload ? pbo : BIAS[D::b_o + nO]);
+        yo = pick<R>(ao, O.rho) + pbo;
         put_granule<R>(X, X3_O, nO, O.rho, yo);
         oput(nO, O.rho, yo);
       }
@@ -1356,13 +1287,13 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
         Acc<R> ap;
         ap.zero();
         float pbp = 0.f;
-        if constexpr (kEpiPreload) pbp = BIAS[D::b_p1o + n8];
+        pbp = BIAS[D::b_p1o + n8];
         mv<R, 4, 64>(wp1, YS, L.lane, ap);
-        if constexpr (kEpiPreload) keep_alive(pbp);
+        keep_alive(pbp);
         col_sum_all<R, 64>(ap);
         if (L.res) {
           // layer 1 of a step fed by this step's output, straight from (x + h3) with Wo[:, last frame] W1
-          yp = fmaxf(pick<R>(ap, L.rho) + (kEpiPreload ? pbp : BIAS[D::b_p1o + n8]), 0.f) * (a.keep1 ? (k1n ? 2.f : 0.f) : 1.f);
+          yp = fmaxf(pick<R>(ap, L.rho) + pbp, 0.f) * (a.keep1 ? (k1n ? 2.f : 0.f) : 1.f);
           P1[n8 * R + L.rho] = yp;
           put_granule<R>(X, X3_P1, n8, L.rho, yp);
         }
@@ -1464,12 +1395,12 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
         Acc<R> ap;
         ap.zero();
         float pb2 = 0.f;
-        if constexpr (kEpiPreload) pb2 = BIAS[D::b_p2 + n4];
+        pb2 = BIAS[D::b_p2 + n4];
         mv<R, 4, 64>(wp2, P1, L.lane, ap);
-        if constexpr (kEpiPreload) keep_alive(pb2);
+        keep_alive(pb2);
         col_sum_all<R, 64>(ap);
         if (L.res && L.wave < 4) {
-          y2 = fmaxf(pick<R>(ap, L.rho) + (kEpiPreload ? pb2 : BIAS[D::b_p2 + n4]), 0.f) * (a.keep2 ? (k2n ? 2.f : 0.f) : 1.f);
+          y2 = fmaxf(pick<R>(ap, L.rho) + pb2, 0.f) * (a.keep2 ? (k2n ? 2.f : 0.f) : 1.f);
           put_granule<R>(X, X3_P2, n4, L.rho, y2);
           if (rsel<R>(from_out, L.rho)) U0[n4 * R + L.rho] = y2;
         }
@@ -1491,13 +1422,13 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
           if constexpr (D::kES & 1) {
             g0x.zero();
             mv_part<R, D::KPLX, 64, 2, D::KPLX>(wx, U0, tl & 63, g0x);
-            if constexpr (kPinShadow) pin<R>(g0x);
+            pin<R>(g0x);
           }
           if constexpr (D::kES & 6) {
             typedef EShadowSplit<D::KPLG0, D::kES> ES_;
             g0g.zero();
             mv_part<R, D::KPLG0, 32, ES_::lo, ES_::hi>(wg0, U0, tl & 31, g0g);
-            if constexpr (kPinShadow) pin<R>(g0g);
+            pin<R>(g0g);
           }
         }
         gather_end<R, MU>(
@@ -1512,11 +1443,7 @@ __global__ __launch_bounds__(NT) void decoder3_fwd_kernel(DecFwdArgs a) {
             [&](int n, int q) { return n < kPre2 || n - kPre2 < rsel<R>(len, q); });
       }
       tstamp(X);   // E: gathered (before the deferred stores / next-step prefetch)
-#ifdef TACO_P_NOTAIL
-      if (false) {   // timing probe: no deferred stores behind round E (the stash misses p2 of sampled rows, prein is not written)
-#else
       if (TR && has_next) {
-#endif
         // (column n4 = peer 4 + wave of the wave's unit slot 8 peer + wave: shift the lane's offset by the difference)
         if (L.wave < 4) st_store(y2, (sb64 >= 0 && rsel<R>(from_out, L.rho)) ? vo64 - (peer * 4) * 4 : kOOBs, (t + 1) * (kStRec * 4) + kStP2 * 4);
       }
@@ -1782,9 +1709,6 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
     const int r64 = rs_rho<R, 64>(lane), r32 = rs_rho<R, 32>(lane & 31);
     sb64 = (r64 >= 0 && rsel<R>(valid, r64)) ? rsel<R>(brow, r64) : -1;
     sb32 = (r32 >= 0 && rsel<R>(valid, r32)) ? rsel<R>(brow, r32) : -1;
-#ifdef TACO_P_NOSTASH
-    sb64 = sb32 = -1;   // timing probe: no gradient-stash stores at all (results are garbage)
-#endif
   }
   float* const gst = a.gstash;
   auto own = [&](int slot, int wv, int rho) -> float& { return OWN[(slot * 8 + wv) * R + rho]; };
@@ -1792,7 +1716,7 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
   // ---- prefetch of the next processed step's inputs (registers; landed in LDS at the head of that step) ----
   // LOADER WAVES.  Vector-memory loads return in order, so a poll issued behind a prefetch load cannot return before it: with every
   // thread prefetching, the first exchange round after the prefetch paid the whole HBM round trip of the stash reads (1.2 us of
-  // the 13.2 us step; probe build TACO_P_NOPREF).  Waves 4-7 are therefore the only ones that prefetch -- during the softmax
+  // the 13.2 us step).  Waves 4-7 are therefore the only ones that prefetch -- during the softmax
   // backward, which occupies waves < R only -- and they sit out the polling of the NEXT round (DQ: waves 0-3 poll for everybody),
   // so their loads have the softmax, the DQ round and round OUT's mat-vec to land before they poll again.
   // A loader thread owns a fixed job list (source = base + tp * stride, LDS destination), set up once:
@@ -1948,7 +1872,7 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
         ap.zero();
         float pm = smem[D::o_p2m + (L.wave & 3) * R + L.rho];
         mv<R, 4, 64>(wdp2, VO + (R80 + 2 * kAtt) * R, L.lane, ap);
-        if constexpr (kEpiPreload) keep_alive(pm);
+        keep_alive(pm);
         col_sum_all<R, 64>(ap);
         if (L.res && L.wave < 4) {
           const int n4 = peer * 4 + L.wave;
@@ -1971,9 +1895,7 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
     lds_barrier();
     tstamp(X);   // 2: FAN done
     // next processed step's inputs: the loader waves issue them while waves < R run the softmax backward
-#ifndef TACO_P_NOPREF   // (timing probe: no next-step input loads at all -- results are garbage)
     if (loader && t > 0) prefetch(t - 1);
-#endif
     // ---- 2. softmax backward: de = al * (dal - sum al dal)   (wave rho handles row rho) ----
     {
       const Lane<R, 64> L;
@@ -2098,12 +2020,8 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
       // longest of the step (0.8-0.9 us against 0.3-0.45).  With eight waves the loader waves wait for their prefetch first (one
       // in-order counter), which by now has had the softmax backward and the energy backward to land: BPTT 10.63 -> 10.34 us per
       // step, same box (profiles/r06_dec_chain_ab.txt).  Issuing the prefetch at the step start and sitting out round FAN's
-      // polling instead is slower (10.72).  -DTACO_DQ_HALFPOLL: the previous form (A/B builds).
-#ifndef TACO_DQ_HALFPOLL
+      // polling instead is slower (10.72).
       constexpr int NPQ = NT;
-#else
-      constexpr int NPQ = NT / 2;
-#endif
       if constexpr (!kShO) {
         gather<R, (512 * (R >= 2 ? R / 2 : 1) + NPQ - 1) / NPQ, NPQ>(
             X, Y3_DQ, has_next ? 512 : 256, [&](int n) { return ((n & 255) >> 3) == peer; },
@@ -2158,12 +2076,12 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
       Acc<R> ao;
       ao.zero();
       if constexpr (kShO) ao = aop;
-      // (epilogue operands in front of the mat-vec: kEpiPreload)
+      // (epilogue operands in front of the mat-vec: see keep_alive)
       float pdh = own(D::w_dh + 2, L.wave, L.rho), puu = own(D::w_rec + 4 * 2 + 1, L.wave, L.rho), pc = own(D::w_rec + 4 * 2 + 2, L.wave, L.rho),
             php = own(D::w_rec + 4 * 2 + 3, L.wave, L.rho);
       if constexpr (kShO) mv_part<R, D::KPL_O, 64, D::J_A, D::J_B>(wout, VO, L.lane, ao);
       else mv<R, D::KPL_O, 64>(wout, VO, L.lane, ao);
-      if constexpr (kEpiPreload) keep_alive(pdh, puu, pc, php);
+      keep_alive(pdh, puu, pc, php);
       col_sum_all<R, 64>(ao);
       if (L.res) {
         const float dy = pick<R>(ao, L.rho);
@@ -2188,7 +2106,7 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
         float rr = own(D::w_rec + 4 * l + 0, M.wave, M.rho), uu = own(D::w_rec + 4 * l + 1, M.wave, M.rho),
               hp = own(D::w_rec + 4 * l + 3, M.wave, M.rho), pdht = own(D::w_dht, M.wave, M.rho);
         mv<R, 8, 32>(l == 0 ? wc0 : (l == 1 ? wc1 : wc2), DCP, M.lk, ac);
-        if constexpr (kEpiPreload) keep_alive(rr, uu, hp, pdht);
+        keep_alive(rr, uu, hp, pdht);
         col_sum_all<R, 32>(ac);
         float gr = 0.f;
         if (M.res) {
@@ -2212,7 +2130,7 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
             if (l == 0) mv_part<R, 16, 32, 8, 16>(wg0, smem + o_dgp, lk, gdp);
             else if (l == 1) mv_part<R, 16, 32, 8, 16>(wg1, smem + o_dgp, lk, gdp);
             else mv_part<R, 16, 32, 8, 16>(wg2, smem + o_dgp, lk, gdp);
-            if constexpr (kPinShadow) pin<R>(gdp);
+            pin<R>(gdp);
           }
           gather_end<R, MU>(X, S, OneRegion{Y3_GR + l * 256}, [&](int n, int q, float v) { smem[o_dgp + n * R + q] = v; });
         }
@@ -2231,10 +2149,8 @@ __device__ __forceinline__ void decoder3_bwd_body(const DecBwdArgs& a) {
         float puu = own(D::w_rec + 4 * lb + 1, M.wave, M.rho), pc = own(D::w_rec + 4 * lb + 2, M.wave, M.rho), php = own(D::w_rec + 4 * lb + 3, M.wave, M.rho);
         if constexpr (kBwdShadow) mv_part<R, 16, 32, 0, 8>(l == 0 ? wg0 : (l == 1 ? wg1 : wg2), smem + o_dgp, M.lk, ag);
         else mv<R, 16, 32>(l == 0 ? wg0 : (l == 1 ? wg1 : wg2), smem + o_dgp, M.lk, ag);
-        if constexpr (kEpiPreload) {
-          keep_alive(pa, pb);
-          if (l > 0) keep_alive(puu, pc, php);
-        }
+        keep_alive(pa, pb);
+        if (l > 0) keep_alive(puu, pc, php);
         col_sum_all<R, 32>(ag);
         float dxv = 0.f;
         if (M.res) {

@@ -259,16 +259,12 @@ __global__ __launch_bounds__(256, 2) void conv_gemm2_kernel(Gemm2Args G) {
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
-#ifndef TACO_BF16X_ACC1
   f32x16 acc_lo[BX ? 4 : 1];   // bf16x3: the five low-order plane products of every sub-tile (bf16x3.h mfma6_2); added to acc behind the k-loop
 #pragma unroll
   for (int j = 0; j < (BX ? 4 : 1); ++j)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc_lo[j][e] = 0.f;
 #define MF6(j, a, b) mfma6_2(acc[j], acc_lo[j], a, b)
-#else
-#define MF6(j, a, b) mfma6(acc[j], a, b)
-#endif
 
   const int li = lane & 31, kh = lane >> 5;
   const int arow = wave * 32 + li;
@@ -306,9 +302,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm2_kernel(Gemm2Args G) {
       //  the only fixed point is the wait + sched_barrier at the head of the next step -- guide rule 18)
       if (s + 2 < NSTEP) b4[(s + 2) % 3] = dsr128<(8 * ((s + 2) >> 2) + ((s + 2) & 3)) * TN * 4>(bb);
       if (c == 1 && p + 1 < NP) a4[(p + 1) & 1] = dsr128<0>(sb + a_off[p + 1]);
-#ifndef GEMM2_LAB_NODMA
       if (s < NLD && fill) issue_piece(s, fill_stage);
-#endif
     });
   };
 
@@ -332,12 +326,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm2_kernel(Gemm2Args G) {
     });
     __builtin_amdgcn_sched_barrier(0);
     MF6(2, pa_c, pb2_c);
-#ifndef GEMM2_LAB_NODMA
     if (fill) {
 #pragma unroll
       for (int g = 0; g < NLD; ++g) issue_piece(g, fill_stage);
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     wait_lgkm<0>();
     __builtin_amdgcn_sched_barrier(0);
@@ -384,51 +376,33 @@ __global__ __launch_bounds__(256, 2) void conv_gemm2_kernel(Gemm2Args G) {
       constexpr int j = decltype(jc)::value;
       static_for<0, 3>([&](auto pc) {
         constexpr int pp = decltype(pc)::value;
-#ifdef GEMM2_LAB_NOBREAD   // timing lab: no B fragment reads (results are garbage)
-        pl[j][pp] = u32x4{(unsigned)bb, 0x3f803f80u, (unsigned)j, (unsigned)pp};
-#else
         pl[j][pp] = __builtin_bit_cast(u32x4, dsr128<(4 * pp + j) * 1024>(bb));
-#endif
       });
     });
     __builtin_amdgcn_sched_barrier(0);
-#if !defined(TACO_BF16X_ACC1) && !defined(TACO_GEMM2_NO_PAIR23)
     // Sub-tiles 2 and 3 INTERLEAVED (round 6, late): as two blocks of six, five MFMAs of each block were back-to-back on ONE accumulator
     // with the DMA issues / the split's VALU between them -- an instruction between two MFMAs on the same accumulator costs ~40
     // cycles, between MFMAs on different accumulators ~6 (MI355X guide).  Every accumulator still receives its products in mfma6_2's
-    // order: results are bit-identical.  -DTACO_GEMM2_NO_PAIR23: the previous form.
+    // order: results are bit-identical.
     acc_lo[2] = mfma_bf(pa_c.l, qb2_c.h, acc_lo[2]);
     acc_lo[3] = mfma_bf(pa_c.l, qb3_c.h, acc_lo[3]);
     acc[2] = mfma_bf(pa_c.h, qb2_c.h, acc[2]);
     acc[3] = mfma_bf(pa_c.h, qb3_c.h, acc[3]);
     acc_lo[2] = mfma_bf(pa_c.h, qb2_c.l, acc_lo[2]);
     acc_lo[3] = mfma_bf(pa_c.h, qb3_c.l, acc_lo[3]);
-#else
-    MF6(2, pa_c, qb2_c);
-#endif
-#ifndef GEMM2_LAB_NODMA
     if (fill) {
 #pragma unroll
       for (int g = 0; g < NLD; ++g) issue_piece(g, fill_stage);
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifdef GEMM2_LAB_NOBREAD
-    wait_lgkm<0>();
-#else
     wait_lgkm<12>();                 // the two A reads were issued first
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#if !defined(TACO_BF16X_ACC1) && !defined(TACO_GEMM2_NO_PAIR23)
     acc_lo[2] = mfma_bf(pa_c.m, qb2_c.m, acc_lo[2]);      // (still the previous tile's A planes)
     acc_lo[3] = mfma_bf(pa_c.m, qb3_c.m, acc_lo[3]);
     acc_lo[2] = mfma_bf(pa_c.m, qb2_c.h, acc_lo[2]);
     acc_lo[3] = mfma_bf(pa_c.m, qb3_c.h, acc_lo[3]);
     acc_lo[2] = mfma_bf(pa_c.h, qb2_c.m, acc_lo[2]);
     acc_lo[3] = mfma_bf(pa_c.h, qb3_c.m, acc_lo[3]);
-#else
-    MF6(3, pa_c, qb3_c);      // (still the previous tile's A planes)
-#endif
     const Pl3 pa_n = split8(ra0[0], ra0[1], ra0[2], ra0[3], ra1[0], ra1[1], ra1[2], ra1[3]);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {    // one MFMA, then its share of the 44 split instructions
@@ -472,9 +446,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm2_kernel(Gemm2Args G) {
   for (; it + NS - 1 < nit; ++it) {   // steady state: tile it + NS - 1 refills the stage tile it - 1 just vacated
     // this wave's share of tile `it` has landed once at most the younger tiles' DMA instructions are outstanding
     wait_vm<NLD*(NS - 2)>();
-#ifndef GEMM2_LAB_NOBAR
     __builtin_amdgcn_s_barrier();   // every wave's share has landed AND every wave has finished reading tile it - 1
-#endif
     asm volatile("" ::: "memory");
     run_tile(it % NS, (it + NS - 1) % NS, std::true_type{});
     advance();
@@ -493,12 +465,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm2_kernel(Gemm2Args G) {
     MF6(2, pa_c, qb2_c);
     MF6(3, pa_c, qb3_c);
   }
-#ifndef TACO_BF16X_ACC1
   if constexpr (BX != 0) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] += acc_lo[j];
   }
-#endif
 #undef MF6
   wait_vm<0>();   // (nothing outstanding by construction; keeps the invariant explicit before the epilogue's ordinary loads)
 

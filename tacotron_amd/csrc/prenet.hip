@@ -21,11 +21,6 @@ namespace {
 #else
 #define PN_STAMP(i) do { } while (0)
 #endif
-#ifdef TACO_PN_P_NOW   // timing probe (tools/ab_build.sh): no weight loads at all -- results are garbage
-#define PN_W(x) (0.001f * (float)(j + s))
-#else
-#define PN_W(x) (x)
-#endif
 
 constexpr int PB = 32;          // rows per workgroup
 constexpr int PPAD = PB + 1;    // activation pitch, feature-major
@@ -50,7 +45,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_kernel(PrenetArgs a) {
 #pragma unroll
     for (int j = 0; j < PCK; ++j)
 #pragma unroll
-      for (int s = 0; s < S1; ++s) wr[0][s][j] = PN_W(src[(int64_t)2 * j * N1 + 32 * s]);
+      for (int s = 0; s < S1; ++s) wr[0][s][j] = src[(int64_t)2 * j * N1 + 32 * s];
   }
   // ---- stage 0: input tile -> aT (backward: through the ReLU / dropout of layer 2, and out to dz2) ----
   {
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_kernel(PrenetArgs a) {
 #pragma unroll
       for (int j = 0; j < PCK; ++j)
 #pragma unroll
-        for (int s = 0; s < S1; ++s) wr[set][s][j] = PN_W(src[(int64_t)2 * j * N1 + 32 * s]);
+        for (int s = 0; s < S1; ++s) wr[set][s][j] = src[(int64_t)2 * j * N1 + 32 * s];
     };
 #pragma unroll
     for (int s = 0; s < S1; ++s)
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_kernel(PrenetArgs a) {
 #pragma unroll
         for (int j = 0; j < PCK; ++j)
 #pragma unroll
-          for (int s = 0; s < S2; ++s) wr[(c + 1) & 1][s][j] = PN_W(src[(int64_t)2 * j * N2 + 32 * s]);
+          for (int s = 0; s < S2; ++s) wr[(c + 1) & 1][s][j] = src[(int64_t)2 * j * N2 + 32 * s];
       }
       __builtin_amdgcn_sched_barrier(0);
       float av[PCK];
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void mlp2_kernel(PrenetArgs a) {
 #pragma unroll
       for (int j = 0; j < PCK; ++j)
 #pragma unroll
-        for (int s = 0; s < S2; ++s) wr[set][s][j] = PN_W(src[(int64_t)2 * j * N2 + 32 * s]);
+        for (int s = 0; s < S2; ++s) wr[set][s][j] = src[(int64_t)2 * j * N2 + 32 * s];
     };
 #pragma unroll
     for (int s = 0; s < S2; ++s)

@@ -49,15 +49,21 @@ def csrc_files():
     return sorted(glob.glob(os.path.join(CSRC, '*')))
 
 
+# the compile-time names: each is selected by build.sh (the probe and previous-decoder libraries) or by a tool
+COMPILE_TIME = {'TACO_DEC_PROBES', 'TACO_NO_RS', 'TACO_NO_POLL128', 'TACO_NO_SHADOW', 'TACO_NO_GROUPED_FANDQ', 'TACO_NO_UNIPOLL',
+                'TACO_NO_TANH_SPLIT', 'TACO_PN_TRACE', 'TACO_GRU_TRACE'}
+
+
 def compile_time_names():
-    """Names that csrc/ tests in a preprocessor condition."""
+    """Every identifier that csrc/ tests in a preprocessor condition, whatever its prefix."""
     names = set()
     for path in csrc_files():
         if path.endswith(('.hip', '.h')):
             for line in open(path):
-                if re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b', line):
-                    names.update(NAME.findall(line))
-    return names
+                m = re.match(r'\s*#\s*(if|ifdef|ifndef|elif)\b(.*)', line)
+                if m:
+                    names.update(re.findall(r'\b[A-Za-z_]\w*', m.group(2).split('//')[0]))
+    return names - {'defined'}
 
 
 def test_table_is_the_pinned_one():
@@ -179,6 +185,17 @@ def test_names_in_tests_tools_and_drivers_exist():
         for name in set(NAME.findall(open(path).read())) - known:
             unknown.setdefault(name, []).append(os.path.relpath(path, ROOT))
     assert not unknown, 'names that nothing reads, tests or defines: %r' % unknown
+
+
+def test_every_compile_time_name_is_selected_by_a_build_or_a_tool():
+    """A fork that no build script, benchmark or tool compiles is code that nothing exercises: it goes, with its -D."""
+    selectors = ''.join(open(path).read() for path in (
+        [os.path.join(CSRC, 'build.sh'), os.path.join(ROOT, 'bench.py')] + glob.glob(os.path.join(ROOT, 'tools', '*.py')) +
+        glob.glob(os.path.join(ROOT, 'tools', '*.sh')) + glob.glob(os.path.join(ROOT, 'tools', 'micro', '*.hip'))))
+    names = compile_time_names()
+    unselected = sorted(n for n in names if not re.search(r'(-D|#\s*define\s+)%s\b' % re.escape(n), selectors))
+    assert not unselected, 'tested under csrc/, selected nowhere: %r' % unselected
+    assert names == COMPILE_TIME
 
 
 def test_integration_md_documents_exactly_the_switches():

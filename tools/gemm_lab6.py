@@ -1,5 +1,5 @@
 """Round-6 lab for the B-image form of conv_gemm2 (BX = 2): plain shapes, steady state, with the weight image registered.
-usage: TACO_LIB=<lab build> python tools/gemm_lab6.py      (GPU box; lab builds: tools/ab_build.sh <name> "-DGEMM2_LAB_..." gemm2)"""
+usage: TACO_LIB=<lab build> python tools/gemm_lab6.py      (GPU box)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ['TACO_BF16X_MAX_CHAIN'] = str(1 << 30)   # (the lab times the bf16x3 forms at any depth)
