@@ -324,6 +324,47 @@ int taco_debug_fabric_probe(long long* out32, void* gran4k, const void* scratch,
 int taco_denorm_unframe(const float* output, const float* stft_mean, const float* stft_std, float* spec, float* mag_t,
                         int B, int Td, int r, int C, void* stream);
 
+/* Speaking rate at synthesis (no reference counterpart: the reference speaks at the rate its model learned).  Between
+ * taco_denorm_unframe and Griffin-Lim an utterance is a magnitude matrix with no phase attached; resampling it along the frame axis
+ * changes the duration, and Griffin-Lim then finds phases consistent with the new length, so the pitch does not move.
+ *   mag_t  (B, C, F) fp32 and out (B, C, Fo) fp32, the frame index contiguous (the layout of taco_denorm_unframe's mag_t)
+ *   frames (B) int32 on the DEVICE, or NULL: F_b = clamp(frames[b] * frames_per_unit, 0, F), the product formed in 64 bits; NULL:
+ *          F_b = F.  frames_per_unit >= 1 is required either way (pass r with the lengths of taco_infer_stop)
+ *   step_q (B) int32 on the DEVICE, or NULL: the source frames advanced per output frame in units of 2^-16 -- the rate as an
+ *          integer, so that the device and a NumPy restatement agree exactly (the choice TacoStopRule made).  Used as
+ *          s_b = clamp(step_q[b], TACO_STRETCH_MIN_STEP, TACO_STRETCH_MAX_STEP); NULL: TACO_STRETCH_ONE.  The host reads nothing
+ *          from frames or step_q
+ *   frames_out (B) int32, required
+ * Per row b, exactly:
+ *   Fo_b = 0 when F_b == 0, else min(Fo, ((F_b - 1) << 16) / s_b + 1) in integer division;  frames_out[b] = Fo_b
+ *   for j < Fo_b: p = j * s_b, i = p >> 16, w = float(p & 0xFFFF) * 2^-16 (exact in fp32)
+ *     w == 0: out[b, k, j] = mag_t[b, k, i] bit for bit, and element i + 1 is NOT read (the last output frame can sit exactly on
+ *             source frame F_b - 1)
+ *     else:   out[b, k, j] = a + (w * (c - a)), a = mag_t[b, k, i], c = mag_t[b, k, i + 1]: one fp32 subtraction, one multiply and
+ *             one addition, each rounded to nearest even, nothing contracted into an FMA -- NumPy float32 gives the same bits.  The
+ *             formula for Fo_b guarantees i + 1 <= F_b - 1 here
+ *   out[b, k, j] = 0 exactly for Fo_b <= j < Fo
+ *   - every element of out and frames_out is written and nothing outside them, for any F, Fo and any alignment of mag_t and out
+ *     (one form: 4-byte accesses, 256 contiguous bytes per wave; two forms with 16-byte stores measured no faster and were deleted);
+ *   - with s_b = TACO_STRETCH_ONE and Fo >= F_b the first F_b columns are a bit-identical copy;
+ *   - columns t >= F_b of mag_t and every other row's data have no influence on row b (they may hold NaN);
+ *   - row b of a B-row call equals a B = 1, F = F_b call on a contiguous copy of the row's first F_b columns;
+ *   - no atomics: the same arguments give the same bits.
+ * One launch of B x ceil(C / 16) x ceil(Fo / 256) workgroups, no workspace, no allocation, no host synchronisation, no workgroup
+ * waits for another one: graph-capturable, and a replay follows whatever frames and step_q hold at replay time.  NULL mag_t / out /
+ * frames_out, out overlapping mag_t, B, C, F or Fo <= 0, F or Fo > TACO_STRETCH_MAX_FRAMES and frames_per_unit < 1 return
+ * TACO_EINVAL, with a message that names the argument, before anything is enqueued.  TACO_VERSION did not change with this entry
+ * point: detect it by the symbol.
+ * Not here: pitch (a warp of the bin axis moves the formants with the pitch; a formant-preserving shift needs an envelope split), a
+ * rate that varies inside an utterance, interpolation of log-magnitudes or of mel frames.  Nobody has listened to the result: the
+ * limits 0.25 and 4 are bounds of the arithmetic ((frame << 16) and j * s_b stay inside 31 bits), not recommendations. */
+#define TACO_STRETCH_ONE        65536     /* step_q of rate 1 */
+#define TACO_STRETCH_MIN_STEP   16384     /* rate 0.25: four times slower */
+#define TACO_STRETCH_MAX_STEP   262144    /* rate 4 */
+#define TACO_STRETCH_MAX_FRAMES 8192      /* F and Fo; keeps (frame << 16) inside 31 bits */
+int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q,
+                        float* out, int32_t* frames_out, int B, int C, int F, int Fo, void* stream);
+
 /* ---- corpus boundary ----------------------------------------------------------------------------------------------------- */
 /* The batch gather of the training corpus with the reference's target standardisation (data_input.py:55-65
  * `(x - mean) / std`, which the reference applies to the whole corpus on the host) fused in: the inverse of

@@ -571,6 +571,96 @@ __global__ void denorm_unframe_kernel(const float* __restrict__ out, const float
   }
 }
 
+// taco_frames_stretch: speaking rate at synthesis.  Row b of mag_t (B, C, F) is resampled along its contiguous frame axis into
+// out (B, C, Fo): output frame j sits at source position p = j * s_b in units of 2^-16 frames, i = p >> 16, w = (p & 0xFFFF) 2^-16,
+// and is a + (w * (c - a)) of the two frames around it -- three separately rounded fp32 operations (the pragma in the kernel's body
+// keeps hipcc from contracting them; __fmul_rn / __fadd_rn are plain operators in this toolchain, see dtw.hip) -- or frame i itself,
+// bit for bit and without touching frame i + 1, when w == 0.  A gather along the contiguous axis, bound by memory: lanes run
+// along j, so the stores of a wave are one contiguous run and the two loads of neighbouring lanes fall into the same or adjacent
+// lines.  A workgroup (64 x 4 threads) owns one row, kStretchBins bins and kStretchSpan output frames; a thread forms the index
+// and weight of its four frames j0 + lane + 64 u once and walks the tile's bins with them, so every load and every store of a wave
+// covers 64 consecutive output frames: 256 contiguous bytes stored, for any Fo and any alignment.  F_b, s_b and Fo_b are the same for
+// the whole workgroup and read once.  A span behind Fo_b writes zeros and loads nothing.
+// There is ONE form.  Two with 16-byte stores were measured beside it at 32 x 1025 x 360 and deleted (DESIGN.md 4b,
+// profiles/frames_stretch_store_forms.txt): a thread owning frames j0 + 4 lane .. + 3 spreads each load of a wave over 1 KiB and
+// was up to 2 x slower; this form's values turned through LDS into one 16-byte store per thread was equal within the spread.  The
+// source span is not staged in LDS: that variant was not built.
+constexpr int kStretchBins = 16;
+constexpr int kStretchSpan = 256;
+__global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                             int frames_per_unit, const int32_t* __restrict__ step_q,
+                                                             float* __restrict__ out, int32_t* __restrict__ frames_out, int C, int F,
+                                                             int Fo, int nspan, int ntile) {
+#pragma clang fp contract(off)
+  const uint32_t x = blockIdx.x;
+  const int span = (int)(x % (uint32_t)nspan);
+  const uint32_t t = x / (uint32_t)nspan;
+  const int tile = (int)(t % (uint32_t)ntile), b = (int)(t / (uint32_t)ntile);
+  int Fb = F, s = TACO_STRETCH_ONE;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  if (step_q) {
+    s = step_q[b];
+    s = s < TACO_STRETCH_MIN_STEP ? TACO_STRETCH_MIN_STEP : (s > TACO_STRETCH_MAX_STEP ? TACO_STRETCH_MAX_STEP : s);
+  }
+  int Fob = 0;
+  if (Fb > 0) {
+    const uint32_t need = ((uint32_t)(Fb - 1) << 16) / (uint32_t)s + 1u;   // (Fb <= 8192: the shift stays below 2^29)
+    Fob = need > (uint32_t)Fo ? Fo : (int)need;
+  }
+  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  s = __builtin_amdgcn_readfirstlane(s);
+  Fob = __builtin_amdgcn_readfirstlane(Fob);
+  if (span == 0 && tile == 0 && threadIdx.x == 0 && threadIdx.y == 0) frames_out[b] = Fob;
+
+  const int j0 = span * kStretchSpan, lane = threadIdx.x;
+  const int k0 = tile * kStretchBins;
+  int jj[4], i0[4], i1[4];
+  float w[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    jj[u] = j0 + lane + 64 * u;
+    // j < Fo_b: p <= (F_b - 1) << 16, so i <= F_b - 1, and i == F_b - 1 only with w == 0 -- i1 then stays i.  j >= Fo_b: frame 0 is
+    // named and nothing is loaded (j < 8192 and s <= 2^18: the product fits 32 bits either way)
+    const uint32_t p = jj[u] < Fob ? (uint32_t)jj[u] * (uint32_t)s : 0u;
+    const uint32_t frac = p & 0xFFFFu;
+    i0[u] = (int)(p >> 16);
+    i1[u] = i0[u] + (frac != 0u ? 1 : 0);
+    w[u] = (float)frac * (1.0f / 65536.0f);   // exact: 16 bits times a power of two
+  }
+  const bool live = j0 < Fob;   // (uniform over the workgroup)
+  for (int kk = threadIdx.y; kk < kStretchBins; kk += 4) {
+    const int k = k0 + kk;
+    if (k >= C) break;
+    const float* __restrict__ src = mag_t + ((int64_t)b * C + k) * F;
+    float* __restrict__ dst = out + ((int64_t)b * C + k) * Fo;
+    float y[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+      float a[4], c[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {   // all loads first
+        if (jj[u] < Fob) {
+          a[u] = src[i0[u]];
+          c[u] = src[i1[u]];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (jj[u] < Fob) {
+          const float d = c[u] - a[u];
+          const float m = w[u] * d;
+          y[u] = i1[u] != i0[u] ? a[u] + m : a[u];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (jj[u] < Fo) dst[jj[u]] = y[u];
+  }
+}
+
 // taco_corpus_batch: the forward map denorm_unframe_kernel inverts, fused into the batch gather.  out[b, e] =
 // (float(src[index[b], e]) - mean[e % C]) / stdv[e % C] over rows of `row` = Td * C elements; T = _Float16 (the corpus as
 // preprocess stores it) or float.  One IEEE subtraction and one correctly rounded division per element: the bits of NumPy's
@@ -1019,6 +1109,29 @@ extern "C" int taco_denorm_unframe(const float* out, const float* mean, const fl
   TACO_KLAUNCH(denorm_unframe_kernel, dim3((C + 31) / 32, (F + 31) / 32, B), dim3(32, 8), 0, s, out, mean, stdv, spec,
                      mag_t, Td, r, C, F);
   TACO_LAUNCH_CHECK("denorm_unframe");
+  return TACO_OK;
+}
+extern "C" int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, float* out,
+                                   int32_t* frames_out, int B, int C, int F, int Fo, void* stream) {
+  TACO_REQUIRE(mag_t, "frames_stretch: mag_t is NULL");
+  TACO_REQUIRE(out, "frames_stretch: out is NULL");
+  TACO_REQUIRE(frames_out, "frames_stretch: frames_out is NULL");
+  TACO_REQUIRE(B > 0, "frames_stretch: B=%d must be positive", B);
+  TACO_REQUIRE(C > 0, "frames_stretch: C=%d must be positive", C);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "frames_stretch: F=%d must be in 1..%d", F, TACO_STRETCH_MAX_FRAMES);
+  TACO_REQUIRE(Fo > 0 && Fo <= TACO_STRETCH_MAX_FRAMES, "frames_stretch: Fo=%d must be in 1..%d", Fo, TACO_STRETCH_MAX_FRAMES);
+  TACO_REQUIRE(frames_per_unit >= 1, "frames_stretch: frames_per_unit=%d must be >= 1", frames_per_unit);
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
+  const uint64_t rows = (uint64_t)B * (uint64_t)C;   // (< 2^62; F, Fo <= 2^13: the byte counts below fit 64 bits)
+  TACO_REQUIRE(rows <= (UINT64_MAX >> 16) / 4, "frames_stretch: B=%d x C=%d: the tensors exceed the address space", B, C);
+  TACO_REQUIRE(o0 + rows * Fo * 4 <= m0 || m0 + rows * F * 4 <= o0, "frames_stretch: out overlaps mag_t");
+  const int nspan = cdiv(Fo, kStretchSpan), ntile = cdiv(C, kStretchBins);
+  const int64_t blocks = (int64_t)B * ntile * nspan;
+  TACO_REQUIRE(blocks <= 0x7fffffff, "frames_stretch: B=%d x C=%d x Fo=%d needs more than 2^31 workgroups", B, C, Fo);
+  hipStream_t s = as_stream(stream);
+  TACO_KLAUNCH(frames_stretch_kernel, dim3((unsigned)blocks), dim3(64, 4), 0, s, mag_t, frames, frames_per_unit, step_q, out, frames_out,
+               C, F, Fo, nspan, ntile);
+  TACO_LAUNCH_CHECK("frames_stretch");
   return TACO_OK;
 }
 // The widest access taco_corpus_batch may use: the largest V in {8 (fp16 only), 4, 2, 1} that divides the row pitch, with the

@@ -13,6 +13,9 @@ phase0 -- initial phases from the library's counter-hash generator: no host rand
 With `momentum` (opt-in) the rounds are those of the fast Griffin-Lim algorithm (taco_griffinlim_fast), and `want_conv` returns the
 per-round spectral convergence next to the waveform.
 
+With `rate` (opt-in) the magnitude matrix is resampled along its frame axis before Griffin-Lim (taco_frames_stretch): the utterance gets
+slower or faster and Griffin-Lim finds phases for the new length, so the pitch stays where it was.
+
 `finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
 front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16.
 
@@ -32,7 +35,7 @@ SR = 16000   # test.py:11
 
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
-                       lengths=None, momentum=None, want_conv=False):
+                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -41,13 +44,44 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     generator (seeded by `seed`; no host draw, no upload) -- not the torch-generator phases of the momentum=None path without
     lengths, so the same seed gives another waveform there.
     want_conv (needs momentum): returns (waveform, conv (B, n_iter + 1)), the spectral convergence in front of every round and of
-    the waveform returned (include/taco_hip.h)."""
+    the waveform returned (include/taco_hip.h).
+    rate: None for the model's own speaking rate on the paths above, untouched.  Otherwise a number in [0.25, 4] (1.0: the model's rate,
+    0.8 slower, 1.25 faster), a host sequence of B such numbers, or a (B) int32 device tensor of step_q values (lib.stretch_step): the
+    first len_b r frames of every row (all F frames without `lengths`) are resampled by lib.frames_stretch into (B, 1025, Fo), Fo the
+    capacity at the slowest rate of the batch (a device tensor: at rate 0.25) and at least the 5 frames Griffin-Lim needs, and the
+    stretched matrix is vocoded over the device's frames_out with frames_per_unit = 1.  With a rate the vocoder ALWAYS takes the
+    per-row entry points (lib.griffinlim_rows, or lib.griffinlim_fast with `momentum`), so without phase0 the phases come from the
+    device's counter-hash generator over (B, 1025, Fo) -- not the torch-generator phases of the rate=None path without lengths.
+    Returns what the call returns without a rate, over Fo frames -- the waveform (B, 300 (Fo - 1)), or (waveform, conv) -- followed
+    by frames_out (B) int32 on the device: (waveform, frames_out) or (waveform, conv, frames_out).  wave / work / phase0 are then
+    sized for Fo frames; frames_out: the caller's own buffer for the stretched frame counts (needs rate)."""
+    if frames_out is not None and rate is None:
+        raise ValueError('invert_spectrogram: frames_out needs rate')
     if want_conv and momentum is None:
         raise ValueError('invert_spectrogram: want_conv needs momentum (0 for the plain rounds)')
     dev = out.device
     mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
+    if rate is not None:
+        F = mag_t.shape[2]
+        if torch.is_tensor(rate) and rate.device.type != 'cpu':
+            step_q, slowest = rate, lib.STRETCH_MIN_STEP
+        else:
+            rates = rate.tolist() if torch.is_tensor(rate) else rate
+            one = not hasattr(rates, '__len__')
+            step_q = lib.stretch_step(rates) if one else [lib.stretch_step(x) for x in rates]
+            slowest = step_q if one else min(step_q, default=lib.STRETCH_ONE)
+        Fo = max(5, lib.stretch_capacity(F, slowest))
+        stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=r if lengths is not None else 1, Fo=Fo,
+                                                   frames_out=frames_out)
+        phase0 = None if phase0 is None else phase0.contiguous()
+        if momentum is not None:
+            res = lib.griffinlim_fast(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, momentum=momentum,
+                                      frames_per_unit=1, want_conv=want_conv, out=wave, work=work)
+            return (res[0], res[1], frames_out) if want_conv else (res, frames_out)
+        return lib.griffinlim_rows(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=1, out=wave,
+                                   work=work), frames_out
     if momentum is not None:
         return lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
                                    momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work)

@@ -115,6 +115,7 @@ EXPORTS = {
     'taco_debug_clock_probe': (C.c_int, [_P, _I, _P]),
     'taco_debug_fabric_probe': (C.c_int, [_P, _P, _P, C.c_int64, _I, _P]),
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'taco_frames_stretch': (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_corpus_batch': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -449,6 +450,99 @@ def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=Fa
     if want_spec and want_mag_t:
         return spec, mag_t
     return spec if want_spec else mag_t
+
+
+STRETCH_ONE, STRETCH_MIN_STEP, STRETCH_MAX_STEP, STRETCH_MAX_FRAMES = 65536, 16384, 262144, 8192   # include/taco_hip.h
+
+
+def stretch_step(rate) -> int:
+    """A speaking rate (1.0: the model's own, 0.8 slower, 1.25 faster) -> step_q of taco_frames_stretch = round(65536 * rate), the
+    source frames advanced per output frame in units of 2^-16; ValueError outside [0.25, 4] or for NaN"""
+    try:
+        rate = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError('rate must be a number in [0.25, 4], got %r' % (rate,)) from None
+    if not 0.25 <= rate <= 4.0:   # (NaN fails both comparisons)
+        raise ValueError('rate must be in [0.25, 4], got %r' % (rate,))
+    return int(round(65536.0 * rate))
+
+
+def _stretch_clamp(step_q) -> int:
+    return min(max(int(step_q), STRETCH_MIN_STEP), STRETCH_MAX_STEP)
+
+
+def stretch_frames(F_b, step_q, cap=None) -> int:
+    """Fo_b of taco_frames_stretch on the host: 0 for F_b <= 0, else ((F_b - 1) << 16) // s + 1 with s = step_q clamped as the device
+    clamps it, and at most `cap` (the Fo of the call) when given"""
+    F_b = int(F_b)
+    if F_b <= 0:
+        return 0
+    n = ((F_b - 1) << 16) // _stretch_clamp(step_q) + 1
+    return n if cap is None else min(int(cap), n)
+
+
+def stretch_capacity(F, step_q_min) -> int:
+    """The Fo no row of a (B, C, F) call can exceed when no row's step is below step_q_min (the slowest rate of the batch)"""
+    return stretch_frames(F, step_q_min)
+
+
+def frames_stretch(mag_t, frames=None, step_q=None, frames_per_unit=1, Fo=None, out=None, frames_out=None):
+    """Speaking rate on the magnitude frames (include/taco_hip.h taco_frames_stretch): mag_t (B, C, F) fp32 on the device ->
+    (out (B, C, Fo) fp32, frames_out (B) int32): row b's first F_b = clamp(frames[b] * frames_per_unit, 0, F) frames resampled
+    linearly at step_q[b] / 65536 source frames per output frame, Fo_b = stretch_frames(F_b, step_q[b], Fo) of them, zeros behind.
+    frames: (B) int32 on the device, or None (all F frames).  step_q: None (65536: a copy), an int (the whole batch), a host sequence
+    of B ints (checked against [16384, 262144], then uploaded) or a (B) int32 tensor on the device (clamped there, never read here).
+    Fo: default the capacity at the slowest step the host knows of (16384 for a device tensor).  out / frames_out: the caller's own
+    buffers; default: fresh ones.  Enqueued on the current stream; nothing is read back and nothing waits."""
+    who = 'frames_stretch'
+    if not torch.is_tensor(mag_t) or mag_t.dim() != 3 or mag_t.dtype != torch.float32 or min(mag_t.shape) < 1:
+        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, C, F), got %s %s'
+                         % (who, getattr(mag_t, 'dtype', type(mag_t)), tuple(getattr(mag_t, 'shape', ()))))
+    if not mag_t.is_contiguous():
+        raise ValueError('%s: mag_t must be contiguous' % who)
+    B, Cw, F = mag_t.shape
+    dev = mag_t.device
+    if F > STRETCH_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
+    if frames is not None and (not torch.is_tensor(frames) or tuple(frames.shape) != (B,) or frames.dtype != torch.int32
+                               or frames.device != dev or not frames.is_contiguous()):
+        raise ValueError('%s: frames must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
+    if isinstance(frames_per_unit, bool) or int(frames_per_unit) != frames_per_unit or int(frames_per_unit) < 1:
+        raise ValueError('%s: frames_per_unit must be an integer >= 1, got %r' % (who, frames_per_unit))
+    slowest = STRETCH_MIN_STEP
+    if step_q is None:
+        slowest = STRETCH_ONE
+    elif torch.is_tensor(step_q) and step_q.device.type != 'cpu':
+        if tuple(step_q.shape) != (B,) or step_q.dtype != torch.int32 or step_q.device != dev or not step_q.is_contiguous():
+            raise ValueError('%s: step_q on a device must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
+    else:
+        one = not torch.is_tensor(step_q) and not hasattr(step_q, '__len__')
+        host = _host_int32([step_q] * B if one else step_q, B, who + ': step_q')
+        if min(host) < STRETCH_MIN_STEP or max(host) > STRETCH_MAX_STEP:
+            raise ValueError('%s: step_q must be in [%d, %d] (rates 0.25 to 4), got %r'
+                             % (who, STRETCH_MIN_STEP, STRETCH_MAX_STEP, step_q if one else host))
+        slowest = min(host)
+        step_q = torch.tensor(host, dtype=torch.int32).to(dev)
+    if Fo is None:
+        Fo = stretch_capacity(F, slowest)
+        if out is None and Fo > STRETCH_MAX_FRAMES:
+            raise ValueError('%s: F = %d frames at step %d may need %d output frames, more than %d: give Fo'
+                             % (who, F, slowest, Fo, STRETCH_MAX_FRAMES))
+        if out is not None and torch.is_tensor(out) and out.dim() == 3:
+            Fo = out.shape[2]
+    if isinstance(Fo, bool) or int(Fo) != Fo or not 1 <= int(Fo) <= STRETCH_MAX_FRAMES:
+        raise ValueError('%s: Fo must be an integer in [1, %d], got %r' % (who, STRETCH_MAX_FRAMES, Fo))
+    Fo = int(Fo)
+    out = _own_or_given(out, (B, Cw, Fo), torch.float32, dev, who + ': out')
+    m0, o0 = mag_t.data_ptr(), out.data_ptr()
+    if o0 < m0 + B * Cw * F * 4 and m0 < o0 + B * Cw * Fo * 4:
+        raise ValueError('%s: out may not overlap mag_t' % who)
+    frames_out = _own_or_given(frames_out, (B,), torch.int32, dev, who + ': frames_out')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_frames_stretch(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(step_q), ptr(out), ptr(frames_out), B, Cw, F, Fo,
+                                    stream_ptr()), 'taco_frames_stretch')
+    return out, frames_out
 
 
 DTW_MAX_FRAMES, DTW_MAX_K, DTW_MAX_C = 1024, 32, 128   # TACO_DTW_MAX_FRAMES / _K / _C

@@ -25,7 +25,13 @@ piece and the per-piece arrays are prompt_NNN_kMM_{spec,align,len,trim}.npy.  A 
 scores are computed on the device (Tacotron.alignment_scores, taco_alignment_scores; over each prompt's own steps with --stop) and
 prompt_NNN_ascore.npy holds the prompt's 8 values as float64 (lib.ALIGN_COUNTS, then lib.ALIGN_MEANS); prompt_NNN_align.png is the
 attention picture over the kept steps (alignment.attention_png); a prompt that alignment.flags marks gets one `WARNING prompt N: ...`
-line.  With --long a prompt of several pieces writes one pair per piece (prompt_NNN_kMM_*).  It combines with every option above."""
+line.  With --long a prompt of several pieces writes one pair per piece (prompt_NNN_kMM_*).  It combines with every option above.
+--rate R (opt-in, not in the reference): the speaking rate, 1.0 the model's own, 0.8 slower, 1.25 faster, 0.25 <= R <= 4.  The magnitude
+frames are resampled on the device between the de-normalisation and Griffin-Lim (lib.frames_stretch, taco_frames_stretch), which then
+finds phases for the new length: the duration changes, the pitch does not.  prompt_NNN.wav holds the stretched audio, 300 (Fo_b - 1)
+samples before any trim, and prompt_NNN_rate.npy holds (step_q, Fo_b) as int32; the spectrogram, alignment, length and score files
+stay the model's own output.  With --stop the stretch and the vocoder run over each prompt's own len_b r frames, phases drawn on the
+device.  Nobody has listened to the result.  It combines with every option above; with --long the pieces of a prompt inherit its rate."""
 from __future__ import annotations
 
 import argparse
@@ -92,8 +98,28 @@ def long_options(long):
     return pause_ms, fade_ms
 
 
-def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None):
+def rate_steps(rate, n):
+    """`rate` of test(): None, a number or a sequence of n numbers in [0.25, 4] -> None or the n step_q values (lib.stretch_step);
+    ValueError"""
+    if rate is None:
+        return None
+    if hasattr(rate, '__len__'):
+        if n is not None and len(rate) != n:
+            raise ValueError('rate (--rate): %d rates for %d prompts' % (len(rate), n))
+        return [lib.stretch_step(x) for x in rate]
+    return [lib.stretch_step(rate)] * (1 if n is None else n)
+
+
+def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
+                  vocode=True):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given); ValueError."""
+    if rate is not None:
+        if not vocode:
+            raise ValueError('rate (--rate) stretches the magnitudes in front of Griffin-Lim: it needs vocode')
+        try:
+            rate_steps(rate, None)
+        except ValueError as e:
+            raise ValueError('rate (--rate): %s' % e) from None
     if long_options(long) is not None and not stop:
         raise ValueError('long (--long) needs a stop rule (--stop): without one every piece carries max_decode_iter steps')
     if vocode_lengths and not stop:
@@ -108,19 +134,26 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
         raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (trim_db,))
 
 
-def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4):
+def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
+                 rate=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
     ascore (--align-scores): the prompt's 8 alignment scores, written as _ascore.npy (float64) next to _align.png, the attention picture
-    over the kept alignment rows at `zoom` pixels per cell."""
+    over the kept alignment rows at `zoom` pixels per cell.
+    rate (--rate): (step_q, Fo_b) of the prompt, written as _rate.npy; wav is then the stretched waveform and keeps 300 (Fo_b - 1)
+    samples, whatever len_b says."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
         spec, align = spec[:frames], align[:len_b]
-        if wav is not None:
+        if wav is not None and rate is None:
             wav = wav[:300 * (frames - 1)]
         np.save(path + '_len.npy', np.int32(len_b))
+    if rate is not None:
+        if wav is not None:
+            wav = wav[:300 * max(0, int(rate[1]) - 1)]
+        np.save(path + '_rate.npy', np.asarray(rate, dtype=np.int32))
     np.save(path + '_spec.npy', spec)
     np.save(path + '_align.npy', align)
     if wav is not None:
@@ -137,7 +170,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False):
+         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -163,8 +196,16 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     contents it writes without `long`.
     `align_scores`: every batch is scored on the device (Tacotron.alignment_scores: over model.lengths with `stop`, else all steps) and
     each prompt -- with `long`, each piece -- additionally writes _ascore.npy and _align.png (write_prompt); a prompt whose scores
-    alignment.flags marks is named in one WARNING line.  Nothing else changes."""
-    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long)
+    alignment.flags marks is named in one WARNING line.  Nothing else changes.
+    `rate` (needs `vocode`): None, a speaking rate in [0.25, 4] (1.0: the model's own) or a sequence with one rate per prompt; with
+    `long`, a prompt's pieces inherit its rate.  The magnitudes of every row are stretched on the device in front of Griffin-Lim
+    (invert_spectrogram(rate=...)): over the row's own len_b r frames with `stop` (whether or not `vocode_lengths` is set; the phases
+    are then drawn on the device), else over all frames.  prompt_NNN.wav holds 300 (Fo_b - 1) samples, Fo_b = lib.stretch_frames of
+    those frames -- cut on the host by that formula, or with finishing on the device from the stretch's own frames_out -- and
+    prompt_NNN_rate.npy (step_q, Fo_b) as int32.  Every other file is the model's own output, unstretched; without `rate` every file
+    is what it was."""
+    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode)
+    steps = rate_steps(rate, len(prompts))
     long = long_options(long)
     if long is not None and not vocode:
         raise ValueError('long (--long) joins waveforms: it needs vocode')
@@ -212,13 +253,27 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
         wav = conv = pcm = trim = None
         if vocode:
-            wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                     want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None)
+            fout = None
+            if steps is None:
+                wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
+                                         want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None)
+            else:   # (the rows' own frames whenever there is a rule: the host's Fo_b and the device's frames_out are then one number)
+                *wav, fout = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
+                                                want_conv=gl_momentum is not None, lengths=model.lengths if stop is not None else None,
+                                                rate=[q / 65536.0 for q in row_steps[n:n + Bn]])
+                wav = wav[0] if gl_momentum is None else wav
             if gl_momentum is not None:
                 wav, conv = wav[0], wav[1].cpu().numpy()
                 print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
                       % (gl_momentum, n_iter, float(conv[:, -1].max())))
-            if finish:   # (the fp32 waveform stays on the device)
+            if finish and fout is not None:   # (a rate: the row ends where the stretch says; `long`: the rows are wider than this batch's)
+                fin, pcm, trim, _ = finish_waveform(wav, fout, 1, deemphasis=0.0 if deemphasis is None else deemphasis,
+                                                    trim_top_db=0.0 if trim_db is None else trim_db, want_out=out_rows is not None,
+                                                    want_pcm=out_rows is None, bounds=bounds_rows)
+                if out_rows is not None:
+                    out_rows[:, :fin.shape[1]].copy_(fin)
+                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
+            elif finish:   # (the fp32 waveform stays on the device)
                 _, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
                                                   deemphasis=0.0 if deemphasis is None else deemphasis,
                                                   trim_top_db=0.0 if trim_db is None else trim_db, want_out=out_rows is not None,
@@ -235,9 +290,22 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
         return flags(score[:6], score[6:], L, end_offset=stop.end_offset if stop is not None else 1)
 
+    F = (config.max_decode_iter // 4) * 4 * config.r   # frames per row of the model's output
+
+    def rate_of(row, len_b):
+        """(step_q, Fo_b) of global row `row`, or None without a rate"""
+        if steps is None:
+            return None
+        return row_steps[row], lib.stretch_frames(F if len_b is None else min(int(len_b) * config.r, F), row_steps[row])
+
     n = 0
+    row_steps = steps
     if long is not None:
-        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks)
+        L = None
+        if steps is not None:   # a piece has its prompt's rate; every row of the joined buffer holds the slowest one's samples
+            row_steps = [steps[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
+            L = 300 * (max(5, lib.stretch_capacity(F, min(row_steps, default=lib.STRETCH_ONE))) - 1)
+        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of)
         print('wrote %d samples to %s' % (n, out_dir))
         return n
     for batch in load_prompts(prompts, ivocab):
@@ -245,7 +313,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         spec, al, wav, conv, pcm, trim, lengths, scores = synthesise(batch, n)
         for i in range(Bn):
             wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
-            write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si)
+            write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
+                         rate=rate_of(n, len_b))
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
             if found:
                 print('WARNING prompt %d: %s' % (n, ', '.join(found)))
@@ -254,8 +323,9 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     return n
 
 
-def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks):
-    """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write"""
+def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None):
+    """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write.  L: the samples
+    per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b): what write_prompt gets as `rate`"""
     pause_ms, fade_ms = long
     split = [split_prompt(p) for p in prompts]
     groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
@@ -265,7 +335,8 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks):
         if held >= JOIN_GROUP or p == len(split) - 1:
             groups.append((start, p + 1))
             start, held = p + 1, 0
-    L = 300 * ((config.max_decode_iter // 4) * 4 * config.r - 1)   # samples per row of invert_spectrogram
+    if L is None:
+        L = 300 * ((config.max_decode_iter // 4) * 4 * config.r - 1)   # samples per row of invert_spectrogram
     row = 0   # index of the next piece over the whole run (the Griffin-Lim seed of its batch, as the prompt index is without `long`)
     for lo, hi in groups:
         lines = [line for pieces in split[lo:hi] for line, _ in pieces]
@@ -291,7 +362,8 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks):
             found = []
             for k in range(a, b):
                 spec, al, len_b, trim, conv, score, text_len = arrays[k]
-                write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score)
+                write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score,
+                             rate=rate_of(row + k, len_b))
                 names = marks(score, text_len) if score is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
@@ -342,13 +414,16 @@ def parse_args(argv=None):
                          '300,150,0: choices of the author, not tuned by ear; a cut inside a word gets none)')
     ap.add_argument('--fade-ms', type=float, default=FADE_MS,
                     help='--long: milliseconds of linear ramp at every interior edge of a piece (default 5: a choice, not tuned by ear)')
+    ap.add_argument('--rate', type=float, default=None, metavar='R',
+                    help='speaking rate, 0.25 <= R <= 4: 1.0 is the model\'s own, 0.8 slower, 1.25 faster; the magnitudes are stretched on '
+                         'the device in front of Griffin-Lim, so the pitch stays; writes prompt_NNN_rate.npy (not in the reference)')
     ap.add_argument('--align-scores', action='store_true',
                     help='score every prompt\'s attention on the device: prompt_NNN_ascore.npy (8 values: n, end, pad_steps, back, skip, '
                          'covered, focus, pad_mass), prompt_NNN_align.png, and a WARNING line for a prompt the (untuned) thresholds mark')
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
     try:
-        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long)
+        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -364,4 +439,4 @@ if __name__ == '__main__':
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
-         align_scores=a.align_scores)
+         align_scores=a.align_scores, rate=a.rate)
