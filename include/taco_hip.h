@@ -355,8 +355,7 @@ int taco_denorm_unframe(const float* output, const float* stft_mean, const float
  * frames_out, out overlapping mag_t, B, C, F or Fo <= 0, F or Fo > TACO_STRETCH_MAX_FRAMES and frames_per_unit < 1 return
  * TACO_EINVAL, with a message that names the argument, before anything is enqueued.  TACO_VERSION did not change with this entry
  * point: detect it by the symbol.
- * Not here: pitch (a warp of the bin axis moves the formants with the pitch; a formant-preserving shift needs an envelope split), a
- * rate that varies inside an utterance, interpolation of log-magnitudes or of mel frames.  Nobody has listened to the result: the
+ * Not here: a rate that varies inside an utterance, interpolation of log-magnitudes or of mel frames.  Nobody has listened to the result: the
  * limits 0.25 and 4 are bounds of the arithmetic ((frame << 16) and j * s_b stay inside 31 bits), not recommendations. */
 #define TACO_STRETCH_ONE        65536     /* step_q of rate 1 */
 #define TACO_STRETCH_MIN_STEP   16384     /* rate 0.25: four times slower */
@@ -364,6 +363,50 @@ int taco_denorm_unframe(const float* output, const float* stft_mean, const float
 #define TACO_STRETCH_MAX_FRAMES 8192      /* F and Fo; keeps (frame << 16) inside 31 bits */
 int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q,
                         float* out, int32_t* frames_out, int B, int C, int F, int Fo, void* stream);
+
+/* Pitch at synthesis (no reference counterpart), the second prosody control beside the speaking rate and in the same place: between
+ * taco_denorm_unframe and Griffin-Lim, where a frame is magnitudes without phases.  A warp of the bin axis alone would move the
+ * formants with the pitch, so each frame's log-magnitudes are split into a smooth log-envelope (the low quefrencies of the cepstrum)
+ * and a log-excitation (the rest, which carries the harmonics); the excitation alone is warped and put back under the unmoved
+ * envelope, and Griffin-Lim then finds phases for the harmonics it is given.
+ *   mag_t  (B, C, F) fp32 and out (B, C, F) fp32, the frame index contiguous (the layout of taco_denorm_unframe's mag_t);
+ *          C - 1 a power of two, 8 <= C - 1 <= 1024; N = 2 (C - 1).  Production: C = 1025; the small C keep tests cheap
+ *   frames, frames_per_unit: as taco_frames_stretch: F_b = clamp(frames[b] * frames_per_unit, 0, F), NULL: F_b = F
+ *   step_q (B) int32 on the DEVICE, or NULL: source bins advanced per output bin in units of 2^-16 = 65536 / ratio, ratio =
+ *          2^(semitones / 12); used as s_b = clamp(step_q[b], TACO_PITCH_MIN_STEP, TACO_PITCH_MAX_STEP); NULL: TACO_PITCH_ONE.
+ *          The host reads nothing from frames or step_q
+ *   lifter Q, 1 <= Q <= min(TACO_PITCH_MAX_LIFTER, (C - 1) / 2): the quefrencies 0 .. Q make the envelope (rectangular lifter)
+ * For frame f < F_b of row b, m[k] = mag_t[b, k, f], in real numbers:
+ *   L[k] = log(max(m[k], TACO_PITCH_FLOOR))                                        (the front end's own epsilon)
+ *   c[n] = (L[0] + (-1)^n L[C-1] + 2 sum_{k=1..C-2} L[k] cos(2 pi n k / N)) / N,  n = 0 .. Q  (cepstrum of the even extension)
+ *   E[k] = c[0] + 2 sum_{n=1..Q} c[n] cos(2 pi n k / N);   R[k] = L[k] - E[k]
+ *   p = k * s_b, i = p >> 16, w = (p & 0xFFFF) 2^-16:  R'[k] = R[i] + w (R[i+1] - R[i]) for i < C - 1;  R[C-1] for i == C - 1 and
+ *   w == 0;  0 beyond the top bin (there the output is the envelope alone)
+ *   out[b, k, f] = exp(E[k] + R'[k])
+ * computed in fp32 (logf, expf, a cosine table from cospif, the two cosine products as ordered fmaf chains in a fixed order) and
+ * held by the tests to an fp64 restatement within a tolerance sized from a float32 restatement (tests/pitch_ref.py).  Exactly:
+ *   - a row with s_b == TACO_PITCH_ONE is copied: out[b, k, f] = mag_t[b, k, f] bit for bit for f < F_b, no log / exp round trip;
+ *   - out[b, k, f] = +0 for F_b <= f < F;
+ *   - every element of out is written and nothing outside it, for any F and any 4-byte alignment of mag_t and out;
+ *   - columns f >= F_b, every other row and every other frame have no influence on a frame (they may hold NaN); a non-finite value
+ *     inside a frame leaves unspecified values in that frame only;
+ *   - the bits of a frame depend on its own C bins, s_b and Q alone -- not on B, F, its position f or the buffers' alignment; no
+ *     atomics; the same arguments give the same bits.
+ * One launch of B x ceil(F / 32) workgroups, no workspace, no allocation, no host synchronisation, no workgroup waits for another
+ * one: graph-capturable, and a replay follows whatever frames and step_q hold at replay time.  NULL mag_t / out, out overlapping
+ * mag_t, B or F <= 0, F > TACO_STRETCH_MAX_FRAMES, C - 1 not a power of two in 8 .. 1024, lifter out of range and
+ * frames_per_unit < 1 return TACO_EINVAL, with a message that names the argument, before anything is enqueued.  TACO_VERSION did
+ * not change with this entry point: detect it by the symbol.
+ * Not here: a tapered or caller-supplied lifter, a pitch contour inside an utterance, mel frames.  Nobody has listened to the
+ * result: the default lifter of the Python layer (32: quefrencies up to 2 ms at 16 kHz) is untuned, and the limits of +-12
+ * semitones are bounds of the arithmetic (k * s_b <= 2^27), not recommendations. */
+#define TACO_PITCH_ONE        65536     /* step_q of 0 semitones */
+#define TACO_PITCH_MIN_STEP   32768     /* +12 semitones */
+#define TACO_PITCH_MAX_STEP   131072    /* -12 semitones */
+#define TACO_PITCH_MAX_LIFTER 64
+#define TACO_PITCH_FLOOR      1e-8f     /* audio.py:59 */
+int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                      float* out, int B, int C, int F, void* stream);
 
 /* ---- corpus boundary ----------------------------------------------------------------------------------------------------- */
 /* The batch gather of the training corpus with the reference's target standardisation (data_input.py:55-65

@@ -661,6 +661,196 @@ __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __rest
   }
 }
 
+// taco_frames_pitch: pitch at synthesis.  A frame's log-magnitudes L[k] are split into a log-envelope E (the cepstrum of the even
+// extension, quefrencies 0 .. Q kept) and a log-excitation R = L - E; R alone is warped along the bin axis by s_b (2^-16 source bins
+// per output bin) and put back under the unmoved envelope: out = exp(E[k] + R'[k]) (include/taco_hip.h has the definition).
+// A workgroup of kPitchWaves waves owns kPitchFrames = 32 consecutive frames of one row: the frame index is the lane's low five
+// bits, which is both the contiguous axis of mag_t / out (a half-wave reads or writes 128 contiguous bytes of one bin row) and the
+// column index of a 32x32x2 fp32 MFMA.  The two cosine products are those MFMAs -- an ordered fmaf chain per element, so the bits
+// of a frame do not depend on its column:
+//   cepstrum  c[n][f] = sum_k cos(2 pi n k / N) (wt_k L[k][f] / N), n = 1 .. 32 NB: rows = n, the bin pairs (k, k + 1) dealt to the
+//             waves round robin, the waves' partial tiles summed through LDS in wave order; c[0] is a plain sum beside it;
+//   envelope  E[k][f] = c[0][f] + sum_n cos(2 pi n k / N) (2 c[n][f]): rows = 32 bins, 16 NB MFMAs per tile, the tiles dealt to the
+//             waves; c[n] behind the lifter are zeros; the top bin C - 1 (cos = (-1)^n) is a sum on the side.
+// NB = 1 for Q <= 32 (16 waves), 2 above (8 waves: 149 registers); which of the two runs depends on Q alone, so the bits do too.
+// E stays in LDS for the frame tile (C x 32 floats, 131 KB at C = 1025; the cepstrum partials use the same bytes before it) next to
+// the cosine table (N floats, indexed (n k) & (N - 1)) and the cepstra: 148 KB, one workgroup per CU.  L is NOT kept: the warp re-reads
+// its two source bins (from L2 or the Infinity Cache) and takes their logarithms again -- 3 reads per element where 1 is
+// compulsory, which is what keeps the kernel at four times the copy's time (profiles/frames_pitch_forms.txt, DESIGN.md 4b: the forms
+// measured, and the 16-frame tile with L and E both in LDS that was not built).  With one workgroup per CU nothing hides a load but
+// the workgroup's own waves, so every loop issues a batch of loads in front of the arithmetic that uses them.  Rows with
+// s_b == TACO_PITCH_ONE are copied and tiles behind F_b zeroed without any of this.
+constexpr int kPitchFrames = 32;
+constexpr int kPitchMaxC = 1025;
+constexpr int kPitchBatch = 8;         // bins a thread has in flight in the copy and in the warp
+template <int NB, int kPitchWaves>
+__global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                                         int frames_per_unit, const int32_t* __restrict__ step_q, int Q,
+                                                                         float* __restrict__ out, int C, int F, int ntile) {
+  constexpr int NR = 32 * NB;                                // cepstrum rows n = 1 .. NR
+  __shared__ float tab[2 * (kPitchMaxC - 1)];
+  __shared__ float cep[(NR + 1) * kPitchFrames];             // c[n][f], n = 0 .. NR
+  __shared__ float env[kPitchMaxC * kPitchFrames];           // E[k][f]; before that the waves' partial cepstra
+  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
+  int Fb = F, s = TACO_PITCH_ONE;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  if (step_q) {
+    s = step_q[b];
+    s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+  }
+  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  s = __builtin_amdgcn_readfirstlane(s);
+  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int f0 = tile * kPitchFrames, f = f0 + fl;
+  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
+  float* __restrict__ dst = out + (int64_t)b * C * F + f;
+  const bool live = f < Fb, inside = f < F;
+  if (f0 >= Fb || s == TACO_PITCH_ONE) {   // (uniform) nothing to shift: zeros behind the row's end, the row's own bits in front of it
+    for (int kb = 2 * wave + h; kb < C; kb += 2 * kPitchWaves * kPitchBatch) {   // (kPitchBatch loads in flight per thread)
+      float m[kPitchBatch];
+#pragma unroll
+      for (int u = 0; u < kPitchBatch; ++u) {
+        const int k = kb + 2 * kPitchWaves * u;
+        m[u] = (live && k < C) ? src[k * F] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kPitchBatch; ++u) {
+        const int k = kb + 2 * kPitchWaves * u;
+        if (inside && k < C) dst[k * F] = m[u];
+      }
+    }
+    return;
+  }
+  const int N = 2 * (C - 1), mask = N - 1;
+  for (int j = tid; j < N; j += 64 * kPitchWaves) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
+  __syncthreads();
+
+  // ---- cepstrum ----
+  const float wt = 2.0f / (float)N;   // (a power of two: the weight and the 1 / N cost no rounding)
+  f32x16 acc[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+  float c0p = 0.f;
+  float m[4], nx[4];   // four bin pairs per trip, the next trip's loads issued in front of this trip's arithmetic
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int k = 2 * wave + 2 * kPitchWaves * u + h;
+    m[u] = (live && k < C) ? src[k * F] : 1.0f;
+  }
+  for (int k0 = 2 * wave; k0 < C; k0 += 8 * kPitchWaves) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + 8 * kPitchWaves + 2 * kPitchWaves * u + h;
+      nx[u] = (live && k < C) ? src[k * F] : 1.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + 2 * kPitchWaves * u + h;   // (k >= C: m = 1, v = 0, and the table is read at some valid index)
+      const float v = logf(fmaxf(m[u], TACO_PITCH_FLOOR)) * ((k == 0 || k == C - 1) ? 0.5f * wt : wt);
+      c0p += v;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + fl) * k) & mask], v, acc[nb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) m[u] = nx[u];
+  }
+  float* part = env;                       // [wave][n - 1][f], then [wave][h][f] for c[0]
+  float* part0 = env + kPitchWaves * NR * kPitchFrames;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      part[((wave * NR) + 32 * nb + (r & 3) + 8 * (r >> 2) + 4 * h) * kPitchFrames + fl] = acc[nb][r];
+  part0[(2 * wave + h) * kPitchFrames + fl] = c0p;
+  __syncthreads();
+  for (int e = tid; e < NR * kPitchFrames; e += 64 * kPitchWaves) {   // e = (n - 1) * 32 + f
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kPitchWaves; ++w) t += part[w * NR * kPitchFrames + e];
+    cep[kPitchFrames + e] = (e >> 5) < Q ? t : 0.f;   // the rectangular lifter
+  }
+  if (tid < kPitchFrames) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 2 * kPitchWaves; ++w) t += part0[w * kPitchFrames + tid];
+    cep[tid] = t;
+  }
+  __syncthreads();   // (nothing reads the partials from here on: env is the envelope's)
+
+  // ---- envelope ----
+  const float c0 = cep[fl];
+  float cb[NB][16];   // 2 c[n][f], n = 32 nb + 1 + 2 j + h: this lane's B operands
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) cb[nb][j] = 2.0f * cep[(32 * nb + 1 + 2 * j + h) * kPitchFrames + fl];
+  if (tid < kPitchFrames) {   // bin C - 1: cos(pi n) = (-1)^n
+    float t = c0;
+    for (int n = 1; n <= NR; ++n) {
+      const float c2 = 2.0f * cep[n * kPitchFrames + tid];
+      t += (n & 1) ? -c2 : c2;
+    }
+    env[(C - 1) * kPitchFrames + tid] = t;
+  }
+  const int nblk = (C - 1 + 31) >> 5;
+  for (int kb = wave; kb < nblk; kb += kPitchWaves) {
+    const int k = 32 * kb + fl;
+    f32x16 d;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d[r] = c0;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        d = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + 2 * j + h) * k) & mask], cb[nb][j], d, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kk = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (kk < C - 1) env[kk * kPitchFrames + fl] = d[r];
+    }
+  }
+  __syncthreads();
+
+  // ---- warp of the excitation, output ----  kPitchBatch bins per trip: every load of the trip first, at indices clamped into the
+  // frame (a value from a clamped index is never used)
+  for (int kb = 2 * wave + h; kb < C; kb += 2 * kPitchWaves * kPitchBatch) {
+    float m0[kPitchBatch], m1[kPitchBatch];
+    if (live) {
+#pragma unroll
+      for (int u = 0; u < kPitchBatch; ++u) {
+        const int k = min(kb + 2 * kPitchWaves * u, C - 1);
+        const int i = (int)(((uint32_t)k * (uint32_t)s) >> 16);   // (k s <= 1024 * 2^17)
+        m0[u] = src[min(i, C - 1) * F];
+        m1[u] = src[min(i + 1, C - 1) * F];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kPitchWaves * u;
+      if (k >= C) break;
+      float y = 0.f;
+      if (live) {
+        const uint32_t p = (uint32_t)k * (uint32_t)s;
+        const int i = (int)(p >> 16), ia = min(i, C - 1), ib = min(i + 1, C - 1);
+        const uint32_t frac = p & 0xFFFFu;
+        const float r0 = logf(fmaxf(m0[u], TACO_PITCH_FLOOR)) - env[ia * kPitchFrames + fl];
+        const float r1 = logf(fmaxf(m1[u], TACO_PITCH_FLOOR)) - env[ib * kPitchFrames + fl];
+        // i < C - 1: between two bins; i == C - 1 with w == 0: the top bin itself; beyond it the envelope alone
+        const float rp = i < C - 1 ? r0 + (float)frac * (1.0f / 65536.0f) * (r1 - r0) : ((i == C - 1 && frac == 0u) ? r0 : 0.f);
+        y = expf(env[k * kPitchFrames + fl] + rp);
+      }
+      if (inside) dst[k * F] = y;
+    }
+  }
+}
+
 // taco_corpus_batch: the forward map denorm_unframe_kernel inverts, fused into the batch gather.  out[b, e] =
 // (float(src[index[b], e]) - mean[e % C]) / stdv[e % C] over rows of `row` = Td * C elements; T = _Float16 (the corpus as
 // preprocess stores it) or float.  One IEEE subtraction and one correctly rounded division per element: the bits of NumPy's
@@ -1132,6 +1322,33 @@ extern "C" int taco_frames_stretch(const float* mag_t, const int32_t* frames, in
   TACO_KLAUNCH(frames_stretch_kernel, dim3((unsigned)blocks), dim3(64, 4), 0, s, mag_t, frames, frames_per_unit, step_q, out, frames_out,
                C, F, Fo, nspan, ntile);
   TACO_LAUNCH_CHECK("frames_stretch");
+  return TACO_OK;
+}
+extern "C" int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                                 float* out, int B, int C, int F, void* stream) {
+  TACO_REQUIRE(mag_t, "frames_pitch: mag_t is NULL");
+  TACO_REQUIRE(out, "frames_pitch: out is NULL");
+  TACO_REQUIRE(B > 0, "frames_pitch: B=%d must be positive", B);
+  TACO_REQUIRE(C >= 9 && C <= kPitchMaxC && ((C - 1) & (C - 2)) == 0,
+               "frames_pitch: C=%d: C - 1 must be a power of two in 8..%d", C, kPitchMaxC - 1);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "frames_pitch: F=%d must be in 1..%d", F, TACO_STRETCH_MAX_FRAMES);
+  const int qmax = (C - 1) / 2 < TACO_PITCH_MAX_LIFTER ? (C - 1) / 2 : TACO_PITCH_MAX_LIFTER;
+  TACO_REQUIRE(lifter >= 1 && lifter <= qmax, "frames_pitch: lifter=%d must be in 1..%d at C=%d", lifter, qmax, C);
+  TACO_REQUIRE(frames_per_unit >= 1, "frames_pitch: frames_per_unit=%d must be >= 1", frames_per_unit);
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
+  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
+  TACO_REQUIRE(o0 + bytes <= m0 || m0 + bytes <= o0, "frames_pitch: out overlaps mag_t");
+  const int ntile = cdiv(F, kPitchFrames);
+  const int64_t blocks = (int64_t)B * ntile;
+  TACO_REQUIRE(blocks <= 0x7fffffff, "frames_pitch: B=%d x F=%d needs more than 2^31 workgroups", B, F);
+  hipStream_t s = as_stream(stream);
+  if (lifter <= 32)
+    TACO_KLAUNCH((frames_pitch_kernel<1, 16>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, step_q,
+                 lifter, out, C, F, ntile);
+  else
+    TACO_KLAUNCH((frames_pitch_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, step_q,
+                 lifter, out, C, F, ntile);
+  TACO_LAUNCH_CHECK("frames_pitch");
   return TACO_OK;
 }
 // The widest access taco_corpus_batch may use: the largest V in {8 (fp16 only), 4, 2, 1} that divides the row pitch, with the

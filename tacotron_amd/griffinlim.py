@@ -16,6 +16,9 @@ per-round spectral convergence next to the waveform.
 With `rate` (opt-in) the magnitude matrix is resampled along its frame axis before Griffin-Lim (taco_frames_stretch): the utterance gets
 slower or faster and Griffin-Lim finds phases for the new length, so the pitch stays where it was.
 
+With `pitch` (opt-in) the harmonics of every magnitude frame are moved along the bin axis under the frame's own spectral envelope before
+Griffin-Lim (taco_frames_pitch): the voice gets higher or lower, the formants and the duration stay.
+
 `finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
 front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16.
 
@@ -35,7 +38,7 @@ SR = 16000   # test.py:11
 
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
-                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None):
+                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -54,7 +57,12 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     device's counter-hash generator over (B, 1025, Fo) -- not the torch-generator phases of the rate=None path without lengths.
     Returns what the call returns without a rate, over Fo frames -- the waveform (B, 300 (Fo - 1)), or (waveform, conv) -- followed
     by frames_out (B) int32 on the device: (waveform, frames_out) or (waveform, conv, frames_out).  wave / work / phase0 are then
-    sized for Fo frames; frames_out: the caller's own buffer for the stretched frame counts (needs rate)."""
+    sized for Fo frames; frames_out: the caller's own buffer for the stretched frame counts (needs rate).
+    pitch: None for the model's own pitch, untouched.  Otherwise a number of semitones in [-12, 12] (0: the model's pitch, which gives
+    the bits of None), a host sequence of B such numbers, or a (B) int32 device tensor of step_q values (lib.pitch_step): right after
+    the de-normalisation the first len_b r frames of every row (all F frames without `lengths`) go through lib.frames_pitch with
+    `lifter` quefrencies of envelope (32: untuned), and the result takes the place of the magnitudes on every path above -- in
+    front of the stretch when `rate` is given too.  It changes no phase source and no return shape."""
     if frames_out is not None and rate is None:
         raise ValueError('invert_spectrogram: frames_out needs rate')
     if want_conv and momentum is None:
@@ -63,6 +71,13 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
+    if pitch is not None:
+        if torch.is_tensor(pitch) and pitch.device.type != 'cpu':
+            pitch_q = pitch
+        else:
+            semitones = pitch.tolist() if torch.is_tensor(pitch) else pitch
+            pitch_q = [lib.pitch_step(x) for x in semitones] if hasattr(semitones, '__len__') else lib.pitch_step(semitones)
+        mag_t = lib.frames_pitch(mag_t, lengths, pitch_q, frames_per_unit=r if lengths is not None else 1, lifter=lifter)
     if rate is not None:
         F = mag_t.shape[2]
         if torch.is_tensor(rate) and rate.device.type != 'cpu':

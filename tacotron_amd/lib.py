@@ -116,6 +116,7 @@ EXPORTS = {
     'taco_debug_fabric_probe': (C.c_int, [_P, _P, _P, C.c_int64, _I, _P]),
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_stretch': (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'taco_frames_pitch': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     'taco_corpus_batch': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -543,6 +544,74 @@ def frames_stretch(mag_t, frames=None, step_q=None, frames_per_unit=1, Fo=None, 
     _check(_lib.taco_frames_stretch(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(step_q), ptr(out), ptr(frames_out), B, Cw, F, Fo,
                                     stream_ptr()), 'taco_frames_stretch')
     return out, frames_out
+
+
+PITCH_ONE, PITCH_MIN_STEP, PITCH_MAX_STEP, PITCH_MAX_LIFTER = 65536, 32768, 131072, 64   # include/taco_hip.h
+
+
+def pitch_step(semitones) -> int:
+    """A pitch shift in semitones (0: the model's own, +12 an octave up) -> step_q of taco_frames_pitch =
+    round(65536 * 2^(-semitones / 12)), the source bins advanced per output bin in units of 2^-16; ValueError outside [-12, 12] or for
+    a non-finite value"""
+    try:
+        semitones = float(semitones)
+    except (TypeError, ValueError):
+        raise ValueError('pitch must be a number of semitones in [-12, 12], got %r' % (semitones,)) from None
+    if not -12.0 <= semitones <= 12.0:   # (NaN fails both comparisons)
+        raise ValueError('pitch must be in [-12, 12] semitones, got %r' % (semitones,))
+    return int(round(65536.0 * 2.0 ** (-semitones / 12.0)))
+
+
+def frames_pitch(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, out=None):
+    """Pitch on the magnitude frames (include/taco_hip.h taco_frames_pitch): mag_t (B, C, F) fp32 on the device, C - 1 a power of two
+    in [8, 1024] -> out (B, C, F) fp32: in the first F_b = clamp(frames[b] * frames_per_unit, 0, F) frames of row b the log-excitation
+    is warped along the bin axis at step_q[b] / 65536 source bins per output bin under the frame's own log-envelope (the cepstrum's
+    quefrencies 0 .. lifter), zeros behind.
+    frames: (B) int32 on the device, or None (all F frames).  step_q: None (65536: a copy), an int (the whole batch), a host sequence
+    of B ints (checked against [32768, 131072], then uploaded) or a (B) int32 tensor on the device (clamped there, never read here).
+    lifter: 1 .. min(64, (C - 1) / 2); the default 32 (quefrencies up to 2 ms at 16 kHz) is untuned.  out: the caller's own buffer;
+    default: a fresh one.  Enqueued on the current stream; nothing is read back and nothing waits."""
+    who = 'frames_pitch'
+    if not torch.is_tensor(mag_t) or mag_t.dim() != 3 or mag_t.dtype != torch.float32 or min(mag_t.shape) < 1:
+        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, C, F), got %s %s'
+                         % (who, getattr(mag_t, 'dtype', type(mag_t)), tuple(getattr(mag_t, 'shape', ()))))
+    if not mag_t.is_contiguous():
+        raise ValueError('%s: mag_t must be contiguous' % who)
+    B, Cw, F = mag_t.shape
+    dev = mag_t.device
+    if not 9 <= Cw <= 1025 or (Cw - 1) & (Cw - 2):
+        raise ValueError('%s: C - 1 must be a power of two in [8, 1024], got C = %d' % (who, Cw))
+    if F > STRETCH_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
+    if frames is not None and (not torch.is_tensor(frames) or tuple(frames.shape) != (B,) or frames.dtype != torch.int32
+                               or frames.device != dev or not frames.is_contiguous()):
+        raise ValueError('%s: frames must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
+    if isinstance(frames_per_unit, bool) or int(frames_per_unit) != frames_per_unit or int(frames_per_unit) < 1:
+        raise ValueError('%s: frames_per_unit must be an integer >= 1, got %r' % (who, frames_per_unit))
+    qmax = min(PITCH_MAX_LIFTER, (Cw - 1) // 2)
+    if isinstance(lifter, bool) or int(lifter) != lifter or not 1 <= int(lifter) <= qmax:
+        raise ValueError('%s: lifter must be an integer in [1, %d] at C = %d, got %r' % (who, qmax, Cw, lifter))
+    if step_q is None:
+        pass
+    elif torch.is_tensor(step_q) and step_q.device.type != 'cpu':
+        if tuple(step_q.shape) != (B,) or step_q.dtype != torch.int32 or step_q.device != dev or not step_q.is_contiguous():
+            raise ValueError('%s: step_q on a device must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
+    else:
+        one = not torch.is_tensor(step_q) and not hasattr(step_q, '__len__')
+        host = _host_int32([step_q] * B if one else step_q, B, who + ': step_q')
+        if min(host) < PITCH_MIN_STEP or max(host) > PITCH_MAX_STEP:
+            raise ValueError('%s: step_q must be in [%d, %d] (+12 to -12 semitones), got %r'
+                             % (who, PITCH_MIN_STEP, PITCH_MAX_STEP, step_q if one else host))
+        step_q = torch.tensor(host, dtype=torch.int32).to(dev)
+    out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
+    m0, o0, nbytes = mag_t.data_ptr(), out.data_ptr(), B * Cw * F * 4
+    if o0 < m0 + nbytes and m0 < o0 + nbytes:
+        raise ValueError('%s: out may not overlap mag_t' % who)
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_frames_pitch(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(step_q), int(lifter), ptr(out), B, Cw, F,
+                                  stream_ptr()), 'taco_frames_pitch')
+    return out
 
 
 DTW_MAX_FRAMES, DTW_MAX_K, DTW_MAX_C = 1024, 32, 128   # TACO_DTW_MAX_FRAMES / _K / _C

@@ -31,7 +31,14 @@ frames are resampled on the device between the de-normalisation and Griffin-Lim 
 finds phases for the new length: the duration changes, the pitch does not.  prompt_NNN.wav holds the stretched audio, 300 (Fo_b - 1)
 samples before any trim, and prompt_NNN_rate.npy holds (step_q, Fo_b) as int32; the spectrogram, alignment, length and score files
 stay the model's own output.  With --stop the stretch and the vocoder run over each prompt's own len_b r frames, phases drawn on the
-device.  Nobody has listened to the result.  It combines with every option above; with --long the pieces of a prompt inherit its rate."""
+device.  Nobody has listened to the result.  It combines with every option above; with --long the pieces of a prompt inherit its rate.
+--pitch SEMITONES [--lifter Q] (opt-in, not in the reference): the pitch, 0 the model's own, +3 higher, -3 lower, -12 <= SEMITONES <= 12.
+Right behind the de-normalisation every magnitude frame is split on the device into a smooth log-envelope (the Q lowest quefrencies of
+its cepstrum; default 32, untuned) and the rest; the rest alone -- the harmonics -- is moved along the bin axis and put back under the
+unmoved envelope (lib.frames_pitch, taco_frames_pitch), so the formants and the duration stay.  prompt_NNN_pitch.npy holds (step_q,
+lifter) as int32; every other file keeps its size, and the spectrogram, alignment, length, score and rate files stay the model's own.
+--pitch 0 writes the audio of a run without --pitch.  Nobody has listened to the result.  It combines with every option above (it runs
+in front of the stretch of --rate); with --long the pieces of a prompt inherit its pitch."""
 from __future__ import annotations
 
 import argparse
@@ -110,9 +117,30 @@ def rate_steps(rate, n):
     return [lib.stretch_step(rate)] * (1 if n is None else n)
 
 
+def pitch_steps(pitch, n):
+    """`pitch` of test(): None, a number or a sequence of n numbers of semitones in [-12, 12] -> None or the n step_q values
+    (lib.pitch_step); ValueError"""
+    if pitch is None:
+        return None
+    if hasattr(pitch, '__len__'):
+        if n is not None and len(pitch) != n:
+            raise ValueError('pitch (--pitch): %d pitches for %d prompts' % (len(pitch), n))
+        return [lib.pitch_step(x) for x in pitch]
+    return [lib.pitch_step(pitch)] * (1 if n is None else n)
+
+
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True):
+                  vocode=True, pitch=None, lifter=32):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given); ValueError."""
+    if pitch is not None:
+        if not vocode:
+            raise ValueError('pitch (--pitch) shifts the magnitudes in front of Griffin-Lim: it needs vocode')
+        try:
+            pitch_steps(pitch, None)
+        except ValueError as e:
+            raise ValueError('pitch (--pitch): %s' % e) from None
+        if isinstance(lifter, bool) or int(lifter) != lifter or not 1 <= int(lifter) <= lib.PITCH_MAX_LIFTER:
+            raise ValueError('lifter (--lifter) must be an integer in [1, %d], got %r' % (lib.PITCH_MAX_LIFTER, lifter))
     if rate is not None:
         if not vocode:
             raise ValueError('rate (--rate) stretches the magnitudes in front of Griffin-Lim: it needs vocode')
@@ -135,14 +163,15 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None):
+                 rate=None, pitch=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
     ascore (--align-scores): the prompt's 8 alignment scores, written as _ascore.npy (float64) next to _align.png, the attention picture
     over the kept alignment rows at `zoom` pixels per cell.
     rate (--rate): (step_q, Fo_b) of the prompt, written as _rate.npy; wav is then the stretched waveform and keeps 300 (Fo_b - 1)
-    samples, whatever len_b says."""
+    samples, whatever len_b says.
+    pitch (--pitch): (step_q, lifter) of the prompt, written as _pitch.npy; nothing else depends on it."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -154,6 +183,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         if wav is not None:
             wav = wav[:300 * max(0, int(rate[1]) - 1)]
         np.save(path + '_rate.npy', np.asarray(rate, dtype=np.int32))
+    if pitch is not None:
+        np.save(path + '_pitch.npy', np.asarray(pitch, dtype=np.int32))
     np.save(path + '_spec.npy', spec)
     np.save(path + '_align.npy', align)
     if wav is not None:
@@ -170,7 +201,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None):
+         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -203,9 +234,15 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     are then drawn on the device), else over all frames.  prompt_NNN.wav holds 300 (Fo_b - 1) samples, Fo_b = lib.stretch_frames of
     those frames -- cut on the host by that formula, or with finishing on the device from the stretch's own frames_out -- and
     prompt_NNN_rate.npy (step_q, Fo_b) as int32.  Every other file is the model's own output, unstretched; without `rate` every file
-    is what it was."""
-    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode)
+    is what it was.
+    `pitch` (needs `vocode`) / `lifter`: None, a pitch shift in semitones in [-12, 12] (0: the model's own) or a sequence with one per
+    prompt; with `long`, a prompt's pieces inherit its pitch.  The harmonics of every magnitude frame the vocoder is given are moved
+    under the frame's own envelope of `lifter` quefrencies (invert_spectrogram(pitch=...), in front of the stretch of `rate`): over the
+    row's own len_b r frames wherever the vocoder gets the lengths, else over all frames.  prompt_NNN_pitch.npy holds (step_q, lifter)
+    as int32; no file changes its size, the model's own files stay what they are, and pitch 0 gives the audio of pitch None."""
+    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter)
     steps = rate_steps(rate, len(prompts))
+    row_pitch = pitch_steps(pitch, len(prompts))
     long = long_options(long)
     if long is not None and not vocode:
         raise ValueError('long (--long) joins waveforms: it needs vocode')
@@ -254,13 +291,16 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         wav = conv = pcm = trim = None
         if vocode:
             fout = None
+            shift = {}
+            if row_pitch is not None:   # (step_q as the device takes it: no way back through semitones)
+                shift = dict(pitch=torch.tensor(row_pitch[n:n + Bn], dtype=torch.int32).cuda(), lifter=lifter)
             if steps is None:
                 wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None)
+                                         want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None, **shift)
             else:   # (the rows' own frames whenever there is a rule: the host's Fo_b and the device's frames_out are then one number)
                 *wav, fout = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
                                                 want_conv=gl_momentum is not None, lengths=model.lengths if stop is not None else None,
-                                                rate=[q / 65536.0 for q in row_steps[n:n + Bn]])
+                                                rate=[q / 65536.0 for q in row_steps[n:n + Bn]], **shift)
                 wav = wav[0] if gl_momentum is None else wav
             if gl_momentum is not None:
                 wav, conv = wav[0], wav[1].cpu().numpy()
@@ -298,14 +338,20 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             return None
         return row_steps[row], lib.stretch_frames(F if len_b is None else min(int(len_b) * config.r, F), row_steps[row])
 
+    def pitch_of(row):
+        """(step_q, lifter) of global row `row`, or None without a pitch"""
+        return None if row_pitch is None else (row_pitch[row], int(lifter))
+
     n = 0
     row_steps = steps
     if long is not None:
+        if row_pitch is not None:
+            row_pitch = [row_pitch[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
         L = None
         if steps is not None:   # a piece has its prompt's rate; every row of the joined buffer holds the slowest one's samples
             row_steps = [steps[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
             L = 300 * (max(5, lib.stretch_capacity(F, min(row_steps, default=lib.STRETCH_ONE))) - 1)
-        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of)
+        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of)
         print('wrote %d samples to %s' % (n, out_dir))
         return n
     for batch in load_prompts(prompts, ivocab):
@@ -314,7 +360,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         for i in range(Bn):
             wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
             write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
-                         rate=rate_of(n, len_b))
+                         rate=rate_of(n, len_b), pitch=pitch_of(n))
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
             if found:
                 print('WARNING prompt %d: %s' % (n, ', '.join(found)))
@@ -323,9 +369,11 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     return n
 
 
-def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None):
+def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None,
+               pitch_of=lambda row: None):
     """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write.  L: the samples
-    per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b): what write_prompt gets as `rate`"""
+    per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b) / pitch_of(row): what write_prompt gets as
+    `rate` / `pitch`"""
     pause_ms, fade_ms = long
     split = [split_prompt(p) for p in prompts]
     groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
@@ -363,7 +411,7 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
             for k in range(a, b):
                 spec, al, len_b, trim, conv, score, text_len = arrays[k]
                 write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score,
-                             rate=rate_of(row + k, len_b))
+                             rate=rate_of(row + k, len_b), pitch=pitch_of(row + k))
                 names = marks(score, text_len) if score is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
@@ -417,13 +465,21 @@ def parse_args(argv=None):
     ap.add_argument('--rate', type=float, default=None, metavar='R',
                     help='speaking rate, 0.25 <= R <= 4: 1.0 is the model\'s own, 0.8 slower, 1.25 faster; the magnitudes are stretched on '
                          'the device in front of Griffin-Lim, so the pitch stays; writes prompt_NNN_rate.npy (not in the reference)')
+    ap.add_argument('--pitch', type=float, default=None, metavar='SEMITONES',
+                    help='pitch shift, -12 <= SEMITONES <= 12: 0 is the model\'s own, 3 higher, -3 lower; the harmonics of every magnitude '
+                         'frame are moved under its own spectral envelope on the device in front of Griffin-Lim, so the formants and the '
+                         'duration stay; writes prompt_NNN_pitch.npy (not in the reference)')
+    ap.add_argument('--lifter', type=int, default=32, metavar='Q',
+                    help='--pitch: the quefrencies 0 .. Q of the cepstrum make the envelope, 1 <= Q <= 64 (default 32 = 2 ms at 16 kHz: '
+                         'a choice, not tuned by ear)')
     ap.add_argument('--align-scores', action='store_true',
                     help='score every prompt\'s attention on the device: prompt_NNN_ascore.npy (8 values: n, end, pad_steps, back, skip, '
                          'covered, focus, pad_mass), prompt_NNN_align.png, and a WARNING line for a prompt the (untuned) thresholds mark')
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
     try:
-        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate)
+        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
+                      lifter=a.lifter)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -439,4 +495,4 @@ if __name__ == '__main__':
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
-         align_scores=a.align_scores, rate=a.rate)
+         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter)
