@@ -408,6 +408,61 @@ int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_pe
 int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
                       float* out, int B, int C, int F, void* stream);
 
+/* F0 tracker (no reference counterpart): the per-frame pitch of magnitude frames, measured where the two prosody controls above
+ * run -- the instrument that stands in for listening to them.  By Wiener-Khinchin the cosine transform of a frame's power spectrum is
+ * the autocorrelation of the windowed frame, so no waveform, phase or vocoder run is needed: the same call serves the model's output,
+ * the frames behind taco_frames_pitch / taco_frames_stretch and a corpus' recorded stft targets.
+ *   mag_t  (B, C, F) fp32, the frame index contiguous; C - 1 a power of two, 8 <= C - 1 <= 1024; N = 2 (C - 1)
+ *   frames, frames_per_unit: as taco_frames_pitch: F_b = clamp(frames[b] * frames_per_unit, 0, F), NULL: F_b = F; never read by the host
+ *   weight (C) fp32 or NULL (all ones): a weight per bin of the power spectrum (the Python layer undoes the features' pre-emphasis
+ *          with it; it can also band-limit)
+ *   gain   (L) fp32 or NULL (all ones), L = lag_max - lag_min + 3: gain[j] multiplies lag lag_min - 1 + j (the Python layer passes
+ *          the inverse of the analysis window's own autocorrelation: Boersma's correction)
+ *   2 <= lag_min <= lag_max <= C - 2 and L <= TACO_F0_MAX_LAGS; 0 < ratio <= 1; threshold any number
+ *   period (B, F), strength (B, F) fp32: required; acf (B, L, F) fp32 or NULL
+ * For frame f < F_b of row b, m[k] = mag_t[b, k, f], u[0] = u[C-1] = 1 and u[k] = 2 otherwise, in real numbers:
+ *   p[k] = u[k] weight[k] m[k]^2;   r0 = sum_k p[k];   r[n] = sum_k p[k] cos(2 pi n k / N), n = lag_min - 1 .. lag_max + 1
+ *   r0 > 0 false (zero, underflowed, NaN): the frame is unvoiced, period = strength = +0 and its acf column is +0.  Otherwise
+ *   y[n] = (r[n] / r0) gain[n - lag_min + 1];   acf[b, j, f] = y[lag_min - 1 + j]
+ * computed in fp32 (a cosine table from cospif; the product on v_mfma_f32_32x32x2_f32, one ordered chain over the bin pairs per
+ * lag and frame) and held by the tests to an fp64
+ * restatement within a tolerance sized from a float32 restatement (tests/f0_ref.py).  The pick is EXACT: every operation below is one
+ * fp32 operation rounded to nearest even on the fp32 values y that acf holds, nothing contracted, so a NumPy float32 restatement
+ * applied to the device's own acf gives the device's period and strength bit for bit:
+ *   candidates: the n in [lag_min, lag_max] with y[n] > y[n-1] and y[n] >= y[n+1]; none: unvoiced
+ *   g = the largest candidate value; n* = the smallest candidate with y[n] >= ratio * g (the bias towards short lags suppresses
+ *   octave-down errors); y[n*] >= threshold false: unvoiced
+ *   a = y[n*-1] - y[n*+1], t = y[n*] + y[n*], d = (y[n*-1] - t) + y[n*+1];  delta = 0 when d == 0, else (0.5f * a) / d correctly
+ *   rounded and clamped to [-0.5, 0.5];  period = float(n*) + delta in samples (F0 = sr / period is the host's to form);
+ *   strength = y[n*] (it may exceed 1 with a gain)
+ * Further:
+ *   - period, strength and acf are +0 for F_b <= f < F;
+ *   - every element of the outputs is written and nothing outside them, for any F and any 4-byte alignment;
+ *   - columns f >= F_b, every other row and every other frame have no influence on a frame (they may hold NaN); a non-finite value
+ *     inside a frame leaves unspecified values in that frame's outputs only;
+ *   - the bits of a frame depend on its own C bins and the arguments alone -- not on B, F, its position f or the buffers'
+ *     alignment; no atomics; with acf == NULL period and strength have the bits of the call with it.
+ * One launch of B x ceil(F / 32) workgroups, no workspace, no allocation, no host synchronisation, no workgroup waits for another
+ * one: graph-capturable, and a replay follows whatever frames holds at replay time.  NULL mag_t / period / strength, an output
+ * overlapping mag_t, B or F <= 0, F > TACO_STRETCH_MAX_FRAMES, C - 1 not a power of two in 8 .. 1024, lags out of range, ratio
+ * outside (0, 1] or NaN, a NaN threshold and frames_per_unit < 1 return TACO_EINVAL, with a message that names the argument, before
+ * anything is enqueued.  TACO_VERSION did not change with this entry point: detect it by the symbol.
+ * Not here: smoothing across frames (Viterbi), F0 from mel frames.  The Python layer's ratio 0.9 and threshold 0.3 are untuned. */
+#define TACO_F0_MAX_LAGS 512
+int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_unit, const float* weight, const float* gain,
+                   int lag_min, int lag_max, float ratio, float threshold, float* period, float* strength, float* acf,
+                   int B, int C, int F, void* stream);
+
+/* Statistics of a pitch track: a frame counts when f < F_b and period[b, f] > 0 -- with `other` (B, F) given, other[b, f] > 0 too.
+ *   x_f = log2(period[b, f]) without other;  x_f = log2(other[b, f]) - log2(period[b, f]) with it: the octaves by which period's
+ *   pitch lies above other's (12 x the mean: semitones)
+ *   stats (B, 3) fp32 = (the count as a float, the mean of x, the population standard deviation of x); the last two 0 at count 0
+ * fp32, one workgroup per row, two passes in a fixed order (the sum, then the squares around the mean): no atomics, no workspace,
+ * graph-capturable; frames / frames_per_unit as above.  NULL period / stats, B or F <= 0, F > TACO_STRETCH_MAX_FRAMES and
+ * frames_per_unit < 1 return TACO_EINVAL before anything is enqueued.  Detect it by the symbol. */
+int taco_f0_stats(const float* period, const float* other, const int32_t* frames, int frames_per_unit, float* stats, int B, int F,
+                  void* stream);
+
 /* ---- corpus boundary ----------------------------------------------------------------------------------------------------- */
 /* The batch gather of the training corpus with the reference's target standardisation (data_input.py:55-65
  * `(x - mean) / std`, which the reference applies to the whole corpus on the host) fused in: the inverse of

@@ -851,6 +851,225 @@ __global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const fl
   }
 }
 
+// taco_frames_f0: the pitch of a magnitude frame.  By Wiener-Khinchin the cosine transform of the power spectrum is the
+// autocorrelation of the windowed frame: p[k] = u[k] weight[k] m[k]^2, r[n] = sum_k p[k] cos(2 pi n k / N) over the band of lags
+// n = lag_min - 1 .. lag_max + 1, y[n] = (r[n] / r0) gain[n - lag_min + 1], and the period is the first high local maximum of y,
+// refined by a parabola (include/taco_hip.h has the definition and the exact rules of the pick).
+// The form of frames_pitch_kernel's cepstrum: a workgroup of kF0Waves waves owns kF0Frames = 32 consecutive frames of one row, the
+// frame index is the lane's low five bits (128 contiguous bytes per bin row, and the column of a 32x32x2 fp32 MFMA).  p is formed
+// once per element into LDS (C x 32 floats, and one row of zeros behind the top bin, which pairs with it), its r0 summed beside it
+// from 2 kF0Waves partials in a fixed order.  The product (L x C) (C x 32) is dealt to the waves by tiles of 32 lags: wave w owns
+// tiles w and, for L > 32 kF0Waves, w + kF0Waves (NT = 1 | 2; a tile's chain of MFMAs runs over the bin pairs in ascending order
+// whichever NT, so the bits do not depend on it), A from the cosine table indexed (n k) & (N - 1), B from p.  Behind a barrier the
+// y tile takes p's place in LDS; the pick reads it with 2 kF0Waves threads per frame, each over a contiguous run of lags -- the
+// largest candidate (a maximum: no order), then the smallest lag at or above ratio * g -- and one thread per frame finishes.
+// A tile behind F_b writes zeros and loads nothing; a frame behind F_b inside a live tile has p = 0, hence r0 = 0 and zeros.
+constexpr int kF0Frames = 32;
+constexpr int kF0Waves = 8;
+constexpr int kF0Parts = 2 * kF0Waves;   // threads per frame: forming p, and in the pick
+static_assert(TACO_F0_MAX_LAGS <= 2 * 32 * kF0Waves, "two tiles of 32 lags per wave at the most");
+template <int NT>
+__global__ __launch_bounds__(64 * kF0Waves) void frames_f0_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                                  int frames_per_unit, const float* __restrict__ weight,
+                                                                  const float* __restrict__ gain, int lag_min, int lag_max, float ratio,
+                                                                  float threshold, float* __restrict__ period,
+                                                                  float* __restrict__ strength, float* __restrict__ acf, int C, int F,
+                                                                  int ntile) {
+#pragma clang fp contract(off)
+  __shared__ float tab[2 * (kPitchMaxC - 1)];
+  __shared__ float pw[(kPitchMaxC + 1) * kF0Frames];   // p[k][f], k = 0 .. C (row C: zeros); behind the product y[j][f]
+  __shared__ float part[kF0Parts * kF0Frames];         // the partial sums of r0; in the pick the parts' largest candidates
+  __shared__ int first[kF0Parts * kF0Frames];          // the parts' first candidates at or above ratio * g
+  __shared__ float r0s[kF0Frames];
+  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
+  int Fb = F;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int pt = 2 * wave + h;   // = tid >> 5
+  const int f0 = tile * kF0Frames, f = f0 + fl;
+  const int L = lag_max - lag_min + 3;
+  const bool live = f < Fb, inside = f < F;
+  float* __restrict__ ac = acf ? acf + (int64_t)b * L * F + f : nullptr;   // (L F <= 512 * 8192: the offsets below fit 32 bits)
+  if (f0 >= Fb) {   // (uniform) behind the row's end
+    if (inside) {
+      if (tid < kF0Frames) period[(int64_t)b * F + f] = strength[(int64_t)b * F + f] = 0.f;
+      if (ac)
+        for (int j = pt; j < L; j += kF0Parts) ac[j * F] = 0.f;
+    }
+    return;
+  }
+  const int N = 2 * (C - 1), mask = N - 1;
+  for (int j = tid; j < N; j += 64 * kF0Waves) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
+
+  // ---- p and r0 ----
+  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;   // (C F <= 1025 * 8192)
+  float r0p = 0.f;
+#pragma unroll 4
+  for (int k = pt; k <= C; k += kF0Parts) {
+    float v = 0.f;
+    if (live && k < C) {
+      const float m = src[k * F];
+      const float w = weight ? weight[k] : 1.0f;
+      v = (((k == 0 || k == C - 1) ? 1.0f : 2.0f) * w) * (m * m);
+    }
+    pw[k * kF0Frames + fl] = v;
+    r0p += v;
+  }
+  part[pt * kF0Frames + fl] = r0p;
+  __syncthreads();
+  if (tid < kF0Frames) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kF0Parts; ++w) t += part[w * kF0Frames + tid];
+    r0s[tid] = t;
+  }
+
+  // ---- r[n] over the band ----
+  f32x16 acc[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  if (32 * wave < L) {   // (uniform per wave; rows at and behind L of a tile are computed at valid table indices and dropped)
+    const int n0 = lag_min - 1 + 32 * wave + fl;
+#pragma unroll 4
+    for (int k0 = 0; k0 < C; k0 += 2) {
+      const int k = k0 + h;   // (k == C: the row of zeros)
+      const float v = pw[k * kF0Frames + fl];
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((n0 + 32 * kF0Waves * j) * k) & mask], v, acc[j], 0, 0, 0);
+    }
+  }
+  __syncthreads();   // (nothing reads p from here on: pw is the y tile's)
+  const float r0 = r0s[fl];
+  const bool sounding = r0 > 0.f;   // (false for zero, underflowed and NaN)
+#pragma unroll
+  for (int j = 0; j < NT; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = 32 * (wave + kF0Waves * j) + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (row < L) pw[row * kF0Frames + fl] = sounding ? __fdiv_rn(acc[j][r], r0) * (gain ? gain[row] : 1.0f) : 0.f;
+    }
+  __syncthreads();
+  if (ac && inside)
+    for (int j = pt; j < L; j += kF0Parts) ac[j * F] = pw[j * kF0Frames + fl];
+
+  // ---- the pick ----  row i of the tile is lag lag_min - 1 + i; the candidates are rows 1 .. L - 2
+  const int chunk = (L - 2 + kF0Parts - 1) / kF0Parts;
+  const int lo = 1 + pt * chunk, hi = min(lo + chunk, L - 1);
+  float g = -INFINITY;
+  for (int i = lo; i < hi; ++i) {
+    const float y0 = pw[i * kF0Frames + fl];
+    if (y0 > pw[(i - 1) * kF0Frames + fl] && y0 >= pw[(i + 1) * kF0Frames + fl] && y0 > g) g = y0;
+  }
+  part[pt * kF0Frames + fl] = g;   // (its sums of r0 were read in front of the product)
+  __syncthreads();
+  g = -INFINITY;
+#pragma unroll
+  for (int w = 0; w < kF0Parts; ++w) {
+    const float v = part[w * kF0Frames + fl];
+    g = v > g ? v : g;
+  }
+  const float bar = ratio * g;
+  int at = 0x7fffffff;
+  for (int i = lo; i < hi; ++i) {
+    const float y0 = pw[i * kF0Frames + fl];
+    if (y0 > pw[(i - 1) * kF0Frames + fl] && y0 >= pw[(i + 1) * kF0Frames + fl] && y0 >= bar) {
+      at = i;
+      break;
+    }
+  }
+  first[pt * kF0Frames + fl] = at;
+  __syncthreads();
+  if (tid < kF0Frames && inside) {
+#pragma unroll
+    for (int w = 0; w < kF0Parts; ++w) at = min(at, first[w * kF0Frames + tid]);
+    float per = 0.f, str = 0.f;
+    if (g > -INFINITY && at != 0x7fffffff) {
+      const float ym = pw[(at - 1) * kF0Frames + tid], y0 = pw[at * kF0Frames + tid], yp = pw[(at + 1) * kF0Frames + tid];
+      if (y0 >= threshold) {
+        const float a = ym - yp;
+        const float t = y0 + y0;
+        const float d = (ym - t) + yp;
+        float delta = 0.f;
+        if (d != 0.f) {
+          delta = __fdiv_rn(0.5f * a, d);
+          delta = delta < -0.5f ? -0.5f : (delta > 0.5f ? 0.5f : delta);
+        }
+        per = (float)(lag_min - 1 + at) + delta;
+        str = y0;
+      }
+    }
+    period[(int64_t)b * F + f] = per;
+    strength[(int64_t)b * F + f] = str;
+  }
+}
+
+// taco_f0_stats: count, mean and population standard deviation of x_f = log2(period) -- or log2(other) - log2(period), the octaves
+// by which period's pitch lies above other's -- over the voiced frames of a row.  One workgroup per row, two passes (the sum, then
+// the squares around the mean), a thread's frames in ascending order and the threads' partials down a fixed tree.
+__global__ __launch_bounds__(256) void f0_stats_kernel(const float* __restrict__ period, const float* __restrict__ other,
+                                                       const int32_t* __restrict__ frames, int frames_per_unit,
+                                                       float* __restrict__ stats, int F) {
+  __shared__ float red[256];
+  __shared__ int cnt[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int Fb = F;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  const float* __restrict__ p = period + (int64_t)b * F;
+  const float* __restrict__ o = other ? other + (int64_t)b * F : nullptr;
+  float s = 0.f;
+  int c = 0;
+  for (int f = tid; f < Fb; f += 256) {
+    const float pv = p[f], ov = o ? o[f] : 1.0f;
+    if (pv > 0.f && ov > 0.f) {
+      s += o ? log2f(ov) - log2f(pv) : log2f(pv);
+      ++c;
+    }
+  }
+  red[tid] = s;
+  cnt[tid] = c;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      red[tid] += red[tid + w];
+      cnt[tid] += cnt[tid + w];
+    }
+    __syncthreads();
+  }
+  const int n = cnt[0];
+  const float mean = n > 0 ? red[0] / (float)n : 0.f;
+  __syncthreads();
+  s = 0.f;
+  for (int f = tid; f < Fb; f += 256) {
+    const float pv = p[f], ov = o ? o[f] : 1.0f;
+    if (pv > 0.f && ov > 0.f) {
+      const float x = (o ? log2f(ov) - log2f(pv) : log2f(pv)) - mean;
+      s += x * x;
+    }
+  }
+  red[tid] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    stats[3 * b] = (float)n;
+    stats[3 * b + 1] = mean;
+    stats[3 * b + 2] = n > 0 ? sqrtf(red[0] / (float)n) : 0.f;
+  }
+}
+
 // taco_corpus_batch: the forward map denorm_unframe_kernel inverts, fused into the batch gather.  out[b, e] =
 // (float(src[index[b], e]) - mean[e % C]) / stdv[e % C] over rows of `row` = Td * C elements; T = _Float16 (the corpus as
 // preprocess stores it) or float.  One IEEE subtraction and one correctly rounded division per element: the bits of NumPy's
@@ -1349,6 +1568,55 @@ extern "C" int taco_frames_pitch(const float* mag_t, const int32_t* frames, int 
     TACO_KLAUNCH((frames_pitch_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, step_q,
                  lifter, out, C, F, ntile);
   TACO_LAUNCH_CHECK("frames_pitch");
+  return TACO_OK;
+}
+extern "C" int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_unit, const float* weight, const float* gain,
+                              int lag_min, int lag_max, float ratio, float threshold, float* period, float* strength, float* acf,
+                              int B, int C, int F, void* stream) {
+  TACO_REQUIRE(mag_t, "frames_f0: mag_t is NULL");
+  TACO_REQUIRE(period, "frames_f0: period is NULL");
+  TACO_REQUIRE(strength, "frames_f0: strength is NULL");
+  TACO_REQUIRE(B > 0, "frames_f0: B=%d must be positive", B);
+  TACO_REQUIRE(C >= 9 && C <= kPitchMaxC && ((C - 1) & (C - 2)) == 0,
+               "frames_f0: C=%d: C - 1 must be a power of two in 8..%d", C, kPitchMaxC - 1);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "frames_f0: F=%d must be in 1..%d", F, TACO_STRETCH_MAX_FRAMES);
+  TACO_REQUIRE(lag_min >= 2 && lag_min <= lag_max && lag_max <= C - 2,
+               "frames_f0: lag_min=%d, lag_max=%d must satisfy 2 <= lag_min <= lag_max <= %d at C=%d", lag_min, lag_max, C - 2, C);
+  const int L = lag_max - lag_min + 3;
+  TACO_REQUIRE(L <= TACO_F0_MAX_LAGS, "frames_f0: lag_min=%d .. lag_max=%d are %d lags with their neighbours, at most %d", lag_min,
+               lag_max, L, TACO_F0_MAX_LAGS);
+  TACO_REQUIRE(ratio > 0.f && ratio <= 1.f, "frames_f0: ratio=%g must be in (0, 1]", (double)ratio);   // (NaN fails both)
+  TACO_REQUIRE(threshold == threshold, "frames_f0: threshold is NaN");
+  TACO_REQUIRE(frames_per_unit >= 1, "frames_f0: frames_per_unit=%d must be >= 1", frames_per_unit);
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t);
+  const uint64_t mbytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4, row = (uint64_t)B * (uint64_t)F * 4;
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(period), s0 = reinterpret_cast<uintptr_t>(strength),
+                  a0 = reinterpret_cast<uintptr_t>(acf);
+  TACO_REQUIRE(p0 + row <= m0 || m0 + mbytes <= p0, "frames_f0: period overlaps mag_t");
+  TACO_REQUIRE(s0 + row <= m0 || m0 + mbytes <= s0, "frames_f0: strength overlaps mag_t");
+  TACO_REQUIRE(!acf || a0 + row * (uint64_t)L <= m0 || m0 + mbytes <= a0, "frames_f0: acf overlaps mag_t");
+  const int ntile = cdiv(F, kF0Frames);
+  const int64_t blocks = (int64_t)B * ntile;
+  TACO_REQUIRE(blocks <= 0x7fffffff, "frames_f0: B=%d x F=%d needs more than 2^31 workgroups", B, F);
+  hipStream_t s = as_stream(stream);
+  if (L <= 32 * kF0Waves)
+    TACO_KLAUNCH((frames_f0_kernel<1>), dim3((unsigned)blocks), dim3(64 * kF0Waves), 0, s, mag_t, frames, frames_per_unit, weight, gain,
+                 lag_min, lag_max, ratio, threshold, period, strength, acf, C, F, ntile);
+  else
+    TACO_KLAUNCH((frames_f0_kernel<2>), dim3((unsigned)blocks), dim3(64 * kF0Waves), 0, s, mag_t, frames, frames_per_unit, weight, gain,
+                 lag_min, lag_max, ratio, threshold, period, strength, acf, C, F, ntile);
+  TACO_LAUNCH_CHECK("frames_f0");
+  return TACO_OK;
+}
+extern "C" int taco_f0_stats(const float* period, const float* other, const int32_t* frames, int frames_per_unit, float* stats, int B,
+                             int F, void* stream) {
+  TACO_REQUIRE(period, "f0_stats: period is NULL");
+  TACO_REQUIRE(stats, "f0_stats: stats is NULL");
+  TACO_REQUIRE(B > 0, "f0_stats: B=%d must be positive", B);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "f0_stats: F=%d must be in 1..%d", F, TACO_STRETCH_MAX_FRAMES);
+  TACO_REQUIRE(frames_per_unit >= 1, "f0_stats: frames_per_unit=%d must be >= 1", frames_per_unit);
+  TACO_KLAUNCH(f0_stats_kernel, dim3((unsigned)B), dim3(256), 0, as_stream(stream), period, other, frames, frames_per_unit, stats, F);
+  TACO_LAUNCH_CHECK("f0_stats");
   return TACO_OK;
 }
 // The widest access taco_corpus_batch may use: the largest V in {8 (fp16 only), 4, 2, 1} that divides the row pitch, with the

@@ -19,6 +19,16 @@ the model's OWN 80-band natural-log mel frames along the path, and steps counts 
 checkpoints of this project on the same held-out set.  It is NOT comparable with figures published from other feature extractors
 (mel-generalised cepstra of a vocoder analysis, other band counts, log bases, frame rates or path-length conventions).
 
+--f0 (opt-in): the pitch of the free-running output and of the recording, the standard companions of MCD.  The predicted
+magnitude frames (the decoder's output de-normalised, over each row's own frames) and the recorded ones (the corpus `stft` as
+stored, through lib.corpus_batch + lib.denorm_unframe as `mel` is) are tracked on the device (lib.frames_f0) and summarised there
+(lib.f0_stats); each utterance's row gains F0_COLUMNS: the mean of log2 F0 over its voiced frames, its standard deviation, the
+voiced share of its frames, and the same three of the recording.  The batch line and the final line add the mean difference of
+the pitch level in cents and of the voiced share.  There is NO alignment between the two tracks: lib.frame_dtw returns a cost and
+no path, so these are statistics per utterance, not an F0 error along the warp.  The pick's ratio 0.9 and threshold 0.3 are untuned.
+The sample rate of the lag tables and of the Hz columns is the corpus' own (meta.pkl 'sr', as preprocess records it; 16000 without one),
+and the predicted share is taken over the frames tracked, min(na, F) with F = (max_decode_iter // 4) 4 r.
+
 The final batch is padded to the batch size by repeating its last utterance; the copies are left out of the per-utterance rows and
 of the MCD statistics.  The teacher-forced loss is one number per batch (and the CBHG's batch normalisation sees the whole batch),
 so the padded batch enters the mean loss weighted by its share of real rows.  Without a corpus on disk the synthetic pool of
@@ -39,6 +49,8 @@ from .params import ParamBuffer
 from .train import latest_checkpoint, open_corpus
 
 COLUMNS = ('index', 'na', 'nb', 'steps', 'cost', 'mcd')
+F0_COLUMNS = ('f0_mean', 'f0_sd', 'voiced', 'rec_f0_mean', 'rec_f0_sd', 'rec_voiced')   # appended with --f0; the first two in log2 Hz
+SR = 16000   # of a corpus whose meta.pkl records no 'sr', and of the synthetic pool
 PAD_FLOOR = float(np.float16(np.log(1e-8)))   # the value preprocess stores in the padding frames (fp16 of log(1e-8))
 
 
@@ -79,16 +91,48 @@ def mcd_rows(index, na, nb, steps, cost):
                      cost, mcd], axis=1)
 
 
-def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None):
-    """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  stop: the lib.TacoStopRule of the
+def f0_columns(stats, frames, sr=SR):
+    """lib.f0_stats rows (n, 3) (count, mean and deviation of log2(period in samples)) and the n frame counts they were taken over ->
+    (n, 3) float64: mean log2 F0 in Hz, its deviation, voiced share.  An utterance without a voiced frame has NaN for the first two;
+    one without frames NaN for the share too."""
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1, 3)
+    frames = np.asarray(frames, dtype=np.float64)
+    out = np.full((len(stats), 3), np.nan)
+    some = stats[:, 0] > 0
+    out[some, 0] = np.log2(float(sr)) - stats[some, 1]
+    out[some, 1] = stats[some, 2]
+    np.divide(stats[:, 0], frames, out=out[:, 2], where=frames > 0)
+    return out
+
+
+def f0_rows(rows, stats, na, rec_stats, nb, sr=SR):
+    """rows (n, 6) in the order COLUMNS -> (n, 12): F0_COLUMNS appended.  na / nb: the frames the two tracks were taken over"""
+    return np.concatenate([np.asarray(rows, dtype=np.float64), f0_columns(stats, na, sr), f0_columns(rec_stats, nb, sr)], axis=1)
+
+
+def f0_summary(cols):
+    """(n, 6) in the order F0_COLUMNS -> (mean difference of the pitch level in cents, mean difference of the voiced share), predicted
+    minus recorded, over the utterances that have both; NaN without any"""
+    cols = np.asarray(cols, dtype=np.float64).reshape(-1, 6)
+    level, share = 1200.0 * (cols[:, 0] - cols[:, 3]), cols[:, 2] - cols[:, 5]
+    return (float(np.nanmean(level)) if np.isfinite(level).any() else float('nan'),
+            float(np.nanmean(share)) if np.isfinite(share).any() else float('nan'))
+
+
+def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None,
+             f0=False):
+    """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  f0: rows (n, 12), F0_COLUMNS behind
+    COLUMNS.  stop: the lib.TacoStopRule of the
     free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
     ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection)."""
     torch.cuda.set_device(device)
     dev = torch.device('cuda', device)
     corpus = open_corpus(config.data_path)
     norm = None
+    sr = SR
     if corpus is not None:
         meta, data, norm = corpus
+        sr = int(meta.get('sr', SR))
         config.r, config.vocab_size = meta['r'], len(meta['vocab'])
         if 'speaker' in data:
             config.num_speakers = int(data['speaker'].max()) + 1
@@ -129,7 +173,17 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     raw = torch.empty(B, Td, 80 * r, device=dev)
     nb = torch.empty(B, dtype=torch.int32, device=dev)
     zeros, ones = torch.zeros(80 * r, device=dev), torch.ones(80 * r, device=dev)
-    per = {k: [] for k in ('na', 'nb', 'steps', 'cost')}
+    per = {k: [] for k in ('na', 'nb', 'steps', 'cost') + (('f0', 'rec_f0', 'f0_frames') if f0 else ())}
+    if f0:
+        Cs = batch['stft'].shape[2] // r
+        w, g, lag_min, lag_max = lib.f0_tables(sr, C=Cs)
+        f0_opt = dict(weight=torch.from_numpy(w).to(dev), gain=torch.from_numpy(g).to(dev), lag_min=lag_min, lag_max=lag_max)
+        raw_stft = torch.empty(B, Td, Cs * r, device=dev)
+        mags = torch.empty(B, Cs, (Td // 4) * 4 * r, device=dev)
+        szeros, sones = torch.zeros(Cs * r, device=dev), torch.ones(Cs * r, device=dev)
+        smean, sstd = norm['stft'] if norm is not None and 'stft' in norm else (forced.stft_mean, forced.stft_std)
+        smean = szeros if smean is None else torch.as_tensor(smean, dtype=torch.float32).to(dev)
+        sstd = sones if sstd is None else torch.as_tensor(sstd, dtype=torch.float32).to(dev)
     losses = []
     for i, (index, valid) in enumerate(batches):
         if i:
@@ -143,10 +197,22 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         lib.denorm_unframe(raw, zeros, ones, r, spec=recorded)
         lib.frames_active(recorded, PAD_FLOOR, nb)
         cost, steps, na = free.mel_distortion(recorded, nb, cepstra)
+        if f0:   # the decoder's own frames over lengths * r (max_decode_iter steps wide), then the recording's over nb
+            pmags = lib.denorm_unframe(free.output, smean, sstd, r, want_spec=False, want_mag_t=True)
+            Fp = pmags.shape[2]   # (the tracker counts over clamp(lengths r, 0, Fp); na is lengths r unclamped)
+            pred_stats = lib.f0_stats(lib.frames_f0(pmags, free.lengths, r, **f0_opt)[0], None, free.lengths, r)
+            lib.corpus_batch(feeder.data['stft'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw_stft)
+            lib.denorm_unframe(raw_stft, szeros, sones, r, want_spec=False, want_mag_t=True, mag_t=mags)
+            rec_stats = lib.f0_stats(lib.frames_f0(mags, nb, 1, **f0_opt)[0], None, nb, 1)
         loss = forced._loss.cpu().numpy().astype(np.float64)       # the host synchronisation of the batch
         forced.check()
         free.check()
         got = {'na': na.cpu().numpy(), 'nb': nb.cpu().numpy(), 'steps': steps.cpu().numpy(), 'cost': cost.cpu().numpy()}
+        if f0:
+            got['f0'], got['rec_f0'] = pred_stats.cpu().numpy(), rec_stats.cpu().numpy()
+            got['f0_frames'] = np.minimum(got['na'], Fp)
+            cents, share = f0_summary(np.concatenate([f0_columns(got['f0'][:valid], got['f0_frames'][:valid], sr),
+                                                      f0_columns(got['rec_f0'][:valid], got['nb'][:valid], sr)], axis=1))
         if trace is not None:
             trace.append({'predicted': free.predicted_mel()[0].cpu().numpy(), 'recorded': recorded.cpu().numpy(), 'na': got['na'].copy(),
                           'nb': got['nb'].copy()})
@@ -157,8 +223,14 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         print('batch %d (%d utterances) loss %.1f (seq2seq %.1f + output %.1f) mcd mean %.3f dB worst %.3f dB frames %d / %d'
               % (i, valid, loss[0], loss[1], loss[2], np.nanmean(mcd), np.nanmax(mcd), int(got['na'][:valid].sum()),
                  int(got['nb'][:valid].sum())))
+        if f0:
+            print('batch %d pitch level %+.0f cents, voiced share %+.3f against the recordings (per utterance, not aligned)' % (i, cents, share))
     feeder.close()
     rows = mcd_rows(unpad(batches, [b[0] for b in batches]), *(unpad(batches, per[k]) for k in ('na', 'nb', 'steps', 'cost')))
+    if f0:
+        rows = f0_rows(rows, unpad(batches, per['f0']), unpad(batches, per['f0_frames']), unpad(batches, per['rec_f0']), rows[:, 2], sr)
+        print('held out: pitch level %+.0f cents, voiced share %+.3f against the recordings (untuned tracker, per utterance, not aligned)'
+              % f0_summary(rows[:, 6:]))
     weight = np.array([valid for _, valid in batches], dtype=np.float64)
     mean_loss = float((np.stack(losses)[:, 0] * weight).sum() / weight.sum())
     print('held out: %d utterances, teacher-forced loss %.1f, MCD-DTW mean %.3f dB worst %.3f dB (utterance %d) over %d cepstra of '
@@ -177,6 +249,9 @@ def parse_args(argv=None):
     ap.add_argument('--speaker', type=int, default=None, help='multi-speaker corpus: only the held-out utterances of this speaker')
     ap.add_argument('--cepstra', type=int, default=13, help='DCT coefficients 1 .. N of the 80 mel bands the distance is taken over')
     ap.add_argument('--out-dir', default='log/eval')
+    ap.add_argument('--f0', action='store_true',
+                    help='also track the pitch of the predicted and of the recorded magnitude frames on the device and append '
+                         'F0_COLUMNS to every row (untuned tracker; statistics per utterance, no alignment)')
     return ap.parse_args(argv)
 
 
@@ -187,7 +262,7 @@ def main(argv=None, config=None):
     if config is None:
         c.data_path = 'data/%s/' % a.train_set
     checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
-    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir)
+    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0)
 
 
 if __name__ == '__main__':

@@ -19,6 +19,9 @@ slower or faster and Griffin-Lim finds phases for the new length, so the pitch s
 With `pitch` (opt-in) the harmonics of every magnitude frame are moved along the bin axis under the frame's own spectral envelope before
 Griffin-Lim (taco_frames_pitch): the voice gets higher or lower, the formants and the duration stay.
 
+With `f0` (opt-in) the pitch of the magnitude frames is measured on the device (taco_frames_f0, taco_f0_stats): the frames as de-normalised
+and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective stand-in for listening to those two controls.
+
 `finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
 front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16.
 
@@ -29,6 +32,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from . import lib
@@ -38,7 +42,7 @@ SR = 16000   # test.py:11
 
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
-                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32):
+                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -62,7 +66,35 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     the bits of None), a host sequence of B such numbers, or a (B) int32 device tensor of step_q values (lib.pitch_step): right after
     the de-normalisation the first len_b r frames of every row (all F frames without `lengths`) go through lib.frames_pitch with
     `lifter` quefrencies of envelope (32: untuned), and the result takes the place of the magnitudes on every path above -- in
-    front of the stretch when `rate` is given too.  It changes no phase source and no return shape."""
+    front of the stretch when `rate` is given too.  It changes no phase source and no return shape.
+    f0: None: nothing is measured and the path and the return are what they were.  True, or a dict of lib.frames_f0's keywords
+    (weight, gain, lag_min, lag_max, ratio, threshold; True: lib.f0_tables() and the UNTUNED ratio 0.9 / threshold 0.3) and optionally
+    'lengths', the (B) int32 decoder steps to measure over when the vocoder itself is not given them: the frames are tracked as
+    de-normalised, behind `pitch`, and behind `rate`, each over the row's own frames, and the return gains one last element (a bare
+    waveform becomes (waveform, tracks)), the dict
+      'model' / 'vocoder': (period, strength) (B, F) of the de-normalised frames / of the frames Griffin-Lim was handed (the same
+                 tensors without pitch and rate; over Fo frames with a rate), 'pitched': behind `pitch`, in front of the stretch
+      'model_stats' / 'vocoder_stats': lib.f0_stats of those periods (B, 3): count, mean and deviation of log2(period)
+      'pitch_stats': with `pitch`, the paired lib.f0_stats (B, 3) of 'pitched' against 'model': 12 x its mean is the shift measured
+                 in semitones over the frames voiced in both.
+    Everything stays on the device.  F0 in Hz is SR / period."""
+    track = None
+    if f0 is not None and f0 is not False:
+        opt = {} if f0 is True else dict(f0)
+        unknown = set(opt) - {'weight', 'gain', 'lag_min', 'lag_max', 'ratio', 'threshold', 'lengths'}
+        if unknown:
+            raise ValueError('invert_spectrogram: f0: unknown settings %s' % sorted(unknown))
+        f0_lengths = opt.pop('lengths', lengths)
+        if not {'weight', 'gain', 'lag_min', 'lag_max'} & set(opt):   # (none given: the production tables at this bin count)
+            opt['weight'], opt['gain'], opt['lag_min'], opt['lag_max'] = lib.f0_tables(C=out.shape[2] // r)
+        for k in ('weight', 'gain'):   # (host tables go up once, not once per track)
+            if opt.get(k) is not None and not (torch.is_tensor(opt[k]) and opt[k].device == out.device):
+                opt[k] = torch.as_tensor(np.asarray(opt[k], dtype=np.float32)).to(out.device)
+        tracks = {}
+
+        def track(name, frames_t, counts, per_unit):
+            tracks[name] = lib.frames_f0(frames_t, counts, per_unit, **opt)
+            tracks[name + '_stats'] = lib.f0_stats(tracks[name][0], None, counts, per_unit)
     if frames_out is not None and rate is None:
         raise ValueError('invert_spectrogram: frames_out needs rate')
     if want_conv and momentum is None:
@@ -77,7 +109,18 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         else:
             semitones = pitch.tolist() if torch.is_tensor(pitch) else pitch
             pitch_q = [lib.pitch_step(x) for x in semitones] if hasattr(semitones, '__len__') else lib.pitch_step(semitones)
+        if track:
+            track('model', mag_t, f0_lengths, r if f0_lengths is not None else 1)
         mag_t = lib.frames_pitch(mag_t, lengths, pitch_q, frames_per_unit=r if lengths is not None else 1, lifter=lifter)
+        if track:
+            track('pitched', mag_t, f0_lengths, r if f0_lengths is not None else 1)
+            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], f0_lengths, r if f0_lengths is not None else 1)
+    elif track:
+        track('model', mag_t, f0_lengths, r if f0_lengths is not None else 1)
+    if track:
+        last = 'pitched' if pitch is not None else 'model'
+        tracks['vocoder'], tracks['vocoder_stats'] = tracks[last], tracks[last + '_stats']
+    done = (lambda res: res) if not track else (lambda res: (tuple(res) if isinstance(res, tuple) else (res,)) + (tracks,))
     if rate is not None:
         F = mag_t.shape[2]
         if torch.is_tensor(rate) and rate.device.type != 'cpu':
@@ -91,22 +134,24 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=r if lengths is not None else 1, Fo=Fo,
                                                    frames_out=frames_out)
         phase0 = None if phase0 is None else phase0.contiguous()
+        if track:   # (the stretched rows hold frames_out frames each, whatever `lengths` was)
+            track('vocoder', stretched, frames_out, 1)
         if momentum is not None:
             res = lib.griffinlim_fast(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, momentum=momentum,
                                       frames_per_unit=1, want_conv=want_conv, out=wave, work=work)
-            return (res[0], res[1], frames_out) if want_conv else (res, frames_out)
-        return lib.griffinlim_rows(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=1, out=wave,
-                                   work=work), frames_out
+            return done((res[0], res[1], frames_out) if want_conv else (res, frames_out))
+        return done((lib.griffinlim_rows(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=1, out=wave,
+                                         work=work), frames_out))
     if momentum is not None:
-        return lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
-                                   momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work)
+        return done(lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
+                                        momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work))
     if lengths is not None:
-        return lib.griffinlim_rows(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
-                                   frames_per_unit=r, out=wave, work=work)
+        return done(lib.griffinlim_rows(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
+                                        frames_per_unit=r, out=wave, work=work))
     if phase0 is None:
         g = torch.Generator(device='cpu').manual_seed(seed)
         phase0 = (2.0 * math.pi * torch.rand(mag_t.shape, generator=g)).to(dev)
-    return lib.griffinlim(mag_t, phase0.contiguous(), n_iter, out=wave, work=work)
+    return done(lib.griffinlim(mag_t, phase0.contiguous(), n_iter, out=wave, work=work))
 
 
 def finish_samples(lengths, r, L):

@@ -117,6 +117,8 @@ EXPORTS = {
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_stretch': (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_pitch': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
+    'taco_frames_f0': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
+    'taco_f0_stats': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _P]),
     'taco_corpus_batch': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -611,6 +613,151 @@ def frames_pitch(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, 
         raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
     _check(_lib.taco_frames_pitch(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(step_q), int(lifter), ptr(out), B, Cw, F,
                                   stream_ptr()), 'taco_frames_pitch')
+    return out
+
+
+F0_MAX_LAGS = 512          # TACO_F0_MAX_LAGS
+F0_RATIO, F0_THRESHOLD = 0.9, 0.3   # UNTUNED defaults of the pick: nobody has compared them with a labelled pitch track
+
+
+def f0_lags(sr=16000, fmin=60.0, fmax=400.0):
+    """(lag_min, lag_max) of a pitch range in Hz at sample rate sr: floor(sr / fmax) .. floor(sr / fmin); 40 .. 266 by default"""
+    sr, fmin, fmax = float(sr), float(fmin), float(fmax)
+    if not 0.0 < fmin < fmax < sr:
+        raise ValueError('f0_lags: need 0 < fmin < fmax < sr, got fmin = %r, fmax = %r, sr = %r' % (fmin, fmax, sr))
+    return int(math.floor(sr / fmax)), int(math.floor(sr / fmin))
+
+
+def f0_tables(sr=16000, fmin=60.0, fmax=400.0, deemphasis=0.97, C=1025, win_length=1200):
+    """The tables of taco_frames_f0 for features made with pre-emphasis `deemphasis` and a periodic Hann window of win_length samples
+    -> (weight (C) float32, gain (L) float32, lag_min, lag_max), host NumPy (computed in float64):
+      weight[k] = 1 / |1 - a e^{-i pi k / (C - 1)}|^2, which undoes the pre-emphasis on the power spectrum (all ones for a = 0);
+      gain[j] = wa[0] / wa[lag_min - 1 + j], wa the autocorrelation of the window zero-padded to N = 2 (C - 1): the window's own
+      autocorrelation divided out of the frame's (Boersma's correction).
+    ValueError when the lags do not fit C or the cap of 512, or the window does not cover lag_max + 1."""
+    lag_min, lag_max = f0_lags(sr, fmin, fmax)
+    C, win_length, a = int(C), int(win_length), float(deemphasis)
+    if not 9 <= C <= 1025 or (C - 1) & (C - 2):
+        raise ValueError('f0_tables: C - 1 must be a power of two in [8, 1024], got C = %d' % C)
+    if not 0.0 <= a < 1.0:
+        raise ValueError('f0_tables: deemphasis must be in [0, 1), got %r' % (deemphasis,))
+    L = lag_max - lag_min + 3
+    if not 2 <= lag_min <= lag_max <= C - 2 or L > F0_MAX_LAGS:
+        raise ValueError('f0_tables: %g .. %g Hz at %g Hz are lags %d .. %d: need 2 <= lag_min <= lag_max <= %d and at most %d lags '
+                         'with their neighbours' % (fmin, fmax, sr, lag_min, lag_max, C - 2, F0_MAX_LAGS))
+    N = 2 * (C - 1)
+    if not lag_max + 1 < win_length <= N:
+        raise ValueError('f0_tables: win_length must be in (lag_max + 1, N] = (%d, %d], got %d' % (lag_max + 1, N, win_length))
+    k = np.arange(C, dtype=np.float64)
+    weight = 1.0 / (1.0 - 2.0 * a * np.cos(np.pi * k / (C - 1)) + a * a)
+    w = np.zeros(N)
+    w[:win_length] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win_length) / win_length)
+    wa = np.fft.irfft(np.abs(np.fft.rfft(w, 2 * N)) ** 2)   # (2 N points: no lag wraps around)
+    lags = np.arange(lag_min - 1, lag_max + 2)
+    return weight.astype(np.float32), (wa[0] / wa[lags]).astype(np.float32), lag_min, lag_max
+
+
+def _f0_table(x, n, dev, what):
+    """None, a (n) float32 tensor on `dev`, or host numbers (uploaded) -> None or the device tensor; ValueError"""
+    if x is None:
+        return None
+    if torch.is_tensor(x) and x.device.type != 'cpu':
+        if tuple(x.shape) != (n,) or x.dtype != torch.float32 or x.device != dev or not x.is_contiguous():
+            raise ValueError('%s on a device must be a contiguous float32 tensor of shape (%d,) on %s' % (what, n, dev))
+        return x
+    host = np.asarray(x.numpy() if torch.is_tensor(x) else x, dtype=np.float32)
+    if host.shape != (n,):
+        raise ValueError('%s must hold %d numbers, got shape %s' % (what, n, host.shape))
+    return torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+
+
+def _f0_frames_arg(who, frames, frames_per_unit, B, dev):
+    if frames is not None and (not torch.is_tensor(frames) or tuple(frames.shape) != (B,) or frames.dtype != torch.int32
+                               or frames.device != dev or not frames.is_contiguous()):
+        raise ValueError('%s: frames must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
+    if isinstance(frames_per_unit, bool) or int(frames_per_unit) != frames_per_unit or int(frames_per_unit) < 1:
+        raise ValueError('%s: frames_per_unit must be an integer >= 1, got %r' % (who, frames_per_unit))
+
+
+def frames_f0(mag_t, frames=None, frames_per_unit=1, weight=None, gain=None, lag_min=40, lag_max=266, ratio=F0_RATIO,
+              threshold=F0_THRESHOLD, want_acf=False, out=None):
+    """The pitch of magnitude frames (include/taco_hip.h taco_frames_f0): mag_t (B, C, F) fp32 on the device, C - 1 a power of two in
+    [8, 1024] -> (period (B, F), strength (B, F)) fp32, and acf (B, L, F) behind them with want_acf, L = lag_max - lag_min + 3: per
+    frame the normalised autocorrelation over lags lag_min - 1 .. lag_max + 1 (the cosine transform of the weighted power spectrum,
+    times gain), the first local maximum at or above ratio times the largest one, refined by a parabola: period in samples (F0 =
+    sr / period), strength its height; both 0 for an unvoiced frame (no maximum, or strength below threshold) and behind F_b =
+    clamp(frames[b] * frames_per_unit, 0, F).
+    frames: (B) int32 on the device, or None (all F frames).  weight (C) / gain (L): None (ones), float32 device tensors, or host
+    numbers (uploaded); f0_tables() makes them, with lag_min and lag_max (the defaults 40 .. 266 are 400 .. 60 Hz at 16 kHz).
+    ratio 0.9 and threshold 0.3 are UNTUNED defaults.  out: the caller's own (period, strength) or (period, strength, acf); default:
+    fresh ones.  Enqueued on the current stream; nothing is read back and nothing waits."""
+    who = 'frames_f0'
+    if not torch.is_tensor(mag_t) or mag_t.dim() != 3 or mag_t.dtype != torch.float32 or min(mag_t.shape) < 1:
+        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, C, F), got %s %s'
+                         % (who, getattr(mag_t, 'dtype', type(mag_t)), tuple(getattr(mag_t, 'shape', ()))))
+    if not mag_t.is_contiguous():
+        raise ValueError('%s: mag_t must be contiguous' % who)
+    B, Cw, F = mag_t.shape
+    dev = mag_t.device
+    if not 9 <= Cw <= 1025 or (Cw - 1) & (Cw - 2):
+        raise ValueError('%s: C - 1 must be a power of two in [8, 1024], got C = %d' % (who, Cw))
+    if F > STRETCH_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
+    _f0_frames_arg(who, frames, frames_per_unit, B, dev)
+    for name, v in (('lag_min', lag_min), ('lag_max', lag_max)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError('%s: %s must be an integer, got %r' % (who, name, v))
+    lag_min, lag_max = int(lag_min), int(lag_max)
+    L = lag_max - lag_min + 3
+    if not 2 <= lag_min <= lag_max <= Cw - 2 or L > F0_MAX_LAGS:
+        raise ValueError('%s: need 2 <= lag_min <= lag_max <= %d at C = %d and at most %d lags with their neighbours, got lag_min = %d, '
+                         'lag_max = %d' % (who, Cw - 2, Cw, F0_MAX_LAGS, lag_min, lag_max))
+    ratio, threshold = float(ratio), float(threshold)
+    if not 0.0 < ratio <= 1.0:   # (NaN fails)
+        raise ValueError('%s: ratio must be in (0, 1], got %r' % (who, ratio))
+    if threshold != threshold:
+        raise ValueError('%s: threshold is NaN' % who)
+    weight = _f0_table(weight, Cw, dev, who + ': weight')
+    gain = _f0_table(gain, L, dev, who + ': gain')
+    if out is not None and len(out) != (3 if want_acf else 2):
+        raise ValueError('%s: out must be (period, strength%s)' % (who, ', acf' if want_acf else ''))
+    period = _own_or_given(None if out is None else out[0], (B, F), torch.float32, dev, who + ': period')
+    strength = _own_or_given(None if out is None else out[1], (B, F), torch.float32, dev, who + ': strength')
+    acf = _own_or_given(None if out is None else out[2], (B, L, F), torch.float32, dev, who + ': acf') if want_acf else None
+    m0, nbytes = mag_t.data_ptr(), B * Cw * F * 4
+    for name, t in (('period', period), ('strength', strength), ('acf', acf)):
+        if t is not None and t.data_ptr() < m0 + nbytes and m0 < t.data_ptr() + t.numel() * 4:
+            raise ValueError('%s: %s may not overlap mag_t' % (who, name))
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_frames_f0(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(weight), ptr(gain), lag_min, lag_max, ratio, threshold,
+                               ptr(period), ptr(strength), ptr(acf), B, Cw, F, stream_ptr()), 'taco_frames_f0')
+    return (period, strength, acf) if want_acf else (period, strength)
+
+
+def f0_stats(period, other=None, frames=None, frames_per_unit=1, out=None):
+    """Statistics of a pitch track (include/taco_hip.h taco_f0_stats): period (B, F) fp32 on the device, as frames_f0 returns it ->
+    stats (B, 3) fp32 = (count, mean, population standard deviation) of log2(period) over the frames with period > 0 among the first
+    F_b.  other (B, F): the statistics of log2(other) - log2(period) over the frames voiced in both: the octaves by which `period`
+    is higher in pitch than `other` (12 x the mean: semitones).  Nothing is read back."""
+    who = 'f0_stats'
+    if not torch.is_tensor(period) or period.dim() != 2 or period.dtype != torch.float32 or min(period.shape) < 1:
+        raise ValueError('%s: period must be a float32 tensor of shape (B, F), got %s %s'
+                         % (who, getattr(period, 'dtype', type(period)), tuple(getattr(period, 'shape', ()))))
+    if not period.is_contiguous():
+        raise ValueError('%s: period must be contiguous' % who)
+    B, F = period.shape
+    dev = period.device
+    if F > STRETCH_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
+    if other is not None and (not torch.is_tensor(other) or tuple(other.shape) != (B, F) or other.dtype != torch.float32
+                              or other.device != dev or not other.is_contiguous()):
+        raise ValueError('%s: other must be a contiguous float32 tensor of shape (%d, %d) on %s' % (who, B, F, dev))
+    _f0_frames_arg(who, frames, frames_per_unit, B, dev)
+    out = _own_or_given(out, (B, 3), torch.float32, dev, who + ': out')
+    if dev.type != 'cuda':
+        raise ValueError('%s: period must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_f0_stats(ptr(period), ptr(other), ptr(frames), int(frames_per_unit), ptr(out), B, F, stream_ptr()), 'taco_f0_stats')
     return out
 
 

@@ -38,7 +38,16 @@ its cepstrum; default 32, untuned) and the rest; the rest alone -- the harmonics
 unmoved envelope (lib.frames_pitch, taco_frames_pitch), so the formants and the duration stay.  prompt_NNN_pitch.npy holds (step_q,
 lifter) as int32; every other file keeps its size, and the spectrogram, alignment, length, score and rate files stay the model's own.
 --pitch 0 writes the audio of a run without --pitch.  Nobody has listened to the result.  It combines with every option above (it runs
-in front of the stretch of --rate); with --long the pieces of a prompt inherit its pitch."""
+in front of the stretch of --rate); with --long the pieces of a prompt inherit its pitch.
+--f0 [--f0-range LO,HI] (opt-in, not in the reference): the pitch of every magnitude frame is measured on the device (lib.frames_f0,
+taco_frames_f0: the autocorrelation of a frame is the cosine transform of its power spectrum, so no waveform is needed) between LO and
+HI Hz (default 60,400) and prompt_NNN_f0.npy holds (period in samples, strength) as float32, one row per frame the vocoder was given;
+0, 0 is an unvoiced frame, F0 = 16000 / period.  With --pitch one line per prompt gives the semitones asked for and the semitones
+measured -- 12 x the mean over the frames voiced in both of log2(period unshifted / period shifted) (lib.f0_stats) -- and the count of
+those frames; with --rate alone the line gives the change of the mean log-F0 in cents, which should be near 0 (unpaired: the frame
+counts differ).  The pick's ratio 0.9 and threshold 0.3 are UNTUNED, and on an untrained model the frames have no pitch: the numbers
+then mean nothing.  It is the objective stand-in for listening to --pitch and --rate, which nobody has done.  It combines with every
+option above; with --long the files are per piece."""
 from __future__ import annotations
 
 import argparse
@@ -129,9 +138,40 @@ def pitch_steps(pitch, n):
     return [lib.pitch_step(pitch)] * (1 if n is None else n)
 
 
+def f0_range(f0):
+    """`f0` of test(): None / False (off), True (60 .. 400 Hz) or (lo, hi) in Hz -> None or (lo, hi) after lib.f0_tables has accepted
+    them at 16 kHz; ValueError"""
+    if f0 is None or f0 is False:
+        return None
+    try:
+        lo, hi = (60.0, 400.0) if f0 is True else (float(x) for x in f0)
+        lib.f0_tables(SR, lo, hi)
+    except (TypeError, ValueError) as e:
+        raise ValueError('f0 (--f0 / --f0-range): %s' % e) from None
+    return lo, hi
+
+
+def f0_lines(who, f0row, asked_step=None, rate_step=None):
+    """the line(s) --f0 prints for `who` ('prompt 3', or 'prompt 3 piece 1' with --long) from its row of the statistics: f0row =
+    (model_stats, vocoder_stats, pitch_stats | None)"""
+    model, voc, paired = f0row
+    out = []
+    if asked_step is not None and paired is not None:
+        out.append('%s pitch: asked %+.2f, measured %+.2f semitones over %d voiced frames'
+                   % (who, 12.0 * np.log2(65536.0 / asked_step), 12.0 * float(paired[1]), int(paired[0])))
+    elif rate_step is not None:
+        out.append('%s rate %.3f: mean log-F0 moved %+.1f cents (%d -> %d voiced frames)'
+                   % (who, rate_step / 65536.0, 1200.0 * (float(model[1]) - float(voc[1])), int(model[0]), int(voc[0])))
+    return out
+
+
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32):
+                  vocode=True, pitch=None, lifter=32, f0=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given); ValueError."""
+    if f0 is not None and f0 is not False:
+        if not vocode:
+            raise ValueError('f0 (--f0) measures the magnitudes in front of Griffin-Lim: it needs vocode')
+        f0_range(f0)
     if pitch is not None:
         if not vocode:
             raise ValueError('pitch (--pitch) shifts the magnitudes in front of Griffin-Lim: it needs vocode')
@@ -163,7 +203,7 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None):
+                 rate=None, pitch=None, f0=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -171,7 +211,9 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     over the kept alignment rows at `zoom` pixels per cell.
     rate (--rate): (step_q, Fo_b) of the prompt, written as _rate.npy; wav is then the stretched waveform and keeps 300 (Fo_b - 1)
     samples, whatever len_b says.
-    pitch (--pitch): (step_q, lifter) of the prompt, written as _pitch.npy; nothing else depends on it."""
+    pitch (--pitch): (step_q, lifter) of the prompt, written as _pitch.npy; nothing else depends on it.
+    f0 (--f0): the prompt's (frames, 2) float32 rows of (period, strength) over the frames the vocoder was given, already cut to them;
+    written as _f0.npy."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -185,6 +227,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_rate.npy', np.asarray(rate, dtype=np.int32))
     if pitch is not None:
         np.save(path + '_pitch.npy', np.asarray(pitch, dtype=np.int32))
+    if f0 is not None:
+        np.save(path + '_f0.npy', np.asarray(f0, dtype=np.float32))
     np.save(path + '_spec.npy', spec)
     np.save(path + '_align.npy', align)
     if wav is not None:
@@ -201,7 +245,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32):
+         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -239,8 +283,14 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     prompt; with `long`, a prompt's pieces inherit its pitch.  The harmonics of every magnitude frame the vocoder is given are moved
     under the frame's own envelope of `lifter` quefrencies (invert_spectrogram(pitch=...), in front of the stretch of `rate`): over the
     row's own len_b r frames wherever the vocoder gets the lengths, else over all frames.  prompt_NNN_pitch.npy holds (step_q, lifter)
-    as int32; no file changes its size, the model's own files stay what they are, and pitch 0 gives the audio of pitch None."""
-    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter)
+    as int32; no file changes its size, the model's own files stay what they are, and pitch 0 gives the audio of pitch None.
+    `f0` (needs `vocode`): None, True (60 .. 400 Hz) or (lo, hi) in Hz: invert_spectrogram(f0=...) tracks the pitch of the frames on the
+    device, over the row's own len_b r frames with `stop`; prompt_NNN_f0.npy holds (period, strength) of the frames the vocoder was
+    given, and f0_lines() prints what `pitch` or `rate` did to it.  Untuned, and meaningless on an untrained model; nothing else
+    changes."""
+    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0)
+    f0 = f0_range(f0)
+    f0_opt = None   # the tables on the device, made at the first batch
     steps = rate_steps(rate, len(prompts))
     row_pitch = pitch_steps(pitch, len(prompts))
     long = long_options(long)
@@ -264,8 +314,10 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     os.makedirs(out_dir, exist_ok=True)
 
     def synthesise(batch, n, out_rows=None, bounds_rows=None):
-        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores), host arrays or None.  out_rows /
-        bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made"""
+        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res), host arrays or None.
+        out_rows / bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made.
+        f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None)"""
+        nonlocal f0_opt
         Bn = batch['text'].shape[0]
         if config.num_speakers > 1:
             batch['speaker'] = torch.full((Bn,), int(speaker), dtype=torch.int32)
@@ -288,20 +340,32 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = conv = pcm = trim = None
+        wav = conv = pcm = trim = f0res = None
         if vocode:
             fout = None
             shift = {}
             if row_pitch is not None:   # (step_q as the device takes it: no way back through semitones)
                 shift = dict(pitch=torch.tensor(row_pitch[n:n + Bn], dtype=torch.int32).cuda(), lifter=lifter)
+            if f0 is not None:
+                if f0_opt is None:
+                    w, g, lag_min, lag_max = lib.f0_tables(SR, f0[0], f0[1])
+                    f0_opt = dict(weight=torch.from_numpy(w).cuda(), gain=torch.from_numpy(g).cuda(), lag_min=lag_min, lag_max=lag_max)
+                shift['f0'] = dict(f0_opt, lengths=model.lengths if stop is not None else None)
             if steps is None:
-                wav = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
+                res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
                                          want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None, **shift)
             else:   # (the rows' own frames whenever there is a rule: the host's Fo_b and the device's frames_out are then one number)
-                *wav, fout = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                                want_conv=gl_momentum is not None, lengths=model.lengths if stop is not None else None,
-                                                rate=[q / 65536.0 for q in row_steps[n:n + Bn]], **shift)
-                wav = wav[0] if gl_momentum is None else wav
+                res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
+                                         want_conv=gl_momentum is not None, lengths=model.lengths if stop is not None else None,
+                                         rate=[q / 65536.0 for q in row_steps[n:n + Bn]], **shift)
+            res = list(res) if isinstance(res, tuple) else [res]   # waveform [, conv] [, frames_out] [, tracks]
+            if f0 is not None:
+                tracks = res.pop()
+                f0res = (torch.stack(tracks['vocoder'], dim=2).cpu().numpy(), tracks['model_stats'].cpu().numpy(),
+                         tracks['vocoder_stats'].cpu().numpy(), tracks['pitch_stats'].cpu().numpy() if 'pitch_stats' in tracks else None)
+            if steps is not None:
+                fout = res.pop()
+            wav = res[0] if gl_momentum is None else res
             if gl_momentum is not None:
                 wav, conv = wav[0], wav[1].cpu().numpy()
                 print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
@@ -324,7 +388,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         if scores is not None:
             scores = np.stack([scores_row(c, m) for c, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
-        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores
+        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res
 
     def marks(score, L):
         """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
@@ -342,6 +406,17 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         """(step_q, lifter) of global row `row`, or None without a pitch"""
         return None if row_pitch is None else (row_pitch[row], int(lifter))
 
+    def f0_of(row, i, len_b, f0res, who):
+        """the _f0.npy rows of row i of a batch (global row `row`), cut to the frames the vocoder was given; prints the row's line"""
+        if f0res is None:
+            return None
+        stretched = rate_of(row, len_b)
+        frames = stretched[1] if stretched is not None else (F if len_b is None else min(int(len_b) * config.r, F))
+        for line in f0_lines(who, [None if a is None else a[i] for a in f0res[1:]], None if row_pitch is None else row_pitch[row],
+                             None if steps is None else row_steps[row]):
+            print(line)
+        return f0res[0][i, :frames]
+
     n = 0
     row_steps = steps
     if long is not None:
@@ -351,16 +426,16 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         if steps is not None:   # a piece has its prompt's rate; every row of the joined buffer holds the slowest one's samples
             row_steps = [steps[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
             L = 300 * (max(5, lib.stretch_capacity(F, min(row_steps, default=lib.STRETCH_ONE))) - 1)
-        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of)
+        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of, f0_of)
         print('wrote %d samples to %s' % (n, out_dir))
         return n
     for batch in load_prompts(prompts, ivocab):
         Bn = batch['text'].shape[0]
-        spec, al, wav, conv, pcm, trim, lengths, scores = synthesise(batch, n)
+        spec, al, wav, conv, pcm, trim, lengths, scores, f0res = synthesise(batch, n)
         for i in range(Bn):
             wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
             write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
-                         rate=rate_of(n, len_b), pitch=pitch_of(n))
+                         rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n))
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
             if found:
                 print('WARNING prompt %d: %s' % (n, ', '.join(found)))
@@ -370,10 +445,10 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
 
 
 def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None,
-               pitch_of=lambda row: None):
+               pitch_of=lambda row: None, f0_of=lambda row, i, len_b, f0res, who: None):
     """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write.  L: the samples
-    per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b) / pitch_of(row): what write_prompt gets as
-    `rate` / `pitch`"""
+    per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b) / pitch_of(row) / f0_of(row, i, len_b, f0res,
+    who): what write_prompt gets as `rate` / `pitch` / `f0`"""
     pause_ms, fade_ms = long
     split = [split_prompt(p) for p in prompts]
     groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
@@ -385,6 +460,7 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
             start, held = p + 1, 0
     if L is None:
         L = 300 * ((config.max_decode_iter // 4) * 4 * config.r - 1)   # samples per row of invert_spectrogram
+    who = ['prompt %d' % p if len(pieces) == 1 else 'prompt %d piece %d' % (p, k) for p, pieces in enumerate(split) for k in range(len(pieces))]
     row = 0   # index of the next piece over the whole run (the Griffin-Lim seed of its batch, as the prompt index is without `long`)
     for lo, hi in groups:
         lines = [line for pieces in split[lo:hi] for line, _ in pieces]
@@ -393,13 +469,14 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
         N = len(lines)
         rows = torch.empty(N, L, dtype=torch.float32, device='cuda')
         bounds = torch.empty(N, 2, dtype=torch.int32, device='cuda')
-        arrays = []   # per piece: (spec, align, len_b, trim, conv, scores, text length)
+        arrays = []   # per piece: (spec, align, len_b, trim, conv, scores, text length, f0 rows)
         at = 0
         for batch in load_prompts(lines, ivocab):
             Bn = batch['text'].shape[0]
-            spec, al, _, conv, _, trim, lengths, scores = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            spec, al, _, conv, _, trim, lengths, scores, f0res = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
             arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i],
-                        None if scores is None else scores[i], int(batch['text_length'][i])) for i in range(Bn)]
+                        None if scores is None else scores[i], int(batch['text_length'][i]),
+                        f0_of(row + at + i, i, int(lengths[i]), f0res, who[row + at + i])) for i in range(Bn)]
             at += Bn
         gap = join_gaps(kinds, pause_ms)
         _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
@@ -409,9 +486,9 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
             path = os.path.join(out_dir, 'prompt_%03d' % p)
             found = []
             for k in range(a, b):
-                spec, al, len_b, trim, conv, score, text_len = arrays[k]
+                spec, al, len_b, trim, conv, score, text_len, f0rows = arrays[k]
                 write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score,
-                             rate=rate_of(row + k, len_b), pitch=pitch_of(row + k))
+                             rate=rate_of(row + k, len_b), pitch=pitch_of(row + k), f0=f0rows)
                 names = marks(score, text_len) if score is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
@@ -432,6 +509,13 @@ def _pause_ms(text):
     parts = text.split(',')
     if len(parts) != 3:
         raise argparse.ArgumentTypeError('expected SENTENCE,CLAUSE,WORD, got %r' % text)
+    return tuple(float(x) for x in parts)
+
+
+def _f0_range(text):
+    parts = text.split(',')
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError('expected LO,HI in Hz, got %r' % text)
     return tuple(float(x) for x in parts)
 
 
@@ -472,14 +556,22 @@ def parse_args(argv=None):
     ap.add_argument('--lifter', type=int, default=32, metavar='Q',
                     help='--pitch: the quefrencies 0 .. Q of the cepstrum make the envelope, 1 <= Q <= 64 (default 32 = 2 ms at 16 kHz: '
                          'a choice, not tuned by ear)')
+    ap.add_argument('--f0', action='store_true',
+                    help='measure the pitch of every magnitude frame the vocoder is given on the device; writes prompt_NNN_f0.npy (period '
+                         'in samples, strength) and, with --pitch or --rate, prints what was asked for and what is measured (untuned '
+                         'ratio 0.9 / threshold 0.3; meaningless on an untrained model; not in the reference)')
+    ap.add_argument('--f0-range', type=_f0_range, default=None, metavar='LO,HI', help='--f0: the pitch range searched in Hz (default 60,400)')
     ap.add_argument('--align-scores', action='store_true',
                     help='score every prompt\'s attention on the device: prompt_NNN_ascore.npy (8 values: n, end, pad_steps, back, skip, '
                          'covered, focus, pad_mass), prompt_NNN_align.png, and a WARNING line for a prompt the (untuned) thresholds mark')
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
+    if a.f0_range is not None and not a.f0:
+        ap.error('--f0-range needs --f0')
+    a.f0 = (a.f0_range if a.f0_range is not None else True) if a.f0 else None
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
-                      lifter=a.lifter)
+                      lifter=a.lifter, f0=a.f0)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -495,4 +587,4 @@ if __name__ == '__main__':
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
-         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter)
+         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0)
