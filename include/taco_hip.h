@@ -239,7 +239,8 @@ int taco_frames_active(const float* x, float floor, int32_t* n, int B, int F, in
  * coefficients are computed once per row, into LDS where they fit beside the diagonals (160 KiB) and else into the row's slice of
  * `workspace`.  The Fa x Fb table is never materialised.  No allocation, no host synchronisation, no workgroup waits for another
  * one; graph-capturable; the same arguments give the same bits.
- * NOT provided: the warping path itself (it needs an Fa x Fb direction table) and a Sakoe-Chiba band (every cell is visited).
+ * The warping path itself: taco_frame_dtw_path below (it needs a direction table in the workspace; this entry point keeps none).
+ * NOT provided: a Sakoe-Chiba band (every cell is visited).
  * NULL a / b / cost / steps, B, Fa, Fb, C or K <= 0, basis == NULL with K != C, K > TACO_DTW_MAX_K, C > TACO_DTW_MAX_C, Fa or Fb >
  * TACO_DTW_MAX_FRAMES, or a NULL workspace where one is needed return TACO_EINVAL before anything is enqueued; the size function
  * returns TACO_EINVAL for the same shapes.  TACO_VERSION did not change with these entry points: detect them by the symbol. */
@@ -249,6 +250,29 @@ int taco_frames_active(const float* x, float floor, int32_t* n, int B, int F, in
 int64_t taco_frame_dtw_workspace_bytes(int B, int Fa, int Fb, int K);
 int taco_frame_dtw(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
                    int32_t* steps, void* workspace, int B, int Fa, int Fb, int C, int K, void* stream);
+
+/* The same warp with its path.  a, na, b, nb, basis, cost, steps: exactly as taco_frame_dtw takes them, with the same limits;
+ * steps 1-4 above with the same tie order, and cost / steps have the same BITS as taco_frame_dtw's on the same inputs.
+ *   path_a, path_b (B, P) int32, P = Fa + Fb - 1, both required: entries t = 0 .. steps[b]-1 of row b hold the cells (i_t, j_t) of
+ *   the chosen path in chronological order -- (i_0, j_0) = (0, 0), the last one (na-1, nb-1), (i_{t-1}, j_{t-1}) the predecessor
+ *   step 3 chose for (i_t, j_t) -- and entries t >= steps[b] hold -1 (the whole row when na or nb is 0).  Every element of both
+ *   is written.
+ *   workspace: taco_frame_dtw_path_workspace_bytes(B, Fa, Fb, K) bytes, required (never 0), 4-byte aligned, arbitrary contents:
+ *   the coefficients where taco_frame_dtw keeps them there, then per row a direction table of one byte per cell, stored by
+ *   anti-diagonal: (Fa + Fb - 1) Fa bytes a row (253 KiB at 360 x 360, 2 MiB at 1024 x 1024).
+ * One launch, a workgroup per row: the walk of taco_frame_dtw storing one direction byte per cell, then the path read off the table
+ * backwards by one lane (one dependent load per step), each entry written in its final place, while the whole workgroup fills the
+ * tails.  Measured on an MI355X (profiles/frame_dtw_path_timing.json): 1.09 x the cost-only call at 32 x 360 x 360, K = 13, 1.12 x
+ * at 32 x 1000 x 1000; 0.17 us per step of the backtrack.  No allocation, no host synchronisation, no workgroup waits for another
+ * one; graph-capturable; the same arguments give the same bits.  Nothing outside cost / steps / path_a / path_b / workspace is
+ * written, also with non-finite inputs (whose results are unspecified).  No Sakoe-Chiba band.
+ * Every refusal of taco_frame_dtw, NULL path_a / path_b and a NULL workspace return TACO_EINVAL (message "frame_dtw_path: ...")
+ * before anything is enqueued; the size function returns TACO_EINVAL for the shapes taco_frame_dtw_workspace_bytes refuses.
+ * TACO_VERSION did not change with these entry points: detect them by the symbol. */
+int64_t taco_frame_dtw_path_workspace_bytes(int B, int Fa, int Fb, int K);
+int taco_frame_dtw_path(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
+                        int32_t* steps, int32_t* path_a, int32_t* path_b, void* workspace, int B, int Fa, int Fb, int C, int K,
+                        void* stream);
 
 /* add_train_op (tacotron.py:167-185): global-norm clip (cap_grads) then TF-form Adam, in place.
  *   step = global_step after this update (1-based).  scratch: >= 256 floats.  gnorm_out[0] receives ||g||. */
@@ -462,6 +486,24 @@ int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_uni
  * frames_per_unit < 1 return TACO_EINVAL before anything is enqueued.  Detect it by the symbol. */
 int taco_f0_stats(const float* period, const float* other, const int32_t* frames, int frames_per_unit, float* stats, int B, int F,
                   void* stream);
+
+/* F0 error along a warping path: the frame-by-frame companions of MCD (F0 RMSE, voicing decision error, gross pitch error).
+ *   period_a (B, Fa), period_b (B, Fb) fp32 periods as taco_frames_f0 writes them (0: unvoiced);  path_a, path_b (B, P) int32,
+ *   P = Fa + Fb - 1, and steps (B) int32 as taco_frame_dtw_path writes them;  gross fp32 > 1 (1.2 is usual)
+ * steps[b] is used clamped to [0, P].  For t < steps[b] with i = path_a[b, t] in [0, Fa) and j = path_b[b, t] in [0, Fb) -- any
+ * other entry is skipped and nothing is read for it -- pa = period_a[b, i], pb = period_b[b, j]:
+ *   counts (B, 5) int32 = { cells visited, both voiced (pa > 0 && pb > 0), a only, b only, gross errors among the both-voiced cells:
+ *                           pa > gross * pb || pb > gross * pa, each product ONE rounded fp32 multiply (a NumPy float32
+ *                           restatement gives the count exactly) }
+ *   means (B, 2) fp32 = { mean, root mean square } of x = log2(pb) - log2(pa) over the both-voiced cells: the octaves by which a's
+ *                       pitch lies above b's (x 1200: cents; the RMS x 1200 is the F0 RMSE in cents); both +0 without such a cell
+ * x is formed in double and rounded once to fp32; the sums of x and x x are fp32, in a fixed order (the same arguments give the
+ * same bits).  One workgroup per row, no atomics, no workspace, no
+ * allocation, no host synchronisation; graph-capturable.  Nothing outside counts and means is written.  NULL pointers, B, Fa or
+ * Fb <= 0, Fa or Fb > TACO_DTW_MAX_FRAMES, gross <= 1 or NaN return TACO_EINVAL (message "path_f0_scores: ...") before anything is
+ * enqueued.  Detect it by the symbol. */
+int taco_path_f0_scores(const float* period_a, const float* period_b, const int32_t* path_a, const int32_t* path_b,
+                        const int32_t* steps, float gross, int32_t* counts, float* means, int B, int Fa, int Fb, void* stream);
 
 /* ---- corpus boundary ----------------------------------------------------------------------------------------------------- */
 /* The batch gather of the training corpus with the reference's target standardisation (data_input.py:55-65

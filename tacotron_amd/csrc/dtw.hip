@@ -1,6 +1,7 @@
-// dtw.hip -- held-out evaluation on the device (include/taco_hip.h taco_frames_active, taco_frame_dtw): how many frames of a padded
-// recording are in use, and the cost of the best dynamic-time-warping path between two frame sequences per batch row -- the warp
-// behind mel-cepstral distortion.  No counterpart in the reference, which never scores a checkpoint.
+// dtw.hip -- held-out evaluation on the device (include/taco_hip.h taco_frames_active, taco_frame_dtw, taco_frame_dtw_path): how many
+// frames of a padded recording are in use, and the cost of the best dynamic-time-warping path between two frame sequences per batch
+// row -- the warp behind mel-cepstral distortion -- with or without the path itself.  No counterpart in the reference, which never
+// scores a checkpoint.
 //
 // frame_dtw: one workgroup per row, one launch.  Cell (i, j) of the Fa x Fb table needs (i-1, j-1), (i-1, j) and (i, j-1) only, so
 // the cells of one anti-diagonal d = i + j are independent and need the two diagonals before it: the workgroup walks d = 0 ..
@@ -46,6 +47,9 @@ DtwPlan dtw_plan(int Fa, int Fb, int K) {
   p.row_floats = p.coef_in_lds ? 0 : (int64_t)(Fa + Fb) * dtw_stride(K);
   return p;
 }
+// The path form's workspace: the B rows' coefficients as the cost-only form lays them out (none where they fit LDS), then B
+// direction tables, a byte per cell of (Fa + Fb - 1) diagonals x Fa.
+__host__ __device__ inline int64_t dtw_way_bytes(int Fa, int Fb) { return (int64_t)(Fa + Fb - 1) * Fa; }
 bool dtw_shape_ok(int B, int Fa, int Fb, int K) {
   return B > 0 && Fa > 0 && Fb > 0 && K > 0 && K <= TACO_DTW_MAX_K && Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES;
 }
@@ -75,16 +79,38 @@ __device__ __forceinline__ void dtw_project(const float* __restrict__ x, int n, 
   }
 }
 
-template <bool COEF_LDS>
+// PATH: every cell also stores which predecessor it took (0: (i-1, j-1), 1: (i-1, j), 2: (i, j-1)) as a byte at way[d * Fa + i],
+// d = i + j -- diagonal-major, so the lanes of a wave, which hold consecutive i of one diagonal, store consecutive bytes -- and
+// behind the walk the path is read off that table backwards from (na - 1, nb - 1).  `steps` is known by then, so entry steps - 1 - t
+// is written directly and nothing is reversed.  The stores are global and nobody waits for them in the walk (lds_barrier() waits
+// for LDS only); in front of the backtrack every wave waits for its own (s_waitcnt vmcnt(0)) and then for the others (barrier), and
+// the backtrack loads on the vector path past the CU's vector cache (sc1), served by the L2 that acknowledged the stores.
+// The cost-only form takes an EMPTY DtwPath behind its twelve arguments and every line of the path form sits under `if constexpr
+// (PATH)`: its instructions are those it had before the path form existed (compared in the assembly, kernel by kernel).
+template <bool PATH>
+struct DtwPath {};
+template <>
+struct DtwPath<true> {
+  int32_t* path_a;     // (B, Fa + Fb - 1)
+  int32_t* path_b;
+  uint8_t* way;        // B tables of (Fa + Fb - 1) x Fa bytes
+};
+
+template <bool COEF_LDS, bool PATH>
 __global__ __launch_bounds__(kDtwThreads) void frame_dtw_kernel(const float* __restrict__ a, const int32_t* __restrict__ na_p,
                                                                 const float* __restrict__ b, const int32_t* __restrict__ nb_p,
                                                                 const float* __restrict__ basis, float* __restrict__ cost,
-                                                                int32_t* __restrict__ steps, float* ws, int Fa, int Fb, int C, int K) {
+                                                                int32_t* __restrict__ steps, float* ws, int Fa, int Fb, int C, int K,
+                                                                DtwPath<PATH> out) {
   extern __shared__ float dtw_lds[];   // D[3][Fa] | N[3][Fa] | COEF_LDS: U[Fa][S] | V[Fb][S]
   const int row = blockIdx.x, tid = threadIdx.x;
   const int na = clamp_len(na_p, row, Fa), nb = clamp_len(nb_p, row, Fb);
   if (na == 0 || nb == 0) {
     if (tid == 0) cost[row] = 0.f, steps[row] = 0;
+    if constexpr (PATH) {
+      const int P = Fa + Fb - 1;
+      for (int t = tid; t < P; t += kDtwThreads) out.path_a[(int64_t)row * P + t] = -1, out.path_b[(int64_t)row * P + t] = -1;
+    }
     return;
   }
   const int S = dtw_stride(K);
@@ -95,6 +121,8 @@ __global__ __launch_bounds__(kDtwThreads) void frame_dtw_kernel(const float* __r
   dtw_project(a + (int64_t)row * Fa * C, na, basis, U, C, K, S);
   dtw_project(b + (int64_t)row * Fb * C, nb, basis, V, C, K, S);
   __syncthreads();   // (also orders the workspace form's global stores in front of this workgroup's loads)
+  uint8_t* way = nullptr;
+  if constexpr (PATH) way = out.way + row * dtw_way_bytes(Fa, Fb);
 
   const int last = na + nb - 2;
   for (int d = 0; d <= last; ++d) {
@@ -117,6 +145,7 @@ __global__ __launch_bounds__(kDtwThreads) void frame_dtw_kernel(const float* __r
       }
       float best = sqrtf(s);
       int count = 1;
+      uint8_t took = 0;
       if (d > 0) {
         // in the order (i-1, j-1), (i-1, j), (i, j-1); a later candidate replaces an earlier one only when strictly smaller
         const bool has_up = i > 0, has_left = j > 0;
@@ -129,12 +158,37 @@ __global__ __launch_bounds__(kDtwThreads) void frame_dtw_kernel(const float* __r
         pd = take_left ? d_left : pd, pn = take_left ? n_left : pn;
         best = pd + best;
         count = pn + 1;
+        if constexpr (PATH) took = take_left ? 2 : (take_up ? 1 : 0);
       }
       D[c0 + i] = best;
       N[c0 + i] = count;
+      if constexpr (PATH) way[d * Fa + i] = took;
       if (d == last) cost[row] = best, steps[row] = count;   // (the last diagonal is the one cell (na - 1, nb - 1))
     }
     lds_barrier();
+  }
+  if constexpr (PATH) {
+    // every wave's direction stores are acknowledged before any lane reads the table.  The wait is written out: at workgroup
+    // scope hipcc's __syncthreads() waits for lgkmcnt only on this target (stores and plain loads of one CU meet in its vector
+    // cache), and the loads below do not go through that cache
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int P = Fa + Fb - 1;
+    int32_t* path_a = out.path_a + (int64_t)row * P;
+    int32_t* path_b = out.path_b + (int64_t)row * P;
+    int n = N[(last % 3) * Fa + na - 1];   // steps[row]
+    n = n < 0 ? 0 : (n > P ? P : n);       // (it is in 1 .. P; the bounds of the stores below do not rest on the data)
+    for (int t = n + tid; t < P; t += kDtwThreads) path_a[t] = -1, path_b[t] = -1;
+    if (tid == 0) {   // one dependent load per step: tools/frame_dtw_path_timing.py has what the chain costs
+      int i = na - 1, j = nb - 1;
+      for (int t = n - 1; t >= 0; --t) {
+        path_a[t] = i, path_b[t] = j;
+        if (t == 0) break;
+        const unsigned w = __hip_atomic_load(way + (i + j) * Fa + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        i = (w != 2 && i > 0) ? i - 1 : i;
+        j = (w != 1 && j > 0) ? j - 1 : j;
+      }
+    }
   }
 }
 
@@ -167,18 +221,40 @@ int launch_frame_dtw(const float* a, const int32_t* na, const float* b, const in
                      float* workspace, int B, int Fa, int Fb, int C, int K, hipStream_t s) {
   const DtwPlan p = dtw_plan(Fa, Fb, K);
   static DynSmemOnce raised;
+  const auto in_lds = frame_dtw_kernel<true, false>, in_ws = frame_dtw_kernel<false, false>;
   if (p.coef_in_lds) {   // up to the whole budget, raised once per device for every later shape
-    if (!ensure_dyn_smem(raised, reinterpret_cast<const void*>(frame_dtw_kernel<true>), kDtwLdsBudget)) {
+    if (!ensure_dyn_smem(raised, reinterpret_cast<const void*>(in_lds), kDtwLdsBudget)) {
       taco_set_error("frame_dtw: cannot raise the dynamic LDS limit to %zu bytes", kDtwLdsBudget);
       return TACO_ELAUNCH;
     }
-    TACO_KLAUNCH(frame_dtw_kernel<true>, dim3(B), dim3(kDtwThreads), p.lds_bytes, s, a, na, b, nb, basis, cost, steps, workspace, Fa, Fb,
-                 C, K);
+    TACO_KLAUNCH(in_lds, dim3(B), dim3(kDtwThreads), p.lds_bytes, s, a, na, b, nb, basis, cost, steps, workspace, Fa, Fb, C, K,
+                 DtwPath<false>{});
   } else {               // the diagonals alone: 24 KiB at the most
-    TACO_KLAUNCH(frame_dtw_kernel<false>, dim3(B), dim3(kDtwThreads), p.lds_bytes, s, a, na, b, nb, basis, cost, steps, workspace, Fa, Fb,
-                 C, K);
+    TACO_KLAUNCH(in_ws, dim3(B), dim3(kDtwThreads), p.lds_bytes, s, a, na, b, nb, basis, cost, steps, workspace, Fa, Fb, C, K,
+                 DtwPath<false>{});
   }
   TACO_LAUNCH_CHECK("frame_dtw");
+  return TACO_OK;
+}
+
+int launch_frame_dtw_path(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
+                          int32_t* steps, int32_t* path_a, int32_t* path_b, void* workspace, int B, int Fa, int Fb, int C, int K,
+                          hipStream_t s) {
+  const DtwPlan p = dtw_plan(Fa, Fb, K);
+  float* coef = static_cast<float*>(workspace);
+  const DtwPath<true> out = {path_a, path_b, reinterpret_cast<uint8_t*>(coef + (int64_t)B * p.row_floats)};
+  static DynSmemOnce raised;
+  const auto in_lds = frame_dtw_kernel<true, true>, in_ws = frame_dtw_kernel<false, true>;
+  if (p.coef_in_lds) {
+    if (!ensure_dyn_smem(raised, reinterpret_cast<const void*>(in_lds), kDtwLdsBudget)) {
+      taco_set_error("frame_dtw_path: cannot raise the dynamic LDS limit to %zu bytes", kDtwLdsBudget);
+      return TACO_ELAUNCH;
+    }
+    TACO_KLAUNCH(in_lds, dim3(B), dim3(kDtwThreads), p.lds_bytes, s, a, na, b, nb, basis, cost, steps, coef, Fa, Fb, C, K, out);
+  } else {
+    TACO_KLAUNCH(in_ws, dim3(B), dim3(kDtwThreads), p.lds_bytes, s, a, na, b, nb, basis, cost, steps, coef, Fa, Fb, C, K, out);
+  }
+  TACO_LAUNCH_CHECK("frame_dtw_path");
   return TACO_OK;
 }
 
@@ -212,4 +288,31 @@ extern "C" int taco_frame_dtw(const float* a, const int32_t* na, const float* b,
                Fb, TACO_DTW_MAX_FRAMES);
   TACO_REQUIRE(workspace || dtw_plan(Fa, Fb, K).row_floats == 0, "frame_dtw: workspace is NULL and Fa=%d, Fb=%d, K=%d need one", Fa, Fb, K);
   return launch_frame_dtw(a, na, b, nb, basis, cost, steps, static_cast<float*>(workspace), B, Fa, Fb, C, K, as_stream(stream));
+}
+
+extern "C" int64_t taco_frame_dtw_path_workspace_bytes(int B, int Fa, int Fb, int K) {
+  if (!dtw_shape_ok(B, Fa, Fb, K)) return TACO_EINVAL;
+  return (int64_t)B * (dtw_plan(Fa, Fb, K).row_floats * (int64_t)sizeof(float) + dtw_way_bytes(Fa, Fb));
+}
+
+extern "C" int taco_frame_dtw_path(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
+                                   int32_t* steps, int32_t* path_a, int32_t* path_b, void* workspace, int B, int Fa, int Fb, int C, int K,
+                                   void* stream) {
+  TACO_REQUIRE(a, "frame_dtw_path: a is NULL");
+  TACO_REQUIRE(b, "frame_dtw_path: b is NULL");
+  TACO_REQUIRE(cost, "frame_dtw_path: cost is NULL");
+  TACO_REQUIRE(steps, "frame_dtw_path: steps is NULL");
+  TACO_REQUIRE(path_a, "frame_dtw_path: path_a is NULL");
+  TACO_REQUIRE(path_b, "frame_dtw_path: path_b is NULL");
+  TACO_REQUIRE(workspace, "frame_dtw_path: workspace is NULL (the direction table lives there)");
+  TACO_REQUIRE(B > 0, "frame_dtw_path: B=%d must be positive", B);
+  TACO_REQUIRE(Fa > 0 && Fb > 0, "frame_dtw_path: Fa=%d and Fb=%d must be positive", Fa, Fb);
+  TACO_REQUIRE(C > 0 && K > 0, "frame_dtw_path: C=%d and K=%d must be positive", C, K);
+  TACO_REQUIRE(basis || K == C, "frame_dtw_path: without a basis K=%d must equal C=%d", K, C);
+  TACO_REQUIRE(K <= TACO_DTW_MAX_K, "frame_dtw_path: K=%d is above the %d coefficients a frame may have", K, TACO_DTW_MAX_K);
+  TACO_REQUIRE(C <= TACO_DTW_MAX_C, "frame_dtw_path: C=%d is above the %d channels a frame may have", C, TACO_DTW_MAX_C);
+  TACO_REQUIRE(Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES, "frame_dtw_path: Fa=%d or Fb=%d is above the %d frames a row may have",
+               Fa, Fb, TACO_DTW_MAX_FRAMES);
+  return launch_frame_dtw_path(a, na, b, nb, basis, cost, steps, path_a, path_b, workspace, B, Fa, Fb, C, K,
+                               as_stream(stream));
 }

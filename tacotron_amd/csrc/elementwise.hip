@@ -1070,6 +1070,70 @@ __global__ __launch_bounds__(256) void f0_stats_kernel(const float* __restrict__
   }
 }
 
+// taco_path_f0_scores: two pitch tracks compared cell by cell along a warping path (taco_frame_dtw_path's).  One workgroup per
+// row; thread tid takes the cells t = tid, tid + 256, ... in ascending order (at most 8 of the 2047 a path can have), and the
+// threads' five counts and two sums go down the fixed tree f0_stats_kernel uses: no atomics, the same arguments give the same
+// bits.  The gross test is two single products (contraction is off in this kernel, as the header promises).
+__global__ __launch_bounds__(256) void path_f0_scores_kernel(const float* __restrict__ period_a, const float* __restrict__ period_b,
+                                                             const int32_t* __restrict__ path_a, const int32_t* __restrict__ path_b,
+                                                             const int32_t* __restrict__ steps, float gross,
+                                                             int32_t* __restrict__ counts, float* __restrict__ means, int Fa, int Fb) {
+#pragma clang fp contract(off)
+  __shared__ float red[2][256];
+  __shared__ int cnt[5][256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int P = Fa + Fb - 1;
+  int n = steps[b];
+  n = n < 0 ? 0 : (n > P ? P : n);
+  const float* __restrict__ ra = period_a + (int64_t)b * Fa;
+  const float* __restrict__ rb = period_b + (int64_t)b * Fb;
+  const int32_t* __restrict__ ia = path_a + (int64_t)b * P;
+  const int32_t* __restrict__ ib = path_b + (int64_t)b * P;
+  float s1 = 0.f, s2 = 0.f;
+  int c[5] = {0, 0, 0, 0, 0};
+  for (int t = tid; t < n; t += 256) {
+    const int i = ia[t], j = ib[t];
+    if (i < 0 || i >= Fa || j < 0 || j >= Fb) continue;   // (not a cell of the tables: skipped, nothing is read for it)
+    const float pa = ra[i], pb = rb[j];
+    const bool va = pa > 0.f, vb = pb > 0.f;
+    ++c[0];
+    if (va && vb) {
+      // formed in double and rounded once: two fp32 logarithms near 7 (1 ulp each on this hardware) would leave up to 1e-6 in a
+      // difference below 3, which is the whole tolerance of a row with one voiced cell; at most 8 cells a thread
+      const float x = (float)(log2((double)pb) - log2((double)pa));
+      s1 += x;
+      s2 += x * x;
+      ++c[1];
+      const float ga = gross * pa, gb = gross * pb;
+      if (pa > gb || pb > ga) ++c[4];
+    } else if (va) {
+      ++c[2];
+    } else if (vb) {
+      ++c[3];
+    }
+  }
+  red[0][tid] = s1;
+  red[1][tid] = s2;
+#pragma unroll
+  for (int q = 0; q < 5; ++q) cnt[q][tid] = c[q];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) {
+      red[0][tid] += red[0][tid + w];
+      red[1][tid] += red[1][tid + w];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) cnt[q][tid] += cnt[q][tid + w];
+    }
+    __syncthreads();
+  }
+  if (tid < 5) counts[5 * b + tid] = cnt[tid][0];
+  if (tid == 0) {
+    const int both = cnt[1][0];
+    means[2 * b] = both > 0 ? red[0][0] / (float)both : 0.f;
+    means[2 * b + 1] = both > 0 ? sqrtf(red[1][0] / (float)both) : 0.f;
+  }
+}
+
 // taco_corpus_batch: the forward map denorm_unframe_kernel inverts, fused into the batch gather.  out[b, e] =
 // (float(src[index[b], e]) - mean[e % C]) / stdv[e % C] over rows of `row` = Td * C elements; T = _Float16 (the corpus as
 // preprocess stores it) or float.  One IEEE subtraction and one correctly rounded division per element: the bits of NumPy's
@@ -1617,6 +1681,22 @@ extern "C" int taco_f0_stats(const float* period, const float* other, const int3
   TACO_REQUIRE(frames_per_unit >= 1, "f0_stats: frames_per_unit=%d must be >= 1", frames_per_unit);
   TACO_KLAUNCH(f0_stats_kernel, dim3((unsigned)B), dim3(256), 0, as_stream(stream), period, other, frames, frames_per_unit, stats, F);
   TACO_LAUNCH_CHECK("f0_stats");
+  return TACO_OK;
+}
+extern "C" int taco_path_f0_scores(const float* period_a, const float* period_b, const int32_t* path_a, const int32_t* path_b,
+                                   const int32_t* steps, float gross, int32_t* counts, float* means, int B, int Fa, int Fb, void* stream) {
+  TACO_REQUIRE(period_a && period_b, "path_f0_scores: period_a or period_b is NULL");
+  TACO_REQUIRE(path_a && path_b, "path_f0_scores: path_a or path_b is NULL");
+  TACO_REQUIRE(steps, "path_f0_scores: steps is NULL");
+  TACO_REQUIRE(counts && means, "path_f0_scores: counts or means is NULL");
+  TACO_REQUIRE(B > 0, "path_f0_scores: B=%d must be positive", B);
+  TACO_REQUIRE(Fa > 0 && Fb > 0, "path_f0_scores: Fa=%d and Fb=%d must be positive", Fa, Fb);
+  TACO_REQUIRE(Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES, "path_f0_scores: Fa=%d or Fb=%d is above the %d frames a row may have",
+               Fa, Fb, TACO_DTW_MAX_FRAMES);
+  TACO_REQUIRE(gross > 1.0f, "path_f0_scores: gross=%g must be above 1", (double)gross);   // (false for a NaN)
+  TACO_KLAUNCH(path_f0_scores_kernel, dim3((unsigned)B), dim3(256), 0, as_stream(stream), period_a, period_b, path_a, path_b, steps, gross,
+               counts, means, Fa, Fb);
+  TACO_LAUNCH_CHECK("path_f0_scores");
   return TACO_OK;
 }
 // The widest access taco_corpus_batch may use: the largest V in {8 (fp16 only), 4, 2, 1} that divides the row pitch, with the

@@ -202,6 +202,9 @@ int launch_alignment_scores(const float* align, const int32_t* text_length, cons
 int launch_frames_active(const float* x, float floor, int32_t* n, int B, int F, int C, hipStream_t s);
 int launch_frame_dtw(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost, int32_t* steps,
                      float* workspace, int B, int Fa, int Fb, int C, int K, hipStream_t s);
+int launch_frame_dtw_path(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
+                          int32_t* steps, int32_t* path_a, int32_t* path_b, void* workspace, int B, int Fa, int Fb, int C, int K,
+                          hipStream_t s);
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);  // y = a + b
 // L1 losses + sign gradients.  loss_parts[0..kLossParts) = per-block partial sums of |a-b| (overwritten; summed in block
 // order by launch_finish_loss: no atomics, reproducible).  grad (ldg >= N) = sign(a-b), pad columns zeroed.

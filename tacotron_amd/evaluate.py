@@ -9,7 +9,7 @@ utterances of the corpus, the ones `train --holdout N` never draws,
       with frames of log(1e-8) and stores no length.
 Only cost, steps, na, nb and the three losses of each batch travel to the host.
 
-    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval]
+    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned]
 
 prints one line per batch and a final line with the mean teacher-forced loss and the mean and worst MCD, and writes
 eval_<step>.npy, one row per utterance: index, na, nb, steps, cost, mcd (float64; COLUMNS).
@@ -28,6 +28,14 @@ the pitch level in cents and of the voiced share.  There is NO alignment between
 no path, so these are statistics per utterance, not an F0 error along the warp.  The pick's ratio 0.9 and threshold 0.3 are untuned.
 The sample rate of the lag tables and of the Hz columns is the corpus' own (meta.pkl 'sr', as preprocess records it; 16000 without one),
 and the predicted share is taken over the frames tracked, min(na, F) with F = (max_decode_iter // 4) 4 r.
+
+--f0-aligned (opt-in, implies the tracking of --f0): the F0 error ALONG the warp.  The warp is taken with its path
+(Tacotron.mel_distortion(want_path=True) -> lib.frame_dtw_path; the same cost and steps), and the two period tracks are compared
+cell by cell of that path on the device (lib.path_f0_scores); only its counts and means travel to the host.  Each row gains
+ALIGNED_COLUMNS behind F0_COLUMNS: the cells voiced in both tracks, the F0 RMSE and the F0 bias (predicted above recorded: positive)
+in cents over those cells, the voicing decision error (cells voiced in one track only / cells) and the gross pitch error (both-voiced
+cells whose periods differ by more than a factor GROSS / both-voiced cells); a column is NaN where its denominator is 0.  One more
+line per batch and one final line give their means over the utterances.  --f0 alone prints and saves exactly what it did.
 
 The final batch is padded to the batch size by repeating its last utterance; the copies are left out of the per-utterance rows and
 of the MCD statistics.  The teacher-forced loss is one number per batch (and the CBHG's batch normalisation sees the whole batch),
@@ -50,6 +58,8 @@ from .train import latest_checkpoint, open_corpus
 
 COLUMNS = ('index', 'na', 'nb', 'steps', 'cost', 'mcd')
 F0_COLUMNS = ('f0_mean', 'f0_sd', 'voiced', 'rec_f0_mean', 'rec_f0_sd', 'rec_voiced')   # appended with --f0; the first two in log2 Hz
+ALIGNED_COLUMNS = ('path_voiced', 'f0_rmse_cents', 'f0_bias_cents', 'vuv_error', 'gross_error')   # appended with --f0-aligned
+GROSS = 1.2  # a both-voiced cell is a gross pitch error when one period is above GROSS times the other (the usual 20 %)
 SR = 16000   # of a corpus whose meta.pkl records no 'sr', and of the synthetic pool
 PAD_FLOOR = float(np.float16(np.log(1e-8)))   # the value preprocess stores in the padding frames (fp16 of log(1e-8))
 
@@ -119,12 +129,37 @@ def f0_summary(cols):
             float(np.nanmean(share)) if np.isfinite(share).any() else float('nan'))
 
 
+def aligned_columns(counts, means):
+    """lib.path_f0_scores' counts (n, 5) and means (n, 2), a the predicted track and b the recorded one -> (n, 5) float64 in the order
+    ALIGNED_COLUMNS; NaN where the denominator (the both-voiced cells; for vuv_error the cells) is 0"""
+    counts = np.asarray(counts, dtype=np.float64).reshape(-1, 5)
+    means = np.asarray(means, dtype=np.float64).reshape(-1, 2)
+    cells, both = counts[:, 0], counts[:, 1]
+    out = np.full((len(counts), 5), np.nan)
+    out[:, 0] = both
+    some = both > 0
+    out[some, 1] = 1200.0 * means[some, 1]
+    out[some, 2] = 1200.0 * means[some, 0]    # (log2 period_recorded - log2 period_predicted: predicted higher in pitch -> positive)
+    np.divide(counts[:, 2] + counts[:, 3], cells, out=out[:, 3], where=cells > 0)
+    np.divide(counts[:, 4], both, out=out[:, 4], where=some)
+    return out
+
+
+def aligned_summary(cols):
+    """(n, 5) in the order ALIGNED_COLUMNS -> (mean F0 RMSE in cents, mean V/UV error, mean gross error) over the utterances that have
+    one; NaN without any"""
+    cols = np.asarray(cols, dtype=np.float64).reshape(-1, 5)
+    return tuple(float(np.nanmean(cols[:, k])) if np.isfinite(cols[:, k]).any() else float('nan') for k in (1, 3, 4))
+
+
 def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None,
-             f0=False):
+             f0=False, f0_aligned=False):
     """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  f0: rows (n, 12), F0_COLUMNS behind
-    COLUMNS.  stop: the lib.TacoStopRule of the
+    COLUMNS.  f0_aligned (implies f0): rows (n, 17), ALIGNED_COLUMNS behind those.  stop: the lib.TacoStopRule of the
     free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
-    ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection)."""
+    ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection; with f0_aligned also the two period
+    tracks 'period' and 'rec_period')."""
+    f0 = bool(f0 or f0_aligned)
     torch.cuda.set_device(device)
     dev = torch.device('cuda', device)
     corpus = open_corpus(config.data_path)
@@ -173,7 +208,8 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     raw = torch.empty(B, Td, 80 * r, device=dev)
     nb = torch.empty(B, dtype=torch.int32, device=dev)
     zeros, ones = torch.zeros(80 * r, device=dev), torch.ones(80 * r, device=dev)
-    per = {k: [] for k in ('na', 'nb', 'steps', 'cost') + (('f0', 'rec_f0', 'f0_frames') if f0 else ())}
+    per = {k: [] for k in ('na', 'nb', 'steps', 'cost') + (('f0', 'rec_f0', 'f0_frames') if f0 else ())
+           + (('path_counts', 'path_means') if f0_aligned else ())}
     if f0:
         Cs = batch['stft'].shape[2] // r
         w, g, lag_min, lag_max = lib.f0_tables(sr, C=Cs)
@@ -196,14 +232,25 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         lib.corpus_batch(feeder.data['mel'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw)
         lib.denorm_unframe(raw, zeros, ones, r, spec=recorded)
         lib.frames_active(recorded, PAD_FLOOR, nb)
-        cost, steps, na = free.mel_distortion(recorded, nb, cepstra)
+        if f0_aligned:
+            cost, steps, na, path_a, path_b = free.mel_distortion(recorded, nb, cepstra, want_path=True)
+        else:
+            cost, steps, na = free.mel_distortion(recorded, nb, cepstra)
         if f0:   # the decoder's own frames over lengths * r (max_decode_iter steps wide), then the recording's over nb
             pmags = lib.denorm_unframe(free.output, smean, sstd, r, want_spec=False, want_mag_t=True)
             Fp = pmags.shape[2]   # (the tracker counts over clamp(lengths r, 0, Fp); na is lengths r unclamped)
-            pred_stats = lib.f0_stats(lib.frames_f0(pmags, free.lengths, r, **f0_opt)[0], None, free.lengths, r)
+            pred_period = lib.frames_f0(pmags, free.lengths, r, **f0_opt)[0]
+            pred_stats = lib.f0_stats(pred_period, None, free.lengths, r)
             lib.corpus_batch(feeder.data['stft'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw_stft)
             lib.denorm_unframe(raw_stft, szeros, sones, r, want_spec=False, want_mag_t=True, mag_t=mags)
-            rec_stats = lib.f0_stats(lib.frames_f0(mags, nb, 1, **f0_opt)[0], None, nb, 1)
+            rec_period = lib.frames_f0(mags, nb, 1, **f0_opt)[0]
+            rec_stats = lib.f0_stats(rec_period, None, nb, 1)
+        if f0_aligned:   # the two tracks cell by cell of the warp's path; the path indexes the predicted mel frames
+            Fm = path_a.shape[1] - recorded.shape[1] + 1
+            if Fp != Fm:
+                raise ValueError('evaluate --f0-aligned: the predicted pitch track is %d frames wide and the predicted mel frames %d: '
+                                 'the path of one does not index the other' % (Fp, Fm))
+            path_counts, path_means = lib.path_f0_scores(pred_period, rec_period, path_a, path_b, steps, GROSS)
         loss = forced._loss.cpu().numpy().astype(np.float64)       # the host synchronisation of the batch
         forced.check()
         free.check()
@@ -211,11 +258,15 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         if f0:
             got['f0'], got['rec_f0'] = pred_stats.cpu().numpy(), rec_stats.cpu().numpy()
             got['f0_frames'] = np.minimum(got['na'], Fp)
+            if f0_aligned:
+                got['path_counts'], got['path_means'] = path_counts.cpu().numpy(), path_means.cpu().numpy()
             cents, share = f0_summary(np.concatenate([f0_columns(got['f0'][:valid], got['f0_frames'][:valid], sr),
                                                       f0_columns(got['rec_f0'][:valid], got['nb'][:valid], sr)], axis=1))
         if trace is not None:
             trace.append({'predicted': free.predicted_mel()[0].cpu().numpy(), 'recorded': recorded.cpu().numpy(), 'na': got['na'].copy(),
                           'nb': got['nb'].copy()})
+            if f0_aligned:
+                trace[-1].update(period=pred_period.cpu().numpy(), rec_period=rec_period.cpu().numpy())
         for k, v in got.items():
             per[k].append(v)
         losses.append(loss)
@@ -225,12 +276,19 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
                  int(got['nb'][:valid].sum())))
         if f0:
             print('batch %d pitch level %+.0f cents, voiced share %+.3f against the recordings (per utterance, not aligned)' % (i, cents, share))
+        if f0_aligned:
+            print('batch %d F0 RMSE %.0f cents, V/UV error %.3f, gross error %.3f along the warping path (aligned)'
+                  % ((i,) + aligned_summary(aligned_columns(got['path_counts'][:valid], got['path_means'][:valid]))))
     feeder.close()
     rows = mcd_rows(unpad(batches, [b[0] for b in batches]), *(unpad(batches, per[k]) for k in ('na', 'nb', 'steps', 'cost')))
     if f0:
         rows = f0_rows(rows, unpad(batches, per['f0']), unpad(batches, per['f0_frames']), unpad(batches, per['rec_f0']), rows[:, 2], sr)
         print('held out: pitch level %+.0f cents, voiced share %+.3f against the recordings (untuned tracker, per utterance, not aligned)'
               % f0_summary(rows[:, 6:]))
+    if f0_aligned:
+        rows = np.concatenate([rows, aligned_columns(unpad(batches, per['path_counts']), unpad(batches, per['path_means']))], axis=1)
+        print('held out: F0 RMSE %.0f cents, V/UV error %.3f, gross error %.3f along the warping path (untuned tracker, aligned)'
+              % aligned_summary(rows[:, 12:]))
     weight = np.array([valid for _, valid in batches], dtype=np.float64)
     mean_loss = float((np.stack(losses)[:, 0] * weight).sum() / weight.sum())
     print('held out: %d utterances, teacher-forced loss %.1f, MCD-DTW mean %.3f dB worst %.3f dB (utterance %d) over %d cepstra of '
@@ -252,6 +310,9 @@ def parse_args(argv=None):
     ap.add_argument('--f0', action='store_true',
                     help='also track the pitch of the predicted and of the recorded magnitude frames on the device and append '
                          'F0_COLUMNS to every row (untuned tracker; statistics per utterance, no alignment)')
+    ap.add_argument('--f0-aligned', action='store_true',
+                    help='--f0, and the F0 error along the warping path: ALIGNED_COLUMNS (F0 RMSE and bias in cents, voicing decision '
+                         'error, gross pitch error) behind F0_COLUMNS')
     return ap.parse_args(argv)
 
 
@@ -262,7 +323,7 @@ def main(argv=None, config=None):
     if config is None:
         c.data_path = 'data/%s/' % a.train_set
     checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
-    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0)
+    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0, f0_aligned=a.f0_aligned)
 
 
 if __name__ == '__main__':

@@ -105,6 +105,9 @@ EXPORTS = {
     'taco_frames_active': (C.c_int, [_P, C.c_float, _P, _I, _I, _I, _P]),
     'taco_frame_dtw_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
     'taco_frame_dtw': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'taco_frame_dtw_path_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
+    'taco_frame_dtw_path': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'taco_path_f0_scores': (C.c_int, [_P, _P, _P, _P, _P, C.c_float, _P, _P, _I, _I, _I, _P]),
     'taco_clip_adam_step': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P]),
     'taco_clip_adam_step_guarded': (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_int64, _P, _P, _P, _P]),
     'taco_clear_error': (C.c_int, [_SH, _I, _P, _P]),
@@ -805,18 +808,8 @@ def frames_active(x, floor, n=None):
     return n
 
 
-def frame_dtw_workspace_bytes(B, Fa, Fb, K) -> int:
-    return _size('taco_frame_dtw_workspace_bytes', B, Fa, Fb, K)
-
-
-def frame_dtw(a, b, na=None, nb=None, basis=None, cost=None, steps=None, work=None):
-    """Dynamic time warping per batch row (include/taco_hip.h taco_frame_dtw): a (B, Fa, C), b (B, Fb, C) fp32 chronological frames,
-    na / nb (B) int32 or None (all Fa / Fb frames), basis (K, C) fp32 or None (the channels themselves), all on the device ->
-    (cost (B) fp32, steps (B) int32), device tensors: the summed Euclidean distance of the coefficient vectors along the cheapest
-    warping path and the number of cells on it; cost / steps is the mean distance per step, MCD_DB times that the distortion in dB.
-    Enqueued on the current stream; nothing is copied and nothing waits.  cost / steps / work: the caller's own buffers (work: uint8,
-    frame_dtw_workspace_bytes(B, Fa, Fb, K) bytes); default: fresh ones."""
-    who = 'frame_dtw'
+def _dtw_args(who, a, b, na, nb, basis, cost, steps):
+    """the argument checks frame_dtw and frame_dtw_path share -> (B, Fa, Fb, C, K, device, cost, steps)"""
     _frames_arg(who, 'a', a)
     _frames_arg(who, 'b', b)
     B, Fa, Cw = a.shape
@@ -839,6 +832,22 @@ def frame_dtw(a, b, na=None, nb=None, basis=None, cost=None, steps=None, work=No
                          % (who, DTW_MAX_K, K, ' (no basis: the channels themselves)' if basis is None else ''))
     cost = _own_or_given(cost, (B,), torch.float32, dev, who + ': cost')
     steps = _own_or_given(steps, (B,), torch.int32, dev, who + ': steps')
+    return B, Fa, Fb, Cw, K, dev, cost, steps
+
+
+def frame_dtw_workspace_bytes(B, Fa, Fb, K) -> int:
+    return _size('taco_frame_dtw_workspace_bytes', B, Fa, Fb, K)
+
+
+def frame_dtw(a, b, na=None, nb=None, basis=None, cost=None, steps=None, work=None):
+    """Dynamic time warping per batch row (include/taco_hip.h taco_frame_dtw): a (B, Fa, C), b (B, Fb, C) fp32 chronological frames,
+    na / nb (B) int32 or None (all Fa / Fb frames), basis (K, C) fp32 or None (the channels themselves), all on the device ->
+    (cost (B) fp32, steps (B) int32), device tensors: the summed Euclidean distance of the coefficient vectors along the cheapest
+    warping path and the number of cells on it; cost / steps is the mean distance per step, MCD_DB times that the distortion in dB.
+    Enqueued on the current stream; nothing is copied and nothing waits.  cost / steps / work: the caller's own buffers (work: uint8,
+    frame_dtw_workspace_bytes(B, Fa, Fb, K) bytes); default: fresh ones."""
+    who = 'frame_dtw'
+    B, Fa, Fb, Cw, K, dev, cost, steps = _dtw_args(who, a, b, na, nb, basis, cost, steps)
     if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
         raise ValueError('%s: a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
     nbytes = frame_dtw_workspace_bytes(B, Fa, Fb, K)
@@ -846,6 +855,68 @@ def frame_dtw(a, b, na=None, nb=None, basis=None, cost=None, steps=None, work=No
     _check(_lib.taco_frame_dtw(ptr(a), ptr(na), ptr(b), ptr(nb), ptr(basis), ptr(cost), ptr(steps), ptr(work) if nbytes else None,
                                B, Fa, Fb, Cw, K, stream_ptr()), 'taco_frame_dtw')
     return cost, steps
+
+
+def frame_dtw_path_workspace_bytes(B, Fa, Fb, K) -> int:
+    return _size('taco_frame_dtw_path_workspace_bytes', B, Fa, Fb, K)
+
+
+def frame_dtw_path(a, b, na=None, nb=None, basis=None, cost=None, steps=None, path_a=None, path_b=None, work=None):
+    """frame_dtw with the warping path (include/taco_hip.h taco_frame_dtw_path): the same arguments, the same cost and steps bit for
+    bit -> (cost, steps, path_a, path_b); path_a / path_b (B, Fa + Fb - 1) int32: entries t < steps[b] are the cells (i_t, j_t) of the
+    path from (0, 0) to (na - 1, nb - 1), the rest -1.  work: uint8, frame_dtw_path_workspace_bytes(B, Fa, Fb, K) bytes (never 0: the
+    direction table, a byte per cell of Fa + Fb - 1 diagonals of Fa).  Enqueued on the current stream; nothing is copied and nothing
+    waits.  The outputs and work: the caller's own buffers; default: fresh ones."""
+    who = 'frame_dtw_path'
+    B, Fa, Fb, Cw, K, dev, cost, steps = _dtw_args(who, a, b, na, nb, basis, cost, steps)
+    P = Fa + Fb - 1
+    path_a = _own_or_given(path_a, (B, P), torch.int32, dev, who + ': path_a')
+    path_b = _own_or_given(path_b, (B, P), torch.int32, dev, who + ': path_b')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    work = _own_or_given(work, (frame_dtw_path_workspace_bytes(B, Fa, Fb, K),), torch.uint8, dev, who + ': work')
+    _check(_lib.taco_frame_dtw_path(ptr(a), ptr(na), ptr(b), ptr(nb), ptr(basis), ptr(cost), ptr(steps), ptr(path_a), ptr(path_b),
+                                    ptr(work), B, Fa, Fb, Cw, K, stream_ptr()), 'taco_frame_dtw_path')
+    return cost, steps, path_a, path_b
+
+
+PATH_SCORE_COUNTS = ('cells', 'both_voiced', 'a_only', 'b_only', 'gross')   # the columns of path_f0_scores' counts
+
+
+def path_f0_scores(period_a, period_b, path_a, path_b, steps, gross=1.2, counts=None, means=None):
+    """Two pitch tracks compared along a warping path (include/taco_hip.h taco_path_f0_scores): period_a (B, Fa), period_b (B, Fb)
+    fp32 as frames_f0 returns them, path_a / path_b (B, Fa + Fb - 1) int32 and steps (B) int32 as frame_dtw_path returns them, all on
+    the device -> (counts (B, 5) int32 in the order PATH_SCORE_COUNTS, means (B, 2) fp32: the mean and the root mean square of
+    log2(period_b) - log2(period_a) over the cells voiced in both -- the octaves by which a lies above b; x 1200: cents).  A cell is a
+    gross error when one period is more than `gross` times the other.  Nothing is read back."""
+    who = 'path_f0_scores'
+    if not torch.is_tensor(period_a) or period_a.dim() != 2 or period_a.dtype != torch.float32 or min(period_a.shape) < 1:
+        raise ValueError('%s: period_a must be a float32 tensor of shape (B, Fa), got %s %s'
+                         % (who, getattr(period_a, 'dtype', type(period_a)), tuple(getattr(period_a, 'shape', ()))))
+    B, Fa = period_a.shape
+    dev = period_a.device
+    if not torch.is_tensor(period_b) or period_b.dim() != 2 or period_b.shape[0] != B or period_b.shape[1] < 1 \
+            or period_b.dtype != torch.float32 or period_b.device != dev:
+        raise ValueError('%s: period_b must be a float32 tensor of shape (%d, Fb) on %s' % (who, B, dev))
+    Fb = period_b.shape[1]
+    if max(Fa, Fb) > DTW_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got Fa = %d, Fb = %d' % (who, DTW_MAX_FRAMES, Fa, Fb))
+    if not period_a.is_contiguous() or not period_b.is_contiguous():
+        raise ValueError('%s: period_a and period_b must be contiguous' % who)
+    P = Fa + Fb - 1
+    for name, t, shape in (('path_a', path_a, (B, P)), ('path_b', path_b, (B, P)), ('steps', steps, (B,))):
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            raise ValueError('%s: %s must be a contiguous int32 tensor of shape %s on %s' % (who, name, shape, dev))
+    gross = float(gross)
+    if not gross > 1.0 or not C.c_float(gross).value > 1.0:   # (NaN fails)
+        raise ValueError('%s: gross must be above 1 (as a float32 too), got %r' % (who, gross))
+    counts = _own_or_given(counts, (B, 5), torch.int32, dev, who + ': counts')
+    means = _own_or_given(means, (B, 2), torch.float32, dev, who + ': means')
+    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
+        raise ValueError('%s: period_a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    _check(_lib.taco_path_f0_scores(ptr(period_a), ptr(period_b), ptr(path_a), ptr(path_b), ptr(steps), gross, ptr(counts), ptr(means),
+                                    B, Fa, Fb, stream_ptr()), 'taco_path_f0_scores')
+    return counts, means
 
 
 def corpus_batch_width(src_addr, out_addr, row, fp16) -> int:

@@ -289,18 +289,31 @@ class Tacotron(object):
             torch.mul(self.lengths, self.shape.r, out=e['na'])
         return e['frames'], e['na']
 
-    def mel_distortion(self, recorded, nb=None, cepstra=13):
+    def mel_distortion(self, recorded, nb=None, cepstra=13, want_path=False):
         """Distance of the model's mel frames from `recorded` over a dynamic-time-warping path (lib.frame_dtw): recorded (B, Fb, 80)
         fp32 chronological de-normalised log-mel frames on the device, nb (B) int32 their frame counts or None (all Fb), cepstra the
         DCT coefficients 1 .. cepstra the distance is taken over (lib.dct_basis) -> (cost (B) fp32, steps (B) int32, na (B) int32),
         device tensors; lib.MCD_DB * cost / steps is the row's mel-cepstral distortion in dB, taken over this model's own 80-band
         natural-log mel frames.  The prediction is predicted_mel().  Everything is enqueued on the current stream into tensors the
-        model allocates once (per cepstra / Fb) and returns every time; no copy and no synchronisation."""
+        model allocates once (per cepstra / Fb) and returns every time; no copy and no synchronisation.
+        want_path: the warp with its path (lib.frame_dtw_path; the same cost and steps) -> (cost, steps, na, path_a, path_b), the
+        last two (B, F + Fb - 1) int32: the predicted and the recorded frame of every cell of the path, -1 behind steps."""
         cepstra = int(cepstra)
         lib._frames_arg('mel_distortion', 'recorded', recorded)
         e = self._mel_eval_tensors(cepstra)
         frames, na = self.predicted_mel()
         key = (recorded.shape[1], cepstra)
+        if want_path:
+            if key not in e.setdefault('path', {}):
+                P = frames.shape[1] + recorded.shape[1] - 1
+                e['path'][key] = (torch.empty(self.shape.B, P, dtype=torch.int32, device=self.device),
+                                  torch.empty(self.shape.B, P, dtype=torch.int32, device=self.device),
+                                  torch.empty(lib.frame_dtw_path_workspace_bytes(self.shape.B, frames.shape[1], *key), dtype=torch.uint8,
+                                              device=self.device))
+            path_a, path_b, work = e['path'][key]
+            cost, steps, path_a, path_b = lib.frame_dtw_path(frames, recorded, na, nb, e['basis'][cepstra], e['cost'], e['steps'], path_a,
+                                                             path_b, work)
+            return cost, steps, na, path_a, path_b
         if key not in e['work']:   # (empty unless the coefficients of both sequences do not fit LDS: include/taco_hip.h)
             e['work'][key] = torch.empty(lib.frame_dtw_workspace_bytes(self.shape.B, frames.shape[1], *key), dtype=torch.uint8,
                                          device=self.device)
