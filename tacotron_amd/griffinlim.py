@@ -85,6 +85,7 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         if unknown:
             raise ValueError('invert_spectrogram: f0: unknown settings %s' % sorted(unknown))
         f0_lengths = opt.pop('lengths', lengths)
+        f0_unit = r if f0_lengths is not None else 1
         if not {'weight', 'gain', 'lag_min', 'lag_max'} & set(opt):   # (none given: the production tables at this bin count)
             opt['weight'], opt['gain'], opt['lag_min'], opt['lag_max'] = lib.f0_tables(C=out.shape[2] // r)
         for k in ('weight', 'gain'):   # (host tables go up once, not once per track)
@@ -103,36 +104,30 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
+    per_unit = r if lengths is not None else 1
     if pitch is not None:
-        if torch.is_tensor(pitch) and pitch.device.type != 'cpu':
-            pitch_q = pitch
-        else:
-            semitones = pitch.tolist() if torch.is_tensor(pitch) else pitch
-            pitch_q = [lib.pitch_step(x) for x in semitones] if hasattr(semitones, '__len__') else lib.pitch_step(semitones)
+        pitch_q = lib.steps_of(pitch, lib.pitch_step)
         if track:
-            track('model', mag_t, f0_lengths, r if f0_lengths is not None else 1)
-        mag_t = lib.frames_pitch(mag_t, lengths, pitch_q, frames_per_unit=r if lengths is not None else 1, lifter=lifter)
+            track('model', mag_t, f0_lengths, f0_unit)
+        mag_t = lib.frames_pitch(mag_t, lengths, pitch_q, frames_per_unit=per_unit, lifter=lifter)
         if track:
-            track('pitched', mag_t, f0_lengths, r if f0_lengths is not None else 1)
-            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], f0_lengths, r if f0_lengths is not None else 1)
+            track('pitched', mag_t, f0_lengths, f0_unit)
+            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], f0_lengths, f0_unit)
     elif track:
-        track('model', mag_t, f0_lengths, r if f0_lengths is not None else 1)
+        track('model', mag_t, f0_lengths, f0_unit)
     if track:
         last = 'pitched' if pitch is not None else 'model'
         tracks['vocoder'], tracks['vocoder_stats'] = tracks[last], tracks[last + '_stats']
     done = (lambda res: res) if not track else (lambda res: (tuple(res) if isinstance(res, tuple) else (res,)) + (tracks,))
     if rate is not None:
         F = mag_t.shape[2]
-        if torch.is_tensor(rate) and rate.device.type != 'cpu':
-            step_q, slowest = rate, lib.STRETCH_MIN_STEP
+        step_q = lib.steps_of(rate, lib.stretch_step)
+        if torch.is_tensor(step_q):   # (on a device, never read: any rate down to the slowest)
+            slowest = lib.STRETCH_MIN_STEP
         else:
-            rates = rate.tolist() if torch.is_tensor(rate) else rate
-            one = not hasattr(rates, '__len__')
-            step_q = lib.stretch_step(rates) if one else [lib.stretch_step(x) for x in rates]
-            slowest = step_q if one else min(step_q, default=lib.STRETCH_ONE)
+            slowest = min(step_q, default=lib.STRETCH_ONE) if isinstance(step_q, list) else step_q
         Fo = max(5, lib.stretch_capacity(F, slowest))
-        stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=r if lengths is not None else 1, Fo=Fo,
-                                                   frames_out=frames_out)
+        stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=per_unit, Fo=Fo, frames_out=frames_out)
         phase0 = None if phase0 is None else phase0.contiguous()
         if track:   # (the stretched rows hold frames_out frames each, whatever `lengths` was)
             track('vocoder', stretched, frames_out, 1)

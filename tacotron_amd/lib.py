@@ -20,6 +20,9 @@ from . import QUEUES_SET_BY_USER as _QUEUES_SET_BY_USER, TORCH_IMPORTED_FIRST as
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from .argcheck import (int_arg, no_overlap, on_gpu, pow2_bins, step_q_arg, tensor_arg,   # noqa: E402
+                       host_int32 as _host_int32, own_or_given as _own_or_given, unit_interval as _unit_interval)
+
 # If the process may have touched the GPU before importing this package (and did not set the variable itself) the runtime is up
 # with its default of 4 queues: the default came too late, and high-priority communication streams would then cost 1.3 ms per
 # step instead of saving one (dist._comm_priority asks here).  "May have": the runtime reads the variable at the FIRST HIP API call
@@ -81,6 +84,7 @@ _lib = C.CDLL(LIB_PATH)
 _P = C.c_void_p
 _I = C.c_int
 _SH = C.POINTER(TacoShape)
+_INT_MAX = (1 << 31) - 1   # the largest value an `int` argument of the C ABI holds
 
 EXPORTS = {
     'taco_version': (C.c_int, []),
@@ -186,16 +190,6 @@ def _size(fn_name, *args) -> int:
     if n < 0:
         raise TacoError('%s(%s): bad arguments (rc=%d)' % (fn_name, ', '.join(repr(a) for a in args), n))
     return n
-
-
-def _unit_interval(x, what) -> float:
-    """x as a float in [0, 1) that is still below 1 as a float32, or ValueError"""
-    x = float(x)
-    if not 0.0 <= x < 1.0:   # (NaN fails both comparisons)
-        raise ValueError('%s must be in [0, 1), got %r' % (what, x))
-    if C.c_float(x).value >= 1.0:
-        raise ValueError('%s %r rounds to 1 in float32' % (what, x))
-    return x
 
 
 def param_count(shape: TacoShape) -> int:
@@ -333,27 +327,17 @@ def alignment_scores(alignments, text_length, steps=None, max_jump=MAX_JUMP, cou
     order ALIGN_COUNTS, means (B, 2) fp32 in the order ALIGN_MEANS), device tensors.  Enqueued on the current stream; nothing is
     copied and nothing waits.  counts / means: the caller's own buffers; default: fresh ones."""
     who = 'alignment_scores'
-    if not torch.is_tensor(alignments) or alignments.dim() != 3 or alignments.dtype != torch.float32 or min(alignments.shape) < 1:
-        raise ValueError('%s: alignments must be a float32 tensor of shape (B, Td, Tt), got %s %s'
-                         % (who, getattr(alignments, 'dtype', type(alignments)), tuple(getattr(alignments, 'shape', ()))))
-    if not alignments.is_contiguous():
-        raise ValueError('%s: alignments must be contiguous' % who)
-    B, Td, Tt = alignments.shape
+    B, Td, Tt = tensor_arg(who, 'alignments', alignments, torch.float32, ('B', 'Td', 'Tt'))
     dev = alignments.device
     if Td > ALIGN_MAX_TD or Tt > ALIGN_MAX_TT:
         raise ValueError('%s: at most %d steps and %d characters, got Td = %d, Tt = %d' % (who, ALIGN_MAX_TD, ALIGN_MAX_TT, Td, Tt))
-    for name, t, needed in (('text_length', text_length, True), ('steps', steps, False)):
-        if t is None and not needed:
-            continue
-        if (not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
-            raise ValueError('%s: %s must be a contiguous int32 tensor of shape (%d,) on %s' % (who, name, B, dev))
-    if isinstance(max_jump, bool) or int(max_jump) != max_jump or not 0 <= int(max_jump) < (1 << 31):
-        raise ValueError('%s: max_jump must be an integer in [0, 2^31), got %r' % (who, max_jump))
+    tensor_arg(who, 'text_length', text_length, torch.int32, (B,), dev)
+    tensor_arg(who, 'steps', steps, torch.int32, (B,), dev, optional=True)
+    max_jump = int_arg(who, 'max_jump', max_jump, 0, _INT_MAX)
     counts = _own_or_given(counts, (B, len(ALIGN_COUNTS)), torch.int32, dev, who + ': counts')
     means = _own_or_given(means, (B, len(ALIGN_MEANS)), torch.float32, dev, who + ': means')
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: alignments must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
-    _check(_lib.taco_alignment_scores(ptr(alignments), ptr(text_length), ptr(steps), int(max_jump), ptr(counts), ptr(means), B, Td, Tt,
+    on_gpu(who, 'alignments', dev)
+    _check(_lib.taco_alignment_scores(ptr(alignments), ptr(text_length), ptr(steps), max_jump, ptr(counts), ptr(means), B, Td, Tt,
                                       stream_ptr()), 'taco_alignment_scores')
     return counts, means
 
@@ -434,15 +418,6 @@ def debug_spin(blocks, threads, lds_bytes, usec, stream=None):
     _check(_lib.taco_debug_spin(int(blocks), int(threads), int(lds_bytes), int(usec), sp), 'taco_debug_spin')
 
 
-def _own_or_given(given, shape, dtype, device, what):
-    """a fresh torch.empty tensor, or the caller's buffer after a shape / dtype / device check"""
-    if given is None:
-        return torch.empty(*shape, dtype=dtype, device=device)
-    if tuple(given.shape) != tuple(shape) or given.dtype != dtype or given.device != device or not given.is_contiguous():
-        raise ValueError('%s: expected a contiguous %s tensor of shape %s on %s' % (what, dtype, tuple(shape), device))
-    return given
-
-
 def denorm_unframe(output, stft_mean, stft_std, r, want_spec=True, want_mag_t=False, spec=None, mag_t=None):
     """(B, Td, r*C) normalised r-frame layout -> chronological de-normalised (B, F, C) [and / or exp() transposed (B, C, F)].
     spec / mag_t: the caller's own output buffers (default: fresh ones)."""
@@ -492,6 +467,17 @@ def stretch_capacity(F, step_q_min) -> int:
     return stretch_frames(F, step_q_min)
 
 
+def _frames_cap(who, F):
+    if F > STRETCH_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
+
+
+def _row_frames_arg(who, frames, frames_per_unit, B, dev) -> int:
+    """the per-row frame counts of the frames_* calls: frames None or (B) int32 on dev, in units of frames_per_unit >= 1 (returned)"""
+    tensor_arg(who, 'frames', frames, torch.int32, (B,), dev, optional=True)
+    return int_arg(who, 'frames_per_unit', frames_per_unit, 1)
+
+
 def frames_stretch(mag_t, frames=None, step_q=None, frames_per_unit=1, Fo=None, out=None, frames_out=None):
     """Speaking rate on the magnitude frames (include/taco_hip.h taco_frames_stretch): mag_t (B, C, F) fp32 on the device ->
     (out (B, C, Fo) fp32, frames_out (B) int32): row b's first F_b = clamp(frames[b] * frames_per_unit, 0, F) frames resampled
@@ -501,52 +487,24 @@ def frames_stretch(mag_t, frames=None, step_q=None, frames_per_unit=1, Fo=None, 
     Fo: default the capacity at the slowest step the host knows of (16384 for a device tensor).  out / frames_out: the caller's own
     buffers; default: fresh ones.  Enqueued on the current stream; nothing is read back and nothing waits."""
     who = 'frames_stretch'
-    if not torch.is_tensor(mag_t) or mag_t.dim() != 3 or mag_t.dtype != torch.float32 or min(mag_t.shape) < 1:
-        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, C, F), got %s %s'
-                         % (who, getattr(mag_t, 'dtype', type(mag_t)), tuple(getattr(mag_t, 'shape', ()))))
-    if not mag_t.is_contiguous():
-        raise ValueError('%s: mag_t must be contiguous' % who)
-    B, Cw, F = mag_t.shape
+    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
     dev = mag_t.device
-    if F > STRETCH_MAX_FRAMES:
-        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
-    if frames is not None and (not torch.is_tensor(frames) or tuple(frames.shape) != (B,) or frames.dtype != torch.int32
-                               or frames.device != dev or not frames.is_contiguous()):
-        raise ValueError('%s: frames must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
-    if isinstance(frames_per_unit, bool) or int(frames_per_unit) != frames_per_unit or int(frames_per_unit) < 1:
-        raise ValueError('%s: frames_per_unit must be an integer >= 1, got %r' % (who, frames_per_unit))
-    slowest = STRETCH_MIN_STEP
-    if step_q is None:
-        slowest = STRETCH_ONE
-    elif torch.is_tensor(step_q) and step_q.device.type != 'cpu':
-        if tuple(step_q.shape) != (B,) or step_q.dtype != torch.int32 or step_q.device != dev or not step_q.is_contiguous():
-            raise ValueError('%s: step_q on a device must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
-    else:
-        one = not torch.is_tensor(step_q) and not hasattr(step_q, '__len__')
-        host = _host_int32([step_q] * B if one else step_q, B, who + ': step_q')
-        if min(host) < STRETCH_MIN_STEP or max(host) > STRETCH_MAX_STEP:
-            raise ValueError('%s: step_q must be in [%d, %d] (rates 0.25 to 4), got %r'
-                             % (who, STRETCH_MIN_STEP, STRETCH_MAX_STEP, step_q if one else host))
-        slowest = min(host)
-        step_q = torch.tensor(host, dtype=torch.int32).to(dev)
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    step_q, slowest = step_q_arg(who, step_q, B, dev, STRETCH_MIN_STEP, STRETCH_MAX_STEP, 'rates 0.25 to 4')
     if Fo is None:
-        Fo = stretch_capacity(F, slowest)
+        Fo = stretch_capacity(F, STRETCH_ONE if slowest is None else slowest)
         if out is None and Fo > STRETCH_MAX_FRAMES:
             raise ValueError('%s: F = %d frames at step %d may need %d output frames, more than %d: give Fo'
                              % (who, F, slowest, Fo, STRETCH_MAX_FRAMES))
         if out is not None and torch.is_tensor(out) and out.dim() == 3:
             Fo = out.shape[2]
-    if isinstance(Fo, bool) or int(Fo) != Fo or not 1 <= int(Fo) <= STRETCH_MAX_FRAMES:
-        raise ValueError('%s: Fo must be an integer in [1, %d], got %r' % (who, STRETCH_MAX_FRAMES, Fo))
-    Fo = int(Fo)
+    Fo = int_arg(who, 'Fo', Fo, 1, STRETCH_MAX_FRAMES)
     out = _own_or_given(out, (B, Cw, Fo), torch.float32, dev, who + ': out')
-    m0, o0 = mag_t.data_ptr(), out.data_ptr()
-    if o0 < m0 + B * Cw * F * 4 and m0 < o0 + B * Cw * Fo * 4:
-        raise ValueError('%s: out may not overlap mag_t' % who)
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
     frames_out = _own_or_given(frames_out, (B,), torch.int32, dev, who + ': frames_out')
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
-    _check(_lib.taco_frames_stretch(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(step_q), ptr(out), ptr(frames_out), B, Cw, F, Fo,
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_stretch(ptr(mag_t), ptr(frames), frames_per_unit, ptr(step_q), ptr(out), ptr(frames_out), B, Cw, F, Fo,
                                     stream_ptr()), 'taco_frames_stretch')
     return out, frames_out
 
@@ -567,6 +525,20 @@ def pitch_step(semitones) -> int:
     return int(round(65536.0 * 2.0 ** (-semitones / 12.0)))
 
 
+def steps_of(values, to_step, n=None):
+    """Rates or pitches -> step_q values by to_step (stretch_step / pitch_step): None -> None; a number -> an int; a host sequence or
+    host tensor -> a list of ints (ValueError unless it holds n of them, when n is given); a tensor on a device holds step_q values
+    already and is passed through, never read"""
+    if values is None or (torch.is_tensor(values) and values.device.type != 'cpu'):
+        return values
+    values = values.tolist() if torch.is_tensor(values) else values
+    if not hasattr(values, '__len__'):
+        return to_step(values)
+    if n is not None and len(values) != n:
+        raise ValueError('%d values for %d rows' % (len(values), n))
+    return [to_step(x) for x in values]
+
+
 def frames_pitch(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, out=None):
     """Pitch on the magnitude frames (include/taco_hip.h taco_frames_pitch): mag_t (B, C, F) fp32 on the device, C - 1 a power of two
     in [8, 1024] -> out (B, C, F) fp32: in the first F_b = clamp(frames[b] * frames_per_unit, 0, F) frames of row b the log-excitation
@@ -577,45 +549,18 @@ def frames_pitch(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, 
     lifter: 1 .. min(64, (C - 1) / 2); the default 32 (quefrencies up to 2 ms at 16 kHz) is untuned.  out: the caller's own buffer;
     default: a fresh one.  Enqueued on the current stream; nothing is read back and nothing waits."""
     who = 'frames_pitch'
-    if not torch.is_tensor(mag_t) or mag_t.dim() != 3 or mag_t.dtype != torch.float32 or min(mag_t.shape) < 1:
-        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, C, F), got %s %s'
-                         % (who, getattr(mag_t, 'dtype', type(mag_t)), tuple(getattr(mag_t, 'shape', ()))))
-    if not mag_t.is_contiguous():
-        raise ValueError('%s: mag_t must be contiguous' % who)
-    B, Cw, F = mag_t.shape
+    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
     dev = mag_t.device
-    if not 9 <= Cw <= 1025 or (Cw - 1) & (Cw - 2):
-        raise ValueError('%s: C - 1 must be a power of two in [8, 1024], got C = %d' % (who, Cw))
-    if F > STRETCH_MAX_FRAMES:
-        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
-    if frames is not None and (not torch.is_tensor(frames) or tuple(frames.shape) != (B,) or frames.dtype != torch.int32
-                               or frames.device != dev or not frames.is_contiguous()):
-        raise ValueError('%s: frames must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
-    if isinstance(frames_per_unit, bool) or int(frames_per_unit) != frames_per_unit or int(frames_per_unit) < 1:
-        raise ValueError('%s: frames_per_unit must be an integer >= 1, got %r' % (who, frames_per_unit))
-    qmax = min(PITCH_MAX_LIFTER, (Cw - 1) // 2)
-    if isinstance(lifter, bool) or int(lifter) != lifter or not 1 <= int(lifter) <= qmax:
-        raise ValueError('%s: lifter must be an integer in [1, %d] at C = %d, got %r' % (who, qmax, Cw, lifter))
-    if step_q is None:
-        pass
-    elif torch.is_tensor(step_q) and step_q.device.type != 'cpu':
-        if tuple(step_q.shape) != (B,) or step_q.dtype != torch.int32 or step_q.device != dev or not step_q.is_contiguous():
-            raise ValueError('%s: step_q on a device must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
-    else:
-        one = not torch.is_tensor(step_q) and not hasattr(step_q, '__len__')
-        host = _host_int32([step_q] * B if one else step_q, B, who + ': step_q')
-        if min(host) < PITCH_MIN_STEP or max(host) > PITCH_MAX_STEP:
-            raise ValueError('%s: step_q must be in [%d, %d] (+12 to -12 semitones), got %r'
-                             % (who, PITCH_MIN_STEP, PITCH_MAX_STEP, step_q if one else host))
-        step_q = torch.tensor(host, dtype=torch.int32).to(dev)
+    pow2_bins(who, Cw)
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, 1, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
+    step_q, _ = step_q_arg(who, step_q, B, dev, PITCH_MIN_STEP, PITCH_MAX_STEP, '+12 to -12 semitones')
     out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
-    m0, o0, nbytes = mag_t.data_ptr(), out.data_ptr(), B * Cw * F * 4
-    if o0 < m0 + nbytes and m0 < o0 + nbytes:
-        raise ValueError('%s: out may not overlap mag_t' % who)
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
-    _check(_lib.taco_frames_pitch(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(step_q), int(lifter), ptr(out), B, Cw, F,
-                                  stream_ptr()), 'taco_frames_pitch')
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_pitch(ptr(mag_t), ptr(frames), frames_per_unit, ptr(step_q), lifter, ptr(out), B, Cw, F, stream_ptr()),
+           'taco_frames_pitch')
     return out
 
 
@@ -640,8 +585,7 @@ def f0_tables(sr=16000, fmin=60.0, fmax=400.0, deemphasis=0.97, C=1025, win_leng
     ValueError when the lags do not fit C or the cap of 512, or the window does not cover lag_max + 1."""
     lag_min, lag_max = f0_lags(sr, fmin, fmax)
     C, win_length, a = int(C), int(win_length), float(deemphasis)
-    if not 9 <= C <= 1025 or (C - 1) & (C - 2):
-        raise ValueError('f0_tables: C - 1 must be a power of two in [8, 1024], got C = %d' % C)
+    pow2_bins('f0_tables', C)
     if not 0.0 <= a < 1.0:
         raise ValueError('f0_tables: deemphasis must be in [0, 1), got %r' % (deemphasis,))
     L = lag_max - lag_min + 3
@@ -660,26 +604,15 @@ def f0_tables(sr=16000, fmin=60.0, fmax=400.0, deemphasis=0.97, C=1025, win_leng
     return weight.astype(np.float32), (wa[0] / wa[lags]).astype(np.float32), lag_min, lag_max
 
 
-def _f0_table(x, n, dev, what):
+def _f0_table(who, name, x, n, dev):
     """None, a (n) float32 tensor on `dev`, or host numbers (uploaded) -> None or the device tensor; ValueError"""
-    if x is None:
-        return None
-    if torch.is_tensor(x) and x.device.type != 'cpu':
-        if tuple(x.shape) != (n,) or x.dtype != torch.float32 or x.device != dev or not x.is_contiguous():
-            raise ValueError('%s on a device must be a contiguous float32 tensor of shape (%d,) on %s' % (what, n, dev))
+    if x is None or (torch.is_tensor(x) and x.device.type != 'cpu'):
+        tensor_arg(who, name + ' on a device', x, torch.float32, (n,), dev, optional=True)
         return x
     host = np.asarray(x.numpy() if torch.is_tensor(x) else x, dtype=np.float32)
     if host.shape != (n,):
-        raise ValueError('%s must hold %d numbers, got shape %s' % (what, n, host.shape))
+        raise ValueError('%s: %s must hold %d numbers, got shape %s' % (who, name, n, host.shape))
     return torch.from_numpy(np.ascontiguousarray(host)).to(dev)
-
-
-def _f0_frames_arg(who, frames, frames_per_unit, B, dev):
-    if frames is not None and (not torch.is_tensor(frames) or tuple(frames.shape) != (B,) or frames.dtype != torch.int32
-                               or frames.device != dev or not frames.is_contiguous()):
-        raise ValueError('%s: frames must be a contiguous int32 tensor of shape (%d,) on %s' % (who, B, dev))
-    if isinstance(frames_per_unit, bool) or int(frames_per_unit) != frames_per_unit or int(frames_per_unit) < 1:
-        raise ValueError('%s: frames_per_unit must be an integer >= 1, got %r' % (who, frames_per_unit))
 
 
 def frames_f0(mag_t, frames=None, frames_per_unit=1, weight=None, gain=None, lag_min=40, lag_max=266, ratio=F0_RATIO,
@@ -695,22 +628,12 @@ def frames_f0(mag_t, frames=None, frames_per_unit=1, weight=None, gain=None, lag
     ratio 0.9 and threshold 0.3 are UNTUNED defaults.  out: the caller's own (period, strength) or (period, strength, acf); default:
     fresh ones.  Enqueued on the current stream; nothing is read back and nothing waits."""
     who = 'frames_f0'
-    if not torch.is_tensor(mag_t) or mag_t.dim() != 3 or mag_t.dtype != torch.float32 or min(mag_t.shape) < 1:
-        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, C, F), got %s %s'
-                         % (who, getattr(mag_t, 'dtype', type(mag_t)), tuple(getattr(mag_t, 'shape', ()))))
-    if not mag_t.is_contiguous():
-        raise ValueError('%s: mag_t must be contiguous' % who)
-    B, Cw, F = mag_t.shape
+    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
     dev = mag_t.device
-    if not 9 <= Cw <= 1025 or (Cw - 1) & (Cw - 2):
-        raise ValueError('%s: C - 1 must be a power of two in [8, 1024], got C = %d' % (who, Cw))
-    if F > STRETCH_MAX_FRAMES:
-        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
-    _f0_frames_arg(who, frames, frames_per_unit, B, dev)
-    for name, v in (('lag_min', lag_min), ('lag_max', lag_max)):
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError('%s: %s must be an integer, got %r' % (who, name, v))
-    lag_min, lag_max = int(lag_min), int(lag_max)
+    pow2_bins(who, Cw)
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    lag_min, lag_max = int_arg(who, 'lag_min', lag_min), int_arg(who, 'lag_max', lag_max)
     L = lag_max - lag_min + 3
     if not 2 <= lag_min <= lag_max <= Cw - 2 or L > F0_MAX_LAGS:
         raise ValueError('%s: need 2 <= lag_min <= lag_max <= %d at C = %d and at most %d lags with their neighbours, got lag_min = %d, '
@@ -720,20 +643,17 @@ def frames_f0(mag_t, frames=None, frames_per_unit=1, weight=None, gain=None, lag
         raise ValueError('%s: ratio must be in (0, 1], got %r' % (who, ratio))
     if threshold != threshold:
         raise ValueError('%s: threshold is NaN' % who)
-    weight = _f0_table(weight, Cw, dev, who + ': weight')
-    gain = _f0_table(gain, L, dev, who + ': gain')
+    weight = _f0_table(who, 'weight', weight, Cw, dev)
+    gain = _f0_table(who, 'gain', gain, L, dev)
     if out is not None and len(out) != (3 if want_acf else 2):
         raise ValueError('%s: out must be (period, strength%s)' % (who, ', acf' if want_acf else ''))
     period = _own_or_given(None if out is None else out[0], (B, F), torch.float32, dev, who + ': period')
     strength = _own_or_given(None if out is None else out[1], (B, F), torch.float32, dev, who + ': strength')
     acf = _own_or_given(None if out is None else out[2], (B, L, F), torch.float32, dev, who + ': acf') if want_acf else None
-    m0, nbytes = mag_t.data_ptr(), B * Cw * F * 4
     for name, t in (('period', period), ('strength', strength), ('acf', acf)):
-        if t is not None and t.data_ptr() < m0 + nbytes and m0 < t.data_ptr() + t.numel() * 4:
-            raise ValueError('%s: %s may not overlap mag_t' % (who, name))
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: mag_t must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
-    _check(_lib.taco_frames_f0(ptr(mag_t), ptr(frames), int(frames_per_unit), ptr(weight), ptr(gain), lag_min, lag_max, ratio, threshold,
+        no_overlap(who, 'mag_t', mag_t, name, t)
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_f0(ptr(mag_t), ptr(frames), frames_per_unit, ptr(weight), ptr(gain), lag_min, lag_max, ratio, threshold,
                                ptr(period), ptr(strength), ptr(acf), B, Cw, F, stream_ptr()), 'taco_frames_f0')
     return (period, strength, acf) if want_acf else (period, strength)
 
@@ -744,23 +664,14 @@ def f0_stats(period, other=None, frames=None, frames_per_unit=1, out=None):
     F_b.  other (B, F): the statistics of log2(other) - log2(period) over the frames voiced in both: the octaves by which `period`
     is higher in pitch than `other` (12 x the mean: semitones).  Nothing is read back."""
     who = 'f0_stats'
-    if not torch.is_tensor(period) or period.dim() != 2 or period.dtype != torch.float32 or min(period.shape) < 1:
-        raise ValueError('%s: period must be a float32 tensor of shape (B, F), got %s %s'
-                         % (who, getattr(period, 'dtype', type(period)), tuple(getattr(period, 'shape', ()))))
-    if not period.is_contiguous():
-        raise ValueError('%s: period must be contiguous' % who)
-    B, F = period.shape
+    B, F = tensor_arg(who, 'period', period, torch.float32, ('B', 'F'))
     dev = period.device
-    if F > STRETCH_MAX_FRAMES:
-        raise ValueError('%s: at most %d frames, got F = %d' % (who, STRETCH_MAX_FRAMES, F))
-    if other is not None and (not torch.is_tensor(other) or tuple(other.shape) != (B, F) or other.dtype != torch.float32
-                              or other.device != dev or not other.is_contiguous()):
-        raise ValueError('%s: other must be a contiguous float32 tensor of shape (%d, %d) on %s' % (who, B, F, dev))
-    _f0_frames_arg(who, frames, frames_per_unit, B, dev)
+    _frames_cap(who, F)
+    tensor_arg(who, 'other', other, torch.float32, (B, F), dev, optional=True)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
     out = _own_or_given(out, (B, 3), torch.float32, dev, who + ': out')
-    if dev.type != 'cuda':
-        raise ValueError('%s: period must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
-    _check(_lib.taco_f0_stats(ptr(period), ptr(other), ptr(frames), int(frames_per_unit), ptr(out), B, F, stream_ptr()), 'taco_f0_stats')
+    on_gpu(who, 'period', dev)
+    _check(_lib.taco_f0_stats(ptr(period), ptr(other), ptr(frames), frames_per_unit, ptr(out), B, F, stream_ptr()), 'taco_f0_stats')
     return out
 
 
@@ -784,11 +695,8 @@ def dct_basis(C=80, first=1, count=13):
 
 
 def _frames_arg(who, name, x):
-    if not torch.is_tensor(x) or x.dim() != 3 or x.dtype != torch.float32 or min(x.shape) < 1:
-        raise ValueError('%s: %s must be a float32 tensor of shape (B, F, C), got %s %s'
-                         % (who, name, getattr(x, 'dtype', type(x)), tuple(getattr(x, 'shape', ()))))
-    if not x.is_contiguous():
-        raise ValueError('%s: %s must be contiguous' % (who, name))
+    """chronological frames (B, F, C) fp32 -> (B, F, C)"""
+    return tensor_arg(who, name, x, torch.float32, ('B', 'F', 'C'))
 
 
 def frames_active(x, floor, n=None):
@@ -796,37 +704,26 @@ def frames_active(x, floor, n=None):
     n (B) int32 on the device, 1 + the last frame with an element above `floor` (0: none; a NaN is not above anything).  Enqueued on
     the current stream; nothing is copied and nothing waits.  n: the caller's own buffer; default: a fresh one."""
     who = 'frames_active'
-    _frames_arg(who, 'x', x)
+    B, F, Cw = _frames_arg(who, 'x', x)
     floor = float(floor)
     if floor != floor:
         raise ValueError('%s: floor is NaN' % who)
-    B, F, Cw = x.shape
     n = _own_or_given(n, (B,), torch.int32, x.device, who + ': n')
-    if x.device.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: x must be on the GPU, got %s (there is no CPU fallback)' % (who, x.device))
+    on_gpu(who, 'x', x.device)
     _check(_lib.taco_frames_active(ptr(x), floor, ptr(n), B, F, Cw, stream_ptr()), 'taco_frames_active')
     return n
 
 
 def _dtw_args(who, a, b, na, nb, basis, cost, steps):
     """the argument checks frame_dtw and frame_dtw_path share -> (B, Fa, Fb, C, K, device, cost, steps)"""
-    _frames_arg(who, 'a', a)
-    _frames_arg(who, 'b', b)
-    B, Fa, Cw = a.shape
+    B, Fa, Cw = _frames_arg(who, 'a', a)
     dev = a.device
-    if b.shape[0] != B or b.shape[2] != Cw or b.device != dev:
-        raise ValueError('%s: b must have shape (%d, Fb, %d) on %s, got %s on %s' % (who, B, Cw, dev, tuple(b.shape), b.device))
-    Fb = b.shape[1]
+    Fb, = tensor_arg(who, 'b', b, torch.float32, (B, 'Fb', Cw), dev)
     if max(Fa, Fb) > DTW_MAX_FRAMES or Cw > DTW_MAX_C:
         raise ValueError('%s: at most %d frames of %d channels, got Fa = %d, Fb = %d, C = %d' % (who, DTW_MAX_FRAMES, DTW_MAX_C, Fa, Fb, Cw))
-    for name, t in (('na', na), ('nb', nb)):
-        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != torch.int32 or t.device != dev
-                              or not t.is_contiguous()):
-            raise ValueError('%s: %s must be a contiguous int32 tensor of shape (%d,) on %s' % (who, name, B, dev))
-    if basis is not None and (not torch.is_tensor(basis) or basis.dim() != 2 or basis.shape[1] != Cw or basis.shape[0] < 1
-                              or basis.dtype != torch.float32 or basis.device != dev or not basis.is_contiguous()):
-        raise ValueError('%s: basis must be a contiguous float32 tensor of shape (K, %d) on %s' % (who, Cw, dev))
-    K = Cw if basis is None else basis.shape[0]
+    tensor_arg(who, 'na', na, torch.int32, (B,), dev, optional=True)
+    tensor_arg(who, 'nb', nb, torch.int32, (B,), dev, optional=True)
+    K = Cw if basis is None else tensor_arg(who, 'basis', basis, torch.float32, ('K', Cw), dev)[0]
     if K > DTW_MAX_K:
         raise ValueError('%s: at most %d coefficients per frame, got %d%s'
                          % (who, DTW_MAX_K, K, ' (no basis: the channels themselves)' if basis is None else ''))
@@ -848,8 +745,7 @@ def frame_dtw(a, b, na=None, nb=None, basis=None, cost=None, steps=None, work=No
     frame_dtw_workspace_bytes(B, Fa, Fb, K) bytes); default: fresh ones."""
     who = 'frame_dtw'
     B, Fa, Fb, Cw, K, dev, cost, steps = _dtw_args(who, a, b, na, nb, basis, cost, steps)
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    on_gpu(who, 'a', dev)
     nbytes = frame_dtw_workspace_bytes(B, Fa, Fb, K)
     work = _own_or_given(work, (nbytes,), torch.uint8, dev, who + ': work')
     _check(_lib.taco_frame_dtw(ptr(a), ptr(na), ptr(b), ptr(nb), ptr(basis), ptr(cost), ptr(steps), ptr(work) if nbytes else None,
@@ -872,8 +768,7 @@ def frame_dtw_path(a, b, na=None, nb=None, basis=None, cost=None, steps=None, pa
     P = Fa + Fb - 1
     path_a = _own_or_given(path_a, (B, P), torch.int32, dev, who + ': path_a')
     path_b = _own_or_given(path_b, (B, P), torch.int32, dev, who + ': path_b')
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    on_gpu(who, 'a', dev)
     work = _own_or_given(work, (frame_dtw_path_workspace_bytes(B, Fa, Fb, K),), torch.uint8, dev, who + ': work')
     _check(_lib.taco_frame_dtw_path(ptr(a), ptr(na), ptr(b), ptr(nb), ptr(basis), ptr(cost), ptr(steps), ptr(path_a), ptr(path_b),
                                     ptr(work), B, Fa, Fb, Cw, K, stream_ptr()), 'taco_frame_dtw_path')
@@ -890,30 +785,20 @@ def path_f0_scores(period_a, period_b, path_a, path_b, steps, gross=1.2, counts=
     log2(period_b) - log2(period_a) over the cells voiced in both -- the octaves by which a lies above b; x 1200: cents).  A cell is a
     gross error when one period is more than `gross` times the other.  Nothing is read back."""
     who = 'path_f0_scores'
-    if not torch.is_tensor(period_a) or period_a.dim() != 2 or period_a.dtype != torch.float32 or min(period_a.shape) < 1:
-        raise ValueError('%s: period_a must be a float32 tensor of shape (B, Fa), got %s %s'
-                         % (who, getattr(period_a, 'dtype', type(period_a)), tuple(getattr(period_a, 'shape', ()))))
-    B, Fa = period_a.shape
+    B, Fa = tensor_arg(who, 'period_a', period_a, torch.float32, ('B', 'Fa'))
     dev = period_a.device
-    if not torch.is_tensor(period_b) or period_b.dim() != 2 or period_b.shape[0] != B or period_b.shape[1] < 1 \
-            or period_b.dtype != torch.float32 or period_b.device != dev:
-        raise ValueError('%s: period_b must be a float32 tensor of shape (%d, Fb) on %s' % (who, B, dev))
-    Fb = period_b.shape[1]
+    Fb, = tensor_arg(who, 'period_b', period_b, torch.float32, (B, 'Fb'), dev)
     if max(Fa, Fb) > DTW_MAX_FRAMES:
         raise ValueError('%s: at most %d frames, got Fa = %d, Fb = %d' % (who, DTW_MAX_FRAMES, Fa, Fb))
-    if not period_a.is_contiguous() or not period_b.is_contiguous():
-        raise ValueError('%s: period_a and period_b must be contiguous' % who)
     P = Fa + Fb - 1
     for name, t, shape in (('path_a', path_a, (B, P)), ('path_b', path_b, (B, P)), ('steps', steps, (B,))):
-        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-            raise ValueError('%s: %s must be a contiguous int32 tensor of shape %s on %s' % (who, name, shape, dev))
+        tensor_arg(who, name, t, torch.int32, shape, dev)
     gross = float(gross)
     if not gross > 1.0 or not C.c_float(gross).value > 1.0:   # (NaN fails)
         raise ValueError('%s: gross must be above 1 (as a float32 too), got %r' % (who, gross))
     counts = _own_or_given(counts, (B, 5), torch.int32, dev, who + ': counts')
     means = _own_or_given(means, (B, 2), torch.float32, dev, who + ': means')
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: period_a must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    on_gpu(who, 'period_a', dev)
     _check(_lib.taco_path_f0_scores(ptr(period_a), ptr(period_b), ptr(path_a), ptr(path_b), ptr(steps), gross, ptr(counts), ptr(means),
                                     B, Fa, Fb, stream_ptr()), 'taco_path_f0_scores')
     return counts, means
@@ -935,30 +820,17 @@ def corpus_batch_width(src_addr, out_addr, row, fp16) -> int:
 def _corpus_batch_args(src, mean, std, index, n_bad):
     """The argument check of corpus_batch -> (N, row, C, B, device); ValueError before any library call."""
     who = 'corpus_batch'
-    if src.dtype not in (torch.float16, torch.float32):
-        raise ValueError('%s: src must be float16 or float32, got %s' % (who, src.dtype))
-    if src.dim() != 3 or min(src.shape) < 1:
-        raise ValueError('%s: src must have shape (N, Td, C), got %s' % (who, tuple(src.shape)))
-    if not src.is_contiguous():
-        raise ValueError('%s: src must be contiguous' % who)
-    N, Td, Cw = src.shape
+    N, Td, Cw = tensor_arg(who, 'src', src, (torch.float16, torch.float32), ('N', 'Td', 'C'))
     dev = src.device
     if (mean is None) != (std is None):
         raise ValueError('%s: mean and std must both be given or both be None' % who)
-    for name, t in (('mean', mean), ('std', std)):
-        if t is not None and (tuple(t.shape) != (Cw,) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
-            raise ValueError('%s: %s must be a contiguous float32 tensor of shape (%d,) on %s, got %s %s on %s'
-                             % (who, name, Cw, dev, t.dtype, tuple(t.shape), t.device))
-    if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != dev or not index.is_contiguous()):
-        raise ValueError('%s: index must be a contiguous int64 tensor of shape (B,) on %s, got %s %s on %s'
-                         % (who, dev, index.dtype, tuple(index.shape), index.device))
-    if index is not None and index.numel() < 1:
-        raise ValueError('%s: index is empty' % who)
-    if n_bad is not None and (n_bad.numel() != 1 or n_bad.dtype != torch.int32 or n_bad.device != dev):
-        raise ValueError('%s: n_bad must be one int32 on %s' % (who, dev))
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: src must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
-    return N, Td * Cw, Cw, (N if index is None else index.numel()), dev
+    tensor_arg(who, 'mean', mean, torch.float32, (Cw,), dev, optional=True)
+    tensor_arg(who, 'std', std, torch.float32, (Cw,), dev, optional=True)
+    B = N if index is None else tensor_arg(who, 'index', index, torch.int64, ('B',), dev)[0]
+    if n_bad is not None and (not torch.is_tensor(n_bad) or n_bad.numel() != 1 or n_bad.dtype != torch.int32 or n_bad.device != dev):
+        raise ValueError('%s: n_bad must be one int32 on %s' % (who, dev))   # (of any shape: (), (1,), (1, 1))
+    on_gpu(who, 'src', dev)
+    return N, Td * Cw, Cw, B, dev
 
 
 def corpus_batch(src, mean, std, index=None, out=None, n_bad=None):
@@ -976,17 +848,10 @@ def corpus_batch(src, mean, std, index=None, out=None, n_bad=None):
 
 def _griffinlim_args(who, mag_t, frames, phase0, frames_per_unit, n_iter, need_frames=False, need_phase0=False):
     """The argument check of the three Griffin-Lim wrappers -> (B, F, device, frames_per_unit, n_iter); ValueError names `who`."""
-    if mag_t.dim() != 3 or mag_t.shape[1] != 1025 or mag_t.dtype != torch.float32:
-        raise ValueError('%s: mag_t must be a float32 tensor of shape (B, 1025, F), got %s %s' % (who, mag_t.dtype, tuple(mag_t.shape)))
-    B, _, F = mag_t.shape
+    B, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 1025, 'F'), empty_ok=True)   # (B >= 1, F >= 5: the size functions refuse)
     dev = mag_t.device
-    if (frames is None and need_frames) or (
-            frames is not None and (tuple(frames.shape) != (B,) or frames.dtype != torch.int32 or frames.device != dev)):
-        raise ValueError('%s: frames must be an int32 tensor of shape (%d,) on %s, got %s'
-                         % (who, B, dev, frames if frames is None else '%s %s on %s' % (frames.dtype, tuple(frames.shape), frames.device)))
-    if (phase0 is None and need_phase0) or (
-            phase0 is not None and (phase0.shape != mag_t.shape or phase0.dtype != torch.float32 or phase0.device != dev)):
-        raise ValueError('%s: phase0 must be a float32 tensor of shape %s on %s' % (who, tuple(mag_t.shape), dev))
+    tensor_arg(who, 'frames', frames, torch.int32, (B,), dev, optional=not need_frames)
+    tensor_arg(who, 'phase0', phase0, torch.float32, (B, 1025, F), dev, optional=not need_phase0)
     if int(frames_per_unit) < 1 or int(n_iter) < 0:
         raise ValueError('%s: frames_per_unit >= 1 and n_iter >= 0, got %d and %d' % (who, frames_per_unit, n_iter))
     return B, F, dev, int(frames_per_unit), int(n_iter)
@@ -1058,15 +923,9 @@ def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=T
     and pcm = write_wav's PCM16 of it, zeros behind.  samples (B) int32 on the device, or None: every row has L samples.
     deemphasis in [0, 1); trim_top_db >= 0.  out / pcm / bounds / peak / work: the caller's own buffers (work:
     wave_finish_workspace_floats(B, L) floats); default: fresh ones.  An out / pcm buffer implies want_out / want_pcm."""
-    if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[0] < 1 or wave.shape[1] < 1:
-        raise ValueError('wave_finish: wave must be a float32 tensor of shape (B, L), got %s %s' % (wave.dtype, tuple(wave.shape)))
-    if not wave.is_contiguous():
-        raise ValueError('wave_finish: wave must be contiguous')
-    B, L = wave.shape
+    B, L = tensor_arg('wave_finish', 'wave', wave, torch.float32, ('B', 'L'))
     dev = wave.device
-    if samples is not None and (tuple(samples.shape) != (B,) or samples.dtype != torch.int32 or samples.device != dev):
-        raise ValueError('wave_finish: samples must be an int32 tensor of shape (%d,) on %s, got %s %s on %s'
-                         % (B, dev, samples.dtype, tuple(samples.shape), samples.device))
+    tensor_arg('wave_finish', 'samples', samples, torch.int32, (B,), dev, optional=True)
     deemphasis, trim_top_db = _unit_interval(deemphasis, 'wave_finish: deemphasis'), float(trim_top_db)
     if not trim_top_db >= 0.0:
         raise ValueError('wave_finish: trim_top_db must be >= 0, got %r' % trim_top_db)
@@ -1088,28 +947,6 @@ def wave_finish(wave, samples=None, deemphasis=0.97, trim_top_db=0.0, want_out=T
 
 def wave_join_workspace_bytes(N, P, Lj) -> int:
     return _size('taco_wave_join_workspace_bytes', N, P, Lj)
-
-
-def _host_int32(x, n, what):
-    """a host sequence of n integers that fit int32 -> a list of ints, or ValueError"""
-    if torch.is_tensor(x):
-        if x.device.type != 'cpu' or x.dtype.is_floating_point or x.dtype == torch.bool:
-            raise ValueError('%s must be integers in host memory, got a %s tensor on %s' % (what, x.dtype, x.device))
-        x = x.tolist()
-    try:
-        x = list(x)
-    except TypeError:
-        raise ValueError('%s must be a sequence of %d integers, got %r' % (what, n, x)) from None
-    if len(x) != n:
-        raise ValueError('%s must hold %d integers, got %d' % (what, n, len(x)))
-    for v in x:
-        try:
-            ok = not isinstance(v, bool) and int(v) == v and -(1 << 31) <= int(v) < (1 << 31)
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError('%s must hold integers that fit int32, got %r' % (what, v))
-    return [int(v) for v in x]
 
 
 def wave_join(pieces, bounds, first, gap, fade=0, Lj=None, want_out=True, want_pcm=True, out=None, pcm=None, offsets=None, total=None,
@@ -1134,9 +971,7 @@ def wave_join(pieces, bounds, first, gap, fade=0, Lj=None, want_out=True, want_p
     pitch = pieces.stride(0) if N > 1 else max(pieces.stride(0), L)
     if pitch < L:
         raise ValueError('%s: the rows of pieces are %d floats apart, fewer than L = %d' % (who, pitch, L))
-    if (not torch.is_tensor(bounds) or tuple(bounds.shape) != (N, 2) or bounds.dtype != torch.int32 or bounds.device != dev
-            or not bounds.is_contiguous()):
-        raise ValueError('%s: bounds must be a contiguous int32 tensor of shape (%d, 2) on %s' % (who, N, dev))
+    tensor_arg(who, 'bounds', bounds, torch.int32, (N, 2), dev)
     try:
         P = len(first) - 1
     except TypeError:
@@ -1151,9 +986,7 @@ def wave_join(pieces, bounds, first, gap, fade=0, Lj=None, want_out=True, want_p
         raise ValueError('%s: first must not decrease, got %r' % (who, first))
     if min(gap) < 0:
         raise ValueError('%s: gap must be >= 0, got %d' % (who, min(gap)))
-    if isinstance(fade, bool) or int(fade) != fade or int(fade) < 0:
-        raise ValueError('%s: fade must be an integer >= 0, got %r' % (who, fade))
-    fade = int(fade)
+    fade = int_arg(who, 'fade', fade, 0)
     want_out = bool(want_out) or out is not None
     want_pcm = bool(want_pcm) or pcm is not None
     if not (want_out or want_pcm):
@@ -1161,21 +994,15 @@ def wave_join(pieces, bounds, first, gap, fade=0, Lj=None, want_out=True, want_p
     if Lj is None:
         worst = max((first[p + 1] - first[p]) * L + sum(gap[first[p]:first[p + 1] - 1]) for p in range(P))
         Lj = max(8, -(-worst // 8) * 8)
-    if isinstance(Lj, bool) or int(Lj) != Lj or not 1 <= int(Lj) < (1 << 31):
-        raise ValueError('%s: Lj must be an integer in [1, 2^31), got %r' % (who, Lj))
-    Lj = int(Lj)
+    Lj = int_arg(who, 'Lj', Lj, 1, _INT_MAX)
     out = _own_or_given(out, (P, Lj), torch.float32, dev, who + ': out') if want_out else None
-    if out is not None:
-        p0, o0 = pieces.data_ptr(), out.data_ptr()
-        if o0 < p0 + ((N - 1) * pitch + L) * 4 and p0 < o0 + P * Lj * 4:
-            raise ValueError('%s: out may not overlap pieces' % who)
+    no_overlap(who, 'pieces', pieces, 'out', out, span_in=((N - 1) * pitch + L) * 4)
     pcm = _own_or_given(pcm, (P, Lj), torch.int16, dev, who + ': pcm') if want_pcm else None
     offsets = _own_or_given(offsets, (N,), torch.int32, dev, who + ': offsets')
     total = _own_or_given(total, (P,), torch.int32, dev, who + ': total')
     peak = _own_or_given(peak, (P,), torch.float32, dev, who + ': peak')
     work = _own_or_given(work, (wave_join_workspace_bytes(N, P, Lj),), torch.uint8, dev, who + ': work')
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: pieces must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    on_gpu(who, 'pieces', dev)
     _check(_lib.taco_wave_join(C.c_void_p(pieces.data_ptr()), pitch, ptr(bounds), (C.c_int32 * (P + 1))(*first), (C.c_int32 * N)(*gap),
                                fade, ptr(out), ptr(pcm), ptr(offsets), ptr(total), ptr(peak), ptr(work), N, P, L, Lj, stream_ptr()),
            'taco_wave_join')
@@ -1191,6 +1018,8 @@ def audio_features(wave, wave_len, mel_basis, r, max_len=108000, out_dtype=torch
     ints, mel_basis (80, 1025) fp32 on the device -> (mel (B, Td, 80 r), stft (B, Td, 1025 r), kept (B) int32, bounds (B, 2) int32),
     device tensors; out_dtype float16 or float32.  out: the caller's own (mel, stft, kept, bounds) buffers, work: the caller's
     own workspace (uint8, audio_features_workspace_bytes(B, L) bytes); default: fresh ones."""
+    if not torch.is_tensor(wave):
+        raise ValueError('audio_features: wave must be a tensor of shape (B, L), got %s' % type(wave))
     B, L = wave.shape
     if len(wave_len) != B:
         raise ValueError('audio_features: %d lengths for %d waves' % (len(wave_len), B))
@@ -1221,32 +1050,19 @@ def wave_resample(pcm, rows, taps, width, channels, P, Q, n_left, n_right, L=Non
     P == Q: decode-only) -> wave (B, L) float32: row b holds its n_calc_b resampled samples (P == Q: its decoded frames), zeros behind.
     L: the width of a fresh result; out: the caller's own (B, L) buffer instead."""
     who = 'wave_resample'
-    if pcm.dim() != 2 or pcm.dtype != torch.uint8 or pcm.shape[0] < 1 or pcm.shape[1] < 1 or not pcm.is_contiguous():
-        raise ValueError('%s: pcm must be a contiguous uint8 tensor of shape (B, row_bytes), got %s %s' % (who, pcm.dtype, tuple(pcm.shape)))
-    B, row_bytes = pcm.shape
+    B, row_bytes = tensor_arg(who, 'pcm', pcm, torch.uint8, ('B', 'row_bytes'))
     dev = pcm.device
     if B > 65535:
         raise ValueError('%s: at most 65535 rows per call, got %d' % (who, B))
-    ints = dict(width=width, channels=channels, P=P, Q=Q, n_left=n_left, n_right=n_right)
-    for name, v in ints.items():
-        if isinstance(v, bool) or int(v) != v:
-            raise ValueError('%s: %s must be an integer, got %r' % (who, name, v))
-    width, channels, P, Q, n_left, n_right = (int(ints[k]) for k in ('width', 'channels', 'P', 'Q', 'n_left', 'n_right'))
-    if not (1 <= width <= 4 and 1 <= channels <= 8):
-        raise ValueError('%s: width must be in 1..4 and channels in 1..8, got %d and %d' % (who, width, channels))
-    if min(P, Q, n_left, n_right) < 1:
-        raise ValueError('%s: P, Q, n_left and n_right must be >= 1, got %d, %d, %d, %d' % (who, P, Q, n_left, n_right))
+    width, channels = int_arg(who, 'width', width, 1, 4), int_arg(who, 'channels', channels, 1, 8)
+    P, Q = int_arg(who, 'P', P, 1), int_arg(who, 'Q', Q, 1)
+    n_left, n_right = int_arg(who, 'n_left', n_left, 1), int_arg(who, 'n_right', n_right, 1)
     if row_bytes % (width * channels):
         raise ValueError('%s: row_bytes %d is not a multiple of width * channels = %d' % (who, row_bytes, width * channels))
-    if tuple(rows.shape) != (B, 2) or rows.dtype != torch.int32 or rows.device != dev or not rows.is_contiguous():
-        raise ValueError('%s: rows must be a contiguous int32 tensor of shape (%d, 2) on %s, got %s %s on %s'
-                         % (who, B, dev, rows.dtype, tuple(rows.shape), rows.device))
+    tensor_arg(who, 'rows', rows, torch.int32, (B, 2), dev)
     if taps is None and P != Q:
         raise ValueError('%s: taps may be None only when P == Q (decode-only), got P = %d, Q = %d' % (who, P, Q))
-    if taps is not None and (tuple(taps.shape) != (Q, n_left + n_right) or taps.dtype != torch.float32 or taps.device != dev
-                             or not taps.is_contiguous()):
-        raise ValueError('%s: taps must be a contiguous float32 tensor of shape (%d, %d) on %s, got %s %s on %s'
-                         % (who, Q, n_left + n_right, dev, taps.dtype, tuple(taps.shape), taps.device))
+    tensor_arg(who, 'taps', taps, torch.float32, (Q, n_left + n_right), dev, optional=True)
     if P != Q:   # the library's own rule: the frames one tile reads must fit 64 KiB of LDS
         span = (WAVE_RESAMPLE_TILE - 1) * P // Q + 1 + n_left + n_right
         if (-(-span // P) * P + n_left + n_right if Q == 1 else span) * 4 > 64 * 1024:
@@ -1254,15 +1070,8 @@ def wave_resample(pcm, rows, taps, width, channels, P, Q, n_left, n_right, L=Non
                              % (who, P, Q, n_left + n_right, span))
     if (L is None) == (out is None):
         raise ValueError('%s: give exactly one of L and out' % who)
-    if out is None and (isinstance(L, bool) or int(L) != L or int(L) < 1):
-        raise ValueError('%s: L must be a positive integer, got %r' % (who, L))
-    if out is not None and (out.dim() != 2 or out.shape[0] != B or out.shape[1] < 1):
-        raise ValueError('%s: out must have shape (%d, L), got %s' % (who, B, tuple(out.shape)))
-    L = int(L) if out is None else out.shape[1]
-    if out is not None:
-        _own_or_given(out, (B, L), torch.float32, dev, who + ': out')
-    if dev.type != 'cuda':   # (last: the checks above are the same for tensors of any device)
-        raise ValueError('%s: pcm must be on the GPU, got %s (there is no CPU fallback)' % (who, dev))
+    L = int_arg(who, 'L', L, 1) if out is None else tensor_arg(who, 'out', out, torch.float32, (B, 'L'), dev)[0]
+    on_gpu(who, 'pcm', dev)
     wave = _own_or_given(out, (B, L), torch.float32, dev, who + ': out')
     _check(_lib.taco_wave_resample(ptr(pcm), row_bytes, width, channels, ptr(rows), ptr(taps), P, Q, n_left, n_right, ptr(wave), B, L,
                                    stream_ptr()), 'taco_wave_resample')

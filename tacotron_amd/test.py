@@ -114,28 +114,25 @@ def long_options(long):
     return pause_ms, fade_ms
 
 
+def _steps(name, values, to_step, n):
+    """lib.steps_of for an option of test(), a single number repeated for every prompt; ValueError names the option"""
+    try:
+        steps = lib.steps_of(values, to_step, n)
+    except ValueError as e:
+        raise ValueError('%s (--%s): %s' % (name, name, e)) from None
+    return [steps] * (1 if n is None else n) if isinstance(steps, int) else steps
+
+
 def rate_steps(rate, n):
     """`rate` of test(): None, a number or a sequence of n numbers in [0.25, 4] -> None or the n step_q values (lib.stretch_step);
     ValueError"""
-    if rate is None:
-        return None
-    if hasattr(rate, '__len__'):
-        if n is not None and len(rate) != n:
-            raise ValueError('rate (--rate): %d rates for %d prompts' % (len(rate), n))
-        return [lib.stretch_step(x) for x in rate]
-    return [lib.stretch_step(rate)] * (1 if n is None else n)
+    return _steps('rate', rate, lib.stretch_step, n)
 
 
 def pitch_steps(pitch, n):
     """`pitch` of test(): None, a number or a sequence of n numbers of semitones in [-12, 12] -> None or the n step_q values
     (lib.pitch_step); ValueError"""
-    if pitch is None:
-        return None
-    if hasattr(pitch, '__len__'):
-        if n is not None and len(pitch) != n:
-            raise ValueError('pitch (--pitch): %d pitches for %d prompts' % (len(pitch), n))
-        return [lib.pitch_step(x) for x in pitch]
-    return [lib.pitch_step(pitch)] * (1 if n is None else n)
+    return _steps('pitch', pitch, lib.pitch_step, n)
 
 
 def f0_range(f0):
@@ -175,19 +172,12 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
     if pitch is not None:
         if not vocode:
             raise ValueError('pitch (--pitch) shifts the magnitudes in front of Griffin-Lim: it needs vocode')
-        try:
-            pitch_steps(pitch, None)
-        except ValueError as e:
-            raise ValueError('pitch (--pitch): %s' % e) from None
-        if isinstance(lifter, bool) or int(lifter) != lifter or not 1 <= int(lifter) <= lib.PITCH_MAX_LIFTER:
-            raise ValueError('lifter (--lifter) must be an integer in [1, %d], got %r' % (lib.PITCH_MAX_LIFTER, lifter))
+        pitch_steps(pitch, None)
+        lib.int_arg('check_options', 'lifter (--lifter)', lifter, 1, lib.PITCH_MAX_LIFTER)
     if rate is not None:
         if not vocode:
             raise ValueError('rate (--rate) stretches the magnitudes in front of Griffin-Lim: it needs vocode')
-        try:
-            rate_steps(rate, None)
-        except ValueError as e:
-            raise ValueError('rate (--rate): %s' % e) from None
+        rate_steps(rate, None)
     if long_options(long) is not None and not stop:
         raise ValueError('long (--long) needs a stop rule (--stop): without one every piece carries max_decode_iter steps')
     if vocode_lengths and not stop:
