@@ -65,15 +65,30 @@ class Recorder:
     Names: 'encoder/emb', 'encoder/pre_net/{l1,l2}pre', '<cbhg prefix>{in,pool,proj1pre,proj1}' (proj1 = after its ReLU and
     BN: the proj2 input), 'decoder/keys', 'decoder/values', 'seq2seq_output', and per step t '@t' names:
     'decoder/pre_net/{l1,l2}pre', 'decoder/x', 'decoder/gru_<l>/{gates,candidate}' (pre-activations), 'decoder/o'
-    (cell_output), 'decoder/q', 'decoder/ctx'."""
+    (cell_output), 'decoder/q', 'decoder/ctx'.
 
-    def __init__(self):
+    values=True (tests/test_gpu_forward_stages.py): `val[name]` also holds the FORWARD value (detached, fp64, numpy) of every
+    site above and of the value-only sites, which take no part in the gradient bookkeeping: per step 'decoder/gru_<l>/{r,u,c,
+    rh,h}@t' (rh = r * h_prev, h the new state), 'decoder/y@t' (x + h3, the out-proj input), 'decoder/pre_net/{l1,l2}@t' (after
+    ReLU and dropout), 'decoder/alignments@t'; 'encoder/pre_net/{l1,l2}'; per CBHG 'bank' (after its ReLU), 'proj1act' (after
+    its ReLU, before its BN), 'proj2pre' / 'proj2' (before / after its BN), 'res', 'highway_<l>/{in,T,H,out}' (in = after the
+    adapter where there is one), 'highway_<l>/spk' and 'gru_init' (speaker vectors), 'out' and 'bigru/{fw,bw}/{r,u,c}'
+    (B, T, 128); 'speaker_embed', 'output'.  Works under torch.no_grad().  Reading a value changes no bit of anything."""
+
+    def __init__(self, values=False):
         self.t, self.acc, self.grad = {}, {}, {}
+        self.values, self.val = values, {}
 
     def keep(self, name, x):
         if x.requires_grad:
             x.retain_grad()
             self.t[name] = x
+        return self.value(name, x)
+
+    def value(self, name, x):
+        """A value-only site: kept when values=True, otherwise nothing happens."""
+        if self.values:
+            self.val[name] = x.detach().to(torch.float64).numpy().copy()
         return x
 
     def accumulate(self, name, x, fn):
@@ -95,6 +110,10 @@ class Recorder:
 
 def _keep(rec, name, x):
     return x if rec is None else rec.keep(name, x)
+
+
+def _val(rec, name, x):
+    return x if rec is None else rec.value(name, x)
 
 
 def _relu(dec, name, x):
@@ -122,61 +141,84 @@ def _maxpool(x):
     return F.max_pool1d(xt, 2, 1).transpose(1, 2)
 
 
-def _gru(x, h, wg, bg, wc, bc, rec=None, name='{}'):
+def _gru(x, h, wg, bg, wc, bc, rec=None, name='{}', ruc=None):
+    """name: the step's site names ('...{}@t'), or None for none; ruc: a list that receives this step's (r, u, c)."""
     H = h.shape[-1]
-    g = torch.sigmoid(_keep(rec, name.format('gates'), torch.addmm(bg, torch.cat([x, h], 1), wg)))
+    named = rec is not None and name is not None
+    g = torch.addmm(bg, torch.cat([x, h], 1), wg)
+    g = torch.sigmoid(_keep(rec, name.format('gates'), g) if named else g)
     r, u = g.split(H, 1)
-    c = torch.tanh(_keep(rec, name.format('candidate'), torch.addmm(bc, torch.cat([x, r * h], 1), wc)))
-    return u * h + (1 - u) * c
+    rh = r * h
+    c = torch.addmm(bc, torch.cat([x, rh], 1), wc)
+    c = torch.tanh(_keep(rec, name.format('candidate'), c) if named else c)
+    hn = u * h + (1 - u) * c
+    if named:
+        for k, v in (('r', r), ('u', u), ('c', c), ('rh', rh), ('h', hn)):
+            rec.value(name.format(k), v)
+    if ruc is not None:
+        ruc.append((r, u, c))
+    return hn
 
 
-def _bigru(x, p, prefix, h0=None):
+def _bigru(x, p, prefix, h0=None, rec=None):
     B, T, _ = x.shape
     H = p[prefix + 'fw/gates/bias'].shape[0] // 2
     outs = []
+    values = rec is not None and rec.values
     for name, order in (('fw', range(T)), ('bw', range(T - 1, -1, -1))):
         wg, bg = p[prefix + name + '/gates/kernel'], p[prefix + name + '/gates/bias']
         wc, bc = p[prefix + name + '/candidate/kernel'], p[prefix + name + '/candidate/bias']
         h = x.new_zeros(B, H) if h0 is None else h0
         seq = [None] * T
+        ruc = [None] * T if values else None
         for t in order:
-            h = _gru(x[:, t], h, wg, bg, wc, bc)
+            step = [] if values else None
+            h = _gru(x[:, t], h, wg, bg, wc, bc, None, None, step)
             seq[t] = h
+            if values:
+                ruc[t] = step[0]
         outs.append(torch.stack(seq, 1))
+        if values:
+            for i, k in enumerate('ruc'):
+                rec.value(prefix + name + '/' + k, torch.stack([s[i] for s in ruc], 1))
     return torch.cat(outs, 2)
 
 
-def _highway(x, p, prefix, dec=None):
+def _highway(x, p, prefix, dec=None, rec=None):
     if (prefix + 'adapt/kernel') in p:
         x = F.linear(x, p[prefix + 'adapt/kernel'].t(), p[prefix + 'adapt/bias'])
-    t = torch.sigmoid(F.linear(x, p[prefix + 'T/kernel'].t(), p[prefix + 'T/bias']))
+    _val(rec, prefix + 'in', x)
+    t = _val(rec, prefix + 'T', torch.sigmoid(F.linear(x, p[prefix + 'T/kernel'].t(), p[prefix + 'T/bias'])))
     h = _relu(dec, prefix + 'H', F.linear(x, p[prefix + 'H/kernel'].t(), p[prefix + 'H/bias']))
-    return h * t + x * (1 - t)
+    _val(rec, prefix + 'H', h)
+    return _val(rec, prefix + 'out', h * t + x * (1 - t))
 
 
 def cbhg(x, p, prefix, K, spk=None, dec=None, rec=None):
     x = _keep(rec, prefix + 'in', x)
     bank = torch.cat([_conv_same(x, p[prefix + 'bank_%d/kernel' % k], p[prefix + 'bank_%d/bias' % k])
                       for k in range(1, K + 1)], 2)
-    bank = _relu(dec, prefix + 'bank', bank)
+    bank = _val(rec, prefix + 'bank', _relu(dec, prefix + 'bank', bank))
     z = _bn(bank, p[prefix + 'bank_bn/gamma'], p[prefix + 'bank_bn/beta'])
     y = _keep(rec, prefix + 'pool', _maxpool(z) if dec is None else dec.pool2(prefix + 'pool', z))
     y = _keep(rec, prefix + 'proj1pre', _conv_same(y, p[prefix + 'proj1/kernel'], p[prefix + 'proj1/bias']))
-    y = _bn(_relu(dec, prefix + 'proj1', y), p[prefix + 'proj1_bn/gamma'], p[prefix + 'proj1_bn/beta'])
+    y = _bn(_val(rec, prefix + 'proj1act', _relu(dec, prefix + 'proj1', y)), p[prefix + 'proj1_bn/gamma'], p[prefix + 'proj1_bn/beta'])
     y = _keep(rec, prefix + 'proj1', y)
-    y = _conv_same(y, p[prefix + 'proj2/kernel'], p[prefix + 'proj2/bias'])
-    y = _bn(y, p[prefix + 'proj2_bn/gamma'], p[prefix + 'proj2_bn/beta'])
-    h = y + x
+    y = _val(rec, prefix + 'proj2pre', _conv_same(y, p[prefix + 'proj2/kernel'], p[prefix + 'proj2/bias']))
+    y = _val(rec, prefix + 'proj2', _bn(y, p[prefix + 'proj2_bn/gamma'], p[prefix + 'proj2_bn/beta']))
+    h = _val(rec, prefix + 'res', y + x)
     for l in range(4):
         hp = prefix + 'highway_%d/' % l
         if spk is not None:   # ops.py:101-105
             sv = _relu(dec, hp + 'spk', F.linear(spk, p[hp + 'spk/kernel'].t(), p[hp + 'spk/bias']))
+            _val(rec, hp + 'spk', sv)
             h = torch.cat([h, sv[:, None, :].expand(-1, h.shape[1], -1)], 2)
-        h = _highway(h, p, hp, dec)
+        h = _highway(h, p, hp, dec, rec)
     h0 = None
     if spk is not None:       # ops.py:111-115
         h0 = _relu(dec, prefix + 'gru_init', F.linear(spk, p[prefix + 'gru_init/kernel'].t(), p[prefix + 'gru_init/bias']))
-    return _bigru(h, p, prefix + 'bigru/', h0)
+        _val(rec, prefix + 'gru_init', h0)
+    return _val(rec, prefix + 'out', _bigru(h, p, prefix + 'bigru/', h0, rec))
 
 
 def _prenet(x, p, prefix, k1, k2, dec=None, tag='', rec=None):
@@ -184,24 +226,27 @@ def _prenet(x, p, prefix, k1, k2, dec=None, tag='', rec=None):
     l1 = _relu(dec, prefix + 'l1' + tag, l1)
     if k1 is not None:
         l1 = l1 * (2.0 * k1)
+    _val(rec, prefix + 'l1' + tag, l1)
     l2 = _keep(rec, prefix + 'l2pre' + tag, F.linear(l1, p[prefix + 'dense_1/kernel'].t(), p[prefix + 'dense_1/bias']))
     l2 = _relu(dec, prefix + 'l2' + tag, l2)
     if k2 is not None:
         l2 = l2 * (2.0 * k2)
-    return l2
+    return _val(rec, prefix + 'l2' + tag, l2)
 
 
 def forward(p, inputs, r, n_steps, train, masks=None, dec=None, rec=None):
     """p: dict name->tensor; inputs: dict of tensors (text int64, text_length int64, mel, stft);
     masks: dict of float tensors (0/1); dec: optional Decisions (record / force the ReLU and max-pool decisions; the decoder
     pre_net sites are named per step: 'decoder/pre_net/l1@<t>'); rec: optional Recorder (named intermediates whose gradients
-    the backward pass leaves in it).  Returns (seq2seq_output, output, alignments, encoded)."""
+    the backward pass leaves in it and, with values=True, whose forward values it holds).  Returns (seq2seq_output, output, alignments, encoded)."""
     masks = masks or {}
     g = (lambda k: masks.get(k)) if train else (lambda k: None)
     text = inputs['text']
     B, Tt = text.shape
     emb = _keep(rec, 'encoder/emb', F.embedding(text, p['embedding']))
     spk = F.embedding(inputs['speaker'], p['speaker_embed']) if ('speaker' in inputs and 'speaker_embed' in p) else None
+    if spk is not None:
+        _val(rec, 'speaker_embed', spk)
     enc = cbhg(_prenet(emb, p, 'encoder/pre_net/', g('enc_keep1'), g('enc_keep2'), dec, rec=rec), p, 'encoder/cbhg/', 16, spk, dec,
                rec)
 
@@ -229,14 +274,15 @@ def forward(p, inputs, r, n_steps, train, masks=None, dec=None, rec=None):
                         p['decoder/gru_%d/candidate/kernel' % l], p['decoder/gru_%d/candidate/bias' % l], rec,
                         'decoder/gru_%d/{}@%d' % (l, t))
             inp = h[l]
-        o = _keep(rec, 'decoder/o@%d' % t, F.linear(x + h[2], p['decoder/out_proj/kernel'].t(), p['decoder/out_proj/bias']))
+        y = _val(rec, 'decoder/y@%d' % t, x + h[2])
+        o = _keep(rec, 'decoder/o@%d' % t, F.linear(y, p['decoder/out_proj/kernel'].t(), p['decoder/out_proj/bias']))
         q = _keep(rec, 'decoder/q@%d' % t, torch.mm(o, p['decoder/query_layer/kernel']))
         e = torch.tanh(keys + q[:, None, :])
         score = e.matmul(v)
         if rec is not None:   # d v = sum over (b, t, s) of d score * e: keep the sum over (t, s) per row b
             rec.accumulate('decoder/attention_v@row', score, lambda gs, e=e: torch.einsum('bs,bsk->bk', gs, e.detach()))
         score = score.masked_fill(~valid, float('-inf'))
-        a = torch.softmax(score, 1)
+        a = _val(rec, 'decoder/alignments@%d' % t, torch.softmax(score, 1))
         ctx = _keep(rec, 'decoder/ctx@%d' % t, torch.bmm(a[:, None, :], values)[:, 0])
         if rec is not None:   # ctx = a . values: d values += a^T d ctx
             rec.accumulate('decoder/values@ctx', ctx, lambda gc, a=a: torch.einsum('bs,bk->bsk', a.detach(), gc))
@@ -252,7 +298,7 @@ def forward(p, inputs, r, n_steps, train, masks=None, dec=None, rec=None):
     s2s = _keep(rec, 'seq2seq_output', torch.stack(outs, 1))
     al = torch.stack(aligns, 1)
     post = cbhg(s2s.reshape(B, n_steps * r, nmel), p, 'post/cbhg/', 8, None, dec, rec)
-    out = F.linear(post, p['post/dense/kernel'].t(), p['post/dense/bias']).reshape(B, n_steps, -1)
+    out = _val(rec, 'output', F.linear(post, p['post/dense/kernel'].t(), p['post/dense/bias']).reshape(B, n_steps, -1))
     return s2s, out, al, enc
 
 

@@ -5,6 +5,9 @@ import numpy as np
 import torch
 
 K_ST_P1, K_ST_P2 = 0, 256   # csrc/kernels.h: pre-net slots of the decoder stash record
+# ... and the rest of the record (kSt* of csrc/kernels.h; tests/forward_map.py checks the record width against the workspace table)
+K_ST_X, K_ST_H, K_ST_R, K_ST_U, K_ST_C, K_ST_RH = 384, 640, 1408, 2176, 2944, 3712
+K_ST_CTX, K_ST_ATT, K_ST_Q, K_ST_Y, K_ST_REC = 4480, 4736, 4992, 5248, 5504
 
 
 def _pool_decisions(bank, pool, gamma, beta, B, T):

@@ -245,6 +245,38 @@ def test_recorder_changes_nothing():
     assert G['decoder/keys'].shape == (4, 37, 256) and G['post/cbhg/pool'].shape == (4, 2 * Td, 1024)
 
 
+def test_value_recorder_changes_nothing():
+    """Recorder(values=True): outputs, parameter gradients and every recorded gradient are bit-identical to the gradient-only
+    recorder's; the values are the graph's own (x + h3 = y, u h_prev + (1 - u) c = h, the last step's outputs) and are also
+    kept under no_grad, where nothing requires a gradient."""
+    p, inp, masks, r, Td = _recorded_case()
+    rec0, rec1 = ot.Recorder(), ot.Recorder(values=True)
+    plain = ot.loss_and_grads(p, inp, r, Td, masks, rec=rec0)
+    got = ot.loss_and_grads(p, inp, r, Td, masks, rec=rec1)
+    assert got[0] == plain[0] and not rec0.val
+    for a, b in zip(got[1:4], plain[1:4]):
+        assert np.array_equal(a, b)
+    for k, g in plain[4].items():
+        assert np.array_equal(got[4][k], g), k
+    assert set(rec0.grad) == set(rec1.grad)
+    for k, g in rec0.grad.items():
+        assert (g is None and rec1.grad[k] is None) or np.array_equal(rec1.grad[k], g), k
+    V = rec1.val
+    assert all(v.dtype == np.float64 for v in V.values())
+    assert np.array_equal(np.stack([V['decoder/o@%d' % t] for t in range(Td)], 1), got[1]) and np.array_equal(V['output'], got[2])
+    t = Td - 2
+    assert np.array_equal(V['decoder/y@%d' % t], V['decoder/x@%d' % t] + V['decoder/gru_2/h@%d' % t])
+    u, c, h0 = V['decoder/gru_1/u@%d' % t], V['decoder/gru_1/c@%d' % t], V['decoder/gru_1/h@%d' % (t - 1)]
+    assert np.array_equal(V['decoder/gru_1/h@%d' % t], u * h0 + (1 - u) * c)
+    assert np.array_equal(V['decoder/gru_1/rh@%d' % t], V['decoder/gru_1/r@%d' % t] * h0)
+    assert V['post/cbhg/bigru/bw/c'].shape == (4, 2 * Td, 128) and V['encoder/cbhg/highway_3/T'].shape == (4, 37, 128)
+    from tests.forward_map import oracle_forward
+    W, _ = oracle_forward(p, inp, masks, r, Td)
+    assert set(W) == set(V)
+    for k in V:
+        assert np.array_equal(W[k], V[k]), k
+
+
 def test_recorder_per_row_attention_v_and_context_part():
     """The per-row attention_v contributions sum to the parameter's gradient; the context part of d values plus the keys
     part (d keys Wm^T) is the whole gradient of the values."""
