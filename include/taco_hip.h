@@ -212,6 +212,44 @@ int taco_infer_stop(const TacoShape* shape, const float* params, const int32_t* 
 int taco_alignment_scores(const float* alignments, const int32_t* text_length, const int32_t* steps, int max_jump,
                           int32_t* counts, float* means, int B, int Td, int Tt, void* stream);
 
+/* Alignment path: per utterance, the best MONOTONE path through the attention matrix -- which character each decoder step speaks,
+ * and from it how many steps each character lasts.  taco_alignment_scores' argmax walk may go back and skip; a timing cannot be
+ * read off it.  No counterpart in the reference.
+ *   alignments, text_length, steps: exactly as taco_alignment_scores takes them (steps on the DEVICE, or NULL)
+ *   1 <= max_jump <= TACO_ALIGN_PATH_MAX_JUMP: how many characters a step may advance
+ *   path (B, Td) int32, dur (B, Tt) int32, counts (B, 3) int32, mass (B) fp32: all required, every element of each is written
+ *   workspace: taco_alignment_path_workspace_bytes(B, Td, Tt) bytes, arbitrary contents (NULL allowed when that is 0)
+ * For row b:  L = clamp(text_length[b], 1, Tt);  n = Td when steps is NULL, else clamp(steps[b], 0, Td);  J = max_jump.  The
+ * criterion is the attention MASS on the path, not its log-probability: a sum of fp32 values, one addition per cell, so a NumPy
+ * float32 restatement gives the same bits, and the exactly-zero rows behind a stop need no floor.
+ *   1. weights       w(t, s) = a[t, s] if a[t, s] > 0, else +0 (NaN, negative values and -0 give +0)
+ *   2. start         the path starts on character 0:  Q(0, 0) = w(0, 0)
+ *   3. reachability  cell (t, s) is reachable iff s <= min(L - 1, J t)
+ *   4. recurrence    for a reachable cell with t >= 1 the predecessor is (t-1, s-d), d the SMALLEST d in 0 .. min(J, s) at which
+ *                    Q(t-1, s-d) is largest among the reachable candidates;  Q(t, s) = w(t, s) + Q(t-1, s-d), one fp32 addition
+ *                    rounded to nearest even
+ *   5. end           free: e = the lowest s at which Q(n-1, s) is largest;  mass[b] = Q(n-1, e)
+ *   6. path          path[b, n-1] = e,  path[b, t-1] = path[b, t] - d(t, path[b, t]);  path[b, t] = -1 for t >= n
+ *   7. durations     dur[b, s] = #{t < n : path[b, t] == s} for every s < Tt (0 for skipped characters, for s > e and for s >= L)
+ *   8. counts        counts[b] = { n, e, skipped = #{s <= e : dur[b, s] == 0} }
+ *   9. empty row     n == 0: path all -1, dur all 0, counts {0, 0, 0}, mass +0
+ * Defined for every input, +inf included (no NaN arises from sums of non-negative values).  Steps t >= n, characters s >= L and
+ * every other row's data have no influence on row b; the same arguments give the same bits.
+ * One launch of B workgroups: no allocation, no host synchronisation, no workgroup waits for another one; graph-capturable.
+ * Nothing outside path / dur / counts / mass / workspace is written; alignments needs the alignment of a float only.  The
+ * workspace holds the direction table (a byte per cell) of the shapes whose table does not fit LDS; it is 0 bytes for Tt <= 256
+ * at the decoder lengths the product uses.  Any of the five required pointers NULL, a NULL workspace where one is needed, B, Td
+ * or Tt <= 0, Td > TACO_ALIGN_PATH_MAX_TD, Tt > TACO_ALIGN_PATH_MAX_TT or max_jump outside 1 .. TACO_ALIGN_PATH_MAX_JUMP return
+ * TACO_EINVAL before anything is enqueued; the size function returns TACO_EINVAL for the same shapes.  TACO_VERSION did not
+ * change with these entry points: detect them by the symbol. */
+#define TACO_ALIGN_PATH_MAX_TD   16384
+#define TACO_ALIGN_PATH_MAX_TT   4096
+#define TACO_ALIGN_PATH_MAX_JUMP 15
+int64_t taco_alignment_path_workspace_bytes(int B, int Td, int Tt);
+int taco_alignment_path(const float* alignments, const int32_t* text_length, const int32_t* steps, int max_jump,
+                        int32_t* path, int32_t* dur, int32_t* counts, float* mass, void* workspace,
+                        int B, int Td, int Tt, void* stream);
+
 /* ---- held-out evaluation: frame distance over a dynamic-time-warping path ------------------------------------------------- */
 /* Frames in use: x (B, F, C) chronological frames (taco_denorm_unframe's spec).  n[b] = 1 + the last f with x[b, f, c] > floor for
  * some c, and 0 when there is none; a NaN compares false.  The corpus pads every recording with frames of exactly log(1e-8) and

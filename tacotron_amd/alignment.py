@@ -1,6 +1,11 @@
 """Host side of the alignment monitor: what the per-utterance scores of lib.alignment_scores say about a row (`flags`) and the
 attention picture of the reference (data_input.generate_attention_plot, drawn by train.py:92-103 and test.py:60-69) as a PNG
-without axes (`attention_png`).  NumPy, zlib and struct only: a picture of Td x Tt cells is host work, the scores are not."""
+without axes (`attention_png`).  NumPy, zlib and struct only: a picture of Td x Tt cells is host work, the scores are not.
+
+Timings (`char_steps`, `step_samples`, `word_times`): the arithmetic that turns the per-character durations of lib.alignment_path
+into seconds of the file a prompt was written to.  RESOLUTION: the r-frame layout (audio.reshape_frames) interleaves the frames of
+the 4 decoder steps of a block, so a boundary is exact at multiples of 4 steps and nominal (frame r t) inside a block: the blur is
+up to one block, 4 r frames = 150 ms at r = 2 and 16 kHz.  Good enough for subtitles; this is not a phonetic aligner."""
 from __future__ import annotations
 
 import struct
@@ -10,6 +15,7 @@ import numpy as np
 
 from .lib import ALIGN_COUNTS, ALIGN_MEANS
 
+HOP, SR = 300, 16000   # samples per frame and per second (audio.py)
 FLAGS = ('unfinished', 'skips', 'goes back', 'on padding', 'diffuse')
 
 # matplotlib's `hot` map: (x, y) break points of its three piecewise-linear channels
@@ -102,3 +108,77 @@ def attention_png(path, align, n=None, zoom=4):
         f.write(b'\x89PNG\r\n\x1a\n' + _chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0))
                 + _chunk(b'IDAT', zlib.compress(raw, 6)) + _chunk(b'IEND', b''))
     return h, w
+
+
+# ---- timings: durations in decoder steps -> seconds of the written file -----------------------------------------------------------
+def char_steps(dur):
+    """dur (L,) steps per character (lib.alignment_path) -> (start, end): character s is spoken over the steps start[s] .. end[s] - 1;
+    cumulative sums, so a skipped character (dur 0) has start == end, the step at which its neighbours meet"""
+    d = np.asarray(dur, dtype=np.int64).reshape(-1)
+    if (d < 0).any():
+        raise ValueError('char_steps: durations must be >= 0, got %s' % (d[d < 0][:4],))
+    end = np.cumsum(d)
+    return end - d, end
+
+
+def step_samples(t, r, step_q=None, trim=None, offset=0, total=None):
+    """Decoder step(s) t -> sample position(s) in the written file, float64.  Step t sits at source frame r t and at sample 300 r t;
+    with a rate (step_q: the Q16 step of lib.frames_stretch, 65536 the model's own) the frame becomes r t 65536 / step_q.  trim = (s, e)
+    of a finished waveform (prompt_NNN_trim.npy): s is subtracted and the result clipped to [0, e - s]; without finishing the result is
+    clipped to [0, total], total the 300 (frames - 1) samples the file holds (None: unclipped).  offset: where the piece starts in a
+    joined file (--long), added last.  Nominal inside a block of 4 steps: see the module's note on resolution."""
+    frame = np.asarray(t, dtype=np.float64) * int(r)
+    if step_q is not None:
+        frame = frame * 65536.0 / int(step_q)
+    x = frame * HOP
+    if trim is not None:
+        s, e = int(trim[0]), int(trim[1])
+        x = np.clip(x - s, 0, max(0, e - s))
+    elif total is not None:
+        x = np.clip(x, 0, max(0, int(total)))
+    return x + int(offset)
+
+
+def encoded_chars(line, ivocab):
+    """the characters of a raw line that data.load_prompts encodes, in order: those of line.strip() that the vocabulary holds"""
+    known = set(ivocab.values())
+    return [w for w in line.strip() if w in known]
+
+
+def word_times(line, ivocab, dur, r, step_q=None, trim=None, offset=0, total=None, sr=SR):
+    """[(start_s, end_s, word)] of one prompt (or one piece of a --long prompt): `dur` its per-character steps (lib.alignment_path; entry
+    i belongs to encoded character i -- text_length also counts the newline and the dropped characters, so dur may be longer than the
+    encoded text and the surplus is ignored; a shorter dur counts as 0 steps for the rest).  A word is a maximal run of encoded
+    non-space characters, punctuation attached; it starts with the first step of its first character and ends with the last step of
+    its last one (char_steps), mapped to seconds by step_samples(...) / sr.  A word whose characters were all skipped has start == end."""
+    chars = encoded_chars(line, ivocab)
+    d = np.zeros(len(chars), dtype=np.int64)
+    given = np.asarray(dur, dtype=np.int64).reshape(-1)[:len(chars)]
+    d[:len(given)] = given
+    start, end = char_steps(d)
+    out, i = [], 0
+    while i < len(chars):
+        if chars[i] == ' ':
+            i += 1
+            continue
+        j = i
+        while j + 1 < len(chars) and chars[j + 1] != ' ':
+            j += 1
+        a, b = step_samples([start[i], end[j]], r, step_q, trim, offset, total) / float(sr)
+        out.append((float(a), float(b), ''.join(chars[i:j + 1])))
+        i = j + 1
+    return out
+
+
+def words_tsv(rows):
+    """the text of prompt_NNN_words.tsv: start_s<TAB>end_s<TAB>word, milliseconds kept"""
+    return ''.join('%.3f\t%.3f\t%s\n' % row for row in rows)
+
+
+def path_line(who, counts, mass, L, end_offset=1):
+    """(the line --timings prints for one row, whether it is a WARNING): counts (3) and mass of lib.alignment_path, L the text length"""
+    n, end, skipped = (int(x) for x in np.asarray(counts).reshape(-1))
+    L = max(1, int(L))
+    short = end < L - 1 - int(end_offset)
+    text = '%s path: mass per step %.3f over %d steps, end %d of %d, %d skipped' % (who, float(mass) / n if n else 0.0, n, end, L - 1, skipped)
+    return ('WARNING ' + text + ': the path ends before the text does') if short else text, short

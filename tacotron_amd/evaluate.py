@@ -9,7 +9,7 @@ utterances of the corpus, the ones `train --holdout N` never draws,
       with frames of log(1e-8) and stores no length.
 Only cost, steps, na, nb and the three losses of each batch travel to the host.
 
-    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned]
+    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--durations]
 
 prints one line per batch and a final line with the mean teacher-forced loss and the mean and worst MCD, and writes
 eval_<step>.npy, one row per utterance: index, na, nb, steps, cost, mcd (float64; COLUMNS).
@@ -37,6 +37,16 @@ in cents over those cells, the voicing decision error (cells voiced in one track
 cells whose periods differ by more than a factor GROSS / both-voiced cells); a column is NaN where its denominator is 0.  One more
 line per batch and one final line give their means over the utterances.  --f0 alone prints and saves exactly what it did.
 
+--durations [--path-jump J] (opt-in): duration, the third of the usual prosody measures next to MCD and F0.  The best monotone path
+through the attention (Tacotron.alignment_path, taco_alignment_path; a step advances by at most J characters, default
+lib.PATH_JUMP = 4, untuned) gives every character a duration in decoder steps, twice: the PREDICTED one from the free-running
+alignments over free.lengths, and the RECORDED one from the teacher-forced alignments of forced.forward(None) over the recording's
+own steps, min(Td, 4 ceil(nb / (4 r))), formed on the device from nb.  Each row gains DUR_COLUMNS behind whatever the other options
+append: the mean absolute difference of the two durations per character in ms (a step is r frames of 300 samples), the bias
+(predicted longer: positive) in ms, and the attention mass per step on both paths.  One more line per batch and one final line give
+their means.  The other modes print and save exactly what they did.  On an untrained model the attention follows no text and the
+numbers mean nothing; and a boundary is exact at multiples of 4 steps only (alignment.py).
+
 The final batch is padded to the batch size by repeating its last utterance; the copies are left out of the per-utterance rows and
 of the MCD statistics.  The teacher-forced loss is one number per batch (and the CBHG's batch normalisation sees the whole batch),
 so the padded batch enters the mean loss weighted by its share of real rows.  Without a corpus on disk the synthetic pool of
@@ -59,6 +69,7 @@ from .train import latest_checkpoint, open_corpus
 COLUMNS = ('index', 'na', 'nb', 'steps', 'cost', 'mcd')
 F0_COLUMNS = ('f0_mean', 'f0_sd', 'voiced', 'rec_f0_mean', 'rec_f0_sd', 'rec_voiced')   # appended with --f0; the first two in log2 Hz
 ALIGNED_COLUMNS = ('path_voiced', 'f0_rmse_cents', 'f0_bias_cents', 'vuv_error', 'gross_error')   # appended with --f0-aligned
+DUR_COLUMNS = ('dur_mae_ms', 'dur_bias_ms', 'path_mass', 'rec_path_mass')   # appended with --durations (last)
 GROSS = 1.2  # a both-voiced cell is a gross pitch error when one period is above GROSS times the other (the usual 20 %)
 SR = 16000   # of a corpus whose meta.pkl records no 'sr', and of the synthetic pool
 PAD_FLOOR = float(np.float16(np.log(1e-8)))   # the value preprocess stores in the padding frames (fp16 of log(1e-8))
@@ -152,10 +163,36 @@ def aligned_summary(cols):
     return tuple(float(np.nanmean(cols[:, k])) if np.isfinite(cols[:, k]).any() else float('nan') for k in (1, 3, 4))
 
 
+def duration_columns(dur, rec_dur, text_length, counts, mass, rec_counts, rec_mass, step_ms):
+    """lib.alignment_path's dur (n, Tt), counts (n, 3) and mass (n) of the free-running and of the teacher-forced alignments, the n
+    text lengths and the milliseconds of a decoder step -> (n, 4) float64 in the order DUR_COLUMNS: mean |dur - rec_dur| and mean
+    (dur - rec_dur) over the utterance's characters, in ms, and mass / n of both paths (NaN for a path of 0 steps)"""
+    dur, rec_dur = np.asarray(dur, dtype=np.float64), np.asarray(rec_dur, dtype=np.float64)
+    L = np.clip(np.asarray(text_length, dtype=np.int64).reshape(-1), 1, dur.shape[1])
+    own = np.arange(dur.shape[1])[None, :] < L[:, None]
+    diff = np.where(own, dur - rec_dur, 0.0)
+    out = np.full((len(L), 4), np.nan)
+    out[:, 0] = np.abs(diff).sum(1) / L * float(step_ms)
+    out[:, 1] = diff.sum(1) / L * float(step_ms)
+    for k, (c, m) in enumerate(((counts, mass), (rec_counts, rec_mass))):
+        n = np.asarray(c, dtype=np.float64).reshape(-1, 3)[:, 0]
+        np.divide(np.asarray(m, dtype=np.float64).reshape(-1), n, out=out[:, 2 + k], where=n > 0)
+    return out
+
+
+def duration_summary(cols):
+    """(n, 4) in the order DUR_COLUMNS -> their means over the utterances that have one; NaN without any"""
+    cols = np.asarray(cols, dtype=np.float64).reshape(-1, 4)
+    return tuple(float(np.nanmean(cols[:, k])) if np.isfinite(cols[:, k]).any() else float('nan') for k in range(4))
+
+
+DUR_LINE = 'duration error %.0f ms per character (bias %+.0f ms), path mass per step %.3f free-running / %.3f teacher-forced'
+
+
 def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None,
-             f0=False, f0_aligned=False):
+             f0=False, f0_aligned=False, durations=False, path_jump=lib.PATH_JUMP):
     """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  f0: rows (n, 12), F0_COLUMNS behind
-    COLUMNS.  f0_aligned (implies f0): rows (n, 17), ALIGNED_COLUMNS behind those.  stop: the lib.TacoStopRule of the
+    COLUMNS.  f0_aligned (implies f0): rows (n, 17), ALIGNED_COLUMNS behind those.  durations: DUR_COLUMNS behind all of them (path_jump: the max_jump of the two paths).  stop: the lib.TacoStopRule of the
     free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
     ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection; with f0_aligned also the two period
     tracks 'period' and 'rec_period')."""
@@ -220,6 +257,10 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         smean, sstd = norm['stft'] if norm is not None and 'stft' in norm else (forced.stft_mean, forced.stft_std)
         smean = szeros if smean is None else torch.as_tensor(smean, dtype=torch.float32).to(dev)
         sstd = sones if sstd is None else torch.as_tensor(sstd, dtype=torch.float32).to(dev)
+    if durations:
+        path_jump = lib.int_arg('evaluate', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
+        per.update(dur=[])
+        step_ms = 1000.0 * r * 300 / sr
     losses = []
     for i, (index, valid) in enumerate(batches):
         if i:
@@ -251,6 +292,10 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
                 raise ValueError('evaluate --f0-aligned: the predicted pitch track is %d frames wide and the predicted mel frames %d: '
                                  'the path of one does not index the other' % (Fp, Fm))
             path_counts, path_means = lib.path_f0_scores(pred_period, rec_period, path_a, path_b, steps, GROSS)
+        if durations:   # the recording's own steps, on the device: its nb frames in blocks of 4 steps of r frames
+            rec_steps = torch.clamp((nb + (4 * r - 1)) // (4 * r) * 4, max=Td).to(torch.int32)
+            free_path = free.alignment_path(path_jump)
+            rec_path = forced.alignment_path(path_jump, steps=rec_steps)
         loss = forced._loss.cpu().numpy().astype(np.float64)       # the host synchronisation of the batch
         forced.check()
         free.check()
@@ -262,11 +307,21 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
                 got['path_counts'], got['path_means'] = path_counts.cpu().numpy(), path_means.cpu().numpy()
             cents, share = f0_summary(np.concatenate([f0_columns(got['f0'][:valid], got['f0_frames'][:valid], sr),
                                                       f0_columns(got['rec_f0'][:valid], got['nb'][:valid], sr)], axis=1))
+        if durations:
+            got['dur'] = duration_columns(free_path[1].cpu().numpy(), rec_path[1].cpu().numpy(), batch['text_length'].cpu().numpy(),
+                                          free_path[2].cpu().numpy(), free_path[3].cpu().numpy(), rec_path[2].cpu().numpy(),
+                                          rec_path[3].cpu().numpy(), step_ms)
+        if trace is not None and durations:
+            trace_dur = {'alignments': free.alignments.cpu().numpy(), 'lengths': free.lengths.cpu().numpy(),
+                         'rec_alignments': forced.alignments.cpu().numpy(), 'rec_steps': rec_steps.cpu().numpy(),
+                         'text_length': batch['text_length'].cpu().numpy()}
         if trace is not None:
             trace.append({'predicted': free.predicted_mel()[0].cpu().numpy(), 'recorded': recorded.cpu().numpy(), 'na': got['na'].copy(),
                           'nb': got['nb'].copy()})
             if f0_aligned:
                 trace[-1].update(period=pred_period.cpu().numpy(), rec_period=rec_period.cpu().numpy())
+            if durations:
+                trace[-1].update(trace_dur)
         for k, v in got.items():
             per[k].append(v)
         losses.append(loss)
@@ -279,6 +334,8 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         if f0_aligned:
             print('batch %d F0 RMSE %.0f cents, V/UV error %.3f, gross error %.3f along the warping path (aligned)'
                   % ((i,) + aligned_summary(aligned_columns(got['path_counts'][:valid], got['path_means'][:valid]))))
+        if durations:
+            print(('batch %d ' % i) + DUR_LINE % duration_summary(got['dur'][:valid]))
     feeder.close()
     rows = mcd_rows(unpad(batches, [b[0] for b in batches]), *(unpad(batches, per[k]) for k in ('na', 'nb', 'steps', 'cost')))
     if f0:
@@ -289,6 +346,9 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         rows = np.concatenate([rows, aligned_columns(unpad(batches, per['path_counts']), unpad(batches, per['path_means']))], axis=1)
         print('held out: F0 RMSE %.0f cents, V/UV error %.3f, gross error %.3f along the warping path (untuned tracker, aligned)'
               % aligned_summary(rows[:, 12:]))
+    if durations:
+        rows = np.concatenate([rows, unpad(batches, per['dur'])], axis=1)
+        print('held out: ' + DUR_LINE % duration_summary(rows[:, -4:]) + ' (untuned max_jump %d; meaningless on an untrained model)' % path_jump)
     weight = np.array([valid for _, valid in batches], dtype=np.float64)
     mean_loss = float((np.stack(losses)[:, 0] * weight).sum() / weight.sum())
     print('held out: %d utterances, teacher-forced loss %.1f, MCD-DTW mean %.3f dB worst %.3f dB (utterance %d) over %d cepstra of '
@@ -313,6 +373,11 @@ def parse_args(argv=None):
     ap.add_argument('--f0-aligned', action='store_true',
                     help='--f0, and the F0 error along the warping path: ALIGNED_COLUMNS (F0 RMSE and bias in cents, voicing decision '
                          'error, gross pitch error) behind F0_COLUMNS')
+    ap.add_argument('--durations', action='store_true',
+                    help='per-character durations from the best monotone attention path, free-running against teacher-forced: '
+                         'DUR_COLUMNS (mean absolute difference and bias in ms, path mass per step of both) behind the other columns')
+    ap.add_argument('--path-jump', type=int, default=lib.PATH_JUMP, metavar='J',
+                    help='--durations: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     return ap.parse_args(argv)
 
 
@@ -323,7 +388,8 @@ def main(argv=None, config=None):
     if config is None:
         c.data_path = 'data/%s/' % a.train_set
     checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
-    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0, f0_aligned=a.f0_aligned)
+    return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0, f0_aligned=a.f0_aligned, durations=a.durations,
+                    path_jump=a.path_jump)
 
 
 if __name__ == '__main__':

@@ -106,6 +106,8 @@ EXPORTS = {
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
     'taco_infer_stop': (C.c_int, [_SH, _P, _P, _P, _P, C.POINTER(TacoStopRule), _P, _P, _P, _P, _P, _P]),
     'taco_alignment_scores': (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    'taco_alignment_path_workspace_bytes': (C.c_int64, [_I, _I, _I]),
+    'taco_alignment_path': (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'taco_frames_active': (C.c_int, [_P, C.c_float, _P, _I, _I, _I, _P]),
     'taco_frame_dtw_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
     'taco_frame_dtw': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -340,6 +342,50 @@ def alignment_scores(alignments, text_length, steps=None, max_jump=MAX_JUMP, cou
     _check(_lib.taco_alignment_scores(ptr(alignments), ptr(text_length), ptr(steps), max_jump, ptr(counts), ptr(means), B, Td, Tt,
                                       stream_ptr()), 'taco_alignment_scores')
     return counts, means
+
+
+PATH_COUNTS = ('n', 'end', 'skipped')   # columns of counts (include/taco_hip.h taco_alignment_path)
+PATH_JUMP = 4                      # characters a decoder step may advance on the path; untuned -- at r = 5 a step covers more than
+                                   # one character of ordinary speech, so 1 is not usable
+PATH_MAX_TD, PATH_MAX_TT, PATH_MAX_JUMP = 16384, 4096, 15   # TACO_ALIGN_PATH_MAX_TD / _TT / _JUMP
+
+
+def _path_shape(who, B, Td, Tt):
+    if Td > PATH_MAX_TD or Tt > PATH_MAX_TT:
+        raise ValueError('%s: at most %d steps and %d characters, got Td = %d, Tt = %d' % (who, PATH_MAX_TD, PATH_MAX_TT, Td, Tt))
+    return int_arg(who, 'B', B, 1, _INT_MAX), int_arg(who, 'Td', Td, 1), int_arg(who, 'Tt', Tt, 1)
+
+
+def alignment_path_workspace_bytes(B, Td, Tt) -> int:
+    return _size('taco_alignment_path_workspace_bytes', *_path_shape('alignment_path_workspace_bytes', B, Td, Tt))
+
+
+def alignment_path(alignments, text_length, steps=None, max_jump=PATH_JUMP, path=None, dur=None, counts=None, mass=None, workspace=None):
+    """The best monotone path through each attention matrix (include/taco_hip.h taco_alignment_path): alignments (B, Td, Tt) fp32,
+    text_length (B) int32, steps (B) int32 or None -- the lengths of infer_stop; None walks all Td steps -- all on the device, max_jump
+    in 1 .. 15 the characters a step may advance -> (path (B, Td) int32: the character of every step, -1 from the row's length on;
+    dur (B, Tt) int32: the steps of every character; counts (B, 3) int32 in the order PATH_COUNTS; mass (B) fp32: the attention mass
+    on the path), device tensors.  workspace: uint8, alignment_path_workspace_bytes(B, Td, Tt) bytes (0 for the product's shapes).
+    Enqueued on the current stream; nothing is copied and nothing waits.  The outputs and workspace: the caller's own buffers;
+    default: fresh ones."""
+    who = 'alignment_path'
+    B, Td, Tt = tensor_arg(who, 'alignments', alignments, torch.float32, ('B', 'Td', 'Tt'))
+    dev = alignments.device
+    _path_shape(who, B, Td, Tt)
+    tensor_arg(who, 'text_length', text_length, torch.int32, (B,), dev)
+    tensor_arg(who, 'steps', steps, torch.int32, (B,), dev, optional=True)
+    max_jump = int_arg(who, 'max_jump', max_jump, 1, PATH_MAX_JUMP)
+    path = _own_or_given(path, (B, Td), torch.int32, dev, who + ': path')
+    dur = _own_or_given(dur, (B, Tt), torch.int32, dev, who + ': dur')
+    counts = _own_or_given(counts, (B, len(PATH_COUNTS)), torch.int32, dev, who + ': counts')
+    mass = _own_or_given(mass, (B,), torch.float32, dev, who + ': mass')
+    if workspace is not None:
+        tensor_arg(who, 'workspace', workspace, torch.uint8, ('bytes',), dev, empty_ok=True)
+    on_gpu(who, 'alignments', dev)
+    workspace = _own_or_given(workspace, (alignment_path_workspace_bytes(B, Td, Tt),), torch.uint8, dev, who + ': workspace')
+    _check(_lib.taco_alignment_path(ptr(alignments), ptr(text_length), ptr(steps), max_jump, ptr(path), ptr(dur), ptr(counts), ptr(mass),
+                                    ptr(workspace) if workspace.numel() else None, B, Td, Tt, stream_ptr()), 'taco_alignment_path')
+    return path, dur, counts, mass
 
 
 def clip_adam_step(params, grads, m, v, lr, cap, step, scratch, gnorm_out, err_words=None):

@@ -42,6 +42,7 @@ class Tacotron(object):
         self.lengths = None               # (B) int32 decoder steps kept per row after run(stop=...); None after run()
         self._lengths = None
         self._align_scores = None         # (counts, means) of alignment_scores(), allocated at its first call
+        self._align_path = None           # (path, dur, counts, mass, workspace) of alignment_path(), allocated at its first call
         self._mel_eval = None             # the tensors of predicted_mel() / mel_distortion(), allocated at their first call
         self.mel_mean = self.mel_std = None   # (80 r) statistics the corpus's mel targets were standardised with; None: identity
         self._loss = torch.zeros(3, device=dev)
@@ -255,6 +256,21 @@ class Tacotron(object):
                                   torch.empty(B, len(lib.ALIGN_MEANS), dtype=torch.float32, device=self.device))
         counts, means = self._align_scores
         return lib.alignment_scores(self.alignments, self.inputs['text_length'], self.lengths, max_jump, counts, means)
+
+    def alignment_path(self, max_jump=lib.PATH_JUMP, steps=None):
+        """The best monotone path through each row of `alignments` (lib.alignment_path): (path (B, Td) int32, dur (B, Tt) int32,
+        counts (B, 3) int32 in the order lib.PATH_COUNTS, mass (B) fp32).  After run(stop=...) each row's path runs over its own
+        `lengths` steps, otherwise over all Td; `steps` (B) int32 on the device overrides both.  One launch on the current stream into
+        tensors (and a workspace) the model allocates once and returns every time; no copy and no synchronisation."""
+        if self._align_path is None:
+            B, Td, Tt, dev = self.shape.B, self.shape.Td, self.shape.Tt, self.device
+            self._align_path = (torch.empty(B, Td, dtype=torch.int32, device=dev), torch.empty(B, Tt, dtype=torch.int32, device=dev),
+                                torch.empty(B, len(lib.PATH_COUNTS), dtype=torch.int32, device=dev),
+                                torch.empty(B, dtype=torch.float32, device=dev),
+                                torch.empty(lib.alignment_path_workspace_bytes(B, Td, Tt), dtype=torch.uint8, device=dev))
+        path, dur, counts, mass, work = self._align_path
+        return lib.alignment_path(self.alignments, self.inputs['text_length'], self.lengths if steps is None else steps, max_jump, path,
+                                  dur, counts, mass, work)
 
     # -- held-out evaluation ------------------------------------------------------------------------------
     def _mel_eval_tensors(self, cepstra):

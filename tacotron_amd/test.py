@@ -47,7 +47,17 @@ measured -- 12 x the mean over the frames voiced in both of log2(period unshifte
 those frames; with --rate alone the line gives the change of the mean log-F0 in cents, which should be near 0 (unpaired: the frame
 counts differ).  The pick's ratio 0.9 and threshold 0.3 are UNTUNED, and on an untrained model the frames have no pitch: the numbers
 then mean nothing.  It is the objective stand-in for listening to --pitch and --rate, which nobody has done.  It combines with every
-option above; with --long the files are per piece."""
+option above; with --long the files are per piece.
+--timings [--path-jump J] (opt-in, not in the reference): when each word is spoken.  The best monotone path through every prompt's
+attention is found on the device (Tacotron.alignment_path, taco_alignment_path; over each prompt's own steps with --stop; a step may
+advance by at most J characters, default lib.PATH_JUMP = 4, untuned) and only its durations, counts and mass come back with the other
+results.  prompt_NNN_dur.npy holds the steps of each of the prompt's text_length characters as int32 and prompt_NNN_words.tsv one
+`start_s<TAB>end_s<TAB>word` line per word of the written file (alignment.word_times: --rate, the trim of --deemphasis / --trim-db and,
+with --long, the piece's offset in the joined file are applied; with --long each piece of a prompt of several writes
+prompt_NNN_kMM_dur.npy and the prompt one _words.tsv).  One line per prompt gives the path's mass per step, its end against L - 1 and
+the skipped characters, as a WARNING when the path ends more than end_offset characters before the text does.  A boundary is exact at
+multiples of 4 decoder steps and nominal inside such a block (alignment.py): good for subtitles, not a phonetic aligner.  It combines
+with every option above; without it every file is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -60,7 +70,7 @@ import numpy as np
 import torch
 
 from .config import Config
-from .alignment import attention_png, flags, scores_row
+from .alignment import attention_png, flags, path_line, scores_row, word_times, words_tsv
 from .data import KIND_NAMES, load_prompts, split_prompt
 from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform
 from .model import Tacotron
@@ -163,8 +173,11 @@ def f0_lines(who, f0row, asked_step=None, rate_step=None):
 
 
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32, f0=None):
-    """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given); ValueError."""
+                  vocode=True, pitch=None, lifter=32, f0=None, path_jump=None):
+    """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
+    without --timings); ValueError."""
+    if path_jump is not None:
+        lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
     if f0 is not None and f0 is not False:
         if not vocode:
             raise ValueError('f0 (--f0) measures the magnitudes in front of Griffin-Lim: it needs vocode')
@@ -193,7 +206,7 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None, f0=None):
+                 rate=None, pitch=None, f0=None, dur=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -203,7 +216,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     samples, whatever len_b says.
     pitch (--pitch): (step_q, lifter) of the prompt, written as _pitch.npy; nothing else depends on it.
     f0 (--f0): the prompt's (frames, 2) float32 rows of (period, strength) over the frames the vocoder was given, already cut to them;
-    written as _f0.npy."""
+    written as _f0.npy.
+    dur (--timings): the steps of each of the prompt's characters, written as _dur.npy (int32)."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -219,6 +233,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_pitch.npy', np.asarray(pitch, dtype=np.int32))
     if f0 is not None:
         np.save(path + '_f0.npy', np.asarray(f0, dtype=np.float32))
+    if dur is not None:
+        np.save(path + '_dur.npy', np.asarray(dur, dtype=np.int32))
     np.save(path + '_spec.npy', spec)
     np.save(path + '_align.npy', align)
     if wav is not None:
@@ -235,7 +251,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
-         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None):
+         gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None,
+         timings=False, path_jump=lib.PATH_JUMP):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -277,8 +294,13 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     `f0` (needs `vocode`): None, True (60 .. 400 Hz) or (lo, hi) in Hz: invert_spectrogram(f0=...) tracks the pitch of the frames on the
     device, over the row's own len_b r frames with `stop`; prompt_NNN_f0.npy holds (period, strength) of the frames the vocoder was
     given, and f0_lines() prints what `pitch` or `rate` did to it.  Untuned, and meaningless on an untrained model; nothing else
-    changes."""
-    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0)
+    changes.
+    `timings` / `path_jump`: every batch's best monotone attention paths are found on the device (Tacotron.alignment_path with
+    max_jump = path_jump: over model.lengths with `stop`, else all steps); each prompt -- with `long`, each piece -- additionally
+    writes _dur.npy, each prompt _words.tsv (alignment.word_times of the file it wrote) and one line, a WARNING when the path ends
+    before the text does.  Nothing else changes."""
+    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
+                  path_jump=path_jump if timings else None)
     f0 = f0_range(f0)
     f0_opt = None   # the tables on the device, made at the first batch
     steps = rate_steps(rate, len(prompts))
@@ -304,7 +326,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     os.makedirs(out_dir, exist_ok=True)
 
     def synthesise(batch, n, out_rows=None, bounds_rows=None):
-        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res), host arrays or None.
+        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths), host arrays or
+        None.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
         out_rows / bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made.
         f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None)"""
         nonlocal f0_opt
@@ -324,6 +347,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             model.set_inputs(batch)
         out, al = model.run(stop=stop)
         scores = model.alignment_scores() if align_scores else None   # (enqueued behind the decode; read with the other results below)
+        paths = model.alignment_path(path_jump)[1:] if timings else None   # (likewise; the path itself stays on the device)
         model.check()
         mean = model.stft_mean if model.stft_mean is not None else torch.zeros(config.fft_size * config.r)
         std = model.stft_std if model.stft_std is not None else torch.ones(config.fft_size * config.r)
@@ -378,7 +402,9 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         if scores is not None:
             scores = np.stack([scores_row(c, m) for c, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
-        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res
+        if paths is not None:
+            paths = tuple(x.cpu().numpy() for x in paths)
+        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res, paths
 
     def marks(score, L):
         """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
@@ -407,6 +433,23 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             print(line)
         return f0res[0][i, :frames]
 
+    def timing_of(row, i, len_b, trim, paths, text_len, line, who, offset=0):
+        """(_dur.npy of row i of a batch (global row `row`), its word rows in the file it goes to) with `timings`, else (None, None);
+        prints the row's line.  trim: the row's [s, e] when the waveform was finished; offset: of the piece in a joined file"""
+        if paths is None:
+            return None, None
+        dur, counts, mass = (a[i] for a in paths)
+        print(path_line(who, counts, mass, text_len, stop.end_offset if stop is not None else 1)[0])
+        stretched = rate_of(row, len_b)
+        frames = stretched[1] if stretched is not None else (F if len_b is None else min(int(len_b) * config.r, F))
+        words = word_times(line, ivocab, dur[:text_len], config.r, None if steps is None else row_steps[row], trim, offset,
+                           300 * max(0, frames - 1), SR)
+        return dur[:text_len], words
+
+    def write_words(n, words):
+        with open(os.path.join(out_dir, 'prompt_%03d_words.tsv' % n), 'w') as f:
+            f.write(words_tsv(words))
+
     n = 0
     row_steps = steps
     if long is not None:
@@ -416,16 +459,20 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         if steps is not None:   # a piece has its prompt's rate; every row of the joined buffer holds the slowest one's samples
             row_steps = [steps[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
             L = 300 * (max(5, lib.stretch_capacity(F, min(row_steps, default=lib.STRETCH_ONE))) - 1)
-        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of, f0_of)
+        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of, f0_of,
+                       timing_of if timings else None, write_words)
         print('wrote %d samples to %s' % (n, out_dir))
         return n
     for batch in load_prompts(prompts, ivocab):
         Bn = batch['text'].shape[0]
-        spec, al, wav, conv, pcm, trim, lengths, scores, f0res = synthesise(batch, n)
+        spec, al, wav, conv, pcm, trim, lengths, scores, f0res, paths = synthesise(batch, n)
         for i in range(Bn):
             wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
+            dur, words = timing_of(n, i, len_b, ti, paths, int(batch['text_length'][i]), prompts[n], 'prompt %d' % n)
             write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
-                         rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n))
+                         rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n), dur=dur)
+            if words is not None:
+                write_words(n, words)
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
             if found:
                 print('WARNING prompt %d: %s' % (n, ', '.join(found)))
@@ -435,10 +482,11 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
 
 
 def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None,
-               pitch_of=lambda row: None, f0_of=lambda row, i, len_b, f0res, who: None):
+               pitch_of=lambda row: None, f0_of=lambda row, i, len_b, f0res, who: None, timing_of=None, write_words=None):
     """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write.  L: the samples
     per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b) / pitch_of(row) / f0_of(row, i, len_b, f0res,
-    who): what write_prompt gets as `rate` / `pitch` / `f0`"""
+    who): what write_prompt gets as `rate` / `pitch` / `f0`; timing_of / write_words (`timings`): test()'s own, called once the joined
+    offsets of a group are known"""
     pause_ms, fade_ms = long
     split = [split_prompt(p) for p in prompts]
     groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
@@ -460,10 +508,12 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
         rows = torch.empty(N, L, dtype=torch.float32, device='cuda')
         bounds = torch.empty(N, 2, dtype=torch.int32, device='cuda')
         arrays = []   # per piece: (spec, align, len_b, trim, conv, scores, text length, f0 rows)
+        timed = []    # per piece with `timings`: (the batch's paths, row in the batch)
         at = 0
         for batch in load_prompts(lines, ivocab):
             Bn = batch['text'].shape[0]
-            spec, al, _, conv, _, trim, lengths, scores, f0res = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            spec, al, _, conv, _, trim, lengths, scores, f0res, paths = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            timed += [(paths, i) for i in range(Bn)]
             arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i],
                         None if scores is None else scores[i], int(batch['text_length'][i]),
                         f0_of(row + at + i, i, int(lengths[i]), f0res, who[row + at + i])) for i in range(Bn)]
@@ -474,17 +524,24 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
         for p in range(lo, hi):
             a, b = first[p - lo], first[p - lo + 1]
             path = os.path.join(out_dir, 'prompt_%03d' % p)
-            found = []
+            found, words = [], []
             for k in range(a, b):
                 spec, al, len_b, trim, conv, score, text_len, f0rows = arrays[k]
+                dur = None
+                if timing_of is not None:
+                    dur, piece_words = timing_of(row + k, timed[k][1], len_b, trim, timed[k][0], text_len, lines[k], who[row + k],
+                                                 int(offsets[k]))
+                    words += piece_words
                 write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score,
-                             rate=rate_of(row + k, len_b), pitch=pitch_of(row + k), f0=f0rows)
+                             rate=rate_of(row + k, len_b), pitch=pitch_of(row + k), f0=f0rows, dur=dur)
                 names = marks(score, text_len) if score is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
             if found:
                 print('WARNING prompt %d: %s' % (p, '; '.join(found)))
             write_wav_pcm(path + '.wav', pcm[p - lo, :int(total[p - lo])])
+            if timing_of is not None:
+                write_words(p, words)
             if b - a > 1:
                 table = [[int(offsets[k]), min(L, max(0, int(arrays[k][3][1]) - int(arrays[k][3][0]))), 0 if k == b - 1 else gap[k],
                           kinds[k]] for k in range(a, b)]
@@ -554,14 +611,23 @@ def parse_args(argv=None):
     ap.add_argument('--align-scores', action='store_true',
                     help='score every prompt\'s attention on the device: prompt_NNN_ascore.npy (8 values: n, end, pad_steps, back, skip, '
                          'covered, focus, pad_mass), prompt_NNN_align.png, and a WARNING line for a prompt the (untuned) thresholds mark')
+    ap.add_argument('--timings', action='store_true',
+                    help='when each word is spoken: the best monotone path through every prompt\'s attention, found on the device; writes '
+                         'prompt_NNN_dur.npy (steps per character) and prompt_NNN_words.tsv (start_s, end_s, word); exact at multiples of 4 '
+                         'decoder steps, nominal inside a block (not in the reference)')
+    ap.add_argument('--path-jump', type=int, default=None, metavar='J',
+                    help='--timings: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
     if a.f0_range is not None and not a.f0:
         ap.error('--f0-range needs --f0')
     a.f0 = (a.f0_range if a.f0_range is not None else True) if a.f0 else None
+    if a.path_jump is not None and not a.timings:
+        ap.error('--path-jump needs --timings')
+    a.path_jump = lib.PATH_JUMP if a.path_jump is None else a.path_jump
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
-                      lifter=a.lifter, f0=a.f0)
+                      lifter=a.lifter, f0=a.f0, path_jump=a.path_jump if a.timings else None)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -577,4 +643,4 @@ if __name__ == '__main__':
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
-         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0)
+         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump)
