@@ -509,7 +509,8 @@ int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_
  * overlapping mag_t, B or F <= 0, F > TACO_STRETCH_MAX_FRAMES, C - 1 not a power of two in 8 .. 1024, lags out of range, ratio
  * outside (0, 1] or NaN, a NaN threshold and frames_per_unit < 1 return TACO_EINVAL, with a message that names the argument, before
  * anything is enqueued.  TACO_VERSION did not change with this entry point: detect it by the symbol.
- * Not here: smoothing across frames (Viterbi), F0 from mel frames.  The Python layer's ratio 0.9 and threshold 0.3 are untuned. */
+ * Not here: F0 from mel frames.  Smoothing across frames is taco_f0_viterbi below, which reads the acf this call writes.  The Python
+ * layer's ratio 0.9 and threshold 0.3 are untuned. */
 #define TACO_F0_MAX_LAGS 512
 int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_unit, const float* weight, const float* gain,
                    int lag_min, int lag_max, float ratio, float threshold, float* period, float* strength, float* acf,
@@ -524,6 +525,51 @@ int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_uni
  * frames_per_unit < 1 return TACO_EINVAL before anything is enqueued.  Detect it by the symbol. */
 int taco_f0_stats(const float* period, const float* other, const int32_t* frames, int frames_per_unit, float* stats, int B, int F,
                   void* stream);
+
+/* A pitch track smoothed across frames (no reference counterpart): up to K candidates per frame out of the acf taco_frames_f0 writes,
+ * and per frame one of them, or "unvoiced", chosen by the best path under a cost for pitch jumps and one for voiced / unvoiced
+ * switches (Boersma 1993) -- the cure for the octave flips and single-frame voicing drops of a pick that decides every frame alone.
+ *   acf    (B, L, F) fp32 as taco_frames_f0 writes it, L = lag_max - lag_min + 3, row j the lag lag_min - 1 + j; any 4-byte alignment
+ *   frames, frames_per_unit: as taco_frames_f0 (F_b = clamp(frames[b] * frames_per_unit, 0, F) in 64 bits, NULL: F); never read by the host
+ *   bias   (L) fp32 or NULL (zeros): subtracted from a candidate's height (Boersma's octave cost; the Python layer makes it)
+ *   lg     (L) fp32, required: the caller's log2 of the lag of every row -- the device takes no logarithm
+ *   1 <= K <= TACO_F0_MAX_CAND voiced candidates kept per frame; slot K is the unvoiced state
+ *   period, strength (B, F) fp32 with the meaning of taco_frames_f0's; counts (B, 4) int32; score (B) fp32: all required, every
+ *   element written;  workspace: taco_f0_viterbi_workspace_bytes(B, L, F, K) bytes, arbitrary contents
+ * EXACT rules, every arithmetic step one fp32 operation rounded to nearest even, nothing contracted, per row b over its frames
+ * f < F_b with y[i] = acf[b, i, f] (tests/f0_viterbi_ref.py restates them in NumPy float32 and gives the device's bits):
+ *   1. candidates: the rows 1 <= i <= L - 2 with y[i] > y[i-1] and y[i] >= y[i+1] (a NaN is never one); v(i) = y[i] - bias[i], and
+ *      v(i) = y[i] without an operation when bias is NULL
+ *   2. kept: the K first under "larger v first, smaller i on equal v", sorted by ascending i into slots 0 .. k_f - 1; the slots
+ *      k_f .. K - 1 are absent (v = -inf); slot K has v = threshold
+ *   3. T(p -> c) between slots of consecutive frames: both voiced: jump_cost * |lg[i_p] - lg[i_c]| (one subtraction, its absolute
+ *      value, one product); exactly one of them slot K: switch_cost; both slot K: +0
+ *   4. E(0, c) = v_c;  E(f, c) = max_p (D(f-1, p) - T(p -> c)) + v_c, the predecessor the lowest p of the largest difference (a
+ *      strict > from p = 0 on);  m_f = max_c E(f, c);  D(f, c) = E(f, c) - m_f
+ *   5. s(F_b - 1) = the lowest c of the largest D(F_b - 1, c);  s(f - 1) = the recorded predecessor of s(f)
+ *   6. a frame on a voiced slot with row i: period = float(lag_min - 1 + i) + delta with taco_frames_f0's parabola on y (a, t, d and
+ *      the clamp as above), strength = y[i]; a frame on slot K and every frame f >= F_b: +0 and +0;  score[b] = m_0 + m_1 + ...
+ *      summed in frame order, +0 for an empty row
+ *   7. counts[b] = { F_b, voiced = #{f : s(f) < K}, moved = #{f : s(f) != the lowest slot of the frame's largest local score v},
+ *      switches = #{f >= 1 : exactly one of s(f-1), s(f) is K} }; four zeros at F_b = 0
+ *   8. hence with jump_cost = switch_cost = 0 and bias NULL period and strength have the bits of taco_frames_f0 at ratio = 1 and
+ *      the same threshold, and moved = 0
+ * Frames f >= F_b and every other row have no influence on a row (they may hold NaN); a non-finite value among a row's first F_b
+ * columns leaves unspecified values in that row's outputs only -- the launch still ends and nothing outside the outputs and the
+ * workspace is written.  No float atomics: the same arguments give the same bits.  Two launches (B x ceil(F / 32) workgroups for the
+ * candidates, B for the paths), no allocation, no host synchronisation, no workgroup waits for another one: graph-capturable, and a
+ * replay follows whatever frames holds at replay time.  NULL acf / lg / period / strength / counts / score / workspace, an output
+ * overlapping acf, B or F <= 0, F > TACO_STRETCH_MAX_FRAMES, lags outside 2 <= lag_min <= lag_max or L > TACO_F0_MAX_LAGS, K outside
+ * 1 .. TACO_F0_MAX_CAND, a NaN or infinite threshold, a negative, NaN or infinite jump_cost or switch_cost and frames_per_unit < 1
+ * return TACO_EINVAL, with a message "f0_viterbi: ..." that names the argument, before anything is enqueued; the size function
+ * returns TACO_EINVAL for the same shapes.  TACO_VERSION did not change with this entry point: detect it by the symbol.
+ * Not here: the candidates formed inside taco_frames_f0's kernel (which would save the acf round trip), Boersma's silence term in
+ * the unvoiced score, tuned costs (the Python layer's are Praat's, untuned). */
+#define TACO_F0_MAX_CAND 15
+int64_t taco_f0_viterbi_workspace_bytes(int B, int L, int F, int K);
+int taco_f0_viterbi(const float* acf, const int32_t* frames, int frames_per_unit, const float* bias, const float* lg, int lag_min,
+                    int lag_max, int K, float threshold, float jump_cost, float switch_cost, float* period, float* strength,
+                    int32_t* counts, float* score, void* workspace, int B, int F, void* stream);
 
 /* F0 error along a warping path: the frame-by-frame companions of MCD (F0 RMSE, voicing decision error, gross pitch error).
  *   period_a (B, Fa), period_b (B, Fb) fp32 periods as taco_frames_f0 writes them (0: unvoiced);  path_a, path_b (B, P) int32,

@@ -9,7 +9,7 @@ utterances of the corpus, the ones `train --holdout N` never draws,
       with frames of log(1e-8) and stores no length.
 Only cost, steps, na, nb and the three losses of each batch travel to the host.
 
-    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--durations]
+    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--f0-smooth] [--durations]
 
 prints one line per batch and a final line with the mean teacher-forced loss and the mean and worst MCD, and writes
 eval_<step>.npy, one row per utterance: index, na, nb, steps, cost, mcd (float64; COLUMNS).
@@ -36,6 +36,13 @@ ALIGNED_COLUMNS behind F0_COLUMNS: the cells voiced in both tracks, the F0 RMSE 
 in cents over those cells, the voicing decision error (cells voiced in one track only / cells) and the gross pitch error (both-voiced
 cells whose periods differ by more than a factor GROSS / both-voiced cells); a column is NaN where its denominator is 0.  One more
 line per batch and one final line give their means over the utterances.  --f0 alone prints and saves exactly what it did.
+
+--f0-smooth (opt-in, implies --f0, combines with --f0-aligned): both tracks are smoothed across frames on the device
+(lib.f0_viterbi, taco_f0_viterbi: lib.F0_CANDIDATES candidates per frame, one of them or "unvoiced" per frame by the best path under
+lib.f0_viterbi_tables' bias and costs at the corpus' sample rate -- Praat's numbers, UNTUNED) in front of lib.f0_stats and
+lib.path_f0_scores, so F0_COLUMNS and ALIGNED_COLUMNS are those of the smoothed tracks.  Each row gains SMOOTH_COLUMNS behind every
+other column: the share of the frames tracked whose choice the smoothing moved away from the frame's own best, predicted and recorded.
+One more line per batch and one final line give their means.  Without it every mode prints and saves exactly what it did.
 
 --durations [--path-jump J] (opt-in): duration, the third of the usual prosody measures next to MCD and F0.  The best monotone path
 through the attention (Tacotron.alignment_path, taco_alignment_path; a step advances by at most J characters, default
@@ -69,7 +76,8 @@ from .train import latest_checkpoint, open_corpus
 COLUMNS = ('index', 'na', 'nb', 'steps', 'cost', 'mcd')
 F0_COLUMNS = ('f0_mean', 'f0_sd', 'voiced', 'rec_f0_mean', 'rec_f0_sd', 'rec_voiced')   # appended with --f0; the first two in log2 Hz
 ALIGNED_COLUMNS = ('path_voiced', 'f0_rmse_cents', 'f0_bias_cents', 'vuv_error', 'gross_error')   # appended with --f0-aligned
-DUR_COLUMNS = ('dur_mae_ms', 'dur_bias_ms', 'path_mass', 'rec_path_mass')   # appended with --durations (last)
+DUR_COLUMNS = ('dur_mae_ms', 'dur_bias_ms', 'path_mass', 'rec_path_mass')   # appended with --durations
+SMOOTH_COLUMNS = ('f0_moved', 'rec_f0_moved')   # appended with --f0-smooth (last): shares of the frames tracked
 GROSS = 1.2  # a both-voiced cell is a gross pitch error when one period is above GROSS times the other (the usual 20 %)
 SR = 16000   # of a corpus whose meta.pkl records no 'sr', and of the synthetic pool
 PAD_FLOOR = float(np.float16(np.log(1e-8)))   # the value preprocess stores in the padding frames (fp16 of log(1e-8))
@@ -189,14 +197,35 @@ def duration_summary(cols):
 DUR_LINE = 'duration error %.0f ms per character (bias %+.0f ms), path mass per step %.3f free-running / %.3f teacher-forced'
 
 
+def smooth_columns(counts, rec_counts):
+    """lib.f0_viterbi's counts (n, 4) of the predicted and of the recorded track -> (n, 2) float64 in the order SMOOTH_COLUMNS: moved /
+    F_b, NaN for a row without frames"""
+    out = np.full((len(counts), 2), np.nan)
+    for k, c in enumerate((np.asarray(counts, dtype=np.float64), np.asarray(rec_counts, dtype=np.float64))):
+        has = c[:, 0] > 0
+        out[has, k] = c[has, 2] / c[has, 0]
+    return out
+
+
+def smooth_summary(cols):
+    """(n, 2) in the order SMOOTH_COLUMNS -> their means over the utterances that have one; NaN without any"""
+    cols = np.asarray(cols, dtype=np.float64)
+    return tuple(float(np.nanmean(cols[:, k])) if np.isfinite(cols[:, k]).any() else float('nan') for k in range(2))
+
+
+SMOOTH_LINE = 'smoothing moved %.3f of the predicted and %.3f of the recorded frames'
+
+
 def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None,
-             f0=False, f0_aligned=False, durations=False, path_jump=lib.PATH_JUMP):
+             f0=False, f0_aligned=False, durations=False, path_jump=lib.PATH_JUMP, f0_smooth=False):
     """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  f0: rows (n, 12), F0_COLUMNS behind
     COLUMNS.  f0_aligned (implies f0): rows (n, 17), ALIGNED_COLUMNS behind those.  durations: DUR_COLUMNS behind all of them (path_jump: the max_jump of the two paths).  stop: the lib.TacoStopRule of the
     free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
     ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection; with f0_aligned also the two period
-    tracks 'period' and 'rec_period')."""
-    f0 = bool(f0 or f0_aligned)
+    tracks 'period' and 'rec_period').  f0_smooth (implies f0): both tracks go through lib.f0_viterbi in front of the statistics and the
+    path scores, SMOOTH_COLUMNS behind every other column; trace then also receives the per-frame tracks 'period_raw' and
+    'rec_period_raw' and the smoothed ones 'period' and 'rec_period'."""
+    f0 = bool(f0 or f0_aligned or f0_smooth)
     torch.cuda.set_device(device)
     dev = torch.device('cuda', device)
     corpus = open_corpus(config.data_path)
@@ -246,11 +275,16 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     nb = torch.empty(B, dtype=torch.int32, device=dev)
     zeros, ones = torch.zeros(80 * r, device=dev), torch.ones(80 * r, device=dev)
     per = {k: [] for k in ('na', 'nb', 'steps', 'cost') + (('f0', 'rec_f0', 'f0_frames') if f0 else ())
-           + (('path_counts', 'path_means') if f0_aligned else ())}
+           + (('path_counts', 'path_means') if f0_aligned else ()) + (('smooth',) if f0_smooth else ())}
     if f0:
         Cs = batch['stft'].shape[2] // r
         w, g, lag_min, lag_max = lib.f0_tables(sr, C=Cs)
         f0_opt = dict(weight=torch.from_numpy(w).to(dev), gain=torch.from_numpy(g).to(dev), lag_min=lag_min, lag_max=lag_max)
+        if f0_smooth:
+            bias, lg = lib.f0_viterbi_lag_tables(lag_min, lag_max)
+            _, _, jump, switch = lib.f0_viterbi_tables(sr, hop=300)
+            smooth_opt = dict(lag_min=lag_min, lag_max=lag_max, bias=torch.from_numpy(bias).to(dev), lg=torch.from_numpy(lg).to(dev),
+                              jump_cost=jump, switch_cost=switch)
         raw_stft = torch.empty(B, Td, Cs * r, device=dev)
         mags = torch.empty(B, Cs, (Td // 4) * 4 * r, device=dev)
         szeros, sones = torch.zeros(Cs * r, device=dev), torch.ones(Cs * r, device=dev)
@@ -280,11 +314,19 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         if f0:   # the decoder's own frames over lengths * r (max_decode_iter steps wide), then the recording's over nb
             pmags = lib.denorm_unframe(free.output, smean, sstd, r, want_spec=False, want_mag_t=True)
             Fp = pmags.shape[2]   # (the tracker counts over clamp(lengths r, 0, Fp); na is lengths r unclamped)
-            pred_period = lib.frames_f0(pmags, free.lengths, r, **f0_opt)[0]
+            if f0_smooth:
+                pred_raw, _, acf = lib.frames_f0(pmags, free.lengths, r, want_acf=True, **f0_opt)
+                pred_period, _, pred_moved, _ = lib.f0_viterbi(acf, free.lengths, r, **smooth_opt)
+            else:
+                pred_period = lib.frames_f0(pmags, free.lengths, r, **f0_opt)[0]
             pred_stats = lib.f0_stats(pred_period, None, free.lengths, r)
             lib.corpus_batch(feeder.data['stft'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw_stft)
             lib.denorm_unframe(raw_stft, szeros, sones, r, want_spec=False, want_mag_t=True, mag_t=mags)
-            rec_period = lib.frames_f0(mags, nb, 1, **f0_opt)[0]
+            if f0_smooth:
+                rec_raw, _, acf = lib.frames_f0(mags, nb, 1, want_acf=True, **f0_opt)
+                rec_period, _, rec_moved, _ = lib.f0_viterbi(acf, nb, 1, **smooth_opt)
+            else:
+                rec_period = lib.frames_f0(mags, nb, 1, **f0_opt)[0]
             rec_stats = lib.f0_stats(rec_period, None, nb, 1)
         if f0_aligned:   # the two tracks cell by cell of the warp's path; the path indexes the predicted mel frames
             Fm = path_a.shape[1] - recorded.shape[1] + 1
@@ -305,6 +347,8 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
             got['f0_frames'] = np.minimum(got['na'], Fp)
             if f0_aligned:
                 got['path_counts'], got['path_means'] = path_counts.cpu().numpy(), path_means.cpu().numpy()
+            if f0_smooth:
+                got['smooth'] = smooth_columns(pred_moved.cpu().numpy(), rec_moved.cpu().numpy())
             cents, share = f0_summary(np.concatenate([f0_columns(got['f0'][:valid], got['f0_frames'][:valid], sr),
                                                       f0_columns(got['rec_f0'][:valid], got['nb'][:valid], sr)], axis=1))
         if durations:
@@ -318,8 +362,10 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
         if trace is not None:
             trace.append({'predicted': free.predicted_mel()[0].cpu().numpy(), 'recorded': recorded.cpu().numpy(), 'na': got['na'].copy(),
                           'nb': got['nb'].copy()})
-            if f0_aligned:
+            if f0_aligned or f0_smooth:
                 trace[-1].update(period=pred_period.cpu().numpy(), rec_period=rec_period.cpu().numpy())
+            if f0_smooth:
+                trace[-1].update(period_raw=pred_raw.cpu().numpy(), rec_period_raw=rec_raw.cpu().numpy())
             if durations:
                 trace[-1].update(trace_dur)
         for k, v in got.items():
@@ -336,6 +382,8 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
                   % ((i,) + aligned_summary(aligned_columns(got['path_counts'][:valid], got['path_means'][:valid]))))
         if durations:
             print(('batch %d ' % i) + DUR_LINE % duration_summary(got['dur'][:valid]))
+        if f0_smooth:
+            print(('batch %d ' % i) + SMOOTH_LINE % smooth_summary(got['smooth'][:valid]))
     feeder.close()
     rows = mcd_rows(unpad(batches, [b[0] for b in batches]), *(unpad(batches, per[k]) for k in ('na', 'nb', 'steps', 'cost')))
     if f0:
@@ -349,6 +397,9 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     if durations:
         rows = np.concatenate([rows, unpad(batches, per['dur'])], axis=1)
         print('held out: ' + DUR_LINE % duration_summary(rows[:, -4:]) + ' (untuned max_jump %d; meaningless on an untrained model)' % path_jump)
+    if f0_smooth:
+        rows = np.concatenate([rows, unpad(batches, per['smooth'])], axis=1)
+        print('held out: ' + SMOOTH_LINE % smooth_summary(rows[:, -2:]) + ' (untuned costs, %d candidates per frame)' % lib.F0_CANDIDATES)
     weight = np.array([valid for _, valid in batches], dtype=np.float64)
     mean_loss = float((np.stack(losses)[:, 0] * weight).sum() / weight.sum())
     print('held out: %d utterances, teacher-forced loss %.1f, MCD-DTW mean %.3f dB worst %.3f dB (utterance %d) over %d cepstra of '
@@ -373,6 +424,9 @@ def parse_args(argv=None):
     ap.add_argument('--f0-aligned', action='store_true',
                     help='--f0, and the F0 error along the warping path: ALIGNED_COLUMNS (F0 RMSE and bias in cents, voicing decision '
                          'error, gross pitch error) behind F0_COLUMNS')
+    ap.add_argument('--f0-smooth', action='store_true',
+                    help='--f0, with both tracks smoothed across frames on the device (a Viterbi path over the candidates of every '
+                         'frame, untuned costs) in front of the statistics and of --f0-aligned; SMOOTH_COLUMNS behind every other column')
     ap.add_argument('--durations', action='store_true',
                     help='per-character durations from the best monotone attention path, free-running against teacher-forced: '
                          'DUR_COLUMNS (mean absolute difference and bias in ms, path mass per step of both) behind the other columns')
@@ -389,7 +443,7 @@ def main(argv=None, config=None):
         c.data_path = 'data/%s/' % a.train_set
     checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
     return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0, f0_aligned=a.f0_aligned, durations=a.durations,
-                    path_jump=a.path_jump)
+                    path_jump=a.path_jump, f0_smooth=a.f0_smooth)
 
 
 if __name__ == '__main__':

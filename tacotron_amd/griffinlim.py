@@ -20,7 +20,8 @@ With `pitch` (opt-in) the harmonics of every magnitude frame are moved along the
 Griffin-Lim (taco_frames_pitch): the voice gets higher or lower, the formants and the duration stay.
 
 With `f0` (opt-in) the pitch of the magnitude frames is measured on the device (taco_frames_f0, taco_f0_stats): the frames as de-normalised
-and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective stand-in for listening to those two controls.
+and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective stand-in for listening to those two controls.  With
+'smooth' in it every track is smoothed across frames (taco_f0_viterbi) before it is summarised.
 
 `finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
 front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16.
@@ -77,13 +78,27 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
       'model_stats' / 'vocoder_stats': lib.f0_stats of those periods (B, 3): count, mean and deviation of log2(period)
       'pitch_stats': with `pitch`, the paired lib.f0_stats (B, 3) of 'pitched' against 'model': 12 x its mean is the shift measured
                  in semitones over the frames voiced in both.
+      'smooth' in the dict (opt-in): True, or a dict of lib.f0_viterbi's keywords (bias, lg, candidates, threshold, jump_cost,
+                 switch_cost; True and whatever is missing: lib.f0_viterbi_lag_tables for the lags tracked, Praat's costs of
+                 lib.f0_viterbi_tables() and the pick's threshold -- all UNTUNED).  Every track is then taken with want_acf=True and
+                 passed through lib.f0_viterbi: tracks[name] holds the SMOOTHED (period, strength) and every *_stats is taken over
+                 those; tracks[name + '_raw'] holds the per-frame pair (the bits of a run without 'smooth') and
+                 tracks[name + '_counts'] the (B, 4) int32 counts in the order lib.F0_VITERBI_COUNTS.  The waveform does not change.
     Everything stays on the device.  F0 in Hz is SR / period."""
     track = None
     if f0 is not None and f0 is not False:
         opt = {} if f0 is True else dict(f0)
-        unknown = set(opt) - {'weight', 'gain', 'lag_min', 'lag_max', 'ratio', 'threshold', 'lengths'}
+        unknown = set(opt) - {'weight', 'gain', 'lag_min', 'lag_max', 'ratio', 'threshold', 'lengths', 'smooth'}
         if unknown:
             raise ValueError('invert_spectrogram: f0: unknown settings %s' % sorted(unknown))
+        smooth = opt.pop('smooth', None)
+        if smooth is not None and smooth is not False:
+            smooth = {} if smooth is True else dict(smooth)
+            unknown = set(smooth) - {'bias', 'lg', 'candidates', 'threshold', 'jump_cost', 'switch_cost'}
+            if unknown:
+                raise ValueError('invert_spectrogram: f0: smooth: unknown settings %s' % sorted(unknown))
+        else:
+            smooth = None
         f0_lengths = opt.pop('lengths', lengths)
         f0_unit = r if f0_lengths is not None else 1
         if not {'weight', 'gain', 'lag_min', 'lag_max'} & set(opt):   # (none given: the production tables at this bin count)
@@ -91,10 +106,27 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         for k in ('weight', 'gain'):   # (host tables go up once, not once per track)
             if opt.get(k) is not None and not (torch.is_tensor(opt[k]) and opt[k].device == out.device):
                 opt[k] = torch.as_tensor(np.asarray(opt[k], dtype=np.float32)).to(out.device)
+        if smooth is not None:   # (after the lags are known; host tables go up once)
+            lags = {k: opt[k] for k in ('lag_min', 'lag_max') if k in opt}
+            lag_min, lag_max = lags.get('lag_min', 40), lags.get('lag_max', 266)
+            if 'lg' not in smooth or 'bias' not in smooth:
+                bias, lg = lib.f0_viterbi_lag_tables(lag_min, lag_max)
+                smooth.setdefault('bias', bias)
+                smooth.setdefault('lg', lg)
+            for k in ('bias', 'lg'):
+                if smooth[k] is not None and not (torch.is_tensor(smooth[k]) and smooth[k].device == out.device):
+                    smooth[k] = torch.as_tensor(np.asarray(smooth[k], dtype=np.float32)).to(out.device)
+            smooth.setdefault('threshold', opt.get('threshold', lib.F0_THRESHOLD))
+            smooth.update(lags)
         tracks = {}
 
         def track(name, frames_t, counts, per_unit):
-            tracks[name] = lib.frames_f0(frames_t, counts, per_unit, **opt)
+            if smooth is None:
+                tracks[name] = lib.frames_f0(frames_t, counts, per_unit, **opt)
+            else:
+                period, strength, acf = lib.frames_f0(frames_t, counts, per_unit, want_acf=True, **opt)
+                smoothed = lib.f0_viterbi(acf, counts, per_unit, **smooth)
+                tracks[name], tracks[name + '_raw'], tracks[name + '_counts'] = smoothed[:2], (period, strength), smoothed[2]
             tracks[name + '_stats'] = lib.f0_stats(tracks[name][0], None, counts, per_unit)
     if frames_out is not None and rate is None:
         raise ValueError('invert_spectrogram: frames_out needs rate')
@@ -118,6 +150,8 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     if track:
         last = 'pitched' if pitch is not None else 'model'
         tracks['vocoder'], tracks['vocoder_stats'] = tracks[last], tracks[last + '_stats']
+        if smooth is not None:
+            tracks['vocoder_raw'], tracks['vocoder_counts'] = tracks[last + '_raw'], tracks[last + '_counts']
     done = (lambda res: res) if not track else (lambda res: (tuple(res) if isinstance(res, tuple) else (res,)) + (tracks,))
     if rate is not None:
         F = mag_t.shape[2]

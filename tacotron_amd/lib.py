@@ -128,6 +128,8 @@ EXPORTS = {
     'taco_frames_pitch': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     'taco_frames_f0': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     'taco_f0_stats': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _P]),
+    'taco_f0_viterbi_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
+    'taco_f0_viterbi': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_corpus_batch': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
     'taco_griffinlim_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim': (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P]),
@@ -719,6 +721,120 @@ def f0_stats(period, other=None, frames=None, frames_per_unit=1, out=None):
     on_gpu(who, 'period', dev)
     _check(_lib.taco_f0_stats(ptr(period), ptr(other), ptr(frames), frames_per_unit, ptr(out), B, F, stream_ptr()), 'taco_f0_stats')
     return out
+
+
+F0_MAX_CAND = 15           # TACO_F0_MAX_CAND
+F0_CANDIDATES = 4          # candidates kept per frame by default: UNTUNED
+F0_VITERBI_COUNTS = ('frames', 'voiced', 'moved', 'switches')   # the columns of f0_viterbi's counts
+F0_OCTAVE_COST, F0_JUMP_COST, F0_SWITCH_COST = 0.01, 0.35, 0.14   # Praat's defaults (Boersma 1993), per 0.01 s of frame period: UNTUNED
+
+
+def f0_viterbi_lag_tables(lag_min, lag_max, octave_cost=F0_OCTAVE_COST):
+    """(bias (L) float32, lg (L) float32) of f0_viterbi for the lags lag_min - 1 .. lag_max + 1 (f0_viterbi_tables has the formulas);
+    float64 on the host, rounded once"""
+    who = 'f0_viterbi_lag_tables'
+    lag_min, lag_max = int_arg(who, 'lag_min', lag_min, 2), int_arg(who, 'lag_max', lag_max)
+    if lag_max < lag_min or lag_max - lag_min + 3 > F0_MAX_LAGS:
+        raise ValueError('%s: need lag_min <= lag_max and at most %d lags with their neighbours, got lag_min = %d, lag_max = %d'
+                         % (who, F0_MAX_LAGS, lag_min, lag_max))
+    octave_cost = float(octave_cost)
+    if not (0.0 <= octave_cost < math.inf):   # (NaN fails)
+        raise ValueError('%s: octave_cost must be finite and not negative, got %r' % (who, octave_cost))
+    lags = np.arange(lag_min - 1, lag_max + 2, dtype=np.float64)
+    return (octave_cost * np.log2(lags / lag_max)).astype(np.float32), np.log2(lags).astype(np.float32)
+
+
+def f0_viterbi_tables(sr=16000, fmin=60.0, fmax=400.0, octave_cost=F0_OCTAVE_COST, hop=300):
+    """The tables and costs of f0_viterbi for frames `hop` samples apart -> (bias (L) float32, lg (L) float32, jump_cost, switch_cost),
+    host NumPy computed in float64 and rounded once; row j is the lag lag_min - 1 + j of f0_lags(sr, fmin, fmax):
+      lg[j] = log2(lag_j);
+      bias[j] = octave_cost * log2(lag_j / lag_max): <= 0 up to lag_max and zero at the lowest pitch, so that a shorter lag of the same
+      height scores higher (Praat's octave cost);
+      jump_cost, switch_cost = Praat's 0.35 and 0.14 times 0.01 s / (hop / sr), its own correction for the frame period.
+    All of them are UNTUNED: nobody has compared them with a labelled pitch track."""
+    lag_min, lag_max = f0_lags(sr, fmin, fmax)
+    L = lag_max - lag_min + 3
+    if lag_min < 2 or L > F0_MAX_LAGS:
+        raise ValueError('f0_viterbi_tables: %g .. %g Hz at %g Hz are lags %d .. %d: need lag_min >= 2 and at most %d lags with their '
+                         'neighbours' % (fmin, fmax, sr, lag_min, lag_max, F0_MAX_LAGS))
+    octave_cost, hop = float(octave_cost), float(hop)
+    if not (0.0 <= octave_cost < math.inf):   # (NaN fails)
+        raise ValueError('f0_viterbi_tables: octave_cost must be finite and not negative, got %r' % (octave_cost,))
+    if not (0.0 < hop < math.inf):
+        raise ValueError('f0_viterbi_tables: hop must be a positive number of samples, got %r' % (hop,))
+    bias, lg = f0_viterbi_lag_tables(lag_min, lag_max, octave_cost)
+    scale = 0.01 / (hop / float(sr))
+    return bias, lg, F0_JUMP_COST * scale, F0_SWITCH_COST * scale
+
+
+def _f0_viterbi_shape(who, B, L, F, K):
+    B, L, F = int_arg(who, 'B', B, 1, _INT_MAX), int_arg(who, 'L', L, 3, F0_MAX_LAGS), int_arg(who, 'F', F, 1)
+    _frames_cap(who, F)
+    return B, L, F, int_arg(who, 'candidates', K, 1, F0_MAX_CAND)
+
+
+def f0_viterbi_workspace_bytes(B, L, F, K) -> int:
+    return _size('taco_f0_viterbi_workspace_bytes', *_f0_viterbi_shape('f0_viterbi_workspace_bytes', B, L, F, K))
+
+
+def _cost_arg(who, name, x) -> float:
+    x = float(x)
+    if not (0.0 <= x < math.inf) or not (C.c_float(x).value < math.inf):   # (NaN fails; so does what rounds to infinity in float32)
+        raise ValueError('%s: %s must be finite and not negative, got %r' % (who, name, x))
+    return x
+
+
+def f0_viterbi(acf, frames=None, frames_per_unit=1, lag_min=40, lag_max=266, bias=None, lg=None, candidates=F0_CANDIDATES,
+               threshold=F0_THRESHOLD, jump_cost=None, switch_cost=None, out=None, workspace=None):
+    """A pitch track smoothed across frames (include/taco_hip.h taco_f0_viterbi): acf (B, L, F) fp32 on the device as
+    frames_f0(..., want_acf=True) returns it, L = lag_max - lag_min + 3 -> (period (B, F) fp32, strength (B, F) fp32 with the meaning
+    of frames_f0's, counts (B, 4) int32 in the order F0_VITERBI_COUNTS, score (B) fp32), device tensors.  Per frame the `candidates`
+    highest local maxima of acf minus bias are kept, and one of them or "unvoiced" (which scores `threshold`) is chosen per frame by
+    the best path under jump_cost per octave between consecutive voiced frames and switch_cost per voiced / unvoiced switch.
+    frames: (B) int32 on the device, or None.  bias (L): None (zeros), a float32 device tensor or host numbers; lg (L): the log2 of
+    every row's lag, likewise -- None: the table of f0_viterbi_tables for these lags.  jump_cost / switch_cost None: those of
+    f0_viterbi_tables() (16 kHz, hop 300).  All defaults are UNTUNED.  With both costs 0 and no bias the result is frames_f0's at
+    ratio = 1.  out: the caller's own (period, strength, counts, score); workspace: uint8, f0_viterbi_workspace_bytes(B, L, F,
+    candidates) bytes; default: fresh ones.  Enqueued on the current stream; nothing is read back and nothing waits."""
+    who = 'f0_viterbi'
+    B, L, F = tensor_arg(who, 'acf', acf, torch.float32, ('B', 'L', 'F'))
+    dev = acf.device
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    lag_min, lag_max = int_arg(who, 'lag_min', lag_min), int_arg(who, 'lag_max', lag_max)
+    if not 2 <= lag_min <= lag_max or lag_max - lag_min + 3 > F0_MAX_LAGS:
+        raise ValueError('%s: need 2 <= lag_min <= lag_max and at most %d lags with their neighbours, got lag_min = %d, lag_max = %d'
+                         % (who, F0_MAX_LAGS, lag_min, lag_max))
+    if L != lag_max - lag_min + 3:
+        raise ValueError('%s: acf must have lag_max - lag_min + 3 = %d rows, got %d' % (who, lag_max - lag_min + 3, L))
+    K = int_arg(who, 'candidates', candidates, 1, F0_MAX_CAND)
+    threshold = float(threshold)
+    if not (-math.inf < threshold < math.inf) or not (abs(C.c_float(threshold).value) < math.inf):
+        raise ValueError('%s: threshold must be finite, got %r' % (who, threshold))
+    if jump_cost is None or switch_cost is None:
+        _, _, jump_d, switch_d = f0_viterbi_tables()
+        jump_cost, switch_cost = jump_d if jump_cost is None else jump_cost, switch_d if switch_cost is None else switch_cost
+    jump_cost, switch_cost = _cost_arg(who, 'jump_cost', jump_cost), _cost_arg(who, 'switch_cost', switch_cost)
+    if lg is None:
+        lg = f0_viterbi_lag_tables(lag_min, lag_max)[1]
+    bias = _f0_table(who, 'bias', bias, L, dev)
+    lg = _f0_table(who, 'lg', lg, L, dev)
+    if out is not None and len(out) != 4:
+        raise ValueError('%s: out must be (period, strength, counts, score)' % who)
+    period = _own_or_given(None if out is None else out[0], (B, F), torch.float32, dev, who + ': period')
+    strength = _own_or_given(None if out is None else out[1], (B, F), torch.float32, dev, who + ': strength')
+    counts = _own_or_given(None if out is None else out[2], (B, len(F0_VITERBI_COUNTS)), torch.int32, dev, who + ': counts')
+    score = _own_or_given(None if out is None else out[3], (B,), torch.float32, dev, who + ': score')
+    for name, t in (('period', period), ('strength', strength), ('counts', counts), ('score', score)):
+        no_overlap(who, 'acf', acf, name, t)
+    if workspace is not None:
+        tensor_arg(who, 'workspace', workspace, torch.uint8, ('bytes',), dev)
+    on_gpu(who, 'acf', dev)
+    workspace = _own_or_given(workspace, (f0_viterbi_workspace_bytes(B, L, F, K),), torch.uint8, dev, who + ': workspace')
+    _check(_lib.taco_f0_viterbi(ptr(acf), ptr(frames), frames_per_unit, ptr(bias), ptr(lg), lag_min, lag_max, K, threshold, jump_cost,
+                                switch_cost, ptr(period), ptr(strength), ptr(counts), ptr(score), ptr(workspace), B, F, stream_ptr()),
+           'taco_f0_viterbi')
+    return period, strength, counts, score
 
 
 DTW_MAX_FRAMES, DTW_MAX_K, DTW_MAX_C = 1024, 32, 128   # TACO_DTW_MAX_FRAMES / _K / _C

@@ -48,6 +48,11 @@ those frames; with --rate alone the line gives the change of the mean log-F0 in 
 counts differ).  The pick's ratio 0.9 and threshold 0.3 are UNTUNED, and on an untrained model the frames have no pitch: the numbers
 then mean nothing.  It is the objective stand-in for listening to --pitch and --rate, which nobody has done.  It combines with every
 option above; with --long the files are per piece.
+--f0-smooth [--f0-candidates K] (opt-in, implies --f0): the track is smoothed across frames on the device (lib.f0_viterbi,
+taco_f0_viterbi: the K highest maxima of every frame's autocorrelation are kept, default lib.F0_CANDIDATES = 4, and one of them or
+"unvoiced" is chosen per frame by the best path under Praat's costs for octave jumps and voicing switches -- UNTUNED).
+prompt_NNN_f0.npy and the per-prompt line then use the smoothed track, and the line gains `, smoothing moved M of N frames`: the
+frames whose choice differs from the frame's own best.  Without it every file and line is what it was.
 --timings [--path-jump J] (opt-in, not in the reference): when each word is spoken.  The best monotone path through every prompt's
 attention is found on the device (Tacotron.alignment_path, taco_alignment_path; over each prompt's own steps with --stop; a step may
 advance by at most J characters, default lib.PATH_JUMP = 4, untuned) and only its durations, counts and mass come back with the other
@@ -160,9 +165,14 @@ def f0_range(f0):
 
 def f0_lines(who, f0row, asked_step=None, rate_step=None):
     """the line(s) --f0 prints for `who` ('prompt 3', or 'prompt 3 piece 1' with --long) from its row of the statistics: f0row =
-    (model_stats, vocoder_stats, pitch_stats | None)"""
-    model, voc, paired = f0row
+    (model_stats, vocoder_stats, pitch_stats | None), and with --f0-smooth behind them the row's lib.f0_viterbi counts: the line
+    gains `, smoothing moved M of N frames` (without --pitch and --rate that is the whole line)"""
+    model, voc, paired = f0row[:3]
     out = []
+    if len(f0row) > 3 and f0row[3] is not None:
+        tail = 'smoothing moved %d of %d frames' % (int(f0row[3][2]), int(f0row[3][0]))
+        lines = f0_lines(who, f0row[:3], asked_step, rate_step)
+        return ['%s, %s' % (lines[0], tail)] + lines[1:] if lines else ['%s f0: %s' % (who, tail)]
     if asked_step is not None and paired is not None:
         out.append('%s pitch: asked %+.2f, measured %+.2f semitones over %d voiced frames'
                    % (who, 12.0 * np.log2(65536.0 / asked_step), 12.0 * float(paired[1]), int(paired[0])))
@@ -173,9 +183,14 @@ def f0_lines(who, f0row, asked_step=None, rate_step=None):
 
 
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32, f0=None, path_jump=None):
+                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, path_jump=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
-    without --timings); ValueError."""
+    without --timings; `f0_smooth`: None / False, True or the number of candidates); ValueError."""
+    if f0_smooth is not None and f0_smooth is not False:
+        if f0 is None or f0 is False:
+            raise ValueError('f0_smooth (--f0-smooth) smooths the track of f0 (--f0): it needs f0')
+        if f0_smooth is not True:
+            lib.int_arg('check_options', 'f0_smooth (--f0-candidates)', f0_smooth, 1, lib.F0_MAX_CAND)
     if path_jump is not None:
         lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
     if f0 is not None and f0 is not False:
@@ -252,7 +267,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
          gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None,
-         timings=False, path_jump=lib.PATH_JUMP):
+         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -295,12 +310,16 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     device, over the row's own len_b r frames with `stop`; prompt_NNN_f0.npy holds (period, strength) of the frames the vocoder was
     given, and f0_lines() prints what `pitch` or `rate` did to it.  Untuned, and meaningless on an untrained model; nothing else
     changes.
+    `f0_smooth` (needs `f0`): None, True (lib.F0_CANDIDATES candidates per frame) or their number in 1 .. 15: the tracks are smoothed
+    across frames on the device (invert_spectrogram(f0={'smooth': ...}), lib.f0_viterbi with lib.f0_viterbi_tables' UNTUNED bias and
+    costs for the range of `f0`); _f0.npy and f0_lines() use the smoothed track and the line names the frames the smoothing moved.
     `timings` / `path_jump`: every batch's best monotone attention paths are found on the device (Tacotron.alignment_path with
     max_jump = path_jump: over model.lengths with `stop`, else all steps); each prompt -- with `long`, each piece -- additionally
     writes _dur.npy, each prompt _words.tsv (alignment.word_times of the file it wrote) and one line, a WARNING when the path ends
     before the text does.  Nothing else changes."""
     check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
-                  path_jump=path_jump if timings else None)
+                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None)
+    f0_smooth = None if f0_smooth is None or f0_smooth is False else (lib.F0_CANDIDATES if f0_smooth is True else int(f0_smooth))
     f0 = f0_range(f0)
     f0_opt = None   # the tables on the device, made at the first batch
     steps = rate_steps(rate, len(prompts))
@@ -329,7 +348,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths), host arrays or
         None.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
         out_rows / bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made.
-        f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None)"""
+        f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
+        lib.f0_viterbi counts (B, 4))"""
         nonlocal f0_opt
         Bn = batch['text'].shape[0]
         if config.num_speakers > 1:
@@ -364,6 +384,10 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                 if f0_opt is None:
                     w, g, lag_min, lag_max = lib.f0_tables(SR, f0[0], f0[1])
                     f0_opt = dict(weight=torch.from_numpy(w).cuda(), gain=torch.from_numpy(g).cuda(), lag_min=lag_min, lag_max=lag_max)
+                    if f0_smooth is not None:
+                        bias, lg, jump, switch = lib.f0_viterbi_tables(SR, f0[0], f0[1])
+                        f0_opt['smooth'] = dict(bias=torch.from_numpy(bias).cuda(), lg=torch.from_numpy(lg).cuda(), candidates=f0_smooth,
+                                                jump_cost=jump, switch_cost=switch)
                 shift['f0'] = dict(f0_opt, lengths=model.lengths if stop is not None else None)
             if steps is None:
                 res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
@@ -377,6 +401,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                 tracks = res.pop()
                 f0res = (torch.stack(tracks['vocoder'], dim=2).cpu().numpy(), tracks['model_stats'].cpu().numpy(),
                          tracks['vocoder_stats'].cpu().numpy(), tracks['pitch_stats'].cpu().numpy() if 'pitch_stats' in tracks else None)
+                if f0_smooth is not None:
+                    f0res += (tracks['vocoder_counts'].cpu().numpy(),)
             if steps is not None:
                 fout = res.pop()
             wav = res[0] if gl_momentum is None else res
@@ -608,6 +634,11 @@ def parse_args(argv=None):
                          'in samples, strength) and, with --pitch or --rate, prints what was asked for and what is measured (untuned '
                          'ratio 0.9 / threshold 0.3; meaningless on an untrained model; not in the reference)')
     ap.add_argument('--f0-range', type=_f0_range, default=None, metavar='LO,HI', help='--f0: the pitch range searched in Hz (default 60,400)')
+    ap.add_argument('--f0-smooth', action='store_true',
+                    help='--f0, with the track smoothed across frames on the device (a Viterbi path over the candidates of every frame, '
+                         'untuned costs); _f0.npy and the per-prompt line use the smoothed track')
+    ap.add_argument('--f0-candidates', type=int, default=None, metavar='K',
+                    help='--f0-smooth: candidates kept per frame, 1 <= K <= 15 (default %d, untuned)' % lib.F0_CANDIDATES)
     ap.add_argument('--align-scores', action='store_true',
                     help='score every prompt\'s attention on the device: prompt_NNN_ascore.npy (8 values: n, end, pad_steps, back, skip, '
                          'covered, focus, pad_mass), prompt_NNN_align.png, and a WARNING line for a prompt the (untuned) thresholds mark')
@@ -619,6 +650,10 @@ def parse_args(argv=None):
                     help='--timings: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
+    if a.f0_candidates is not None and not a.f0_smooth:
+        ap.error('--f0-candidates needs --f0-smooth')
+    a.f0 = a.f0 or a.f0_smooth
+    a.f0_smooth = (a.f0_candidates if a.f0_candidates is not None else True) if a.f0_smooth else None
     if a.f0_range is not None and not a.f0:
         ap.error('--f0-range needs --f0')
     a.f0 = (a.f0_range if a.f0_range is not None else True) if a.f0 else None
@@ -627,7 +662,7 @@ def parse_args(argv=None):
     a.path_jump = lib.PATH_JUMP if a.path_jump is None else a.path_jump
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
-                      lifter=a.lifter, f0=a.f0, path_jump=a.path_jump if a.timings else None)
+                      lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings else None)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -643,4 +678,5 @@ if __name__ == '__main__':
     rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
-         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump)
+         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump,
+         f0_smooth=a.f0_smooth)
