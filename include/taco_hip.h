@@ -124,6 +124,52 @@ int taco_bigru_fwd(const float* x, const float* wg_fw, const float* bg_fw, const
                    const float* wg_bw, const float* bg_bw, const float* wc_bw, const float* bc_bw, float* xg,
                    float* out, float* ruc, int B, int T, void* stream);
 
+/* ---- op-level debug doors of the CBHG tail (tests/test_gpu_cbhg_tail.py) ------------------------------------
+ * Thin wrappers over the launches the model makes for the bi-GRU recurrences (bigru.hip), the highway stacks (highway.hip) and
+ * the encoder pre_net (prenet.hip), so that a test can place every operand itself.  All tensors fp32, dense and row-major.  A null
+ * operand that is not marked nullable, a size out of range, or an output whose bytes meet those of any other operand returns
+ * TACO_EINVAL with a message that names the argument, before anything is enqueued.  Outputs arrive with arbitrary contents; no
+ * call writes a byte outside the extents given here.  TACO_VERSION did not change with these entry points: detect them by the
+ * symbol.
+ *
+ * taco_debug_bigru_rec_fwd: the forward recurrence of both directions without the x-side projection.
+ *   xg (B,T,768): per direction d the pre-activations [x.Wg_x + bg (256: r | u) | x.Wc_x + bc (128)] at columns [384 d, 384 d + 384);
+ *   wg_* (256,256), wc_* (256,128): the GRUCell kernels in TF layout, of which rows [128, 256) (the h side) are read;
+ *   h0 (B,128) initial state of both directions, nullable (zeros).
+ *   out (B,T,256) = [fw | bw]; ruc (B,T,768), nullable: per direction [r | u | c] at columns [384 d, 384 d + 384).
+ * taco_debug_bigru_bwd: the backward recurrence (BPTT) of both directions.
+ *   dout (B,T,256) gradient of out; out, ruc as the forward call wrote them; h0 as given to it (nullable);
+ *   wghT_* (256,128) = Wg[128:, :]^T, wchT_* (128,128) = Wc[128:, :]^T (the layout of BiGruBwdWeights, csrc/kernels.h).
+ *   dxg (B,T,768) gradient of xg; rh (B,T,256) = r * h_prev per direction; dh0 (2,B,128), nullable: gradient of h0 per direction. */
+int taco_debug_bigru_rec_fwd(const float* xg, const float* wg_fw, const float* wc_fw, const float* wg_bw, const float* wc_bw,
+                             const float* h0, float* out, float* ruc, int B, int T, void* stream);
+int taco_debug_bigru_bwd(const float* dout, const float* out, const float* ruc, const float* wghT_fw, const float* wchT_fw,
+                         const float* wghT_bw, const float* wchT_bw, const float* h0, float* dxg, float* rh, float* dh0, int B, int T,
+                         void* stream);
+/* taco_debug_highway_stack_fwd / _bwd: the fields of HighwayStackArgs / HighwayStackBwdArgs (csrc/kernels.h).  Every `const*`
+ * argument is a table of 4 pointers, one per layer, of which entries [0, nl) are read; nl in [1, 4].
+ *   forward : x (M,128); wt, wh (128,128), bt, bh (128) per layer; y[l] (M,128) the layer's output; th, nullable as a table:
+ *             th[l] (M,256) = [T | H].  Adapter form (wa != NULL; nl == 4, T divides M): wa[l] (128,128), rowb[l] (M / T,128),
+ *             hx[l] (M,128) = y[l-1] . wa[l] + rowb[l][m / T], the input of the layer's gates.
+ *   backward: g (M,128) gradient of y[nl-1]; wT[l] (256,128) = [Wt^T ; Wh^T]; th[l] as the forward wrote it; x[l] (M,128) the input of
+ *             layer l's gates (plain: x, y[0], ..; adapter form: hx[l]); dth[l] (M,256) gradient of the pre-activations of [T | H];
+ *             gout (M,128) gradient of x.  Adapter form (waT != NULL; nl == 4): waT[l] (128,128) = wa[l]^T, dhx[l] (M,128) gradient
+ *             of hx[l]. */
+int taco_debug_highway_stack_fwd(const float* x, const float* const* wt, const float* const* bt, const float* const* wh,
+                                 const float* const* bh, float* const* th, float* const* y, const float* const* wa,
+                                 const float* const* rowb, float* const* hx, int M, int nl, int T, void* stream);
+int taco_debug_highway_stack_bwd(const float* g, const float* const* wT, const float* const* th, const float* const* x,
+                                 float* const* dth, float* gout, const float* const* waT, float* const* dhx, int M, int nl, void* stream);
+/* taco_debug_prenet_fwd / _bwd: the fields of PrenetArgs (csrc/kernels.h).  keep1 (M,256), keep2 (M,128): uint8 0 / 1 keep masks of
+ * the two dropout layers, both nullable (no dropout; a kept unit is scaled by 2).
+ *   forward : x (M,256); w1 (256,256), b1 (256), w2 (256,128), b2 (128) (biases nullable); y1 (M,256), y2 (M,128) after ReLU and dropout.
+ *   backward: dy2 (M,128) gradient of y2; w2T (128,256) = w2^T, w1T (256,256) = w1^T; y1_in, y2_in the forward's y1, y2;
+ *             dz2 (M,128), dz1 (M,256) gradients of the two pre-activations; dx (M,256) gradient of x. */
+int taco_debug_prenet_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const uint8_t* keep1,
+                          const uint8_t* keep2, float* y1, float* y2, int M, void* stream);
+int taco_debug_prenet_bwd(const float* dy2, const float* w2T, const float* w1T, const uint8_t* keep1, const uint8_t* keep2,
+                          const float* y1_in, const float* y2_in, float* dz2, float* dz1, float* dx, int M, void* stream);
+
 /* ---- model level ---------------------------------------------------------------------------------------- */
 /* Tacotron.inference with train=True (tacotron.py:107-154) + add_loss_op (tacotron.py:156-165).
  *   text (B,Tt) int32; text_length (B) int32; mel (B,Td,80r); stft (B,Td,1025r);

@@ -354,3 +354,49 @@ int launch_bigru_bwd(const float* dout, const float* out, const float* ruc, cons
   TACO_LAUNCH_CHECK("bigru_bwd");
   return TACO_OK;
 }
+
+// ---- debug doors (include/taco_hip.h): the recurrences alone, operands placed by the caller ----
+extern "C" int taco_debug_bigru_rec_fwd(const float* xg, const float* wg_fw, const float* wc_fw, const float* wg_bw, const float* wc_bw,
+                                        const float* h0, float* out, float* ruc, int B, int T, void* stream) {
+  const char* who = "taco_debug_bigru_rec_fwd";
+  TACO_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= (1 << 24), "%s: B and T must be positive with B * T <= 2^24, got B = %d, T = %d", who, B, T);
+  const size_t M = (size_t)B * T, f = sizeof(float);
+  DoorOperands o;
+  o.in(xg, M * 6 * H * f, "xg");
+  o.in(wg_fw, (size_t)2 * H * 2 * H * f, "wg_fw");
+  o.in(wc_fw, (size_t)2 * H * H * f, "wc_fw");
+  o.in(wg_bw, (size_t)2 * H * 2 * H * f, "wg_bw");
+  o.in(wc_bw, (size_t)2 * H * H * f, "wc_bw");
+  o.in_opt(h0, (size_t)B * H * f, "h0");
+  o.out(out, M * 2 * H * f, "out");
+  o.out_opt(ruc, M * 6 * H * f, "ruc");
+  TACO_TRY(o.check(who));
+  BiGruWeights w;
+  w.wg[0] = wg_fw; w.wc[0] = wc_fw; w.wg[1] = wg_bw; w.wc[1] = wc_bw;
+  w.bg[0] = w.bg[1] = w.bc[0] = w.bc[1] = nullptr;   // (the biases are part of xg)
+  return launch_bigru_fwd(xg, w, h0, out, ruc, B, T, as_stream(stream));
+}
+
+extern "C" int taco_debug_bigru_bwd(const float* dout, const float* out, const float* ruc, const float* wghT_fw, const float* wchT_fw,
+                                    const float* wghT_bw, const float* wchT_bw, const float* h0, float* dxg, float* rh, float* dh0,
+                                    int B, int T, void* stream) {
+  const char* who = "taco_debug_bigru_bwd";
+  TACO_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= (1 << 24), "%s: B and T must be positive with B * T <= 2^24, got B = %d, T = %d", who, B, T);
+  const size_t M = (size_t)B * T, f = sizeof(float);
+  DoorOperands o;
+  o.in(dout, M * 2 * H * f, "dout");
+  o.in(out, M * 2 * H * f, "out");
+  o.in(ruc, M * 6 * H * f, "ruc");
+  o.in(wghT_fw, (size_t)2 * H * H * f, "wghT_fw");
+  o.in(wchT_fw, (size_t)H * H * f, "wchT_fw");
+  o.in(wghT_bw, (size_t)2 * H * H * f, "wghT_bw");
+  o.in(wchT_bw, (size_t)H * H * f, "wchT_bw");
+  o.in_opt(h0, (size_t)B * H * f, "h0");
+  o.out(dxg, M * 6 * H * f, "dxg");
+  o.out(rh, M * 2 * H * f, "rh");
+  o.out_opt(dh0, (size_t)2 * B * H * f, "dh0");
+  TACO_TRY(o.check(who));
+  BiGruBwdWeights w;
+  w.wghT[0] = wghT_fw; w.wchT[0] = wchT_fw; w.wghT[1] = wghT_bw; w.wchT[1] = wchT_bw;
+  return launch_bigru_bwd(dout, out, ruc, w, h0, dxg, rh, dh0, B, T, as_stream(stream));
+}

@@ -128,6 +128,39 @@ static inline bool ensure_dyn_smem(DynSmemOnce& done, const void* func, size_t b
   return true;
 }
 
+// ---- argument checks of the op-level debug doors (taco_debug_bigru_*, taco_debug_highway_stack_*, taco_debug_prenet_*) ----
+// Every operand of a call as (name, pointer, bytes, written by the call, may be null).  A missing operand, or an output whose
+// bytes meet those of any other operand, is refused by name before anything is enqueued.
+struct DoorOperands {
+  struct Op { char name[24]; const void* p; size_t bytes; bool out, optional; };
+  Op ops[64];
+  int n = 0;
+  void add(const void* p, size_t bytes, bool out, bool optional, const char* fmt, int idx = 0) {
+    if (n >= 64) return;
+    Op& o = ops[n++];
+    snprintf(o.name, sizeof(o.name), fmt, idx);
+    o.p = p; o.bytes = bytes; o.out = out; o.optional = optional;
+  }
+  void in(const void* p, size_t bytes, const char* fmt, int idx = 0) { add(p, bytes, false, false, fmt, idx); }
+  void in_opt(const void* p, size_t bytes, const char* fmt, int idx = 0) { add(p, bytes, false, true, fmt, idx); }
+  void out(const void* p, size_t bytes, const char* fmt, int idx = 0) { add(p, bytes, true, false, fmt, idx); }
+  void out_opt(const void* p, size_t bytes, const char* fmt, int idx = 0) { add(p, bytes, true, true, fmt, idx); }
+  int check(const char* who) const {
+    for (int i = 0; i < n; ++i)
+      TACO_REQUIRE(ops[i].p || ops[i].optional, "%s: %s is null", who, ops[i].name);
+    for (int i = 0; i < n; ++i) {
+      if (!ops[i].out || !ops[i].p) continue;
+      const char* o0 = static_cast<const char*>(ops[i].p);
+      for (int j = 0; j < n; ++j) {
+        if (j == i || !ops[j].p || (ops[j].out && j < i)) continue;   // (a pair of outputs is reported once)
+        const char* i0 = static_cast<const char*>(ops[j].p);
+        TACO_REQUIRE(!(o0 < i0 + ops[j].bytes && i0 < o0 + ops[i].bytes), "%s: %s may not overlap %s", who, ops[i].name, ops[j].name);
+      }
+    }
+    return TACO_OK;
+  }
+};
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

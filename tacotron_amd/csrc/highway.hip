@@ -334,3 +334,76 @@ int launch_highway_stack_fwd(const HighwayStackArgs& a, hipStream_t s) {
   TACO_LAUNCH_CHECK("highway_stack_fwd");
   return TACO_OK;
 }
+
+// ---- debug doors (include/taco_hip.h): the stacks alone, every field of the argument records given by the caller ----
+extern "C" int taco_debug_highway_stack_fwd(const float* x, const float* const* wt, const float* const* bt, const float* const* wh,
+                                            const float* const* bh, float* const* th, float* const* y, const float* const* wa,
+                                            const float* const* rowb, float* const* hx, int M, int nl, int T, void* stream) {
+  const char* who = "taco_debug_highway_stack_fwd";
+  TACO_REQUIRE(M > 0 && M <= (1 << 24), "%s: M must be in [1, 2^24], got %d", who, M);
+  TACO_REQUIRE(nl >= 1 && nl <= 4, "%s: nl must be in [1, 4], got %d", who, nl);
+  TACO_REQUIRE(wt && bt && wh && bh && y, "%s: a null pointer table (wt, bt, wh, bh, y)", who);
+  const bool ad = wa != nullptr;
+  TACO_REQUIRE(!ad || (rowb && hx), "%s: the adapter form needs the rowb and hx tables", who);
+  TACO_REQUIRE(!ad || nl == 4, "%s: the adapter form has nl == 4, got %d", who, nl);
+  TACO_REQUIRE(!ad || (T > 0 && M % T == 0), "%s: T must be positive and divide M in the adapter form, got T = %d, M = %d", who, T, M);
+  const size_t f = sizeof(float), m = (size_t)M;
+  DoorOperands o;
+  o.in(x, m * HC * f, "x");
+  HighwayStackArgs a;
+  a.x = x; a.M = M; a.nl = nl; a.T = ad ? T : 0;
+  for (int l = 0; l < 4; ++l) {
+    const bool on = l < nl;
+    a.wt[l] = on ? wt[l] : nullptr; a.bt[l] = on ? bt[l] : nullptr; a.wh[l] = on ? wh[l] : nullptr; a.bh[l] = on ? bh[l] : nullptr;
+    a.th[l] = on && th ? th[l] : nullptr; a.y[l] = on ? y[l] : nullptr;
+    if (!on) continue;
+    o.in(a.wt[l], (size_t)HC * HC * f, "wt[%d]", l);
+    o.in(a.bt[l], HC * f, "bt[%d]", l);
+    o.in(a.wh[l], (size_t)HC * HC * f, "wh[%d]", l);
+    o.in(a.bh[l], HC * f, "bh[%d]", l);
+    if (th) o.out(a.th[l], m * 2 * HC * f, "th[%d]", l);
+    o.out(a.y[l], m * HC * f, "y[%d]", l);
+    if (ad) {
+      a.wa[l] = wa[l]; a.rowb[l] = rowb[l]; a.hx[l] = hx[l];
+      o.in(a.wa[l], (size_t)HC * HC * f, "wa[%d]", l);
+      o.in(a.rowb[l], (size_t)(M / T) * HC * f, "rowb[%d]", l);
+      o.out(a.hx[l], m * HC * f, "hx[%d]", l);
+    }
+  }
+  TACO_TRY(o.check(who));
+  return launch_highway_stack_fwd(a, as_stream(stream));
+}
+
+extern "C" int taco_debug_highway_stack_bwd(const float* g, const float* const* wT, const float* const* th, const float* const* x,
+                                            float* const* dth, float* gout, const float* const* waT, float* const* dhx, int M, int nl,
+                                            void* stream) {
+  const char* who = "taco_debug_highway_stack_bwd";
+  TACO_REQUIRE(M > 0 && M <= (1 << 24), "%s: M must be in [1, 2^24], got %d", who, M);
+  TACO_REQUIRE(nl >= 1 && nl <= 4, "%s: nl must be in [1, 4], got %d", who, nl);
+  TACO_REQUIRE(wT && th && x && dth, "%s: a null pointer table (wT, th, x, dth)", who);
+  const bool ad = waT != nullptr;
+  TACO_REQUIRE(!ad || dhx, "%s: the adapter form needs the dhx table", who);
+  TACO_REQUIRE(!ad || nl == 4, "%s: the adapter form has nl == 4, got %d", who, nl);
+  const size_t f = sizeof(float), m = (size_t)M;
+  DoorOperands o;
+  o.in(g, m * HC * f, "g");
+  o.out(gout, m * HC * f, "gout");
+  HighwayStackBwdArgs a;
+  a.g = g; a.gout = gout; a.M = M; a.nl = nl;
+  for (int l = 0; l < 4; ++l) {
+    const bool on = l < nl;
+    a.wT[l] = on ? wT[l] : nullptr; a.th[l] = on ? th[l] : nullptr; a.x[l] = on ? x[l] : nullptr; a.dth[l] = on ? dth[l] : nullptr;
+    if (!on) continue;
+    o.in(a.wT[l], (size_t)2 * HC * HC * f, "wT[%d]", l);
+    o.in(a.th[l], m * 2 * HC * f, "th[%d]", l);
+    o.in(a.x[l], m * HC * f, "x[%d]", l);
+    o.out(a.dth[l], m * 2 * HC * f, "dth[%d]", l);
+    if (ad) {
+      a.waT[l] = waT[l]; a.dhx[l] = dhx[l];
+      o.in(a.waT[l], (size_t)HC * HC * f, "waT[%d]", l);
+      o.out(a.dhx[l], m * HC * f, "dhx[%d]", l);
+    }
+  }
+  TACO_TRY(o.check(who));
+  return launch_highway_stack_bwd(a, as_stream(stream));
+}

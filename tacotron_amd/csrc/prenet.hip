@@ -261,3 +261,48 @@ int launch_prenet_bwd(const PrenetArgs& a, hipStream_t s) {
   TACO_LAUNCH_CHECK("prenet_bwd");
   return TACO_OK;
 }
+
+// ---- debug doors (include/taco_hip.h): the two launches alone, every field of PrenetArgs given by the caller ----
+extern "C" int taco_debug_prenet_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                     const uint8_t* keep1, const uint8_t* keep2, float* y1, float* y2, int M, void* stream) {
+  const char* who = "taco_debug_prenet_fwd";
+  TACO_REQUIRE(M > 0 && M <= (1 << 22), "%s: M must be in [1, 2^22], got %d", who, M);
+  const size_t f = sizeof(float), m = (size_t)M;
+  DoorOperands o;
+  o.in(x, m * kEmbed * f, "x");
+  o.in(w1, (size_t)kEmbed * kPre1 * f, "w1");
+  o.in_opt(b1, kPre1 * f, "b1");
+  o.in(w2, (size_t)kPre1 * kPre2 * f, "w2");
+  o.in_opt(b2, kPre2 * f, "b2");
+  o.in_opt(keep1, m * kPre1, "keep1");
+  o.in_opt(keep2, m * kPre2, "keep2");
+  o.out(y1, m * kPre1 * f, "y1");
+  o.out(y2, m * kPre2 * f, "y2");
+  TACO_TRY(o.check(who));
+  PrenetArgs a;
+  a.x = x; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.keep1 = keep1; a.keep2 = keep2; a.y1 = y1; a.y2 = y2; a.M = M;
+  return launch_prenet_fwd(a, as_stream(stream));
+}
+
+extern "C" int taco_debug_prenet_bwd(const float* dy2, const float* w2T, const float* w1T, const uint8_t* keep1, const uint8_t* keep2,
+                                     const float* y1_in, const float* y2_in, float* dz2, float* dz1, float* dx, int M, void* stream) {
+  const char* who = "taco_debug_prenet_bwd";
+  TACO_REQUIRE(M > 0 && M <= (1 << 22), "%s: M must be in [1, 2^22], got %d", who, M);
+  const size_t f = sizeof(float), m = (size_t)M;
+  DoorOperands o;
+  o.in(dy2, m * kPre2 * f, "dy2");
+  o.in(w2T, (size_t)kPre2 * kPre1 * f, "w2T");
+  o.in(w1T, (size_t)kPre1 * kEmbed * f, "w1T");
+  o.in_opt(keep1, m * kPre1, "keep1");
+  o.in_opt(keep2, m * kPre2, "keep2");
+  o.in(y1_in, m * kPre1 * f, "y1_in");
+  o.in(y2_in, m * kPre2 * f, "y2_in");
+  o.out(dz2, m * kPre2 * f, "dz2");
+  o.out(dz1, m * kPre1 * f, "dz1");
+  o.out(dx, m * kEmbed * f, "dx");
+  TACO_TRY(o.check(who));
+  PrenetArgs a;
+  a.x = dy2; a.x_out = dz2; a.y2_in = y2_in; a.y1_in = y1_in; a.keep2 = keep2; a.keep1 = keep1;
+  a.w1 = w2T; a.w2 = w1T; a.y1 = dz1; a.y2 = dx; a.M = M;
+  return launch_prenet_bwd(a, as_stream(stream));
+}

@@ -101,6 +101,12 @@ EXPORTS = {
     'taco_gemm_tn': (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'taco_debug_gemm_naive': (C.c_int, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'taco_bigru_fwd': (C.c_int, [_P] * 12 + [_I, _I, _P]),
+    'taco_debug_bigru_rec_fwd': (C.c_int, [_P] * 8 + [_I, _I, _P]),
+    'taco_debug_bigru_bwd': (C.c_int, [_P] * 11 + [_I, _I, _P]),
+    'taco_debug_highway_stack_fwd': (C.c_int, [_P] * 10 + [_I, _I, _I, _P]),
+    'taco_debug_highway_stack_bwd': (C.c_int, [_P] * 8 + [_I, _I, _P]),
+    'taco_debug_prenet_fwd': (C.c_int, [_P] * 9 + [_I, _P]),
+    'taco_debug_prenet_bwd': (C.c_int, [_P] * 10 + [_I, _P]),
     'taco_forward': (C.c_int, [_SH] + [_P] * 17),
     'taco_backward': (C.c_int, [_SH] + [_P] * 14),
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
@@ -289,6 +295,187 @@ def bigru_fwd(x, w, xg, out, ruc, B, T):
                                ptr(w['bw/gates/kernel']), ptr(w['bw/gates/bias']),
                                ptr(w['bw/candidate/kernel']), ptr(w['bw/candidate/bias']),
                                ptr(xg), ptr(out), ptr(ruc), B, T, stream_ptr()), 'taco_bigru_fwd')
+
+
+# ---- op-level debug doors of the CBHG tail (include/taco_hip.h; tests/test_gpu_cbhg_tail.py) ----
+DOOR_MAX_ROWS = 1 << 24          # B * T resp. M of the bi-GRU and highway doors
+DOOR_MAX_PRENET_ROWS = 1 << 22   # M of the pre-net doors
+
+
+def _disjoint(who, ins, outs):
+    """no output (name, tensor or None) may meet an input or another output"""
+    outs = [(n, t) for n, t in outs if t is not None]
+    ins = [(n, t) for n, t in ins if t is not None]
+    for i, (n_out, t_out) in enumerate(outs):
+        for n_in, t_in in ins + outs[i + 1:]:
+            no_overlap(who, n_in, t_in, n_out, t_out)
+
+
+def _layer_table(who, name, ts, nl, shape, dev, dtype=torch.float32):
+    """a list of nl tensors of one shape -> ([(name[l], tensor)], the table of 4 pointers the C ABI takes)"""
+    if not isinstance(ts, (list, tuple)) or len(ts) != nl:
+        raise ValueError('%s: %s must be a list of %d tensors (one per layer), got %s'
+                         % (who, name, nl, '%d' % len(ts) if isinstance(ts, (list, tuple)) else 'a %s' % type(ts).__name__))
+    named = [('%s[%d]' % (name, l), t) for l, t in enumerate(ts)]
+    for n, t in named:
+        tensor_arg(who, n, t, dtype, shape, dev)
+    return named, (C.c_void_p * 4)(*([t.data_ptr() for t in ts] + [None] * (4 - nl)))
+
+
+def debug_bigru_rec_fwd(xg, w, out, ruc=None, h0=None):
+    """The bi-GRU's forward recurrence alone (taco_debug_bigru_rec_fwd): xg (B, T, 768) the x-side pre-activations with their biases,
+    w the GRUCell kernels by the names bigru_fwd uses ('fw/gates/kernel' (256, 256), 'fw/candidate/kernel' (256, 128), 'bw/..'),
+    h0 (B, 128) or None -> out (B, T, 256), ruc (B, T, 768) or None, the caller's buffers."""
+    who = 'debug_bigru_rec_fwd'
+    B, T = tensor_arg(who, 'xg', xg, torch.float32, ('B', 'T', 768))
+    dev = xg.device
+    if B * T > DOOR_MAX_ROWS:
+        raise ValueError('%s: at most %d rows, got B * T = %d' % (who, DOOR_MAX_ROWS, B * T))
+    ws = []
+    for d in ('fw', 'bw'):
+        for part, cols in (('gates', 256), ('candidate', 128)):
+            k = '%s/%s/kernel' % (d, part)
+            tensor_arg(who, 'w[%r]' % k, w.get(k), torch.float32, (256, cols), dev)
+            ws.append(('w[%r]' % k, w[k]))
+    tensor_arg(who, 'h0', h0, torch.float32, (B, 128), dev, optional=True)
+    tensor_arg(who, 'out', out, torch.float32, (B, T, 256), dev)
+    tensor_arg(who, 'ruc', ruc, torch.float32, (B, T, 768), dev, optional=True)
+    _disjoint(who, [('xg', xg), ('h0', h0)] + ws, [('out', out), ('ruc', ruc)])
+    on_gpu(who, 'xg', dev)
+    _check(_lib.taco_debug_bigru_rec_fwd(ptr(xg), ptr(ws[0][1]), ptr(ws[1][1]), ptr(ws[2][1]), ptr(ws[3][1]), ptr(h0), ptr(out), ptr(ruc),
+                                         B, T, stream_ptr()), 'taco_debug_bigru_rec_fwd')
+
+
+def debug_bigru_bwd(dout, out, ruc, wT, dxg, rh, h0=None, dh0=None):
+    """The bi-GRU's backward recurrence alone (taco_debug_bigru_bwd): dout, out (B, T, 256), ruc (B, T, 768), wT the transposed h-side
+    kernels {'fw/wghT': (256, 128), 'fw/wchT': (128, 128), 'bw/..'}, h0 (B, 128) or None -> dxg (B, T, 768), rh (B, T, 256), dh0
+    (2, B, 128) or None, the caller's buffers."""
+    who = 'debug_bigru_bwd'
+    B, T = tensor_arg(who, 'dout', dout, torch.float32, ('B', 'T', 256))
+    dev = dout.device
+    if B * T > DOOR_MAX_ROWS:
+        raise ValueError('%s: at most %d rows, got B * T = %d' % (who, DOOR_MAX_ROWS, B * T))
+    tensor_arg(who, 'out', out, torch.float32, (B, T, 256), dev)
+    tensor_arg(who, 'ruc', ruc, torch.float32, (B, T, 768), dev)
+    ws = []
+    for d in ('fw', 'bw'):
+        for part, rows in (('wghT', 256), ('wchT', 128)):
+            k = '%s/%s' % (d, part)
+            tensor_arg(who, 'wT[%r]' % k, wT.get(k), torch.float32, (rows, 128), dev)
+            ws.append(('wT[%r]' % k, wT[k]))
+    tensor_arg(who, 'h0', h0, torch.float32, (B, 128), dev, optional=True)
+    tensor_arg(who, 'dxg', dxg, torch.float32, (B, T, 768), dev)
+    tensor_arg(who, 'rh', rh, torch.float32, (B, T, 256), dev)
+    tensor_arg(who, 'dh0', dh0, torch.float32, (2, B, 128), dev, optional=True)
+    _disjoint(who, [('dout', dout), ('out', out), ('ruc', ruc), ('h0', h0)] + ws, [('dxg', dxg), ('rh', rh), ('dh0', dh0)])
+    on_gpu(who, 'dout', dev)
+    _check(_lib.taco_debug_bigru_bwd(ptr(dout), ptr(out), ptr(ruc), ptr(ws[0][1]), ptr(ws[1][1]), ptr(ws[2][1]), ptr(ws[3][1]), ptr(h0),
+                                     ptr(dxg), ptr(rh), ptr(dh0), B, T, stream_ptr()), 'taco_debug_bigru_bwd')
+
+
+def debug_highway_stack_fwd(x, wt, bt, wh, bh, y, th=None, wa=None, rowb=None, hx=None, T=None):
+    """The highway stack's forward launch (taco_debug_highway_stack_fwd): x (M, 128); wt, bt, wh, bh, y (and th, or None: no stash)
+    lists of nl = len(y) tensors, nl in 1..4.  Adapter form: wa, rowb, hx lists of 4 and T, the rows per sequence."""
+    who = 'debug_highway_stack_fwd'
+    M, = tensor_arg(who, 'x', x, torch.float32, ('M', 128))
+    dev = x.device
+    if M > DOOR_MAX_ROWS:
+        raise ValueError('%s: at most %d rows, got M = %d' % (who, DOOR_MAX_ROWS, M))
+    nl = int_arg(who, 'nl (the length of y)', len(y) if isinstance(y, (list, tuple)) else None, 1, 4)
+    ins, outs, tabs = [('x', x)], [], {}
+    for name, ts, shape, is_out in (('wt', wt, (128, 128), 0), ('bt', bt, (128,), 0), ('wh', wh, (128, 128), 0), ('bh', bh, (128,), 0),
+                                    ('th', th, (M, 256), 1), ('y', y, (M, 128), 1)):
+        if ts is None and name == 'th':
+            tabs[name] = None
+            continue
+        named, tabs[name] = _layer_table(who, name, ts, nl, shape, dev)
+        (outs if is_out else ins).extend(named)
+    ad = wa is not None
+    if ad:
+        if nl != 4:
+            raise ValueError('%s: the adapter form has 4 layers, got nl = %d' % (who, nl))
+        T = int_arg(who, 'T', T, 1, M)
+        if M % T:
+            raise ValueError('%s: T must divide M, got T = %d, M = %d' % (who, T, M))
+        for name, ts, shape, is_out in (('wa', wa, (128, 128), 0), ('rowb', rowb, (M // T, 128), 0), ('hx', hx, (M, 128), 1)):
+            named, tabs[name] = _layer_table(who, name, ts, 4, shape, dev)
+            (outs if is_out else ins).extend(named)
+    elif rowb is not None or hx is not None:
+        raise ValueError('%s: rowb and hx belong to the adapter form, which wa selects' % who)
+    _disjoint(who, ins, outs)
+    on_gpu(who, 'x', dev)
+    _check(_lib.taco_debug_highway_stack_fwd(ptr(x), tabs['wt'], tabs['bt'], tabs['wh'], tabs['bh'], tabs['th'], tabs['y'], tabs.get('wa'),
+                                             tabs.get('rowb'), tabs.get('hx'), M, nl, T if ad else 0, stream_ptr()),
+           'taco_debug_highway_stack_fwd')
+
+
+def debug_highway_stack_bwd(g, wT, th, x, dth, gout, waT=None, dhx=None):
+    """The highway stack's backward launch (taco_debug_highway_stack_bwd): g (M, 128); wT (256, 128), th (M, 256), x (M, 128), dth
+    (M, 256) lists of nl = len(dth) tensors; gout (M, 128).  Adapter form: waT (128, 128), dhx (M, 128) lists of 4."""
+    who = 'debug_highway_stack_bwd'
+    M, = tensor_arg(who, 'g', g, torch.float32, ('M', 128))
+    dev = g.device
+    if M > DOOR_MAX_ROWS:
+        raise ValueError('%s: at most %d rows, got M = %d' % (who, DOOR_MAX_ROWS, M))
+    nl = int_arg(who, 'nl (the length of dth)', len(dth) if isinstance(dth, (list, tuple)) else None, 1, 4)
+    tensor_arg(who, 'gout', gout, torch.float32, (M, 128), dev)
+    ins, outs, tabs = [('g', g)], [('gout', gout)], {}
+    for name, ts, shape, is_out in (('wT', wT, (256, 128), 0), ('th', th, (M, 256), 0), ('x', x, (M, 128), 0), ('dth', dth, (M, 256), 1)):
+        named, tabs[name] = _layer_table(who, name, ts, nl, shape, dev)
+        (outs if is_out else ins).extend(named)
+    if waT is not None:
+        if nl != 4:
+            raise ValueError('%s: the adapter form has 4 layers, got nl = %d' % (who, nl))
+        for name, ts, shape, is_out in (('waT', waT, (128, 128), 0), ('dhx', dhx, (M, 128), 1)):
+            named, tabs[name] = _layer_table(who, name, ts, 4, shape, dev)
+            (outs if is_out else ins).extend(named)
+    elif dhx is not None:
+        raise ValueError('%s: dhx belongs to the adapter form, which waT selects' % who)
+    _disjoint(who, ins, outs)
+    on_gpu(who, 'g', dev)
+    _check(_lib.taco_debug_highway_stack_bwd(ptr(g), tabs['wT'], tabs['th'], tabs['x'], tabs['dth'], ptr(gout), tabs.get('waT'),
+                                             tabs.get('dhx'), M, nl, stream_ptr()), 'taco_debug_highway_stack_bwd')
+
+
+def debug_prenet_fwd(x, w1, b1, w2, b2, y1, y2, keep1=None, keep2=None):
+    """The encoder pre-net's forward launch (taco_debug_prenet_fwd): x (M, 256), w1 (256, 256), b1 (256), w2 (256, 128), b2 (128), keep1
+    (M, 256) / keep2 (M, 128) uint8 or None -> y1 (M, 256), y2 (M, 128), the caller's buffers."""
+    who = 'debug_prenet_fwd'
+    M, = tensor_arg(who, 'x', x, torch.float32, ('M', 256))
+    dev = x.device
+    if M > DOOR_MAX_PRENET_ROWS:
+        raise ValueError('%s: at most %d rows, got M = %d' % (who, DOOR_MAX_PRENET_ROWS, M))
+    ins = [('x', x), ('w1', w1), ('b1', b1), ('w2', w2), ('b2', b2), ('keep1', keep1), ('keep2', keep2)]
+    shapes = {'w1': (256, 256), 'b1': (256,), 'w2': (256, 128), 'b2': (128,), 'keep1': (M, 256), 'keep2': (M, 128)}
+    for name, t in ins[1:]:
+        tensor_arg(who, name, t, torch.uint8 if name.startswith('keep') else torch.float32, shapes[name], dev, optional=name[0] in 'bk')
+    tensor_arg(who, 'y1', y1, torch.float32, (M, 256), dev)
+    tensor_arg(who, 'y2', y2, torch.float32, (M, 128), dev)
+    _disjoint(who, ins, [('y1', y1), ('y2', y2)])
+    on_gpu(who, 'x', dev)
+    _check(_lib.taco_debug_prenet_fwd(ptr(x), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(keep1), ptr(keep2), ptr(y1), ptr(y2), M, stream_ptr()),
+           'taco_debug_prenet_fwd')
+
+
+def debug_prenet_bwd(dy2, w2T, w1T, y1_in, y2_in, dz2, dz1, dx, keep1=None, keep2=None):
+    """The encoder pre-net's backward launch (taco_debug_prenet_bwd): dy2 (M, 128), w2T (128, 256), w1T (256, 256), the forward's y1_in
+    (M, 256) and y2_in (M, 128), the keep masks or None -> dz2 (M, 128), dz1 (M, 256), dx (M, 256), the caller's buffers."""
+    who = 'debug_prenet_bwd'
+    M, = tensor_arg(who, 'dy2', dy2, torch.float32, ('M', 128))
+    dev = dy2.device
+    if M > DOOR_MAX_PRENET_ROWS:
+        raise ValueError('%s: at most %d rows, got M = %d' % (who, DOOR_MAX_PRENET_ROWS, M))
+    ins = [('dy2', dy2), ('w2T', w2T), ('w1T', w1T), ('y1_in', y1_in), ('y2_in', y2_in), ('keep1', keep1), ('keep2', keep2)]
+    shapes = {'w2T': (128, 256), 'w1T': (256, 256), 'y1_in': (M, 256), 'y2_in': (M, 128), 'keep1': (M, 256), 'keep2': (M, 128)}
+    for name, t in ins[1:]:
+        tensor_arg(who, name, t, torch.uint8 if name.startswith('keep') else torch.float32, shapes[name], dev, optional=name[0] == 'k')
+    outs = [('dz2', dz2), ('dz1', dz1), ('dx', dx)]
+    for (name, t), cols in zip(outs, (128, 256, 256)):
+        tensor_arg(who, name, t, torch.float32, (M, cols), dev)
+    _disjoint(who, ins, outs)
+    on_gpu(who, 'dy2', dev)
+    _check(_lib.taco_debug_prenet_bwd(ptr(dy2), ptr(w2T), ptr(w1T), ptr(keep1), ptr(keep2), ptr(y1_in), ptr(y2_in), ptr(dz2), ptr(dz1),
+                                      ptr(dx), M, stream_ptr()), 'taco_debug_prenet_bwd')
 
 
 def forward(shape, params, text, text_length, mel, stft, masks, s2s, out, align, loss, workspace, speaker=None):
