@@ -463,7 +463,7 @@ int taco_denorm_unframe(const float* output, const float* stft_mean, const float
  * frames_out, out overlapping mag_t, B, C, F or Fo <= 0, F or Fo > TACO_STRETCH_MAX_FRAMES and frames_per_unit < 1 return
  * TACO_EINVAL, with a message that names the argument, before anything is enqueued.  TACO_VERSION did not change with this entry
  * point: detect it by the symbol.
- * Not here: a rate that varies inside an utterance, interpolation of log-magnitudes or of mel frames.  Nobody has listened to the result: the
+ * Not here: interpolation of log-magnitudes or of mel frames (a rate that varies inside an utterance: taco_frames_stretch_curve).  Nobody has listened to the result: the
  * limits 0.25 and 4 are bounds of the arithmetic ((frame << 16) and j * s_b stay inside 31 bits), not recommendations. */
 #define TACO_STRETCH_ONE        65536     /* step_q of rate 1 */
 #define TACO_STRETCH_MIN_STEP   16384     /* rate 0.25: four times slower */
@@ -505,7 +505,7 @@ int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_pe
  * mag_t, B or F <= 0, F > TACO_STRETCH_MAX_FRAMES, C - 1 not a power of two in 8 .. 1024, lifter out of range and
  * frames_per_unit < 1 return TACO_EINVAL, with a message that names the argument, before anything is enqueued.  TACO_VERSION did
  * not change with this entry point: detect it by the symbol.
- * Not here: a tapered or caller-supplied lifter, a pitch contour inside an utterance, mel frames.  Nobody has listened to the
+ * Not here: a tapered or caller-supplied lifter, mel frames (a pitch contour inside an utterance: taco_frames_pitch_curve).  Nobody has listened to the
  * result: the default lifter of the Python layer (32: quefrencies up to 2 ms at 16 kHz) is untuned, and the limits of +-12
  * semitones are bounds of the arithmetic (k * s_b <= 2^27), not recommendations. */
 #define TACO_PITCH_ONE        65536     /* step_q of 0 semitones */
@@ -515,6 +515,61 @@ int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_pe
 #define TACO_PITCH_FLOOR      1e-8f     /* audio.py:59 */
 int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
                       float* out, int B, int C, int F, void* stream);
+
+/* Prosody inside an utterance (no reference counterpart): the two controls above with one value per FRAME instead of one per row, and
+ * the gather that makes such curves from per-character values along the path of taco_alignment_path -- which decoder step speaks
+ * which character is the anchor a per-word rate or pitch needs.  Each is one or two plain launches on the caller's stream: no
+ * workspace, no allocation, no atomics, nothing read back by the host, graph-capturable, and a replay follows whatever the device
+ * buffers hold at replay time.  Refusals return TACO_EINVAL with a message that names the argument, before anything is enqueued.
+ * TACO_VERSION did not change with these entry points: detect them by the symbol.
+ *
+ * taco_path_curve: per-character values -> a per-frame curve.
+ *   path   (B, Td) int32 as taco_alignment_path writes it (-1 behind the row's steps); values (B, Tt) int32; both on the DEVICE
+ *   curve  (B, Td * frames_per_step) int32, every element written:
+ *          curve[b, t * frames_per_step + u] = values[b, path[b, t]] when 0 <= path[b, t] < Tt, else `fill`
+ *   A pure gather, exact; no clamping -- the consumers clamp.  One launch.  Any NULL pointer, B, Td, Tt or frames_per_step < 1 and
+ *   Td * frames_per_step > TACO_STRETCH_MAX_FRAMES are refused.
+ *
+ * taco_frames_stretch_curve: a rate that varies along the utterance.  mag_t, frames, frames_per_unit, out, frames_out, B, C, F, Fo and
+ * F_b exactly as taco_frames_stretch.
+ *   dur_q (B, F) int32 on the DEVICE, or NULL: the output frames source frame i lasts, in units of 2^-16 -- the inverse sense of
+ *          step_q, because durations add and steps do not.  Used as d_i = clamp(dur_q[b, i], TACO_STRETCH_MIN_STEP,
+ *          TACO_STRETCH_MAX_STEP) (16384: rate 4; 262144: rate 0.25); NULL: 65536 everywhere.  Never read by the host
+ *   src   (B, Fo) int32, required: the time map, an OUTPUT (the timings place word boundaries in the stretched audio with it)
+ * Per row b, all in integers:
+ *   D_0 = 0, D_{i+1} = D_i + d_i  (D reaches 2^31 at F = 8192 with every d_i = 262144: unsigned 32 bits hold it, signed do not)
+ *   Fo_b = 0 when F_b == 0, else min(Fo, (D_{F_b - 1} >> 16) + 1);  frames_out[b] = Fo_b
+ *   for j < Fo_b: q = j << 16, i = the largest index <= F_b - 1 with D_i <= q, wq = ((q - D_i) << 16) / d_i in 64-bit integer
+ *     division (0 <= wq < 65536), w = wq 2^-16;  src[b, j] = (i << 16) | wq
+ *     wq == 0: out[b, k, j] = mag_t[b, k, i] bit for bit, and frame i + 1 is NOT read
+ *     else:    out[b, k, j] = a + (w * (c - a)), a = mag_t[b, k, i], c = mag_t[b, k, i + 1]: the three separately rounded fp32
+ *              operations of taco_frames_stretch
+ *   src[b, j] = -1 and out[b, k, j] = +0 for Fo_b <= j < Fo
+ * Fo_b's formula gives q <= D_{F_b - 1}: i = F_b - 1 occurs only with wq == 0, and nothing behind a row's end is read.  src rises
+ * strictly along a row.  With a constant d of 16384, 32768, 65536, 131072 or 262144 the map, Fo_b and hence every bit of out equal
+ * taco_frames_stretch at step 262144, 131072, 65536, 32768, 16384; other constants quantise the weight differently and no equality is
+ * claimed.  The guarantees of taco_frames_stretch carry over: every element of out, frames_out and src is written and nothing
+ * outside them, any 4-byte alignment, columns behind F_b and other rows have no influence (they may hold NaN), row b of a B-row
+ * call equals the call on that row alone.  Two launches: the map (one workgroup per row: the scan of d in LDS, a binary search and
+ * the one division per output frame), then taco_frames_stretch's gather reading positions from src.  The refusals of
+ * taco_frames_stretch, and NULL src.
+ *
+ * taco_frames_pitch_curve: a pitch contour.  Everything as taco_frames_pitch, but
+ *   step_q (B, F) int32 on the DEVICE, or NULL: frame f of row b uses s = clamp(step_q[b, f], TACO_PITCH_MIN_STEP,
+ *          TACO_PITCH_MAX_STEP); NULL: TACO_PITCH_ONE
+ * and because the bits of a frame depend on its own C bins, its step and Q alone: frame f has exactly the bits of the same frame in a
+ * taco_frames_pitch call whose row step is s; a frame at TACO_PITCH_ONE is its input bit for bit, also next to shifted frames (no
+ * log / exp round trip); +0 behind F_b.  One launch, the kernel of taco_frames_pitch with the step per lane; the lifter path
+ * depends on Q alone.
+ *
+ * Not here: ramps across word boundaries (a word's characters share one value, the curve steps at its edges), long prompts split
+ * into pieces (--long: the pieces re-index words), mel frames.  Nobody has listened to the result. */
+int taco_path_curve(const int32_t* path, const int32_t* values, int frames_per_step, int32_t fill, int32_t* curve, int B, int Td,
+                    int Tt, void* stream);
+int taco_frames_stretch_curve(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* dur_q, float* out,
+                              int32_t* frames_out, int32_t* src, int B, int C, int F, int Fo, void* stream);
+int taco_frames_pitch_curve(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                            float* out, int B, int C, int F, void* stream);
 
 /* F0 tracker (no reference counterpart): the per-frame pitch of magnitude frames, measured where the two prosody controls above
  * run -- the instrument that stands in for listening to them.  By Wiener-Khinchin the cosine transform of a frame's power spectrum is

@@ -5,7 +5,12 @@ without axes (`attention_png`).  NumPy, zlib and struct only: a picture of Td x 
 Timings (`char_steps`, `step_samples`, `word_times`): the arithmetic that turns the per-character durations of lib.alignment_path
 into seconds of the file a prompt was written to.  RESOLUTION: the r-frame layout (audio.reshape_frames) interleaves the frames of
 the 4 decoder steps of a block, so a boundary is exact at multiples of 4 steps and nominal (frame r t) inside a block: the blur is
-up to one block, 4 r frames = 150 ms at r = 2 and 16 kHz.  Good enough for subtitles; this is not a phonetic aligner."""
+up to one block, 4 r frames = 150 ms at r = 2 and 16 kHz.  Good enough for subtitles; this is not a phonetic aligner.
+Behind a rate that varies inside the utterance (lib.frames_stretch_curve) a boundary goes through the time map `src` of that call:
+source frame r t becomes the first output frame at or behind it, which adds a resolution of one output frame (18.75 ms) on top.
+
+Prosody (`word_values`): one value per encoded character from one value per word -- the `values` that lib.path_curve spreads along the
+path."""
 from __future__ import annotations
 
 import struct
@@ -121,13 +126,23 @@ def char_steps(dur):
     return end - d, end
 
 
-def step_samples(t, r, step_q=None, trim=None, offset=0, total=None):
+def step_samples(t, r, step_q=None, trim=None, offset=0, total=None, src=None):
     """Decoder step(s) t -> sample position(s) in the written file, float64.  Step t sits at source frame r t and at sample 300 r t;
     with a rate (step_q: the Q16 step of lib.frames_stretch, 65536 the model's own) the frame becomes r t 65536 / step_q.  trim = (s, e)
     of a finished waveform (prompt_NNN_trim.npy): s is subtracted and the result clipped to [0, e - s]; without finishing the result is
     clipped to [0, total], total the 300 (frames - 1) samples the file holds (None: unclipped).  offset: where the piece starts in a
-    joined file (--long), added last.  Nominal inside a block of 4 steps: see the module's note on resolution."""
+    joined file (--long), added last.  Nominal inside a block of 4 steps: see the module's note on resolution.
+    src: the time map of one row of lib.frames_stretch_curve cut to its Fo_b entries ((i << 16) | wq, rising strictly), in place of
+    step_q: source frame r t becomes output frame searchsorted(src, (r t) << 16), the first output frame at or behind it (Fo_b
+    for a step behind the row's end) -- a resolution of one output frame."""
+    if src is not None and step_q is not None:
+        raise ValueError('step_samples: give step_q (one rate) or src (a time map), not both')
     frame = np.asarray(t, dtype=np.float64) * int(r)
+    if src is not None:
+        m = np.asarray(src, dtype=np.int64).reshape(-1)
+        if (m < 0).any() or (np.diff(m) <= 0).any():
+            raise ValueError('step_samples: src must be the first Fo_b entries of a time map: non-negative and rising strictly')
+        frame = np.searchsorted(m, (np.asarray(t, dtype=np.int64) * int(r)) << 16).astype(np.float64)
     if step_q is not None:
         frame = frame * 65536.0 / int(step_q)
     x = frame * HOP
@@ -145,17 +160,8 @@ def encoded_chars(line, ivocab):
     return [w for w in line.strip() if w in known]
 
 
-def word_times(line, ivocab, dur, r, step_q=None, trim=None, offset=0, total=None, sr=SR):
-    """[(start_s, end_s, word)] of one prompt (or one piece of a --long prompt): `dur` its per-character steps (lib.alignment_path; entry
-    i belongs to encoded character i -- text_length also counts the newline and the dropped characters, so dur may be longer than the
-    encoded text and the surplus is ignored; a shorter dur counts as 0 steps for the rest).  A word is a maximal run of encoded
-    non-space characters, punctuation attached; it starts with the first step of its first character and ends with the last step of
-    its last one (char_steps), mapped to seconds by step_samples(...) / sr.  A word whose characters were all skipped has start == end."""
-    chars = encoded_chars(line, ivocab)
-    d = np.zeros(len(chars), dtype=np.int64)
-    given = np.asarray(dur, dtype=np.int64).reshape(-1)[:len(chars)]
-    d[:len(given)] = given
-    start, end = char_steps(d)
+def word_spans(chars):
+    """[(i, j)] of the words of a list of characters: maximal runs of non-space characters, i .. j inclusive"""
     out, i = [], 0
     while i < len(chars):
         if chars[i] == ' ':
@@ -164,9 +170,43 @@ def word_times(line, ivocab, dur, r, step_q=None, trim=None, offset=0, total=Non
         j = i
         while j + 1 < len(chars) and chars[j + 1] != ' ':
             j += 1
-        a, b = step_samples([start[i], end[j]], r, step_q, trim, offset, total) / float(sr)
-        out.append((float(a), float(b), ''.join(chars[i:j + 1])))
+        out.append((i, j))
         i = j + 1
+    return out
+
+
+def word_values(line, ivocab, per_word, base):
+    """One value per encoded character of a prompt from one value per word: per_word {word index: value}, words as word_times
+    defines them (0-based, maximal runs of encoded non-space characters, punctuation attached).  The characters of a listed word
+    take its value; spaces, the words not listed and everything behind the text take `base` (the caller pads with it).
+    ValueError for a word index the prompt does not have.  -> (list of len(encoded_chars) values, the number of words)"""
+    chars = encoded_chars(line, ivocab)
+    spans = word_spans(chars)
+    out = [base] * len(chars)
+    for w, v in per_word.items():
+        if isinstance(w, bool) or int(w) != w or not 0 <= int(w) < len(spans):
+            raise ValueError('word_values: word %r: the prompt has the words 0 .. %d' % (w, len(spans) - 1))
+        i, j = spans[int(w)]
+        out[i:j + 1] = [v] * (j + 1 - i)
+    return out, len(spans)
+
+
+def word_times(line, ivocab, dur, r, step_q=None, trim=None, offset=0, total=None, sr=SR, src=None):
+    """[(start_s, end_s, word)] of one prompt (or one piece of a --long prompt): `dur` its per-character steps (lib.alignment_path; entry
+    i belongs to encoded character i -- text_length also counts the newline and the dropped characters, so dur may be longer than the
+    encoded text and the surplus is ignored; a shorter dur counts as 0 steps for the rest).  A word is a maximal run of encoded
+    non-space characters, punctuation attached; it starts with the first step of its first character and ends with the last step of
+    its last one (char_steps), mapped to seconds by step_samples(...) / sr.  A word whose characters were all skipped has start == end.
+    src: the row's time map behind lib.frames_stretch_curve, cut to Fo_b entries (step_samples), in place of step_q."""
+    chars = encoded_chars(line, ivocab)
+    d = np.zeros(len(chars), dtype=np.int64)
+    given = np.asarray(dur, dtype=np.int64).reshape(-1)[:len(chars)]
+    d[:len(given)] = given
+    start, end = char_steps(d)
+    out = []
+    for i, j in word_spans(chars):
+        a, b = step_samples([start[i], end[j]], r, step_q, trim, offset, total, src) / float(sr)
+        out.append((float(a), float(b), ''.join(chars[i:j + 1])))
     return out
 
 

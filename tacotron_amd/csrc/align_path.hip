@@ -327,7 +327,41 @@ bool launch_path_wave(int NL, size_t lds, hipStream_t s, const float* align, con
   }
 }
 
+// ---- taco_path_curve --------------------------------------------------------------------------------------------------------------
+// Per-character values along the path: curve[b, t r + u] = values[b, path[b, t]], `fill` where the path names no character of the
+// row (-1 behind the row's steps, or an index >= Tt).  A pure gather, one element per thread, the r frames of a step next to each
+// other: stores are contiguous, the loads of r neighbouring lanes hit one address.
+__global__ __launch_bounds__(256) void path_curve_kernel(const int32_t* __restrict__ path, const int32_t* __restrict__ values, int r,
+                                                          int32_t fill, int32_t* __restrict__ curve, int64_t total, int Td, int Tt) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;   // = (b Td + t) r + u
+  if (e >= total) return;
+  const int64_t step = e / r;
+  const int64_t b = step / Td;
+  const int s = path[step];
+  curve[e] = (s >= 0 && s < Tt) ? values[b * Tt + s] : fill;
+}
+
 }  // namespace
+
+extern "C" int taco_path_curve(const int32_t* path, const int32_t* values, int frames_per_step, int32_t fill, int32_t* curve, int B, int Td,
+                               int Tt, void* stream) {
+  TACO_REQUIRE(path, "path_curve: path is NULL");
+  TACO_REQUIRE(values, "path_curve: values is NULL");
+  TACO_REQUIRE(curve, "path_curve: curve is NULL");
+  TACO_REQUIRE(B > 0, "path_curve: B=%d must be positive", B);
+  TACO_REQUIRE(Td > 0, "path_curve: Td=%d must be positive", Td);
+  TACO_REQUIRE(Tt > 0, "path_curve: Tt=%d must be positive", Tt);
+  TACO_REQUIRE(frames_per_step >= 1, "path_curve: frames_per_step=%d must be >= 1", frames_per_step);
+  TACO_REQUIRE((int64_t)Td * frames_per_step <= TACO_STRETCH_MAX_FRAMES, "path_curve: Td=%d x frames_per_step=%d is above the %d frames of a curve",
+               Td, frames_per_step, TACO_STRETCH_MAX_FRAMES);
+  const int64_t total = (int64_t)B * Td * frames_per_step;   // (< 2^31 * 2^13)
+  const int64_t blocks = (total + 255) / 256;
+  TACO_REQUIRE(blocks <= 0x7fffffff, "path_curve: B=%d x Td=%d x frames_per_step=%d needs more than 2^31 workgroups", B, Td, frames_per_step);
+  hipStream_t s = as_stream(stream);
+  TACO_KLAUNCH(path_curve_kernel, dim3((unsigned)blocks), dim3(256), 0, s, path, values, frames_per_step, fill, curve, total, Td, Tt);
+  TACO_LAUNCH_CHECK("path_curve");
+  return TACO_OK;
+}
 
 extern "C" int64_t taco_alignment_path_workspace_bytes(int B, int Td, int Tt) {
   if (!path_shape_ok(B, Td, Tt)) return TACO_EINVAL;

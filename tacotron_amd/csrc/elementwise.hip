@@ -585,8 +585,13 @@ __global__ void denorm_unframe_kernel(const float* __restrict__ out, const float
 // profiles/frames_stretch_store_forms.txt): a thread owning frames j0 + 4 lane .. + 3 spreads each load of a wave over 1 KiB and
 // was up to 2 x slower; this form's values turned through LDS into one 16-byte store per thread was equal within the spread.  The
 // source span is not staged in LDS: that variant was not built.
+//
+// taco_frames_stretch_curve (a rate that varies along the utterance) is the same gather behind another time map: MAP = true reads
+// the packed position (i << 16) | wq of output frame j from the map frames_stretch_map_kernel (below) left in `step_q` (B, Fo) and
+// Fo_b from frames_out, instead of forming j * s_b; everything from the index and the weight on is the one body.
 constexpr int kStretchBins = 16;
 constexpr int kStretchSpan = 256;
+template <bool MAP>
 __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
                                                              int frames_per_unit, const int32_t* __restrict__ step_q,
                                                              float* __restrict__ out, int32_t* __restrict__ frames_out, int C, int F,
@@ -597,23 +602,29 @@ __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __rest
   const uint32_t t = x / (uint32_t)nspan;
   const int tile = (int)(t % (uint32_t)ntile), b = (int)(t / (uint32_t)ntile);
   int Fb = F, s = TACO_STRETCH_ONE;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  if (step_q) {
-    s = step_q[b];
-    s = s < TACO_STRETCH_MIN_STEP ? TACO_STRETCH_MIN_STEP : (s > TACO_STRETCH_MAX_STEP ? TACO_STRETCH_MAX_STEP : s);
-  }
   int Fob = 0;
-  if (Fb > 0) {
-    const uint32_t need = ((uint32_t)(Fb - 1) << 16) / (uint32_t)s + 1u;   // (Fb <= 8192: the shift stays below 2^29)
-    Fob = need > (uint32_t)Fo ? Fo : (int)need;
+  if constexpr (MAP) {   // the map kernel, earlier on the stream, wrote Fo_b and the positions: frames is not read again
+    Fob = frames_out[b];
+    Fob = Fob < 0 ? 0 : (Fob > Fo ? Fo : Fob);
+    Fob = __builtin_amdgcn_readfirstlane(Fob);
+  } else {
+    if (frames) {
+      const int64_t n = (int64_t)frames[b] * frames_per_unit;
+      Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+    }
+    if (step_q) {
+      s = step_q[b];
+      s = s < TACO_STRETCH_MIN_STEP ? TACO_STRETCH_MIN_STEP : (s > TACO_STRETCH_MAX_STEP ? TACO_STRETCH_MAX_STEP : s);
+    }
+    if (Fb > 0) {
+      const uint32_t need = ((uint32_t)(Fb - 1) << 16) / (uint32_t)s + 1u;   // (Fb <= 8192: the shift stays below 2^29)
+      Fob = need > (uint32_t)Fo ? Fo : (int)need;
+    }
+    Fb = __builtin_amdgcn_readfirstlane(Fb);
+    s = __builtin_amdgcn_readfirstlane(s);
+    Fob = __builtin_amdgcn_readfirstlane(Fob);
+    if (span == 0 && tile == 0 && threadIdx.x == 0 && threadIdx.y == 0) frames_out[b] = Fob;
   }
-  Fb = __builtin_amdgcn_readfirstlane(Fb);
-  s = __builtin_amdgcn_readfirstlane(s);
-  Fob = __builtin_amdgcn_readfirstlane(Fob);
-  if (span == 0 && tile == 0 && threadIdx.x == 0 && threadIdx.y == 0) frames_out[b] = Fob;
 
   const int j0 = span * kStretchSpan, lane = threadIdx.x;
   const int k0 = tile * kStretchBins;
@@ -624,10 +635,13 @@ __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __rest
     jj[u] = j0 + lane + 64 * u;
     // j < Fo_b: p <= (F_b - 1) << 16, so i <= F_b - 1, and i == F_b - 1 only with w == 0 -- i1 then stays i.  j >= Fo_b: frame 0 is
     // named and nothing is loaded (j < 8192 and s <= 2^18: the product fits 32 bits either way)
-    const uint32_t p = jj[u] < Fob ? (uint32_t)jj[u] * (uint32_t)s : 0u;
+    uint32_t p;
+    if constexpr (MAP) p = jj[u] < Fob ? (uint32_t)step_q[(int64_t)b * Fo + jj[u]] : 0u;   // (>= 0 below Fo_b: i < 8192)
+    else p = jj[u] < Fob ? (uint32_t)jj[u] * (uint32_t)s : 0u;
     const uint32_t frac = p & 0xFFFFu;
     i0[u] = (int)(p >> 16);
     i1[u] = i0[u] + (frac != 0u ? 1 : 0);
+    if constexpr (MAP) i0[u] = min(i0[u], F - 1), i1[u] = min(i1[u], F - 1);   // (the map names frames below F_b; the bounds do not rest on it)
     w[u] = (float)frac * (1.0f / 65536.0f);   // exact: 16 bits times a power of two
   }
   const bool live = j0 < Fob;   // (uniform over the workgroup)
@@ -661,6 +675,78 @@ __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __rest
   }
 }
 
+// The time map of taco_frames_stretch_curve: source frame i of row b lasts d_i = clamp(dur_q[b, i]) output frames in units of 2^-16,
+// D_i = d_0 + .. + d_{i-1} is where it starts, and output frame j sits in the source frame i with D_i <= j << 16 < D_{i+1}, at the
+// fraction wq = ((q - D_i) << 16) / d_i of it (include/taco_hip.h has the definition).  All integers: D reaches 2^31 at F = 8192 and
+// d = 2^18, so it is unsigned.  One workgroup of 1024 threads per row: a thread sums its ceil(F_b / 1024) <= 8 consecutive durations,
+// the 1024 sums are scanned in LDS, the thread writes its D_i (32 KB at F = 8192); then a thread per output frame finds i by binary
+// search in LDS -- 13 probes -- and does the one 64-bit division.  B workgroups on 256 CUs is no way to fill the chip; the call is a
+// few microseconds in front of a gather that is bound by memory, and the map is an output the timings need anyway.
+constexpr int kMapThreads = 1024;
+__device__ __forceinline__ uint32_t stretch_dur(const int32_t* __restrict__ dq, int i) {
+  int d = dq ? dq[i] : TACO_STRETCH_ONE;
+  d = d < TACO_STRETCH_MIN_STEP ? TACO_STRETCH_MIN_STEP : (d > TACO_STRETCH_MAX_STEP ? TACO_STRETCH_MAX_STEP : d);
+  return (uint32_t)d;
+}
+__global__ __launch_bounds__(kMapThreads) void frames_stretch_map_kernel(const int32_t* __restrict__ frames, int frames_per_unit,
+                                                                         const int32_t* __restrict__ dur_q,
+                                                                         int32_t* __restrict__ frames_out, int32_t* __restrict__ src, int F,
+                                                                         int Fo) {
+  __shared__ uint32_t D[TACO_STRETCH_MAX_FRAMES];
+  __shared__ uint32_t part[kMapThreads];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int Fb = F;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  src += (int64_t)b * Fo;
+  if (Fb == 0) {   // (uniform)
+    for (int j = tid; j < Fo; j += kMapThreads) src[j] = -1;
+    if (tid == 0) frames_out[b] = 0;
+    return;
+  }
+  const int32_t* __restrict__ dq = dur_q ? dur_q + (int64_t)b * F : nullptr;   // (columns behind F_b are never read)
+  const int per = (Fb + kMapThreads - 1) / kMapThreads, i0 = tid * per;
+  uint32_t sum = 0;
+  for (int u = 0; u < per; ++u)
+    if (i0 + u < Fb) sum += stretch_dur(dq, i0 + u);
+  part[tid] = sum;
+  __syncthreads();
+  for (int off = 1; off < kMapThreads; off <<= 1) {   // inclusive scan of the threads' sums (at most 2^31 in all: no wrap)
+    const uint32_t v = tid >= off ? part[tid - off] : 0u;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[tid] - sum;
+  for (int u = 0; u < per; ++u)
+    if (i0 + u < Fb) {
+      D[i0 + u] = run;
+      run += stretch_dur(dq, i0 + u);
+    }
+  __syncthreads();
+  const uint32_t need = (D[Fb - 1] >> 16) + 1u;
+  const int Fob = need > (uint32_t)Fo ? Fo : (int)need;
+  if (tid == 0) frames_out[b] = Fob;
+  for (int j = tid; j < Fo; j += kMapThreads) {
+    int v = -1;
+    if (j < Fob) {
+      const uint32_t q = (uint32_t)j << 16;   // (j < 8192) q <= D[F_b - 1]: the search ends on F_b - 1 only with q == D there
+      int lo = 0, hi = Fb - 1;
+      while (lo < hi) {   // the largest i with D[i] <= q; D[0] = 0 and D rises strictly
+        const int mid = (lo + hi + 1) >> 1;
+        if (D[mid] <= q) lo = mid;
+        else hi = mid - 1;
+      }
+      const uint32_t wq = (uint32_t)(((uint64_t)(q - D[lo]) << 16) / stretch_dur(dq, lo));   // (q - D_i < d_i: wq < 65536)
+      v = (lo << 16) | (int)(wq & 0xFFFFu);
+    }
+    src[j] = v;
+  }
+}
+
 // taco_frames_pitch: pitch at synthesis.  A frame's log-magnitudes L[k] are split into a log-envelope E (the cepstrum of the even
 // extension, quefrencies 0 .. Q kept) and a log-excitation R = L - E; R alone is warped along the bin axis by s_b (2^-16 source bins
 // per output bin) and put back under the unmoved envelope: out = exp(E[k] + R'[k]) (include/taco_hip.h has the definition).
@@ -683,7 +769,13 @@ __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __rest
 constexpr int kPitchFrames = 32;
 constexpr int kPitchMaxC = 1025;
 constexpr int kPitchBatch = 8;         // bins a thread has in flight in the copy and in the warp
-template <int NB, int kPitchWaves>
+//
+// taco_frames_pitch_curve (a pitch contour) is CURVE = true: step_q is (B, F) and the step belongs to the frame, that is to the lane
+// (its low five bits), so s is a per-lane register from here on and costs no LDS.  The cepstrum and the envelope do not know s; the
+// warp's k * s >> 16 takes it per lane.  The copy branch is taken when all 32 frames of the tile are at ONE or behind F_b -- every
+// wave holds the same 32 frames in both halves, so one ballot per wave gives every wave the same answer -- and a ONE lane of a mixed
+// tile stores its source value, no log / exp round trip.
+template <int NB, int kPitchWaves, bool CURVE>
 __global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
                                                                          int frames_per_unit, const int32_t* __restrict__ step_q, int Q,
                                                                          float* __restrict__ out, int C, int F, int ntile) {
@@ -697,19 +789,31 @@ __global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const fl
     const int64_t n = (int64_t)frames[b] * frames_per_unit;
     Fb = n < 0 ? 0 : (n > F ? F : (int)n);
   }
-  if (step_q) {
-    s = step_q[b];
-    s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+  if constexpr (!CURVE) {
+    if (step_q) {
+      s = step_q[b];
+      s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+    }
   }
   Fb = __builtin_amdgcn_readfirstlane(Fb);
-  s = __builtin_amdgcn_readfirstlane(s);
+  if constexpr (!CURVE) s = __builtin_amdgcn_readfirstlane(s);
   const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int f0 = tile * kPitchFrames, f = f0 + fl;
   const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
   float* __restrict__ dst = out + (int64_t)b * C * F + f;
   const bool live = f < Fb, inside = f < F;
-  if (f0 >= Fb || s == TACO_PITCH_ONE) {   // (uniform) nothing to shift: zeros behind the row's end, the row's own bits in front of it
+  bool plain;
+  if constexpr (CURVE) {
+    if (step_q && live) {   // (a frame behind F_b keeps ONE: its step is never read)
+      s = step_q[(int64_t)b * F + f];
+      s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+    }
+    plain = __ballot(live && s != TACO_PITCH_ONE) == 0;
+  } else {
+    plain = f0 >= Fb || s == TACO_PITCH_ONE;
+  }
+  if (plain) {   // (uniform) nothing to shift: zeros behind the row's end, the row's own bits in front of it
     for (int kb = 2 * wave + h; kb < C; kb += 2 * kPitchWaves * kPitchBatch) {   // (kPitchBatch loads in flight per thread)
       float m[kPitchBatch];
 #pragma unroll
@@ -845,6 +949,8 @@ __global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const fl
         // i < C - 1: between two bins; i == C - 1 with w == 0: the top bin itself; beyond it the envelope alone
         const float rp = i < C - 1 ? r0 + (float)frac * (1.0f / 65536.0f) * (r1 - r0) : ((i == C - 1 && frac == 0u) ? r0 : 0.f);
         y = expf(env[k * kPitchFrames + fl] + rp);
+        if constexpr (CURVE)
+          if (s == TACO_PITCH_ONE) y = m0[u];   // (k s >> 16 == k: m0 is the frame's own bin) a ONE frame among shifted ones
       }
       if (inside) dst[k * F] = y;
     }
@@ -1584,55 +1690,93 @@ extern "C" int taco_denorm_unframe(const float* out, const float* mean, const fl
   TACO_LAUNCH_CHECK("denorm_unframe");
   return TACO_OK;
 }
-extern "C" int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, float* out,
-                                   int32_t* frames_out, int B, int C, int F, int Fo, void* stream) {
-  TACO_REQUIRE(mag_t, "frames_stretch: mag_t is NULL");
-  TACO_REQUIRE(out, "frames_stretch: out is NULL");
-  TACO_REQUIRE(frames_out, "frames_stretch: frames_out is NULL");
-  TACO_REQUIRE(B > 0, "frames_stretch: B=%d must be positive", B);
-  TACO_REQUIRE(C > 0, "frames_stretch: C=%d must be positive", C);
-  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "frames_stretch: F=%d must be in 1..%d", F, TACO_STRETCH_MAX_FRAMES);
-  TACO_REQUIRE(Fo > 0 && Fo <= TACO_STRETCH_MAX_FRAMES, "frames_stretch: Fo=%d must be in 1..%d", Fo, TACO_STRETCH_MAX_FRAMES);
-  TACO_REQUIRE(frames_per_unit >= 1, "frames_stretch: frames_per_unit=%d must be >= 1", frames_per_unit);
+namespace {
+// the refusals taco_frames_stretch and taco_frames_stretch_curve share, and the gather's grid
+int frames_stretch_args(const char* who, const float* mag_t, const float* out, const int32_t* frames_out, int frames_per_unit, int B, int C,
+                        int F, int Fo, int* nspan, int* ntile, int64_t* blocks) {
+  TACO_REQUIRE(mag_t, "%s: mag_t is NULL", who);
+  TACO_REQUIRE(out, "%s: out is NULL", who);
+  TACO_REQUIRE(frames_out, "%s: frames_out is NULL", who);
+  TACO_REQUIRE(B > 0, "%s: B=%d must be positive", who, B);
+  TACO_REQUIRE(C > 0, "%s: C=%d must be positive", who, C);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "%s: F=%d must be in 1..%d", who, F, TACO_STRETCH_MAX_FRAMES);
+  TACO_REQUIRE(Fo > 0 && Fo <= TACO_STRETCH_MAX_FRAMES, "%s: Fo=%d must be in 1..%d", who, Fo, TACO_STRETCH_MAX_FRAMES);
+  TACO_REQUIRE(frames_per_unit >= 1, "%s: frames_per_unit=%d must be >= 1", who, frames_per_unit);
   const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
   const uint64_t rows = (uint64_t)B * (uint64_t)C;   // (< 2^62; F, Fo <= 2^13: the byte counts below fit 64 bits)
-  TACO_REQUIRE(rows <= (UINT64_MAX >> 16) / 4, "frames_stretch: B=%d x C=%d: the tensors exceed the address space", B, C);
-  TACO_REQUIRE(o0 + rows * Fo * 4 <= m0 || m0 + rows * F * 4 <= o0, "frames_stretch: out overlaps mag_t");
-  const int nspan = cdiv(Fo, kStretchSpan), ntile = cdiv(C, kStretchBins);
-  const int64_t blocks = (int64_t)B * ntile * nspan;
-  TACO_REQUIRE(blocks <= 0x7fffffff, "frames_stretch: B=%d x C=%d x Fo=%d needs more than 2^31 workgroups", B, C, Fo);
+  TACO_REQUIRE(rows <= (UINT64_MAX >> 16) / 4, "%s: B=%d x C=%d: the tensors exceed the address space", who, B, C);
+  TACO_REQUIRE(o0 + rows * Fo * 4 <= m0 || m0 + rows * F * 4 <= o0, "%s: out overlaps mag_t", who);
+  *nspan = cdiv(Fo, kStretchSpan), *ntile = cdiv(C, kStretchBins);
+  *blocks = (int64_t)B * *ntile * *nspan;
+  TACO_REQUIRE(*blocks <= 0x7fffffff, "%s: B=%d x C=%d x Fo=%d needs more than 2^31 workgroups", who, B, C, Fo);
+  return TACO_OK;
+}
+
+// taco_frames_pitch (CURVE = false: step_q (B)) and taco_frames_pitch_curve (true: step_q (B, F)): one set of refusals, and the
+// lifter path chosen by Q alone either way
+template <bool CURVE>
+int frames_pitch_call(const char* who, const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                      float* out, int B, int C, int F, void* stream) {
+  TACO_REQUIRE(mag_t, "%s: mag_t is NULL", who);
+  TACO_REQUIRE(out, "%s: out is NULL", who);
+  TACO_REQUIRE(B > 0, "%s: B=%d must be positive", who, B);
+  TACO_REQUIRE(C >= 9 && C <= kPitchMaxC && ((C - 1) & (C - 2)) == 0, "%s: C=%d: C - 1 must be a power of two in 8..%d", who, C,
+               kPitchMaxC - 1);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "%s: F=%d must be in 1..%d", who, F, TACO_STRETCH_MAX_FRAMES);
+  const int qmax = (C - 1) / 2 < TACO_PITCH_MAX_LIFTER ? (C - 1) / 2 : TACO_PITCH_MAX_LIFTER;
+  TACO_REQUIRE(lifter >= 1 && lifter <= qmax, "%s: lifter=%d must be in 1..%d at C=%d", who, lifter, qmax, C);
+  TACO_REQUIRE(frames_per_unit >= 1, "%s: frames_per_unit=%d must be >= 1", who, frames_per_unit);
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
+  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
+  TACO_REQUIRE(o0 + bytes <= m0 || m0 + bytes <= o0, "%s: out overlaps mag_t", who);
+  const int ntile = cdiv(F, kPitchFrames);
+  const int64_t blocks = (int64_t)B * ntile;
+  TACO_REQUIRE(blocks <= 0x7fffffff, "%s: B=%d x F=%d needs more than 2^31 workgroups", who, B, F);
   hipStream_t s = as_stream(stream);
-  TACO_KLAUNCH(frames_stretch_kernel, dim3((unsigned)blocks), dim3(64, 4), 0, s, mag_t, frames, frames_per_unit, step_q, out, frames_out,
-               C, F, Fo, nspan, ntile);
+  if (lifter <= 32)
+    TACO_KLAUNCH((frames_pitch_kernel<1, 16, CURVE>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, step_q,
+                 lifter, out, C, F, ntile);
+  else
+    TACO_KLAUNCH((frames_pitch_kernel<2, 8, CURVE>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, step_q,
+                 lifter, out, C, F, ntile);
+  TACO_LAUNCH_CHECK(who);
+  return TACO_OK;
+}
+}  // namespace
+
+extern "C" int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, float* out,
+                                   int32_t* frames_out, int B, int C, int F, int Fo, void* stream) {
+  int nspan, ntile;
+  int64_t blocks;
+  TACO_TRY(frames_stretch_args("frames_stretch", mag_t, out, frames_out, frames_per_unit, B, C, F, Fo, &nspan, &ntile, &blocks));
+  hipStream_t s = as_stream(stream);
+  TACO_KLAUNCH(frames_stretch_kernel<false>, dim3((unsigned)blocks), dim3(64, 4), 0, s, mag_t, frames, frames_per_unit, step_q, out,
+               frames_out, C, F, Fo, nspan, ntile);
   TACO_LAUNCH_CHECK("frames_stretch");
+  return TACO_OK;
+}
+// two launches on the caller's stream: the map (B workgroups), then the gather of taco_frames_stretch reading it
+extern "C" int taco_frames_stretch_curve(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* dur_q, float* out,
+                                         int32_t* frames_out, int32_t* src, int B, int C, int F, int Fo, void* stream) {
+  int nspan, ntile;
+  int64_t blocks;
+  TACO_TRY(frames_stretch_args("frames_stretch_curve", mag_t, out, frames_out, frames_per_unit, B, C, F, Fo, &nspan, &ntile, &blocks));
+  TACO_REQUIRE(src, "frames_stretch_curve: src is NULL");
+  hipStream_t s = as_stream(stream);
+  TACO_KLAUNCH(frames_stretch_map_kernel, dim3((unsigned)B), dim3(kMapThreads), 0, s, frames, frames_per_unit, dur_q, frames_out, src, F,
+               Fo);
+  TACO_KLAUNCH(frames_stretch_kernel<true>, dim3((unsigned)blocks), dim3(64, 4), 0, s, mag_t, nullptr, 1, src, out, frames_out, C, F, Fo,
+               nspan, ntile);
+  TACO_LAUNCH_CHECK("frames_stretch_curve");
   return TACO_OK;
 }
 extern "C" int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
                                  float* out, int B, int C, int F, void* stream) {
-  TACO_REQUIRE(mag_t, "frames_pitch: mag_t is NULL");
-  TACO_REQUIRE(out, "frames_pitch: out is NULL");
-  TACO_REQUIRE(B > 0, "frames_pitch: B=%d must be positive", B);
-  TACO_REQUIRE(C >= 9 && C <= kPitchMaxC && ((C - 1) & (C - 2)) == 0,
-               "frames_pitch: C=%d: C - 1 must be a power of two in 8..%d", C, kPitchMaxC - 1);
-  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "frames_pitch: F=%d must be in 1..%d", F, TACO_STRETCH_MAX_FRAMES);
-  const int qmax = (C - 1) / 2 < TACO_PITCH_MAX_LIFTER ? (C - 1) / 2 : TACO_PITCH_MAX_LIFTER;
-  TACO_REQUIRE(lifter >= 1 && lifter <= qmax, "frames_pitch: lifter=%d must be in 1..%d at C=%d", lifter, qmax, C);
-  TACO_REQUIRE(frames_per_unit >= 1, "frames_pitch: frames_per_unit=%d must be >= 1", frames_per_unit);
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
-  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
-  TACO_REQUIRE(o0 + bytes <= m0 || m0 + bytes <= o0, "frames_pitch: out overlaps mag_t");
-  const int ntile = cdiv(F, kPitchFrames);
-  const int64_t blocks = (int64_t)B * ntile;
-  TACO_REQUIRE(blocks <= 0x7fffffff, "frames_pitch: B=%d x F=%d needs more than 2^31 workgroups", B, F);
-  hipStream_t s = as_stream(stream);
-  if (lifter <= 32)
-    TACO_KLAUNCH((frames_pitch_kernel<1, 16>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, step_q,
-                 lifter, out, C, F, ntile);
-  else
-    TACO_KLAUNCH((frames_pitch_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, step_q,
-                 lifter, out, C, F, ntile);
-  TACO_LAUNCH_CHECK("frames_pitch");
-  return TACO_OK;
+  return frames_pitch_call<false>("frames_pitch", mag_t, frames, frames_per_unit, step_q, lifter, out, B, C, F, stream);
+}
+extern "C" int taco_frames_pitch_curve(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                                       float* out, int B, int C, int F, void* stream) {
+  return frames_pitch_call<true>("frames_pitch_curve", mag_t, frames, frames_per_unit, step_q, lifter, out, B, C, F, stream);
 }
 extern "C" int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_unit, const float* weight, const float* gain,
                               int lag_min, int lag_max, float ratio, float threshold, float* period, float* strength, float* acf,

@@ -19,6 +19,9 @@ slower or faster and Griffin-Lim finds phases for the new length, so the pitch s
 With `pitch` (opt-in) the harmonics of every magnitude frame are moved along the bin axis under the frame's own spectral envelope before
 Griffin-Lim (taco_frames_pitch): the voice gets higher or lower, the formants and the duration stay.
 
+With `rate_curve` / `pitch_curve` (opt-in) the two controls take one value per frame instead of one per row (taco_frames_stretch_curve,
+taco_frames_pitch_curve): a word slower, a question raised at its end.  The stretch then also returns its time map `src`.
+
 With `f0` (opt-in) the pitch of the magnitude frames is measured on the device (taco_frames_f0, taco_f0_stats): the frames as de-normalised
 and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective stand-in for listening to those two controls.  With
 'smooth' in it every track is smoothed across frames (taco_f0_viterbi) before it is summarised.
@@ -43,7 +46,8 @@ SR = 16000   # test.py:11
 
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
-                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None):
+                       lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
+                       rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -84,6 +88,16 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
                  passed through lib.f0_viterbi: tracks[name] holds the SMOOTHED (period, strength) and every *_stats is taken over
                  those; tracks[name + '_raw'] holds the per-frame pair (the bits of a run without 'smooth') and
                  tracks[name + '_counts'] the (B, 4) int32 counts in the order lib.F0_VITERBI_COUNTS.  The waveform does not change.
+    pitch_curve / rate_curve (opt-in): prosody inside an utterance, one value per FRAME -- (B, F) int32 device tensors, F = the frames
+    of mag_t, e.g. lib.path_curve of per-character values along lib.alignment_path.  pitch_curve holds step_q values
+    (lib.pitch_step) and takes the place of `pitch` (lib.frames_pitch_curve); rate_curve holds dur_q values (lib.stretch_dur: the
+    output frames a source frame lasts) and takes the place of `rate` (lib.frames_stretch_curve).  Giving both of a pair is a
+    ValueError.  The order is the same: pitch on the unstretched frames, then the stretch.  Fo is
+    lib.stretch_curve_capacity(F, dur_q_max), dur_q_max the caller's statement of the slowest duration in rate_curve (default
+    262144: rate 0.25), and at least 5; the vocoder takes the per-row entry points over frames_out as with `rate`, and the return
+    gains frames_out (B) and src (B, Fo) int32 -- the time map, (i << 16) | wq per output frame, -1 behind Fo_b -- behind the
+    waveform: (waveform, frames_out, src) or (waveform, conv, frames_out, src).  frames_out / src: the caller's own buffers.  The
+    f0 tracks behave as behind `pitch` / `rate`.  Neutral curves (65536 everywhere) give the bits of pitch=0 / rate=1.0.
     Everything stays on the device.  F0 in Hz is SR / period."""
     track = None
     if f0 is not None and f0 is not False:
@@ -128,8 +142,14 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
                 smoothed = lib.f0_viterbi(acf, counts, per_unit, **smooth)
                 tracks[name], tracks[name + '_raw'], tracks[name + '_counts'] = smoothed[:2], (period, strength), smoothed[2]
             tracks[name + '_stats'] = lib.f0_stats(tracks[name][0], None, counts, per_unit)
-    if frames_out is not None and rate is None:
+    if pitch is not None and pitch_curve is not None:
+        raise ValueError('invert_spectrogram: pitch_curve excludes pitch: give one of them')
+    if rate is not None and rate_curve is not None:
+        raise ValueError('invert_spectrogram: rate_curve excludes rate: give one of them')
+    if frames_out is not None and rate is None and rate_curve is None:
         raise ValueError('invert_spectrogram: frames_out needs rate')
+    if src is not None and rate_curve is None:
+        raise ValueError('invert_spectrogram: src needs rate_curve')
     if want_conv and momentum is None:
         raise ValueError('invert_spectrogram: want_conv needs momentum (0 for the plain rounds)')
     dev = out.device
@@ -137,40 +157,51 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
     per_unit = r if lengths is not None else 1
-    if pitch is not None:
-        pitch_q = lib.steps_of(pitch, lib.pitch_step)
+    shifted = pitch is not None or pitch_curve is not None
+    if shifted:
         if track:
             track('model', mag_t, f0_lengths, f0_unit)
-        mag_t = lib.frames_pitch(mag_t, lengths, pitch_q, frames_per_unit=per_unit, lifter=lifter)
+        if pitch_curve is not None:
+            mag_t = lib.frames_pitch_curve(mag_t, lengths, pitch_curve, frames_per_unit=per_unit, lifter=lifter)
+        else:
+            mag_t = lib.frames_pitch(mag_t, lengths, lib.steps_of(pitch, lib.pitch_step), frames_per_unit=per_unit, lifter=lifter)
         if track:
             track('pitched', mag_t, f0_lengths, f0_unit)
             tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], f0_lengths, f0_unit)
     elif track:
         track('model', mag_t, f0_lengths, f0_unit)
     if track:
-        last = 'pitched' if pitch is not None else 'model'
+        last = 'pitched' if shifted else 'model'
         tracks['vocoder'], tracks['vocoder_stats'] = tracks[last], tracks[last + '_stats']
         if smooth is not None:
             tracks['vocoder_raw'], tracks['vocoder_counts'] = tracks[last + '_raw'], tracks[last + '_counts']
     done = (lambda res: res) if not track else (lambda res: (tuple(res) if isinstance(res, tuple) else (res,)) + (tracks,))
-    if rate is not None:
+    if rate is not None or rate_curve is not None:
         F = mag_t.shape[2]
-        step_q = lib.steps_of(rate, lib.stretch_step)
-        if torch.is_tensor(step_q):   # (on a device, never read: any rate down to the slowest)
-            slowest = lib.STRETCH_MIN_STEP
+        if rate_curve is not None:
+            Fo = max(5, lib.stretch_curve_capacity(F, lib.int_arg('invert_spectrogram', 'dur_q_max', dur_q_max, lib.STRETCH_MIN_STEP,
+                                                                  lib.STRETCH_MAX_STEP)))
+            stretched, frames_out, src = lib.frames_stretch_curve(mag_t, lengths, rate_curve, frames_per_unit=per_unit, Fo=Fo,
+                                                                  frames_out=frames_out, src=src)
+            tail = (frames_out, src)
         else:
-            slowest = min(step_q, default=lib.STRETCH_ONE) if isinstance(step_q, list) else step_q
-        Fo = max(5, lib.stretch_capacity(F, slowest))
-        stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=per_unit, Fo=Fo, frames_out=frames_out)
+            step_q = lib.steps_of(rate, lib.stretch_step)
+            if torch.is_tensor(step_q):   # (on a device, never read: any rate down to the slowest)
+                slowest = lib.STRETCH_MIN_STEP
+            else:
+                slowest = min(step_q, default=lib.STRETCH_ONE) if isinstance(step_q, list) else step_q
+            Fo = max(5, lib.stretch_capacity(F, slowest))
+            stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=per_unit, Fo=Fo, frames_out=frames_out)
+            tail = (frames_out,)
         phase0 = None if phase0 is None else phase0.contiguous()
         if track:   # (the stretched rows hold frames_out frames each, whatever `lengths` was)
             track('vocoder', stretched, frames_out, 1)
         if momentum is not None:
             res = lib.griffinlim_fast(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, momentum=momentum,
                                       frames_per_unit=1, want_conv=want_conv, out=wave, work=work)
-            return done((res[0], res[1], frames_out) if want_conv else (res, frames_out))
+            return done(((res[0], res[1]) if want_conv else (res,)) + tail)
         return done((lib.griffinlim_rows(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=1, out=wave,
-                                         work=work), frames_out))
+                                         work=work),) + tail)
     if momentum is not None:
         return done(lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
                                         momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work))

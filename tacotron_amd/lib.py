@@ -132,6 +132,9 @@ EXPORTS = {
     'taco_denorm_unframe': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_stretch': (C.c_int, [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_pitch': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
+    'taco_path_curve': (C.c_int, [_P, _P, _I, C.c_int32, _P, _I, _I, _I, _P]),
+    'taco_frames_stretch_curve': (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'taco_frames_pitch_curve': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     'taco_frames_f0': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     'taco_f0_stats': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _P]),
     'taco_f0_viterbi_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
@@ -796,6 +799,99 @@ def frames_pitch(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, 
     on_gpu(who, 'mag_t', dev)
     _check(_lib.taco_frames_pitch(ptr(mag_t), ptr(frames), frames_per_unit, ptr(step_q), lifter, ptr(out), B, Cw, F, stream_ptr()),
            'taco_frames_pitch')
+    return out
+
+
+def stretch_dur(rate) -> int:
+    """A speaking rate -> dur_q of taco_frames_stretch_curve = round(65536 / rate), the output frames a source frame lasts in units
+    of 2^-16 (the inverse sense of stretch_step: durations add); ValueError outside [0.25, 4] or for NaN"""
+    try:
+        rate = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError('rate must be a number in [0.25, 4], got %r' % (rate,)) from None
+    if not 0.25 <= rate <= 4.0:   # (NaN fails both comparisons)
+        raise ValueError('rate must be in [0.25, 4], got %r' % (rate,))
+    return int(round(65536.0 / rate))
+
+
+def stretch_curve_capacity(F, dur_q_max) -> int:
+    """The Fo no row of a (B, C, F) taco_frames_stretch_curve call can exceed when no duration is above dur_q_max (clamped as the
+    device clamps it): min(8192, ((F - 1) * dur_q_max >> 16) + 1)"""
+    F = int(F)
+    if F <= 0:
+        return 0
+    return min(STRETCH_MAX_FRAMES, (((F - 1) * _stretch_clamp(dur_q_max)) >> 16) + 1)
+
+
+def path_curve(path, values, frames_per_step=1, fill=0, curve=None):
+    """Per-character values to a per-frame curve along the path of alignment_path (include/taco_hip.h taco_path_curve): path (B, Td)
+    int32 and values (B, Tt) int32 on the device -> curve (B, Td * frames_per_step) int32 with
+    curve[b, t * frames_per_step + u] = values[b, path[b, t]], and `fill` where the path names no character (-1 behind the row's
+    steps, an index >= Tt).  Exact, nothing clamped.  curve: the caller's own buffer; default: a fresh one.  Enqueued on the current
+    stream; nothing is read back and nothing waits."""
+    who = 'path_curve'
+    B, Td = tensor_arg(who, 'path', path, torch.int32, ('B', 'Td'))
+    dev = path.device
+    (Tt,) = tensor_arg(who, 'values', values, torch.int32, (B, 'Tt'), dev)
+    frames_per_step = int_arg(who, 'frames_per_step', frames_per_step, 1, STRETCH_MAX_FRAMES)
+    if Td * frames_per_step > STRETCH_MAX_FRAMES:
+        raise ValueError('%s: at most %d frames, got Td = %d x frames_per_step = %d' % (who, STRETCH_MAX_FRAMES, Td, frames_per_step))
+    fill = int_arg(who, 'fill', fill, -(1 << 31), _INT_MAX)
+    curve = _own_or_given(curve, (B, Td * frames_per_step), torch.int32, dev, who + ': curve')
+    on_gpu(who, 'path', dev)
+    _check(_lib.taco_path_curve(ptr(path), ptr(values), frames_per_step, fill, ptr(curve), B, Td, Tt, stream_ptr()), 'taco_path_curve')
+    return curve
+
+
+def frames_stretch_curve(mag_t, frames=None, dur_q=None, frames_per_unit=1, Fo=None, dur_q_max=STRETCH_MAX_STEP, out=None,
+                         frames_out=None, src=None):
+    """A speaking rate that varies along the utterance (include/taco_hip.h taco_frames_stretch_curve): mag_t (B, C, F) fp32 on the
+    device -> (out (B, C, Fo) fp32, frames_out (B) int32, src (B, Fo) int32).  dur_q: (B, F) int32 on the device -- the output frames
+    source frame i lasts in units of 2^-16 (stretch_dur(rate)), clamped there to [16384, 262144] and never read here -- or None
+    (65536 everywhere: a copy).  src is the time map: (i << 16) | wq per output frame, -1 behind Fo_b.  frames: (B) int32 on the
+    device, or None.  Fo: default stretch_curve_capacity(F, dur_q_max), dur_q_max being the caller's statement of the slowest
+    duration in dur_q (F for None).  out / frames_out / src: the caller's own buffers; default: fresh ones.  Enqueued on the
+    current stream; nothing is read back and nothing waits."""
+    who = 'frames_stretch_curve'
+    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
+    dev = mag_t.device
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    tensor_arg(who, 'dur_q', dur_q, torch.int32, (B, F), dev, optional=True)
+    if Fo is None:
+        if out is not None and torch.is_tensor(out) and out.dim() == 3:
+            Fo = out.shape[2]
+        else:
+            Fo = F if dur_q is None else stretch_curve_capacity(F, int_arg(who, 'dur_q_max', dur_q_max, STRETCH_MIN_STEP, STRETCH_MAX_STEP))
+    Fo = int_arg(who, 'Fo', Fo, 1, STRETCH_MAX_FRAMES)
+    out = _own_or_given(out, (B, Cw, Fo), torch.float32, dev, who + ': out')
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
+    frames_out = _own_or_given(frames_out, (B,), torch.int32, dev, who + ': frames_out')
+    src = _own_or_given(src, (B, Fo), torch.int32, dev, who + ': src')
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_stretch_curve(ptr(mag_t), ptr(frames), frames_per_unit, ptr(dur_q), ptr(out), ptr(frames_out), ptr(src), B, Cw,
+                                          F, Fo, stream_ptr()), 'taco_frames_stretch_curve')
+    return out, frames_out, src
+
+
+def frames_pitch_curve(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, out=None):
+    """A pitch contour (include/taco_hip.h taco_frames_pitch_curve): frames_pitch with a step per frame.  step_q: (B, F) int32 on the
+    device (pitch_step(semitones) per frame; clamped there to [32768, 131072], never read here) or None (65536: a copy).  Frame f has
+    the bits frames_pitch gives it at the row step step_q[b, f]; a frame at 65536 is its input bit for bit.  Everything else as
+    frames_pitch."""
+    who = 'frames_pitch_curve'
+    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
+    dev = mag_t.device
+    pow2_bins(who, Cw)
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, 1, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
+    tensor_arg(who, 'step_q', step_q, torch.int32, (B, F), dev, optional=True)
+    out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_pitch_curve(ptr(mag_t), ptr(frames), frames_per_unit, ptr(step_q), lifter, ptr(out), B, Cw, F, stream_ptr()),
+           'taco_frames_pitch_curve')
     return out
 
 

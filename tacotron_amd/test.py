@@ -62,7 +62,19 @@ with --long, the piece's offset in the joined file are applied; with --long each
 prompt_NNN_kMM_dur.npy and the prompt one _words.tsv).  One line per prompt gives the path's mass per step, its end against L - 1 and
 the skipped characters, as a WARNING when the path ends more than end_offset characters before the text does.  A boundary is exact at
 multiples of 4 decoder steps and nominal inside such a block (alignment.py): good for subtitles, not a phonetic aligner.  It combines
-with every option above; without it every file is what it was."""
+with every option above; without it every file is what it was.
+--prosody FILE (opt-in, with --stop; not in the reference): rate and pitch per WORD.  FILE holds lines
+`prompt<TAB>word<TAB>rate<TAB>semitones`, both indices 0-based, a word as --timings defines it, `-` in the rate or semitones field for
+"leave"; words not listed take --rate / --pitch, or stay neutral.  The best monotone path through the attention says which decoder step
+speaks which character (taco_alignment_path); two gathers turn the per-character durations and pitch steps into per-frame curves along
+it (lib.path_curve, taco_path_curve), and the magnitudes go through the pitch curve (lib.frames_pitch_curve) and then the stretch curve
+(lib.frames_stretch_curve) in front of Griffin-Lim -- inference, path, gathers, de-normalisation, pitch, stretch, Griffin-Lim and
+finishing all on the device.  prompt_NNN.wav holds 300 (Fo_b - 1) samples before any trim, Fo_b the stretch's own frames_out;
+prompt_NNN_prosody.npy holds the per-character (dur_q, step_q) as int32 (in place of _rate.npy / _pitch.npy); with --timings the word
+rows go through the stretch's time map; with --f0 the line gives the drift of the mean log-F0 with no "asked" figure.  A word's
+characters share one value and the curve steps at its edges: no ramps across word boundaries.  Refused with --long: the pieces
+re-index the words of a prompt, which is out of scope here.  Nobody has listened to the result.  Without it every file is what it
+was."""
 from __future__ import annotations
 
 import argparse
@@ -75,7 +87,7 @@ import numpy as np
 import torch
 
 from .config import Config
-from .alignment import attention_png, flags, path_line, scores_row, word_times, words_tsv
+from .alignment import attention_png, encoded_chars, flags, path_line, scores_row, word_times, word_values, words_tsv
 from .data import KIND_NAMES, load_prompts, split_prompt
 from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform
 from .model import Tacotron
@@ -150,6 +162,62 @@ def pitch_steps(pitch, n):
     return _steps('pitch', pitch, lib.pitch_step, n)
 
 
+def parse_prosody(text):
+    """The text of a --prosody file -> [(prompt, word, rate | None, semitones | None)]: lines `prompt<TAB>word<TAB>rate<TAB>semitones`,
+    both indices 0-based integers, `-` in the rate or semitones field for "leave"; empty lines and lines starting with # are skipped.
+    ValueError names the line."""
+    rows = []
+    for k, line in enumerate(text.splitlines(), 1):
+        if not line.strip() or line.lstrip().startswith('#'):
+            continue
+        parts = line.rstrip('\r\n').split('\t')
+        try:
+            if len(parts) != 4:
+                raise ValueError('expected 4 fields, got %d' % len(parts))
+            prompt, word = int(parts[0]), int(parts[1])
+            rate = None if parts[2].strip() == '-' else float(parts[2])
+            semitones = None if parts[3].strip() == '-' else float(parts[3])
+        except ValueError as e:
+            raise ValueError('prosody (--prosody): line %d %r: expected prompt<TAB>word<TAB>rate<TAB>semitones: %s' % (k, line, e)) from None
+        rows.append((prompt, word, rate, semitones))
+    return rows
+
+
+def prosody_table(rows, prompts, ivocab, base_dur=None, base_step=None):
+    """The rows of parse_prosody against the prompts -> per prompt an (L, 2) int32 array of (dur_q, step_q) per encoded character
+    (alignment.word_values): the characters of a listed word take lib.stretch_dur(rate) / lib.pitch_step(semitones), everything else
+    the prompt's base_dur / base_step (sequences with one value per prompt; None: 65536, neutral).  ValueError for a prompt or word
+    index that does not exist, a rate outside [0.25, 4], semitones outside [-12, 12] and a word listed twice."""
+    per = [({}, {}) for _ in prompts]
+    for prompt, word, rate, semitones in rows:
+        who = 'prosody (--prosody): prompt %d word %d' % (prompt, word)
+        if not 0 <= prompt < len(prompts):
+            raise ValueError('%s: there are the prompts 0 .. %d' % (who, len(prompts) - 1))
+        durs, steps = per[prompt]
+        if word in durs or word in steps:
+            raise ValueError('%s is listed twice' % who)
+        try:
+            if rate is not None:
+                durs[word] = lib.stretch_dur(rate)
+            if semitones is not None:
+                steps[word] = lib.pitch_step(semitones)
+            if rate is None and semitones is None:
+                durs[word] = None   # (listed, nothing asked: only the index is checked)
+        except ValueError as e:
+            raise ValueError('%s: %s' % (who, e)) from None
+    out = []
+    for p, line in enumerate(prompts):
+        bd = lib.STRETCH_ONE if base_dur is None else int(base_dur[p])
+        bs = lib.PITCH_ONE if base_step is None else int(base_step[p])
+        try:
+            d, _ = word_values(line, ivocab, {w: (bd if v is None else v) for w, v in per[p][0].items()}, bd)
+            q, _ = word_values(line, ivocab, per[p][1], bs)
+        except ValueError as e:
+            raise ValueError('prosody (--prosody): prompt %d: %s' % (p, e)) from None
+        out.append(np.array([d, q], dtype=np.int32).reshape(2, -1).T.copy())
+    return out
+
+
 def f0_range(f0):
     """`f0` of test(): None / False (off), True (60 .. 400 Hz) or (lo, hi) in Hz -> None or (lo, hi) after lib.f0_tables has accepted
     them at 16 kHz; ValueError"""
@@ -163,17 +231,21 @@ def f0_range(f0):
     return lo, hi
 
 
-def f0_lines(who, f0row, asked_step=None, rate_step=None):
+def f0_lines(who, f0row, asked_step=None, rate_step=None, prosody=False):
     """the line(s) --f0 prints for `who` ('prompt 3', or 'prompt 3 piece 1' with --long) from its row of the statistics: f0row =
     (model_stats, vocoder_stats, pitch_stats | None), and with --f0-smooth behind them the row's lib.f0_viterbi counts: the line
-    gains `, smoothing moved M of N frames` (without --pitch and --rate that is the whole line)"""
+    gains `, smoothing moved M of N frames` (without --pitch and --rate that is the whole line).  prosody (--prosody): the drift line of
+    --rate without a figure asked for -- the curves ask for something else in every word"""
     model, voc, paired = f0row[:3]
     out = []
     if len(f0row) > 3 and f0row[3] is not None:
         tail = 'smoothing moved %d of %d frames' % (int(f0row[3][2]), int(f0row[3][0]))
-        lines = f0_lines(who, f0row[:3], asked_step, rate_step)
+        lines = f0_lines(who, f0row[:3], asked_step, rate_step, prosody)
         return ['%s, %s' % (lines[0], tail)] + lines[1:] if lines else ['%s f0: %s' % (who, tail)]
-    if asked_step is not None and paired is not None:
+    if prosody:
+        out.append('%s prosody: mean log-F0 moved %+.1f cents (%d -> %d voiced frames)'
+                   % (who, 1200.0 * (float(model[1]) - float(voc[1])), int(model[0]), int(voc[0])))
+    elif asked_step is not None and paired is not None:
         out.append('%s pitch: asked %+.2f, measured %+.2f semitones over %d voiced frames'
                    % (who, 12.0 * np.log2(65536.0 / asked_step), 12.0 * float(paired[1]), int(paired[0])))
     elif rate_step is not None:
@@ -183,9 +255,17 @@ def f0_lines(who, f0row, asked_step=None, rate_step=None):
 
 
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, path_jump=None):
+                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, path_jump=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
-    without --timings; `f0_smooth`: None / False, True or the number of candidates); ValueError."""
+    without --timings; `f0_smooth`: None / False, True or the number of candidates; `prosody`: None / False or anything else for
+    given); ValueError."""
+    if prosody is not None and prosody is not False:
+        if not vocode:
+            raise ValueError('prosody (--prosody) shapes the magnitudes in front of Griffin-Lim: it needs vocode')
+        if not stop:
+            raise ValueError('prosody (--prosody) needs a stop rule (--stop): the curves follow the path over each prompt\'s own steps')
+        if long_options(long) is not None:
+            raise ValueError('prosody (--prosody) cannot be combined with long (--long): the pieces re-index the words of a prompt')
     if f0_smooth is not None and f0_smooth is not False:
         if f0 is None or f0 is False:
             raise ValueError('f0_smooth (--f0-smooth) smooths the track of f0 (--f0): it needs f0')
@@ -221,7 +301,7 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None, f0=None, dur=None):
+                 rate=None, pitch=None, f0=None, dur=None, prosody=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -232,12 +312,14 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     pitch (--pitch): (step_q, lifter) of the prompt, written as _pitch.npy; nothing else depends on it.
     f0 (--f0): the prompt's (frames, 2) float32 rows of (period, strength) over the frames the vocoder was given, already cut to them;
     written as _f0.npy.
-    dur (--timings): the steps of each of the prompt's characters, written as _dur.npy (int32)."""
+    dur (--timings): the steps of each of the prompt's characters, written as _dur.npy (int32).
+    prosody (--prosody): (the prompt's (L, 2) per-character (dur_q, step_q), Fo_b): the table is written as _prosody.npy (int32); wav is
+    then the waveform behind the stretch curve and keeps 300 (Fo_b - 1) samples, whatever len_b says."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
         spec, align = spec[:frames], align[:len_b]
-        if wav is not None and rate is None:
+        if wav is not None and rate is None and prosody is None:
             wav = wav[:300 * (frames - 1)]
         np.save(path + '_len.npy', np.int32(len_b))
     if rate is not None:
@@ -246,6 +328,10 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_rate.npy', np.asarray(rate, dtype=np.int32))
     if pitch is not None:
         np.save(path + '_pitch.npy', np.asarray(pitch, dtype=np.int32))
+    if prosody is not None:
+        if wav is not None:
+            wav = wav[:300 * max(0, int(prosody[1]) - 1)]
+        np.save(path + '_prosody.npy', np.asarray(prosody[0], dtype=np.int32).reshape(-1, 2))
     if f0 is not None:
         np.save(path + '_f0.npy', np.asarray(f0, dtype=np.float32))
     if dur is not None:
@@ -267,7 +353,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
          gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None,
-         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None):
+         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -316,9 +402,21 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     `timings` / `path_jump`: every batch's best monotone attention paths are found on the device (Tacotron.alignment_path with
     max_jump = path_jump: over model.lengths with `stop`, else all steps); each prompt -- with `long`, each piece -- additionally
     writes _dur.npy, each prompt _words.tsv (alignment.word_times of the file it wrote) and one line, a WARNING when the path ends
-    before the text does.  Nothing else changes."""
+    before the text does.  Nothing else changes.
+    `prosody` (needs `stop` and `vocode`, excludes `long`): None, or the rows of parse_prosody -- (prompt, word, rate | None,
+    semitones | None) -- rate and pitch per word; words not listed take `rate` / `pitch`, or stay neutral.  Per batch, all on the
+    device: the path (Tacotron.alignment_path, max_jump = path_jump), two lib.path_curve gathers of the per-character dur_q / step_q
+    into per-frame curves, then invert_spectrogram(rate_curve=..., pitch_curve=...) over each row's own len_b r frames (the pitch curve
+    only when a pitch is asked for anywhere).  prompt_NNN.wav holds 300 (Fo_b - 1) samples, Fo_b the stretch's frames_out (with finishing
+    the row ends there on the device); prompt_NNN_prosody.npy the per-character (dur_q, step_q); _rate.npy / _pitch.npy are not written.
+    With `timings` the word rows go through the stretch's time map (alignment.word_times(src=...)); with `f0` the line is the drift
+    line without a figure asked for."""
     check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
-                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None)
+                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody)
+    if prosody is not None and prosody is not False:
+        lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
+    else:
+        prosody = None
     f0_smooth = None if f0_smooth is None or f0_smooth is False else (lib.F0_CANDIDATES if f0_smooth is True else int(f0_smooth))
     f0 = f0_range(f0)
     f0_opt = None   # the tables on the device, made at the first batch
@@ -340,13 +438,19 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     if ckpt is not None:
         config.r, config.vocab_size = ckpt.get('shape', (config.r, config.vocab_size))
         config.num_speakers = int(ckpt.get('num_speakers', 1))
+    pros = None   # per prompt: (L, 2) int32 (dur_q, step_q) per encoded character
+    if prosody is not None:   # the curves carry --rate and --pitch as the value of every character no row of the table names
+        pros = prosody_table(prosody, prompts, ivocab, _steps('rate', rate, lib.stretch_dur, len(prompts)), row_pitch)
+        pros_pitch = row_pitch is not None or any(sem is not None for _, _, _, sem in prosody)
+        pros_max = max([lib.STRETCH_ONE] + [int(t[:, 0].max()) for t in pros if len(t)])
+        steps = row_pitch = None
     state = {'params': None}
     models = {}   # batch size -> Tacotron
     os.makedirs(out_dir, exist_ok=True)
 
     def synthesise(batch, n, out_rows=None, bounds_rows=None):
-        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths), host arrays or
-        None.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
+        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved), host
+        arrays or None.  curved (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
         out_rows / bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made.
         f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
         lib.f0_viterbi counts (B, 4))"""
@@ -367,14 +471,15 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             model.set_inputs(batch)
         out, al = model.run(stop=stop)
         scores = model.alignment_scores() if align_scores else None   # (enqueued behind the decode; read with the other results below)
-        paths = model.alignment_path(path_jump)[1:] if timings else None   # (likewise; the path itself stays on the device)
+        found = model.alignment_path(path_jump) if timings or pros is not None else None   # (likewise; the path stays on the device)
+        paths = found[1:] if timings else None
         model.check()
         mean = model.stft_mean if model.stft_mean is not None else torch.zeros(config.fft_size * config.r)
         std = model.stft_std if model.stft_std is not None else torch.ones(config.fft_size * config.r)
         mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = conv = pcm = trim = f0res = None
+        wav = conv = pcm = trim = f0res = curved = None
         if vocode:
             fout = None
             shift = {}
@@ -389,7 +494,20 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                         f0_opt['smooth'] = dict(bias=torch.from_numpy(bias).cuda(), lg=torch.from_numpy(lg).cuda(), candidates=f0_smooth,
                                                 jump_cost=jump, switch_cost=switch)
                 shift['f0'] = dict(f0_opt, lengths=model.lengths if stop is not None else None)
-            if steps is None:
+            if pros is not None:
+                Tt, Fm = batch['text'].shape[1], (out.shape[1] // 4) * 4 * config.r
+                values = np.empty((2, Bn, Tt), dtype=np.int32)
+                values[0], values[1] = lib.STRETCH_ONE, lib.PITCH_ONE
+                for i in range(Bn):
+                    table = pros[n + i][:Tt]
+                    values[:, i, :len(table)] = table.T
+                values = torch.from_numpy(values).cuda()
+                curves = [lib.path_curve(found[0], values[k], config.r, one)[:, :Fm].contiguous()
+                          for k, one in ((0, lib.STRETCH_ONE), (1, lib.PITCH_ONE)) if k == 0 or pros_pitch]
+                res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
+                                         want_conv=gl_momentum is not None, lengths=model.lengths, rate_curve=curves[0],
+                                         pitch_curve=curves[1] if pros_pitch else None, lifter=lifter, dur_q_max=pros_max, **shift)
+            elif steps is None:
                 res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
                                          want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None, **shift)
             else:   # (the rows' own frames whenever there is a rule: the host's Fo_b and the device's frames_out are then one number)
@@ -403,8 +521,12 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                          tracks['vocoder_stats'].cpu().numpy(), tracks['pitch_stats'].cpu().numpy() if 'pitch_stats' in tracks else None)
                 if f0_smooth is not None:
                     f0res += (tracks['vocoder_counts'].cpu().numpy(),)
-            if steps is not None:
+            if pros is not None:
+                src = res.pop()
+            if steps is not None or pros is not None:
                 fout = res.pop()
+            if pros is not None:
+                curved = (fout.cpu().numpy(), src.cpu().numpy())
             wav = res[0] if gl_momentum is None else res
             if gl_momentum is not None:
                 wav, conv = wav[0], wav[1].cpu().numpy()
@@ -430,7 +552,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             scores = np.stack([scores_row(c, m) for c, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
         if paths is not None:
             paths = tuple(x.cpu().numpy() for x in paths)
-        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res, paths
+        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res, paths, curved
 
     def marks(score, L):
         """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
@@ -448,26 +570,33 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         """(step_q, lifter) of global row `row`, or None without a pitch"""
         return None if row_pitch is None else (row_pitch[row], int(lifter))
 
-    def f0_of(row, i, len_b, f0res, who):
+    def f0_of(row, i, len_b, f0res, who, curved=None):
         """the _f0.npy rows of row i of a batch (global row `row`), cut to the frames the vocoder was given; prints the row's line"""
         if f0res is None:
             return None
         stretched = rate_of(row, len_b)
         frames = stretched[1] if stretched is not None else (F if len_b is None else min(int(len_b) * config.r, F))
+        if curved is not None:
+            frames = int(curved[0][i])
         for line in f0_lines(who, [None if a is None else a[i] for a in f0res[1:]], None if row_pitch is None else row_pitch[row],
-                             None if steps is None else row_steps[row]):
+                             None if steps is None else row_steps[row], curved is not None):
             print(line)
         return f0res[0][i, :frames]
 
-    def timing_of(row, i, len_b, trim, paths, text_len, line, who, offset=0):
+    def timing_of(row, i, len_b, trim, paths, text_len, line, who, offset=0, curved=None):
         """(_dur.npy of row i of a batch (global row `row`), its word rows in the file it goes to) with `timings`, else (None, None);
-        prints the row's line.  trim: the row's [s, e] when the waveform was finished; offset: of the piece in a joined file"""
+        prints the row's line.  trim: the row's [s, e] when the waveform was finished; offset: of the piece in a joined file; curved
+        (`prosody`): the batch's (frames_out, src) -- the word boundaries then go through the row's time map"""
         if paths is None:
             return None, None
         dur, counts, mass = (a[i] for a in paths)
         print(path_line(who, counts, mass, text_len, stop.end_offset if stop is not None else 1)[0])
         stretched = rate_of(row, len_b)
         frames = stretched[1] if stretched is not None else (F if len_b is None else min(int(len_b) * config.r, F))
+        if curved is not None:
+            frames = int(curved[0][i])
+            return dur[:text_len], word_times(line, ivocab, dur[:text_len], config.r, None, trim, offset, 300 * max(0, frames - 1), SR,
+                                              src=curved[1][i, :frames])
         words = word_times(line, ivocab, dur[:text_len], config.r, None if steps is None else row_steps[row], trim, offset,
                            300 * max(0, frames - 1), SR)
         return dur[:text_len], words
@@ -491,12 +620,13 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         return n
     for batch in load_prompts(prompts, ivocab):
         Bn = batch['text'].shape[0]
-        spec, al, wav, conv, pcm, trim, lengths, scores, f0res, paths = synthesise(batch, n)
+        spec, al, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved = synthesise(batch, n)
         for i in range(Bn):
             wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
-            dur, words = timing_of(n, i, len_b, ti, paths, int(batch['text_length'][i]), prompts[n], 'prompt %d' % n)
+            dur, words = timing_of(n, i, len_b, ti, paths, int(batch['text_length'][i]), prompts[n], 'prompt %d' % n, curved=curved)
             write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
-                         rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n), dur=dur)
+                         rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n, curved), dur=dur,
+                         prosody=None if curved is None else (pros[n], int(curved[0][i])))
             if words is not None:
                 write_words(n, words)
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
@@ -538,7 +668,7 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
         at = 0
         for batch in load_prompts(lines, ivocab):
             Bn = batch['text'].shape[0]
-            spec, al, _, conv, _, trim, lengths, scores, f0res, paths = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            spec, al, _, conv, _, trim, lengths, scores, f0res, paths, _ = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
             timed += [(paths, i) for i in range(Bn)]
             arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i],
                         None if scores is None else scores[i], int(batch['text_length'][i]),
@@ -646,8 +776,13 @@ def parse_args(argv=None):
                     help='when each word is spoken: the best monotone path through every prompt\'s attention, found on the device; writes '
                          'prompt_NNN_dur.npy (steps per character) and prompt_NNN_words.tsv (start_s, end_s, word); exact at multiples of 4 '
                          'decoder steps, nominal inside a block (not in the reference)')
+    ap.add_argument('--prosody', default=None, metavar='FILE',
+                    help='--stop: rate and pitch per word.  FILE holds lines prompt<TAB>word<TAB>rate<TAB>semitones, both indices '
+                         '0-based, - in the rate or semitones field for "leave"; words not listed take --rate / --pitch or stay neutral.  '
+                         'The curves follow the attention path on the device; writes prompt_NNN_prosody.npy (dur_q, step_q per character).  '
+                         'Refused with --long: the pieces re-index the words of a prompt, which is out of scope (not in the reference)')
     ap.add_argument('--path-jump', type=int, default=None, metavar='J',
-                    help='--timings: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
+                    help='--timings / --prosody: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
     a.long = dict(pause_ms=a.pause_ms, fade_ms=a.fade_ms) if a.long else None
     if a.f0_candidates is not None and not a.f0_smooth:
@@ -657,13 +792,17 @@ def parse_args(argv=None):
     if a.f0_range is not None and not a.f0:
         ap.error('--f0-range needs --f0')
     a.f0 = (a.f0_range if a.f0_range is not None else True) if a.f0 else None
-    if a.path_jump is not None and not a.timings:
-        ap.error('--path-jump needs --timings')
+    if a.path_jump is not None and not a.timings and a.prosody is None:
+        ap.error('--path-jump needs --timings or --prosody')
     a.path_jump = lib.PATH_JUMP if a.path_jump is None else a.path_jump
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
-                      lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings else None)
-    except ValueError as e:
+                      lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings or a.prosody is not None else None,
+                      prosody=a.prosody)
+        if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
+            with open(a.prosody) as f:
+                a.prosody = parse_prosody(f.read())
+    except (ValueError, OSError) as e:
         ap.error(str(e))
     return a
 
@@ -679,4 +818,4 @@ if __name__ == '__main__':
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
          align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump,
-         f0_smooth=a.f0_smooth)
+         f0_smooth=a.f0_smooth, prosody=a.prosody)
