@@ -779,6 +779,46 @@ int64_t taco_griffinlim_fast_workspace_bytes(int B, int F);      /* B > 0, F >= 
 int taco_griffinlim_fast(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int frames_per_unit,
                          float momentum, float* wave, float* conv, void* workspace, int B, int F, int n_iter, void* stream);
 
+/* Initial phases read off the magnitudes (no reference counterpart: the reference draws them at random, audio.py:81): single-pass
+ * spectrogram inversion (Beauregard, Harish and Wyse, "Single pass spectrogram inversion", DSP 2015).  Every spectral peak of a frame
+ * is taken as a sinusoid: its frequency is refined by a parabola through three bins, its phase is advanced by hop x frequency from
+ * the previous frame, and the bins of its lobe are locked to it.  The result is the phase0 of the three Griffin-Lim entry points above.
+ *   mag_t  (B, 1025, F) fp32 magnitudes (taco_denorm_unframe's mag_t, or what the pitch / stretch calls made of it)
+ *   frames, frames_per_unit: as for the calls above (F_b = clamp(frames[b] * frames_per_unit, 0, F) in 64 bits, NULL: F); never read
+ *          by the host
+ *   phase0 (B, 1025, F) fp32 radians in [0, 2 pi), every element written;  workspace: taco_phase_estimate_workspace_bytes(B, F)
+ *          bytes, 4-byte aligned, arbitrary contents
+ * EXACT rules.  Only fp32 subtraction, multiplication, one IEEE division and integers, nothing contracted: a restatement in NumPy
+ * float32 / uint32 (tests/phase_estimate_ref.py) gives the device's bits.  K = 1025 bins, N = 2048, hop = 300; per row b and frame
+ * t < F_b, m[j] = |mag_t[b, j, t]|; acc[0 .. K-1] one unsigned 32-bit accumulator per bin and row, the phase at the centre of the
+ * frame in turns x 2^32, wrapping modulo 2^32, all zero in front of frame 0:
+ *   1. peaks: bin j is a peak when 1 <= j <= K - 2, m[j] > m[j-1] and m[j] >= m[j+1]
+ *   2. offset of a peak j, with a = m[j-1], b = m[j], c = m[j+1]: den = (a - 2 b) + c; p = 0 when den == 0, else
+ *      (0.5 (a - c)) / den clamped to [-0.5, 0.5]; q = (int) rint(p x 65536)
+ *   3. advance: adv[j] = (300 x (j x 65536 + q)) << 5 modulo 2^32 -- hop (j + p) / N turns in Q32 (300 x 2^32 / (2048 x 65536) =
+ *      300 x 32), in wrapping unsigned arithmetic, never in float
+ *   4. owner: left[j] the largest peak index <= j, right[j] the smallest peak index > j, either may be absent;
+ *      own[j] = right[j] when j < K - 1 and m[j+1] > m[j], else left[j] (a peak owns itself).  A bin whose owner is absent has none:
+ *      every bin of a frame without peaks, the bins left of the first peak that do not rise, the bins that rise into bin K - 1
+ *   5. update, all bins at once from the previous frame's accumulators: acc'[j] = acc[own[j]] + adv[own[j]] modulo 2^32 when j has
+ *      an owner, else acc'[j] = acc[j]
+ *   6. output: u = ((acc'[j] + (j << 31)) mod 2^32) >> 8; phase0[b, j, t] = (float) u x (2 pi / 2^24), one rounded fp32 product with
+ *      the fp32 constant.  The half turn per bin stands for the analysis window being centred in its 2048-sample frame
+ *   - phase0[b, :, t >= F_b] is exactly +0; columns t >= F_b of mag_t have no influence on anything (they may hold NaN);
+ *   - row b of a B-row call is bit-identical to a B = 1, F = F_b call on a contiguous copy of its first F_b columns;
+ *   - no atomics: the same arguments give the same bits; nothing is written outside phase0 and the workspace;
+ *   - a non-finite magnitude inside F_b does not fault; that row's phases are then unspecified.
+ * Two launches (B x ceil(F / 16) workgroups for peaks, owners and advances, B workgroups for the chain across frames), no
+ * allocation, no host synchronisation, no workgroup waits for another one: graph-capturable, and a replay follows whatever frames
+ * holds at replay time.  NULL mag_t / phase0 / workspace, B or F <= 0, frames_per_unit < 1 and phase0 overlapping mag_t return
+ * TACO_EINVAL, with a message "phase_estimate: ..." that names the argument, before anything is enqueued; the size function returns
+ * TACO_EINVAL for B or F <= 0.  TACO_VERSION did not change with these two entry points: detect them by the symbol.
+ * Not here: a parabola through log-magnitudes (better on stationary tones, but the device's logf is not NumPy's log: it would give
+ * up the bit-exact rule above). */
+int64_t taco_phase_estimate_workspace_bytes(int B, int F);       /* B > 0, F > 0, else TACO_EINVAL */
+int taco_phase_estimate(const float* mag_t, const int32_t* frames, int frames_per_unit, float* phase0, void* workspace, int B, int F,
+                        void* stream);
+
 /* Waveform finishing (no reference counterpart: the reference writes the pre-emphasised Griffin-Lim signal as it is,
  * audio.py:67-74).  Undoes the front end's pre-emphasis, optionally cuts leading / trailing silence by the front end's energy
  * rule, and emits fp32 samples and / or PCM16 by write_wav's rule, so that what leaves the device is finished audio.

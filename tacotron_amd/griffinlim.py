@@ -26,6 +26,9 @@ With `f0` (opt-in) the pitch of the magnitude frames is measured on the device (
 and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective stand-in for listening to those two controls.  With
 'smooth' in it every track is smoothed across frames (taco_f0_viterbi) before it is summarised.
 
+With `phase_init='estimate'` (opt-in) Griffin-Lim starts from phases read off the magnitudes (taco_phase_estimate: single-pass
+spectrogram inversion) instead of random ones; with n_iter = 0 that estimate alone is the waveform -- a draft voice at one synthesis pass.
+
 `finish_waveform(wave, lengths, r)` (opt-in) turns that waveform into finished audio on the device (taco_wave_finish): it undoes the
 front end's pre-emphasis, optionally trims silence by the front end's energy rule and emits fp32 samples and PCM16.
 
@@ -47,7 +50,7 @@ SR = 16000   # test.py:11
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
                        lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
-                       rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None):
+                       rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -98,7 +101,18 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     gains frames_out (B) and src (B, Fo) int32 -- the time map, (i << 16) | wq per output frame, -1 behind Fo_b -- behind the
     waveform: (waveform, frames_out, src) or (waveform, conv, frames_out, src).  frames_out / src: the caller's own buffers.  The
     f0 tracks behave as behind `pitch` / `rate`.  Neutral curves (65536 everywhere) give the bits of pitch=0 / rate=1.0.
+    phase_init (opt-in): None or 'random' -- the phase sources described above, bit for bit -- or 'estimate': the initial phases are
+    read off the magnitudes the vocoder is handed (lib.phase_estimate, taco_phase_estimate: single-pass spectrogram inversion), behind
+    pitch and behind the stretch, over each row's own frames (frames_out with per-unit 1 where there is a rate, like the 'vocoder' F0
+    track), and go in as phase0 to the entry point the path takes anyway; `seed` then has no influence.  With n_iter = 0 the
+    waveform is the estimate's own: one synthesis pass, a draft voice.  'estimate' together with phase0 is a ValueError.  Return
+    shapes do not change.
     Everything stays on the device.  F0 in Hz is SR / period."""
+    if phase_init not in (None, 'random', 'estimate'):
+        raise ValueError("invert_spectrogram: phase_init must be None, 'random' or 'estimate', got %r" % (phase_init,))
+    estimate = phase_init == 'estimate'
+    if estimate and phase0 is not None:
+        raise ValueError("invert_spectrogram: phase_init='estimate' excludes phase0: give one of them")
     track = None
     if f0 is not None and f0 is not False:
         opt = {} if f0 is True else dict(f0)
@@ -196,12 +210,16 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         phase0 = None if phase0 is None else phase0.contiguous()
         if track:   # (the stretched rows hold frames_out frames each, whatever `lengths` was)
             track('vocoder', stretched, frames_out, 1)
+        if estimate:
+            phase0 = lib.phase_estimate(stretched, frames_out, 1)
         if momentum is not None:
             res = lib.griffinlim_fast(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, momentum=momentum,
                                       frames_per_unit=1, want_conv=want_conv, out=wave, work=work)
             return done(((res[0], res[1]) if want_conv else (res,)) + tail)
         return done((lib.griffinlim_rows(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=1, out=wave,
                                          work=work),) + tail)
+    if estimate:   # (over the frames the vocoder runs on: every row's own with `lengths`, else all of them)
+        phase0 = lib.phase_estimate(mag_t, lengths, per_unit)
     if momentum is not None:
         return done(lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
                                         momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work))

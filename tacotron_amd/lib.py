@@ -146,6 +146,8 @@ EXPORTS = {
     'taco_griffinlim_rows': (C.c_int, [_P, _P, C.c_uint64, _P, _I, _P, _P, _I, _I, _I, _P]),
     'taco_griffinlim_fast_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_griffinlim_fast': (C.c_int, [_P, _P, C.c_uint64, _P, _I, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
+    'taco_phase_estimate_workspace_bytes': (C.c_int64, [_I, _I]),
+    'taco_phase_estimate': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _P]),
     'taco_wave_finish_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_wave_finish': (C.c_int, [_P, _P, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_wave_join_workspace_bytes': (C.c_int64, [_I, _I, _I]),
@@ -1354,6 +1356,33 @@ def griffinlim_fast(mag_t, frames=None, phase0=None, seed=0, n_iter=50, momentum
     _check(_lib.taco_griffinlim_fast(ptr(mag_t), ptr(phase0), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(frames), frames_per_unit,
                                      momentum, ptr(wave), ptr(conv), ptr(work), B, F, n_iter, stream_ptr()), 'taco_griffinlim_fast')
     return (wave, conv) if want_conv else wave
+
+
+def phase_estimate_workspace_bytes(B, F) -> int:
+    who = 'phase_estimate_workspace_bytes'
+    return _size('taco_phase_estimate_workspace_bytes', int_arg(who, 'B', B, 1, _INT_MAX), int_arg(who, 'F', F, 1, _INT_MAX))
+
+
+def phase_estimate(mag_t, frames=None, frames_per_unit=1, out=None, workspace=None):
+    """Initial phases for Griffin-Lim read off the magnitudes (include/taco_hip.h taco_phase_estimate; single-pass spectrogram
+    inversion): mag_t (B, 1025, F) fp32 on the device -> phase0 (B, 1025, F) fp32 radians, the `phase0` of griffinlim /
+    griffinlim_rows / griffinlim_fast.  Row b is estimated over its first F_b = clamp(frames[b] * frames_per_unit, 0, F) frames,
+    zeros behind.  frames: (B) int32 on the device, or None (all F frames).  out: the caller's own phase0; workspace: uint8,
+    phase_estimate_workspace_bytes(B, F) bytes; default: fresh ones.  Enqueued on the current stream; nothing is read back and
+    nothing waits."""
+    who = 'phase_estimate'
+    B, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 1025, 'F'))
+    dev = mag_t.device
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    out = _own_or_given(out, (B, 1025, F), torch.float32, dev, who + ': out')
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
+    if workspace is not None:
+        tensor_arg(who, 'workspace', workspace, torch.uint8, ('bytes',), dev)
+    on_gpu(who, 'mag_t', dev)
+    workspace = _own_or_given(workspace, (phase_estimate_workspace_bytes(B, F),), torch.uint8, dev, who + ': workspace')
+    _check(_lib.taco_phase_estimate(ptr(mag_t), ptr(frames), frames_per_unit, ptr(out), ptr(workspace), B, F, stream_ptr()),
+           'taco_phase_estimate')
+    return out
 
 
 def wave_finish_workspace_floats(B, L) -> int:

@@ -10,6 +10,11 @@ drawn on the device, so prompt_NNN.wav is the Griffin-Lim of that prompt alone.
 --gl-momentum A (opt-in, not in the reference): fast Griffin-Lim rounds with momentum A in [0, 1) (lib.griffinlim_fast), phases drawn
 on the device; prompt_NNN_conv.npy holds the prompt's n_iter + 1 spectral-convergence values and the batch's worst final value is
 printed.  --gl-iters N: the number of rounds (default 50, the reference's).  Both combine with --stop / --vocode-lengths.
+--gl-init {random,estimate} (opt-in, not in the reference; default random: every file is what it was): with `estimate` Griffin-Lim
+starts from phases read off the magnitudes it is handed (lib.phase_estimate, taco_phase_estimate: every spectral peak a sinusoid
+advanced by hop x its frequency, its lobe locked to it) instead of random ones.  --gl-iters 0 --gl-init estimate is the draft voice:
+no Griffin-Lim round at all, one synthesis pass from the estimate.  Measured on fp64 restatements only; nobody has listened to it.  It
+combines with everything the vocoder combines with; with --gl-momentum the convergence line is printed as it is.
 --deemphasis [A] / --trim-db DB (opt-in, not in the reference): the waveform is finished on the device (griffinlim.finish_waveform,
 taco_wave_finish): de-emphasis with A in [0, 1) (0.97 when A is left out: the inverse of the training features' pre-emphasis) and / or
 the front end's energy trim at DB > 0 decibels below the loudest frame.  prompt_NNN.wav is then written from the device's int16
@@ -255,10 +260,14 @@ def f0_lines(who, f0row, asked_step=None, rate_step=None, prosody=False):
 
 
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, path_jump=None):
+                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, gl_init=None, path_jump=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
     without --timings; `f0_smooth`: None / False, True or the number of candidates; `prosody`: None / False or anything else for
-    given); ValueError."""
+    given; `gl_init`: None, 'random' or 'estimate'); ValueError."""
+    if gl_init not in (None, 'random', 'estimate'):
+        raise ValueError("gl_init (--gl-init) must be 'random' or 'estimate', got %r" % (gl_init,))
+    if gl_init == 'estimate' and not vocode:
+        raise ValueError('gl_init (--gl-init) estimates the phases Griffin-Lim starts from: it needs vocode')
     if prosody is not None and prosody is not False:
         if not vocode:
             raise ValueError('prosody (--prosody) shapes the magnitudes in front of Griffin-Lim: it needs vocode')
@@ -353,7 +362,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
          gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None,
-         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None):
+         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None, gl_init=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -410,9 +419,13 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     only when a pitch is asked for anywhere).  prompt_NNN.wav holds 300 (Fo_b - 1) samples, Fo_b the stretch's frames_out (with finishing
     the row ends there on the device); prompt_NNN_prosody.npy the per-character (dur_q, step_q); _rate.npy / _pitch.npy are not written.
     With `timings` the word rows go through the stretch's time map (alignment.word_times(src=...)); with `f0` the line is the drift
-    line without a figure asked for."""
+    line without a figure asked for.
+    `gl_init` (needs `vocode` for 'estimate'): None or 'random' -- every file is what it was -- or 'estimate': Griffin-Lim starts from
+    phases read off the magnitudes it is handed (invert_spectrogram(phase_init='estimate'), lib.phase_estimate), on whichever path the
+    other options choose; with n_iter = 0 the waveform is the estimate's own synthesis pass.  No file changes its size."""
     check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
-                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody)
+                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody, gl_init=gl_init)
+    gl_init = None if gl_init == 'random' else gl_init
     if prosody is not None and prosody is not False:
         lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
     else:
@@ -505,14 +518,14 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                 curves = [lib.path_curve(found[0], values[k], config.r, one)[:, :Fm].contiguous()
                           for k, one in ((0, lib.STRETCH_ONE), (1, lib.PITCH_ONE)) if k == 0 or pros_pitch]
                 res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, lengths=model.lengths, rate_curve=curves[0],
+                                         want_conv=gl_momentum is not None, phase_init=gl_init, lengths=model.lengths, rate_curve=curves[0],
                                          pitch_curve=curves[1] if pros_pitch else None, lifter=lifter, dur_q_max=pros_max, **shift)
             elif steps is None:
                 res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, lengths=model.lengths if vocode_lengths else None, **shift)
+                                         want_conv=gl_momentum is not None, phase_init=gl_init, lengths=model.lengths if vocode_lengths else None, **shift)
             else:   # (the rows' own frames whenever there is a rule: the host's Fo_b and the device's frames_out are then one number)
                 res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, lengths=model.lengths if stop is not None else None,
+                                         want_conv=gl_momentum is not None, phase_init=gl_init, lengths=model.lengths if stop is not None else None,
                                          rate=[q / 65536.0 for q in row_steps[n:n + Bn]], **shift)
             res = list(res) if isinstance(res, tuple) else [res]   # waveform [, conv] [, frames_out] [, tracks]
             if f0 is not None:
@@ -737,6 +750,10 @@ def parse_args(argv=None):
     ap.add_argument('--gl-momentum', type=float, default=None,
                     help='fast Griffin-Lim rounds with this momentum in [0, 1) (0.99: librosa\'s default); writes prompt_NNN_conv.npy')
     ap.add_argument('--gl-iters', type=int, default=50, help='Griffin-Lim rounds (the reference: 50)')
+    ap.add_argument('--gl-init', choices=('random', 'estimate'), default='random',
+                    help='where Griffin-Lim starts: random phases (the default; every file is what it was), or an estimate read off the '
+                         'magnitudes on the device (single-pass spectrogram inversion); --gl-iters 0 --gl-init estimate is a draft voice '
+                         'without any round (not in the reference; nobody has listened to it)')
     ap.add_argument('--deemphasis', type=float, nargs='?', const=0.97, default=None, metavar='A',
                     help='undo the training features\' pre-emphasis on the device: y[n] = x[n] + A y[n-1], A in [0, 1) (default 0.97)')
     ap.add_argument('--trim-db', type=float, default=None, metavar='DB',
@@ -798,7 +815,7 @@ def parse_args(argv=None):
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
                       lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings or a.prosody is not None else None,
-                      prosody=a.prosody)
+                      prosody=a.prosody, gl_init=a.gl_init)
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -818,4 +835,4 @@ if __name__ == '__main__':
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
          align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump,
-         f0_smooth=a.f0_smooth, prosody=a.prosody)
+         f0_smooth=a.f0_smooth, prosody=a.prosody, gl_init=a.gl_init)
