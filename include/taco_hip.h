@@ -896,6 +896,78 @@ int taco_wave_join(const float* pieces, int64_t pitch, const int32_t* bounds, co
                    float* out, int16_t* pcm, int32_t* offsets, int32_t* total, float* peak, void* workspace,
                    int N, int P, int L, int Lj, void* stream);
 
+/* Loudness (no reference counterpart: the reference writes whatever level the checkpoint produced).  Measures the integrated
+ * loudness of finished rows by ITU-R BS.1770 -- K-weighting, 400 ms blocks at 75 % overlap, an absolute and a relative gate -- and
+ * optionally emits the rows at a target loudness under a ceiling on the sample peak, as fp32 and / or PCM16.
+ *
+ * taco_k_weighting is a HOST function (no GPU call): coef = b0 b1 b2 a1 a2 of the shelf, then b0 b1 b2 a1 a2 of the high-pass, in
+ * fp64, for sr a multiple of 10 with 8000 <= sr <= 48000 (else TACO_EINVAL; NULL coef likewise):
+ *   shelf      f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, K = tan(pi f0 / sr), Vh = 10^(G/20),
+ *              Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2, b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],
+ *              a1 = 2 (K^2 - 1)/a0, a2 = (1 - K/Q + K^2)/a0
+ *   high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi f0 / sr), d = 1 + K/Q + K^2, b = [1, -2, 1],
+ *              a1 = 2 (K^2 - 1)/d, a2 = (1 - K/Q + K^2)/d
+ * which is the standard's table at 48 kHz.  The device uses these values rounded once to fp32.
+ *
+ * taco_wave_loudness:
+ *   wave    (B, L) fp32, contiguous: the rows taco_wave_finish writes to `out`, or the rows taco_wave_join writes
+ *   samples (B) int32 on the DEVICE, or NULL: n_b = clamp(samples[b], 0, L); NULL: n_b = L.  The host reads nothing from it
+ *   sr      as for taco_k_weighting;  target_lufs in [-70, 0];  ceiling in (0, 1], on |sample|
+ *   out     (B, L) fp32, nullable;  pcm (B, L) int16, nullable.  With both NULL the call measures only and neither target_lufs nor
+ *           ceiling is looked at
+ *   loud    (B, 4) fp32 = (I, M, g, peak_out) and blocks (B, 4) int32 = (nb, blocks past the absolute gate, blocks past both
+ *           gates, limited), both required
+ * Per row b, in this order:
+ *   1. K-weighting  y = highpass(shelf(x[0 : n_b])) from a zero state, each biquad in the transposed direct form II in fused
+ *      multiply-adds: u = b0 x + s1; s1 = -a1 u + (b1 x + s2); s2 = -a2 u + b2 x; y = u + t1; t1 = -a1' y + (-2 u + t2);
+ *      t2 = -a2' y + u.  With S = (s1, s2, t1, t2) a sample is S -> M S + v x for a constant 4 x 4 matrix M, so k samples are
+ *      S -> M^k S + R.  Evaluated as a scan of these maps over chunks of TACO_LOUD_CHUNK = 2048 samples at fixed positions of the
+ *      row, a thread owning 8 consecutive samples: the thread's run from a zero state; a scan over the 64 lanes of a wave in steps of
+ *      1, 2, ..., 32 lanes (X_l += M^(8 d) X_(l-d)); the four waves of a chunk in order with M^512; the state that enters chunk c by
+ *      the same scan over the chunks' end states, 64 chunks at a time in order, in steps of 1, 2, ..., 32 chunks with M^(2048 d), the
+ *      state that enters a group of 64 folded into its first chunk's end state with M^2048; the state entering the wave folded into
+ *      lane 0's end state (with M^8) and the lane scan once more -- all of this in
+ *      fp64, with the fp32 coefficients widened and the powers of M formed from them on the host in fp64 by repeated squaring
+ *      (nothing assumes that a power is negligible); the state that enters a thread's run is then rounded to fp32 once and the
+ *      thread's run AGAIN from it, in fp32 by the recursion above, yields y.  The fp64 part is there because the high-pass has a
+ *      double pole at radius 0.985 to 0.995: fp32 runs from a zero state leave 1e-3 of a constant input in y at 48 kHz
+ *   2. hops and blocks  H = sr / 10, nh = n_b / H.  h_k = the sum of the rounded fp32 squares y^2 over hop k: 64 partial sums, partial
+ *      l adding samples l, l + 64, ... of the hop in that order, then a fixed tree over the 64.  nh >= 4: nb = nh - 3 blocks,
+ *      z_j = (((h_j + h_j+1) + h_j+2) + h_j+3) / (4 H), one IEEE division.  1 <= n_b < 4 H: ONE block over all samples,
+ *      z_0 = sum(y^2) / n_b (the same 64-way sum over [0, n_b)) -- a stated deviation from BS.1770, which leaves a signal shorter
+ *      than 400 ms unmeasured.  n_b == 0: no block
+ *   3. gates, in the power domain (no logarithm takes part in a decision): block j passes the absolute gate when z_j > Z_ABS = the
+ *      fp32 value of 10^((-70 + 0.691)/10); with m_A the mean of those (256 partial sums, partial t adding blocks t, t + 256, ...,
+ *      a fixed tree, one division by the count), it passes the relative gate when also z_j > 0.1f m_A; z_I = the mean of the
+ *      blocks past both, summed likewise
+ *   4. readings  I = -0.691 + 10 log10(z_I), -inf when no block passes; M = -0.691 + 10 log10(max_j z_j), -inf without a block or
+ *      with z = 0; both formed in fp64 from the fp32 means and rounded once
+ *   5. gain (only with out or pcm)  peak_in = max |x| over [0, n_b), exact.  g = 10^((target_lufs - I)/20) (fp64, rounded once);
+ *      when the fp32 product peak_in g > ceiling: g = ceiling / peak_in (one IEEE fp32 division), limited = 1.  g = 1, limited = 0
+ *      when I is -inf or peak_in is 0.  out[b, n] = x[n] g, one rounded fp32 multiply, no contraction; peak_out = max |out| (exact:
+ *      it is the rounded product peak_in g);  pcm[b, n] = (int16) trunc(v * 32767.0f) with v = out clamped to [-1, 1] first.
+ *      Everything from n_b to L is exactly 0 in out and pcm.  Measure-only: g = 1, limited = 0, peak_out = peak_in
+ *   - every element of out, pcm, loud and blocks is written and nothing outside them, for any L and any alignment of out and pcm
+ *     (16-byte / 8-byte stores where the row's address allows, scalar ones at a row's two edges); the workspace may hold arbitrary
+ *     bytes;
+ *   - no atomics: the same arguments give the same bits;
+ *   - row b of a B-row call is bit-identical to a B = 1, L = n_b call on a contiguous copy of x[b, 0 : n_b] (n_b >= 1);
+ *   - x[b, n >= n_b] has no influence on anything (it may hold NaN); non-finite samples inside n_b do not fault, the row's values
+ *     are then unspecified;
+ *   - out may alias wave (out == wave): the map is elementwise and nothing is shifted, unlike taco_wave_finish.
+ * No allocation, no host synchronisation, no workgroup waits for another one: graph-capturable, and a replay follows whatever
+ * samples holds at replay time.  Five to seven launches.  workspace: taco_wave_loudness_workspace_bytes bytes, 16-byte aligned (y, the
+ * chunks' end states, carries and maxima, the hop sums).  NULL wave / loud / blocks / workspace, B <= 0, L <= 0, an sr that taco_k_weighting refuses and -- with out
+ * or pcm -- target_lufs outside [-70, 0] or NaN, ceiling outside (0, 1] or NaN return TACO_EINVAL, with a message
+ * "wave_loudness: ...", before anything is enqueued; the size function returns TACO_EINVAL for the same shapes.  TACO_VERSION did not
+ * change with these entry points: detect them by the symbol.
+ * Not here: loudness range and short-term loudness, true-peak (oversampled) limiting, more than one channel. */
+#define TACO_LOUD_CHUNK 2048
+int taco_k_weighting(int sr, double coef[10]);
+int64_t taco_wave_loudness_workspace_bytes(int B, int L, int sr);   /* B > 0, L > 0, sr as above, else TACO_EINVAL */
+int taco_wave_loudness(const float* wave, const int32_t* samples, int sr, float target_lufs, float ceiling, float* out, int16_t* pcm,
+                       float* loud, int32_t* blocks, void* workspace, int B, int L, void* stream);
+
 /* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
 /* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length
  * 1200, hop_length 300, pre-emphasis 0.97, log(|.| + 1e-8), 80 mels): librosa.effects.trim (0.6 form: frame mean squares at

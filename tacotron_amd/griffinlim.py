@@ -279,3 +279,26 @@ def join_waveform(pieces, bounds, first, kinds, pause_ms=(300.0, 150.0, 0.0), fa
     fade_ms milliseconds at every interior edge.  The defaults (300 / 150 / 0 ms pauses, 5 ms ramps) are choices, not tuned by ear.
     Keywords go to lib.wave_join (Lj, want_out, want_pcm and the caller's own buffers)."""
     return lib.wave_join(pieces, bounds, first, join_gaps(kinds, pause_ms), fade=join_samples(fade_ms), **kw)
+
+
+def level_waveform(fin, bounds=None, total=None, target=-23.0, ceiling_db=-1.0, sr=SR, **kw):
+    """fin (B, L) finished fp32 rows -> (out, pcm, loud, blocks) of lib.wave_loudness: every row measured by ITU-R BS.1770 over its own
+    samples and emitted at `target` LUFS (-23: EBU R 128) with its sample peak at or below ceiling_db decibels re full scale (<= 0).
+    bounds: (B, 2) int32 on the device as finish_waveform returns them -- row b holds bounds[b, 1] - bounds[b, 0] samples; total: (B)
+    int32 on the device as join_waveform returns it -- row b holds total[b]; neither: every row holds L samples.  The counts are
+    formed by torch ops on the device; nothing is read back.  target None measures only.  Keywords go to lib.wave_loudness (want_out,
+    want_pcm and the caller's own buffers)."""
+    if bounds is not None and total is not None:
+        raise ValueError('level_waveform: give bounds (of finish_waveform) or total (of join_waveform), not both')
+    B = fin.shape[0] if torch.is_tensor(fin) and fin.dim() == 2 else None
+    samples = None
+    if bounds is not None:
+        lib.tensor_arg('level_waveform', 'bounds', bounds, torch.int32, (B, 2), fin.device)
+        samples = (bounds[:, 1] - bounds[:, 0]).contiguous()
+    elif total is not None:
+        lib.tensor_arg('level_waveform', 'total', total, torch.int32, (B,), fin.device)
+        samples = total
+    ceiling_db = float(ceiling_db)
+    if not ceiling_db <= 0.0 or math.isinf(ceiling_db):
+        raise ValueError('level_waveform: ceiling_db must be a finite number of decibels <= 0, got %r' % (ceiling_db,))
+    return lib.wave_loudness(fin, samples, sr=sr, target=target, ceiling=10.0 ** (ceiling_db / 20.0), **kw)

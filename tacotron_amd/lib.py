@@ -153,6 +153,9 @@ EXPORTS = {
     'taco_wave_join_workspace_bytes': (C.c_int64, [_I, _I, _I]),
     'taco_wave_join': (C.c_int, [_P, C.c_int64, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
                                  _P]),
+    'taco_k_weighting': (C.c_int, [_I, C.POINTER(C.c_double)]),
+    'taco_wave_loudness_workspace_bytes': (C.c_int64, [_I, _I, _I]),
+    'taco_wave_loudness': (C.c_int, [_P, _P, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_wave_resample': (C.c_int, [_P, C.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
@@ -1481,6 +1484,72 @@ def wave_join(pieces, bounds, first, gap, fade=0, Lj=None, want_out=True, want_p
                                fade, ptr(out), ptr(pcm), ptr(offsets), ptr(total), ptr(peak), ptr(work), N, P, L, Lj, stream_ptr()),
            'taco_wave_join')
     return out, pcm, offsets, total, peak
+
+LOUD_CHUNK = 2048   # TACO_LOUD_CHUNK: the samples of a row that one workgroup of taco_wave_loudness filters
+
+
+def _loud_sr(who, sr) -> int:
+    sr = int_arg(who, 'sr', sr, 8000, 48000)
+    if sr % 10:
+        raise ValueError('%s: sr must be a multiple of 10 (a hop is sr / 10 samples), got %d' % (who, sr))
+    return sr
+
+
+def k_weighting(sr):
+    """The K-weighting of ITU-R BS.1770 at sample rate sr (include/taco_hip.h taco_k_weighting; a host function): ten floats,
+    b0 b1 b2 a1 a2 of the shelf, then of the high-pass.  sr: a multiple of 10 in [8000, 48000]."""
+    sr = _loud_sr('k_weighting', sr)
+    coef = (C.c_double * 10)()
+    _check(_lib.taco_k_weighting(sr, coef), 'taco_k_weighting')
+    return [float(c) for c in coef]
+
+
+def wave_loudness_workspace_floats(B, L, sr) -> int:
+    return _size('taco_wave_loudness_workspace_bytes', B, L, sr) // 4
+
+
+def wave_loudness(wave, samples=None, sr=16000, target=None, ceiling=1.0, want_out=None, want_pcm=None, out=None, pcm=None, loud=None,
+                  blocks=None, work=None):
+    """Integrated loudness and a target level (include/taco_hip.h taco_wave_loudness): wave (B, L) fp32 -> (out (B, L) fp32 or None,
+    pcm (B, L) int16 or None, loud (B, 4) fp32 = (I, M, g, peak_out), blocks (B, 4) int32 = (nb, past the absolute gate, past both
+    gates, limited)).  Per row: the K-weighted mean squares of 400 ms blocks at 75 % overlap over its first n_b samples, gated at
+    -70 LUFS and at 10 LU below the mean of what is left, give I (LUFS) and the maximum momentary loudness M; a row shorter than
+    400 ms is one block.  target None: measure only (g = 1; out and pcm stay None).  target in [-70, 0] LUFS: out = wave * g with
+    g = 10^((target - I) / 20), or ceiling / max |wave| where that would carry the peak above ceiling, in (0, 1]; pcm = PCM16 of
+    out, zeros behind n_b.  samples (B) int32 on the device, or None: every row has L samples.  want_out / want_pcm default to
+    whether there is a target.  out / pcm / loud / blocks / work: the caller's own buffers (work:
+    wave_loudness_workspace_floats(B, L, sr) floats); default: fresh ones.  An out / pcm buffer implies want_out / want_pcm; out may
+    be wave itself."""
+    who = 'wave_loudness'
+    B, L = tensor_arg(who, 'wave', wave, torch.float32, ('B', 'L'))
+    dev = wave.device
+    tensor_arg(who, 'samples', samples, torch.int32, (B,), dev, optional=True)
+    sr = _loud_sr(who, sr)
+    want_out = (target is not None if want_out is None else bool(want_out)) or out is not None
+    want_pcm = (target is not None if want_pcm is None else bool(want_pcm)) or pcm is not None
+    if target is None:
+        if want_out or want_pcm:
+            raise ValueError('%s: out and pcm need a target (target=None measures only)' % who)
+        target, ceiling = 0.0, 1.0
+    else:
+        target, ceiling = float(target), float(ceiling)
+        if not -70.0 <= target <= 0.0:   # (NaN fails)
+            raise ValueError('%s: target must be in [-70, 0] LUFS, got %r' % (who, target))
+        if not 0.0 < ceiling <= 1.0 or C.c_float(ceiling).value <= 0.0:
+            raise ValueError('%s: ceiling must be in (0, 1], got %r' % (who, ceiling))
+        if not (want_out or want_pcm):
+            raise ValueError('%s: a target needs at least one of out and pcm' % who)
+    out = _own_or_given(out, (B, L), torch.float32, dev, who + ': out') if want_out else None
+    pcm = _own_or_given(pcm, (B, L), torch.int16, dev, who + ': pcm') if want_pcm else None
+    loud = _own_or_given(loud, (B, 4), torch.float32, dev, who + ': loud')
+    blocks = _own_or_given(blocks, (B, 4), torch.int32, dev, who + ': blocks')
+    if work is not None:
+        tensor_arg(who, 'work', work, torch.float32, ('floats',), dev)
+    on_gpu(who, 'wave', dev)
+    work = _own_or_given(work, (wave_loudness_workspace_floats(B, L, sr),), torch.float32, dev, who + ': work')
+    _check(_lib.taco_wave_loudness(ptr(wave), ptr(samples), sr, target, ceiling, ptr(out), ptr(pcm), ptr(loud), ptr(blocks), ptr(work),
+                                   B, L, stream_ptr()), 'taco_wave_loudness')
+    return out, pcm, loud, blocks
 
 
 def audio_features_workspace_bytes(B, L) -> int:

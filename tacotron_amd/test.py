@@ -79,7 +79,15 @@ prompt_NNN_prosody.npy holds the per-character (dur_q, step_q) as int32 (in plac
 rows go through the stretch's time map; with --f0 the line gives the drift of the mean log-F0 with no "asked" figure.  A word's
 characters share one value and the curve steps at its edges: no ramps across word boundaries.  Refused with --long: the pieces
 re-index the words of a prompt, which is out of scope here.  Nobody has listened to the result.  Without it every file is what it
-was."""
+was.
+--loudness LUFS [--peak-db DB] (opt-in, not in the reference): the level.  The finished rows are measured on the device by ITU-R
+BS.1770 -- K-weighting, 400 ms blocks, an absolute and a relative gate (griffinlim.level_waveform, taco_wave_loudness) -- and written
+at LUFS, -70 <= LUFS <= 0 (-23: EBU R 128; -16 to -19: voice assistants and podcasts), with the sample peak at or below DB decibels re
+full scale (default -1, <= 0); where the ceiling binds, the gain is what the ceiling allows.  It implies finishing, as --long does
+(de-emphasis and trim stay off unless asked for).  prompt_NNN.wav holds the device's int16 samples, prompt_NNN_loud.npy holds
+(I, M, g, peak_out, nb, past_abs, past_both, limited) as float64 and one line per prompt gives the loudness before and after.  A prompt
+shorter than 400 ms is measured as one block (the standard leaves it unmeasured).  With --long the JOINED prompt is levelled, so its
+pieces keep their relative levels.  It combines with every option above; without it every file is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -94,7 +102,7 @@ import torch
 from .config import Config
 from .alignment import attention_png, encoded_chars, flags, path_line, scores_row, word_times, word_values, words_tsv
 from .data import KIND_NAMES, load_prompts, split_prompt
-from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform
+from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform, level_waveform
 from .model import Tacotron
 from .params import ParamBuffer
 from . import lib
@@ -103,6 +111,7 @@ SR = 16000   # test.py:11
 PAUSE_MS = (300.0, 150.0, 0.0)   # --long: silence behind a SENTENCE / CLAUSE / WORD cut; choices, not tuned by anyone's ear
 FADE_MS = 5.0                    # --long: the ramp at every interior edge; likewise
 JOIN_GROUP = 256                 # --long: pieces per lib.wave_join call (a group ends at the first prompt boundary at or past it)
+PEAK_DB = -1.0                   # --loudness: the ceiling on the sample peak, decibels re full scale
 
 
 def write_wav(path, samples, sr=SR):
@@ -259,11 +268,38 @@ def f0_lines(who, f0row, asked_step=None, rate_step=None, prosody=False):
     return out
 
 
+def loud_row(loud, blocks):
+    """a row of lib.wave_loudness's loud (4) and blocks (4) -> the 8 float64 values of prompt_NNN_loud.npy"""
+    return np.concatenate([np.asarray(loud, dtype=np.float64), np.asarray(blocks, dtype=np.float64)])
+
+
+def loud_line(who, row, peak_db=PEAK_DB):
+    """the line --loudness prints for `who` from its loud_row"""
+    I, g, limited = float(row[0]), float(row[2]), int(row[7])
+    if not np.isfinite(I):
+        return '%s: no block above the gates, level unchanged' % who
+    after = I + 20.0 * np.log10(g)
+    if limited:
+        return '%s: %.1f LUFS -> %.1f, limited by the %g dB ceiling' % (who, I, after, peak_db)
+    return '%s: %.1f LUFS -> %.1f (gain %+.1f dB)' % (who, I, after, 20.0 * np.log10(g))
+
+
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, gl_init=None, path_jump=None):
+                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, gl_init=None, loudness=None, peak_db=None,
+                  path_jump=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
     without --timings; `f0_smooth`: None / False, True or the number of candidates; `prosody`: None / False or anything else for
-    given; `gl_init`: None, 'random' or 'estimate'); ValueError."""
+    given; `gl_init`: None, 'random' or 'estimate'; `peak_db`: None for not given); ValueError."""
+    if loudness is not None:
+        if not vocode:
+            raise ValueError('loudness (--loudness) levels the waveform: it needs vocode')
+        if not -70.0 <= float(loudness) <= 0.0:   # (NaN fails)
+            raise ValueError('loudness (--loudness) must be in [-70, 0] LUFS, got %r' % (loudness,))
+    if peak_db is not None:
+        if loudness is None:
+            raise ValueError('peak_db (--peak-db) is the ceiling of loudness (--loudness): it needs loudness')
+        if not float(peak_db) <= 0.0 or np.isinf(float(peak_db)):
+            raise ValueError('peak_db (--peak-db) must be a finite number of decibels <= 0, got %r' % (peak_db,))
     if gl_init not in (None, 'random', 'estimate'):
         raise ValueError("gl_init (--gl-init) must be 'random' or 'estimate', got %r" % (gl_init,))
     if gl_init == 'estimate' and not vocode:
@@ -310,7 +346,7 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None, f0=None, dur=None, prosody=None):
+                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -323,7 +359,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     written as _f0.npy.
     dur (--timings): the steps of each of the prompt's characters, written as _dur.npy (int32).
     prosody (--prosody): (the prompt's (L, 2) per-character (dur_q, step_q), Fo_b): the table is written as _prosody.npy (int32); wav is
-    then the waveform behind the stretch curve and keeps 300 (Fo_b - 1) samples, whatever len_b says."""
+    then the waveform behind the stretch curve and keeps 300 (Fo_b - 1) samples, whatever len_b says.
+    loud (--loudness): the prompt's loud_row, written as _loud.npy (float64); pcm then holds the levelled samples."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -355,6 +392,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_trim.npy', trim)
     if conv is not None:
         np.save(path + '_conv.npy', conv)
+    if loud is not None:
+        np.save(path + '_loud.npy', np.asarray(loud, dtype=np.float64))
     if ascore is not None:
         np.save(path + '_ascore.npy', np.asarray(ascore, dtype=np.float64))
         attention_png(path + '_align.png', align, zoom=zoom)
@@ -362,7 +401,7 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
 
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
          gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None,
-         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None, gl_init=None):
+         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None, gl_init=None, loudness=None, peak_db=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -422,9 +461,16 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     line without a figure asked for.
     `gl_init` (needs `vocode` for 'estimate'): None or 'random' -- every file is what it was -- or 'estimate': Griffin-Lim starts from
     phases read off the magnitudes it is handed (invert_spectrogram(phase_init='estimate'), lib.phase_estimate), on whichever path the
-    other options choose; with n_iter = 0 the waveform is the estimate's own synthesis pass.  No file changes its size."""
+    other options choose; with n_iter = 0 the waveform is the estimate's own synthesis pass.  No file changes its size.
+    `loudness` (needs `vocode`) / `peak_db`: None, or the target in LUFS in [-70, 0] and the ceiling on the sample peak in decibels
+    <= 0 (None: -1).  The waveform is finished on the device as with `long` (without `deemphasis` / `trim_db`: bounds [0, n_b)) and
+    the finished rows are levelled there (level_waveform over each row's own e - s samples); with `long` the JOINED prompts are
+    levelled, after join_waveform.  prompt_NNN.wav holds the levelled int16 samples, prompt_NNN_loud.npy the prompt's loud_row, and
+    loud_line() is printed per prompt.  Without it lib.wave_loudness is never reached and every file is what it was."""
     check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
-                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody, gl_init=gl_init)
+                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody, gl_init=gl_init, loudness=loudness,
+                  peak_db=peak_db)
+    level = None if loudness is None else dict(target=float(loudness), ceiling_db=PEAK_DB if peak_db is None else float(peak_db))
     gl_init = None if gl_init == 'random' else gl_init
     if prosody is not None and prosody is not False:
         lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
@@ -438,7 +484,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     long = long_options(long)
     if long is not None and not vocode:
         raise ValueError('long (--long) joins waveforms: it needs vocode')
-    finish = deemphasis is not None or trim_db is not None or long is not None
+    finish = deemphasis is not None or trim_db is not None or long is not None or level is not None
     meta_path = os.path.join(config.data_path, 'meta.pkl')
     if os.path.exists(meta_path):
         with open(meta_path, 'rb') as f:
@@ -462,8 +508,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     os.makedirs(out_dir, exist_ok=True)
 
     def synthesise(batch, n, out_rows=None, bounds_rows=None):
-        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved), host
-        arrays or None.  curved (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
+        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved, louds),
+        host arrays or None.  louds (`loudness` without `long`): the batch's loud_rows (B, 8); pcm then is the levelled one.  curved (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
         out_rows / bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made.
         f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
         lib.f0_viterbi counts (B, 4))"""
@@ -492,7 +538,8 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
         mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
         std = torch.as_tensor(std, dtype=torch.float32).cuda()
         spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = conv = pcm = trim = f0res = curved = None
+        wav = conv = pcm = trim = f0res = curved = louds = None
+        level_rows = level is not None and out_rows is None   # (`long` levels the joined prompts instead)
         if vocode:
             fout = None
             shift = {}
@@ -547,25 +594,30 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                       % (gl_momentum, n_iter, float(conv[:, -1].max())))
             if finish and fout is not None:   # (a rate: the row ends where the stretch says; `long`: the rows are wider than this batch's)
                 fin, pcm, trim, _ = finish_waveform(wav, fout, 1, deemphasis=0.0 if deemphasis is None else deemphasis,
-                                                    trim_top_db=0.0 if trim_db is None else trim_db, want_out=out_rows is not None,
-                                                    want_pcm=out_rows is None, bounds=bounds_rows)
+                                                    trim_top_db=0.0 if trim_db is None else trim_db,
+                                                    want_out=out_rows is not None or level_rows,
+                                                    want_pcm=out_rows is None and not level_rows, bounds=bounds_rows)
                 if out_rows is not None:
                     out_rows[:, :fin.shape[1]].copy_(fin)
-                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
             elif finish:   # (the fp32 waveform stays on the device)
-                _, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
-                                                  deemphasis=0.0 if deemphasis is None else deemphasis,
-                                                  trim_top_db=0.0 if trim_db is None else trim_db, want_out=out_rows is not None,
-                                                  want_pcm=out_rows is None, out=out_rows, bounds=bounds_rows)
-                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
+                fin, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
+                                                    deemphasis=0.0 if deemphasis is None else deemphasis,
+                                                    trim_top_db=0.0 if trim_db is None else trim_db,
+                                                    want_out=out_rows is not None or level_rows,
+                                                    want_pcm=out_rows is None and not level_rows, out=out_rows, bounds=bounds_rows)
             else:
                 wav = wav.cpu().numpy()
+            if finish:
+                if level_rows:   # (the finished fp32 rows stay on the device; their PCM16 is the levelled one)
+                    _, pcm, loud, blocks = level_waveform(fin, bounds=trim, want_out=False, want_pcm=True, **level)
+                    louds = np.stack([loud_row(a, b) for a, b in zip(loud.cpu().numpy(), blocks.cpu().numpy())])
+                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         if scores is not None:
             scores = np.stack([scores_row(c, m) for c, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
         if paths is not None:
             paths = tuple(x.cpu().numpy() for x in paths)
-        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res, paths, curved
+        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res, paths, curved, louds
 
     def marks(score, L):
         """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
@@ -628,18 +680,20 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
             row_steps = [steps[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
             L = 300 * (max(5, lib.stretch_capacity(F, min(row_steps, default=lib.STRETCH_ONE))) - 1)
         n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of, f0_of,
-                       timing_of if timings else None, write_words)
+                       timing_of if timings else None, write_words, level)
         print('wrote %d samples to %s' % (n, out_dir))
         return n
     for batch in load_prompts(prompts, ivocab):
         Bn = batch['text'].shape[0]
-        spec, al, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved = synthesise(batch, n)
+        spec, al, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved, louds = synthesise(batch, n)
         for i in range(Bn):
-            wi, len_b, pi, ti, ci, si = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores))
+            wi, len_b, pi, ti, ci, si, li = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores, louds))
             dur, words = timing_of(n, i, len_b, ti, paths, int(batch['text_length'][i]), prompts[n], 'prompt %d' % n, curved=curved)
             write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
                          rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n, curved), dur=dur,
-                         prosody=None if curved is None else (pros[n], int(curved[0][i])))
+                         prosody=None if curved is None else (pros[n], int(curved[0][i])), loud=li)
+            if li is not None:
+                print(loud_line('prompt %d' % n, li, level['ceiling_db']))
             if words is not None:
                 write_words(n, words)
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
@@ -651,11 +705,11 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
 
 
 def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None,
-               pitch_of=lambda row: None, f0_of=lambda row, i, len_b, f0res, who: None, timing_of=None, write_words=None):
+               pitch_of=lambda row: None, f0_of=lambda row, i, len_b, f0res, who: None, timing_of=None, write_words=None, level=None):
     """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write.  L: the samples
     per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b) / pitch_of(row) / f0_of(row, i, len_b, f0res,
     who): what write_prompt gets as `rate` / `pitch` / `f0`; timing_of / write_words (`timings`): test()'s own, called once the joined
-    offsets of a group are known"""
+    offsets of a group are known; level (`loudness`): level_waveform's target and ceiling_db -- the joined prompts are levelled"""
     pause_ms, fade_ms = long
     split = [split_prompt(p) for p in prompts]
     groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
@@ -681,14 +735,20 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
         at = 0
         for batch in load_prompts(lines, ivocab):
             Bn = batch['text'].shape[0]
-            spec, al, _, conv, _, trim, lengths, scores, f0res, paths, _ = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            spec, al, _, conv, _, trim, lengths, scores, f0res, paths, _, _ = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
             timed += [(paths, i) for i in range(Bn)]
             arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i],
                         None if scores is None else scores[i], int(batch['text_length'][i]),
                         f0_of(row + at + i, i, int(lengths[i]), f0res, who[row + at + i])) for i in range(Bn)]
             at += Bn
         gap = join_gaps(kinds, pause_ms)
-        _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
+        louds = None
+        if level is None:
+            _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
+        else:   # (the joined fp32 prompts stay on the device; their PCM16 is the levelled one)
+            joined, _, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_pcm=False)
+            _, pcm, loud, blocks = level_waveform(joined, total=total, want_out=False, want_pcm=True, **level)
+            louds = [loud_row(a, b) for a, b in zip(loud.cpu().numpy(), blocks.cpu().numpy())]
         pcm, total, offsets = pcm.cpu().numpy(), total.cpu().numpy(), offsets.cpu().numpy()   # (the one copy back of the group)
         for p in range(lo, hi):
             a, b = first[p - lo], first[p - lo + 1]
@@ -709,6 +769,9 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
             if found:
                 print('WARNING prompt %d: %s' % (p, '; '.join(found)))
             write_wav_pcm(path + '.wav', pcm[p - lo, :int(total[p - lo])])
+            if louds is not None:
+                np.save(path + '_loud.npy', louds[p - lo])
+                print(loud_line('prompt %d' % p, louds[p - lo], level['ceiling_db']))
             if timing_of is not None:
                 write_words(p, words)
             if b - a > 1:
@@ -798,6 +861,13 @@ def parse_args(argv=None):
                          '0-based, - in the rate or semitones field for "leave"; words not listed take --rate / --pitch or stay neutral.  '
                          'The curves follow the attention path on the device; writes prompt_NNN_prosody.npy (dur_q, step_q per character).  '
                          'Refused with --long: the pieces re-index the words of a prompt, which is out of scope (not in the reference)')
+    ap.add_argument('--loudness', type=float, default=None, metavar='LUFS',
+                    help='write every prompt at this integrated loudness (ITU-R BS.1770, measured and applied on the device), '
+                         '-70 <= LUFS <= 0: -23 is EBU R 128, -16 to -19 voice assistants and podcasts; implies finishing; writes '
+                         'prompt_NNN_loud.npy; with --long the joined prompt is levelled (not in the reference)')
+    ap.add_argument('--peak-db', type=float, default=None, metavar='DB',
+                    help='--loudness: the ceiling on the sample peak in decibels re full scale, DB <= 0 (default %g); where it binds, '
+                         'the gain is what it allows' % PEAK_DB)
     ap.add_argument('--path-jump', type=int, default=None, metavar='J',
                     help='--timings / --prosody: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
@@ -815,7 +885,7 @@ def parse_args(argv=None):
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
                       lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings or a.prosody is not None else None,
-                      prosody=a.prosody, gl_init=a.gl_init)
+                      prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db)
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -835,4 +905,4 @@ if __name__ == '__main__':
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
          align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump,
-         f0_smooth=a.f0_smooth, prosody=a.prosody, gl_init=a.gl_init)
+         f0_smooth=a.f0_smooth, prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db)
