@@ -961,12 +961,60 @@ int taco_wave_join(const float* pieces, int64_t pitch, const int32_t* bounds, co
  * or pcm -- target_lufs outside [-70, 0] or NaN, ceiling outside (0, 1] or NaN return TACO_EINVAL, with a message
  * "wave_loudness: ...", before anything is enqueued; the size function returns TACO_EINVAL for the same shapes.  TACO_VERSION did not
  * change with these entry points: detect them by the symbol.
- * Not here: loudness range and short-term loudness, true-peak (oversampled) limiting, more than one channel. */
+ * Not here: loudness range and short-term loudness, more than one channel.  True-peak (oversampled) limiting is taco_wave_limit,
+ * below: this call's own ceiling stays what it was, on the sample peak and by the whole row's gain. */
 #define TACO_LOUD_CHUNK 2048
 int taco_k_weighting(int sr, double coef[10]);
 int64_t taco_wave_loudness_workspace_bytes(int B, int L, int sr);   /* B > 0, L > 0, sr as above, else TACO_EINVAL */
 int taco_wave_loudness(const float* wave, const int32_t* samples, int sr, float target_lufs, float ceiling, float* out, int16_t* pcm,
                        float* loud, int32_t* blocks, void* workspace, int B, int L, void* stream);
+
+/* True-peak meter and look-ahead limiter (no reference counterpart).  taco_wave_loudness reaches its ceiling by holding the whole
+ * row's gain down, and its ceiling is on the sample peak.  taco_wave_limit applies the gain G_b the caller asks for and pulls down
+ * only the neighbourhood of a peak, with the ceiling on the TRUE peak: the largest of the samples and of P - 1 interpolated phases
+ * between them.  There is no recursion in it -- an interpolating FIR, a sliding minimum, a smoothing FIR -- and every value is ONE
+ * rounded fp32 operation in a stated order with no contraction (no fused multiply-add), so a NumPy float32 restatement gives the
+ * same bits (tests/limiter_ref.py).
+ *   wave    (B, L) fp32, contiguous
+ *   samples (B) int32 on the DEVICE, or NULL: n_b = clamp(samples[b], 0, L); NULL: n_b = L.  The host reads nothing from it
+ *   gain    (B) fp32 on the DEVICE, or NULL: G_b = gain[b]; a value that is not a finite positive number counts as 1; NULL: 1
+ *   ceiling in (0, 1], on the true peak
+ *   taps    (P - 1, T) fp32 on the device: phases 1 .. P - 1 of the interpolator; P in 1..8, T even in 2..32.  P = 1: a sample-peak
+ *           limiter, taps is not looked at.  (tacotron_amd.lib.true_peak_taps: a Kaiser-windowed sinc, each phase normalised)
+ *   window  (2 W + 1) fp32 on the device: non-negative smoothing weights; W in 0..512 is the look-ahead in samples
+ *   out     (B, L) fp32, nullable, may be wave itself (else it may not overlap wave);  pcm (B, L) int16, nullable
+ *   peaks   (B, 4) fp32 = (tp_in, G, g_min, peak_out);  counts (B, 2) int32 = (n_b, samples with s < 1); both required
+ * Per row, with x = 0 outside [0, n_b):
+ *   1. envelope  for p = 1 .. P - 1: v_p[n] = sum_{j = 0 .. T - 1} taps[p - 1][j] x[n - (T/2 - 1) + j], accumulated from 0 in order of
+ *      j as acc = fl(acc + fl(t x));  e[n] = max(|x[n]|, |v_1[n]|, ...): phase 0 is the sample itself;  tp_in = max_n e[n] over
+ *      [0, n_b), 0 for an empty row
+ *   2. required gain  ge = fl(G e[n]);  r[n] = fl(ceiling / ge) when ge > ceiling, else exactly 1;  r = 1 outside [0, n_b)
+ *   3. look-ahead  m[i] = min r[j] over |j - i| <= W
+ *   4. smoothing  d[n] = sum_{k = 0 .. 2W} fl(window[k] fl(1 - m[n - W + k])), accumulated from 0 in order of k;
+ *      s[n] = min(fl(1 - d[n]), r[n]).  s is exactly 1 wherever no sample within 2 W needs limiting, and s <= r makes the bound exact
+ *   5. emit  out[n] = fl(fl(G x[n]) s[n]);  pcm = (int16) trunc(v * 32767.0f) with v = out clamped to [-1, 1] first (the rule of
+ *      taco_wave_loudness);  everything from n_b to L is exactly 0;  g_min = min s (1 for an empty row), peak_out = max |out|.
+ *      |out| <= ceiling (1 + 2^-22): |fl(G x)| <= ge, and fl(ge fl(ceiling / ge)) carries two roundings
+ *   6. measure only (out and pcm both NULL): step 1 alone.  peaks = (tp_in, 1, 1, max |x|), counts = (n_b, 0); gain, ceiling, window
+ *      and W are not looked at.  This is the dBTP meter
+ * The contract is that of taco_wave_loudness: every element of out, pcm, peaks and counts is written and nothing outside them, for
+ * any L and any alignment of out and pcm (16-byte / 8-byte stores where the address allows, scalar ones at the edges of a chunk of
+ * TACO_LIMIT_CHUNK = 2048 samples); the workspace may hold arbitrary bytes and needs the alignment of a float; no atomics: the same
+ * arguments give the same bits; row b of a B-row call is bit-identical to the B = 1, L = n_b call on a copy of its samples;
+ * x[b, n >= n_b] has no influence on anything (it may hold NaN); non-finite samples inside n_b do not fault, the row's values are
+ * then unspecified.  No allocation, no host synchronisation, no workgroup waits for another one: graph-capturable, and a replay
+ * follows whatever samples and gain hold at replay time.  Two launches; three when out is the wave (the samples either side of every
+ * chunk are copied into the workspace first, so that no workgroup reads what its neighbour overwrites).  NULL wave / peaks /
+ * counts / workspace, B <= 0 or > 65535, L <= 0, P or T out of range, T odd, NULL taps with P > 1 and -- with out or pcm -- W out
+ * of range, NULL window, ceiling outside (0, 1] or NaN return TACO_EINVAL, with a message "wave_limit: ...", before anything is
+ * enqueued; the size function returns TACO_EINVAL for B <= 0, L <= 0 and W out of range.  TACO_VERSION did not change with this
+ * entry point: detect it by the symbol.
+ * Not here: a recursive (attack / release) limiter, oversampled output, more than one channel. */
+#define TACO_LIMIT_CHUNK 2048
+int64_t taco_wave_limit_workspace_bytes(int B, int L, int W);   /* B > 0, L > 0, W in 0..512, else TACO_EINVAL */
+int taco_wave_limit(const float* wave, const int32_t* samples, const float* gain, float ceiling, const float* taps, int P, int T,
+                    const float* window, int W, float* out, int16_t* pcm, float* peaks, int32_t* counts, void* workspace, int B, int L,
+                    void* stream);
 
 /* ---- feature front end (preprocess.py) ------------------------------------------------------------------------------- */
 /* audio.process_audio (audio.py:38-65) for a batch of waveforms, the reference's constants compiled in (n_fft 2048, win_length

@@ -281,13 +281,41 @@ def join_waveform(pieces, bounds, first, kinds, pause_ms=(300.0, 150.0, 0.0), fa
     return lib.wave_join(pieces, bounds, first, join_gaps(kinds, pause_ms), fade=join_samples(fade_ms), **kw)
 
 
-def level_waveform(fin, bounds=None, total=None, target=-23.0, ceiling_db=-1.0, sr=SR, **kw):
+def limit_settings(who, lookahead_ms=1.5, oversample=4, passes=2, sr=SR):
+    """The checked settings of the true-peak limiter -> (W, P, passes): W = round(lookahead_ms sr / 1000) samples of look-ahead,
+    clamped into 0 .. lib.LIMIT_MAX_W; P = oversample in 1..8 (1: a sample-peak limiter); passes in 1..8.  ValueError otherwise.
+    The defaults (1.5 ms, 4 x, and lib.LIMIT_T = 12 taps at beta 6) are untuned: nobody has listened to a limited file."""
+    try:
+        lookahead_ms = float(lookahead_ms)
+    except (TypeError, ValueError):
+        raise ValueError('%s: lookahead_ms must be a number of milliseconds, got %r' % (who, lookahead_ms)) from None
+    if not lookahead_ms >= 0.0 or math.isinf(lookahead_ms):
+        raise ValueError('%s: lookahead_ms must be a finite number of milliseconds >= 0, got %r' % (who, lookahead_ms))
+    P = lib.int_arg(who, 'oversample', oversample, 1, 8)
+    passes = lib.int_arg(who, 'passes', passes, 1, 8)
+    return min(lib.LIMIT_MAX_W, int(round(lookahead_ms * sr / 1000.0))), P, passes
+
+
+def level_waveform(fin, bounds=None, total=None, target=-23.0, ceiling_db=-1.0, sr=SR, limit=False, lookahead_ms=1.5, oversample=4,
+                   passes=2, **kw):
     """fin (B, L) finished fp32 rows -> (out, pcm, loud, blocks) of lib.wave_loudness: every row measured by ITU-R BS.1770 over its own
     samples and emitted at `target` LUFS (-23: EBU R 128) with its sample peak at or below ceiling_db decibels re full scale (<= 0).
     bounds: (B, 2) int32 on the device as finish_waveform returns them -- row b holds bounds[b, 1] - bounds[b, 0] samples; total: (B)
     int32 on the device as join_waveform returns it -- row b holds total[b]; neither: every row holds L samples.  The counts are
     formed by torch ops on the device; nothing is read back.  target None measures only.  Keywords go to lib.wave_loudness (want_out,
-    want_pcm and the caller's own buffers)."""
+    want_pcm and the caller's own buffers).
+    limit=True: the row gets the gain its target asks for and lib.wave_limit holds its TRUE peak at ceiling_db (dBTP) by pulling down
+    only the neighbourhood of a peak -> (out, pcm, loud, blocks, peaks, counts): the measured gain G = 10^((target - I) / 20) (1
+    where I is not finite) is formed on the device; the rows are limited with it; for each further pass the output is measured, G
+    is multiplied by 10^((target - I_out) / 20) and the ORIGINAL rows are limited again; loud and blocks are a last measurement of
+    the final out, peaks and counts those of lib.wave_limit.  lookahead_ms, oversample, passes: limit_settings.  Keywords then go to
+    lib.wave_limit (want_pcm and the caller's own out, pcm, peaks, counts, work); out is always formed.  Nothing is read back."""
+    if not isinstance(limit, bool):
+        raise ValueError('level_waveform: limit must be True or False, got %r' % (limit,))
+    if limit:
+        W, P, passes = limit_settings('level_waveform', lookahead_ms, oversample, passes, sr)
+        if target is None:
+            raise ValueError('level_waveform: limit=True needs a target')
     if bounds is not None and total is not None:
         raise ValueError('level_waveform: give bounds (of finish_waveform) or total (of join_waveform), not both')
     B = fin.shape[0] if torch.is_tensor(fin) and fin.dim() == 2 else None
@@ -301,4 +329,27 @@ def level_waveform(fin, bounds=None, total=None, target=-23.0, ceiling_db=-1.0, 
     ceiling_db = float(ceiling_db)
     if not ceiling_db <= 0.0 or math.isinf(ceiling_db):
         raise ValueError('level_waveform: ceiling_db must be a finite number of decibels <= 0, got %r' % (ceiling_db,))
-    return lib.wave_loudness(fin, samples, sr=sr, target=target, ceiling=10.0 ** (ceiling_db / 20.0), **kw)
+    if not limit:
+        return lib.wave_loudness(fin, samples, sr=sr, target=target, ceiling=10.0 ** (ceiling_db / 20.0), **kw)
+    target = float(target)
+    if not -70.0 <= target <= 0.0:   # (NaN fails)
+        raise ValueError('level_waveform: target must be in [-70, 0] LUFS, got %r' % (target,))
+    if kw.get('want_out', True) is False:
+        raise ValueError('level_waveform: limit=True always forms out (the passes measure it)')
+    kw = dict(kw, want_out=True)
+    kw.setdefault('want_pcm', True)
+    taps = lib.true_peak_taps(P, lib.LIMIT_T, lib.LIMIT_BETA) if P > 1 else np.zeros((0, lib.LIMIT_T), np.float32)
+    loud = lib.wave_loudness(fin, samples, sr=sr, target=None)[2]   # (refuses what is no (B, L) fp32 tensor on the GPU)
+    taps, window = torch.from_numpy(taps).to(fin.device), torch.from_numpy(lib.limit_window(W)).to(fin.device)
+
+    def towards(I):   # the factor that carries a row read at I LUFS to the target; 1 where there is no reading
+        return torch.where(torch.isfinite(I), torch.pow(10.0, (target - I) / 20.0), torch.ones_like(I))
+
+    G = towards(loud[:, 0]).contiguous()
+    for k in range(passes):
+        out, pcm, peaks, counts = lib.wave_limit(fin, samples, gain=G, ceiling=10.0 ** (ceiling_db / 20.0), taps=taps, window=window, **kw)
+        kw.update(out=out, pcm=pcm, peaks=peaks, counts=counts)   # (the next pass writes the same buffers)
+        _, _, loud, blocks = lib.wave_loudness(out, samples, sr=sr, target=None)
+        if k + 1 < passes:
+            G = (G * towards(loud[:, 0])).contiguous()
+    return out, pcm, loud, blocks, peaks, counts

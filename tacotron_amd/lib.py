@@ -156,6 +156,8 @@ EXPORTS = {
     'taco_k_weighting': (C.c_int, [_I, C.POINTER(C.c_double)]),
     'taco_wave_loudness_workspace_bytes': (C.c_int64, [_I, _I, _I]),
     'taco_wave_loudness': (C.c_int, [_P, _P, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'taco_wave_limit_workspace_bytes': (C.c_int64, [_I, _I, _I]),
+    'taco_wave_limit': (C.c_int, [_P, _P, _P, C.c_float, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_audio_features_workspace_bytes': (C.c_int64, [_I, _I]),
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_wave_resample': (C.c_int, [_P, C.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
@@ -1550,6 +1552,127 @@ def wave_loudness(wave, samples=None, sr=16000, target=None, ceiling=1.0, want_o
     _check(_lib.taco_wave_loudness(ptr(wave), ptr(samples), sr, target, ceiling, ptr(out), ptr(pcm), ptr(loud), ptr(blocks), ptr(work),
                                    B, L, stream_ptr()), 'taco_wave_loudness')
     return out, pcm, loud, blocks
+
+
+LIMIT_CHUNK = 2048   # TACO_LIMIT_CHUNK: the samples of a row that one workgroup of taco_wave_limit handles
+LIMIT_MAX_W = 512    # the longest look-ahead of taco_wave_limit, in samples
+# The defaults of the true-peak limiter: 4 x oversampling, 12 taps per phase, Kaiser beta 6 (and 1.5 ms of look-ahead in
+# griffinlim.level_waveform).  They are UNTUNED: chosen so that the meter reads tones within EBU Tech 3341's +0.2 / -0.4 dB
+# (tests/test_wave_limit_host.py); nobody has listened to a limited file.
+LIMIT_P, LIMIT_T, LIMIT_BETA = 4, 12, 6.0
+
+
+def true_peak_taps(P=LIMIT_P, T=LIMIT_T, beta=LIMIT_BETA):
+    """The interpolator of taco_wave_limit: a (P - 1, T) float32 array, phases 1 .. P - 1 of a Kaiser-windowed sinc.  Tap j of phase p
+    sits at t = j - (T/2 - 1) - p/P samples: h = sinc(t) I0(beta sqrt(1 - (t / (T/2))^2)) / I0(beta), 0 where the root's argument is
+    negative; each phase is divided by its own sum, in fp64, and rounded once.  P in 1..8 (P = 1: an empty table), T even in 2..32."""
+    who = 'true_peak_taps'
+    P, T = int_arg(who, 'P', P, 1, 8), int_arg(who, 'T', T, 2, 32)
+    if T % 2:
+        raise ValueError('%s: T must be even, got %d' % (who, T))
+    beta = float(beta)
+    if not 0.0 <= beta < math.inf:
+        raise ValueError('%s: beta must be a finite number >= 0, got %r' % (who, beta))
+    half = T // 2
+    t = np.arange(T, dtype=np.float64)[None, :] - (half - 1) - np.arange(1, P, dtype=np.float64)[:, None] / P
+    u = 1.0 - (t / half) ** 2
+    h = np.where(u >= 0.0, np.sinc(t) * np.i0(beta * np.sqrt(np.maximum(u, 0.0))) / np.i0(beta), 0.0)
+    return (h / h.sum(axis=1, keepdims=True)).astype(np.float32)
+
+
+def limit_window(W):
+    """The smoothing weights of taco_wave_limit: a (2 W + 1) float32 array, 0.5 - 0.5 cos(2 pi (k + 1) / (2 W + 2)) (a Hann window
+    without its zero ends) divided by its sum in fp64 and rounded once.  W in 0..512 is the look-ahead in samples."""
+    W = int_arg('limit_window', 'W', W, 0, LIMIT_MAX_W)
+    k = np.arange(2 * W + 1, dtype=np.float64)
+    h = 0.5 - 0.5 * np.cos(2.0 * np.pi * (k + 1.0) / (2 * W + 2))
+    return (h / h.sum()).astype(np.float32)
+
+
+def wave_limit_workspace_floats(B, L, W) -> int:
+    return _size('taco_wave_limit_workspace_bytes', B, L, W) // 4
+
+
+_default_taps = {}   # device -> the default interpolator, uploaded once
+
+
+def _limit_table(who, name, x, shape, dev, empty_ok=False):
+    """a float32 table on `dev`: the caller's device tensor (checked, never read), or a host array / tensor (checked and uploaded)"""
+    if not torch.is_tensor(x):
+        try:
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        except TypeError:
+            raise ValueError('%s: %s must be a float32 array or tensor, got a %s' % (who, name, type(x).__name__)) from None
+    free = tensor_arg(who, name, x, torch.float32, shape, None if x.device.type == 'cpu' else dev, empty_ok=empty_ok)
+    return x, free
+
+
+def wave_limit(wave, samples=None, gain=None, ceiling=1.0, taps=None, window=None, want_out=None, want_pcm=None, out=None, pcm=None,
+               peaks=None, counts=None, work=None):
+    """True-peak meter and look-ahead limiter (include/taco_hip.h taco_wave_limit): wave (B, L) fp32 -> (out (B, L) fp32 or None,
+    pcm (B, L) int16 or None, peaks (B, 4) fp32 = (tp_in, G, g_min, peak_out), counts (B, 2) int32 = (n_b, samples limited)).  Per row
+    over its first n_b samples: the envelope e = the largest of |x| and of the P - 1 interpolated phases of `taps`; the gain
+    r = ceiling / (G e) where G e passes the ceiling, else 1; its minimum over W samples either side, smoothed by `window`, and never
+    above r: out = (G x) s, pcm its PCM16, zeros behind n_b.  tp_in is the true peak of the input, peak_out the sample peak of out.
+    samples (B) int32 on the device, or None: every row has L samples.  gain (B) fp32 on the device, or None: G = 1.  ceiling in
+    (0, 1], on the true peak.  taps: a (P - 1, T) float32 table (a device tensor, or a host array that is uploaded); None: the
+    default true_peak_taps(), uploaded once per device; a (0, T) table is P = 1, a sample-peak limiter.  window: (2 W + 1) float32
+    likewise, limit_window(W); None: MEASURE ONLY -- the dBTP meter: peaks = (tp_in, 1, 1, max |x|), out and pcm stay None and gain
+    and ceiling are not looked at.  want_out / want_pcm default to whether there is a window.  out / pcm / peaks / counts / work: the
+    caller's own buffers (work: wave_limit_workspace_floats(B, L, W) floats); default: fresh ones.  An out / pcm buffer implies
+    want_out / want_pcm; out may be wave itself."""
+    who = 'wave_limit'
+    B, L = tensor_arg(who, 'wave', wave, torch.float32, ('B', 'L'))
+    dev = wave.device
+    if B > 65535:
+        raise ValueError('%s: at most 65535 rows per call, got %d' % (who, B))
+    tensor_arg(who, 'samples', samples, torch.int32, (B,), dev, optional=True)
+    tensor_arg(who, 'gain', gain, torch.float32, (B,), dev, optional=True)
+    if taps is None:
+        P, T = LIMIT_P, LIMIT_T
+    else:
+        taps, (P, T) = _limit_table(who, 'taps', taps, ('P - 1', 'T'), dev, empty_ok=True)
+        P += 1
+        if not 1 <= P <= 8 or not 2 <= T <= 32 or T % 2:
+            raise ValueError('%s: taps must hold P - 1 in [0, 7] phases of an even number T in [2, 32] of taps, got %s'
+                             % (who, tuple(taps.shape)))
+    want_out = (window is not None if want_out is None else bool(want_out)) or out is not None
+    want_pcm = (window is not None if want_pcm is None else bool(want_pcm)) or pcm is not None
+    if window is None:
+        if want_out or want_pcm:
+            raise ValueError('%s: out and pcm need a window (window=None measures only)' % who)
+        W, ceiling = 0, 1.0
+    else:
+        window, (n_w,) = _limit_table(who, 'window', window, ('2 W + 1',), dev)
+        if n_w % 2 == 0 or n_w // 2 > LIMIT_MAX_W:
+            raise ValueError('%s: window must hold 2 W + 1 weights with W in [0, %d], got %d' % (who, LIMIT_MAX_W, n_w))
+        W = n_w // 2
+        ceiling = float(ceiling)
+        if not 0.0 < ceiling <= 1.0 or C.c_float(ceiling).value <= 0.0:   # (NaN fails)
+            raise ValueError('%s: ceiling must be in (0, 1], got %r' % (who, ceiling))
+        if not (want_out or want_pcm):
+            raise ValueError('%s: a window needs at least one of out and pcm' % who)
+    out = _own_or_given(out, (B, L), torch.float32, dev, who + ': out') if want_out else None
+    if out is not None and out.data_ptr() != wave.data_ptr():
+        no_overlap(who, 'wave', wave, 'out', out)
+    pcm = _own_or_given(pcm, (B, L), torch.int16, dev, who + ': pcm') if want_pcm else None
+    peaks = _own_or_given(peaks, (B, 4), torch.float32, dev, who + ': peaks')
+    counts = _own_or_given(counts, (B, 2), torch.int32, dev, who + ': counts')
+    if work is not None:
+        tensor_arg(who, 'work', work, torch.float32, ('floats',), dev)
+    on_gpu(who, 'wave', dev)
+    if taps is None:
+        if dev not in _default_taps:
+            _default_taps[dev] = torch.from_numpy(true_peak_taps()).to(dev)
+        taps = _default_taps[dev]
+    elif taps.device != dev:
+        taps = taps.to(dev)
+    if window is not None and window.device != dev:
+        window = window.to(dev)
+    work = _own_or_given(work, (wave_limit_workspace_floats(B, L, W),), torch.float32, dev, who + ': work')
+    _check(_lib.taco_wave_limit(ptr(wave), ptr(samples), ptr(gain), ceiling, ptr(taps) if P > 1 else None, P, T, ptr(window), W,
+                                ptr(out), ptr(pcm), ptr(peaks), ptr(counts), ptr(work), B, L, stream_ptr()), 'taco_wave_limit')
+    return out, pcm, peaks, counts
 
 
 def audio_features_workspace_bytes(B, L) -> int:

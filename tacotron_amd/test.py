@@ -87,7 +87,15 @@ full scale (default -1, <= 0); where the ceiling binds, the gain is what the cei
 (de-emphasis and trim stay off unless asked for).  prompt_NNN.wav holds the device's int16 samples, prompt_NNN_loud.npy holds
 (I, M, g, peak_out, nb, past_abs, past_both, limited) as float64 and one line per prompt gives the loudness before and after.  A prompt
 shorter than 400 ms is measured as one block (the standard leaves it unmeasured).  With --long the JOINED prompt is levelled, so its
-pieces keep their relative levels.  It combines with every option above; without it every file is what it was."""
+pieces keep their relative levels.  It combines with every option above; without it every file is what it was.
+--loudness LUFS --limit [--limit-ms MS] [--true-peak P] [--limit-passes N] (opt-in, not in the reference): the true-peak limiter.
+Where the ceiling would hold the whole prompt under its target, the prompt gets the gain the target asks for and a look-ahead limiter
+on the device (griffinlim.level_waveform(limit=True), taco_wave_limit) pulls down only the neighbourhood of a peak; DB then is the
+ceiling on the TRUE peak (dBTP), read between the samples through a P-phase interpolator (default 4; 1: the sample peak).  MS is the
+look-ahead (default 1.5 ms), N the passes (default 2: the second re-aims the gain at the target).  These defaults are untuned and
+nobody has listened to a limited file.  prompt_NNN.wav holds the limited int16 samples, prompt_NNN_limit.npy holds (tp_in, G, g_min,
+peak_out, n_b, n_limited, I_reached, tp_out) as float64 in place of _loud.npy, and one line per prompt gives the loudness before
+and after, the true peak and how much was limited.  With --long the JOINED prompt is limited.  Without --limit no new code is reached."""
 from __future__ import annotations
 
 import argparse
@@ -102,7 +110,7 @@ import torch
 from .config import Config
 from .alignment import attention_png, encoded_chars, flags, path_line, scores_row, word_times, word_values, words_tsv
 from .data import KIND_NAMES, load_prompts, split_prompt
-from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform, level_waveform
+from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform, level_waveform, limit_settings
 from .model import Tacotron
 from .params import ParamBuffer
 from . import lib
@@ -111,6 +119,8 @@ SR = 16000   # test.py:11
 PAUSE_MS = (300.0, 150.0, 0.0)   # --long: silence behind a SENTENCE / CLAUSE / WORD cut; choices, not tuned by anyone's ear
 FADE_MS = 5.0                    # --long: the ramp at every interior edge; likewise
 JOIN_GROUP = 256                 # --long: pieces per lib.wave_join call (a group ends at the first prompt boundary at or past it)
+LIMIT_MS = 1.5                   # --limit: the look-ahead in milliseconds (untuned, as are lib.LIMIT_P / LIMIT_T / LIMIT_BETA)
+LIMIT_PASSES = 2                 # --limit: limiter passes; every pass after the first re-aims the gain at the target
 PEAK_DB = -1.0                   # --loudness: the ceiling on the sample peak, decibels re full scale
 
 
@@ -284,12 +294,52 @@ def loud_line(who, row, peak_db=PEAK_DB):
     return '%s: %.1f LUFS -> %.1f (gain %+.1f dB)' % (who, I, after, 20.0 * np.log10(g))
 
 
+def limit_row(peaks, counts, I_reached, tp_out, I_in):
+    """a row of lib.wave_limit's peaks (4) and counts (2), the loudness reached, the true peak of the output and the loudness of the
+    input -> 9 float64 values: the 8 of prompt_NNN_limit.npy (tp_in, G, g_min, peak_out, n_b, n_limited, I_reached, tp_out), then I_in"""
+    return np.concatenate([np.asarray(peaks, dtype=np.float64), np.asarray(counts, dtype=np.float64),
+                           np.asarray([I_reached, tp_out, I_in], dtype=np.float64)])
+
+
+def limit_line(who, row, target):
+    """the line --loudness --limit prints for `who` from its limit_row"""
+    g_min, n_b, n_lim, I_out, tp_out, I_in = (float(row[k]) for k in (2, 4, 5, 6, 7, 8))
+    if not np.isfinite(I_in):
+        return '%s: no block above the gates, level unchanged' % who
+    db = lambda v: 20.0 * np.log10(v) if v > 0.0 else -np.inf
+    return ('%s: %.1f LUFS -> %.1f (asked %.1f), true peak %.1f dBTP, %.1f %% of samples limited, deepest %.1f dB'
+            % (who, I_in, I_out, target, db(tp_out), 100.0 * n_lim / max(n_b, 1.0), db(g_min)))
+
+
+def level_line(who, row, level):
+    """loud_line or limit_line, by what `level` asked for"""
+    return limit_line(who, row, level['target']) if level.get('limit') else loud_line(who, row, level['ceiling_db'])
+
+
+def level_finished(fin, level, **rows):
+    """level_waveform(fin, **rows, **level) on finished device rows -> (pcm (B, L) int16 on the device, the rows' loud_rows; with
+    level['limit'] their limit_rows).  With the limiter the input is measured once more for the line, and the TRUE peak of the
+    output by one measure-only call of lib.wave_limit; everything is read back in one go at the end"""
+    if not level.get('limit'):
+        _, pcm, loud, blocks = level_waveform(fin, want_out=False, want_pcm=True, **rows, **level)
+        return pcm, np.stack([loud_row(a, b) for a, b in zip(loud.cpu().numpy(), blocks.cpu().numpy())])
+    out, pcm, loud, _, peaks, counts = level_waveform(fin, want_pcm=True, **rows, **level)
+    n_b = counts[:, 0].contiguous()
+    I_in = lib.wave_loudness(fin, n_b, sr=SR, target=None)[2][:, 0]
+    P = level['oversample']
+    taps = lib.true_peak_taps(P) if P > 1 else np.zeros((0, lib.LIMIT_T), np.float32)
+    tp_out = lib.wave_limit(out, n_b, taps=taps)[2][:, 0]
+    return pcm, np.stack([limit_row(*r) for r in zip(peaks.cpu().numpy(), counts.cpu().numpy(), loud[:, 0].cpu().numpy(),
+                                                     tp_out.cpu().numpy(), I_in.cpu().numpy())])
+
+
 def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
                   vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, gl_init=None, loudness=None, peak_db=None,
-                  path_jump=None):
+                  limit=False, limit_ms=None, true_peak=None, limit_passes=None, path_jump=None):
     """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
     without --timings; `f0_smooth`: None / False, True or the number of candidates; `prosody`: None / False or anything else for
-    given; `gl_init`: None, 'random' or 'estimate'; `peak_db`: None for not given); ValueError."""
+    given; `gl_init`: None, 'random' or 'estimate'; `peak_db`: None for not given; `limit`: True / False, `limit_ms`, `true_peak`,
+    `limit_passes`: None for not given); ValueError."""
     if loudness is not None:
         if not vocode:
             raise ValueError('loudness (--loudness) levels the waveform: it needs vocode')
@@ -300,6 +350,15 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
             raise ValueError('peak_db (--peak-db) is the ceiling of loudness (--loudness): it needs loudness')
         if not float(peak_db) <= 0.0 or np.isinf(float(peak_db)):
             raise ValueError('peak_db (--peak-db) must be a finite number of decibels <= 0, got %r' % (peak_db,))
+    if not isinstance(limit, bool):
+        raise ValueError('limit (--limit) must be True or False, got %r' % (limit,))
+    if limit and loudness is None:
+        raise ValueError('limit (--limit) holds the true peak of loudness (--loudness) at its ceiling: it needs loudness')
+    for name, v in (('limit_ms (--limit-ms)', limit_ms), ('true_peak (--true-peak)', true_peak), ('limit_passes (--limit-passes)', limit_passes)):
+        if v is not None and not limit:
+            raise ValueError('%s is a setting of limit (--limit): it needs limit' % name)
+    if limit:
+        limit_options(limit_ms, true_peak, limit_passes)
     if gl_init not in (None, 'random', 'estimate'):
         raise ValueError("gl_init (--gl-init) must be 'random' or 'estimate', got %r" % (gl_init,))
     if gl_init == 'estimate' and not vocode:
@@ -345,6 +404,14 @@ def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, 
         raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (trim_db,))
 
 
+def limit_options(limit_ms=None, true_peak=None, limit_passes=None):
+    """the limiter's keywords of level_waveform from the options (None: the default), checked; ValueError"""
+    opt = dict(lookahead_ms=LIMIT_MS if limit_ms is None else limit_ms, oversample=lib.LIMIT_P if true_peak is None else true_peak,
+               passes=LIMIT_PASSES if limit_passes is None else limit_passes)
+    limit_settings('limit (--limit-ms, --true-peak, --limit-passes)', sr=SR, **opt)
+    return dict(limit=True, **opt)
+
+
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
                  rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
@@ -360,7 +427,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     dur (--timings): the steps of each of the prompt's characters, written as _dur.npy (int32).
     prosody (--prosody): (the prompt's (L, 2) per-character (dur_q, step_q), Fo_b): the table is written as _prosody.npy (int32); wav is
     then the waveform behind the stretch curve and keeps 300 (Fo_b - 1) samples, whatever len_b says.
-    loud (--loudness): the prompt's loud_row, written as _loud.npy (float64); pcm then holds the levelled samples."""
+    loud (--loudness): the prompt's loud_row, written as _loud.npy (float64); pcm then holds the levelled samples.  With --limit: the
+    prompt's limit_row, whose first 8 values are written as _limit.npy instead."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -393,15 +461,22 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     if conv is not None:
         np.save(path + '_conv.npy', conv)
     if loud is not None:
-        np.save(path + '_loud.npy', np.asarray(loud, dtype=np.float64))
+        save_level(path, loud)
     if ascore is not None:
         np.save(path + '_ascore.npy', np.asarray(ascore, dtype=np.float64))
         attention_png(path + '_align.png', align, zoom=zoom)
 
 
+def save_level(path, row):
+    """a loud_row -> path_loud.npy; a limit_row -> its 8 values of path_limit.npy"""
+    row = np.asarray(row, dtype=np.float64)
+    np.save(path + ('_limit.npy' if len(row) == 9 else '_loud.npy'), row[:8])
+
+
 def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter=50, vocode=True, stop=None, vocode_lengths=False,
          gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False, rate=None, pitch=None, lifter=32, f0=None,
-         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None, gl_init=None, loudness=None, peak_db=None):
+         timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None, gl_init=None, loudness=None, peak_db=None, limit=False,
+         limit_ms=None, true_peak=None, limit_passes=None):
     """test.py:13-70: restore the checkpoint (weights AND stft_mean / stft_std, test.py:27-28), run every prompt batch,
     de-normalise `out * stft_std + stft_mean` (test.py:64), undo the r-frame layout and invert with Griffin-Lim -- all on the
     GPU (lib.denorm_unframe, tacotron_amd.griffinlim).  ONE Tacotron (workspace + outputs) serves every batch of the same
@@ -466,11 +541,19 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     <= 0 (None: -1).  The waveform is finished on the device as with `long` (without `deemphasis` / `trim_db`: bounds [0, n_b)) and
     the finished rows are levelled there (level_waveform over each row's own e - s samples); with `long` the JOINED prompts are
     levelled, after join_waveform.  prompt_NNN.wav holds the levelled int16 samples, prompt_NNN_loud.npy the prompt's loud_row, and
-    loud_line() is printed per prompt.  Without it lib.wave_loudness is never reached and every file is what it was."""
+    loud_line() is printed per prompt.  Without it lib.wave_loudness is never reached and every file is what it was.
+    `limit` (needs `loudness`) / `limit_ms` / `true_peak` / `limit_passes`: the true-peak limiter (level_waveform(limit=True),
+    taco_wave_limit): the prompt gets the gain its target asks for and only the neighbourhood of a peak is pulled down; `peak_db` then
+    is the ceiling on the TRUE peak (dBTP).  None: LIMIT_MS of look-ahead, lib.LIMIT_P x oversampling, LIMIT_PASSES passes -- untuned,
+    and nobody has listened to a limited file.  prompt_NNN.wav holds the limited int16 samples, prompt_NNN_limit.npy (tp_in, G, g_min, peak_out, n_b,
+    n_limited, I_reached, tp_out) as float64 (no _loud.npy), and limit_line() is printed per prompt.  Without it lib.wave_limit is
+    never reached."""
     check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
                   f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody, gl_init=gl_init, loudness=loudness,
-                  peak_db=peak_db)
+                  peak_db=peak_db, limit=limit, limit_ms=limit_ms, true_peak=true_peak, limit_passes=limit_passes)
     level = None if loudness is None else dict(target=float(loudness), ceiling_db=PEAK_DB if peak_db is None else float(peak_db))
+    if limit:
+        level.update(limit_options(limit_ms, true_peak, limit_passes))
     gl_init = None if gl_init == 'random' else gl_init
     if prosody is not None and prosody is not False:
         lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
@@ -609,8 +692,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                 wav = wav.cpu().numpy()
             if finish:
                 if level_rows:   # (the finished fp32 rows stay on the device; their PCM16 is the levelled one)
-                    _, pcm, loud, blocks = level_waveform(fin, bounds=trim, want_out=False, want_pcm=True, **level)
-                    louds = np.stack([loud_row(a, b) for a, b in zip(loud.cpu().numpy(), blocks.cpu().numpy())])
+                    pcm, louds = level_finished(fin, level, bounds=trim)
                 pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
         lengths = model.lengths.cpu().numpy() if stop is not None else None
         if scores is not None:
@@ -693,7 +775,7 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
                          rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n, curved), dur=dur,
                          prosody=None if curved is None else (pros[n], int(curved[0][i])), loud=li)
             if li is not None:
-                print(loud_line('prompt %d' % n, li, level['ceiling_db']))
+                print(level_line('prompt %d' % n, li, level))
             if words is not None:
                 write_words(n, words)
             found = marks(si, int(batch['text_length'][i])) if si is not None else []
@@ -747,8 +829,7 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
             _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
         else:   # (the joined fp32 prompts stay on the device; their PCM16 is the levelled one)
             joined, _, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_pcm=False)
-            _, pcm, loud, blocks = level_waveform(joined, total=total, want_out=False, want_pcm=True, **level)
-            louds = [loud_row(a, b) for a, b in zip(loud.cpu().numpy(), blocks.cpu().numpy())]
+            pcm, louds = level_finished(joined, level, total=total)
         pcm, total, offsets = pcm.cpu().numpy(), total.cpu().numpy(), offsets.cpu().numpy()   # (the one copy back of the group)
         for p in range(lo, hi):
             a, b = first[p - lo], first[p - lo + 1]
@@ -770,8 +851,8 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
                 print('WARNING prompt %d: %s' % (p, '; '.join(found)))
             write_wav_pcm(path + '.wav', pcm[p - lo, :int(total[p - lo])])
             if louds is not None:
-                np.save(path + '_loud.npy', louds[p - lo])
-                print(loud_line('prompt %d' % p, louds[p - lo], level['ceiling_db']))
+                save_level(path, louds[p - lo])
+                print(level_line('prompt %d' % p, louds[p - lo], level))
             if timing_of is not None:
                 write_words(p, words)
             if b - a > 1:
@@ -868,6 +949,16 @@ def parse_args(argv=None):
     ap.add_argument('--peak-db', type=float, default=None, metavar='DB',
                     help='--loudness: the ceiling on the sample peak in decibels re full scale, DB <= 0 (default %g); where it binds, '
                          'the gain is what it allows' % PEAK_DB)
+    ap.add_argument('--limit', action='store_true',
+                    help='--loudness: give every prompt the gain its target asks for and hold its TRUE peak (inter-sample peaks read '
+                         'through a polyphase interpolator) at --peak-db by a look-ahead limiter on the device that pulls down only the '
+                         'neighbourhood of a peak; writes prompt_NNN_limit.npy.  The defaults below are untuned and nobody has listened '
+                         'to a limited file (not in the reference)')
+    ap.add_argument('--limit-ms', type=float, default=None, metavar='MS', help='--limit: the look-ahead in milliseconds (default %g)' % LIMIT_MS)
+    ap.add_argument('--true-peak', type=int, default=None, metavar='P',
+                    help='--limit: the oversampling of the true-peak meter, 1 <= P <= 8; 1 limits the sample peak (default %d)' % lib.LIMIT_P)
+    ap.add_argument('--limit-passes', type=int, default=None, metavar='N',
+                    help='--limit: passes of the limiter, each after the first re-aimed at the target, 1 <= N <= 8 (default %d)' % LIMIT_PASSES)
     ap.add_argument('--path-jump', type=int, default=None, metavar='J',
                     help='--timings / --prosody: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
@@ -885,7 +976,8 @@ def parse_args(argv=None):
     try:
         check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
                       lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings or a.prosody is not None else None,
-                      prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db)
+                      prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db, limit=a.limit, limit_ms=a.limit_ms,
+                      true_peak=a.true_peak, limit_passes=a.limit_passes)
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -905,4 +997,5 @@ if __name__ == '__main__':
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
          vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
          align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump,
-         f0_smooth=a.f0_smooth, prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db)
+         f0_smooth=a.f0_smooth, prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db, limit=a.limit,
+         limit_ms=a.limit_ms, true_peak=a.true_peak, limit_passes=a.limit_passes)
