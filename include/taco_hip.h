@@ -170,6 +170,65 @@ int taco_debug_prenet_fwd(const float* x, const float* w1, const float* b1, cons
 int taco_debug_prenet_bwd(const float* dy2, const float* w2T, const float* w1T, const uint8_t* keep1, const uint8_t* keep2,
                           const float* y1_in, const float* y2_in, float* dz2, float* dz1, float* dx, int M, void* stream);
 
+/* ---- op-level debug doors of the GEMM forms only the model reaches (tests/test_gpu_gemm_forms.py) ------------
+ * Thin wrappers over the launches model.hip makes for the CBHG's conv bank and the decoder's `d keys` product: each builds its
+ * ConvGemmProblem / GemmTnArgs (csrc/kernels.h) exactly as cbhg_fwd, cbhg_bwd and taco_backward build theirs; no kernel of their own.
+ * All tensors fp32, row-major, (rows, cols) with the row pitch given (element (m, n) at p[m * ld + n]; operands without a pitch
+ * argument are dense).  Conventions of the CBHG-tail doors above: a null operand that is not nullable, a size out of range
+ * (rows <= 2^22, columns <= 2^14, T must divide M) or an output whose bytes meet those of another operand returns TACO_EINVAL
+ * with a message naming the argument, before anything is enqueued; where the library itself would fall back to another form a
+ * door returns TACO_ENOTFOUND with nothing enqueued, so that a test can tell which form ran.  TACO_VERSION did not change with these
+ * entry points: detect them by the symbol.
+ *
+ * taco_debug_conv_bank_pool_fwd: the conv bank with the pooled epilogue (ConvGemmProblem::pool == 1), F problems of ONE launch.
+ *   Filter f = 1..F: 'same' conv of width f (pad_l = (f - 1) / 2) of x (M, K; lda) with W[f-1] (f, K, N) dense, bias[f-1] (N, nullable),
+ *   ReLU -> bank[:, (f-1) N ..] (nullable: not stored); z = bank * scale * scale_mul + shift (scale, shift (F N));
+ *   pool[m] = max(z[m], z[m+1]) inside a sequence of T rows, z[m] on its last row.  pool, bank (M, F N; ldc).
+ *   TACO_ENOTFOUND where cbhg_fwd runs the convolutions and taco_debug_bn_maxpool_fwd's launch as two passes (gemm2.hip does not take
+ *   the batch: TACO_GEMM2_MIN_TILES, the float4 contract of csrc/gemm2.hip pool_contract).
+ * taco_debug_conv_gemm_pool_bwd: one problem with pool == 2: dy = sum_tap shift_tap(A) . W[tap] (A (M, K; lda), W (taps, K, N; ldw)) is
+ *   d(pooled); with z = pool_x * scale * scale_mul + shift (pool_x (M, N; ldc) the stored bank activations, scale, shift (N)):
+ *   dz[m] = [last row of its sequence or z[m] >= z[m+1]] dy[m] + [not the first and z[m] > z[m-1]] dy[m-1],
+ *   C[m] = (pool_x[m] > 0) dz[m] scale scale_mul (C (M, N; ldc)), dgamma[n] += sum_m dz pool_x scale_mul, dbeta[n] += sum_m dz (both (N),
+ *   ACCUMULATED into).  TACO_ENOTFOUND where cbhg_bwd takes the two-pass form (TACO_DETERMINISTIC=1, or as above).
+ * taco_debug_bn_maxpool_fwd / _bwd: the two-pass twins (elementwise.hip), dense (B T, C), C % 4 == 0, scale_mul = 1 / sqrt(1 + 1e-3)
+ *   fixed: y = pool(x gamma scale_mul + beta); dx, dgamma (+=), dbeta (+=) as C, dgamma, dbeta above with dy given.
+ * taco_debug_bank_gather: the conv bank's input gradient as ONE reduction (ConvGemmProblem::bank_filters) cut into S chunks of the
+ *   (tap, 32-deep k-tile) sequence, each into its own slab, then the slab sum: dx_out (M, N; ldc) += sum_f convT_f(dbank[:, (f-1) K ..])
+ *   + residual (M, N; ldr; nullable).  dbank (M, F K; lda); WT[f-1] (f, K, N) dense, the transposed kernel of width f whose tap j reads
+ *   the rows shifted by j - ((f - 1) - (f - 1) / 2); slabs: scratch of slab_floats floats.  pad_l as cbhg_bwd passes it,
+ *   (F - 1) - (F - 1) / 2.  TACO_ENOTFOUND (nothing written) where cbhg_bwd falls back to the atomic batch below: S < 2, WT[f] not
+ *   contiguous behind WT[f-1], N % 4 != 0, K % 32 != 0, fewer than ceil(nit / ceil(nit / S)) M N slab floats, another pad_l, operands
+ *   off the float4 contract.
+ * taco_debug_conv_gemm_batch_atomic: that fall-back -- the F transposed convolutions as F problems of one launch adding into
+ *   dx_out with fp32 atomics (atomic_out), the residual on the f = 1 problem.  dx_out must hold what the sum is added to.
+ * taco_debug_conv_gemm_rowbias: C (M, N; ldc) = A (M, K; lda) . W (K, N; ldw) + rowb[m / T] with rowb (M / T, N; bias_stride): the
+ *   per-sequence bias of the speaker sites (ConvGemmProblem::bias_stride).
+ * taco_debug_gemm_tn_group: n <= 26 weight gradients W[i] (taps, K, N; ldw) += shift(A[i])^T . Y[i] as one launch_gemm_tn_batch call
+ *   (every argument a table of n entries); dbias (nullable as a table and per entry): dbias[i][n] += sum_m Y[i][m][n].
+ * taco_debug_gemm_tn_strided: `batch` problems of one launch, member z at A + z strideA, Y + z strideY, W + z strideW (floats),
+ *   accumulated into W; taps = 1 (the decoder's d keys product: M = T = Td, K = Tt, pad_l = 1). */
+int taco_debug_conv_bank_pool_fwd(const float* x, int lda, const float* const* W, const float* const* bias, const float* scale,
+                                  const float* shift, float scale_mul, float* pool, float* bank, int ldc, int M, int T, int F, int N, int K,
+                                  void* stream);
+int taco_debug_conv_gemm_pool_bwd(const float* A, int lda, const float* W, int ldw, const float* pool_x, const float* scale,
+                                  const float* shift, float scale_mul, float* C, int ldc, float* dgamma, float* dbeta, int M, int N, int K,
+                                  int taps, int T, int pad_l, void* stream);
+int taco_debug_bn_maxpool_fwd(const float* x, const float* gamma, const float* beta, float* y, int B, int T, int C, void* stream);
+int taco_debug_bn_maxpool_bwd(const float* x, const float* gamma, const float* beta, const float* dy, float* dx, float* dgamma,
+                              float* dbeta, int B, int T, int C, void* stream);
+int taco_debug_bank_gather(const float* dbank, int lda, const float* const* WT, const float* residual, int ldr, float* dx_out, int ldc,
+                           float* slabs, int64_t slab_floats, int M, int T, int F, int K, int N, int pad_l, int S, void* stream);
+int taco_debug_conv_gemm_batch_atomic(const float* dbank, int lda, const float* const* WT, const float* residual, int ldr, float* dx_out,
+                                      int ldc, int M, int T, int F, int K, int N, void* stream);
+int taco_debug_conv_gemm_rowbias(const float* A, int lda, const float* W, int ldw, const float* rowb, int bias_stride, float* C, int ldc,
+                                 int M, int T, int N, int K, void* stream);
+int taco_debug_gemm_tn_group(int n, const float* const* A, const int* lda, const float* const* Y, const int* ldy, float* const* W,
+                             const int* ldw, float* const* dbias, const int* M, const int* N, const int* K, const int* taps,
+                             const int* T, const int* pad_l, void* stream);
+int taco_debug_gemm_tn_strided(const float* A, int lda, int64_t strideA, const float* Y, int ldy, int64_t strideY, float* W, int ldw,
+                               int64_t strideW, int M, int N, int K, int T, int pad_l, int batch, void* stream);
+
 /* ---- model level ---------------------------------------------------------------------------------------- */
 /* Tacotron.inference with train=True (tacotron.py:107-154) + add_loss_op (tacotron.py:156-165).
  *   text (B,Tt) int32; text_length (B) int32; mel (B,Td,80r); stft (B,Td,1025r);

@@ -133,10 +133,12 @@ static inline bool ensure_dyn_smem(DynSmemOnce& done, const void* func, size_t b
 // bytes meet those of any other operand, is refused by name before anything is enqueued.
 struct DoorOperands {
   struct Op { char name[24]; const void* p; size_t bytes; bool out, optional; };
-  Op ops[64];
+  static constexpr int kMax = 128;   // (taco_debug_gemm_tn_group: 4 operands for each of kMaxTnBatch = 26 problems)
+  Op ops[kMax];
   int n = 0;
+  bool overflow = false;   // an operand that did not fit: check() refuses the call instead of leaving it unchecked
   void add(const void* p, size_t bytes, bool out, bool optional, const char* fmt, int idx = 0) {
-    if (n >= 64) return;
+    if (n >= kMax) { overflow = true; return; }
     Op& o = ops[n++];
     snprintf(o.name, sizeof(o.name), fmt, idx);
     o.p = p; o.bytes = bytes; o.out = out; o.optional = optional;
@@ -146,6 +148,7 @@ struct DoorOperands {
   void out(const void* p, size_t bytes, const char* fmt, int idx = 0) { add(p, bytes, true, false, fmt, idx); }
   void out_opt(const void* p, size_t bytes, const char* fmt, int idx = 0) { add(p, bytes, true, true, fmt, idx); }
   int check(const char* who) const {
+    TACO_REQUIRE(!overflow, "%s: more than %d operands to check", who, kMax);
     for (int i = 0; i < n; ++i)
       TACO_REQUIRE(ops[i].p || ops[i].optional, "%s: %s is null", who, ops[i].name);
     for (int i = 0; i < n; ++i) {
@@ -160,6 +163,10 @@ struct DoorOperands {
     return TACO_OK;
   }
 };
+
+// bytes of a (rows, cols) operand with row pitch ld, and the size limits of the GEMM-form doors (gemm.hip, gemm2.hip, elementwise.hip)
+static inline size_t door_span(int64_t rows, int64_t cols, int64_t ld) { return (size_t)((rows - 1) * ld + cols) * sizeof(float); }
+constexpr int kDoorMaxRows = 1 << 22, kDoorMaxCols = 1 << 14;
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

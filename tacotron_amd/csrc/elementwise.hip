@@ -1586,6 +1586,37 @@ int launch_bn_maxpool_bwd(const float* x, const float* gamma, const float* beta,
   TACO_LAUNCH_CHECK("bn_maxpool_bwd");
   return TACO_OK;
 }
+// ---- debug doors (include/taco_hip.h "op-level debug doors of the GEMM forms"): the two-pass twins of the pooled epilogues ----
+extern "C" int taco_debug_bn_maxpool_fwd(const float* x, const float* gamma, const float* beta, float* y, int B, int T, int C, void* stream) {
+  const char* who = "taco_debug_bn_maxpool_fwd";
+  TACO_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= kDoorMaxRows, "%s: B T must be in [1, 2^22], got B = %d, T = %d", who, B, T);
+  TACO_REQUIRE(C > 0 && C <= kDoorMaxCols && C % 4 == 0, "%s: C must be a multiple of 4 in [4, 2^14], got %d", who, C);
+  const size_t mc = (size_t)B * T * C * sizeof(float);
+  DoorOperands o;
+  o.in(x, mc, "x");
+  o.in(gamma, (size_t)C * sizeof(float), "gamma");
+  o.in(beta, (size_t)C * sizeof(float), "beta");
+  o.out(y, mc, "y");
+  TACO_TRY(o.check(who));
+  return launch_bn_maxpool(x, gamma, beta, y, B, T, C, as_stream(stream));
+}
+extern "C" int taco_debug_bn_maxpool_bwd(const float* x, const float* gamma, const float* beta, const float* dy, float* dx, float* dgamma,
+                                         float* dbeta, int B, int T, int C, void* stream) {
+  const char* who = "taco_debug_bn_maxpool_bwd";
+  TACO_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= kDoorMaxRows, "%s: B T must be in [1, 2^22], got B = %d, T = %d", who, B, T);
+  TACO_REQUIRE(C > 0 && C <= kDoorMaxCols && C % 4 == 0, "%s: C must be a multiple of 4 in [4, 2^14], got %d", who, C);
+  const size_t mc = (size_t)B * T * C * sizeof(float);
+  DoorOperands o;
+  o.in(x, mc, "x");
+  o.in(gamma, (size_t)C * sizeof(float), "gamma");
+  o.in(beta, (size_t)C * sizeof(float), "beta");
+  o.in(dy, mc, "dy");
+  o.out(dx, mc, "dx");
+  o.out(dgamma, (size_t)C * sizeof(float), "dgamma");
+  o.out(dbeta, (size_t)C * sizeof(float), "dbeta");
+  TACO_TRY(o.check(who));
+  return launch_bn_maxpool_bwd(x, gamma, beta, dy, dx, dgamma, dbeta, B, T, C, as_stream(stream));
+}
 int launch_highway_combine(const float* th, const float* x, float* y, int64_t M, hipStream_t s) {
   EW_LAUNCH(highway_combine_kernel, M * (kCb / 4), s, th, x, y, M);
   return TACO_OK;

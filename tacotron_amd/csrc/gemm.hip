@@ -937,3 +937,126 @@ int launch_gemm_naive(const ConvGemmProblem& p, hipStream_t stream) {
   TACO_LAUNCH_CHECK("gemm_naive");
   return TACO_OK;
 }
+
+// ---- debug doors (include/taco_hip.h "op-level debug doors of the GEMM forms"): the atomic K-problem batch, the row bias, the
+//      grouped and the strided-batch weight gradient, each built as model.hip builds it ----
+
+extern "C" int taco_debug_conv_gemm_batch_atomic(const float* dbank, int lda, const float* const* WT, const float* residual, int ldr,
+                                                 float* dx_out, int ldc, int M, int T, int F, int K, int N, void* stream) {
+  const char* who = "taco_debug_conv_gemm_batch_atomic";
+  TACO_REQUIRE(M > 0 && M <= kDoorMaxRows, "%s: M must be in [1, 2^22], got %d", who, M);
+  TACO_REQUIRE(T > 0 && M % T == 0, "%s: T must be positive and divide M = %d, got %d", who, M, T);
+  TACO_REQUIRE(F >= 1 && F <= kMaxGemmBatch, "%s: F must be in [1, %d], got %d", who, kMaxGemmBatch, F);
+  TACO_REQUIRE(N > 0 && N <= kDoorMaxCols, "%s: N must be in [1, 2^14], got %d", who, N);
+  TACO_REQUIRE(K > 0 && K <= kDoorMaxCols, "%s: K must be in [1, 2^14], got %d", who, K);
+  TACO_REQUIRE(lda >= F * K, "%s: lda must be >= F K = %d, got %d", who, F * K, lda);
+  TACO_REQUIRE(ldc >= N, "%s: ldc must be >= N = %d, got %d", who, N, ldc);
+  TACO_REQUIRE(!residual || ldr >= N, "%s: ldr must be >= N = %d, got %d", who, N, ldr);
+  TACO_REQUIRE(WT, "%s: WT is null", who);
+  DoorOperands o;
+  o.in(dbank, door_span(M, (int64_t)F * K, lda), "dbank");
+  for (int f = 1; f <= F; ++f) o.in(WT[f - 1], (size_t)f * K * N * sizeof(float), "WT[%d]", f - 1);
+  o.in_opt(residual, door_span(M, N, ldr), "residual");
+  o.out(dx_out, door_span(M, N, ldc), "dx_out");
+  TACO_TRY(o.check(who));
+  ConvGemmBatch batch;
+  batch.n = F;
+  for (int k = 1; k <= F; ++k) {   // cbhg_bwd's fall-back of the gather
+    ConvGemmProblem& p = batch.p[F - k];
+    p = ConvGemmProblem();
+    p.A = dbank + (k - 1) * K; p.lda = lda; p.W = WT[k - 1]; p.ldw = N; p.C = dx_out; p.ldc = ldc; p.M = M; p.N = N;
+    p.K = K; p.taps = k; p.T = T; p.pad_l = (k - 1) - (k - 1) / 2; p.act = TACO_ACT_NONE; p.atomic_out = 1;
+    if (k == 1) {
+      p.residual = residual;
+      p.ldr = ldr;
+    }
+  }
+  return launch_conv_gemm_batch(batch, as_stream(stream));
+}
+
+extern "C" int taco_debug_conv_gemm_rowbias(const float* A, int lda, const float* W, int ldw, const float* rowb, int bias_stride, float* C,
+                                            int ldc, int M, int T, int N, int K, void* stream) {
+  const char* who = "taco_debug_conv_gemm_rowbias";
+  TACO_REQUIRE(M > 0 && M <= kDoorMaxRows, "%s: M must be in [1, 2^22], got %d", who, M);
+  TACO_REQUIRE(T > 0 && M % T == 0, "%s: T must be positive and divide M = %d, got %d", who, M, T);
+  TACO_REQUIRE(N > 0 && N <= kDoorMaxCols, "%s: N must be in [1, 2^14], got %d", who, N);
+  TACO_REQUIRE(K > 0 && K <= kDoorMaxCols, "%s: K must be in [1, 2^14], got %d", who, K);
+  TACO_REQUIRE(lda >= K, "%s: lda must be >= K = %d, got %d", who, K, lda);
+  TACO_REQUIRE(ldw >= N, "%s: ldw must be >= N = %d, got %d", who, N, ldw);
+  TACO_REQUIRE(ldc >= N, "%s: ldc must be >= N = %d, got %d", who, N, ldc);
+  TACO_REQUIRE(bias_stride >= N, "%s: bias_stride must be >= N = %d, got %d", who, N, bias_stride);
+  DoorOperands o;
+  o.in(A, door_span(M, K, lda), "A");
+  o.in(W, door_span(K, N, ldw), "W");
+  o.in(rowb, door_span(M / T, N, bias_stride), "rowb");
+  o.out(C, door_span(M, N, ldc), "C");
+  TACO_TRY(o.check(who));
+  ConvGemmProblem p;   // the speaker site: dense_problem(...) + T + bias_stride
+  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = rowb; p.C = C; p.ldc = ldc;
+  p.M = M; p.N = N; p.K = K; p.taps = 1; p.pad_l = 0; p.act = TACO_ACT_NONE;
+  p.T = T;
+  p.bias_stride = bias_stride;
+  return launch_conv_gemm(p, as_stream(stream));
+}
+
+extern "C" int taco_debug_gemm_tn_group(int n, const float* const* A, const int* lda, const float* const* Y, const int* ldy,
+                                        float* const* W, const int* ldw, float* const* dbias, const int* M, const int* N, const int* K,
+                                        const int* taps, const int* T, const int* pad_l, void* stream) {
+  const char* who = "taco_debug_gemm_tn_group";
+  TACO_REQUIRE(n >= 1 && n <= kMaxTnBatch, "%s: n must be in [1, %d], got %d", who, kMaxTnBatch, n);
+  TACO_REQUIRE(A && lda && Y && ldy && W && ldw && M && N && K && taps && T && pad_l, "%s: a table is null", who);
+  DoorOperands o;
+  for (int i = 0; i < n; ++i) {
+    TACO_REQUIRE(M[i] > 0 && M[i] <= kDoorMaxRows, "%s: M[%d] must be in [1, 2^22], got %d", who, i, M[i]);
+    TACO_REQUIRE(T[i] > 0 && M[i] % T[i] == 0, "%s: T[%d] must be positive and divide M[%d] = %d, got %d", who, i, i, M[i], T[i]);
+    TACO_REQUIRE(N[i] > 0 && N[i] <= kDoorMaxCols, "%s: N[%d] must be in [1, 2^14], got %d", who, i, N[i]);
+    TACO_REQUIRE(K[i] > 0 && K[i] <= kDoorMaxCols, "%s: K[%d] must be in [1, 2^14], got %d", who, i, K[i]);
+    TACO_REQUIRE(taps[i] >= 1 && taps[i] <= 64, "%s: taps[%d] must be in [1, 64], got %d", who, i, taps[i]);
+    TACO_REQUIRE(pad_l[i] >= -64 && pad_l[i] <= 64, "%s: pad_l[%d] must be in [-64, 64], got %d", who, i, pad_l[i]);
+    TACO_REQUIRE(lda[i] >= K[i], "%s: lda[%d] must be >= K = %d, got %d", who, i, K[i], lda[i]);
+    TACO_REQUIRE(ldy[i] >= N[i], "%s: ldy[%d] must be >= N = %d, got %d", who, i, N[i], ldy[i]);
+    TACO_REQUIRE(ldw[i] >= N[i], "%s: ldw[%d] must be >= N = %d, got %d", who, i, N[i], ldw[i]);
+    o.in(A[i], door_span(M[i], K[i], lda[i]), "A[%d]", i);
+    o.in(Y[i], door_span(M[i], N[i], ldy[i]), "Y[%d]", i);
+    o.out(W[i], door_span((int64_t)taps[i] * K[i], N[i], ldw[i]), "W[%d]", i);
+    if (dbias) o.out_opt(dbias[i], (size_t)N[i] * sizeof(float), "dbias[%d]", i);
+  }
+  TACO_TRY(o.check(who));
+  GemmTnBatch b;
+  for (int i = 0; i < n; ++i) {   // model.hip `tn` inside a TnGroup scope
+    GemmTnArgs a;
+    a.dbias = dbias ? dbias[i] : nullptr;
+    a.A = A[i]; a.lda = lda[i]; a.Y = Y[i]; a.ldy = ldy[i]; a.W = W[i]; a.ldw = ldw[i]; a.M = M[i]; a.N = N[i]; a.K = K[i];
+    a.taps = taps[i]; a.T = T[i]; a.pad_l = pad_l[i];
+    b.p[b.n++] = a;
+  }
+  return launch_gemm_tn_batch(b, as_stream(stream));
+}
+
+extern "C" int taco_debug_gemm_tn_strided(const float* A, int lda, int64_t strideA, const float* Y, int ldy, int64_t strideY, float* W,
+                                          int ldw, int64_t strideW, int M, int N, int K, int T, int pad_l, int batch, void* stream) {
+  const char* who = "taco_debug_gemm_tn_strided";
+  TACO_REQUIRE(M > 0 && M <= kDoorMaxRows, "%s: M must be in [1, 2^22], got %d", who, M);
+  TACO_REQUIRE(T > 0 && M % T == 0, "%s: T must be positive and divide M = %d, got %d", who, M, T);
+  TACO_REQUIRE(N > 0 && N <= kDoorMaxCols, "%s: N must be in [1, 2^14], got %d", who, N);
+  TACO_REQUIRE(K > 0 && K <= kDoorMaxCols, "%s: K must be in [1, 2^14], got %d", who, K);
+  TACO_REQUIRE(batch >= 1 && batch <= 4096, "%s: batch must be in [1, 4096], got %d", who, batch);
+  TACO_REQUIRE(pad_l >= -64 && pad_l <= 64, "%s: pad_l must be in [-64, 64], got %d", who, pad_l);
+  TACO_REQUIRE(lda >= K, "%s: lda must be >= K = %d, got %d", who, K, lda);
+  TACO_REQUIRE(ldy >= N, "%s: ldy must be >= N = %d, got %d", who, N, ldy);
+  TACO_REQUIRE(ldw >= N, "%s: ldw must be >= N = %d, got %d", who, N, ldw);
+  const int64_t needA = (int64_t)(M - 1) * lda + K, needY = (int64_t)(M - 1) * ldy + N, needW = (int64_t)(K - 1) * ldw + N;
+  TACO_REQUIRE(strideA >= needA, "%s: strideA must be >= (M - 1) lda + K = %lld, got %lld", who, (long long)needA, (long long)strideA);
+  TACO_REQUIRE(strideY >= needY, "%s: strideY must be >= (M - 1) ldy + N = %lld, got %lld", who, (long long)needY, (long long)strideY);
+  TACO_REQUIRE(strideW >= needW, "%s: strideW must be >= (K - 1) ldw + N = %lld, got %lld", who, (long long)needW, (long long)strideW);
+  DoorOperands o;
+  o.in(A, (size_t)((batch - 1) * strideA + needA) * sizeof(float), "A");
+  o.in(Y, (size_t)((batch - 1) * strideY + needY) * sizeof(float), "Y");
+  o.out(W, (size_t)((batch - 1) * strideW + needW) * sizeof(float), "W");
+  TACO_TRY(o.check(who));
+  GemmTnArgs a;   // the decoder's `d keys` product (model.hip, "attention memory")
+  a.A = A; a.lda = lda; a.Y = Y; a.ldy = ldy; a.W = W; a.ldw = ldw;
+  a.M = M; a.N = N; a.K = K; a.taps = 1; a.T = T; a.pad_l = pad_l; a.batch = batch;
+  a.strideA = strideA; a.strideY = strideY; a.strideW = strideW;
+  return launch_gemm_tn(a, false, as_stream(stream));
+}

@@ -1275,3 +1275,128 @@ int launch_gemm_tn2(const GemmTnArgs* probs, int n, hipStream_t stream) {
   TACO_KLAUNCH(gemm_tn2_kernel, dim3(blocks), dim3(256), 2 * 2 * 32 * 128 * sizeof(float), stream, g);
   return TACO_OK;
 }
+
+// ---- debug doors (include/taco_hip.h "op-level debug doors of the GEMM forms"): the pooled epilogues and the bank gather alone,
+//      every ConvGemmProblem built exactly as cbhg_fwd / cbhg_bwd (model.hip) build theirs ----
+
+extern "C" int taco_debug_conv_bank_pool_fwd(const float* x, int lda, const float* const* W, const float* const* bias, const float* scale,
+                                             const float* shift, float scale_mul, float* pool, float* bank, int ldc, int M, int T, int F,
+                                             int N, int K, void* stream) {
+  const char* who = "taco_debug_conv_bank_pool_fwd";
+  TACO_REQUIRE(M > 0 && M <= kDoorMaxRows, "%s: M must be in [1, 2^22], got %d", who, M);
+  TACO_REQUIRE(T > 0 && M % T == 0, "%s: T must be positive and divide M = %d, got %d", who, M, T);
+  TACO_REQUIRE(F >= 1 && F <= kMaxGemmBatch, "%s: F must be in [1, %d], got %d", who, kMaxGemmBatch, F);
+  TACO_REQUIRE(N > 0 && N <= kDoorMaxCols, "%s: N must be in [1, 2^14], got %d", who, N);
+  TACO_REQUIRE(K > 0 && K <= kDoorMaxCols, "%s: K must be in [1, 2^14], got %d", who, K);
+  TACO_REQUIRE(lda >= K, "%s: lda must be >= K = %d, got %d", who, K, lda);
+  TACO_REQUIRE(ldc >= F * N, "%s: ldc must be >= F N = %d, got %d", who, F * N, ldc);
+  TACO_REQUIRE(W && bias, "%s: %s is null", who, W ? "bias" : "W");
+  DoorOperands o;
+  o.in(x, door_span(M, K, lda), "x");
+  for (int f = 1; f <= F; ++f) {
+    o.in(W[f - 1], (size_t)f * K * N * sizeof(float), "W[%d]", f - 1);
+    o.in_opt(bias[f - 1], (size_t)N * sizeof(float), "bias[%d]", f - 1);
+  }
+  o.in(scale, (size_t)F * N * sizeof(float), "scale");
+  o.in(shift, (size_t)F * N * sizeof(float), "shift");
+  o.out(pool, door_span(M, (int64_t)F * N, ldc), "pool");
+  o.out_opt(bank, door_span(M, (int64_t)F * N, ldc), "bank");
+  TACO_TRY(o.check(who));
+  ConvGemmBatch batch;
+  batch.n = F;
+  for (int k = 1; k <= F; ++k) {
+    ConvGemmProblem& p = batch.p[F - k];   // widest kernel first, as cbhg_fwd
+    p = ConvGemmProblem();
+    p.A = x; p.lda = lda; p.W = W[k - 1]; p.ldw = N; p.bias = bias[k - 1];
+    p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.taps = k; p.T = T;
+    p.pad_l = (k - 1) / 2; p.act = TACO_ACT_RELU;
+    p.C = pool + (k - 1) * N; p.Cpre = bank ? bank + (k - 1) * N : nullptr;
+    p.scale = scale + (k - 1) * N; p.shift = shift + (k - 1) * N; p.scale_mul = scale_mul; p.pool = 1;
+  }
+  return launch_conv_gemm_batch(batch, as_stream(stream));   // TACO_ENOTFOUND: the caller runs conv + bn_maxpool as two passes
+}
+
+extern "C" int taco_debug_conv_gemm_pool_bwd(const float* A, int lda, const float* W, int ldw, const float* pool_x, const float* scale,
+                                             const float* shift, float scale_mul, float* C, int ldc, float* dgamma, float* dbeta, int M,
+                                             int N, int K, int taps, int T, int pad_l, void* stream) {
+  const char* who = "taco_debug_conv_gemm_pool_bwd";
+  TACO_REQUIRE(M > 0 && M <= kDoorMaxRows, "%s: M must be in [1, 2^22], got %d", who, M);
+  TACO_REQUIRE(T > 0 && M % T == 0, "%s: T must be positive and divide M = %d, got %d", who, M, T);
+  TACO_REQUIRE(N > 0 && N <= kDoorMaxCols, "%s: N must be in [1, 2^14], got %d", who, N);
+  TACO_REQUIRE(K > 0 && K <= kDoorMaxCols, "%s: K must be in [1, 2^14], got %d", who, K);
+  TACO_REQUIRE(taps >= 1 && taps <= 64, "%s: taps must be in [1, 64], got %d", who, taps);
+  TACO_REQUIRE(pad_l >= -64 && pad_l <= 64, "%s: pad_l must be in [-64, 64], got %d", who, pad_l);
+  TACO_REQUIRE(lda >= K, "%s: lda must be >= K = %d, got %d", who, K, lda);
+  TACO_REQUIRE(ldw >= N, "%s: ldw must be >= N = %d, got %d", who, N, ldw);
+  TACO_REQUIRE(ldc >= N, "%s: ldc must be >= N = %d, got %d", who, N, ldc);
+  DoorOperands o;
+  o.in(A, door_span(M, K, lda), "A");
+  o.in(W, door_span((int64_t)taps * K, N, ldw), "W");
+  o.in(pool_x, door_span(M, N, ldc), "pool_x");
+  o.in(scale, (size_t)N * sizeof(float), "scale");
+  o.in(shift, (size_t)N * sizeof(float), "shift");
+  o.out(C, door_span(M, N, ldc), "C");
+  o.out(dgamma, (size_t)N * sizeof(float), "dgamma");
+  o.out(dbeta, (size_t)N * sizeof(float), "dbeta");
+  TACO_TRY(o.check(who));
+  if (taco_deterministic()) return TACO_ENOTFOUND;   // cbhg_bwd: a fixed summation order takes the two-pass form
+  ConvGemmProblem q;
+  q.A = A; q.lda = lda; q.W = W; q.ldw = ldw; q.C = C; q.ldc = ldc; q.M = M; q.N = N; q.K = K;
+  q.taps = taps; q.T = T; q.pad_l = pad_l; q.act = TACO_ACT_NONE;
+  q.pool = 2; q.pool_x = pool_x; q.scale = scale; q.shift = shift;
+  q.scale_mul = scale_mul; q.pool_dgamma = dgamma; q.pool_dbeta = dbeta;
+  return launch_conv_gemm(q, as_stream(stream));
+}
+
+extern "C" int taco_debug_bank_gather(const float* dbank, int lda, const float* const* WT, const float* residual, int ldr, float* dx_out,
+                                      int ldc, float* slabs, int64_t slab_floats, int M, int T, int F, int K, int N, int pad_l, int S,
+                                      void* stream) {
+  const char* who = "taco_debug_bank_gather";
+  TACO_REQUIRE(M > 0 && M <= kDoorMaxRows, "%s: M must be in [1, 2^22], got %d", who, M);
+  TACO_REQUIRE(T > 0 && M % T == 0, "%s: T must be positive and divide M = %d, got %d", who, M, T);
+  TACO_REQUIRE(F >= 1 && F <= kMaxGemmBatch, "%s: F must be in [1, %d], got %d", who, kMaxGemmBatch, F);
+  TACO_REQUIRE(N > 0 && N <= kDoorMaxCols, "%s: N must be in [1, 2^14], got %d", who, N);
+  TACO_REQUIRE(K > 0 && K <= kDoorMaxCols, "%s: K must be in [1, 2^14], got %d", who, K);
+  TACO_REQUIRE(S >= 1 && S <= kMaxGemmBatch, "%s: S must be in [1, %d], got %d", who, kMaxGemmBatch, S);
+  TACO_REQUIRE(pad_l >= -64 && pad_l <= 64, "%s: pad_l must be in [-64, 64], got %d", who, pad_l);
+  TACO_REQUIRE(lda >= F * K, "%s: lda must be >= F K = %d, got %d", who, F * K, lda);
+  TACO_REQUIRE(ldc >= N, "%s: ldc must be >= N = %d, got %d", who, N, ldc);
+  TACO_REQUIRE(!residual || ldr >= N, "%s: ldr must be >= N = %d, got %d", who, N, ldr);
+  TACO_REQUIRE(slab_floats >= 0, "%s: slab_floats must be >= 0, got %lld", who, (long long)slab_floats);
+  TACO_REQUIRE(WT, "%s: WT is null", who);
+  DoorOperands o;
+  o.in(dbank, door_span(M, (int64_t)F * K, lda), "dbank");
+  for (int f = 1; f <= F; ++f) o.in(WT[f - 1], (size_t)f * K * N * sizeof(float), "WT[%d]", f - 1);
+  o.in_opt(residual, door_span(M, N, ldr), "residual");
+  o.out(dx_out, door_span(M, N, ldc), "dx_out");
+  if (slab_floats > 0) o.out(slabs, (size_t)slab_floats * sizeof(float), "slabs");
+  TACO_TRY(o.check(who));
+  // what follows is cbhg_bwd's gather branch with its S given by the caller
+  bool contiguous = true;
+  for (int k = 2; k <= F; ++k) contiguous = contiguous && WT[k - 1] == WT[k - 2] + (int64_t)(k - 1) * K * N;
+  const int64_t mn = (int64_t)M * N;
+  if (!contiguous || !slabs || N % 4 != 0 || S < 2 || K % 32 != 0) return TACO_ENOTFOUND;
+  const int taps = F * (F + 1) / 2, nit = taps * (K / 32);
+  const int per = cdiv(nit, S);
+  ConvGemmBatch g;
+  g.n = cdiv(nit, per);
+  if ((int64_t)g.n * mn > slab_floats) return TACO_ENOTFOUND;
+  for (int ch = 0; ch < g.n; ++ch) {
+    ConvGemmProblem& p = g.p[ch];
+    p = ConvGemmProblem();
+    p.A = dbank; p.lda = lda; p.W = WT[0]; p.ldw = N; p.C = slabs + ch * mn; p.ldc = N; p.M = M;
+    p.N = N; p.K = K; p.taps = taps; p.T = T; p.pad_l = pad_l; p.act = TACO_ACT_NONE;
+    p.bank_filters = F;
+    p.it0 = ch * per;
+    p.it1 = std::min(nit, (ch + 1) * per);
+    conv_gemm_set_flags(p);
+  }
+  hipStream_t s = as_stream(stream);
+  int rc = launch_conv_gemm2(g, s, /*force=*/true);
+  if (rc != TACO_OK) return rc;
+  ConvGemmProblem fin;
+  fin.M = M; fin.N = N; fin.T = T; fin.C = dx_out; fin.ldc = ldc; fin.act = TACO_ACT_NONE;
+  fin.residual = residual; fin.ldr = ldr;
+  fin.atomic_out = 1;   // dx_out += ...
+  return launch_conv_gemm_slab_sum(fin, slabs, g.n, s);
+}

@@ -107,6 +107,15 @@ EXPORTS = {
     'taco_debug_highway_stack_bwd': (C.c_int, [_P] * 8 + [_I, _I, _P]),
     'taco_debug_prenet_fwd': (C.c_int, [_P] * 9 + [_I, _P]),
     'taco_debug_prenet_bwd': (C.c_int, [_P] * 10 + [_I, _P]),
+    'taco_debug_conv_bank_pool_fwd': (C.c_int, [_P, _I, _P, _P, _P, _P, C.c_float, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'taco_debug_conv_gemm_pool_bwd': (C.c_int, [_P, _I, _P, _I, _P, _P, _P, C.c_float, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'taco_debug_bn_maxpool_fwd': (C.c_int, [_P] * 4 + [_I, _I, _I, _P]),
+    'taco_debug_bn_maxpool_bwd': (C.c_int, [_P] * 7 + [_I, _I, _I, _P]),
+    'taco_debug_bank_gather': (C.c_int, [_P, _I, _P, _P, _I, _P, _I, _P, C.c_int64, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'taco_debug_conv_gemm_batch_atomic': (C.c_int, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'taco_debug_conv_gemm_rowbias': (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'taco_debug_gemm_tn_group': (C.c_int, [_I] + [_P] * 13 + [_P]),
+    'taco_debug_gemm_tn_strided': (C.c_int, [_P, _I, C.c_int64, _P, _I, C.c_int64, _P, _I, C.c_int64, _I, _I, _I, _I, _I, _I, _P]),
     'taco_forward': (C.c_int, [_SH] + [_P] * 17),
     'taco_backward': (C.c_int, [_SH] + [_P] * 14),
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
@@ -486,6 +495,215 @@ def debug_prenet_bwd(dy2, w2T, w1T, y1_in, y2_in, dz2, dz1, dx, keep1=None, keep
     on_gpu(who, 'dy2', dev)
     _check(_lib.taco_debug_prenet_bwd(ptr(dy2), ptr(w2T), ptr(w1T), ptr(keep1), ptr(keep2), ptr(y1_in), ptr(y2_in), ptr(dz2), ptr(dz1),
                                       ptr(dx), M, stream_ptr()), 'taco_debug_prenet_bwd')
+
+
+# ---- op-level debug doors of the GEMM forms only the model reaches (include/taco_hip.h; tests/test_gpu_gemm_forms.py) ----
+# Every tensor is a FLAT contiguous float32 tensor that starts at the operand's element (0, 0) and holds at least
+# (rows - 1) * pitch + cols floats; a door returns True when its form ran and False where the library falls back to another
+# (TACO_ENOTFOUND: nothing was enqueued).
+TACO_ENOTFOUND = -3
+DOOR_MAX_GEMM_ROWS = 1 << 22
+DOOR_MAX_GEMM_COLS = 1 << 14
+
+
+def _span(rows, cols, ld):
+    return (rows - 1) * ld + cols
+
+
+def _flat_args(who, ins, outs):
+    """ins, outs: [(name, tensor, floats needed, optional)] -> the device of the first input.  Each must be a flat float32 tensor
+    of at least that many floats, all on one device; no output's extent may meet another operand's; the device check comes last."""
+    dev = ins[0][1].device if torch.is_tensor(ins[0][1]) else None
+    for name, t, need, optional in ins + outs:
+        if tensor_arg(who, name, t, torch.float32, ('n',), dev, optional) is not None and t.numel() < need:
+            raise ValueError('%s: %s must hold at least %d floats, got %d' % (who, name, need, t.numel()))
+    live_in = [(n, t, need) for n, t, need, _ in ins if t is not None]
+    live_out = [(n, t, need) for n, t, need, _ in outs if t is not None]
+    for i, (n_out, t_out, need_out) in enumerate(live_out):
+        for n_in, t_in, need_in in live_in + live_out[i + 1:]:
+            no_overlap(who, n_in, t_in, n_out, t_out[:need_out], span_in=4 * need_in)
+    on_gpu(who, ins[0][0], dev)
+    return dev
+
+
+def _gemm_dims(who, M, T, **cols):
+    M = int_arg(who, 'M', M, 1, DOOR_MAX_GEMM_ROWS)
+    T = int_arg(who, 'T', T, 1, M)
+    if M % T:
+        raise ValueError('%s: T must divide M, got M = %d, T = %d' % (who, M, T))
+    return (M, T) + tuple(int_arg(who, k, v, 1, DOOR_MAX_GEMM_COLS) for k, v in cols.items())
+
+
+def _pitch(who, name, ld, least):
+    ld = int_arg(who, name, least if ld is None else ld, 1, _INT_MAX)
+    if ld < least:
+        raise ValueError('%s: %s must be >= %d, got %d' % (who, name, least, ld))
+    return ld
+
+
+def _ptr_table(ts):
+    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _filter_list(who, name, ts, lo=1, hi=16):
+    if not isinstance(ts, (list, tuple)) or not lo <= len(ts) <= hi:
+        raise ValueError('%s: %s must be a list of %d to %d tensors (one per filter width), got %s'
+                         % (who, name, lo, hi, '%d' % len(ts) if isinstance(ts, (list, tuple)) else 'a %s' % type(ts).__name__))
+    return len(ts)
+
+
+def _door(rc, what):
+    if rc == TACO_ENOTFOUND:
+        return False
+    _check(rc, what)
+    return True
+
+
+def debug_conv_bank_pool_fwd(x, W, bias, scale, shift, pool, M, T, N, K, scale_mul=1.0, bank=None, lda=None, ldc=None):
+    """The conv bank with the pooled epilogue (taco_debug_conv_bank_pool_fwd): x (M, K; lda), W[f-1] (f, K, N) and bias[f-1] (N) or
+    None for f = 1..F = len(W), scale / shift (F N) -> pool and, when given, bank (M, F N; ldc).  False: gemm2.hip did not take it."""
+    who = 'debug_conv_bank_pool_fwd'
+    F = _filter_list(who, 'W', W)
+    if not isinstance(bias, (list, tuple)) or len(bias) != F:
+        raise ValueError('%s: bias must be a list of %d tensors or Nones (one per filter width)' % (who, F))
+    M, T, N, K = _gemm_dims(who, M, T, N=N, K=K)
+    lda, ldc = _pitch(who, 'lda', lda, K), _pitch(who, 'ldc', ldc, F * N)
+    ins = [('x', x, _span(M, K, lda), False)]
+    ins += [('W[%d]' % f, W[f], (f + 1) * K * N, False) for f in range(F)] + [('bias[%d]' % f, bias[f], N, True) for f in range(F)]
+    ins += [('scale', scale, F * N, False), ('shift', shift, F * N, False)]
+    _flat_args(who, ins, [('pool', pool, _span(M, F * N, ldc), False), ('bank', bank, _span(M, F * N, ldc), True)])
+    return _door(_lib.taco_debug_conv_bank_pool_fwd(ptr(x), lda, _ptr_table(W), _ptr_table(bias), ptr(scale), ptr(shift), float(scale_mul),
+                                                    ptr(pool), ptr(bank), ldc, M, T, F, N, K, stream_ptr()), 'taco_debug_conv_bank_pool_fwd')
+
+
+def debug_conv_gemm_pool_bwd(A, W, pool_x, scale, shift, C_out, dgamma, dbeta, M, T, N, K, taps=3, pad_l=1, scale_mul=1.0, lda=None,
+                             ldw=None, ldc=None):
+    """One GEMM with the backward pooled epilogue (taco_debug_conv_gemm_pool_bwd): A (M, K; lda), W (taps, K, N; ldw), pool_x (M, N;
+    ldc), scale / shift (N) -> C_out (M, N; ldc); dgamma, dbeta (N) are added to.  False: the two-pass form would run."""
+    who = 'debug_conv_gemm_pool_bwd'
+    M, T, N, K = _gemm_dims(who, M, T, N=N, K=K)
+    taps, pad_l = int_arg(who, 'taps', taps, 1, 64), int_arg(who, 'pad_l', pad_l, -64, 64)
+    lda, ldw, ldc = _pitch(who, 'lda', lda, K), _pitch(who, 'ldw', ldw, N), _pitch(who, 'ldc', ldc, N)
+    _flat_args(who, [('A', A, _span(M, K, lda), False), ('W', W, _span(taps * K, N, ldw), False), ('pool_x', pool_x, _span(M, N, ldc), False),
+                     ('scale', scale, N, False), ('shift', shift, N, False)],
+               [('C_out', C_out, _span(M, N, ldc), False), ('dgamma', dgamma, N, False), ('dbeta', dbeta, N, False)])
+    return _door(_lib.taco_debug_conv_gemm_pool_bwd(ptr(A), lda, ptr(W), ldw, ptr(pool_x), ptr(scale), ptr(shift), float(scale_mul), ptr(C_out),
+                                                    ldc, ptr(dgamma), ptr(dbeta), M, N, K, taps, T, pad_l, stream_ptr()),
+                 'taco_debug_conv_gemm_pool_bwd')
+
+
+def _bn_pool_dims(who, B, T, C_cols):
+    B, T = int_arg(who, 'B', B, 1, DOOR_MAX_GEMM_ROWS), int_arg(who, 'T', T, 1, DOOR_MAX_GEMM_ROWS)
+    if B * T > DOOR_MAX_GEMM_ROWS:
+        raise ValueError('%s: B T must be <= %d, got %d' % (who, DOOR_MAX_GEMM_ROWS, B * T))
+    C_cols = int_arg(who, 'C', C_cols, 4, DOOR_MAX_GEMM_COLS)
+    if C_cols % 4:
+        raise ValueError('%s: C must be a multiple of 4, got %d' % (who, C_cols))
+    return B, T, C_cols
+
+
+def debug_bn_maxpool_fwd(x, gamma, beta, y, B, T, C_cols):
+    """The two-pass twin of the pooled forward epilogue (taco_debug_bn_maxpool_fwd): x, y dense (B T, C), gamma, beta (C)."""
+    who = 'debug_bn_maxpool_fwd'
+    B, T, C_cols = _bn_pool_dims(who, B, T, C_cols)
+    mc = B * T * C_cols
+    _flat_args(who, [('x', x, mc, False), ('gamma', gamma, C_cols, False), ('beta', beta, C_cols, False)], [('y', y, mc, False)])
+    _check(_lib.taco_debug_bn_maxpool_fwd(ptr(x), ptr(gamma), ptr(beta), ptr(y), B, T, C_cols, stream_ptr()), 'taco_debug_bn_maxpool_fwd')
+
+
+def debug_bn_maxpool_bwd(x, gamma, beta, dy, dx, dgamma, dbeta, B, T, C_cols):
+    """The two-pass twin of the pooled backward epilogue (taco_debug_bn_maxpool_bwd): x, dy, dx dense (B T, C); dgamma, dbeta (C) are
+    added to."""
+    who = 'debug_bn_maxpool_bwd'
+    B, T, C_cols = _bn_pool_dims(who, B, T, C_cols)
+    mc = B * T * C_cols
+    _flat_args(who, [('x', x, mc, False), ('gamma', gamma, C_cols, False), ('beta', beta, C_cols, False), ('dy', dy, mc, False)],
+               [('dx', dx, mc, False), ('dgamma', dgamma, C_cols, False), ('dbeta', dbeta, C_cols, False)])
+    _check(_lib.taco_debug_bn_maxpool_bwd(ptr(x), ptr(gamma), ptr(beta), ptr(dy), ptr(dx), ptr(dgamma), ptr(dbeta), B, T, C_cols, stream_ptr()),
+           'taco_debug_bn_maxpool_bwd')
+
+
+def debug_bank_gather(dbank, WT, dx_out, slabs, M, T, K, N, S, residual=None, pad_l=None, lda=None, ldc=None, ldr=None):
+    """The conv bank's input gradient as one reduction in S chunks + slab sum (taco_debug_bank_gather): dbank (M, F K; lda), WT[f-1]
+    (f, K, N) the transposed kernels (contiguous one behind the other for the gather to run), residual (M, N; ldr) or None ->
+    dx_out (M, N; ldc) is added to.  pad_l None: (F - 1) - (F - 1) // 2.  False: the library would run the atomic batch."""
+    who = 'debug_bank_gather'
+    F = _filter_list(who, 'WT', WT)
+    M, T, N, K = _gemm_dims(who, M, T, N=N, K=K)
+    S = int_arg(who, 'S', S, 1, 16)
+    pad_l = int_arg(who, 'pad_l', (F - 1) - (F - 1) // 2 if pad_l is None else pad_l, -64, 64)
+    lda, ldc, ldr = _pitch(who, 'lda', lda, F * K), _pitch(who, 'ldc', ldc, N), _pitch(who, 'ldr', ldr, N)
+    ins = [('dbank', dbank, _span(M, F * K, lda), False)] + [('WT[%d]' % f, WT[f], (f + 1) * K * N, False) for f in range(F)]
+    ins += [('residual', residual, _span(M, N, ldr), True)]
+    _flat_args(who, ins, [('dx_out', dx_out, _span(M, N, ldc), False), ('slabs', slabs, slabs.numel() if torch.is_tensor(slabs) else 1, False)])
+    return _door(_lib.taco_debug_bank_gather(ptr(dbank), lda, _ptr_table(WT), ptr(residual), ldr, ptr(dx_out), ldc, ptr(slabs), slabs.numel(),
+                                             M, T, F, K, N, pad_l, S, stream_ptr()), 'taco_debug_bank_gather')
+
+
+def debug_conv_gemm_batch_atomic(dbank, WT, dx_out, M, T, K, N, residual=None, lda=None, ldc=None, ldr=None):
+    """The atomic K-problem batch, the gather's fall-back (taco_debug_conv_gemm_batch_atomic): operands as debug_bank_gather; dx_out
+    is added to with fp32 atomics."""
+    who = 'debug_conv_gemm_batch_atomic'
+    F = _filter_list(who, 'WT', WT)
+    M, T, N, K = _gemm_dims(who, M, T, N=N, K=K)
+    lda, ldc, ldr = _pitch(who, 'lda', lda, F * K), _pitch(who, 'ldc', ldc, N), _pitch(who, 'ldr', ldr, N)
+    ins = [('dbank', dbank, _span(M, F * K, lda), False)] + [('WT[%d]' % f, WT[f], (f + 1) * K * N, False) for f in range(F)]
+    ins += [('residual', residual, _span(M, N, ldr), True)]
+    _flat_args(who, ins, [('dx_out', dx_out, _span(M, N, ldc), False)])
+    _check(_lib.taco_debug_conv_gemm_batch_atomic(ptr(dbank), lda, _ptr_table(WT), ptr(residual), ldr, ptr(dx_out), ldc, M, T, F, K, N,
+                                                  stream_ptr()), 'taco_debug_conv_gemm_batch_atomic')
+
+
+def debug_conv_gemm_rowbias(A, W, rowb, C_out, M, T, N, K, bias_stride=None, lda=None, ldw=None, ldc=None):
+    """A dense layer with a per-sequence bias (taco_debug_conv_gemm_rowbias): C_out (M, N; ldc) = A (M, K; lda) . W (K, N; ldw) +
+    rowb[m // T] with rowb (M // T, N; bias_stride)."""
+    who = 'debug_conv_gemm_rowbias'
+    M, T, N, K = _gemm_dims(who, M, T, N=N, K=K)
+    lda, ldw, ldc = _pitch(who, 'lda', lda, K), _pitch(who, 'ldw', ldw, N), _pitch(who, 'ldc', ldc, N)
+    bias_stride = _pitch(who, 'bias_stride', bias_stride, N)
+    _flat_args(who, [('A', A, _span(M, K, lda), False), ('W', W, _span(K, N, ldw), False), ('rowb', rowb, _span(M // T, N, bias_stride), False)],
+               [('C_out', C_out, _span(M, N, ldc), False)])
+    _check(_lib.taco_debug_conv_gemm_rowbias(ptr(A), lda, ptr(W), ldw, ptr(rowb), bias_stride, ptr(C_out), ldc, M, T, N, K, stream_ptr()),
+           'taco_debug_conv_gemm_rowbias')
+
+
+def debug_gemm_tn_group(problems):
+    """Up to 26 (kMaxTnBatch) weight gradients as one grouped launch (taco_debug_gemm_tn_group).  problems: a list of dicts with A (M, K;
+    lda), Y (M, N; ldy), W (taps, K, N; ldw; added to), M, T, N, K, taps, pad_l and optionally dbias ((N), added to), lda, ldy, ldw."""
+    who = 'debug_gemm_tn_group'
+    if not isinstance(problems, (list, tuple)) or not 1 <= len(problems) <= 26:
+        raise ValueError('%s: problems must be a list of 1 to 26 dicts' % who)
+    ins, outs, rows = [], [], []
+    for i, p in enumerate(problems):
+        w = '%s: problems[%d]' % (who, i)
+        M, T, N, K = _gemm_dims(w, p['M'], p['T'], N=p['N'], K=p['K'])
+        taps, pad_l = int_arg(w, 'taps', p['taps'], 1, 64), int_arg(w, 'pad_l', p['pad_l'], -64, 64)
+        lda, ldy, ldw = _pitch(w, 'lda', p.get('lda'), K), _pitch(w, 'ldy', p.get('ldy'), N), _pitch(w, 'ldw', p.get('ldw'), N)
+        ins += [('A[%d]' % i, p['A'], _span(M, K, lda), False), ('Y[%d]' % i, p['Y'], _span(M, N, ldy), False)]
+        outs += [('W[%d]' % i, p['W'], _span(taps * K, N, ldw), False), ('dbias[%d]' % i, p.get('dbias'), N, True)]
+        rows.append((lda, ldy, ldw, M, N, K, taps, T, pad_l))
+    _flat_args(who, ins, outs)
+    n = len(problems)
+    col = lambda j: (C.c_int * n)(*[r[j] for r in rows])
+    dbias = [p.get('dbias') for p in problems]
+    _check(_lib.taco_debug_gemm_tn_group(n, _ptr_table([p['A'] for p in problems]), col(0), _ptr_table([p['Y'] for p in problems]), col(1),
+                                         _ptr_table([p['W'] for p in problems]), col(2), _ptr_table(dbias) if any(d is not None for d in dbias) else None,
+                                         col(3), col(4), col(5), col(6), col(7), col(8), stream_ptr()), 'taco_debug_gemm_tn_group')
+
+
+def debug_gemm_tn_strided(A, Y, W, M, N, K, batch, strideA, strideY, strideW, T=None, pad_l=1, lda=None, ldy=None, ldw=None):
+    """`batch` weight gradients of one launch (taco_debug_gemm_tn_strided): member z reads A + z strideA (M, K; lda) and Y + z strideY
+    (M, N; ldy) and adds to W + z strideW (K, N; ldw); strides in floats."""
+    who = 'debug_gemm_tn_strided'
+    M, T, N, K = _gemm_dims(who, M, M if T is None else T, N=N, K=K)
+    batch, pad_l = int_arg(who, 'batch', batch, 1, 4096), int_arg(who, 'pad_l', pad_l, -64, 64)
+    lda, ldy, ldw = _pitch(who, 'lda', lda, K), _pitch(who, 'ldy', ldy, N), _pitch(who, 'ldw', ldw, N)
+    need = (_span(M, K, lda), _span(M, N, ldy), _span(K, N, ldw))
+    strides = [_pitch(who, n, s, least) for n, s, least in zip(('strideA', 'strideY', 'strideW'), (strideA, strideY, strideW), need)]
+    ext = [(batch - 1) * s + n for s, n in zip(strides, need)]
+    _flat_args(who, [('A', A, ext[0], False), ('Y', Y, ext[1], False)], [('W', W, ext[2], False)])
+    _check(_lib.taco_debug_gemm_tn_strided(ptr(A), lda, strides[0], ptr(Y), ldy, strides[1], ptr(W), ldw, strides[2], M, N, K, T, pad_l, batch,
+                                           stream_ptr()), 'taco_debug_gemm_tn_strided')
 
 
 def forward(shape, params, text, text_length, mel, stft, masks, s2s, out, align, loss, workspace, speaker=None):

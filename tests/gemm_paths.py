@@ -22,10 +22,13 @@ Path labels (PATH_TABLE; tests/test_gemm_paths_host.py requires the case lists t
   g2.{f32,bx}.{vec,shifted,scalar}   conv_gemm2_kernel's MFMA form and epilogue form
   ksplit.S2 / S3 / S5          the k-split launch with the S that really runs
   tn.t64.* / tn.t128.*         gemm_tn_kernel<1,1,..> / <2,2,..>: f3.bx, f3.f32, f1, f2, f0
+  g2.pool1.* g2.pool2 ew.bnpool.* g2.bank.S* nn.atomic nn.rowbias tn.group tn.strided   see tests/gemm_forms.py
 
-Not covered by these lists, because the C ABI (taco_conv_gemm, taco_gemm_tn and the debug entries) does not reach them:
-bias_stride, atomic_out, scale_mul, pool, bank_filters, the grouped TN launch and strideA / strideY / strideW.  The model-level
-tests remain their only cover.
+The forms only the model's own launches build -- bias_stride, atomic_out, scale_mul, pool, bank_filters, the grouped TN launch and
+strideA / strideY / strideW -- have their references, contracts, labels and case lists in tests/gemm_forms.py (through the debug
+doors of include/taco_hip.h); their labels are part of PATH_TABLE below.  Still reached by the model-level tests only: the conv-bank
+XCD order of gemm2.hip (xcd_map == 2), which needs a batch of 8 or 16 problems with equal tile counts -- a tile ORDER, not a form:
+it changes which workgroup computes a tile, not what the tile holds.
 """
 import zlib
 from collections import namedtuple
@@ -219,7 +222,10 @@ PATH_TABLE = frozenset(
     ['nn.t%d.f%d' % (t, f) for t in (64, 128) for f in range(4)] +
     ['g2.%s.%s' % (m, e) for m in ('f32', 'bx') for e in ('vec', 'shifted', 'scalar')] +
     ['ksplit.S2', 'ksplit.S3', 'ksplit.S5'] +
-    ['tn.t%d.%s' % (t, f) for t in (64, 128) for f in ('f3.bx', 'f3.f32', 'f1', 'f2', 'f0')])
+    ['tn.t%d.%s' % (t, f) for t in (64, 128) for f in ('f3.bx', 'f3.f32', 'f1', 'f2', 'f0')] +
+    # the forms of tests/gemm_forms.py
+    ['g2.pool1.f32', 'g2.pool1.bx', 'g2.pool2', 'ew.bnpool.fwd', 'ew.bnpool.bwd', 'g2.bank.S2', 'g2.bank.S3', 'nn.atomic', 'nn.rowbias',
+     'tn.group', 'tn.strided'])
 
 # ------------------------------------------------------------------------------------------------------------------
 # case lists.  Offsets are in floats from a 256-byte aligned buffer start (offK: bytes); every pitch is written out.

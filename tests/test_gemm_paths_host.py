@@ -4,6 +4,7 @@ torch.nn.functional.conv1d in fp64; the predicates against the known routes of t
 import numpy as np
 import torch
 
+from tests import gemm_forms as gf
 from tests import gemm_paths as gp
 
 
@@ -18,6 +19,8 @@ def _labels():
         out.setdefault('ksplit.S%d' % S, []).append(c.id)
     for c in gp.TN_PATH_CASES:
         out.setdefault(gp.tn_case_plan(c)['label'], []).append(c.id)
+    for label, ids in gf.form_labels().items():         # the forms of tests/gemm_forms.py
+        out.setdefault(label, []).extend(ids)
     return out
 
 
@@ -25,7 +28,7 @@ def test_case_lists_reach_every_path_label():
     got = _labels()
     assert set(got) == set(gp.PATH_TABLE), 'missing: %s, not in the table: %s' % (sorted(set(gp.PATH_TABLE) - set(got)),
                                                                                   sorted(set(got) - set(gp.PATH_TABLE)))
-    assert len(gp.PATH_TABLE) == 8 + 6 + 3 + 10
+    assert len(gp.PATH_TABLE) == 8 + 6 + 3 + 10 + len(gf.FORM_LABELS) and set(gf.FORM_LABELS) <= set(got)
 
 
 def test_every_case_states_the_path_the_restatement_gives():

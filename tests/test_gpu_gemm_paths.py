@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import gemm_forms as gf
 from tests import gemm_paths as gp
 from tests.poison import Guarded
 
@@ -24,17 +25,28 @@ pytestmark = pytest.mark.gpu
 STATS = {}      # path label -> [cases, worst rel-L2, worst |err| / element bound]
 
 
+def write_error_table():
+    """The whole table from STATS, the one place that writes it: the rows of this file, then those of tests/test_gpu_gemm_forms.py
+    under a comment line of their own.  Both modules call it when they end, so the file is complete after whichever ends last."""
+    out = os.environ.get('GEMM_PATHS_ERRORS_OUT')
+    if not out or not STATS:
+        return
+    row = lambda k: '%-18s %6d %12.3e %12.3e\n' % (k, STATS[k][0], STATS[k][1], STATS[k][2])
+    forms = [k for k in sorted(STATS) if k in gf.FORM_LABELS]
+    with open(out, 'w') as f:
+        f.write('# tests/test_gpu_gemm_paths.py: per path label, cases run, worst rel-L2 against fp64 (bar 5e-6) and worst\n'
+                '# |got - ref| / element bound (bar 1; tests/gemm_paths.py element_bound)\n')
+        f.write('%-18s %6s %12s %12s\n' % ('path', 'cases', 'rel-L2', 'elem-ratio'))
+        f.writelines(row(k) for k in sorted(STATS) if k not in gf.FORM_LABELS)
+        if forms:
+            f.write('# tests/test_gpu_gemm_forms.py: the forms only the model reaches, same columns\n')
+            f.writelines(row(k) for k in forms)
+
+
 @pytest.fixture(scope='module', autouse=True)
 def _error_table():
     yield
-    out = os.environ.get('GEMM_PATHS_ERRORS_OUT')
-    if out and STATS:
-        with open(out, 'w') as f:
-            f.write('# tests/test_gpu_gemm_paths.py: per path label, cases run, worst rel-L2 against fp64 (bar 5e-6) and worst\n'
-                    '# |got - ref| / element bound (bar 1; tests/gemm_paths.py element_bound)\n')
-            f.write('%-18s %6s %12s %12s\n' % ('path', 'cases', 'rel-L2', 'elem-ratio'))
-            for k in sorted(STATS):
-                f.write('%-18s %6d %12.3e %12.3e\n' % (k, STATS[k][0], STATS[k][1], STATS[k][2]))
+    write_error_table()
 
 
 def judge(label, what, got, ref, n, S, g):
