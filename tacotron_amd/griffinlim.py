@@ -4,7 +4,8 @@
 log-magnitude frames in the r-frame layout -- and returns waveforms (B, 300 (F - 1)), F = (Td // 4) * 4 * r:
 de-normalise + inverse r-frame layout + exp + transpose in ONE HIP gather (taco_denorm_unframe), then Griffin-Lim
 (taco_griffinlim: hand-written 2048-point FFT, 50 rounds like the reference).  The reference draws the initial phase with
-np.random.rand; here it comes from a seeded torch generator so that a run can be reproduced.
+np.random.rand; here it comes from a seeded torch generator so that a run can be reproduced.  `vocode(...)` is the same call with
+its results by name (a `Vocoded`); `invert_spectrogram` flattens it into the reference-shaped return.
 
 With `lengths` (the per-row decoder steps `Tacotron.run(stop=rule)` leaves on the device) every row is vocoded over its own
 len_b r frames (taco_griffinlim_rows): the Griffin-Lim of that prompt alone, zeros behind it, and -- unless the caller gives
@@ -38,6 +39,7 @@ PCM16 row per prompt."""
 from __future__ import annotations
 
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -108,54 +110,79 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     waveform is the estimate's own: one synthesis pass, a draft voice.  'estimate' together with phase0 is a ValueError.  Return
     shapes do not change.
     Everything stays on the device.  F0 in Hz is SR / period."""
+    res = tuple(x for x in vocode(**locals()) if x is not None)   # (the first statement: locals() are the parameters)
+    return res[0] if len(res) == 1 else res
+
+
+class Vocoded(NamedTuple):
+    """what vocode() returns: invert_spectrogram's "waveform [, conv] [, frames_out] [, src] [, tracks]" by name; a field is None when
+    it was not asked for"""
+    waveform: torch.Tensor
+    conv: Optional[torch.Tensor] = None
+    frames_out: Optional[torch.Tensor] = None
+    src: Optional[torch.Tensor] = None
+    tracks: Optional[dict] = None
+
+
+def _f0_tracker(f0, out, r, lengths):
+    """`f0` of vocode() -> None, or (track, tracks): track(name, frames_t) measures the frames of one stage into the dict tracks --
+    tracks[name], tracks[name + '_stats'], with 'smooth' also name + '_raw' / '_counts', behind 'pitched' the paired 'pitch_stats' --
+    over the decoder steps `f0` names, or track('vocoder', stretched, frames_out) over the frames a stretch left.  The stage measured
+    last is the vocoder's: its entries are tracks['vocoder' ...] too.  Host tables go up once here, not once per track; ValueError"""
+    if f0 is None or f0 is False:
+        return None
+    opt = {} if f0 is True else dict(f0)
+    unknown = set(opt) - {'weight', 'gain', 'lag_min', 'lag_max', 'ratio', 'threshold', 'lengths', 'smooth'}
+    if unknown:
+        raise ValueError('invert_spectrogram: f0: unknown settings %s' % sorted(unknown))
+    smooth = opt.pop('smooth', None)
+    smooth = None if smooth is None or smooth is False else {} if smooth is True else dict(smooth)
+    unknown = set(smooth or ()) - {'bias', 'lg', 'candidates', 'threshold', 'jump_cost', 'switch_cost'}
+    if unknown:
+        raise ValueError('invert_spectrogram: f0: smooth: unknown settings %s' % sorted(unknown))
+    f0_lengths = opt.pop('lengths', lengths)
+    if not {'weight', 'gain', 'lag_min', 'lag_max'} & set(opt):   # (none given: the production tables at this bin count)
+        opt['weight'], opt['gain'], opt['lag_min'], opt['lag_max'] = lib.f0_tables(C=out.shape[2] // r)
+    if smooth is not None:   # (after the lags are known)
+        lags = {k: opt[k] for k in ('lag_min', 'lag_max') if k in opt}
+        if 'lg' not in smooth or 'bias' not in smooth:
+            bias, lg = lib.f0_viterbi_lag_tables(lags.get('lag_min', 40), lags.get('lag_max', 266))
+            smooth.setdefault('bias', bias)
+            smooth.setdefault('lg', lg)
+        smooth.setdefault('threshold', opt.get('threshold', lib.F0_THRESHOLD))
+        smooth.update(lags)
+    for d, k in ((opt, 'weight'), (opt, 'gain'), (smooth, 'bias'), (smooth, 'lg')):
+        if d and d.get(k) is not None and not (torch.is_tensor(d[k]) and d[k].device == out.device):
+            d[k] = torch.as_tensor(np.asarray(d[k], dtype=np.float32)).to(out.device)
+    tracks = {}
+
+    def track(name, frames_t, frames_out=None):
+        counts, per_unit = (f0_lengths, r if f0_lengths is not None else 1) if frames_out is None else (frames_out, 1)
+        if smooth is None:
+            tracks[name] = lib.frames_f0(frames_t, counts, per_unit, **opt)
+        else:
+            period, strength, acf = lib.frames_f0(frames_t, counts, per_unit, want_acf=True, **opt)
+            smoothed = lib.f0_viterbi(acf, counts, per_unit, **smooth)
+            tracks[name], tracks[name + '_raw'], tracks[name + '_counts'] = smoothed[:2], (period, strength), smoothed[2]
+        tracks[name + '_stats'] = lib.f0_stats(tracks[name][0], None, counts, per_unit)
+        if name == 'pitched':
+            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], counts, per_unit)
+        for k in ('', '_stats', '_raw', '_counts'):
+            if name + k in tracks:
+                tracks['vocoder' + k] = tracks[name + k]
+
+    return track, tracks
+
+
+def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
+           lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
+           rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None):
+    """invert_spectrogram with its result by name: the same parameters, documented there -> Vocoded"""
     if phase_init not in (None, 'random', 'estimate'):
         raise ValueError("invert_spectrogram: phase_init must be None, 'random' or 'estimate', got %r" % (phase_init,))
-    estimate = phase_init == 'estimate'
-    if estimate and phase0 is not None:
+    if phase_init == 'estimate' and phase0 is not None:
         raise ValueError("invert_spectrogram: phase_init='estimate' excludes phase0: give one of them")
-    track = None
-    if f0 is not None and f0 is not False:
-        opt = {} if f0 is True else dict(f0)
-        unknown = set(opt) - {'weight', 'gain', 'lag_min', 'lag_max', 'ratio', 'threshold', 'lengths', 'smooth'}
-        if unknown:
-            raise ValueError('invert_spectrogram: f0: unknown settings %s' % sorted(unknown))
-        smooth = opt.pop('smooth', None)
-        if smooth is not None and smooth is not False:
-            smooth = {} if smooth is True else dict(smooth)
-            unknown = set(smooth) - {'bias', 'lg', 'candidates', 'threshold', 'jump_cost', 'switch_cost'}
-            if unknown:
-                raise ValueError('invert_spectrogram: f0: smooth: unknown settings %s' % sorted(unknown))
-        else:
-            smooth = None
-        f0_lengths = opt.pop('lengths', lengths)
-        f0_unit = r if f0_lengths is not None else 1
-        if not {'weight', 'gain', 'lag_min', 'lag_max'} & set(opt):   # (none given: the production tables at this bin count)
-            opt['weight'], opt['gain'], opt['lag_min'], opt['lag_max'] = lib.f0_tables(C=out.shape[2] // r)
-        for k in ('weight', 'gain'):   # (host tables go up once, not once per track)
-            if opt.get(k) is not None and not (torch.is_tensor(opt[k]) and opt[k].device == out.device):
-                opt[k] = torch.as_tensor(np.asarray(opt[k], dtype=np.float32)).to(out.device)
-        if smooth is not None:   # (after the lags are known; host tables go up once)
-            lags = {k: opt[k] for k in ('lag_min', 'lag_max') if k in opt}
-            lag_min, lag_max = lags.get('lag_min', 40), lags.get('lag_max', 266)
-            if 'lg' not in smooth or 'bias' not in smooth:
-                bias, lg = lib.f0_viterbi_lag_tables(lag_min, lag_max)
-                smooth.setdefault('bias', bias)
-                smooth.setdefault('lg', lg)
-            for k in ('bias', 'lg'):
-                if smooth[k] is not None and not (torch.is_tensor(smooth[k]) and smooth[k].device == out.device):
-                    smooth[k] = torch.as_tensor(np.asarray(smooth[k], dtype=np.float32)).to(out.device)
-            smooth.setdefault('threshold', opt.get('threshold', lib.F0_THRESHOLD))
-            smooth.update(lags)
-        tracks = {}
-
-        def track(name, frames_t, counts, per_unit):
-            if smooth is None:
-                tracks[name] = lib.frames_f0(frames_t, counts, per_unit, **opt)
-            else:
-                period, strength, acf = lib.frames_f0(frames_t, counts, per_unit, want_acf=True, **opt)
-                smoothed = lib.f0_viterbi(acf, counts, per_unit, **smooth)
-                tracks[name], tracks[name + '_raw'], tracks[name + '_counts'] = smoothed[:2], (period, strength), smoothed[2]
-            tracks[name + '_stats'] = lib.f0_stats(tracks[name][0], None, counts, per_unit)
+    track, tracks = _f0_tracker(f0, out, r, lengths) or (None, None)
     if pitch is not None and pitch_curve is not None:
         raise ValueError('invert_spectrogram: pitch_curve excludes pitch: give one of them')
     if rate is not None and rate_curve is not None:
@@ -166,38 +193,26 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
         raise ValueError('invert_spectrogram: src needs rate_curve')
     if want_conv and momentum is None:
         raise ValueError('invert_spectrogram: want_conv needs momentum (0 for the plain rounds)')
-    dev = out.device
-    mean = torch.as_tensor(stft_mean, dtype=torch.float32, device=dev)
-    std = torch.as_tensor(stft_std, dtype=torch.float32, device=dev)
+    mean, std = (torch.as_tensor(x, dtype=torch.float32, device=out.device) for x in (stft_mean, stft_std))
     mag_t = lib.denorm_unframe(out.contiguous(), mean, std, r, want_spec=False, want_mag_t=True, mag_t=mag_t)   # (B, 1025, F)
-    per_unit = r if lengths is not None else 1
-    shifted = pitch is not None or pitch_curve is not None
-    if shifted:
-        if track:
-            track('model', mag_t, f0_lengths, f0_unit)
-        if pitch_curve is not None:
-            mag_t = lib.frames_pitch_curve(mag_t, lengths, pitch_curve, frames_per_unit=per_unit, lifter=lifter)
-        else:
-            mag_t = lib.frames_pitch(mag_t, lengths, lib.steps_of(pitch, lib.pitch_step), frames_per_unit=per_unit, lifter=lifter)
-        if track:
-            track('pitched', mag_t, f0_lengths, f0_unit)
-            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], f0_lengths, f0_unit)
-    elif track:
-        track('model', mag_t, f0_lengths, f0_unit)
+    # (mag_t, counts, per_unit): the frames the next stage is handed -- row b holds counts[b] * per_unit of them, all without counts.
+    # taco_griffinlim_fast / _rows are given r as the frames per unit of an unstretched matrix also without counts: gl_unit
+    counts, per_unit, gl_unit = lengths, r if lengths is not None else 1, r
     if track:
-        last = 'pitched' if shifted else 'model'
-        tracks['vocoder'], tracks['vocoder_stats'] = tracks[last], tracks[last + '_stats']
-        if smooth is not None:
-            tracks['vocoder_raw'], tracks['vocoder_counts'] = tracks[last + '_raw'], tracks[last + '_counts']
-    done = (lambda res: res) if not track else (lambda res: (tuple(res) if isinstance(res, tuple) else (res,)) + (tracks,))
+        track('model', mag_t)
+    if pitch_curve is not None:
+        mag_t = lib.frames_pitch_curve(mag_t, counts, pitch_curve, frames_per_unit=per_unit, lifter=lifter)
+    elif pitch is not None:
+        mag_t = lib.frames_pitch(mag_t, counts, lib.steps_of(pitch, lib.pitch_step), frames_per_unit=per_unit, lifter=lifter)
+    if track and (pitch is not None or pitch_curve is not None):
+        track('pitched', mag_t)
     if rate is not None or rate_curve is not None:
         F = mag_t.shape[2]
         if rate_curve is not None:
             Fo = max(5, lib.stretch_curve_capacity(F, lib.int_arg('invert_spectrogram', 'dur_q_max', dur_q_max, lib.STRETCH_MIN_STEP,
                                                                   lib.STRETCH_MAX_STEP)))
-            stretched, frames_out, src = lib.frames_stretch_curve(mag_t, lengths, rate_curve, frames_per_unit=per_unit, Fo=Fo,
-                                                                  frames_out=frames_out, src=src)
-            tail = (frames_out, src)
+            mag_t, frames_out, src = lib.frames_stretch_curve(mag_t, counts, rate_curve, frames_per_unit=per_unit, Fo=Fo,
+                                                              frames_out=frames_out, src=src)
         else:
             step_q = lib.steps_of(rate, lib.stretch_step)
             if torch.is_tensor(step_q):   # (on a device, never read: any rate down to the slowest)
@@ -205,31 +220,28 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
             else:
                 slowest = min(step_q, default=lib.STRETCH_ONE) if isinstance(step_q, list) else step_q
             Fo = max(5, lib.stretch_capacity(F, slowest))
-            stretched, frames_out = lib.frames_stretch(mag_t, lengths, step_q, frames_per_unit=per_unit, Fo=Fo, frames_out=frames_out)
-            tail = (frames_out,)
-        phase0 = None if phase0 is None else phase0.contiguous()
-        if track:   # (the stretched rows hold frames_out frames each, whatever `lengths` was)
-            track('vocoder', stretched, frames_out, 1)
-        if estimate:
-            phase0 = lib.phase_estimate(stretched, frames_out, 1)
-        if momentum is not None:
-            res = lib.griffinlim_fast(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, momentum=momentum,
-                                      frames_per_unit=1, want_conv=want_conv, out=wave, work=work)
-            return done(((res[0], res[1]) if want_conv else (res,)) + tail)
-        return done((lib.griffinlim_rows(stretched, frames_out, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=1, out=wave,
-                                         work=work),) + tail)
-    if estimate:   # (over the frames the vocoder runs on: every row's own with `lengths`, else all of them)
-        phase0 = lib.phase_estimate(mag_t, lengths, per_unit)
+            mag_t, frames_out = lib.frames_stretch(mag_t, counts, step_q, frames_per_unit=per_unit, Fo=Fo, frames_out=frames_out)
+        counts, per_unit, gl_unit = frames_out, 1, 1   # (the stretched rows hold frames_out frames each, whatever `lengths` was)
+        if track:
+            track('vocoder', mag_t, frames_out)
+    if phase0 is not None:
+        phase0 = phase0.contiguous()
+    if phase_init == 'estimate':   # (over the frames the vocoder runs on: every row's own with counts, else all of them)
+        phase0 = lib.phase_estimate(mag_t, counts, per_unit)
+    conv = None
     if momentum is not None:
-        return done(lib.griffinlim_fast(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
-                                        momentum=momentum, frames_per_unit=r, want_conv=want_conv, out=wave, work=work))
-    if lengths is not None:
-        return done(lib.griffinlim_rows(mag_t, lengths, phase0=None if phase0 is None else phase0.contiguous(), seed=seed, n_iter=n_iter,
-                                        frames_per_unit=r, out=wave, work=work))
-    if phase0 is None:
-        g = torch.Generator(device='cpu').manual_seed(seed)
-        phase0 = (2.0 * math.pi * torch.rand(mag_t.shape, generator=g)).to(dev)
-    return done(lib.griffinlim(mag_t, phase0.contiguous(), n_iter, out=wave, work=work))
+        waveform = lib.griffinlim_fast(mag_t, counts, phase0=phase0, seed=seed, n_iter=n_iter, momentum=momentum, frames_per_unit=gl_unit,
+                                       want_conv=want_conv, out=wave, work=work)
+        if want_conv:
+            waveform, conv = waveform
+    elif counts is not None:
+        waveform = lib.griffinlim_rows(mag_t, counts, phase0=phase0, seed=seed, n_iter=n_iter, frames_per_unit=gl_unit, out=wave, work=work)
+    else:
+        if phase0 is None:
+            g = torch.Generator(device='cpu').manual_seed(seed)
+            phase0 = (2.0 * math.pi * torch.rand(mag_t.shape, generator=g)).to(out.device)
+        waveform = lib.griffinlim(mag_t, phase0, n_iter, out=wave, work=work)
+    return Vocoded(waveform, conv, frames_out, src, tracks)
 
 
 def finish_samples(lengths, r, L):

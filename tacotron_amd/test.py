@@ -99,10 +99,13 @@ and after, the true peak and how much was limited.  With --long the JOINED promp
 from __future__ import annotations
 
 import argparse
+import collections
+import dataclasses
 import os
 import pickle as pkl
 import sys
 import wave
+from typing import Any
 
 import numpy as np
 import torch
@@ -110,7 +113,7 @@ import torch
 from .config import Config
 from .alignment import attention_png, encoded_chars, flags, path_line, scores_row, word_times, word_values, words_tsv
 from .data import KIND_NAMES, load_prompts, split_prompt
-from .griffinlim import finish_waveform, invert_spectrogram, join_gaps, join_samples, join_waveform, level_waveform, limit_settings
+from .griffinlim import finish_waveform, join_gaps, join_samples, join_waveform, level_waveform, limit_settings, vocode
 from .model import Tacotron
 from .params import ParamBuffer
 from . import lib
@@ -333,75 +336,124 @@ def level_finished(fin, level, **rows):
                                                      tp_out.cpu().numpy(), I_in.cpu().numpy())])
 
 
-def check_options(n_iter=50, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, rate=None,
-                  vocode=True, pitch=None, lifter=32, f0=None, f0_smooth=None, prosody=None, gl_init=None, loudness=None, peak_db=None,
-                  limit=False, limit_ms=None, true_peak=None, limit_passes=None, path_jump=None):
-    """The option ranges of test() and of the command line (`stop`: a rule, or True / None for given / not given; `path_jump`: None
-    without --timings; `f0_smooth`: None / False, True or the number of candidates; `prosody`: None / False or anything else for
-    given; `gl_init`: None, 'random' or 'estimate'; `peak_db`: None for not given; `limit`: True / False, `limit_ms`, `true_peak`,
-    `limit_passes`: None for not given); ValueError."""
-    if loudness is not None:
-        if not vocode:
-            raise ValueError('loudness (--loudness) levels the waveform: it needs vocode')
-        if not -70.0 <= float(loudness) <= 0.0:   # (NaN fails)
-            raise ValueError('loudness (--loudness) must be in [-70, 0] LUFS, got %r' % (loudness,))
-    if peak_db is not None:
-        if loudness is None:
-            raise ValueError('peak_db (--peak-db) is the ceiling of loudness (--loudness): it needs loudness')
-        if not float(peak_db) <= 0.0 or np.isinf(float(peak_db)):
-            raise ValueError('peak_db (--peak-db) must be a finite number of decibels <= 0, got %r' % (peak_db,))
-    if not isinstance(limit, bool):
-        raise ValueError('limit (--limit) must be True or False, got %r' % (limit,))
-    if limit and loudness is None:
-        raise ValueError('limit (--limit) holds the true peak of loudness (--loudness) at its ceiling: it needs loudness')
-    for name, v in (('limit_ms (--limit-ms)', limit_ms), ('true_peak (--true-peak)', true_peak), ('limit_passes (--limit-passes)', limit_passes)):
-        if v is not None and not limit:
-            raise ValueError('%s is a setting of limit (--limit): it needs limit' % name)
-    if limit:
-        limit_options(limit_ms, true_peak, limit_passes)
-    if gl_init not in (None, 'random', 'estimate'):
-        raise ValueError("gl_init (--gl-init) must be 'random' or 'estimate', got %r" % (gl_init,))
-    if gl_init == 'estimate' and not vocode:
-        raise ValueError('gl_init (--gl-init) estimates the phases Griffin-Lim starts from: it needs vocode')
-    if prosody is not None and prosody is not False:
-        if not vocode:
-            raise ValueError('prosody (--prosody) shapes the magnitudes in front of Griffin-Lim: it needs vocode')
-        if not stop:
-            raise ValueError('prosody (--prosody) needs a stop rule (--stop): the curves follow the path over each prompt\'s own steps')
-        if long_options(long) is not None:
-            raise ValueError('prosody (--prosody) cannot be combined with long (--long): the pieces re-index the words of a prompt')
-    if f0_smooth is not None and f0_smooth is not False:
-        if f0 is None or f0 is False:
-            raise ValueError('f0_smooth (--f0-smooth) smooths the track of f0 (--f0): it needs f0')
-        if f0_smooth is not True:
-            lib.int_arg('check_options', 'f0_smooth (--f0-candidates)', f0_smooth, 1, lib.F0_MAX_CAND)
-    if path_jump is not None:
-        lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
-    if f0 is not None and f0 is not False:
-        if not vocode:
-            raise ValueError('f0 (--f0) measures the magnitudes in front of Griffin-Lim: it needs vocode')
-        f0_range(f0)
-    if pitch is not None:
-        if not vocode:
-            raise ValueError('pitch (--pitch) shifts the magnitudes in front of Griffin-Lim: it needs vocode')
-        pitch_steps(pitch, None)
-        lib.int_arg('check_options', 'lifter (--lifter)', lifter, 1, lib.PITCH_MAX_LIFTER)
-    if rate is not None:
-        if not vocode:
-            raise ValueError('rate (--rate) stretches the magnitudes in front of Griffin-Lim: it needs vocode')
-        rate_steps(rate, None)
-    if long_options(long) is not None and not stop:
-        raise ValueError('long (--long) needs a stop rule (--stop): without one every piece carries max_decode_iter steps')
-    if vocode_lengths and not stop:
-        raise ValueError('vocode_lengths (--vocode-lengths) needs a stop rule (--stop): the lengths come from taco_infer_stop')
-    if gl_momentum is not None and not 0.0 <= float(gl_momentum) < 1.0:
-        raise ValueError('gl_momentum (--gl-momentum) must be in [0, 1), got %r' % (gl_momentum,))
-    if int(n_iter) < 0:
-        raise ValueError('n_iter (--gl-iters) must be >= 0, got %r' % (n_iter,))
-    if deemphasis is not None and not 0.0 <= float(deemphasis) < 1.0:
-        raise ValueError('deemphasis (--deemphasis) must be in [0, 1), got %r' % (deemphasis,))
-    if trim_db is not None and not float(trim_db) > 0.0:
-        raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (trim_db,))
+def given(option):
+    """whether an option whose None / False mean "off" is set"""
+    return option is not None and option is not False
+
+
+_OptionFields = dataclasses.make_dataclass('_OptionFields', frozen=True, fields=[(name, Any, default) for name, default in dict(
+    n_iter=50, vocode=True, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None, align_scores=False,
+    rate=None, pitch=None, lifter=32, f0=None, timings=False, path_jump=lib.PATH_JUMP, f0_smooth=None, prosody=None, gl_init=None,
+    loudness=None, peak_db=None, limit=False, limit_ms=None, true_peak=None, limit_passes=None).items()])
+
+
+class Options(_OptionFields):
+    """The synthesis options of test(), a frozen record with test()'s names and defaults (the fields above); test() documents them.
+    check() holds their ranges, resolved() what a run reads.  As the command line and check_options() see them: `stop` a rule, or
+    True / None for given / not given; `prosody` None / False or anything else for given."""
+
+    def check(self):
+        """The option ranges of test() and of the command line (`path_jump` is held to its range with `timings`; `f0_smooth`: None /
+        False, True or the number of candidates; `gl_init`: None, 'random' or 'estimate'; `peak_db`, `limit_ms`, `true_peak`,
+        `limit_passes`: None for not given); ValueError."""
+        o = self
+        if o.loudness is not None:
+            if not o.vocode:
+                raise ValueError('loudness (--loudness) levels the waveform: it needs vocode')
+            if not -70.0 <= float(o.loudness) <= 0.0:   # (NaN fails)
+                raise ValueError('loudness (--loudness) must be in [-70, 0] LUFS, got %r' % (o.loudness,))
+        if o.peak_db is not None:
+            if o.loudness is None:
+                raise ValueError('peak_db (--peak-db) is the ceiling of loudness (--loudness): it needs loudness')
+            if not float(o.peak_db) <= 0.0 or np.isinf(float(o.peak_db)):
+                raise ValueError('peak_db (--peak-db) must be a finite number of decibels <= 0, got %r' % (o.peak_db,))
+        if not isinstance(o.limit, bool):
+            raise ValueError('limit (--limit) must be True or False, got %r' % (o.limit,))
+        if o.limit and o.loudness is None:
+            raise ValueError('limit (--limit) holds the true peak of loudness (--loudness) at its ceiling: it needs loudness')
+        for name, v in (('limit_ms (--limit-ms)', o.limit_ms), ('true_peak (--true-peak)', o.true_peak),
+                        ('limit_passes (--limit-passes)', o.limit_passes)):
+            if v is not None and not o.limit:
+                raise ValueError('%s is a setting of limit (--limit): it needs limit' % name)
+        if o.limit:
+            limit_options(o.limit_ms, o.true_peak, o.limit_passes)
+        if o.gl_init not in (None, 'random', 'estimate'):
+            raise ValueError("gl_init (--gl-init) must be 'random' or 'estimate', got %r" % (o.gl_init,))
+        if o.gl_init == 'estimate' and not o.vocode:
+            raise ValueError('gl_init (--gl-init) estimates the phases Griffin-Lim starts from: it needs vocode')
+        if given(o.prosody):
+            if not o.vocode:
+                raise ValueError('prosody (--prosody) shapes the magnitudes in front of Griffin-Lim: it needs vocode')
+            if not o.stop:
+                raise ValueError('prosody (--prosody) needs a stop rule (--stop): the curves follow the path over each prompt\'s own steps')
+            if long_options(o.long) is not None:
+                raise ValueError('prosody (--prosody) cannot be combined with long (--long): the pieces re-index the words of a prompt')
+        if given(o.f0_smooth):
+            if not given(o.f0):
+                raise ValueError('f0_smooth (--f0-smooth) smooths the track of f0 (--f0): it needs f0')
+            if o.f0_smooth is not True:
+                lib.int_arg('check_options', 'f0_smooth (--f0-candidates)', o.f0_smooth, 1, lib.F0_MAX_CAND)
+        if o.timings:
+            lib.int_arg('check_options', 'path_jump (--path-jump)', o.path_jump, 1, lib.PATH_MAX_JUMP)
+        if given(o.f0):
+            if not o.vocode:
+                raise ValueError('f0 (--f0) measures the magnitudes in front of Griffin-Lim: it needs vocode')
+            f0_range(o.f0)
+        if o.pitch is not None:
+            if not o.vocode:
+                raise ValueError('pitch (--pitch) shifts the magnitudes in front of Griffin-Lim: it needs vocode')
+            pitch_steps(o.pitch, None)
+            lib.int_arg('check_options', 'lifter (--lifter)', o.lifter, 1, lib.PITCH_MAX_LIFTER)
+        if o.rate is not None:
+            if not o.vocode:
+                raise ValueError('rate (--rate) stretches the magnitudes in front of Griffin-Lim: it needs vocode')
+            rate_steps(o.rate, None)
+        if long_options(o.long) is not None and not o.stop:
+            raise ValueError('long (--long) needs a stop rule (--stop): without one every piece carries max_decode_iter steps')
+        if o.vocode_lengths and not o.stop:
+            raise ValueError('vocode_lengths (--vocode-lengths) needs a stop rule (--stop): the lengths come from taco_infer_stop')
+        if o.gl_momentum is not None and not 0.0 <= float(o.gl_momentum) < 1.0:
+            raise ValueError('gl_momentum (--gl-momentum) must be in [0, 1), got %r' % (o.gl_momentum,))
+        if int(o.n_iter) < 0:
+            raise ValueError('n_iter (--gl-iters) must be >= 0, got %r' % (o.n_iter,))
+        if o.deemphasis is not None and not 0.0 <= float(o.deemphasis) < 1.0:
+            raise ValueError('deemphasis (--deemphasis) must be in [0, 1), got %r' % (o.deemphasis,))
+        if o.trim_db is not None and not float(o.trim_db) > 0.0:
+            raise ValueError('trim_db (--trim-db) must be > 0, got %r' % (o.trim_db,))
+        if long_options(o.long) is not None and not o.vocode:
+            raise ValueError('long (--long) joins waveforms: it needs vocode')
+
+    def resolved(self):
+        """check(), then the options as a run reads them, a Resolved: `gl_init` None for 'random', `f0` None or (lo, hi), `f0_smooth`
+        None or the number of candidates, `long` None or (pause_ms, fade_ms), `prosody` None when not given -- given, it holds
+        `path_jump` to its range as `timings` does; ValueError"""
+        self.check()
+        level = None if self.loudness is None else dict(target=float(self.loudness),
+                                                        ceiling_db=PEAK_DB if self.peak_db is None else float(self.peak_db))
+        if self.limit:
+            level.update(limit_options(self.limit_ms, self.true_peak, self.limit_passes))
+        if given(self.prosody):
+            lib.int_arg('check_options', 'path_jump (--path-jump)', self.path_jump, 1, lib.PATH_MAX_JUMP)
+        smooth = (lib.F0_CANDIDATES if self.f0_smooth is True else int(self.f0_smooth)) if given(self.f0_smooth) else None
+        f0, long = f0_range(self.f0), long_options(self.long)
+        return Resolved(**dict(vars(self), gl_init=None if self.gl_init == 'random' else self.gl_init, f0=f0, f0_smooth=smooth, long=long,
+                               prosody=self.prosody if given(self.prosody) else None), level=level,
+                        finish=self.deemphasis is not None or self.trim_db is not None or long is not None or level is not None)
+
+
+@dataclasses.dataclass(frozen=True)
+class Resolved(Options):
+    """Options.resolved(): the options in the form a run reads, and what follows from them.  level: None, or level_waveform's target,
+    ceiling_db and, with `limit`, limiter keywords; finish: whether the waveform is finished on the device"""
+    level: Any = None
+    finish: bool = False
+
+
+def check_options(*, n_iter=50, vocode=True, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None,
+                  align_scores=False, rate=None, pitch=None, lifter=32, f0=None, timings=False, f0_smooth=None, prosody=None, gl_init=None,
+                  loudness=None, peak_db=None, limit=False, limit_ms=None, true_peak=None, limit_passes=None, path_jump=None):
+    """Options.check() for keywords (`path_jump`: None without --timings; given, it is held to its range); ValueError."""
+    Options(**dict(locals(), timings=timings or path_jump is not None)).check()
 
 
 def limit_options(limit_ms=None, true_peak=None, limit_passes=None):
@@ -505,22 +557,22 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     alignment.flags marks is named in one WARNING line.  Nothing else changes.
     `rate` (needs `vocode`): None, a speaking rate in [0.25, 4] (1.0: the model's own) or a sequence with one rate per prompt; with
     `long`, a prompt's pieces inherit its rate.  The magnitudes of every row are stretched on the device in front of Griffin-Lim
-    (invert_spectrogram(rate=...)): over the row's own len_b r frames with `stop` (whether or not `vocode_lengths` is set; the phases
+    (vocode(rate=...)): over the row's own len_b r frames with `stop` (whether or not `vocode_lengths` is set; the phases
     are then drawn on the device), else over all frames.  prompt_NNN.wav holds 300 (Fo_b - 1) samples, Fo_b = lib.stretch_frames of
     those frames -- cut on the host by that formula, or with finishing on the device from the stretch's own frames_out -- and
     prompt_NNN_rate.npy (step_q, Fo_b) as int32.  Every other file is the model's own output, unstretched; without `rate` every file
     is what it was.
     `pitch` (needs `vocode`) / `lifter`: None, a pitch shift in semitones in [-12, 12] (0: the model's own) or a sequence with one per
     prompt; with `long`, a prompt's pieces inherit its pitch.  The harmonics of every magnitude frame the vocoder is given are moved
-    under the frame's own envelope of `lifter` quefrencies (invert_spectrogram(pitch=...), in front of the stretch of `rate`): over the
+    under the frame's own envelope of `lifter` quefrencies (vocode(pitch=...), in front of the stretch of `rate`): over the
     row's own len_b r frames wherever the vocoder gets the lengths, else over all frames.  prompt_NNN_pitch.npy holds (step_q, lifter)
     as int32; no file changes its size, the model's own files stay what they are, and pitch 0 gives the audio of pitch None.
-    `f0` (needs `vocode`): None, True (60 .. 400 Hz) or (lo, hi) in Hz: invert_spectrogram(f0=...) tracks the pitch of the frames on the
+    `f0` (needs `vocode`): None, True (60 .. 400 Hz) or (lo, hi) in Hz: vocode(f0=...) tracks the pitch of the frames on the
     device, over the row's own len_b r frames with `stop`; prompt_NNN_f0.npy holds (period, strength) of the frames the vocoder was
     given, and f0_lines() prints what `pitch` or `rate` did to it.  Untuned, and meaningless on an untrained model; nothing else
     changes.
     `f0_smooth` (needs `f0`): None, True (lib.F0_CANDIDATES candidates per frame) or their number in 1 .. 15: the tracks are smoothed
-    across frames on the device (invert_spectrogram(f0={'smooth': ...}), lib.f0_viterbi with lib.f0_viterbi_tables' UNTUNED bias and
+    across frames on the device (vocode(f0={'smooth': ...}), lib.f0_viterbi with lib.f0_viterbi_tables' UNTUNED bias and
     costs for the range of `f0`); _f0.npy and f0_lines() use the smoothed track and the line names the frames the smoothing moved.
     `timings` / `path_jump`: every batch's best monotone attention paths are found on the device (Tacotron.alignment_path with
     max_jump = path_jump: over model.lengths with `stop`, else all steps); each prompt -- with `long`, each piece -- additionally
@@ -529,13 +581,13 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     `prosody` (needs `stop` and `vocode`, excludes `long`): None, or the rows of parse_prosody -- (prompt, word, rate | None,
     semitones | None) -- rate and pitch per word; words not listed take `rate` / `pitch`, or stay neutral.  Per batch, all on the
     device: the path (Tacotron.alignment_path, max_jump = path_jump), two lib.path_curve gathers of the per-character dur_q / step_q
-    into per-frame curves, then invert_spectrogram(rate_curve=..., pitch_curve=...) over each row's own len_b r frames (the pitch curve
+    into per-frame curves, then vocode(rate_curve=..., pitch_curve=...) over each row's own len_b r frames (the pitch curve
     only when a pitch is asked for anywhere).  prompt_NNN.wav holds 300 (Fo_b - 1) samples, Fo_b the stretch's frames_out (with finishing
     the row ends there on the device); prompt_NNN_prosody.npy the per-character (dur_q, step_q); _rate.npy / _pitch.npy are not written.
     With `timings` the word rows go through the stretch's time map (alignment.word_times(src=...)); with `f0` the line is the drift
     line without a figure asked for.
     `gl_init` (needs `vocode` for 'estimate'): None or 'random' -- every file is what it was -- or 'estimate': Griffin-Lim starts from
-    phases read off the magnitudes it is handed (invert_spectrogram(phase_init='estimate'), lib.phase_estimate), on whichever path the
+    phases read off the magnitudes it is handed (vocode(phase_init='estimate'), lib.phase_estimate), on whichever path the
     other options choose; with n_iter = 0 the waveform is the estimate's own synthesis pass.  No file changes its size.
     `loudness` (needs `vocode`) / `peak_db`: None, or the target in LUFS in [-70, 0] and the ceiling on the sample peak in decibels
     <= 0 (None: -1).  The waveform is finished on the device as with `long` (without `deemphasis` / `trim_db`: bounds [0, n_b)) and
@@ -548,252 +600,256 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     and nobody has listened to a limited file.  prompt_NNN.wav holds the limited int16 samples, prompt_NNN_limit.npy (tp_in, G, g_min, peak_out, n_b,
     n_limited, I_reached, tp_out) as float64 (no _loud.npy), and limit_line() is printed per prompt.  Without it lib.wave_limit is
     never reached."""
-    check_options(n_iter, stop, vocode_lengths, gl_momentum, deemphasis, trim_db, long, rate, vocode, pitch, lifter, f0,
-                  f0_smooth=f0_smooth, path_jump=path_jump if timings else None, prosody=prosody, gl_init=gl_init, loudness=loudness,
-                  peak_db=peak_db, limit=limit, limit_ms=limit_ms, true_peak=true_peak, limit_passes=limit_passes)
-    level = None if loudness is None else dict(target=float(loudness), ceiling_db=PEAK_DB if peak_db is None else float(peak_db))
-    if limit:
-        level.update(limit_options(limit_ms, true_peak, limit_passes))
-    gl_init = None if gl_init == 'random' else gl_init
-    if prosody is not None and prosody is not False:
-        lib.int_arg('check_options', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
-    else:
-        prosody = None
-    f0_smooth = None if f0_smooth is None or f0_smooth is False else (lib.F0_CANDIDATES if f0_smooth is True else int(f0_smooth))
-    f0 = f0_range(f0)
-    f0_opt = None   # the tables on the device, made at the first batch
-    steps = rate_steps(rate, len(prompts))
-    row_pitch = pitch_steps(pitch, len(prompts))
-    long = long_options(long)
-    if long is not None and not vocode:
-        raise ValueError('long (--long) joins waveforms: it needs vocode')
-    finish = deemphasis is not None or trim_db is not None or long is not None or level is not None
-    meta_path = os.path.join(config.data_path, 'meta.pkl')
-    if os.path.exists(meta_path):
-        with open(meta_path, 'rb') as f:
-            ivocab = pkl.load(f)['vocab']
-    else:
-        ivocab = {i + 1: ch for i, ch in enumerate("abcdefghijklmnopqrstuvwxyz '.,?!-")}
-        ivocab[0] = '<pad>'
-    config.vocab_size = len(ivocab)
-    ckpt = torch.load(checkpoint) if checkpoint else None
-    if ckpt is not None:
-        config.r, config.vocab_size = ckpt.get('shape', (config.r, config.vocab_size))
-        config.num_speakers = int(ckpt.get('num_speakers', 1))
-    pros = None   # per prompt: (L, 2) int32 (dur_q, step_q) per encoded character
-    if prosody is not None:   # the curves carry --rate and --pitch as the value of every character no row of the table names
-        pros = prosody_table(prosody, prompts, ivocab, _steps('rate', rate, lib.stretch_dur, len(prompts)), row_pitch)
-        pros_pitch = row_pitch is not None or any(sem is not None for _, _, _, sem in prosody)
-        pros_max = max([lib.STRETCH_ONE] + [int(t[:, 0].max()) for t in pros if len(t)])
-        steps = row_pitch = None
-    state = {'params': None}
-    models = {}   # batch size -> Tacotron
-    os.makedirs(out_dir, exist_ok=True)
-
-    def synthesise(batch, n, out_rows=None, bounds_rows=None):
-        """one batch whose first row has index n -> (spec, align, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved, louds),
-        host arrays or None.  louds (`loudness` without `long`): the batch's loud_rows (B, 8); pcm then is the levelled one.  curved (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve.  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.
-        out_rows / bounds_rows (`long`): the finished fp32 samples and their bounds go to these device rows and no PCM16 is made.
-        f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
-        lib.f0_viterbi counts (B, 4))"""
-        nonlocal f0_opt
-        Bn = batch['text'].shape[0]
-        if config.num_speakers > 1:
-            batch['speaker'] = torch.full((Bn,), int(speaker), dtype=torch.int32)
-        if state['params'] is None:
-            shape = lib.make_shape(Bn, batch['text'].shape[1], config.max_decode_iter, config.r, config.vocab_size,
-                                   config.num_speakers)
-            state['params'] = ParamBuffer(shape, 'cuda').init_(0)
-        model = models.get(Bn)
-        if model is None:
-            model = models[Bn] = Tacotron(config, batch, train=False, params=state['params'])
-            if ckpt is not None:
-                model.load_state_dict(ckpt)
-        else:
-            model.set_inputs(batch)
-        out, al = model.run(stop=stop)
-        scores = model.alignment_scores() if align_scores else None   # (enqueued behind the decode; read with the other results below)
-        found = model.alignment_path(path_jump) if timings or pros is not None else None   # (likewise; the path stays on the device)
-        paths = found[1:] if timings else None
-        model.check()
-        mean = model.stft_mean if model.stft_mean is not None else torch.zeros(config.fft_size * config.r)
-        std = model.stft_std if model.stft_std is not None else torch.ones(config.fft_size * config.r)
-        mean = torch.as_tensor(mean, dtype=torch.float32).cuda()
-        std = torch.as_tensor(std, dtype=torch.float32).cuda()
-        spec = lib.denorm_unframe(out, mean, std, config.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = conv = pcm = trim = f0res = curved = louds = None
-        level_rows = level is not None and out_rows is None   # (`long` levels the joined prompts instead)
-        if vocode:
-            fout = None
-            shift = {}
-            if row_pitch is not None:   # (step_q as the device takes it: no way back through semitones)
-                shift = dict(pitch=torch.tensor(row_pitch[n:n + Bn], dtype=torch.int32).cuda(), lifter=lifter)
-            if f0 is not None:
-                if f0_opt is None:
-                    w, g, lag_min, lag_max = lib.f0_tables(SR, f0[0], f0[1])
-                    f0_opt = dict(weight=torch.from_numpy(w).cuda(), gain=torch.from_numpy(g).cuda(), lag_min=lag_min, lag_max=lag_max)
-                    if f0_smooth is not None:
-                        bias, lg, jump, switch = lib.f0_viterbi_tables(SR, f0[0], f0[1])
-                        f0_opt['smooth'] = dict(bias=torch.from_numpy(bias).cuda(), lg=torch.from_numpy(lg).cuda(), candidates=f0_smooth,
-                                                jump_cost=jump, switch_cost=switch)
-                shift['f0'] = dict(f0_opt, lengths=model.lengths if stop is not None else None)
-            if pros is not None:
-                Tt, Fm = batch['text'].shape[1], (out.shape[1] // 4) * 4 * config.r
-                values = np.empty((2, Bn, Tt), dtype=np.int32)
-                values[0], values[1] = lib.STRETCH_ONE, lib.PITCH_ONE
-                for i in range(Bn):
-                    table = pros[n + i][:Tt]
-                    values[:, i, :len(table)] = table.T
-                values = torch.from_numpy(values).cuda()
-                curves = [lib.path_curve(found[0], values[k], config.r, one)[:, :Fm].contiguous()
-                          for k, one in ((0, lib.STRETCH_ONE), (1, lib.PITCH_ONE)) if k == 0 or pros_pitch]
-                res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, phase_init=gl_init, lengths=model.lengths, rate_curve=curves[0],
-                                         pitch_curve=curves[1] if pros_pitch else None, lifter=lifter, dur_q_max=pros_max, **shift)
-            elif steps is None:
-                res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, phase_init=gl_init, lengths=model.lengths if vocode_lengths else None, **shift)
-            else:   # (the rows' own frames whenever there is a rule: the host's Fo_b and the device's frames_out are then one number)
-                res = invert_spectrogram(out, mean, std, config.r, n_iter=n_iter, seed=n, momentum=gl_momentum,
-                                         want_conv=gl_momentum is not None, phase_init=gl_init, lengths=model.lengths if stop is not None else None,
-                                         rate=[q / 65536.0 for q in row_steps[n:n + Bn]], **shift)
-            res = list(res) if isinstance(res, tuple) else [res]   # waveform [, conv] [, frames_out] [, tracks]
-            if f0 is not None:
-                tracks = res.pop()
-                f0res = (torch.stack(tracks['vocoder'], dim=2).cpu().numpy(), tracks['model_stats'].cpu().numpy(),
-                         tracks['vocoder_stats'].cpu().numpy(), tracks['pitch_stats'].cpu().numpy() if 'pitch_stats' in tracks else None)
-                if f0_smooth is not None:
-                    f0res += (tracks['vocoder_counts'].cpu().numpy(),)
-            if pros is not None:
-                src = res.pop()
-            if steps is not None or pros is not None:
-                fout = res.pop()
-            if pros is not None:
-                curved = (fout.cpu().numpy(), src.cpu().numpy())
-            wav = res[0] if gl_momentum is None else res
-            if gl_momentum is not None:
-                wav, conv = wav[0], wav[1].cpu().numpy()
-                print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
-                      % (gl_momentum, n_iter, float(conv[:, -1].max())))
-            if finish and fout is not None:   # (a rate: the row ends where the stretch says; `long`: the rows are wider than this batch's)
-                fin, pcm, trim, _ = finish_waveform(wav, fout, 1, deemphasis=0.0 if deemphasis is None else deemphasis,
-                                                    trim_top_db=0.0 if trim_db is None else trim_db,
-                                                    want_out=out_rows is not None or level_rows,
-                                                    want_pcm=out_rows is None and not level_rows, bounds=bounds_rows)
-                if out_rows is not None:
-                    out_rows[:, :fin.shape[1]].copy_(fin)
-            elif finish:   # (the fp32 waveform stays on the device)
-                fin, pcm, trim, _ = finish_waveform(wav, model.lengths if stop is not None else None, config.r,
-                                                    deemphasis=0.0 if deemphasis is None else deemphasis,
-                                                    trim_top_db=0.0 if trim_db is None else trim_db,
-                                                    want_out=out_rows is not None or level_rows,
-                                                    want_pcm=out_rows is None and not level_rows, out=out_rows, bounds=bounds_rows)
-            else:
-                wav = wav.cpu().numpy()
-            if finish:
-                if level_rows:   # (the finished fp32 rows stay on the device; their PCM16 is the levelled one)
-                    pcm, louds = level_finished(fin, level, bounds=trim)
-                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
-        lengths = model.lengths.cpu().numpy() if stop is not None else None
-        if scores is not None:
-            scores = np.stack([scores_row(c, m) for c, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
-        if paths is not None:
-            paths = tuple(x.cpu().numpy() for x in paths)
-        return spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, lengths, scores, f0res, paths, curved, louds
-
-    def marks(score, L):
-        """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
-        return flags(score[:6], score[6:], L, end_offset=stop.end_offset if stop is not None else 1)
-
-    F = (config.max_decode_iter // 4) * 4 * config.r   # frames per row of the model's output
-
-    def rate_of(row, len_b):
-        """(step_q, Fo_b) of global row `row`, or None without a rate"""
-        if steps is None:
-            return None
-        return row_steps[row], lib.stretch_frames(F if len_b is None else min(int(len_b) * config.r, F), row_steps[row])
-
-    def pitch_of(row):
-        """(step_q, lifter) of global row `row`, or None without a pitch"""
-        return None if row_pitch is None else (row_pitch[row], int(lifter))
-
-    def f0_of(row, i, len_b, f0res, who, curved=None):
-        """the _f0.npy rows of row i of a batch (global row `row`), cut to the frames the vocoder was given; prints the row's line"""
-        if f0res is None:
-            return None
-        stretched = rate_of(row, len_b)
-        frames = stretched[1] if stretched is not None else (F if len_b is None else min(int(len_b) * config.r, F))
-        if curved is not None:
-            frames = int(curved[0][i])
-        for line in f0_lines(who, [None if a is None else a[i] for a in f0res[1:]], None if row_pitch is None else row_pitch[row],
-                             None if steps is None else row_steps[row], curved is not None):
-            print(line)
-        return f0res[0][i, :frames]
-
-    def timing_of(row, i, len_b, trim, paths, text_len, line, who, offset=0, curved=None):
-        """(_dur.npy of row i of a batch (global row `row`), its word rows in the file it goes to) with `timings`, else (None, None);
-        prints the row's line.  trim: the row's [s, e] when the waveform was finished; offset: of the piece in a joined file; curved
-        (`prosody`): the batch's (frames_out, src) -- the word boundaries then go through the row's time map"""
-        if paths is None:
-            return None, None
-        dur, counts, mass = (a[i] for a in paths)
-        print(path_line(who, counts, mass, text_len, stop.end_offset if stop is not None else 1)[0])
-        stretched = rate_of(row, len_b)
-        frames = stretched[1] if stretched is not None else (F if len_b is None else min(int(len_b) * config.r, F))
-        if curved is not None:
-            frames = int(curved[0][i])
-            return dur[:text_len], word_times(line, ivocab, dur[:text_len], config.r, None, trim, offset, 300 * max(0, frames - 1), SR,
-                                              src=curved[1][i, :frames])
-        words = word_times(line, ivocab, dur[:text_len], config.r, None if steps is None else row_steps[row], trim, offset,
-                           300 * max(0, frames - 1), SR)
-        return dur[:text_len], words
-
-    def write_words(n, words):
-        with open(os.path.join(out_dir, 'prompt_%03d_words.tsv' % n), 'w') as f:
-            f.write(words_tsv(words))
-
-    n = 0
-    row_steps = steps
-    if long is not None:
-        if row_pitch is not None:
-            row_pitch = [row_pitch[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
-        L = None
-        if steps is not None:   # a piece has its prompt's rate; every row of the joined buffer holds the slowest one's samples
-            row_steps = [steps[p] for p, line in enumerate(prompts) for _ in split_prompt(line)]
-            L = 300 * (max(5, lib.stretch_capacity(F, min(row_steps, default=lib.STRETCH_ONE))) - 1)
-        n = _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L, rate_of, pitch_of, f0_of,
-                       timing_of if timings else None, write_words, level)
-        print('wrote %d samples to %s' % (n, out_dir))
-        return n
-    for batch in load_prompts(prompts, ivocab):
-        Bn = batch['text'].shape[0]
-        spec, al, wav, conv, pcm, trim, lengths, scores, f0res, paths, curved, louds = synthesise(batch, n)
-        for i in range(Bn):
-            wi, len_b, pi, ti, ci, si, li = (None if a is None else a[i] for a in (wav, lengths, pcm, trim, conv, scores, louds))
-            dur, words = timing_of(n, i, len_b, ti, paths, int(batch['text_length'][i]), prompts[n], 'prompt %d' % n, curved=curved)
-            write_prompt(out_dir, n, config.r, spec[i], al[i], wi, None if len_b is None else int(len_b), pi, ti, ci, ascore=si,
-                         rate=rate_of(n, len_b), pitch=pitch_of(n), f0=f0_of(n, i, len_b, f0res, 'prompt %d' % n, curved), dur=dur,
-                         prosody=None if curved is None else (pros[n], int(curved[0][i])), loud=li)
-            if li is not None:
-                print(level_line('prompt %d' % n, li, level))
-            if words is not None:
-                write_words(n, words)
-            found = marks(si, int(batch['text_length'][i])) if si is not None else []
-            if found:
-                print('WARNING prompt %d: %s' % (n, ', '.join(found)))
-            n += 1
+    opt = Options(**{k: v for k, v in locals().items() if k in Options.__dataclass_fields__}).resolved()   # (locals(): the parameters)
+    run = Run(config, opt, prompts, out_dir, checkpoint, speaker)
+    n = _test_long(run) if opt.long is not None else _test_rows(run, prompts)
     print('wrote %d samples to %s' % (n, out_dir))
     return n
 
 
-def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None, rate_of=lambda row, len_b: None,
-               pitch_of=lambda row: None, f0_of=lambda row, i, len_b, f0res, who: None, timing_of=None, write_words=None, level=None):
-    """the `long` mode of test(): split, synthesise the pieces into the rows of one device buffer per group, join, write.  L: the samples
-    per row when a rate makes them more or fewer than the model's own; rate_of(row, len_b) / pitch_of(row) / f0_of(row, i, len_b, f0res,
-    who): what write_prompt gets as `rate` / `pitch` / `f0`; timing_of / write_words (`timings`): test()'s own, called once the joined
-    offsets of a group are known; level (`loudness`): level_waveform's target and ceiling_db -- the joined prompts are levelled"""
-    pause_ms, fade_ms = long
-    split = [split_prompt(p) for p in prompts]
+class Batch(collections.namedtuple('Batch', 'spec al wav conv pcm trim lengths scores f0res paths curved louds')):
+    """What Run.synthesise returns for one batch: host arrays with one row per prompt, or None.  wav: the float waveform when it was
+    not finished on the device, else pcm and trim: the device's int16 samples and [s, e].  lengths (`stop`): len_b.  louds (`loudness`
+    without `long`): the loud_rows (B, 8), with `limit` the limit_rows; pcm then is the levelled one.  scores (`align_scores`): (B, 8).
+    f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
+    lib.f0_viterbi counts (B, 4)).  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.  curved
+    (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve."""
+
+    def row(self, i):
+        """the same fields for row i of the batch alone: row i of every array, inside the tuples too"""
+        def at(a):
+            if a is None:
+                return None
+            return tuple(at(x) for x in a) if isinstance(a, tuple) else a[i]
+        return Batch(*(at(a) for a in self))
+
+
+class Run:
+    """What one call of test() holds across its batches: the configuration, the resolved options and the vocabulary, the checkpoint,
+    the parameter buffer and ONE Tacotron per batch size, the F0 tables on the device, the `prosody` table, and per ROW -- a prompt,
+    with `long` a piece of one, which inherits its prompt's rate and pitch -- the line, its name in printed lines and its step_q
+    values, all resolved before the first batch."""
+
+    def __init__(self, config, opt, prompts, out_dir, checkpoint=None, speaker=0):
+        steps, pitch = rate_steps(opt.rate, len(prompts)), pitch_steps(opt.pitch, len(prompts))
+        self.config, self.opt, self.out_dir, self.speaker = config, opt, out_dir, speaker
+        meta_path = os.path.join(config.data_path, 'meta.pkl')
+        if os.path.exists(meta_path):
+            with open(meta_path, 'rb') as f:
+                self.ivocab = pkl.load(f)['vocab']
+        else:
+            self.ivocab = {i + 1: ch for i, ch in enumerate("abcdefghijklmnopqrstuvwxyz '.,?!-")}
+            self.ivocab[0] = '<pad>'
+        config.vocab_size = len(self.ivocab)
+        self.ckpt = torch.load(checkpoint) if checkpoint else None
+        if self.ckpt is not None:
+            config.r, config.vocab_size = self.ckpt.get('shape', (config.r, config.vocab_size))
+            config.num_speakers = int(self.ckpt.get('num_speakers', 1))
+        self.F = (config.max_decode_iter // 4) * 4 * config.r   # frames per row of the model's output
+        self.pros = None   # per prompt: (L, 2) int32 (dur_q, step_q) per encoded character
+        if opt.prosody is not None:   # the curves carry --rate and --pitch as the value of every character no row of the table names
+            self.pros = prosody_table(opt.prosody, prompts, self.ivocab, _steps('rate', opt.rate, lib.stretch_dur, len(prompts)), pitch)
+            self.pros_pitch = pitch is not None or any(sem is not None for _, _, _, sem in opt.prosody)
+            self.pros_max = max([lib.STRETCH_ONE] + [int(t[:, 0].max()) for t in self.pros if len(t)])
+            steps = pitch = None
+        self.params = None
+        self.models = {}     # batch size -> Tacotron
+        self.f0_opt = None   # the tables on the device, made at the first batch
+        os.makedirs(out_dir, exist_ok=True)
+        self.pieces = [split_prompt(p) if opt.long is not None else [(p, None)] for p in prompts]   # per prompt: its (line, kind of cut)
+        owner = [p for p, pieces in enumerate(self.pieces) for _ in pieces]
+        self.lines = [line for pieces in self.pieces for line, _ in pieces]
+        self.who = ['prompt %d' % p if len(pieces) == 1 else 'prompt %d piece %d' % (p, k)
+                    for p, pieces in enumerate(self.pieces) for k in range(len(pieces))]
+        self.row_steps = None if steps is None else [steps[p] for p in owner]
+        self.row_pitch = None if pitch is None else [pitch[p] for p in owner]
+        self.L = 300 * (self.F - 1)   # `long`: samples per row of the joined buffer; with a rate, every row holds the slowest one's
+        if opt.long is not None and steps is not None:
+            self.L = 300 * (max(5, lib.stretch_capacity(self.F, min(self.row_steps, default=lib.STRETCH_ONE))) - 1)
+
+    def model_for(self, batch):
+        """the Tacotron for this batch's size with the batch as its inputs; only a smaller final batch builds a second one"""
+        c, Bn = self.config, batch['text'].shape[0]
+        if c.num_speakers > 1:
+            batch['speaker'] = torch.full((Bn,), int(self.speaker), dtype=torch.int32)
+        if self.params is None:
+            shape = lib.make_shape(Bn, batch['text'].shape[1], c.max_decode_iter, c.r, c.vocab_size, c.num_speakers)
+            self.params = ParamBuffer(shape, 'cuda').init_(0)
+        model = self.models.get(Bn)
+        if model is None:
+            model = self.models[Bn] = Tacotron(c, batch, train=False, params=self.params)
+            if self.ckpt is not None:
+                model.load_state_dict(self.ckpt)
+        else:
+            model.set_inputs(batch)
+        return model
+
+    def f0_tables(self):
+        """vocode's `f0` keywords for the range of `f0`, and with `f0_smooth` its 'smooth' ones; the tables go up once"""
+        o = self.opt
+        if self.f0_opt is None:
+            w, g, lag_min, lag_max = lib.f0_tables(SR, o.f0[0], o.f0[1])
+            self.f0_opt = dict(weight=torch.from_numpy(w).cuda(), gain=torch.from_numpy(g).cuda(), lag_min=lag_min, lag_max=lag_max)
+            if o.f0_smooth is not None:
+                bias, lg, jump, switch = lib.f0_viterbi_tables(SR, o.f0[0], o.f0[1])
+                self.f0_opt['smooth'] = dict(bias=torch.from_numpy(bias).cuda(), lg=torch.from_numpy(lg).cuda(), candidates=o.f0_smooth,
+                                             jump_cost=jump, switch_cost=switch)
+        return self.f0_opt
+
+    def curves(self, path, batch, n):
+        """vocode's rate_curve / pitch_curve for a batch whose first row is prompt n (`prosody`): two gathers of the per-character
+        values along the device's path (the pitch curve only when a pitch is asked for anywhere)"""
+        Bn, Tt = batch['text'].shape
+        Fm = (path.shape[1] // 4) * 4 * self.config.r
+        values = np.empty((2, Bn, Tt), dtype=np.int32)
+        values[0], values[1] = lib.STRETCH_ONE, lib.PITCH_ONE
+        for i in range(Bn):
+            table = self.pros[n + i][:Tt]
+            values[:, i, :len(table)] = table.T
+        values = torch.from_numpy(values).cuda()
+        curves = [lib.path_curve(path, values[k], self.config.r, one)[:, :Fm].contiguous()
+                  for k, one in ((0, lib.STRETCH_ONE), (1, lib.PITCH_ONE)) if k == 0 or self.pros_pitch]
+        return dict(rate_curve=curves[0], pitch_curve=curves[1] if self.pros_pitch else None)
+
+    def synthesise(self, batch, n, out_rows=None, bounds_rows=None):
+        """one batch whose first row has index n -> its Batch.  out_rows / bounds_rows (`long`): the finished fp32 samples and their
+        bounds go to these device rows, no PCM16 is made and nothing is levelled (`long` levels the joined prompts instead)"""
+        o, c = self.opt, self.config
+        rows = slice(n, n + batch['text'].shape[0])
+        model = self.model_for(batch)
+        out, al = model.run(stop=o.stop)
+        lengths = model.lengths if o.stop is not None else None
+        scores = model.alignment_scores() if o.align_scores else None   # (enqueued behind the decode; read with the other results below)
+        found = model.alignment_path(o.path_jump) if o.timings or self.pros is not None else None   # (likewise; the path stays on the device)
+        paths = found[1:] if o.timings else None
+        model.check()
+        mean, std = (torch.as_tensor(s if s is not None else neutral(c.fft_size * c.r), dtype=torch.float32).cuda()
+                     for s, neutral in ((model.stft_mean, torch.zeros), (model.stft_std, torch.ones)))
+        spec = lib.denorm_unframe(out, mean, std, c.r)                       # (B, Td*r, 1025) chronological log-magnitudes
+        wav = conv = pcm = trim = f0res = curved = louds = None
+        if o.vocode:
+            # the vocoder runs over the rows' own frames with `vocode_lengths`, and with a rate or curves whenever there is a rule: the
+            # host's Fo_b and the device's frames_out are then one number
+            kw = dict(lengths=lengths if o.vocode_lengths or self.row_steps is not None or self.pros is not None else None)
+            if self.row_steps is not None:
+                kw['rate'] = [q / 65536.0 for q in self.row_steps[rows]]
+            if self.row_pitch is not None:   # (step_q as the device takes it: no way back through semitones)
+                kw['pitch'] = torch.tensor(self.row_pitch[rows], dtype=torch.int32).cuda()
+            if o.f0 is not None:
+                kw['f0'] = dict(self.f0_tables(), lengths=lengths)
+            if self.pros is not None:
+                kw.update(self.curves(found[0], batch, n), dur_q_max=self.pros_max)
+            v = vocode(out, mean, std, c.r, n_iter=o.n_iter, seed=n, momentum=o.gl_momentum, want_conv=o.gl_momentum is not None,
+                       phase_init=o.gl_init, lifter=o.lifter, **kw)
+            if v.tracks is not None:
+                f0res = (torch.stack(v.tracks['vocoder'], dim=2).cpu().numpy(), v.tracks['model_stats'].cpu().numpy(),
+                         v.tracks['vocoder_stats'].cpu().numpy(), v.tracks['pitch_stats'].cpu().numpy() if 'pitch_stats' in v.tracks else None)
+                if o.f0_smooth is not None:
+                    f0res += (v.tracks['vocoder_counts'].cpu().numpy(),)
+            if v.src is not None:
+                curved = (v.frames_out.cpu().numpy(), v.src.cpu().numpy())
+            wav = v.waveform
+            if v.conv is not None:
+                conv = v.conv.cpu().numpy()
+                print('Griffin-Lim momentum %g, %d rounds: worst final spectral convergence of the batch %.4f'
+                      % (o.gl_momentum, o.n_iter, float(conv[:, -1].max())))
+            if o.finish:   # (the fp32 waveform stays on the device)
+                level_rows = o.level is not None and out_rows is None
+                # a rate or curves: the row ends where the stretch says, and the rows of `long` are wider than this batch's
+                counts, unit, into = (lengths, c.r, out_rows) if v.frames_out is None else (v.frames_out, 1, None)
+                fin, pcm, trim, _ = finish_waveform(wav, counts, unit, deemphasis=0.0 if o.deemphasis is None else o.deemphasis,
+                                                    trim_top_db=0.0 if o.trim_db is None else o.trim_db,
+                                                    want_out=out_rows is not None or level_rows,
+                                                    want_pcm=out_rows is None and not level_rows, out=into, bounds=bounds_rows)
+                if out_rows is not None and into is None:
+                    out_rows[:, :fin.shape[1]].copy_(fin)
+                if level_rows:   # (the finished fp32 rows stay on the device; their PCM16 is the levelled one)
+                    pcm, louds = level_finished(fin, o.level, bounds=trim)
+                pcm, trim, wav = None if pcm is None else pcm.cpu().numpy(), trim.cpu().numpy(), None
+            else:
+                wav = wav.cpu().numpy()
+        if scores is not None:
+            scores = np.stack([scores_row(k, m) for k, m in zip(scores[0].cpu().numpy(), scores[1].cpu().numpy())])
+        if paths is not None:
+            paths = tuple(x.cpu().numpy() for x in paths)
+        return Batch(spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, None if lengths is None else lengths.cpu().numpy(), scores,
+                     f0res, paths, curved, louds)
+
+    def marks(self, score, L):
+        """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
+        return flags(score[:6], score[6:], L, end_offset=self.opt.stop.end_offset if self.opt.stop is not None else 1)
+
+    def frames_of(self, row, rec):
+        """the frames the vocoder was given for global row `row`, rec its Batch.row: the stretch's own frames_out behind curves, Fo_b
+        behind a rate, else the row's own len_b r or all F"""
+        if rec.curved is not None:
+            return int(rec.curved[0])
+        own = self.F if rec.lengths is None else min(int(rec.lengths) * self.config.r, self.F)
+        return own if self.row_steps is None else lib.stretch_frames(own, self.row_steps[row])
+
+    def rate_of(self, row, rec):
+        """(step_q, Fo_b) of global row `row`, or None without a rate"""
+        return None if self.row_steps is None else (self.row_steps[row], self.frames_of(row, rec))
+
+    def pitch_of(self, row):
+        """(step_q, lifter) of global row `row`, or None without a pitch"""
+        return None if self.row_pitch is None else (self.row_pitch[row], int(self.opt.lifter))
+
+    def f0_of(self, row, rec):
+        """the _f0.npy rows of global row `row`, cut to the frames the vocoder was given; prints the row's line"""
+        if rec.f0res is None:
+            return None
+        frames = self.frames_of(row, rec)
+        for line in f0_lines(self.who[row], list(rec.f0res[1:]), None if self.row_pitch is None else self.row_pitch[row],
+                             None if self.row_steps is None else self.row_steps[row], rec.curved is not None):
+            print(line)
+        return rec.f0res[0][:frames]
+
+    def timing_of(self, row, rec, text_len, offset=0):
+        """(_dur.npy of global row `row`, its word rows in the file it goes to) with `timings`, else (None, None); prints the row's
+        line.  offset: of the piece in a joined file; the row's trim [s, e] is applied when the waveform was finished, and behind
+        curves (`prosody`) the word boundaries go through the row's time map"""
+        if rec.paths is None:
+            return None, None
+        dur, counts, mass = rec.paths
+        print(path_line(self.who[row], counts, mass, text_len, self.opt.stop.end_offset if self.opt.stop is not None else 1)[0])
+        frames = self.frames_of(row, rec)
+        words = word_times(self.lines[row], self.ivocab, dur[:text_len], self.config.r, None if self.row_steps is None else self.row_steps[row],
+                           rec.trim, offset, 300 * max(0, frames - 1), SR, src=None if rec.curved is None else rec.curved[1][:frames])
+        return dur[:text_len], words
+
+    def write_words(self, n, words):
+        with open(os.path.join(self.out_dir, 'prompt_%03d_words.tsv' % n), 'w') as f:
+            f.write(words_tsv(words))
+
+
+def _test_rows(run, prompts):
+    """test() without `long`: every prompt is a row of a batch and writes its own files"""
+    n = 0
+    for batch in load_prompts(prompts, run.ivocab):
+        res = run.synthesise(batch, n)
+        for i in range(batch['text'].shape[0]):
+            rec, text_len = res.row(i), int(batch['text_length'][i])
+            dur, words = run.timing_of(n, rec, text_len)
+            write_prompt(run.out_dir, n, run.config.r, rec.spec, rec.al, rec.wav, None if rec.lengths is None else int(rec.lengths), rec.pcm,
+                         rec.trim, rec.conv, ascore=rec.scores, rate=run.rate_of(n, rec), pitch=run.pitch_of(n), f0=run.f0_of(n, rec),
+                         dur=dur, prosody=None if rec.curved is None else (run.pros[n], int(rec.curved[0])), loud=rec.louds)
+            if rec.louds is not None:
+                print(level_line('prompt %d' % n, rec.louds, run.opt.level))
+            if words is not None:
+                run.write_words(n, words)
+            found = run.marks(rec.scores, text_len) if rec.scores is not None else []
+            if found:
+                print('WARNING prompt %d: %s' % (n, ', '.join(found)))
+            n += 1
+    return n
+
+
+def _test_long(run):
+    """the `long` mode of test(): the pieces of the prompts (run.pieces) are the rows; they are synthesised into the rows of one device
+    buffer per group, joined, and written.  With `loudness` the joined prompts are levelled."""
+    o, split, L = run.opt, run.pieces, run.L
+    pause_ms, fade_ms = o.long
     groups, start = [], 0   # [prompt lo, prompt hi): a group ends at the first prompt boundary at which it holds >= JOIN_GROUP pieces
     held = 0
     for p, pieces in enumerate(split):
@@ -801,50 +857,41 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
         if held >= JOIN_GROUP or p == len(split) - 1:
             groups.append((start, p + 1))
             start, held = p + 1, 0
-    if L is None:
-        L = 300 * ((config.max_decode_iter // 4) * 4 * config.r - 1)   # samples per row of invert_spectrogram
-    who = ['prompt %d' % p if len(pieces) == 1 else 'prompt %d piece %d' % (p, k) for p, pieces in enumerate(split) for k in range(len(pieces))]
     row = 0   # index of the next piece over the whole run (the Griffin-Lim seed of its batch, as the prompt index is without `long`)
     for lo, hi in groups:
-        lines = [line for pieces in split[lo:hi] for line, _ in pieces]
         kinds = [kind for pieces in split[lo:hi] for _, kind in pieces]
         first = np.concatenate([[0], np.cumsum([len(pieces) for pieces in split[lo:hi]])]).astype(np.int64).tolist()
-        N = len(lines)
+        N = len(kinds)
         rows = torch.empty(N, L, dtype=torch.float32, device='cuda')
         bounds = torch.empty(N, 2, dtype=torch.int32, device='cuda')
-        arrays = []   # per piece: (spec, align, len_b, trim, conv, scores, text length, f0 rows)
-        timed = []    # per piece with `timings`: (the batch's paths, row in the batch)
-        at = 0
-        for batch in load_prompts(lines, ivocab):
-            Bn = batch['text'].shape[0]
-            spec, al, _, conv, _, trim, lengths, scores, f0res, paths, _, _ = synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
-            timed += [(paths, i) for i in range(Bn)]
-            arrays += [(spec[i], al[i], int(lengths[i]), trim[i], None if conv is None else conv[i],
-                        None if scores is None else scores[i], int(batch['text_length'][i]),
-                        f0_of(row + at + i, i, int(lengths[i]), f0res, who[row + at + i])) for i in range(Bn)]
-            at += Bn
+        done = []   # per piece: (its Batch.row, its text length, its f0 rows)
+        for batch in load_prompts(run.lines[row:row + N], run.ivocab):
+            at, Bn = len(done), batch['text'].shape[0]
+            res = run.synthesise(batch, row + at, rows[at:at + Bn], bounds[at:at + Bn])
+            for i in range(Bn):
+                rec = res.row(i)
+                done.append((rec, int(batch['text_length'][i]), run.f0_of(row + at + i, rec)))
         gap = join_gaps(kinds, pause_ms)
         louds = None
-        if level is None:
+        if o.level is None:
             _, pcm, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_out=False)
         else:   # (the joined fp32 prompts stay on the device; their PCM16 is the levelled one)
             joined, _, offsets, total, _ = join_waveform(rows, bounds, first, kinds, pause_ms=pause_ms, fade_ms=fade_ms, want_pcm=False)
-            pcm, louds = level_finished(joined, level, total=total)
+            pcm, louds = level_finished(joined, o.level, total=total)
         pcm, total, offsets = pcm.cpu().numpy(), total.cpu().numpy(), offsets.cpu().numpy()   # (the one copy back of the group)
         for p in range(lo, hi):
             a, b = first[p - lo], first[p - lo + 1]
-            path = os.path.join(out_dir, 'prompt_%03d' % p)
+            path = os.path.join(run.out_dir, 'prompt_%03d' % p)
             found, words = [], []
             for k in range(a, b):
-                spec, al, len_b, trim, conv, score, text_len, f0rows = arrays[k]
-                dur = None
-                if timing_of is not None:
-                    dur, piece_words = timing_of(row + k, timed[k][1], len_b, trim, timed[k][0], text_len, lines[k], who[row + k],
-                                                 int(offsets[k]))
+                rec, text_len, f0rows = done[k]
+                dur, piece_words = run.timing_of(row + k, rec, text_len, int(offsets[k]))
+                if o.timings:
                     words += piece_words
-                write_prompt(out_dir, p, config.r, spec, al, None, len_b, None, trim, conv, piece=None if b - a == 1 else k - a, ascore=score,
-                             rate=rate_of(row + k, len_b), pitch=pitch_of(row + k), f0=f0rows, dur=dur)
-                names = marks(score, text_len) if score is not None else []
+                write_prompt(run.out_dir, p, run.config.r, rec.spec, rec.al, None, int(rec.lengths), None, rec.trim, rec.conv,
+                             piece=None if b - a == 1 else k - a, ascore=rec.scores, rate=run.rate_of(row + k, rec), pitch=run.pitch_of(row + k),
+                             f0=f0rows, dur=dur)
+                names = run.marks(rec.scores, text_len) if rec.scores is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
             if found:
@@ -852,11 +899,11 @@ def _test_long(config, prompts, ivocab, out_dir, synthesise, long, marks, L=None
             write_wav_pcm(path + '.wav', pcm[p - lo, :int(total[p - lo])])
             if louds is not None:
                 save_level(path, louds[p - lo])
-                print(level_line('prompt %d' % p, louds[p - lo], level))
-            if timing_of is not None:
-                write_words(p, words)
+                print(level_line('prompt %d' % p, louds[p - lo], o.level))
+            if o.timings:
+                run.write_words(p, words)
             if b - a > 1:
-                table = [[int(offsets[k]), min(L, max(0, int(arrays[k][3][1]) - int(arrays[k][3][0]))), 0 if k == b - 1 else gap[k],
+                table = [[int(offsets[k]), min(L, max(0, int(done[k][0].trim[1]) - int(done[k][0].trim[0]))), 0 if k == b - 1 else gap[k],
                           kinds[k]] for k in range(a, b)]
                 np.save(path + '_pieces.npy', np.array(table, dtype=np.int32))
                 print('prompt %d: %d pieces (%s), %d samples' % (p, b - a, ' '.join(KIND_NAMES[kinds[k]] for k in range(a, b)),
@@ -877,6 +924,13 @@ def _f0_range(text):
     if len(parts) != 2:
         raise argparse.ArgumentTypeError('expected LO,HI in Hz, got %r' % text)
     return tuple(float(x) for x in parts)
+
+
+def option_keywords(a):
+    """The namespace of parse_args -> test()'s option keywords: every field of Options under its own name, but `n_iter` (--gl-iters),
+    `stop` (the rule of --stop, --end-offset, --hold and --min-steps, or None) and `vocode`, which has no flag"""
+    kw = {k: getattr(a, k) for k in Options.__dataclass_fields__ if k not in ('n_iter', 'stop', 'vocode')}
+    return dict(kw, n_iter=a.gl_iters, stop=lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None)
 
 
 def parse_args(argv=None):
@@ -974,10 +1028,7 @@ def parse_args(argv=None):
         ap.error('--path-jump needs --timings or --prosody')
     a.path_jump = lib.PATH_JUMP if a.path_jump is None else a.path_jump
     try:
-        check_options(a.gl_iters, a.stop, a.vocode_lengths, a.gl_momentum, a.deemphasis, a.trim_db, a.long, a.rate, pitch=a.pitch,
-                      lifter=a.lifter, f0=a.f0, f0_smooth=a.f0_smooth, path_jump=a.path_jump if a.timings or a.prosody is not None else None,
-                      prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db, limit=a.limit, limit_ms=a.limit_ms,
-                      true_peak=a.true_peak, limit_passes=a.limit_passes)
+        Options(**option_keywords(a)).resolved()
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -993,9 +1044,4 @@ if __name__ == '__main__':
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
     print('Building Tacotron')
-    rule = lib.TacoStopRule(a.end_offset, a.hold, a.min_steps) if a.stop else None
-    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, n_iter=a.gl_iters, stop=rule,
-         vocode_lengths=a.vocode_lengths, gl_momentum=a.gl_momentum, deemphasis=a.deemphasis, trim_db=a.trim_db, long=a.long,
-         align_scores=a.align_scores, rate=a.rate, pitch=a.pitch, lifter=a.lifter, f0=a.f0, timings=a.timings, path_jump=a.path_jump,
-         f0_smooth=a.f0_smooth, prosody=a.prosody, gl_init=a.gl_init, loudness=a.loudness, peak_db=a.peak_db, limit=a.limit,
-         limit_ms=a.limit_ms, true_peak=a.true_peak, limit_passes=a.limit_passes)
+    test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, **option_keywords(a))

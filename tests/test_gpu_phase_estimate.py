@@ -354,14 +354,14 @@ def test_driver_draft_voice_and_unchanged_default(built_lib, tmp_path, monkeypat
     from tacotron_amd import griffinlim as glm
     from tacotron_amd import test as drv
     calls = []
-    real = drv.invert_spectrogram
+    real = drv.vocode
 
     def spy(*a, **k):
         res = real(*a, **k)
-        calls.append((a, dict(k), res))
+        calls.append((a, dict(k), res.waveform))
         return res
 
-    monkeypatch.setattr(drv, 'invert_spectrogram', spy)
+    monkeypatch.setattr(drv, 'vocode', spy)
     with contextlib.redirect_stdout(io.StringIO()):
         assert drv.test(_cfg(tmp_path), PROMPTS, out_dir=str(tmp_path / 'plain'), n_iter=2) == 2
         assert drv.test(_cfg(tmp_path), PROMPTS, out_dir=str(tmp_path / 'random'), n_iter=2, gl_init='random') == 2

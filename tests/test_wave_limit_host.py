@@ -204,3 +204,42 @@ def test_driver_options(built_lib, capsys):
     assert drv.limit_line('prompt 3', row, -16.0) == ('prompt 3: -27.3 LUFS -> -16.2 (asked -16.0), true peak -1.0 dBTP, '
                                                        '3.1 % of samples limited, deepest -4.2 dB')
     assert 'level unchanged' in drv.limit_line('prompt 0', drv.limit_row([0, 1, 1, 0], [5, 0], -math.inf, 0.0, -math.inf), -16.0)
+
+
+def test_the_option_names_exist_once(tmp_path):
+    """The record of the options, check_options and test() name the same options with the same defaults (check_options: path_jump
+    None), and a command line that sets every flag reaches test() whole: what option_keywords makes of the namespace are names
+    test() accepts -- every option but `vocode`, which has no flag -- and the record's check passes on them."""
+    import dataclasses
+    from tacotron_amd import lib
+    from tacotron_amd import test as drv
+    fields = {f.name: f.default for f in dataclasses.fields(drv.Options)}
+    checked = {k: p.default for k, p in inspect.signature(drv.check_options).parameters.items()}
+    driven = {k: p.default for k, p in inspect.signature(drv.test).parameters.items()
+              if k not in ('config', 'prompts', 'out_dir', 'checkpoint', 'speaker')}
+    assert set(fields) == set(checked) == set(driven)
+    assert fields == driven and dict(fields, path_jump=None) == checked
+    assert all(p.kind is inspect.Parameter.KEYWORD_ONLY for p in inspect.signature(drv.check_options).parameters.values())
+    prosody = tmp_path / 'prosody.tsv'
+    prosody.write_text('0\t0\t0.8\t-\n')
+    common = ['--stop', '--end-offset', '2', '--hold', '3', '--min-steps', '5', '--vocode-lengths', '--gl-momentum', '0.99', '--gl-iters', '7',
+              '--gl-init', 'estimate', '--deemphasis', '0.9', '--trim-db', '40', '--rate', '0.8', '--pitch', '2', '--lifter', '24',
+              '--f0-range', '70,350', '--f0-smooth', '--f0-candidates', '3', '--align-scores', '--timings', '--path-jump', '2',
+              '--loudness', '-16', '--peak-db', '-2', '--limit', '--limit-ms', '3', '--true-peak', '2', '--limit-passes', '1']
+    seen = {}
+    for argv in (common + ['--long', '--pause-ms', '200,100,10', '--fade-ms', '2'], common + ['--prosody', str(prosody)]):
+        kw = drv.option_keywords(drv.parse_args(argv))
+        assert set(kw) == set(driven) - {'vocode'}
+        drv.Options(**kw).check()
+        for k, v in kw.items():
+            if v != fields[k]:
+                seen[k] = v
+        rule = kw['stop']
+        assert isinstance(rule, lib.TacoStopRule) and (rule.end_offset, rule.hold, rule.min_steps) == (2, 3, 5)
+        assert (kw['n_iter'], kw['gl_momentum'], kw['gl_init'], kw['deemphasis'], kw['trim_db']) == (7, 0.99, 'estimate', 0.9, 40.0)
+        assert (kw['rate'], kw['pitch'], kw['lifter'], kw['f0'], kw['f0_smooth'], kw['path_jump']) == (0.8, 2.0, 24, (70.0, 350.0), 3, 2)
+        assert (kw['loudness'], kw['peak_db'], kw['limit'], kw['limit_ms'], kw['true_peak'], kw['limit_passes']) == (-16.0, -2.0, True, 3.0, 2, 1)
+        assert kw['vocode_lengths'] is True and kw['align_scores'] is True and kw['timings'] is True
+    assert set(seen) == set(driven) - {'vocode'}            # between them the two command lines move every option off its default
+    assert seen['long'] == dict(pause_ms=(200.0, 100.0, 10.0), fade_ms=2.0) and seen['prosody'] == [(0, 0, 0.8, None)]
+    assert drv.option_keywords(drv.parse_args([]))['stop'] is None
