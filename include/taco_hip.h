@@ -229,6 +229,56 @@ int taco_debug_gemm_tn_group(int n, const float* const* A, const int* lda, const
 int taco_debug_gemm_tn_strided(const float* A, int lda, int64_t strideA, const float* Y, int ldy, int64_t strideY, float* W, int ldw,
                                int64_t strideW, int M, int N, int K, int T, int pad_l, int batch, void* stream);
 
+/* ---- op-level debug doors of the train step's glue kernels (tests/test_gpu_glue_ops.py) ----------------------
+ * The memory-bound passes of csrc/elementwise.hip between the GEMMs and the recurrences, each door one launch_* of that file with
+ * the caller's stream; no kernel of their own, no launch added to any product path.  Conventions of the doors above: fp32,
+ * row-major, dense unless a pitch is given; a null operand that is not nullable, a size out of range (rows <= 2^22, columns
+ * <= 2^14, flat counts < 2^31) or an output whose bytes meet another operand's returns TACO_EINVAL with a message naming the
+ * argument, before anything is enqueued.  TACO_DETERMINISTIC=1 is read on every call, as in the train step.  Detect by the symbol.
+ *
+ * taco_debug_embedding: out (rows, width) = table (V, width) [clamp(ids, 0, V - 1)]; width % 4 == 0 (the model: 256 and 16).
+ * taco_debug_embedding_bwd: dtable[v] += sum of the rows of dout (rows, width) whose clamped id is v; width % 4 == 0, <= 1024.
+ *   min(32, ceil(rows / 256)) row segments that meet in fp32 atomics; ONE segment, plain adds, under TACO_DETERMINISTIC=1.
+ * taco_debug_highway_combine: th (M, 256) = [T | H], x, y (M, 128): y = H T + x (1 - T).
+ * taco_debug_highway_combine_bwd: dth (M, 256) = [dy (H - x) T (1 - T) | H > 0 ? dy T : 0], dx = dy (1 - T).
+ * taco_debug_act_bwd: dz = dy act'(y) over n elements, y the stored OUTPUT of the activation (RELU: y > 0 ? dy : 0; SIGMOID:
+ *   dy y (1 - y); TANH: dy (1 - y y)); keep (n bytes, nullable): dz = keep ? 2 dz : 0.  dz == dy (in place) is allowed.
+ * taco_debug_affine_act_bwd: pre, dy, dz (M, N), rs = 1 / sqrt(1 + 1e-3): dgamma[n] += sum_m dy pre rs, dbeta[n] += sum_m dy (fp32
+ *   atomics, one per row chunk; one chunk under TACO_DETERMINISTIC=1), dz = dy gamma rs, 0 where act == TACO_ACT_RELU and
+ *   !(pre > 0); act NONE or RELU.
+ * taco_debug_colsum_batched: out (B, N) = sum over t < T of x ((B T), N; ld); overwritten.
+ * taco_debug_mask_rows: y (B, T, C) = x where t < len[b], else 0; C % 4 == 0.
+ * taco_debug_center_rows: n = clamp(len[b], 1, T): out[b, s] = x[b, s] - mean over s' < n of x[b, s'] for s < n, else 0; C % 4 == 0.
+ * taco_debug_mask_pos: in place g[r][c] = y[r][c] > 0 ? scale g[r][c] : 0 for c < cols; g (rows, cols; ldg), y (rows, cols; ldy).
+ * taco_debug_zero_tail_rows: rows t >= len[b] of x0 (B, Td, C0) and, when given, x1 (B, Td, C1) become 0 in place.
+ * taco_debug_add: y = a + b over n elements.
+ * taco_debug_l1_loss: the loss as taco_forward forms it.  Term i = 0, 1 (a_i, b_i (M_i, N_i); both null: the term is 0):
+ *   parts[512 i ..] = 512 block partials of sum |a - b| (blocks without rows write 0), grad_i (M_i, N_i; ldg_i; nullable) =
+ *   sign(a - b), 0 at a == b and in the pad columns [N_i, ldg_i); then loss[1], loss[2] = ordered sums of the partials, loss[0] =
+ *   their sum, out (3, nullable) = {loss[0], loss[1], loss[2]}.  parts holds 1024 floats, loss 3.
+ * taco_debug_transpose_batch: n <= 96 jobs of one launch: out[i] (taps, N, K; ldo) = the transposes of in[i] (taps, K, N; ldi) with
+ *   the taps REVERSED (out tap t = in tap taps - 1 - t).  ldi / ldo: null tables or 0 = dense; a pitched job has taps == 1.
+ * taco_debug_sumsq: out[0 .. 256) = per-block partial sums of x[i]^2 over n elements (x 16-byte aligned); taco_clip_adam_step adds
+ *   them in order and takes the root. */
+int taco_debug_embedding(const float* table, const int32_t* ids, float* out, int rows, int V, int width, void* stream);
+int taco_debug_embedding_bwd(const float* dout, const int32_t* ids, float* dtable, int rows, int V, int width, void* stream);
+int taco_debug_highway_combine(const float* th, const float* x, float* y, int M, void* stream);
+int taco_debug_highway_combine_bwd(const float* th, const float* x, const float* dy, float* dth, float* dx, int M, void* stream);
+int taco_debug_act_bwd(const float* y, const float* dy, const uint8_t* keep, float* dz, int64_t n, int act, void* stream);
+int taco_debug_affine_act_bwd(const float* pre, const float* gamma, const float* dy, float* dz, float* dgamma, float* dbeta, int M,
+                              int N, int act, void* stream);
+int taco_debug_colsum_batched(const float* x, int ld, float* out, int B, int T, int N, void* stream);
+int taco_debug_mask_rows(const float* x, const int32_t* len, float* y, int B, int T, int C, void* stream);
+int taco_debug_center_rows(const float* x, const int32_t* len, float* out, int B, int T, int C, void* stream);
+int taco_debug_mask_pos(float* g, int ldg, const float* y, int ldy, int rows, int cols, float scale, void* stream);
+int taco_debug_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* len, int B, int Td, void* stream);
+int taco_debug_add(const float* a, const float* b, float* y, int64_t n, void* stream);
+int taco_debug_l1_loss(const float* a0, const float* b0, float* grad0, int ldg0, int M0, int N0, const float* a1, const float* b1,
+                       float* grad1, int ldg1, int M1, int N1, float* parts, float* loss, float* out, void* stream);
+int taco_debug_transpose_batch(int n, const float* const* in, float* const* out, const int* taps, const int* K, const int* N,
+                               const int* ldi, const int* ldo, void* stream);
+int taco_debug_sumsq(const float* x, int64_t n, float* out, void* stream);
+
 /* ---- model level ---------------------------------------------------------------------------------------- */
 /* Tacotron.inference with train=True (tacotron.py:107-154) + add_loss_op (tacotron.py:156-165).
  *   text (B,Tt) int32; text_length (B) int32; mel (B,Td,80r); stft (B,Td,1025r);

@@ -133,7 +133,7 @@ static inline bool ensure_dyn_smem(DynSmemOnce& done, const void* func, size_t b
 // bytes meet those of any other operand, is refused by name before anything is enqueued.
 struct DoorOperands {
   struct Op { char name[24]; const void* p; size_t bytes; bool out, optional; };
-  static constexpr int kMax = 128;   // (taco_debug_gemm_tn_group: 4 operands for each of kMaxTnBatch = 26 problems)
+  static constexpr int kMax = 192;   // (taco_debug_transpose_batch: 2 operands for each of kMaxTransposeBatch = 96 jobs)
   Op ops[kMax];
   int n = 0;
   bool overflow = false;   // an operand that did not fit: check() refuses the call instead of leaving it unchecked

@@ -1562,6 +1562,73 @@ int launch_colsum_batched(const float* x, int ld, float* out, int B, int T, int 
   TACO_LAUNCH_CHECK("colsum_batched");
   return TACO_OK;
 }
+// ---- debug doors of the glue kernels (include/taco_hip.h "op-level debug doors of the train step's glue kernels"): each checks its
+//      arguments by name, calls the launch_* above it with the caller's stream and returns its code; no kernel of their own ----
+#define DOOR_ROWS(who, name, v) TACO_REQUIRE((v) > 0 && (v) <= kDoorMaxRows, "%s: %s must be in [1, 2^22], got %lld", who, name, (long long)(v))
+#define DOOR_COLS(who, name, v) TACO_REQUIRE((v) > 0 && (v) <= kDoorMaxCols, "%s: %s must be in [1, 2^14], got %lld", who, name, (long long)(v))
+#define DOOR_COLS4(who, name, v) \
+  TACO_REQUIRE((v) > 0 && (v) <= kDoorMaxCols && (v) % 4 == 0, "%s: %s must be a multiple of 4 in [4, 2^14], got %lld", who, name, (long long)(v))
+#define DOOR_PITCH(who, name, v, least) TACO_REQUIRE((v) >= (least), "%s: %s must be >= %lld, got %lld", who, name, (long long)(least), (long long)(v))
+constexpr int64_t kDoorMaxElems = (int64_t)1 << 31;   // flat element counts (act_bwd, add, sumsq)
+extern "C" int taco_debug_embedding(const float* table, const int32_t* ids, float* out, int rows, int V, int width, void* stream) {
+  const char* who = "taco_debug_embedding";
+  DOOR_ROWS(who, "rows", rows);
+  DOOR_COLS(who, "V", V);
+  DOOR_COLS4(who, "width", width);
+  DoorOperands o;
+  o.in(table, (size_t)V * width * sizeof(float), "table");
+  o.in(ids, (size_t)rows * sizeof(int32_t), "ids");
+  o.out(out, (size_t)rows * width * sizeof(float), "out");
+  TACO_TRY(o.check(who));
+  return launch_embedding(table, ids, out, rows, V, as_stream(stream), width);
+}
+extern "C" int taco_debug_embedding_bwd(const float* dout, const int32_t* ids, float* dtable, int rows, int V, int width, void* stream) {
+  const char* who = "taco_debug_embedding_bwd";
+  DOOR_ROWS(who, "rows", rows);
+  DOOR_COLS(who, "V", V);
+  TACO_REQUIRE(width > 0 && width <= 1024 && width % 4 == 0, "%s: width must be a multiple of 4 in [4, 1024], got %d", who, width);
+  DoorOperands o;
+  o.in(dout, (size_t)rows * width * sizeof(float), "dout");
+  o.in(ids, (size_t)rows * sizeof(int32_t), "ids");
+  o.out(dtable, (size_t)V * width * sizeof(float), "dtable");
+  TACO_TRY(o.check(who));
+  return launch_embedding_bwd(dout, ids, dtable, rows, V, as_stream(stream), width);
+}
+extern "C" int taco_debug_center_rows(const float* x, const int32_t* len, float* out, int B, int T, int C, void* stream) {
+  const char* who = "taco_debug_center_rows";
+  TACO_REQUIRE(B > 0 && B <= 65535 && T > 0 && (int64_t)B * T <= kDoorMaxRows, "%s: B must be in [1, 65535] and B T in [1, 2^22], got B = %d, T = %d", who, B, T);
+  DOOR_COLS4(who, "C", C);
+  const size_t mc = (size_t)B * T * C * sizeof(float);
+  DoorOperands o;
+  o.in(x, mc, "x");
+  o.in(len, (size_t)B * sizeof(int32_t), "len");
+  o.out(out, mc, "out");
+  TACO_TRY(o.check(who));
+  return launch_center_rows(x, len, out, B, T, C, as_stream(stream));
+}
+extern "C" int taco_debug_mask_pos(float* g, int ldg, const float* y, int ldy, int rows, int cols, float scale, void* stream) {
+  const char* who = "taco_debug_mask_pos";
+  DOOR_ROWS(who, "rows", rows);
+  DOOR_COLS(who, "cols", cols);
+  DOOR_PITCH(who, "ldg", ldg, cols);
+  DOOR_PITCH(who, "ldy", ldy, cols);
+  DoorOperands o;
+  o.out(g, door_span(rows, cols, ldg), "g");
+  o.in(y, door_span(rows, cols, ldy), "y");
+  TACO_TRY(o.check(who));
+  return launch_mask_pos(g, ldg, y, ldy, rows, cols, scale, as_stream(stream));
+}
+extern "C" int taco_debug_colsum_batched(const float* x, int ld, float* out, int B, int T, int N, void* stream) {
+  const char* who = "taco_debug_colsum_batched";
+  TACO_REQUIRE(B > 0 && B <= 65535 && T > 0 && (int64_t)B * T <= kDoorMaxRows, "%s: B must be in [1, 65535] and B T in [1, 2^22], got B = %d, T = %d", who, B, T);
+  DOOR_COLS(who, "N", N);
+  DOOR_PITCH(who, "ld", ld, N);
+  DoorOperands o;
+  o.in(x, door_span((int64_t)B * T, N, ld), "x");
+  o.out(out, (size_t)B * N * sizeof(float), "out");
+  TACO_TRY(o.check(who));
+  return launch_colsum_batched(x, ld, out, B, T, N, as_stream(stream));
+}
 int launch_bn_maxpool(const float* x, const float* gamma, const float* beta, float* y, int B, int T, int C, hipStream_t s) {
   TACO_REQUIRE(C % 4 == 0, "bn_maxpool: C %% 4 != 0");
   EW_LAUNCH(bn_maxpool_kernel, (int64_t)B * T * (C / 4), s, x, gamma, beta, y, B, T, C);
@@ -1650,6 +1717,83 @@ int launch_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* l
   TACO_LAUNCH_CHECK("zero_tail_rows");
   return TACO_OK;
 }
+extern "C" int taco_debug_highway_combine(const float* th, const float* x, float* y, int M, void* stream) {
+  const char* who = "taco_debug_highway_combine";
+  DOOR_ROWS(who, "M", M);
+  DoorOperands o;
+  o.in(th, (size_t)M * 2 * kCb * sizeof(float), "th");
+  o.in(x, (size_t)M * kCb * sizeof(float), "x");
+  o.out(y, (size_t)M * kCb * sizeof(float), "y");
+  TACO_TRY(o.check(who));
+  return launch_highway_combine(th, x, y, M, as_stream(stream));
+}
+extern "C" int taco_debug_highway_combine_bwd(const float* th, const float* x, const float* dy, float* dth, float* dx, int M, void* stream) {
+  const char* who = "taco_debug_highway_combine_bwd";
+  DOOR_ROWS(who, "M", M);
+  DoorOperands o;
+  o.in(th, (size_t)M * 2 * kCb * sizeof(float), "th");
+  o.in(x, (size_t)M * kCb * sizeof(float), "x");
+  o.in(dy, (size_t)M * kCb * sizeof(float), "dy");
+  o.out(dth, (size_t)M * 2 * kCb * sizeof(float), "dth");
+  o.out(dx, (size_t)M * kCb * sizeof(float), "dx");
+  TACO_TRY(o.check(who));
+  return launch_highway_combine_bwd(th, x, dy, dth, dx, M, as_stream(stream));
+}
+// dz == dy (in place, as the model calls it) is the one overlap a door allows: dy is then checked as the output only
+extern "C" int taco_debug_act_bwd(const float* y, const float* dy, const uint8_t* keep, float* dz, int64_t n, int act, void* stream) {
+  const char* who = "taco_debug_act_bwd";
+  TACO_REQUIRE(n > 0 && n < kDoorMaxElems, "%s: n must be in [1, 2^31), got %lld", who, (long long)n);
+  TACO_REQUIRE(act >= TACO_ACT_NONE && act <= TACO_ACT_TANH, "%s: act must be one of TACO_ACT_*, got %d", who, act);
+  TACO_REQUIRE(dy, "%s: dy is null", who);
+  DoorOperands o;
+  o.in(y, (size_t)n * sizeof(float), "y");
+  if (dy != dz) o.in(dy, (size_t)n * sizeof(float), "dy");
+  o.in_opt(keep, (size_t)n, "keep");
+  o.out(dz, (size_t)n * sizeof(float), "dz");
+  TACO_TRY(o.check(who));
+  return launch_act_bwd(y, dy, keep, dz, n, act, as_stream(stream));
+}
+extern "C" int taco_debug_affine_act_bwd(const float* pre, const float* gamma, const float* dy, float* dz, float* dgamma, float* dbeta, int M,
+                                         int N, int act, void* stream) {
+  const char* who = "taco_debug_affine_act_bwd";
+  DOOR_ROWS(who, "M", M);
+  DOOR_COLS(who, "N", N);
+  TACO_REQUIRE(act == TACO_ACT_NONE || act == TACO_ACT_RELU, "%s: act must be TACO_ACT_NONE or TACO_ACT_RELU, got %d", who, act);
+  const size_t mn = (size_t)M * N * sizeof(float);
+  DoorOperands o;
+  o.in(pre, mn, "pre");
+  o.in(gamma, (size_t)N * sizeof(float), "gamma");
+  o.in(dy, mn, "dy");
+  o.out(dz, mn, "dz");
+  o.out(dgamma, (size_t)N * sizeof(float), "dgamma");
+  o.out(dbeta, (size_t)N * sizeof(float), "dbeta");
+  TACO_TRY(o.check(who));
+  return launch_affine_act_bwd(pre, gamma, dy, dz, dgamma, dbeta, M, N, act, as_stream(stream));
+}
+extern "C" int taco_debug_mask_rows(const float* x, const int32_t* len, float* y, int B, int T, int C, void* stream) {
+  const char* who = "taco_debug_mask_rows";
+  TACO_REQUIRE(B > 0 && T > 0 && (int64_t)B * T <= kDoorMaxRows, "%s: B T must be in [1, 2^22], got B = %d, T = %d", who, B, T);
+  DOOR_COLS4(who, "C", C);
+  const size_t mc = (size_t)B * T * C * sizeof(float);
+  DoorOperands o;
+  o.in(x, mc, "x");
+  o.in(len, (size_t)B * sizeof(int32_t), "len");
+  o.out(y, mc, "y");
+  TACO_TRY(o.check(who));
+  return launch_mask_rows(x, len, y, B, T, C, as_stream(stream));
+}
+extern "C" int taco_debug_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* len, int B, int Td, void* stream) {
+  const char* who = "taco_debug_zero_tail_rows";
+  TACO_REQUIRE(B > 0 && Td > 0 && (int64_t)B * Td <= kDoorMaxRows, "%s: B Td must be in [1, 2^22], got B = %d, Td = %d", who, B, Td);
+  DOOR_COLS(who, "C0", C0);
+  if (x1) DOOR_COLS(who, "C1", C1);
+  DoorOperands o;
+  o.out(x0, (size_t)B * Td * C0 * sizeof(float), "x0");
+  o.out_opt(x1, x1 ? (size_t)B * Td * C1 * sizeof(float) : 0, "x1");
+  o.in(len, (size_t)B * sizeof(int32_t), "len");
+  TACO_TRY(o.check(who));
+  return launch_zero_tail_rows(x0, C0, x1, C1, len, B, Td, as_stream(stream));
+}
 int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* len, int B, int Tt, int Td, int end_offset, int hold,
                      int min_steps, hipStream_t s) {
   TACO_KLAUNCH(stop_rule_kernel, dim3(B), dim3(256), 0, s, align, text_length, len, Tt, Td, end_offset, hold, min_steps);
@@ -1708,6 +1852,77 @@ int launch_transpose_batch(TransposeBatch& b, hipStream_t s) {
   TACO_KLAUNCH(transpose_batch_kernel, dim3(tiles), dim3(32, 8), 0, s, b);
   TACO_LAUNCH_CHECK("transpose_batch");
   return TACO_OK;
+}
+extern "C" int taco_debug_add(const float* a, const float* b, float* y, int64_t n, void* stream) {
+  const char* who = "taco_debug_add";
+  TACO_REQUIRE(n > 0 && n < kDoorMaxElems, "%s: n must be in [1, 2^31), got %lld", who, (long long)n);
+  DoorOperands o;
+  o.in(a, (size_t)n * sizeof(float), "a");
+  o.in(b, (size_t)n * sizeof(float), "b");
+  o.out(y, (size_t)n * sizeof(float), "y");
+  TACO_TRY(o.check(who));
+  return launch_add(a, b, y, n, as_stream(stream));
+}
+// the loss as taco_forward forms it: launch_l1 per term that is given (a term without operands contributes kLossParts zeros), then
+// launch_finish_loss.  parts (2 kLossParts) and loss (3) stay with the caller.
+extern "C" int taco_debug_l1_loss(const float* a0, const float* b0, float* grad0, int ldg0, int M0, int N0, const float* a1,
+                                  const float* b1, float* grad1, int ldg1, int M1, int N1, float* parts, float* loss, float* out,
+                                  void* stream) {
+  const char* who = "taco_debug_l1_loss";
+  const float* a[2] = {a0, a1};
+  const float* b[2] = {b0, b1};
+  float* grad[2] = {grad0, grad1};
+  const int ldg[2] = {ldg0, ldg1}, M[2] = {M0, M1}, N[2] = {N0, N1};
+  DoorOperands o;
+  for (int i = 0; i < 2; ++i) {
+    TACO_REQUIRE((a[i] != nullptr) == (b[i] != nullptr), "%s: a%d and b%d must both be given or both be null", who, i, i);
+    if (!a[i]) {
+      TACO_REQUIRE(!grad[i], "%s: grad%d without a%d", who, i, i);
+      continue;
+    }
+    TACO_REQUIRE(M[i] > 0 && M[i] <= kDoorMaxRows, "%s: M%d must be in [1, 2^22], got %d", who, i, M[i]);
+    TACO_REQUIRE(N[i] > 0 && N[i] <= kDoorMaxCols, "%s: N%d must be in [1, 2^14], got %d", who, i, N[i]);
+    if (grad[i]) TACO_REQUIRE(ldg[i] >= N[i], "%s: ldg%d must be >= %d, got %d", who, i, N[i], ldg[i]);
+    o.in(a[i], (size_t)M[i] * N[i] * sizeof(float), "a%d", i);
+    o.in(b[i], (size_t)M[i] * N[i] * sizeof(float), "b%d", i);
+    o.out_opt(grad[i], grad[i] ? (size_t)M[i] * ldg[i] * sizeof(float) : 0, "grad%d", i);
+  }
+  o.out(parts, (size_t)2 * kLossParts * sizeof(float), "parts");
+  o.out(loss, 3 * sizeof(float), "loss");
+  o.out_opt(out, 3 * sizeof(float), "out");
+  TACO_TRY(o.check(who));
+  hipStream_t s = as_stream(stream);
+  for (int i = 0; i < 2; ++i) {
+    if (a[i]) TACO_TRY(launch_l1(a[i], b[i], grad[i], grad[i] ? ldg[i] : N[i], parts + i * kLossParts, M[i], N[i], s));
+    else TACO_TRY(taco_memset_async(parts + i * kLossParts, 0, kLossParts * sizeof(float), s, who));
+  }
+  return launch_finish_loss(loss, parts, out, s);
+}
+extern "C" int taco_debug_transpose_batch(int n, const float* const* in, float* const* out, const int* taps, const int* K, const int* N,
+                                          const int* ldi, const int* ldo, void* stream) {
+  const char* who = "taco_debug_transpose_batch";
+  TACO_REQUIRE(n >= 1 && n <= kMaxTransposeBatch, "%s: n must be in [1, %d], got %d", who, kMaxTransposeBatch, n);
+  TACO_REQUIRE(in && out && taps && K && N, "%s: a null argument table", who);
+  TACO_REQUIRE((ldi != nullptr) == (ldo != nullptr), "%s: ldi and ldo must both be given or both be null", who);
+  static_assert(2 * kMaxTransposeBatch <= DoorOperands::kMax, "one input and one output per job");
+  TransposeBatch tb;
+  DoorOperands o;
+  for (int i = 0; i < n; ++i) {
+    TACO_REQUIRE(taps[i] >= 1 && taps[i] <= 64, "%s: taps[%d] must be in [1, 64], got %d", who, i, taps[i]);
+    TACO_REQUIRE(K[i] > 0 && K[i] <= kDoorMaxCols, "%s: K[%d] must be in [1, 2^14], got %d", who, i, K[i]);
+    TACO_REQUIRE(N[i] > 0 && N[i] <= kDoorMaxCols, "%s: N[%d] must be in [1, 2^14], got %d", who, i, N[i]);
+    const int li = ldi ? ldi[i] : 0, lo = ldo ? ldo[i] : 0;
+    TACO_REQUIRE(li == 0 || li >= N[i], "%s: ldi[%d] must be 0 or >= %d, got %d", who, i, N[i], li);
+    TACO_REQUIRE(lo == 0 || lo >= K[i], "%s: ldo[%d] must be 0 or >= %d, got %d", who, i, K[i], lo);
+    TACO_REQUIRE((li == 0 && lo == 0) || taps[i] == 1, "%s: job %d has a pitch and taps = %d (a pitched job has one tap)", who, i, taps[i]);
+    o.in(in[i], door_span((int64_t)taps[i] * K[i], N[i], li ? li : N[i]), "in[%d]", i);
+    o.out(out[i], door_span((int64_t)taps[i] * N[i], K[i], lo ? lo : K[i]), "out[%d]", i);
+    TransposeJob& J = tb.j[i];
+    J.in = in[i]; J.out = out[i]; J.taps = taps[i]; J.K = K[i]; J.N = N[i]; J.tile0 = 0; J.ldi = li; J.ldo = lo;
+  }
+  tb.n = n;
+  TACO_TRY(o.check(who));
+  return launch_transpose_batch(tb, as_stream(stream));
 }
 extern "C" int taco_denorm_unframe(const float* out, const float* mean, const float* stdv, float* spec, float* mag_t, int B,
                                    int Td, int r, int C, void* stream) {
@@ -1942,6 +2157,15 @@ int launch_sumsq(const float* x, int64_t n, float* out, hipStream_t s) {
   TACO_KLAUNCH(sumsq_kernel, dim3(kSumsqParts), dim3(kThreads), 0, s, x, n, out);
   TACO_LAUNCH_CHECK("sumsq");
   return TACO_OK;
+}
+extern "C" int taco_debug_sumsq(const float* x, int64_t n, float* out, void* stream) {
+  const char* who = "taco_debug_sumsq";
+  TACO_REQUIRE(n > 0 && n < kDoorMaxElems, "%s: n must be in [1, 2^31), got %lld", who, (long long)n);
+  DoorOperands o;
+  o.in(x, (size_t)n * sizeof(float), "x");
+  o.out(out, (size_t)kSumsqParts * sizeof(float), "out");
+  TACO_TRY(o.check(who));
+  return launch_sumsq(x, n, out, as_stream(stream));
 }
 int launch_clip_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float cap, int64_t step,
                      const float* sumsq, float* gnorm_out, const int32_t* err, hipStream_t s) {

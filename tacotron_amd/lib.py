@@ -116,6 +116,21 @@ EXPORTS = {
     'taco_debug_conv_gemm_rowbias': (C.c_int, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     'taco_debug_gemm_tn_group': (C.c_int, [_I] + [_P] * 13 + [_P]),
     'taco_debug_gemm_tn_strided': (C.c_int, [_P, _I, C.c_int64, _P, _I, C.c_int64, _P, _I, C.c_int64, _I, _I, _I, _I, _I, _I, _P]),
+    'taco_debug_embedding': (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    'taco_debug_embedding_bwd': (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    'taco_debug_highway_combine': (C.c_int, [_P, _P, _P, _I, _P]),
+    'taco_debug_highway_combine_bwd': (C.c_int, [_P] * 5 + [_I, _P]),
+    'taco_debug_act_bwd': (C.c_int, [_P, _P, _P, _P, C.c_int64, _I, _P]),
+    'taco_debug_affine_act_bwd': (C.c_int, [_P] * 6 + [_I, _I, _I, _P]),
+    'taco_debug_colsum_batched': (C.c_int, [_P, _I, _P, _I, _I, _I, _P]),
+    'taco_debug_mask_rows': (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    'taco_debug_center_rows': (C.c_int, [_P, _P, _P, _I, _I, _I, _P]),
+    'taco_debug_mask_pos': (C.c_int, [_P, _I, _P, _I, _I, _I, C.c_float, _P]),
+    'taco_debug_zero_tail_rows': (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _P]),
+    'taco_debug_add': (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    'taco_debug_l1_loss': (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'taco_debug_transpose_batch': (C.c_int, [_I] + [_P] * 7 + [_P]),
+    'taco_debug_sumsq': (C.c_int, [_P, C.c_int64, _P, _P]),
     'taco_forward': (C.c_int, [_SH] + [_P] * 17),
     'taco_backward': (C.c_int, [_SH] + [_P] * 14),
     'taco_infer': (C.c_int, [_SH] + [_P] * 9),
@@ -704,6 +719,226 @@ def debug_gemm_tn_strided(A, Y, W, M, N, K, batch, strideA, strideY, strideW, T=
     _flat_args(who, [('A', A, ext[0], False), ('Y', Y, ext[1], False)], [('W', W, ext[2], False)])
     _check(_lib.taco_debug_gemm_tn_strided(ptr(A), lda, strides[0], ptr(Y), ldy, strides[1], ptr(W), ldw, strides[2], M, N, K, T, pad_l, batch,
                                            stream_ptr()), 'taco_debug_gemm_tn_strided')
+
+
+# ---- op-level debug doors of the train step's glue kernels (include/taco_hip.h; tests/test_gpu_glue_ops.py) ----
+# Flat contiguous tensors again, each of the dtype its operand has (float32, int32 ids and lengths, uint8 keep masks) and of at
+# least the operand's element count; TACO_DETERMINISTIC is read by the library on every call.
+DOOR_MAX_FLAT = (1 << 31) - 1
+LOSS_PARTS = 512           # kLossParts
+SUMSQ_PARTS = 256          # kSumsqParts
+MAX_TRANSPOSE_BATCH = 96   # kMaxTransposeBatch
+_ACTS = {'none': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3}
+
+
+def _typed_args(who, ins, outs, alias=()):
+    """_flat_args for operands of any dtype: ins, outs = [(name, tensor, dtype, elements needed, optional)].  `alias`: (in, out) name
+    pairs that may be the very same tensor (same start: the in-place form); any other meeting of an output with an operand is refused."""
+    dev = ins[0][1].device if torch.is_tensor(ins[0][1]) else None
+    for name, t, dtype, need, optional in ins + outs:
+        if tensor_arg(who, name, t, dtype, ('n',), dev, optional) is not None and t.numel() < need:
+            raise ValueError('%s: %s must hold at least %d elements, got %d' % (who, name, need, t.numel()))
+    live_in = [(n, t, need) for n, t, _, need, _ in ins if t is not None]
+    live_out = [(n, t, need) for n, t, _, need, _ in outs if t is not None]
+    for i, (n_out, t_out, need_out) in enumerate(live_out):
+        for n_in, t_in, need_in in live_in + live_out[i + 1:]:
+            if (n_in, n_out) in alias and t_in.data_ptr() == t_out.data_ptr():
+                continue
+            no_overlap(who, n_in, t_in, n_out, t_out[:need_out], span_in=t_in.element_size() * need_in)
+    on_gpu(who, ins[0][0], dev)
+    return dev
+
+
+def _f(name, t, need, optional=False):
+    return (name, t, torch.float32, need, optional)
+
+
+def _rows_cols(who, **dims):
+    """rows-like dimensions (upper-case first letter B, M, T, R) in [1, 2^22], the others columns in [1, 2^14]"""
+    return tuple(int_arg(who, k.lower() if k == 'Rows' else k, v, 1, DOOR_MAX_GEMM_ROWS if k[0] in 'BMTR' else DOOR_MAX_GEMM_COLS) for k, v in dims.items())
+
+
+def _cols4(who, name, v):
+    if v % 4:
+        raise ValueError('%s: %s must be a multiple of 4, got %d' % (who, name, v))
+    return v
+
+
+def _bt(who, B, T):
+    if B * T > DOOR_MAX_GEMM_ROWS:
+        raise ValueError('%s: B T must be <= %d, got %d' % (who, DOOR_MAX_GEMM_ROWS, B * T))
+
+
+def debug_embedding(table, ids, out, rows, V, width):
+    """out (rows, width) = table (V, width) [clamp(ids)] (taco_debug_embedding); ids int32 (rows)."""
+    who = 'debug_embedding'
+    rows, V, width = _rows_cols(who, Rows=rows, V=V, width=width)
+    _cols4(who, 'width', width)
+    _typed_args(who, [_f('table', table, V * width), ('ids', ids, torch.int32, rows, False)], [_f('out', out, rows * width)])
+    _check(_lib.taco_debug_embedding(ptr(table), ptr(ids), ptr(out), rows, V, width, stream_ptr()), 'taco_debug_embedding')
+
+
+def debug_embedding_bwd(dout, ids, dtable, rows, V, width):
+    """dtable (V, width) += the rows of dout (rows, width) by clamped id (taco_debug_embedding_bwd); width <= 1024."""
+    who = 'debug_embedding_bwd'
+    rows, V = _rows_cols(who, Rows=rows, V=V)
+    width = _cols4(who, 'width', int_arg(who, 'width', width, 4, 1024))
+    _typed_args(who, [_f('dout', dout, rows * width), ('ids', ids, torch.int32, rows, False)], [_f('dtable', dtable, V * width)])
+    _check(_lib.taco_debug_embedding_bwd(ptr(dout), ptr(ids), ptr(dtable), rows, V, width, stream_ptr()), 'taco_debug_embedding_bwd')
+
+
+def debug_highway_combine(th, x, y, M):
+    """y (M, 128) = H T + x (1 - T) with th (M, 256) = [T | H] (taco_debug_highway_combine)."""
+    who = 'debug_highway_combine'
+    M, = _rows_cols(who, M=M)
+    _typed_args(who, [_f('th', th, M * 256), _f('x', x, M * 128)], [_f('y', y, M * 128)])
+    _check(_lib.taco_debug_highway_combine(ptr(th), ptr(x), ptr(y), M, stream_ptr()), 'taco_debug_highway_combine')
+
+
+def debug_highway_combine_bwd(th, x, dy, dth, dx, M):
+    """dth (M, 256), dx (M, 128) of the blend above from dy (M, 128) (taco_debug_highway_combine_bwd)."""
+    who = 'debug_highway_combine_bwd'
+    M, = _rows_cols(who, M=M)
+    _typed_args(who, [_f('th', th, M * 256), _f('x', x, M * 128), _f('dy', dy, M * 128)], [_f('dth', dth, M * 256), _f('dx', dx, M * 128)])
+    _check(_lib.taco_debug_highway_combine_bwd(ptr(th), ptr(x), ptr(dy), ptr(dth), ptr(dx), M, stream_ptr()), 'taco_debug_highway_combine_bwd')
+
+
+def debug_act_bwd(y, dy, dz, n, act, keep=None):
+    """dz = dy act'(y) [keep ? 2 : 0] over n elements (taco_debug_act_bwd); act 'none' | 'relu' | 'sigmoid' | 'tanh'; keep uint8 (n) or
+    None; dz may be dy itself (in place)."""
+    who = 'debug_act_bwd'
+    n = int_arg(who, 'n', n, 1, DOOR_MAX_FLAT)
+    if act not in _ACTS:
+        raise ValueError('%s: act must be one of %s, got %r' % (who, sorted(_ACTS), act))
+    _typed_args(who, [_f('y', y, n), _f('dy', dy, n), ('keep', keep, torch.uint8, n, True)], [_f('dz', dz, n)], alias=(('dy', 'dz'),))
+    _check(_lib.taco_debug_act_bwd(ptr(y), ptr(dy), ptr(keep), ptr(dz), n, _ACTS[act], stream_ptr()), 'taco_debug_act_bwd')
+
+
+def debug_affine_act_bwd(pre, gamma, dy, dz, dgamma, dbeta, M, N, act):
+    """The BN-affine backward (taco_debug_affine_act_bwd): pre, dy, dz (M, N); dgamma, dbeta (N) are added to; act 'none' | 'relu'."""
+    who = 'debug_affine_act_bwd'
+    M, N = _rows_cols(who, M=M, N=N)
+    if act not in ('none', 'relu'):
+        raise ValueError("%s: act must be 'none' or 'relu', got %r" % (who, act))
+    _typed_args(who, [_f('pre', pre, M * N), _f('gamma', gamma, N), _f('dy', dy, M * N)],
+                [_f('dz', dz, M * N), _f('dgamma', dgamma, N), _f('dbeta', dbeta, N)])
+    _check(_lib.taco_debug_affine_act_bwd(ptr(pre), ptr(gamma), ptr(dy), ptr(dz), ptr(dgamma), ptr(dbeta), M, N, _ACTS[act], stream_ptr()),
+           'taco_debug_affine_act_bwd')
+
+
+def debug_colsum_batched(x, out, B, T, N, ld=None):
+    """out (B, N) = the column sums of each sequence of T rows of x (B T, N; ld) (taco_debug_colsum_batched); overwritten."""
+    who = 'debug_colsum_batched'
+    B, T, N = _rows_cols(who, B=int_arg(who, 'B', B, 1, 65535), T=T, N=N)
+    _bt(who, B, T)
+    ld = _pitch(who, 'ld', ld, N)
+    _typed_args(who, [_f('x', x, _span(B * T, N, ld))], [_f('out', out, B * N)])
+    _check(_lib.taco_debug_colsum_batched(ptr(x), ld, ptr(out), B, T, N, stream_ptr()), 'taco_debug_colsum_batched')
+
+
+def debug_mask_rows(x, length, y, B, T, C_cols):
+    """y (B, T, C) = x where t < length[b], else 0 (taco_debug_mask_rows); length int32 (B)."""
+    who = 'debug_mask_rows'
+    B, T, C_cols = _rows_cols(who, B=B, T=T, C=C_cols)
+    _bt(who, B, T)
+    _cols4(who, 'C', C_cols)
+    _typed_args(who, [_f('x', x, B * T * C_cols), ('length', length, torch.int32, B, False)], [_f('y', y, B * T * C_cols)])
+    _check(_lib.taco_debug_mask_rows(ptr(x), ptr(length), ptr(y), B, T, C_cols, stream_ptr()), 'taco_debug_mask_rows')
+
+
+def debug_center_rows(x, length, out, B, T, C_cols):
+    """out (B, T, C) = x less its column means over the first clamp(length[b], 1, T) rows, 0 behind them (taco_debug_center_rows)."""
+    who = 'debug_center_rows'
+    B, T, C_cols = _rows_cols(who, B=int_arg(who, 'B', B, 1, 65535), T=T, C=C_cols)
+    _bt(who, B, T)
+    _cols4(who, 'C', C_cols)
+    _typed_args(who, [_f('x', x, B * T * C_cols), ('length', length, torch.int32, B, False)], [_f('out', out, B * T * C_cols)])
+    _check(_lib.taco_debug_center_rows(ptr(x), ptr(length), ptr(out), B, T, C_cols, stream_ptr()), 'taco_debug_center_rows')
+
+
+def debug_mask_pos(g, y, rows, cols, scale, ldg=None, ldy=None):
+    """in place g (rows, cols; ldg) = y (rows, cols; ldy) > 0 ? scale g : 0 (taco_debug_mask_pos)."""
+    who = 'debug_mask_pos'
+    rows, cols = _rows_cols(who, Rows=rows, cols=cols)
+    ldg, ldy = _pitch(who, 'ldg', ldg, cols), _pitch(who, 'ldy', ldy, cols)
+    _typed_args(who, [_f('y', y, _span(rows, cols, ldy))], [_f('g', g, _span(rows, cols, ldg))])
+    _check(_lib.taco_debug_mask_pos(ptr(g), ldg, ptr(y), ldy, rows, cols, float(scale), stream_ptr()), 'taco_debug_mask_pos')
+
+
+def debug_zero_tail_rows(x0, C0, length, B, Td, x1=None, C1=0):
+    """rows t >= length[b] of x0 (B, Td, C0) and, when given, x1 (B, Td, C1) become 0 in place (taco_debug_zero_tail_rows)."""
+    who = 'debug_zero_tail_rows'
+    B, Td, C0 = _rows_cols(who, B=B, Td=Td, C0=C0)
+    _bt(who, B, Td)
+    C1 = int_arg(who, 'C1', C1, 1, DOOR_MAX_GEMM_COLS) if x1 is not None else 0
+    _typed_args(who, [('length', length, torch.int32, B, False)], [_f('x0', x0, B * Td * C0), _f('x1', x1, B * Td * C1, True)])
+    _check(_lib.taco_debug_zero_tail_rows(ptr(x0), C0, ptr(x1), C1, ptr(length), B, Td, stream_ptr()), 'taco_debug_zero_tail_rows')
+
+
+def debug_add(a, b, y, n):
+    """y = a + b over n elements (taco_debug_add)."""
+    who = 'debug_add'
+    n = int_arg(who, 'n', n, 1, DOOR_MAX_FLAT)
+    _typed_args(who, [_f('a', a, n), _f('b', b, n)], [_f('y', y, n)])
+    _check(_lib.taco_debug_add(ptr(a), ptr(b), ptr(y), n, stream_ptr()), 'taco_debug_add')
+
+
+def debug_l1_loss(terms, parts, loss, out=None):
+    """The loss as taco_forward forms it (taco_debug_l1_loss).  terms: two entries, each None (the term is 0) or a dict with a, b
+    (M, N), M, N and optionally grad (M, N; ldg) and ldg; parts (2 x 512 block partials) and loss (3) are the caller's, out (3) optional."""
+    who = 'debug_l1_loss'
+    if not isinstance(terms, (list, tuple)) or len(terms) != 2 or all(t is None for t in terms):
+        raise ValueError('%s: terms must be a list of two dicts, at most one of them None' % who)
+    ins, outs, args = [], [], []
+    for i, t in enumerate(terms):
+        if t is None:
+            args += [None, None, None, 0, 0, 0]
+            continue
+        M, N = _rows_cols('%s: terms[%d]' % (who, i), M=t['M'], N=t['N'])
+        ldg = _pitch('%s: terms[%d]' % (who, i), 'ldg', t.get('ldg'), N)
+        ins += [_f('a%d' % i, t['a'], M * N), _f('b%d' % i, t['b'], M * N)]
+        outs += [_f('grad%d' % i, t.get('grad'), M * ldg, True)]
+        args += [ptr(t['a']), ptr(t['b']), ptr(t.get('grad')), ldg, M, N]
+    outs += [_f('parts', parts, 2 * LOSS_PARTS), _f('loss', loss, 3), _f('out', out, 3, True)]
+    _typed_args(who, ins, outs)
+    _check(_lib.taco_debug_l1_loss(*args, ptr(parts), ptr(loss), ptr(out), stream_ptr()), 'taco_debug_l1_loss')
+
+
+def debug_transpose_batch(jobs):
+    """Up to 96 (kMaxTransposeBatch) transposes of one launch (taco_debug_transpose_batch).  jobs: dicts with src (taps, K, N; ldi), dst
+    (taps, N, K; ldo; tap order reversed), taps, K, N and optionally ldi, ldo (0 / missing: dense; a pitched job has taps == 1)."""
+    who = 'debug_transpose_batch'
+    if not isinstance(jobs, (list, tuple)) or not 1 <= len(jobs) <= MAX_TRANSPOSE_BATCH:
+        raise ValueError('%s: jobs must be a list of 1 to %d dicts' % (who, MAX_TRANSPOSE_BATCH))
+    ins, outs, rows = [], [], []
+    for i, j in enumerate(jobs):
+        w = '%s: jobs[%d]' % (who, i)
+        taps = int_arg(w, 'taps', j['taps'], 1, 64)
+        K, N = _rows_cols(w, K=j['K'], N=j['N'])
+        ldi, ldo = int_arg(w, 'ldi', j.get('ldi') or 0, 0, _INT_MAX), int_arg(w, 'ldo', j.get('ldo') or 0, 0, _INT_MAX)
+        if (ldi and ldi < N) or (ldo and ldo < K):
+            raise ValueError('%s: ldi must be 0 or >= %d and ldo 0 or >= %d, got %d and %d' % (w, N, K, ldi, ldo))
+        if (ldi or ldo) and taps != 1:
+            raise ValueError('%s: a job with a pitch has taps == 1, got %d' % (w, taps))
+        ins.append(_f('src[%d]' % i, j['src'], _span(taps * K, N, ldi or N)))
+        outs.append(_f('dst[%d]' % i, j['dst'], _span(taps * N, K, ldo or K)))
+        rows.append((taps, K, N, ldi, ldo))
+    _typed_args(who, ins, outs)
+    n = len(jobs)
+    col = lambda k: (C.c_int * n)(*[r[k] for r in rows])
+    pitched = any(r[3] or r[4] for r in rows)
+    _check(_lib.taco_debug_transpose_batch(n, _ptr_table([j['src'] for j in jobs]), _ptr_table([j['dst'] for j in jobs]), col(0), col(1), col(2),
+                                           col(3) if pitched else None, col(4) if pitched else None, stream_ptr()), 'taco_debug_transpose_batch')
+
+
+def debug_sumsq(x, n, out):
+    """out[0 .. 256) = the per-block partial sums of squares of x[0 .. n) that clip+Adam adds up (taco_debug_sumsq); x 16-byte aligned."""
+    who = 'debug_sumsq'
+    n = int_arg(who, 'n', n, 1, DOOR_MAX_FLAT)
+    _typed_args(who, [_f('x', x, n)], [_f('out', out, SUMSQ_PARTS)])
+    if x.data_ptr() % 16:
+        raise ValueError('%s: x must be 16-byte aligned' % who)
+    _check(_lib.taco_debug_sumsq(ptr(x), n, ptr(out), stream_ptr()), 'taco_debug_sumsq')
 
 
 def forward(shape, params, text, text_length, mel, stft, masks, s2s, out, align, loss, workspace, speaker=None):
