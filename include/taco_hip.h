@@ -1182,6 +1182,63 @@ int taco_wave_resample(const uint8_t* pcm, int64_t row_bytes, int width, int cha
 /* Bernoulli(p_keep) bytes from a counter-based hash RNG (replaces TF's dropout / Bernoulli sampler state). */
 int taco_fill_bernoulli(uint8_t* out, int64_t n, float p_one, uint64_t seed, void* stream);
 
+/* ---- training monitor (monitor.hip) -------------------------------------------------------------------------------- */
+/* Statistics and a histogram of each of n segments of ONE fp32 buffer, in one call: what the reference's tf.summary.histogram
+ * sites (models/tacotron.py:129,139,152, models/ops.py:73-130) show of eight activations, here for any named row of
+ * taco_workspace_table and for every tensor of taco_param_table in the parameter, gradient and Adam buffers.
+ *   base      fp32 on the device, 16-byte aligned; segment i is the floats [offset_i, offset_i + size_i) of it
+ *   counts    (n, 6) int64: size, finite, NaN, +Inf, -Inf, exact zeros (+0 and -0)
+ *   moments   (n, 5) fp64 over the FINITE elements: sum, sumsq, min, max, absmax.  min, max and absmax are the fp32 values widened
+ *             (exact; -0 orders below +0); a square is formed in fp64 from the fp32 value (48 bits of product: exact) and only the
+ *             sums round.  With no finite element the row is 0, 0, +inf, -inf, 0
+ *   hist      (n, NB) int64: the finite elements in sign-symmetric logarithmic buckets, by integer arithmetic on the bits alone:
+ *             u = bits(x) & 0x7fffffff, k = u >> (23 - s), s = sub_bits in 0..3;  lo = (127 + e_lo) << s,
+ *             hi = ((127 + e_hi + 1) << s) - 1;  m = 0 when k < lo (zeros, subnormals, everything below 2^e_lo), else
+ *             m = min(k, hi) - lo + 1 (the top bucket takes everything from its lower edge up);  Nm = (e_hi - e_lo + 1) << s,
+ *             NB = 2 Nm + 1;  the bin is Nm for m = 0, Nm + m for a positive and Nm - m for a negative value.
+ *             -126 <= e_lo <= e_hi <= 127; 2^s buckets per octave
+ * The segments are static for a model, so the work list is a PLAN the host builds once:
+ *   taco_tensor_stats_plan_bytes(segments, n)   bytes of the blob for `segments` = (n, 2) int64 in HOST memory, (offset, size) in
+ *             floats; TACO_EINVAL for NULL, n outside 1..TACO_STATS_MAX_SEGMENTS, a negative offset or size
+ *   taco_tensor_stats_plan(segments, n, base_floats, plan, plan_bytes, &n_items)   writes the blob into HOST memory: a 32-byte header
+ *             (4 int64: a tag, n, n_items, base_floats), the segments with their first work item and chunk count, then the work
+ *             items (segment, chunk).  A segment that is not inside [0, base_floats) is refused.  The caller copies the blob to the
+ *             device (8-byte aligned) and keeps the header
+ *   taco_tensor_stats_workspace_bytes(n, n_items, NB)   bytes of the workspace (8-byte aligned): one record and one histogram row
+ *             of NB 32-bit counts per work item
+ *   taco_tensor_stats(base, plan_dev, plan_header, n, n_items, e_lo, e_hi, sub_bits, counts, moments, hist, workspace, stream)
+ *             plan_dev the blob on the device, plan_header its first 32 bytes in HOST memory -- all the call reads on the host; the
+ *             descriptors and the work list are read on the device only
+ * ORDER OF THE SUMS.  Segment i is laid on positions p = (offset_i & 3) + j, j the element's index in the segment: position 0 is the
+ * 16-byte boundary at or below the segment's first float.  Chunk c is the positions [c C, (c + 1) C), C = TACO_STATS_CHUNK; a work
+ * item is one chunk and belongs to one wave.  Within a chunk, partial l of 64 adds the elements of the position groups
+ * [4 g, 4 g + 4) with g mod 64 == l in increasing position (a group inside the segment is one 16-byte load, a segment's two edge
+ * groups scalar loads of its own floats only); the 64 partials meet in the tree v_l += v_(l + 32), then 16, 8, 4, 2, 1.  The chunks'
+ * sums meet 64 at a time in chunk order by the same tree (absent chunks count as +0), and the tiles are added to a running total
+ * in order.  All of it in fp64, nothing fused but the exact square into its sum.  The cut and the order follow from (offset_i,
+ * size_i) alone, never from a neighbour.
+ * HISTOGRAM FORM: partial-and-fold.  A wave counts into a histogram of its own in LDS (integer adds); the waves of a workgroup that
+ * hold consecutive chunks of one segment add theirs and write one row of 32-bit counts into the workspace, and the second launch
+ * adds the rows of a segment as integers -- exact in any order.  No float atomics, no global atomics, no memset.
+ *   - every element of counts, moments and hist is written and nothing outside them; the workspace may hold arbitrary bytes;
+ *   - floats of base outside every segment are never read and may hold NaN; segments may overlap, may be empty and may start at
+ *     any float offset;
+ *   - the same arguments give the same bits, and the row of segment i is bit-identical to a call with that segment alone.
+ * No allocation, no host synchronisation, no workgroup waits for another one: two stream-ordered launches, graph-capturable.
+ * NULL pointers, n outside 1..TACO_STATS_MAX_SEGMENTS, a negative n_items, a bad exponent range or sub_bits, a header that does not
+ * carry the tag, n and n_items, a base that is not 16-byte aligned and a plan_dev or workspace that is not 8-byte aligned return
+ * TACO_EINVAL, with a message "tensor_stats: ...", before anything is enqueued; the size functions return TACO_EINVAL.  TACO_VERSION
+ * did not change with these entry points: detect them by the symbol.
+ * Not here: quantiles, per-row (batch element) statistics, fp16 / bf16 buffers. */
+#define TACO_STATS_CHUNK        8192    /* C: positions per work item */
+#define TACO_STATS_MAX_SEGMENTS 4096
+#define TACO_STATS_MAX_BINS     4065    /* NB of e_lo = -126, e_hi = 127, sub_bits = 3 */
+int64_t taco_tensor_stats_plan_bytes(const int64_t* segments, int n);
+int taco_tensor_stats_plan(const int64_t* segments, int n, int64_t base_floats, void* plan, int64_t plan_bytes, int32_t* n_items);
+int64_t taco_tensor_stats_workspace_bytes(int n, int n_items, int NB);
+int taco_tensor_stats(const float* base, const void* plan_dev, const void* plan_header, int n, int n_items, int e_lo, int e_hi,
+                      int sub_bits, int64_t* counts, double* moments, int64_t* hist, void* workspace, void* stream);
+
 /* ---- measurement --------------------------------------------------------------------------------------------- */
 /* Launch-level timing with hipEventRecord pairs on the launch stream (rings of 4096 event pairs per category; no
  * synchronisation at record time).  Categories: 0 = persistent decoder forward kernel, 1 = decoder backward kernel,

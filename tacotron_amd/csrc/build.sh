@@ -12,7 +12,7 @@ pids=()
 # max-ilp / max-memory-clause / iterative-minreg are slower, the strategy does nothing for bigru.hip.
 D3FLAGS="-mllvm -amdgpu-sched-strategy=iterative-maxocc"
 # every object but the decoder pair, which the three libraries take in different builds
-COMMON="gemm gemm2 vocoder features elementwise align_path f0_viterbi phase_init loudness limiter dtw bigru highway prenet layout stream model"
+COMMON="gemm gemm2 vocoder features elementwise align_path f0_viterbi phase_init loudness limiter monitor dtw bigru highway prenet layout stream model"
 for f in $COMMON decoder; do
   hipcc $FLAGS -c $f.hip -o ../../build/obj/$f.o &
   pids+=($!)

@@ -6,6 +6,7 @@ the import of this module raises, and every entry point raises `TacoError` on a 
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -186,6 +187,10 @@ EXPORTS = {
     'taco_audio_features': (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'taco_wave_resample': (C.c_int, [_P, C.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     'taco_fill_bernoulli': (C.c_int, [_P, C.c_int64, C.c_float, C.c_uint64, _P]),
+    'taco_tensor_stats_plan_bytes': (C.c_int64, [C.POINTER(C.c_int64), _I]),
+    'taco_tensor_stats_plan': (C.c_int, [C.POINTER(C.c_int64), _I, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int32)]),
+    'taco_tensor_stats_workspace_bytes': (C.c_int64, [_I, _I, _I]),
+    'taco_tensor_stats': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'taco_profile_enable': (C.c_int, [_I]),
     'taco_debug_last_cluster': (C.c_int, [_I]),
     'taco_profile_read': (C.c_int, [_I, C.POINTER(C.c_float), _I]),
@@ -2200,6 +2205,112 @@ def wave_resample(pcm, rows, taps, width, channels, P, Q, n_left, n_right, L=Non
 def fill_bernoulli(out, p_one, seed):
     _check(_lib.taco_fill_bernoulli(ptr(out), out.numel(), float(p_one), int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ptr()),
            'taco_fill_bernoulli')
+
+
+STATS_CHUNK = 8192          # TACO_STATS_CHUNK: the positions of a segment that one wave of taco_tensor_stats reads
+STATS_MAX_SEGMENTS = 4096   # TACO_STATS_MAX_SEGMENTS
+STATS_COUNTS = ('size', 'finite', 'nan', 'pinf', 'ninf', 'zeros')   # columns of counts (include/taco_hip.h taco_tensor_stats)
+STATS_MOMENTS = ('sum', 'sumsq', 'min', 'max', 'absmax')            # columns of moments
+STATS_E_LO, STATS_E_HI, STATS_SUB_BITS = -24, 15, 2                 # the default buckets: 2^-24 .. 2^16, four per octave, NB = 321
+
+
+class TensorStats(collections.namedtuple('TensorStats', 'counts moments hist')):
+    """What tensor_stats returns: counts (n, 6) int64, moments (n, 5) fp64, hist (n, NB) int64, device tensors."""
+    __slots__ = ()
+
+
+class TensorStatsPlan(object):
+    """The work list of tensor_stats for one list of segments of one buffer: `dev` the blob on the device (int64 words), `header` its
+    first 32 bytes on the host (the only thing a call reads there), n segments, n_items work items, base_floats the floats the
+    buffer must hold, `segments` the (offset, size) pairs."""
+
+    def __init__(self, dev, header, n, n_items, base_floats, segments):
+        self.dev, self.header, self.n, self.n_items, self.base_floats, self.segments = dev, header, n, n_items, base_floats, segments
+
+
+def _stats_buckets(who, e_lo, e_hi, sub_bits):
+    e_lo = int_arg(who, 'e_lo', e_lo, -126, 127)
+    e_hi = int_arg(who, 'e_hi', e_hi, e_lo, 127)
+    sub_bits = int_arg(who, 'sub_bits', sub_bits, 0, 3)
+    return e_lo, e_hi, sub_bits, 2 * ((e_hi - e_lo + 1) << sub_bits) + 1
+
+
+def tensor_stats_plan(segments, base_floats, device='cuda') -> TensorStatsPlan:
+    """The plan of tensor_stats (include/taco_hip.h taco_tensor_stats_plan) for `segments`, a host sequence of (offset, size) pairs in
+    floats of a buffer of base_floats floats: built on the host, uploaded once.  1 .. STATS_MAX_SEGMENTS segments, each inside
+    [0, base_floats); they may overlap and may be empty."""
+    who = 'tensor_stats_plan'
+    try:
+        segs = [(int_arg(who, 'a segment offset', o, 0), int_arg(who, 'a segment size', s, 0)) for o, s in segments]
+    except (TypeError, ValueError) as e:
+        if isinstance(e, ValueError) and str(e).startswith(who):
+            raise
+        raise ValueError('%s: segments must be a sequence of (offset, size) pairs, got %r' % (who, segments)) from None
+    n = int_arg(who, 'the number of segments', len(segs), 1, STATS_MAX_SEGMENTS)
+    base_floats = int_arg(who, 'base_floats', base_floats, 0)
+    for i, (o, s) in enumerate(segs):
+        if o + s > base_floats:
+            raise ValueError('%s: segment %d = (offset %d, size %d) is outside [0, %d)' % (who, i, o, s, base_floats))
+    dev = torch.device(device)   # (tensor_stats is the judge of the device: the plan goes where its buffer is)
+    flat =(C.c_int64 * (2 * n))(*[v for seg in segs for v in seg])
+    nbytes = _lib.taco_tensor_stats_plan_bytes(flat, n)
+    if nbytes < 0:
+        raise TacoError('taco_tensor_stats_plan_bytes: bad arguments (rc=%d)' % nbytes)
+    blob = np.zeros(nbytes // 8, dtype=np.int64)   # (every part of the blob is whole 8-byte words)
+    n_items = C.c_int32(0)
+    _check(_lib.taco_tensor_stats_plan(flat, n, base_floats, C.c_void_p(blob.ctypes.data), nbytes, C.byref(n_items)), 'taco_tensor_stats_plan')
+    return TensorStatsPlan(torch.from_numpy(blob).to(dev), blob[:4].copy(), n, int(n_items.value), base_floats, segs)
+
+
+def tensor_stats_workspace_bytes(n, n_items, NB) -> int:
+    return _size('taco_tensor_stats_workspace_bytes', n, n_items, NB)
+
+
+def tensor_stats_edges(e_lo=STATS_E_LO, e_hi=STATS_E_HI, sub_bits=STATS_SUB_BITS):
+    """The NB + 1 edges of tensor_stats' buckets as float64, ascending: bin b holds the finite x with edges[b] <= x < edges[b + 1] for
+    the positive bins, edges[b] < x <= edges[b + 1] for the negative ones, and the centre bin is the open interval between its two
+    edges -2^e_lo and 2^e_lo; the outermost edges are -inf and +inf (the top buckets are open-ended).  A positive bucket m opens at
+    the fp32 value with the bits (lo + m - 1) << (23 - sub_bits): 2^e (1 + f / 2^sub_bits)."""
+    e_lo, e_hi, s, NB = _stats_buckets('tensor_stats_edges', e_lo, e_hi, sub_bits)
+    Nm = (NB - 1) // 2
+    pos = np.array([math.ldexp(1.0 + (m % (1 << s)) / float(1 << s), e_lo + (m >> s)) for m in range(Nm)], dtype=np.float64)
+    return np.concatenate([[-np.inf], -pos[::-1], pos, [np.inf]])
+
+
+def tensor_stats(base, plan, e_lo=STATS_E_LO, e_hi=STATS_E_HI, sub_bits=STATS_SUB_BITS, counts=None, moments=None, hist=None, work=None):
+    """Statistics and histograms of the plan's segments of `base` in one call (include/taco_hip.h taco_tensor_stats): base a
+    flat (1-d) fp32 tensor of at least plan.base_floats floats, 16-byte aligned, plan a TensorStatsPlan (tensor_stats_plan) ->
+    TensorStats(counts (n, 6) int64 in the order STATS_COUNTS, moments (n, 5) fp64 in the order STATS_MOMENTS over the finite
+    elements, hist (n, NB) int64 in sign-symmetric log buckets from 2^e_lo to 2^(e_hi + 1), 2^sub_bits per octave,
+    NB = 2 ((e_hi - e_lo + 1) << sub_bits) + 1; tensor_stats_edges gives their edges).  Two launches on the current stream, no copy,
+    no synchronisation.  counts / moments / hist / work: the caller's own buffers (work: uint8,
+    tensor_stats_workspace_bytes(plan.n, plan.n_items, NB) bytes); default: fresh ones."""
+    who = 'tensor_stats'
+    if not isinstance(plan, TensorStatsPlan):
+        raise ValueError('%s: plan must be a TensorStatsPlan (tensor_stats_plan), got a %s' % (who, type(plan).__name__))
+    floats, = tensor_arg(who, 'base', base, torch.float32, ('floats',))
+    if floats < plan.base_floats:
+        raise ValueError('%s: base holds %d floats, the plan was built for %d' % (who, floats, plan.base_floats))
+    dev = base.device
+    e_lo, e_hi, sub_bits, NB = _stats_buckets(who, e_lo, e_hi, sub_bits)
+    if plan.dev.device != dev:
+        raise ValueError('%s: the plan is on %s, base on %s' % (who, plan.dev.device, dev))
+    counts = _own_or_given(counts, (plan.n, len(STATS_COUNTS)), torch.int64, dev, who + ': counts')
+    moments = _own_or_given(moments, (plan.n, len(STATS_MOMENTS)), torch.float64, dev, who + ': moments')
+    hist = _own_or_given(hist, (plan.n, NB), torch.int64, dev, who + ': hist')
+    if work is not None:
+        tensor_arg(who, 'work', work, torch.uint8, ('bytes',), dev)
+    on_gpu(who, 'base', dev)
+    if base.data_ptr() % 16:
+        raise ValueError('%s: base must be 16-byte aligned' % who)
+    need = tensor_stats_workspace_bytes(plan.n, plan.n_items, NB)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif work.numel() < need or work.data_ptr() % 8:
+        raise ValueError('%s: work must hold %d bytes and be 8-byte aligned, got %d' % (who, need, work.numel()))
+    _check(_lib.taco_tensor_stats(ptr(base), ptr(plan.dev), C.c_void_p(plan.header.ctypes.data), plan.n, plan.n_items, e_lo, e_hi,
+                                  sub_bits, ptr(counts), ptr(moments), ptr(hist), ptr(work), stream_ptr()), 'taco_tensor_stats')
+    return TensorStats(counts, moments, hist)
 
 
 def last_cluster(which: int) -> int:

@@ -12,6 +12,27 @@ from . import lib
 from .params import ParamBuffer
 
 
+# the training monitor (Tacotron.monitor_sites): the buffers read after the forward pass and after the update, and the workspace row
+# (under the enc. / post. prefix) of each histogram site of the reference's CBHG (models/ops.py:73-130)
+MONITOR_FORWARD = ('workspace', 'seq2seq_output', 'output')
+MONITOR_UPDATE = ('params', 'grads', 'adam_m', 'adam_v')
+MONITOR_ROWS = (('conv_bank', 'pool'), ('conv_proj_pre_bn', 'pj2pre'), ('conv_res', 'res'), ('highway_out', 'h4'), ('encoded', 'out'))
+
+
+def monitor_sites(shape):
+    """Tacotron.monitor_sites for a training model of `shape` (a lib.TacoShape); needs no device."""
+    table = lib.param_table(shape)
+    rows = {name: (off, size) for name, off, size, _ in lib.workspace_table(shape, True)}
+    sites = {'workspace': [('pre_net_out',) + rows['enc.p2']]}
+    for scope, pre in (('encoder', 'enc.'), ('post', 'post.')):
+        sites['workspace'] += [('%s/%s' % (scope, name),) + rows[pre + row] for name, row in MONITOR_ROWS]
+    sites['seq2seq_output'] = [('seq2seq_output', 0, shape.B * shape.Td * 80 * shape.r)]
+    sites['output'] = [('output', 0, shape.B * shape.Td * 1025 * shape.r)]
+    for buf, group in (('params', 'param'), ('grads', 'grad'), ('adam_m', 'adam_m'), ('adam_v', 'adam_v')):
+        sites[buf] = [('%s/%s' % (group, name), off, size) for name, off, size, _ in table]
+    return sites
+
+
 class Tacotron(object):
     ESCALATE_WINDOW = 2000   # steps: two exchange time-outs closer than this escalate the decoder mode (check())
 
@@ -44,6 +65,9 @@ class Tacotron(object):
         self._align_scores = None         # (counts, means) of alignment_scores(), allocated at its first call
         self._align_path = None           # (path, dur, counts, mass, workspace) of alignment_path(), allocated at its first call
         self._mel_eval = None             # the tensors of predicted_mel() / mel_distortion(), allocated at their first call
+        self._monitor = None              # plans, row ranges and workspace of monitor_stats(), built at its first call
+        self.monitor_result = None        # lib.TensorStats over monitor_names, on the device (step(monitor=True), monitor_stats())
+        self.monitor_names = None
         self.mel_mean = self.mel_std = None   # (80 r) statistics the corpus's mel targets were standardised with; None: identity
         self._loss = torch.zeros(3, device=dev)
         self.workspace = torch.empty(lib.workspace_bytes(self.shape, train) // 4, dtype=torch.float32, device=dev)
@@ -153,16 +177,75 @@ class Tacotron(object):
         lib.clip_adam_step(self.params.flat, self.grads, self.adam_m, self.adam_v, lr, self.config.cap_grads,
                            self.global_step, self._scratch, self._gnorm, self._err)
 
-    def step(self, lr=None, masks='draw'):
+    def step(self, lr=None, masks='draw', monitor=False):
         """One `sess.run(train_op)`: forward + backward (+ gradient all-reduce, overlapped with the backward pass) +
-        clip + Adam.  Everything is enqueued on the current stream; nothing is copied to the host."""
+        clip + Adam.  Everything is enqueued on the current stream; nothing is copied to the host.
+        monitor: the training monitor (monitor_sites, lib.tensor_stats).  The activation sites are read between the forward and the
+        backward pass, which may reuse workspace rows; the parameters, the gradients and both Adam slots AFTER the update: the update
+        reads the gradient buffer and never writes it, so what is seen there is the (reduced) gradient the step used, next to the
+        parameters and slots it left.  Seven calls, into `monitor_result`, which stays on the device.  False: not one launch, copy
+        or synchronisation more than before."""
         if masks == 'draw':
             masks = self.draw_masks()
         self.forward(masks)
+        if monitor:
+            self.monitor_stats(MONITOR_FORWARD)
         self.backward()
         if self.reducer is not None:
             self.reducer.reduce_after_backward(self)
         self.apply_gradients(self.lr if lr is None else lr)
+        if monitor:
+            self.monitor_stats(MONITOR_UPDATE)
+
+    # -- training monitor -----------------------------------------------------------------------------------
+    def monitor_sites(self):
+        """The named segments the monitor reads, per buffer: {buffer: [(name, offset, size)]} in floats of that buffer, the buffers
+        in the order MONITOR_FORWARD + MONITOR_UPDATE.  `params`, `grads`, `adam_m` and `adam_v` hold every tensor of
+        lib.param_table as param/<name>, grad/<name>, adam_m/<name> and adam_v/<name>; `workspace` holds the reference's
+        tf.summary.histogram sites (models/tacotron.py:129, models/ops.py:73-130) under its names, as rows of lib.workspace_table
+        (MONITOR_ROWS); `seq2seq_output` and `output` (tacotron.py:139,152) are the model's own tensors.  The reference's conv_proj
+        has no buffer here: pj2pre is the projection in front of its batch-norm affine and `res` already holds the residual sum,
+        so the former is reported, as conv_proj_pre_bn."""
+        assert self.train, 'monitor_sites: a training model'
+        return monitor_sites(self.shape)
+
+    def _monitor_state(self, e_lo, e_hi, sub_bits):
+        """Plans (once per model), the three result tensors over all sites and one workspace (once per bucket choice)"""
+        m = self._monitor
+        if m is None:
+            sites = self.monitor_sites()
+            bufs = {'params': self.params.flat, 'grads': self.grads, 'adam_m': self.adam_m, 'adam_v': self.adam_v,
+                    'workspace': self.workspace, 'seq2seq_output': self.seq2seq_output.view(-1), 'output': self.output.view(-1)}
+            m = self._monitor = {'plans': {}, 'rows': {}, 'bufs': bufs, 'buckets': None}
+            at = 0
+            for buf in MONITOR_FORWARD + MONITOR_UPDATE:
+                m['plans'][buf] = lib.tensor_stats_plan([(o, s) for _, o, s in sites[buf]], bufs[buf].numel(), self.device)
+                m['rows'][buf] = (at, at + len(sites[buf]))
+                at += len(sites[buf])
+            self.monitor_names = [name for buf in MONITOR_FORWARD + MONITOR_UPDATE for name, _, _ in sites[buf]]
+        if m['buckets'] != (e_lo, e_hi, sub_bits):
+            N, dev = len(self.monitor_names), self.device
+            NB = len(lib.tensor_stats_edges(e_lo, e_hi, sub_bits)) - 1
+            self.monitor_result = lib.TensorStats(torch.zeros(N, len(lib.STATS_COUNTS), dtype=torch.int64, device=dev),
+                                                  torch.zeros(N, len(lib.STATS_MOMENTS), dtype=torch.float64, device=dev),
+                                                  torch.zeros(N, NB, dtype=torch.int64, device=dev))
+            need = max(lib.tensor_stats_workspace_bytes(p.n, p.n_items, NB) for p in m['plans'].values())
+            m['work'] = torch.empty(need, dtype=torch.uint8, device=dev)   # (one for all: the calls follow each other on the stream)
+            m['buckets'] = (e_lo, e_hi, sub_bits)
+        return m
+
+    def monitor_stats(self, buffers=None, e_lo=lib.STATS_E_LO, e_hi=lib.STATS_E_HI, sub_bits=lib.STATS_SUB_BITS):
+        """lib.tensor_stats of the sites of `buffers` (names of monitor_sites; None: all seven) as the buffers are NOW, one call per
+        buffer on the current stream, into the rows of `monitor_result` = lib.TensorStats(counts (N, 6), moments (N, 5), hist (N, NB))
+        that belong to them; row i is `monitor_names[i]`.  The tensors are allocated once and returned every time; rows of buffers
+        not asked for keep what an earlier call left (zeros at first).  No copy and no synchronisation."""
+        m = self._monitor_state(e_lo, e_hi, sub_bits)
+        res = self.monitor_result
+        for buf in (MONITOR_FORWARD + MONITOR_UPDATE if buffers is None else buffers):
+            lo, hi = m['rows'][buf]
+            lib.tensor_stats(m['bufs'][buf], m['plans'][buf], e_lo, e_hi, sub_bits, res.counts[lo:hi], res.moments[lo:hi], res.hist[lo:hi],
+                             m['work'])
+        return res
 
     def check(self):
         """Raises TacoError if a decoder kernel reported a timed-out cluster exchange (the kernels never hang: every spin is

@@ -5,6 +5,10 @@ Without a preprocessed corpus under data/<set>/ it trains on synthetic Nancy-sha
 --align-log (opt-in): the alignment monitor.  At every log step the batch's attention is scored on the device
 (Tacotron.alignment_scores) and a second line gives the batch means of focus, covered / L, back, skip and pad_mass and the number of
 rows alignment.flags marks; the listening sample gets attention_<step>.png and attention_<step>_scores.npy next to its .npy.
+--monitor (opt-in): the training monitor.  The log steps also compute, on the device, statistics and log-bucket histograms of every
+parameter, gradient and Adam slot and of the activations the reference histograms (Tacotron.step(monitor=True), lib.tensor_stats);
+one more line names the largest gradient RMS and lr |grad| / |param|, the share of zeros behind the encoder pre-net and the tensors
+that hold non-finite values, and monitor/monitor_<step>.npz keeps everything.
 --holdout N (default 0): the last N utterances are never drawn, so that tacotron_amd.evaluate can score checkpoints on them."""
 from __future__ import annotations
 
@@ -59,6 +63,54 @@ def align_line(counts, means, text_length, Tt):
     flagged = sum(1 for c, m, l in zip(counts, means, L) if flags(c, m, l))
     return ('align focus %.3f covered %.3f back %.2f skip %.2f pad_mass %.4f flagged %d/%d' %
             (means[:, 0].mean(), (counts[:, 5] / L).mean(), counts[:, 3].mean(), counts[:, 4].mean(), means[:, 1].mean(), flagged, len(L)))
+
+
+def monitor_nonfinite(names, counts):
+    """The names of the monitor's tensors that hold a NaN or an infinity, in the monitor's order: counts (N, 6) as lib.STATS_COUNTS."""
+    counts = np.asarray(counts)
+    return [str(n) for n, c in zip(names, counts) if c[2] + c[3] + c[4] > 0]
+
+
+def monitor_line(names, counts, moments, lr):
+    """The --monitor line of one log step from host arrays: names (N), counts (N, 6) and moments (N, 5) of Tacotron.monitor_result
+    (lib.STATS_COUNTS / lib.STATS_MOMENTS; sums over the finite elements).  It gives the largest per-tensor gradient RMS with its
+    name; the largest lr |grad| / |param| with its name -- a PROXY for the update ratio: the true Adam update (m / (sqrt(v) + eps),
+    clipped) is not computed; the share of exact zeros in pre_net_out (dropout and dead ReLUs alike); and the number of tensors that
+    hold non-finite values with the first three names."""
+    names = [str(n) for n in names]
+    counts, moments = np.asarray(counts), np.asarray(moments, dtype=np.float64)
+    row = {n: i for i, n in enumerate(names)}
+    rms, ratio = (0.0, '-'), (0.0, '-')
+    for n, i in row.items():
+        if not n.startswith('grad/'):
+            continue
+        g2, fin = moments[i, 1], counts[i, 1]
+        if fin > 0 and math.sqrt(g2 / fin) > rms[0]:
+            rms = (math.sqrt(g2 / fin), n[5:])
+        p = row.get('param/' + n[5:])
+        if p is not None and moments[p, 1] > 0.0:
+            q = lr * math.sqrt(g2 / moments[p, 1])
+            if q > ratio[0]:
+                ratio = (q, n[5:])
+    zeros = '-'
+    if 'pre_net_out' in row and counts[row['pre_net_out'], 0] > 0:
+        zeros = '%.1f%%' % (100.0 * counts[row['pre_net_out'], 5] / counts[row['pre_net_out'], 0])
+    bad = monitor_nonfinite(names, counts)
+    return ('monitor grad-rms max %.3e (%s) lr|g|/|w| max %.3e (%s) pre_net_out zeros %s non-finite %d%s' %
+            (rms[0], rms[1], ratio[0], ratio[1], zeros, len(bad), (': ' + ', '.join(bad[:3]) + (', ...' if len(bad) > 3 else '')) if bad else ''))
+
+
+def save_monitor(model, out_dir, step, host=None):
+    """monitor_<step>.npz under out_dir: names, counts, moments, hist of model.monitor_result, the NB + 1 bucket edges and the three
+    bucket parameters.  host: the (counts, moments, hist) arrays when they have been read already."""
+    from . import lib
+    os.makedirs(out_dir, exist_ok=True)
+    counts, moments, hist = host if host is not None else (t.cpu().numpy() for t in model.monitor_result)
+    e_lo, e_hi, sub_bits = lib.STATS_E_LO, lib.STATS_E_HI, lib.STATS_SUB_BITS
+    path = os.path.join(out_dir, 'monitor_%d.npz' % step)
+    np.savez(path, names=np.array(model.monitor_names), counts=counts, moments=moments, hist=hist,
+             edges=lib.tensor_stats_edges(e_lo, e_hi, sub_bits), e_lo=e_lo, e_hi=e_hi, sub_bits=sub_bits)
+    return path
 
 
 def load_corpus(data_path, seed=0):
@@ -134,8 +186,14 @@ def holdout_draw(n, holdout, batch_size, seed):
     return lambda step: rng.integers(n - holdout, size=int(batch_size))
 
 
-def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False, holdout=0):
-    """holdout: the last N utterances of the corpus are never drawn (tacotron_amd.evaluate scores a checkpoint on them); 0: every
+def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False, holdout=0, monitor=False):
+    """monitor: the training monitor.  The log steps (global step a multiple of log_every) run with Tacotron.step(monitor=True):
+    statistics and histograms of every parameter, gradient and Adam slot and of the reference's histogram sites, computed on the
+    device (lib.tensor_stats).  Rank 0 reads them at the log step's synchronisation point, writes
+    log/<save_path>/monitor/monitor_<step>.npz (save_monitor) and prints one more line (monitor_line); before `loss exploded` it
+    names every tensor that holds a non-finite value.  With several ranks the gradients are the reduced ones, the activations
+    rank 0's own.  No launch, copy or synchronisation is added to any other step.
+    holdout: the last N utterances of the corpus are never drawn (tacotron_amd.evaluate scores a checkpoint on them); 0: every
     utterance is drawn, as before.
     align_log: score the batch's attention on the device at every log step and print a second line (module docstring); no launch,
     copy or synchronisation is added to any other step.
@@ -198,12 +256,16 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
                 print('restored %s (global_step %d)' % (path, model.global_step))
     lr = config.init_lr
     import time
+    mon_step, mon_lr, mon_host = None, lr, None           # the step model.monitor_result belongs to, and its host copy once read
     t_mark, s_mark, step = None, 0, -1                    # throughput of the host loop itself (reported when the loop ends)
     try:
         for step in range(num_steps):
             model.set_inputs(next_batch(step))                # device tensors from the feeder: a pointer swap
-            model.step(lr)
+            mon = monitor and (model.global_step + 1) % log_every == 0
+            model.step(lr, monitor=mon)
             gs = model.global_step
+            if mon:
+                mon_step, mon_lr = gs, lr
             if step == 10:                                    # (past the first steps' one-off costs: lazy allocations, LDS attribute calls)
                 torch.cuda.synchronize()
                 t_mark, s_mark = time.perf_counter(), step
@@ -217,16 +279,25 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
                         raise
                     print('WARNING (rank %d): %s -- continuing' % (rank, e))   # check() moved to a more conservative decoder mode
                 if rank == 0:
-                    # tacotron.py:162-164: the summaries 'loss', 'seq2seq_loss', 'output_loss' (scalars only)
+                    # tacotron.py:162-164: the summaries 'loss', 'seq2seq_loss', 'output_loss' (the scalars; --monitor adds the histogram sites below)
                     s2s_l, out_l = (float(x) for x in model.loss_terms)
                     print('step %d loss %.1f (seq2seq %.1f + output %.1f) gnorm %.2f decoder-mode %d' %
                           (gs, loss, s2s_l, out_l, float(model.global_gradient_norm), model.decoder_mode))
                     if scores is not None:                    # (B, 6) + (B, 2) + (B) values, already computed: no alignment tensor travels
                         print('step %d %s' % (gs, align_line(scores[0].cpu().numpy(), scores[1].cpu().numpy(),
                                                              model.inputs['text_length'].cpu().numpy(), model.shape.Tt)))
+                    if mon:                                   # three copies behind the sync above: (N, 6) + (N, 5) + (N, NB) values
+                        mon_host = tuple(t.cpu().numpy() for t in model.monitor_result)
+                        save_monitor(model, os.path.join('log', config.save_path, 'monitor'), gs, mon_host)
+                        print('step %d %s' % (gs, monitor_line(model.monitor_names, mon_host[0], mon_host[1], mon_lr)))
                 # train.py:77-80; `not isfinite` added: the bf16x3 GEMMs turn an Inf operand into NaN (inf - inf in the plane split),
                 # and `NaN > 1e8` is False -- a diverged run must still stop here
                 if (not math.isfinite(loss) or loss > 1e8) and gs > 500:
+                    if rank == 0 and mon_step is not None:    # (the results are on the device already; this log step's, or the last one's)
+                        if mon_host is None or not mon:
+                            mon_host = tuple(t.cpu().numpy() for t in model.monitor_result)
+                        bad = monitor_nonfinite(model.monitor_names, mon_host[0])
+                        print('non-finite at step %d: %s' % (mon_step, ', '.join(bad) if bad else 'no monitored tensor'))
                     print('loss exploded')
                     break
             if gs % 1000 == 0:
@@ -278,6 +349,10 @@ def parse_args(argv=None):
     ap.add_argument('--align-log', action='store_true',
                     help='alignment monitor: a second log line with the batch means of the per-utterance attention scores (computed on '
                          'the device) and the rows the untuned thresholds of alignment.flags mark; attention_<step>.png with every sample')
+    ap.add_argument('--monitor', action='store_true',
+                    help='training monitor: at every log step, statistics and log-bucket histograms of every parameter, gradient and '
+                         'Adam slot and of the reference\'s histogram sites, computed on the device -> one more log line and '
+                         'log/<save_path>/monitor/monitor_<step>.npz; names the non-finite tensors before `loss exploded`')
     ap.add_argument('--holdout', type=int, default=0, metavar='N',
                     help='never draw the last N utterances of the corpus: the set `python -m tacotron_amd.evaluate --holdout N` scores')
     return ap.parse_args(argv)
@@ -290,4 +365,4 @@ if __name__ == '__main__':
     c.restore = a.restore
     c.save_path = 'debug' if a.debug else '%s/tacotron' % a.train_set
     print('Building Tacotron')
-    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log, holdout=a.holdout)
+    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log, holdout=a.holdout, monitor=a.monitor)
