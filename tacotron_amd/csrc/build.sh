@@ -11,8 +11,8 @@ pids=()
 # alternations (profiles/r05_dec_sched_ab.txt): BPTT 14.19 -> 13.66 us per decoder step, forward unchanged, S1 step -0.1 ms;
 # max-ilp / max-memory-clause / iterative-minreg are slower, the strategy does nothing for bigru.hip.
 D3FLAGS="-mllvm -amdgpu-sched-strategy=iterative-maxocc"
-# every object but the decoder pair, which the three libraries take in different builds
-COMMON="gemm gemm2 vocoder features elementwise align_path f0_viterbi phase_init loudness limiter monitor dtw bigru highway prenet layout stream model"
+# every object but the decoder pair, which the three libraries take in different builds: UNITS, one name per line
+COMMON=$(tr '\n' ' ' < UNITS)
 for f in $COMMON decoder; do
   hipcc $FLAGS -c $f.hip -o ../../build/obj/$f.o &
   pids+=($!)

@@ -1,7 +1,7 @@
 // kernels.h -- internal launch interface shared by the .hip translation units of libtaco_hip.so: what one unit calls in another.
 // A C-ABI entry point (include/taco_hip.h) that needs nothing from another unit is defined beside its kernels and has no
-// declaration here: all of vocoder.hip and features.hip, and the op-level and probe entry points of elementwise.hip,
-// decoder.hip and stream.hip.  Device code that features.hip and vocoder.hip share is not an interface between units either: stft.h.
+// declaration here: all of vocoder.hip, features.hip, frames.hip, corpus.hip and probes.hip, taco_alignment_scores of
+// align_scores.hip, and the op-level and probe entry points of elementwise.hip, decoder.hip and stream.hip.  Device code that features.hip and vocoder.hip share is not an interface between units either: stft.h.
 #pragma once
 #include "common.h"
 #include "stream.h"
@@ -190,13 +190,6 @@ int launch_colsum_batched(const float* x, int ld, float* out, int B, int T, int 
 int launch_mask_rows(const float* x, const int32_t* len, float* y, int B, int T, int C, hipStream_t s);
 // taco_infer_stop: rows t >= len[b] of x0 (B, Td, C0) and, when non-null, x1 (B, Td, C1) are set to 0 in place (nothing is read)
 int launch_zero_tail_rows(float* x0, int C0, float* x1, int C1, const int32_t* len, int B, int Td, hipStream_t s);
-// taco_infer_stop's end-detection rule (include/taco_hip.h) over the alignments (B, Td, Tt) of a full decode: len (B) int32
-int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* len, int B, int Tt, int Td, int end_offset, int hold,
-                     int min_steps, hipStream_t s);
-// taco_alignment_scores (include/taco_hip.h) over alignments (B, Td, Tt): counts (B, 6) int32, means (B, 2); steps nullable.  One
-// launch of B workgroups; the entry point has checked the arguments (Td, Tt within TACO_ALIGNMENT_MAX_TD / _TT)
-int launch_alignment_scores(const float* align, const int32_t* text_length, const int32_t* steps, int max_jump, int32_t* counts,
-                            float* means, int B, int Td, int Tt, hipStream_t s);
 // taco_frames_active / taco_frame_dtw (include/taco_hip.h; dtw.hip): one launch of B workgroups each; the entry points have checked
 // the arguments (Fa, Fb, C, K within TACO_DTW_MAX_*; workspace given where the coefficients do not fit LDS)
 int launch_frames_active(const float* x, float floor, int32_t* n, int B, int F, int C, hipStream_t s);
@@ -257,6 +250,11 @@ struct InitBatch {
   }
 };
 int launch_init_batch(InitBatch& b, hipStream_t s);   // communication-kernel stand-in (tests)
+
+// ---------------------------------------------------------------- align_scores.hip
+// taco_infer_stop's end-detection rule (include/taco_hip.h) over the alignments (B, Td, Tt) of a full decode: len (B) int32
+int launch_stop_rule(const float* align, const int32_t* text_length, int32_t* len, int B, int Tt, int Td, int end_offset, int hold,
+                     int min_steps, hipStream_t s);
 
 // ---------------------------------------------------------------- bigru.hip
 struct BiGruWeights {

@@ -198,6 +198,21 @@ def test_every_compile_time_name_is_selected_by_a_build_or_a_tool():
     assert names == COMPILE_TIME
 
 
+def test_units_is_the_one_list_of_translation_units():
+    """csrc/UNITS names every .hip file but the decoder pair (which the build scripts take in several builds) exactly once, names
+    nothing else, and neither build script keeps a list of its own beside it."""
+    units = open(os.path.join(CSRC, 'UNITS')).read().split()
+    on_disk = sorted(os.path.basename(p)[:-len('.hip')] for p in glob.glob(os.path.join(CSRC, '*.hip')))
+    assert sorted(units) == [u for u in on_disk if u not in ('decoder', 'decoder3')]   # (sorted lists: a name twice would not match)
+    for u in units:
+        assert os.path.isfile(os.path.join(CSRC, u + '.hip')), u
+    for script in (os.path.join(CSRC, 'build.sh'), os.path.join(ROOT, 'tools', 'ab_build.sh')):
+        text = open(script).read()
+        assert 'UNITS' in text, script
+        for u in ('gemm2', 'vocoder', 'monitor'):
+            assert not re.search(r'\b%s\b' % u, text), '%s names %s itself' % (os.path.relpath(script, ROOT), u)
+
+
 def test_integration_md_documents_exactly_the_switches():
     section = read('INTEGRATION.md').split('\n## 4. ')[1].split('\n## ')[0]
     runtime, flags = set(), set()
