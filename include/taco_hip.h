@@ -680,6 +680,60 @@ int taco_frames_stretch_curve(const float* mag_t, const int32_t* frames, int fra
 int taco_frames_pitch_curve(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
                             float* out, int B, int C, int F, void* stream);
 
+/* Spectral sharpening at synthesis and the raw material of the global variance (no reference counterpart).  Magnitudes trained under an
+ * L1 loss and handed to Griffin-Lim have over-smoothed envelopes: formant peaks too low, valleys filled in.  The measure is the global
+ * variance (GV): the variance over an utterance's frames of each cepstral coefficient, predicted against recorded.  The cure is a
+ * cepstral post-filter: the envelope's low quefrencies scaled by 1 + beta at unchanged frame energy.
+ *
+ * taco_frames_sharpen: the post-filter, in the place of taco_frames_pitch (between taco_denorm_unframe and Griffin-Lim; the driver
+ * runs it first, in front of pitch, stretch and F0).
+ *   mag_t, out, frames, frames_per_unit, B, C, F and F_b exactly as taco_frames_pitch
+ *   beta   in [TACO_SHARPEN_MIN_BETA, TACO_SHARPEN_MAX_BETA]; one value for the whole call
+ *   lifter Q, TACO_SHARPEN_FIRST <= Q <= min(TACO_PITCH_MAX_LIFTER, (C - 1) / 2): the quefrencies 2 .. Q are scaled (rectangular)
+ * For frame f < F_b of row b, m[k] = mag_t[b, k, f], in real numbers:
+ *   L[k]  = log(max(m[k], TACO_PITCH_FLOOR))
+ *   c[n]  = the cepstrum taco_frames_pitch defines, n = 0 .. Q
+ *   D[k]  = 2 beta sum_{n = 2 .. Q} c[n] cos(2 pi n k / N),  N = 2 (C - 1)
+ *   y[k]  = m[k] exp(D[k])                                      (m, not max(m, floor): a zero bin stays zero)
+ *   P0 = sum_k m[k]^2, P1 = sum_k y[k]^2 (k = 0 .. C - 1, plain sums);  g = sqrt(P0 / P1), and 1 when P1 == 0
+ *   out[b, k, f] = y[k] g
+ * so that, for bins at or above the floor, the cepstrum of out has c'[n] = (1 + beta) c[n] for 2 <= n <= Q, c'[1] = c[1], c'[n] = c[n]
+ * for n > Q, and sum out^2 = sum m^2.  Computed in fp32 with the chains of taco_frames_pitch and held to an fp64 restatement
+ * (tests/sharpen_ref.py).  Exactly:
+ *   - beta == 0 copies the live frames bit for bit, with no log or exp;
+ *   - out[b, k, f] = +0 for F_b <= f < F;
+ *   - every element of out is written and nothing outside it, for any 4-byte alignment;
+ *   - columns behind F_b, other rows and other frames have no influence on a frame (they may hold NaN);
+ *   - the bits of a frame depend on its own bins, beta and Q alone -- not on B, F, its position or the buffers' alignment; no
+ *     atomics; the same arguments give the same bits.
+ * One launch, no workspace, no allocation, no host synchronisation, graph-capturable; a replay follows `frames` on the device.  NULL
+ * mag_t / out, out overlapping mag_t, a bad B, C, F or frames_per_unit, lifter out of range, and beta NaN or outside its range return
+ * TACO_EINVAL with a message that names the argument, before anything is enqueued.
+ *
+ * taco_frames_cepstats: per row the sums over the live frames of every cepstral coefficient and of its square.
+ *   sums   (B, Q + 1, 2) fp64, at any 4-byte alignment: sums[b, n, 0] = sum_{f < F_b} c[n][f], sums[b, n, 1] = sum_{f < F_b} c[n][f]^2,
+ *          the c[n][f] being the fp32 cepstra of taco_frames_sharpen's first stage (the same chains), added in fp64 in a fixed order
+ *   count  (B) int32: count[b] = F_b.  A row with F_b == 0 gives zeros
+ *   workspace: taco_frames_cepstats_workspace_bytes(B, C, F, lifter) bytes at any alignment, with any contents
+ * Frame tiles are reduced in parallel into per-tile partials in the workspace and a second launch folds them in tile order: no
+ * atomics, the same arguments give the same bits, a row does not depend on its neighbours or on columns behind F_b.  No allocation,
+ * no host synchronisation, graph-capturable.  The refusals of taco_frames_sharpen without beta and out, and NULL sums, count or
+ * workspace; the size function returns TACO_EINVAL for the same B, C, F and lifter.  The variance of coefficient n over a row is
+ * sums[b, n, 1] / count - (sums[b, n, 0] / count)^2, formed by the caller in fp64.
+ *
+ * TACO_VERSION did not change with these entry points: detect them by the symbol.
+ * Not here: a per-row or per-frame beta, a tapered lifter, mel frames.  Nobody has listened to the result: the Python layer's
+ * defaults (lifter 32) are untuned, and the cepstra are this model's linear-frequency ones -- a GV ratio from them is comparable
+ * between checkpoints here, not with published mel-cepstral GV figures. */
+#define TACO_SHARPEN_FIRST    2       /* quefrencies 0 (level) and 1 (tilt) are never scaled */
+#define TACO_SHARPEN_MIN_BETA -1.0f   /* removes quefrencies 2 .. Q: used by tests to make an over-smoothed input */
+#define TACO_SHARPEN_MAX_BETA 1.0f
+int taco_frames_sharpen(const float* mag_t, const int32_t* frames, int frames_per_unit, float beta, int lifter, float* out, int B,
+                        int C, int F, void* stream);
+int64_t taco_frames_cepstats_workspace_bytes(int B, int C, int F, int lifter);
+int taco_frames_cepstats(const float* mag_t, const int32_t* frames, int frames_per_unit, int lifter, double* sums, int32_t* count,
+                         void* workspace, int B, int C, int F, void* stream);
+
 /* F0 tracker (no reference counterpart): the per-frame pitch of magnitude frames, measured where the two prosody controls above
  * run -- the instrument that stands in for listening to them.  By Wiener-Khinchin the cosine transform of a frame's power spectrum is
  * the autocorrelation of the windowed frame, so no waveform, phase or vocoder run is needed: the same call serves the model's output,

@@ -49,6 +49,18 @@ def int_arg(who, name, v, lo=None, hi=None) -> int:
     return int(v)
 
 
+def float_arg(who, name, v, lo, hi) -> float:
+    """v as a float in [lo, hi]: no bool, nothing float() cannot take, no NaN"""
+    try:
+        x = float(v)
+        ok = not isinstance(v, bool) and lo <= x <= hi   # (NaN fails both comparisons)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%s: %s must be a number in [%s, %s], got %r' % (who, name, lo, hi, v))
+    return x
+
+
 def unit_interval(x, what) -> float:
     """x as a float in [0, 1) that is still below 1 as a float32, or ValueError"""
     x = float(x)

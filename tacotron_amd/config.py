@@ -50,6 +50,10 @@ class Config(object):
     save_path = 'nancy/tacotron'
     restore = False
 
+    # synthesis only (test.py --sharpen BETA / --sharpen-lifter Q): the cepstral post-filter in front of the vocoder; None: off
+    sharpen = None
+    sharpen_lifter = 32
+
     # models/tacotron.py:13 evaluates maximum_audio_length // (r hop_length) once, with audio.r; here `r` is changed at run time
     # (test.py from the checkpoint, train.py from meta.pkl), so the decode length follows the r in use unless a caller sets it
     _max_decode_iter = None

@@ -1,8 +1,9 @@
 // frames.hip -- the synthesis frame chain: what happens to the decoder's output between the model and the vocoder, and the pitch
 // read-outs over the same magnitude frames (include/taco_hip.h taco_denorm_unframe, taco_frames_stretch, taco_frames_stretch_curve,
-// taco_frames_pitch, taco_frames_pitch_curve, taco_frames_f0, taco_f0_stats, taco_path_f0_scores).  Every entry point stands
-// behind its kernels with the refusals that guard them; each kernel's comment has its form and why.  The cosine
-// products of frames_pitch_kernel and frames_f0_kernel are fp32 MFMAs; everything else here is bound by memory.
+// taco_frames_pitch, taco_frames_pitch_curve, taco_frames_sharpen, taco_frames_cepstats, taco_frames_f0, taco_f0_stats,
+// taco_path_f0_scores).  Every entry point stands behind its kernels with the refusals that guard them; each kernel's comment has its
+// form and why.  The cosine products of frames_pitch_kernel, frames_sharpen_kernel, frames_cepstats_kernel and
+// frames_f0_kernel are fp32 MFMAs; everything else here is bound by memory.
 #include "common.h"
 #include "kernels.h"
 
@@ -425,6 +426,271 @@ __global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const fl
   }
 }
 
+// The cepstrum stage of frames_pitch_kernel restated for the two kernels below (frames_pitch_kernel keeps its own text, so its bits
+// cannot move): c[n][f], n = 0 .. 32 NB, of the 32 frames of a tile into cep[n * 32 + f], WITHOUT a lifter.  The same dealing of the
+// bin pairs to kWaves waves, the same chains, the same fold of the waves' partials in wave order; `part` is scratch of
+// (kWaves 32 NB + 2 kWaves) x 32 floats.  Called by every thread of the workgroup (it has barriers); tab is filled and synchronised
+// by the caller.  Behind it cep is complete and visible, and nothing reads part any more.
+template <int NB, int kWaves>
+__device__ __forceinline__ void cepstrum_tile(const float* __restrict__ src, bool live, int C, int F, const float* tab, float* cep,
+                                              float* part) {
+  constexpr int NR = 32 * NB;
+  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int N = 2 * (C - 1), mask = N - 1;
+  const float wt = 2.0f / (float)N;   // (a power of two: the weight and the 1 / N cost no rounding)
+  f32x16 acc[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+  float c0p = 0.f;
+  float m[4], nx[4];   // four bin pairs per trip, the next trip's loads issued in front of this trip's arithmetic
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int k = 2 * wave + 2 * kWaves * u + h;
+    m[u] = (live && k < C) ? src[k * F] : 1.0f;
+  }
+  for (int k0 = 2 * wave; k0 < C; k0 += 8 * kWaves) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + 8 * kWaves + 2 * kWaves * u + h;
+      nx[u] = (live && k < C) ? src[k * F] : 1.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + 2 * kWaves * u + h;   // (k >= C: m = 1, v = 0, and the table is read at some valid index)
+      const float v = logf(fmaxf(m[u], TACO_PITCH_FLOOR)) * ((k == 0 || k == C - 1) ? 0.5f * wt : wt);
+      c0p += v;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + fl) * k) & mask], v, acc[nb], 0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) m[u] = nx[u];
+  }
+  float* part0 = part + kWaves * NR * kPitchFrames;   // part: [wave][n - 1][f]; part0: [wave][h][f] for c[0]
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      part[((wave * NR) + 32 * nb + (r & 3) + 8 * (r >> 2) + 4 * h) * kPitchFrames + fl] = acc[nb][r];
+  part0[(2 * wave + h) * kPitchFrames + fl] = c0p;
+  __syncthreads();
+  for (int e = tid; e < NR * kPitchFrames; e += 64 * kWaves) {   // e = (n - 1) * 32 + f
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) t += part[w * NR * kPitchFrames + e];
+    cep[kPitchFrames + e] = t;
+  }
+  if (tid < kPitchFrames) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 2 * kWaves; ++w) t += part0[w * kPitchFrames + tid];
+    cep[tid] = t;
+  }
+  __syncthreads();
+}
+
+// taco_frames_sharpen: the cepstral post-filter (include/taco_hip.h has the definition).  The shape of frames_pitch_kernel: a
+// workgroup owns 32 consecutive frames of a row, the frame is the lane's low five bits, NB = 1 (16 waves) for Q <= 32 and 2 (8 waves)
+// above -- chosen by Q alone, so the bits depend on Q alone.  Three stages:
+//   cepstrum  cepstrum_tile above;
+//   D[k][f] = sum_{n = 2 .. Q} cos(2 pi n k / N) (2 beta c[n][f]): the envelope stage of the pitch kernel started at 0 with the rows
+//             n < 2 and n > Q zeroed in the B operands; D of the tile stays in LDS (C x 32 floats);
+//   output    every thread reads its bins once more, y = m exp(D) takes D's place in LDS (the thread that wrote an element is the one
+//             that reads it back), the squares of m and y are summed per thread, the 2 kWaves partials of a frame folded in a fixed
+//             order through the bytes of the cosine table (no longer read), g = sqrt(P0 / P1), and out = y g.
+// Two reads per element where one is compulsory, one logarithm and one exponential.  beta == 0 and tiles behind F_b: the pitch
+// kernel's copy branch.
+template <int NB, int kWaves>
+__global__ __launch_bounds__(64 * kWaves) void frames_sharpen_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                                      int frames_per_unit, float beta, int Q, float* __restrict__ out,
+                                                                      int C, int F, int ntile) {
+  constexpr int NR = 32 * NB;
+  static_assert(4 * kWaves * kPitchFrames <= 2 * (kPitchMaxC - 1), "the partial sums of P0 and P1 fit the cosine table");
+  static_assert((kWaves * NR + 2 * kWaves) <= kPitchMaxC, "the cepstrum partials fit D's bytes");
+  __shared__ float tab[2 * (kPitchMaxC - 1)];
+  __shared__ float cep[(NR + 1) * kPitchFrames];
+  __shared__ float env[kPitchMaxC * kPitchFrames];   // D[k][f], then y[k][f]; before that the waves' partial cepstra
+  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
+  int Fb = F;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int f0 = tile * kPitchFrames, f = f0 + fl;
+  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
+  float* __restrict__ dst = out + (int64_t)b * C * F + f;
+  const bool live = f < Fb, inside = f < F;
+  if (f0 >= Fb || beta == 0.f) {   // (uniform) zeros behind the row's end, the row's own bits in front of it
+    for (int kb = 2 * wave + h; kb < C; kb += 2 * kWaves * kPitchBatch) {
+      float m[kPitchBatch];
+#pragma unroll
+      for (int u = 0; u < kPitchBatch; ++u) {
+        const int k = kb + 2 * kWaves * u;
+        m[u] = (live && k < C) ? src[k * F] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kPitchBatch; ++u) {
+        const int k = kb + 2 * kWaves * u;
+        if (inside && k < C) dst[k * F] = m[u];
+      }
+    }
+    return;
+  }
+  const int N = 2 * (C - 1), mask = N - 1;
+  for (int j = tid; j < N; j += 64 * kWaves) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
+  __syncthreads();
+  cepstrum_tile<NB, kWaves>(src, live, C, F, tab, cep, env);
+
+  // ---- D ----
+  const float b2 = 2.0f * beta;
+  float cb[NB][16];   // 2 beta c[n][f], n = 32 nb + 1 + 2 j + h, zero outside 2 .. Q: this lane's B operands
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int n = 32 * nb + 1 + 2 * j + h;
+      cb[nb][j] = (n >= TACO_SHARPEN_FIRST && n <= Q) ? b2 * cep[n * kPitchFrames + fl] : 0.f;
+    }
+  if (tid < kPitchFrames) {   // bin C - 1: cos(pi n) = (-1)^n
+    float t = 0.f;
+    for (int n = TACO_SHARPEN_FIRST; n <= Q; ++n) {
+      const float c2 = b2 * cep[n * kPitchFrames + tid];
+      t += (n & 1) ? -c2 : c2;
+    }
+    env[(C - 1) * kPitchFrames + tid] = t;
+  }
+  const int nblk = (C - 1 + 31) >> 5;
+  for (int kb = wave; kb < nblk; kb += kWaves) {
+    const int k = 32 * kb + fl;
+    f32x16 d;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d[r] = 0.f;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        d = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + 2 * j + h) * k) & mask], cb[nb][j], d, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kk = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (kk < C - 1) env[kk * kPitchFrames + fl] = d[r];
+    }
+  }
+  __syncthreads();   // (nothing reads the cosine table from here on: tab holds the partial sums)
+
+  // ---- y and the two energies ----  a frame behind F_b inside a live tile has m = 0: y = 0, P0 = P1 = 0, g = 1
+  float p0 = 0.f, p1 = 0.f;
+  for (int kb = 2 * wave + h; kb < C; kb += 2 * kWaves * kPitchBatch) {
+    float m[kPitchBatch];
+#pragma unroll
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kWaves * u;
+      m[u] = (live && k < C) ? src[k * F] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kWaves * u;
+      if (k >= C) break;
+      const float y = m[u] * expf(env[k * kPitchFrames + fl]);
+      p0 += m[u] * m[u];
+      p1 += y * y;
+      env[k * kPitchFrames + fl] = y;
+    }
+  }
+  tab[(2 * wave + h) * kPitchFrames + fl] = p0;
+  tab[(2 * kWaves + 2 * wave + h) * kPitchFrames + fl] = p1;
+  __syncthreads();
+  if (tid < kPitchFrames) {
+    float P0 = 0.f, P1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < 2 * kWaves; ++w) {
+      P0 += tab[w * kPitchFrames + tid];
+      P1 += tab[(2 * kWaves + w) * kPitchFrames + tid];
+    }
+    cep[tid] = P1 == 0.f ? 1.0f : sqrtf(P0 / P1);
+  }
+  __syncthreads();
+  const float g = cep[fl];
+  if (!inside) return;
+  for (int k = 2 * wave + h; k < C; k += 2 * kWaves) dst[k * F] = live ? env[k * kPitchFrames + fl] * g : 0.f;
+}
+
+// taco_frames_cepstats: per row the sums over the live frames of every cepstral coefficient and of its square.  The first launch is
+// the sharpening kernel's first stage per tile of 32 frames (cepstrum_tile: the same chains, so the same fp32 cepstra), then thread n
+// adds the tile's live frames of c[n] and of c[n]^2 in fp64 in frame order and leaves the pair in the workspace at [b][tile][n] --
+// a tile behind F_b leaves zeros and loads nothing.  The second launch (one workgroup per row, thread n) folds the tiles in tile
+// order.  No atomics; the workspace is written before it is read, so its contents on entry do not matter.  sums is written as
+// 32-bit halves: it may sit at any 4-byte alignment; the workspace is aligned up to 8 bytes inside its slack.
+__device__ __forceinline__ void store_f64_halves(double* p, double v) {
+  uint32_t* q = reinterpret_cast<uint32_t*>(p);
+  q[0] = (uint32_t)__double2loint(v);
+  q[1] = (uint32_t)__double2hiint(v);
+}
+template <int NB, int kWaves>
+__global__ __launch_bounds__(64 * kWaves) void frames_cepstats_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                                       int frames_per_unit, int Q, double* __restrict__ partial, int C,
+                                                                       int F, int ntile) {
+  constexpr int NR = 32 * NB;
+  __shared__ float tab[2 * (kPitchMaxC - 1)];
+  __shared__ float cep[(NR + 1) * kPitchFrames];
+  __shared__ float part[(kWaves * NR + 2 * kWaves) * kPitchFrames];
+  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
+  int Fb = F;
+  if (frames) {
+    const int64_t n = (int64_t)frames[b] * frames_per_unit;
+    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
+  }
+  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  const int tid = threadIdx.x, fl = tid & 31;
+  const int f0 = tile * kPitchFrames, f = f0 + fl;
+  double* __restrict__ mine = partial + (int64_t)blockIdx.x * (2 * (Q + 1));
+  if (f0 >= Fb) {   // (uniform)
+    if (tid <= Q) mine[2 * tid] = 0.0, mine[2 * tid + 1] = 0.0;
+    return;
+  }
+  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;
+  const int N = 2 * (C - 1);
+  for (int j = tid; j < N; j += 64 * kWaves) tab[j] = cospif((float)(2 * j) / (float)N);
+  __syncthreads();
+  cepstrum_tile<NB, kWaves>(src, f < Fb, C, F, tab, cep, part);
+  if (tid <= Q) {
+    const int nl = Fb - f0 < kPitchFrames ? Fb - f0 : kPitchFrames;
+    double s = 0.0, s2 = 0.0;
+    for (int j = 0; j < nl; ++j) {
+      const double c = (double)cep[tid * kPitchFrames + j];
+      s += c;
+      s2 += c * c;   // (the square of a float is exact in fp64: contracted or not, one rounding)
+    }
+    mine[2 * tid] = s, mine[2 * tid + 1] = s2;
+  }
+}
+__global__ __launch_bounds__(128) void frames_cepstats_fold_kernel(const double* __restrict__ partial, const int32_t* __restrict__ frames,
+                                                                    int frames_per_unit, int Q, double* __restrict__ sums,
+                                                                    int32_t* __restrict__ count, int F, int ntile) {
+  static_assert(TACO_PITCH_MAX_LIFTER + 1 <= 128, "one thread per quefrency");
+  const int b = blockIdx.x, n = threadIdx.x;
+  if (n == 0) {
+    int Fb = F;
+    if (frames) {
+      const int64_t v = (int64_t)frames[b] * frames_per_unit;
+      Fb = v < 0 ? 0 : (v > F ? F : (int)v);
+    }
+    count[b] = Fb;
+  }
+  if (n > Q) return;
+  const double* __restrict__ p = partial + ((int64_t)b * ntile) * (2 * (Q + 1)) + 2 * n;
+  double s = 0.0, s2 = 0.0;
+  for (int t = 0; t < ntile; ++t) s += p[(int64_t)t * (2 * (Q + 1))], s2 += p[(int64_t)t * (2 * (Q + 1)) + 1];
+  store_f64_halves(sums + ((int64_t)b * (Q + 1) + n) * 2, s);
+  store_f64_halves(sums + ((int64_t)b * (Q + 1) + n) * 2 + 1, s2);
+}
+
 // taco_frames_f0: the pitch of a magnitude frame.  By Wiener-Khinchin the cosine transform of the power spectrum is the
 // autocorrelation of the windowed frame: p[k] = u[k] weight[k] m[k]^2, r[n] = sum_k p[k] cos(2 pi n k / N) over the band of lags
 // n = lag_min - 1 .. lag_max + 1, y[n] = (r[n] / r0) gain[n - lag_min + 1], and the period is the first high local maximum of y,
@@ -774,7 +1040,79 @@ int frames_pitch_call(const char* who, const float* mag_t, const int32_t* frames
   TACO_LAUNCH_CHECK(who);
   return TACO_OK;
 }
+
+// the refusals taco_frames_sharpen and taco_frames_cepstats share (those of taco_frames_pitch with the lifter from
+// TACO_SHARPEN_FIRST), and the grid
+int frames_cepstrum_args(const char* who, const float* mag_t, int frames_per_unit, int lifter, int B, int C, int F, int* ntile,
+                         int64_t* blocks) {
+  TACO_REQUIRE(mag_t, "%s: mag_t is NULL", who);
+  TACO_REQUIRE(B > 0, "%s: B=%d must be positive", who, B);
+  TACO_REQUIRE(C >= 9 && C <= kPitchMaxC && ((C - 1) & (C - 2)) == 0, "%s: C=%d: C - 1 must be a power of two in 8..%d", who, C,
+               kPitchMaxC - 1);
+  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "%s: F=%d must be in 1..%d", who, F, TACO_STRETCH_MAX_FRAMES);
+  const int qmax = (C - 1) / 2 < TACO_PITCH_MAX_LIFTER ? (C - 1) / 2 : TACO_PITCH_MAX_LIFTER;
+  TACO_REQUIRE(lifter >= TACO_SHARPEN_FIRST && lifter <= qmax, "%s: lifter=%d must be in %d..%d at C=%d", who, lifter,
+               TACO_SHARPEN_FIRST, qmax, C);
+  TACO_REQUIRE(frames_per_unit >= 1, "%s: frames_per_unit=%d must be >= 1", who, frames_per_unit);
+  *ntile = cdiv(F, kPitchFrames);
+  *blocks = (int64_t)B * *ntile;
+  TACO_REQUIRE(*blocks <= 0x7fffffff, "%s: B=%d x F=%d needs more than 2^31 workgroups", who, B, F);
+  return TACO_OK;
+}
 }  // namespace
+
+extern "C" int taco_frames_sharpen(const float* mag_t, const int32_t* frames, int frames_per_unit, float beta, int lifter, float* out,
+                                   int B, int C, int F, void* stream) {
+  const char* who = "frames_sharpen";
+  int ntile;
+  int64_t blocks;
+  TACO_REQUIRE(out, "%s: out is NULL", who);
+  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, lifter, B, C, F, &ntile, &blocks));
+  TACO_REQUIRE(beta >= TACO_SHARPEN_MIN_BETA && beta <= TACO_SHARPEN_MAX_BETA, "%s: beta=%g must be in [%g, %g]", who, (double)beta,
+               (double)TACO_SHARPEN_MIN_BETA, (double)TACO_SHARPEN_MAX_BETA);   // (false for a NaN)
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
+  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
+  TACO_REQUIRE(o0 + bytes <= m0 || m0 + bytes <= o0, "%s: out overlaps mag_t", who);
+  hipStream_t s = as_stream(stream);
+  if (lifter <= 32)
+    TACO_KLAUNCH((frames_sharpen_kernel<1, 16>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, beta, lifter,
+                 out, C, F, ntile);
+  else
+    TACO_KLAUNCH((frames_sharpen_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, beta, lifter,
+                 out, C, F, ntile);
+  TACO_LAUNCH_CHECK(who);
+  return TACO_OK;
+}
+// per tile of 32 frames (Q + 1) pairs of fp64, and 8 bytes of slack to align them in a workspace at any address
+extern "C" int64_t taco_frames_cepstats_workspace_bytes(int B, int C, int F, int lifter) {
+  int ntile;
+  int64_t blocks;
+  const float dummy = 0.f;
+  if (frames_cepstrum_args("frames_cepstats_workspace_bytes", &dummy, 1, lifter, B, C, F, &ntile, &blocks) != TACO_OK) return TACO_EINVAL;
+  return blocks * (lifter + 1) * 16 + 8;
+}
+extern "C" int taco_frames_cepstats(const float* mag_t, const int32_t* frames, int frames_per_unit, int lifter, double* sums,
+                                    int32_t* count, void* workspace, int B, int C, int F, void* stream) {
+  const char* who = "frames_cepstats";
+  int ntile;
+  int64_t blocks;
+  TACO_REQUIRE(sums, "%s: sums is NULL", who);
+  TACO_REQUIRE(count, "%s: count is NULL", who);
+  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, lifter, B, C, F, &ntile, &blocks));
+  TACO_REQUIRE(workspace, "%s: workspace is NULL", who);
+  double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + 7) & ~(uintptr_t)7);
+  hipStream_t s = as_stream(stream);
+  if (lifter <= 32)
+    TACO_KLAUNCH((frames_cepstats_kernel<1, 16>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, lifter,
+                 partial, C, F, ntile);
+  else
+    TACO_KLAUNCH((frames_cepstats_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, lifter,
+                 partial, C, F, ntile);
+  TACO_KLAUNCH(frames_cepstats_fold_kernel, dim3((unsigned)B), dim3(128), 0, s, partial, frames, frames_per_unit, lifter, sums, count, F,
+               ntile);
+  TACO_LAUNCH_CHECK(who);
+  return TACO_OK;
+}
 
 extern "C" int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, float* out,
                                    int32_t* frames_out, int B, int C, int F, int Fo, void* stream) {

@@ -9,7 +9,7 @@ utterances of the corpus, the ones `train --holdout N` never draws,
       with frames of log(1e-8) and stores no length.
 Only cost, steps, na, nb and the three losses of each batch travel to the host.
 
-    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--f0-smooth] [--durations]
+    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--f0-smooth] [--durations] [--gv [--gv-lifter Q] [--sharpen BETA]]
 
 prints one line per batch and a final line with the mean teacher-forced loss and the mean and worst MCD, and writes
 eval_<step>.npy, one row per utterance: index, na, nb, steps, cost, mcd (float64; COLUMNS).
@@ -54,6 +54,20 @@ append: the mean absolute difference of the two durations per character in ms (a
 their means.  The other modes print and save exactly what they did.  On an untrained model the attention follows no text and the
 numbers mean nothing; and a boundary is exact at multiples of 4 steps only (alignment.py).
 
+--gv [--gv-lifter Q] [--sharpen BETA] (opt-in): global variance, the standard measure of over-smoothed spectral envelopes.  The
+predicted and the recorded magnitude frames are built as for --f0 (and shared with it), and per utterance the sums over its frames of
+every cepstral coefficient and of its square are taken on the device (lib.frames_cepstats, taco_frames_cepstats; the predicted frames
+counted by the stop rule, the recorded ones by lib.frames_active); only those sums travel to the host, where
+var[n] = sums[n, 1] / count - (sums[n, 0] / count)^2 and the GV ratio = exp(mean over n = 1 .. Q of log(var_pred[n] / var_rec[n])),
+Q = 32 by default.  Well below 1: the prediction's envelopes are over-smoothed.  An utterance with fewer than 2 frames on either side
+has NaN.  Each row gains GV_COLUMNS behind every other column, and one more line per batch and one final line give the mean ratio and
+the share of utterances below GV_LOW = 0.8.  With --sharpen BETA the predicted magnitudes are also passed through the post-filter of
+`test --sharpen BETA` at its default lifter (lib.frames_sharpen) and scored again: a second column (GV_SHARPEN_COLUMNS) and both
+numbers on the lines, so one run shows what the filter does to the measure.  Sharpening here touches the GV columns only: MCD, F0 and
+durations are computed on what they were computed on.  The ratio is over this model's LINEAR-frequency cepstra, quefrencies 1 .. Q: it
+is comparable between checkpoints here, NOT with published mel-cepstral GV figures.  BETA has no tuned default, and on an untrained
+model the numbers mean nothing.  Without --gv every mode prints and saves exactly what it did.
+
 The final batch is padded to the batch size by repeating its last utterance; the copies are left out of the per-utterance rows and
 of the MCD statistics.  The teacher-forced loss is one number per batch (and the CBHG's batch normalisation sees the whole batch),
 so the padded batch enters the mean loss weighted by its share of real rows.  Without a corpus on disk the synthetic pool of
@@ -78,6 +92,9 @@ F0_COLUMNS = ('f0_mean', 'f0_sd', 'voiced', 'rec_f0_mean', 'rec_f0_sd', 'rec_voi
 ALIGNED_COLUMNS = ('path_voiced', 'f0_rmse_cents', 'f0_bias_cents', 'vuv_error', 'gross_error')   # appended with --f0-aligned
 DUR_COLUMNS = ('dur_mae_ms', 'dur_bias_ms', 'path_mass', 'rec_path_mass')   # appended with --durations
 SMOOTH_COLUMNS = ('f0_moved', 'rec_f0_moved')   # appended with --f0-smooth (last): shares of the frames tracked
+GV_COLUMNS = ('gv_ratio',)   # appended with --gv (behind every other column); with --sharpen: GV_SHARPEN_COLUMNS
+GV_SHARPEN_COLUMNS = ('gv_ratio', 'gv_ratio_sharpened')
+GV_LOW = 0.8   # the final line gives the share of utterances whose GV ratio lies below this
 GROSS = 1.2  # a both-voiced cell is a gross pitch error when one period is above GROSS times the other (the usual 20 %)
 SR = 16000   # of a corpus whose meta.pkl records no 'sr', and of the synthetic pool
 PAD_FLOOR = float(np.float16(np.log(1e-8)))   # the value preprocess stores in the padding frames (fp16 of log(1e-8))
@@ -216,16 +233,58 @@ def smooth_summary(cols):
 SMOOTH_LINE = 'smoothing moved %.3f of the predicted and %.3f of the recorded frames'
 
 
+def gv_columns(sums_pred, n_pred, sums_rec, n_rec, sums_sharp=None):
+    """lib.frames_cepstats' sums (n, Q + 1, 2) and counts (n) of the predicted and of the recorded frames, and optionally the sums of
+    the sharpened predicted frames (same counts) -> (n, 1) float64 in the order GV_COLUMNS, or (n, 2) in the order GV_SHARPEN_COLUMNS:
+    lib.gv_ratio; NaN for an utterance with fewer than 2 frames on either side"""
+    cols = [lib.gv_ratio(sums_pred, n_pred, sums_rec, n_rec)]
+    if sums_sharp is not None:
+        cols.append(lib.gv_ratio(sums_sharp, n_pred, sums_rec, n_rec))
+    return np.stack([np.asarray(c, dtype=np.float64).reshape(-1) for c in cols], axis=1)
+
+
+def gv_summary(cols):
+    """(n, 1 | 2) in the order GV_COLUMNS / GV_SHARPEN_COLUMNS -> per column (mean ratio, share of the utterances below GV_LOW) over the
+    utterances that have one, flattened: 2 or 4 numbers; NaN without any"""
+    cols = np.asarray(cols, dtype=np.float64)
+    cols = cols.reshape(len(cols), -1)
+    out = []
+    for k in range(cols.shape[1]):
+        have = cols[np.isfinite(cols[:, k]), k]
+        out += [float(have.mean()), float((have < GV_LOW).mean())] if len(have) else [float('nan'), float('nan')]
+    return tuple(out)
+
+
+def gv_line(summary, sharpen=None):
+    """gv_summary's numbers -> 'GV ratio 0.61 (0.750 of the utterances below 0.8)', with --sharpen 'GV ratio 0.61, with --sharpen
+    0.40: 0.97 (... below 0.8: 0.750, 0.000)'"""
+    if len(summary) == 2:
+        return 'GV ratio %.2f (%.3f of the utterances below %g)' % (summary[0], summary[1], GV_LOW)
+    return 'GV ratio %.2f, with --sharpen %.2f: %.2f (share of the utterances below %g: %.3f, %.3f)' % (
+        summary[0], float(sharpen), summary[2], GV_LOW, summary[1], summary[3])
+
+
 def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None,
-             f0=False, f0_aligned=False, durations=False, path_jump=lib.PATH_JUMP, f0_smooth=False):
+             f0=False, f0_aligned=False, durations=False, path_jump=lib.PATH_JUMP, f0_smooth=False, gv=False, gv_lifter=lib.SHARPEN_LIFTER,
+             sharpen=None):
     """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  f0: rows (n, 12), F0_COLUMNS behind
     COLUMNS.  f0_aligned (implies f0): rows (n, 17), ALIGNED_COLUMNS behind those.  durations: DUR_COLUMNS behind all of them (path_jump: the max_jump of the two paths).  stop: the lib.TacoStopRule of the
     free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
     ({'predicted', 'recorded', 'na', 'nb'}: an extra copy per batch, for tests and inspection; with f0_aligned also the two period
     tracks 'period' and 'rec_period').  f0_smooth (implies f0): both tracks go through lib.f0_viterbi in front of the statistics and the
     path scores, SMOOTH_COLUMNS behind every other column; trace then also receives the per-frame tracks 'period_raw' and
-    'rec_period_raw' and the smoothed ones 'period' and 'rec_period'."""
+    'rec_period_raw' and the smoothed ones 'period' and 'rec_period'.  gv / gv_lifter / sharpen (needs gv): the global-variance ratio
+    over the quefrencies 1 .. gv_lifter, GV_COLUMNS behind every other column -- with a sharpen beta other than None and 0,
+    GV_SHARPEN_COLUMNS; trace then also receives the magnitudes the sums were taken over, 'pred_mags' and 'rec_mags' (B, C, F), with
+    sharpen also 'sharp_mags', and 'lengths', the decoder steps of the predicted rows."""
     f0 = bool(f0 or f0_aligned or f0_smooth)
+    if sharpen is not None and not gv:
+        raise ValueError('evaluate: sharpen (--sharpen) scores the post-filter by the global variance: it needs gv (--gv)')
+    if gv:
+        gv_lifter = lib.int_arg('evaluate', 'gv_lifter (--gv-lifter)', gv_lifter, lib.SHARPEN_FIRST, lib.PITCH_MAX_LIFTER)
+        sharpen = None if sharpen is None else lib.float_arg('evaluate', 'sharpen (--sharpen)', sharpen, lib.SHARPEN_MIN_BETA,
+                                                             lib.SHARPEN_MAX_BETA)
+        sharpen = None if sharpen == 0.0 else sharpen
     torch.cuda.set_device(device)
     dev = torch.device('cuda', device)
     corpus = open_corpus(config.data_path)
@@ -275,9 +334,16 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     nb = torch.empty(B, dtype=torch.int32, device=dev)
     zeros, ones = torch.zeros(80 * r, device=dev), torch.ones(80 * r, device=dev)
     per = {k: [] for k in ('na', 'nb', 'steps', 'cost') + (('f0', 'rec_f0', 'f0_frames') if f0 else ())
-           + (('path_counts', 'path_means') if f0_aligned else ()) + (('smooth',) if f0_smooth else ())}
-    if f0:
+           + (('path_counts', 'path_means') if f0_aligned else ()) + (('smooth',) if f0_smooth else ()) + (('gv',) if gv else ())}
+    if f0 or gv:   # the magnitudes of both sides, built once for the two of them
         Cs = batch['stft'].shape[2] // r
+        raw_stft = torch.empty(B, Td, Cs * r, device=dev)
+        mags = torch.empty(B, Cs, (Td // 4) * 4 * r, device=dev)
+        szeros, sones = torch.zeros(Cs * r, device=dev), torch.ones(Cs * r, device=dev)
+        smean, sstd = norm['stft'] if norm is not None and 'stft' in norm else (forced.stft_mean, forced.stft_std)
+        smean = szeros if smean is None else torch.as_tensor(smean, dtype=torch.float32).to(dev)
+        sstd = sones if sstd is None else torch.as_tensor(sstd, dtype=torch.float32).to(dev)
+    if f0:
         w, g, lag_min, lag_max = lib.f0_tables(sr, C=Cs)
         f0_opt = dict(weight=torch.from_numpy(w).to(dev), gain=torch.from_numpy(g).to(dev), lag_min=lag_min, lag_max=lag_max)
         if f0_smooth:
@@ -285,12 +351,6 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
             _, _, jump, switch = lib.f0_viterbi_tables(sr, hop=300)
             smooth_opt = dict(lag_min=lag_min, lag_max=lag_max, bias=torch.from_numpy(bias).to(dev), lg=torch.from_numpy(lg).to(dev),
                               jump_cost=jump, switch_cost=switch)
-        raw_stft = torch.empty(B, Td, Cs * r, device=dev)
-        mags = torch.empty(B, Cs, (Td // 4) * 4 * r, device=dev)
-        szeros, sones = torch.zeros(Cs * r, device=dev), torch.ones(Cs * r, device=dev)
-        smean, sstd = norm['stft'] if norm is not None and 'stft' in norm else (forced.stft_mean, forced.stft_std)
-        smean = szeros if smean is None else torch.as_tensor(smean, dtype=torch.float32).to(dev)
-        sstd = sones if sstd is None else torch.as_tensor(sstd, dtype=torch.float32).to(dev)
     if durations:
         path_jump = lib.int_arg('evaluate', 'path_jump (--path-jump)', path_jump, 1, lib.PATH_MAX_JUMP)
         per.update(dur=[])
@@ -311,17 +371,24 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
             cost, steps, na, path_a, path_b = free.mel_distortion(recorded, nb, cepstra, want_path=True)
         else:
             cost, steps, na = free.mel_distortion(recorded, nb, cepstra)
-        if f0:   # the decoder's own frames over lengths * r (max_decode_iter steps wide), then the recording's over nb
+        if f0 or gv:   # the decoder's own frames over lengths * r (max_decode_iter steps wide), and the recording's over nb
             pmags = lib.denorm_unframe(free.output, smean, sstd, r, want_spec=False, want_mag_t=True)
             Fp = pmags.shape[2]   # (the tracker counts over clamp(lengths r, 0, Fp); na is lengths r unclamped)
+            lib.corpus_batch(feeder.data['stft'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw_stft)
+            lib.denorm_unframe(raw_stft, szeros, sones, r, want_spec=False, want_mag_t=True, mag_t=mags)
+        if gv:   # sharpening stays inside this block: every other score is taken on pmags as it is
+            gv_pred, gv_rec = lib.frames_cepstats(pmags, gv_lifter, free.lengths, r), lib.frames_cepstats(mags, gv_lifter, nb, 1)
+            gv_sharp = None
+            if sharpen is not None:
+                sharp_mags = lib.frames_sharpen(pmags, sharpen, lib.SHARPEN_LIFTER, free.lengths, r)
+                gv_sharp = lib.frames_cepstats(sharp_mags, gv_lifter, free.lengths, r)
+        if f0:
             if f0_smooth:
                 pred_raw, _, acf = lib.frames_f0(pmags, free.lengths, r, want_acf=True, **f0_opt)
                 pred_period, _, pred_moved, _ = lib.f0_viterbi(acf, free.lengths, r, **smooth_opt)
             else:
                 pred_period = lib.frames_f0(pmags, free.lengths, r, **f0_opt)[0]
             pred_stats = lib.f0_stats(pred_period, None, free.lengths, r)
-            lib.corpus_batch(feeder.data['stft'], None, None, index=torch.as_tensor(index - first).to(dev), out=raw_stft)
-            lib.denorm_unframe(raw_stft, szeros, sones, r, want_spec=False, want_mag_t=True, mag_t=mags)
             if f0_smooth:
                 rec_raw, _, acf = lib.frames_f0(mags, nb, 1, want_acf=True, **f0_opt)
                 rec_period, _, rec_moved, _ = lib.f0_viterbi(acf, nb, 1, **smooth_opt)
@@ -351,6 +418,9 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
                 got['smooth'] = smooth_columns(pred_moved.cpu().numpy(), rec_moved.cpu().numpy())
             cents, share = f0_summary(np.concatenate([f0_columns(got['f0'][:valid], got['f0_frames'][:valid], sr),
                                                       f0_columns(got['rec_f0'][:valid], got['nb'][:valid], sr)], axis=1))
+        if gv:
+            got['gv'] = gv_columns(gv_pred[0].cpu().numpy(), gv_pred[1].cpu().numpy(), gv_rec[0].cpu().numpy(), gv_rec[1].cpu().numpy(),
+                                   None if gv_sharp is None else gv_sharp[0].cpu().numpy())
         if durations:
             got['dur'] = duration_columns(free_path[1].cpu().numpy(), rec_path[1].cpu().numpy(), batch['text_length'].cpu().numpy(),
                                           free_path[2].cpu().numpy(), free_path[3].cpu().numpy(), rec_path[2].cpu().numpy(),
@@ -368,6 +438,10 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
                 trace[-1].update(period_raw=pred_raw.cpu().numpy(), rec_period_raw=rec_raw.cpu().numpy())
             if durations:
                 trace[-1].update(trace_dur)
+            if gv:
+                trace[-1].update(pred_mags=pmags.cpu().numpy(), rec_mags=mags.cpu().numpy(), lengths=free.lengths.cpu().numpy())
+                if sharpen is not None:
+                    trace[-1].update(sharp_mags=sharp_mags.cpu().numpy())
         for k, v in got.items():
             per[k].append(v)
         losses.append(loss)
@@ -384,6 +458,8 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
             print(('batch %d ' % i) + DUR_LINE % duration_summary(got['dur'][:valid]))
         if f0_smooth:
             print(('batch %d ' % i) + SMOOTH_LINE % smooth_summary(got['smooth'][:valid]))
+        if gv:
+            print(('batch %d ' % i) + gv_line(gv_summary(got['gv'][:valid]), sharpen))
     feeder.close()
     rows = mcd_rows(unpad(batches, [b[0] for b in batches]), *(unpad(batches, per[k]) for k in ('na', 'nb', 'steps', 'cost')))
     if f0:
@@ -400,6 +476,10 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     if f0_smooth:
         rows = np.concatenate([rows, unpad(batches, per['smooth'])], axis=1)
         print('held out: ' + SMOOTH_LINE % smooth_summary(rows[:, -2:]) + ' (untuned costs, %d candidates per frame)' % lib.F0_CANDIDATES)
+    if gv:
+        rows = np.concatenate([rows, unpad(batches, per['gv'])], axis=1)
+        print('held out: ' + gv_line(gv_summary(rows[:, -per['gv'][0].shape[1]:]), sharpen)
+              + ' (linear-frequency cepstra 1 .. %d; untuned; meaningless on an untrained model)' % gv_lifter)
     weight = np.array([valid for _, valid in batches], dtype=np.float64)
     mean_loss = float((np.stack(losses)[:, 0] * weight).sum() / weight.sum())
     print('held out: %d utterances, teacher-forced loss %.1f, MCD-DTW mean %.3f dB worst %.3f dB (utterance %d) over %d cepstra of '
@@ -432,7 +512,22 @@ def parse_args(argv=None):
                          'DUR_COLUMNS (mean absolute difference and bias in ms, path mass per step of both) behind the other columns')
     ap.add_argument('--path-jump', type=int, default=lib.PATH_JUMP, metavar='J',
                     help='--durations: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
-    return ap.parse_args(argv)
+    ap.add_argument('--gv', action='store_true',
+                    help='the global-variance ratio of the predicted against the recorded magnitude frames, per utterance: GV_COLUMNS '
+                         'behind every other column; well below 1 means over-smoothed envelopes.  Taken over this model\'s '
+                         'linear-frequency cepstra, quefrencies 1 .. Q: comparable between checkpoints here, not with published '
+                         'mel-cepstral GV figures; meaningless on an untrained model')
+    ap.add_argument('--gv-lifter', type=int, default=None, metavar='Q', help='--gv: the highest quefrency measured, 2 <= Q <= 64 (default %d)'
+                    % lib.SHARPEN_LIFTER)
+    ap.add_argument('--sharpen', type=float, default=None, metavar='BETA',
+                    help='--gv: also pass the predicted magnitudes through the post-filter of `test --sharpen BETA`, -1 <= BETA <= 1, and '
+                         'score them again (a second column; the GV columns only -- MCD, F0 and durations do not change).  BETA has no '
+                         'tuned default')
+    a = ap.parse_args(argv)
+    if (a.gv_lifter is not None or a.sharpen is not None) and not a.gv:
+        ap.error('--gv-lifter and --sharpen need --gv')
+    a.gv_lifter = lib.SHARPEN_LIFTER if a.gv_lifter is None else a.gv_lifter
+    return a
 
 
 def main(argv=None, config=None):
@@ -443,7 +538,7 @@ def main(argv=None, config=None):
         c.data_path = 'data/%s/' % a.train_set
     checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
     return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0, f0_aligned=a.f0_aligned, durations=a.durations,
-                    path_jump=a.path_jump, f0_smooth=a.f0_smooth)
+                    path_jump=a.path_jump, f0_smooth=a.f0_smooth, gv=a.gv, gv_lifter=a.gv_lifter, sharpen=a.sharpen)
 
 
 if __name__ == '__main__':

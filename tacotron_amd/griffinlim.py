@@ -27,6 +27,9 @@ With `f0` (opt-in) the pitch of the magnitude frames is measured on the device (
 and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective stand-in for listening to those two controls.  With
 'smooth' in it every track is smoothed across frames (taco_f0_viterbi) before it is summarised.
 
+With `sharpen` (opt-in) every magnitude frame goes through a cepstral post-filter first (taco_frames_sharpen): the low quefrencies of
+its envelope are scaled up at unchanged energy, against the over-smoothed envelopes an L1 loss leaves.
+
 With `phase_init='estimate'` (opt-in) Griffin-Lim starts from phases read off the magnitudes (taco_phase_estimate: single-pass
 spectrogram inversion) instead of random ones; with n_iter = 0 that estimate alone is the waveform -- a draft voice at one synthesis pass.
 
@@ -52,7 +55,8 @@ SR = 16000   # test.py:11
 
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
                        lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
-                       rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None):
+                       rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None, sharpen=None,
+                       sharpen_lifter=lib.SHARPEN_LIFTER):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -109,6 +113,11 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     track), and go in as phase0 to the entry point the path takes anyway; `seed` then has no influence.  With n_iter = 0 the
     waveform is the estimate's own: one synthesis pass, a draft voice.  'estimate' together with phase0 is a ValueError.  Return
     shapes do not change.
+    sharpen (opt-in): None or 0 -- nothing is touched, bit for bit -- or a beta in [-1, 1]: directly behind the de-normalisation, in
+    front of the 'model' F0 track, `pitch` and `rate`, the first len_b r frames of every row (all F frames without `lengths`) go
+    through lib.frames_sharpen (taco_frames_sharpen): the quefrencies 2 .. sharpen_lifter of every frame's cepstrum scaled by
+    1 + beta at unchanged frame energy, against the over-smoothed envelopes of an L1-trained post-net.  beta and the lifter (32)
+    are UNTUNED: nobody has listened.  Return shapes do not change.
     Everything stays on the device.  F0 in Hz is SR / period."""
     res = tuple(x for x in vocode(**locals()) if x is not None)   # (the first statement: locals() are the parameters)
     return res[0] if len(res) == 1 else res
@@ -176,7 +185,8 @@ def _f0_tracker(f0, out, r, lengths):
 
 def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
            lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
-           rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None):
+           rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None, sharpen=None,
+           sharpen_lifter=lib.SHARPEN_LIFTER):
     """invert_spectrogram with its result by name: the same parameters, documented there -> Vocoded"""
     if phase_init not in (None, 'random', 'estimate'):
         raise ValueError("invert_spectrogram: phase_init must be None, 'random' or 'estimate', got %r" % (phase_init,))
@@ -198,6 +208,8 @@ def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=No
     # (mag_t, counts, per_unit): the frames the next stage is handed -- row b holds counts[b] * per_unit of them, all without counts.
     # taco_griffinlim_fast / _rows are given r as the frames per unit of an unstretched matrix also without counts: gl_unit
     counts, per_unit, gl_unit = lengths, r if lengths is not None else 1, r
+    if sharpen is not None and float(sharpen) != 0.0:   # (first: every later stage, the F0 tracks included, sees the sharpened frames)
+        mag_t = lib.frames_sharpen(mag_t, sharpen, sharpen_lifter, counts, per_unit)
     if track:
         track('model', mag_t)
     if pitch_curve is not None:

@@ -21,7 +21,7 @@ from . import QUEUES_SET_BY_USER as _QUEUES_SET_BY_USER, TORCH_IMPORTED_FIRST as
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from .argcheck import (int_arg, no_overlap, on_gpu, pow2_bins, step_q_arg, tensor_arg,   # noqa: E402
+from .argcheck import (float_arg, int_arg, no_overlap, on_gpu, pow2_bins, step_q_arg, tensor_arg,   # noqa: E402
                        host_int32 as _host_int32, own_or_given as _own_or_given, unit_interval as _unit_interval)
 
 # If the process may have touched the GPU before importing this package (and did not set the variable itself) the runtime is up
@@ -160,6 +160,9 @@ EXPORTS = {
     'taco_path_curve': (C.c_int, [_P, _P, _I, C.c_int32, _P, _I, _I, _I, _P]),
     'taco_frames_stretch_curve': (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_pitch_curve': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
+    'taco_frames_sharpen': (C.c_int, [_P, _P, _I, C.c_float, _I, _P, _I, _I, _I, _P]),
+    'taco_frames_cepstats_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
+    'taco_frames_cepstats': (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'taco_frames_f0': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     'taco_f0_stats': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _P]),
     'taco_f0_viterbi_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
@@ -1358,6 +1361,82 @@ def frames_pitch_curve(mag_t, frames=None, step_q=None, frames_per_unit=1, lifte
     _check(_lib.taco_frames_pitch_curve(ptr(mag_t), ptr(frames), frames_per_unit, ptr(step_q), lifter, ptr(out), B, Cw, F, stream_ptr()),
            'taco_frames_pitch_curve')
     return out
+
+
+SHARPEN_FIRST, SHARPEN_MIN_BETA, SHARPEN_MAX_BETA = 2, -1.0, 1.0   # include/taco_hip.h
+SHARPEN_LIFTER = 32   # UNTUNED, like every beta: nobody has listened
+
+
+def _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit):
+    """the argument checks frames_sharpen and frames_cepstats share -> (B, C, F, device, frames_per_unit, lifter)"""
+    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
+    dev = mag_t.device
+    pow2_bins(who, Cw)
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, SHARPEN_FIRST, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
+    return B, Cw, F, dev, frames_per_unit, lifter
+
+
+def frames_sharpen(mag_t, beta, lifter=SHARPEN_LIFTER, frames=None, frames_per_unit=1, out=None):
+    """The cepstral post-filter (include/taco_hip.h taco_frames_sharpen): mag_t (B, C, F) fp32 on the device, C - 1 a power of two in
+    [8, 1024] -> out (B, C, F) fp32: in the first F_b = clamp(frames[b] * frames_per_unit, 0, F) frames of row b the quefrencies
+    2 .. lifter of the frame's cepstrum are scaled by 1 + beta at unchanged frame energy, zeros behind.  beta: a number in [-1, 1]
+    for the whole batch; 0 is a bit copy.  lifter: 2 .. min(64, (C - 1) / 2); the default 32 is untuned.  frames: (B) int32 on the
+    device, or None (all F frames).  out: the caller's own buffer; default: a fresh one.  Enqueued on the current stream; nothing
+    is read back and nothing waits."""
+    who = 'frames_sharpen'
+    B, Cw, F, dev, frames_per_unit, lifter = _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit)
+    beta = float_arg(who, 'beta', beta, SHARPEN_MIN_BETA, SHARPEN_MAX_BETA)
+    out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_sharpen(ptr(mag_t), ptr(frames), frames_per_unit, beta, lifter, ptr(out), B, Cw, F, stream_ptr()),
+           'taco_frames_sharpen')
+    return out
+
+
+def frames_cepstats_workspace_bytes(B, C_bins, F, lifter=SHARPEN_LIFTER) -> int:
+    return _size('taco_frames_cepstats_workspace_bytes', B, C_bins, F, lifter)
+
+
+def frames_cepstats(mag_t, lifter=SHARPEN_LIFTER, frames=None, frames_per_unit=1, out=None, workspace=None):
+    """The raw material of the global variance (include/taco_hip.h taco_frames_cepstats): mag_t (B, C, F) fp32 on the device ->
+    (sums (B, lifter + 1, 2) fp64, count (B) int32), device tensors: per row the sums over its first F_b frames of each cepstral
+    coefficient c[n], n = 0 .. lifter, and of its square, and F_b.  gv_variance() makes variances of them on the host.  frames: (B)
+    int32 on the device, or None.  out: the caller's own (sums, count); workspace: uint8, frames_cepstats_workspace_bytes(B, C, F,
+    lifter) bytes; default: fresh ones.  Enqueued on the current stream; nothing is read back and nothing waits."""
+    who = 'frames_cepstats'
+    B, Cw, F, dev, frames_per_unit, lifter = _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit)
+    if out is not None and len(out) != 2:
+        raise ValueError('%s: out must be (sums, count)' % who)
+    sums = _own_or_given(None if out is None else out[0], (B, lifter + 1, 2), torch.float64, dev, who + ': sums')
+    count = _own_or_given(None if out is None else out[1], (B,), torch.int32, dev, who + ': count')
+    if workspace is not None:
+        tensor_arg(who, 'workspace', workspace, torch.uint8, ('bytes',), dev)
+    on_gpu(who, 'mag_t', dev)
+    workspace = _own_or_given(workspace, (frames_cepstats_workspace_bytes(B, Cw, F, lifter),), torch.uint8, dev, who + ': workspace')
+    _check(_lib.taco_frames_cepstats(ptr(mag_t), ptr(frames), frames_per_unit, lifter, ptr(sums), ptr(count), ptr(workspace), B, Cw, F,
+                                     stream_ptr()), 'taco_frames_cepstats')
+    return sums, count
+
+
+def gv_variance(sums, count):
+    """sums (..., Q + 1, 2) and count (...) as frames_cepstats returns them, on the HOST (NumPy) -> var (..., Q + 1) float64:
+    sums[n, 1] / count - (sums[n, 0] / count)^2; NaN where count < 2"""
+    sums, count = np.asarray(sums, dtype=np.float64), np.asarray(count, dtype=np.float64)[..., None]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        var = sums[..., 1] / count - (sums[..., 0] / count) ** 2
+    return np.where(count >= 2, var, np.nan)
+
+
+def gv_ratio(sums_pred, n_pred, sums_rec, n_rec):
+    """The global-variance ratio per utterance, on the HOST: exp(mean over n = 1 .. Q of log(var_pred[n] / var_rec[n])) of this
+    model's linear-frequency cepstra -- below 1: the prediction is over-smoothed.  NaN for an utterance with fewer than 2 frames
+    on either side (or a variance that is not positive)."""
+    vp, vr = gv_variance(sums_pred, n_pred)[..., 1:], gv_variance(sums_rec, n_rec)[..., 1:]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.exp(np.log(vp / vr).mean(axis=-1))
 
 
 F0_MAX_LAGS = 512          # TACO_F0_MAX_LAGS

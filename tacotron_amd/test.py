@@ -95,7 +95,17 @@ ceiling on the TRUE peak (dBTP), read between the samples through a P-phase inte
 look-ahead (default 1.5 ms), N the passes (default 2: the second re-aims the gain at the target).  These defaults are untuned and
 nobody has listened to a limited file.  prompt_NNN.wav holds the limited int16 samples, prompt_NNN_limit.npy holds (tp_in, G, g_min,
 peak_out, n_b, n_limited, I_reached, tp_out) as float64 in place of _loud.npy, and one line per prompt gives the loudness before
-and after, the true peak and how much was limited.  With --long the JOINED prompt is limited.  Without --limit no new code is reached."""
+and after, the true peak and how much was limited.  With --long the JOINED prompt is limited.  Without --limit no new code is reached.
+--sharpen BETA [--sharpen-lifter Q] (opt-in, not in the reference): spectral sharpening, -1 <= BETA <= 1.  Magnitudes trained under an
+L1 loss have over-smoothed envelopes; directly behind the de-normalisation -- in front of --pitch, --rate, --prosody and --f0 -- every
+magnitude frame goes through a cepstral post-filter on the device (lib.frames_sharpen, taco_frames_sharpen): the quefrencies 2 .. Q of
+its cepstrum (default 32) are scaled by 1 + BETA and the frame keeps its energy.  prompt_NNN_sharpen.npy holds (beta, lifter) as
+float64; every other file keeps its size, and the spectrogram, alignment, length and score files stay the model's own.  --sharpen 0 is
+a run without the flag: the same files, byte for byte.  BETA and Q are UNTUNED and nobody has listened to the result;
+`python -m tacotron_amd.evaluate --gv --sharpen BETA` gives the global-variance ratio with and without it.  It combines with every option
+above; with --long every piece is sharpened.  The two settings are not fields of the options record of test(): they travel as
+Config.sharpen / Config.sharpen_lifter, next to the paths the command line also leaves there, and a run reads them from its resolved
+options like every other."""
 from __future__ import annotations
 
 import argparse
@@ -423,11 +433,13 @@ class Options(_OptionFields):
         if long_options(o.long) is not None and not o.vocode:
             raise ValueError('long (--long) joins waveforms: it needs vocode')
 
-    def resolved(self):
+    def resolved(self, sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER):
         """check(), then the options as a run reads them, a Resolved: `gl_init` None for 'random', `f0` None or (lo, hi), `f0_smooth`
         None or the number of candidates, `long` None or (pause_ms, fade_ms), `prosody` None when not given -- given, it holds
-        `path_jump` to its range as `timings` does; ValueError"""
+        `path_jump` to its range as `timings` does.  sharpen / sharpen_lifter (--sharpen, --sharpen-lifter; Config.sharpen /
+        Config.sharpen_lifter): checked by sharpen_options, the Resolved holds what it returns; ValueError"""
         self.check()
+        sharpen = sharpen_options(sharpen, sharpen_lifter, self.vocode)
         level = None if self.loudness is None else dict(target=float(self.loudness),
                                                         ceiling_db=PEAK_DB if self.peak_db is None else float(self.peak_db))
         if self.limit:
@@ -438,15 +450,36 @@ class Options(_OptionFields):
         f0, long = f0_range(self.f0), long_options(self.long)
         return Resolved(**dict(vars(self), gl_init=None if self.gl_init == 'random' else self.gl_init, f0=f0, f0_smooth=smooth, long=long,
                                prosody=self.prosody if given(self.prosody) else None), level=level,
-                        finish=self.deemphasis is not None or self.trim_db is not None or long is not None or level is not None)
+                        finish=self.deemphasis is not None or self.trim_db is not None or long is not None or level is not None,
+                        sharpen=sharpen)
 
 
 @dataclasses.dataclass(frozen=True)
 class Resolved(Options):
     """Options.resolved(): the options in the form a run reads, and what follows from them.  level: None, or level_waveform's target,
-    ceiling_db and, with `limit`, limiter keywords; finish: whether the waveform is finished on the device"""
+    ceiling_db and, with `limit`, limiter keywords; finish: whether the waveform is finished on the device; sharpen: None, or
+    (beta, lifter) of the post-filter in front of every other stage"""
     level: Any = None
     finish: bool = False
+    sharpen: Any = None
+
+
+def sharpen_options(sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, vocode=True):
+    """--sharpen BETA / --sharpen-lifter Q -> None for no post-filter (BETA None or 0: every file is what it was), else
+    (beta, lifter), checked against lib.frames_sharpen's ranges at the 1025 bins of the model; ValueError"""
+    if sharpen is None:
+        return None
+    try:
+        beta = float(sharpen)
+        ok = not isinstance(sharpen, bool) and lib.SHARPEN_MIN_BETA <= beta <= lib.SHARPEN_MAX_BETA   # (NaN fails)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('sharpen (--sharpen) must be a number in [%g, %g], got %r' % (lib.SHARPEN_MIN_BETA, lib.SHARPEN_MAX_BETA, sharpen))
+    lifter = lib.int_arg('check_options', 'sharpen_lifter (--sharpen-lifter)', sharpen_lifter, lib.SHARPEN_FIRST, lib.PITCH_MAX_LIFTER)
+    if not vocode:
+        raise ValueError('sharpen (--sharpen) filters the magnitudes in front of Griffin-Lim: it needs vocode')
+    return None if beta == 0.0 else (beta, lifter)
 
 
 def check_options(*, n_iter=50, vocode=True, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None,
@@ -465,7 +498,7 @@ def limit_options(limit_ms=None, true_peak=None, limit_passes=None):
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None):
+                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None, sharpen=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -480,7 +513,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     prosody (--prosody): (the prompt's (L, 2) per-character (dur_q, step_q), Fo_b): the table is written as _prosody.npy (int32); wav is
     then the waveform behind the stretch curve and keeps 300 (Fo_b - 1) samples, whatever len_b says.
     loud (--loudness): the prompt's loud_row, written as _loud.npy (float64); pcm then holds the levelled samples.  With --limit: the
-    prompt's limit_row, whose first 8 values are written as _limit.npy instead."""
+    prompt's limit_row, whose first 8 values are written as _limit.npy instead.
+    sharpen (--sharpen): (beta, lifter) of the post-filter, written as _sharpen.npy (float64); nothing else depends on it."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -494,6 +528,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_rate.npy', np.asarray(rate, dtype=np.int32))
     if pitch is not None:
         np.save(path + '_pitch.npy', np.asarray(pitch, dtype=np.int32))
+    if sharpen is not None:
+        np.save(path + '_sharpen.npy', np.asarray(sharpen, dtype=np.float64))
     if prosody is not None:
         if wav is not None:
             wav = wav[:300 * max(0, int(prosody[1]) - 1)]
@@ -599,8 +635,13 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     is the ceiling on the TRUE peak (dBTP).  None: LIMIT_MS of look-ahead, lib.LIMIT_P x oversampling, LIMIT_PASSES passes -- untuned,
     and nobody has listened to a limited file.  prompt_NNN.wav holds the limited int16 samples, prompt_NNN_limit.npy (tp_in, G, g_min, peak_out, n_b,
     n_limited, I_reached, tp_out) as float64 (no _loud.npy), and limit_line() is printed per prompt.  Without it lib.wave_limit is
-    never reached."""
-    opt = Options(**{k: v for k, v in locals().items() if k in Options.__dataclass_fields__}).resolved()   # (locals(): the parameters)
+    never reached.
+    `config.sharpen` / `config.sharpen_lifter` (need `vocode`; Config's defaults: None, 32): None or 0 -- every file is what it was -- or
+    a beta in [-1, 1]: the magnitudes of every row go through the cepstral post-filter first (vocode(sharpen=...), lib.frames_sharpen),
+    in front of `pitch`, `rate`, `prosody` and `f0`, over the row's own len_b r frames wherever the vocoder gets the lengths, else over
+    all frames; with `long`, every piece.  prompt_NNN_sharpen.npy holds (beta, lifter) as float64.  Untuned; nobody has listened."""
+    opt = Options(**{k: v for k, v in locals().items() if k in Options.__dataclass_fields__}).resolved(   # (locals(): the parameters)
+        getattr(config, 'sharpen', None), getattr(config, 'sharpen_lifter', lib.SHARPEN_LIFTER))
     run = Run(config, opt, prompts, out_dir, checkpoint, speaker)
     n = _test_long(run) if opt.long is not None else _test_rows(run, prompts)
     print('wrote %d samples to %s' % (n, out_dir))
@@ -739,6 +780,8 @@ class Run:
                 kw['f0'] = dict(self.f0_tables(), lengths=lengths)
             if self.pros is not None:
                 kw.update(self.curves(found[0], batch, n), dur_q_max=self.pros_max)
+            if o.sharpen is not None:
+                kw.update(sharpen=o.sharpen[0], sharpen_lifter=o.sharpen[1])
             v = vocode(out, mean, std, c.r, n_iter=o.n_iter, seed=n, momentum=o.gl_momentum, want_conv=o.gl_momentum is not None,
                        phase_init=o.gl_init, lifter=o.lifter, **kw)
             if v.tracks is not None:
@@ -833,7 +876,8 @@ def _test_rows(run, prompts):
             dur, words = run.timing_of(n, rec, text_len)
             write_prompt(run.out_dir, n, run.config.r, rec.spec, rec.al, rec.wav, None if rec.lengths is None else int(rec.lengths), rec.pcm,
                          rec.trim, rec.conv, ascore=rec.scores, rate=run.rate_of(n, rec), pitch=run.pitch_of(n), f0=run.f0_of(n, rec),
-                         dur=dur, prosody=None if rec.curved is None else (run.pros[n], int(rec.curved[0])), loud=rec.louds)
+                         dur=dur, prosody=None if rec.curved is None else (run.pros[n], int(rec.curved[0])), loud=rec.louds,
+                         sharpen=run.opt.sharpen)
             if rec.louds is not None:
                 print(level_line('prompt %d' % n, rec.louds, run.opt.level))
             if words is not None:
@@ -890,7 +934,7 @@ def _test_long(run):
                     words += piece_words
                 write_prompt(run.out_dir, p, run.config.r, rec.spec, rec.al, None, int(rec.lengths), None, rec.trim, rec.conv,
                              piece=None if b - a == 1 else k - a, ascore=rec.scores, rate=run.rate_of(row + k, rec), pitch=run.pitch_of(row + k),
-                             f0=f0rows, dur=dur)
+                             f0=f0rows, dur=dur, sharpen=o.sharpen)
                 names = run.marks(rec.scores, text_len) if rec.scores is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
@@ -1013,6 +1057,13 @@ def parse_args(argv=None):
                     help='--limit: the oversampling of the true-peak meter, 1 <= P <= 8; 1 limits the sample peak (default %d)' % lib.LIMIT_P)
     ap.add_argument('--limit-passes', type=int, default=None, metavar='N',
                     help='--limit: passes of the limiter, each after the first re-aimed at the target, 1 <= N <= 8 (default %d)' % LIMIT_PASSES)
+    ap.add_argument('--sharpen', type=float, default=None, metavar='BETA',
+                    help='spectral sharpening, -1 <= BETA <= 1: a cepstral post-filter on the device in front of every other stage scales '
+                         'the quefrencies 2 .. Q of every magnitude frame by 1 + BETA at unchanged frame energy, against the over-smoothed '
+                         'envelopes of an L1-trained model; 0 is a run without the flag; writes prompt_NNN_sharpen.npy (untuned; nobody has '
+                         'listened; not in the reference)')
+    ap.add_argument('--sharpen-lifter', type=int, default=None, metavar='Q',
+                    help='--sharpen: the highest quefrency scaled, 2 <= Q <= 64 (default %d, untuned)' % lib.SHARPEN_LIFTER)
     ap.add_argument('--path-jump', type=int, default=None, metavar='J',
                     help='--timings / --prosody: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
@@ -1027,8 +1078,11 @@ def parse_args(argv=None):
     if a.path_jump is not None and not a.timings and a.prosody is None:
         ap.error('--path-jump needs --timings or --prosody')
     a.path_jump = lib.PATH_JUMP if a.path_jump is None else a.path_jump
+    if a.sharpen_lifter is not None and a.sharpen is None:
+        ap.error('--sharpen-lifter needs --sharpen')
+    a.sharpen_lifter = lib.SHARPEN_LIFTER if a.sharpen_lifter is None else a.sharpen_lifter
     try:
-        Options(**option_keywords(a)).resolved()
+        Options(**option_keywords(a)).resolved(a.sharpen, a.sharpen_lifter)
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -1043,5 +1097,6 @@ if __name__ == '__main__':
     c = Config()
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
+    c.sharpen, c.sharpen_lifter = a.sharpen, a.sharpen_lifter
     print('Building Tacotron')
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, **option_keywords(a))
