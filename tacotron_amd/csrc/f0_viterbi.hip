@@ -22,6 +22,7 @@
 // are in flight while a step is computed.  Behind the chain one lane walks the back pointers into an LDS copy of the path, and the
 // workgroup writes period and strength (the pick's parabola on acf), the zeros behind F_b, and the counts (integer LDS atomics: no
 // order dependence).  No float atomics anywhere: the same arguments give the same bits.
+#include "frames.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -37,15 +38,6 @@ constexpr size_t kF0vLdsBudget = 96 * 1024;
 constexpr int kF0vNone = 0x7fffffff;
 static_assert(TACO_F0_MAX_CAND + 1 == kF0vSlots, "the unvoiced state is the last of sixteen slots");
 static_assert(TACO_F0_MAX_LAGS <= 32 * kF0vParts, "a part's run of lags fits a 32-bit candidate mask");
-
-__device__ __forceinline__ int f0v_row_frames(const int32_t* __restrict__ frames, int frames_per_unit, int b, int F) {
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  return __builtin_amdgcn_readfirstlane(Fb);
-}
 
 inline size_t f0v_cand_lds(int L) { return ((size_t)L * kF0vFrames + 6 * kF0vParts * kF0vFrames) * 4; }
 inline size_t f0v_path_lds(int F) { return (size_t)F * 8 + (size_t)((F + 7) & ~7); }
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(kF0vParts* kF0vFrames) void f0_candidates_kernel(co
   float* keep_v = reinterpret_cast<float*>(pi + 2 * kF0vParts * kF0vFrames);
   int* keep_i = reinterpret_cast<int*>(keep_v + kF0vParts * kF0vFrames);
   const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
-  const int Fb = f0v_row_frames(frames, frames_per_unit, b, F);
+  const int Fb = row_frames_uniform(frames, frames_per_unit, b, F);
   const int tid = threadIdx.x, fl = tid & 31, pt = tid >> 5;
   const int f0 = tile * kF0vFrames, f = f0 + fl;
   if (f0 >= Fb) return;   // (uniform) nothing of this tile is ever read
@@ -165,7 +157,7 @@ __global__ __launch_bounds__(kF0vPathThreads) void f0_path_kernel(const float* _
   uint64_t* bpw = f0p_lds;
   uint8_t* sl = reinterpret_cast<uint8_t*>(f0p_lds + F);
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int Fb = f0v_row_frames(frames, frames_per_unit, b, F);
+  const int Fb = row_frames_uniform(frames, frames_per_unit, b, F);
   period += (int64_t)b * F, strength += (int64_t)b * F, counts += (int64_t)b * 4, score += b;
   ws_i += (int64_t)b * F * kF0vSlots, ws_v += (int64_t)b * F * kF0vSlots, ws_lg += (int64_t)b * F * kF0vSlots;
   if (tid < 3) tally[tid] = 0;

@@ -4,7 +4,10 @@
 // taco_path_f0_scores).  Every entry point stands behind its kernels with the refusals that guard them; each kernel's comment has its
 // form and why.  The cosine products of frames_pitch_kernel, frames_sharpen_kernel, frames_cepstats_kernel and
 // frames_f0_kernel are fp32 MFMAs; everything else here is bound by memory.
+#include <type_traits>
+
 #include "common.h"
+#include "frames.h"
 #include "kernels.h"
 
 namespace {
@@ -77,10 +80,7 @@ __global__ __launch_bounds__(256) void frames_stretch_kernel(const float* __rest
     Fob = Fob < 0 ? 0 : (Fob > Fo ? Fo : Fob);
     Fob = __builtin_amdgcn_readfirstlane(Fob);
   } else {
-    if (frames) {
-      const int64_t n = (int64_t)frames[b] * frames_per_unit;
-      Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-    }
+    Fb = row_frames(frames, frames_per_unit, b, F);
     if (step_q) {
       s = step_q[b];
       s = s < TACO_STRETCH_MIN_STEP ? TACO_STRETCH_MIN_STEP : (s > TACO_STRETCH_MAX_STEP ? TACO_STRETCH_MAX_STEP : s);
@@ -164,12 +164,7 @@ __global__ __launch_bounds__(kMapThreads) void frames_stretch_map_kernel(const i
   __shared__ uint32_t D[TACO_STRETCH_MAX_FRAMES];
   __shared__ uint32_t part[kMapThreads];
   const int b = blockIdx.x, tid = threadIdx.x;
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  Fb = __builtin_amdgcn_readfirstlane(Fb);
+  const int Fb = row_frames_uniform(frames, frames_per_unit, b, F);
   src += (int64_t)b * Fo;
   if (Fb == 0) {   // (uniform)
     for (int j = tid; j < Fo; j += kMapThreads) src[j] = -1;
@@ -238,202 +233,59 @@ __global__ __launch_bounds__(kMapThreads) void frames_stretch_map_kernel(const i
 constexpr int kPitchFrames = 32;
 constexpr int kPitchMaxC = 1025;
 constexpr int kPitchBatch = 8;         // bins a thread has in flight in the copy and in the warp
-//
-// taco_frames_pitch_curve (a pitch contour) is CURVE = true: step_q is (B, F) and the step belongs to the frame, that is to the lane
-// (its low five bits), so s is a per-lane register from here on and costs no LDS.  The cepstrum and the envelope do not know s; the
-// warp's k * s >> 16 takes it per lane.  The copy branch is taken when all 32 frames of the tile are at ONE or behind F_b -- every
-// wave holds the same 32 frames in both halves, so one ballot per wave gives every wave the same answer -- and a ONE lane of a mixed
-// tile stores its source value, no log / exp round trip.
-template <int NB, int kPitchWaves, bool CURVE>
-__global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
-                                                                         int frames_per_unit, const int32_t* __restrict__ step_q, int Q,
-                                                                         float* __restrict__ out, int C, int F, int ntile) {
-  constexpr int NR = 32 * NB;                                // cepstrum rows n = 1 .. NR
-  __shared__ float tab[2 * (kPitchMaxC - 1)];
-  __shared__ float cep[(NR + 1) * kPitchFrames];             // c[n][f], n = 0 .. NR
-  __shared__ float env[kPitchMaxC * kPitchFrames];           // E[k][f]; before that the waves' partial cepstra
-  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
-  int Fb = F, s = TACO_PITCH_ONE;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  if constexpr (!CURVE) {
-    if (step_q) {
-      s = step_q[b];
-      s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
-    }
-  }
-  Fb = __builtin_amdgcn_readfirstlane(Fb);
-  if constexpr (!CURVE) s = __builtin_amdgcn_readfirstlane(s);
-  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int f0 = tile * kPitchFrames, f = f0 + fl;
-  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
-  float* __restrict__ dst = out + (int64_t)b * C * F + f;
-  const bool live = f < Fb, inside = f < F;
-  bool plain;
-  if constexpr (CURVE) {
-    if (step_q && live) {   // (a frame behind F_b keeps ONE: its step is never read)
-      s = step_q[(int64_t)b * F + f];
-      s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
-    }
-    plain = __ballot(live && s != TACO_PITCH_ONE) == 0;
-  } else {
-    plain = f0 >= Fb || s == TACO_PITCH_ONE;
-  }
-  if (plain) {   // (uniform) nothing to shift: zeros behind the row's end, the row's own bits in front of it
-    for (int kb = 2 * wave + h; kb < C; kb += 2 * kPitchWaves * kPitchBatch) {   // (kPitchBatch loads in flight per thread)
-      float m[kPitchBatch];
-#pragma unroll
-      for (int u = 0; u < kPitchBatch; ++u) {
-        const int k = kb + 2 * kPitchWaves * u;
-        m[u] = (live && k < C) ? src[k * F] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kPitchBatch; ++u) {
-        const int k = kb + 2 * kPitchWaves * u;
-        if (inside && k < C) dst[k * F] = m[u];
-      }
-    }
-    return;
-  }
-  const int N = 2 * (C - 1), mask = N - 1;
-  for (int j = tid; j < N; j += 64 * kPitchWaves) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
-  __syncthreads();
 
-  // ---- cepstrum ----
-  const float wt = 2.0f / (float)N;   // (a power of two: the weight and the 1 / N cost no rounding)
-  f32x16 acc[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-  float c0p = 0.f;
-  float m[4], nx[4];   // four bin pairs per trip, the next trip's loads issued in front of this trip's arithmetic
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int k = 2 * wave + 2 * kPitchWaves * u + h;
-    m[u] = (live && k < C) ? src[k * F] : 1.0f;
-  }
-  for (int k0 = 2 * wave; k0 < C; k0 += 8 * kPitchWaves) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = k0 + 8 * kPitchWaves + 2 * kPitchWaves * u + h;
-      nx[u] = (live && k < C) ? src[k * F] : 1.0f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = k0 + 2 * kPitchWaves * u + h;   // (k >= C: m = 1, v = 0, and the table is read at some valid index)
-      const float v = logf(fmaxf(m[u], TACO_PITCH_FLOOR)) * ((k == 0 || k == C - 1) ? 0.5f * wt : wt);
-      c0p += v;
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + fl) * k) & mask], v, acc[nb], 0, 0, 0);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) m[u] = nx[u];
-  }
-  float* part = env;                       // [wave][n - 1][f], then [wave][h][f] for c[0]
-  float* part0 = env + kPitchWaves * NR * kPitchFrames;
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-      part[((wave * NR) + 32 * nb + (r & 3) + 8 * (r >> 2) + 4 * h) * kPitchFrames + fl] = acc[nb][r];
-  part0[(2 * wave + h) * kPitchFrames + fl] = c0p;
-  __syncthreads();
-  for (int e = tid; e < NR * kPitchFrames; e += 64 * kPitchWaves) {   // e = (n - 1) * 32 + f
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < kPitchWaves; ++w) t += part[w * NR * kPitchFrames + e];
-    cep[kPitchFrames + e] = (e >> 5) < Q ? t : 0.f;   // the rectangular lifter
-  }
-  if (tid < kPitchFrames) {
-    float t = 0.f;
-#pragma unroll
-    for (int w = 0; w < 2 * kPitchWaves; ++w) t += part0[w * kPitchFrames + tid];
-    cep[tid] = t;
-  }
-  __syncthreads();   // (nothing reads the partials from here on: env is the envelope's)
+// ---- what the kernels over tiles of 32 frames share (pitch, sharpen, cepstats, F0) ----
+// Where a thread stands: row b with its F_b frames, tile f0 .. f0 + 31, this lane's frame f = f0 + fl (fl: the lane's low five
+// bits, h: its half of the wave), `live` in front of F_b, `inside` in front of F.  b, Fb, f0 and wave are uniform.
+struct FrameTile {
+  int b, Fb, f0, f, fl, h, wave;
+  bool live, inside;
+};
+__device__ __forceinline__ FrameTile frame_tile(const int32_t* __restrict__ frames, int frames_per_unit, int F, int ntile) {
+  FrameTile t;
+  const int tile = (int)(blockIdx.x % (uint32_t)ntile), lane = threadIdx.x & 63;
+  t.b = (int)(blockIdx.x / (uint32_t)ntile);
+  t.Fb = row_frames_uniform(frames, frames_per_unit, t.b, F);
+  t.fl = lane & 31, t.h = lane >> 5;
+  t.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  t.f0 = tile * kPitchFrames, t.f = t.f0 + t.fl;
+  t.live = t.f < t.Fb, t.inside = t.f < F;
+  return t;
+}
 
-  // ---- envelope ----
-  const float c0 = cep[fl];
-  float cb[NB][16];   // 2 c[n][f], n = 32 nb + 1 + 2 j + h: this lane's B operands
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) cb[nb][j] = 2.0f * cep[(32 * nb + 1 + 2 * j + h) * kPitchFrames + fl];
-  if (tid < kPitchFrames) {   // bin C - 1: cos(pi n) = (-1)^n
-    float t = c0;
-    for (int n = 1; n <= NR; ++n) {
-      const float c2 = 2.0f * cep[n * kPitchFrames + tid];
-      t += (n & 1) ? -c2 : c2;
-    }
-    env[(C - 1) * kPitchFrames + tid] = t;
-  }
-  const int nblk = (C - 1 + 31) >> 5;
-  for (int kb = wave; kb < nblk; kb += kPitchWaves) {
-    const int k = 32 * kb + fl;
-    f32x16 d;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) d[r] = c0;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        d = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + 2 * j + h) * k) & mask], cb[nb][j], d, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int kk = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (kk < C - 1) env[kk * kPitchFrames + fl] = d[r];
-    }
-  }
-  __syncthreads();
+// tab[j] = cos(2 pi j / N), j < N, by the nthreads threads of the workgroup; the caller synchronises
+__device__ __forceinline__ void fill_cos_table(float* tab, int N, int nthreads) {
+  for (int j = threadIdx.x; j < N; j += nthreads) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
+}
 
-  // ---- warp of the excitation, output ----  kPitchBatch bins per trip: every load of the trip first, at indices clamped into the
-  // frame (a value from a clamped index is never used)
-  for (int kb = 2 * wave + h; kb < C; kb += 2 * kPitchWaves * kPitchBatch) {
-    float m0[kPitchBatch], m1[kPitchBatch];
-    if (live) {
+// Nothing to compute for this tile: zeros behind the row's end, the row's own bits in front of it (kPitchBatch loads in flight per
+// thread).  src and dst point at this lane's frame of bin 0.
+template <int kWaves>
+__device__ __forceinline__ void copy_tile(const float* __restrict__ src, float* __restrict__ dst, const FrameTile& t, int C, int F) {
+  for (int kb = 2 * t.wave + t.h; kb < C; kb += 2 * kWaves * kPitchBatch) {
+    float m[kPitchBatch];
 #pragma unroll
-      for (int u = 0; u < kPitchBatch; ++u) {
-        const int k = min(kb + 2 * kPitchWaves * u, C - 1);
-        const int i = (int)(((uint32_t)k * (uint32_t)s) >> 16);   // (k s <= 1024 * 2^17)
-        m0[u] = src[min(i, C - 1) * F];
-        m1[u] = src[min(i + 1, C - 1) * F];
-      }
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kWaves * u;
+      m[u] = (t.live && k < C) ? src[k * F] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < kPitchBatch; ++u) {
-      const int k = kb + 2 * kPitchWaves * u;
-      if (k >= C) break;
-      float y = 0.f;
-      if (live) {
-        const uint32_t p = (uint32_t)k * (uint32_t)s;
-        const int i = (int)(p >> 16), ia = min(i, C - 1), ib = min(i + 1, C - 1);
-        const uint32_t frac = p & 0xFFFFu;
-        const float r0 = logf(fmaxf(m0[u], TACO_PITCH_FLOOR)) - env[ia * kPitchFrames + fl];
-        const float r1 = logf(fmaxf(m1[u], TACO_PITCH_FLOOR)) - env[ib * kPitchFrames + fl];
-        // i < C - 1: between two bins; i == C - 1 with w == 0: the top bin itself; beyond it the envelope alone
-        const float rp = i < C - 1 ? r0 + (float)frac * (1.0f / 65536.0f) * (r1 - r0) : ((i == C - 1 && frac == 0u) ? r0 : 0.f);
-        y = expf(env[k * kPitchFrames + fl] + rp);
-        if constexpr (CURVE)
-          if (s == TACO_PITCH_ONE) y = m0[u];   // (k s >> 16 == k: m0 is the frame's own bin) a ONE frame among shifted ones
-      }
-      if (inside) dst[k * F] = y;
+      const int k = kb + 2 * kWaves * u;
+      if (t.inside && k < C) dst[k * F] = m[u];
     }
   }
 }
 
-// The cepstrum stage of frames_pitch_kernel restated for the two kernels below (frames_pitch_kernel keeps its own text, so its bits
-// cannot move): c[n][f], n = 0 .. 32 NB, of the 32 frames of a tile into cep[n * 32 + f], WITHOUT a lifter.  The same dealing of the
-// bin pairs to kWaves waves, the same chains, the same fold of the waves' partials in wave order; `part` is scratch of
+// The cepstrum stage: c[n][f], n = 0 .. 32 NB, of the 32 frames of a tile into cep[n * 32 + f], rows behind the rectangular lifter
+// Q zeroed.  The bin pairs (k, k + 1) are dealt to the kWaves waves round robin, each an ordered chain of 32x32x2 fp32 MFMAs, and the
+// waves' partial tiles are folded through LDS in wave order; c[0] is a plain sum beside it.  This is the ONE text of these chains:
+// "the same fp32 cepstra" in the pitch, sharpen and cepstats kernels means this function.  `part` is scratch of
 // (kWaves 32 NB + 2 kWaves) x 32 floats.  Called by every thread of the workgroup (it has barriers); tab is filled and synchronised
 // by the caller.  Behind it cep is complete and visible, and nothing reads part any more.
 template <int NB, int kWaves>
-__device__ __forceinline__ void cepstrum_tile(const float* __restrict__ src, bool live, int C, int F, const float* tab, float* cep,
-                                              float* part) {
+__device__ __forceinline__ void cepstrum_tile(const float* __restrict__ src, bool live, int Q, int C, int F, const float* tab,
+                                              float* cep, float* part) {
   constexpr int NR = 32 * NB;
   const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -481,7 +333,7 @@ __device__ __forceinline__ void cepstrum_tile(const float* __restrict__ src, boo
     float t = 0.f;
 #pragma unroll
     for (int w = 0; w < kWaves; ++w) t += part[w * NR * kPitchFrames + e];
-    cep[kPitchFrames + e] = t;
+    cep[kPitchFrames + e] = (e >> 5) < Q ? t : 0.f;   // the rectangular lifter
   }
   if (tid < kPitchFrames) {
     float t = 0.f;
@@ -490,6 +342,132 @@ __device__ __forceinline__ void cepstrum_tile(const float* __restrict__ src, boo
     cep[tid] = t;
   }
   __syncthreads();
+}
+
+// The cosine synthesis stage: X[k][f] = init[f] + sum_n cos(2 pi n k / N) (scale c[n][f]) over n = first .. last of the tile's cepstra
+// into X[k * 32 + f].  Bins k < C - 1 in blocks of 32 dealt to the waves, 16 NB MFMAs per block in ascending (nb, j) with rows outside
+// first .. last zero in the B operands; the top bin C - 1 (cos = (-1)^n) is a sum on the side in ascending n.  init is this lane's
+// frame's start value.  Called by every thread of the workgroup; behind it X is complete and visible.
+template <int NB, int kWaves>
+__device__ __forceinline__ void cosine_tile(const float* tab, const float* cep, float init, float scale, int first, int last, int C,
+                                            float* X) {
+  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int mask = 2 * (C - 1) - 1;
+  float cb[NB][16];   // scale c[n][f], n = 32 nb + 1 + 2 j + h: this lane's B operands
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int n = 32 * nb + 1 + 2 * j + h;
+      cb[nb][j] = (n >= first && n <= last) ? scale * cep[n * kPitchFrames + fl] : 0.f;
+    }
+  if (tid < kPitchFrames) {   // bin C - 1: cos(pi n) = (-1)^n
+    float t = init;
+    for (int n = first; n <= last; ++n) {
+      const float c2 = scale * cep[n * kPitchFrames + tid];
+      t += (n & 1) ? -c2 : c2;
+    }
+    X[(C - 1) * kPitchFrames + tid] = t;
+  }
+  const int nblk = (C - 1 + 31) >> 5;
+  for (int kb = wave; kb < nblk; kb += kWaves) {
+    const int k = 32 * kb + fl;
+    f32x16 d;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d[r] = init;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        d = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + 2 * j + h) * k) & mask], cb[nb][j], d, 0, 0, 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int kk = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
+      if (kk < C - 1) X[kk * kPitchFrames + fl] = d[r];
+    }
+  }
+  __syncthreads();
+}
+
+// taco_frames_pitch_curve (a pitch contour) is CURVE = true: step_q is (B, F) and the step belongs to the frame, that is to the lane
+// (its low five bits), so s is a per-lane register from here on and costs no LDS.  The cepstrum and the envelope do not know s; the
+// warp's k * s >> 16 takes it per lane.  The copy branch is taken when all 32 frames of the tile are at ONE or behind F_b -- every
+// wave holds the same 32 frames in both halves, so one ballot per wave gives every wave the same answer -- and a ONE lane of a mixed
+// tile stores its source value, no log / exp round trip.
+template <int NB, int kPitchWaves, bool CURVE>
+__global__ __launch_bounds__(64 * kPitchWaves) void frames_pitch_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                                         int frames_per_unit, const int32_t* __restrict__ step_q, int Q,
+                                                                         float* __restrict__ out, int C, int F, int ntile) {
+  constexpr int NR = 32 * NB;                                // cepstrum rows n = 1 .. NR
+  __shared__ float tab[2 * (kPitchMaxC - 1)];
+  __shared__ float cep[(NR + 1) * kPitchFrames];             // c[n][f], n = 0 .. NR
+  __shared__ float env[kPitchMaxC * kPitchFrames];           // E[k][f]; before that the waves' partial cepstra
+  const FrameTile t = frame_tile(frames, frames_per_unit, F, ntile);
+  const int b = t.b, f = t.f, fl = t.fl, h = t.h, wave = t.wave;
+  const bool live = t.live, inside = t.inside;
+  int s = TACO_PITCH_ONE;
+  if constexpr (!CURVE) {
+    if (step_q) {
+      s = step_q[b];
+      s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+    }
+    s = __builtin_amdgcn_readfirstlane(s);
+  }
+  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
+  float* __restrict__ dst = out + (int64_t)b * C * F + f;
+  bool plain;
+  if constexpr (CURVE) {
+    if (step_q && live) {   // (a frame behind F_b keeps ONE: its step is never read)
+      s = step_q[(int64_t)b * F + f];
+      s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+    }
+    plain = __ballot(live && s != TACO_PITCH_ONE) == 0;
+  } else {
+    plain = t.f0 >= t.Fb || s == TACO_PITCH_ONE;
+  }
+  if (plain) {   // (uniform) nothing to shift
+    copy_tile<kPitchWaves>(src, dst, t, C, F);
+    return;
+  }
+  fill_cos_table(tab, 2 * (C - 1), 64 * kPitchWaves);
+  __syncthreads();
+  cepstrum_tile<NB, kPitchWaves>(src, live, Q, C, F, tab, cep, env);   // (the partials in env's bytes: nothing reads them behind it)
+  cosine_tile<NB, kPitchWaves>(tab, cep, cep[fl], 2.0f, 1, NR, C, env);   // the envelope: c[0] + sum of 2 c[n], zeros behind the lifter
+
+  // ---- warp of the excitation, output ----  kPitchBatch bins per trip: every load of the trip first, at indices clamped into the
+  // frame (a value from a clamped index is never used)
+  for (int kb = 2 * wave + h; kb < C; kb += 2 * kPitchWaves * kPitchBatch) {
+    float m0[kPitchBatch], m1[kPitchBatch];
+    if (live) {
+#pragma unroll
+      for (int u = 0; u < kPitchBatch; ++u) {
+        const int k = min(kb + 2 * kPitchWaves * u, C - 1);
+        const int i = (int)(((uint32_t)k * (uint32_t)s) >> 16);   // (k s <= 1024 * 2^17)
+        m0[u] = src[min(i, C - 1) * F];
+        m1[u] = src[min(i + 1, C - 1) * F];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kPitchWaves * u;
+      if (k >= C) break;
+      float y = 0.f;
+      if (live) {
+        const uint32_t p = (uint32_t)k * (uint32_t)s;
+        const int i = (int)(p >> 16), ia = min(i, C - 1), ib = min(i + 1, C - 1);
+        const uint32_t frac = p & 0xFFFFu;
+        const float r0 = logf(fmaxf(m0[u], TACO_PITCH_FLOOR)) - env[ia * kPitchFrames + fl];
+        const float r1 = logf(fmaxf(m1[u], TACO_PITCH_FLOOR)) - env[ib * kPitchFrames + fl];
+        // i < C - 1: between two bins; i == C - 1 with w == 0: the top bin itself; beyond it the envelope alone
+        const float rp = i < C - 1 ? r0 + (float)frac * (1.0f / 65536.0f) * (r1 - r0) : ((i == C - 1 && frac == 0u) ? r0 : 0.f);
+        y = expf(env[k * kPitchFrames + fl] + rp);
+        if constexpr (CURVE)
+          if (s == TACO_PITCH_ONE) y = m0[u];   // (k s >> 16 == k: m0 is the frame's own bin) a ONE frame among shifted ones
+      }
+      if (inside) dst[k * F] = y;
+    }
+  }
 }
 
 // taco_frames_sharpen: the cepstral post-filter (include/taco_hip.h has the definition).  The shape of frames_pitch_kernel: a
@@ -513,76 +491,20 @@ __global__ __launch_bounds__(64 * kWaves) void frames_sharpen_kernel(const float
   __shared__ float tab[2 * (kPitchMaxC - 1)];
   __shared__ float cep[(NR + 1) * kPitchFrames];
   __shared__ float env[kPitchMaxC * kPitchFrames];   // D[k][f], then y[k][f]; before that the waves' partial cepstra
-  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  Fb = __builtin_amdgcn_readfirstlane(Fb);
-  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int f0 = tile * kPitchFrames, f = f0 + fl;
-  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
-  float* __restrict__ dst = out + (int64_t)b * C * F + f;
-  const bool live = f < Fb, inside = f < F;
-  if (f0 >= Fb || beta == 0.f) {   // (uniform) zeros behind the row's end, the row's own bits in front of it
-    for (int kb = 2 * wave + h; kb < C; kb += 2 * kWaves * kPitchBatch) {
-      float m[kPitchBatch];
-#pragma unroll
-      for (int u = 0; u < kPitchBatch; ++u) {
-        const int k = kb + 2 * kWaves * u;
-        m[u] = (live && k < C) ? src[k * F] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < kPitchBatch; ++u) {
-        const int k = kb + 2 * kWaves * u;
-        if (inside && k < C) dst[k * F] = m[u];
-      }
-    }
+  const FrameTile t = frame_tile(frames, frames_per_unit, F, ntile);
+  const int tid = threadIdx.x, fl = t.fl, h = t.h, wave = t.wave;
+  const bool live = t.live, inside = t.inside;
+  const float* __restrict__ src = mag_t + (int64_t)t.b * C * F + t.f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
+  float* __restrict__ dst = out + (int64_t)t.b * C * F + t.f;
+  if (t.f0 >= t.Fb || beta == 0.f) {   // (uniform)
+    copy_tile<kWaves>(src, dst, t, C, F);
     return;
   }
-  const int N = 2 * (C - 1), mask = N - 1;
-  for (int j = tid; j < N; j += 64 * kWaves) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
+  fill_cos_table(tab, 2 * (C - 1), 64 * kWaves);
   __syncthreads();
-  cepstrum_tile<NB, kWaves>(src, live, C, F, tab, cep, env);
-
-  // ---- D ----
-  const float b2 = 2.0f * beta;
-  float cb[NB][16];   // 2 beta c[n][f], n = 32 nb + 1 + 2 j + h, zero outside 2 .. Q: this lane's B operands
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int n = 32 * nb + 1 + 2 * j + h;
-      cb[nb][j] = (n >= TACO_SHARPEN_FIRST && n <= Q) ? b2 * cep[n * kPitchFrames + fl] : 0.f;
-    }
-  if (tid < kPitchFrames) {   // bin C - 1: cos(pi n) = (-1)^n
-    float t = 0.f;
-    for (int n = TACO_SHARPEN_FIRST; n <= Q; ++n) {
-      const float c2 = b2 * cep[n * kPitchFrames + tid];
-      t += (n & 1) ? -c2 : c2;
-    }
-    env[(C - 1) * kPitchFrames + tid] = t;
-  }
-  const int nblk = (C - 1 + 31) >> 5;
-  for (int kb = wave; kb < nblk; kb += kWaves) {
-    const int k = 32 * kb + fl;
-    f32x16 d;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) d[r] = 0.f;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        d = __builtin_amdgcn_mfma_f32_32x32x2f32(tab[((32 * nb + 1 + 2 * j + h) * k) & mask], cb[nb][j], d, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int kk = 32 * kb + (r & 3) + 8 * (r >> 2) + 4 * h;
-      if (kk < C - 1) env[kk * kPitchFrames + fl] = d[r];
-    }
-  }
-  __syncthreads();   // (nothing reads the cosine table from here on: tab holds the partial sums)
+  cepstrum_tile<NB, kWaves>(src, live, Q, C, F, tab, cep, env);
+  // D; nothing reads the cosine table behind it: tab holds the partial sums
+  cosine_tile<NB, kWaves>(tab, cep, 0.f, 2.0f * beta, TACO_SHARPEN_FIRST, Q, C, env);
 
   // ---- y and the two energies ----  a frame behind F_b inside a live tile has m = 0: y = 0, P0 = P1 = 0, g = 1
   float p0 = 0.f, p1 = 0.f;
@@ -640,27 +562,18 @@ __global__ __launch_bounds__(64 * kWaves) void frames_cepstats_kernel(const floa
   __shared__ float tab[2 * (kPitchMaxC - 1)];
   __shared__ float cep[(NR + 1) * kPitchFrames];
   __shared__ float part[(kWaves * NR + 2 * kWaves) * kPitchFrames];
-  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  Fb = __builtin_amdgcn_readfirstlane(Fb);
-  const int tid = threadIdx.x, fl = tid & 31;
-  const int f0 = tile * kPitchFrames, f = f0 + fl;
+  const FrameTile t = frame_tile(frames, frames_per_unit, F, ntile);
+  const int tid = threadIdx.x;
   double* __restrict__ mine = partial + (int64_t)blockIdx.x * (2 * (Q + 1));
-  if (f0 >= Fb) {   // (uniform)
+  if (t.f0 >= t.Fb) {   // (uniform)
     if (tid <= Q) mine[2 * tid] = 0.0, mine[2 * tid + 1] = 0.0;
     return;
   }
-  const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;
-  const int N = 2 * (C - 1);
-  for (int j = tid; j < N; j += 64 * kWaves) tab[j] = cospif((float)(2 * j) / (float)N);
+  fill_cos_table(tab, 2 * (C - 1), 64 * kWaves);
   __syncthreads();
-  cepstrum_tile<NB, kWaves>(src, f < Fb, C, F, tab, cep, part);
+  cepstrum_tile<NB, kWaves>(mag_t + (int64_t)t.b * C * F + t.f, t.live, Q, C, F, tab, cep, part);
   if (tid <= Q) {
-    const int nl = Fb - f0 < kPitchFrames ? Fb - f0 : kPitchFrames;
+    const int nl = t.Fb - t.f0 < kPitchFrames ? t.Fb - t.f0 : kPitchFrames;
     double s = 0.0, s2 = 0.0;
     for (int j = 0; j < nl; ++j) {
       const double c = (double)cep[tid * kPitchFrames + j];
@@ -675,14 +588,7 @@ __global__ __launch_bounds__(128) void frames_cepstats_fold_kernel(const double*
                                                                     int32_t* __restrict__ count, int F, int ntile) {
   static_assert(TACO_PITCH_MAX_LIFTER + 1 <= 128, "one thread per quefrency");
   const int b = blockIdx.x, n = threadIdx.x;
-  if (n == 0) {
-    int Fb = F;
-    if (frames) {
-      const int64_t v = (int64_t)frames[b] * frames_per_unit;
-      Fb = v < 0 ? 0 : (v > F ? F : (int)v);
-    }
-    count[b] = Fb;
-  }
+  if (n == 0) count[b] = row_frames(frames, frames_per_unit, b, F);
   if (n > Q) return;
   const double* __restrict__ p = partial + ((int64_t)b * ntile) * (2 * (Q + 1)) + 2 * n;
   double s = 0.0, s2 = 0.0;
@@ -705,6 +611,7 @@ __global__ __launch_bounds__(128) void frames_cepstats_fold_kernel(const double*
 // largest candidate (a maximum: no order), then the smallest lag at or above ratio * g -- and one thread per frame finishes.
 // A tile behind F_b writes zeros and loads nothing; a frame behind F_b inside a live tile has p = 0, hence r0 = 0 and zeros.
 constexpr int kF0Frames = 32;
+static_assert(kF0Frames == kPitchFrames, "frame_tile's tile");
 constexpr int kF0Waves = 8;
 constexpr int kF0Parts = 2 * kF0Waves;   // threads per frame: forming p, and in the pick
 static_assert(TACO_F0_MAX_LAGS <= 2 * 32 * kF0Waves, "two tiles of 32 lags per wave at the most");
@@ -721,21 +628,13 @@ __global__ __launch_bounds__(64 * kF0Waves) void frames_f0_kernel(const float* _
   __shared__ float part[kF0Parts * kF0Frames];         // the partial sums of r0; in the pick the parts' largest candidates
   __shared__ int first[kF0Parts * kF0Frames];          // the parts' first candidates at or above ratio * g
   __shared__ float r0s[kF0Frames];
-  const int tile = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  Fb = __builtin_amdgcn_readfirstlane(Fb);
-  const int tid = threadIdx.x, lane = tid & 63, fl = lane & 31, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const FrameTile t = frame_tile(frames, frames_per_unit, F, ntile);
+  const int tid = threadIdx.x, b = t.b, f = t.f, fl = t.fl, h = t.h, wave = t.wave;
   const int pt = 2 * wave + h;   // = tid >> 5
-  const int f0 = tile * kF0Frames, f = f0 + fl;
   const int L = lag_max - lag_min + 3;
-  const bool live = f < Fb, inside = f < F;
+  const bool live = t.live, inside = t.inside;
   float* __restrict__ ac = acf ? acf + (int64_t)b * L * F + f : nullptr;   // (L F <= 512 * 8192: the offsets below fit 32 bits)
-  if (f0 >= Fb) {   // (uniform) behind the row's end
+  if (t.f0 >= t.Fb) {   // (uniform) behind the row's end
     if (inside) {
       if (tid < kF0Frames) period[(int64_t)b * F + f] = strength[(int64_t)b * F + f] = 0.f;
       if (ac)
@@ -744,7 +643,7 @@ __global__ __launch_bounds__(64 * kF0Waves) void frames_f0_kernel(const float* _
     return;
   }
   const int N = 2 * (C - 1), mask = N - 1;
-  for (int j = tid; j < N; j += 64 * kF0Waves) tab[j] = cospif((float)(2 * j) / (float)N);   // (2 j / N is exact)
+  fill_cos_table(tab, N, 64 * kF0Waves);   // (visible behind the barrier below)
 
   // ---- p and r0 ----
   const float* __restrict__ src = mag_t + (int64_t)b * C * F + f;   // (C F <= 1025 * 8192)
@@ -860,11 +759,7 @@ __global__ __launch_bounds__(256) void f0_stats_kernel(const float* __restrict__
   __shared__ float red[256];
   __shared__ int cnt[256];
   const int b = blockIdx.x, tid = threadIdx.x;
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
+  const int Fb = row_frames(frames, frames_per_unit, b, F);
   const float* __restrict__ p = period + (int64_t)b * F;
   const float* __restrict__ o = other ? other + (int64_t)b * F : nullptr;
   float s = 0.f;
@@ -989,6 +884,13 @@ extern "C" int taco_denorm_unframe(const float* out, const float* mean, const fl
   return TACO_OK;
 }
 namespace {
+// refuses an output `name` of obytes bytes that overlaps the mbytes bytes of mag_t
+int frames_no_overlap(const char* who, const char* name, const void* out, uint64_t obytes, const float* mag_t, uint64_t mbytes) {
+  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
+  TACO_REQUIRE(o0 + obytes <= m0 || m0 + mbytes <= o0, "%s: %s overlaps mag_t", who, name);
+  return TACO_OK;
+}
+
 // the refusals taco_frames_stretch and taco_frames_stretch_curve share, and the gather's grid
 int frames_stretch_args(const char* who, const float* mag_t, const float* out, const int32_t* frames_out, int frames_per_unit, int B, int C,
                         int F, int Fo, int* nspan, int* ntile, int64_t* blocks) {
@@ -1000,50 +902,18 @@ int frames_stretch_args(const char* who, const float* mag_t, const float* out, c
   TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "%s: F=%d must be in 1..%d", who, F, TACO_STRETCH_MAX_FRAMES);
   TACO_REQUIRE(Fo > 0 && Fo <= TACO_STRETCH_MAX_FRAMES, "%s: Fo=%d must be in 1..%d", who, Fo, TACO_STRETCH_MAX_FRAMES);
   TACO_REQUIRE(frames_per_unit >= 1, "%s: frames_per_unit=%d must be >= 1", who, frames_per_unit);
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
   const uint64_t rows = (uint64_t)B * (uint64_t)C;   // (< 2^62; F, Fo <= 2^13: the byte counts below fit 64 bits)
   TACO_REQUIRE(rows <= (UINT64_MAX >> 16) / 4, "%s: B=%d x C=%d: the tensors exceed the address space", who, B, C);
-  TACO_REQUIRE(o0 + rows * Fo * 4 <= m0 || m0 + rows * F * 4 <= o0, "%s: out overlaps mag_t", who);
+  TACO_TRY(frames_no_overlap(who, "out", out, rows * Fo * 4, mag_t, rows * F * 4));
   *nspan = cdiv(Fo, kStretchSpan), *ntile = cdiv(C, kStretchBins);
   *blocks = (int64_t)B * *ntile * *nspan;
   TACO_REQUIRE(*blocks <= 0x7fffffff, "%s: B=%d x C=%d x Fo=%d needs more than 2^31 workgroups", who, B, C, Fo);
   return TACO_OK;
 }
 
-// taco_frames_pitch (CURVE = false: step_q (B)) and taco_frames_pitch_curve (true: step_q (B, F)): one set of refusals, and the
-// lifter path chosen by Q alone either way
-template <bool CURVE>
-int frames_pitch_call(const char* who, const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
-                      float* out, int B, int C, int F, void* stream) {
-  TACO_REQUIRE(mag_t, "%s: mag_t is NULL", who);
-  TACO_REQUIRE(out, "%s: out is NULL", who);
-  TACO_REQUIRE(B > 0, "%s: B=%d must be positive", who, B);
-  TACO_REQUIRE(C >= 9 && C <= kPitchMaxC && ((C - 1) & (C - 2)) == 0, "%s: C=%d: C - 1 must be a power of two in 8..%d", who, C,
-               kPitchMaxC - 1);
-  TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "%s: F=%d must be in 1..%d", who, F, TACO_STRETCH_MAX_FRAMES);
-  const int qmax = (C - 1) / 2 < TACO_PITCH_MAX_LIFTER ? (C - 1) / 2 : TACO_PITCH_MAX_LIFTER;
-  TACO_REQUIRE(lifter >= 1 && lifter <= qmax, "%s: lifter=%d must be in 1..%d at C=%d", who, lifter, qmax, C);
-  TACO_REQUIRE(frames_per_unit >= 1, "%s: frames_per_unit=%d must be >= 1", who, frames_per_unit);
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
-  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
-  TACO_REQUIRE(o0 + bytes <= m0 || m0 + bytes <= o0, "%s: out overlaps mag_t", who);
-  const int ntile = cdiv(F, kPitchFrames);
-  const int64_t blocks = (int64_t)B * ntile;
-  TACO_REQUIRE(blocks <= 0x7fffffff, "%s: B=%d x F=%d needs more than 2^31 workgroups", who, B, F);
-  hipStream_t s = as_stream(stream);
-  if (lifter <= 32)
-    TACO_KLAUNCH((frames_pitch_kernel<1, 16, CURVE>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, step_q,
-                 lifter, out, C, F, ntile);
-  else
-    TACO_KLAUNCH((frames_pitch_kernel<2, 8, CURVE>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, step_q,
-                 lifter, out, C, F, ntile);
-  TACO_LAUNCH_CHECK(who);
-  return TACO_OK;
-}
-
-// the refusals taco_frames_sharpen and taco_frames_cepstats share (those of taco_frames_pitch with the lifter from
-// TACO_SHARPEN_FIRST), and the grid
-int frames_cepstrum_args(const char* who, const float* mag_t, int frames_per_unit, int lifter, int B, int C, int F, int* ntile,
+// the refusals of the entry points behind cepstrum_tile (taco_frames_pitch, _pitch_curve, _sharpen, _cepstats; `first`: the smallest
+// lifter), and the grid
+int frames_cepstrum_args(const char* who, const float* mag_t, int frames_per_unit, int first, int lifter, int B, int C, int F, int* ntile,
                          int64_t* blocks) {
   TACO_REQUIRE(mag_t, "%s: mag_t is NULL", who);
   TACO_REQUIRE(B > 0, "%s: B=%d must be positive", who, B);
@@ -1051,12 +921,40 @@ int frames_cepstrum_args(const char* who, const float* mag_t, int frames_per_uni
                kPitchMaxC - 1);
   TACO_REQUIRE(F > 0 && F <= TACO_STRETCH_MAX_FRAMES, "%s: F=%d must be in 1..%d", who, F, TACO_STRETCH_MAX_FRAMES);
   const int qmax = (C - 1) / 2 < TACO_PITCH_MAX_LIFTER ? (C - 1) / 2 : TACO_PITCH_MAX_LIFTER;
-  TACO_REQUIRE(lifter >= TACO_SHARPEN_FIRST && lifter <= qmax, "%s: lifter=%d must be in %d..%d at C=%d", who, lifter,
-               TACO_SHARPEN_FIRST, qmax, C);
+  TACO_REQUIRE(lifter >= first && lifter <= qmax, "%s: lifter=%d must be in %d..%d at C=%d", who, lifter, first, qmax, C);
   TACO_REQUIRE(frames_per_unit >= 1, "%s: frames_per_unit=%d must be >= 1", who, frames_per_unit);
   *ntile = cdiv(F, kPitchFrames);
   *blocks = (int64_t)B * *ntile;
   TACO_REQUIRE(*blocks <= 0x7fffffff, "%s: B=%d x F=%d needs more than 2^31 workgroups", who, B, F);
+  return TACO_OK;
+}
+
+// The two lifter paths of those kernels, chosen by the lifter alone (so the bits depend on it alone): launch(NB, kWaves) is called
+// with <1, 16> for a lifter up to 32 and with <2, 8> above, as types that carry the numbers.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class Launch>
+void by_lifter(int lifter, Launch&& launch) {
+  if (lifter <= 32) launch(int_c<1>{}, int_c<16>{});
+  else launch(int_c<2>{}, int_c<8>{});
+}
+
+// taco_frames_pitch (CURVE = false: step_q (B)) and taco_frames_pitch_curve (true: step_q (B, F)): one set of refusals
+template <bool CURVE>
+int frames_pitch_call(const char* who, const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                      float* out, int B, int C, int F, void* stream) {
+  int ntile;
+  int64_t blocks;
+  TACO_REQUIRE(!mag_t || out, "%s: out is NULL", who);   // (mag_t is refused first, below)
+  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, 1, lifter, B, C, F, &ntile, &blocks));
+  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
+  TACO_TRY(frames_no_overlap(who, "out", out, bytes, mag_t, bytes));
+  hipStream_t s = as_stream(stream);
+  by_lifter(lifter, [&](auto nb, auto waves) {
+    TACO_KLAUNCH((frames_pitch_kernel<nb.value, waves.value, CURVE>), dim3((unsigned)blocks), dim3(64 * waves.value), 0, s, mag_t, frames,
+                 frames_per_unit, step_q, lifter, out, C, F, ntile);
+  });
+  TACO_LAUNCH_CHECK(who);
   return TACO_OK;
 }
 }  // namespace
@@ -1067,19 +965,16 @@ extern "C" int taco_frames_sharpen(const float* mag_t, const int32_t* frames, in
   int ntile;
   int64_t blocks;
   TACO_REQUIRE(out, "%s: out is NULL", who);
-  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, lifter, B, C, F, &ntile, &blocks));
+  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, TACO_SHARPEN_FIRST, lifter, B, C, F, &ntile, &blocks));
   TACO_REQUIRE(beta >= TACO_SHARPEN_MIN_BETA && beta <= TACO_SHARPEN_MAX_BETA, "%s: beta=%g must be in [%g, %g]", who, (double)beta,
                (double)TACO_SHARPEN_MIN_BETA, (double)TACO_SHARPEN_MAX_BETA);   // (false for a NaN)
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
   const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
-  TACO_REQUIRE(o0 + bytes <= m0 || m0 + bytes <= o0, "%s: out overlaps mag_t", who);
+  TACO_TRY(frames_no_overlap(who, "out", out, bytes, mag_t, bytes));
   hipStream_t s = as_stream(stream);
-  if (lifter <= 32)
-    TACO_KLAUNCH((frames_sharpen_kernel<1, 16>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, beta, lifter,
-                 out, C, F, ntile);
-  else
-    TACO_KLAUNCH((frames_sharpen_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, beta, lifter,
-                 out, C, F, ntile);
+  by_lifter(lifter, [&](auto nb, auto waves) {
+    TACO_KLAUNCH((frames_sharpen_kernel<nb.value, waves.value>), dim3((unsigned)blocks), dim3(64 * waves.value), 0, s, mag_t, frames,
+                 frames_per_unit, beta, lifter, out, C, F, ntile);
+  });
   TACO_LAUNCH_CHECK(who);
   return TACO_OK;
 }
@@ -1088,7 +983,8 @@ extern "C" int64_t taco_frames_cepstats_workspace_bytes(int B, int C, int F, int
   int ntile;
   int64_t blocks;
   const float dummy = 0.f;
-  if (frames_cepstrum_args("frames_cepstats_workspace_bytes", &dummy, 1, lifter, B, C, F, &ntile, &blocks) != TACO_OK) return TACO_EINVAL;
+  if (frames_cepstrum_args("frames_cepstats_workspace_bytes", &dummy, 1, TACO_SHARPEN_FIRST, lifter, B, C, F, &ntile, &blocks) != TACO_OK)
+    return TACO_EINVAL;
   return blocks * (lifter + 1) * 16 + 8;
 }
 extern "C" int taco_frames_cepstats(const float* mag_t, const int32_t* frames, int frames_per_unit, int lifter, double* sums,
@@ -1098,16 +994,14 @@ extern "C" int taco_frames_cepstats(const float* mag_t, const int32_t* frames, i
   int64_t blocks;
   TACO_REQUIRE(sums, "%s: sums is NULL", who);
   TACO_REQUIRE(count, "%s: count is NULL", who);
-  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, lifter, B, C, F, &ntile, &blocks));
+  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, TACO_SHARPEN_FIRST, lifter, B, C, F, &ntile, &blocks));
   TACO_REQUIRE(workspace, "%s: workspace is NULL", who);
   double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + 7) & ~(uintptr_t)7);
   hipStream_t s = as_stream(stream);
-  if (lifter <= 32)
-    TACO_KLAUNCH((frames_cepstats_kernel<1, 16>), dim3((unsigned)blocks), dim3(64 * 16), 0, s, mag_t, frames, frames_per_unit, lifter,
-                 partial, C, F, ntile);
-  else
-    TACO_KLAUNCH((frames_cepstats_kernel<2, 8>), dim3((unsigned)blocks), dim3(64 * 8), 0, s, mag_t, frames, frames_per_unit, lifter,
-                 partial, C, F, ntile);
+  by_lifter(lifter, [&](auto nb, auto waves) {
+    TACO_KLAUNCH((frames_cepstats_kernel<nb.value, waves.value>), dim3((unsigned)blocks), dim3(64 * waves.value), 0, s, mag_t, frames,
+                 frames_per_unit, lifter, partial, C, F, ntile);
+  });
   TACO_KLAUNCH(frames_cepstats_fold_kernel, dim3((unsigned)B), dim3(128), 0, s, partial, frames, frames_per_unit, lifter, sums, count, F,
                ntile);
   TACO_LAUNCH_CHECK(who);
@@ -1166,13 +1060,10 @@ extern "C" int taco_frames_f0(const float* mag_t, const int32_t* frames, int fra
   TACO_REQUIRE(ratio > 0.f && ratio <= 1.f, "frames_f0: ratio=%g must be in (0, 1]", (double)ratio);   // (NaN fails both)
   TACO_REQUIRE(threshold == threshold, "frames_f0: threshold is NaN");
   TACO_REQUIRE(frames_per_unit >= 1, "frames_f0: frames_per_unit=%d must be >= 1", frames_per_unit);
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t);
   const uint64_t mbytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4, row = (uint64_t)B * (uint64_t)F * 4;
-  const uintptr_t p0 = reinterpret_cast<uintptr_t>(period), s0 = reinterpret_cast<uintptr_t>(strength),
-                  a0 = reinterpret_cast<uintptr_t>(acf);
-  TACO_REQUIRE(p0 + row <= m0 || m0 + mbytes <= p0, "frames_f0: period overlaps mag_t");
-  TACO_REQUIRE(s0 + row <= m0 || m0 + mbytes <= s0, "frames_f0: strength overlaps mag_t");
-  TACO_REQUIRE(!acf || a0 + row * (uint64_t)L <= m0 || m0 + mbytes <= a0, "frames_f0: acf overlaps mag_t");
+  TACO_TRY(frames_no_overlap("frames_f0", "period", period, row, mag_t, mbytes));
+  TACO_TRY(frames_no_overlap("frames_f0", "strength", strength, row, mag_t, mbytes));
+  if (acf) TACO_TRY(frames_no_overlap("frames_f0", "acf", acf, row * (uint64_t)L, mag_t, mbytes));
   const int ntile = cdiv(F, kF0Frames);
   const int64_t blocks = (int64_t)B * ntile;
   TACO_REQUIRE(blocks <= 0x7fffffff, "frames_f0: B=%d x F=%d needs more than 2^31 workgroups", B, F);

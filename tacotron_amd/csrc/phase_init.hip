@@ -21,6 +21,7 @@
 // other's gather latency: with 256 threads and four bins each the chain took 1.02 us per frame, with these 0.61.  The
 // phases collect in an LDS tile of 16 frames and go out transposed into (B, 1025, F) in runs of 64 bytes along t.  The same launch
 // writes the zeros behind F_b.  No atomics, no flags, nothing polled: a row's chain lives inside its workgroup.
+#include "frames.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
@@ -42,15 +43,6 @@ constexpr float kPeScale = (float)(6.283185307179586 / 16777216.0);   // 2 pi / 
 static_assert(kPeWords * 64 >= kPeBins && (kPePer - 1) * kPeChainThreads + 1 == kPeBins, "bins per lane / per thread");
 static_assert(kPeChainLds <= kPeLdsBudget, "LDS of the chain");
 
-__device__ __forceinline__ int pe_row_frames(const int32_t* __restrict__ frames, int frames_per_unit, int b, int F) {
-  int Fb = F;
-  if (frames) {
-    const int64_t n = (int64_t)frames[b] * frames_per_unit;
-    Fb = n < 0 ? 0 : (n > F ? F : (int)n);
-  }
-  return __builtin_amdgcn_readfirstlane(Fb);
-}
-
 // steps 2 and 3 for the peak at bin j (1 <= j <= 1023) of the tile column `col`
 __device__ __forceinline__ uint32_t pe_advance(const float* __restrict__ col, int j) {
   const float a = col[(j - 1) * kPePitch], b = col[j * kPePitch], c = col[(j + 1) * kPePitch];
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(kPeThreads) void phase_owner_kernel(const float* __
   extern __shared__ __attribute__((aligned(16))) float pe_lds[];   // |mag_t| [1025][17]
   float* tile = pe_lds;
   const int tl = (int)(blockIdx.x % (uint32_t)ntile), b = (int)(blockIdx.x / (uint32_t)ntile);
-  const int Fb = pe_row_frames(frames, frames_per_unit, b, F);
+  const int Fb = row_frames_uniform(frames, frames_per_unit, b, F);
   const int f0 = tl * kPeTile;
   if (f0 >= Fb) return;   // (uniform) nothing of this tile is ever read
   const int tid = threadIdx.x;
@@ -151,7 +143,7 @@ __global__ __launch_bounds__(kPeChainThreads) void phase_chain_kernel(const uint
   float* tile = pe_lds;
   uint32_t* acc = reinterpret_cast<uint32_t*>(pe_lds + kPeBins * kPePitch);
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int Fb = pe_row_frames(frames, frames_per_unit, b, F);
+  const int Fb = row_frames_uniform(frames, frames_per_unit, b, F);
   float* __restrict__ out = phase0 + (int64_t)b * kPeBins * F;
   if (Fb > 0) {   // (uniform)
     const int last = Fb - 1;

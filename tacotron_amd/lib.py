@@ -1255,12 +1255,7 @@ def frames_pitch(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, 
     lifter: 1 .. min(64, (C - 1) / 2); the default 32 (quefrencies up to 2 ms at 16 kHz) is untuned.  out: the caller's own buffer;
     default: a fresh one.  Enqueued on the current stream; nothing is read back and nothing waits."""
     who = 'frames_pitch'
-    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
-    dev = mag_t.device
-    pow2_bins(who, Cw)
-    _frames_cap(who, F)
-    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
-    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, 1, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
+    B, Cw, F, dev, frames_per_unit, lifter = _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit, first=1)
     step_q, _ = step_q_arg(who, step_q, B, dev, PITCH_MIN_STEP, PITCH_MAX_STEP, '+12 to -12 semitones')
     out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
     no_overlap(who, 'mag_t', mag_t, 'out', out)
@@ -1348,12 +1343,7 @@ def frames_pitch_curve(mag_t, frames=None, step_q=None, frames_per_unit=1, lifte
     the bits frames_pitch gives it at the row step step_q[b, f]; a frame at 65536 is its input bit for bit.  Everything else as
     frames_pitch."""
     who = 'frames_pitch_curve'
-    B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
-    dev = mag_t.device
-    pow2_bins(who, Cw)
-    _frames_cap(who, F)
-    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
-    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, 1, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
+    B, Cw, F, dev, frames_per_unit, lifter = _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit, first=1)
     tensor_arg(who, 'step_q', step_q, torch.int32, (B, F), dev, optional=True)
     out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
     no_overlap(who, 'mag_t', mag_t, 'out', out)
@@ -1367,14 +1357,14 @@ SHARPEN_FIRST, SHARPEN_MIN_BETA, SHARPEN_MAX_BETA = 2, -1.0, 1.0   # include/tac
 SHARPEN_LIFTER = 32   # UNTUNED, like every beta: nobody has listened
 
 
-def _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit):
-    """the argument checks frames_sharpen and frames_cepstats share -> (B, C, F, device, frames_per_unit, lifter)"""
+def _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit, first=SHARPEN_FIRST):
+    """the argument checks the cepstral wrappers share (first: the smallest lifter) -> (B, C, F, device, frames_per_unit, lifter)"""
     B, Cw, F = tensor_arg(who, 'mag_t', mag_t, torch.float32, ('B', 'C', 'F'))
     dev = mag_t.device
     pow2_bins(who, Cw)
     _frames_cap(who, F)
     frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
-    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, SHARPEN_FIRST, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
+    lifter = int_arg(who, 'lifter (at C = %d)' % Cw, lifter, first, min(PITCH_MAX_LIFTER, (Cw - 1) // 2))
     return B, Cw, F, dev, frames_per_unit, lifter
 
 
