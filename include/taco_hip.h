@@ -1293,6 +1293,43 @@ int64_t taco_tensor_stats_workspace_bytes(int n, int n_items, int NB);
 int taco_tensor_stats(const float* base, const void* plan_dev, const void* plan_header, int n, int n_items, int e_lo, int e_hi,
                       int sub_bits, int64_t* counts, double* moments, int64_t* hist, void* workspace, void* stream);
 
+/* ---- weight averaging (ema.hip) ------------------------------------------------------------------------------------ */
+/* Exponential moving average of the parameters, tf.train.ExponentialMovingAverage's `shadow -= (1 - decay) (shadow - var)`; no
+ * counterpart in the reference, which decodes from the weights as the last minibatch left them.  One pass over two flat fp32
+ * buffers of n floats, enqueued behind taco_clip_adam_step_guarded on the step's stream.
+ *   ema, params   n floats each on the device, at ANY float alignment (16-byte loads and stores when both are 16-byte aligned, else
+ *                 float by float; the result is the same bits either way); they may not overlap
+ *   w             1 - decay of THIS update, in [0, 1], from the host: the kernel holds no schedule (the num_updates warm-up
+ *                 min(decay, (1 + k) / (10 + k)) is the caller's)
+ * THE UPDATE is three separately rounded fp32 operations per element, in this order, nothing fused:
+ *   d = params[i] - ema[i];   t = w * d;   ema[i] = ema[i] + t
+ * so ema holds the same bits as a NumPy float32 restatement.  (w = 1 does not make ema a copy of params: e + (p - e) is not p in
+ * fp32.  Start an average as a copy.)
+ * THE GUARD is taco_clip_adam_step_guarded's: err_words (nullable) are the decoder kernels' two error words; when either is non-zero
+ * ema is neither read nor written -- a skipped Adam update is not averaged in as if it had happened -- and stats, if given, reads
+ * (-1, -1, 0).
+ *   stats         nullable; 3 doubles on the device, 8-byte aligned:
+ *                 [0] sum of (double)d (double)d, d the fp32 difference above: the squared distance of the live weights from the
+ *                     average BEFORE this update;  [1] sum of (double)params[i]^2;  [2] 1 when the update was applied.
+ *                 The squares of fp32 values are exact in fp64, so only the order of the additions rounds: per thread in the order
+ *                 the thread meets its elements, the 64 lanes of a wave in the tree v_l += v_(l + 32), 16, 8, 4, 2, 1, the waves of a
+ *                 workgroup in sequence, one pair of partials per workgroup into the workspace; a second launch of one workgroup adds
+ *                 the partials in a fixed order.  The grid follows from n, the alignment and the device's CU count alone
+ *   workspace     taco_param_ema_workspace_bytes(n) bytes, 8-byte aligned, arbitrary contents; needed with stats only
+ *   - no atomics: the same call on the same inputs gives the same bits;
+ *   - the bits of ema do not depend on whether stats is given; with stats == NULL the reduction and the second launch are skipped
+ *     and workspace may be NULL;
+ *   - nothing is written outside ema, stats and the workspace.
+ * No allocation, no host synchronisation, no workgroup waits for another one: one or two stream-ordered launches, graph-capturable.
+ * NULL ema or params, n <= 0, w outside [0, 1] or NaN, ema overlapping params, stats without a workspace and a stats or workspace that
+ * is not 8-byte aligned return TACO_EINVAL, with a message "param_ema: ...", before anything is enqueued; the size function returns
+ * TACO_EINVAL for n <= 0 and needs no device.  TACO_VERSION did not change with these two entry points: detect them by the symbol.
+ * Not here: the average inside the Adam kernel (one read of params less; that kernel's bits are pinned), averaging across
+ * checkpoint files, fp16 / bf16 buffers, moving statistics of batch norm (the model's BN keeps none). */
+int64_t taco_param_ema_workspace_bytes(int64_t n);            /* n > 0, else TACO_EINVAL; needs no device */
+int taco_param_ema(float* ema, const float* params, int64_t n, float w, const int32_t* err_words,
+                   double* stats, void* workspace, void* stream);
+
 /* ---- measurement --------------------------------------------------------------------------------------------- */
 /* Launch-level timing with hipEventRecord pairs on the launch stream (rings of 4096 event pairs per category; no
  * synchronisation at record time).  Categories: 0 = persistent decoder forward kernel, 1 = decoder backward kernel,

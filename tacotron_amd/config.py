@@ -54,6 +54,12 @@ class Config(object):
     sharpen = None
     sharpen_lifter = 32
 
+    # training only (train.py --ema DECAY; not in the reference): an exponential moving average of the parameters, kept on the device
+    # beside the Adam slots and saved with them; 0: off -- no buffer, no launch, no checkpoint key.  No tuned default
+    ema_decay = 0.0
+    # synthesis only (test.py --ema): decode from the checkpoint's averaged weights instead of the live ones
+    use_ema = False
+
     # models/tacotron.py:13 evaluates maximum_audio_length // (r hop_length) once, with audio.r; here `r` is changed at run time
     # (test.py from the checkpoint, train.py from meta.pkl), so the decode length follows the r in use unless a caller sets it
     _max_decode_iter = None
@@ -78,6 +84,8 @@ class Config(object):
             raise ValueError('Config.num_speakers must be >= 1')
         if self.num_speakers > 1 and self.speaker_embed_dim != 16:
             raise ValueError('Config.speaker_embed_dim=%r is not supported by libtaco_hip (compiled for 16)' % self.speaker_embed_dim)
+        if not 0.0 <= float(self.ema_decay) < 1.0:   # (NaN fails)
+            raise ValueError('Config.ema_decay must be in [0, 1) (0: no weight averaging), got %r' % (self.ema_decay,))
         if not (1 <= self.r <= 5):
             raise ValueError('Config.r must be in 1..5')
         for k in ('char_dropout_prob', 'audio_dropout_prob'):

@@ -4,7 +4,10 @@ One process per GPU; each rank runs forward+backward on its own minibatch; ONE e
 flat fp32 gradient buffer (loss is a plain sum, so SUM -- not mean -- reproduces the N*B-batch gradient exactly), then
 every rank applies the same clip + Adam update, so replicas stay identical.  Backend "nccl" is RCCL on ROCm (xGMI);
 "gloo" is used by the CPU tests.  The buffer is reduced in a few large buckets issued back-to-back (xGMI rings are
-per-link bound, so few large messages beat many small ones): 10 MB buckets make each of the five segments ONE collective."""
+per-link bound, so few large messages beat many small ones): 10 MB buckets make each of the five segments ONE collective.
+Weight averaging (Config.ema_decay, lib.param_ema) needs no collective: every rank applies the same update to identical parameter
+bits with the same host-computed weight, and the error words that make it skip are MAX-reduced with the gradients, so the skips
+agree and the averages stay identical too."""
 from __future__ import annotations
 
 import os

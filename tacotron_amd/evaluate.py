@@ -9,7 +9,7 @@ utterances of the corpus, the ones `train --holdout N` never draws,
       with frames of log(1e-8) and stores no length.
 Only cost, steps, na, nb and the three losses of each batch travel to the host.
 
-    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--f0-smooth] [--durations] [--gv [--gv-lifter Q] [--sharpen BETA]]
+    python -m tacotron_amd.evaluate -t nancy [--checkpoint P] [--holdout N] [--speaker S] [--cepstra 13] [--out-dir log/eval] [--f0 | --f0-aligned] [--f0-smooth] [--durations] [--gv [--gv-lifter Q] [--sharpen BETA]] [--ema]
 
 prints one line per batch and a final line with the mean teacher-forced loss and the mean and worst MCD, and writes
 eval_<step>.npy, one row per utterance: index, na, nb, steps, cost, mcd (float64; COLUMNS).
@@ -67,6 +67,10 @@ numbers on the lines, so one run shows what the filter does to the measure.  Sha
 durations are computed on what they were computed on.  The ratio is over this model's LINEAR-frequency cepstra, quefrencies 1 .. Q: it
 is comparable between checkpoints here, NOT with published mel-cepstral GV figures.  BETA has no tuned default, and on an untrained
 model the numbers mean nothing.  Without --gv every mode prints and saves exactly what it did.
+
+--ema: both passes run on the checkpoint's AVERAGED weights (`train --ema DECAY` keeps an exponential moving average of the parameters
+and saves it with them) instead of the ones the last minibatch left; a checkpoint that holds none is refused before anything is
+scored.  Every column means what it meant: two runs on one checkpoint, with and without the flag, show what averaging buys there.
 
 The final batch is padded to the batch size by repeating its last utterance; the copies are left out of the per-utterance rows and
 of the MCD statistics.  The teacher-forced loss is one number per batch (and the CBHG's batch normalisation sees the whole batch),
@@ -266,7 +270,7 @@ def gv_line(summary, sharpen=None):
 
 def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_dir='log/eval', stop=None, device=0, trace=None,
              f0=False, f0_aligned=False, durations=False, path_jump=lib.PATH_JUMP, f0_smooth=False, gv=False, gv_lifter=lib.SHARPEN_LIFTER,
-             sharpen=None):
+             sharpen=None, ema=False):
     """-> (rows (n, 6) float64 in the order COLUMNS, mean teacher-forced loss).  Module docstring.  f0: rows (n, 12), F0_COLUMNS behind
     COLUMNS.  f0_aligned (implies f0): rows (n, 17), ALIGNED_COLUMNS behind those.  durations: DUR_COLUMNS behind all of them (path_jump: the max_jump of the two paths).  stop: the lib.TacoStopRule of the
     free-running decode (default: TacoStopRule()).  trace: a list that receives, per batch, host copies of what the warp was given
@@ -276,7 +280,9 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     'rec_period_raw' and the smoothed ones 'period' and 'rec_period'.  gv / gv_lifter / sharpen (needs gv): the global-variance ratio
     over the quefrencies 1 .. gv_lifter, GV_COLUMNS behind every other column -- with a sharpen beta other than None and 0,
     GV_SHARPEN_COLUMNS; trace then also receives the magnitudes the sums were taken over, 'pred_mags' and 'rec_mags' (B, C, F), with
-    sharpen also 'sharp_mags', and 'lengths', the decoder steps of the predicted rows."""
+    sharpen also 'sharp_mags', and 'lengths', the decoder steps of the predicted rows.  ema (--ema; needs a checkpoint): both passes
+    run on the checkpoint's AVERAGED weights (train --ema; Tacotron.load_state_dict(use_ema=True)) instead of the live ones;
+    lib.TacoError before anything is scored when the checkpoint holds none.  Every column means what it meant."""
     f0 = bool(f0 or f0_aligned or f0_smooth)
     if sharpen is not None and not gv:
         raise ValueError('evaluate: sharpen (--sharpen) scores the post-filter by the global variance: it needs gv (--gv)')
@@ -314,6 +320,10 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     held = {k: v[first:] for k, v in data.items()}   # (a memmap stays one: only the held-out rows are read and uploaded)
     feeder = DeviceCorpus(held, B, device=dev, norm=norm, draw=lambda step: batches[step][0] - first)
     ckpt = torch.load(checkpoint) if checkpoint else None
+    if ema and (ckpt is None or 'ema' not in ckpt):   # (before anything is built)
+        raise lib.TacoError('ema (--ema): %s' % ('there is no checkpoint to take averaged weights from' if ckpt is None else
+                                                 'the checkpoint %s holds no averaged weights (written without `train --ema`, or imported): '
+                                                 'its keys are %s' % (checkpoint, ', '.join(sorted(map(str, ckpt))))))
     batch = feeder.next()
     shape = lib.make_shape(B, batch['text'].shape[1], batch['mel'].shape[1], config.r, config.vocab_size, config.num_speakers)
     params = ParamBuffer(shape, dev).init_(0)
@@ -321,7 +331,11 @@ def evaluate(config, holdout=64, checkpoint=None, speaker=None, cepstra=13, out_
     text = {k: batch[k] for k in ('text', 'text_length', 'speaker') if k in batch}
     free = Tacotron(config, text, train=False, device=dev, params=params)    # (b): max_decode_iter free-running steps at the most
     if ckpt is not None:
-        forced.load_state_dict(ckpt)
+        if ema:
+            forced.load_state_dict(ckpt, use_ema=True)
+            print('scoring the averaged weights (decay %s, %s updates)' % (ckpt.get('ema_decay', '?'), ckpt.get('ema_updates', '?')))
+        else:
+            forced.load_state_dict(ckpt)
         free.global_step = forced.global_step
     else:
         print('no checkpoint -- scoring the seed-0 initialisation')
@@ -523,6 +537,9 @@ def parse_args(argv=None):
                     help='--gv: also pass the predicted magnitudes through the post-filter of `test --sharpen BETA`, -1 <= BETA <= 1, and '
                          'score them again (a second column; the GV columns only -- MCD, F0 and durations do not change).  BETA has no '
                          'tuned default')
+    ap.add_argument('--ema', action='store_true',
+                    help='score the averaged weights of a checkpoint written by `train --ema DECAY` instead of the live ones; an error '
+                         'when the checkpoint holds none.  Run it with and without the flag to see what averaging buys')
     a = ap.parse_args(argv)
     if (a.gv_lifter is not None or a.sharpen is not None) and not a.gv:
         ap.error('--gv-lifter and --sharpen need --gv')
@@ -538,7 +555,7 @@ def main(argv=None, config=None):
         c.data_path = 'data/%s/' % a.train_set
     checkpoint = a.checkpoint or latest_checkpoint(os.path.join('weights', '%s/tacotron' % a.train_set))
     return evaluate(c, a.holdout, checkpoint, a.speaker, a.cepstra, a.out_dir, f0=a.f0, f0_aligned=a.f0_aligned, durations=a.durations,
-                    path_jump=a.path_jump, f0_smooth=a.f0_smooth, gv=a.gv, gv_lifter=a.gv_lifter, sharpen=a.sharpen)
+                    path_jump=a.path_jump, f0_smooth=a.f0_smooth, gv=a.gv, gv_lifter=a.gv_lifter, sharpen=a.sharpen, ema=a.ema)
 
 
 if __name__ == '__main__':

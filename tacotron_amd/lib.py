@@ -194,6 +194,8 @@ EXPORTS = {
     'taco_tensor_stats_plan': (C.c_int, [C.POINTER(C.c_int64), _I, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int32)]),
     'taco_tensor_stats_workspace_bytes': (C.c_int64, [_I, _I, _I]),
     'taco_tensor_stats': (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'taco_param_ema_workspace_bytes': (C.c_int64, [C.c_int64]),
+    'taco_param_ema': (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
     'taco_profile_enable': (C.c_int, [_I]),
     'taco_debug_last_cluster': (C.c_int, [_I]),
     'taco_profile_read': (C.c_int, [_I, C.POINTER(C.c_float), _I]),
@@ -2380,6 +2382,54 @@ def tensor_stats(base, plan, e_lo=STATS_E_LO, e_hi=STATS_E_HI, sub_bits=STATS_SU
     _check(_lib.taco_tensor_stats(ptr(base), ptr(plan.dev), C.c_void_p(plan.header.ctypes.data), plan.n, plan.n_items, e_lo, e_hi,
                                   sub_bits, ptr(counts), ptr(moments), ptr(hist), ptr(work), stream_ptr()), 'taco_tensor_stats')
     return TensorStats(counts, moments, hist)
+
+
+EMA_WARMUP = (1.0, 10.0)   # tf.train.ExponentialMovingAverage(num_updates=k): decay_k = min(decay, (1 + k) / (10 + k))
+
+
+def ema_decay(decay, k) -> float:
+    """The decay of weight-averaging update number k (k = 0 the first: the EMA updates attempted before this one), TF's num_updates
+    warm-up min(decay, (1 + k) / (10 + k)) in Python floats: 0.1, 0.18, ... until the configured decay takes over."""
+    decay = float_arg('ema_decay', 'decay', decay, 0.0, 1.0)
+    k = int_arg('ema_decay', 'k', k, 0)
+    return min(decay, (EMA_WARMUP[0] + k) / (EMA_WARMUP[1] + k))
+
+
+def ema_weight(decay, k):
+    """w of param_ema for update number k: 1 - ema_decay(decay, k) in Python floats, rounded once to float32"""
+    return np.float32(1.0 - ema_decay(decay, k))
+
+
+def param_ema_workspace_bytes(n) -> int:
+    return _size('taco_param_ema_workspace_bytes', n)
+
+
+def param_ema(ema, params, w, err_words=None, stats=None, workspace=None):
+    """One weight-averaging update in place (include/taco_hip.h taco_param_ema): ema[i] += w (params[i] - ema[i]) as three rounded
+    fp32 operations, ema and params flat fp32 tensors of one length on the GPU that do not overlap (any float alignment), w in [0, 1]
+    (ema_weight).  err_words: the two int32 error words of clip_adam_step, or None (unguarded): with either set, ema stays as it is.
+    stats: None, or 3 float64 on the device that receive (sum of the squared differences before the update, sum of params^2, 1), or
+    (-1, -1, 0) for a skipped update; workspace then is param_ema_workspace_bytes(n) bytes of uint8 (default: a fresh one).  One
+    launch, two with stats, on the current stream; no copy and no synchronisation.  Returns stats."""
+    who = 'param_ema'
+    n, = tensor_arg(who, 'ema', ema, torch.float32, ('floats',))
+    dev = ema.device
+    tensor_arg(who, 'params', params, torch.float32, (n,), dev)
+    w = float_arg(who, 'w', w, 0.0, 1.0)
+    tensor_arg(who, 'err_words', err_words, torch.int32, (2,), dev, optional=True)
+    tensor_arg(who, 'stats', stats, torch.float64, (3,), dev, optional=True)
+    tensor_arg(who, 'workspace', workspace, torch.uint8, ('bytes',), dev, optional=True)
+    no_overlap(who, 'params', params, 'ema', ema)
+    on_gpu(who, 'ema', dev)
+    if stats is not None:
+        need = param_ema_workspace_bytes(n)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif workspace.numel() < need or workspace.data_ptr() % 8:
+            raise ValueError('%s: workspace must hold %d bytes and be 8-byte aligned, got %d' % (who, need, workspace.numel()))
+    _check(_lib.taco_param_ema(ptr(ema), ptr(params), n, w, ptr(err_words), ptr(stats), ptr(workspace) if stats is not None else None,
+                               stream_ptr()), 'taco_param_ema')
+    return stats
 
 
 def last_cluster(which: int) -> int:

@@ -85,6 +85,16 @@ class Tacotron(object):
             self.adam_v = torch.zeros(n, device=dev)
             self._scratch = torch.zeros(256, device=dev)
             self._gnorm = torch.zeros(1, device=dev)
+            # weight averaging (Config.ema_decay in (0, 1); lib.param_ema): the average starts as a COPY of the weights -- an update
+            # with w = 1 would not give one, e + (p - e) is not p in fp32.  With averaging off none of these attributes exists
+            decay = float(getattr(config, 'ema_decay', 0.0) or 0.0)
+            if decay > 0.0:
+                self.ema_decay = decay
+                self.ema = params.flat.detach().clone()
+                self.ema_updates = 0              # ATTEMPTED updates, like global_step (apply_gradients)
+                self.ema_stats = torch.zeros(3, dtype=torch.float64, device=dev)   # what the last step(ema_stats=True) left
+                self._ema_work = torch.empty(lib.param_ema_workspace_bytes(n), dtype=torch.uint8, device=dev)
+                self._ema_said = False
             # the five mask tensors are views of ONE byte buffer (16-byte aligned pieces), so that neighbours with the same
             # Bernoulli parameter are filled by a single launch (all five, with the reference's default rates)
             shapes = (('enc_keep1', (B, Tt, 256)), ('enc_keep2', (B, Tt, 128)), ('dec_keep1', (B, Td, 256)),
@@ -166,25 +176,35 @@ class Tacotron(object):
         lib.backward(self.shape, self.params.flat, i['text'], i['text_length'], self.seq2seq_output, self.alignments,
                      self.masks, self.grads, self.workspace, self.speaker)
 
-    def apply_gradients(self, lr):
+    def apply_gradients(self, lr, ema_stats=False):
         """Guarded: if a decoder kernel flagged a timed-out exchange (on ANY rank -- the error words are MAX-reduced with
         the gradients) the update is skipped on the device and `global_gradient_norm` reads -1; check() raises.
         `global_step` counts ATTEMPTED updates (it is advanced on the host before the device decides): after a skipped update
         the Adam bias-correction step, the annealing cadence and the checkpoint numbering run ahead of the updates actually
         applied by the number of skipped steps -- which check() reports at the next synchronisation point, where the drivers
-        stop."""
+        stop.
+        With weight averaging on (Config.ema_decay), lib.param_ema follows on the same stream under the same error words, so the
+        average skips what Adam skips; `ema_updates` counts attempted updates like `global_step`, with the same caveat, and sets the
+        warm-up (lib.ema_decay).  ema_stats: the call also leaves its three statistics in `self.ema_stats` (device, fp64)."""
         self.global_step += 1
         lib.clip_adam_step(self.params.flat, self.grads, self.adam_m, self.adam_v, lr, self.config.cap_grads,
                            self.global_step, self._scratch, self._gnorm, self._err)
+        if hasattr(self, 'ema'):
+            lib.param_ema(self.ema, self.params.flat, lib.ema_weight(self.ema_decay, self.ema_updates), self._err,
+                          self.ema_stats if ema_stats else None, self._ema_work if ema_stats else None)
+            self.ema_updates += 1
 
-    def step(self, lr=None, masks='draw', monitor=False):
+    def step(self, lr=None, masks='draw', monitor=False, ema_stats=False):
         """One `sess.run(train_op)`: forward + backward (+ gradient all-reduce, overlapped with the backward pass) +
         clip + Adam.  Everything is enqueued on the current stream; nothing is copied to the host.
         monitor: the training monitor (monitor_sites, lib.tensor_stats).  The activation sites are read between the forward and the
         backward pass, which may reuse workspace rows; the parameters, the gradients and both Adam slots AFTER the update: the update
         reads the gradient buffer and never writes it, so what is seen there is the (reduced) gradient the step used, next to the
         parameters and slots it left.  Seven calls, into `monitor_result`, which stays on the device.  False: not one launch, copy
-        or synchronisation more than before."""
+        or synchronisation more than before.
+        ema_stats (weight averaging on only): this step's lib.param_ema also writes `self.ema_stats` = (squared distance of the new
+        weights from the average before the update, sum of the weights' squares, 1; or -1, -1, 0 for a skipped update), which stays
+        on the device.  False: the averaging pass is one launch and reduces nothing."""
         if masks == 'draw':
             masks = self.draw_masks()
         self.forward(masks)
@@ -193,7 +213,10 @@ class Tacotron(object):
         self.backward()
         if self.reducer is not None:
             self.reducer.reduce_after_backward(self)
-        self.apply_gradients(self.lr if lr is None else lr)
+        if ema_stats and hasattr(self, 'ema'):
+            self.apply_gradients(self.lr if lr is None else lr, ema_stats=True)
+        else:
+            self.apply_gradients(self.lr if lr is None else lr)
         if monitor:
             self.monitor_stats(MONITOR_UPDATE)
 
@@ -432,19 +455,43 @@ class Tacotron(object):
         if self.train:
             d['adam_m'] = self.adam_m.cpu()
             d['adam_v'] = self.adam_v.cpu()
+            if hasattr(self, 'ema'):   # weight averaging on: the average travels with the Adam slots; off: no key
+                d['ema'] = self.ema.cpu()
+                d['ema_updates'] = self.ema_updates
+                d['ema_decay'] = self.ema_decay
         return d
 
-    def load_state_dict(self, d):
+    def load_state_dict(self, d, use_ema=False):
+        """use_ema (test.py --ema, evaluate.py --ema): the weights are the checkpoint's AVERAGED weights d['ema'] instead of the live
+        ones; lib.TacoError when the checkpoint holds none (written without --ema, or imported from TF).
+        A training model with weight averaging on continues the checkpoint's average and its update count when it has them; else
+        the average starts again from the restored weights with ema_updates = 0, said once."""
+        if use_ema and 'ema' not in d:
+            raise lib.TacoError('the checkpoint holds no averaged weights (written without --ema, or imported): its keys are %s'
+                                % ', '.join(sorted(str(k) for k in d)))
         if tuple(d.get('shape', (self.shape.r, self.shape.V))) != (self.shape.r, self.shape.V) or \
                 int(d.get('num_speakers', max(1, self.shape.S))) != max(1, self.shape.S) or \
                 d['params'].numel() != self.params.numel:
             raise lib.TacoError('checkpoint was written for (r, V)=%s, %s speaker(s), %d parameters; this model has (r, V)=%s, '
                                 '%d speaker(s), %d parameters' % (d.get('shape'), d.get('num_speakers', '?'), d['params'].numel(),
                                                                   (self.shape.r, self.shape.V), max(1, self.shape.S), self.params.numel))
-        self.params.flat.copy_(d['params'])
+        if use_ema and d['ema'].numel() != self.params.numel:
+            raise lib.TacoError('the checkpoint\'s averaged weights hold %d floats, this model has %d parameters'
+                                % (d['ema'].numel(), self.params.numel))
+        self.params.flat.copy_(d['ema'] if use_ema else d['params'])
         self.global_step = int(d.get('global_step', 0))
         if 'stft_mean' in d:
             self.stft_mean, self.stft_std = d['stft_mean'], d['stft_std']
         if self.train and 'adam_m' in d:
             self.adam_m.copy_(d['adam_m'])
             self.adam_v.copy_(d['adam_v'])
+        if self.train and hasattr(self, 'ema'):
+            if 'ema' in d and d['ema'].numel() == self.params.numel:
+                self.ema.copy_(d['ema'])
+                self.ema_updates = int(d.get('ema_updates', 0))
+            else:
+                self.ema.copy_(self.params.flat)
+                self.ema_updates = 0
+                if not self._ema_said:
+                    self._ema_said = True
+                    print('the checkpoint holds no averaged weights: the average starts from the restored weights (ema_updates = 0)')

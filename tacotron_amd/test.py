@@ -105,7 +105,11 @@ a run without the flag: the same files, byte for byte.  BETA and Q are UNTUNED a
 `python -m tacotron_amd.evaluate --gv --sharpen BETA` gives the global-variance ratio with and without it.  It combines with every option
 above; with --long every piece is sharpened.  The two settings are not fields of the options record of test(): they travel as
 Config.sharpen / Config.sharpen_lifter, next to the paths the command line also leaves there, and a run reads them from its resolved
-options like every other."""
+options like every other.
+--ema (opt-in, with --checkpoint; not in the reference): the weights are the checkpoint's exponential moving average of the parameters
+(`train --ema DECAY`) instead of the ones the last minibatch left.  A checkpoint without an average -- written without `train --ema`,
+or imported from TF -- is refused before anything is synthesised.  Everything downstream is unchanged, and it combines with every
+option above.  Nobody has listened to the difference."""
 from __future__ import annotations
 
 import argparse
@@ -639,10 +643,14 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     `config.sharpen` / `config.sharpen_lifter` (need `vocode`; Config's defaults: None, 32): None or 0 -- every file is what it was -- or
     a beta in [-1, 1]: the magnitudes of every row go through the cepstral post-filter first (vocode(sharpen=...), lib.frames_sharpen),
     in front of `pitch`, `rate`, `prosody` and `f0`, over the row's own len_b r frames wherever the vocoder gets the lengths, else over
-    all frames; with `long`, every piece.  prompt_NNN_sharpen.npy holds (beta, lifter) as float64.  Untuned; nobody has listened."""
+    all frames; with `long`, every piece.  prompt_NNN_sharpen.npy holds (beta, lifter) as float64.  Untuned; nobody has listened.
+    `config.use_ema` (--ema; needs `checkpoint`; Config's default: False): decode from the checkpoint's AVERAGED weights (train --ema,
+    Tacotron.load_state_dict(use_ema=True)) instead of the live ones; lib.TacoError before the first batch when the checkpoint holds
+    none.  Like the sharpening pair it travels on the Config, not in the options record: it chooses the weights, and everything
+    downstream is unchanged."""
     opt = Options(**{k: v for k, v in locals().items() if k in Options.__dataclass_fields__}).resolved(   # (locals(): the parameters)
         getattr(config, 'sharpen', None), getattr(config, 'sharpen_lifter', lib.SHARPEN_LIFTER))
-    run = Run(config, opt, prompts, out_dir, checkpoint, speaker)
+    run = Run(config, opt, prompts, out_dir, checkpoint, speaker, bool(getattr(config, 'use_ema', False)))
     n = _test_long(run) if opt.long is not None else _test_rows(run, prompts)
     print('wrote %d samples to %s' % (n, out_dir))
     return n
@@ -671,7 +679,7 @@ class Run:
     with `long` a piece of one, which inherits its prompt's rate and pitch -- the line, its name in printed lines and its step_q
     values, all resolved before the first batch."""
 
-    def __init__(self, config, opt, prompts, out_dir, checkpoint=None, speaker=0):
+    def __init__(self, config, opt, prompts, out_dir, checkpoint=None, speaker=0, use_ema=False):
         steps, pitch = rate_steps(opt.rate, len(prompts)), pitch_steps(opt.pitch, len(prompts))
         self.config, self.opt, self.out_dir, self.speaker = config, opt, out_dir, speaker
         meta_path = os.path.join(config.data_path, 'meta.pkl')
@@ -683,6 +691,11 @@ class Run:
             self.ivocab[0] = '<pad>'
         config.vocab_size = len(self.ivocab)
         self.ckpt = torch.load(checkpoint) if checkpoint else None
+        self.use_ema = bool(use_ema)
+        if self.use_ema and (self.ckpt is None or 'ema' not in self.ckpt):   # (before anything is built or written)
+            raise lib.TacoError('use_ema (--ema): %s' % ('there is no checkpoint to take averaged weights from' if self.ckpt is None else
+                                                         'the checkpoint %s holds no averaged weights (written without `train --ema`, or '
+                                                         'imported): its keys are %s' % (checkpoint, ', '.join(sorted(map(str, self.ckpt))))))
         if self.ckpt is not None:
             config.r, config.vocab_size = self.ckpt.get('shape', (config.r, config.vocab_size))
             config.num_speakers = int(self.ckpt.get('num_speakers', 1))
@@ -720,7 +733,7 @@ class Run:
         if model is None:
             model = self.models[Bn] = Tacotron(c, batch, train=False, params=self.params)
             if self.ckpt is not None:
-                model.load_state_dict(self.ckpt)
+                model.load_state_dict(self.ckpt, use_ema=True) if self.use_ema else model.load_state_dict(self.ckpt)
         else:
             model.set_inputs(batch)
         return model
@@ -1064,6 +1077,9 @@ def parse_args(argv=None):
                          'listened; not in the reference)')
     ap.add_argument('--sharpen-lifter', type=int, default=None, metavar='Q',
                     help='--sharpen: the highest quefrency scaled, 2 <= Q <= 64 (default %d, untuned)' % lib.SHARPEN_LIFTER)
+    ap.add_argument('--ema', action='store_true',
+                    help='decode from the averaged weights of a checkpoint written by `train --ema DECAY` instead of the live ones; an '
+                         'error when the checkpoint holds none (not in the reference; nobody has listened to the difference)')
     ap.add_argument('--path-jump', type=int, default=None, metavar='J',
                     help='--timings / --prosody: characters a decoder step may advance on the path, 1 <= J <= 15 (default %d, untuned)' % lib.PATH_JUMP)
     a = ap.parse_args(argv)
@@ -1080,6 +1096,8 @@ def parse_args(argv=None):
     a.path_jump = lib.PATH_JUMP if a.path_jump is None else a.path_jump
     if a.sharpen_lifter is not None and a.sharpen is None:
         ap.error('--sharpen-lifter needs --sharpen')
+    if a.ema and a.checkpoint is None:
+        ap.error('--ema needs --checkpoint: the averaged weights come from a checkpoint of `train --ema`')
     a.sharpen_lifter = lib.SHARPEN_LIFTER if a.sharpen_lifter is None else a.sharpen_lifter
     try:
         Options(**option_keywords(a)).resolved(a.sharpen, a.sharpen_lifter)
@@ -1098,5 +1116,6 @@ if __name__ == '__main__':
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
     c.sharpen, c.sharpen_lifter = a.sharpen, a.sharpen_lifter
+    c.use_ema = a.ema
     print('Building Tacotron')
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, **option_keywords(a))

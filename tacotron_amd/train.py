@@ -9,7 +9,11 @@ rows alignment.flags marks; the listening sample gets attention_<step>.png and a
 parameter, gradient and Adam slot and of the activations the reference histograms (Tacotron.step(monitor=True), lib.tensor_stats);
 one more line names the largest gradient RMS and lr |grad| / |param|, the share of zeros behind the encoder pre-net and the tensors
 that hold non-finite values, and monitor/monitor_<step>.npz keeps everything.
---holdout N (default 0): the last N utterances are never drawn, so that tacotron_amd.evaluate can score checkpoints on them."""
+--holdout N (default 0): the last N utterances are never drawn, so that tacotron_amd.evaluate can score checkpoints on them.
+--ema DECAY (opt-in, 0 < DECAY < 1, no default): weight averaging.  Behind every update one more pass on the device moves an
+exponential moving average of the parameters towards the new weights (lib.param_ema; tf.train.ExponentialMovingAverage's rule and
+num_updates warm-up, skipped when the Adam update is); the log steps print the decay in use and the distance of the weights from
+their average, and checkpoints carry the average for `test --ema` and `evaluate --ema`.  Without it nothing changes."""
 from __future__ import annotations
 
 import argparse
@@ -113,6 +117,17 @@ def save_monitor(model, out_dir, step, host=None):
     return path
 
 
+def ema_line(decay, k, stats):
+    """The --ema line of one log step: decay the configured one, k the number of the update the step made (0 the first), stats the
+    three host values of Tacotron.ema_stats (lib.param_ema).  It gives the decay the warm-up used and lag = |weights - average| /
+    |weights|, the distance before the update over the norm of the weights; a skipped update says so."""
+    from . import lib
+    d2, p2, applied = (float(x) for x in stats)
+    if applied != 1.0:
+        return 'ema decay %.6f update skipped (decoder error words set)' % lib.ema_decay(decay, k)
+    return 'ema decay %.6f lag %.3e' % (lib.ema_decay(decay, k), math.sqrt(d2 / p2) if p2 > 0.0 else float('nan'))
+
+
 def load_corpus(data_path, seed=0):
     """data_input.load_meta + load_from_npy (data_input.py:43-85,110-113) when the npy files exist.  The normalisation
     statistics come from 100 utterances like the reference's (data_input.py:55-65) but from a SEEDED draw, so every rank
@@ -186,8 +201,15 @@ def holdout_draw(n, holdout, batch_size, seed):
     return lambda step: rng.integers(n - holdout, size=int(batch_size))
 
 
-def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False, holdout=0, monitor=False):
-    """monitor: the training monitor.  The log steps (global step a multiple of log_every) run with Tacotron.step(monitor=True):
+def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus_fp32=False, align_log=False, holdout=0, monitor=False,
+          ema=None):
+    """ema: None, or the decay of weight averaging, 0 < ema < 1 (Config.ema_decay).  Every step then ends with one more pass on the
+    device (lib.param_ema) that moves an average of the parameters towards the new weights, under TF's num_updates warm-up; the log
+    steps also reduce its statistics and print one more line (ema_line), read at the synchronisation point that is there already.
+    Checkpoints carry the average (`test --ema`, `evaluate --ema`); the listening sample stays on the live weights.  No decay is
+    tuned here and nobody has listened to a voice decoded from an average.  None: every step, file, line and checkpoint is what it
+    was.
+    monitor: the training monitor.  The log steps (global step a multiple of log_every) run with Tacotron.step(monitor=True):
     statistics and histograms of every parameter, gradient and Adam slot and of the reference's histogram sites, computed on the
     device (lib.tensor_stats).  Rank 0 reads them at the log step's synchronisation point, writes
     log/<save_path>/monitor/monitor_<step>.npz (save_monitor) and prints one more line (monitor_line); before `loss exploded` it
@@ -199,6 +221,10 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
     copy or synchronisation is added to any other step.
     corpus_fp32: standardise the whole corpus on the host and feed fp32 (load_corpus; A/B runs) instead of keeping it as stored
     and standardising in the batch gather (open_corpus + norm=, the default).  The batches are bit-identical either way."""
+    if ema is not None:
+        if not 0.0 < float(ema) < 1.0:   # (NaN fails)
+            raise ValueError('ema (--ema) must be a decay in (0, 1), got %r' % (ema,))
+        config.ema_decay = float(ema)
     rank, world, local = init_from_env()
     torch.cuda.set_device(local)
     corpus = load_corpus(config.data_path) if corpus_fp32 else open_corpus(config.data_path)
@@ -255,6 +281,7 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
             if rank == 0:
                 print('restored %s (global_step %d)' % (path, model.global_step))
     lr = config.init_lr
+    averaging = hasattr(model, 'ema')
     import time
     mon_step, mon_lr, mon_host = None, lr, None           # the step model.monitor_result belongs to, and its host copy once read
     t_mark, s_mark, step = None, 0, -1                    # throughput of the host loop itself (reported when the loop ends)
@@ -262,7 +289,11 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
         for step in range(num_steps):
             model.set_inputs(next_batch(step))                # device tensors from the feeder: a pointer swap
             mon = monitor and (model.global_step + 1) % log_every == 0
-            model.step(lr, monitor=mon)
+            ema_log = averaging and (model.global_step + 1) % log_every == 0
+            if ema_log:
+                model.step(lr, monitor=mon, ema_stats=True)   # (the averaging pass of this step also reduces its statistics)
+            else:
+                model.step(lr, monitor=mon)
             gs = model.global_step
             if mon:
                 mon_step, mon_lr = gs, lr
@@ -286,6 +317,8 @@ def train(config, num_steps=1000000, log_every=50, save_every=SAVE_EVERY, corpus
                     if scores is not None:                    # (B, 6) + (B, 2) + (B) values, already computed: no alignment tensor travels
                         print('step %d %s' % (gs, align_line(scores[0].cpu().numpy(), scores[1].cpu().numpy(),
                                                              model.inputs['text_length'].cpu().numpy(), model.shape.Tt)))
+                    if ema_log:                               # three doubles, behind the sync above
+                        print('step %d %s' % (gs, ema_line(model.ema_decay, model.ema_updates - 1, model.ema_stats.tolist())))
                     if mon:                                   # three copies behind the sync above: (N, 6) + (N, 5) + (N, NB) values
                         mon_host = tuple(t.cpu().numpy() for t in model.monitor_result)
                         save_monitor(model, os.path.join('log', config.save_path, 'monitor'), gs, mon_host)
@@ -355,7 +388,15 @@ def parse_args(argv=None):
                          'log/<save_path>/monitor/monitor_<step>.npz; names the non-finite tensors before `loss exploded`')
     ap.add_argument('--holdout', type=int, default=0, metavar='N',
                     help='never draw the last N utterances of the corpus: the set `python -m tacotron_amd.evaluate --holdout N` scores')
-    return ap.parse_args(argv)
+    ap.add_argument('--ema', type=float, default=None, metavar='DECAY',
+                    help='weight averaging: keep an exponential moving average of the parameters on the device, 0 < DECAY < 1 (e.g. '
+                         '0.999; no default and none tuned here), with TF\'s num_updates warm-up; one more pass per step, one more log '
+                         'line, and checkpoints that `test --ema` / `evaluate --ema` can decode from (not in the reference; nobody has '
+                         'listened to the result)')
+    a = ap.parse_args(argv)
+    if a.ema is not None and not 0.0 < a.ema < 1.0:
+        ap.error('--ema DECAY must be in (0, 1), got %r' % (a.ema,))
+    return a
 
 
 if __name__ == '__main__':
@@ -365,4 +406,4 @@ if __name__ == '__main__':
     c.restore = a.restore
     c.save_path = 'debug' if a.debug else '%s/tacotron' % a.train_set
     print('Building Tacotron')
-    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log, holdout=a.holdout, monitor=a.monitor)
+    train(c, a.steps, corpus_fp32=a.corpus_fp32, align_log=a.align_log, holdout=a.holdout, monitor=a.monitor, ema=a.ema)
