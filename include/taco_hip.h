@@ -625,6 +625,38 @@ int taco_frames_stretch(const float* mag_t, const int32_t* frames, int frames_pe
 int taco_frames_pitch(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
                       float* out, int B, int C, int F, void* stream);
 
+/* Timbre at synthesis (no reference counterpart), the dual of taco_frames_pitch in the same place: the envelope (the formants, the
+ * apparent vocal-tract length) moves along the bin axis and the harmonics stay where they are.  Every argument exactly as
+ * taco_frames_pitch: mag_t, out (B, C, F) fp32 with the frame index contiguous, C - 1 a power of two in 8 .. 1024; frames,
+ * frames_per_unit and F_b; step_q (B) int32 on the DEVICE or NULL, s_b = clamp(step_q[b], TACO_PITCH_MIN_STEP, TACO_PITCH_MAX_STEP),
+ * NULL: TACO_PITCH_ONE, step_q = 65536 / ratio with ratio = 2^(semitones / 12) -- a ratio above 1 moves the formants UP; lifter Q in
+ * 1 .. min(TACO_PITCH_MAX_LIFTER, (C - 1) / 2).  The host reads nothing from frames or step_q.
+ * For frame f < F_b of row b, m[k] = mag_t[b, k, f], in real numbers:
+ *   L[k], c[n] (n = 0 .. Q), E[k]          exactly as taco_frames_pitch defines them (floor TACO_PITCH_FLOOR, rectangular lifter)
+ *   p = k * s_b, i = p >> 16, w = (p & 0xFFFF) 2^-16
+ *   E'[k] = E[i] + w (E[i+1] - E[i])       for i < C - 1;  E[C-1] otherwise (the envelope is held beyond the top bin)
+ *   y[k]  = m[k] exp(E'[k] - E[k])         (m, not max(m, floor): a zero bin stays exactly zero)
+ *   P0 = sum_k m[k]^2, P1 = sum_k y[k]^2   (plain sums, k = 0 .. C - 1);  g = sqrt(P0 / P1), and 1 when P1 == 0
+ *   out[b, k, f] = y[k] g
+ * so the log-excitation L - E of every bin at or above the floor is unchanged, the envelope is the input's read at k / ratio, and
+ * the frame energy is the input's, as in taco_frames_sharpen.  Computed in fp32 with the cepstrum and envelope chains of
+ * taco_frames_pitch (the same fp32 cepstra and envelope) and held to an fp64 restatement (tests/formant_ref.py).  Exactly:
+ *   - a row with s_b == TACO_PITCH_ONE is copied bit for bit for f < F_b, no log / exp round trip;
+ *   - out[b, k, f] = +0 for F_b <= f < F;
+ *   - every element of out is written and nothing outside it, for any 4-byte alignment of mag_t and out;
+ *   - columns behind F_b, other rows and other frames have no influence on a frame (they may hold NaN);
+ *   - the bits of a frame depend on its own C bins, s_b and Q alone -- not on B, F, its position or the buffers' alignment; no
+ *     atomics; the same arguments give the same bits; row b of a B-row call equals the call on that row alone.
+ * One launch of B x ceil(F / 32) workgroups, no workspace, no allocation, no host synchronisation: graph-capturable, and a replay
+ * follows whatever frames and step_q hold at replay time.  The refusals of taco_frames_pitch: NULL mag_t / out, out overlapping
+ * mag_t, a bad B, C, F or frames_per_unit and lifter out of range return TACO_EINVAL with a message that names the argument, before
+ * anything is enqueued.  TACO_VERSION did not change with this entry point: detect it by the symbol.
+ * Not here: a per-frame or per-word formant curve, a fused pitch + formant launch that shares one cepstrum, mel frames, a tapered
+ * lifter.  Nobody has listened to the result: the default lifter of the Python layer (32) is untuned, and the limits of +-12
+ * semitones are those of taco_frames_pitch's arithmetic, not recommendations. */
+int taco_frames_formant(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                        float* out, int B, int C, int F, void* stream);
+
 /* Prosody inside an utterance (no reference counterpart): the two controls above with one value per FRAME instead of one per row, and
  * the gather that makes such curves from per-character values along the path of taco_alignment_path -- which decoder step speaks
  * which character is the anchor a per-word rate or pitch needs.  Each is one or two plain launches on the caller's stream: no

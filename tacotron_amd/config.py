@@ -54,6 +54,10 @@ class Config(object):
     sharpen = None
     sharpen_lifter = 32
 
+    # synthesis only (test.py --formant SEMITONES / --formant-lifter Q): the formant shift behind the post-filter; None: off
+    formant = None
+    formant_lifter = 32
+
     # training only (train.py --ema DECAY; not in the reference): an exponential moving average of the parameters, kept on the device
     # beside the Adam slots and saved with them; 0: off -- no buffer, no launch, no checkpoint key.  No tuned default
     ema_decay = 0.0

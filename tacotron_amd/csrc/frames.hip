@@ -1,9 +1,9 @@
 // frames.hip -- the synthesis frame chain: what happens to the decoder's output between the model and the vocoder, and the pitch
 // read-outs over the same magnitude frames (include/taco_hip.h taco_denorm_unframe, taco_frames_stretch, taco_frames_stretch_curve,
-// taco_frames_pitch, taco_frames_pitch_curve, taco_frames_sharpen, taco_frames_cepstats, taco_frames_f0, taco_f0_stats,
-// taco_path_f0_scores).  Every entry point stands behind its kernels with the refusals that guard them; each kernel's comment has its
-// form and why.  The cosine products of frames_pitch_kernel, frames_sharpen_kernel, frames_cepstats_kernel and
-// frames_f0_kernel are fp32 MFMAs; everything else here is bound by memory.
+// taco_frames_pitch, taco_frames_pitch_curve, taco_frames_sharpen, taco_frames_formant, taco_frames_cepstats, taco_frames_f0,
+// taco_f0_stats, taco_path_f0_scores).  Every entry point stands behind its kernels with the refusals that guard them; each kernel's
+// comment has its form and why.  The cosine products of frames_pitch_kernel, frames_sharpen_kernel,
+// frames_formant_kernel, frames_cepstats_kernel and frames_f0_kernel are fp32 MFMAs; everything else here is bound by memory.
 #include <type_traits>
 
 #include "common.h"
@@ -543,6 +543,106 @@ __global__ __launch_bounds__(64 * kWaves) void frames_sharpen_kernel(const float
   for (int k = 2 * wave + h; k < C; k += 2 * kWaves) dst[k * F] = live ? env[k * kPitchFrames + fl] * g : 0.f;
 }
 
+// taco_frames_formant: the dual of taco_frames_pitch -- the envelope is read at k * s_b and the excitation stays (include/taco_hip.h
+// has the definition).  The shape of frames_sharpen_kernel: 32 frames of a row per workgroup, the frame in the lane's low five bits,
+// NB = 1 (16 waves) for Q <= 32 and 2 (8 waves) above, chosen by Q alone.  Three stages:
+//   cepstrum  cepstrum_tile above;
+//   E[k][f]   the envelope call of the pitch kernel (cosine_tile, init c[0], scale 2, rows 1 .. NR), so E has the same fp32 cepstra
+//             and envelope by construction; E of the tile stays in LDS (C x 32 floats);
+//   output    E'[k] reads E at the bins i and i + 1 that other threads own, so y cannot take E's place element by element as in the
+//             sharpen kernel, and a second C x 32 array does not fit the LDS beside E.  A thread therefore keeps the y of its own
+//             bins -- at most kFormantTrips kPitchBatch = 40 | 72 of them, k = 2 wave + h + 2 kWaves j -- in registers across the fold of
+//             the two energies (through the cosine table's bytes, as in the sharpen kernel) and stores y g from them: two reads per
+//             element where one is compulsory, one logarithm and one exponential.  The loop over the trips has a constant trip count
+//             and is unrolled, which is what keeps y in registers; trips at and behind C do nothing.  The other form -- the bins run
+//             twice, once for the energies and once to store y g -- was measured beside it at 32 x 1025 x 360 | 720 and deleted: 83 |
+//             126 us against 70 | 106 (profiles/frames_formant_forms.txt).
+// s_b == TACO_PITCH_ONE and tiles behind F_b: the pitch kernel's copy branch.
+template <int kWaves>
+constexpr int kFormantTrips = (kPitchMaxC + 2 * kWaves * kPitchBatch - 1) / (2 * kWaves * kPitchBatch);
+template <int NB, int kWaves>
+__global__ __launch_bounds__(64 * kWaves) void frames_formant_kernel(const float* __restrict__ mag_t, const int32_t* __restrict__ frames,
+                                                                      int frames_per_unit, const int32_t* __restrict__ step_q, int Q,
+                                                                      float* __restrict__ out, int C, int F, int ntile) {
+  constexpr int NR = 32 * NB;
+  constexpr int NT = kFormantTrips<kWaves>;
+  static_assert(4 * kWaves * kPitchFrames <= 2 * (kPitchMaxC - 1), "the partial sums of P0 and P1 fit the cosine table");
+  static_assert((kWaves * NR + 2 * kWaves) <= kPitchMaxC, "the cepstrum partials fit E's bytes");
+  __shared__ float tab[2 * (kPitchMaxC - 1)];
+  __shared__ float cep[(NR + 1) * kPitchFrames];
+  __shared__ float env[kPitchMaxC * kPitchFrames];   // E[k][f]; before that the waves' partial cepstra
+  const FrameTile t = frame_tile(frames, frames_per_unit, F, ntile);
+  const int tid = threadIdx.x, fl = t.fl, h = t.h, wave = t.wave;
+  const bool live = t.live, inside = t.inside;
+  int s = TACO_PITCH_ONE;
+  if (step_q) {
+    s = step_q[t.b];
+    s = s < TACO_PITCH_MIN_STEP ? TACO_PITCH_MIN_STEP : (s > TACO_PITCH_MAX_STEP ? TACO_PITCH_MAX_STEP : s);
+  }
+  s = __builtin_amdgcn_readfirstlane(s);
+  const float* __restrict__ src = mag_t + (int64_t)t.b * C * F + t.f;    // (C F <= 1025 * 8192: the offsets below fit 32 bits)
+  float* __restrict__ dst = out + (int64_t)t.b * C * F + t.f;
+  if (t.f0 >= t.Fb || s == TACO_PITCH_ONE) {   // (uniform) nothing to shift
+    copy_tile<kWaves>(src, dst, t, C, F);
+    return;
+  }
+  fill_cos_table(tab, 2 * (C - 1), 64 * kWaves);
+  __syncthreads();
+  cepstrum_tile<NB, kWaves>(src, live, Q, C, F, tab, cep, env);
+  // the envelope; nothing reads the cosine table behind it: tab holds the partial sums
+  cosine_tile<NB, kWaves>(tab, cep, cep[fl], 2.0f, 1, NR, C, env);
+
+  // ---- y and the two energies ----  a frame behind F_b inside a live tile has m = 0: y = 0, P0 = P1 = 0, g = 1.  The envelope is
+  // read at indices clamped into the frame; beyond the top bin it is held at E[C - 1]
+  float y[NT * kPitchBatch];
+  float p0 = 0.f, p1 = 0.f;
+#pragma unroll
+  for (int trip = 0; trip < NT; ++trip) {
+    const int kb = 2 * wave + h + 2 * kWaves * kPitchBatch * trip;
+    float m[kPitchBatch];
+#pragma unroll
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kWaves * u;
+      m[u] = (live && k < C) ? src[k * F] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kPitchBatch; ++u) {
+      const int k = kb + 2 * kWaves * u;
+      float v = 0.f;
+      if (k < C) {
+        const uint32_t p = (uint32_t)k * (uint32_t)s;   // (k s <= 1024 * 2^17)
+        const int i = (int)(p >> 16);
+        const float e0 = env[min(i, C - 1) * kPitchFrames + fl], e1 = env[min(i + 1, C - 1) * kPitchFrames + fl];
+        const float ep = i < C - 1 ? e0 + (float)(p & 0xFFFFu) * (1.0f / 65536.0f) * (e1 - e0) : e0;
+        v = m[u] * expf(ep - env[k * kPitchFrames + fl]);
+        p0 += m[u] * m[u];
+        p1 += v * v;
+      }
+      y[trip * kPitchBatch + u] = v;
+    }
+  }
+  tab[(2 * wave + h) * kPitchFrames + fl] = p0;
+  tab[(2 * kWaves + 2 * wave + h) * kPitchFrames + fl] = p1;
+  __syncthreads();
+  if (tid < kPitchFrames) {
+    float P0 = 0.f, P1 = 0.f;
+#pragma unroll
+    for (int w = 0; w < 2 * kWaves; ++w) {
+      P0 += tab[w * kPitchFrames + tid];
+      P1 += tab[(2 * kWaves + w) * kPitchFrames + tid];
+    }
+    cep[tid] = P1 == 0.f ? 1.0f : sqrtf(P0 / P1);
+  }
+  __syncthreads();
+  const float g = cep[fl];
+  if (!inside) return;
+#pragma unroll
+  for (int j = 0; j < NT * kPitchBatch; ++j) {
+    const int k = 2 * wave + h + 2 * kWaves * j;
+    if (k < C) dst[k * F] = live ? y[j] * g : 0.f;
+  }
+}
+
 // taco_frames_cepstats: per row the sums over the live frames of every cepstral coefficient and of its square.  The first launch is
 // the sharpening kernel's first stage per tile of 32 frames (cepstrum_tile: the same chains, so the same fp32 cepstra), then thread n
 // adds the tile's live frames of c[n] and of c[n]^2 in fp64 in frame order and leaves the pair in the workspace at [b][tile][n] --
@@ -1041,6 +1141,24 @@ extern "C" int taco_frames_pitch(const float* mag_t, const int32_t* frames, int 
 extern "C" int taco_frames_pitch_curve(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
                                        float* out, int B, int C, int F, void* stream) {
   return frames_pitch_call<true>("frames_pitch_curve", mag_t, frames, frames_per_unit, step_q, lifter, out, B, C, F, stream);
+}
+// the refusals of taco_frames_pitch in its order
+extern "C" int taco_frames_formant(const float* mag_t, const int32_t* frames, int frames_per_unit, const int32_t* step_q, int lifter,
+                                   float* out, int B, int C, int F, void* stream) {
+  const char* who = "frames_formant";
+  int ntile;
+  int64_t blocks;
+  TACO_REQUIRE(!mag_t || out, "%s: out is NULL", who);   // (mag_t is refused first, below)
+  TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, 1, lifter, B, C, F, &ntile, &blocks));
+  const uint64_t bytes = (uint64_t)B * (uint64_t)C * (uint64_t)F * 4;   // (< 2^31 * 2^11 * 2^13 * 4)
+  TACO_TRY(frames_no_overlap(who, "out", out, bytes, mag_t, bytes));
+  hipStream_t s = as_stream(stream);
+  by_lifter(lifter, [&](auto nb, auto waves) {
+    TACO_KLAUNCH((frames_formant_kernel<nb.value, waves.value>), dim3((unsigned)blocks), dim3(64 * waves.value), 0, s, mag_t, frames,
+                 frames_per_unit, step_q, lifter, out, C, F, ntile);
+  });
+  TACO_LAUNCH_CHECK(who);
+  return TACO_OK;
 }
 extern "C" int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_unit, const float* weight, const float* gain,
                               int lag_min, int lag_max, float ratio, float threshold, float* period, float* strength, float* acf,

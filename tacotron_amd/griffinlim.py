@@ -30,6 +30,9 @@ and, behind `pitch` / `rate`, the frames the vocoder is handed -- the objective 
 With `sharpen` (opt-in) every magnitude frame goes through a cepstral post-filter first (taco_frames_sharpen): the low quefrencies of
 its envelope are scaled up at unchanged energy, against the over-smoothed envelopes an L1 loss leaves.
 
+With `formant` (opt-in) the envelope of every magnitude frame is moved along the bin axis under the frame's own unmoved harmonics
+(taco_frames_formant), the dual of `pitch`: the voice gets smaller or larger, the pitch and the duration stay.
+
 With `phase_init='estimate'` (opt-in) Griffin-Lim starts from phases read off the magnitudes (taco_phase_estimate: single-pass
 spectrogram inversion) instead of random ones; with n_iter = 0 that estimate alone is the waveform -- a draft voice at one synthesis pass.
 
@@ -56,7 +59,7 @@ SR = 16000   # test.py:11
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
                        lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
                        rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None, sharpen=None,
-                       sharpen_lifter=lib.SHARPEN_LIFTER):
+                       sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=32):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -118,6 +121,15 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     through lib.frames_sharpen (taco_frames_sharpen): the quefrencies 2 .. sharpen_lifter of every frame's cepstrum scaled by
     1 + beta at unchanged frame energy, against the over-smoothed envelopes of an L1-trained post-net.  beta and the lifter (32)
     are UNTUNED: nobody has listened.  Return shapes do not change.
+    formant (opt-in): None or 0 -- nothing is touched, bit for bit -- or a number of semitones in [-12, 12] (+ moves the formants up:
+    a shorter vocal tract), a host sequence of B such numbers, or a (B) int32 device tensor of step_q values (lib.formant_step):
+    behind `sharpen` and the 'model' F0 track and in front of `pitch` / `pitch_curve` and the stretch, the first len_b r frames of
+    every row (all F frames without `lengths`) go through lib.frames_formant (taco_frames_formant) with formant_lifter quefrencies
+    of envelope (32: UNTUNED): the envelope is read at k / ratio under the unmoved harmonics, at unchanged frame energy.  With `f0`
+    the frames behind the stage are tracked as 'formant' (with 'formant_raw' / 'formant_counts' under 'smooth'), and
+    'formant_stats' is the paired lib.f0_stats (B, 3) of 'formant' against 'model': 1200 x its mean is the drift of the pitch in
+    cents, which should be none.  'pitch_stats' then compares 'pitched' with 'formant', the track directly in front of the pitch
+    stage.  Nobody has listened.  Return shapes do not change.
     Everything stays on the device.  F0 in Hz is SR / period."""
     res = tuple(x for x in vocode(**locals()) if x is not None)   # (the first statement: locals() are the parameters)
     return res[0] if len(res) == 1 else res
@@ -174,11 +186,14 @@ def _f0_tracker(f0, out, r, lengths):
             smoothed = lib.f0_viterbi(acf, counts, per_unit, **smooth)
             tracks[name], tracks[name + '_raw'], tracks[name + '_counts'] = smoothed[:2], (period, strength), smoothed[2]
         tracks[name + '_stats'] = lib.f0_stats(tracks[name][0], None, counts, per_unit)
-        if name == 'pitched':
-            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['model'][0], counts, per_unit)
+        if name == 'pitched':   # against the track directly in front of the pitch stage
+            tracks['pitch_stats'] = lib.f0_stats(tracks['pitched'][0], tracks['formant' if 'formant' in tracks else 'model'][0], counts,
+                                                 per_unit)
         for k in ('', '_stats', '_raw', '_counts'):
             if name + k in tracks:
                 tracks['vocoder' + k] = tracks[name + k]
+        if name == 'formant':   # (behind the loop: 'vocoder_stats' keeps the track's own summary) the paired one takes the name
+            tracks['formant_stats'] = lib.f0_stats(tracks['formant'][0], tracks['model'][0], counts, per_unit)
 
     return track, tracks
 
@@ -186,7 +201,7 @@ def _f0_tracker(f0, out, r, lengths):
 def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
            lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
            rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None, sharpen=None,
-           sharpen_lifter=lib.SHARPEN_LIFTER):
+           sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=32):
     """invert_spectrogram with its result by name: the same parameters, documented there -> Vocoded"""
     if phase_init not in (None, 'random', 'estimate'):
         raise ValueError("invert_spectrogram: phase_init must be None, 'random' or 'estimate', got %r" % (phase_init,))
@@ -212,6 +227,10 @@ def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=No
         mag_t = lib.frames_sharpen(mag_t, sharpen, sharpen_lifter, counts, per_unit)
     if track:
         track('model', mag_t)
+    if formant is not None and not (isinstance(formant, (int, float)) and not isinstance(formant, bool) and float(formant) == 0.0):
+        mag_t = lib.frames_formant(mag_t, counts, lib.steps_of(formant, lib.formant_step), frames_per_unit=per_unit, lifter=formant_lifter)
+        if track:
+            track('formant', mag_t)
     if pitch_curve is not None:
         mag_t = lib.frames_pitch_curve(mag_t, counts, pitch_curve, frames_per_unit=per_unit, lifter=lifter)
     elif pitch is not None:

@@ -161,6 +161,7 @@ EXPORTS = {
     'taco_frames_stretch_curve': (C.c_int, [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     'taco_frames_pitch_curve': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     'taco_frames_sharpen': (C.c_int, [_P, _P, _I, C.c_float, _I, _P, _I, _I, _I, _P]),
+    'taco_frames_formant': (C.c_int, [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     'taco_frames_cepstats_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
     'taco_frames_cepstats': (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'taco_frames_f0': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
@@ -1385,6 +1386,38 @@ def frames_sharpen(mag_t, beta, lifter=SHARPEN_LIFTER, frames=None, frames_per_u
     on_gpu(who, 'mag_t', dev)
     _check(_lib.taco_frames_sharpen(ptr(mag_t), ptr(frames), frames_per_unit, beta, lifter, ptr(out), B, Cw, F, stream_ptr()),
            'taco_frames_sharpen')
+    return out
+
+
+def formant_step(semitones) -> int:
+    """A formant shift in semitones (0: the model's own, +12 moves the envelope an octave up) -> step_q of taco_frames_formant =
+    round(65536 * 2^(-semitones / 12)): the arithmetic of pitch_step; ValueError outside [-12, 12] or for a non-finite value"""
+    try:
+        semitones = float(semitones)
+    except (TypeError, ValueError):
+        raise ValueError('formant must be a number of semitones in [-12, 12], got %r' % (semitones,)) from None
+    if not -12.0 <= semitones <= 12.0:   # (NaN fails both comparisons)
+        raise ValueError('formant must be in [-12, 12] semitones, got %r' % (semitones,))
+    return int(round(65536.0 * 2.0 ** (-semitones / 12.0)))
+
+
+def frames_formant(mag_t, frames=None, step_q=None, frames_per_unit=1, lifter=32, out=None):
+    """Timbre on the magnitude frames (include/taco_hip.h taco_frames_formant), the dual of frames_pitch: mag_t (B, C, F) fp32 on the
+    device, C - 1 a power of two in [8, 1024] -> out (B, C, F) fp32: in the first F_b = clamp(frames[b] * frames_per_unit, 0, F)
+    frames of row b the frame's own log-envelope (the cepstrum's quefrencies 0 .. lifter) is read at step_q[b] / 65536 source bins
+    per output bin under the unmoved log-excitation, at unchanged frame energy; zeros behind.
+    frames: (B) int32 on the device, or None (all F frames).  step_q: None (65536: a copy), an int (the whole batch), a host sequence
+    of B ints (checked against [32768, 131072], then uploaded) or a (B) int32 tensor on the device (clamped there, never read here);
+    formant_step(semitones) makes one.  lifter: 1 .. min(64, (C - 1) / 2); the default 32 is untuned.  out: the caller's own buffer;
+    default: a fresh one.  Enqueued on the current stream; nothing is read back and nothing waits."""
+    who = 'frames_formant'
+    B, Cw, F, dev, frames_per_unit, lifter = _cepstrum_args(who, mag_t, lifter, frames, frames_per_unit, first=1)
+    step_q, _ = step_q_arg(who, step_q, B, dev, PITCH_MIN_STEP, PITCH_MAX_STEP, '+12 to -12 semitones')
+    out = _own_or_given(out, (B, Cw, F), torch.float32, dev, who + ': out')
+    no_overlap(who, 'mag_t', mag_t, 'out', out)
+    on_gpu(who, 'mag_t', dev)
+    _check(_lib.taco_frames_formant(ptr(mag_t), ptr(frames), frames_per_unit, ptr(step_q), lifter, ptr(out), B, Cw, F, stream_ptr()),
+           'taco_frames_formant')
     return out
 
 

@@ -106,6 +106,16 @@ a run without the flag: the same files, byte for byte.  BETA and Q are UNTUNED a
 above; with --long every piece is sharpened.  The two settings are not fields of the options record of test(): they travel as
 Config.sharpen / Config.sharpen_lifter, next to the paths the command line also leaves there, and a run reads them from its resolved
 options like every other.
+--formant SEMITONES [--formant-lifter Q] (opt-in, not in the reference): timbre, -12 <= SEMITONES <= 12, the dual of --pitch.  Behind
+--sharpen and in front of --pitch, --prosody's curves and --rate every magnitude frame goes through lib.frames_formant
+(taco_frames_formant): the frame's envelope of Q quefrencies (default 32) is read at k / ratio, ratio = 2^(SEMITONES / 12) -- + moves
+the formants up, a shorter vocal tract -- under the unmoved harmonics, and the frame keeps its energy.  prompt_NNN_formant.npy holds
+(step_q, lifter) as int32; every other file keeps its name and size, and the spectrogram, alignment, length and score files stay the
+model's own.  --formant 0 is a run without the flag: the same files, byte for byte.  With --f0 one line per prompt says "formant asked
++2.00 semitones, F0 moved +N cents over M voiced frames": the drift of the pitch, which should be none.  It combines with every option
+above; with --long every piece is shifted, and with --prosody it is a per-row constant in front of the curves.  Q is UNTUNED and nobody
+has listened to the result.  Like the sharpening pair the two settings travel as Config.formant / Config.formant_lifter and a run
+reads them from its resolved options.
 --ema (opt-in, with --checkpoint; not in the reference): the weights are the checkpoint's exponential moving average of the parameters
 (`train --ema DECAY`) instead of the ones the last minibatch left.  A checkpoint without an average -- written without `train --ema`,
 or imported from TF -- is refused before anything is synthesised.  Everything downstream is unchanged, and it combines with every
@@ -295,6 +305,13 @@ def f0_lines(who, f0row, asked_step=None, rate_step=None, prosody=False):
     return out
 
 
+def formant_line(who, step_q, paired):
+    """the line --f0 prints for `who` behind --formant from the row of 'formant_stats' (the formant track against the model's over
+    the frames voiced in both): what was asked of the envelope, and how far the pitch moved with it -- which should be nowhere"""
+    return ('%s formant asked %+.2f semitones, F0 moved %+.0f cents over %d voiced frames'
+            % (who, 12.0 * np.log2(65536.0 / step_q), 1200.0 * float(paired[1]), int(paired[0])))
+
+
 def loud_row(loud, blocks):
     """a row of lib.wave_loudness's loud (4) and blocks (4) -> the 8 float64 values of prompt_NNN_loud.npy"""
     return np.concatenate([np.asarray(loud, dtype=np.float64), np.asarray(blocks, dtype=np.float64)])
@@ -348,6 +365,9 @@ def level_finished(fin, level, **rows):
     tp_out = lib.wave_limit(out, n_b, taps=taps)[2][:, 0]
     return pcm, np.stack([limit_row(*r) for r in zip(peaks.cpu().numpy(), counts.cpu().numpy(), loud[:, 0].cpu().numpy(),
                                                      tp_out.cpu().numpy(), I_in.cpu().numpy())])
+
+
+FORMANT_LIFTER = 32   # --formant-lifter's default, lib.frames_formant's: UNTUNED, nobody has listened
 
 
 def given(option):
@@ -437,13 +457,15 @@ class Options(_OptionFields):
         if long_options(o.long) is not None and not o.vocode:
             raise ValueError('long (--long) joins waveforms: it needs vocode')
 
-    def resolved(self, sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER):
+    def resolved(self, sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=FORMANT_LIFTER):
         """check(), then the options as a run reads them, a Resolved: `gl_init` None for 'random', `f0` None or (lo, hi), `f0_smooth`
         None or the number of candidates, `long` None or (pause_ms, fade_ms), `prosody` None when not given -- given, it holds
         `path_jump` to its range as `timings` does.  sharpen / sharpen_lifter (--sharpen, --sharpen-lifter; Config.sharpen /
-        Config.sharpen_lifter): checked by sharpen_options, the Resolved holds what it returns; ValueError"""
+        Config.sharpen_lifter): checked by sharpen_options, the Resolved holds what it returns; formant / formant_lifter (--formant,
+        --formant-lifter; Config.formant / Config.formant_lifter) likewise by formant_options; ValueError"""
         self.check()
         sharpen = sharpen_options(sharpen, sharpen_lifter, self.vocode)
+        formant = formant_options(formant, formant_lifter, self.vocode)
         level = None if self.loudness is None else dict(target=float(self.loudness),
                                                         ceiling_db=PEAK_DB if self.peak_db is None else float(self.peak_db))
         if self.limit:
@@ -455,17 +477,19 @@ class Options(_OptionFields):
         return Resolved(**dict(vars(self), gl_init=None if self.gl_init == 'random' else self.gl_init, f0=f0, f0_smooth=smooth, long=long,
                                prosody=self.prosody if given(self.prosody) else None), level=level,
                         finish=self.deemphasis is not None or self.trim_db is not None or long is not None or level is not None,
-                        sharpen=sharpen)
+                        sharpen=sharpen, formant=formant)
 
 
 @dataclasses.dataclass(frozen=True)
 class Resolved(Options):
     """Options.resolved(): the options in the form a run reads, and what follows from them.  level: None, or level_waveform's target,
     ceiling_db and, with `limit`, limiter keywords; finish: whether the waveform is finished on the device; sharpen: None, or
-    (beta, lifter) of the post-filter in front of every other stage"""
+    (beta, lifter) of the post-filter in front of every other stage; formant: None, or (step_q, lifter) of the formant shift
+    behind it"""
     level: Any = None
     finish: bool = False
     sharpen: Any = None
+    formant: Any = None
 
 
 def sharpen_options(sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, vocode=True):
@@ -486,6 +510,21 @@ def sharpen_options(sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, vocode=True
     return None if beta == 0.0 else (beta, lifter)
 
 
+def formant_options(formant=None, formant_lifter=FORMANT_LIFTER, vocode=True):
+    """--formant SEMITONES / --formant-lifter Q -> None for no shift (SEMITONES None or 0: every file is what it was), else
+    (step_q, lifter): lib.formant_step of the semitones, the lifter checked against lib.frames_formant's range at the 1025 bins of
+    the model; ValueError"""
+    if formant is None:
+        return None
+    if isinstance(formant, bool):
+        raise ValueError('formant (--formant) must be a number of semitones in [-12, 12], got %r' % (formant,))
+    step = lib.formant_step(formant)
+    lifter = lib.int_arg('check_options', 'formant_lifter (--formant-lifter)', formant_lifter, 1, lib.PITCH_MAX_LIFTER)
+    if not vocode:
+        raise ValueError('formant (--formant) shifts the envelope of the magnitudes in front of Griffin-Lim: it needs vocode')
+    return None if float(formant) == 0.0 else (step, lifter)
+
+
 def check_options(*, n_iter=50, vocode=True, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None,
                   align_scores=False, rate=None, pitch=None, lifter=32, f0=None, timings=False, f0_smooth=None, prosody=None, gl_init=None,
                   loudness=None, peak_db=None, limit=False, limit_ms=None, true_peak=None, limit_passes=None, path_jump=None):
@@ -502,7 +541,7 @@ def limit_options(limit_ms=None, true_peak=None, limit_passes=None):
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None, sharpen=None):
+                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None, sharpen=None, formant=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -518,7 +557,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     then the waveform behind the stretch curve and keeps 300 (Fo_b - 1) samples, whatever len_b says.
     loud (--loudness): the prompt's loud_row, written as _loud.npy (float64); pcm then holds the levelled samples.  With --limit: the
     prompt's limit_row, whose first 8 values are written as _limit.npy instead.
-    sharpen (--sharpen): (beta, lifter) of the post-filter, written as _sharpen.npy (float64); nothing else depends on it."""
+    sharpen (--sharpen): (beta, lifter) of the post-filter, written as _sharpen.npy (float64); nothing else depends on it.
+    formant (--formant): (step_q, lifter) of the formant shift, written as _formant.npy (int32); nothing else depends on it."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -534,6 +574,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_pitch.npy', np.asarray(pitch, dtype=np.int32))
     if sharpen is not None:
         np.save(path + '_sharpen.npy', np.asarray(sharpen, dtype=np.float64))
+    if formant is not None:
+        np.save(path + '_formant.npy', np.asarray(formant, dtype=np.int32))
     if prosody is not None:
         if wav is not None:
             wav = wav[:300 * max(0, int(prosody[1]) - 1)]
@@ -644,12 +686,18 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     a beta in [-1, 1]: the magnitudes of every row go through the cepstral post-filter first (vocode(sharpen=...), lib.frames_sharpen),
     in front of `pitch`, `rate`, `prosody` and `f0`, over the row's own len_b r frames wherever the vocoder gets the lengths, else over
     all frames; with `long`, every piece.  prompt_NNN_sharpen.npy holds (beta, lifter) as float64.  Untuned; nobody has listened.
+    `config.formant` / `config.formant_lifter` (need `vocode`; Config's defaults: None, 32): None or 0 -- every file is what it was --
+    or semitones in [-12, 12]: behind the post-filter and in front of `pitch`, `prosody`'s curves and `rate`, the envelope of every
+    frame is moved under its harmonics (vocode(formant=...), lib.frames_formant), over the frames `sharpen` runs over; with `long`,
+    every piece.  prompt_NNN_formant.npy holds (step_q, lifter) as int32, and with `f0` formant_line() is printed per prompt.
+    Untuned; nobody has listened.
     `config.use_ema` (--ema; needs `checkpoint`; Config's default: False): decode from the checkpoint's AVERAGED weights (train --ema,
     Tacotron.load_state_dict(use_ema=True)) instead of the live ones; lib.TacoError before the first batch when the checkpoint holds
     none.  Like the sharpening pair it travels on the Config, not in the options record: it chooses the weights, and everything
     downstream is unchanged."""
     opt = Options(**{k: v for k, v in locals().items() if k in Options.__dataclass_fields__}).resolved(   # (locals(): the parameters)
-        getattr(config, 'sharpen', None), getattr(config, 'sharpen_lifter', lib.SHARPEN_LIFTER))
+        getattr(config, 'sharpen', None), getattr(config, 'sharpen_lifter', lib.SHARPEN_LIFTER), getattr(config, 'formant', None),
+        getattr(config, 'formant_lifter', FORMANT_LIFTER))
     run = Run(config, opt, prompts, out_dir, checkpoint, speaker, bool(getattr(config, 'use_ema', False)))
     n = _test_long(run) if opt.long is not None else _test_rows(run, prompts)
     print('wrote %d samples to %s' % (n, out_dir))
@@ -661,7 +709,8 @@ class Batch(collections.namedtuple('Batch', 'spec al wav conv pcm trim lengths s
     not finished on the device, else pcm and trim: the device's int16 samples and [s, e].  lengths (`stop`): len_b.  louds (`loudness`
     without `long`): the loud_rows (B, 8), with `limit` the limit_rows; pcm then is the levelled one.  scores (`align_scores`): (B, 8).
     f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
-    lib.f0_viterbi counts (B, 4)).  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.  curved
+    lib.f0_viterbi counts (B, 4); with a formant shift a sixth place behind them -- the fifth None without `f0_smooth` -- holds
+    'formant_stats' (B, 3)).  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.  curved
     (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve."""
 
     def row(self, i):
@@ -795,6 +844,8 @@ class Run:
                 kw.update(self.curves(found[0], batch, n), dur_q_max=self.pros_max)
             if o.sharpen is not None:
                 kw.update(sharpen=o.sharpen[0], sharpen_lifter=o.sharpen[1])
+            if o.formant is not None:   # (step_q as the device takes it, one value for every row)
+                kw.update(formant=torch.full((batch['text'].shape[0],), o.formant[0], dtype=torch.int32).cuda(), formant_lifter=o.formant[1])
             v = vocode(out, mean, std, c.r, n_iter=o.n_iter, seed=n, momentum=o.gl_momentum, want_conv=o.gl_momentum is not None,
                        phase_init=o.gl_init, lifter=o.lifter, **kw)
             if v.tracks is not None:
@@ -802,6 +853,8 @@ class Run:
                          v.tracks['vocoder_stats'].cpu().numpy(), v.tracks['pitch_stats'].cpu().numpy() if 'pitch_stats' in v.tracks else None)
                 if o.f0_smooth is not None:
                     f0res += (v.tracks['vocoder_counts'].cpu().numpy(),)
+                if 'formant_stats' in v.tracks:   # (the sixth place, whether or not the fifth is taken)
+                    f0res = f0res[:5] + (None,) * (5 - len(f0res)) + (v.tracks['formant_stats'].cpu().numpy(),)
             if v.src is not None:
                 curved = (v.frames_out.cpu().numpy(), v.src.cpu().numpy())
             wav = v.waveform
@@ -856,9 +909,11 @@ class Run:
         if rec.f0res is None:
             return None
         frames = self.frames_of(row, rec)
-        for line in f0_lines(self.who[row], list(rec.f0res[1:]), None if self.row_pitch is None else self.row_pitch[row],
+        for line in f0_lines(self.who[row], list(rec.f0res[1:5]), None if self.row_pitch is None else self.row_pitch[row],
                              None if self.row_steps is None else self.row_steps[row], rec.curved is not None):
             print(line)
+        if len(rec.f0res) > 5:
+            print(formant_line(self.who[row], self.opt.formant[0], rec.f0res[5]))
         return rec.f0res[0][:frames]
 
     def timing_of(self, row, rec, text_len, offset=0):
@@ -890,7 +945,7 @@ def _test_rows(run, prompts):
             write_prompt(run.out_dir, n, run.config.r, rec.spec, rec.al, rec.wav, None if rec.lengths is None else int(rec.lengths), rec.pcm,
                          rec.trim, rec.conv, ascore=rec.scores, rate=run.rate_of(n, rec), pitch=run.pitch_of(n), f0=run.f0_of(n, rec),
                          dur=dur, prosody=None if rec.curved is None else (run.pros[n], int(rec.curved[0])), loud=rec.louds,
-                         sharpen=run.opt.sharpen)
+                         sharpen=run.opt.sharpen, formant=run.opt.formant)
             if rec.louds is not None:
                 print(level_line('prompt %d' % n, rec.louds, run.opt.level))
             if words is not None:
@@ -947,7 +1002,7 @@ def _test_long(run):
                     words += piece_words
                 write_prompt(run.out_dir, p, run.config.r, rec.spec, rec.al, None, int(rec.lengths), None, rec.trim, rec.conv,
                              piece=None if b - a == 1 else k - a, ascore=rec.scores, rate=run.rate_of(row + k, rec), pitch=run.pitch_of(row + k),
-                             f0=f0rows, dur=dur, sharpen=o.sharpen)
+                             f0=f0rows, dur=dur, sharpen=o.sharpen, formant=o.formant)
                 names = run.marks(rec.scores, text_len) if rec.scores is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
@@ -1077,6 +1132,13 @@ def parse_args(argv=None):
                          'listened; not in the reference)')
     ap.add_argument('--sharpen-lifter', type=int, default=None, metavar='Q',
                     help='--sharpen: the highest quefrency scaled, 2 <= Q <= 64 (default %d, untuned)' % lib.SHARPEN_LIFTER)
+    ap.add_argument('--formant', type=float, default=None, metavar='SEMITONES',
+                    help='timbre, -12 <= SEMITONES <= 12: behind --sharpen and in front of --pitch and --rate the envelope of every magnitude '
+                         'frame is moved along the bin axis on the device (+: formants up) under the unmoved harmonics at unchanged frame '
+                         'energy; 0 is a run without the flag; writes prompt_NNN_formant.npy, and with --f0 prints how far the pitch moved '
+                         '(untuned; nobody has listened; not in the reference)')
+    ap.add_argument('--formant-lifter', type=int, default=None, metavar='Q',
+                    help='--formant: the quefrencies 0 .. Q make the envelope, 1 <= Q <= 64 (default %d, untuned)' % FORMANT_LIFTER)
     ap.add_argument('--ema', action='store_true',
                     help='decode from the averaged weights of a checkpoint written by `train --ema DECAY` instead of the live ones; an '
                          'error when the checkpoint holds none (not in the reference; nobody has listened to the difference)')
@@ -1099,8 +1161,11 @@ def parse_args(argv=None):
     if a.ema and a.checkpoint is None:
         ap.error('--ema needs --checkpoint: the averaged weights come from a checkpoint of `train --ema`')
     a.sharpen_lifter = lib.SHARPEN_LIFTER if a.sharpen_lifter is None else a.sharpen_lifter
+    if a.formant_lifter is not None and a.formant is None:
+        ap.error('--formant-lifter needs --formant')
+    a.formant_lifter = FORMANT_LIFTER if a.formant_lifter is None else a.formant_lifter
     try:
-        Options(**option_keywords(a)).resolved(a.sharpen, a.sharpen_lifter)
+        Options(**option_keywords(a)).resolved(a.sharpen, a.sharpen_lifter, a.formant, a.formant_lifter)
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -1116,6 +1181,7 @@ if __name__ == '__main__':
     c.data_path = 'data/%s/' % a.train_set
     c.save_path = a.train_set + '/tacotron'
     c.sharpen, c.sharpen_lifter = a.sharpen, a.sharpen_lifter
+    c.formant, c.formant_lifter = a.formant, a.formant_lifter
     c.use_ema = a.ema
     print('Building Tacotron')
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, **option_keywords(a))
