@@ -822,6 +822,50 @@ int taco_frames_f0(const float* mag_t, const int32_t* frames, int frames_per_uni
 int taco_f0_stats(const float* period, const float* other, const int32_t* frames, int frames_per_unit, float* stats, int B, int F,
                   void* stream);
 
+/* The intonation range of an utterance (no reference counterpart): a tracked pitch contour -> the per-frame step curve
+ * taco_frames_pitch_curve consumes, which multiplies every frame's distance from the row's own pitch level, in octaves, by k --
+ * the cure for the flattened intonation of an L1-trained model that taco_f0_stats' deviation measures.
+ *   period  (B, F) fp32 as taco_frames_f0 / taco_f0_viterbi write it; a frame is voiced when f < F_b and period[b, f] > 0
+ *   frames, frames_per_unit: as taco_frames_f0 (F_b = clamp(frames[b] * frames_per_unit, 0, F) in 64 bits, NULL: F); never read by the host
+ *   scale_q (B) int32 on the device or NULL (65536): k_b = clamp(scale_q[b], 0, 4 * 65536) * 2^-16; 0 flattens the contour to the
+ *           row's level, 65536 is neutral, 98304 widens every excursion by 1.5
+ *   base_q  (B, F) int32 on the device or NULL (TACO_PITCH_ONE): a step curve to compose with (a broadcast pitch, a prosody curve),
+ *           used as clamp(base, TACO_PITCH_MIN_STEP, TACO_PITCH_MAX_STEP)
+ *   smooth  = W, 0 <= W <= TACO_F0_RANGE_MAX_SMOOTH;  limit in octaves, 0 < limit <= 1: the ceiling on the excursion change of one
+ *           frame, so that an octave error of the tracker cannot be amplified without bound
+ *   step_q  (B, F) int32: the output;  stats (B, 3) fp32 or NULL: exactly what taco_f0_stats(period, NULL, ...) writes for the row
+ * Per row, with x_f = log2f(period[b, f]) on voiced frames, fp32, every step one rounded operation, nothing contracted:
+ *   1. count, c (the mean) and the deviation are THE BITS of taco_f0_stats: one device function, both kernels.  count == 0: every
+ *      frame f < F_b gets clamp(base), or TACO_PITCH_ONE without a base
+ *   2. d_f = x_f - c on voiced frames
+ *   3. an unvoiced frame f with p the nearest voiced frame before it and n the nearest one after it: t = float(f - p) / float(n - p),
+ *      d_f = d_p + t * (d_n - d_p); with only one of them: that neighbour's value.  The search runs in integers.
+ *   4. s_f = (sum_{j = -W .. W} (W + 1 - |j|) * d[clamp(f + j, 0, F_b - 1)]) / (W + 1)^2, summed in the order j = -W .. W from +0
+ *   5. e_f = clamp((k_b - 1) * s_f, -limit, limit)
+ *   6. with a base: e_f += log2f(float(clamp(base)) * 2^-16)
+ *   7. step_q[b, f] = clamp((int)rintf(65536 * exp2f(e_f)), TACO_PITCH_MIN_STEP, TACO_PITCH_MAX_STEP)
+ *   8. step_q[b, f] = TACO_PITCH_ONE for F_b <= f < F
+ * The sign follows from the units: a longer period is a lower pitch and step = 65536 / ratio, so step = 65536 * 2^((k - 1)(x - c))
+ * multiplies the frame's distance from the level by k.  tests/f0_range_ref.py restates this in float64 and float32; the device is
+ * held to the former within a bar sized from the latter.  Further:
+ *   - a row with scale_q == 65536 gives clamp(base), or TACO_PITCH_ONE, bit for bit on every frame f < F_b: no log, no exp;
+ *   - every element of step_q, and of stats when given, is written and nothing outside them, for any 4-byte alignment;
+ *   - columns f >= F_b and other rows have no influence (they may hold NaN): row b of a B-row call equals the call on it alone;
+ *   - no atomics: the same arguments give the same bits.
+ * One launch of B workgroups, no workspace, no allocation, no host synchronisation: graph-capturable, and a replay follows
+ * whatever frames, scale_q, base_q and period hold at replay time.  NULL period / step_q, step_q overlapping period or base_q, B or
+ * F <= 0, F > TACO_STRETCH_MAX_FRAMES, frames_per_unit < 1, smooth outside 0 .. 8 and a limit that is NaN or outside (0, 1] return
+ * TACO_EINVAL, with a message that names the argument, before anything is enqueued.  TACO_VERSION did not change with this entry
+ * point: detect it by the symbol.
+ * The Python layer's smooth = 2 and limit = 0.5 are UNTUNED: nobody has listened.  Measured on one MI355X at 32 rows of 360 | 720 |
+ * 8192 frames (profiles/f0_range_timing.json): 6.0 | 7.3 | 44.2 us with W = 2 and a base = 1.62 | 1.77 | 2.84 x taco_f0_stats on
+ * the same period in the same run, 0.02 | 0.013 % of the Griffin-Lim call behind the chain; the factor at 8192 frames is an open
+ * item.  Not here: a per-word range, a target range in semitones
+ * instead of a factor, an energy contour, mel frames. */
+#define TACO_F0_RANGE_MAX_SMOOTH 8
+int taco_f0_range_curve(const float* period, const int32_t* frames, int frames_per_unit, const int32_t* scale_q, const int32_t* base_q,
+                        int smooth, float limit, int32_t* step_q, float* stats, int B, int F, void* stream);
+
 /* A pitch track smoothed across frames (no reference counterpart): up to K candidates per frame out of the acf taco_frames_f0 writes,
  * and per frame one of them, or "unvoiced", chosen by the best path under a cost for pitch jumps and one for voiced / unvoiced
  * switches (Boersma 1993) -- the cure for the octave flips and single-frame voicing drops of a pick that decides every frame alone.

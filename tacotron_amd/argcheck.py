@@ -119,19 +119,20 @@ def on_gpu(who, name, dev):
         raise ValueError('%s: %s must be on the GPU, got %s (there is no CPU fallback)' % (who, name, dev))
 
 
-def step_q_arg(who, step_q, B, dev, lo, hi, what):
-    """The step_q of frames_stretch / frames_pitch -> (step_q for the library, the smallest step the host knows of):
+def step_q_arg(who, step_q, B, dev, lo, hi, what, name='step_q'):
+    """The step_q of frames_stretch / frames_pitch (`name`: what the wrapper calls it) -> (step_q for the library, the smallest step
+    the host knows of):
     None -> (None, None); a (B) int32 tensor on `dev` (a device), shape-checked and never read -> (it, lo); an int (the whole batch)
     or a host sequence of B ints, each checked against [lo, hi] (`what` says what that range means) and uploaded -> (tensor, min)"""
     if step_q is None:
         return None, None
     if torch.is_tensor(step_q) and step_q.device.type != 'cpu':
-        tensor_arg(who, 'step_q on a device', step_q, torch.int32, (B,), dev)
+        tensor_arg(who, name + ' on a device', step_q, torch.int32, (B,), dev)
         return step_q, lo
     one = not torch.is_tensor(step_q) and not hasattr(step_q, '__len__')
-    host = host_int32([step_q] * B if one else step_q, B, who + ': step_q')
+    host = host_int32([step_q] * B if one else step_q, B, '%s: %s' % (who, name))
     if min(host) < lo or max(host) > hi:
-        raise ValueError('%s: step_q must be in [%d, %d] (%s), got %r' % (who, lo, hi, what, step_q if one else host))
+        raise ValueError('%s: %s must be in [%d, %d] (%s), got %r' % (who, name, lo, hi, what, step_q if one else host))
     return torch.tensor(host, dtype=torch.int32).to(dev), min(host)
 
 

@@ -57,6 +57,11 @@ class Config(object):
     # synthesis only (test.py --formant SEMITONES / --formant-lifter Q): the formant shift behind the post-filter; None: off
     formant = None
     formant_lifter = 32
+    # synthesis only (test.py --pitch-range K / --pitch-range-smooth W / --pitch-range-limit OCT): the intonation range where the pitch
+    # stage sits; None: off.  The two settings are UNTUNED (lib.F0_RANGE_SMOOTH, lib.F0_RANGE_LIMIT)
+    pitch_range = None
+    pitch_range_smooth = 2
+    pitch_range_limit = 0.5
 
     # training only (train.py --ema DECAY; not in the reference): an exponential moving average of the parameters, kept on the device
     # beside the Adam slots and saved with them; 0: off -- no buffer, no launch, no checkpoint key.  No tuned default

@@ -852,7 +852,8 @@ __global__ __launch_bounds__(64 * kF0Waves) void frames_f0_kernel(const float* _
 
 // taco_f0_stats: count, mean and population standard deviation of x_f = log2(period) -- or log2(other) - log2(period), the octaves
 // by which period's pitch lies above other's -- over the voiced frames of a row.  One workgroup per row, two passes (the sum, then
-// the squares around the mean), a thread's frames in ascending order and the threads' partials down a fixed tree.
+// the squares around the mean), a thread's frames in ascending order and the threads' partials down a fixed tree: f0_row_stats of
+// frames.h, which taco_f0_range_curve (f0_curve.hip) centres its rows with.
 __global__ __launch_bounds__(256) void f0_stats_kernel(const float* __restrict__ period, const float* __restrict__ other,
                                                        const int32_t* __restrict__ frames, int frames_per_unit,
                                                        float* __restrict__ stats, int F) {
@@ -860,48 +861,11 @@ __global__ __launch_bounds__(256) void f0_stats_kernel(const float* __restrict__
   __shared__ int cnt[256];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int Fb = row_frames(frames, frames_per_unit, b, F);
-  const float* __restrict__ p = period + (int64_t)b * F;
-  const float* __restrict__ o = other ? other + (int64_t)b * F : nullptr;
-  float s = 0.f;
-  int c = 0;
-  for (int f = tid; f < Fb; f += 256) {
-    const float pv = p[f], ov = o ? o[f] : 1.0f;
-    if (pv > 0.f && ov > 0.f) {
-      s += o ? log2f(ov) - log2f(pv) : log2f(pv);
-      ++c;
-    }
-  }
-  red[tid] = s;
-  cnt[tid] = c;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) {
-      red[tid] += red[tid + w];
-      cnt[tid] += cnt[tid + w];
-    }
-    __syncthreads();
-  }
-  const int n = cnt[0];
-  const float mean = n > 0 ? red[0] / (float)n : 0.f;
-  __syncthreads();
-  s = 0.f;
-  for (int f = tid; f < Fb; f += 256) {
-    const float pv = p[f], ov = o ? o[f] : 1.0f;
-    if (pv > 0.f && ov > 0.f) {
-      const float x = (o ? log2f(ov) - log2f(pv) : log2f(pv)) - mean;
-      s += x * x;
-    }
-  }
-  red[tid] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
+  const F0RowStats r = f0_row_stats(period + (int64_t)b * F, other ? other + (int64_t)b * F : nullptr, Fb, tid, red, cnt);
   if (tid == 0) {
-    stats[3 * b] = (float)n;
-    stats[3 * b + 1] = mean;
-    stats[3 * b + 2] = n > 0 ? sqrtf(red[0] / (float)n) : 0.f;
+    stats[3 * b] = (float)r.n;
+    stats[3 * b + 1] = r.mean;
+    stats[3 * b + 2] = r.n > 0 ? sqrtf(r.ss / (float)r.n) : 0.f;
   }
 }
 

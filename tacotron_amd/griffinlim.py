@@ -33,6 +33,10 @@ its envelope are scaled up at unchanged energy, against the over-smoothed envelo
 With `formant` (opt-in) the envelope of every magnitude frame is moved along the bin axis under the frame's own unmoved harmonics
 (taco_frames_formant), the dual of `pitch`: the voice gets smaller or larger, the pitch and the duration stay.
 
+With `intonation` (opt-in) the pitch contour of the frames in front of the pitch stage is tracked and every frame's distance from the
+utterance's own level is scaled (taco_f0_range_curve, then taco_frames_pitch_curve): a wider, narrower or flat intonation around the
+same level, against the regression to the mean an L1 loss leaves in the F0 contour.
+
 With `phase_init='estimate'` (opt-in) Griffin-Lim starts from phases read off the magnitudes (taco_phase_estimate: single-pass
 spectrogram inversion) instead of random ones; with n_iter = 0 that estimate alone is the waveform -- a draft voice at one synthesis pass.
 
@@ -59,7 +63,8 @@ SR = 16000   # test.py:11
 def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
                        lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
                        rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None, sharpen=None,
-                       sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=32):
+                       sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=32, intonation=None,
+                       intonation_smooth=lib.F0_RANGE_SMOOTH, intonation_limit=lib.F0_RANGE_LIMIT, intonation_stats=None):
     """mag_t / wave / work: the caller's own buffers for the magnitudes, the waveform and Griffin-Lim's workspace (default: fresh).
     lengths: (B) int32 decoder steps on the device (e.g. model.lengths); work then holds lib.griffinlim_rows_workspace_floats.
     momentum: None for the plain algorithm on the two paths above, or a number in [0, 1) for the fast Griffin-Lim of Perraudin,
@@ -130,6 +135,20 @@ def invert_spectrogram(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=No
     'formant_stats' is the paired lib.f0_stats (B, 3) of 'formant' against 'model': 1200 x its mean is the drift of the pitch in
     cents, which should be none.  'pitch_stats' then compares 'pitched' with 'formant', the track directly in front of the pitch
     stage.  Nobody has listened.  Return shapes do not change.
+    intonation (opt-in): None or a plain 1.0 -- nothing is touched, bit for bit -- or the factor k in [0, 4] by which every frame's
+    distance from the row's own pitch level is multiplied (0 flat, 0.5 half the range, 1.5 half as wide again), a host sequence of B
+    such numbers, or a (B) int32 device tensor of scale_q values (lib.range_scale; clamped on the device, never read here), against
+    the flattened intonation of an L1-trained model that 'model_stats' measures.  The stage sits where the pitch stage sits: the
+    frames directly in front of it ('formant' if that stage ran, else 'model') are tracked -- with `f0` that track and its settings
+    are reused, the Viterbi-smoothed one under 'smooth'; without `f0` they are tracked once with lib.f0_tables() defaults, and the
+    return shape does not change -- lib.f0_range_curve (taco_f0_range_curve) turns the track into a per-frame step curve, composed
+    with `pitch_curve`, or with `pitch` broadcast to (B, F) on the device, and the curve goes through lib.frames_pitch_curve in place
+    of the pitch stage.  intonation_smooth (frames, 0 .. 8) and intonation_limit (octaves, (0, 1]) default to 2 and 0.5: UNTUNED,
+    nobody has listened.  With `f0` the frames behind the stage are tracked as 'pitched', as behind `pitch`, and
+    tracks['range_stats'] is (B, 4) fp32: the count of 'pitched', the deviation of log2(period) of the track in front, that of
+    'pitched', and their ratio (0 where the former is 0) -- the closed-loop reading "asked x1.5, measured x1.47".
+    intonation_stats (needs the stage to run): the caller's own (B, 3) fp32 buffer for what lib.f0_range_curve says of the track in
+    front -- lib.f0_stats' count, centre and deviation over the frames the stage ran on -- also without `f0`.
     Everything stays on the device.  F0 in Hz is SR / period."""
     res = tuple(x for x in vocode(**locals()) if x is not None)   # (the first statement: locals() are the parameters)
     return res[0] if len(res) == 1 else res
@@ -198,10 +217,26 @@ def _f0_tracker(f0, out, r, lengths):
     return track, tracks
 
 
+def _intonation_scale(intonation, B, dev):
+    """`intonation` of vocode() -> None for a run without the stage (None, a plain 1.0), else the scale_q lib.f0_range_curve takes:
+    a (B) int32 device tensor passed through, never read, or the lib.range_scale of a number or of B host numbers; ValueError"""
+    if intonation is None:
+        return None
+    if torch.is_tensor(intonation) and intonation.device.type != 'cpu':
+        return intonation
+    if isinstance(intonation, bool):
+        raise ValueError('invert_spectrogram: intonation must be a factor in [0, 4], got %r' % (intonation,))
+    if isinstance(intonation, (int, float)) and float(intonation) == 1.0:
+        return None
+    scale = lib.steps_of(intonation, lib.range_scale, B)
+    return torch.tensor(scale if isinstance(scale, list) else [scale] * B, dtype=torch.int32).to(dev)
+
+
 def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=None, wave=None, work=None,
            lengths=None, momentum=None, want_conv=False, rate=None, frames_out=None, pitch=None, lifter=32, f0=None,
            rate_curve=None, pitch_curve=None, dur_q_max=lib.STRETCH_MAX_STEP, src=None, phase_init=None, sharpen=None,
-           sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=32):
+           sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=32, intonation=None,
+           intonation_smooth=lib.F0_RANGE_SMOOTH, intonation_limit=lib.F0_RANGE_LIMIT, intonation_stats=None):
     """invert_spectrogram with its result by name: the same parameters, documented there -> Vocoded"""
     if phase_init not in (None, 'random', 'estimate'):
         raise ValueError("invert_spectrogram: phase_init must be None, 'random' or 'estimate', got %r" % (phase_init,))
@@ -231,12 +266,36 @@ def vocode(out, stft_mean, stft_std, r, n_iter=50, seed=0, phase0=None, mag_t=No
         mag_t = lib.frames_formant(mag_t, counts, lib.steps_of(formant, lib.formant_step), frames_per_unit=per_unit, lifter=formant_lifter)
         if track:
             track('formant', mag_t)
-    if pitch_curve is not None:
+    ranged = _intonation_scale(intonation, mag_t.shape[0], out.device)
+    if intonation_stats is not None and ranged is None:
+        raise ValueError('invert_spectrogram: intonation_stats needs intonation')
+    if ranged is not None:   # in place of the pitch stage: the contour in front of it, scaled, composed with pitch / pitch_curve
+        front = 'formant' if track and 'formant' in tracks else 'model'
+        if track:
+            period = tracks[front][0]
+        else:
+            w, g, lag_min, lag_max = lib.f0_tables(C=mag_t.shape[1])
+            period = lib.frames_f0(mag_t, counts, per_unit, w, g, lag_min, lag_max)[0]
+        base_q = pitch_curve
+        if base_q is None and pitch is not None:
+            step_q = lib.steps_of(pitch, lib.pitch_step, mag_t.shape[0])
+            if not torch.is_tensor(step_q):
+                step_q = torch.tensor(step_q if isinstance(step_q, list) else [step_q] * mag_t.shape[0], dtype=torch.int32).to(out.device)
+            base_q = step_q.view(-1, 1).expand(-1, mag_t.shape[2]).contiguous()
+        curve = lib.f0_range_curve(period, counts, per_unit, ranged, base_q, intonation_smooth, intonation_limit,
+                                   out=None if intonation_stats is None else (None, intonation_stats), want_stats=intonation_stats is not None)
+        curve = curve[0] if intonation_stats is not None else curve
+        mag_t = lib.frames_pitch_curve(mag_t, counts, curve, frames_per_unit=per_unit, lifter=lifter)
+    elif pitch_curve is not None:
         mag_t = lib.frames_pitch_curve(mag_t, counts, pitch_curve, frames_per_unit=per_unit, lifter=lifter)
     elif pitch is not None:
         mag_t = lib.frames_pitch(mag_t, counts, lib.steps_of(pitch, lib.pitch_step), frames_per_unit=per_unit, lifter=lifter)
-    if track and (pitch is not None or pitch_curve is not None):
+    if track and (pitch is not None or pitch_curve is not None or ranged is not None):
         track('pitched', mag_t)
+        if ranged is not None:   # (count of 'pitched', sd in front, sd behind, their ratio) from the two *_stats, on the device
+            sd_in, behind = tracks[front + '_stats'][:, 2], tracks['pitched_stats']
+            ratio = torch.where(sd_in > 0, behind[:, 2] / sd_in, torch.zeros_like(sd_in))
+            tracks['range_stats'] = torch.stack([behind[:, 0], sd_in, behind[:, 2], ratio], dim=1)
     if rate is not None or rate_curve is not None:
         F = mag_t.shape[2]
         if rate_curve is not None:

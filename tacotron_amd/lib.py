@@ -166,6 +166,7 @@ EXPORTS = {
     'taco_frames_cepstats': (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'taco_frames_f0': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, C.c_float, C.c_float, _P, _P, _P, _I, _I, _I, _P]),
     'taco_f0_stats': (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _P]),
+    'taco_f0_range_curve': (C.c_int, [_P, _P, _I, _P, _P, _I, C.c_float, _P, _P, _I, _I, _P]),
     'taco_f0_viterbi_workspace_bytes': (C.c_int64, [_I, _I, _I, _I]),
     'taco_f0_viterbi': (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P, _P, _I, _I, _P]),
     'taco_corpus_batch': (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.c_int64, _I, C.c_int64, _I, _P]),
@@ -1573,6 +1574,62 @@ def f0_stats(period, other=None, frames=None, frames_per_unit=1, out=None):
     on_gpu(who, 'period', dev)
     _check(_lib.taco_f0_stats(ptr(period), ptr(other), ptr(frames), frames_per_unit, ptr(out), B, F, stream_ptr()), 'taco_f0_stats')
     return out
+
+
+F0_RANGE_MAX_SCALE, F0_RANGE_MAX_SMOOTH = 4.0, 8   # include/taco_hip.h: scale_q up to 4 x 65536, TACO_F0_RANGE_MAX_SMOOTH
+F0_RANGE_SMOOTH, F0_RANGE_LIMIT = 2, 0.5           # f0_range_curve's smooth and limit (octaves): UNTUNED, nobody has listened
+
+
+def range_scale(k) -> int:
+    """An intonation range factor (1: the contour as tracked, 0 flat, 1.5 every excursion half as wide again) -> scale_q of
+    taco_f0_range_curve = round(65536 * k), the companion of pitch_step; ValueError outside [0, 4] or for a non-finite value"""
+    try:
+        if isinstance(k, bool):
+            raise TypeError
+        k = float(k)
+    except (TypeError, ValueError):
+        raise ValueError('the intonation range must be a factor in [0, 4], got %r' % (k,)) from None
+    if not 0.0 <= k <= F0_RANGE_MAX_SCALE:   # (NaN fails both comparisons)
+        raise ValueError('the intonation range must be in [0, 4], got %r' % (k,))
+    return int(round(65536.0 * k))
+
+
+def f0_range_curve(period, frames=None, frames_per_unit=1, scale_q=None, base_q=None, smooth=F0_RANGE_SMOOTH, limit=F0_RANGE_LIMIT,
+                   out=None, want_stats=False):
+    """The intonation range as a pitch curve (include/taco_hip.h taco_f0_range_curve): period (B, F) fp32 on the device, as frames_f0
+    or f0_viterbi return it -> step_q (B, F) int32 for frames_pitch_curve, and with want_stats (step_q, stats (B, 3)), stats being
+    f0_stats(period, None, frames, frames_per_unit) bit for bit: every frame's distance from the row's own level (the mean of
+    log2(period) over its voiced frames) is multiplied by k = scale_q / 65536; unvoiced frames lie on the line between their voiced
+    neighbours, the deviations are smoothed by a triangle of half-width `smooth` frames, and one frame's excursion changes by at
+    most `limit` octaves.
+    frames: (B) int32 on the device, or None (all F frames).  scale_q: None (65536: neutral, base_q or 65536 copied), an int
+    (range_scale(k), the whole batch), a host sequence of B ints (checked against [0, 262144], then uploaded) or a (B) int32
+    tensor on the device (clamped there, never read here).  base_q: None or (B, F) int32 on the device, a step curve to compose
+    with (clamped there to [32768, 131072]).  smooth in 0 .. 8 and limit in (0, 1]: the defaults 2 and 0.5 are UNTUNED.  out: the
+    caller's own step_q, or (step_q, stats) with want_stats; default: fresh ones.  Enqueued on the current stream; nothing is read
+    back and nothing waits."""
+    who = 'f0_range_curve'
+    B, F = tensor_arg(who, 'period', period, torch.float32, ('B', 'F'))
+    dev = period.device
+    _frames_cap(who, F)
+    frames_per_unit = _row_frames_arg(who, frames, frames_per_unit, B, dev)
+    scale_q, _ = step_q_arg(who, scale_q, B, dev, 0, int(F0_RANGE_MAX_SCALE * 65536), 'range factors 0 to 4', name='scale_q')
+    tensor_arg(who, 'base_q', base_q, torch.int32, (B, F), dev, optional=True)
+    smooth = int_arg(who, 'smooth', smooth, 0, F0_RANGE_MAX_SMOOTH)
+    limit = float_arg(who, 'limit', limit, 0.0, 1.0)
+    if limit == 0.0:
+        raise ValueError('%s: limit must be a number of octaves in (0, 1], got %r' % (who, limit))
+    if want_stats and out is not None and (torch.is_tensor(out) or len(out) != 2):
+        raise ValueError('%s: out must be (step_q, stats)' % who)
+    step_q = _own_or_given(out[0] if want_stats and out is not None else out, (B, F), torch.int32, dev, who + ': step_q')
+    stats = _own_or_given(None if out is None else out[1], (B, 3), torch.float32, dev, who + ': stats') if want_stats else None
+    no_overlap(who, 'period', period, 'step_q', step_q)
+    if base_q is not None:
+        no_overlap(who, 'base_q', base_q, 'step_q', step_q)
+    on_gpu(who, 'period', dev)
+    _check(_lib.taco_f0_range_curve(ptr(period), ptr(frames), frames_per_unit, ptr(scale_q), ptr(base_q), smooth, limit, ptr(step_q),
+                                    ptr(stats), B, F, stream_ptr()), 'taco_f0_range_curve')
+    return (step_q, stats) if want_stats else step_q
 
 
 F0_MAX_CAND = 15           # TACO_F0_MAX_CAND

@@ -106,6 +106,17 @@ a run without the flag: the same files, byte for byte.  BETA and Q are UNTUNED a
 above; with --long every piece is sharpened.  The two settings are not fields of the options record of test(): they travel as
 Config.sharpen / Config.sharpen_lifter, next to the paths the command line also leaves there, and a run reads them from its resolved
 options like every other.
+--pitch-range K [--pitch-range-smooth W] [--pitch-range-limit OCT] (opt-in, not in the reference): the intonation range, 0 <= K <= 4.
+Where --pitch sits, the pitch of the frames in front of it is tracked on the device (lib.frames_f0; with --f0 that track, range and
+smoothing are reused), lib.f0_range_curve (taco_f0_range_curve) turns the track into a per-frame pitch curve that multiplies every
+frame's distance from the utterance's own level, in octaves, by K -- 0 a flat contour, 0.5 half the range, 1.5 half as wide again, the
+cure for the flattened intonation of an L1-trained model that --f0 measures -- composed with --pitch or --prosody's pitch curve, and
+the magnitudes go through lib.frames_pitch_curve.  W (default 2 frames) smooths the contour, OCT (default 0.5 octaves) caps the change
+of one frame.  prompt_NNN_range.npy holds (scale_q, W, OCT, voiced frames, their mean log2 period, its deviation in front) as float64.
+--pitch-range 1 is a run without the flag: the same files, byte for byte.  With --f0 one line per prompt says "range asked x1.50,
+measured x1.46 (2.1 -> 3.1 semitones) over 212 voiced frames".  It combines with every option above; with --long every piece gets its
+own centre.  K, W and OCT are UNTUNED, nobody has listened to the result, and on an untrained model the frames have no pitch: the
+numbers then mean nothing.  The three settings travel as Config.pitch_range / pitch_range_smooth / pitch_range_limit.
 --formant SEMITONES [--formant-lifter Q] (opt-in, not in the reference): timbre, -12 <= SEMITONES <= 12, the dual of --pitch.  Behind
 --sharpen and in front of --pitch, --prosody's curves and --rate every magnitude frame goes through lib.frames_formant
 (taco_frames_formant): the frame's envelope of Q quefrencies (default 32) is read at k / ratio, ratio = 2^(SEMITONES / 12) -- + moves
@@ -312,6 +323,14 @@ def formant_line(who, step_q, paired):
             % (who, 12.0 * np.log2(65536.0 / step_q), 1200.0 * float(paired[1]), int(paired[0])))
 
 
+def range_line(who, row):
+    """the line --f0 prints for `who` behind --pitch-range from (scale_q, the row of 'range_stats': the voiced frames behind the stage,
+    the deviation of log2(period) in front of it and behind it, their ratio)"""
+    scale_q, (count, sd_in, sd_out, ratio) = row
+    return ('%s range asked x%.2f, measured x%.2f (%.1f -> %.1f semitones) over %d voiced frames'
+            % (who, scale_q / 65536.0, float(ratio), 12.0 * float(sd_in), 12.0 * float(sd_out), int(count)))
+
+
 def loud_row(loud, blocks):
     """a row of lib.wave_loudness's loud (4) and blocks (4) -> the 8 float64 values of prompt_NNN_loud.npy"""
     return np.concatenate([np.asarray(loud, dtype=np.float64), np.asarray(blocks, dtype=np.float64)])
@@ -457,15 +476,18 @@ class Options(_OptionFields):
         if long_options(o.long) is not None and not o.vocode:
             raise ValueError('long (--long) joins waveforms: it needs vocode')
 
-    def resolved(self, sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=FORMANT_LIFTER):
+    def resolved(self, sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, formant=None, formant_lifter=FORMANT_LIFTER, pitch_range=None,
+                 pitch_range_smooth=lib.F0_RANGE_SMOOTH, pitch_range_limit=lib.F0_RANGE_LIMIT):
         """check(), then the options as a run reads them, a Resolved: `gl_init` None for 'random', `f0` None or (lo, hi), `f0_smooth`
         None or the number of candidates, `long` None or (pause_ms, fade_ms), `prosody` None when not given -- given, it holds
         `path_jump` to its range as `timings` does.  sharpen / sharpen_lifter (--sharpen, --sharpen-lifter; Config.sharpen /
         Config.sharpen_lifter): checked by sharpen_options, the Resolved holds what it returns; formant / formant_lifter (--formant,
-        --formant-lifter; Config.formant / Config.formant_lifter) likewise by formant_options; ValueError"""
+        --formant-lifter; Config.formant / Config.formant_lifter) likewise by formant_options; pitch_range / pitch_range_smooth / pitch_range_limit (--pitch-range and
+        its two settings; Config's fields of those names) by pitch_range_options; ValueError"""
         self.check()
         sharpen = sharpen_options(sharpen, sharpen_lifter, self.vocode)
         formant = formant_options(formant, formant_lifter, self.vocode)
+        pitch_range = pitch_range_options(pitch_range, pitch_range_smooth, pitch_range_limit, self.vocode)
         level = None if self.loudness is None else dict(target=float(self.loudness),
                                                         ceiling_db=PEAK_DB if self.peak_db is None else float(self.peak_db))
         if self.limit:
@@ -477,7 +499,7 @@ class Options(_OptionFields):
         return Resolved(**dict(vars(self), gl_init=None if self.gl_init == 'random' else self.gl_init, f0=f0, f0_smooth=smooth, long=long,
                                prosody=self.prosody if given(self.prosody) else None), level=level,
                         finish=self.deemphasis is not None or self.trim_db is not None or long is not None or level is not None,
-                        sharpen=sharpen, formant=formant)
+                        sharpen=sharpen, formant=formant, pitch_range=pitch_range)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -485,11 +507,12 @@ class Resolved(Options):
     """Options.resolved(): the options in the form a run reads, and what follows from them.  level: None, or level_waveform's target,
     ceiling_db and, with `limit`, limiter keywords; finish: whether the waveform is finished on the device; sharpen: None, or
     (beta, lifter) of the post-filter in front of every other stage; formant: None, or (step_q, lifter) of the formant shift
-    behind it"""
+    behind it; pitch_range: None, or (scale_q, smooth, limit) of the intonation range where the pitch stage sits"""
     level: Any = None
     finish: bool = False
     sharpen: Any = None
     formant: Any = None
+    pitch_range: Any = None
 
 
 def sharpen_options(sharpen=None, sharpen_lifter=lib.SHARPEN_LIFTER, vocode=True):
@@ -525,6 +548,25 @@ def formant_options(formant=None, formant_lifter=FORMANT_LIFTER, vocode=True):
     return None if float(formant) == 0.0 else (step, lifter)
 
 
+def pitch_range_options(pitch_range=None, smooth=lib.F0_RANGE_SMOOTH, limit=lib.F0_RANGE_LIMIT, vocode=True):
+    """--pitch-range K / --pitch-range-smooth W / --pitch-range-limit OCT -> None for the model's own intonation (K None or 1: every
+    file is what it was), else (scale_q, W, OCT): lib.range_scale of the factor, the two UNTUNED settings checked against
+    lib.f0_range_curve's ranges; ValueError"""
+    if pitch_range is None:
+        return None
+    try:
+        scale_q = lib.range_scale(pitch_range)
+    except ValueError:
+        raise ValueError('pitch_range (--pitch-range) must be a factor in [0, 4], got %r' % (pitch_range,)) from None
+    smooth = lib.int_arg('check_options', 'pitch_range_smooth (--pitch-range-smooth)', smooth, 0, lib.F0_RANGE_MAX_SMOOTH)
+    limit = lib.float_arg('check_options', 'pitch_range_limit (--pitch-range-limit)', limit, 0.0, 1.0)
+    if limit == 0.0:
+        raise ValueError('check_options: pitch_range_limit (--pitch-range-limit) must be a number of octaves in (0, 1], got %r' % (limit,))
+    if not vocode:
+        raise ValueError('pitch_range (--pitch-range) scales the pitch contour of the magnitudes in front of Griffin-Lim: it needs vocode')
+    return None if float(pitch_range) == 1.0 else (scale_q, smooth, limit)
+
+
 def check_options(*, n_iter=50, vocode=True, stop=None, vocode_lengths=False, gl_momentum=None, deemphasis=None, trim_db=None, long=None,
                   align_scores=False, rate=None, pitch=None, lifter=32, f0=None, timings=False, f0_smooth=None, prosody=None, gl_init=None,
                   loudness=None, peak_db=None, limit=False, limit_ms=None, true_peak=None, limit_passes=None, path_jump=None):
@@ -541,7 +583,7 @@ def limit_options(limit_ms=None, true_peak=None, limit_passes=None):
 
 
 def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, trim=None, conv=None, piece=None, ascore=None, zoom=4,
-                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None, sharpen=None, formant=None):
+                 rate=None, pitch=None, f0=None, dur=None, prosody=None, loud=None, sharpen=None, formant=None, pitch_range=None):
     """The files of prompt n from its rows of the batch's arrays.  len_b (with a stop rule): the prompt keeps frames = min(len_b r, F)
     spectrogram frames, len_b alignment rows and the 300 (frames - 1) samples Griffin-Lim gives for that many frames (hop 300).
     piece (--long): the arrays of piece `piece` of a prompt of several, as prompt_NNN_kMM_*.npy; its samples are in the prompt's wav.
@@ -558,7 +600,9 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
     loud (--loudness): the prompt's loud_row, written as _loud.npy (float64); pcm then holds the levelled samples.  With --limit: the
     prompt's limit_row, whose first 8 values are written as _limit.npy instead.
     sharpen (--sharpen): (beta, lifter) of the post-filter, written as _sharpen.npy (float64); nothing else depends on it.
-    formant (--formant): (step_q, lifter) of the formant shift, written as _formant.npy (int32); nothing else depends on it."""
+    formant (--formant): (step_q, lifter) of the formant shift, written as _formant.npy (int32); nothing else depends on it.
+    pitch_range (--pitch-range): (scale_q, smooth, limit, voiced frames, centre, deviation in front), written as _range.npy (float64);
+    nothing else depends on it."""
     path = os.path.join(out_dir, 'prompt_%03d' % n if piece is None else 'prompt_%03d_k%02d' % (n, piece))
     if len_b is not None:
         frames = min(len_b * r, spec.shape[0])
@@ -576,6 +620,8 @@ def write_prompt(out_dir, n, r, spec, align, wav=None, len_b=None, pcm=None, tri
         np.save(path + '_sharpen.npy', np.asarray(sharpen, dtype=np.float64))
     if formant is not None:
         np.save(path + '_formant.npy', np.asarray(formant, dtype=np.int32))
+    if pitch_range is not None:
+        np.save(path + '_range.npy', np.asarray(pitch_range, dtype=np.float64))
     if prosody is not None:
         if wav is not None:
             wav = wav[:300 * max(0, int(prosody[1]) - 1)]
@@ -697,21 +743,23 @@ def test(config, prompts, out_dir='log/test', checkpoint=None, speaker=0, n_iter
     downstream is unchanged."""
     opt = Options(**{k: v for k, v in locals().items() if k in Options.__dataclass_fields__}).resolved(   # (locals(): the parameters)
         getattr(config, 'sharpen', None), getattr(config, 'sharpen_lifter', lib.SHARPEN_LIFTER), getattr(config, 'formant', None),
-        getattr(config, 'formant_lifter', FORMANT_LIFTER))
+        getattr(config, 'formant_lifter', FORMANT_LIFTER), getattr(config, 'pitch_range', None),
+        getattr(config, 'pitch_range_smooth', lib.F0_RANGE_SMOOTH), getattr(config, 'pitch_range_limit', lib.F0_RANGE_LIMIT))
     run = Run(config, opt, prompts, out_dir, checkpoint, speaker, bool(getattr(config, 'use_ema', False)))
     n = _test_long(run) if opt.long is not None else _test_rows(run, prompts)
     print('wrote %d samples to %s' % (n, out_dir))
     return n
 
 
-class Batch(collections.namedtuple('Batch', 'spec al wav conv pcm trim lengths scores f0res paths curved louds')):
+class Batch(collections.namedtuple('Batch', 'spec al wav conv pcm trim lengths scores f0res paths curved louds ranged')):
     """What Run.synthesise returns for one batch: host arrays with one row per prompt, or None.  wav: the float waveform when it was
     not finished on the device, else pcm and trim: the device's int16 samples and [s, e].  lengths (`stop`): len_b.  louds (`loudness`
     without `long`): the loud_rows (B, 8), with `limit` the limit_rows; pcm then is the levelled one.  scores (`align_scores`): (B, 8).
     f0res (`f0`): (track (B, Fv, 2), model_stats, vocoder_stats, pitch_stats | None, and with `f0_smooth` the vocoder track's
     lib.f0_viterbi counts (B, 4); with a formant shift a sixth place behind them -- the fifth None without `f0_smooth` -- holds
     'formant_stats' (B, 3)).  paths (`timings`): (dur (B, Tt), counts (B, 3), mass (B)) of the best monotone paths.  curved
-    (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve."""
+    (`prosody`): (frames_out (B), src (B, Fo)) of the stretch curve.  ranged (a pitch range): (the lib.f0_range_curve stats (B, 3) of the
+    track in front of the stage, and with `f0` vocode's 'range_stats' (B, 4), else None)."""
 
     def row(self, i):
         """the same fields for row i of the batch alone: row i of every array, inside the tuples too"""
@@ -829,7 +877,7 @@ class Run:
         mean, std = (torch.as_tensor(s if s is not None else neutral(c.fft_size * c.r), dtype=torch.float32).cuda()
                      for s, neutral in ((model.stft_mean, torch.zeros), (model.stft_std, torch.ones)))
         spec = lib.denorm_unframe(out, mean, std, c.r)                       # (B, Td*r, 1025) chronological log-magnitudes
-        wav = conv = pcm = trim = f0res = curved = louds = None
+        wav = conv = pcm = trim = f0res = curved = louds = ranged = None
         if o.vocode:
             # the vocoder runs over the rows' own frames with `vocode_lengths`, and with a rate or curves whenever there is a rule: the
             # host's Fo_b and the device's frames_out are then one number
@@ -846,6 +894,10 @@ class Run:
                 kw.update(sharpen=o.sharpen[0], sharpen_lifter=o.sharpen[1])
             if o.formant is not None:   # (step_q as the device takes it, one value for every row)
                 kw.update(formant=torch.full((batch['text'].shape[0],), o.formant[0], dtype=torch.int32).cuda(), formant_lifter=o.formant[1])
+            if o.pitch_range is not None:   # (scale_q as the device takes it, one value for every row; every row, piece or prompt, its own centre)
+                Bn = batch['text'].shape[0]
+                kw.update(intonation=torch.full((Bn,), o.pitch_range[0], dtype=torch.int32).cuda(), intonation_smooth=o.pitch_range[1],
+                          intonation_limit=o.pitch_range[2], intonation_stats=torch.empty(Bn, 3, dtype=torch.float32, device='cuda'))
             v = vocode(out, mean, std, c.r, n_iter=o.n_iter, seed=n, momentum=o.gl_momentum, want_conv=o.gl_momentum is not None,
                        phase_init=o.gl_init, lifter=o.lifter, **kw)
             if v.tracks is not None:
@@ -855,6 +907,8 @@ class Run:
                     f0res += (v.tracks['vocoder_counts'].cpu().numpy(),)
                 if 'formant_stats' in v.tracks:   # (the sixth place, whether or not the fifth is taken)
                     f0res = f0res[:5] + (None,) * (5 - len(f0res)) + (v.tracks['formant_stats'].cpu().numpy(),)
+            if o.pitch_range is not None:
+                ranged = (kw['intonation_stats'].cpu().numpy(), v.tracks['range_stats'].cpu().numpy() if v.tracks is not None else None)
             if v.src is not None:
                 curved = (v.frames_out.cpu().numpy(), v.src.cpu().numpy())
             wav = v.waveform
@@ -882,7 +936,7 @@ class Run:
         if paths is not None:
             paths = tuple(x.cpu().numpy() for x in paths)
         return Batch(spec.cpu().numpy(), al.cpu().numpy(), wav, conv, pcm, trim, None if lengths is None else lengths.cpu().numpy(), scores,
-                     f0res, paths, curved, louds)
+                     f0res, paths, curved, louds, ranged)
 
     def marks(self, score, L):
         """the flags of one row's 8 scores, against the stop rule's own target when there is a rule"""
@@ -903,6 +957,14 @@ class Run:
     def pitch_of(self, row):
         """(step_q, lifter) of global row `row`, or None without a pitch"""
         return None if self.row_pitch is None else (self.row_pitch[row], int(self.opt.lifter))
+
+    def range_of(self, row, rec):
+        """the _range.npy values of global row `row`, or None without a pitch range; with `f0` prints the row's line"""
+        if rec.ranged is None:
+            return None
+        if rec.ranged[1] is not None:
+            print(range_line(self.who[row], (self.opt.pitch_range[0], rec.ranged[1])))
+        return tuple(self.opt.pitch_range) + tuple(float(x) for x in rec.ranged[0])
 
     def f0_of(self, row, rec):
         """the _f0.npy rows of global row `row`, cut to the frames the vocoder was given; prints the row's line"""
@@ -945,7 +1007,7 @@ def _test_rows(run, prompts):
             write_prompt(run.out_dir, n, run.config.r, rec.spec, rec.al, rec.wav, None if rec.lengths is None else int(rec.lengths), rec.pcm,
                          rec.trim, rec.conv, ascore=rec.scores, rate=run.rate_of(n, rec), pitch=run.pitch_of(n), f0=run.f0_of(n, rec),
                          dur=dur, prosody=None if rec.curved is None else (run.pros[n], int(rec.curved[0])), loud=rec.louds,
-                         sharpen=run.opt.sharpen, formant=run.opt.formant)
+                         sharpen=run.opt.sharpen, formant=run.opt.formant, pitch_range=run.range_of(n, rec))
             if rec.louds is not None:
                 print(level_line('prompt %d' % n, rec.louds, run.opt.level))
             if words is not None:
@@ -1002,7 +1064,7 @@ def _test_long(run):
                     words += piece_words
                 write_prompt(run.out_dir, p, run.config.r, rec.spec, rec.al, None, int(rec.lengths), None, rec.trim, rec.conv,
                              piece=None if b - a == 1 else k - a, ascore=rec.scores, rate=run.rate_of(row + k, rec), pitch=run.pitch_of(row + k),
-                             f0=f0rows, dur=dur, sharpen=o.sharpen, formant=o.formant)
+                             f0=f0rows, dur=dur, sharpen=o.sharpen, formant=o.formant, pitch_range=run.range_of(row + k, rec))
                 names = run.marks(rec.scores, text_len) if rec.scores is not None else []
                 if names:
                     found.append(', '.join(names) if b - a == 1 else 'piece %d %s' % (k - a, ', '.join(names)))
@@ -1139,6 +1201,18 @@ def parse_args(argv=None):
                          '(untuned; nobody has listened; not in the reference)')
     ap.add_argument('--formant-lifter', type=int, default=None, metavar='Q',
                     help='--formant: the quefrencies 0 .. Q make the envelope, 1 <= Q <= 64 (default %d, untuned)' % FORMANT_LIFTER)
+    ap.add_argument('--pitch-range', type=float, default=None, metavar='K',
+                    help='intonation range, 0 <= K <= 4: where --pitch sits the pitch contour of the frames is tracked on the device and '
+                         'every frame\'s distance from the utterance\'s own level is multiplied by K (0 flat, 1.5 half as wide again), composed '
+                         'with --pitch / --prosody; 1 is a run without the flag; writes prompt_NNN_range.npy, and with --f0 prints the range '
+                         'asked for and the range measured (K and its two settings are untuned; nobody has listened; on an untrained model '
+                         'the frames have no pitch and the numbers mean nothing; not in the reference)')
+    ap.add_argument('--pitch-range-smooth', type=int, default=None, metavar='W',
+                    help='--pitch-range: the contour is smoothed by a triangle of half-width W frames, 0 <= W <= 8 (default %d, untuned)'
+                         % lib.F0_RANGE_SMOOTH)
+    ap.add_argument('--pitch-range-limit', type=float, default=None, metavar='OCT',
+                    help='--pitch-range: the most one frame\'s excursion may change, 0 < OCT <= 1 octaves (default %g, untuned)'
+                         % lib.F0_RANGE_LIMIT)
     ap.add_argument('--ema', action='store_true',
                     help='decode from the averaged weights of a checkpoint written by `train --ema DECAY` instead of the live ones; an '
                          'error when the checkpoint holds none (not in the reference; nobody has listened to the difference)')
@@ -1164,8 +1238,13 @@ def parse_args(argv=None):
     if a.formant_lifter is not None and a.formant is None:
         ap.error('--formant-lifter needs --formant')
     a.formant_lifter = FORMANT_LIFTER if a.formant_lifter is None else a.formant_lifter
+    if (a.pitch_range_smooth is not None or a.pitch_range_limit is not None) and a.pitch_range is None:
+        ap.error('--pitch-range-smooth and --pitch-range-limit need --pitch-range')
+    a.pitch_range_smooth = lib.F0_RANGE_SMOOTH if a.pitch_range_smooth is None else a.pitch_range_smooth
+    a.pitch_range_limit = lib.F0_RANGE_LIMIT if a.pitch_range_limit is None else a.pitch_range_limit
     try:
-        Options(**option_keywords(a)).resolved(a.sharpen, a.sharpen_lifter, a.formant, a.formant_lifter)
+        Options(**option_keywords(a)).resolved(a.sharpen, a.sharpen_lifter, a.formant, a.formant_lifter, a.pitch_range,
+                                               a.pitch_range_smooth, a.pitch_range_limit)
         if a.prosody is not None:   # (the indices are held against the prompts in test(), once they are read)
             with open(a.prosody) as f:
                 a.prosody = parse_prosody(f.read())
@@ -1182,6 +1261,7 @@ if __name__ == '__main__':
     c.save_path = a.train_set + '/tacotron'
     c.sharpen, c.sharpen_lifter = a.sharpen, a.sharpen_lifter
     c.formant, c.formant_lifter = a.formant, a.formant_lifter
+    c.pitch_range, c.pitch_range_smooth, c.pitch_range_limit = a.pitch_range, a.pitch_range_smooth, a.pitch_range_limit
     c.use_ema = a.ema
     print('Building Tacotron')
     test(c, prompts, out_dir=a.out_dir, checkpoint=a.checkpoint, speaker=a.speaker, **option_keywords(a))
