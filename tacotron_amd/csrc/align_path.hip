@@ -61,6 +61,18 @@ PathPlan path_plan(int Td, int Tt) {
   }
   return p;
 }
+// workspace of taco_alignment_path: a direction byte per cell of each row's (Td, Tt) table (none in the single-wave form)
+struct PathWs {
+  uint8_t* way;
+  int64_t bytes;
+};
+PathWs path_ws(void* ws, int B, int Td, int Tt) {
+  WsCarver c(ws);
+  PathWs w;
+  w.way = c.take<uint8_t>(B * path_plan(Td, Tt).row_bytes);
+  w.bytes = c.bytes;
+  return w;
+}
 bool path_shape_ok(int B, int Td, int Tt) {
   return B > 0 && Td > 0 && Tt > 0 && Td <= TACO_ALIGN_PATH_MAX_TD && Tt <= TACO_ALIGN_PATH_MAX_TT;
 }
@@ -365,7 +377,7 @@ extern "C" int taco_path_curve(const int32_t* path, const int32_t* values, int f
 
 extern "C" int64_t taco_alignment_path_workspace_bytes(int B, int Td, int Tt) {
   if (!path_shape_ok(B, Td, Tt)) return TACO_EINVAL;
-  return (int64_t)B * path_plan(Td, Tt).row_bytes;
+  return path_ws(nullptr, B, Td, Tt).bytes;
 }
 
 extern "C" int taco_alignment_path(const float* alignments, const int32_t* text_length, const int32_t* steps, int max_jump,
@@ -387,7 +399,7 @@ extern "C" int taco_alignment_path(const float* alignments, const int32_t* text_
                TACO_ALIGN_PATH_MAX_JUMP);
   const PathPlan p = path_plan(Td, Tt);
   TACO_REQUIRE(p.row_bytes == 0 || workspace, "alignment_path: workspace is NULL (the direction table of this shape needs %lld bytes)",
-               (long long)((int64_t)B * p.row_bytes));
+               (long long)path_ws(nullptr, B, Td, Tt).bytes);
   hipStream_t s = as_stream(stream);
   if (p.wave) {
     const bool vec = Tt % 4 == 0 && (reinterpret_cast<uintptr_t>(alignments) & 15) == 0;
@@ -409,7 +421,7 @@ extern "C" int taco_alignment_path(const float* alignments, const int32_t* text_
       return TACO_ELAUNCH;
     }
     TACO_KLAUNCH(alignment_path_block_kernel, dim3(B), dim3(p.threads), p.lds_bytes, s, alignments, text_length, steps, max_jump, path,
-                 dur, counts, mass, static_cast<uint8_t*>(workspace), Td, Tt);
+                 dur, counts, mass, path_ws(workspace, B, Td, Tt).way, Td, Tt);
   }
   TACO_LAUNCH_CHECK("alignment_path");
   return TACO_OK;

@@ -168,6 +168,31 @@ struct DoorOperands {
 static inline size_t door_span(int64_t rows, int64_t cols, int64_t ld) { return (size_t)((rows - 1) * ld + cols) * sizeof(float); }
 constexpr int kDoorMaxRows = 1 << 22, kDoorMaxCols = 1 << 14;
 
+// ---- workspaces of the auxiliary entry points ---------------------------------------------------------------------------------
+// One walk over a workspace serves both its size function (built from nullptr: the walk only counts) and its entry point (built
+// from the caller's pointer: the walk hands out the arrays), so the two cannot disagree.  take<T>(count, align) returns the next
+// array, at an offset from the base that is a multiple of align, and advances.  base_align > 1 first rounds the caller's pointer
+// up to it; the bytes that costs are not counted, the layout's slack term pays for them.
+struct WsCarver {
+  char* base;          // nullptr: count only
+  int64_t bytes = 0;   // consumed so far
+  explicit WsCarver(void* ws, uintptr_t base_align = 1)
+      : base(reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + base_align - 1) / base_align * base_align)) {}
+  template <class T>
+  T* take(int64_t count, int64_t align = alignof(T)) {
+    bytes = (bytes + align - 1) / align * align;
+    T* p = base ? reinterpret_cast<T*>(base + bytes) : nullptr;
+    bytes += count * (int64_t)sizeof(T);
+    return p;
+  }
+};
+
+// whether the byte ranges [a, a + abytes) and [b, b + bbytes) meet: the overlap refusals of every entry point outside DoorOperands
+static inline bool bytes_meet(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

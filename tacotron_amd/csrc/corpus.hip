@@ -115,9 +115,8 @@ extern "C" int taco_corpus_batch(const void* src, int src_fp16, const int64_t* i
   TACO_REQUIRE((mean == nullptr) == (stdv == nullptr), "corpus_batch: mean and std must both be given or both be NULL");
   TACO_REQUIRE(index || B <= N, "corpus_batch: index is NULL (identity) but B=%d exceeds N=%lld", B, (long long)N);
   const int esz = src_fp16 ? 2 : 4;
-  const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), o0 = reinterpret_cast<uintptr_t>(out);
   TACO_REQUIRE(N <= INT64_MAX / row / esz && (int64_t)B <= INT64_MAX / row / 4, "corpus_batch: N, B, row: the tensors exceed the address space");
-  TACO_REQUIRE(o0 + (uintptr_t)B * row * 4 <= s0 || s0 + (uintptr_t)N * row * esz <= o0, "corpus_batch: out overlaps src");
+  TACO_REQUIRE(!bytes_meet(out, (uint64_t)B * row * 4, src, (uint64_t)N * row * esz), "corpus_batch: out overlaps src");
   const int V = corpus_batch_width(src, src_fp16, out, row);
   const int64_t per = (int64_t)kCorpusU * 256 * V;
   const int64_t chunks = (row + per - 1) / per;

@@ -47,9 +47,22 @@ DtwPlan dtw_plan(int Fa, int Fb, int K) {
   p.row_floats = p.coef_in_lds ? 0 : (int64_t)(Fa + Fb) * dtw_stride(K);
   return p;
 }
-// The path form's workspace: the B rows' coefficients as the cost-only form lays them out (none where they fit LDS), then B
-// direction tables, a byte per cell of (Fa + Fb - 1) diagonals x Fa.
+// The workspace: the B rows' coefficients (none where they fit LDS), and behind them in the path form B direction tables, a byte
+// per cell of (Fa + Fb - 1) diagonals x Fa.
 __host__ __device__ inline int64_t dtw_way_bytes(int Fa, int Fb) { return (int64_t)(Fa + Fb - 1) * Fa; }
+struct DtwWs {
+  float* coef;
+  uint8_t* way;   // (path form only)
+  int64_t bytes;
+};
+DtwWs dtw_ws(void* ws, int B, int Fa, int Fb, int K, bool path) {
+  WsCarver c(ws);
+  DtwWs w;
+  w.coef = c.take<float>(B * dtw_plan(Fa, Fb, K).row_floats);
+  w.way = path ? c.take<uint8_t>(B * dtw_way_bytes(Fa, Fb)) : nullptr;
+  w.bytes = c.bytes;
+  return w;
+}
 bool dtw_shape_ok(int B, int Fa, int Fb, int K) {
   return B > 0 && Fa > 0 && Fb > 0 && K > 0 && K <= TACO_DTW_MAX_K && Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES;
 }
@@ -241,8 +254,9 @@ int launch_frame_dtw_path(const float* a, const int32_t* na, const float* b, con
                           int32_t* steps, int32_t* path_a, int32_t* path_b, void* workspace, int B, int Fa, int Fb, int C, int K,
                           hipStream_t s) {
   const DtwPlan p = dtw_plan(Fa, Fb, K);
-  float* coef = static_cast<float*>(workspace);
-  const DtwPath<true> out = {path_a, path_b, reinterpret_cast<uint8_t*>(coef + (int64_t)B * p.row_floats)};
+  const DtwWs w = dtw_ws(workspace, B, Fa, Fb, K, true);
+  float* coef = w.coef;
+  const DtwPath<true> out = {path_a, path_b, w.way};
   static DynSmemOnce raised;
   const auto in_lds = frame_dtw_kernel<true, true>, in_ws = frame_dtw_kernel<false, true>;
   if (p.coef_in_lds) {
@@ -267,52 +281,52 @@ extern "C" int taco_frames_active(const float* x, float floor, int32_t* n, int B
   return launch_frames_active(x, floor, n, B, F, C, as_stream(stream));
 }
 
+// What taco_frame_dtw and taco_frame_dtw_path both require, in the order a caller sees the refusals.  `who`: the entry point's name
+// in the messages; missing: what that entry point alone needs and did not get (refused behind the shared operands), or nullptr.
+static int dtw_require(const char* who, const void* a, const void* b, const void* cost, const void* steps, const char* missing,
+                       const void* basis, int B, int Fa, int Fb, int C, int K) {
+  TACO_REQUIRE(a, "%s: a is NULL", who);
+  TACO_REQUIRE(b, "%s: b is NULL", who);
+  TACO_REQUIRE(cost, "%s: cost is NULL", who);
+  TACO_REQUIRE(steps, "%s: steps is NULL", who);
+  TACO_REQUIRE(!missing, "%s: %s", who, missing);
+  TACO_REQUIRE(B > 0, "%s: B=%d must be positive", who, B);
+  TACO_REQUIRE(Fa > 0 && Fb > 0, "%s: Fa=%d and Fb=%d must be positive", who, Fa, Fb);
+  TACO_REQUIRE(C > 0 && K > 0, "%s: C=%d and K=%d must be positive", who, C, K);
+  TACO_REQUIRE(basis || K == C, "%s: without a basis K=%d must equal C=%d", who, K, C);
+  TACO_REQUIRE(K <= TACO_DTW_MAX_K, "%s: K=%d is above the %d coefficients a frame may have", who, K, TACO_DTW_MAX_K);
+  TACO_REQUIRE(C <= TACO_DTW_MAX_C, "%s: C=%d is above the %d channels a frame may have", who, C, TACO_DTW_MAX_C);
+  TACO_REQUIRE(Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES, "%s: Fa=%d or Fb=%d is above the %d frames a row may have", who, Fa,
+               Fb, TACO_DTW_MAX_FRAMES);
+  return TACO_OK;
+}
+
 extern "C" int64_t taco_frame_dtw_workspace_bytes(int B, int Fa, int Fb, int K) {
   if (!dtw_shape_ok(B, Fa, Fb, K)) return TACO_EINVAL;
-  return (int64_t)B * dtw_plan(Fa, Fb, K).row_floats * (int64_t)sizeof(float);
+  return dtw_ws(nullptr, B, Fa, Fb, K, false).bytes;
 }
 
 extern "C" int taco_frame_dtw(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
                               int32_t* steps, void* workspace, int B, int Fa, int Fb, int C, int K, void* stream) {
-  TACO_REQUIRE(a, "frame_dtw: a is NULL");
-  TACO_REQUIRE(b, "frame_dtw: b is NULL");
-  TACO_REQUIRE(cost, "frame_dtw: cost is NULL");
-  TACO_REQUIRE(steps, "frame_dtw: steps is NULL");
-  TACO_REQUIRE(B > 0, "frame_dtw: B=%d must be positive", B);
-  TACO_REQUIRE(Fa > 0 && Fb > 0, "frame_dtw: Fa=%d and Fb=%d must be positive", Fa, Fb);
-  TACO_REQUIRE(C > 0 && K > 0, "frame_dtw: C=%d and K=%d must be positive", C, K);
-  TACO_REQUIRE(basis || K == C, "frame_dtw: without a basis K=%d must equal C=%d", K, C);
-  TACO_REQUIRE(K <= TACO_DTW_MAX_K, "frame_dtw: K=%d is above the %d coefficients a frame may have", K, TACO_DTW_MAX_K);
-  TACO_REQUIRE(C <= TACO_DTW_MAX_C, "frame_dtw: C=%d is above the %d channels a frame may have", C, TACO_DTW_MAX_C);
-  TACO_REQUIRE(Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES, "frame_dtw: Fa=%d or Fb=%d is above the %d frames a row may have", Fa,
-               Fb, TACO_DTW_MAX_FRAMES);
+  TACO_TRY(dtw_require("frame_dtw", a, b, cost, steps, nullptr, basis, B, Fa, Fb, C, K));
   TACO_REQUIRE(workspace || dtw_plan(Fa, Fb, K).row_floats == 0, "frame_dtw: workspace is NULL and Fa=%d, Fb=%d, K=%d need one", Fa, Fb, K);
-  return launch_frame_dtw(a, na, b, nb, basis, cost, steps, static_cast<float*>(workspace), B, Fa, Fb, C, K, as_stream(stream));
+  return launch_frame_dtw(a, na, b, nb, basis, cost, steps, dtw_ws(workspace, B, Fa, Fb, K, false).coef, B, Fa, Fb, C, K,
+                          as_stream(stream));
 }
 
 extern "C" int64_t taco_frame_dtw_path_workspace_bytes(int B, int Fa, int Fb, int K) {
   if (!dtw_shape_ok(B, Fa, Fb, K)) return TACO_EINVAL;
-  return (int64_t)B * (dtw_plan(Fa, Fb, K).row_floats * (int64_t)sizeof(float) + dtw_way_bytes(Fa, Fb));
+  return dtw_ws(nullptr, B, Fa, Fb, K, true).bytes;
 }
 
 extern "C" int taco_frame_dtw_path(const float* a, const int32_t* na, const float* b, const int32_t* nb, const float* basis, float* cost,
                                    int32_t* steps, int32_t* path_a, int32_t* path_b, void* workspace, int B, int Fa, int Fb, int C, int K,
                                    void* stream) {
-  TACO_REQUIRE(a, "frame_dtw_path: a is NULL");
-  TACO_REQUIRE(b, "frame_dtw_path: b is NULL");
-  TACO_REQUIRE(cost, "frame_dtw_path: cost is NULL");
-  TACO_REQUIRE(steps, "frame_dtw_path: steps is NULL");
-  TACO_REQUIRE(path_a, "frame_dtw_path: path_a is NULL");
-  TACO_REQUIRE(path_b, "frame_dtw_path: path_b is NULL");
-  TACO_REQUIRE(workspace, "frame_dtw_path: workspace is NULL (the direction table lives there)");
-  TACO_REQUIRE(B > 0, "frame_dtw_path: B=%d must be positive", B);
-  TACO_REQUIRE(Fa > 0 && Fb > 0, "frame_dtw_path: Fa=%d and Fb=%d must be positive", Fa, Fb);
-  TACO_REQUIRE(C > 0 && K > 0, "frame_dtw_path: C=%d and K=%d must be positive", C, K);
-  TACO_REQUIRE(basis || K == C, "frame_dtw_path: without a basis K=%d must equal C=%d", K, C);
-  TACO_REQUIRE(K <= TACO_DTW_MAX_K, "frame_dtw_path: K=%d is above the %d coefficients a frame may have", K, TACO_DTW_MAX_K);
-  TACO_REQUIRE(C <= TACO_DTW_MAX_C, "frame_dtw_path: C=%d is above the %d channels a frame may have", C, TACO_DTW_MAX_C);
-  TACO_REQUIRE(Fa <= TACO_DTW_MAX_FRAMES && Fb <= TACO_DTW_MAX_FRAMES, "frame_dtw_path: Fa=%d or Fb=%d is above the %d frames a row may have",
-               Fa, Fb, TACO_DTW_MAX_FRAMES);
+  const char* missing = !path_a      ? "path_a is NULL"
+                        : !path_b    ? "path_b is NULL"
+                        : !workspace ? "workspace is NULL (the direction table lives there)"
+                                     : nullptr;
+  TACO_TRY(dtw_require("frame_dtw_path", a, b, cost, steps, missing, basis, B, Fa, Fb, C, K));
   return launch_frame_dtw_path(a, na, b, nb, basis, cost, steps, path_a, path_b, workspace, B, Fa, Fb, C, K,
                                as_stream(stream));
 }

@@ -153,12 +153,25 @@ int em_grid(int64_t n, bool vec) {
   return g < 1 ? 1 : (int)g;
 }
 
+// workspace of taco_param_ema: one pair of fp64 partials per workgroup the call can launch, on any device.  No slack: a base that
+// is not 8-byte aligned is refused.
+struct EmWs {
+  double* part;
+  int64_t bytes;
+};
+EmWs em_ws(void* ws) {
+  WsCarver c(ws);
+  EmWs w;
+  w.part = c.take<double>((int64_t)EM_MAX_BLOCKS * 2);
+  w.bytes = c.bytes;
+  return w;
+}
+
 }  // namespace
 
-// one pair of fp64 partials per workgroup the call can launch, on any device
 extern "C" int64_t taco_param_ema_workspace_bytes(int64_t n) {
   if (n <= 0) return TACO_EINVAL;
-  return (int64_t)EM_MAX_BLOCKS * 2 * (int64_t)sizeof(double);
+  return em_ws(nullptr).bytes;
 }
 
 extern "C" int taco_param_ema(float* ema, const float* params, int64_t n, float w, const int32_t* err_words, double* stats,
@@ -166,18 +179,14 @@ extern "C" int taco_param_ema(float* ema, const float* params, int64_t n, float 
   TACO_REQUIRE(ema && params, "param_ema: ema or params is NULL");
   TACO_REQUIRE(n > 0, "param_ema: n=%lld must be positive", (long long)n);
   TACO_REQUIRE(w >= 0.f && w <= 1.f, "param_ema: w=%g is not in [0, 1]", (double)w);   // (NaN fails both)
-  {
-    const uintptr_t e0 = reinterpret_cast<uintptr_t>(ema), p0 = reinterpret_cast<uintptr_t>(params);
-    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
-    TACO_REQUIRE(!(e0 < p0 + bytes && p0 < e0 + bytes), "param_ema: ema may not overlap params");
-  }
+  TACO_REQUIRE(!bytes_meet(ema, (uint64_t)n * sizeof(float), params, (uint64_t)n * sizeof(float)), "param_ema: ema may not overlap params");
   TACO_REQUIRE(!stats || workspace, "param_ema: stats given without a workspace");
   TACO_REQUIRE(!stats || ((reinterpret_cast<uintptr_t>(stats) & 7) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0),
                "param_ema: stats or workspace is not 8-byte aligned");
   hipStream_t s = as_stream(stream);
   const bool vec = ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(params)) & 15) == 0;
   const int grid = em_grid(n, vec);
-  double* part = static_cast<double*>(workspace);
+  double* part = em_ws(workspace).part;   // (null without a workspace: only the stats forms read it)
   if (stats) {
     if (vec) TACO_KLAUNCH((ema_kernel<true, true>), dim3(grid), dim3(EM_T), 0, s, ema, params, n, w, err_words, part);
     else TACO_KLAUNCH((ema_kernel<false, true>), dim3(grid), dim3(EM_T), 0, s, ema, params, n, w, err_words, part);

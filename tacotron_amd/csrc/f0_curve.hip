@@ -128,11 +128,6 @@ __global__ __launch_bounds__(256) void f0_range_curve_kernel(const float* __rest
   }
 }
 
-bool bytes_meet(const void* a, uint64_t abytes, const void* b, uint64_t bbytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-
 }  // namespace
 
 extern "C" int taco_f0_range_curve(const float* period, const int32_t* frames, int frames_per_unit, const int32_t* scale_q,

@@ -296,16 +296,28 @@ __global__ __launch_bounds__(kF0vPathThreads) void f0_path_kernel(const float* _
 bool f0v_shape_ok(int B, int L, int F, int K) {
   return B > 0 && F > 0 && F <= TACO_STRETCH_MAX_FRAMES && L >= 3 && L <= TACO_F0_MAX_LAGS && K >= 1 && K <= TACO_F0_MAX_CAND;
 }
-bool f0v_overlaps(const void* out, uint64_t out_bytes, const void* in, uint64_t in_bytes) {
-  const uint64_t o = reinterpret_cast<uintptr_t>(out), i = reinterpret_cast<uintptr_t>(in);
-  return o < i + in_bytes && i < o + out_bytes;
+
+// workspace of taco_f0_viterbi: three planes of candidate records, the rows, the values and the log lags
+struct F0vWs {
+  int32_t* i;
+  float *v, *lg;
+  int64_t bytes;
+};
+F0vWs f0v_ws(void* ws, int B, int F) {
+  WsCarver c(ws);
+  F0vWs w;
+  w.i = c.take<int32_t>(f0v_plane(B, F));
+  w.v = c.take<float>(f0v_plane(B, F));
+  w.lg = c.take<float>(f0v_plane(B, F));
+  w.bytes = c.bytes;
+  return w;
 }
 
 }  // namespace
 
 extern "C" int64_t taco_f0_viterbi_workspace_bytes(int B, int L, int F, int K) {
   if (!f0v_shape_ok(B, L, F, K)) return TACO_EINVAL;
-  return 3 * f0v_plane(B, F) * 4;
+  return f0v_ws(nullptr, B, F).bytes;
 }
 
 extern "C" int taco_f0_viterbi(const float* acf, const int32_t* frames, int frames_per_unit, const float* bias, const float* lg, int lag_min,
@@ -334,10 +346,10 @@ extern "C" int taco_f0_viterbi(const float* acf, const int32_t* frames, int fram
                (double)switch_cost);
   TACO_REQUIRE(frames_per_unit >= 1, "f0_viterbi: frames_per_unit=%d must be >= 1", frames_per_unit);
   const uint64_t row = (uint64_t)B * F * 4, abytes = row * (uint64_t)L;
-  TACO_REQUIRE(!f0v_overlaps(period, row, acf, abytes), "f0_viterbi: period overlaps acf");
-  TACO_REQUIRE(!f0v_overlaps(strength, row, acf, abytes), "f0_viterbi: strength overlaps acf");
-  TACO_REQUIRE(!f0v_overlaps(counts, (uint64_t)B * 16, acf, abytes), "f0_viterbi: counts overlaps acf");
-  TACO_REQUIRE(!f0v_overlaps(score, (uint64_t)B * 4, acf, abytes), "f0_viterbi: score overlaps acf");
+  TACO_REQUIRE(!bytes_meet(period, row, acf, abytes), "f0_viterbi: period overlaps acf");
+  TACO_REQUIRE(!bytes_meet(strength, row, acf, abytes), "f0_viterbi: strength overlaps acf");
+  TACO_REQUIRE(!bytes_meet(counts, (uint64_t)B * 16, acf, abytes), "f0_viterbi: counts overlaps acf");
+  TACO_REQUIRE(!bytes_meet(score, (uint64_t)B * 4, acf, abytes), "f0_viterbi: score overlaps acf");
   const int ntile = cdiv(F, kF0vFrames);
   const int64_t blocks = (int64_t)B * ntile;
   TACO_REQUIRE(blocks <= 0x7fffffff, "f0_viterbi: B=%d x F=%d needs more than 2^31 workgroups", B, F);
@@ -349,9 +361,9 @@ extern "C" int taco_f0_viterbi(const float* acf, const int32_t* frames, int fram
     return TACO_ELAUNCH;
   }
   hipStream_t s = as_stream(stream);
-  int32_t* ws_i = static_cast<int32_t*>(workspace);
-  float* ws_v = reinterpret_cast<float*>(ws_i + f0v_plane(B, F));
-  float* ws_lg = ws_v + f0v_plane(B, F);
+  const F0vWs w = f0v_ws(workspace, B, F);
+  int32_t* ws_i = w.i;
+  float *ws_v = w.v, *ws_lg = w.lg;
   TACO_KLAUNCH(f0_candidates_kernel, dim3((unsigned)blocks), dim3(kF0vParts * kF0vFrames), cand_lds, s, acf, frames, frames_per_unit, bias, lg,
                K, ws_i, ws_v, ws_lg, L, F, ntile);
   TACO_KLAUNCH(f0_path_kernel, dim3((unsigned)B), dim3(kF0vPathThreads), path_lds, s, acf, frames, frames_per_unit, lag_min, K, threshold,

@@ -213,17 +213,22 @@ __global__ __launch_bounds__(FT) void fb_frames_kernel(FrameArgs a) {
   }
 }
 
+// workspace of taco_audio_features: the device copy of the lengths, the filterbank's bin ranges, the trim frames' mean squares,
+// each on a 256-byte boundary
 struct FeatWs {
-  int64_t len, rng, ms, ms_stride, bytes;
+  int *len, *rng;
+  float* ms;
+  int64_t ms_stride, bytes;
 };
-FeatWs feat_ws(int B, int L) {
+FeatWs feat_ws(void* ws, int B, int L) {
+  WsCarver c(ws);
   FeatWs w;
-  auto up = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-  w.len = 0;
-  w.rng = up((int64_t)B * 4);
-  w.ms = w.rng + up(2 * NMEL * 4);
   w.ms_stride = 1 + (int64_t)L / TRIM_HOP;
-  w.bytes = w.ms + up((int64_t)B * w.ms_stride * 4);
+  w.len = c.take<int>(B, 256);
+  w.rng = c.take<int>(2 * NMEL, 256);
+  w.ms = c.take<float>(B * w.ms_stride, 256);
+  c.take<char>(0, 256);   // the size is a whole number of 256-byte blocks
+  w.bytes = c.bytes;
   return w;
 }
 
@@ -232,7 +237,7 @@ FeatWs feat_ws(int B, int L) {
 // ---- C ABI (include/taco_hip.h)
 extern "C" int64_t taco_audio_features_workspace_bytes(int B, int L) {
   if (B <= 0 || L <= 0) return TACO_EINVAL;
-  return feat_ws(B, L).bytes;
+  return feat_ws(nullptr, B, L).bytes;
 }
 
 extern "C" int taco_audio_features(const float* wave, const int* wave_len_host, const float* mel_basis, void* mel, void* stft,
@@ -252,11 +257,9 @@ extern "C" int taco_audio_features(const float* wave, const int* wave_len_host, 
     TACO_REQUIRE(wave_len_host[b] >= 1 && wave_len_host[b] <= L, "audio_features: wave_len[%d]=%d outside 1..L=%d", b,
                  wave_len_host[b], L);
   hipStream_t s = as_stream(stream);
-  const FeatWs W = feat_ws(B, L);
-  char* ws = static_cast<char*>(workspace);
-  int* len_d = reinterpret_cast<int*>(ws + W.len);
-  int* rng = reinterpret_cast<int*>(ws + W.rng);
-  float* ms = reinterpret_cast<float*>(ws + W.ms);
+  const FeatWs W = feat_ws(workspace, B, L);
+  int *len_d = W.len, *rng = W.rng;
+  float* ms = W.ms;
   TACO_TRY(taco_upload_async(len_d, wave_len_host, (size_t)B * sizeof(int), s, "audio_features: length upload"));
   TACO_KLAUNCH(fb_ranges_kernel, dim3(1), dim3(256), 0, s, mel_basis, rng);
   TACO_KLAUNCH(fb_trim_kernel, dim3(B), dim3(TT), 0, s, wave, len_d, ms, W.ms_stride, bounds, kept, L, max_len);

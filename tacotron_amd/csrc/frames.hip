@@ -950,8 +950,7 @@ extern "C" int taco_denorm_unframe(const float* out, const float* mean, const fl
 namespace {
 // refuses an output `name` of obytes bytes that overlaps the mbytes bytes of mag_t
 int frames_no_overlap(const char* who, const char* name, const void* out, uint64_t obytes, const float* mag_t, uint64_t mbytes) {
-  const uintptr_t m0 = reinterpret_cast<uintptr_t>(mag_t), o0 = reinterpret_cast<uintptr_t>(out);
-  TACO_REQUIRE(o0 + obytes <= m0 || m0 + mbytes <= o0, "%s: %s overlaps mag_t", who, name);
+  TACO_REQUIRE(!bytes_meet(out, obytes, mag_t, mbytes), "%s: %s overlaps mag_t", who, name);
   return TACO_OK;
 }
 
@@ -1042,14 +1041,26 @@ extern "C" int taco_frames_sharpen(const float* mag_t, const int32_t* frames, in
   TACO_LAUNCH_CHECK(who);
   return TACO_OK;
 }
-// per tile of 32 frames (Q + 1) pairs of fp64, and 8 bytes of slack to align them in a workspace at any address
+// workspace of taco_frames_cepstats: per tile of 32 frames (Q + 1) pairs of fp64
+struct CepWs {
+  double* partial;
+  int64_t bytes;
+};
+static CepWs cep_ws(void* ws, int64_t blocks, int lifter) {
+  WsCarver c(ws, 8);   // a workspace at any address: the base is rounded up
+  CepWs w;
+  w.partial = c.take<double>(blocks * (lifter + 1) * 2);
+  c.take<char>(8);   // slack: the up to 7 bytes that rounding the base up costs
+  w.bytes = c.bytes;
+  return w;
+}
 extern "C" int64_t taco_frames_cepstats_workspace_bytes(int B, int C, int F, int lifter) {
   int ntile;
   int64_t blocks;
   const float dummy = 0.f;
   if (frames_cepstrum_args("frames_cepstats_workspace_bytes", &dummy, 1, TACO_SHARPEN_FIRST, lifter, B, C, F, &ntile, &blocks) != TACO_OK)
     return TACO_EINVAL;
-  return blocks * (lifter + 1) * 16 + 8;
+  return cep_ws(nullptr, blocks, lifter).bytes;
 }
 extern "C" int taco_frames_cepstats(const float* mag_t, const int32_t* frames, int frames_per_unit, int lifter, double* sums,
                                     int32_t* count, void* workspace, int B, int C, int F, void* stream) {
@@ -1060,7 +1071,7 @@ extern "C" int taco_frames_cepstats(const float* mag_t, const int32_t* frames, i
   TACO_REQUIRE(count, "%s: count is NULL", who);
   TACO_TRY(frames_cepstrum_args(who, mag_t, frames_per_unit, TACO_SHARPEN_FIRST, lifter, B, C, F, &ntile, &blocks));
   TACO_REQUIRE(workspace, "%s: workspace is NULL", who);
-  double* partial = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + 7) & ~(uintptr_t)7);
+  double* partial = cep_ws(workspace, blocks, lifter).partial;
   hipStream_t s = as_stream(stream);
   by_lifter(lifter, [&](auto nb, auto waves) {
     TACO_KLAUNCH((frames_cepstats_kernel<nb.value, waves.value>), dim3((unsigned)blocks), dim3(64 * waves.value), 0, s, mag_t, frames,

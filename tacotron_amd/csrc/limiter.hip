@@ -344,12 +344,27 @@ __global__ __launch_bounds__(64) void lm_rows_kernel(const float* __restrict__ p
 int lm_chunks(int L) { return cdiv(L, LM_CHUNK); }
 bool lm_w_ok(int W) { return W >= 0 && W <= LM_WMAX; }
 
+// workspace of taco_wave_limit: per chunk the four partials and (used only when out is the wave) its two halos of 2 W + 16 floats
+struct LmWs {
+  float *part, *halo;
+  int64_t bytes;
+};
+LmWs lm_ws(void* ws, int B, int L, int W) {
+  WsCarver c(ws);
+  LmWs w;
+  const int64_t chunks = (int64_t)B * lm_chunks(L);
+  w.part = c.take<float>(chunks * 4);
+  w.halo = c.take<float>(chunks * 2 * (2 * (int64_t)W + LM_HPITCH_PAD));
+  c.take<float>(64);   // slack, for nothing: no array is aligned beyond the base.  Callers size buffers with it.
+  w.bytes = c.bytes;
+  return w;
+}
+
 }  // namespace
 
-// workspace of taco_wave_limit: per chunk the four partials and (used only when out is the wave) its two halos of 2 W + 16 floats
 extern "C" int64_t taco_wave_limit_workspace_bytes(int B, int L, int W) {
   if (B <= 0 || L <= 0 || !lm_w_ok(W)) return TACO_EINVAL;
-  return ((int64_t)B * lm_chunks(L) * (4 + 2 * (2 * (int64_t)W + LM_HPITCH_PAD)) + 64) * (int64_t)sizeof(float);
+  return lm_ws(nullptr, B, L, W).bytes;
 }
 
 extern "C" int taco_wave_limit(const float* wave, const int32_t* samples, const float* gain, float ceiling, const float* taps, int P,
@@ -371,10 +386,11 @@ extern "C" int taco_wave_limit(const float* wave, const int32_t* samples, const 
   TACO_REQUIRE(B <= 65535, "wave_limit: B=%d rows are more than one grid holds", B);
   const int nch = lm_chunks(L), half = T / 2, H = 2 * W + half, hpitch = 2 * W + LM_HPITCH_PAD;
   hipStream_t s = as_stream(stream);
-  float* part = static_cast<float*>(workspace);
+  const LmWs w = lm_ws(workspace, B, L, W);
+  float* part = w.part;
   float* halo = nullptr;
   if (emit && out == wave) {
-    halo = part + (int64_t)B * nch * 4;
+    halo = w.halo;
     TACO_KLAUNCH(lm_halo_kernel, dim3(nch, B), dim3(LM_T), 0, s, wave, samples, halo, hpitch, H, nch, L);
   }
   const size_t lds = (size_t)(lm_lds_floats(LM_CHUNK + 2 * H) + (emit ? lm_lds_floats(LM_CHUNK + 4 * W) : 0)) * sizeof(float);

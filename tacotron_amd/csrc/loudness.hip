@@ -472,6 +472,28 @@ int64_t wl_pitch(int L) { return ((int64_t)L + 3) & ~(int64_t)3; }
 int wl_chunks(int L) { return cdiv(L, WL_CHUNK); }
 int wl_hops(int L, int sr) { return std::max(1, L / (sr / 10)); }
 
+// workspace of taco_wave_loudness: y (B, L rounded up to 4), the chunks' end states and carries (4 doubles each), the chunk maxima,
+// the hop sums.  Every offset is a multiple of 4 floats up to cmax: y and agg are read by 16 bytes.
+struct WlWs {
+  float* y;
+  double *agg, *carry;
+  float *cmax, *h;
+  int64_t bytes;
+};
+WlWs wl_ws(void* ws, int B, int L, int sr) {
+  WsCarver c(ws);
+  WlWs w;
+  const int64_t nch = wl_chunks(L);
+  w.y = c.take<float>(B * wl_pitch(L));
+  w.agg = c.take<double>(B * nch * 4);
+  w.carry = c.take<double>(B * nch * 4);
+  w.cmax = c.take<float>(B * nch);
+  w.h = c.take<float>((int64_t)B * wl_hops(L, sr));
+  c.take<float>(64);   // slack, for nothing: a base that is not 16-byte aligned is refused.  Callers size buffers with it.
+  w.bytes = c.bytes;
+  return w;
+}
+
 }  // namespace
 
 extern "C" int taco_k_weighting(int sr, double coef[10]) {
@@ -481,11 +503,9 @@ extern "C" int taco_k_weighting(int sr, double coef[10]) {
   return TACO_OK;
 }
 
-// workspace of taco_wave_loudness: y (B, L rounded up to 4), the chunks' end states and carries (4 doubles each), the chunk maxima,
-// the hop sums
 extern "C" int64_t taco_wave_loudness_workspace_bytes(int B, int L, int sr) {
   if (B <= 0 || L <= 0 || !wl_sr_ok(sr)) return TACO_EINVAL;
-  return ((int64_t)B * (wl_pitch(L) + 17 * (int64_t)wl_chunks(L) + wl_hops(L, sr)) + 64) * (int64_t)sizeof(float);
+  return wl_ws(nullptr, B, L, sr).bytes;
 }
 
 extern "C" int taco_wave_loudness(const float* wave, const int32_t* samples, int sr, float target_lufs, float ceiling, float* out,
@@ -507,11 +527,9 @@ extern "C" int taco_wave_loudness(const float* wave, const int32_t* samples, int
   WlCarryParams q;
   const WlParams p = wl_params(sr, q);
   const float z_abs = (float)pow(10.0, (-70.0 + 0.691) / 10.0);
-  float* y = static_cast<float*>(workspace);   // (the offsets below are multiples of 4 floats: y and agg are read by 16 bytes)
-  double* agg = reinterpret_cast<double*>(y + (int64_t)B * pitch);
-  double* carry = agg + (int64_t)B * nch * 4;
-  float* cmax = reinterpret_cast<float*>(carry + (int64_t)B * nch * 4);
-  float* h = cmax + (int64_t)B * nch;
+  const WlWs w = wl_ws(workspace, B, L, sr);
+  float *y = w.y, *cmax = w.cmax, *h = w.h;
+  double *agg = w.agg, *carry = w.carry;
   if (nch > 1) {
     TACO_KLAUNCH((wl_filter_kernel<true>), dim3(nch - 1, B), dim3(WL_T), 0, s, wave, samples, p, y, pitch, agg, nch, cmax, L);
     TACO_KLAUNCH(wl_carry_kernel, dim3(B), dim3(64), 0, s, agg, carry, samples, q, nch, L);

@@ -281,7 +281,21 @@ bool ms_buckets(int e_lo, int e_hi, int sub_bits, MsBuckets& q) {
   return true;
 }
 
-int64_t ms_part_off(int64_t n_items) { return (n_items * (int64_t)sizeof(MsRec) + 63) & ~(int64_t)63; }
+// workspace of taco_tensor_stats: one record per work item, then (on a 64-byte boundary) each item's nb bucket counts
+struct MsWs {
+  MsRec* recs;
+  uint32_t* part;
+  int64_t bytes;
+};
+MsWs ms_ws(void* ws, int n_items, int nb) {
+  WsCarver c(ws);
+  MsWs w;
+  w.recs = c.take<MsRec>(n_items);
+  w.part = c.take<uint32_t>((int64_t)n_items * nb, 64);
+  c.take<char>(64);   // slack, for nothing: a base that is not 8-byte aligned is refused.  Callers size buffers with it.
+  w.bytes = c.bytes;
+  return w;
+}
 
 }  // namespace
 
@@ -328,7 +342,7 @@ extern "C" int taco_tensor_stats_plan(const int64_t* segments, int n, int64_t ba
 
 extern "C" int64_t taco_tensor_stats_workspace_bytes(int n, int n_items, int nb) {
   if (n < 1 || n > TACO_STATS_MAX_SEGMENTS || n_items < 0 || nb < 3 || nb > TACO_STATS_MAX_BINS || !(nb & 1)) return TACO_EINVAL;
-  return ms_part_off(n_items) + (int64_t)n_items * nb * (int64_t)sizeof(uint32_t) + 64;
+  return ms_ws(nullptr, n_items, nb).bytes;
 }
 
 extern "C" int taco_tensor_stats(const float* base, const void* plan_dev, const void* plan_header, int n, int n_items, int e_lo,
@@ -354,8 +368,9 @@ extern "C" int taco_tensor_stats(const float* base, const void* plan_dev, const 
   const char* pd = static_cast<const char*>(plan_dev);
   const MsSeg* segs = reinterpret_cast<const MsSeg*>(pd + sizeof(MsHeader));
   const MsItem* items = reinterpret_cast<const MsItem*>(pd + sizeof(MsHeader) + n * sizeof(MsSeg));
-  MsRec* recs = static_cast<MsRec*>(workspace);
-  uint32_t* part = reinterpret_cast<uint32_t*>(static_cast<char*>(workspace) + ms_part_off(n_items));
+  const MsWs w = ms_ws(workspace, n_items, q.nb);
+  MsRec* recs = w.recs;
+  uint32_t* part = w.part;
   if (n_items > 0)
     TACO_KLAUNCH(stats_items_kernel, dim3(cdiv(n_items, MS_WAVES)), dim3(MS_T), MS_WAVES * q.nb * sizeof(uint32_t), s, base, segs,
                  items, n_items, q, recs, part);

@@ -194,18 +194,28 @@ __global__ __launch_bounds__(kPeChainThreads) void phase_chain_kernel(const uint
   }
 }
 
-bool pe_overlaps(const void* out, uint64_t out_bytes, const void* in, uint64_t in_bytes) {
-  const uint64_t o = reinterpret_cast<uintptr_t>(out), i = reinterpret_cast<uintptr_t>(in);
-  return o < i + in_bytes && i < o + out_bytes;
+// workspace of taco_phase_estimate: the advances (uint32) and the owners (int16), frame-major, 1025 entries per frame
+struct PeWs {
+  uint32_t* adv;
+  int16_t* own;
+  int64_t bytes;
+};
+PeWs pe_ws(void* ws, int B, int F) {
+  WsCarver c(ws);
+  PeWs w;
+  const int64_t n = (int64_t)B * F * kPeBins;
+  w.adv = c.take<uint32_t>(n);
+  w.own = c.take<int16_t>(n);
+  c.take<char>(0, 4);   // the size is a whole number of 4-byte words (B F odd: 2 bytes behind the owners)
+  w.bytes = c.bytes;
+  return w;
 }
-inline int64_t pe_adv_bytes(int B, int F) { return (int64_t)B * F * kPeBins * 4; }
-inline int64_t pe_own_bytes(int B, int F) { return ((int64_t)B * F * kPeBins * 2 + 3) & ~(int64_t)3; }
 
 }  // namespace
 
 extern "C" int64_t taco_phase_estimate_workspace_bytes(int B, int F) {
   if (B <= 0 || F <= 0) return TACO_EINVAL;
-  return pe_adv_bytes(B, F) + pe_own_bytes(B, F);
+  return pe_ws(nullptr, B, F).bytes;
 }
 
 extern "C" int taco_phase_estimate(const float* mag_t, const int32_t* frames, int frames_per_unit, float* phase0, void* workspace, int B,
@@ -217,7 +227,7 @@ extern "C" int taco_phase_estimate(const float* mag_t, const int32_t* frames, in
   TACO_REQUIRE(F > 0, "phase_estimate: F=%d must be positive", F);
   TACO_REQUIRE(frames_per_unit >= 1, "phase_estimate: frames_per_unit=%d must be >= 1", frames_per_unit);
   const uint64_t bytes = (uint64_t)B * F * kPeBins * 4;
-  TACO_REQUIRE(!pe_overlaps(phase0, bytes, mag_t, bytes), "phase_estimate: phase0 overlaps mag_t");
+  TACO_REQUIRE(!bytes_meet(phase0, bytes, mag_t, bytes), "phase_estimate: phase0 overlaps mag_t");
   const int ntile = cdiv(F, kPeTile);
   const int64_t blocks = (int64_t)B * ntile;
   TACO_REQUIRE(blocks <= 0x7fffffff, "phase_estimate: B=%d x F=%d needs more than 2^31 workgroups", B, F);
@@ -228,8 +238,9 @@ extern "C" int taco_phase_estimate(const float* mag_t, const int32_t* frames, in
     return TACO_ELAUNCH;
   }
   hipStream_t s = as_stream(stream);
-  uint32_t* ws_adv = static_cast<uint32_t*>(workspace);
-  int16_t* ws_own = reinterpret_cast<int16_t*>(static_cast<char*>(workspace) + pe_adv_bytes(B, F));
+  const PeWs w = pe_ws(workspace, B, F);
+  uint32_t* ws_adv = w.adv;
+  int16_t* ws_own = w.own;
   TACO_KLAUNCH(phase_owner_kernel, dim3((unsigned)blocks), dim3(kPeThreads), kPeTileLds, s, mag_t, frames, frames_per_unit, ws_adv, ws_own,
                F, ntile);
   TACO_KLAUNCH(phase_chain_kernel, dim3((unsigned)B), dim3(kPeChainThreads), kPeChainLds, s, ws_adv, ws_own, frames, frames_per_unit, phase0, F);

@@ -627,33 +627,44 @@ __global__ __launch_bounds__(WJ_T) void wj_pcm_kernel(const float* __restrict__ 
 
 }  // namespace
 
-// ---- C ABI (include/taco_hip.h): the Griffin-Lim entry points, taco_wave_finish and taco_wave_join, each workspace
-// size beside its float count
-static int64_t griffinlim_workspace_floats(int B, int F) {
-  return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (NFFT + (int64_t)HOP * (F - 1)) + 64;
-}
-
-static int64_t griffinlim_rows_workspace_floats(int B, int F) {   // one window sum-of-squares table per row (it depends on F_b)
-  return (int64_t)B * F * NBIN * 2 + (int64_t)B * F * WIN + (int64_t)B * (NFFT + (int64_t)HOP * (F - 1)) + 64;
-}
-
-// the rows layout (without its 64 floats of slack), then the previous spectrum, the two (B, F) partial-sum tables, ||M||^2 per row
-static int64_t griffinlim_fast_offset(int B, int F) { return griffinlim_rows_workspace_floats(B, F) - 64; }
-static int64_t griffinlim_fast_workspace_floats(int B, int F) {
-  return griffinlim_fast_offset(B, F) + (int64_t)B * F * NBIN * 2 + 2 * (int64_t)B * F + B + 64;
+// ---- C ABI (include/taco_hip.h): the Griffin-Lim entry points, taco_wave_finish and taco_wave_join, each behind the one layout
+// of its workspace
+// Griffin-Lim: the angles, the segments, the window sum-of-squares tables (wss_rows: 1 where one table serves the batch, B where
+// each row has its own, since it depends on F_b); fast adds the previous spectrum, the two (B, F) partial-sum tables and ||M||^2
+// per row.
+struct GlWs {
+  float *ang, *seg, *wss, *tprev, *red, *mpart, *msq;
+  int64_t bytes;
+};
+static GlWs gl_ws(void* ws, int B, int F, int wss_rows, bool fast) {
+  WsCarver c(ws);
+  GlWs w{};
+  const int64_t BF = (int64_t)B * F;
+  w.ang = c.take<float>(BF * NBIN * 2);
+  w.seg = c.take<float>(BF * WIN);
+  w.wss = c.take<float>(wss_rows * (NFFT + (int64_t)HOP * (F - 1)));
+  if (fast) {
+    w.tprev = c.take<float>(BF * NBIN * 2);
+    w.red = c.take<float>(BF);
+    w.mpart = c.take<float>(BF);
+    w.msq = c.take<float>(B);
+  }
+  c.take<float>(64);   // slack, for nothing: no array is aligned beyond the base.  Callers size buffers with it.
+  w.bytes = c.bytes;
+  return w;
 }
 
 // F >= 5: the centre (reflect) padding of n_fft / 2 = 1024 samples at hop 300 needs more than 1024 samples
 static bool griffinlim_shape_ok(int B, int F) { return B > 0 && F >= 5; }
 
 extern "C" int64_t taco_griffinlim_workspace_bytes(int B, int F) {
-  return griffinlim_shape_ok(B, F) ? griffinlim_workspace_floats(B, F) * (int64_t)sizeof(float) : TACO_EINVAL;
+  return griffinlim_shape_ok(B, F) ? gl_ws(nullptr, B, F, 1, false).bytes : TACO_EINVAL;
 }
 extern "C" int64_t taco_griffinlim_rows_workspace_bytes(int B, int F) {
-  return griffinlim_shape_ok(B, F) ? griffinlim_rows_workspace_floats(B, F) * (int64_t)sizeof(float) : TACO_EINVAL;
+  return griffinlim_shape_ok(B, F) ? gl_ws(nullptr, B, F, B, false).bytes : TACO_EINVAL;
 }
 extern "C" int64_t taco_griffinlim_fast_workspace_bytes(int B, int F) {
-  return griffinlim_shape_ok(B, F) ? griffinlim_fast_workspace_floats(B, F) * (int64_t)sizeof(float) : TACO_EINVAL;
+  return griffinlim_shape_ok(B, F) ? gl_ws(nullptr, B, F, B, true).bytes : TACO_EINVAL;
 }
 
 // What all three Griffin-Lim entry points require, in the order a caller sees the refusals.  `who`: the entry point's name in the
@@ -666,20 +677,16 @@ static int griffinlim_require(const char* who, bool pointers, int B, int F, int 
 }
 
 // the launches of all three entry points.  frames == nullptr: every row has F frames and one window table serves the batch.
-// alpha > 0: momentum rounds with the previous spectrum in `tprev`; conv != nullptr: the readout, (B, n_iter + 1), with its
-// scratch in `red` (2 B F + B floats).  alpha == 0 and conv == nullptr are the launches of taco_griffinlim / taco_griffinlim_rows.
+// alpha > 0: momentum rounds with the previous spectrum in w.tprev; conv != nullptr: the readout, (B, n_iter + 1), with its
+// scratch in w.red, w.mpart, w.msq.  alpha == 0 and conv == nullptr are the launches of taco_griffinlim / taco_griffinlim_rows.
 static int griffinlim_launches(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames, int per_unit,
-                               float* wave, float* work, int B, int F, int n_iter, hipStream_t s, float alpha = 0.f,
-                               float* conv = nullptr, float* tprev = nullptr, float* red = nullptr) {
-  float* ang = work;
-  float* seg = ang + (int64_t)B * F * NBIN * 2;
-  float* wss = seg + (int64_t)B * F * WIN;
+                               float* wave, const GlWs& w, int B, int F, int n_iter, hipStream_t s, float alpha = 0.f,
+                               float* conv = nullptr) {
+  float *ang = w.ang, *seg = w.seg, *wss = w.wss, *red = w.red, *mpart = w.mpart, *msq = w.msq;
   const int n = NFFT + HOP * (F - 1);
   const int64_t wss_pitch = frames ? n : 0;
   const bool mom = alpha > 0.f;
-  GlExtra x{mom ? tprev : nullptr, alpha, 0, 0, mag_t, red};
-  float* mpart = red ? red + (int64_t)B * F : nullptr;
-  float* msq = red ? mpart + (int64_t)B * F : nullptr;
+  GlExtra x{mom ? w.tprev : nullptr, alpha, 0, 0, mag_t, red};
   TACO_KLAUNCH(gl_wss_kernel, dim3((n + 255) / 256, frames ? B : 1), dim3(256), 0, s, wss, wss_pitch, F, frames, per_unit);
   const int64_t total = (int64_t)B * F * NBIN;
   TACO_KLAUNCH(gl_init_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, phase0, seed, ang, F,
@@ -713,7 +720,7 @@ static int griffinlim_launches(const float* mag_t, const float* phase0, uint64_t
 extern "C" int taco_griffinlim(const float* mag_t, const float* phase0, float* wave, void* workspace, int B, int F, int n_iter,
                                void* stream) {
   TACO_TRY(griffinlim_require("griffinlim", mag_t && phase0 && wave && workspace, B, F, n_iter, 1));
-  griffinlim_launches(mag_t, phase0, 0, nullptr, 1, wave, static_cast<float*>(workspace), B, F, n_iter, as_stream(stream));
+  griffinlim_launches(mag_t, phase0, 0, nullptr, 1, wave, gl_ws(workspace, B, F, 1, false), B, F, n_iter, as_stream(stream));
   TACO_LAUNCH_CHECK("griffinlim");
   return TACO_OK;
 }
@@ -721,7 +728,7 @@ extern "C" int taco_griffinlim(const float* mag_t, const float* phase0, float* w
 extern "C" int taco_griffinlim_rows(const float* mag_t, const float* phase0, uint64_t seed, const int32_t* frames,
                                     int frames_per_unit, float* wave, void* workspace, int B, int F, int n_iter, void* stream) {
   TACO_TRY(griffinlim_require("griffinlim_rows", mag_t && frames && wave && workspace, B, F, n_iter, frames_per_unit));
-  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, static_cast<float*>(workspace), B, F, n_iter,
+  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, gl_ws(workspace, B, F, B, false), B, F, n_iter,
                       as_stream(stream));
   TACO_LAUNCH_CHECK("griffinlim_rows");
   return TACO_OK;
@@ -732,24 +739,36 @@ extern "C" int taco_griffinlim_fast(const float* mag_t, const float* phase0, uin
                                     int n_iter, void* stream) {
   TACO_TRY(griffinlim_require("griffinlim_fast", mag_t && wave && workspace, B, F, n_iter, frames_per_unit, momentum));
   TACO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "griffinlim_fast: workspace is not 8-byte aligned");
-  float* work = static_cast<float*>(workspace);
-  float* tprev = work + griffinlim_fast_offset(B, F);
-  float* red = tprev + (int64_t)B * F * NBIN * 2;
-  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, work, B, F, n_iter, as_stream(stream), momentum, conv, tprev,
-                      red);
+  griffinlim_launches(mag_t, phase0, seed, frames, frames_per_unit, wave, gl_ws(workspace, B, F, B, true), B, F, n_iter,
+                      as_stream(stream), momentum, conv);
   TACO_LAUNCH_CHECK("griffinlim_fast");
   return TACO_OK;
 }
 
 // workspace of taco_wave_finish: y (B, L rounded up to 4), the chunk aggregates, the 512-sample maxima, the trim frames' mean
-// squares, and 64 floats of slack for the 16-byte alignment of y
+// squares
 static int64_t wf_pitch(int L) { return ((int64_t)L + 3) & ~(int64_t)3; }
 static int wf_chunks(int L) { return cdiv(L, WF_CHUNK); }
 static int wf_blocks(int L) { return cdiv(L, 512); }
 static int wf_frames(int L) { return 1 + L / TRIM_HOP; }
+struct WfWs {
+  float *y, *agg, *pm, *ms;
+  int64_t bytes;
+};
+static WfWs wf_ws(void* ws, int B, int L) {
+  WsCarver c(ws, 16);   // y is read by 16 bytes: the base is rounded up
+  WfWs w;
+  w.y = c.take<float>(B * wf_pitch(L));
+  w.agg = c.take<float>((int64_t)B * wf_chunks(L));
+  w.pm = c.take<float>((int64_t)B * wf_blocks(L));
+  w.ms = c.take<float>((int64_t)B * wf_frames(L));
+  c.take<float>(64);   // slack: the up to 15 bytes that rounding the base up costs
+  w.bytes = c.bytes;
+  return w;
+}
 extern "C" int64_t taco_wave_finish_workspace_bytes(int B, int L) {
   if (B <= 0 || L <= 0) return TACO_EINVAL;
-  return ((int64_t)B * (wf_pitch(L) + wf_chunks(L) + wf_blocks(L) + wf_frames(L)) + 64) * (int64_t)sizeof(float);
+  return wf_ws(nullptr, B, L).bytes;
 }
 
 extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float deemphasis, float trim_top_db, float* out,
@@ -762,10 +781,8 @@ extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float
   hipStream_t s = as_stream(stream);
   const int64_t pitch = wf_pitch(L);
   const int nch = wf_chunks(L), npm = wf_blocks(L), nms = wf_frames(L);
-  float* y = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-  float* agg = y + (int64_t)B * pitch;
-  float* pm = agg + (int64_t)B * nch;
-  float* ms = pm + (int64_t)B * npm;
+  const WfWs w = wf_ws(workspace, B, L);
+  float *y = w.y, *agg = w.agg, *pm = w.pm, *ms = w.ms;
   if (deemphasis != 0.f && nch > 1)
     TACO_KLAUNCH((wf_scan_kernel<true>), dim3(nch - 1, B), dim3(WF_T), 0, s, wave, samples, deemphasis, y, pitch, agg, nch, pm, npm, L);
   TACO_KLAUNCH((wf_scan_kernel<false>), dim3(nch, B), dim3(WF_T), 0, s, wave, samples, deemphasis, y, pitch, agg, nch, pm, npm, L);
@@ -778,12 +795,28 @@ extern "C" int taco_wave_finish(const float* wave, const int32_t* samples, float
 }
 
 // workspace of taco_wave_join: the joined fp32 rows (P, Lj rounded up to 4; used when out is NULL), the tile maxima, the device copies
-// of first and gap, and 64 bytes of slack for the 16-byte alignment of the rows
+// of first and gap
 static int64_t wj_pitch(int Lj) { return ((int64_t)Lj + 3) & ~(int64_t)3; }
 static int wj_tiles(int Lj) { return cdiv(cdiv((int64_t)Lj + 3, WJ_PER), WJ_T); }   // chunks of a row at its worst alignment
+struct WjWs {
+  float *rows, *tmax;
+  int32_t *first, *gap;
+  int64_t bytes;
+};
+static WjWs wj_ws(void* ws, int N, int P, int Lj) {
+  WsCarver c(ws, 16);   // the rows are written by 16 bytes: the base is rounded up
+  WjWs w;
+  w.rows = c.take<float>(P * wj_pitch(Lj));
+  w.tmax = c.take<float>((int64_t)P * wj_tiles(Lj));
+  w.first = c.take<int32_t>((int64_t)P + 1);
+  w.gap = c.take<int32_t>(N);
+  c.take<char>(64);   // slack: the up to 15 bytes that rounding the base up costs
+  w.bytes = c.bytes;
+  return w;
+}
 extern "C" int64_t taco_wave_join_workspace_bytes(int N, int P, int Lj) {
   if (N <= 0 || P <= 0 || Lj <= 0) return TACO_EINVAL;
-  return ((int64_t)P * (wj_pitch(Lj) + wj_tiles(Lj)) + (int64_t)P + 1 + N) * 4 + 64;
+  return wj_ws(nullptr, N, P, Lj).bytes;
 }
 
 extern "C" int taco_wave_join(const float* pieces, int64_t pitch, const int32_t* bounds, const int32_t* first, const int32_t* gap,
@@ -794,11 +827,8 @@ extern "C" int taco_wave_join(const float* pieces, int64_t pitch, const int32_t*
   TACO_REQUIRE(N > 0 && P > 0 && L > 0 && Lj > 0, "wave_join: N=%d P=%d L=%d Lj=%d", N, P, L, Lj);
   TACO_REQUIRE(pitch >= L, "wave_join: pitch %lld is below L=%d", (long long)pitch, L);
   TACO_REQUIRE(fade >= 0, "wave_join: fade %d is negative", fade);
-  if (out) {
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(pieces), p1 = p0 + (((uint64_t)N - 1) * (uint64_t)pitch + (uint64_t)L) * 4;
-    const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uint64_t)P * (uint64_t)Lj * 4;
-    TACO_REQUIRE(o1 <= p0 || p1 <= o0, "wave_join: out overlaps pieces");
-  }
+  TACO_REQUIRE(!out || !bytes_meet(out, (uint64_t)P * (uint64_t)Lj * 4, pieces, (((uint64_t)N - 1) * (uint64_t)pitch + (uint64_t)L) * 4),
+               "wave_join: out overlaps pieces");
   TACO_REQUIRE(first[0] == 0 && first[P] == N, "wave_join: first[0]=%d, first[P]=%d: they must be 0 and N=%d", first[0], first[P], N);
   for (int p = 0; p < P; ++p)
     TACO_REQUIRE(first[p] <= first[p + 1], "wave_join: first[%d]=%d is above first[%d]=%d", p, first[p], p + 1, first[p + 1]);
@@ -807,10 +837,9 @@ extern "C" int taco_wave_join(const float* pieces, int64_t pitch, const int32_t*
   TACO_REQUIRE((int64_t)P * ntile <= 0x7fffffff, "wave_join: P=%d prompts of %d tiles are more than one grid holds", P, ntile);
   hipStream_t s = as_stream(stream);
   const int64_t rpitch = wj_pitch(Lj);
-  float* rows = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 15) & ~(uintptr_t)15);
-  float* tmax = rows + (int64_t)P * rpitch;
-  int32_t* first_d = reinterpret_cast<int32_t*>(tmax + (int64_t)P * ntile);
-  int32_t* gap_d = first_d + P + 1;
+  const WjWs w = wj_ws(workspace, N, P, Lj);
+  float *rows = w.rows, *tmax = w.tmax;
+  int32_t *first_d = w.first, *gap_d = w.gap;
   TACO_TRY(taco_upload_async(first_d, first, ((size_t)P + 1) * sizeof(int32_t), s, "wave_join: first upload"));
   TACO_TRY(taco_upload_async(gap_d, gap, (size_t)N * sizeof(int32_t), s, "wave_join: gap upload"));
   float* dst = out ? out : rows;
